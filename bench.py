@@ -28,11 +28,6 @@ import time
 # Python thread that launches the next GPU leg (measured: a 5.6 ms leg read 15 ms right after a baseline)
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 os.environ.setdefault("GOMP_SPINCOUNT", "0")
-# HIP multiplexes a process's streams onto 4 hardware queues by default; this process creates more than a dozen
-# (one per training engine, the cosine job's side streams), and when the job's two chains land on the SAME queue
-# they serialise: 28.0 ms instead of 24.9 for the 350 k x 350 k top-100 job (measured in this file, both ways).
-# Read by the runtime when it initialises, i.e. before the first torch.cuda call below.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 import numpy as np
 
@@ -90,7 +85,36 @@ def alphas_for(n_steps, lr=1e-5, t0=0):
     return [adam_alpha(lr, t0 + i + 1) for i in range(n_steps)]
 
 
-def run_single(workload, steps, warmup, batch, use_graph=True, cpu_baseline=True, quiet=False):
+DUMP_USER_ROWS = 16_384        # user rows in the --dump-outputs sample (the whole S109M user table is 179 MB)
+DUMP_MAX_BYTES = 64 << 20
+HEAD_FIELDS = ("w", "b", "gamma", "beta", "mov_mean", "mov_var")
+
+
+def dump_outputs(eng, out_dir, seed=20260102):
+    """What the timed path hands its caller after its last step, as .npy files in `out_dir`: the anime table and its
+    Adam moments whole, the same for a fixed seeded sample of user rows (`user_rows`: their indices), the head
+    parameters (`head`: HEAD_FIELDS, `head_adam`: their Adam m and v) and the step's loss and MSE (`loss`)."""
+    import torch
+    nu = eng.n_user_rows
+    rows = np.sort(np.random.default_rng(seed).choice(nu, min(nu, DUMP_USER_ROWS), replace=False))
+    sel = torch.from_numpy(rows).to(eng.device)
+    rec = eng.read_state()
+    out = {"user_rows": rows.astype(np.float64)}
+    for name, T in (("table", eng.W), ("adam_m", eng.M), ("adam_v", eng.V)):
+        out["user_" + name] = T[:nu].index_select(0, sel).cpu().numpy()
+        out["anime_" + name] = T[nu:].cpu().numpy()
+    out["head"] = np.array([rec[k] for k in HEAD_FIELDS], np.float32)
+    out["head_adam"] = np.stack([rec["adam_m"], rec["adam_v"]]).astype(np.float32)
+    out["loss"] = np.array([rec["last_loss"], rec["last_mse"]], np.float32)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_single(workload, steps, warmup, batch, use_graph=True, cpu_baseline=True, quiet=False, dump_dir=None):
     import torch
     from anime_recommendations_amd.engine import TrainEngine
     n_users, n_anime = WORKLOADS[workload]
@@ -114,6 +138,8 @@ def run_single(workload, steps, warmup, batch, use_graph=True, cpu_baseline=True
     dt = time.perf_counter() - t0
     rec = eng.read_state()
     assert int(rec["step_fwd"]) == warmup + steps and np.isfinite(rec["last_loss"])
+    if dump_dir:        # before the instrumented pass below trains on
+        dump_outputs(eng, dump_dir)
 
     # instrumented pass: the SAME step sequence continued eagerly, every kernel stamping the constant-clock time of each
     # workgroup's first and last instruction (anirec_train_stage_ticks): a launch's duration is max(end) - min(start),
@@ -816,15 +842,21 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the secondary workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (one GPU only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 or args.gpus > 1 or os.environ.get("ANIREC_FORCE_DIST") == "1":
+        if args.dump_outputs:
+            ap.error("--dump-outputs is only supported on the one-GPU path")
         from anime_recommendations_amd import dist_bench
         return dist_bench.main(args)
 
     res = run_single(args.workload, args.steps, args.warmup, args.batch, use_graph=not args.no_graph,
-                     cpu_baseline=not args.no_cpu_baseline)
+                     cpu_baseline=not args.no_cpu_baseline, dump_dir=args.dump_outputs)
     n_users, n_anime = WORKLOADS[args.workload]
     line = {
         "metric": "training_ratings_per_sec", "value": res["value"], "unit": "ratings/s",

@@ -1,7 +1,7 @@
 """Copies the DATA fixtures the reference holds for the hot path into tests/golden/.
 
-Run in the build container only (reads /root/reference, which never travels):
-    python tests/golden/make_reference_fixtures.py
+Run against a checkout of the reference project (Dyrutter/anime_recommendations):
+    python tests/golden/make_reference_fixtures.py <reference checkout>
 
 * anime_nn_history.csv  (reference: figure_file/anime_nn_history.csv) — the Keras
   History CSV of the author's run; its ``lr`` column is the one numeric
@@ -12,13 +12,15 @@ Run in the build container only (reads /root/reference, which never travels):
 import csv
 import json
 import os
+import sys
 
-REF = "/root/reference/figure_file"
+REF = None                # the reference checkout (command line)
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
 def main():
-    with open(os.path.join(REF, "anime_nn_history.csv")) as f:
+    fig = os.path.join(REF, "figure_file")
+    with open(os.path.join(fig, "anime_nn_history.csv")) as f:
         rows = list(csv.reader(f))
     with open(os.path.join(OUT, "anime_nn_history.csv"), "w", newline="") as f:
         csv.writer(f).writerows(rows)
@@ -28,8 +30,8 @@ def main():
                          ("anime_similar_to_SilentMobius.csv", "Similarity"),
                          ("User_ID_153695_model_recs.csv", "Prediction")]:
         # the Möbius file name is stored NFD-normalised on disk: match by prefix
-        real = [n for n in os.listdir(REF) if n.startswith(name[:22])][0]
-        with open(os.path.join(REF, real), newline="") as f:
+        real = [n for n in os.listdir(fig) if n.startswith(name[:22])][0]
+        with open(os.path.join(fig, real), newline="") as f:
             r = list(csv.DictReader(f))
         fmt[name] = {"columns": list(r[0].keys()), "n_rows": len(r),
                      "value_column": valcol, "values": [float(x[valcol]) for x in r]}
@@ -41,9 +43,9 @@ def main():
     import re
     flags = {}
     for c in ("neural_network", "similar_anime", "similar_users", "model_recs", "preprocess"):
-        src = open("/root/reference/%s/%s.py" % (c, c)).read()
+        src = open(os.path.join(REF, c, c + ".py")).read()
         found = re.findall(r'add_argument\(\s*"--(\w+)",\s*type=([^,]+),', src)
-        ml = open("/root/reference/%s/MLproject" % c).read()
+        ml = open(os.path.join(REF, c, "MLproject")).read()
         params = re.findall(r"^      (\w+):\s*$", ml, flags=re.M)
         flags[c] = {"flags": [n for n, _ in found],
                     "bool_flags": [n for n, t in found if "strtobool" in t],
@@ -53,4 +55,5 @@ def main():
 
 
 if __name__ == "__main__":
+    REF = sys.argv[1]
     main()

@@ -1,6 +1,6 @@
-"""Golden vectors produced by the reference's OWN function bodies (build container only).
+"""Golden vectors produced by the reference's OWN function bodies (Dyrutter/anime_recommendations).
 
-    python tests/golden/make_reference_function_fixtures.py
+    python tests/golden/make_reference_function_fixtures.py <reference checkout>
 
 The reference's hot-path modules cannot be imported here (their first statements import wandb and
 tensorflow, which are absent), but many of their functions touch neither: they are plain
@@ -33,6 +33,7 @@ import logging
 import os
 import re
 import string
+import sys
 import types
 import unicodedata
 import warnings
@@ -40,7 +41,7 @@ import warnings
 import numpy as np
 import pandas as pd
 
-REF = "/root/reference"
+REF = None                # the reference checkout (command line)
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_fn")
 
 
@@ -301,4 +302,5 @@ def main():
 
 
 if __name__ == "__main__":
+    REF = sys.argv[1]
     main()
