@@ -19,10 +19,12 @@ CHUNK = 32
 ADAM_BLOCKS = 8192
 MAX_TOPK = 128
 MAX_SEG = 16
-ABI_VERSION = 4
+ABI_VERSION = 5
 TOPK_MAX_BATCHES = 64
 RCCL_ID_BYTES = 128
 LAZY_WINDOW = 8
+# anirec_train_desc.optimizer (ANIREC_OPT_*)
+OPT_ADAM, OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
 
 
 class AnirecError(RuntimeError):
@@ -61,7 +63,7 @@ class TrainDesc(C.Structure):
         ("state", C.c_void_p), ("user_idx", C.c_void_p), ("anime_idx", C.c_void_p),
         ("rating", C.c_void_p), ("sched", C.c_void_p), ("n_steps", C.c_int32), ("pad2", C.c_int32),
         ("packets", C.c_void_p), ("dense_grad", C.c_void_p), ("workspace", C.c_void_p),
-        ("workspace_bytes", C.c_size_t), ("lazy_state", C.c_void_p),
+        ("workspace_bytes", C.c_size_t), ("lazy_state", C.c_void_p), ("optimizer", C.c_int32),
     ]
 
 
@@ -111,6 +113,7 @@ PROTOTYPES = {
     "anirec_trainer_run": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "anirec_eval": (C.c_int, [_DP, _vp, _vp, _vp, _i32, _vp]),
     "anirec_adam_flat": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _vp]),
+    "anirec_opt_flat": (C.c_int, [_i32, _vp, _vp, _vp, _sz, _f32, _vp]),
     "anirec_selftest_lazy_math": (C.c_int, [C.c_uint64, _vp, _vp]),
     "anirec_gather_ratings": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "anirec_rownorm": (C.c_int, [_vp, _i32, _vp, _vp]),

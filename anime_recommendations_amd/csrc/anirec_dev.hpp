@@ -78,6 +78,40 @@ __device__ __forceinline__ void adam_elem(float &w, float &m, float &v, float g,
   w = w - (m * alpha) / (sqrtf(v) + kAdamEps);
 }
 
+// The one-slot Keras-2.12 optimisers (include/anirec.h, ANIREC_OPT_*), the same rules: `s` is the RMSprop velocity /
+// the Adagrad accumulator, `lr` the schedule's rate.  Keras takes tf.math.rsqrt; here it is the correctly rounded
+// 1/sqrtf, so that a NumPy restatement holds the kernels bitwise.
+constexpr float kRmsRho = 0.9f;
+constexpr float kRmsOneMinusRho = 0.1f;  // float32(1 - 0.9)
+__device__ __forceinline__ void sgd_elem(float &w, float g, float lr) {
+#pragma clang fp contract(off)
+  w = w - g * lr;
+}
+__device__ __forceinline__ void rmsprop_elem(float &w, float &s, float g, float lr) {
+#pragma clang fp contract(off)
+  s = kRmsRho * s + kRmsOneMinusRho * (g * g);
+  w = w - (lr * g) * (1.0f / sqrtf(s + kAdamEps));
+}
+__device__ __forceinline__ void adagrad_elem(float &w, float &s, float g, float lr) {
+#pragma clang fp contract(off)
+  s = s + g * g;
+  w = w - (lr * g) / sqrtf(s + kAdamEps);
+}
+// one element of any kind, chosen at compile time: m is Adam's first moment, v its second / the one slot
+template <int kOpt>
+__device__ __forceinline__ void opt_elem(float &w, float &m, float &v, float g, float rate) {
+  if constexpr (kOpt == ANIREC_OPT_ADAM) {
+    adam_elem(w, m, v, g, rate);
+  } else if constexpr (kOpt == ANIREC_OPT_SGD) {
+    sgd_elem(w, g, rate);
+  } else if constexpr (kOpt == ANIREC_OPT_RMSPROP) {
+    rmsprop_elem(w, v, g, rate);
+  } else {
+    static_assert(kOpt == ANIREC_OPT_ADAGRAD, "unknown optimiser kind");
+    adagrad_elem(w, v, g, rate);
+  }
+}
+
 // g_total = (g_sparse - s*w) + two_l2*w with every product and sum rounded once.
 __device__ __forceinline__ float grad_total(float gs, float s, float w, float two_l2) {
 #pragma clang fp contract(off)

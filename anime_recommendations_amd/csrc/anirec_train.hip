@@ -966,9 +966,10 @@ struct RowLoad {
   int rm;              // > 0: chunk list; 0: untouched
 };
 
-// issue every load of one row up front: W, M, V and — the row map word having been
-// prefetched one iteration earlier — the first chunk partial of a touched row
-template <bool kNT>
+// issue every load of one row up front: W and the slots the update rule keeps (Adam: M and V; RMSprop / Adagrad: V;
+// SGD: none) and — the row map word having been prefetched one iteration earlier — the first chunk partial of a
+// touched row
+template <bool kNT, int kOpt>
 __device__ __forceinline__ void row_issue(const AdamArgs &a, int par, int r, int l, int rm, RowLoad &x) {
   const size_t e = (size_t)r * kRowVec + l;
   x.rm = rm;
@@ -978,8 +979,10 @@ __device__ __forceinline__ void row_issue(const AdamArgs &a, int par, int r, int
   const float4 *Mp = reinterpret_cast<const float4 *>(a.M) + e;
   const float4 *Vp = reinterpret_cast<const float4 *>(a.V) + e;
   x.w = kNT ? ld_nt(Wp) : *Wp;
-  x.m = kNT ? ld_nt(Mp) : *Mp;
-  x.v = kNT ? ld_nt(Vp) : *Vp;
+  if (kOpt == ANIREC_OPT_ADAM) x.m = kNT ? ld_nt(Mp) : *Mp;
+  else x.m = x.p0;  // (zero: not read)
+  if (kOpt != ANIREC_OPT_SGD) x.v = kNT ? ld_nt(Vp) : *Vp;
+  else x.v = x.p0;
   if (a.dense != nullptr && r >= a.dense_lo) {
     const int dr = r - a.dense_lo;
     x.p0 = reinterpret_cast<const float4 *>(a.dense)[(size_t)dr * kRowVec + l];
@@ -992,8 +995,9 @@ __device__ __forceinline__ void row_issue(const AdamArgs &a, int par, int r, int
   }
 }
 
-// returns sum(W_new^2) of this lane's four elements; the row map word of a touched row is cleared
-template <bool kNT, int kB = 4>
+// returns sum(W_new^2) of this lane's four elements; the row map word of a touched row is cleared.  `alpha` is the
+// step's rate: Adam's bias-corrected alpha, or lr
+template <bool kNT, int kOpt, int kB = 4>
 __device__ __forceinline__ float row_finish(const AdamArgs &a, int par, int r, int l, float alpha, RowLoad &x) {
   int32_t *rmw = a.rowmap + (size_t)par * a.rows + r;
   const size_t e = (size_t)r * kRowVec + l;
@@ -1011,18 +1015,18 @@ __device__ __forceinline__ float row_finish(const AdamArgs &a, int par, int r, i
   g.y = grad_total(g.y, s, w.y, a.two_l2);
   g.z = grad_total(g.z, s, w.z, a.two_l2);
   g.w = grad_total(g.w, s, w.w, a.two_l2);
-  adam_elem(w.x, m.x, v.x, g.x, alpha);
-  adam_elem(w.y, m.y, v.y, g.y, alpha);
-  adam_elem(w.z, m.z, v.z, g.z, alpha);
-  adam_elem(w.w, m.w, v.w, g.w, alpha);
+  opt_elem<kOpt>(w.x, m.x, v.x, g.x, alpha);
+  opt_elem<kOpt>(w.y, m.y, v.y, g.y, alpha);
+  opt_elem<kOpt>(w.z, m.z, v.z, g.z, alpha);
+  opt_elem<kOpt>(w.w, m.w, v.w, g.w, alpha);
   if (kNT) {
     st_nt(reinterpret_cast<float4 *>(a.W) + e, w);
-    st_nt(reinterpret_cast<float4 *>(a.M) + e, m);
-    st_nt(reinterpret_cast<float4 *>(a.V) + e, v);
+    if (kOpt == ANIREC_OPT_ADAM) st_nt(reinterpret_cast<float4 *>(a.M) + e, m);
+    if (kOpt != ANIREC_OPT_SGD) st_nt(reinterpret_cast<float4 *>(a.V) + e, v);
   } else {
     reinterpret_cast<float4 *>(a.W)[e] = w;
-    reinterpret_cast<float4 *>(a.M)[e] = m;
-    reinterpret_cast<float4 *>(a.V)[e] = v;
+    if (kOpt == ANIREC_OPT_ADAM) reinterpret_cast<float4 *>(a.M)[e] = m;
+    if (kOpt != ANIREC_OPT_SGD) reinterpret_cast<float4 *>(a.V)[e] = v;
   }
   return w.x * w.x + w.y * w.y + w.z * w.z + w.w * w.w;
 }
@@ -1052,7 +1056,8 @@ __device__ __forceinline__ void block_sq_partials(float sq, float sqa, float *sc
 // kMode 2 (user-sharded multi-GPU step with lazy user rows): the anime table is updated densely every step, so its L2
 // sum is here; the user rows' sum is deferred — the step is accounted with the anime term only, its batch count goes
 // to `ring`, and k_lazy_reduce adds the user term of every step of the window at the flush.
-template <int kMode = 0>
+// kOpt: the update rule of the four scalars (their one slot, if any, is adam_v; the lazy modes are Adam's only).
+template <int kMode = 0, int kOpt = ANIREC_OPT_ADAM>
 __device__ __forceinline__ void finish_step(const AdamArgs &a, int par, float *scratch, float *ring = nullptr,
                                             int ring_slot = 0) {
   constexpr bool kLazy = kMode == 1;
@@ -1107,9 +1112,9 @@ __device__ __forceinline__ void finish_step(const AdamArgs &a, int par, float *s
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float mm = am[k], vv = av[k];
-      adam_elem(p4[k], mm, vv, g4[k], pub.alpha);
-      st->adam_m[k] = mm;
-      st->adam_v[k] = vv;
+      opt_elem<kOpt>(p4[k], mm, vv, g4[k], pub.alpha);
+      if (kOpt == ANIREC_OPT_ADAM) st->adam_m[k] = mm;
+      if (kOpt != ANIREC_OPT_SGD) st->adam_v[k] = vv;
     }
     st->w = p4[0];
     st->b = p4[1];
@@ -1144,8 +1149,8 @@ __device__ __forceinline__ void finish_step(const AdamArgs &a, int par, float *s
   }
 }
 
-// every row of [row_lo, n_rows); workgroup 0 finishes the step when parts & 4
-template <bool kNT>
+// every row of [row_lo, n_rows) under update rule kOpt (ANIREC_OPT_*); workgroup 0 finishes the step when parts & 4
+template <bool kNT, int kOpt>
 __device__ __forceinline__ void adam_body(const AdamArgs &a, int bid, int nblocks, float *scratch) {
   const int l = threadIdx.x & 31;
   const int nhw = nblocks * 8;
@@ -1163,20 +1168,20 @@ __device__ __forceinline__ void adam_body(const AdamArgs &a, int bid, int nblock
   for (; r + nhw < a.n_rows; r += 2 * nhw) {
     const int r1 = r + nhw;
     RowLoad x0, x1;
-    row_issue<kNT>(a, par, r, l, rm0, x0);
-    row_issue<kNT>(a, par, r1, l, rm1, x1);
+    row_issue<kNT, kOpt>(a, par, r, l, rm0, x0);
+    row_issue<kNT, kOpt>(a, par, r1, l, rm1, x1);
     const int rn0 = r + 2 * nhw, rn1 = r + 3 * nhw;
     rm0 = rn0 < a.n_rows ? rowmap[rn0] : 0;
     rm1 = rn1 < a.n_rows ? rowmap[rn1] : 0;
-    const float q0 = row_finish<kNT>(a, par, r, l, alpha, x0);
-    const float q1 = row_finish<kNT>(a, par, r1, l, alpha, x1);
+    const float q0 = row_finish<kNT, kOpt>(a, par, r, l, alpha, x0);
+    const float q1 = row_finish<kNT, kOpt>(a, par, r1, l, alpha, x1);
     if (r < a.n_user_rows) sq += q0; else sqa += q0;
     if (r1 < a.n_user_rows) sq += q1; else sqa += q1;
   }
   if (r < a.n_rows) {
     RowLoad x0;
-    row_issue<kNT>(a, par, r, l, rm0, x0);
-    const float q0 = row_finish<kNT>(a, par, r, l, alpha, x0);
+    row_issue<kNT, kOpt>(a, par, r, l, rm0, x0);
+    const float q0 = row_finish<kNT, kOpt>(a, par, r, l, alpha, x0);
     if (r < a.n_user_rows) sq += q0; else sqa += q0;
   }
   float *rp = a.regpart + (size_t)(par * 2) * ANIREC_ADAM_BLOCKS;
@@ -1184,9 +1189,9 @@ __device__ __forceinline__ void adam_body(const AdamArgs &a, int bid, int nblock
                     (a.parts & 2) ? rp + ANIREC_ADAM_BLOCKS + bid : nullptr);
   if (bid == 0 && (a.parts & 4)) {
     if (a.ring != nullptr)
-      finish_step<2>(a, par, scratch, a.ring, step - a.w0[0]);
+      finish_step<2, kOpt>(a, par, scratch, a.ring, step - a.w0[0]);
     else
-      finish_step<0>(a, par, scratch);
+      finish_step<0, kOpt>(a, par, scratch);
   }
 }
 
@@ -1194,7 +1199,16 @@ template <bool kNT>
 __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
   __shared__ float scratch[kHeadCols * 16];
   tick(a.ticks, 0);
-  adam_body<kNT>(a, blockIdx.x, gridDim.x, scratch);
+  adam_body<kNT, ANIREC_OPT_ADAM>(a, blockIdx.x, gridDim.x, scratch);
+  tick(a.ticks, 1);
+}
+
+// the same dense update under one of the one-slot rules (SGD: 8 B/element, RMSprop / Adagrad: 16 B/element)
+template <bool kNT, int kOpt>
+__global__ __launch_bounds__(256) void k_dense_opt(AdamArgs a) {
+  __shared__ float scratch[kHeadCols * 16];
+  tick(a.ticks, 0);
+  adam_body<kNT, kOpt>(a, blockIdx.x, gridDim.x, scratch);
   tick(a.ticks, 1);
 }
 
@@ -1812,6 +1826,18 @@ __global__ __launch_bounds__(256) void k_adam_flat(float *w, float *m, float *v,
   }
 }
 
+// flat one-slot update with an explicit gradient (anirec_opt_flat; the dense kernel's element rule)
+template <int kOpt>
+__global__ __launch_bounds__(256) void k_opt_flat(float *w, float *slot, const float *g, size_t n, float rate) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    float ww = w[i], mm = 0.f, vv = kOpt == ANIREC_OPT_SGD ? 0.f : slot[i];
+    opt_elem<kOpt>(ww, mm, vv, g[i], rate);
+    w[i] = ww;
+    if (kOpt != ANIREC_OPT_SGD) slot[i] = vv;
+  }
+}
+
 // Self-test of the lazy replay's short sequences (anirec_selftest_lazy_math; tests only).  Square root: EVERY float
 // of the range the sequence is used on, [2^-96, 2^96], against the compiler's correctly rounded sqrtf — 1.6 x 10^9
 // inputs, exhaustive.  Divide: `n_div` pseudo-random (numerator, denominator) pairs drawn over the ranges the
@@ -1966,6 +1992,13 @@ static inline bool lazy_users(const anirec_train_desc *d) {
   return d->lazy != 0 && d->lazy_state != nullptr && d->dense_mode == 1;
 }
 
+// the update rule: a known kind, and the lazy update (Adam's only) not asked for with another
+static int check_opt(const anirec_train_desc *d) {
+  if (d->optimizer < ANIREC_OPT_ADAM || d->optimizer > ANIREC_OPT_ADAGRAD) return ANIREC_EINVAL;
+  if (d->lazy != 0 && d->optimizer != ANIREC_OPT_ADAM) return ANIREC_EINVAL;
+  return ANIREC_OK;
+}
+
 static int check_desc(const anirec_train_desc *d) {
   if (!d || !d->W || !d->M || !d->V || !d->rowmap || !d->state || !d->workspace || !d->packets)
     return ANIREC_EINVAL;
@@ -1974,6 +2007,7 @@ static int check_desc(const anirec_train_desc *d) {
   if (d->n_seg < 1 || d->n_seg > ANIREC_MAX_SEG || d->my_seg < 0 || d->my_seg >= d->n_seg)
     return ANIREC_EINVAL;
   if (d->dense_mode < 0 || d->dense_mode > 2) return ANIREC_EINVAL;
+  if (check_opt(d)) return ANIREC_EINVAL;
   if (d->dense_mode) {
     if (!d->dense_grad || d->dense_rows < table_rows(d) - dense_lo_of(d)) return ANIREC_EINVAL;
     if (d->adam_row_lo < 0 || d->adam_row_hi < d->adam_row_lo || d->adam_row_hi > table_rows(d)) return ANIREC_EINVAL;
@@ -2235,10 +2269,25 @@ static int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStr
       a.w0 = w.sel + 1;
     }
   }
-  if (stream_nt(d))
-    hipLaunchKernelGGL((k_adam<true>), dim3(adam_grid(d)), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_adam<false>), dim3(adam_grid(d)), dim3(256), 0, s, a);
+  const bool nt = stream_nt(d);
+  const dim3 grid(adam_grid(d)), block(256);
+  switch (d->optimizer) {
+    case ANIREC_OPT_SGD:
+      if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_SGD>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((k_dense_opt<false, ANIREC_OPT_SGD>), grid, block, 0, s, a);
+      break;
+    case ANIREC_OPT_RMSPROP:
+      if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_RMSPROP>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((k_dense_opt<false, ANIREC_OPT_RMSPROP>), grid, block, 0, s, a);
+      break;
+    case ANIREC_OPT_ADAGRAD:
+      if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_ADAGRAD>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((k_dense_opt<false, ANIREC_OPT_ADAGRAD>), grid, block, 0, s, a);
+      break;
+    default:
+      if (nt) hipLaunchKernelGGL((k_adam<true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((k_adam<false>), grid, block, 0, s, a);
+  }
   if (int te = ticks_collect(w, 3, s)) return te;
   return (int)hipGetLastError();
 }
@@ -2946,7 +2995,7 @@ int anirec_trainer_run(anirec_trainer *t, int32_t first_step, int32_t n_steps, i
 
 int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32_t *anime_idx,
                 const float *rating, int32_t n, void *stream) {
-  if (!d || !d->W || !d->state || !user_idx || !anime_idx || !rating || n < 0)
+  if (!d || !d->W || !d->state || !user_idx || !anime_idx || !rating || n < 0 || check_opt(d))
     return ANIREC_EINVAL;
   if (n == 0) return ANIREC_OK;
   EvalArgs a;
@@ -2969,6 +3018,22 @@ int anirec_adam_flat(float *w, float *m, float *v, const float *g, size_t n, flo
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(k_adam_flat, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, m,
                      v, g, n, alpha);
+  return (int)hipGetLastError();
+}
+
+int anirec_opt_flat(int32_t kind, float *w, float *slot, const float *g, size_t n, float rate, void *stream) {
+  if (kind < ANIREC_OPT_SGD || kind > ANIREC_OPT_ADAGRAD || !w || !g || (kind != ANIREC_OPT_SGD && !slot))
+    return ANIREC_EINVAL;
+  if (n == 0) return ANIREC_OK;
+  size_t blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipStream_t s = (hipStream_t)stream;
+  if (kind == ANIREC_OPT_SGD)
+    hipLaunchKernelGGL(k_opt_flat<ANIREC_OPT_SGD>, dim3((unsigned)blocks), dim3(256), 0, s, w, slot, g, n, rate);
+  else if (kind == ANIREC_OPT_RMSPROP)
+    hipLaunchKernelGGL(k_opt_flat<ANIREC_OPT_RMSPROP>, dim3((unsigned)blocks), dim3(256), 0, s, w, slot, g, n, rate);
+  else
+    hipLaunchKernelGGL(k_opt_flat<ANIREC_OPT_ADAGRAD>, dim3((unsigned)blocks), dim3(256), 0, s, w, slot, g, n, rate);
   return (int)hipGetLastError();
 }
 

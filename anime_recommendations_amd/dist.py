@@ -47,7 +47,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, schedule
 
 MODES = ("sharded", "replicated", "replicated_rs")
 
@@ -107,7 +107,7 @@ class DistTrainEngine:
     """TrainEngine facade for G ranks (same interface as engine.TrainEngine for trainer.fit)."""
 
     def __init__(self, n_users, n_anime, batch_per_rank, l2=1e-4, arena_steps=64, device="cuda:0",
-                 engine_factory=None, mode=None, lazy=None):
+                 engine_factory=None, mode=None, lazy=None, optimizer="adam"):
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
@@ -139,6 +139,9 @@ class DistTrainEngine:
                 self.shard_rows = (rows + self.world - 1) // self.world
                 lo = min(rows, self.rank * self.shard_rows)
                 kw.update(row_pad=self.world, adam_rows=(lo, min(rows, lo + self.shard_rows)))
+        self.optimizer = schedule.resolve_optimizer(optimizer)
+        if self.optimizer != "adam":   # (Adam is every engine's default: a factory need not know the keyword)
+            kw["optimizer"] = self.optimizer
         self.eng = engine_factory(self.n_local, self.n_anime, max_batch=max_batch, l2=l2,
                                   arena_steps=arena_steps, device=device, n_seg=self.world,
                                   my_seg=self.rank, **kw)
@@ -227,15 +230,15 @@ class DistTrainEngine:
         return self.gather_user_table() if self.mode == "sharded" else self.eng.U
 
     def optimizer_state(self, iterations=0):
-        """Collective: the full-table Adam slots."""
+        """Collective: the full-table optimiser slots."""
         st = self.eng.optimizer_state(iterations)
         nl = self.n_local
         if self.mode == "sharded":
-            st["user_embedding/m"] = self.gather_user_table(self.eng.M[:nl]).cpu().numpy()
-            st["user_embedding/v"] = self.gather_user_table(self.eng.V[:nl]).cpu().numpy()
+            for key, t in self.eng.slot_tensors():
+                st["user_embedding/" + key] = self.gather_user_table(t[:nl]).cpu().numpy()
         elif self.mode == "replicated_rs" and self.world > 1:
-            # every rank only keeps the moments of its own row shard up to date
-            for key, t in (("m", self.eng.M), ("v", self.eng.V)):
+            # every rank only keeps the slots of its own row shard up to date
+            for key, t in self.eng.slot_tensors():
                 full = self._gather_row_shards(t)
                 st["user_embedding/" + key] = full[:nl].cpu().numpy()
                 st["anime_embedding/" + key] = full[nl:].cpu().numpy()

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import DIM, MAX_TOPK
+from .schedule import OPTIMIZERS, resolve_optimizer
 
 
 def _stream():
@@ -421,6 +422,15 @@ def adam_flat(w, m, v, g, alpha):
     lib = _lib.load()
     _lib.check(lib.anirec_adam_flat(_lib.ptr(w), _lib.ptr(m), _lib.ptr(v), _lib.ptr(g), w.numel(),
                                     float(np.float32(alpha)), _stream()), "anirec_adam_flat")
+
+
+def opt_flat(kind, w, slot, g, rate):
+    """In-place SGD / RMSprop / Adagrad update of flat fp32 tensors (``slot``: the RMSprop velocity / Adagrad
+    accumulator, None for SGD; ``rate``: lr), the dense train step's element rule."""
+    _need_gpu()
+    lib = _lib.load()
+    _lib.check(lib.anirec_opt_flat(OPTIMIZERS[resolve_optimizer(kind)], _lib.ptr(w), _lib.ptr(slot), _lib.ptr(g),
+                                   w.numel(), float(np.float32(rate)), _stream()), "anirec_opt_flat")
 
 
 def gather_ratings(user_idx, anime_idx, rating, perm):

@@ -1,8 +1,9 @@
-"""Learning-rate schedule and Adam step size of the training component (host logic).
+"""Learning-rate schedule and optimiser step sizes of the training component (host logic).
 
 Mirrors ``lrfn`` (reference neural_network/neural_network.py:109-125) driven by
-``LearningRateScheduler`` (:184-186), and the bias-corrected step size of the Keras-2.12
-Adam the reference compiles with (``optimizer='Adam'``, :104).
+``LearningRateScheduler`` (:184-186), the bias-corrected step size of the Keras-2.12
+Adam the reference compiles with by default (``optimizer='Adam'``, :104), and the name lookup
+``model.compile(optimizer=<name>)`` performs for the other optimisers the kernels implement.
 """
 from __future__ import annotations
 
@@ -10,6 +11,19 @@ import numpy as np
 
 ADAM_B1 = 0.9
 ADAM_B2 = 0.999
+
+# update rules of the HIP train step, by the name tf.keras.optimizers.get resolves (case-insensitively), with the
+# value of anirec_train_desc.optimizer (ANIREC_OPT_*); every one with Keras' default hyper-parameters
+OPTIMIZERS = {"adam": 0, "sgd": 1, "rmsprop": 2, "adagrad": 3}
+
+
+def resolve_optimizer(name):
+    """Canonical (lower-case) name of a Keras optimizer the kernels implement; ValueError for any other."""
+    key = str(name).lower()
+    if key not in OPTIMIZERS:
+        raise ValueError("optimizer %r is not supported by the HIP train step (supported: %s)"
+                         % (name, ", ".join(sorted(OPTIMIZERS))))
+    return key
 
 
 def lrfn(epoch, start_lr=1e-5, max_lr=5e-5, min_lr=1e-5, rampup_epochs=5, sustain_epochs=0,
@@ -41,3 +55,12 @@ def adam_alphas(lr, t_first, n):
     b1p = np.power(f(ADAM_B1), ts, dtype=f)
     b2p = np.power(f(ADAM_B2), ts, dtype=f)
     return (f(lr) * np.sqrt(f(1) - b2p, dtype=f) / (f(1) - b1p)).astype(f)
+
+
+def step_rates(kind, lr, t_first, n):
+    """The per-step rate of anirec_step.alpha for iterations t_first .. t_first+n-1 (fp32): Adam's bias-corrected
+    step size (``adam_alphas``), float32(lr) for SGD, RMSprop and Adagrad (no bias correction)."""
+    kind = resolve_optimizer(kind)
+    if kind == "adam":
+        return adam_alphas(lr, t_first, n)
+    return np.full(int(n), np.float32(lr), dtype=np.float32)

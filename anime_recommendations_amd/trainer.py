@@ -38,6 +38,7 @@ class FitConfig:
     verbose: int = 1
     use_graph: bool = True
     arena_steps: int = 64
+    optimizer: str = "adam"          # config.yaml model.optimizer: adam, sgd, rmsprop, adagrad (any case)
 
     def lr(self, epoch):
         return schedule.lrfn(epoch, self.start_lr, self.max_lr, self.min_lr, self.rampup_epochs,
@@ -56,6 +57,7 @@ class FitResult:
     best_epoch: int = -1
     stopped_epoch: int = -1
     optimizer: dict = field(default_factory=dict)
+    optimizer_name: str = "adam"     # whose slots ``optimizer`` holds (weights_io.save_model's optimizer_name)
     step_loop_seconds: list = field(default_factory=list)   # per epoch: wall time of the step loop alone (synchronised)
     epoch_seconds: list = field(default_factory=list)       # per epoch: shuffle + steps + metrics + validation + snapshot
 
@@ -96,12 +98,16 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     ``ingest.EncodedRatings`` whose columns already live in HBM); returns History + last and best weights."""
     if cfg.embedding_size != 128:
         raise ValueError("libanirec kernels are specialised for embedding_size 128 (config.yaml:63)")
+    kind = schedule.resolve_optimizer(cfg.optimizer)
     tr, te = table.split(cfg.test_size)
     n_train = tr.stop - tr.start
     if engine is None:
         from .engine import TrainEngine
         engine = TrainEngine(table.n_users, table.n_anime, max_batch=min(cfg.batch_size, n_train),
-                             l2=cfg.l2_reg_factor, arena_steps=cfg.arena_steps, device=device)
+                             l2=cfg.l2_reg_factor, arena_steps=cfg.arena_steps, device=device, optimizer=kind)
+    elif getattr(engine, "optimizer", "adam") != kind:
+        raise ValueError("the engine was built for optimizer %r, the config asks for %r"
+                         % (getattr(engine, "optimizer", "adam"), kind))
     dev = engine.device
     U0, A0, w0 = init_weights(table.n_users, table.n_anime, 128, cfg.seed)
     engine.set_head(w=w0)
@@ -132,7 +138,7 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
         lr = cfg.lr(epoch)
         gen.manual_seed(cfg.seed * 1_000_003 + epoch)
         perm = torch.randperm(n_train, generator=gen, device=dev)     # model.fit(shuffle=True)
-        alphas = schedule.adam_alphas(lr, t_global + 1, n_steps)
+        alphas = schedule.step_rates(kind, lr, t_global + 1, n_steps)
         if multi:
             import torch.distributed as dist
             if dist.is_initialized() and dist.get_world_size() > 1:
@@ -176,8 +182,8 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     rec = engine.read_state()
     res = FitResult(history=hist, U=engine.U.cpu().numpy().copy(), A=engine.A.cpu().numpy().copy(),
                     head=head_of(rec), best_epoch=best_epoch, stopped_epoch=stopped, step_loop_seconds=loop_s,
-                    epoch_seconds=epoch_s)
-    if hasattr(engine, "optimizer_state"):       # Adam m, v and the step count of the LAST epoch (model.save)
+                    epoch_seconds=epoch_s, optimizer_name=kind)
+    if hasattr(engine, "optimizer_state"):       # optimiser slots and the step count of the LAST epoch (model.save)
         res.optimizer = engine.optimizer_state(iterations=t_global)
     if best_w is not None:
         best_w = (best_w[0].cpu().numpy(), best_w[1].cpu().numpy(), best_w[2])

@@ -4,7 +4,8 @@ similar_anime.py:155,164) stored as safetensors (h5py/TensorFlow are not install
 SURVEY.md §8(f)-1 lists .h5 interop as a later row).
 
 Tensor names:  <ID_emb_name>/embeddings, <anime_emb_name>/embeddings, dense/kernel, dense/bias,
-batch_normalization/{gamma,beta,moving_mean,moving_variance}; optimiser slots under adam/.
+batch_normalization/{gamma,beta,moving_mean,moving_variance}; optimiser slots under <optimizer>/ — adam/ (m, v),
+rmsprop/ (velocity), adagrad/ (accumulator) or sgd/ (the step count alone).
 """
 from __future__ import annotations
 
@@ -14,10 +15,14 @@ import numpy as np
 from safetensors.numpy import load_file, save_file
 
 HEAD_KEYS = ("w", "b", "gamma", "beta", "mov_mean", "mov_var")
+OPTIMIZER_KINDS = ("adam", "sgd", "rmsprop", "adagrad")
 
 
 def save_model(path, U, A, head, user_ids=None, anime_ids=None, user_name="user_embedding",
-               anime_name="anime_embedding", optimizer=None, extra=None):
+               anime_name="anime_embedding", optimizer=None, extra=None, optimizer_name="adam"):
+    """``optimizer``: the slots of ``optimizer_name`` (TrainEngine.optimizer_state), stored under <optimizer_name>/."""
+    if optimizer_name not in OPTIMIZER_KINDS:
+        raise ValueError("optimizer_name must be one of %s (got %r)" % (OPTIMIZER_KINDS, optimizer_name))
     t = {
         user_name + "/embeddings": np.ascontiguousarray(U, np.float32),
         anime_name + "/embeddings": np.ascontiguousarray(A, np.float32),
@@ -33,7 +38,7 @@ def save_model(path, U, A, head, user_ids=None, anime_ids=None, user_name="user_
     if anime_ids is not None:
         t["index/anime_ids"] = np.ascontiguousarray(anime_ids, np.int64)
     for k, v in (optimizer or {}).items():
-        t["adam/" + k] = np.ascontiguousarray(v)
+        t[optimizer_name + "/" + k] = np.ascontiguousarray(v)
     meta = {"format": "anime_recommendations_amd/1", "user_layer": user_name, "anime_layer": anime_name}
     meta.update({k: json.dumps(v) for k, v in (extra or {}).items()})
     save_file(t, path, metadata=meta)
@@ -41,7 +46,8 @@ def save_model(path, U, A, head, user_ids=None, anime_ids=None, user_name="user_
 
 
 def load_model(path, user_name="user_embedding", anime_name="anime_embedding"):
-    """Returns dict(U, A, head, user_ids, anime_ids, optimizer)."""
+    """Returns dict(U, A, head, user_ids, anime_ids, optimizer, optimizer_name): the slots found under the first
+    optimiser prefix the file holds and that optimiser's name (None when it holds no slots)."""
     t = load_file(path)
     ukey, akey = user_name + "/embeddings", anime_name + "/embeddings"
     if ukey not in t or akey not in t:
@@ -50,6 +56,7 @@ def load_model(path, user_name="user_embedding", anime_name="anime_embedding"):
             "gamma": float(t["batch_normalization/gamma"][0]), "beta": float(t["batch_normalization/beta"][0]),
             "mov_mean": float(t["batch_normalization/moving_mean"][0]),
             "mov_var": float(t["batch_normalization/moving_variance"][0])}
+    kind = next((o for o in OPTIMIZER_KINDS if any(k.startswith(o + "/") for k in t)), None)
+    slots = {k[len(kind) + 1:]: v for k, v in t.items() if k.startswith(kind + "/")} if kind else {}
     return {"U": t[ukey], "A": t[akey], "head": head, "user_ids": t.get("index/user_ids"),
-            "anime_ids": t.get("index/anime_ids"),
-            "optimizer": {k[5:]: v for k, v in t.items() if k.startswith("adam/")}}
+            "anime_ids": t.get("index/anime_ids"), "optimizer": slots, "optimizer_name": kind}

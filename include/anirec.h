@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ANIREC_ABI_VERSION 4
+#define ANIREC_ABI_VERSION 5
 #define ANIREC_DIM 128          /* embedding width (floats) */
 #define ANIREC_MAX_BATCH 16384  /* ratings per rank per step handled by one sort workgroup */
 #define ANIREC_CHUNK 32         /* max gradient contributions summed by one half-wave */
@@ -61,8 +61,24 @@ int anirec_device_name(char *buf_host, size_t buf_len);
  *   -> sigmoid; binary_crossentropy + whole-table L2; Keras-2.12 Adam, dense update).
  * ------------------------------------------------------------------------- */
 
-/* One optimiser step of the schedule.  `alpha` is the bias-corrected Adam step size
- * lr*sqrt(1-b2^t)/(1-b1^t) for this step, computed on the host from lrfn(epoch)
+/* Update rule of the dense optimiser step (anirec_train_desc::optimizer): the Keras-2.12 optimisers with their
+ * default hyper-parameters that model.compile(optimizer=...) resolves by name (neural_network.py:102-104).  fp32,
+ * never contracted into FMA, g = chunk sums + 2*l2*W, lr = float32(lrfn(epoch)):
+ *   ADAM     m += (g-m)*0.1; v += (g*g-v)*0.001; w -= (m*alpha)/(sqrt(v)+1e-7)   slots m, v (init 0)
+ *   SGD      w -= g*lr                                                             (momentum 0; no slot)
+ *   RMSPROP  v = 0.9*v + 0.1*(g*g); w -= (lr*g)*(1/sqrt(v+1e-7))                  (rho 0.9, not centred; init 0)
+ *   ADAGRAD  v = v + g*g; w -= (lr*g)/sqrt(v+1e-7)                                  (accumulator, init 0.1)
+ * The one slot of RMSprop / Adagrad lives in V (and anirec_state.adam_v for the four head scalars); M and
+ * anirec_state.adam_m are not touched by them.  sqrt and divide are correctly rounded. */
+enum {
+  ANIREC_OPT_ADAM = 0,
+  ANIREC_OPT_SGD = 1,
+  ANIREC_OPT_RMSPROP = 2,
+  ANIREC_OPT_ADAGRAD = 3
+};
+
+/* One optimiser step of the schedule.  `alpha` is Adam's bias-corrected step size
+ * lr*sqrt(1-b2^t)/(1-b1^t) for this step, or `lr` for the other kinds, computed on the host from lrfn(epoch)
  * (neural_network.py:109-125) so host and oracle agree bit-for-bit. */
 typedef struct anirec_step {
   int32_t start; /* first rating of this rank's part of the batch in the epoch arrays */
@@ -137,6 +153,8 @@ typedef struct anirec_train_desc {
   void *workspace;      /* >= anirec_train_workspace_bytes(max_batch, arena_steps); zero before first use */
   size_t workspace_bytes;
   void *lazy_state;     /* lazy != 0: anirec_train_lazy_bytes(rows) bytes, zero before first use; else NULL */
+  int32_t optimizer;    /* ANIREC_OPT_*: the update rule of the adam stage.  The lazy update exists for ADAM only: a
+                           descriptor with lazy != 0 and another kind is rejected (ANIREC_EINVAL) by every call */
 } anirec_train_desc;
 
 /* floats in one head packet: c[pcap], t[pcap], 4 ints {count,0,0,0}; pcap = max_batch rounded
@@ -261,6 +279,10 @@ int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32
  * (Keras-2.12 Adam dense branch; bit-exact to the oracle given the same g). */
 int anirec_adam_flat(float *w, float *m, float *v, const float *g, size_t n, float alpha,
                      void *stream);
+/* The same for the one-slot kinds (ANIREC_OPT_SGD / _RMSPROP / _ADAGRAD; the header's formulas, bit-exact given the
+ * same g): `slot` is the RMSprop / Adagrad slot (ignored by SGD, may be NULL there), `rate` is lr.  ADAM has two
+ * slots: ANIREC_EINVAL, use anirec_adam_flat. */
+int anirec_opt_flat(int32_t kind, float *w, float *slot, const float *g, size_t n, float rate, void *stream);
 
 /* Self-test of the lazy update's short arithmetic sequences (tests only; no reference call site — it guards the claim
  * that the lazy dense Adam performs the dense kernel's fp32 operations): the correctly rounded square root the replay

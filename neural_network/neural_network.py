@@ -28,9 +28,10 @@ logger = C.setup_logging("neural_network")
 
 
 def go(args):
-    from anime_recommendations_amd import data, ingest, trainer, weights_io
+    from anime_recommendations_amd import data, ingest, schedule, trainer, weights_io
     # the graph is fixed by the kernels: reject configurations they do not implement
-    for flag, want in (("model_loss", "binary_crossentropy"), ("optimizer", "adam"),
+    optimizer = schedule.resolve_optimizer(args.optimizer)     # Keras name, any case: adam, sgd, rmsprop, adagrad
+    for flag, want in (("model_loss", "binary_crossentropy"),
                        ("activation_function", "sigmoid"), ("kernel_initializer", "he_normal")):
         if str(getattr(args, flag)).lower() != want:
             raise ValueError("--%s %r is not supported by the HIP train step (only %r)"
@@ -57,7 +58,7 @@ def go(args):
         start_lr=float(args.start_lr), min_lr=float(args.min_lr), max_lr=float(args.max_lr),
         rampup_epochs=int(args.rampup_epochs), sustain_epochs=int(args.sustain_epochs),
         exp_decay=float(args.exp_decay), monitor=args.checkpoint_metric, mode=args.mode,
-        verbose=int(args.verbose), seed=int(os.environ.get("ANIREC_SEED", "0")))
+        verbose=int(args.verbose), seed=int(os.environ.get("ANIREC_SEED", "0")), optimizer=optimizer)
     # >1 rank: ratings sharded by user over RCCL.  The reference's TPU branch (neural_network.py:173-178)
     # computes batch_size * replicas and max_lr * replicas but never uses them: model.fit gets
     # args.batch_size (:213) and lrfn reads args.max_lr (:113), so the GLOBAL batch and the schedule are
@@ -83,7 +84,7 @@ def go(args):
                                  "ANIREC_WEAK_SCALING=1 for batch_size ratings PER rank)" % (cfg.batch_size, world))
             per_rank = cfg.batch_size // world
         engine = DistTrainEngine(table.n_users, table.n_anime, min(per_rank, max(1, n_train // world)),
-                                 l2=cfg.l2_reg_factor, device="cuda:%d" % local)
+                                 l2=cfg.l2_reg_factor, device="cuda:%d" % local, optimizer=optimizer)
         if rank != 0:
             cfg.verbose = 0
     res = trainer.fit(table, cfg, engine=engine, log=lambda s: (print(s), logger.info(s)))
@@ -102,6 +103,7 @@ def go(args):
     if args.save_model:
         weights_io.save_model(mpath, res.U, res.A, res.head, table.user_ids, table.anime_ids,
                               args.ID_emb_name, args.anime_emb_name, optimizer=res.optimizer,
+                              optimizer_name=res.optimizer_name,
                               extra={"best_epoch": res.best_epoch, "stopped_epoch": res.stopped_epoch})
     hist = trainer.history_frame(res.history)
     with open("history.json", "w") as f:
