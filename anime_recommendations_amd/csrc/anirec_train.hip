@@ -2203,11 +2203,11 @@ static int launch_bwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t 
   return e;
 }
 
-// Grid of every table-streaming launch of a descriptor (init, rest, full, parts): a function of the table
-// size only, so the same regpart entries are rewritten each step.  Two rows per half-wave at least, so the
-// two-rows-in-flight pipeline has something to overlap on small (cache-resident) tables.
-static inline int adam_grid(const anirec_train_desc *d) {
-  const long long rows = (long long)table_rows(d);
+// Grid of a launch that streams `rows` table rows (the dense updates and the L2 init: the whole table; the lazy flush:
+// the lazily updated rows): a function of the row count only, so the same regpart / partial slots are rewritten each
+// launch.  Two rows per half-wave at least, so the two-rows-in-flight pipeline has something to overlap on small
+// (cache-resident) tables.
+static inline int stream_grid(long long rows) {
   long long b = (rows + 15) / 16;
   if (b < 64) b = 64;
   if (b > ANIREC_ADAM_BLOCKS) b = ANIREC_ADAM_BLOCKS;
@@ -2270,7 +2270,7 @@ static int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStr
     }
   }
   const bool nt = stream_nt(d);
-  const dim3 grid(adam_grid(d)), block(256);
+  const dim3 grid(stream_grid(table_rows(d))), block(256);
   switch (d->optimizer) {
     case ANIREC_OPT_SGD:
       if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_SGD>), grid, block, 0, s, a);
@@ -2290,10 +2290,6 @@ static int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStr
   }
   if (int te = ticks_collect(w, 3, s)) return te;
   return (int)hipGetLastError();
-}
-
-static int launch_adam(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
-  return launch_adam_full(d, w, s, 0);
 }
 
 // ---- lazy dense Adam: host side ----
@@ -2332,16 +2328,8 @@ static LazyArgs lazy_args(const anirec_train_desc *d, const TrainWs &w, int tick
 static inline int lazy_chunk_grid(const anirec_train_desc *d, const TrainWs &w) {
   return ((lazy_users(d) ? 1 : 2) * w.capC + 7) / 8;
 }
-// grid of the flush: a function of the lazily updated row count only (the same partial slots every window)
-static inline int flush_grid(const anirec_train_desc *d) {
-  const long long rows = lazy_users(d) ? d->n_user_rows : table_rows(d);
-  long long b = (rows + 15) / 16;
-  if (b < 64) b = 64;
-  if (b > ANIREC_ADAM_BLOCKS) b = ANIREC_ADAM_BLOCKS;
-  return (int)b;
-}
 
-// every row is current as of `first_step` (each anirec_trainer_run call ends flushed): open a window there
+// every row is current as of `first_step` (every run ends flushed): open a window there
 static int lazy_begin(const anirec_train_desc *d, const TrainWs &w, int first_step, hipStream_t s) {
   const LazyState z = lazy_carve(d->lazy_state, table_rows(d));
   ANIREC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)z.row_step, first_step, (size_t)table_rows(d), s));
@@ -2350,9 +2338,39 @@ static int lazy_begin(const anirec_train_desc *d, const TrainWs &w, int first_st
   return ANIREC_OK;
 }
 
-// catchup_first: the rows of this step's batch are not known to be current (first step of a run or of a prepared
-// block): a stand-alone catch-up launch.  fuse_next: the NEXT step's batch is already in the prep arena, so this step's
-// head launch also catches its rows up and the next step needs no catch-up launch.
+// What a step of the lazy update launches besides fwd, head, bwd and the sparse step; ignored by the dense update.
+struct StepFlags {
+  bool catchup_first;  // the rows of this step's batch are not known to be current: a stand-alone catch-up launch
+  bool fuse_next;      // the NEXT step's batch is in the prep arena: this step's launches also catch its rows up
+  bool flush_after;    // a flush follows the step: its window is full, or the run ends with it
+};
+
+// The cadence of a run of steps walked in prepared blocks (a block: steps whose batches are all in the prep arena).
+// Only a block's first step needs a catch-up launch of its own, every step but a block's last fuses the next batch's
+// catch-up, and a flush follows every kLzWin steps and the last step of the run, so a run ends flushed.
+struct Walk {
+  int run_left = 0;              // steps of the run still to come
+  int blk_len = 0, blk_pos = 0;  // the prepared block the next step belongs to
+  int open = 0;                  // steps taken since the last flush
+  void begin(int n_steps) {
+    run_left = n_steps;
+    blk_len = blk_pos = open = 0;
+  }
+  void block(int n_steps) {
+    blk_len = n_steps;
+    blk_pos = 0;
+  }
+  bool in_block() const { return run_left > 0 && blk_pos < blk_len; }
+  StepFlags peek() const { return {blk_pos == 0, blk_pos + 1 < blk_len, open + 1 == kLzWin || run_left == 1}; }
+  StepFlags next() {  // the flags of the next step, which is taken
+    const StepFlags f = peek();
+    open = f.flush_after ? 0 : open + 1;
+    if (run_left > 0) --run_left;
+    if (blk_pos < blk_len) ++blk_pos;
+    return f;
+  }
+};
+
 static int launch_lazy_catchup(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   hipLaunchKernelGGL(k_lazy_catchup, dim3(lazy_chunk_grid(d, w)), dim3(256), 0, s, lazy_args(d, w, 4));
   if (int e = ticks_collect(w, 4, s)) return e;
@@ -2373,18 +2391,9 @@ static int launch_lazy_adam(const anirec_train_desc *d, const TrainWs &w, hipStr
   return (int)hipGetLastError();
 }
 
-static int lazy_step(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool catchup_first, bool fuse_next) {
-  int e;
-  if (catchup_first && (e = launch_lazy_catchup(d, w, s))) return e;
-  if ((e = launch_fwd(d, w, s))) return e;
-  if ((e = launch_head(d, w, s, fuse_next))) return e;
-  if ((e = launch_bwd_only(d, w, s, true))) return e;
-  return launch_lazy_adam(d, w, s, fuse_next);
-}
-
 static int lazy_flush(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   LazyArgs a = lazy_args(d, w, 6);
-  const int grid = flush_grid(d);
+  const int grid = stream_grid(a.lazy_rows);
   // the grid's share of each table (a function of the table sizes only: the same partial slots every window)
   a.split = grid;
   if (a.tables == 2) {
@@ -2401,6 +2410,107 @@ static int lazy_flush(const anirec_train_desc *d, const TrainWs &w, hipStream_t 
   hipLaunchKernelGGL(k_lazy_reduce, dim3(1), dim3(1024), 0, s, lazy_args(d, w, 7));
   if (int te = ticks_collect(w, 7, s)) return te;
   return (int)hipGetLastError();
+}
+
+static int launch_prep(const anirec_train_desc *d, const TrainWs &w, int first_step, int n_steps,
+                       bool relative_to_cursor, hipStream_t s) {
+  PrepArgs a;
+  a.user_idx = d->user_idx;
+  a.anime_idx = d->anime_idx;
+  a.sched = d->sched;
+  a.first_step = first_step;
+  a.cursor = relative_to_cursor ? d->state : nullptr;
+  a.n_steps_total = d->n_steps;
+  a.n_user_rows = d->n_user_rows;
+  a.n_anime_rows = d->n_anime_rows;
+  a.cap = w.cap;
+  a.capC = w.capC;
+  a.arena_steps = w.arena_steps;
+  a.arena = w.arena;
+  a.slot_bytes = w.slot_bytes;
+  hipLaunchKernelGGL(k_prep, dim3(2 * n_steps), dim3(kSortThreads), 0, s, a);
+  return (int)hipGetLastError();
+}
+
+// The part of a handle (anirec_trainer, anirec_dist_stepper) the block scheduler works on.
+struct RunHandle {
+  anirec_train_desc d;
+  TrainWs ws;
+  hipGraphExec_t exec = nullptr;  // the captured block of graph_steps steps
+  int graph_steps = 0;            // < 0: a capture failed, the handle runs eagerly from then on
+};
+
+// Runs steps [first_step, first_step + n_steps) of h's descriptor, `step(stream, flags)` enqueuing the launches of one
+// step.  With use_graph a block of G = min(32, arena_steps / 2) steps is captured once per handle and replayed: a
+// replay starts with the prep of the G steps AFTER it (relative to the device cursor), so no host work falls between
+// replays; the arena holds 2G steps.  The steps left over run eagerly, in arena-sized blocks prepared from the host —
+// except after a replay, which has prepared them already.  A failed capture returns ANIREC_ECAPTURE with nothing of
+// the run enqueued.
+template <class Step>
+static int run_blocks(RunHandle *h, hipStream_t s, int first_step, int n_steps, bool use_graph, Step step) {
+  const anirec_train_desc *d = &h->d;
+  int G = d->arena_steps / 2;
+  if (G > 32) G = 32;
+  // (stamped steps run eagerly)
+  const bool graph = use_graph && s != nullptr && G >= 4 && n_steps >= G && !g_ticks_on && h->graph_steps >= 0;
+  if (graph && !h->exec) {
+    hipGraph_t g = nullptr;
+    int e = ANIREC_ECAPTURE;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
+      e = launch_prep(d, h->ws, G, G, true, s);  // steps cursor+G .. cursor+2G
+      Walk walk;  // a run of G steps in one block of G: a replay leaves the tables up to date
+      walk.begin(G);
+      walk.block(G);
+      for (int i = 0; i < G && !e; ++i) e = step(s, walk.next());
+      if (hipStreamEndCapture(s, &g) != hipSuccess || !g) e = ANIREC_ECAPTURE;
+    }
+    if (!e && hipGraphInstantiate(&h->exec, g, nullptr, nullptr, 0) != hipSuccess) e = ANIREC_ECAPTURE;
+    if (g) (void)hipGraphDestroy(g);
+    if (e) {
+      h->exec = nullptr;
+      (void)hipGetLastError();
+      return ANIREC_ECAPTURE;
+    }
+    h->graph_steps = G;
+  }
+  if (n_steps > 0 && (lazy_on(d) || lazy_users(d))) {
+    const int e = lazy_begin(d, h->ws, first_step, s);
+    if (e) return e;
+  }
+  int done = 0;
+  if (graph) {
+    const int e = launch_prep(d, h->ws, first_step, G, false, s);  // the first block; later ones by the graph
+    if (e) return e;
+    for (; n_steps - done >= G; done += G) ANIREC_HIP_CHECK(hipGraphLaunch(h->exec, s));
+  }
+  Walk walk;
+  walk.begin(n_steps - done);
+  while (done < n_steps) {
+    int blk = n_steps - done;
+    if (!graph) {  // (after replays the last one has prepared the tail)
+      if (blk > d->arena_steps) blk = d->arena_steps;
+      const int e = launch_prep(d, h->ws, first_step + done, blk, false, s);
+      if (e) return e;
+    }
+    walk.block(blk);
+    for (int i = 0; i < blk; ++i)
+      if (const int e = step(s, walk.next())) return e;
+    done += blk;
+  }
+  return ANIREC_OK;
+}
+
+// one step on one GPU: the dense update, or the lazy one with the launches its flags ask for
+static int train_step(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, StepFlags f) {
+  const bool lazy = lazy_on(d);
+  int e;
+  if (lazy && f.catchup_first && (e = launch_lazy_catchup(d, w, s))) return e;
+  if ((e = launch_fwd(d, w, s))) return e;
+  if ((e = launch_head(d, w, s, lazy && f.fuse_next))) return e;
+  if ((e = launch_bwd_only(d, w, s, lazy))) return e;
+  if (!lazy) return launch_adam_full(d, w, s, 0);
+  if ((e = launch_lazy_adam(d, w, s, f.fuse_next))) return e;
+  return f.flush_after ? lazy_flush(d, w, s) : ANIREC_OK;
 }
 
 }  // namespace anirec
@@ -2436,29 +2546,9 @@ int anirec_train_init_reg(const anirec_train_desc *d, void *stream) {
     lo = d->adam_row_lo;
     hi = d->adam_row_hi;
   }
-  hipLaunchKernelGGL(k_reg_init, dim3(adam_grid(d)), dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
+  hipLaunchKernelGGL(k_reg_init, dim3(stream_grid(table_rows(d))), dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
   ANIREC_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_sum_regpart, dim3(1), dim3(1024), 0, s, d->state, w.regpart);
-  return (int)hipGetLastError();
-}
-
-static int launch_prep(const anirec_train_desc *d, const TrainWs &w, int first_step, int n_steps,
-                       bool relative_to_cursor, hipStream_t s) {
-  PrepArgs a;
-  a.user_idx = d->user_idx;
-  a.anime_idx = d->anime_idx;
-  a.sched = d->sched;
-  a.first_step = first_step;
-  a.cursor = relative_to_cursor ? d->state : nullptr;
-  a.n_steps_total = d->n_steps;
-  a.n_user_rows = d->n_user_rows;
-  a.n_anime_rows = d->n_anime_rows;
-  a.cap = w.cap;
-  a.capC = w.capC;
-  a.arena_steps = w.arena_steps;
-  a.arena = w.arena;
-  a.slot_bytes = w.slot_bytes;
-  hipLaunchKernelGGL(k_prep, dim3(2 * n_steps), dim3(kSortThreads), 0, s, a);
   return (int)hipGetLastError();
 }
 
@@ -2498,7 +2588,7 @@ int anirec_train_bwd(const anirec_train_desc *d, void *stream) {
 int anirec_train_adam(const anirec_train_desc *d, void *stream) {
   int rc = check_desc(d);
   if (rc) return rc;
-  return launch_adam(d, carve(d->workspace, d->max_batch, d->arena_steps), (hipStream_t)stream);
+  return launch_adam_full(d, carve(d->workspace, d->max_batch, d->arena_steps), (hipStream_t)stream, 0);
 }
 
 // Measurement hook (bench.py).  While armed, every training kernel launched through this library stamps the
@@ -2531,21 +2621,18 @@ int anirec_train_adam_part(const anirec_train_desc *d, int32_t which, void *stre
   TrainWs w = carve(d->workspace, d->max_batch, d->arena_steps);
   hipStream_t s = (hipStream_t)stream;
   if ((which != 1 && which != 2) || d->dense_mode != 1) return ANIREC_EINVAL;
+  // lazy user rows are only kept current by the run's cadence (anirec_dist_stepper_begin / _block): a part on its own
+  // would update rows that are steps behind, or account into a window that was never opened
+  if (lazy_users(d)) return ANIREC_EINVAL;
   return launch_adam_full(d, w, s, which);
 }
 
 // ---- multi-GPU step halves (one C call each; the caller issues the two collectives between them) ----------
-struct anirec_dist_stepper {
-  anirec_train_desc d;
-  TrainWs ws;
-  hipStream_t side;
-  hipEvent_t fork, join;
-  hipGraphExec_t exec;  // anirec_dist_run(use_graph): a captured block of steps, collectives included
-  int graph_steps;
-  // lazy user rows (desc.lazy, dense_mode 1): where the step-by-step callers are in their run / prepared block
-  int run_left;  // steps of the current run still to come (anirec_dist_stepper_begin)
-  int blk_len, blk_pos;  // the prepared block the next step belongs to (anirec_dist_stepper_block)
-  int lz_open;   // steps taken since the last flush
+// (the graph of anirec_dist_run holds a block of steps, collectives included)
+struct anirec_dist_stepper : RunHandle {
+  hipStream_t side = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  Walk walk;  // lazy user rows: where the step-by-step callers are in their run and prepared block
 };
 
 int anirec_dist_stepper_create(const anirec_train_desc *d, anirec_dist_stepper **out) {
@@ -2557,11 +2644,6 @@ int anirec_dist_stepper_create(const anirec_train_desc *d, anirec_dist_stepper *
   if (!h) return ANIREC_EINVAL;
   h->d = *d;
   h->ws = carve(d->workspace, d->max_batch, d->arena_steps);
-  h->side = nullptr;
-  h->fork = h->join = nullptr;
-  h->exec = nullptr;
-  h->graph_steps = 0;
-  h->run_left = h->blk_len = h->blk_pos = h->lz_open = 0;
   if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&h->join, hipEventDisableTiming) != hipSuccess) {
@@ -2630,43 +2712,33 @@ static int dist_back(anirec_dist_stepper *h, hipStream_t s, bool flush_after) {
 // otherwise: a run that is never told where it ends would leave the tables behind); without, they are no-ops.
 int anirec_dist_stepper_begin(anirec_dist_stepper *h, int32_t first_step, int32_t n_steps, void *stream) {
   if (!h || first_step < 0 || n_steps < 0 || first_step + n_steps > h->d.n_steps) return ANIREC_EINVAL;
-  h->run_left = n_steps;
-  h->blk_len = h->blk_pos = h->lz_open = 0;
+  h->walk.begin(n_steps);
   if (lazy_users(&h->d) && n_steps > 0) return lazy_begin(&h->d, h->ws, first_step, (hipStream_t)stream);
   return ANIREC_OK;
 }
 
 int anirec_dist_stepper_block(anirec_dist_stepper *h, int32_t n_steps) {
   if (!h || n_steps < 0 || n_steps > h->d.arena_steps) return ANIREC_EINVAL;
-  h->blk_len = n_steps;
-  h->blk_pos = 0;
+  h->walk.block(n_steps);
   return ANIREC_OK;
 }
 
+// (the walk advances at the back of a step: front and mid look at the step it is at)
+static bool outside_walk(const anirec_dist_stepper *h) { return lazy_users(&h->d) && !h->walk.in_block(); }
+
 int anirec_dist_step_front(anirec_dist_stepper *h, void *stream) {
-  if (!h) return ANIREC_EINVAL;
-  if (lazy_users(&h->d) && (h->run_left <= 0 || h->blk_pos >= h->blk_len)) return ANIREC_EINVAL;
-  return dist_front(h, (hipStream_t)stream, h->blk_pos == 0);
+  if (!h || outside_walk(h)) return ANIREC_EINVAL;
+  return dist_front(h, (hipStream_t)stream, h->walk.peek().catchup_first);
 }
 
 int anirec_dist_step_mid(anirec_dist_stepper *h, void *stream) {
-  if (!h) return ANIREC_EINVAL;
-  if (lazy_users(&h->d) && (h->run_left <= 0 || h->blk_pos >= h->blk_len)) return ANIREC_EINVAL;
-  return dist_mid(h, (hipStream_t)stream, h->blk_pos + 1 < h->blk_len);
+  if (!h || outside_walk(h)) return ANIREC_EINVAL;
+  return dist_mid(h, (hipStream_t)stream, h->walk.peek().fuse_next);
 }
 
 int anirec_dist_step_back(anirec_dist_stepper *h, void *stream) {
-  if (!h) return ANIREC_EINVAL;
-  bool flush = false;
-  if (lazy_users(&h->d)) {
-    if (h->run_left <= 0 || h->blk_pos >= h->blk_len) return ANIREC_EINVAL;
-    flush = ++h->lz_open == kLzWin || h->run_left == 1;
-    if (flush) h->lz_open = 0;
-  }
-  const int e = dist_back(h, (hipStream_t)stream, flush);
-  if (h->run_left > 0) --h->run_left;
-  if (h->blk_pos < h->blk_len) ++h->blk_pos;
-  return e;
+  if (!h || outside_walk(h)) return ANIREC_EINVAL;
+  return dist_back(h, (hipStream_t)stream, h->walk.next().flush_after);
 }
 
 // ---- multi-GPU: the whole loop in the library, RCCL called from here -----------------------------------------
@@ -2771,15 +2843,14 @@ static inline bool row_sharded(const anirec_train_desc *d) {
   return d->dense_mode == 2 && (d->adam_row_lo | d->adam_row_hi) != 0;
 }
 
-static int dist_one_step(anirec_dist_stepper *h, anirec_dist_comm *c, hipStream_t s, bool catchup_first, bool fuse_next,
-                         bool flush_after) {
+static int dist_one_step(anirec_dist_stepper *h, anirec_dist_comm *c, hipStream_t s, StepFlags f) {
   const anirec_train_desc *d = &h->d;
   int e;
-  if ((e = dist_front(h, s, catchup_first))) return e;
+  if ((e = dist_front(h, s, f.catchup_first))) return e;
   // BatchNorm sees the global batch: every rank's (c, t, count, mean, M2) packet, gathered in place
   const size_t pf = anirec_packet_floats(d->max_batch);
   ANIREC_RCCL_CHECK(g_rccl.AllGather(d->packets + pf * (size_t)c->rank, d->packets, pf, ncclFloat, c->comm, s));
-  if ((e = dist_mid(h, s, fuse_next))) return e;
+  if ((e = dist_mid(h, s, f.fuse_next))) return e;
   float *g = d->dense_grad;
   const size_t nd = (size_t)d->dense_rows;
   if (row_sharded(d)) {
@@ -2793,7 +2864,7 @@ static int dist_one_step(anirec_dist_stepper *h, anirec_dist_comm *c, hipStream_
   } else {
     ANIREC_RCCL_CHECK(g_rccl.AllReduce(g, g, nd * (kDim + 1), ncclFloat, ncclSum, c->comm, s));
   }
-  if ((e = dist_back(h, s, flush_after))) return e;
+  if ((e = dist_back(h, s, f.flush_after))) return e;
   if (row_sharded(d)) {  // every rank updated its row shard: collect the updated rows of W (padded to whole shards)
     const size_t sr = nd / (size_t)c->world;
     ANIREC_RCCL_CHECK(g_rccl.AllGather(d->W + (size_t)c->rank * sr * kDim, d->W, sr * kDim, ncclFloat, c->comm, s));
@@ -2801,10 +2872,8 @@ static int dist_one_step(anirec_dist_stepper *h, anirec_dist_comm *c, hipStream_
   return ANIREC_OK;
 }
 
-// use_graph: blocks of G = min(32, arena_steps / 2) steps — their RCCL collectives and the side-stream fork / join
-// included — are captured once and replayed, the first node of a replay preparing the G steps after it (as the
-// one-GPU trainer does); every rank replays in lockstep.  If the capture or the instantiation fails the loop falls
-// back to eager launches for good (decided before anything of the block has been enqueued).
+// use_graph: the blocks run_blocks captures hold their RCCL collectives and the side-stream fork / join too; every rank
+// replays in lockstep.  If the capture or the instantiation fails the loop falls back to eager launches for good.
 int anirec_dist_run(anirec_dist_stepper *h, anirec_dist_comm *c, int32_t first_step, int32_t n_steps, int32_t use_graph,
                     void *stream) {
   if (!h || !c || n_steps < 0 || first_step < 0 || first_step + n_steps > h->d.n_steps) return ANIREC_EINVAL;
@@ -2812,73 +2881,17 @@ int anirec_dist_run(anirec_dist_stepper *h, anirec_dist_comm *c, int32_t first_s
   if (c->world != h->d.n_seg || c->rank != h->d.my_seg) return ANIREC_EINVAL;
   if (!h->d.user_idx || !h->d.anime_idx || !h->d.rating || !h->d.sched || !h->d.dense_grad) return ANIREC_EINVAL;
   if (row_sharded(&h->d) && h->d.dense_rows % c->world) return ANIREC_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  int G = h->d.arena_steps / 2;
-  if (G > 32) G = 32;
-  int done = 0;
-  bool graph = use_graph && s != nullptr && G >= 4 && n_steps >= G && !g_ticks_on && h->graph_steps >= 0;
-  if (graph && !h->exec) {
-    hipGraph_t g = nullptr;
-    int e = ANIREC_ECAPTURE;
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
-      e = launch_prep(&h->d, h->ws, G, G, true, s);  // steps cursor+G .. cursor+2G
-      // lazy user rows: as in the one-GPU capture — only the block's first step needs a catch-up launch of its own,
-      // a flush every kLzWin steps and at the end of the block (a replay leaves the tables up to date)
-      for (int i = 0; i < G && !e; ++i)
-        e = dist_one_step(h, c, s, i == 0, i + 1 < G, (i + 1) % kLzWin == 0 || i + 1 == G);
-      if (hipStreamEndCapture(s, &g) != hipSuccess || !g) e = e ? e : ANIREC_ECAPTURE;
-    }
-    if (!e && hipGraphInstantiate(&h->exec, g, nullptr, nullptr, 0) != hipSuccess) {
-      h->exec = nullptr;
-      e = ANIREC_ECAPTURE;
-    }
-    if (g) (void)hipGraphDestroy(g);
-    if (e) {
-      (void)hipGetLastError();
-      h->graph_steps = -1;  // never again: eager from here on
-      graph = false;
-    } else {
-      h->graph_steps = G;
-    }
+  const auto step = [h, c](hipStream_t s, StepFlags f) { return dist_one_step(h, c, s, f); };
+  int e = run_blocks(h, (hipStream_t)stream, first_step, n_steps, use_graph != 0, step);
+  if (e == ANIREC_ECAPTURE) {
+    h->graph_steps = -1;
+    e = run_blocks(h, (hipStream_t)stream, first_step, n_steps, false, step);
   }
-  if (lazy_users(&h->d) && n_steps > 0) {  // every row is current at first_step: a lazy window opens there
-    const int e = lazy_begin(&h->d, h->ws, first_step, s);
-    if (e) return e;
-  }
-  if (graph) {
-    int e = launch_prep(&h->d, h->ws, first_step, G, false, s);  // the first block; later ones by the graph
-    if (e) return e;
-    while (n_steps - done >= G) {
-      ANIREC_HIP_CHECK(hipGraphLaunch(h->exec, s));
-      done += G;
-    }
-  }
-  int open = 0;  // lazy user rows: steps since the last flush (eager part)
-  while (done < n_steps) {
-    int blk = n_steps - done;
-    if (!(graph && done > 0)) {  // no replay before: prepare arena-sized blocks from the host
-      if (blk > h->d.arena_steps) blk = h->d.arena_steps;
-      int e = launch_prep(&h->d, h->ws, first_step + done, blk, false, s);
-      if (e) return e;
-    }
-    for (int i = 0; i < blk; ++i) {
-      const bool flush = ++open == kLzWin || (i + 1 == blk && done + blk >= n_steps);
-      if (flush) open = 0;
-      int e = dist_one_step(h, c, s, i == 0, i + 1 < blk, flush);
-      if (e) return e;
-    }
-    done += blk;
-  }
-  return ANIREC_OK;
+  return e;
 }
 
 // ---- one GPU: the whole loop ------------------------------------------------------------------------------
-struct anirec_trainer {
-  anirec_train_desc d;
-  TrainWs ws;
-  hipGraphExec_t exec;
-  int graph_steps;
-};
+struct anirec_trainer : RunHandle {};
 
 int anirec_trainer_create(const anirec_train_desc *d, anirec_trainer **out) {
   if (!out) return ANIREC_EINVAL;
@@ -2889,8 +2902,6 @@ int anirec_trainer_create(const anirec_train_desc *d, anirec_trainer **out) {
   if (!t) return ANIREC_EINVAL;
   t->d = *d;
   t->ws = carve(d->workspace, d->max_batch, d->arena_steps);
-  t->exec = nullptr;
-  t->graph_steps = 0;
   *out = t;
   return ANIREC_OK;
 }
@@ -2902,95 +2913,13 @@ int anirec_trainer_destroy(anirec_trainer *t) {
   return ANIREC_OK;
 }
 
-static int front_of_step(anirec_trainer *t, hipStream_t s) {
-  int e;
-  if ((e = launch_fwd(&t->d, t->ws, s))) return e;
-  if ((e = launch_head(&t->d, t->ws, s))) return e;
-  return launch_bwd_only(&t->d, t->ws, s);
-}
-
-static int one_step(anirec_trainer *t, hipStream_t s, bool catchup_first = true, bool fuse_next = false) {
-  if (lazy_on(&t->d)) return lazy_step(&t->d, t->ws, s, catchup_first, fuse_next);
-  int e;
-  if ((e = front_of_step(t, s))) return e;
-  return launch_adam(&t->d, t->ws, s);
-}
-
-// Runs steps [first_step, first_step + n_steps); first_step must equal the device cursor
-// (state->step_fwd).  The batch prep (sort + chunk tables) is driven from here: with use_graph a
-// captured graph of G steps starts with the prep of the G steps AFTER it (relative to the device
-// cursor), so a replay needs no host work between blocks; the arena holds 2G steps.
+// Runs steps [first_step, first_step + n_steps); first_step must equal the device cursor (state->step_fwd).
 int anirec_trainer_run(anirec_trainer *t, int32_t first_step, int32_t n_steps, int32_t use_graph,
                        void *stream) {
   if (!t || n_steps < 0 || first_step < 0 || first_step + n_steps > t->d.n_steps) return ANIREC_EINVAL;
   if (!t->d.user_idx || !t->d.anime_idx || !t->d.rating || !t->d.sched) return ANIREC_EINVAL;
-  if (n_steps == 0) return ANIREC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  int G = t->d.arena_steps / 2;
-  if (G > 32) G = 32;
-  int done = 0;
-  const bool graph = use_graph && s != nullptr && G >= 4 && n_steps >= G && !g_ticks_on;  // (stamped steps run eagerly)
-  const bool lazy = lazy_on(&t->d);
-  if (lazy) {
-    const int e = lazy_begin(&t->d, t->ws, first_step, s);
-    if (e) return e;
-  }
-  int open = 0;  // lazy: steps since the last flush (eager part)
-  if (graph) {
-    if (!t->exec || t->graph_steps != G) {
-      if (t->exec) (void)hipGraphExecDestroy(t->exec);
-      t->exec = nullptr;
-      hipGraph_t g = nullptr;
-      if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess)
-        return ANIREC_ECAPTURE;
-      const bool lazy = lazy_on(&t->d);
-      int e = launch_prep(&t->d, t->ws, G, G, true, s);  // steps cursor+G .. cursor+2G
-      for (int i = 0; i < G && !e; ++i) {
-        // lazy: the batches of the whole block (and of the next one) are in the arena: every sparse launch but the
-        // last also catches the next batch's rows up; only the block's first step needs a catch-up launch of its own
-        e = one_step(t, s, i == 0, i + 1 < G);
-        // lazy: a flush every kLzWin steps and at the end of the block (a replay leaves the tables up to date)
-        if (!e && lazy && ((i + 1) % kLzWin == 0 || i + 1 == G)) e = lazy_flush(&t->d, t->ws, s);
-      }
-      hipError_t ce = hipStreamEndCapture(s, &g);
-      if (e || ce != hipSuccess || !g) {
-        if (g) (void)hipGraphDestroy(g);
-        return e ? e : ANIREC_ECAPTURE;
-      }
-      hipError_t ie = hipGraphInstantiate(&t->exec, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      if (ie != hipSuccess) {
-        t->exec = nullptr;
-        return ANIREC_ECAPTURE;
-      }
-      t->graph_steps = G;
-    }
-    int e = launch_prep(&t->d, t->ws, first_step, G, false, s);  // the first block; later ones by the graph
-    if (e) return e;
-    while (n_steps - done >= G) {
-      ANIREC_HIP_CHECK(hipGraphLaunch(t->exec, s));
-      done += G;
-    }
-    // the last replay already prepared steps [first_step+done, first_step+done+G): the tail is covered
-  }
-  while (done < n_steps) {
-    int blk = n_steps - done;
-    if (!(graph && done > 0)) {  // no replay before: prepare arena-sized blocks from the host
-      if (blk > t->d.arena_steps) blk = t->d.arena_steps;
-      int e = launch_prep(&t->d, t->ws, first_step + done, blk, false, s);
-      if (e) return e;
-    }
-    for (int i = 0; i < blk; ++i) {
-      int e = one_step(t, s, i == 0, i + 1 < blk);  // (within a prepared block the next batch's tables exist)
-      if (e) return e;
-      if (lazy && (++open == kLzWin || (i + 1 == blk && done + blk >= n_steps))) {
-        if ((e = lazy_flush(&t->d, t->ws, s))) return e;
-        open = 0;
-      }
-    }
-    done += blk;
-  }
-  return ANIREC_OK;
+  return run_blocks(t, (hipStream_t)stream, first_step, n_steps, use_graph != 0,
+                    [t](hipStream_t s, StepFlags f) { return train_step(&t->d, t->ws, s, f); });
 }
 
 int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32_t *anime_idx,

@@ -103,6 +103,20 @@ def partition_epoch_replicated(user, anime, rating, perm, global_batch, rank, wo
             starts, counts, gcounts)
 
 
+def prepared_blocks(eng, first_step, n_steps):
+    """The stepper protocol of a run driven step by step: declares the run (lazy user rows: a window opens there, the
+    run's last step flushes), then prepares and declares arena-sized blocks, yielding each block's size once its steps
+    may be taken."""
+    eng.stepper_begin(first_step, n_steps)
+    done = 0
+    while done < n_steps:
+        blk = min(eng.arena_steps, n_steps - done)
+        eng.prep(first_step + done, blk)
+        eng.stepper_block(blk)
+        yield blk
+        done += blk
+
+
 class DistTrainEngine:
     """TrainEngine facade for G ranks (same interface as engine.TrainEngine for trainer.fit)."""
 
@@ -353,16 +367,10 @@ class DistTrainEngine:
                                              e._sp()), "anirec_dist_run")
             self.cursor = first_step + n_steps
             return n_steps
-        done = 0
         with torch.cuda.stream(e.stream) if self.device.type == "cuda" else _null_ctx():
-            e.stepper_begin(first_step, n_steps)       # (lazy user rows: a window opens here, the last step flushes)
-            while done < n_steps:
-                blk = min(e.arena_steps, n_steps - done)
-                e.prep(first_step + done, blk)
-                e.stepper_block(blk)
+            for blk in prepared_blocks(e, first_step, n_steps):
                 for _ in range(blk):
                     self.step()
-                done += blk
         self.cursor = first_step + n_steps
         return n_steps
 

@@ -118,7 +118,7 @@ def _train_leg(mode, data, tables, n_users, n_anime, B, K, W, inst, rank, world,
     instrumented pass with HIP events on the engine's stream around each step half and collective."""
     import torch
     import torch.distributed as dist
-    from .dist import DistTrainEngine
+    from .dist import DistTrainEngine, prepared_blocks
     from . import schedule
     ui, ai, t = data
     U, A = tables
@@ -159,14 +159,9 @@ def _train_leg(mode, data, tables, n_users, n_anime, B, K, W, inst, rank, world,
         e1.record(e.stream)
         evs[name].append((e0, e1))
 
-    done = 0
     if eng.loop:
         with torch.cuda.stream(e.stream):
-            e.stepper_begin(W + K, inst)
-            while done < inst:
-                blk = min(e.arena_steps, inst - done)
-                e.prep(W + K + done, blk)
-                e.stepper_block(blk)
+            for blk in prepared_blocks(e, W + K, inst):
                 for _ in range(blk):
                     timed("front", e.step_front)
                     timed("gather", eng._all_gather_packets)
@@ -175,7 +170,6 @@ def _train_leg(mode, data, tables, n_users, n_anime, B, K, W, inst, rank, world,
                     timed("back", e.step_back)
                     if mode == "replicated_rs":
                         timed("allgather_w", eng._all_gather_rows)
-                done += blk
     eng.synchronize()
     torch.cuda.synchronize()
     kern_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in evs.items() if v}

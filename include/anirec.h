@@ -197,7 +197,8 @@ int anirec_train_stage_ticks(const anirec_train_desc *d, int32_t enable, float *
                              void *stream);
 
 /* adam as two launches (dense_mode 1): which == 1 updates the user rows (may run while the anime gradient is
- * still in the all-reduce), which == 2 the anime rows and finishes the step. */
+ * still in the all-reduce), which == 2 the anime rows and finishes the step.  ANIREC_EINVAL with lazy user rows
+ * (below), before anything is launched: their update is only kept by the stepper's run and block protocol. */
 int anirec_train_adam_part(const anirec_train_desc *d, int32_t which, void *stream);
 
 /* Multi-GPU step as three C calls and two collectives (dense_mode 1 or 2; the stepper owns a side stream):

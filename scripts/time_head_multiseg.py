@@ -10,7 +10,8 @@ for nseg in (1, 2, 4, 8):
     cap = min(16384, int(B + 6 * np.sqrt(B) + 16)) if nseg > 1 else B
     ui, ai, t = bench.synth_ratings(n_users, n_anime, 4 * B, dev)
     U, A = bench.init_tables(n_users, n_anime, dev)
-    eng = TrainEngine(n_users, n_anime, max_batch=cap, arena_steps=8, n_seg=nseg, my_seg=0, anime_dense=nseg > 1)
+    eng = TrainEngine(n_users, n_anime, max_batch=cap, arena_steps=8, n_seg=nseg, my_seg=0,
+                      dense_mode=1 if nseg > 1 else 0, lazy=False)
     eng.set_head(w=1.2); eng.set_weights(U, A)
     eng.set_epoch(ui, ai, t, np.arange(4) * B, np.full(4, B), schedule.adam_alphas(1e-5, 1, 4))
     eng.prep(0, 4); eng.fwd(); eng.synchronize()

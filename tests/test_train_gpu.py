@@ -400,6 +400,43 @@ def test_lazy_adam_is_bitwise_the_dense_update(use_graph):
     d.close(); z.close()
 
 
+def test_adam_parts_are_refused_with_lazy_user_rows():
+    """The two-launch adam of the user-sharded step (anirec_train_adam_part) is refused on a descriptor with lazy user
+    rows — those rows are only kept current by the stepper's run / block protocol — before anything is launched; the
+    same engine without the lazy update takes both parts."""
+    from anime_recommendations_amd import _lib
+    from anime_recommendations_amd.engine import TrainEngine
+    n_u, n_a, B = 4000, 300, 500
+    U, A, ui, ai, t = _problem(23, n_u, n_a, 2 * B)
+    starts, counts, alphas = _schedule(len(ui), B, 1e-5)
+    for lazy in (True, False):
+        eng = TrainEngine(n_u, n_a, max_batch=B, arena_steps=4, n_seg=2, my_seg=0, dense_mode=1, lazy=lazy)
+        assert eng.lazy == lazy
+        eng.set_head(w=1.2)
+        eng.set_weights(U, A)
+        eng.set_epoch(ui, ai, t, starts, counts, alphas, counts)
+        eng.prep(0, 1)
+        eng.fwd(); eng.head(); eng.bwd()
+        eng.synchronize()
+        W0, M0, V0, r0 = (eng.W.cpu().numpy().copy(), eng.M.cpu().numpy().copy(), eng.V.cpu().numpy().copy(),
+                          eng.read_state())
+        for part in (eng.adam_users, eng.adam_anime_finish):
+            if lazy:
+                with pytest.raises(_lib.AnirecError):
+                    part()
+            else:
+                part()
+        eng.synchronize()
+        W, M, V, rec = eng.W.cpu().numpy(), eng.M.cpu().numpy(), eng.V.cpu().numpy(), eng.read_state()
+        if lazy:
+            assert W.tobytes() == W0.tobytes() and M.tobytes() == M0.tobytes() and V.tobytes() == V0.tobytes()
+            assert rec.tobytes() == r0.tobytes()
+        else:
+            assert np.isfinite(W).all() and not np.array_equal(W[:n_u], W0[:n_u]) and not np.array_equal(W[n_u:], W0[n_u:])
+            assert int(rec["step_fwd"]) == 1 and rec.tobytes() != r0.tobytes()
+        eng.close()
+
+
 def test_fit_with_the_lazy_update_returns_the_dense_history_and_tables():
     """`trainer.fit` end to end (epoch shuffles, ragged last batch, graph blocks + eager tail, validation between the
     epochs, best-weights snapshot) over an engine with the lazy dense Adam and one with the dense kernel: the tables,
