@@ -25,6 +25,9 @@ RCCL_ID_BYTES = 128
 LAZY_WINDOW = 8
 # anirec_train_desc.optimizer (ANIREC_OPT_*)
 OPT_ADAM, OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
+# anirec_train_desc.loss (ANIREC_LOSS_*) and .activation / the predict calls' activation (ANIREC_ACT_*)
+LOSS_BCE, LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOGCOSH = 0, 1, 2, 3, 4
+ACT_SIGMOID, ACT_LINEAR, ACT_TANH, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4
 
 
 class AnirecError(RuntimeError):
@@ -61,9 +64,10 @@ class TrainDesc(C.Structure):
         ("adam_row_hi", C.c_int32), ("lazy", C.c_int32),
         ("W", C.c_void_p), ("M", C.c_void_p), ("V", C.c_void_p), ("rowmap", C.c_void_p),
         ("state", C.c_void_p), ("user_idx", C.c_void_p), ("anime_idx", C.c_void_p),
-        ("rating", C.c_void_p), ("sched", C.c_void_p), ("n_steps", C.c_int32), ("pad2", C.c_int32),
+        ("rating", C.c_void_p), ("sched", C.c_void_p), ("n_steps", C.c_int32), ("loss", C.c_int32),
         ("packets", C.c_void_p), ("dense_grad", C.c_void_p), ("workspace", C.c_void_p),
         ("workspace_bytes", C.c_size_t), ("lazy_state", C.c_void_p), ("optimizer", C.c_int32),
+        ("activation", C.c_int32),
     ]
 
 
@@ -140,6 +144,13 @@ PROTOTYPES = {
     "anirec_predict_grid_mfma": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _vp, _vp, _sz, _vp]),
     "anirec_predict_topk": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _vp, _i32, _vp,
                                       _vp, _vp, _sz, _vp]),
+    "anirec_predict_pairs_act": (C.c_int, [_vp, _vp, _vp, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp]),
+    "anirec_predict_grid_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _sz, _vp]),
+    "anirec_predict_grid_mfma_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _sz, _vp]),
+    "anirec_predict_topk_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
+                                          _vp, _vp, _sz, _vp]),
+    "anirec_predict_topk_mfma_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
+                                               _vp, _vp, _vp, _sz, _vp]),
     "anirec_predict_topk_mfma_workspace_bytes": (_sz, [_i32, _i32]),
     "anirec_predict_topk_mfma": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _vp, _i32, _vp,
                                            _vp, _vp, _vp, _sz, _vp]),

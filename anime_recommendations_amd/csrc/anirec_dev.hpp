@@ -6,6 +6,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/anirec.h"
 
 #define ANIREC_HIP_CHECK(expr)                  \
@@ -124,10 +126,143 @@ __device__ __forceinline__ float sigmoidf_stable(float y) {
   return y >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
 }
 
+// tf.nn.sigmoid_cross_entropy_with_logits: the binary_crossentropy of the sigmoid head (Keras takes the logits)
+__device__ __forceinline__ float bce_logits(float y, float t) {
+  return fmaxf(y, 0.f) - y * t + log1pf(expf(-fabsf(y)));
+}
+
+// ---- the output head (include/anirec.h, ANIREC_ACT_* / ANIREC_LOSS_*): ONE definition per kind, shared by the
+// training head, validation and every predict path.  Outside the default sigmoid + BCE pair (whose code the kernels keep
+// as it was: from logits, dy = (p - t) / B) every product and sum is rounded once, so that a NumPy restatement in the
+// same order holds them to a few ulps of the transcendental functions.
+constexpr float kBceEps = 1e-7f;                // Keras backend.epsilon()
+constexpr float kBceOneMinusEps = 1.0f - 1e-7f; // rounded in fp32, as tf.clip_by_value's 1 - epsilon
+constexpr float kLn2 = 0.693147180559945309f;
+
+__device__ __forceinline__ float softplusf_stable(float x) {
+#pragma clang fp contract(off)
+  return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x)));
+}
+
+// p = act(y): every kind is non-decreasing in y (the top-k paths rely on it)
+template <int kAct>
+__device__ __forceinline__ float act_fwd(float y) {
+  if constexpr (kAct == ANIREC_ACT_SIGMOID) {
+    return sigmoidf_stable(y);
+  } else if constexpr (kAct == ANIREC_ACT_LINEAR) {
+    return y;
+  } else if constexpr (kAct == ANIREC_ACT_TANH) {
+    return tanhf(y);
+  } else if constexpr (kAct == ANIREC_ACT_RELU) {
+    return fmaxf(y, 0.f);
+  } else {
+    static_assert(kAct == ANIREC_ACT_SOFTPLUS, "unknown activation");
+    return softplusf_stable(y);
+  }
+}
+
+// d act / d y as TF's gradient op computes it, from y and p = act(y)
+template <int kAct>
+__device__ __forceinline__ float act_grad(float y, float p) {
+#pragma clang fp contract(off)
+  if constexpr (kAct == ANIREC_ACT_SIGMOID) {
+    return p * (1.f - p);
+  } else if constexpr (kAct == ANIREC_ACT_LINEAR) {
+    return 1.f;
+  } else if constexpr (kAct == ANIREC_ACT_TANH) {
+    return 1.f - p * p;
+  } else if constexpr (kAct == ANIREC_ACT_RELU) {
+    return y > 0.f ? 1.f : 0.f;
+  } else {
+    static_assert(kAct == ANIREC_ACT_SOFTPLUS, "unknown activation");
+    return sigmoidf_stable(y);
+  }
+}
+
+// the loss l(p, t) of one rating and dl/dp (the probability form of BCE: outside the sigmoid head)
+template <int kLoss>
+__device__ __forceinline__ void loss_terms(float p, float t, float &l, float &g) {
+#pragma clang fp contract(off)
+  const float e = p - t;
+  if constexpr (kLoss == ANIREC_LOSS_BCE) {
+    const float q = fminf(fmaxf(p, kBceEps), kBceOneMinusEps);
+    const float a = q + kBceEps, b = (1.f - q) + kBceEps;
+    l = -(t * logf(a) + (1.f - t) * logf(b));
+    // tf.clip_by_value's gradient passes on the closed interval [eps, 1 - eps] (a NaN p passes nothing)
+    g = (p >= kBceEps && p <= kBceOneMinusEps) ? -(t / a) + (1.f - t) / b : 0.f;
+  } else if constexpr (kLoss == ANIREC_LOSS_MSE) {
+    l = e * e;
+    g = 2.f * e;
+  } else if constexpr (kLoss == ANIREC_LOSS_MAE) {
+    l = fabsf(e);
+    g = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
+  } else if constexpr (kLoss == ANIREC_LOSS_HUBER) {
+    const float ae = fabsf(e);
+    l = ae <= 1.f ? 0.5f * (e * e) : ae - 0.5f;
+    g = ae <= 1.f ? e : (e > 0.f ? 1.f : -1.f);
+  } else {
+    static_assert(kLoss == ANIREC_LOSS_LOGCOSH, "unknown loss");
+    l = (e + softplusf_stable(-2.f * e)) - kLn2;
+    g = 1.f - 2.f * sigmoidf_stable(-2.f * e);
+  }
+}
+
+// one rating through the head: p = act(y) and dl/dy (the 1/B of the batch mean not applied) ...
+template <int kAct, int kLoss>
+__device__ __forceinline__ void head_grad(float y, float t, float &p, float &g) {
+#pragma clang fp contract(off)
+  p = act_fwd<kAct>(y);
+  if constexpr (kAct == ANIREC_ACT_SIGMOID && kLoss == ANIREC_LOSS_BCE) {
+    g = p - t;
+  } else {
+    float l, gp;
+    loss_terms<kLoss>(p, t, l, gp);
+    g = gp * act_grad<kAct>(y, p);
+  }
+}
+// ... and its data loss
+template <int kAct, int kLoss>
+__device__ __forceinline__ float head_loss(float y, float t, float p) {
+  if constexpr (kAct == ANIREC_ACT_SIGMOID && kLoss == ANIREC_LOSS_BCE) {
+    return bce_logits(y, t);
+  } else {
+    float l, gp;
+    loss_terms<kLoss>(p, t, l, gp);
+    return l;
+  }
+}
+
 // rating of a pair from its cosine through the folded BN-inference head: ONE definition shared by the
 // exact path (k_scores epilogue) and the MFMA path's re-rank, so both produce the same fp32 value
+template <int kAct = ANIREC_ACT_SIGMOID>
 __device__ __forceinline__ float rating_from_cosine(float c, float hs, float hb) {
-  return sigmoidf_stable(__fmaf_rn(c, hs, hb));
+  return act_fwd<kAct>(__fmaf_rn(c, hs, hb));
+}
+
+// host: an ANIREC_ACT_* / ANIREC_LOSS_* value the kernels implement
+static inline bool act_ok(int32_t a) { return a >= ANIREC_ACT_SIGMOID && a <= ANIREC_ACT_SOFTPLUS; }
+static inline bool loss_ok(int32_t l) { return l >= ANIREC_LOSS_BCE && l <= ANIREC_LOSS_LOGCOSH; }
+
+// host: calls f(std::integral_constant<int, kAct>) with the activation as a compile-time constant
+template <typename F>
+static inline auto with_act(int32_t act, F &&f) {
+  switch (act) {
+    case ANIREC_ACT_LINEAR: return f(std::integral_constant<int, ANIREC_ACT_LINEAR>());
+    case ANIREC_ACT_TANH: return f(std::integral_constant<int, ANIREC_ACT_TANH>());
+    case ANIREC_ACT_RELU: return f(std::integral_constant<int, ANIREC_ACT_RELU>());
+    case ANIREC_ACT_SOFTPLUS: return f(std::integral_constant<int, ANIREC_ACT_SOFTPLUS>());
+    default: return f(std::integral_constant<int, ANIREC_ACT_SIGMOID>());
+  }
+}
+template <typename F>
+static inline auto with_loss(int32_t loss, F &&f) {
+  switch (loss) {
+    case ANIREC_LOSS_MSE: return f(std::integral_constant<int, ANIREC_LOSS_MSE>());
+    case ANIREC_LOSS_MAE: return f(std::integral_constant<int, ANIREC_LOSS_MAE>());
+    case ANIREC_LOSS_HUBER: return f(std::integral_constant<int, ANIREC_LOSS_HUBER>());
+    case ANIREC_LOSS_LOGCOSH: return f(std::integral_constant<int, ANIREC_LOSS_LOGCOSH>());
+    default: return f(std::integral_constant<int, ANIREC_LOSS_BCE>());
+  }
 }
 
 // sigmoid(gamma*(w*c+b-mu)/sqrt(var+eps)+beta) = sigmoid(c*hs + hb); folded in fp32 exactly as

@@ -66,10 +66,11 @@ struct ScoreArgs {
   int n;
   float *out;             // [nq][ld]
   size_t ld;
-  int use_head;           // 1: sigmoid(c*hs + hb)
+  int use_head;           // 1: act(c*hs + hb), the kernel's activation kAct
   float hs, hb;
 };
 
+template <int kAct>
 __global__ __launch_bounds__(256) void k_scores(ScoreArgs a) {
   __shared__ __attribute__((aligned(16))) float Qs[kTile * kPitch];
   __shared__ __attribute__((aligned(16))) float Ws[kTile * kPitch];
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void k_scores(ScoreArgs a) {
       const int j = j0 + tx + 16 * r;
       if (j >= a.n) continue;
       float s = acc[qq][r];
-      if (a.use_head) s = rating_from_cosine(s, a.hs, a.hb);
+      if (a.use_head) s = rating_from_cosine<kAct>(s, a.hs, a.hb);
       a.out[(size_t)q * a.ld + j] = s;
     }
   }
@@ -363,6 +364,7 @@ __global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a) {
 // ------------------------------------------------------------------------------------
 // predict on explicit pairs (model.predict([user_arr, anime_arr]))
 // ------------------------------------------------------------------------------------
+template <int kAct>
 __global__ __launch_bounds__(256) void k_predict_pairs(const float *U, const float *A,
                                                        const int32_t *ui, const int32_t *ai, int n,
                                                        float hs, float hb, float *p) {
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(256) void k_predict_pairs(const float *U, const flo
   if (l == 0) {
     const float ru = 1.0f / sqrtf(fmaxf(su, kL2nEps));
     const float ra = 1.0f / sqrtf(fmaxf(sa, kL2nEps));
-    p[i] = sigmoidf_stable(dd * ru * ra * hs + hb);
+    p[i] = act_fwd<kAct>(dd * ru * ra * hs + hb);
   }
 }
 
@@ -394,6 +396,7 @@ static inline void head_affine(const anirec_head *h, float *hs, float *hb) { hea
 // bit for bit — so the 64 x 64 tile kernel's 63/64 wasted lanes disappear and the pass is HBM-bound.
 constexpr int kFewQ = 16;
 constexpr int kFewPitch = kDim + 4;
+template <int kAct>
 __global__ __launch_bounds__(256) void k_scores_few(ScoreArgs a) {
   __shared__ __attribute__((aligned(16))) float Ws[64 * kFewPitch];
   __shared__ __attribute__((aligned(16))) float Qs[kFewQ * kDim];
@@ -424,7 +427,7 @@ __global__ __launch_bounds__(256) void k_scores_few(ScoreArgs a) {
       s = __fmaf_rn(x.z, y.z, s);
       s = __fmaf_rn(x.w, y.w, s);
     }
-    if (a.use_head) s = rating_from_cosine(s, a.hs, a.hb);
+    if (a.use_head) s = rating_from_cosine<kAct>(s, a.hs, a.hb);
     if (j < a.n) a.out[(size_t)q * a.ld + j] = s;
   }
 }
@@ -469,13 +472,17 @@ static int launch_select(SelectArgs sa, void *tmp, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-static int launch_scores(const ScoreArgs &a, hipStream_t s) {
-  if (a.nq <= kFewQ) {
-    hipLaunchKernelGGL(k_scores_few, dim3((a.n + 63) / 64), dim3(256), 0, s, a);
-    return (int)hipGetLastError();
-  }
-  dim3 grid((a.n + kTile - 1) / kTile, (a.nq + kTile - 1) / kTile);
-  hipLaunchKernelGGL(k_scores, grid, dim3(256), 0, s, a);
+// act: the activation of a head (use_head != 0); plain cosine scores take the default instantiation
+static int launch_scores(const ScoreArgs &a, hipStream_t s, int32_t act = ANIREC_ACT_SIGMOID) {
+  with_act(act, [&](auto k) {
+    constexpr int kAct = decltype(k)::value;
+    if (a.nq <= kFewQ) {
+      hipLaunchKernelGGL(k_scores_few<kAct>, dim3((a.n + 63) / 64), dim3(256), 0, s, a);
+    } else {
+      dim3 grid((a.n + kTile - 1) / kTile, (a.nq + kTile - 1) / kTile);
+      hipLaunchKernelGGL(k_scores<kAct>, grid, dim3(256), 0, s, a);
+    }
+  });
   return (int)hipGetLastError();
 }
 
@@ -569,16 +576,24 @@ int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int
   return ANIREC_OK;
 }
 
-int anirec_predict_pairs(const float *U, const float *A, const int32_t *user_idx,
-                         const int32_t *anime_idx, int32_t n, const anirec_head *head, float *p,
-                         void *stream) {
-  if (!U || !A || !user_idx || !anime_idx || !head || !p || n < 0) return ANIREC_EINVAL;
+int anirec_predict_pairs_act(const float *U, const float *A, const int32_t *user_idx,
+                             const int32_t *anime_idx, int32_t n, const anirec_head *head, int32_t activation,
+                             float *p, void *stream) {
+  if (!U || !A || !user_idx || !anime_idx || !head || !p || n < 0 || !act_ok(activation)) return ANIREC_EINVAL;
   if (n == 0) return ANIREC_OK;
   float hs, hb;
   head_affine(head, &hs, &hb);
-  hipLaunchKernelGGL(k_predict_pairs, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, U, A,
-                     user_idx, anime_idx, n, hs, hb, p);
+  with_act(activation, [&](auto k) {
+    hipLaunchKernelGGL(k_predict_pairs<decltype(k)::value>, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, U, A,
+                       user_idx, anime_idx, n, hs, hb, p);
+  });
   return (int)hipGetLastError();
+}
+
+int anirec_predict_pairs(const float *U, const float *A, const int32_t *user_idx,
+                         const int32_t *anime_idx, int32_t n, const anirec_head *head, float *p,
+                         void *stream) {
+  return anirec_predict_pairs_act(U, A, user_idx, anime_idx, n, head, ANIREC_ACT_SIGMOID, p, stream);
 }
 
 // workspace of predict_grid / predict_topk: normalised copies of the query users and of A,
@@ -600,7 +615,14 @@ size_t anirec_predict_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t 
 int anirec_predict_grid(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                         int32_t n_users, const anirec_head *head, float *out, void *workspace,
                         size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out || !workspace || n_anime < 1 || n_users < 0)
+  return anirec_predict_grid_act(U, A, n_anime, users, n_users, head, ANIREC_ACT_SIGMOID, out, workspace,
+                                 workspace_bytes, stream);
+}
+
+int anirec_predict_grid_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                            int32_t n_users, const anirec_head *head, int32_t activation, float *out,
+                            void *workspace, size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out || !workspace || n_anime < 1 || n_users < 0 || !act_ok(activation))
     return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
   if (workspace_bytes < norm_bytes(n_anime, n_users)) return ANIREC_EWORKSPACE;
@@ -623,14 +645,22 @@ int anirec_predict_grid(const float *U, const float *A, int32_t n_anime, const i
   a.ld = (size_t)n_anime;
   a.use_head = 1;
   head_affine(head, &a.hs, &a.hb);
-  return launch_scores(a, s);
+  return launch_scores(a, s, activation);
 }
 
 int anirec_predict_topk(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                         int32_t n_users, const anirec_head *head, const uint32_t *watched,
                         int32_t k, int32_t *out_idx, float *out_p, void *workspace,
                         size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace) return ANIREC_EINVAL;
+  return anirec_predict_topk_act(U, A, n_anime, users, n_users, head, ANIREC_ACT_SIGMOID, watched, k, out_idx, out_p,
+                                 workspace, workspace_bytes, stream);
+}
+
+int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                            int32_t n_users, const anirec_head *head, int32_t activation,
+                            const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation)) return ANIREC_EINVAL;
   if (n_anime < 1 || n_users < 0 || k < 1 || k > ANIREC_MAX_TOPK) return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
   const size_t nb = norm_bytes(n_anime, n_users) + kSelTmpBytes;
@@ -664,7 +694,7 @@ int anirec_predict_topk(const float *U, const float *A, int32_t n_anime, const i
     a.use_head = 1;
     a.hs = hs;
     a.hb = hb;
-    int e = launch_scores(a, s);
+    int e = launch_scores(a, s, activation);
     if (e) return e;
     SelectArgs sa;
     sa.scores = buf;

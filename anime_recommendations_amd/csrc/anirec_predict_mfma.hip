@@ -64,15 +64,65 @@ __device__ __forceinline__ float sigmoid_fast(float y) {
   return __builtin_amdgcn_rcpf(1.0f + __expf(-y));
 }
 
+// The fast form of every activation (include/anirec.h, ANIREC_ACT_*), all within the 1e-5 ratings bar of act_fwd:
+//   linear, relu   exact (the same fp32 operations as the exact path);
+//   tanh           1 - 2 / (1 + 2^(2 y log2 e)): exp2 and rcp within 1 ulp each, absolute error < 1e-6; saturates to
+//                  +-1 (rcp(inf) = 0) without a NaN;
+//   softplus       max(y, 0) + ln 2 * log2(1 + 2^(-|y| log2 e)): the log2 term lies in (0, 1], absolute error < 1e-6.
+constexpr float kLog2e = 1.44269504088896341f;
+template <int kAct>
+__device__ __forceinline__ float act_fast(float y) {
+  if constexpr (kAct == ANIREC_ACT_SIGMOID) {
+    return sigmoid_fast(y);
+  } else if constexpr (kAct == ANIREC_ACT_LINEAR) {
+    return y;
+  } else if constexpr (kAct == ANIREC_ACT_TANH) {
+    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y * (2.0f * kLog2e)));
+  } else if constexpr (kAct == ANIREC_ACT_RELU) {
+    return fmaxf(y, 0.f);
+  } else {
+    static_assert(kAct == ANIREC_ACT_SOFTPLUS, "unknown activation");
+    return fmaxf(y, 0.f) + kLn2 * __builtin_amdgcn_logf(1.0f + __builtin_amdgcn_exp2f(fabsf(y) * -kLog2e));
+  }
+}
+
+// k_predict_mfma2's epilogue: act(c * hs + hb) with the head's scale folded into the exponent where there is one
+template <int kAct>
+struct FastHead {
+  float s, b;
+  __device__ __forceinline__ FastHead(float hs, float hb) {
+    if constexpr (kAct == ANIREC_ACT_SIGMOID) {  // sigmoid(c * hs + hb) = 1 / (1 + 2^(c * nhs + nhb))
+      s = -hs * 1.44269504088896341f;
+      b = -hb * 1.44269504088896341f;
+    } else if constexpr (kAct == ANIREC_ACT_TANH) {  // tanh(y) = 1 - 2 / (1 + 2^(c * 2 hs log2 e + 2 hb log2 e))
+      s = hs * (2.0f * kLog2e);
+      b = hb * (2.0f * kLog2e);
+    } else {
+      s = hs;
+      b = hb;
+    }
+  }
+  __device__ __forceinline__ float operator()(float c) const {
+    if constexpr (kAct == ANIREC_ACT_SIGMOID) {
+      return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(c, s, b)));
+    } else if constexpr (kAct == ANIREC_ACT_TANH) {
+      return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(c, s, b)));
+    } else {
+      return act_fast<kAct>(__builtin_fmaf(c, s, b));
+    }
+  }
+};
+
 struct PredArgs {
   const uint4 *Ub;  // [n_users][32] 16-B chunks: 16 hi chunks then 16 lo chunks per row
   const uint4 *Ab;  // [n_anime][32]
   int n_users, n_anime;
   int tiles_per_part;  // k_predict_mfma2: blockIdx.y walks anime tiles [y * tiles_per_part, (y+1) * tiles_per_part)
-  float hs, hb;     // sigmoid(c * hs + hb); hs already carries the 2^-16 of the operand scaling
+  float hs, hb;     // act(c * hs + hb); hs already carries the 2^-16 of the operand scaling
   float *out;       // [n_users][n_anime]
 };
 
+template <int kAct>
 __global__ __launch_bounds__(256, 2) void k_predict_mfma(PredArgs a) {
   __shared__ __attribute__((aligned(16))) uint4 Ks[2][kPN * 32];  // 2 x 32 KB: hi+lo of 64 anime rows
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -146,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_mfma(PredArgs a) {
       for (int g = 0; g < 16; ++g) {
         const int urow = u0 + 32 * w + (g & 3) + 8 * (g >> 2) + 4 * h;
         if (urow < a.n_users && col < a.n_anime)
-          a.out[(size_t)urow * a.n_anime + col] = sigmoid_fast(acc[cb][g] * a.hs + a.hb);
+          a.out[(size_t)urow * a.n_anime + col] = act_fast<kAct>(acc[cb][g] * a.hs + a.hb);
       }
     }
     __syncthreads();
@@ -189,8 +239,9 @@ struct Acc2 {
   f32x4 c[4][2];  // [anime block of 16][user block of 16]
 };
 
-// kDbg (timing only, wrong output): 1 = epilogue + stores without the MFMAs, 2 = MFMAs without the stores
-template <int kDbg>
+// kDbg (timing only, wrong output): 1 = epilogue + stores without the MFMAs, 2 = MFMAs without the stores; kAct: the
+// activation of the epilogue (FastHead)
+template <int kDbg, int kAct>
 __global__ __launch_bounds__(256, 2) void k_predict_mfma2(PredArgs a) {
   // one LDS array (a second object beside an LDS-DMA target makes hipcc drain vmcnt before every ds_read):
   // 2 x 32 KB key tiles (hi+lo planes of 64 anime rows), then 4 x 4 KB output staging (one per wave)
@@ -255,8 +306,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_mfma2(PredArgs a) {
   // store instruction j of user block ub: lane -> row 4 j + gq of the block, 16-byte piece c16 of its 256 B
   const uint32_t vrow = (uint32_t)((32 * w + gq) * a.n_anime + 4 * c16) * 4u;
   const uint32_t vrow4 = (uint32_t)(4 * a.n_anime) * 4u;
-  // sigmoid(c * hs + hb) = 1 / (1 + 2^(c * nhs + nhb))
-  const float nhs = -a.hs * 1.44269504088896341f, nhb = -a.hb * 1.44269504088896341f;
+  const FastHead<kAct> head(a.hs, a.hb);
 
   // this workgroup's anime tiles [tb, tb + ntiles): the grid's y dimension cuts the anime table into parts so that
   // there are several times more workgroups than the 512 the chip holds and the dispatcher balances the tail
@@ -296,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_mfma2(PredArgs a) {
           f32x4 o;
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            o[i] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(v[i], nhs, nhb)));
+            o[i] = head(v[i]);
           // piece (anime block eab, quad gq) of user c16
           stg[c16 * 16 + ((4 * eab + gq) ^ c16)] = __builtin_bit_cast(uint4, o);
           if (eab == 3) {  // the user block is complete: 4 rows x 256 B per store instruction
@@ -364,7 +414,14 @@ size_t anirec_predict_mfma_workspace_bytes(int32_t n_anime, int32_t n_users) {
 int anirec_predict_grid_mfma(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                              int32_t n_users, const anirec_head *head, float *out, void *workspace,
                              size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out || !workspace || n_anime < 1 || n_users < 0)
+  return anirec_predict_grid_mfma_act(U, A, n_anime, users, n_users, head, ANIREC_ACT_SIGMOID, out, workspace,
+                                      workspace_bytes, stream);
+}
+
+int anirec_predict_grid_mfma_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                                 int32_t n_users, const anirec_head *head, int32_t activation, float *out,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out || !workspace || n_anime < 1 || n_users < 0 || !act_ok(activation))
     return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
   if (workspace_bytes < anirec_predict_mfma_workspace_bytes(n_anime, n_users)) return ANIREC_EWORKSPACE;
@@ -403,14 +460,18 @@ int anirec_predict_grid_mfma(const float *U, const float *A, int32_t n_anime, co
     const char *dbg = getenv("ANIREC_PREDICT_DEBUG");
     const int mode = dbg ? atoi(dbg) : 0;
     if (mode == 1)
-      hipLaunchKernelGGL(k_predict_mfma2<1>, grid, dim3(256), 0, s, pa);
+      hipLaunchKernelGGL((k_predict_mfma2<1, ANIREC_ACT_SIGMOID>), grid, dim3(256), 0, s, pa);
     else if (mode == 2)
-      hipLaunchKernelGGL(k_predict_mfma2<2>, grid, dim3(256), 0, s, pa);
-
+      hipLaunchKernelGGL((k_predict_mfma2<2, ANIREC_ACT_SIGMOID>), grid, dim3(256), 0, s, pa);
     else
-      hipLaunchKernelGGL(k_predict_mfma2<0>, grid, dim3(256), 0, s, pa);
-  } else
-    hipLaunchKernelGGL(k_predict_mfma, dim3((n_users + kPM - 1) / kPM), dim3(256), 0, s, pa);
+      with_act(activation, [&](auto k) {
+        hipLaunchKernelGGL((k_predict_mfma2<0, decltype(k)::value>), grid, dim3(256), 0, s, pa);
+      });
+  } else {
+    with_act(activation, [&](auto k) {
+      hipLaunchKernelGGL(k_predict_mfma<decltype(k)::value>, dim3((n_users + kPM - 1) / kPM), dim3(256), 0, s, pa);
+    });
+  }
   return (int)hipGetLastError();
 }
 

@@ -767,7 +767,7 @@ struct RerankArgs {
   int32_t *flags;          // bit1: incomplete window / too many survivors / too few candidates
   int32_t *out_idx;        // [nq][k]
   float *out_score;        // [nq][k]
-  float hs, hb, sign;      // kPredict: rating = sigmoid(c * hs + hb); MFMA scores are sign * c
+  float hs, hb, sign;      // kPredict: rating = act(c * hs + hb) (the kernel's kAct); MFMA scores are sign * c
   const int32_t *unnorm;   // cosine path: non-zero when some row was not unit-norm (window unproven) -> flags bit 2
 };
 
@@ -777,8 +777,9 @@ constexpr int kMaxSurv = 256;
 // exact cosine chain, mapped through the BN-inference head exactly as the exact path does
 // (rating_from_cosine) and ranked by (rating desc, index asc).  Ratings are a non-decreasing function of
 // sign * c, so every key that is not a survivor has rating <= rating(tau - eps): the row is complete iff
-// k survivors lie strictly above that bound (a few ulps of slack for the fast exp); saturated heads and
-// worst-case MFMA errors fail the test and fall back to the exact path.
+// k survivors lie strictly above that bound (a few ulps of slack for the fast exp, rating_slack); saturated heads,
+// flat regions of the activation (relu at y <= 0, softplus underflowing to 0) and worst-case MFMA errors fail the test
+// and fall back to the exact path.
 //
 // Measured in round 3 (rocprofv3, 350 k keys x 65 536 queries): at k = 100 the kernel re-reads ~110 fp32 rows of
 // 512 B per query — 56 KB per query, 3.7 GB per 65 536 queries, 19.7 GB for the all-pairs job — and runs at
@@ -797,7 +798,28 @@ constexpr int kMaxSurv = 256;
 // (4 line requests per row instead of 32) changed neither case (0.599 vs 0.598 ms for the 18 k job).
 // kSlots = ceil(entries / 64) register slots per lane, as in refresh_row: after the last refresh a row holds about
 // 2 k entries, so the 32-step select and the survivor scan run over 2-4 slots, not kCap / 64.
-template <bool kPredict, int kSlots>
+// The bound a non-survivor's rating cannot exceed: rating(x) computed for x below the bound's argument xb.  A rating whose
+// computed value is within d ulps of the exact one is non-decreasing up to 2d ulps: |r(xb)| * 2d more covers it.
+//   sigmoid   1 + __expf in fp32 and an IEEE divide, < 2.5 ulp: 6e-7 (5 ulps; the kernel's factor since round 3);
+//   linear    fmaf is correctly rounded and rounding is monotone: exactly non-decreasing, no slack;
+//   relu      fmaxf of the same: no slack;
+//   tanh      the device library's tanhf, < 4 ulp: 1e-6 (8 ulps);
+//   softplus  fmaxf + log1pf(__expf): < 8 ulp of the sum: 2e-6 (16 ulps).
+// (tests/test_heads_gpu.py sweeps each activation through a dense ramp of arguments and checks these bounds.)
+template <int kAct>
+__device__ __forceinline__ float rating_bound(float r) {
+  if constexpr (kAct == ANIREC_ACT_SIGMOID) {
+    return r * (1.0f + 6e-7f);  // r >= 0
+  } else if constexpr (kAct == ANIREC_ACT_LINEAR || kAct == ANIREC_ACT_RELU) {
+    return r;
+  } else if constexpr (kAct == ANIREC_ACT_TANH) {
+    return r + fabsf(r) * 1e-6f;
+  } else {
+    return r + fabsf(r) * 2e-6f;
+  }
+}
+
+template <bool kPredict, int kSlots, int kAct>
 __device__ __forceinline__ void rerank_row(const RerankArgs &a, int row, int c, bool ovf, int lane, float *qs, int32_t *sidx,
                                            float *sval,
                                            unsigned long long *skey) {
@@ -874,13 +896,13 @@ __device__ __forceinline__ void rerank_row(const RerankArgs &a, int row, int c, 
       s = __fmaf_rn(x.z, qs[4 * k4 + 2], s);
       s = __fmaf_rn(x.w, qs[4 * k4 + 3], s);
     }
-    sval[i] = kPredict ? rating_from_cosine(s, a.hs, a.hb) : s;
+    sval[i] = kPredict ? rating_from_cosine<kAct>(s, a.hs, a.hb) : s;
   }
   __syncthreads();
   if (kPredict) {
     // k-th best rating among the survivors vs the best any excluded key could reach
     // keys that are not survivors have MFMA value < tau - 2 eps, i.e. sign * c < tau - eps
-    const float p_bound = rating_from_cosine(a.sign * (lo + kEpsMfma), a.hs, a.hb) * (1.0f + 6e-7f);
+    const float p_bound = rating_bound<kAct>(rating_from_cosine<kAct>(a.sign * (lo + kEpsMfma), a.hs, a.hb));
     int above = 0;  // survivors strictly above the bound
     for (int i0 = 0; i0 < ns; i0 += 64) {
       const int i = i0 + lane;
@@ -952,7 +974,7 @@ __device__ __forceinline__ void rerank_row(const RerankArgs &a, int row, int c, 
   }
 }
 
-template <bool kPredict>
+template <bool kPredict, int kAct>
 __device__ __forceinline__ void rerank_one(const RerankArgs &a, int row, int lane, float *qs, int32_t *sidx, float *sval,
                                            unsigned long long *skey) {
   int c = fold_regions(a.cand + (size_t)row * kCap, a.cnt + row, a.cnt2 + (size_t)row * kMaxSplit,
@@ -963,21 +985,22 @@ __device__ __forceinline__ void rerank_one(const RerankArgs &a, int row, int lan
     c = fold_inbox(a.cand + (size_t)row * kCap, a.cnt + row, a.inbox + g * kInbox, a.icnt + g, a.theta[row], c, lane, ovf);
   }
   if (c <= 128)
-    rerank_row<kPredict, 2>(a, row, c, ovf, lane, qs, sidx, sval, skey);
+    rerank_row<kPredict, 2, kAct>(a, row, c, ovf, lane, qs, sidx, sval, skey);
   else if (c <= 256)
-    rerank_row<kPredict, 4>(a, row, c, ovf, lane, qs, sidx, sval, skey);
+    rerank_row<kPredict, 4, kAct>(a, row, c, ovf, lane, qs, sidx, sval, skey);
   else
-    rerank_row<kPredict, kCap / 64>(a, row, c, ovf, lane, qs, sidx, sval, skey);
+    rerank_row<kPredict, kCap / 64, kAct>(a, row, c, ovf, lane, qs, sidx, sval, skey);
 }
 
-template <bool kPredict>
+// kAct: the activation of the predict head (kPredict); the cosine top-k takes ANIREC_ACT_SIGMOID, which it does not use
+template <bool kPredict, int kAct>
 __global__ __launch_bounds__(64) void k_rerank(RerankArgs a) {  // bounded grid, strides over the rows (see k_refresh)
   __shared__ float qs[kDim];
   __shared__ int32_t sidx[kMaxSurv];
   __shared__ float sval[kMaxSurv];
   __shared__ unsigned long long skey[kMaxSurv];
   for (int row = blockIdx.x; row < a.nq; row += gridDim.x) {
-    rerank_one<kPredict>(a, row, threadIdx.x, qs, sidx, sval, skey);
+    rerank_one<kPredict, kAct>(a, row, threadIdx.x, qs, sidx, sval, skey);
     __syncthreads();  // the next row rewrites qs / sidx / sval
   }
 }
@@ -1401,7 +1424,7 @@ static int run_batch(const float *What, const _Float16 *Wb, int n, const int32_t
   ra.hs = ra.hb = 0.f;
   ra.sign = 1.f;
   ra.unnorm = unnorm;
-  hipLaunchKernelGGL(k_rerank<false>, dim3(side_grid(nq)), dim3(64), 0, s, ra);
+  hipLaunchKernelGGL((k_rerank<false, ANIREC_ACT_SIGMOID>), dim3(side_grid(nq)), dim3(64), 0, s, ra);
   return (int)hipGetLastError();
 }
 
@@ -1841,7 +1864,16 @@ int anirec_predict_topk_mfma(const float *U, const float *A, int32_t n_anime, co
                              int32_t n_users, const anirec_head *head, const uint32_t *watched, int32_t k,
                              int32_t *out_idx, float *out_p, int32_t *flags_out, void *workspace,
                              size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out_idx || !out_p || !flags_out || !workspace) return ANIREC_EINVAL;
+  return anirec_predict_topk_mfma_act(U, A, n_anime, users, n_users, head, ANIREC_ACT_SIGMOID, watched, k, out_idx,
+                                      out_p, flags_out, workspace, workspace_bytes, stream);
+}
+
+int anirec_predict_topk_mfma_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                                 int32_t n_users, const anirec_head *head, int32_t activation,
+                                 const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, int32_t *flags_out,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out_idx || !out_p || !flags_out || !workspace || !act_ok(activation))
+    return ANIREC_EINVAL;
   if (n_anime < 1 || n_users < 0 || k < 1 || k > ANIREC_MAX_TOPK - 1) return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
   if (workspace_bytes < anirec_predict_topk_mfma_workspace_bytes(n_anime, n_users)) return ANIREC_EWORKSPACE;
@@ -1865,7 +1897,7 @@ int anirec_predict_topk_mfma(const float *U, const float *A, int32_t n_anime, co
   float *theta = (float *)p;
   p += al((size_t)n_users * 4);
   int32_t *cnt2 = (int32_t *)(p + 256);
-  // sigmoid(gamma*(w*c+b-mu)/sqrt(var+eps)+beta) = sigmoid(c*hs + hb), folded exactly as the exact path does
+  // act(gamma*(w*c+b-mu)/sqrt(var+eps)+beta) = act(c*hs + hb), folded exactly as the exact path does
   float hs, hb;
   head_affine_f32(head, &hs, &hb);
   const float sign = hs < 0.f ? -1.f : 1.f;
@@ -1926,7 +1958,9 @@ int anirec_predict_topk_mfma(const float *U, const float *A, int32_t n_anime, co
     hipLaunchKernelGGL(k_flag_all, dim3((n_users + 255) / 256), dim3(256), 0, s, flags_out, n_users, out_idx, out_p, k);
     return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(k_rerank<true>, dim3(side_grid(n_users)), dim3(64), 0, s, ra);
+  with_act(activation, [&](auto k) {
+    hipLaunchKernelGGL((k_rerank<true, decltype(k)::value>), dim3(side_grid(n_users)), dim3(64), 0, s, ra);
+  });
   return (int)hipGetLastError();
 }
 

@@ -9,7 +9,8 @@
 //   fwd   half-wave per rating: coalesced 512-B gathers of U[ui], A[ai], three dot-128
 //         reductions by wavefront shuffles -> c, sum(u^2), sum(a^2)
 //   head  one workgroup per 256 ratings: batch mean/variance recomputed per workgroup,
-//         Dense(1) -> BatchNorm(batch stats) -> sigmoid -> BCE, d loss/d y, partial sums
+//         Dense(1) -> BatchNorm(batch stats) -> activation -> loss (anirec_train_desc::activation / ::loss; one
+//         instantiation per pair, the default sigmoid + BCE as it always was), d loss/d y, partial sums
 //   bwd   half-wave per chunk: weighted sum of the OTHER table's rows, accumulated in
 //         registers in a fixed order, one coalesced 512-B store per chunk (no float atomics)
 //   adam  half-wave per table row, dense: g = chunk sums - s*W + 2*l2*W, Keras-2.12 Adam,
@@ -68,7 +69,8 @@ struct TrainWs {
   unsigned long long *ticks;    // [8][ANIREC_ADAM_BLOCKS][2] measurement stamps (fwd, head, bwd, adam, lazy catch-up,
                                 // lazy adam, lazy flush, lazy reduce), behind the arena
   float *lzpart;                // [ANIREC_LAZY_WINDOW][2][ANIREC_ADAM_BLOCKS] lazy flush: per-step sum(W^2) block partials
-  float *lzring;                // [ANIREC_LAZY_WINDOW][2] lazy: {n, bce mean} of the open window's steps
+  float *lzring;                // [ANIREC_LAZY_WINDOW][2] lazy: {n, bce mean} of the open window's steps (bce: the data
+                                //   term of the descriptor's loss, whichever it is)
   float *regpart;               // [2][2][ANIREC_ADAM_BLOCKS]: user-row / anime-row sum(W^2) partials
   float *P;                     // [2][2*capC][128] chunk partial rows
   float *S;                     // [2][2*capC]      chunk self-coefficient sums
@@ -466,7 +468,7 @@ __global__ __launch_bounds__(1024) void k_seg_stats(float *pk, int pcap, int cap
 }
 
 // ------------------------------------------------------------------------------------
-// head: Dense(1) -> BatchNorm(batch stats) -> sigmoid -> BCE, spread over many workgroups.
+// head: Dense(1) -> BatchNorm(batch stats) -> activation -> loss (head_terms), spread over many workgroups.
 // Every workgroup recomputes the batch mean/variance of z from all c (two-pass, no
 // transcendentals, 40 KB from L2), then does the sigmoid/log work of ITS 256 ratings and
 // leaves eight partial sums.  Workgroup 0 publishes the step constants for bwd / adam.
@@ -488,10 +490,6 @@ struct HeadArgs {
   float l2;
   unsigned long long *ticks;
 };
-
-__device__ __forceinline__ float bce_logits(float y, float t) {
-  return fmaxf(y, 0.f) - y * t + log1pf(expf(-fabsf(y)));
-}
 
 __device__ __forceinline__ int packet_count(const float *pk, int cap) {
   return min(ld_i32(reinterpret_cast<const int32_t *>(pk + 2 * (size_t)packet_cap(cap))), cap);
@@ -543,7 +541,9 @@ struct HeadIn {
   float w, b, gamma, beta;
 };
 
-// workgroup vblk of nvb: the batch statistics (recomputed per workgroup) + 256 ratings
+// workgroup vblk of nvb: the batch statistics (recomputed per workgroup) + 256 ratings; kAct / kLoss: the output head
+// (ANIREC_ACT_* / ANIREC_LOSS_*, head_terms), one instantiation per pair
+template <int kAct, int kLoss>
 __device__ __forceinline__ void head_block(const HeadArgs &a, const HeadIn in, int vblk, int nvb, float *scratch) {
   const int tid = threadIdx.x;
   const int pcap = packet_cap(a.cap);
@@ -618,12 +618,13 @@ __device__ __forceinline__ void head_block(const HeadArgs &a, const HeadIn in, i
     const float c = my_c, t = my_t;
     const float z = c * w + b;
     const float y = z * inv + shift;
-    const float p = sigmoidf_stable(y);
-    const float dy = (p - t) / Bf;
+    float p, g;
+    head_grad<kAct, kLoss>(y, t, p, g);
+    const float dy = g / Bf;
     const float zh = (z - mu) * rs;
     r[0] = dy;
     r[1] = dy * zh;
-    r[2] = bce_logits(y, t);
+    r[2] = head_loss<kAct, kLoss>(y, t, p);
     r[3] = (p - t) * (p - t);
     r[4] = dy * c;
     r[5] = c;
@@ -933,7 +934,8 @@ struct AdamArgs {
   size_t hpart_stride;
   float two_l2;
   float *regpart;  // [2][2][ANIREC_ADAM_BLOCKS]
-  float *ring;         // user-sharded lazy mode: the open window's {n, bce mean} per step (else nullptr)
+  float *ring;         // user-sharded lazy mode: the open window's {n, bce mean} per step (else nullptr; bce = the
+                       // loss's data term)
   const int32_t *w0;   // ... and the first step of that window
   unsigned long long *ticks;
 };
@@ -1551,6 +1553,7 @@ __global__ __launch_bounds__(256) void k_lazy_catchup(LazyArgs a) {
 // disjoint from everything those read or write, so no order between them matters, and the next step starts at fwd.
 // (Step t itself is an L2-only step for them.)  Round 3 ran this catch-up as the second half of k_lazy_adam(t), on
 // the critical path behind bwd: 19 us for that launch; here it hides behind a head launch that used 40 of 256 CUs.
+template <int kAct, int kLoss>
 __global__ __launch_bounds__(kHeadThreads) void k_head(HeadArgs a, LazyArgs z, int n_head) {
   __shared__ float scratch[kHeadCols * 16];
   tick(a.ticks, 0);
@@ -1563,7 +1566,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_head(HeadArgs a, LazyArgs z, i
     return;
   }
   const HeadIn in = {st->step_fwd, st->w, st->b, st->gamma, st->beta};
-  head_block(a, in, blockIdx.x, n_head, scratch);
+  head_block<kAct, kLoss>(a, in, blockIdx.x, n_head, scratch);
   tick(a.ticks, 1);
 }
 
@@ -1909,6 +1912,7 @@ struct EvalArgs {
   anirec_state *state;
 };
 
+template <int kAct, int kLoss>
 __global__ __launch_bounds__(256) void k_eval(EvalArgs a) {
   __shared__ float sh[2][8];
   const anirec_state *st = a.state;
@@ -1924,9 +1928,10 @@ __global__ __launch_bounds__(256) void k_eval(EvalArgs a) {
               l32, su, sa, dd);
     const float c = cos_from_dots(su, sa, dd);
     const float y = (c * w + b) * inv + shift;
-    const float p = sigmoidf_stable(y);
     const float t = a.rating[i];
-    li = bce_logits(y, t);
+    float p, g;
+    head_grad<kAct, kLoss>(y, t, p, g);
+    li = head_loss<kAct, kLoss>(y, t, p);
     se = (p - t) * (p - t);
   }
   if (l32 == 0) {
@@ -1992,8 +1997,9 @@ static inline bool lazy_users(const anirec_train_desc *d) {
   return d->lazy != 0 && d->lazy_state != nullptr && d->dense_mode == 1;
 }
 
-// the update rule: a known kind, and the lazy update (Adam's only) not asked for with another
+// the update rule: a known kind, and the lazy update (Adam's only) not asked for with another; a known head
 static int check_opt(const anirec_train_desc *d) {
+  if (!loss_ok(d->loss) || !act_ok(d->activation)) return ANIREC_EINVAL;
   if (d->optimizer < ANIREC_OPT_ADAM || d->optimizer > ANIREC_OPT_ADAGRAD) return ANIREC_EINVAL;
   if (d->lazy != 0 && d->optimizer != ANIREC_OPT_ADAM) return ANIREC_EINVAL;
   return ANIREC_OK;
@@ -2134,7 +2140,13 @@ static int launch_head(const anirec_train_desc *d, const TrainWs &w, hipStream_t
     z.ticks = nullptr;  // (the head's own stamps cover every workgroup of the launch)
     extra = catchup_head_share(d, w);
   }
-  hipLaunchKernelGGL(k_head, dim3(nh + extra), dim3(kHeadThreads), 0, s, a, z, nh);
+  // the output head is a template parameter: the default pair's instantiation is the kernel as it always was
+  with_act(d->activation, [&](auto act) {
+    with_loss(d->loss, [&](auto loss) {
+      hipLaunchKernelGGL((k_head<decltype(act)::value, decltype(loss)::value>), dim3(nh + extra), dim3(kHeadThreads), 0,
+                         s, a, z, nh);
+    });
+  });
   if (int te = ticks_collect(w, 1, s)) return te;
   return (int)hipGetLastError();
 }
@@ -2935,7 +2947,12 @@ int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32
   a.rating = rating;
   a.n = n;
   a.state = d->state;
-  hipLaunchKernelGGL(k_eval, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
+  with_act(d->activation, [&](auto act) {
+    with_loss(d->loss, [&](auto loss) {
+      hipLaunchKernelGGL((k_eval<decltype(act)::value, decltype(loss)::value>), dim3((n + 7) / 8), dim3(256), 0,
+                         (hipStream_t)stream, a);
+    });
+  });
   return (int)hipGetLastError();
 }
 

@@ -121,7 +121,8 @@ class DistTrainEngine:
     """TrainEngine facade for G ranks (same interface as engine.TrainEngine for trainer.fit)."""
 
     def __init__(self, n_users, n_anime, batch_per_rank, l2=1e-4, arena_steps=64, device="cuda:0",
-                 engine_factory=None, mode=None, lazy=None, optimizer="adam"):
+                 engine_factory=None, mode=None, lazy=None, optimizer="adam", loss="binary_crossentropy",
+                 activation="sigmoid"):
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
@@ -156,6 +157,9 @@ class DistTrainEngine:
         self.optimizer = schedule.resolve_optimizer(optimizer)
         if self.optimizer != "adam":   # (Adam is every engine's default: a factory need not know the keyword)
             kw["optimizer"] = self.optimizer
+        self.loss, self.activation = schedule.resolve_loss(loss), schedule.resolve_activation(activation)
+        if (self.loss, self.activation) != ("binary_crossentropy", "sigmoid"):   # (likewise the default head)
+            kw.update(loss=self.loss, activation=self.activation)
         self.eng = engine_factory(self.n_local, self.n_anime, max_batch=max_batch, l2=l2,
                                   arena_steps=arena_steps, device=device, n_seg=self.world,
                                   my_seg=self.rank, **kw)

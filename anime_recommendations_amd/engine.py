@@ -35,7 +35,7 @@ def _dev_bytes(n, device):
 class TrainEngine:
     def __init__(self, n_user_rows, n_anime_rows, max_batch, l2=1e-4, arena_steps=64,
                  device="cuda:0", n_seg=1, my_seg=0, dense_mode=0, row_pad=1, adam_rows=None, lazy=None,
-                 optimizer="adam"):
+                 optimizer="adam", loss="binary_crossentropy", activation="sigmoid"):
         """dense_mode: 0 one GPU; 1 user-sharded DP (anime gradient through ``dense_grad``); 2 replicated
         tables (every gradient through ``dense_grad``).  row_pad: the tables and the dense buffer are
         allocated with their row count rounded up to a multiple of it (equal reduce-scatter / all-gather
@@ -49,8 +49,12 @@ class TrainEngine:
         bound by its 188 MB collectives, not by the Adam stream.
         optimizer: the update rule, a Keras optimizer name (``schedule.OPTIMIZERS``: adam, sgd, rmsprop, adagrad; any
         case).  The lazy update is Adam's alone: the other kinds always take the dense update (``lazy=True`` with them
-        is a ValueError; ANIREC_LAZY_ADAM does not concern them)."""
+        is a ValueError; ANIREC_LAZY_ADAM does not concern them).
+        loss, activation: the output head (``schedule.LOSSES`` / ``schedule.ACTIVATIONS``, Keras names, any case); the
+        default is the reference's sigmoid + binary_crossentropy."""
         self.optimizer = schedule.resolve_optimizer(optimizer)
+        self.loss = schedule.resolve_loss(loss)
+        self.activation = schedule.resolve_activation(activation)
         if self.optimizer != "adam" and lazy:
             raise ValueError("the lazy update exists for Adam only (optimizer %r)" % optimizer)
         self.lib = _lib.load()
@@ -209,6 +213,8 @@ class TrainEngine:
         d.workspace, d.workspace_bytes = _lib.ptr(self.workspace), self.workspace.numel()
         d.lazy, d.lazy_state = int(self.lazy), _lib.ptr(self.lazy_state)
         d.optimizer = schedule.OPTIMIZERS[self.optimizer]
+        d.loss = schedule.LOSSES[self.loss]
+        d.activation = schedule.ACTIVATIONS[self.activation]
         self._desc = d
         if self._trainer is not None:
             _lib.check(self.lib.anirec_trainer_destroy(self._trainer), "anirec_trainer_destroy")

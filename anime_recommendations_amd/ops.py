@@ -2,6 +2,8 @@
 
 Names follow the reference: ``get_weights`` row-normalisation (similar_anime.py:136-171),
 cosine neighbours (similar_users.py:290-296), ``model.predict`` (model_recs.py:394).
+A head dict (w, b, gamma, beta, mov_mean, mov_var) may carry an "activation" (Keras name, ``schedule.ACTIVATIONS``);
+without one the head is the reference's sigmoid.
 """
 from __future__ import annotations
 
@@ -13,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import DIM, MAX_TOPK
-from .schedule import OPTIMIZERS, resolve_optimizer
+from .schedule import ACTIVATIONS, OPTIMIZERS, resolve_activation, resolve_optimizer
 
 
 def _stream():
@@ -299,6 +301,11 @@ def topk_mfma_timing(enable):
     return float(ms.value), int(nl.value)
 
 
+def _head_act(head):
+    """ANIREC_ACT_* of a head dict: its optional "activation" (a Keras name), sigmoid without one"""
+    return ACTIVATIONS[resolve_activation(head.get("activation", "sigmoid"))]
+
+
 def _head_struct(head):
     return _lib.Head(float(head["w"]), float(head["b"]), float(head["gamma"]), float(head["beta"]),
                      float(head["mov_mean"]), float(head["mov_var"]))
@@ -313,8 +320,8 @@ def predict_pairs(U, A, head, user_idx, anime_idx):
     assert ui.numel() == ai.numel()
     p = torch.empty(ui.numel(), dtype=torch.float32, device=dev)
     h = _head_struct(head)
-    _lib.check(lib.anirec_predict_pairs(_lib.ptr(U), _lib.ptr(A), _lib.ptr(ui), _lib.ptr(ai),
-                                        int(ui.numel()), C.byref(h), _lib.ptr(p), _stream()),
+    _lib.check(lib.anirec_predict_pairs_act(_lib.ptr(U), _lib.ptr(A), _lib.ptr(ui), _lib.ptr(ai),
+                                            int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
                "anirec_predict_pairs")
     return p
 
@@ -329,8 +336,8 @@ def predict_grid(U, A, head, users):
     out = torch.empty(n_q, n_a, dtype=torch.float32, device=dev)
     ws = torch.empty(int(lib.anirec_predict_workspace_bytes(n_a, max(n_q, 1), 0)), dtype=torch.uint8, device=dev)
     h = _head_struct(head)
-    _lib.check(lib.anirec_predict_grid(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
-                                       _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
+    _lib.check(lib.anirec_predict_grid_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
+                                           _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
                "anirec_predict_grid")
     return out
 
@@ -346,8 +353,8 @@ def predict_grid_mfma(U, A, head, users, out=None):
         out = torch.empty(n_q, n_a, dtype=torch.float32, device=dev)
     ws = torch.empty(int(lib.anirec_predict_mfma_workspace_bytes(n_a, max(n_q, 1))), dtype=torch.uint8, device=dev)
     h = _head_struct(head)
-    _lib.check(lib.anirec_predict_grid_mfma(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
-                                            _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
+    _lib.check(lib.anirec_predict_grid_mfma_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
+                                                _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
                "anirec_predict_grid_mfma")
     return out
 
@@ -370,9 +377,9 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
         assert wb.shape == (n_q, (n_a + 31) // 32)
     ws = torch.empty(int(lib.anirec_predict_workspace_bytes(n_a, n_q, 1)), dtype=torch.uint8, device=dev)
     h = _head_struct(head)
-    _lib.check(lib.anirec_predict_topk(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
-                                       _lib.ptr(wb), int(k), _lib.ptr(out_i), _lib.ptr(out_p),
-                                       _lib.ptr(ws), ws.numel(), _stream()), "anirec_predict_topk")
+    _lib.check(lib.anirec_predict_topk_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
+                                           _head_act(head), _lib.ptr(wb), int(k), _lib.ptr(out_i), _lib.ptr(out_p),
+                                           _lib.ptr(ws), ws.numel(), _stream()), "anirec_predict_topk")
     return out_i, out_p
 
 
@@ -396,6 +403,7 @@ def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fal
         wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
         assert wb.shape == (n_q, (n_a + 31) // 32)
     h = _head_struct(head)
+    act = _head_act(head)
     bq = min(n_q, int(batch))
     ws = torch.empty(int(lib.anirec_predict_topk_mfma_workspace_bytes(n_a, bq)), dtype=torch.uint8, device=dev)
     flags = torch.empty(bq, dtype=torch.int32, device=dev)
@@ -403,10 +411,11 @@ def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fal
     for q0 in range(0, n_q, bq):
         cnt = min(bq, n_q - q0)
         wq = wb[q0:q0 + cnt] if wb is not None else None
-        _lib.check(lib.anirec_predict_topk_mfma(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us[q0:q0 + cnt]), cnt,
-                                                C.byref(h), _lib.ptr(wq), int(k), _lib.ptr(out_i[q0:q0 + cnt]),
-                                                _lib.ptr(out_p[q0:q0 + cnt]), _lib.ptr(flags), _lib.ptr(ws),
-                                                ws.numel(), _stream()), "anirec_predict_topk_mfma")
+        _lib.check(lib.anirec_predict_topk_mfma_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us[q0:q0 + cnt]), cnt,
+                                                    C.byref(h), act, _lib.ptr(wq), int(k),
+                                                    _lib.ptr(out_i[q0:q0 + cnt]), _lib.ptr(out_p[q0:q0 + cnt]),
+                                                    _lib.ptr(flags), _lib.ptr(ws), ws.numel(), _stream()),
+                   "anirec_predict_topk_mfma")
         bad = torch.nonzero(flags[:cnt], as_tuple=False).flatten()
         n_fb += int(bad.numel())
         if bad.numel() and fallback:

@@ -26,6 +26,52 @@ def resolve_optimizer(name):
     return key
 
 
+# output heads of the HIP train step: the Keras losses and output activations by canonical name, with the values of
+# anirec_train_desc.loss (ANIREC_LOSS_*) and .activation (ANIREC_ACT_*) — include/anirec.h states what each computes
+LOSSES = {"binary_crossentropy": 0, "mean_squared_error": 1, "mean_absolute_error": 2, "huber": 3, "log_cosh": 4}
+ACTIVATIONS = {"sigmoid": 0, "linear": 1, "tanh": 2, "relu": 3, "softplus": 4}
+# Dense(1) kernel initialisers (trainer.init_weights)
+INITIALIZERS = ("he_normal", "he_uniform", "glorot_normal", "glorot_uniform", "lecun_normal", "lecun_uniform",
+                "random_normal", "random_uniform", "truncated_normal", "zeros", "ones")
+
+# the other names tf.keras.losses.get / initializers.get resolve to the same objects (lower case): aliases and the
+# Keras class names
+_LOSS_NAMES = {"bce": "binary_crossentropy", "binarycrossentropy": "binary_crossentropy",
+               "mse": "mean_squared_error", "meansquarederror": "mean_squared_error",
+               "mae": "mean_absolute_error", "meanabsoluteerror": "mean_absolute_error",
+               "logcosh": "log_cosh"}
+_INIT_NAMES = {"henormal": "he_normal", "heuniform": "he_uniform", "glorotnormal": "glorot_normal",
+               "glorotuniform": "glorot_uniform", "lecunnormal": "lecun_normal", "lecununiform": "lecun_uniform",
+               "randomnormal": "random_normal", "randomuniform": "random_uniform",
+               "truncatednormal": "truncated_normal", "zeros": "zeros", "ones": "ones"}
+
+
+def _resolve(what, name, known, aliases):
+    key = str(name).lower()
+    key = aliases.get(key, key)
+    if key not in known:
+        raise ValueError("%s %r is not supported by the HIP train step (supported: %s)"
+                         % (what, name, ", ".join(sorted(known))))
+    return key
+
+
+def resolve_loss(name):
+    """Canonical Keras name of a loss the kernels implement (any case; aliases bce / mse / mae / logcosh and the class
+    names resolve too); ValueError, listing the supported set, for any other."""
+    return _resolve("loss", name, LOSSES, _LOSS_NAMES)
+
+
+def resolve_activation(name):
+    """Canonical name of an output activation the kernels implement (any case); ValueError for any other — selu, gelu
+    and swish among them: they are not monotone, which the top-k paths need."""
+    return _resolve("activation", name, ACTIVATIONS, {})
+
+
+def resolve_initializer(name):
+    """Canonical Keras name of a Dense kernel initialiser ``trainer.init_weights`` draws (any case, class names too)."""
+    return _resolve("kernel_initializer", name, INITIALIZERS, _INIT_NAMES)
+
+
 def lrfn(epoch, start_lr=1e-5, max_lr=5e-5, min_lr=1e-5, rampup_epochs=5, sustain_epochs=0,
          exp_decay=0.8):
     """Learning rate of ``epoch`` (0-based): linear ramp start->max over ``rampup_epochs``,

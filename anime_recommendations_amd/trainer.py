@@ -39,6 +39,9 @@ class FitConfig:
     use_graph: bool = True
     arena_steps: int = 64
     optimizer: str = "adam"          # config.yaml model.optimizer: adam, sgd, rmsprop, adagrad (any case)
+    loss: str = "binary_crossentropy"        # config.yaml model.model_loss (schedule.LOSSES, any case / alias)
+    activation: str = "sigmoid"              # config.yaml model.activation_function (schedule.ACTIVATIONS)
+    kernel_initializer: str = "he_normal"    # config.yaml model.kernel_initializer (schedule.INITIALIZERS)
 
     def lr(self, epoch):
         return schedule.lrfn(epoch, self.start_lr, self.max_lr, self.min_lr, self.rampup_epochs,
@@ -58,21 +61,46 @@ class FitResult:
     stopped_epoch: int = -1
     optimizer: dict = field(default_factory=dict)
     optimizer_name: str = "adam"     # whose slots ``optimizer`` holds (weights_io.save_model's optimizer_name)
+    loss: str = "binary_crossentropy"    # the head the model was trained with (canonical names)
+    activation: str = "sigmoid"
     step_loop_seconds: list = field(default_factory=list)   # per epoch: wall time of the step loop alone (synchronised)
     epoch_seconds: list = field(default_factory=list)       # per epoch: shuffle + steps + metrics + validation + snapshot
 
 
-def init_weights(n_users, n_anime, dim=128, seed=0):
-    """Keras initialisers at the reference's call sites: Embedding 'uniform' = U(-0.05, 0.05)
-    (neural_network.py:75-85); Dense(1, he_normal) = truncated normal, stddev
-    sqrt(2/fan_in)/0.87962566103423978 with fan_in = 1, cut at 2 stddev (neural_network.py:97)."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    U = rng.uniform(-0.05, 0.05, (n_users, dim)).astype(np.float32)
-    A = rng.uniform(-0.05, 0.05, (n_anime, dim)).astype(np.float32)
-    std = np.sqrt(2.0 / 1.0) / 0.87962566103423978
+def _truncated_normal(rng, std):
+    """N(0, std) cut at 2 stddev by redrawing (Keras' truncated normal)"""
     w = rng.normal(0.0, std)
     while abs(w) > 2 * std:
         w = rng.normal(0.0, std)
+    return w
+
+
+def init_weights(n_users, n_anime, dim=128, seed=0, initializer="he_normal"):
+    """Keras initialisers at the reference's call sites: Embedding 'uniform' = U(-0.05, 0.05)
+    (neural_network.py:75-85); Dense(1, kernel_initializer) with fan_in = fan_out = 1 (neural_network.py:97):
+    he_normal (the default) = truncated normal, stddev sqrt(2/fan_in)/0.87962566103423978, cut at 2 stddev;
+    he_uniform U(+-sqrt(6)); glorot_normal / lecun_normal the truncated normal of scale 1; glorot_uniform /
+    lecun_uniform U(+-sqrt(3)); random_normal N(0, 0.05); random_uniform U(+-0.05); truncated_normal stddev 0.05
+    cut at 2 stddev; zeros; ones.  Every draw comes from the one PCG64 stream, after the tables."""
+    kind = schedule.resolve_initializer(initializer)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    U = rng.uniform(-0.05, 0.05, (n_users, dim)).astype(np.float32)
+    A = rng.uniform(-0.05, 0.05, (n_anime, dim)).astype(np.float32)
+    fan = 1.0
+    if kind in ("he_normal", "glorot_normal", "lecun_normal"):    # VarianceScaling(truncated_normal)
+        scale = 2.0 if kind == "he_normal" else 1.0
+        w = _truncated_normal(rng, np.sqrt(scale / fan) / 0.87962566103423978)
+    elif kind in ("he_uniform", "glorot_uniform", "lecun_uniform"):   # VarianceScaling(uniform)
+        lim = np.sqrt(3.0 * (2.0 if kind == "he_uniform" else 1.0) / fan)
+        w = rng.uniform(-lim, lim)
+    elif kind == "random_normal":
+        w = rng.normal(0.0, 0.05)
+    elif kind == "random_uniform":
+        w = rng.uniform(-0.05, 0.05)
+    elif kind == "truncated_normal":
+        w = _truncated_normal(rng, 0.05)
+    else:
+        w = 0.0 if kind == "zeros" else 1.0
     return U, A, float(np.float32(w))
 
 
@@ -99,17 +127,23 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     if cfg.embedding_size != 128:
         raise ValueError("libanirec kernels are specialised for embedding_size 128 (config.yaml:63)")
     kind = schedule.resolve_optimizer(cfg.optimizer)
+    loss_name, act_name = schedule.resolve_loss(cfg.loss), schedule.resolve_activation(cfg.activation)
     tr, te = table.split(cfg.test_size)
     n_train = tr.stop - tr.start
     if engine is None:
         from .engine import TrainEngine
         engine = TrainEngine(table.n_users, table.n_anime, max_batch=min(cfg.batch_size, n_train),
-                             l2=cfg.l2_reg_factor, arena_steps=cfg.arena_steps, device=device, optimizer=kind)
+                             l2=cfg.l2_reg_factor, arena_steps=cfg.arena_steps, device=device, optimizer=kind,
+                             loss=loss_name, activation=act_name)
     elif getattr(engine, "optimizer", "adam") != kind:
         raise ValueError("the engine was built for optimizer %r, the config asks for %r"
                          % (getattr(engine, "optimizer", "adam"), kind))
+    for what, want, default in (("loss", loss_name, "binary_crossentropy"), ("activation", act_name, "sigmoid")):
+        have = getattr(engine, what, default)
+        if have != want:
+            raise ValueError("the engine was built for %s %r, the config asks for %r" % (what, have, want))
     dev = engine.device
-    U0, A0, w0 = init_weights(table.n_users, table.n_anime, 128, cfg.seed)
+    U0, A0, w0 = init_weights(table.n_users, table.n_anime, 128, cfg.seed, cfg.kernel_initializer)
     engine.set_head(w=w0)
     engine.set_weights(U0, A0)
     engine.reset_optimizer()
@@ -182,7 +216,7 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     rec = engine.read_state()
     res = FitResult(history=hist, U=engine.U.cpu().numpy().copy(), A=engine.A.cpu().numpy().copy(),
                     head=head_of(rec), best_epoch=best_epoch, stopped_epoch=stopped, step_loop_seconds=loop_s,
-                    epoch_seconds=epoch_s, optimizer_name=kind)
+                    epoch_seconds=epoch_s, optimizer_name=kind, loss=loss_name, activation=act_name)
     if hasattr(engine, "optimizer_state"):       # optimiser slots and the step count of the LAST epoch (model.save)
         res.optimizer = engine.optimizer_state(iterations=t_global)
     if best_w is not None:

@@ -77,6 +77,39 @@ enum {
   ANIREC_OPT_ADAGRAD = 3
 };
 
+/* Output head of the model (anirec_train_desc::loss / ::activation; the predict entry points' `activation`): Keras 2.12's
+ * losses and output activations that model.compile(loss=...) and Activation(...) resolve by name (neural_network.py:
+ * 97-104).  y = BatchNorm output, p = act(y), t = scaled rating, e = p - t, B = global batch; the data loss is
+ * sum_i l(p_i, t_i) / B and dy_i = l'(p_i, t_i) * act'(y_i) / B (Keras SUM_OVER_BATCH_SIZE).
+ *   ACT_SIGMOID   sigmoid(y)                            act' = p(1-p)
+ *   ACT_LINEAR    y                                     1
+ *   ACT_TANH      tanh(y)                               1 - p^2
+ *   ACT_RELU      max(y, 0)                             y > 0 ? 1 : 0
+ *   ACT_SOFTPLUS  max(y,0) + log1p(exp(-|y|))           sigmoid(y)
+ *   LOSS_BCE      with ACT_SIGMOID: from logits, max(y,0) - y t + log1p(exp(-|y|)), dy = (p - t)/B;
+ *                 else q = clip(p, 1e-7, 1-1e-7): -(t log(q+1e-7) + (1-t) log(1-q+1e-7)), gradient through q
+ *                 (0 outside the closed clip interval)
+ *   LOSS_MSE      e^2                                   2e
+ *   LOSS_MAE      |e|                                   sign(e), 0 at 0
+ *   LOSS_HUBER    |e| <= 1 ? e^2/2 : |e| - 1/2          |e| <= 1 ? e : sign(e)
+ *   LOSS_LOGCOSH  e + softplus(-2e) - log 2             1 - 2 sigmoid(-2e)
+ * Every activation is non-decreasing: the top-k paths rank by the cosine and re-score through the head.  0, 0 is the
+ * reference's default model (sigmoid + binary_crossentropy). */
+enum {
+  ANIREC_LOSS_BCE = 0,
+  ANIREC_LOSS_MSE = 1,
+  ANIREC_LOSS_MAE = 2,
+  ANIREC_LOSS_HUBER = 3,
+  ANIREC_LOSS_LOGCOSH = 4
+};
+enum {
+  ANIREC_ACT_SIGMOID = 0,
+  ANIREC_ACT_LINEAR = 1,
+  ANIREC_ACT_TANH = 2,
+  ANIREC_ACT_RELU = 3,
+  ANIREC_ACT_SOFTPLUS = 4
+};
+
 /* One optimiser step of the schedule.  `alpha` is Adam's bias-corrected step size
  * lr*sqrt(1-b2^t)/(1-b1^t) for this step, or `lr` for the other kinds, computed on the host from lrfn(epoch)
  * (neural_network.py:109-125) so host and oracle agree bit-for-bit. */
@@ -104,11 +137,12 @@ typedef struct anirec_state {
   double se_sum;      /* sum of squared errors (mse numerator) */
   double n_seen;      /* ratings seen */
   /* validation accumulators, BN inference mode (neural_network.py:216) */
-  double val_bce_sum; /* sum of per-row BCE */
+  double val_bce_sum; /* sum of per-row data loss (BCE by default; the descriptor's loss) */
   double val_se_sum;
   double val_n;
   /* the same epoch loss split for user-partitioned multi-GPU runs: the caller adds the
-   * other ranks' user-table terms.  sums over steps of count * {bce, sum(U_local^2), sum(A^2)} */
+   * other ranks' user-table terms.  sums over steps of count * {bce, sum(U_local^2), sum(A^2)}; bce = the data term of
+   * the descriptor's loss */
   double bce_wsum, reg_user_wsum, reg_anime_wsum;
   float reg_user_sumsq, reg_anime_sumsq; /* split of reg_sumsq */
 } anirec_state;
@@ -145,7 +179,7 @@ typedef struct anirec_train_desc {
   const float *rating;
   const anirec_step *sched; /* [n_steps] */
   int32_t n_steps;
-  int32_t pad2;
+  int32_t loss;         /* ANIREC_LOSS_*: the data loss of the head stage and of anirec_eval (0 = binary_crossentropy) */
   /* head packets: n_seg packets of anirec_packet_floats(max_batch) floats each; packet
    * my_seg is written by the fwd kernel, the others by the caller's all-gather. */
   float *packets;
@@ -155,7 +189,11 @@ typedef struct anirec_train_desc {
   void *lazy_state;     /* lazy != 0: anirec_train_lazy_bytes(rows) bytes, zero before first use; else NULL */
   int32_t optimizer;    /* ANIREC_OPT_*: the update rule of the adam stage.  The lazy update exists for ADAM only: a
                            descriptor with lazy != 0 and another kind is rejected (ANIREC_EINVAL) by every call */
+  int32_t activation;   /* ANIREC_ACT_*: the output activation (0 = sigmoid).  loss / activation out of range: every call
+                           that takes the descriptor returns ANIREC_EINVAL before it enqueues anything */
 } anirec_train_desc;
+/* A descriptor must be zero-initialised before its fields are set: fields added in the struct's former padding (loss,
+ * activation) then read 0, the reference's default model. */
 
 /* floats in one head packet: c[pcap], t[pcap], 4 ints {count,0,0,0}; pcap = max_batch rounded
  * up to a multiple of 4 */
@@ -177,7 +215,7 @@ int anirec_train_prep(const anirec_train_desc *d, int32_t first_step, int32_t n_
  * state->step_bwd / a workspace word head publishes) so that a captured graph can be replayed for every step;
  * the per-step scratch is double-buffered by step parity:
  *   fwd  : gather U[ui], A[ai]; c = <l2n(u), l2n(a)>      -> packet, su, sa
- *   head : Dense(1) + BatchNorm(batch stats over ALL packets) + sigmoid + BCE,
+ *   head : Dense(1) + BatchNorm(batch stats over ALL packets) + the activation and loss of the descriptor,
  *          d loss / d y per rating and the batch partial sums
  *   bwd  : closed-form backward to d loss / d c, per-chunk weighted row sums of the OTHER
  *          table -> chunk partials (+rowmap)
@@ -272,7 +310,8 @@ int anirec_trainer_run(anirec_trainer *t, int32_t first_step, int32_t n_steps, i
                        void *stream);
 
 /* Validation pass on n rows (BN inference, moving stats): accumulates
- * state->val_* ; val_loss = val_bce_sum/val_n + l2*reg_sumsq  (neural_network.py:216). */
+ * state->val_* ; val_loss = val_bce_sum/val_n + l2*reg_sumsq  (neural_network.py:216).  val_bce_sum and the state's
+ * bce_wsum carry the data term of the descriptor's loss (the name is historical). */
 int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32_t *anime_idx,
                 const float *rating, int32_t n, void *stream);
 
@@ -385,7 +424,9 @@ int anirec_topk_mfma_timing(int32_t enable, float *cand_ms, int32_t *launches);
  *  PREDICTION — replaces model.predict([user_arr, anime_arr]), model_recs/model_recs.py:394
  * ------------------------------------------------------------------------- */
 
-/* Inference head: sigmoid(gamma*(w*c+b-mov_mean)/sqrt(mov_var+1e-3)+beta). */
+/* Inference head: act(gamma*(w*c+b-mov_mean)/sqrt(mov_var+1e-3)+beta); the five entry points below without an
+ * `activation` argument use ANIREC_ACT_SIGMOID, each *_act variant takes ANIREC_ACT_* (ANIREC_EINVAL out of range,
+ * before anything is enqueued). */
 typedef struct anirec_head {
   float w, b, gamma, beta, mov_mean, mov_var;
 } anirec_head;
@@ -395,6 +436,10 @@ int anirec_predict_pairs(const float *U, const float *A, const int32_t *user_idx
                          const int32_t *anime_idx, int32_t n, const anirec_head *head_host,
                          float *p, void *stream);
 
+int anirec_predict_pairs_act(const float *U, const float *A, const int32_t *user_idx,
+                             const int32_t *anime_idx, int32_t n, const anirec_head *head_host,
+                             int32_t activation, float *p, void *stream);
+
 /* Workspace of predict_grid / predict_topk: l2-normalised copies of A and of the query
  * users (+ a batch of rating rows when topk != 0). */
 size_t anirec_predict_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t topk);
@@ -403,6 +448,9 @@ size_t anirec_predict_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t 
 int anirec_predict_grid(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                         int32_t n_users, const anirec_head *head_host, float *out,
                         void *workspace, size_t workspace_bytes, void *stream);
+int anirec_predict_grid_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                            int32_t n_users, const anirec_head *head_host, int32_t activation, float *out,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* The same grid on the matrix cores: rows are split x = hi + lo in fp16 and accumulated as
  * hi*hi + hi*lo + lo*hi by v_mfma_f32_32x32x16_f16 (ratings within 1e-5 of the fp32 path). */
@@ -410,6 +458,10 @@ size_t anirec_predict_mfma_workspace_bytes(int32_t n_anime, int32_t n_users);
 int anirec_predict_grid_mfma(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                              int32_t n_users, const anirec_head *head_host, float *out,
                              void *workspace, size_t workspace_bytes, void *stream);
+/* the epilogue of each activation is a fast form (hardware exp2 / log2 / rcp) within 1e-5 of the exact path */
+int anirec_predict_grid_mfma_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                                 int32_t n_users, const anirec_head *head_host, int32_t activation, float *out,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* Per query user: top-k anime by descending predicted rating among anime whose
  * watched bit is clear.  watched: optional [n_users][ceil(n_anime/32)] bitmask words.
@@ -418,6 +470,10 @@ int anirec_predict_topk(const float *U, const float *A, int32_t n_anime, const i
                         int32_t n_users, const anirec_head *head_host, const uint32_t *watched,
                         int32_t k, int32_t *out_idx, float *out_p, void *workspace,
                         size_t workspace_bytes, void *stream);
+int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                            int32_t n_users, const anirec_head *head_host, int32_t activation,
+                            const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                            size_t workspace_bytes, void *stream);
 
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
@@ -430,6 +486,13 @@ int anirec_predict_topk_mfma(const float *U, const float *A, int32_t n_anime, co
                              int32_t n_users, const anirec_head *head_host, const uint32_t *watched,
                              int32_t k, int32_t *out_idx, float *out_p, int32_t *flags, void *workspace,
                              size_t workspace_bytes, void *stream);
+/* Any activation: the ratings are non-decreasing in sign * cosine, so the same proof holds; a row whose k-th survivor
+ * does not lie STRICTLY above the best rating a non-survivor could reach (flat regions: relu at y <= 0, softplus
+ * underflowing to 0, saturated sigmoid / tanh) is flagged and falls back to the exact path. */
+int anirec_predict_topk_mfma_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                                 int32_t n_users, const anirec_head *head_host, int32_t activation,
+                                 const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, int32_t *flags,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------- *
  *  INGEST — the step before the hot path, columns resident in HBM.

@@ -40,8 +40,8 @@ def go(args):
     user_ids, anime_ids = C.index_tables(model, df)
     user = select_user(args, df)
     logger.info("Using %s as input user", user)
-    frame = C.model_recs_frame(model["U"], model["A"], model["head"], user_ids, anime_ids, df, anime_df, syn_df,
-                               user, int(args.model_num_recs),
+    frame = C.model_recs_frame(model["U"], model["A"], weights_io.model_head(model), user_ids, anime_ids, df,
+                               anime_df, syn_df, user, int(args.model_num_recs),
                                types=C.literal(args.anime_types) if args.specify_types else None,
                                genres=C.literal(args.model_genres) if args.specify_genres else None)
     fn = "User_ID_" + str(user) + "_" + args.model_recs_fn

@@ -29,13 +29,11 @@ logger = C.setup_logging("neural_network")
 
 def go(args):
     from anime_recommendations_amd import data, ingest, schedule, trainer, weights_io
-    # the graph is fixed by the kernels: reject configurations they do not implement
-    optimizer = schedule.resolve_optimizer(args.optimizer)     # Keras name, any case: adam, sgd, rmsprop, adagrad
-    for flag, want in (("model_loss", "binary_crossentropy"),
-                       ("activation_function", "sigmoid"), ("kernel_initializer", "he_normal")):
-        if str(getattr(args, flag)).lower() != want:
-            raise ValueError("--%s %r is not supported by the HIP train step (only %r)"
-                             % (flag, getattr(args, flag), want))
+    # Keras names, any case; a configuration the kernels do not implement is a ValueError listing what they do
+    optimizer = schedule.resolve_optimizer(args.optimizer)     # adam, sgd, rmsprop, adagrad
+    loss = schedule.resolve_loss(args.model_loss)              # binary_crossentropy, mse, mae, huber, log_cosh
+    activation = schedule.resolve_activation(args.activation_function)   # sigmoid, linear, tanh, relu, softplus
+    initializer = schedule.resolve_initializer(args.kernel_initializer)
     if args.TPU_INIT:
         logger.info("TPU_INIT requested: ignored, training runs on MI355X (use torchrun for >1 GPU)")
     logger.info("Loading data artifact %s", args.input_data)
@@ -58,7 +56,8 @@ def go(args):
         start_lr=float(args.start_lr), min_lr=float(args.min_lr), max_lr=float(args.max_lr),
         rampup_epochs=int(args.rampup_epochs), sustain_epochs=int(args.sustain_epochs),
         exp_decay=float(args.exp_decay), monitor=args.checkpoint_metric, mode=args.mode,
-        verbose=int(args.verbose), seed=int(os.environ.get("ANIREC_SEED", "0")), optimizer=optimizer)
+        verbose=int(args.verbose), seed=int(os.environ.get("ANIREC_SEED", "0")), optimizer=optimizer, loss=loss,
+        activation=activation, kernel_initializer=initializer)
     # >1 rank: ratings sharded by user over RCCL.  The reference's TPU branch (neural_network.py:173-178)
     # computes batch_size * replicas and max_lr * replicas but never uses them: model.fit gets
     # args.batch_size (:213) and lrfn reads args.max_lr (:113), so the GLOBAL batch and the schedule are
@@ -84,7 +83,8 @@ def go(args):
                                  "ANIREC_WEAK_SCALING=1 for batch_size ratings PER rank)" % (cfg.batch_size, world))
             per_rank = cfg.batch_size // world
         engine = DistTrainEngine(table.n_users, table.n_anime, min(per_rank, max(1, n_train // world)),
-                                 l2=cfg.l2_reg_factor, device="cuda:%d" % local, optimizer=optimizer)
+                                 l2=cfg.l2_reg_factor, device="cuda:%d" % local, optimizer=optimizer, loss=loss,
+                                 activation=activation)
         if rank != 0:
             cfg.verbose = 0
     res = trainer.fit(table, cfg, engine=engine, log=lambda s: (print(s), logger.info(s)))
@@ -98,12 +98,13 @@ def go(args):
     # ModelCheckpoint(filepath=weights_artifact, save_best_only): the best-val_loss weights
     wpath = stem(args.weights_artifact)
     bU, bA, bh = (res.best_U, res.best_A, res.best_head) if res.best_U is not None else (res.U, res.A, res.head)
-    weights_io.save_model(wpath, bU, bA, bh, table.user_ids, table.anime_ids, args.ID_emb_name, args.anime_emb_name)
+    weights_io.save_model(wpath, bU, bA, bh, table.user_ids, table.anime_ids, args.ID_emb_name, args.anime_emb_name,
+                          activation=res.activation, loss=res.loss)
     mpath = stem(args.model_name)
     if args.save_model:
         weights_io.save_model(mpath, res.U, res.A, res.head, table.user_ids, table.anime_ids,
                               args.ID_emb_name, args.anime_emb_name, optimizer=res.optimizer,
-                              optimizer_name=res.optimizer_name,
+                              optimizer_name=res.optimizer_name, activation=res.activation, loss=res.loss,
                               extra={"best_epoch": res.best_epoch, "stopped_epoch": res.stopped_epoch})
     hist = trainer.history_frame(res.history)
     with open("history.json", "w") as f:
