@@ -30,7 +30,36 @@ def _problem():
     return U, A, ui, ai, t, rng.permutation(n)
 
 
-def _worker(rank, world, port, out_dir, mode="sharded", backend="gloo", lazy=None):
+def _skewed_problem():
+    """11 global batches of 128 (64 per rank; the last one 37) whose user shares are chosen: batch 3 lies on rank 0's
+    (even) users only, so rank 1 steps with 0 ratings; batch 6 gives rank 1 exactly one rating; the last batch lies on
+    rank 1's users only.  The others split 64 / 64."""
+    rng = np.random.default_rng(22)
+    n_u, n_a, Bg = 3001, 700, 128
+    counts = [Bg] * 10 + [37]
+    odd = {3: 0, 6: 1, 10: 37}                     # ratings on rank 1's users, per batch
+    uo = []
+    for k, c in enumerate(counts):
+        n1 = odd.get(k, c // 2)
+        u = np.concatenate([2 * rng.integers(0, (n_u + 1) // 2, c - n1), 2 * rng.integers(0, n_u // 2, n1) + 1])
+        uo.append(rng.permutation(u))
+    uo = np.concatenate(uo)
+    n = len(uo)
+    U = rng.uniform(-0.05, 0.05, (n_u, 128)).astype(np.float32)
+    A = rng.uniform(-0.05, 0.05, (n_a, 128)).astype(np.float32)
+    perm = rng.permutation(n)
+    ui = np.empty(n, np.int64)
+    ui[perm] = uo                                  # ui[perm[k Bg:(k + 1) Bg]] is batch k
+    ai = (rng.zipf(1.15, n) - 1) % n_a
+    t = (rng.integers(0, 11, n) / 10).astype(np.float32)
+    return U, A, ui, ai, t, perm
+
+
+# problem name -> (problem, ratings per rank per step)
+_PROBLEMS = {"uniform": (_problem, 1000), "skewed": (_skewed_problem, 64)}
+
+
+def _worker(rank, world, port, out_dir, mode="sharded", backend="gloo", lazy=None, problem="uniform"):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
     dev = torch.device("cuda:%d" % (rank if backend == "nccl" else 0))
     if backend == "nccl":
@@ -41,13 +70,14 @@ def _worker(rank, world, port, out_dir, mode="sharded", backend="gloo", lazy=Non
     try:
         from anime_recommendations_amd import schedule
         from anime_recommendations_amd.dist import DistTrainEngine
-        U, A, ui, ai, t, perm = _problem()
-        eng = DistTrainEngine(U.shape[0], A.shape[0], 1000, l2=1e-4, arena_steps=4, device=dev, mode=mode, lazy=lazy)
+        make, bpr = _PROBLEMS[problem]
+        U, A, ui, ai, t, perm = make()
+        eng = DistTrainEngine(U.shape[0], A.shape[0], bpr, l2=1e-4, arena_steps=4, device=dev, mode=mode, lazy=lazy)
         assert eng.eng.lazy == bool(lazy)
         eng.set_head(w=1.2)
         eng.set_weights(U, A)
         tu, ta, tt, tp = (torch.from_numpy(np.asarray(x)).to(dev) for x in (ui, ai, t, perm))
-        n_steps = (len(perm) + 1999) // 2000
+        n_steps = (len(perm) + 2 * bpr - 1) // (2 * bpr)
         eng.set_epoch_global(tu, ta, tt, tp, schedule.adam_alphas(3e-5, 1, n_steps))
         eng.reset_metrics()
         eng.run(n_steps)
@@ -80,11 +110,12 @@ def _port():
     return port
 
 
-def _check_against_oracle(tmp_path):
+def _check_against_oracle(tmp_path, problem="uniform"):
     d = np.load(tmp_path / "dist.npz")
-    U, A, ui, ai, t, perm = _problem()
+    make, bpr = _PROBLEMS[problem]
+    U, A, ui, ai, t, perm = make()
     st = orc.new_state(U, A, orc.new_head(w=1.2))
-    lr, Bg = 3e-5, 2000
+    lr, Bg = 3e-5, 2 * bpr
     losses, ns = [], []
     for k in range(0, len(perm), Bg):
         g = perm[k:k + Bg]
@@ -123,6 +154,21 @@ def test_two_ranks_on_one_gpu_match_oracle_on_global_batches(tmp_path, mode):
     m, lazy = _mode_args(mode)
     mp.spawn(_worker, args=(2, _port(), str(tmp_path), m, "gloo", lazy), nprocs=2, join=True)
     _check_against_oracle(tmp_path)
+
+
+@pytest.mark.parametrize("mode", ["sharded", "sharded-lazy"])
+def test_two_ranks_with_empty_and_single_rating_shares_match_oracle(tmp_path, mode):
+    """The user-sharded step when a rank's share of a global batch is 0 or 1 rating: its k_seg_stats packet is empty
+    (count 0, mean 0) or one z, and the all-gathered BatchNorm must still take the global batch's statistics."""
+    from anime_recommendations_amd.dist import batch_slack
+    U, A, ui, ai, t, perm = _skewed_problem()
+    Bg = 2 * _PROBLEMS["skewed"][1]
+    shares = [np.bincount(ui[perm[k:k + Bg]] % 2, minlength=2) for k in range(0, len(perm), Bg)]
+    assert [list(shares[k]) for k in (3, 6, 10)] == [[128, 0], [127, 1], [0, 37]]
+    assert max(x.max() for x in shares) <= batch_slack(Bg // 2)       # every share fits a rank's max_batch
+    m, lazy = _mode_args(mode)
+    mp.spawn(_worker, args=(2, _port(), str(tmp_path), m, "gloo", lazy, "skewed"), nprocs=2, join=True)
+    _check_against_oracle(tmp_path, "skewed")
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="RCCL needs one GPU per rank: two GPUs")

@@ -1,0 +1,410 @@
+"""The train step against the oracle at the kernels' own limits: batches of 1 and of ANIREC_MAX_BATCH, ragged counts
+around the 4-rating packet rounding, the wave and the 256-rating head block; a BatchNorm whose batch variance is 0; sort
+keys at the radix pass boundaries (one, two and three digit passes, a one-row table); every rating of a batch on one
+user or one anime row (segments of up to 512 chunks); the lazy dense Adam against the oracle, not only against the
+dense update.  Every case runs with the dense update (eager) and the lazy one (graph blocks): both match the oracle,
+and the two are bit-identical on W, M and V.  Then the other optimizers and heads, validation and predict at odd
+counts.
+
+The oracle is oracle.anirec_oracle.train_step in fp32 (tests/test_train_gpu.py's bars).  Where fp32 summation order
+alone moves a result by more than those bars, the check is against the oracle run in fp64: the kernel's distance from
+it may be at most a small multiple of the fp32 oracle's own distance, plus a floor (`_near_fp64`)."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import optim_restatement as optr
+import test_heads_cpu as heads
+from oracle import anirec_oracle as orc
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+LR = 3e-5
+
+
+# ---- the cases ------------------------------------------------------------------------------------------------
+def _tables(rng, n_u, n_a):
+    U = rng.uniform(-0.05, 0.05, (n_u, 128)).astype(f32)
+    A = rng.uniform(-0.05, 0.05, (n_a, 128)).astype(f32)
+    return U, A
+
+
+def _zipf(rng, n, n_a, s):
+    return ((rng.zipf(s, n) - 1) % n_a).astype(np.int64)
+
+
+def _single(rng):
+    U, A = _tables(rng, 50, 20)
+    ui = np.array([7, 3, 41])
+    ai = np.array([0, 19, 5])
+    U[3] = 0.0                                       # a zero user row: l2_normalize clamps, its gradient path is gated
+    return U, A, ui, ai
+
+
+def _tiny_ragged(rng):
+    U, A = _tables(rng, 300, 257)
+    n = 257 + 1 + 3 + 63 + 64 + 65 + 255 + 256
+    return U, A, rng.integers(0, 300, n), _zipf(rng, n, 257, 1.2)
+
+
+def _capacity(rng):
+    U, A = _tables(rng, 20000, 900)
+    n = 16384 + 16383 + 9999 + 1
+    return U, A, rng.integers(0, 20000, n), _zipf(rng, n, 900, 1.05)
+
+
+def _one_user(rng):
+    U, A = _tables(rng, 5000, 700)
+    n = 16384 + 4097                                 # 512 chunks, then 128 chunks + a chunk of one rating
+    return U, A, np.full(n, 4321), rng.integers(0, 700, n)
+
+
+def _one_anime(rng):
+    U, A = _tables(rng, 5000, 1)
+    n = 4096 + 4096 + 17
+    return U, A, rng.integers(0, 5000, n), np.zeros(n, np.int64)
+
+
+def _flat_bn(rng):
+    U, A = _tables(rng, 400, 300)
+    n = 1024 + 513
+    # the pair's rows are kept away from 0: their data gradient is rounding noise (every z is equal, so the BatchNorm
+    # backward cancels it), and an element whose L2 gradient is of that size would take a noise-signed Adam step
+    for W, r in ((U, 17), (A, 123)):
+        W[r] = np.sign(W[r] + 1e-9) * rng.uniform(0.02, 0.05, 128).astype(f32)
+    return U, A, np.full(n, 17), np.full(n, 123)
+
+
+def _edge_keys(rng, n, n_rows):
+    k = rng.integers(0, n_rows, n)
+    edges = np.array([e for e in (0, 255, 256, 65535, 65536) if e < n_rows] + [n_rows - 1])
+    pos = rng.choice(n, 64 * len(edges), replace=False)
+    k[pos] = np.repeat(edges, 64)
+    return k
+
+
+def _pass_edges_users(rng):                          # 17-bit user keys (3 passes), 8-bit anime keys (1 pass)
+    U, A = _tables(rng, 65537, 256)
+    n = 3 * 2048 + 1
+    ui, ai = _edge_keys(rng, n, 65537), _edge_keys(rng, n, 256)
+    ui[-1], ai[-1] = 65536, 255
+    return U, A, ui, ai
+
+
+def _pass_edges_anime(rng):
+    U, A = _tables(rng, 256, 65537)
+    n = 3 * 2048 + 1
+    ui, ai = _edge_keys(rng, n, 256), _edge_keys(rng, n, 65537)
+    ui[-1], ai[-1] = 0, 65536
+    return U, A, ui, ai
+
+
+def _headline(rng):
+    U, A = _tables(rng, 140000, 2000)
+    n = 10 * 16384 + 1
+    return U, A, rng.integers(0, 140000, n), _zipf(rng, n, 2000, 1.1)
+
+
+# name: (problem, max_batch, per-step counts, head).  `capacity` puts the Dense bias at 4, so that z = w c + b has a
+# mean 40 times its spread: a batch variance taken as E[z^2] - E[z]^2 in fp32 is off by ~2e-4 of itself there (2.5e-6,
+# 25 times the per-step bar on bn_var).
+CASES = {
+    "single": (_single, 1, [1, 1, 1], {}),
+    "tiny_ragged": (_tiny_ragged, 257, [257, 1, 3, 63, 64, 65, 255, 256], {}),
+    "capacity": (_capacity, 16384, [16384, 16383, 9999, 1], dict(b=4.0)),
+    "one_user": (_one_user, 16384, [16384, 4097], {}),
+    "one_anime": (_one_anime, 4096, [4096, 4096, 17], {}),
+    "flat_bn": (_flat_bn, 1024, [1024, 513], {}),
+    "pass_edges_users": (_pass_edges_users, 2048, [2048] * 3 + [1], {}),
+    "pass_edges_anime": (_pass_edges_anime, 2048, [2048] * 3 + [1], {}),
+    # a full lazy window of 8 steps, then 3 more (the last a single rating); 142 000 rows >= 8 x 16 384 picks the lazy
+    # update on its own
+    "headline_lazy": (_headline, 16384, [16384] * 10 + [1], {}),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    make, B, counts, head = CASES[name]
+    rng = np.random.default_rng(sum(map(ord, name)))
+    U, A, ui, ai = make(rng)
+    counts = np.asarray(counts)
+    assert len(ui) == len(ai) == counts.sum() and counts.max() <= B
+    t = (rng.integers(0, 11, len(ui)) / 10).astype(f32)
+    starts = np.cumsum(counts) - counts
+    hd = dict(dict(w=1.2), **head)
+    return U, A, ui.astype(np.int64), ai.astype(np.int64), t, B, starts, counts, hd
+
+
+def _batches(name):
+    U, A, ui, ai, t, B, starts, counts, hd = _case(name)
+    return [(ui[s:s + c], ai[s:s + c], t[s:s + c]) for s, c in zip(starts, counts)]
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(name, dtype=f32):
+    """(final state, per-step metrics) of orc.train_step on the case's batches"""
+    U, A, ui, ai, t, B, starts, counts, hd = _case(name)
+    st = orc.new_state(U.astype(dtype), A.astype(dtype), orc.new_head(**hd))
+    if dtype is not f32:
+        st["head"] = {k: np.asarray(v, dtype) if np.ndim(v) else dtype(v) for k, v in st["head"].items()}
+    mets = []
+    for u, a, r in _batches(name):
+        b_in = float(st["head"]["b"])              # the Dense bias the step's z = w c + b is taken with
+        mets.append(dict(orc.train_step(st, u, a, r, LR, dtype=dtype)[0], b_in=b_in))
+    return st, mets
+
+
+def _engine(name, lazy, **kw):
+    from anime_recommendations_amd.engine import TrainEngine
+    U, A, ui, ai, t, B, starts, counts, hd = _case(name)
+    eng = TrainEngine(U.shape[0], A.shape[0], max_batch=B, arena_steps=8, lazy=lazy, **kw)
+    assert eng.lazy == bool(lazy)
+    eng.set_head(**hd)
+    eng.set_weights(U, A)
+    eng.reset_optimizer()
+    return eng
+
+
+def _near_fp64(got, o32, o64, k, floor, what):
+    """|got - fp64| <= k * max|fp32 oracle - fp64| + floor, elementwise on the worst element"""
+    o64 = np.asarray(o64, np.float64)
+    d_got = float(np.max(np.abs(np.asarray(got, np.float64) - o64)))
+    d_ora = float(np.max(np.abs(np.asarray(o32, np.float64) - o64)))
+    assert d_got <= k * d_ora + floor, (what, d_got, d_ora, floor)
+
+
+# ---- 1. the Adam step at the edges, dense and lazy ------------------------------------------------------------
+# flat_bn: the rows of the repeated pair take a data gradient that is pure rounding noise (BatchNorm's backward
+# subtracts the batch mean of dz, and every z is the same); there the fp32 oracle itself is 2.8e-7 from the fp64 one in
+# W (the bar is 1.2e-7) and 1.5-3.3 % in M and V.  Those two rows are held to the fp64 oracle (`_near_fp64`), every
+# other row to the bars.
+NOISY_ROWS = {"flat_bn": (17, 123)}
+# the multiple of the fp32 oracle's own distance from fp64 that the kernel may reach on those rows: its chunked sums
+# (32 ratings, then the chunks in order) are another order than NumPy's pairwise one, not a much worse one.  Measured
+# on an MI355X, kernel / fp32-oracle distance from fp64: U 2.85e-7 / 2.02e-7 (1.41), A 1.78e-7 / 2.84e-7 (0.63),
+# mU 0.48, mA 0.30, vU 0.58, vA 0.27.  4 leaves a margin of 2.8 over the worst of them.
+K64 = 4.0
+
+
+def _check_against_oracle(name, eng, rec):
+    U, A, ui, ai, t, B, starts, counts, hd = _case(name)
+    st, mets = _oracle(name)
+    n_u, steps = U.shape[0], len(counts)
+    assert int(rec["step_fwd"]) == steps
+    W, M, V = eng.W.cpu().numpy(), eng.M.cpu().numpy(), eng.V.cpu().numpy()
+    assert np.isfinite(W).all() and np.isfinite(M).all() and np.isfinite(V).all()
+    tol = LR * 2e-3 * steps + 1e-9
+    keep = np.ones(W.shape[0], bool)
+    if name in NOISY_ROWS:
+        s64, _ = _oracle(name, np.float64)
+        ru, ra = NOISY_ROWS[name]
+        keep[[ru, n_u + ra]] = False
+        for got, k32, r, what, floor in ((W, "U", ru, "U", tol), (W, "A", n_u + ra, "A", tol),
+                                         (M, "mU", ru, "mU", 0), (M, "mA", n_u + ra, "mA", 0),
+                                         (V, "vU", ru, "vU", 0), (V, "vA", n_u + ra, "vA", 0)):
+            row = r if r < n_u else r - n_u
+            if not floor:
+                floor = 1e-4 * float(np.abs(st[k32]).max())
+            _near_fp64(got[r], st[k32][row], s64[k32][row], K64, floor, what)
+    ku, ka = keep[:n_u], keep[n_u:]
+    np.testing.assert_allclose(W[:n_u][ku], st["U"][ku], atol=tol)
+    np.testing.assert_allclose(W[n_u:][ka], st["A"][ka], atol=tol)
+    for got, want, sel, what in ((M[:n_u], st["mU"], ku, "mU"), (M[n_u:], st["mA"], ka, "mA"),
+                                 (V[:n_u], st["vU"], ku, "vU"), (V[n_u:], st["vA"], ka, "vA")):
+        np.testing.assert_allclose(got[sel], want[sel], atol=np.abs(want).max() * 1e-4, err_msg=what)
+    h = st["head"]
+    for k in ("gamma", "beta"):
+        assert abs(float(rec[k]) - float(h[k])) < tol, k
+    if name == "flat_bn":
+        # every z equal: d loss / d w = c sum(dz) is rounding noise like d loss / d b, and moves w by <= lr per step
+        assert abs(float(rec["w"]) - float(h["w"])) <= 2.05 * LR * steps
+    else:
+        assert abs(float(rec["w"]) - float(h["w"])) < tol
+    assert abs(float(rec["b"]) - float(h["b"])) <= 2.05 * LR * steps
+    assert abs(rec["mov_mean"] - h["mov_mean"]) < 1e-6 and abs(rec["mov_var"] - h["mov_var"]) < 1e-6
+    assert abs(rec["last_loss"] - mets[-1]["loss"]) < 5e-6
+    loss_epoch = sum(float(m["loss"]) * c for m, c in zip(mets, counts)) / counts.sum()
+    assert abs(eng.epoch_metrics()[0] - loss_epoch) < 5e-6
+    assert (eng.rowmap.cpu().numpy() == 0).all()
+    from anime_recommendations_amd import ops
+    hd = {k: float(rec[k]) for k in ("w", "b", "gamma", "beta", "mov_mean", "mov_var")}
+    m = min(len(ui), 2000)
+    p = ops.predict_pairs(eng.U, eng.A, hd, ui[-m:], ai[-m:]).cpu().numpy()
+    po = orc.predict_pairs(st["U"], st["A"], h, ui[-m:], ai[-m:])
+    np.testing.assert_allclose(p, po, atol=1e-5)
+
+
+def _check_step_stats(name, s, rec, b_in):
+    """the batch statistics and loss of step s (the dense run goes one step at a time); b_in: the Dense bias the step
+    started from.  The bias random-walks on rounding noise in both runs (d loss / d b = 0 analytically) and carries
+    the batch mean of z with it, so the mean is compared net of it."""
+    _, mets = _oracle(name)
+    mu, var = float(mets[s]["mu"]), float(mets[s]["var"])
+    d_mu = (float(rec["bn_mu"]) - b_in) - (mu - mets[s]["b_in"])
+    assert abs(d_mu) < 1e-6 * (1.0 + abs(mu)), (s, float(rec["bn_mu"]), b_in, mu, mets[s]["b_in"])
+    assert abs(float(rec["bn_var"]) - var) < 1e-7, (s, float(rec["bn_var"]), var)
+    assert abs(float(rec["last_loss"]) - float(mets[s]["loss"])) < 5e-6, s
+    if name == "single":          # one rating: z - mean(z) is exactly 0
+        assert float(rec["bn_var"]) == 0.0, s
+    if name == "flat_bn":
+        # every z equal: the variance is 0 up to the rounding of the mean (the fp32 oracle has 1.4e-17 at 1024), and a
+        # two-pass variance is never negative
+        assert 0.0 <= float(rec["bn_var"]) <= 1e-12, (s, float(rec["bn_var"]))
+        assert all(np.isfinite(float(rec[k])) for k in ("w", "b", "gamma", "beta", "mov_mean", "mov_var", "last_loss",
+                                                         "bn_mu", "bn_var"))
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_train_edges_match_oracle_dense_and_lazy(name):
+    U, A, ui, ai, t, B, starts, counts, hd = _case(name)
+    alphas = [orc.adam_alpha(LR, i + 1) for i in range(len(counts))]
+    out = {}
+    for lazy in (False, True):
+        eng = _engine(name, lazy)
+        eng.set_epoch(ui, ai, t, starts, counts, alphas)
+        eng.reset_metrics()
+        if lazy:        # graph blocks and windows of 8, as the bench runs it
+            eng.run(len(counts), use_graph=True)
+        else:           # one step per call, eager: every step's batch statistics are on record
+            for s in range(len(counts)):
+                b_in = float(eng.read_state()["b"])
+                eng.run(1, use_graph=False, first_step=s)
+                _check_step_stats(name, s, eng.read_state(), b_in)
+        eng.synchronize()
+        rec = eng.read_state()
+        _check_against_oracle(name, eng, rec)
+        out[lazy] = (eng.W.clone(), eng.M.clone(), eng.V.clone(), rec)
+        eng.close()
+    for i, what in enumerate("WMV"):
+        x, y = out[False][i], out[True][i]
+        if not torch.equal(x, y):
+            bad = torch.nonzero((x != y).any(1)).flatten()
+            raise AssertionError("lazy %s differs from dense in %d rows (first %s), max |diff| %.3e" % (
+                what, bad.numel(), bad[:8].tolist(), float((x - y).abs().max())))
+    for k in ("w", "b", "gamma", "beta", "adam_m", "adam_v", "mov_mean", "mov_var", "bn_mu", "bn_var", "step_fwd"):
+        assert np.array_equal(out[False][3][k], out[True][3][k]), k
+
+
+# ---- 2. the other optimizers and heads at the edges -----------------------------------------------------------
+@pytest.mark.parametrize("kind", optr.KINDS)
+@pytest.mark.parametrize("name", ["single", "capacity", "one_user"])
+def test_optimizer_edges_match_the_restatement(name, kind):
+    from anime_recommendations_amd import schedule
+    U, A, ui, ai, t, B, starts, counts, hd = _case(name)
+    n_u, steps = U.shape[0], len(counts)
+    st = optr.new_state(kind, U, A, w=hd["w"])
+    st["head"]["b"] = f32(hd.get("b", 0.0))
+    mets = [optr.step(kind, st, u, a, r, LR) for u, a, r in _batches(name)]
+    eng = _engine(name, False, optimizer=kind)
+    eng.set_epoch(ui, ai, t, starts, counts, schedule.step_rates(kind, LR, 1, steps))
+    eng.reset_metrics()
+    eng.run(steps, use_graph=False)
+    rec = eng.read_state()
+    assert rec["step_fwd"] == steps
+    # test_optimizers_gpu.test_engine_run_matches_the_restated_update's bars
+    tol = LR * 2e-3 * steps + 1e-9
+    np.testing.assert_allclose(eng.U.cpu().numpy(), st["U"], atol=tol)
+    np.testing.assert_allclose(eng.A.cpu().numpy(), st["A"], atol=tol)
+    V = eng.V.cpu().numpy()
+    if kind != "sgd":
+        for got, want in ((V[:n_u], st["sU"]), (V[n_u:], st["sA"])):
+            np.testing.assert_allclose(got, want, atol=np.abs(want).max() * 1e-4)
+        np.testing.assert_allclose(np.array(rec["adam_v"]), st["head"]["v"], atol=np.abs(st["head"]["v"]).max() * 1e-4)
+    else:
+        assert (V == 0).all() and (np.array(rec["adam_v"]) == 0).all()
+    assert (eng.M.cpu().numpy() == 0).all() and (np.array(rec["adam_m"]) == 0).all()
+    h = st["head"]
+    for k in ("w", "gamma", "beta"):
+        assert abs(float(rec[k]) - float(h[k])) < tol, k
+    assert abs(float(rec["b"]) - float(h["b"])) <= 2.05 * LR * steps
+    assert abs(rec["mov_mean"] - h["mov_mean"]) < 1e-6 and abs(rec["mov_var"] - h["mov_var"]) < 1e-6
+    assert abs(rec["last_loss"] - mets[-1]["loss"]) < 5e-6
+    loss_epoch = sum(float(m["loss"]) * c for m, c in zip(mets, counts)) / counts.sum()
+    assert abs(eng.epoch_metrics()[0] - loss_epoch) < 5e-6
+    assert (eng.rowmap.cpu().numpy() == 0).all()
+    eng.close()
+
+
+# five (loss, activation) pairs that take every loss and every activation once; the relu head puts every y at
+# beta + gamma zhat <= -3: p = 0 everywhere, no gradient reaches the tables or the head (only the L2 term moves them)
+HEAD_PAIRS = [("mean_squared_error", "linear"), ("huber", "tanh"), ("log_cosh", "softplus"),
+              ("mean_absolute_error", "sigmoid"), ("binary_crossentropy", "relu")]
+
+
+@pytest.mark.parametrize("loss,act", HEAD_PAIRS)
+@pytest.mark.parametrize("name", ["single", "flat_bn", "capacity"])
+def test_head_edges_match_the_restatement(name, loss, act):
+    U, A, ui, ai, t, B, starts, counts, hd = _case(name)
+    n_u, steps = U.shape[0], len(counts)
+    head = dict(w=hd["w"], b=hd.get("b", 0.05), gamma=0.9, beta=0.3)
+    if act == "relu":
+        head.update(gamma=0.5, beta=-5.0)
+    st = orc.new_state(U, A, orc.new_head(**head))
+    mets = [heads.train_step(st, u, a, r, LR, loss, act) for u, a, r in _batches(name)]
+    eng = _engine(name, False, loss=loss, activation=act)
+    eng.set_head(**head)
+    eng.set_epoch(ui, ai, t, starts, counts, [orc.adam_alpha(LR, i + 1) for i in range(steps)])
+    eng.reset_metrics()
+    eng.run(steps, use_graph=False)
+    rec = eng.read_state()
+    assert rec["step_fwd"] == steps
+    # test_heads_gpu.test_steps_match_the_restatement's bars; flat_bn's pair rows take a gradient of rounding noise
+    # (section 1 holds them to the fp64 oracle): here they are only held to Adam's bound of lr per step
+    tol = LR * 2e-3 * steps + 1e-9
+    W, M = eng.W.cpu().numpy(), eng.M.cpu().numpy()
+    assert np.isfinite(W).all() and np.isfinite(M).all()
+    Wo = np.concatenate([st["U"], st["A"]])
+    Mo = np.concatenate([st["mU"], st["mA"]])
+    keep = np.ones(len(W), bool)
+    if name in NOISY_ROWS:
+        ru, ra = NOISY_ROWS[name]
+        keep[[ru, n_u + ra]] = False
+        np.testing.assert_allclose(W[~keep], Wo[~keep], atol=2.05 * LR * steps)
+    np.testing.assert_allclose(W[keep], Wo[keep], atol=tol)
+    np.testing.assert_allclose(M[keep], Mo[keep], atol=np.abs(Mo).max() * 1e-4)
+    h = st["head"]
+    for k in ("w", "gamma", "beta"):
+        # every z equal: zhat = (z - mean z) r and sum(dz) are 0 up to rounding, and so are d loss / d gamma and / d w
+        if k in ("w", "gamma") and name == "flat_bn":
+            assert abs(float(rec[k]) - float(h[k])) <= 2.05 * LR * steps
+        else:
+            assert abs(float(rec[k]) - float(h[k])) < tol, k
+    assert abs(float(rec["b"]) - float(h["b"])) <= 2.05 * LR * steps
+    assert abs(rec["mov_mean"] - h["mov_mean"]) < 3e-6 and abs(rec["mov_var"] - h["mov_var"]) < 3e-6
+    loss_epoch = sum(float(m["loss"]) * c for m, c in zip(mets, counts)) / counts.sum()
+    mse_epoch = sum(float(m["mse"]) * c for m, c in zip(mets, counts)) / counts.sum()
+    el, em = eng.epoch_metrics()
+    assert abs(el - loss_epoch) < 5e-6 + 2e-5 * abs(loss_epoch)
+    assert abs(em - mse_epoch) < 5e-6
+    if act == "relu":       # no data gradient: w, gamma and beta keep their values; the tables take the L2 steps only
+        for k in ("w", "gamma", "beta"):
+            assert float(rec[k]) == f32(head[k]), k
+    eng.close()
+
+
+# ---- 3. validation and predict at odd counts ------------------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 3, 255, 257, 16385, 100003])
+def test_evaluate_and_predict_at_odd_counts(n):
+    from anime_recommendations_amd import ops
+    from anime_recommendations_amd.engine import TrainEngine
+    rng = np.random.default_rng(1000 + n)
+    U, A = _tables(rng, 3000, 500)
+    ui, ai = rng.integers(0, 3000, n), _zipf(rng, n, 500, 1.2)
+    t = (rng.integers(0, 11, n) / 10).astype(f32)
+    head = dict(w=1.3, b=0.1, gamma=0.9, beta=-0.2, mov_mean=0.05, mov_var=0.4)
+    st = orc.new_state(U, A, orc.new_head(**head))
+    eng = TrainEngine(3000, 500, max_batch=1024, arena_steps=4)
+    eng.set_head(**head)
+    eng.set_weights(U, A)
+    vl, vm = eng.evaluate(ui, ai, t)
+    ev = orc.evaluate(st, ui, ai, t)
+    # (test_train_gpu.test_evaluate_matches_oracle's bars)
+    assert abs(vl - float(ev["val_loss"])) < 3e-6 and abs(vm - float(ev["val_mse"])) < 1e-6, (vl, vm, ev)
+    assert eng.read_state()["val_n"] == n
+    p = ops.predict_pairs(eng.U, eng.A, head, ui, ai).cpu().numpy()
+    assert p.shape == (n,)
+    np.testing.assert_allclose(p, orc.predict_pairs(U, A, st["head"], ui, ai), atol=1e-5)
+    eng.close()

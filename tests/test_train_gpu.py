@@ -140,6 +140,7 @@ def test_train_steps_match_oracle(n_u, n_a, B, steps, zipf):
     np.testing.assert_allclose(M[:n_u], st["mU"], atol=np.abs(st["mU"]).max() * 1e-4)
     np.testing.assert_allclose(M[n_u:], st["mA"], atol=np.abs(st["mA"]).max() * 1e-4)
     V = eng.V.cpu().numpy()
+    np.testing.assert_allclose(V[:n_u], st["vU"], atol=np.abs(st["vU"]).max() * 1e-4)
     np.testing.assert_allclose(V[n_u:], st["vA"], atol=np.abs(st["vA"]).max() * 1e-4)
     h = st["head"]
     for k in ("w", "gamma", "beta"):
