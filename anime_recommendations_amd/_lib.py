@@ -119,6 +119,8 @@ PROTOTYPES = {
     "anirec_adam_flat": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _vp]),
     "anirec_opt_flat": (C.c_int, [_i32, _vp, _vp, _vp, _sz, _f32, _vp]),
     "anirec_selftest_lazy_math": (C.c_int, [C.c_uint64, _vp, _vp]),
+    "anirec_selftest_lazy_div": (C.c_int, [_i32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "anirec_selftest_lazy_replay": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _f32, _i32, _vp, _vp, _vp, _vp]),
     "anirec_gather_ratings": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "anirec_rownorm": (C.c_int, [_vp, _i32, _vp, _vp]),
     "anirec_cosine_scores": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),

@@ -1290,6 +1290,9 @@ __device__ __forceinline__ float l2_only_grad(float w, float two_l2) {
 //    on gfx950 that the compiler could only half fill: 494 s_nop in the round-3 kernel).
 //  * g = 2 lambda w without the "+ 0" of l2_only_grad: it only matters when the product is -0, and then the first
 //    moment of that step is +-0, |m alpha| = 0 fails the range test and the row is redone by the compiler's path.
+// Round 5: the running minima / maxima left the step too — the bounds are derived once per row from the values the
+// replay starts from (lz_entry_ok), only the smallest |m| is still folded per step; and the divide takes one
+// correction instead of two (div4_normal, checked by exhaustion).
 // The four elements of a lane are two PAIRS stepped side by side, statement by statement: every operation is two
 // independent v_pk_*_f32 back to back.  (Written as one pair after the other, hipcc ran one pair's divide chain behind
 // the other's — gfx950 wants a wait state between DEPENDENT packed-f32 instructions, and that schedule paid an s_nop
@@ -1338,8 +1341,9 @@ __device__ __forceinline__ Quad sqrt4_normal(Quad x) {
   return qfma(d1, h, s1);
 }
 
-// correctly rounded n / d for operands that need no v_div_scale scaling and no v_div_fixup
-__device__ __forceinline__ Quad div4_normal(Quad n, Quad d) {
+// refined reciprocal y = y0 + (1 - d y0) y0, y0 = v_rcp_f32(d): anirec_selftest_lazy_div checks y == 1.0f / d on
+// EVERY float d of [1e-7, 2^48] (the denominators sqrt(v) + 1e-7 the replay admits)
+__device__ __forceinline__ Quad rcp4_refined(Quad d) {
 #pragma clang fp contract(off)
   Quad y0;
   y0.a.x = __builtin_amdgcn_rcpf(d.a.x);
@@ -1348,50 +1352,137 @@ __device__ __forceinline__ Quad div4_normal(Quad n, Quad d) {
   y0.b.y = __builtin_amdgcn_rcpf(d.b.y);
   const Quad one = {{1.0f, 1.0f}, {1.0f, 1.0f}};
   const Quad e = qfma(-d, y0, one);
-  const Quad y = qfma(e, y0, y0);
-  const Quad q0 = n * y;
-  const Quad r0 = qfma(-d, q0, n);
-  const Quad q1 = qfma(r0, y, q0);
-  const Quad r1 = qfma(-d, q1, n);
-  return qfma(r1, y, q1);
+  return qfma(e, y0, y0);
 }
 
-// what the short sequences are exact for: second moments in [2^-96, 2^96] (no sqrt scaling), |m alpha| in
-// [2^-60, 2^60] with the denominator sqrt(v) + 1e-7 in [1e-7, 2^48 + eps] (no v_div_scale, no v_div_fixup)
-struct LzRange {
-  float vlo, vhi, nlo, nhi;
+// Correctly rounded n / d for |n| in [2^-60, 2^60], d in [1e-7, 2^48]: q0 = n y, ONE correction q1 = q0 + (n - d q0) y.
+// The compiler's chain (v_div_scale / v_div_fixup aside) takes a second one, r1 = n - d q1, q2 = q1 + r1 y, because
+// Markstein's theorem — y = RN(1/d), q within 1 ulp of n/d, the residual n - d q exact, no underflow — then makes q2
+// = RN(n/d) for any q1 within 1 ulp.  It does NOT cover q1 itself: with y = RN(1/d), q0 = RN(n y) is off by up to
+// 1.48 ulp and the fma's residual n - d q0 is inexact for ~0.15 % of operand pairs.  q1 = RN(n/d) is established by
+// exhaustion instead (anirec_selftest_lazy_div, tests/test_lazy_div_exhaustive_gpu.py):
+//  * y == RN(1/d) for every float d of the range (6e8 values), so y(d 2^k) = y(d) 2^k there;
+//  * then every operation of the sequence commutes with scaling n and d by powers of two as long as no result is
+//    subnormal: q0 and q1 are within 2 ulp of n/d in [2^-108, 2^84], and a nonzero residual n - d q0 is a multiple
+//    of ulp(d) ulp(q0) >= 2^-48 |n| >= 2^-108 (normal: the fma rounds it once, as it does for n, d in [1, 2));
+//  * so q1 == RN(n/d) for the whole range iff it holds for all 2^46 significand pairs n, d in [1, 2) (signs are
+//    symmetric) — the self-test compares q1 with IEEE `/` on every one of them: 0 mismatches.
+// (The second correction is 4 packed operations per lane-step, ~7 % of the flush's VALU issue.)
+__device__ __forceinline__ Quad div4_normal(Quad n, Quad d) {
+#pragma clang fp contract(off)
+  const Quad y = rcp4_refined(d);
+  const Quad q0 = n * y;
+  const Quad r0 = qfma(-d, q0, n);
+  return qfma(r0, y, q0);
+}
+
+// What the short sequences are exact for: every step's second moment in [2^-96, 2^96] (no sqrt scaling), |m alpha| in
+// [2^-60, 2^60] with the denominator sqrt(v) + 1e-7 in [1e-7, 2^48 + eps] (no v_div_scale, no v_div_fixup).
+// The bounds are tested ONCE per row, from the values the replay starts from, instead of folding every step's
+// operands into running minima / maxima (round 4: 8 v_min3 / v_max3 per lane-step).  Window constants (lz_bound):
+// amin / A = the smallest / largest alpha of the window's steps, L = |2 lambda|.  Per element, u = 2^-24, every
+// operation rounding to nearest (monotone, |RN(x)| <= |x| (1 + u), and RN(x) >= x (1 - u) for normal x > 0; a flush
+// to zero only lowers a magnitude), by induction over the <= 8 steps:
+//  (v lo) g^2 >= 0, so RN(g^2 - v) >= RN(-v) = -v and v' = RN(v + RN(RN(g^2 - v) c2)) >= v (1 - c2 (1 + u)) (1 - u)
+//         >= 0.99899 v for normal v.  The FIRST step also lifts v: with G = RN(g_0^2) normal, either v_0 <= G / 2,
+//         then RN(G - v_0) >= (G - v_0) (1 - u) and v_1 >= (v_0 + (G - v_0) c2 (1 - u)^2) (1 - u) >= c2 G (1 - u)^3,
+//         or v_0 > G / 2 and v_1 >= 0.99899 v_0 > c2 G.  So v_1 >= max(0.99899 v_0, c2 G (1 - u)^3), and the
+//         per-element vb = max(v_0, e), e = RN(RN(c2 L^2) RN(w_0^2)) <= c2 G (1 - u)^-10, gives every v_j (j >= 1,
+//         the moments the steps produce) >= 0.99899^7 (1 - 13 u) 0.99899 vb >= 0.989 vb > 2^-96 for vb >= 2^-95 (the
+//         factor-2 margin).  (Rows fresh from initialisation, v_0 = 0, are admitted through e: |w_0| >~ 1e-9 at
+//         lambda = 1e-4, as the per-step test of the moments admitted them.)
+//  (v hi) v' is RN of a combination of v and RN(g^2) with weights (1 - c), c in (0, 1): v' <= max(v, g^2) (1 + u)^2.
+//  (m)    likewise |m'| <= max(|m|, |g|) (1 + u)^3, and |g| = |RN(2 lambda w)| <= L |w| (1 + u).
+//  (w)    |w'| <= (|w| + |q|) (1 + u), q = RN(RN(m' alpha) / RN(RN(sqrt v') + eps)), the denominator >= RN(sqrt v')
+//         >= sqrt(0.989 vb) (1 - u) and >= eps: |q| <= |m'| S, S = min(1.006 A / sqrt(vb), 1.0001 A / eps) (the
+//         second term is what bounds the first window's rows whose tiny |w_0| makes vb tiny).
+//  With X = max(|m|, L |w|): X' <= X (1 + L S) (1 + u)^5.  Over the window, with F = (1 + L S)^8: every |m_j| and
+//  |g_j| <= X_0 F (1 + 2^-17), so every v_j <= max(v_0, (X_0 F)^2) (1 + 2^-15) and |m_j alpha_j| <= A X_0 F (1 + 2^-16).
+//  The row is admitted if every vb >= 2^-95, v_0 <= 2^95, X_0 F <= 2^46 and X_0 F A <= 2^58: a factor 2 below the
+//  2^47 / 2^59 the bounds need, which covers F's own roundings in fp32 and v_rsq_f32's error (with 1.01 for 1.006
+//  and for 1.0001; F is taken at the lane's smallest vb).
+//  (|m alpha| lo) the one bound no entry value gives — m crossing zero — stays per step: the smallest |m_j| of the
+//  steps taken (one v_min3 per pair), times amin once: RN(|m_j| alpha_j) >= RN(min |m| amin) >= 2^-60.
+// A NaN slips through min / max (and fails every comparison); it is sticky (w NaN -> g, m, v NaN; m or v NaN -> w
+// NaN), so the test of the final w catches it.
+struct LzBound {
+  float amin;  // smallest alpha of the window's steps [0, nj)
+  float amax;  // A
+  float k;     // 1.01 L A
+  float kmax;  // 1.01 L A / eps
+  float kv;    // c2 L^2
 };
-__device__ __forceinline__ LzRange lz_range_init() { return {3.0e38f, 0.f, 3.0e38f, 0.f}; }
-__device__ __forceinline__ bool lz_range_ok(const LzRange &r) {
-  return r.vlo >= 0x1p-96f && r.vhi <= 0x1p96f && r.nlo >= 0x1p-60f && r.nhi <= 0x1p60f;
+__device__ __forceinline__ LzBound lz_bound(const float (&alpha)[kLzWin], int nj, float two_l2) {
+  float amin = 3.0e38f, amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < kLzWin; ++j) {
+    if (j < nj) amin = fminf(amin, alpha[j]);
+    amax = fmaxf(amax, alpha[j]);
+  }
+  const float k = 1.01f * fabsf(two_l2) * amax;
+  return {amin, amax, k, k * 1e7f, kOneMinusB2 * two_l2 * two_l2};
 }
 __device__ __forceinline__ float min3f(float a, float b, float c) { return fminf(fminf(a, b), c); }
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+// the entry half of the test above, for a lane's four elements
+__device__ __forceinline__ bool lz_entry_ok(const Row3 &x, const LzBound &bd, float two_l2) {
+  const float vb0 = fmaxf(x.v.x, bd.kv * (x.w.x * x.w.x)), vb1 = fmaxf(x.v.y, bd.kv * (x.w.y * x.w.y)),
+              vb2 = fmaxf(x.v.z, bd.kv * (x.w.z * x.w.z)), vb3 = fmaxf(x.v.w, bd.kv * (x.w.w * x.w.w));
+  const float vlo = fminf(min3f(vb0, vb1, vb2), vb3);
+  const float vhi = fmaxf(max3f(x.v.x, x.v.y, x.v.z), x.v.w);
+  const float mx = fmaxf(max3f(fabsf(x.m.x), fabsf(x.m.y), fabsf(x.m.z)), fabsf(x.m.w));
+  const float wx = fmaxf(max3f(fabsf(x.w.x), fabsf(x.w.y), fabsf(x.w.z)), fabsf(x.w.w));
+  const float x0 = fmaxf(mx, fabsf(two_l2) * wx);
+  float f = 1.0f + fminf(bd.k * __builtin_amdgcn_rsqf(vlo), bd.kmax);
+  f = f * f;
+  f = f * f;
+  f = f * f;
+  const float xf = x0 * f;
+  return vlo >= 0x1p-95f && vhi <= 0x1p95f && xf <= 0x1p46f && xf * bd.amax <= 0x1p58f;
+}
 
-// one L2-only Adam step of a lane's four elements by the short sequences; the operands the sequences are conditional
-// on are folded into `rg` (tested by the caller once per row)
+// The catch-up (k_head / k_lazy_adam / k_lazy_catchup) replays a row's few pending steps on a latency-bound path:
+// there the ~50 instructions of lz_bound + lz_entry_ok cost more than they save (measured: +0.3 / +0.75 / +0.35 us
+// per launch), so it keeps the round-4 test instead — every pair-step folds its second moment and |m alpha| into
+// running minima / maxima, tested after the row's last step (kRowTest = false).  The flush (a whole window per row,
+// VALU-bound) takes the once-per-row test (kRowTest = true).
+struct LzRange {
+  float vlo, vhi, nlo, nhi;  // kRowTest: nlo = the smallest |m| alone
+};
+__device__ __forceinline__ bool lz_range_ok(const LzRange &r) {
+  return r.vlo >= 0x1p-96f && r.vhi <= 0x1p96f && r.nlo >= 0x1p-60f && r.nhi <= 0x1p60f;
+}
+
+// one L2-only Adam step of a lane's four elements by the short sequences; kRowTest: the smallest |m| of the step is
+// folded into rg.nlo (tested by the caller once per row, with the window's smallest alpha); otherwise every operand
+// the sequences are conditional on is folded into rg
+template <bool kRowTest>
 __device__ __forceinline__ void adam4_l2(Quad &w, Quad &m, Quad &v, float alpha, float two_l2, LzRange &rg) {
 #pragma clang fp contract(off)
   const Quad g = w * two_l2;
   const Quad mn = m + (g - m) * kOneMinusB1;
   const Quad vn = v + (g * g - v) * kOneMinusB2;
   const Quad num = mn * alpha;
-  rg.vlo = min3f(min3f(rg.vlo, vn.a.x, vn.a.y), vn.b.x, vn.b.y);
-  rg.vhi = max3f(max3f(rg.vhi, vn.a.x, vn.a.y), vn.b.x, vn.b.y);
-  rg.nlo = min3f(min3f(rg.nlo, fabsf(num.a.x), fabsf(num.a.y)), fabsf(num.b.x), fabsf(num.b.y));
-  rg.nhi = max3f(max3f(rg.nhi, fabsf(num.a.x), fabsf(num.a.y)), fabsf(num.b.x), fabsf(num.b.y));
+  if (kRowTest) {
+    rg.nlo = min3f(min3f(rg.nlo, fabsf(mn.a.x), fabsf(mn.a.y)), fabsf(mn.b.x), fabsf(mn.b.y));
+  } else {
+    rg.vlo = min3f(min3f(rg.vlo, vn.a.x, vn.a.y), vn.b.x, vn.b.y);
+    rg.vhi = max3f(max3f(rg.vhi, vn.a.x, vn.a.y), vn.b.x, vn.b.y);
+    rg.nlo = min3f(min3f(rg.nlo, fabsf(num.a.x), fabsf(num.a.y)), fabsf(num.b.x), fabsf(num.b.y));
+    rg.nhi = max3f(max3f(rg.nhi, fabsf(num.a.x), fabsf(num.a.y)), fabsf(num.b.x), fabsf(num.b.y));
+  }
   const Quad den = sqrt4_normal(vn) + kAdamEps;
   w = w - div4_normal(num, den);
   m = mn;
   v = vn;
 }
 
-template <bool kFast>
+template <bool kFast, bool kRowTest>
 __device__ __forceinline__ void lazy_one_step(Row3 &x, float alpha, float two_l2, float &sq, LzRange &rg) {
   sq = x.w.x * x.w.x + x.w.y * x.w.y + x.w.z * x.w.z + x.w.w * x.w.w;
   if (kFast) {
     Quad w = {{x.w.x, x.w.y}, {x.w.z, x.w.w}}, m = {{x.m.x, x.m.y}, {x.m.z, x.m.w}}, v = {{x.v.x, x.v.y}, {x.v.z, x.v.w}};
-    adam4_l2(w, m, v, alpha, two_l2, rg);
+    adam4_l2<kRowTest>(w, m, v, alpha, two_l2, rg);
     x.w = make_float4(w.a.x, w.a.y, w.b.x, w.b.y);
     x.m = make_float4(m.a.x, m.a.y, m.b.x, m.b.y);
     x.v = make_float4(v.a.x, v.a.y, v.b.x, v.b.y);
@@ -1407,13 +1498,14 @@ __device__ __forceinline__ void lazy_one_step(Row3 &x, float alpha, float two_l2
 }
 
 // returns whether the short sequences were exact for every operand of every step this lane took (kFast)
-template <bool kFast>
+template <bool kFast, bool kRowTest>
 __device__ __forceinline__ bool lazy_replay_path(Row3 &x, int j0, int j1, const float (&alpha)[kLzWin], float two_l2,
-                                                 float (&sq)[kLzWin]) {
-  LzRange rg = lz_range_init();
+                                                 const LzBound &bd, float (&sq)[kLzWin]) {
+  const bool entry_ok = kFast && kRowTest ? lz_entry_ok(x, bd, two_l2) : true;
+  LzRange rg = {3.0e38f, 0.f, 3.0e38f, 0.f};
   if (__all(j0 <= 0 && j1 >= kLzWin)) {  // the common case (a row untouched for a whole window): no predication
 #pragma unroll
-    for (int j = 0; j < kLzWin; ++j) lazy_one_step<kFast>(x, alpha[j], two_l2, sq[j], rg);
+    for (int j = 0; j < kLzWin; ++j) lazy_one_step<kFast, kRowTest>(x, alpha[j], two_l2, sq[j], rg);
   } else {
 #pragma unroll
     for (int j = 0; j < kLzWin; ++j) {
@@ -1421,7 +1513,7 @@ __device__ __forceinline__ bool lazy_replay_path(Row3 &x, int j0, int j1, const 
         Row3 y = x;
         LzRange ry = rg;
         float q;
-        lazy_one_step<kFast>(y, alpha[j], two_l2, q, ry);
+        lazy_one_step<kFast, kRowTest>(y, alpha[j], two_l2, q, ry);
         if (j >= j0 && j < j1) {
           x = y;
           rg = ry;
@@ -1431,9 +1523,10 @@ __device__ __forceinline__ bool lazy_replay_path(Row3 &x, int j0, int j1, const 
     }
   }
   if (!kFast) return true;
-  if (j1 <= j0) return true;           // nothing taken (the accumulators still hold their initial values)
+  if (j1 <= j0) return true;           // nothing taken
   const float t = (x.w.x + x.w.y) + (x.w.z + x.w.w);  // a NaN anywhere in the replay has reached w
-  return lz_range_ok(rg) && t == t;
+  if (!kRowTest) return lz_range_ok(rg) && t == t;
+  return entry_ok && rg.nlo * bd.amin >= 0x1p-60f && t == t;
 }
 
 // The replay by the compiler's full expansions, OUT OF LINE: it runs for a handful of rows per table (a moment decayed
@@ -1455,7 +1548,7 @@ __device__ __attribute__((noinline)) SlowReplay lazy_replay_slow(Row3 x, int j0,
     alpha[j] = al.a[j];
     sq[j] = 0.f;
   }
-  (void)lazy_replay_path<false>(x, j0, j1, alpha, two_l2, sq);
+  (void)lazy_replay_path<false, false>(x, j0, j1, alpha, two_l2, LzBound{}, sq);
   o.x = x;
 #pragma unroll
   for (int j = 0; j < kLzWin; ++j) o.sq[j] = sq[j];
@@ -1463,14 +1556,16 @@ __device__ __attribute__((noinline)) SlowReplay lazy_replay_slow(Row3 x, int j0,
 }
 
 // pending pure-L2 steps [j0, j1) (window-relative) of one row, a float4 per lane; sq[j] receives this lane's part of
-// sum(W_s^2), the weights step s READ.  The packed short sequences first; if any lane of the wave met an operand
+// sum(W_s^2), the weights step s READ, for the steps taken (the others keep what the caller put there).  The packed
+// short sequences first; if any lane of the wave met an operand
 // outside their range, the whole replay is redone from the saved row with the compiler's expansions (rare: a moment
 // decayed to a denormal, an exact zero).
 // (the row is re-read from memory for the redo — nothing has been stored yet — rather than kept in 12 more registers)
+template <bool kRowTest>
 __device__ __forceinline__ void lazy_replay(Row3 &x, int j0, int j1, const float (&alpha)[kLzWin], float two_l2,
-                                            float (&sq)[kLzWin], const float *W, const float *M, const float *V,
-                                            size_t e) {
-  if (__all(lazy_replay_path<true>(x, j0, j1, alpha, two_l2, sq))) return;
+                                            const LzBound &bd, float (&sq)[kLzWin], const float *W, const float *M,
+                                            const float *V, size_t e) {
+  if (__all(lazy_replay_path<true, kRowTest>(x, j0, j1, alpha, two_l2, bd, sq))) return;
   Row3 y;
   y.w = reinterpret_cast<const float4 *>(W)[e];
   y.m = reinterpret_cast<const float4 *>(M)[e];
@@ -1481,7 +1576,8 @@ __device__ __forceinline__ void lazy_replay(Row3 &x, int j0, int j1, const float
   const SlowReplay o = lazy_replay_slow(y, j0, j1, al, two_l2);
   x = o.x;
 #pragma unroll
-  for (int j = 0; j < kLzWin; ++j) sq[j] = o.sq[j];
+  for (int j = 0; j < kLzWin; ++j)
+    if (j >= j0 && j < j1) sq[j] = o.sq[j];
 }
 
 __device__ __forceinline__ void lazy_alphas(const LazyArgs &a, int w0, int nj, float (&alpha)[kLzWin]) {
@@ -1527,7 +1623,7 @@ __device__ __forceinline__ void lazy_catchup_row(const LazyArgs &a, int step, in
   lazy_alphas(a, w0, step - w0, alpha);
 #pragma unroll
   for (int j = 0; j < kLzWin; ++j) sq[j] = 0.f;
-  lazy_replay(x, ta - w0, step - w0, alpha, a.two_l2, sq, a.W, a.M, a.V, e);
+  lazy_replay<false>(x, ta - w0, step - w0, alpha, a.two_l2, LzBound{}, sq, a.W, a.M, a.V, e);
   reinterpret_cast<float4 *>(a.W)[e] = x.w;
   reinterpret_cast<float4 *>(a.M)[e] = x.m;
   reinterpret_cast<float4 *>(a.V)[e] = x.v;
@@ -1647,6 +1743,7 @@ __global__ __launch_bounds__(256) void k_lazy_flush(LazyArgs a) {
   const int nhw = (tab == 0 ? a.split : (int)gridDim.x - a.split) * 8;
   float alpha[kLzWin];
   lazy_alphas(a, w0, nj, alpha);
+  const LzBound bd = lz_bound(alpha, nj, a.two_l2);
   float acc[kLzWin];
 #pragma unroll
   for (int j = 0; j < kLzWin; ++j) acc[j] = 0.f;
@@ -1667,11 +1764,13 @@ __global__ __launch_bounds__(256) void k_lazy_flush(LazyArgs a) {
     const size_t e = (size_t)r * kRowVec + l;
     float rec = 0.f;
     if (l < jt) rec = a.z.rowsq[(size_t)r * kLzWin + l];  // lane j holds the recorded sum of step j
+    // sq[j]: lane j's recorded row sum of step j (rec is 0 on lanes l >= jt), overwritten for the replayed steps
+    // [jt, nj) by their lane parts — what the accumulators take, with no select-and-add per step
     float sq[kLzWin];
 #pragma unroll
-    for (int j = 0; j < kLzWin; ++j) sq[j] = 0.f;
+    for (int j = 0; j < kLzWin; ++j) sq[j] = l == j ? rec : 0.f;
     if (jt < nj) {
-      lazy_replay(x, jt, nj, alpha, a.two_l2, sq, a.W, a.M, a.V, e);
+      lazy_replay<true>(x, jt, nj, alpha, a.two_l2, bd, sq, a.W, a.M, a.V, e);
       if (kNT) {
         st_nt_asm(reinterpret_cast<float4 *>(a.W) + e, x.w);
         st_nt_asm(reinterpret_cast<float4 *>(a.M) + e, x.m);
@@ -1684,7 +1783,7 @@ __global__ __launch_bounds__(256) void k_lazy_flush(LazyArgs a) {
       if (l == 0) a.z.row_step[r] = upto;
     }
 #pragma unroll
-    for (int j = 0; j < kLzWin; ++j) acc[j] += sq[j] + (l == j ? rec : 0.f);  // a replayed step's lane parts, or the recorded row sum
+    for (int j = 0; j < kLzWin; ++j) acc[j] += sq[j];
     fin += x.w.x * x.w.x + x.w.y * x.w.y + x.w.z * x.w.z + x.w.w * x.w.w;
   }
   // block sums in a fixed order: lanes -> waves -> the four waves
@@ -1898,6 +1997,124 @@ __global__ __launch_bounds__(256) void k_selftest_lazy_math(unsigned long long n
     if (bad_s) atomicAdd(counts + 0, bad_s);
     if (bad_d) atomicAdd(counts + 1, bad_d);
   }
+}
+
+// Self-test of the replay's one-correction divide (anirec_selftest_lazy_div; tests only), see div4_normal.
+// kMode 0: the refined reciprocal against 1.0f / d on EVERY float d with bits in [lo, hi].  kMode 1: q1 against the
+// IEEE `/` on every significand pair n, d in [1, 2), d's significands [lo, hi) (one workgroup each) x all 2^23 n's.
+// kMode 2: the same with the uncorrected q0 = n y (the comparison's own sanity leg: it must report misses).
+// counts[0] += mismatches, counts[1] += operands checked, counts[2] / counts[3] = min / max bits of a failing d.
+template <int kMode>
+__global__ __launch_bounds__(256) void k_selftest_lazy_div(uint32_t lo, uint32_t hi, unsigned long long *counts) {
+  unsigned long long bad = 0, seen = 0;
+  uint32_t fmin = 0xFFFFFFFFu, fmax = 0u;
+  if (kMode == 0) {
+    const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned long long nth = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long b = (unsigned long long)lo + 4 * tid; b <= hi; b += 4 * nth) {
+      uint32_t u[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) u[k] = (uint32_t)min(b + k, (unsigned long long)hi);
+      const Quad d = {{__uint_as_float(u[0]), __uint_as_float(u[1])}, {__uint_as_float(u[2]), __uint_as_float(u[3])}};
+      const Quad y = rcp4_refined(d);
+      const float ys[4] = {y.a.x, y.a.y, y.b.x, y.b.y};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (b + k > hi) continue;
+        ++seen;
+        if (__float_as_uint(ys[k]) != __float_as_uint(1.0f / __uint_as_float(u[k]))) {
+          ++bad;
+          fmin = min(fmin, u[k]);
+          fmax = max(fmax, u[k]);
+        }
+      }
+    }
+  } else {
+    const uint32_t db = 0x3F800000u | (lo + blockIdx.x);
+    const float dv = __uint_as_float(db);
+    const Quad d = {{dv, dv}, {dv, dv}};
+    for (uint32_t i = 4 * threadIdx.x; i < (1u << 23); i += 4 * blockDim.x) {
+      const Quad n = {{__uint_as_float(0x3F800000u | i), __uint_as_float(0x3F800000u | (i + 1))},
+                      {__uint_as_float(0x3F800000u | (i + 2)), __uint_as_float(0x3F800000u | (i + 3))}};
+      Quad q;
+      if (kMode == 1) {
+        q = div4_normal(n, d);
+      } else {
+        const Quad y = rcp4_refined(d);
+        q = n * y;
+      }
+      const float qs[4] = {q.a.x, q.a.y, q.b.x, q.b.y}, ns[4] = {n.a.x, n.a.y, n.b.x, n.b.y};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) bad += __float_as_uint(qs[k]) != __float_as_uint(ns[k] / dv);
+      seen += 4;
+    }
+    if (bad) fmin = fmax = db;
+  }
+  bad = (unsigned long long)wave_sum_d((double)bad);
+  seen = (unsigned long long)wave_sum_d((double)seen);
+  if ((threadIdx.x & 63) == 0) {
+    if (bad) atomicAdd(counts + 0, bad);
+    atomicAdd(counts + 1, seen);
+  }
+  if (fmin != 0xFFFFFFFFu) {
+    atomicMin(counts + 2, (unsigned long long)fmin);
+    atomicMax(counts + 3, (unsigned long long)fmax);
+  }
+}
+
+// Self-test of the whole replay on given rows (anirec_selftest_lazy_replay; tests only): one half-wave per row takes
+// the row's pending steps [j0[row], nj) by lazy_replay with the flush's once-per-row test (row_test) or the
+// catch-up's per-step one — the packed sequences, the row test, the redo by the
+// compiler's expansions — and, separately, by the dense kernel's adam_elem; fast[row] = 1 if every lane of the row
+// passed the short sequences' range test (the row alone would not trigger the redo).  wmv / out_*: [3][rows][kDim].
+__global__ __launch_bounds__(256) void k_selftest_lazy_replay(const float *wmv, int rows, const float *alpha8, int nj,
+                                                              const int32_t *j0s, float two_l2, float *out_lazy,
+                                                              float *out_dense, int32_t *fast, int row_test) {
+  const int row = (int)blockIdx.x * 8 + (int)(threadIdx.x >> 5);
+  const int l = threadIdx.x & 31;
+  if (row >= rows) return;
+  const size_t plane = (size_t)rows * kRowVec;
+  const size_t e = (size_t)row * kRowVec + l;
+  const float *W = wmv, *M = wmv + plane * 4, *V = wmv + plane * 8;
+  Row3 x;
+  x.w = reinterpret_cast<const float4 *>(W)[e];
+  x.m = reinterpret_cast<const float4 *>(M)[e];
+  x.v = reinterpret_cast<const float4 *>(V)[e];
+  const Row3 x0 = x;
+  float alpha[kLzWin], sq[kLzWin];
+#pragma unroll
+  for (int j = 0; j < kLzWin; ++j) {
+    alpha[j] = j < nj ? alpha8[j] : 0.f;
+    sq[j] = 0.f;
+  }
+  const LzBound bd = lz_bound(alpha, nj, two_l2);
+  const int j0 = j0s[row];
+  {
+    Row3 t = x;
+    float sqt[kLzWin];
+    const bool ok = row_test ? lazy_replay_path<true, true>(t, j0, nj, alpha, two_l2, bd, sqt)
+                             : lazy_replay_path<true, false>(t, j0, nj, alpha, two_l2, bd, sqt);
+    const unsigned long long badm = __ballot(!ok);
+    if (l == 0) fast[row] = ((badm >> (threadIdx.x & 32)) & 0xFFFFFFFFull) == 0 ? 1 : 0;
+  }
+  if (row_test)
+    lazy_replay<true>(x, j0, nj, alpha, two_l2, bd, sq, W, M, V, e);
+  else
+    lazy_replay<false>(x, j0, nj, alpha, two_l2, bd, sq, W, M, V, e);
+  float4 *o = reinterpret_cast<float4 *>(out_lazy);
+  o[e] = x.w;
+  o[plane + e] = x.m;
+  o[2 * plane + e] = x.v;
+  Row3 y = x0;
+  for (int j = j0 < 0 ? 0 : j0; j < nj; ++j) {
+    float q;
+    LzRange unused{};
+    lazy_one_step<false, false>(y, alpha[j], two_l2, q, unused);
+  }
+  float4 *od = reinterpret_cast<float4 *>(out_dense);
+  od[e] = y.w;
+  od[plane + e] = y.m;
+  od[2 * plane + e] = y.v;
 }
 
 // ------------------------------------------------------------------------------------
@@ -3000,6 +3217,35 @@ int anirec_selftest_lazy_math(uint64_t n_div, uint64_t *counts2, void *stream) {
   else
     hipLaunchKernelGGL(k_selftest_lazy_math<1>, dim3(8192), dim3(256), 0, s, (unsigned long long)n_div,
                        reinterpret_cast<unsigned long long *>(counts2));
+  return (int)hipGetLastError();
+}
+
+int anirec_selftest_lazy_div(int32_t mode, uint32_t lo, uint32_t hi, uint64_t *counts4, void *stream) {
+  if (!counts4 || mode < 0 || mode > 2 || hi < lo) return ANIREC_EINVAL;
+  if (mode != 0 && hi > (1u << 23)) return ANIREC_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const uint64_t init[4] = {0, 0, ~0ull, 0};
+  ANIREC_HIP_CHECK(hipMemcpyAsync(counts4, init, sizeof(init), hipMemcpyHostToDevice, s));
+  ANIREC_HIP_CHECK(hipStreamSynchronize(s));  // (init lives on this stack frame)
+  unsigned long long *c = reinterpret_cast<unsigned long long *>(counts4);
+  if (mode == 0) {
+    hipLaunchKernelGGL(k_selftest_lazy_div<0>, dim3(8192), dim3(256), 0, s, lo, hi, c);
+  } else if (hi > lo) {
+    if (mode == 1)
+      hipLaunchKernelGGL(k_selftest_lazy_div<1>, dim3(hi - lo), dim3(256), 0, s, lo, hi, c);
+    else
+      hipLaunchKernelGGL(k_selftest_lazy_div<2>, dim3(hi - lo), dim3(256), 0, s, lo, hi, c);
+  }
+  return (int)hipGetLastError();
+}
+
+int anirec_selftest_lazy_replay(const float *wmv, int32_t rows, const float *alpha8, int32_t nj, const int32_t *j0,
+                                float two_l2, int32_t row_test, float *out_lazy, float *out_dense, int32_t *fast,
+                                void *stream) {
+  if (!wmv || !alpha8 || !j0 || !out_lazy || !out_dense || !fast || rows <= 0 || nj < 0 || nj > ANIREC_LAZY_WINDOW)
+    return ANIREC_EINVAL;
+  hipLaunchKernelGGL(k_selftest_lazy_replay, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream,
+                     wmv, (int)rows, alpha8, (int)nj, j0, two_l2, out_lazy, out_dense, fast, (int)(row_test != 0));
   return (int)hipGetLastError();
 }
 

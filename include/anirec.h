@@ -330,6 +330,22 @@ int anirec_opt_flat(int32_t kind, float *w, float *slot, const float *g, size_t 
  * pairs of the admitted ranges.  counts2[0] / counts2[1] (device, uint64) receive the numbers of mismatches. */
 int anirec_selftest_lazy_math(uint64_t n_div, uint64_t *counts2, void *stream);
 
+/* Self-test of the replay's one-correction divide (tests only).  mode 0: its refined reciprocal against 1.0f / d on
+ * EVERY float whose bits lie in [lo, hi]; mode 1: the quotient against IEEE `/` on every significand pair n, d in
+ * [1, 2) with d's 23 significand bits in [lo, hi) (hi <= 2^23) and all 2^23 n's; mode 2: the same for the uncorrected
+ * product n * y (must report misses).  counts4 (device, uint64): mismatches, operands checked, min / max bits of a
+ * failing d (~0 / 0 if none). */
+int anirec_selftest_lazy_div(int32_t mode, uint32_t lo, uint32_t hi, uint64_t *counts4, void *stream);
+
+/* Self-test of the lazy replay on given rows (tests only): wmv = W, M, V planes [3][rows][128] (device fp32); every
+ * row takes the L2-only Adam steps [j0[row], nj) of alpha8[0..nj) (nj <= ANIREC_LAZY_WINDOW) once by the replay
+ * (short sequences, range test, redo by the full expansions) into out_lazy, once by the dense update into out_dense
+ * (same layout); fast[row] = 1 if the row passed the short sequences' range test — the flush's once-per-row test
+ * (row_test != 0) or the catch-up's per-step one. */
+int anirec_selftest_lazy_replay(const float *wmv, int32_t rows, const float *alpha8, int32_t nj, const int32_t *j0,
+                                float two_l2, int32_t row_test, float *out_lazy, float *out_dense, int32_t *fast,
+                                void *stream);
+
 /* Epoch shuffle: out[i] = in[perm[i]] for the three rating columns (model.fit shuffle=True). */
 int anirec_gather_ratings(const int32_t *user_in, const int32_t *anime_in, const float *rating_in,
                           const int64_t *perm, size_t n, int32_t *user_out, int32_t *anime_out,

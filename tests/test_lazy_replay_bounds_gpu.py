@@ -1,0 +1,194 @@
+"""GPU tests of the lazy replay's one-correction divide and its once-per-row range test (anirec_train.hip,
+div4_normal / lz_bound / lz_entry_ok): the divide is checked by exhaustion — its reciprocal on every float of the
+denominator range, its quotient on every significand pair — and the replay is held bitwise to the dense update on
+rows built to sit at each edge of the range test, on both sides of it."""
+import ctypes as C
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+def _lib():
+    from anime_recommendations_amd import _lib
+    return _lib, _lib.load()
+
+
+def _bits(x):
+    return struct.unpack("<I", struct.pack("<f", x))[0]
+
+
+def _div_counts(mode, lo, hi):
+    _l, lib = _lib()
+    cnt = torch.zeros(4, dtype=torch.int64, device="cuda")
+    _l.check(lib.anirec_selftest_lazy_div(mode, C.c_uint32(lo), C.c_uint32(hi), _l.ptr(cnt), None),
+             "anirec_selftest_lazy_div")
+    torch.cuda.synchronize()
+    return [int(x) & 0xFFFFFFFFFFFFFFFF for x in cnt.tolist()]
+
+
+def test_refined_reciprocal_is_ieee_on_every_float_of_the_denominator_range():
+    """y = y0 + (1 - d y0) y0, y0 = v_rcp_f32(d), equals 1.0f / d for EVERY float d in [1e-7, 2^48] (72 binades)."""
+    lo, hi = _bits(np.float32(1e-7)), _bits(2.0 ** 48)
+    bad, seen, fmin, fmax = _div_counts(0, lo, hi)
+    assert seen == hi - lo + 1
+    assert bad == 0, "%d denominators miss, bits %08x .. %08x" % (bad, fmin, fmax)
+
+
+def test_one_correction_quotient_is_ieee_on_every_significand_pair():
+    """q1 = q0 + (n - d q0) y equals IEEE n / d for all 2^46 significand pairs n, d in [1, 2); with the reciprocal
+    exact on the whole range, that is every operand pair the replay admits (div4_normal's comment)."""
+    bad = seen = 0
+    step = 1 << 19
+    for lo in range(0, 1 << 23, step):
+        b, s, _, _ = _div_counts(1, lo, lo + step)
+        bad += b
+        seen += s
+    assert seen == 1 << 46
+    assert bad == 0
+
+
+def test_uncorrected_quotient_misses_so_the_pair_comparison_can_fail():
+    bad, seen, fmin, fmax = _div_counts(2, 0, 256)
+    assert seen == 256 << 23
+    assert bad > 1000 and fmin <= fmax
+
+
+# ---- the replay on edge rows ------------------------------------------------------------------------------------
+def _alphas(lr=1e-5, t0=0, n=8):
+    b1, b2 = np.float32(0.9), np.float32(0.999)
+    t = np.arange(t0 + 1, t0 + n + 1, dtype=np.float32)
+    return (np.float32(lr) * np.sqrt(np.float32(1) - b2 ** t) / (np.float32(1) - b1 ** t)).astype(np.float32)
+
+
+def _replay(W, M, V, alpha, nj, j0, two_l2, row_test=1):
+    _l, lib = _lib()
+    rows = W.shape[0]
+    wmv = torch.from_numpy(np.stack([W, M, V]).astype(np.float32)).cuda().contiguous()
+    al = torch.from_numpy(np.asarray(alpha, np.float32)).cuda()
+    j0t = torch.from_numpy(np.asarray(j0, np.int32)).cuda()
+    out_l = torch.empty_like(wmv)
+    out_d = torch.empty_like(wmv)
+    fast = torch.full((rows,), -1, dtype=torch.int32, device="cuda")
+    _l.check(lib.anirec_selftest_lazy_replay(_l.ptr(wmv), rows, _l.ptr(al), nj, _l.ptr(j0t), C.c_float(two_l2),
+                                             row_test, _l.ptr(out_l), _l.ptr(out_d), _l.ptr(fast), None),
+             "anirec_selftest_lazy_replay")
+    torch.cuda.synchronize()
+    return out_l.cpu().numpy(), out_d.cpu().numpy(), fast.cpu().numpy()
+
+
+def _assert_bitwise(out_l, out_d):
+    a, b = out_l.view(np.uint32), out_d.view(np.uint32)
+    bad = np.argwhere(a != b)
+    assert bad.size == 0, "%d elements differ, first %s" % (len(bad), bad[:4].tolist())
+
+
+def _rows(n, rng, w=0.05, m=1e-5, v=1e-10):
+    W = rng.uniform(-w, w, (n, 128)).astype(np.float32)
+    # m of w's sign: the L2 gradient 2 lambda w never pulls it through zero (that case has a test of its own)
+    M = (rng.uniform(0.5, 1.5, (n, 128)) * m * np.where(W < 0, -1, 1)).astype(np.float32)
+    V = (rng.uniform(0.5, 1.5, (n, 128)) * v).astype(np.float32)
+    return W, M, V
+
+
+def _check_family(W, M, V, two_l2, alpha, rng, partial=True):
+    """whole windows, then ragged starts; returns the fast flags of the whole-window run"""
+    rows = W.shape[0]
+    out_l, out_d, fast = _replay(W, M, V, alpha, 8, np.zeros(rows, np.int32), two_l2)
+    _assert_bitwise(out_l, out_d)
+    assert set(np.unique(fast)) <= {0, 1}
+    if partial:
+        for nj in (1, 3, 8):
+            j0 = rng.integers(0, nj + 1, rows).astype(np.int32)
+            for row_test in (1, 0):            # the flush's once-per-row test, the catch-up's per-step one
+                o_l, o_d, _ = _replay(W, M, V, alpha, nj, j0, two_l2, row_test)
+                _assert_bitwise(o_l, o_d)
+    return fast
+
+
+def test_replay_typical_rows_take_the_fast_path():
+    rng = np.random.default_rng(1)
+    W, M, V = _rows(4096, rng)
+    fast = _check_family(W, M, V, 2e-4, _alphas(), rng)
+    assert fast.all()
+
+
+def test_replay_rows_fresh_from_initialisation_take_the_fast_path():
+    """m_0 = v_0 = 0, the moments' initial values: the first step lifts v to c2 (2 lambda w)^2, so the first window's
+    rows are admitted as the per-step test of the moments admitted them"""
+    rng = np.random.default_rng(6)
+    n = 4096
+    W = rng.uniform(-0.05, 0.05, (n, 128)).astype(np.float32)
+    Z = np.zeros_like(W)
+    fast = _check_family(W, Z, Z, 2e-4, _alphas(), rng)
+    assert fast.all()
+
+
+def test_replay_second_moment_at_its_lower_and_upper_thresholds():
+    rng = np.random.default_rng(2)
+    n = 1024
+    W, M, V = _rows(n, rng)
+    lo = np.float32(2.0 ** -95)
+    below, hi = np.nextafter(lo, np.float32(0)), np.float32(2.0 ** 95)
+    vals = np.array([lo, below, np.nextafter(lo, np.float32(1)), hi, np.nextafter(hi, np.float32(np.inf)),
+                     np.nextafter(hi, np.float32(0))], np.float32)
+    pick = (np.arange(n) // 2) % len(vals)     # the two rows of a wave share their kind: each edge gets fast waves
+    V[:, 0] = vals[pick]                       # one element of each row sits at the edge
+    V[:, 1:] = np.float32(2.0 ** -90)
+    fast = _check_family(W, M, V, 0.0, _alphas(), rng)   # (no L2: the growth factor is 1, only v decides)
+    want = np.array([1, 0, 1, 1, 0, 1])[pick]
+    assert (fast == want).all(), (fast[:12], want[:12])
+
+
+def test_replay_first_moment_near_its_small_and_large_limits():
+    rng = np.random.default_rng(3)
+    n = 1024
+    s = (np.float32(2.0) ** np.linspace(-3, 3, n).astype(np.float32)).astype(np.float32)
+    # |m alpha| near 2^-60: without L2, m decays by 0.9 a step, so the smallest |m_j alpha_j| crosses 2^-60 inside
+    W, M, V = _rows(n, rng, m=1e-3, v=1.0)
+    alpha = _alphas()
+    M[:, 0] = (np.float32(2.0 ** -60) / alpha.min() * s).astype(np.float32)
+    fast = _check_family(W, M, V, 0.0, alpha, rng)
+    assert fast.any() and not fast.all()
+    # |m alpha| near 2^58, the growth bound's limit 2^58 / A (rates of 2^13 so that it, not 2^46, is the binding one)
+    W, M, V = _rows(n, rng, m=1e-3, v=1.0)
+    alpha = (_alphas() * np.float32(2.0 ** 31)).astype(np.float32)
+    assert np.float32(2.0 ** 58) / alpha.max() < 2.0 ** 46
+    M[:, 0] = (np.float32(2.0 ** 58) / alpha.max() * s).astype(np.float32)
+    fast = _check_family(W, M, V, 0.0, alpha, rng)
+    assert fast.any() and not fast.all()
+
+
+def test_replay_first_moment_crossing_zero_within_the_window():
+    rng = np.random.default_rng(4)
+    n = 2048
+    two_l2 = np.float32(2e-4)
+    W, M, V = _rows(n, rng)
+    g = (W * two_l2).astype(np.float32)
+    # m_0 = -g k: m_j = 0.9^j m_0 + (1 - 0.9^j) g crosses zero at 0.9^j = 1 / (1 + k), k chosen to cross inside
+    k = np.float32(1) / np.float32(0.9) ** rng.integers(1, 9, (n, 1)).astype(np.float32) - np.float32(1)
+    M[:] = (-g * k * rng.uniform(0.999, 1.001, (n, 128))).astype(np.float32)
+    M[::2] = (-g[::2] / np.float32(9)).astype(np.float32)  # m_1 = 0 up to rounding
+    fast = _check_family(W, M, V, float(two_l2), _alphas(), rng)
+    assert not fast.all()
+
+
+def test_replay_exact_zeros_and_non_finite_take_the_full_expansions():
+    rng = np.random.default_rng(5)
+    n = 560
+    W, M, V = _rows(n, rng)
+    kind = (np.arange(n) // 2) % 7             # the two rows of a wave share their kind
+    V[kind == 0, 3] = 0.0
+    W[kind == 0, 3] = 0.0                      # v = 0 and w = 0: no step lifts v
+    M[kind == 1, 5] = 0.0
+    W[kind == 1, 5] = 0.0                      # m = 0 and w = 0: m stays 0
+    W[kind == 2, 7] = 0.0                      # w = 0 alone: m and v still in range
+    M[kind == 3, 9] = np.inf
+    V[kind == 4, 11] = np.nan
+    V[kind == 6, 13] = 0.0                     # v = 0 alone: the first step lifts it to c2 (2 lambda w)^2
+    fast = _check_family(W, M, V, 2e-4, _alphas(), rng)
+    for k, want in ((0, 0), (1, 0), (2, 1), (3, 0), (4, 0), (5, 1), (6, 1)):
+        assert (fast[kind == k] == want).all(), (k, fast[kind == k])
