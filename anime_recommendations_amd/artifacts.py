@@ -47,11 +47,7 @@ def log_artifact(name, path, type=None, description=None, metadata=None):
     return dst
 
 
-def use_artifact(spec, type=None):
-    """Path of the single file of artifact ``name[:version]``.  A plain existing file path is
-    accepted too (so components can be pointed at files directly)."""
-    if os.path.isfile(spec):
-        return spec
+def _resolve(spec):
     name, ver = _split(spec)
     vs = _versions(name)
     if not vs:
@@ -61,5 +57,19 @@ def use_artifact(spec, type=None):
     if ver not in vs:
         raise FileNotFoundError("artifact %r has no version %s (have %s)" % (name, ver, vs))
     d = os.path.join(root_dir(), name, ver)
-    meta = json.load(open(os.path.join(d, "artifact.json")))
+    return d, json.load(open(os.path.join(d, "artifact.json")))
+
+
+def artifact_metadata(spec):
+    """The ``metadata`` dict ``log_artifact`` stored with artifact ``name[:version]`` (W&B's
+    ``Api().artifact(name).metadata``, which user_recs.py:632-679 assert_flow reads)."""
+    return _resolve(spec)[1]["metadata"]
+
+
+def use_artifact(spec, type=None):
+    """Path of the single file of artifact ``name[:version]``.  A plain existing file path is
+    accepted too (so components can be pointed at files directly)."""
+    if os.path.isfile(spec):
+        return spec
+    d, meta = _resolve(spec)
     return os.path.join(d, meta["file"])

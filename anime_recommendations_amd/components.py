@@ -303,3 +303,257 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
         "Premiered": rows["Premiered"].to_numpy(), "Score": rows["Score"].to_numpy(),
         "Type": rows["Type"].to_numpy()})
     return frame
+
+
+# ----------------------------------------------------------------------------------------
+# user_prefs / user_recs
+# ----------------------------------------------------------------------------------------
+MAX_CATEGORIES = 128     # anirec_fave_profile counts at most 128 categories per call
+MAX_SIM_USERS = 63       # anirec_user_recs(_ex): k_sim <= 63
+MAX_USER_RECS = 256      # anirec_user_recs(_ex): n_recs <= 256
+FAVE_COLUMNS = ["eng_version", "Source", "Genres"]
+USER_RECS_COLUMNS = ["anime_id", "Name", "n_user_prefs", "Source", "Genres", "Sypnopsis", "Episodes",
+                     "Japanese name", "Studios", "Premiered", "Score", "Type"]
+
+
+def load_user_anime_df(path):
+    """get_anime_df of user_prefs.py:62-80 / user_recs.py:104-126: 'Unknown' -> NaN, ``eng_version`` is the
+    anime's Name (get_anime_name), rows in file order (no sort, unlike similar_anime's loader)."""
+    df = pd.read_csv(path)
+    df = df.replace("Unknown", np.nan)
+    df["anime_id"] = df["MAL_ID"]
+    df["japanese_name"] = df["Japanese name"]
+    first = df.drop_duplicates("anime_id").set_index("anime_id")["Name"]
+    df["eng_version"] = first.reindex(df["anime_id"]).to_numpy()
+    keep = ["anime_id", "eng_version", "Score", "Genres", "Episodes", "Premiered", "Studios", "japanese_name",
+            "Name", "Type", "Source", "Rating", "Members"]
+    return df[[c for c in keep if c in df.columns]]
+
+
+def category_tokens(cell):
+    """The tokens get_genres / get_sources (user_prefs.py:95-136) count for one Genres / Source cell:
+    ``str`` cells only, ``split(',')``, each ``strip()``ped."""
+    return [t.strip() for t in cell.split(",")] if isinstance(cell, str) else []
+
+
+def _category_bits(rows, n_cat):
+    """uint32 [len(rows), ceil(n_cat/32)]: bit c of row a set iff c is in rows[a]."""
+    bits = np.zeros((len(rows), max(1, (n_cat + 31) // 32)), np.uint32)
+    for a, cs in enumerate(rows):
+        for c in cs:
+            bits[a, c >> 5] |= np.uint32(1) << np.uint32(c & 31)
+    return bits
+
+
+def category_table(meta, column):
+    """(names, cat_bits) over the anime index: ``names`` the sorted distinct tokens of ``meta[column]``,
+    cat_bits uint32 [n_anime, ceil(len(names)/32)] with bit c of row a set iff anime a carries names[c]."""
+    cells = meta[column].tolist()
+    names = sorted({t for cell in cells for t in category_tokens(cell)})
+    if len(names) > MAX_CATEGORIES:
+        raise ValueError("column %r holds %d distinct tokens; the favourite-profile kernel counts at most %d "
+                         "categories (anirec_fave_profile)" % (column, len(names), MAX_CATEGORIES))
+    index = {n: i for i, n in enumerate(names)}
+    return names, _category_bits([[index[t] for t in category_tokens(cell)] for cell in cells], len(names))
+
+
+def favourite_indices(fav_bits, u, n_anime):
+    """Anime indices whose bit is set in row ``u`` of the favourite-bit matrix (a torch tensor)."""
+    row = fav_bits[int(u)].cpu().numpy().view(np.uint32)
+    bits = np.unpackbits(row.view(np.uint8), bitorder="little")[:int(n_anime)]
+    return np.nonzero(bits)[0]
+
+
+def fave_frame(fav_idx, anime_ids, anime_df):
+    """fave_genres + fave_sources + get_fave_df (user_prefs.py:215-275): the anime_df rows whose id is a
+    favourite, in anime_df order and with anime_df's index, columns eng_version, Source, Genres."""
+    ids = np.asarray(anime_ids)[np.asarray(fav_idx, np.int64)]
+    f = anime_df[anime_df["anime_id"].isin(ids)]
+    return pd.DataFrame(f[FAVE_COLUMNS])
+
+
+def favourite_profiles(fav_bits, meta, users):
+    """Genre and Source histograms of the favourites of ``users`` (user indices): one ({genre: count},
+    {source: count}) pair per user, keyed as get_genres / get_sources key them (only tokens that occur).
+    One anirec_fave_profile call over both tables (Source tokens after the genre tokens) when they fit its
+    128 categories together, one call per table otherwise."""
+    from . import recs
+    gcells, scells = meta["Genres"].tolist(), meta["Source"].tolist()
+    gnames, gbits = category_table(meta, "Genres")
+    snames, sbits = category_table(meta, "Source")
+    ng, ns = len(gnames), len(snames)
+    if ng + ns <= MAX_CATEGORIES:
+        gi = {n: i for i, n in enumerate(gnames)}
+        si = {n: ng + i for i, n in enumerate(snames)}
+        rows = [[gi[t] for t in category_tokens(g)] + [si[t] for t in category_tokens(x)]
+                for g, x in zip(gcells, scells)]
+        tables = [(ng + ns, _category_bits(rows, ng + ns))]
+    else:
+        tables = [(ng, gbits), (ns, sbits)]
+    counts = [recs.fave_profile(fav_bits, bits, n, users=users).cpu().numpy() if n else
+              np.zeros((len(users), 0), np.int32) for n, bits in tables]
+    allc = np.concatenate(counts, axis=1)
+    return [({n: int(c) for n, c in zip(gnames, allc[r, :ng]) if c > 0},
+             {n: int(c) for n, c in zip(snames, allc[r, ng:]) if c > 0}) for r in range(len(users))]
+
+
+def rating_indices(df, user_ids, anime_ids):
+    """The rating table as (user index, anime index, rating) by the model's id tables (not by a re-encoded,
+    filtered frame: the reference's index mismatch); rows whose ids the tables lack are dropped."""
+    ui = pd.Index(np.asarray(user_ids)).get_indexer(df["user_id"].to_numpy())
+    ai = pd.Index(np.asarray(anime_ids)).get_indexer(df["anime_id"].to_numpy())
+    ok = (ui >= 0) & (ai >= 0)
+    return ui[ok].astype(np.int32), ai[ok].astype(np.int32), df["rating"].to_numpy(np.float64)[ok]
+
+
+def favourite_bits(df, user_ids, anime_ids, percentile):
+    """Favourite-bit rows of every user (rating >= np.percentile of the user's OWN ratings, over all of them)."""
+    import torch
+    from . import recs
+    ui, ai, r = rating_indices(df, user_ids, anime_ids)
+    dev = torch.device("cuda")
+    fav, _ = recs.user_favourites(torch.from_numpy(ui).to(dev), torch.from_numpy(ai).to(dev),
+                                  torch.from_numpy(r).to(dev), len(user_ids), len(anime_ids), float(percentile))
+    return fav
+
+
+def random_user(df, min_ratings=400):
+    """get_random_user (user_prefs.py:195-209, user_recs.py:245-259): a random user of the >= 400-rating frame
+    main_df_by_id keeps; every user when none has that many."""
+    import random
+    n = df["user_id"].value_counts(dropna=True)
+    pool = n[n >= int(min_ratings)].index.tolist() or n.index.tolist()
+    return int(random.choice(pool))
+
+
+def user_index(user_ids, user_id):
+    pos = np.nonzero(np.asarray(user_ids) == int(user_id))[0]
+    if len(pos) == 0:
+        raise ValueError("user id %r is not in the model's user table" % (user_id,))
+    return int(pos[0])
+
+
+def user_prefs_frame(fav_bits, user_ids, anime_ids, anime_df, user_id):
+    """(fave_df, genre_freq, source_freq) of one user (user_prefs.py:215-275 and get_genres / get_sources):
+    the favourites frame and the two word-cloud frequency dicts, from one anirec_fave_profile call."""
+    u = user_index(user_ids, user_id)
+    fave_df = fave_frame(favourite_indices(fav_bits, u, len(anime_ids)), anime_ids, anime_df)
+    meta = metadata_by_index(anime_ids, anime_df)
+    genre_freq, source_freq = favourite_profiles(fav_bits, meta, [u])[0]
+    return fave_df, genre_freq, source_freq
+
+
+def _bits_of(mask):
+    n = len(mask)
+    bits = np.zeros((n + 31) // 32, np.uint32)
+    nz = np.nonzero(mask)[0]
+    np.bitwise_or.at(bits, nz >> 5, np.uint32(1) << (nz & 31).astype(np.uint32))
+    return bits
+
+
+def check_user_recs_limits(n_sim, n_recs):
+    if not 1 <= int(n_sim) <= MAX_SIM_USERS:
+        raise ValueError("recs_n_sim_ID = %d: anirec_user_recs counts the favourites of 1 to %d similar users "
+                         "(k_sim <= 63)" % (int(n_sim), MAX_SIM_USERS))
+    if not 1 <= int(n_recs) <= MAX_USER_RECS:
+        raise ValueError("user_num_recs = %d: anirec_user_recs returns 1 to %d anime per query (n_recs <= 256)"
+                         % (int(n_recs), MAX_USER_RECS))
+
+
+def user_recs_frame(fav_bits, user_ids, anime_ids, anime_df, syn_df, sim_user_ids, fave_df, n, genres=None):
+    """similar_user_recs (user_recs.py:708-794): count how many of the similar users (ids, best first) hold each
+    anime as a favourite, skip every anime whose eng_version is named in the query's favourites frame (:743,753),
+    keep anime present in all_anime.csv, rank by (count desc, best similar-user rank asc, anime index asc), first n.
+    ``genres`` (--ID_spec_genres): by_genre's order — the ranked matches of genre 1, then those of genre 2 not yet
+    listed, then genre 3 — cut at n.  Returns the reference's 12-column frame."""
+    from . import recs
+    check_user_recs_limits(len(sim_user_ids), n)
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    names = set(fave_df["eng_version"].tolist())
+    excl = _bits_of(meta["eng_version"].isin(names).to_numpy() & meta["has_meta"].to_numpy())
+    keep = meta["has_meta"].to_numpy()
+    uid = pd.Index(np.asarray(user_ids))
+    sim = uid.get_indexer(np.asarray(sim_user_ids)).astype(np.int32)[None, :]        # unknown ids: -1 = empty
+    masks = [keep]
+    if genres is not None:
+        check_genres(genres, anime_df)
+        wanted = [g for g in clean(list(genres)) if g != "none"]
+        masks = [keep & genre_mask(meta["Genres"], [g]) for g in wanted]
+    order, counts = [], []
+    for m in masks:
+        a, c = recs.user_recs(fav_bits, len(anime_ids), None, sim, int(n), exclude=excl[None, :], keep=_bits_of(m))
+        for ai, ci in zip(a.cpu().numpy()[0].tolist(), c.cpu().numpy()[0].tolist()):
+            if ai >= 0 and ai not in order:
+                order.append(ai)
+                counts.append(ci)
+    order, counts = order[:int(n)], counts[:int(n)]
+    rows = meta.iloc[order]
+    return pd.DataFrame({
+        "anime_id": rows["anime_id"].to_numpy(), "Name": rows["Name"].to_numpy(),
+        "n_user_prefs": np.asarray(counts, np.int64), "Source": rows["Source"].to_numpy(),
+        "Genres": rows["Genres"].to_numpy(), "Sypnopsis": rows["Sypnopsis"].to_numpy(),
+        "Episodes": rows["Episodes"].to_numpy(), "Japanese name": rows["japanese_name"].to_numpy(),
+        "Studios": rows["Studios"].to_numpy(), "Premiered": rows["Premiered"].to_numpy(),
+        "Score": rows["Score"].to_numpy(), "Type": rows["Type"].to_numpy()}, columns=USER_RECS_COLUMNS)
+
+
+_CLOUD_NOTE = []
+
+
+def word_cloud(freqs, fn, width, height, background, colormap):
+    """genre_cloud / source_cloud (user_prefs.py:139-190): a word cloud of ``freqs`` written to ``fn``.  With the
+    wordcloud package: the reference's WordCloud parameters.  Without it: a matplotlib PNG of width x height pixels
+    showing the same words, sized by frequency (logged once).  Returns what show_cloud can display."""
+    width, height = int(width), int(height)
+    try:
+        from wordcloud import WordCloud
+    except ImportError:
+        WordCloud = None
+    if WordCloud is not None and freqs:
+        cloud = WordCloud(width=width, height=height, prefer_horizontal=0.85, background_color=background,
+                          contour_width=0.05, colormap=colormap).generate_from_frequencies(freqs)
+        cloud.to_file(fn)
+        return cloud
+    if not _CLOUD_NOTE:
+        logging.getLogger().info("wordcloud is not installed: the word clouds are drawn with matplotlib")
+        _CLOUD_NOTE.append(True)
+    from matplotlib import colormaps
+    from matplotlib.backends.backend_agg import FigureCanvasAgg
+    from matplotlib.figure import Figure
+    fig = Figure(figsize=(width / 100.0, height / 100.0), dpi=100, facecolor=background)
+    FigureCanvasAgg(fig)
+    ax = fig.add_axes([0, 0, 1, 1])
+    ax.set_axis_off()
+    ax.set_facecolor(background)
+    words = sorted(freqs.items(), key=lambda kv: (-kv[1], kv[0]))
+    top = max(freqs.values()) if freqs else 1
+    cols = max(1, int(np.ceil(np.sqrt(len(words))))) if words else 1
+    rows = max(1, int(np.ceil(len(words) / cols))) if words else 1
+    cmap = colormaps[colormap]
+    for i, (w, f) in enumerate(words):
+        x, y = (i % cols + 0.5) / cols, 1.0 - (i // cols + 0.5) / rows
+        ax.text(x, y, w, ha="center", va="center", fontsize=6 + 18 * f / top, color=cmap(0.15 + 0.7 * f / top),
+                transform=ax.transAxes)
+    fig.savefig(fn, dpi=100, facecolor=background)
+    return fig
+
+
+def show_cloud(cloud, interval):
+    """show_cloud (user_prefs.py:193-206): display for ``interval`` ms — only where the backend is interactive."""
+    import matplotlib
+    import matplotlib.pyplot as plt
+    if matplotlib.get_backend().lower() in ("agg", "pdf", "ps", "svg", "cairo", "template") or \
+            "inline" in matplotlib.get_backend().lower():
+        return False
+    fig = plt.figure(figsize=(8, 6))
+    timer = fig.canvas.new_timer(interval=int(interval))
+    timer.add_callback(plt.close)
+    if hasattr(cloud, "to_array"):
+        plt.imshow(cloud, interpolation="bilinear")
+    else:
+        cloud.canvas.draw()
+        plt.imshow(np.asarray(cloud.canvas.buffer_rgba()), interpolation="bilinear")
+    plt.axis("off")
+    timer.start()
+    plt.show()
+    return True

@@ -409,6 +409,8 @@ struct RecsArgs {
   int nq, k_sim, n_recs;
   int32_t *out_anime;    // [nq][n_recs], -1 padded
   int32_t *out_count;    // [nq][n_recs], 0 padded
+  const uint32_t *excl;  // [nq][wwords] skipped set of query q (anirec_user_recs_ex); nullptr: fav[query[q]]
+  const uint32_t *keep;  // [wwords] only these anime are candidates; nullptr: every anime
 };
 constexpr int kRecsMaxSim = 64;
 constexpr int kRecsMaxOut = 256;
@@ -459,7 +461,7 @@ __global__ __launch_bounds__(256) void k_user_recs(RecsArgs a) {
   __shared__ int n_win;
   __shared__ int wsum[4], tot[2][4];
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  const int qu = a.query[q];
+  const int qu = a.excl ? -1 : a.query[q];
   if (tid < a.k_sim) {
     const int su = a.sim[(size_t)q * a.k_sim + tid];
     sims[tid] = (su < 0 || su >= a.n_users) ? -1 : su;
@@ -517,9 +519,16 @@ __global__ __launch_bounds__(256) void k_user_recs(RecsArgs a) {
 #pragma unroll
     for (int r = 0; r < kR; ++r) {
       const int w = r * 256 + tid;
-      const uint32_t own = (qu >= 0 && qu < a.n_users && w < a.wwords) ? a.fav[(size_t)qu * a.wwords + w] : 0u;
+      uint32_t own = 0u;
+      if (w < a.wwords) {
+        if (a.excl)
+          own = a.excl[(size_t)q * a.wwords + w];
+        else if (qu >= 0 && qu < a.n_users)
+          own = a.fav[(size_t)qu * a.wwords + w];
+      }
       const int left = a.n_anime - w * 32;  // bits of the last word past n_anime are not anime
-      const uint32_t valid = left >= 32 ? ~0u : (left > 0 ? (1u << left) - 1u : 0u);
+      uint32_t valid = left >= 32 ? ~0u : (left > 0 ? (1u << left) - 1u : 0u);
+      if (a.keep && w < a.wwords) valid &= a.keep[w];
       ok[r] = seen[r] & ~own & valid;
     }
   }
@@ -664,6 +673,95 @@ __global__ __launch_bounds__(256) void k_user_recs(RecsArgs a) {
   }
 }
 
+// Favourite profiles: counts[r][c] = number of favourites of user users[r] (or r) that carry category c
+// (user_prefs.py:95-136 get_genres / get_sources over the favourites frame: a histogram of the Genres / Source tokens).
+// One wave per row.  The row's 549 words (17 560 anime) are read by the wave with one coalesced load per 64 words, all
+// in flight together.  The set bits are sparse (a user's favourites are ~20 % of ~300 ratings: ~60 of 17 560 bits),
+// so they are first COMPACTED into a wave-private list of anime indices in LDS: each round every lane whose word still
+// has a bit hands in its lowest one at position pending + mbcnt(ballot).  Every 64 listed anime are then counted with
+// their 64 category rows held one per lane: for each category c, popcount(ballot(bit c)) adds to the counter that lane
+// c % 64 keeps for it.  That costs ~4 instructions per category per 64 favourites instead of one LDS atomic per
+// (favourite, category), which would queue on the few categories (Action, Comedy) most anime carry.  Integer counts:
+// the order of the additions cannot change them.
+constexpr int kProfMaxCat = 128;
+constexpr int kProfLoads = 16;  // words per lane requested together: 1 024 words of a row in flight per wave
+template <int kCW>  // words of a category row (ceil(n_cat / 32))
+__global__ __launch_bounds__(256) void k_fave_profile(const uint32_t *__restrict__ fav, int n_users, int n_anime,
+                                                      int wwords, const int32_t *__restrict__ users, int n_rows,
+                                                      const uint32_t *__restrict__ cat, int n_cat,
+                                                      int32_t *__restrict__ counts, int32_t *__restrict__ err) {
+  __shared__ int32_t lists[4][128];  // pending (<= 63) + one round (<= 64)
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int r = blockIdx.x * 4 + w;
+  if (r >= n_rows) return;  // whole wave leaves together; no block barrier below
+  int32_t *list = lists[w];
+  const int u = users ? users[r] : r;
+  const bool bad = u < 0 || u >= n_users;
+  if (bad && lane == 0) *err = 1;
+  uint32_t acc0 = 0, acc1 = 0;  // counts of categories lane and lane + 64
+  int pending = 0;
+  // count the categories of list[0 .. n), n <= 64
+  auto flush = [&](int n) {
+    const int a = lane < n ? list[lane] : -1;
+    uint32_t cv[kCW];
+#pragma unroll
+    for (int k = 0; k < kCW; ++k) cv[k] = a >= 0 ? cat[(size_t)a * kCW + k] : 0u;
+#pragma unroll
+    for (int k = 0; k < kCW; ++k) {
+#pragma unroll 8
+      for (int b = 0; b < 32; ++b) {
+        const int c = k * 32 + b;
+        if (c >= n_cat) break;
+        const uint32_t pc = (uint32_t)__popcll(__ballot((cv[k] >> b) & 1u));
+        if (c < 64) {
+          acc0 += lane == c ? pc : 0u;
+        } else {
+          acc1 += lane == c - 64 ? pc : 0u;
+        }
+      }
+    }
+  };
+  const uint32_t *row = fav + (size_t)(bad ? 0 : u) * wwords;
+  for (int base = 0; !bad && base < wwords; base += kProfLoads * 64) {
+    uint32_t v[kProfLoads];
+#pragma unroll
+    for (int g = 0; g < kProfLoads; ++g) {
+      const int x = base + g * 64 + lane;
+      v[g] = x < wwords ? row[x] : 0u;
+    }
+#pragma unroll
+    for (int g = 0; g < kProfLoads; ++g) {
+      const int x = base + g * 64 + lane;
+      const int left = n_anime - x * 32;  // bits of the last word past n_anime are not anime
+      uint32_t word = v[g] & (left >= 32 ? ~0u : (left > 0 ? (1u << left) - 1u : 0u));
+      for (;;) {
+        const unsigned long long m = __ballot(word != 0u);
+        if (m == 0ull) break;
+        if (word) {
+          const int pos = pending + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+          list[pos] = x * 32 + (__ffs(word) - 1);
+          word &= word - 1u;
+        }
+        pending += __popcll(m);
+        __builtin_amdgcn_wave_barrier();
+        if (pending >= 64) {
+          flush(64);
+          pending -= 64;
+          const int t = lane < pending ? list[64 + lane] : 0;  // the rest moves to the front
+          __builtin_amdgcn_wave_barrier();
+          if (lane < pending) list[lane] = t;
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
+    }
+  }
+  if (pending > 0) flush(pending);
+  int32_t *out = counts + (size_t)r * n_cat;
+  if (lane < n_cat) out[lane] = (int32_t)acc0;
+  if (lane + 64 < n_cat) out[lane + 64] = (int32_t)acc1;
+}
+
 static inline size_t al256r(size_t x) { return (x + 255) / 256 * 256; }
 static inline int grid_rec(int64_t n) {
   int64_t b = (n + 255) / 256;
@@ -675,6 +773,8 @@ static inline int grid_rec(int64_t n) {
 }  // namespace anirec
 
 using namespace anirec;
+
+static int launch_user_recs(const RecsArgs &a, void *stream);
 
 extern "C" {
 
@@ -756,6 +856,72 @@ int anirec_user_recs(const uint32_t *fav_bits, int32_t n_users, int32_t n_anime,
   a.n_recs = n_recs;
   a.out_anime = out_anime;
   a.out_count = out_count;
+  a.excl = nullptr;
+  a.keep = nullptr;
+  return launch_user_recs(a, stream);
+}
+
+int anirec_user_recs_ex(const uint32_t *fav_bits, int32_t n_users, int32_t n_anime, const int32_t *sim_users,
+                        int32_t nq, int32_t k_sim, const uint32_t *exclude_bits, const uint32_t *keep_bits,
+                        int32_t n_recs, int32_t *out_anime, int32_t *out_count, void *stream) {
+  if (!fav_bits || !sim_users || !exclude_bits || !out_anime || !out_count) return ANIREC_EINVAL;
+  if (n_users < 1 || n_anime < 1 || n_anime >= (1 << 17) || nq < 0 || k_sim < 1 || k_sim > kRecsMaxSim - 1 ||
+      n_recs < 1 || n_recs > kRecsMaxOut)
+    return ANIREC_EINVAL;
+  if (nq == 0) return ANIREC_OK;
+  RecsArgs a;
+  a.fav = fav_bits;
+  a.n_users = n_users;
+  a.n_anime = n_anime;
+  a.wwords = (n_anime + 31) / 32;
+  a.query = nullptr;
+  a.sim = sim_users;
+  a.nq = nq;
+  a.k_sim = k_sim;
+  a.n_recs = n_recs;
+  a.out_anime = out_anime;
+  a.out_count = out_count;
+  a.excl = exclude_bits;
+  a.keep = keep_bits;
+  return launch_user_recs(a, stream);
+}
+
+int anirec_fave_profile(const uint32_t *fav_bits, int32_t n_users, int32_t n_anime, const int32_t *users,
+                        int32_t n_rows, const uint32_t *cat_bits, int32_t n_cat, int32_t *counts, int32_t *err_flag,
+                        void *stream) {
+  if (!fav_bits || !cat_bits || !counts || !err_flag) return ANIREC_EINVAL;
+  if (n_users < 1 || n_anime < 1 || n_rows < 0 || n_cat < 1 || n_cat > kProfMaxCat) return ANIREC_EINVAL;
+  if (!users && n_rows != n_users) return ANIREC_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
+  if (n_rows == 0) return ANIREC_OK;
+  const int wwords = (n_anime + 31) / 32;
+  const dim3 grid((unsigned)((n_rows + 3) / 4)), block(256);
+  switch ((n_cat + 31) / 32) {
+    case 1:
+      hipLaunchKernelGGL(k_fave_profile<1>, grid, block, 0, s, fav_bits, n_users, n_anime, wwords, users, n_rows,
+                         cat_bits, n_cat, counts, err_flag);
+      break;
+    case 2:
+      hipLaunchKernelGGL(k_fave_profile<2>, grid, block, 0, s, fav_bits, n_users, n_anime, wwords, users, n_rows,
+                         cat_bits, n_cat, counts, err_flag);
+      break;
+    case 3:
+      hipLaunchKernelGGL(k_fave_profile<3>, grid, block, 0, s, fav_bits, n_users, n_anime, wwords, users, n_rows,
+                         cat_bits, n_cat, counts, err_flag);
+      break;
+    default:
+      hipLaunchKernelGGL(k_fave_profile<4>, grid, block, 0, s, fav_bits, n_users, n_anime, wwords, users, n_rows,
+                         cat_bits, n_cat, counts, err_flag);
+      break;
+  }
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"
+
+static int launch_user_recs(const RecsArgs &a, void *stream) {
+  const int k_sim = a.k_sim, nq = a.nq, wwords = a.wwords;
   // a lane holds kR words of 32 anime in registers, as kP bit planes
 #define ANIREC_RECS(R)                                                                              \
   do {                                                                                              \
@@ -780,5 +946,3 @@ int anirec_user_recs(const uint32_t *fav_bits, int32_t n_users, int32_t n_anime,
 #undef ANIREC_RECS
   return (int)hipGetLastError();
 }
-
-}  // extern "C"

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -48,19 +49,71 @@ def user_favourites(user_idx, anime_idx, rating, n_users, n_anime, percentile=80
     return fav, thr
 
 
-def user_recs(fav_bits, n_anime, query_users, sim_users, n_recs):
+def _bit_words(x, shape, dev, what):
+    """32-bit words on ``dev``, contiguous, of the given shape (a NumPy uint32 / int32 array or an int32 tensor)."""
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x).view(np.int32))
+    x = x.to(device=dev).contiguous()
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError("%s: expected shape %s, got %s" % (what, tuple(shape), tuple(x.shape)))
+    return x
+
+
+def user_recs(fav_bits, n_anime, query_users, sim_users, n_recs, exclude=None, keep=None):
     """Per query user the ``n_recs`` anime its similar users favourited most often (own favourites skipped).
     ``sim_users``: [nq, k_sim] user indices, best first, -1 = empty.  Returns (anime int32 [nq, n_recs]
-    (-1 padded), count int32 [nq, n_recs])."""
+    (-1 padded), count int32 [nq, n_recs]).
+
+    ``exclude`` ([nq, ceil(n_anime/32)] bit words) replaces the query user's own favourite row as the skipped set
+    (``query_users`` is then not read); ``keep`` ([ceil(n_anime/32)] bit words) limits the candidates to its set bits
+    (anirec_user_recs_ex).  With both None this is anirec_user_recs."""
     lib = _lib.load()
     dev = fav_bits.device
-    q = torch.as_tensor(query_users, device=dev).to(torch.int32).contiguous()
     sim = torch.as_tensor(sim_users, device=dev).to(torch.int32).contiguous()
     nq, k_sim = int(sim.shape[0]), int(sim.shape[1])
-    assert q.numel() == nq
     out_a = torch.empty(nq, int(n_recs), dtype=torch.int32, device=dev)
     out_c = torch.empty(nq, int(n_recs), dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_user_recs(_lib.ptr(fav_bits), int(fav_bits.shape[0]), int(n_anime), _lib.ptr(q),
-                                    _lib.ptr(sim), nq, k_sim, int(n_recs), _lib.ptr(out_a), _lib.ptr(out_c),
-                                    _stream()), "anirec_user_recs")
+    if exclude is None and keep is None:
+        q = torch.as_tensor(query_users, device=dev).to(torch.int32).contiguous()
+        assert q.numel() == nq
+        _lib.check(lib.anirec_user_recs(_lib.ptr(fav_bits), int(fav_bits.shape[0]), int(n_anime), _lib.ptr(q),
+                                        _lib.ptr(sim), nq, k_sim, int(n_recs), _lib.ptr(out_a), _lib.ptr(out_c),
+                                        _stream()), "anirec_user_recs")
+        return out_a, out_c
+    ww = (int(n_anime) + 31) // 32
+    if exclude is None:         # a keep mask alone: the query users' own favourites are still skipped
+        q = torch.as_tensor(query_users, device=dev).to(torch.long)
+        exclude = fav_bits[q]
+    ex = _bit_words(exclude, (nq, ww), dev, "exclude")
+    kp = None if keep is None else _bit_words(keep, (ww,), dev, "keep")
+    _lib.check(lib.anirec_user_recs_ex(_lib.ptr(fav_bits), int(fav_bits.shape[0]), int(n_anime), _lib.ptr(sim), nq,
+                                       k_sim, _lib.ptr(ex), _lib.ptr(kp), int(n_recs), _lib.ptr(out_a),
+                                       _lib.ptr(out_c), _stream()), "anirec_user_recs_ex")
     return out_a, out_c
+
+
+def fave_profile(fav_bits, cat_bits, n_cat, users=None):
+    """Favourite profiles: int32 [n_rows, n_cat], entry [r, c] = number of favourites of user ``users[r]`` (every
+    user when None) whose category row (``cat_bits`` [n_anime, ceil(n_cat/32)] bit words) has bit c set.
+    Raises ValueError on a user index out of range."""
+    lib = _lib.load()
+    dev = fav_bits.device
+    n_cat = int(n_cat)
+    if not 1 <= n_cat <= 128:
+        raise ValueError("n_cat = %d: the profile kernel counts 1 to 128 categories" % n_cat)
+    n_users = int(fav_bits.shape[0])
+    cw = (n_cat + 31) // 32
+    n_anime = int(cat_bits.shape[0])
+    cat = _bit_words(cat_bits, (n_anime, cw), dev, "cat_bits")
+    if int(fav_bits.shape[1]) != (n_anime + 31) // 32:
+        raise ValueError("fav_bits has %d words per row, cat_bits describes %d anime" % (int(fav_bits.shape[1]), n_anime))
+    u = None if users is None else torch.as_tensor(users, device=dev).to(torch.int32).contiguous().view(-1)
+    n_rows = n_users if u is None else int(u.numel())
+    counts = torch.empty(n_rows, n_cat, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.anirec_fave_profile(_lib.ptr(fav_bits.contiguous()), n_users, n_anime, _lib.ptr(u), n_rows,
+                                       _lib.ptr(cat), n_cat, _lib.ptr(counts), _lib.ptr(err), _stream()),
+               "anirec_fave_profile")
+    if int(err.item()):
+        raise ValueError("fave_profile: user index out of range")
+    return counts

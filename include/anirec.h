@@ -588,6 +588,23 @@ int anirec_user_recs(const uint32_t *fav_bits, int32_t n_users, int32_t n_anime,
                      const int32_t *sim_users, int32_t nq, int32_t k_sim, int32_t n_recs, int32_t *out_anime,
                      int32_t *out_count, void *stream);
 
+/* As anirec_user_recs, but the skipped set of query q is exclude_bits[q][ceil(n_anime/32)] (not the favourite row of a
+ * query user), and when keep_bits != NULL only anime a with bit a of keep_bits[ceil(n_anime/32)] set are counted or
+ * returned (user_recs.py:743,753: the reference skips the anime NAMED in the user_prefs CSV, and loses anime missing
+ * from all_anime.csv).  Same limits and tie order as anirec_user_recs. */
+int anirec_user_recs_ex(const uint32_t *fav_bits, int32_t n_users, int32_t n_anime, const int32_t *sim_users,
+                        int32_t nq, int32_t k_sim, const uint32_t *exclude_bits, const uint32_t *keep_bits,
+                        int32_t n_recs, int32_t *out_anime, int32_t *out_count, void *stream);
+
+/* Favourite profiles (user_prefs.py:95-136 get_genres / get_sources over a user's favourites):
+ * counts[r][c] = #{ a : bit a of fav_bits[users[r]] set and bit c of cat_bits[a] set }
+ * users == NULL: r runs over every user 0..n_users-1 (n_rows == n_users).
+ * cat_bits[n_anime][cat_words], cat_words = ceil(n_cat/32), 1 <= n_cat <= 128.
+ * *err_flag (device) becomes 1 on a user index out of range; that row's counts are 0. */
+int anirec_fave_profile(const uint32_t *fav_bits, int32_t n_users, int32_t n_anime, const int32_t *users,
+                        int32_t n_rows, const uint32_t *cat_bits, int32_t n_cat, int32_t *counts, int32_t *err_flag,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
