@@ -126,10 +126,6 @@ PROTOTYPES = {
     "anirec_cosine_scores": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "anirec_topk_workspace_bytes": (_sz, [_i32, _i32]),
     "anirec_cosine_topk": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "anirec_topk_mfma_workspace_bytes": (_sz, [_i32, _i32]),
-    "anirec_cosine_topk_mfma": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "anirec_cosine_topk_mfma_prior": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, C.c_float, _vp, _vp, _vp, _vp, _sz,
-                                                _vp]),
     "anirec_cosine_topk_job_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32)]),
     "anirec_cosine_topk_job_workspace_bytes": (_sz, [_i32, _i32, _i32]),

@@ -220,8 +220,8 @@ __global__ __launch_bounds__(256, 2) void k_predict_mfma(PredArgs a) {
 //     the store tail never runs on its own.
 // Requires n_anime % 4 == 0 (16-byte aligned row quads); other shapes take k_predict_mfma.
 //
-// Round 4, where the 100 k x 18 k grid's time goes (scripts/time_predict.py, interleaved rounds in one process; kDbg 1 =
-// epilogue + stores without the MFMAs, kDbg 2 = MFMAs without the stores):
+// Round 4, where the 100 k x 18 k grid's time goes (interleaved rounds in one process, with timing-only builds since
+// removed: "stores alone" = epilogue + stores without the MFMAs, "MFMAs alone" = MFMAs without the stores):
 //   box A: whole kernel 1.50 ms (4.8 TB/s written), stores alone 1.30, MFMAs alone 1.43 (0.97 PFLOP/s on the
 //   1.38 TFLOP of the three-term split); box B: 1.71 ms (4.2 TB/s), stores alone 1.64, MFMAs alone 1.30.
 // The two sides are within 10 % of each other and of the whole (the overlap works), which of them is longer depends
@@ -239,9 +239,8 @@ struct Acc2 {
   f32x4 c[4][2];  // [anime block of 16][user block of 16]
 };
 
-// kDbg (timing only, wrong output): 1 = epilogue + stores without the MFMAs, 2 = MFMAs without the stores; kAct: the
-// activation of the epilogue (FastHead)
-template <int kDbg, int kAct>
+// kAct: the activation of the epilogue (FastHead)
+template <int kAct>
 __global__ __launch_bounds__(256, 2) void k_predict_mfma2(PredArgs a) {
   // one LDS array (a second object beside an LDS-DMA target makes hipcc drain vmcnt before every ds_read):
   // 2 x 32 KB key tiles (hi+lo planes of 64 anime rows), then 4 x 4 KB output staging (one per wave)
@@ -330,13 +329,9 @@ __global__ __launch_bounds__(256, 2) void k_predict_mfma2(PredArgs a) {
           f32x4 c = nxt.c[ab][ub];
           if (kk == 0) c = (f32x4){0.f, 0.f, 0.f, 0.f};
           // small terms first: lo*hi + hi*lo, then hi*hi
-          if (kDbg != 1) {
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, uh[ub][kk], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, ul[ub][kk], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, uh[ub][kk], c, 0, 0, 0);
-          } else {
-            c[0] += ah[0] + al[1];
-          }
+          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, uh[ub][kk], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, ul[ub][kk], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, uh[ub][kk], c, 0, 0, 0);
           nxt.c[ab][ub] = c;
         }
         if (epi && (kk & 1)) {  // 8 epilogue blocks per tile, one after every 12 MFMAs
@@ -357,10 +352,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_mfma2(PredArgs a) {
               const u32x4 d = __builtin_bit_cast(u32x4, stg[row * 16 + (c16 ^ row)]);
               const uint32_t voff = in ? vrow + (uint32_t)(16 * eub + 4 * j) * (vrow4 / 4u) + (uint32_t)(tc * kPN) * 4u
                                        : 0xFFFFFFF0u;
-              if (kDbg != 2)
-                __builtin_amdgcn_raw_buffer_store_b128(d, rsrc, voff, 0, 2 /* nt */);
-              else
-                asm volatile("" ::"v"(d));
+              __builtin_amdgcn_raw_buffer_store_b128(d, rsrc, voff, 0, 2 /* nt */);
             }
           }
         }
@@ -444,11 +436,12 @@ int anirec_predict_grid_mfma_act(const float *U, const float *A, int32_t n_anime
   head_affine_mfma(head, &pa.hs, &pa.hb);
   pa.out = out;
   // 16-byte row quads need n_anime % 4 == 0 and 32-bit byte offsets inside a workgroup's 128 rows
-  const char *ver = getenv("ANIREC_PREDICT_KERNEL");  // "1": force the dword-store kernel (A/B on one box)
-  const bool v2 = (n_anime % 4 == 0) && ((size_t)n_anime * kPM * 4 < ((size_t)1 << 31)) && !(ver && ver[0] == '1');
+  const bool v2 = (n_anime % 4 == 0) && ((size_t)n_anime * kPM * 4 < ((size_t)1 << 31));
   if (v2) {
     // anime parts: enough workgroups (>= ~8 per resident slot) for the dispatcher to balance the tail, parts of at
-    // least 16 tiles so the pipeline fill of a part stays a few per cent
+    // least 16 tiles so the pipeline fill of a part stays a few per cent.  ANIREC_PREDICT_PARTS=<n> pins the count:
+    // tests/test_infer_gpu.py runs several on the same inputs to show that the grid does not depend on it, which
+    // input shapes alone could only do for one chip size.
     const int ub = (n_users + kPM - 1) / kPM, ntile = n_pad / kPN;
     const char *pe = getenv("ANIREC_PREDICT_PARTS");
     int parts = pe ? atoi(pe) : (4096 + ub - 1) / ub;
@@ -457,16 +450,9 @@ int anirec_predict_grid_mfma_act(const float *U, const float *A, int32_t n_anime
     pa.tiles_per_part = (ntile + parts - 1) / parts;
     parts = (ntile + pa.tiles_per_part - 1) / pa.tiles_per_part;
     const dim3 grid(ub, parts);
-    const char *dbg = getenv("ANIREC_PREDICT_DEBUG");
-    const int mode = dbg ? atoi(dbg) : 0;
-    if (mode == 1)
-      hipLaunchKernelGGL((k_predict_mfma2<1, ANIREC_ACT_SIGMOID>), grid, dim3(256), 0, s, pa);
-    else if (mode == 2)
-      hipLaunchKernelGGL((k_predict_mfma2<2, ANIREC_ACT_SIGMOID>), grid, dim3(256), 0, s, pa);
-    else
-      with_act(activation, [&](auto k) {
-        hipLaunchKernelGGL((k_predict_mfma2<0, decltype(k)::value>), grid, dim3(256), 0, s, pa);
-      });
+    with_act(activation, [&](auto k) {
+      hipLaunchKernelGGL((k_predict_mfma2<decltype(k)::value>), grid, dim3(256), 0, s, pa);
+    });
   } else {
     with_act(activation, [&](auto k) {
       hipLaunchKernelGGL(k_predict_mfma<decltype(k)::value>, dim3((n_users + kPM - 1) / kPM), dim3(256), 0, s, pa);

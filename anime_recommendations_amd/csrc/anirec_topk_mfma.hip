@@ -46,7 +46,7 @@
 //     symmetry is used ACROSS query batches only, where every row of a later batch still sits at the job's learnt
 //     prior, so ONE test against the prior serves both rows; the pairs for the key's row leave through per-wave logs
 //     (k_scatter_log -> inboxes -> k_merge_inbox / the re-rank).  350 k x 350 k top-100: 31.5 -> 24.9 ms.)
-//   Where the k = 100 time goes (ANIREC_TOPK_DEBUG=16, same 65 536-query slice, same box): no filter at all 4.2 ms;
+//   Where the k = 100 time goes (diagnostic builds of k_cand, since removed; same 65 536-query slice, same box): no filter at all 4.2 ms;
 //   the filter with thresholds nothing passes 4.4-4.5 ms; ONE launch with the FINAL thresholds handed in (a row
 //   appends only its k + window candidates) 5.0-5.6 ms; the real schedule — 11 launches, each threshold the k-th
 //   best of the keys seen so far, ~950 appends per row instead of ~110 — 6.6 ms.  The extra ~850 appends are what
@@ -58,7 +58,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <math.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include <mutex>
@@ -180,7 +179,6 @@ struct CandArgs {
   int splits;        // gridDim.y of this launch
   float *theta;      // [nq]
   int32_t *flags;    // [nq] bit0: buffer overflow (dense ties)
-  unsigned long long *dbg;  // kDbg == 2: [0] total appends
   const uint32_t *watched;  // kMask: [nq][wwords] per-query key mask, bit set = key excluded (model_recs)
   int wwords;
   // all-pairs job (every key row is a query row): the key stream of a query batch skips the tiles of EARLIER batches
@@ -351,10 +349,10 @@ __device__ __forceinline__ void refresh_one(const CandArgs &a, int row, int lane
     refresh_row<kCap / 64>(a, cand_row, row, c, lane);
 }
 
-// One wave per row; the grid is bounded by the host (side_grid) and strides over the rows, so that these waves —
-// which run BESIDE another chain's k_cand in a job — never hold more than a few wave slots per CU: an unbounded
-// grid of one-wave workgroups takes every slot a finished MFMA workgroup frees, and the next 8-wave k_cand workgroup
-// (2 x 160 VGPRs per SIMD + 64 KB of LDS at once) cannot start until the whole side kernel has drained.
+// One wave per row, launched with one workgroup per row.  These waves run BESIDE another chain's k_cand in a job, and
+// a grid of one-wave workgroups takes every slot a finished MFMA workgroup frees, so the next 8-wave k_cand workgroup
+// (2 x 160 VGPRs per SIMD + 64 KB of LDS at once) cannot start until the whole side kernel has drained; a grid bounded
+// to a few waves per CU, striding over the rows, was measured and is slower (see the job's comment).
 // Four rows per 256-thread workgroup (waves that never synchronise) measured the same as one row per workgroup
 // (18 k job 0.69 vs 0.69 ms, all-pairs 32.3 vs 32.3 ms): the dispatch rate of one-wave workgroups is not what
 // these kernels wait for.
@@ -370,10 +368,11 @@ __global__ __launch_bounds__(64) void k_refresh(CandArgs a) {
 // MFMA and is used when the queries fill the chip that way; kWaves = 4 (two workgroups per CU) otherwise.
 // kMask: a candidate is dropped at append time when its bit in the query's own mask row is set (the
 // "already watched" set of model_recs); the mask words reach a wave-private LDS image by LDS-DMA two tiles ahead.
-template <int kDbg, int kWaves, bool kMask = false, bool kSym = false>  // kDbg 0: product; 1: no filter (timing only); 2: count appends; 4: stamps
-// (host-side mode 16: after the product run, one launch over all keys with the final / with unreachable thresholds)
+// kVariant is always 0: it keeps the kernel names (k_cand<0, ...>) that bench.py and the committed profiles look up.
+template <int kVariant, int kWaves, bool kMask = false, bool kSym = false>
 __global__ __launch_bounds__(64 * kWaves, 8 / kWaves) void k_cand(CandArgs a) {
-  static_assert(!(kSym && (kMask || kDbg != 0)), "the all-pairs variant exists for the product build only");
+  static_assert(kVariant == 0, "k_cand has one variant");
+  static_assert(!(kSym && kMask), "the all-pairs variant has no key mask");
   constexpr int kBM = 32 * kWaves;
   constexpr int kDma = 32 / kWaves;  // LDS-DMA instructions per wave per key tile (4 key rows each)
   __shared__ __attribute__((aligned(16))) uint4 Ks[2][kBN * 16];  // 2 x 32 KB
@@ -555,10 +554,10 @@ __global__ __launch_bounds__(64 * kWaves, 8 / kWaves) void k_cand(CandArgs a) {
       // NaN scores (masked / padding keys) are quiet NaNs, which v_max3 ignores like fmaxf.
       float m3 = 0.f, mq = 0.f;
       mma1(nxt, 0, 0, qd);
-      if (kDbg != 1) asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(m3) : "v"(cv[0]), "v"(cv[1]), "v"(cv[2]));
+      asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(m3) : "v"(cv[0]), "v"(cv[1]), "v"(cv[2]));
       __builtin_amdgcn_sched_barrier(0);
       mma1(nxt, 1, 0, qd);
-      if (kDbg != 1) asm volatile("v_max_f32 %0, %1, %2" : "=v"(mq) : "v"(m3), "v"(cv[3]));
+      asm volatile("v_max_f32 %0, %1, %2" : "=v"(mq) : "v"(m3), "v"(cv[3]));
       __builtin_amdgcn_sched_barrier(0);
       mma1(nxt, 0, 1, qd);
       bv[0][qd] = kb[qd][(fbuf * kBN + fcb * 32) * 16];
@@ -566,10 +565,6 @@ __global__ __launch_bounds__(64 * kWaves, 8 / kWaves) void k_cand(CandArgs a) {
       mma1(nxt, 1, 1, qd);
       bv[1][qd] = kb[qd][(fbuf * kBN + fcb * 32 + 16) * 16];
       __builtin_amdgcn_sched_barrier(0);
-      if (kDbg == 1) {
-        if (qd == 0) asm volatile("" ::"v"(cur.c[0][0]), "v"(cur.c[0][1]), "v"(cur.c[1][0]), "v"(cur.c[1][1]));
-        continue;
-      }
       if (__ballot(mq >= 0.f)) {
         const int key = key0 + 16 * nb + c16;
 #pragma unroll
@@ -593,11 +588,10 @@ __global__ __launch_bounds__(64 * kWaves, 8 / kWaves) void k_cand(CandArgs a) {
           if (mk) {  // wave-uniform
             const uint32_t mh = (uint32_t)(mk >> sh16) & 0xFFFFu;  // the quarter-wave (= row) of this lane
             const uint32_t pos = (uint32_t)cntr[rb][i] + __popc(mh & lt16);
-            if (kDbg != 8 && hit && pos < cap)  // (kDbg 8, timing only: everything but the candidate store)
+            if (hit && pos < cap)
               *reinterpret_cast<uint2 *>(cand_bytes + (rowoff[rb][i] + pos * 8u)) =
                   make_uint2(__float_as_uint(cv[i] - nthr[rb][i]), (uint32_t)key);
             cntr[rb][i] += __popc(mh);
-            if (kDbg == 2 && lane == 0) atomicAdd(&a.dbg[0], (unsigned long long)__popcll(mk));
           }
         }
       }
@@ -613,8 +607,6 @@ __global__ __launch_bounds__(64 * kWaves, 8 / kWaves) void k_cand(CandArgs a) {
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) fetch(kk, 0, 1);
 
-  unsigned long long dbg_store = 0, dbg_barrier = 0, dbg_t0 = 0;
-  if (kDbg == 4) dbg_t0 = __builtin_amdgcn_s_memtime();
   for (int it = 0; it < nt; ++it) {
     const int buf = it & 1;
     const int lt = tile_lo + it;
@@ -622,21 +614,10 @@ __global__ __launch_bounds__(64 * kWaves, 8 / kWaves) void k_cand(CandArgs a) {
     const int ms = (it % 3) * 128;                     // this tile's slot in the wave's LDS mask image
     stage_fn(acc0, acc1, key0, buf, 2, ms + 0);        // filter block 0 | MFMA block 1 | fetch block 2
     stage_fn(acc1, acc0, key0 + 32, buf, 3, ms + 1);   // filter block 1 | MFMA block 2 | fetch block 3
-    unsigned long long ts0 = 0, ts1 = 0, ts2 = 0;
-    if (kDbg == 4) ts0 = __builtin_amdgcn_s_memtime();
     // tile it+1 was sent to the other buffer one tile ago; its DMA (and this wave's candidate stores,
     // vmcnt counts in order) must have landed before anyone reads it
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (kDbg == 4) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      ts1 = __builtin_amdgcn_s_memtime();
-    }
     __syncthreads();
-    if (kDbg == 4) {
-      ts2 = __builtin_amdgcn_s_memtime();
-      dbg_store += ts1 - ts0;
-      dbg_barrier += ts2 - ts1;
-    }
     // this tile's buffer was last read (fetched) before the barrier: refill it with tile it+2, in
     // flight for a whole tile
     if (kMask && it + 2 < nt) dma_mask(tile_lo + it + 2, (it + 2) % 3);  // its slot was tile it-1's
@@ -645,15 +626,8 @@ __global__ __launch_bounds__(64 * kWaves, 8 / kWaves) void k_cand(CandArgs a) {
     stage_fn(acc0, acc1, key0 + 64, buf ^ 1, 0, ms + 2);  // filter block 2 | MFMA block 3 | fetch next tile's block 0
     stage_fn(acc1, acc0, key0 + 96, buf ^ 1, 1, ms + 3);  // filter block 3 | MFMA next block 0 | fetch next block 1
   }
-  if (kDbg == 4 && lane == 0) {  // in-kernel stamps (diagnostic build only): cycles per wave
-    unsigned long long *d = a.dbg + 4 * (size_t)(blockIdx.x * kWaves + w);
-    d[0] = __builtin_amdgcn_s_memtime() - dbg_t0;
-    d[1] = dbg_store;
-    d[2] = dbg_barrier;
-    d[3] = (unsigned long long)nt;
-  }
   if (kSym && lane == 0) a.logcnt[wave_id] = (int32_t)lcnt;
-  if (kDbg != 1 && c16 == 0) {
+  if (c16 == 0) {
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -994,7 +968,7 @@ __device__ __forceinline__ void rerank_one(const RerankArgs &a, int row, int lan
 
 // kAct: the activation of the predict head (kPredict); the cosine top-k takes ANIREC_ACT_SIGMOID, which it does not use
 template <bool kPredict, int kAct>
-__global__ __launch_bounds__(64) void k_rerank(RerankArgs a) {  // bounded grid, strides over the rows (see k_refresh)
+__global__ __launch_bounds__(64) void k_rerank(RerankArgs a) {  // one wave per row (see k_refresh)
   __shared__ float qs[kDim];
   __shared__ int32_t sidx[kMaxSurv];
   __shared__ float sval[kMaxSurv];
@@ -1046,18 +1020,6 @@ static int cu_count() {
   return cus;
 }
 
-// mid_ev (optional): recorded on s behind the first super-step that ends at or beyond mid_pct % of the key tiles (the
-// job staggers its chains with it)
-// grid of the one-wave-per-row side kernels: one workgroup per row, or — ANIREC_TOPK_SIDE_WAVES > 0, an experiment
-// knob — at most that many waves per CU striding over the rows (measured and NOT adopted: see the job's comment)
-static int side_grid(int nq) {
-  const char *e = getenv("ANIREC_TOPK_SIDE_WAVES");
-  const int per_cu = e ? atoi(e) : 0;
-  if (per_cu <= 0) return nq;
-  const long long g = (long long)cu_count() * per_cu;
-  return (int)(g < nq ? g : nq);
-}
-
 // one batch of the all-pairs job (see CandArgs): its key stream and its inboxes
 struct SymPlan {
   int map_lo, map_skip;  // logical -> physical key tiles
@@ -1090,9 +1052,15 @@ static void cand_defaults(CandArgs &ca) {
   ca.lcap = 0;
 }
 
-static int run_super_steps(CandArgs &ca, int n, int nq, bool masked, int mode, void *dbg_words,
-                           unsigned long long *stamps, size_t n_waves, hipStream_t s, hipEvent_t mid_ev = nullptr,
-                           int mid_pct = 0, bool has_prior = false, const SymPlan *sp = nullptr) {
+template <bool kMask, bool kSym>
+static void launch_cand(bool wide, dim3 grid, dim3 block, size_t shm, hipStream_t s, const CandArgs &ca) {
+  if (wide)
+    hipLaunchKernelGGL((k_cand<0, 8, kMask, kSym>), grid, block, shm, s, ca);
+  else
+    hipLaunchKernelGGL((k_cand<0, 4, kMask, kSym>), grid, block, shm, s, ca);
+}
+
+static int run_super_steps(CandArgs &ca, int n, int nq, bool masked, hipStream_t s, const SymPlan *sp = nullptr) {
   int ntiles = (n + kBN - 1) / kBN;
   int sym_from = 0x7fffffff;
   if (sp) {
@@ -1107,12 +1075,13 @@ static int run_super_steps(CandArgs &ca, int n, int nq, bool masked, int mode, v
     sym_from = sp->sym_from;
   }
   // 256-row workgroups once they give every CU one (8 waves per CU either way); 128-row otherwise
+  // (an all-pairs batch of 24 k rows or more: its launches are cut in three key ranges anyway).
+  // ANIREC_TOPK_WAVES=4|8 pins the shape: tests/test_infer_gpu.py runs both on the same inputs to show that the lists
+  // do not depend on it, which input shapes alone could only do for one chip size.
   const char *wv = getenv("ANIREC_TOPK_WAVES");
-  // (an all-pairs batch of 24 k rows or more: its launches are cut in three key ranges anyway)
   const bool wide = wv ? atoi(wv) == 8 : (nq >= 49152 || (sp != nullptr && nq >= 24576));
   const dim3 grid(wide ? (nq + 255) / 256 : (nq + 127) / 128);
   const dim3 block(wide ? 512 : 256);
-  int n_launch = 0;
   if (masked) {  // 64 KB of key tiles (static) + the mask images (dynamic) exceed the default 64 KB cap
     static bool attr_set = false;
     if (!attr_set) {
@@ -1126,27 +1095,23 @@ static int run_super_steps(CandArgs &ca, int n, int nq, bool masked, int mode, v
   std::vector<hipEvent_t> timed;  // event pairs around the k_cand launches (timing mode only)
   // each super-step sees growth_pct % of the keys seen so far: a row gains about k_eff * growth candidates per
   // step, which must fit the buffer next to the ~2 k_eff it already holds — tripling for small k (fewer
-  // launches and refreshes), doubling otherwise
-  const char *gp = getenv("ANIREC_TOPK_GROWTH");
-  // (rows that start from a prior append little before their own threshold takes over: longer steps, fewer refreshes)
-  const char *gpp = getenv("ANIREC_TOPK_GROWTH_PRIOR");
-  const int growth_pct = has_prior && gpp ? atoi(gpp) : gp ? atoi(gp) : (ca.k_eff <= 32 ? 200 : 100);
+  // launches and refreshes), doubling otherwise.  (Longer steps for rows that start from a prior were measured
+  // slower: see the job's comment.)
+  const int growth_pct = ca.k_eff <= 32 ? 200 : 100;
   // the first super-step runs without a threshold and appends every key it sees: keep it as short as
-  // the k-th-best estimate allows (>= 4 k_eff keys), at most what the buffer holds
+  // the k-th-best estimate allows (>= 4 k_eff keys), at most what the buffer holds.  (Rows that start from a prior
+  // append next to nothing in the first tiles, but a first super-step over a share of the stream measured only 4 %
+  // faster for them and is fragile on clustered embeddings: DESIGN.md 4.2.)
   int first = (4 * ca.k_eff + kBN - 1) / kBN;
   if (first > (kCap - kBN) / kBN) first = (kCap - kBN) / kBN;
   if (first < 1) first = 1;
-  // Rows that start from a prior append next to nothing in the first tiles (a prior near the final threshold passes
-  // ~k keys of the WHOLE stream), and their own threshold only overtakes the prior once about half the keys have been
-  // seen: the tiny first super-steps and their refreshes buy nothing, so the first one takes a share of the stream.
-  const char *fpp = getenv("ANIREC_TOPK_FIRST_PRIOR_PCT");
-  const int first_pct = fpp ? atoi(fpp) : 0;
-  if (has_prior && first_pct > 0 && (long long)ntiles * first_pct / 100 > first) first = (int)((long long)ntiles * first_pct / 100);
   // Few queries: fewer workgroups than the chip holds.  From the second super-step on the key tiles of a super-
   // step are then split over up to kMaxSplit workgroups per row block (the first one, with no threshold yet,
   // needs the whole buffer of a row).
   // The same splits smooth the wave quantisation of bigger launches: 391 workgroups on 256 CUs run as two full
   // rounds; cut in three they run as five rounds of a third of the length (1.67).
+  // ANIREC_TOPK_SPLITS=<n> caps the splits: tests/test_infer_gpu.py runs 1..4 on the same inputs to show that the lists
+  // do not depend on them (the heuristic's choice follows from the CU count).
   const char *spe = getenv("ANIREC_TOPK_SPLITS");
   const int wg_slots = cu_count() * (wide ? 1 : 2);
   // A row gains about k_eff * growth candidates per super-step, spread over the splits: a region (kReg entries)
@@ -1181,19 +1146,11 @@ static int run_super_steps(CandArgs &ca, int n, int nq, bool masked, int mode, v
     }
     ca.tile0 = t0;
     ca.tile1 = t1;
-    int splits = (t0 == 0 && !(has_prior && first_pct > 0)) ? 1 : max_split;
+    int splits = t0 == 0 ? 1 : max_split;
     while (splits > 1 && (t1 - t0) < 2 * splits) --splits;  // at least two tiles per workgroup
     if (splits > 1 && splits < min_split) splits = 1;
     ca.splits = splits;
     const dim3 grid2(grid.x, splits);
-#define ANIREC_LAUNCH_CAND(D, M)                                                                    \
-  do {                                                                                              \
-    const size_t shm = (M) ? (size_t)(wide ? 8 : 4) * 3 * 512 : 0;  /* the waves' LDS mask images */   \
-    if (wide)                                                                                       \
-      hipLaunchKernelGGL((k_cand<D, 8, M>), grid2, block, shm, s, ca);                              \
-    else                                                                                            \
-      hipLaunchKernelGGL((k_cand<D, 4, M>), grid2, block, shm, s, ca);                              \
-  } while (0)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g_time_cand) {
       ANIREC_HIP_CHECK(hipEventCreate(&ev0));
@@ -1204,41 +1161,25 @@ static int run_super_steps(CandArgs &ca, int n, int nq, bool masked, int mode, v
       const size_t lw = (size_t)grid2.x * grid2.y * (wide ? 8 : 4);
       if (lw > log_waves((size_t)nq)) return ANIREC_EINVAL;  // (cannot happen: the workspace was sized by the same formula)
       (void)hipMemsetAsync(ca.logcnt, 0, lw * 4, s);  // (workgroups of an empty split write nothing)
-      if (wide)
-        hipLaunchKernelGGL((k_cand<0, 8, false, true>), grid2, block, 0, s, ca);
-      else
-        hipLaunchKernelGGL((k_cand<0, 4, false, true>), grid2, block, 0, s, ca);
+      launch_cand<false, true>(wide, grid2, block, 0, s, ca);
       hipLaunchKernelGGL(k_scatter_log, dim3((unsigned)lw), dim3(256), 0, s, ca.log, ca.logcnt, kLogCap, sp->inbox_w,
                          sp->icnt_w, sp->ovf);
-    } else if (masked)
-      ANIREC_LAUNCH_CAND(0, true);
-    else if (mode == 1)
-      ANIREC_LAUNCH_CAND(1, false);
-    else if (mode == 2)
-      ANIREC_LAUNCH_CAND(2, false);
-    else if (mode == 4)
-      ANIREC_LAUNCH_CAND(4, false);
-    else if (mode == 8)
-      ANIREC_LAUNCH_CAND(8, false);
-    else
-      ANIREC_LAUNCH_CAND(0, false);
-#undef ANIREC_LAUNCH_CAND
+    } else if (masked) {
+      launch_cand<true, false>(wide, grid2, block, (size_t)(wide ? 8 : 4) * 3 * 512, s, ca);  // + the LDS mask images
+    } else {
+      launch_cand<false, false>(wide, grid2, block, 0, s, ca);
+    }
     if (g_time_cand) {
       ANIREC_HIP_CHECK(hipEventRecord(ev1, s));
       timed.push_back(ev0);
       timed.push_back(ev1);
     }
     // (none after the last super-step: the re-rank folds the split regions itself)
-    if (t1 < ntiles) hipLaunchKernelGGL(k_refresh, dim3(side_grid(nq)), dim3(64), 0, s, ca);
+    if (t1 < ntiles) hipLaunchKernelGGL(k_refresh, dim3(nq), dim3(64), 0, s, ca);
     ANIREC_HIP_CHECK(hipGetLastError());
-    if (mid_ev && (long long)t1 * 100 >= (long long)ntiles * mid_pct) {
-      ANIREC_HIP_CHECK(hipEventRecord(mid_ev, s));
-      mid_ev = nullptr;
-    }
     step = (int)((long long)t1 * growth_pct / 100);  // next super-step: growth_pct % of the tiles seen so far
     if (step < 1) step = 1;
     t0 = t1;
-    ++n_launch;
   }
   if (g_time_cand) {  // blocking: only bench.py's roofline leg arms this
     g_cand_launches += (int)timed.size() / 2;  // summed over the batches of a job until the next arm / disarm
@@ -1250,59 +1191,6 @@ static int run_super_steps(CandArgs &ca, int n, int nq, bool masked, int mode, v
       (void)hipEventDestroy(timed[i]);
       (void)hipEventDestroy(timed[i + 1]);
     }
-  }
-  if (mode == 16 && !masked) {
-    // diagnostic: ONE launch over all keys with the FINAL thresholds (what the filter costs when a row only ever
-    // sees its k + window candidates), and one with thresholds nothing passes (filter without any hit)
-    for (int pass = 0; pass < 2; ++pass) {
-      (void)hipMemsetAsync(ca.cnt, 0, (size_t)nq * 4, s);
-      if (pass == 1) {
-        std::vector<float> big((size_t)nq, 2.0f);
-        (void)hipMemcpyAsync(ca.theta, big.data(), (size_t)nq * 4, hipMemcpyHostToDevice, s);
-      }
-      ca.tile0 = 0;
-      ca.tile1 = ntiles;
-      ca.splits = 1;
-      hipEvent_t e0, e1;
-      (void)hipEventCreate(&e0);
-      (void)hipEventCreate(&e1);
-      (void)hipEventRecord(e0, s);
-      if (wide)
-        hipLaunchKernelGGL((k_cand<0, 8, false>), grid, block, 0, s, ca);
-      else
-        hipLaunchKernelGGL((k_cand<0, 4, false>), grid, block, 0, s, ca);
-      (void)hipEventRecord(e1, s);
-      (void)hipEventSynchronize(e1);
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      fprintf(stderr, "[anirec topk debug] one launch over %d tiles with %s thresholds: %.3f ms\n", ntiles,
-              pass == 0 ? "the final" : "unreachable", ms);
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-    }
-  }
-  if (mode == 2 && !masked) {
-    unsigned long long hv[2] = {0, 0};
-    (void)hipMemcpyAsync(hv, dbg_words, 16, hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    fprintf(stderr, "[anirec topk debug] nq=%d n=%d appends/row=%.1f super-steps=%d\n", nq, n,
-            (double)hv[0] / nq, n_launch);
-  }
-  if (mode == 4 && !masked) {  // stamps of the LAST super-step
-    std::vector<unsigned long long> hv(n_waves * 4);
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpy(hv.data(), stamps, n_waves * 32, hipMemcpyDeviceToHost);
-    (void)hipFree(stamps);
-    double tot = 0, st = 0, br = 0;
-    for (size_t i = 0; i < n_waves; ++i) {
-      tot += (double)hv[4 * i];
-      st += (double)hv[4 * i + 1];
-      br += (double)hv[4 * i + 2];
-    }
-    const double ntl = (double)hv[3];
-    fprintf(stderr, "[anirec topk stamps] last super-step: %d tiles; per wave per tile: total %.0f cycles, "
-            "vmcnt wait %.0f, barrier %.0f\n", (int)ntl, tot / n_waves / ntl, st / n_waves / ntl,
-            br / n_waves / ntl);
   }
   return ANIREC_OK;
 }
@@ -1350,14 +1238,13 @@ static LaneBufs carve_lane(char *p, size_t rows) {
 
 // rows init -> query rows to fp16 -> super-steps of the key stream -> exact re-rank, all on stream s
 static int run_batch(const float *What, const _Float16 *Wb, int n, const int32_t *queries, int nq, int exclude_self, int k,
-                     float theta0, const float *theta0_dev, const LaneBufs &lb, int32_t *unnorm, bool zero_unnorm,
-                     int32_t *out_idx, float *out_score, int32_t *flags, int mode, void *dbg_words, hipStream_t s,
-                     hipEvent_t mid_ev = nullptr, int mid_pct = 0, const SymPlan *sp = nullptr) {
+                     float theta0, const float *theta0_dev, const LaneBufs &lb, int32_t *unnorm, int32_t *out_idx,
+                     float *out_score, int32_t *flags, hipStream_t s, const SymPlan *sp = nullptr) {
   if ((size_t)nq * kCap * 8 >= ((size_t)1 << 32)) return ANIREC_EINVAL;  // 32-bit candidate offsets: batch the queries
   int b2 = (nq + 7) / 8;
   if (b2 > 8192) b2 = 8192;
-  hipLaunchKernelGGL(k_init_rows, dim3((nq + 255) / 256), dim3(256), 0, s, lb.cnt, lb.cnt2, lb.theta, flags, nq,
-                     zero_unnorm ? unnorm : nullptr, theta0, theta0_dev);
+  hipLaunchKernelGGL(k_init_rows, dim3((nq + 255) / 256), dim3(256), 0, s, lb.cnt, lb.cnt2, lb.theta, flags, nq, nullptr,
+                     theta0, theta0_dev);
   hipLaunchKernelGGL(k_to_f16, dim3(b2), dim3(256), 0, s, What, queries, nq, nq, nullptr, 1, lb.Qb, unnorm);
   ANIREC_HIP_CHECK(hipGetLastError());
   CandArgs ca;
@@ -1373,28 +1260,16 @@ static int run_batch(const float *What, const _Float16 *Wb, int n, const int32_t
   ca.splits = 1;
   ca.theta = lb.theta;
   ca.flags = flags;
-  ca.dbg = nullptr;
   ca.watched = nullptr;
   ca.wwords = 0;
-  if (mode == 2) {
-    ca.dbg = (unsigned long long *)dbg_words;
-    (void)hipMemsetAsync(dbg_words, 0, 16, s);
-  }
-  unsigned long long *stamps = nullptr;
-  const size_t n_waves = ((size_t)nq + 255) / 256 * 8;
-  if (mode == 4) {  // diagnostic build with in-kernel stamps
-    ANIREC_HIP_CHECK(hipMalloc((void **)&stamps, n_waves * 32));
-    ca.dbg = stamps;
-  }
   if (sp && sp->inbox_start) {  // what the earlier batches of this chain found for these rows: first candidates
     hipLaunchKernelGGL(k_merge_inbox, dim3(nq), dim3(64), 0, s, lb.cand, lb.cnt, flags, nq, sp->row0, sp->inbox_start,
                        sp->icnt_start);
-    hipLaunchKernelGGL(k_refresh, dim3(side_grid(nq)), dim3(64), 0, s, ca);
+    hipLaunchKernelGGL(k_refresh, dim3(nq), dim3(64), 0, s, ca);
     ANIREC_HIP_CHECK(hipGetLastError());
   }
   {
-    const int rc = run_super_steps(ca, n, nq, false, mode, dbg_words, stamps, n_waves, s, mid_ev, mid_pct,
-                                   theta0_dev != nullptr || theta0 > kThetaInit, sp);
+    const int rc = run_super_steps(ca, n, nq, false, s, sp);
     if (rc) return rc;
   }
   if (sp) {  // the other chain's batches must have delivered before the re-rank merges their inbox
@@ -1424,50 +1299,8 @@ static int run_batch(const float *What, const _Float16 *Wb, int n, const int32_t
   ra.hs = ra.hb = 0.f;
   ra.sign = 1.f;
   ra.unnorm = unnorm;
-  hipLaunchKernelGGL((k_rerank<false, ANIREC_ACT_SIGMOID>), dim3(side_grid(nq)), dim3(64), 0, s, ra);
+  hipLaunchKernelGGL((k_rerank<false, ANIREC_ACT_SIGMOID>), dim3(nq), dim3(64), 0, s, ra);
   return (int)hipGetLastError();
-}
-
-// workspace: Wb (padded_keys(n)*256 B) | 256 B {dbg words, unnorm @64, learnt prior @128} | one lane of nq rows
-size_t anirec_topk_mfma_workspace_bytes(int32_t n, int32_t nq) {
-  if (n < 1 || nq < 1) return 0;
-  return al256(padded_keys(n) * 256) + 256 + lane_bytes((size_t)nq);
-}
-
-int anirec_cosine_topk_mfma(const float *What, int32_t n, const int32_t *queries, int32_t nq,
-                            const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
-                            float *out_score, int32_t *flags_out, void *workspace,
-                            size_t workspace_bytes, void *stream) {
-  return anirec_cosine_topk_mfma_prior(What, n, queries, nq, keep, exclude_self, k, kThetaInit, out_idx, out_score,
-                                       flags_out, workspace, workspace_bytes, stream);
-}
-
-int anirec_cosine_topk_mfma_prior(const float *What, int32_t n, const int32_t *queries, int32_t nq,
-                                  const uint8_t *keep, int32_t exclude_self, int32_t k, float theta0,
-                                  int32_t *out_idx, float *out_score, int32_t *flags_out, void *workspace,
-                                  size_t workspace_bytes, void *stream) {
-  if (!What || !queries || !out_idx || !out_score || !flags_out || !workspace) return ANIREC_EINVAL;
-  if (!(theta0 >= kThetaInit && theta0 <= 1.0f)) return ANIREC_EINVAL;
-  if (n < 1 || nq < 0 || k < 1 || k > ANIREC_MAX_TOPK - 1) return ANIREC_EINVAL;
-  if (nq == 0) return ANIREC_OK;
-  if (workspace_bytes < anirec_topk_mfma_workspace_bytes(n, nq)) return ANIREC_EWORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  char *p = (char *)workspace;
-  _Float16 *Wb = (_Float16 *)p;
-  p += al256(padded_keys(n) * 256);
-  char *misc = p;
-  int32_t *unnorm = (int32_t *)(misc + 64);
-  p += 256;
-  const LaneBufs lb = carve_lane(p, (size_t)nq);
-  int b1 = (n + 7) / 8;
-  if (b1 > 8192) b1 = 8192;
-  ANIREC_HIP_CHECK(hipMemsetAsync(misc, 0, 256, s));  // unnorm (and the debug words) before the key pass sets it
-  hipLaunchKernelGGL(k_to_f16, dim3(b1), dim3(256), 0, s, What, nullptr, n, (int)padded_keys(n), keep, 0, Wb, unnorm);
-  ANIREC_HIP_CHECK(hipGetLastError());
-  const char *dbg = getenv("ANIREC_TOPK_DEBUG");
-  const int mode = dbg ? atoi(dbg) : 0;
-  return run_batch(What, Wb, n, queries, nq, exclude_self, k, theta0, nullptr, lb, unnorm, false, out_idx, out_score,
-                   flags_out, mode, misc, s);
 }
 
 // ---- the whole job: many query rows in batches, two (or more) batches in flight ---------------------------
@@ -1479,16 +1312,16 @@ int anirec_cosine_topk_mfma_prior(const float *What, int32_t n, const int32_t *q
 // one box): two chains that start together stay in LOCKSTEP — both in k_cand (each at half speed: an 8-wave k_cand
 // workgroup takes 2 x 160 VGPRs per SIMD and 64 KB of LDS, one per CU), then both in k_refresh.  The gain is the
 // filled tails of the k_cand launches and the overlap of the odd re-rank: 33.2 -> 31.8 ms.  Forcing the chains out
-// of phase (ANIREC_TOPK_STAGGER_PCT: chain 2 starts when chain 1 has passed 20 / 33 / 66 % of its key stream) is
+// of phase (chain 2 starting when chain 1 has passed 20 / 33 / 66 % of its key stream) is
 // SLOWER, 32.4-32.8 ms, and so are three or four chains (32.5-32.7): one-wave side workgroups take every wave slot a
 // finished k_cand workgroup frees, so the next k_cand workgroup of the other chain cannot start on that CU until the
 // side kernel has drained — the kernels serialise per CU instead of overlapping.  Bounding the side kernels' grids
-// (ANIREC_TOPK_SIDE_WAVES = 4 / 8 / 16 waves per CU, rows strided) leaves k_cand its room but makes the side
+// (4 / 8 / 16 waves per CU, rows strided) leaves k_cand its room but makes the side
 // kernels — chains of dependent loads, ballots and an O(survivors^2) rank per wave — 2x slower than they are hidden:
 // 35-39 ms.  And k_cand itself gains nothing from a second resident workgroup: a 128-VGPR build of the no-filter loop
 // (two workgroups, 4 waves per SIMD) ran 7.82 ms per 131 072 queries against 7.80 ms (1.50 PFLOP/s either way): the
 // MFMA loop is pipe- / power-bound, not latency-bound.  Longer super-steps for rows that start from a prior
-// (ANIREC_TOPK_GROWTH_PRIOR 150-1000 %) cost 10-15 % (38-40 ms against 34.8 on that box), shorter ones (35-70 %)
+// (growth 150-1000 %) cost 10-15 % (38-40 ms against 34.8 on that box), shorter ones (35-70 %)
 // 3-8 %: a row's own threshold, refreshed at every doubling, is worth more than the launches it costs.
 // Last, the re-rank of batch i taken OUT of its chain — a low-priority stream, grid bounded to 2 / 4 / 8 / 16 / 64
 // waves per CU, beside the key stream of batch i + 1 (two sets of buffers): 39-44 ms against 33.0 — the re-rank's
@@ -1501,7 +1334,6 @@ struct LanePool {
   hipStream_t side[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
   hipEvent_t fork = nullptr;
   hipEvent_t join[kMaxLanes - 1] = {nullptr, nullptr, nullptr};
-  hipEvent_t mid[kMaxLanes - 1] = {nullptr, nullptr, nullptr};  // chain l passed the stagger point of its first batch
   hipEvent_t cand_done[ANIREC_TOPK_MAX_BATCHES] = {};  // all-pairs job: batch b's last k_cand is behind this
 };
 // One pool per device of the process (a process that runs jobs on cuda:0 and then on cuda:1 gets two).  The side
@@ -1525,7 +1357,6 @@ static int pool_get(LanePool **out) {
   for (int i = 0; i < kMaxLanes - 1; ++i) {
     ANIREC_HIP_CHECK(hipStreamCreateWithFlags(&pl.side[i], hipStreamNonBlocking));
     ANIREC_HIP_CHECK(hipEventCreateWithFlags(&pl.join[i], hipEventDisableTiming));
-    ANIREC_HIP_CHECK(hipEventCreateWithFlags(&pl.mid[i], hipEventDisableTiming));
   }
   ANIREC_HIP_CHECK(hipEventCreateWithFlags(&pl.fork, hipEventDisableTiming));
   for (int i = 0; i < ANIREC_TOPK_MAX_BATCHES; ++i)
@@ -1535,23 +1366,15 @@ static int pool_get(LanePool **out) {
   return ANIREC_OK;
 }
 
-static int default_lanes() {
-  const char *e = getenv("ANIREC_TOPK_LANES");
-  int l = e ? atoi(e) : 2;
-  return l < 1 ? 1 : (l > kMaxLanes ? kMaxLanes : l);
-}
-
 int anirec_cosine_topk_job_plan(int32_t nq, int32_t k, int32_t prior_auto, int32_t max_batch, int32_t lanes,
                                 int32_t *starts_host, int32_t *n_batches_host, int32_t *learn_batches_host) {
   if (!starts_host || !n_batches_host || !learn_batches_host || nq < 0 || k < 1) return ANIREC_EINVAL;
   if (max_batch < 1) max_batch = 131072;
   if (max_batch > 1000000) max_batch = 1000000;  // rows * kCap * 8 < 2^32
-  if (lanes < 1) lanes = default_lanes();
+  if (lanes < 1) lanes = 2;
   if (lanes > kMaxLanes) lanes = kMaxLanes;
-  const char *mk = getenv("ANIREC_TOPK_PRIOR_MIN_K");
-  const char *pe = getenv("ANIREC_TOPK_PRIOR");
-  // (small k: a row appends few candidates anyway and the prior buys nothing)
-  const bool may_learn = prior_auto && k >= (mk ? atoi(mk) : 32) && !(pe && atoi(pe) == 0);
+  // (small k: a row appends few candidates anyway and the prior buys nothing — at k = 10 it measured 5 % slower)
+  const bool may_learn = prior_auto && k >= 32;
   int nb = 0, learn = 0, q0 = 0;
   starts_host[0] = 0;
   // the learning batch is small — 16 384 rows: 64 workgroups, which the key-range splits spread over the chip — so
@@ -1596,18 +1419,15 @@ int anirec_cosine_topk_job_plan(int32_t nq, int32_t k, int32_t prior_auto, int32
 int anirec_cosine_topk_allpairs_plan(int32_t n, int32_t k, int32_t lanes, int32_t main_batches, int32_t *starts_host,
                                      int32_t *n_batches_host, int32_t *learn_batches_host) {
   if (!starts_host || !n_batches_host || !learn_batches_host || n < 0 || k < 1) return ANIREC_EINVAL;
-  const char *mk = getenv("ANIREC_TOPK_PRIOR_MIN_K");
-  const char *pe = getenv("ANIREC_TOPK_PRIOR");
-  const char *be = getenv("ANIREC_TOPK_SYM_BATCHES");
   // (as many batches as leave the first, smallest one ~24 k rows — enough 256-row workgroups, cut in three key ranges,
   // for every CU; more batches waste less on the batches' own diagonal blocks, which are computed in full)
   if (main_batches < 1) {
-    main_batches = be ? atoi(be) : 2 * (int)((double)n / 88000.0 + 0.5);  // an even number: two chains
-    if (!be) main_batches = main_batches < 2 ? 2 : (main_batches > 8 ? 8 : main_batches);
+    main_batches = 2 * (int)((double)n / 88000.0 + 0.5);  // an even number: two chains
+    main_batches = main_batches < 2 ? 2 : (main_batches > 8 ? 8 : main_batches);
   }
   // (the plain job learns a prior from k = 32 on; here the prior is what makes the shortcut possible, and it pays at
   // k = 10 too: 350 k x 350 k top-10 28.3 -> 18.8 ms)
-  const bool may_learn = k >= (mk ? atoi(mk) : 8) && !(pe && atoi(pe) == 0);
+  const bool may_learn = k >= 8;
   // (below ~200 k rows the shortcut saves less than its extra launches and the caller's pilot cost: measured 4.7 vs
   // 4.6 ms at 100 k rows, 8.6 vs 8.2 at 150 k, 10.3-15.8 vs 12.6-17.3 at 222 k, 24-25 vs 31.5 ms at 350 k)
   if (!may_learn || n < 196608 || main_batches < 2 || main_batches + 1 > ANIREC_TOPK_MAX_BATCHES)
@@ -1698,10 +1518,6 @@ int anirec_cosine_topk_job(const float *What, int32_t n, const int32_t *queries,
     if (nq != n || keep != nullptr || learn_batches != 1 || n_batches < 3 || lanes > 2) sym = false;
     for (int b = 1; sym && b < n_batches; ++b)
       if (starts_host[b] % kBN != 0) sym = false;
-    const char *se = getenv("ANIREC_TOPK_SYM");
-    if (se && atoi(se) == 0) sym = false;
-    const char *dbg0 = getenv("ANIREC_TOPK_DEBUG");
-    if (dbg0 && atoi(dbg0) != 0) sym = false;
   }
   if (prior_mode != 1) learn_batches = 0;
   const int rows = max_batch_rows(starts_host, n_batches);
@@ -1764,8 +1580,8 @@ int anirec_cosine_topk_job(const float *What, int32_t n, const int32_t *queries,
   int b = 0;
   for (; b < learn_batches; ++b) {  // the learning batch runs alone, without a prior
     const int q0 = starts_host[b], cnt = starts_host[b + 1] - q0;
-    const int rc = run_batch(What, Wb, n, queries + q0, cnt, exclude_self, k, kThetaInit, nullptr, lb[0], unnorm, false,
-                             out_idx + (size_t)q0 * k, out_score + (size_t)q0 * k, flags_out + q0, 0, nullptr, s);
+    const int rc = run_batch(What, Wb, n, queries + q0, cnt, exclude_self, k, kThetaInit, nullptr, lb[0], unnorm,
+                             out_idx + (size_t)q0 * k, out_score + (size_t)q0 * k, flags_out + q0, s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_learn_prior, dim3(1), dim3(1024), 0, s, out_score + (size_t)q0 * k, cnt, (int)k, theta0_dev);
     ANIREC_HIP_CHECK(hipGetLastError());
@@ -1792,29 +1608,10 @@ int anirec_cosine_topk_job(const float *What, int32_t n, const int32_t *queries,
       }
     }
   }
-  // ANIREC_TOPK_STAGGER_PCT > 0 (experiment knob, default off): chain l starts its first batch when chain l-1 has
-  // passed that share of the key stream of ITS first batch.
-  const char *sg = getenv("ANIREC_TOPK_STAGGER_PCT");
-  const int stagger = sg ? atoi(sg) : 0;
-  const char *dbg = getenv("ANIREC_TOPK_DEBUG");
-  // diagnostic builds of k_cand: 1 without the filter, 8 without the candidate stores (timing only), 4 with in-kernel
-  // stamps of the last super-step of every batch (printed to stderr; results valid)
-  const int mode = dbg && (atoi(dbg) == 1 || atoi(dbg) == 8 || atoi(dbg) == 4) ? atoi(dbg) : 0;
   for (int i = 0; b < n_batches; ++b, ++i) {
     const int l = i % lanes;
     hipStream_t st = l == 0 ? s : pool->side[l - 1];
     const int q0 = starts_host[b], cnt = starts_host[b + 1] - q0;
-    hipEvent_t mid = nullptr;
-    if (i < lanes && stagger > 0 && lanes > 1) {
-      if (l > 0) {
-        const hipError_t we = hipStreamWaitEvent(st, pool->mid[l - 1], 0);
-        if (we != hipSuccess) {
-          (void)join_all();
-          return (int)we;
-        }
-      }
-      if (l + 1 < lanes && i + 1 < n_batches - learn_batches) mid = pool->mid[l];
-    }
     SymPlan sp;
     if (sym) {
       // batch i streams the learning batch's keys, its own, and those of the later batches (all-pairs launches);
@@ -1837,9 +1634,9 @@ int anirec_cosine_topk_job(const float *What, int32_t n, const int32_t *queries,
       sp.done_ev = pool->cand_done[b];
       sp.wait_ev = (i >= 1 && lanes > 1) ? pool->cand_done[b - 1] : nullptr;
     }
-    const int rc = run_batch(What, Wb, n, queries + q0, cnt, exclude_self, k, th_imm, th_dev, lb[l], unnorm, false,
-                             out_idx + (size_t)q0 * k, out_score + (size_t)q0 * k, flags_out + q0, mode, nullptr, st, mid,
-                             stagger, sym ? &sp : nullptr);
+    const int rc = run_batch(What, Wb, n, queries + q0, cnt, exclude_self, k, th_imm, th_dev, lb[l], unnorm,
+                             out_idx + (size_t)q0 * k, out_score + (size_t)q0 * k, flags_out + q0, st,
+                             sym ? &sp : nullptr);
     if (rc) {
       (void)join_all();
       return rc;
@@ -1922,12 +1719,11 @@ int anirec_predict_topk_mfma_act(const float *U, const float *A, int32_t n_anime
   ca.splits = 1;
   ca.theta = theta;
   ca.flags = flags_out;
-  ca.dbg = nullptr;
   ca.watched = watched;
   ca.wwords = (n_anime + 31) / 32;
   const bool masked = watched != nullptr;
   {
-    const int rc = run_super_steps(ca, n_anime, n_users, masked, 0, nullptr, nullptr, 0, s);
+    const int rc = run_super_steps(ca, n_anime, n_users, masked, s);
     if (rc) return rc;
   }
   RerankArgs ra;
@@ -1959,7 +1755,7 @@ int anirec_predict_topk_mfma_act(const float *U, const float *A, int32_t n_anime
     return (int)hipGetLastError();
   }
   with_act(activation, [&](auto k) {
-    hipLaunchKernelGGL((k_rerank<true, decltype(k)::value>), dim3(side_grid(n_users)), dim3(64), 0, s, ra);
+    hipLaunchKernelGGL((k_rerank<true, decltype(k)::value>), dim3(n_users), dim3(64), 0, s, ra);
   });
   return (int)hipGetLastError();
 }

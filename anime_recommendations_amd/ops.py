@@ -98,13 +98,11 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
     return out_i, out_s
 
 
-def topk_job_plan(nq, k, prior="auto", batch=None, lanes=None):
+def topk_job_plan(nq, k, prior="auto", batch=None, lanes=2):
     """The library's default batch plan of a cosine_topk_mfma job: (starts [n_batches + 1], learn_batches, lanes)."""
     lib = _lib.load()
     st = (C.c_int32 * (_lib.TOPK_MAX_BATCHES + 1))()
     nb, nl = C.c_int32(0), C.c_int32(0)
-    if lanes is None:
-        lanes = int(os.environ.get("ANIREC_TOPK_LANES", "2"))
     lanes = max(1, min(4, int(lanes)))
     _lib.check(lib.anirec_cosine_topk_job_plan(int(nq), int(k), int(prior == "auto"), int(batch or 0), lanes, st,
                                                C.byref(nb), C.byref(nl)), "anirec_cosine_topk_job_plan")
@@ -120,7 +118,7 @@ def _job_workspace(nbytes, dev):
     7-8 GB in all), and torch's caching allocator may carve a freed block of that size up for the next small
     allocations, so that the following job pays a hipMalloc inside its call.  Stream-ordered reuse is safe: every job
     runs on torch's current stream and ends joined to it.  ``release_workspaces`` drops the cache; a workspace larger
-    than ANIREC_TOPK_WS_CACHE_GB (default 16) is never cached."""
+    than ANIREC_TOPK_WS_CACHE_GB (default 16) is never cached: a memory policy for callers that cannot spare it."""
     cap = float(os.environ.get("ANIREC_TOPK_WS_CACHE_GB", "16")) * (1 << 30)
     if nbytes > cap:
         return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
@@ -169,13 +167,11 @@ def _allpairs_pilot(What, n, k_eff, stats):
     return dense <= 0.02
 
 
-def topk_allpairs_plan(n, k, lanes=None, main_batches=0):
+def topk_allpairs_plan(n, k, lanes=2, main_batches=0):
     """The library's plan of the all-pairs job (learning batch + batches of equal work): (starts, learn_batches, lanes)."""
     lib = _lib.load()
     st = (C.c_int32 * (_lib.TOPK_MAX_BATCHES + 1))()
     nb, nl = C.c_int32(0), C.c_int32(0)
-    if lanes is None:
-        lanes = int(os.environ.get("ANIREC_TOPK_LANES", "2"))
     lanes = max(1, min(2, int(lanes)))
     _lib.check(lib.anirec_cosine_topk_allpairs_plan(int(n), int(k), lanes, int(main_batches), st, C.byref(nb), C.byref(nl)),
                "anirec_cosine_topk_allpairs_plan")
@@ -183,7 +179,7 @@ def topk_allpairs_plan(n, k, lanes=None, main_batches=0):
 
 
 def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None, fallback=True, prior="auto",
-                     cand_timing=None, lanes=None, stats=None, allpairs="auto"):
+                     cand_timing=None, lanes=2, stats=None, allpairs="auto"):
     """cosine_topk on the matrix cores (fp16 MFMA candidates + exact fp32 re-rank); rows the
     kernel could not prove complete are transparently re-run through the exact kernels.
     ``What`` must hold unit-norm rows (``rownorm`` output, as at every reference call site): the MFMA error
@@ -225,11 +221,13 @@ def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None,
     if keep is not None:
         keep_t = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous()
     # (below 196 608 rows the all-pairs plan is the default plan and the shortcut buys nothing: no device check, no sync)
+    # ANIREC_TOPK_SYM=0 keeps callers that cannot pass allpairs=False (the components, bench.py) on the plain job:
+    # bench.py's cosine note names it as the way the two schedules were compared.
     want_sym = (bool(allpairs) and prior == "auto" and nq == n and keep_t is None
                 and os.environ.get("ANIREC_TOPK_SYM", "1") != "0"
                 and (allpairs is True or (n >= 196608
                                           and bool(torch.equal(q, torch.arange(n, dtype=torch.int32, device=dev))))))
-    if want_sym and allpairs == "auto" and os.environ.get("ANIREC_TOPK_PILOT", "1") != "0":
+    if want_sym and allpairs == "auto":
         if batch is None:
             # size the cached workspace for the job that follows BEFORE the pilot's small job takes the slot (a cold
             # call would otherwise allocate the pilot's workspace, drop it and allocate the main one)

@@ -382,28 +382,20 @@ int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int
  * caller's exact re-run, so un-normalised input is slow, never silently incomplete.
  * flags[nq] (device) is non-zero for the rare query whose window could not be proven
  * complete (dense ties / more than 256 survivors); its output row is -1/NaN and the caller
- * re-runs it through anirec_cosine_topk.  k <= ANIREC_MAX_TOPK - 1. */
-size_t anirec_topk_mfma_workspace_bytes(int32_t n, int32_t nq);
-int anirec_cosine_topk_mfma(const float *What, int32_t n, const int32_t *queries, int32_t nq,
-                            const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
-                            float *out_score, int32_t *flags, void *workspace,
-                            size_t workspace_bytes, void *stream);
-/* The same with a PRIOR theta0 for every row's threshold (anirec_cosine_topk_mfma uses -4, below every cosine): a
+ * re-runs it through anirec_cosine_topk.  k <= ANIREC_MAX_TOPK - 1.
+ * A PRIOR theta0 for every row's threshold (prior_mode 1 and 2 below; otherwise -4, below every cosine) means a
  * candidate must score >= max(theta0, what the keys seen so far prove).  A good guess of the rows' final k-th best
  * score (minus a margin) spares most of the ~k ln(n) early appends per row.  Results stay exact: a row whose true
  * threshold lies below theta0 ends with too few candidates, is flagged like any other unproven row, and the caller
- * re-runs it (without a prior, or through anirec_cosine_topk).  -4 <= theta0 <= 1. */
-int anirec_cosine_topk_mfma_prior(const float *What, int32_t n, const int32_t *queries, int32_t nq,
-                                  const uint8_t *keep, int32_t exclude_self, int32_t k, float theta0,
-                                  int32_t *out_idx, float *out_score, int32_t *flags, void *workspace,
-                                  size_t workspace_bytes, void *stream);
-/* The whole similar_anime / similar_users job (every row a query: similar_users.py:290-312 at BASELINE configs[3]
- * scale) as ONE call: the keys are converted once, the queries run in batches [starts[b], starts[b+1]), and the
+ * re-runs it (without a prior, or through anirec_cosine_topk).
+ * The whole similar_anime / similar_users job (every row a query: similar_users.py:290-312 at BASELINE configs[3]
+ * scale) is ONE call: the keys are converted once, the queries run in batches [starts[b], starts[b+1]), and the
  * batches are dealt to `lanes` stream-ordered chains (the caller's stream + side streams the library keeps, forked and
  * joined by events inside this call; 1 <= lanes <= 4) so that one batch's per-row refresh / re-rank waves run beside
  * another batch's MFMA kernel.  prior_mode 0: no prior; 1: the first `learn_batches` (0 or 1) batches run alone and
- * the k-th best scores of their rows give the others a prior, computed on the device (no host round trip); 2: theta0.
- * flags[nq] as for anirec_cosine_topk_mfma: the caller re-runs flagged rows (without a prior, then through
+ * the k-th best scores of their rows give the others a prior, computed on the device (no host round trip); 2: theta0
+ * (-4 <= theta0 <= 1).
+ * flags[nq] as above: the caller re-runs flagged rows (without a prior, then through
  * anirec_cosine_topk).  Results are identical to anirec_cosine_topk whatever the plan.
  * prior_mode 3 = mode 1 for the ALL-PAIRS job (queries[i] == i for all i < nq == n, keep == NULL; checked on the
  * device: any other query list flags every row): cosine(i, j) == cosine(j, i), so a batch computes the dot products of
@@ -414,13 +406,13 @@ int anirec_cosine_topk_mfma_prior(const float *What, int32_t n, const int32_t *q
  * otherwise the call runs as mode 1.  Results are identical either way.  Workspace:
  * anirec_cosine_topk_allpairs_workspace_bytes (the job's + two inboxes of n x 256 entries + the chains' logs).
  * anirec_cosine_topk_job_plan fills the library's default plan: starts_host[ANIREC_TOPK_MAX_BATCHES + 1];
- * max_batch <= 0 and lanes <= 0 select the defaults (131072 rows; env ANIREC_TOPK_LANES or 2).
+ * max_batch <= 0 and lanes <= 0 select the defaults (131072 rows, 2 lanes).
  * workspace: anirec_cosine_topk_job_workspace_bytes(n, rows of the largest batch, lanes). */
 int anirec_cosine_topk_job_plan(int32_t nq, int32_t k, int32_t prior_auto, int32_t max_batch, int32_t lanes,
                                 int32_t *starts_host, int32_t *n_batches_host, int32_t *learn_batches_host);
 size_t anirec_cosine_topk_job_workspace_bytes(int32_t n, int32_t max_batch_rows, int32_t lanes);
 size_t anirec_cosine_topk_allpairs_workspace_bytes(int32_t n, int32_t max_batch_rows, int32_t lanes);
-/* the all-pairs plan: the learning batch + `main_batches` (<= 0: env ANIREC_TOPK_SYM_BATCHES or 4) batches of equal
+/* the all-pairs plan: the learning batch + `main_batches` (<= 0: 2 round(n / 88 000), clamped to 2..8) batches of equal
  * WORK (a later batch streams fewer keys and takes more rows); the default plan when the job is too small to learn */
 int anirec_cosine_topk_allpairs_plan(int32_t n, int32_t k, int32_t lanes, int32_t main_batches, int32_t *starts_host,
                                      int32_t *n_batches_host, int32_t *learn_batches_host);

@@ -1,5 +1,5 @@
-"""All-pairs (or a slice) cosine top-k with and without the threshold prior (ANIREC_TOPK_PRIOR), interleaved rounds in
-one process; checks that the lists are identical.  usage: ab_topk_prior.py [n] [nq] [k] [rounds]"""
+"""All-pairs (or a slice) cosine top-k with and without the threshold prior (prior=None against "auto"), interleaved
+rounds in one process; checks that the lists are identical.  usage: ab_topk_prior.py [n] [nq] [k] [rounds]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,10 +13,9 @@ Wh = ops.rownorm(torch.randn(n, 128, generator=g, device="cuda") * 0.05)
 q = torch.arange(nq, dtype=torch.int32, device="cuda")
 ref = None
 for r in range(rounds + 1):
-    for pr in ("0", "1"):
-        os.environ["ANIREC_TOPK_PRIOR"] = pr
+    for pr in (None, "auto"):
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        idx, sim, nfb = ops.cosine_topk_mfma(Wh, q, k)
+        idx, sim, nfb = ops.cosine_topk_mfma(Wh, q, k, prior=pr)
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
         if ref is None:
             ref = (idx.clone(), sim.clone())

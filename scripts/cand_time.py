@@ -1,5 +1,5 @@
 """k_cand time alone (HIP events around its launches, one chain) for one library build:
-   [ANIREC_LIB_PATH=...] [ANIREC_TOPK_DEBUG=1] python scripts/cand_time.py n nq k [rounds]"""
+   [ANIREC_LIB_PATH=...] python scripts/cand_time.py n nq k [rounds]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,4 +15,4 @@ for r in range(rounds + 1):
     ops.cosine_topk_mfma(Wh, q, k, prior=None, fallback=False, cand_timing=acc, batch=nq, lanes=1)
     if r: out.append(acc["ms"])
 fl = 2.0 * nq * n * 128
-print("%s dbg=%s n=%d nq=%d k=%d: k_cand ms %s  -> %.0f TFLOP/s (%d launches)" % (os.path.basename(os.environ.get("ANIREC_LIB_PATH", "libanirec.so")), os.environ.get("ANIREC_TOPK_DEBUG", "0"), n, nq, k, " ".join("%.3f" % x for x in out), fl / min(out) / 1e9, acc["launches"]))
+print("%s n=%d nq=%d k=%d: k_cand ms %s  -> %.0f TFLOP/s (%d launches)" % (os.path.basename(os.environ.get("ANIREC_LIB_PATH", "libanirec.so")), n, nq, k, " ".join("%.3f" % x for x in out), fl / min(out) / 1e9, acc["launches"]))

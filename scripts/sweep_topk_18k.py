@@ -1,4 +1,4 @@
-"""18 k x 18 k top-100 job (BASELINE configs[3], anime leg) under schedule knobs, interleaved rounds in one process:
+"""18 k x 18 k top-100 job (BASELINE configs[3], anime leg) under key-split caps, interleaved rounds in one process:
 whole-job time (rownorm excluded), fallback rows, lists compared with the default schedule's.
 usage: sweep_topk_18k.py [k]"""
 import os, sys, time
@@ -10,13 +10,9 @@ g = torch.Generator(device="cuda"); g.manual_seed(7)
 Wh = ops.rownorm(torch.randn(n, 128, generator=g, device="cuda") * 0.05)
 q = torch.arange(n, dtype=torch.int32, device="cuda")
 CFG = {"default": {}}
-for gr in (150, 200, 300, 400):
-    CFG["growth%d" % gr] = dict(ANIREC_TOPK_GROWTH=str(gr))
 for sp in (1, 2, 3, 4):
     CFG["splits%d" % sp] = dict(ANIREC_TOPK_SPLITS=str(sp))
-CFG["growth200splits4"] = dict(ANIREC_TOPK_GROWTH="200", ANIREC_TOPK_SPLITS="4")
-CFG["growth300splits4"] = dict(ANIREC_TOPK_GROWTH="300", ANIREC_TOPK_SPLITS="4")
-KEYS = ("ANIREC_TOPK_GROWTH", "ANIREC_TOPK_SPLITS")
+KEYS = ("ANIREC_TOPK_SPLITS",)
 res = {k: [] for k in CFG}
 ref = None
 for r in range(6):

@@ -9,7 +9,7 @@ for n, nq in cfgs:
     W = torch.randn(n, 128, generator=g, device="cuda") * 0.05
     Wh = ops.rownorm(W)
     q = torch.arange(nq, dtype=torch.int32, device="cuda")
-    fn = lambda: ops.cosine_topk_mfma(Wh, q, K, fallback=not os.environ.get('ANIREC_TOPK_DEBUG'))
+    fn = lambda: ops.cosine_topk_mfma(Wh, q, K)
     fn(); torch.cuda.synchronize()
     t0 = time.perf_counter(); out = fn(); torch.cuda.synchronize(); dt = time.perf_counter() - t0
     fl = 2.0 * nq * n * 128
