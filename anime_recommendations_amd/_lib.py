@@ -28,6 +28,11 @@ OPT_ADAM, OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
 # anirec_train_desc.loss (ANIREC_LOSS_*) and .activation / the predict calls' activation (ANIREC_ACT_*)
 LOSS_BCE, LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOGCOSH = 0, 1, 2, 3, 4
 ACT_SIGMOID, ACT_LINEAR, ACT_TANH, ACT_RELU, ACT_SOFTPLUS = 0, 1, 2, 3, 4
+# Keras metrics accumulated on the GPU (ANIREC_METRIC_*): the bit of each kind; anirec_metric_acc.sum holds bits 0..5
+METRIC_MAE, METRIC_MAPE, METRIC_MSLE, METRIC_LOGCOSH, METRIC_BCE, METRIC_ACC, METRIC_AUC = 1, 2, 4, 8, 16, 32, 64
+METRIC_KINDS = 6
+AUC_BINS = 200
+AUC_ONE = 1 << 20
 
 
 class AnirecError(RuntimeError):
@@ -52,7 +57,11 @@ STATE_DTYPE = np.dtype([
     ("bce_wsum", "<f8"), ("reg_user_wsum", "<f8"), ("reg_anime_wsum", "<f8"),
     ("reg_user_sumsq", "<f4"), ("reg_anime_sumsq", "<f4"),
 ], align=True)
+# anirec_metric_acc
+METRIC_ACC_DTYPE = np.dtype([("sum", "<f8", (METRIC_KINDS,)), ("auc_pos", "<u8", (AUC_BINS,)),
+                             ("auc_neg", "<u8", (AUC_BINS,))])
 assert STEP_DTYPE.itemsize == 16
+assert METRIC_ACC_DTYPE.itemsize == 8 * (METRIC_KINDS + 2 * AUC_BINS)
 assert STATE_DTYPE.itemsize == 168, STATE_DTYPE.itemsize
 
 
@@ -116,6 +125,9 @@ PROTOTYPES = {
     "anirec_trainer_destroy": (C.c_int, [_vp]),
     "anirec_trainer_run": (C.c_int, [_vp, _i32, _i32, _i32, _vp]),
     "anirec_eval": (C.c_int, [_DP, _vp, _vp, _vp, _i32, _vp]),
+    "anirec_trainer_set_metrics": (C.c_int, [_vp, C.c_uint32, _vp]),
+    "anirec_dist_stepper_set_metrics": (C.c_int, [_vp, C.c_uint32, _vp]),
+    "anirec_eval_metrics": (C.c_int, [_DP, C.c_uint32, _vp, _vp, _vp, _vp, _i32, _vp]),
     "anirec_adam_flat": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _f32, _vp]),
     "anirec_opt_flat": (C.c_int, [_i32, _vp, _vp, _vp, _sz, _f32, _vp]),
     "anirec_selftest_lazy_math": (C.c_int, [C.c_uint64, _vp, _vp]),

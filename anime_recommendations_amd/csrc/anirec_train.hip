@@ -10,7 +10,8 @@
 //         reductions by wavefront shuffles -> c, sum(u^2), sum(a^2)
 //   head  one workgroup per 256 ratings: batch mean/variance recomputed per workgroup,
 //         Dense(1) -> BatchNorm(batch stats) -> activation -> loss (anirec_train_desc::activation / ::loss; one
-//         instantiation per pair, the default sigmoid + BCE as it always was), d loss/d y, partial sums
+//         instantiation per pair, the default sigmoid + BCE as it always was), d loss/d y, partial sums; with a
+//         handle's metric set (anirec_trainer_set_metrics) k_head_metrics also accumulates the Keras metrics
 //   bwd   half-wave per chunk: weighted sum of the OTHER table's rows, accumulated in
 //         registers in a fixed order, one coalesced 512-B store per chunk (no float atomics)
 //   adam  half-wave per table row, dense: g = chunk sums - s*W + 2*l2*W, Keras-2.12 Adam,
@@ -541,10 +542,61 @@ struct HeadIn {
   float w, b, gamma, beta;
 };
 
+// ---- Keras metrics (include/anirec.h, ANIREC_METRIC_*): the metrics instantiations of the head and of validation
+// add the requested kinds to a caller-owned anirec_metric_acc; the default instantiations never see these
+struct MetricArgs {
+  uint32_t mask;  // ANIREC_METRIC_* bits, non-zero (wave-uniform: a kernel argument)
+  anirec_metric_acc *acc;
+};
+constexpr int kMetricKinds = ANIREC_METRIC_KINDS;
+constexpr int kAucBins = ANIREC_AUC_BINS;
+constexpr uint32_t kMetricBits = (1u << (kMetricKinds + 1)) - 1;  // every ANIREC_METRIC_* bit
+
+// the per-rating values of the scalar kinds (0 for a kind the mask does not ask for), Keras 2.12 definitions with one
+// rounding per operation
+template <int kAct>
+__device__ __forceinline__ void metric_terms(uint32_t mask, float y, float t, float p, float (&v)[kMetricKinds]) {
+#pragma clang fp contract(off)
+  const float ae = fabsf(p - t);
+  v[0] = ae;                                                                          // mean_absolute_error
+  v[1] = (mask & ANIREC_METRIC_MAPE) ? 100.f * (ae / fmaxf(fabsf(t), kBceEps)) : 0.f;  // ..._percentage_error
+  if (mask & ANIREC_METRIC_MSLE) {                                                    // ..._squared_logarithmic_error
+    const float d = logf(fmaxf(p, kBceEps) + 1.f) - logf(fmaxf(t, kBceEps) + 1.f);
+    v[2] = d * d;
+  } else {
+    v[2] = 0.f;
+  }
+  float l = 0.f, g;
+  if (mask & ANIREC_METRIC_LOGCOSH) loss_terms<ANIREC_LOSS_LOGCOSH>(p, t, l, g);
+  v[3] = l;
+  v[4] = (mask & ANIREC_METRIC_BCE) ? head_loss<kAct, ANIREC_LOSS_BCE>(y, t, p) : 0.f;  // (from logits: sigmoid)
+  v[5] = t == (p > 0.5f ? 1.f : 0.f) ? 1.f : 0.f;                                       // binary_accuracy
+}
+
+// AUC bucket of a prediction (Keras' evenly-spaced-thresholds path: ceil(p * (200 - 1)) - 1 in fp32, relu) and the
+// fixed-point label mass of a rating; the clamps only keep a NaN or out-of-range value inside the bins
+__device__ __forceinline__ int auc_bucket(float p) {
+  return (int)fminf(fmaxf(ceilf(p * (float)(kAucBins - 1)) - 1.f, 0.f), (float)(kAucBins - 1));
+}
+__device__ __forceinline__ uint32_t auc_pos_mass(float t) {
+  return (uint32_t)rintf(fminf(fmaxf(t, 0.f), 1.f) * (float)ANIREC_AUC_ONE);
+}
+
+// a workgroup's block-summed kinds into the fp64 accumulators: one atomic per requested kind (the order dependence
+// stays far below the History's fp32, as in k_eval)
+__device__ __forceinline__ void metric_flush(const MetricArgs &m, const float (&v)[kMetricKinds]) {
+#pragma unroll
+  for (int k = 0; k < kMetricKinds; ++k)
+    if (m.mask & (1u << k)) atomicAdd(&m.acc->sum[k], (double)v[k]);
+}
+
 // workgroup vblk of nvb: the batch statistics (recomputed per workgroup) + 256 ratings; kAct / kLoss: the output head
-// (ANIREC_ACT_* / ANIREC_LOSS_*, head_terms), one instantiation per pair
-template <int kAct, int kLoss>
-__device__ __forceinline__ void head_block(const HeadArgs &a, const HeadIn in, int vblk, int nvb, float *scratch) {
+// (ANIREC_ACT_* / ANIREC_LOSS_*, head_terms), one instantiation per pair.  kMetrics: also the Keras metrics of m over
+// the workgroup's ratings — scratch then holds kHeadCols * 16 floats and, behind them, the zeroed 2 * kAucBins-word AUC
+// histogram (k_head_metrics)
+template <int kAct, int kLoss, bool kMetrics = false>
+__device__ __forceinline__ void head_block(const HeadArgs &a, const HeadIn in, int vblk, int nvb, float *scratch,
+                                           MetricArgs m = {}) {
   const int tid = threadIdx.x;
   const int pcap = packet_cap(a.cap);
   const int bps = (a.cap + kHeadThreads - 1) / kHeadThreads;  // blocks per segment
@@ -614,6 +666,9 @@ __device__ __forceinline__ void head_block(const HeadArgs &a, const HeadIn in, i
   for (int s = 0; s < ANIREC_MAX_SEG; ++s)
     if (s == seg) cnt = cnts[s];
   float r[kHeadCols] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float mv[kMetricKinds] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  uint32_t *hist = reinterpret_cast<uint32_t *>(scratch + kHeadCols * 16);
+  if constexpr (kMetrics) __syncthreads();  // the zeroed histogram (the several-rank branch has no barrier)
   if (i < cnt) {
     const float c = my_c, t = my_t;
     const float z = c * w + b;
@@ -631,10 +686,29 @@ __device__ __forceinline__ void head_block(const HeadArgs &a, const HeadIn in, i
     r[6] = zh * c;
     r[7] = zh;
     if (seg == a.my_seg) a.dy[i] = dy;
+    if constexpr (kMetrics) {
+      metric_terms<kAct>(m.mask, y, t, p, mv);
+      if (m.mask & ANIREC_METRIC_AUC) {  // LDS integer adds: order-independent
+        const int bk = auc_bucket(p);
+        const uint32_t wt = auc_pos_mass(t);
+        atomicAdd(&hist[bk], wt);
+        atomicAdd(&hist[kAucBins + bk], ANIREC_AUC_ONE - wt);
+      }
+    }
   }
   block_sum<kHeadCols>(r, scratch);
   const int par = step & 1;
   if (tid < kHeadCols) a.hpart[par * a.hpart_stride + (size_t)vblk * kHeadCols + tid] = r[tid];
+  if constexpr (kMetrics) {
+    block_sum<kMetricKinds>(mv, scratch);  // (its barriers also complete the histogram)
+    if (tid == 0) metric_flush(m, mv);
+    if (m.mask & ANIREC_METRIC_AUC) {
+      for (int k = tid; k < 2 * kAucBins; k += kHeadThreads) {
+        const uint32_t h = hist[k];
+        if (h) atomicAdd(k < kAucBins ? &m.acc->auc_pos[k] : &m.acc->auc_neg[k - kAucBins], (unsigned long long)h);
+      }
+    }
+  }
 
   if (vblk == 0) {
     if (tid == 0) {
@@ -1666,6 +1740,29 @@ __global__ __launch_bounds__(kHeadThreads) void k_head(HeadArgs a, LazyArgs z, i
   tick(a.ticks, 1);
 }
 
+// the same launch with the Keras metrics of m (anirec_trainer_set_metrics / anirec_dist_stepper_set_metrics).  ALL of
+// its LDS is one array — the block-sum scratch, then the AUC histogram — since a second __shared__ object can make
+// hipcc wait vmcnt(0) in front of LDS accesses (the histogram is zeroed before the first barrier of head_block)
+template <int kAct, int kLoss>
+__global__ __launch_bounds__(kHeadThreads) void k_head_metrics(HeadArgs a, LazyArgs z, int n_head, MetricArgs m) {
+  __shared__ float lds[kHeadCols * 16 + 2 * kAucBins];
+  tick(a.ticks, 0);
+  const anirec_state *st = a.state;
+  if ((int)blockIdx.x >= n_head) {  // (the catch-up workgroups as in k_head)
+    const int step = st->step_fwd, w0 = z.w0[0];
+    if (step + 1 < z.n_steps && step + 1 - w0 <= kLzWin)
+      lazy_catchup_row(z, step + 1, w0, z.cu_lo + (int)blockIdx.x - n_head, step + 1);
+    tick(a.ticks, 1);
+    return;
+  }
+  if (m.mask & ANIREC_METRIC_AUC) {
+    for (int k = threadIdx.x; k < 2 * kAucBins; k += kHeadThreads) lds[kHeadCols * 16 + k] = 0.f;  // (0.f: 0u)
+  }
+  const HeadIn in = {st->step_fwd, st->w, st->b, st->gamma, st->beta};
+  head_block<kAct, kLoss, true>(a, in, blockIdx.x, n_head, lds, m);
+  tick(a.ticks, 1);
+}
+
 // after bwd(t): step t on the rows the batch touched (chunk gradient - s W + 2 lambda W), the step finish in
 // workgroup 0.  Same operations, same order as the dense kernel's row_issue / row_finish for a touched row.
 // (the catch-up of batch t + 1's rows rides in k_head(t)'s launch)
@@ -2169,6 +2266,63 @@ __global__ __launch_bounds__(256) void k_eval(EvalArgs a) {
   }
 }
 
+// k_eval that also adds the Keras metrics of m (anirec_eval_metrics); k_eval itself stays the kernel it was
+template <int kAct, int kLoss>
+__global__ __launch_bounds__(256) void k_eval_metrics(EvalArgs a, MetricArgs m) {
+  __shared__ float sh[2 + kMetricKinds][8];
+  const anirec_state *st = a.state;
+  const float w = st->w, b = st->b;
+  const float inv = st->gamma * (1.0f / sqrtf(st->mov_var + kBnEps));
+  const float shift = st->beta - st->mov_mean * inv;
+  const int l32 = threadIdx.x & 31, h = threadIdx.x >> 5;
+  const int i = blockIdx.x * 8 + h;
+  float li = 0.f, se = 0.f;
+  float mv[kMetricKinds] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (i < a.n) {
+    float su, sa, dd;
+    pair_dots(reinterpret_cast<const float4 *>(a.W), a.user_idx[i], a.anime_idx[i] + a.n_user_rows,
+              l32, su, sa, dd);
+    const float c = cos_from_dots(su, sa, dd);
+    const float y = (c * w + b) * inv + shift;
+    const float t = a.rating[i];
+    float p, g;
+    head_grad<kAct, kLoss>(y, t, p, g);
+    li = head_loss<kAct, kLoss>(y, t, p);
+    se = (p - t) * (p - t);
+    metric_terms<kAct>(m.mask, y, t, p, mv);
+    if ((m.mask & ANIREC_METRIC_AUC) && l32 == 0) {  // 8 ratings a workgroup: straight into the integer bins
+      const int bk = auc_bucket(p);
+      const uint32_t wt = auc_pos_mass(t);
+      if (wt) atomicAdd(&m.acc->auc_pos[bk], (unsigned long long)wt);
+      if (wt != ANIREC_AUC_ONE) atomicAdd(&m.acc->auc_neg[bk], (unsigned long long)(ANIREC_AUC_ONE - wt));
+    }
+  }
+  if (l32 == 0) {
+    sh[0][h] = li;
+    sh[1][h] = se;
+#pragma unroll
+    for (int k = 0; k < kMetricKinds; ++k) sh[2 + k][h] = mv[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double L = 0., E = 0.;
+    for (int k = 0; k < 8; ++k) {
+      L += sh[0][k];
+      E += sh[1][k];
+    }
+    atomicAdd(&a.state->val_bce_sum, L);
+    atomicAdd(&a.state->val_se_sum, E);
+    if (blockIdx.x == 0) atomicAdd(&a.state->val_n, (double)a.n);
+#pragma unroll
+    for (int k = 0; k < kMetricKinds; ++k) {
+      if (!(m.mask & (1u << k))) continue;
+      double v = 0.;
+      for (int j = 0; j < 8; ++j) v += sh[2 + k][j];
+      atomicAdd(&m.acc->sum[k], v);
+    }
+  }
+}
+
 __global__ __launch_bounds__(1024) void k_sum_regpart(anirec_state *st, const float *regpart) {
   __shared__ float scratch[2 * 16];
   float r[2] = {0.f, 0.f};
@@ -2345,8 +2499,9 @@ static inline int catchup_head_share(const anirec_train_desc *d, const TrainWs &
 }
 
 // fuse_next (lazy update, the next batch's chunk table is in the arena): the launch also carries the catch-up
-// workgroups of that batch's rows
-static int launch_head(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool fuse_next = false) {
+// workgroups of that batch's rows.  m.mask != 0: the metrics instantiation (k_head_metrics)
+static int launch_head(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool fuse_next = false,
+                       MetricArgs m = {}) {
   const HeadArgs a = head_args(d, w);
   const int nh = head_blocks(d);
   LazyArgs z;
@@ -2360,8 +2515,12 @@ static int launch_head(const anirec_train_desc *d, const TrainWs &w, hipStream_t
   // the output head is a template parameter: the default pair's instantiation is the kernel as it always was
   with_act(d->activation, [&](auto act) {
     with_loss(d->loss, [&](auto loss) {
-      hipLaunchKernelGGL((k_head<decltype(act)::value, decltype(loss)::value>), dim3(nh + extra), dim3(kHeadThreads), 0,
-                         s, a, z, nh);
+      if (m.mask)
+        hipLaunchKernelGGL((k_head_metrics<decltype(act)::value, decltype(loss)::value>), dim3(nh + extra),
+                           dim3(kHeadThreads), 0, s, a, z, nh, m);
+      else
+        hipLaunchKernelGGL((k_head<decltype(act)::value, decltype(loss)::value>), dim3(nh + extra),
+                           dim3(kHeadThreads), 0, s, a, z, nh);
     });
   });
   if (int te = ticks_collect(w, 1, s)) return te;
@@ -2667,7 +2826,25 @@ struct RunHandle {
   TrainWs ws;
   hipGraphExec_t exec = nullptr;  // the captured block of graph_steps steps
   int graph_steps = 0;            // < 0: a capture failed, the handle runs eagerly from then on
+  MetricArgs metrics = {};        // the Keras metrics of every step (mask 0: none)
 };
+
+// host: a metric set the kernels implement for this descriptor (AUC needs p in [0, 1]: the sigmoid head)
+static int check_metrics(const anirec_train_desc *d, uint32_t mask) {
+  if (mask & ~kMetricBits) return ANIREC_EINVAL;
+  if ((mask & ANIREC_METRIC_AUC) && d->activation != ANIREC_ACT_SIGMOID) return ANIREC_EINVAL;
+  return ANIREC_OK;
+}
+
+// a handle's metric set; the captured graph holds the old kernel arguments: dropped
+static int set_metrics(RunHandle *h, uint32_t mask, anirec_metric_acc *acc) {
+  if (int e = check_metrics(&h->d, mask)) return e;
+  h->metrics = (mask && acc) ? MetricArgs{mask, acc} : MetricArgs{};
+  if (h->exec) (void)hipGraphExecDestroy(h->exec);
+  h->exec = nullptr;
+  if (h->graph_steps > 0) h->graph_steps = 0;
+  return ANIREC_OK;
+}
 
 // Runs steps [first_step, first_step + n_steps) of h's descriptor, `step(stream, flags)` enqueuing the launches of one
 // step.  With use_graph a block of G = min(32, arena_steps / 2) steps is captured once per handle and replayed: a
@@ -2730,12 +2907,12 @@ static int run_blocks(RunHandle *h, hipStream_t s, int first_step, int n_steps, 
 }
 
 // one step on one GPU: the dense update, or the lazy one with the launches its flags ask for
-static int train_step(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, StepFlags f) {
+static int train_step(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, StepFlags f, MetricArgs m) {
   const bool lazy = lazy_on(d);
   int e;
   if (lazy && f.catchup_first && (e = launch_lazy_catchup(d, w, s))) return e;
   if ((e = launch_fwd(d, w, s))) return e;
-  if ((e = launch_head(d, w, s, lazy && f.fuse_next))) return e;
+  if ((e = launch_head(d, w, s, lazy && f.fuse_next, m))) return e;
   if ((e = launch_bwd_only(d, w, s, lazy))) return e;
   if (!lazy) return launch_adam_full(d, w, s, 0);
   if ((e = launch_lazy_adam(d, w, s, f.fuse_next))) return e;
@@ -2909,7 +3086,7 @@ static int dist_front(anirec_dist_stepper *h, hipStream_t s, bool catchup_first)
 static int dist_mid(anirec_dist_stepper *h, hipStream_t s, bool fuse_next) {
   const bool lz = lazy_users(&h->d);
   int e;
-  if ((e = launch_head(&h->d, h->ws, s, lz && fuse_next))) return e;
+  if ((e = launch_head(&h->d, h->ws, s, lz && fuse_next, h->metrics))) return e;
   if ((e = launch_bwd_only(&h->d, h->ws, s, lz))) return e;
   if (h->d.dense_mode == 1) {
     ANIREC_HIP_CHECK(hipEventRecord(h->fork, s));
@@ -3148,13 +3325,30 @@ int anirec_trainer_run(anirec_trainer *t, int32_t first_step, int32_t n_steps, i
   if (!t || n_steps < 0 || first_step < 0 || first_step + n_steps > t->d.n_steps) return ANIREC_EINVAL;
   if (!t->d.user_idx || !t->d.anime_idx || !t->d.rating || !t->d.sched) return ANIREC_EINVAL;
   return run_blocks(t, (hipStream_t)stream, first_step, n_steps, use_graph != 0,
-                    [t](hipStream_t s, StepFlags f) { return train_step(&t->d, t->ws, s, f); });
+                    [t](hipStream_t s, StepFlags f) { return train_step(&t->d, t->ws, s, f, t->metrics); });
+}
+
+int anirec_trainer_set_metrics(anirec_trainer *t, uint32_t mask, anirec_metric_acc *acc) {
+  if (!t) return ANIREC_EINVAL;
+  return set_metrics(t, mask, acc);
+}
+
+int anirec_dist_stepper_set_metrics(anirec_dist_stepper *h, uint32_t mask, anirec_metric_acc *acc) {
+  if (!h) return ANIREC_EINVAL;
+  return set_metrics(h, mask, acc);
 }
 
 int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32_t *anime_idx,
                 const float *rating, int32_t n, void *stream) {
+  return anirec_eval_metrics(d, 0, nullptr, user_idx, anime_idx, rating, n, stream);
+}
+
+int anirec_eval_metrics(const anirec_train_desc *d, uint32_t mask, anirec_metric_acc *acc, const int32_t *user_idx,
+                        const int32_t *anime_idx, const float *rating, int32_t n, void *stream) {
   if (!d || !d->W || !d->state || !user_idx || !anime_idx || !rating || n < 0 || check_opt(d))
     return ANIREC_EINVAL;
+  if (check_metrics(d, mask)) return ANIREC_EINVAL;
+  const MetricArgs m = (mask && acc) ? MetricArgs{mask, acc} : MetricArgs{};
   if (n == 0) return ANIREC_OK;
   EvalArgs a;
   a.W = d->W;
@@ -3166,8 +3360,12 @@ int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32
   a.state = d->state;
   with_act(d->activation, [&](auto act) {
     with_loss(d->loss, [&](auto loss) {
-      hipLaunchKernelGGL((k_eval<decltype(act)::value, decltype(loss)::value>), dim3((n + 7) / 8), dim3(256), 0,
-                         (hipStream_t)stream, a);
+      if (m.mask)
+        hipLaunchKernelGGL((k_eval_metrics<decltype(act)::value, decltype(loss)::value>), dim3((n + 7) / 8),
+                           dim3(256), 0, (hipStream_t)stream, a, m);
+      else
+        hipLaunchKernelGGL((k_eval<decltype(act)::value, decltype(loss)::value>), dim3((n + 7) / 8), dim3(256), 0,
+                           (hipStream_t)stream, a);
     });
   });
   return (int)hipGetLastError();

@@ -122,7 +122,7 @@ class DistTrainEngine:
 
     def __init__(self, n_users, n_anime, batch_per_rank, l2=1e-4, arena_steps=64, device="cuda:0",
                  engine_factory=None, mode=None, lazy=None, optimizer="adam", loss="binary_crossentropy",
-                 activation="sigmoid"):
+                 activation="sigmoid", metrics=0):
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
@@ -160,6 +160,9 @@ class DistTrainEngine:
         self.loss, self.activation = schedule.resolve_loss(loss), schedule.resolve_activation(activation)
         if (self.loss, self.activation) != ("binary_crossentropy", "sigmoid"):   # (likewise the default head)
             kw.update(loss=self.loss, activation=self.activation)
+        self.metrics = int(metrics)          # ANIREC_METRIC_* bits (engine.TrainEngine)
+        if self.metrics:
+            kw["metrics"] = self.metrics
         self.eng = engine_factory(self.n_local, self.n_anime, max_batch=max_batch, l2=l2,
                                   arena_steps=arena_steps, device=device, n_seg=self.world,
                                   my_seg=self.rank, **kw)
@@ -415,6 +418,30 @@ class DistTrainEngine:
             ru, ra = self._sum_over_ranks([ru, ra])
         n = max(n, 1.0)
         return bce / n + self.l2 * (ru + ra), se / n
+
+    def epoch_logs(self):
+        """{kind: value} of the epoch (engine.TrainEngine.epoch_logs).  Every rank's head covers the whole global
+        batch, so the train metrics need no collective; the loss is ``epoch_metrics``' (collective)."""
+        loss, _ = self.epoch_metrics()
+        rec, acc = self.eng.read_state(), self.eng.read_metric_acc("train")
+        out = schedule.metric_values(self.metrics, acc["sum"], acc["auc_pos"], acc["auc_neg"], rec["n_seen"],
+                                     rec["se_sum"])
+        out["loss"] = loss
+        return out
+
+    def eval_logs(self, user, anime, rating):
+        """Validation pass (``evaluate``, collective); the metric sums and AUC bins of the ranks' rows are summed
+        over the ranks (bins below 2^53: exact in fp64)."""
+        val_loss, _ = self.evaluate(user, anime, rating)
+        rec, acc = self.eng.read_state(), self.eng.read_metric_acc("val")
+        raw = ([float(rec["val_n"]), float(rec["val_se_sum"])] + [float(x) for x in acc["sum"]]
+               + [float(x) for x in acc["auc_pos"]] + [float(x) for x in acc["auc_neg"]])
+        tot = np.array(self._sum_over_ranks(raw), np.float64)
+        k, nb = _lib.METRIC_KINDS, _lib.AUC_BINS
+        out = schedule.metric_values(self.metrics, tot[2:2 + k], tot[2 + k:2 + k + nb], tot[2 + k + nb:], tot[0],
+                                     tot[1])
+        out["loss"] = val_loss
+        return out
 
     def read_state(self):
         return self.eng.read_state()

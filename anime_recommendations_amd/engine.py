@@ -35,7 +35,7 @@ def _dev_bytes(n, device):
 class TrainEngine:
     def __init__(self, n_user_rows, n_anime_rows, max_batch, l2=1e-4, arena_steps=64,
                  device="cuda:0", n_seg=1, my_seg=0, dense_mode=0, row_pad=1, adam_rows=None, lazy=None,
-                 optimizer="adam", loss="binary_crossentropy", activation="sigmoid"):
+                 optimizer="adam", loss="binary_crossentropy", activation="sigmoid", metrics=0):
         """dense_mode: 0 one GPU; 1 user-sharded DP (anime gradient through ``dense_grad``); 2 replicated
         tables (every gradient through ``dense_grad``).  row_pad: the tables and the dense buffer are
         allocated with their row count rounded up to a multiple of it (equal reduce-scatter / all-gather
@@ -51,10 +51,18 @@ class TrainEngine:
         case).  The lazy update is Adam's alone: the other kinds always take the dense update (``lazy=True`` with them
         is a ValueError; ANIREC_LAZY_ADAM does not concern them).
         loss, activation: the output head (``schedule.LOSSES`` / ``schedule.ACTIVATIONS``, Keras names, any case); the
-        default is the reference's sigmoid + binary_crossentropy."""
+        default is the reference's sigmoid + binary_crossentropy.
+        metrics: ANIREC_METRIC_* bits (``schedule.metric_mask``) of the Keras metrics the train step and the validation
+        pass accumulate on the GPU beside the squared error (``epoch_logs`` / ``eval_logs``); 0 = none, the step as
+        without them."""
         self.optimizer = schedule.resolve_optimizer(optimizer)
         self.loss = schedule.resolve_loss(loss)
         self.activation = schedule.resolve_activation(activation)
+        self.metrics = int(metrics)
+        if self.metrics & ~0x7F:
+            raise ValueError("metrics: unknown ANIREC_METRIC_* bits in %#x" % self.metrics)
+        if self.metrics & _lib.METRIC_AUC and self.activation != "sigmoid":
+            raise ValueError("the AUC metric needs the sigmoid output activation (got %r)" % self.activation)
         if self.optimizer != "adam" and lazy:
             raise ValueError("the lazy update exists for Adam only (optimizer %r)" % optimizer)
         self.lib = _lib.load()
@@ -84,6 +92,10 @@ class TrainEngine:
         if ws == 0:
             raise _lib.AnirecError("anirec_train_workspace_bytes rejected the geometry")
         self.workspace = _dev_bytes(ws, dev)
+        # anirec_metric_acc of the train steps and of the validation pass
+        nacc = _lib.METRIC_ACC_DTYPE.itemsize
+        self.metric_acc = _dev_bytes(nacc, dev) if self.metrics else None
+        self.val_metric_acc = _dev_bytes(nacc, dev) if self.metrics else None
         # dense gradient buffer of the multi-GPU modes: [dense_rows][128] gradients, then [dense_rows] self sums
         carried = {0: 0, 1: self.n_anime_rows, 2: self.rows}[self.dense_mode]
         self.dense_rows = (carried + row_pad - 1) // row_pad * row_pad
@@ -265,6 +277,17 @@ class TrainEngine:
                   "reg_user_wsum", "reg_anime_wsum"):
             rec[k] = 0.0
         self.write_state(rec)
+        if self.metric_acc is not None:
+            self.metric_acc.zero_()
+            torch.cuda.synchronize(self.device)
+
+    def read_metric_acc(self, which="train"):
+        """The raw anirec_metric_acc of the train steps (``which="train"``) or of the last validation pass ("val")."""
+        self.stream.synchronize()
+        buf = self.metric_acc if which == "train" else self.val_metric_acc
+        if buf is None:
+            return np.zeros((), dtype=_lib.METRIC_ACC_DTYPE)
+        return np.frombuffer(buf.cpu().numpy().tobytes(), dtype=_lib.METRIC_ACC_DTYPE)[0].copy()
 
     # ---- stages (unit-testable) -----------------------------------------------------
     def prep(self, first_step, n_steps):
@@ -312,6 +335,9 @@ class TrainEngine:
             _lib.check(self.lib.anirec_dist_stepper_create(C.byref(self.desc), C.byref(h)),
                        "anirec_dist_stepper_create")
             self._stepper = h
+            if self.metrics:
+                _lib.check(self.lib.anirec_dist_stepper_set_metrics(h, self.metrics, _lib.ptr(self.metric_acc)),
+                           "anirec_dist_stepper_set_metrics")
         return self._stepper
 
     def stepper_begin(self, first_step, n_steps):
@@ -346,6 +372,9 @@ class TrainEngine:
             h = C.c_void_p()
             _lib.check(self.lib.anirec_trainer_create(C.byref(self.desc), C.byref(h)), "anirec_trainer_create")
             self._trainer = h
+            if self.metrics:
+                _lib.check(self.lib.anirec_trainer_set_metrics(h, self.metrics, _lib.ptr(self.metric_acc)),
+                           "anirec_trainer_set_metrics")
         _lib.check(self.lib.anirec_trainer_run(self._trainer, int(first_step), int(n_steps), int(use_graph),
                                                self._sp()), "anirec_trainer_run")
         return n_steps
@@ -361,8 +390,15 @@ class TrainEngine:
         rec["val_bce_sum"] = rec["val_se_sum"] = rec["val_n"] = 0.0
         self.write_state(rec)
         self.init_reg()  # reg sums of the CURRENT weights
-        _lib.check(self.lib.anirec_eval(C.byref(self.desc), _lib.ptr(u), _lib.ptr(a), _lib.ptr(t),
-                                        int(u.numel()), self._sp()), "anirec_eval")
+        if self.metrics:
+            self.val_metric_acc.zero_()
+            torch.cuda.synchronize(self.device)
+            _lib.check(self.lib.anirec_eval_metrics(C.byref(self.desc), self.metrics, _lib.ptr(self.val_metric_acc),
+                                                    _lib.ptr(u), _lib.ptr(a), _lib.ptr(t), int(u.numel()),
+                                                    self._sp()), "anirec_eval_metrics")
+        else:
+            _lib.check(self.lib.anirec_eval(C.byref(self.desc), _lib.ptr(u), _lib.ptr(a), _lib.ptr(t),
+                                            int(u.numel()), self._sp()), "anirec_eval")
         rec = self.read_state()
         return {k: float(rec[k]) for k in ("val_bce_sum", "val_se_sum", "val_n", "reg_user_sumsq",
                                            "reg_anime_sumsq", "reg_sumsq")}
@@ -379,6 +415,25 @@ class TrainEngine:
         rec = self.read_state()
         n = max(float(rec["n_seen"]), 1.0)
         return float(rec["loss_wsum"] / n), float(rec["se_sum"] / n)
+
+    def epoch_logs(self):
+        """{kind: value} of the epoch so far (``schedule.metric_values``: "loss", "mse", "rmse" and the kinds of
+        ``metrics``), sample-weighted means as Keras' History."""
+        loss, _ = self.epoch_metrics()
+        rec, acc = self.read_state(), self.read_metric_acc("train")
+        out = schedule.metric_values(self.metrics, acc["sum"], acc["auc_pos"], acc["auc_neg"], rec["n_seen"],
+                                     rec["se_sum"])
+        out["loss"] = loss
+        return out
+
+    def eval_logs(self, user_idx, anime_idx, rating):
+        """Validation pass; {kind: value} as ``epoch_logs`` ("loss" is ``evaluate``'s val_loss)."""
+        val_loss, _ = self.evaluate(user_idx, anime_idx, rating)
+        rec, acc = self.read_state(), self.read_metric_acc("val")
+        out = schedule.metric_values(self.metrics, acc["sum"], acc["auc_pos"], acc["auc_neg"], rec["val_n"],
+                                     rec["val_se_sum"])
+        out["loss"] = val_loss
+        return out
 
     def synchronize(self):
         self.stream.synchronize()

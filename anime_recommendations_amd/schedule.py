@@ -110,3 +110,83 @@ def step_rates(kind, lr, t_first, n):
     if kind == "adam":
         return adam_alphas(lr, t_first, n)
     return np.full(int(n), np.float32(lr), dtype=np.float32)
+
+
+# Keras metrics of model.compile(metrics=...) (neural_network.py:102-104) the GPU accumulates: name (lower case) ->
+# (kind, History key or None = the name as written).  Function metrics keep the string as written, metric classes take
+# their default snake-case name (Keras 2.12 compile_utils).  MSE and RMSE come from the squared-error sums every step
+# keeps already; every other kind has its ANIREC_METRIC_* bit (METRIC_BITS).
+_METRIC_NAMES = {
+    "mse": ("mse", None), "mean_squared_error": ("mse", None),
+    "mae": ("mae", None), "mean_absolute_error": ("mae", None),
+    "mape": ("mape", None), "mean_absolute_percentage_error": ("mape", None),
+    "msle": ("msle", None), "mean_squared_logarithmic_error": ("msle", None),
+    "logcosh": ("logcosh", None), "log_cosh": ("logcosh", None),
+    "binary_crossentropy": ("bce", None), "crossentropy": ("bce", None), "ce": ("bce", None), "bce": ("bce", None),
+    "accuracy": ("accuracy", None), "acc": ("accuracy", None), "binary_accuracy": ("accuracy", None),
+    "rootmeansquarederror": ("rmse", "root_mean_squared_error"),
+    "auc": ("auc", "auc"),
+}
+METRIC_BITS = {"mse": 0, "rmse": 0, "mae": 1, "mape": 2, "msle": 4, "logcosh": 8, "bce": 16, "accuracy": 32, "auc": 64}
+# the order of anirec_metric_acc.sum
+METRIC_SUM_KINDS = ("mae", "mape", "msle", "logcosh", "bce", "accuracy")
+
+
+def resolve_metrics(metrics, activation="sigmoid"):
+    """The metric set of ``ast.literal_eval(--model_metrics)``: a list or tuple of Keras metric names (any case; the
+    aliases and classes the kernels implement, ``_METRIC_NAMES``).  Returns the ordered [(History key, kind)];
+    ValueError, listing the supported names, for an unknown entry, a kind named twice, a bare string, or AUC with an
+    output activation other than sigmoid (Keras' AUC asserts predictions in [0, 1])."""
+    supported = "supported: %s, AUC, RootMeanSquaredError" % ", ".join(
+        sorted(k for k, (_, key) in _METRIC_NAMES.items() if key is None))
+    if isinstance(metrics, (str, bytes)) or not isinstance(metrics, (list, tuple)):
+        raise ValueError("model metrics must be a list of metric names, got %r (%s)" % (metrics, supported))
+    act = resolve_activation(activation)
+    out, seen = [], set()
+    for m in metrics:
+        if not isinstance(m, str) or m.lower() not in _METRIC_NAMES:
+            raise ValueError("metric %r is not supported by the HIP train step (%s)" % (m, supported))
+        kind, key = _METRIC_NAMES[m.lower()]
+        if kind in seen:
+            raise ValueError("metric %r names a metric already in the list %r" % (m, list(metrics)))
+        if kind == "auc" and act != "sigmoid":
+            raise ValueError("metric %r needs predictions in [0, 1]: the sigmoid output activation (got %r)"
+                             % (m, activation))
+        seen.add(kind)
+        out.append((key or m, kind))
+    return out
+
+
+def metric_mask(resolved):
+    """ANIREC_METRIC_* bits of a resolved metric set (0: nothing beyond the squared error every step keeps)."""
+    mask = 0
+    for _, kind in resolved:
+        mask |= METRIC_BITS[kind]
+    return mask
+
+
+def auc_from_bins(pos, neg):
+    """Keras 2.12 AUC() (ROC, 'interpolation' = trapezoidal sum) of the bucketed label masses, in fp64: TP / FP at
+    threshold i are the masses of buckets >= i (reverse cumulative sums), TPR = TP / P, FPR = FP / N (0 when P or N is
+    0: divide_no_nan)."""
+    pos = np.asarray(pos, np.float64)
+    neg = np.asarray(neg, np.float64)
+    tp = np.cumsum(pos[::-1])[::-1]
+    fp = np.cumsum(neg[::-1])[::-1]
+    P, N = tp[0], fp[0]
+    tpr = tp / P if P > 0 else np.zeros_like(tp)
+    fpr = fp / N if N > 0 else np.zeros_like(fp)
+    return float(np.sum((fpr[:-1] - fpr[1:]) * (tpr[:-1] + tpr[1:]) / 2.0))
+
+
+def metric_values(mask, sums, auc_pos, auc_neg, n, se_sum):
+    """{kind: epoch value} of the accumulated sums: the sample-weighted means over n ratings, MSE and RMSE from the
+    squared-error sum, AUC from the bins."""
+    n = max(float(n), 1.0)
+    out = {"mse": float(se_sum) / n, "rmse": float(np.sqrt(float(se_sum) / n))}
+    for k, kind in enumerate(METRIC_SUM_KINDS):
+        if mask & METRIC_BITS[kind]:
+            out[kind] = float(sums[k]) / n
+    if mask & METRIC_BITS["auc"]:
+        out["auc"] = auc_from_bins(auc_pos, auc_neg)
+    return out

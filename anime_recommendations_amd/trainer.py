@@ -1,7 +1,7 @@
 """Host mirror of the reference's training driver (neural_network/neural_network.py:141-233):
-``model.fit`` with LearningRateScheduler(lrfn), ModelCheckpoint(save_best_only on val_loss) and
+``model.fit`` with LearningRateScheduler(lrfn), ModelCheckpoint(save_best_only on the monitored column) and
 EarlyStopping(patience=3, restore_best_weights=True), producing the Keras ``History`` columns
-``loss, mse, val_loss, val_mse, lr``.
+``loss, <metrics>, val_loss, val_<metrics>, lr`` (``loss, mse, val_loss, val_mse, lr`` with the default metrics).
 
 All arithmetic of a step runs in libanirec (HIP); this file only sequences epochs.
 """
@@ -42,6 +42,7 @@ class FitConfig:
     loss: str = "binary_crossentropy"        # config.yaml model.model_loss (schedule.LOSSES, any case / alias)
     activation: str = "sigmoid"              # config.yaml model.activation_function (schedule.ACTIVATIONS)
     kernel_initializer: str = "he_normal"    # config.yaml model.kernel_initializer (schedule.INITIALIZERS)
+    metrics: tuple = ("mse",)                # config.yaml model.model_metrics (schedule.resolve_metrics)
 
     def lr(self, epoch):
         return schedule.lrfn(epoch, self.start_lr, self.max_lr, self.min_lr, self.rampup_epochs,
@@ -128,13 +129,21 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
         raise ValueError("libanirec kernels are specialised for embedding_size 128 (config.yaml:63)")
     kind = schedule.resolve_optimizer(cfg.optimizer)
     loss_name, act_name = schedule.resolve_loss(cfg.loss), schedule.resolve_activation(cfg.activation)
+    metrics = schedule.resolve_metrics(cfg.metrics, act_name)
+    mask = schedule.metric_mask(metrics)
+    # the default set (mse alone) reads the two sums every step keeps: epoch_metrics / evaluate, as it always did
+    plain = [kind for _, kind in metrics] == ["mse"]
+    keys = ["loss"] + [k for k, _ in metrics]
+    keys = keys + ["val_" + k for k in keys] + ["lr"]
+    if cfg.monitor not in keys[:-1]:
+        raise ValueError("monitor %r names no History column (%s)" % (cfg.monitor, ", ".join(keys[:-1])))
     tr, te = table.split(cfg.test_size)
     n_train = tr.stop - tr.start
     if engine is None:
         from .engine import TrainEngine
         engine = TrainEngine(table.n_users, table.n_anime, max_batch=min(cfg.batch_size, n_train),
                              l2=cfg.l2_reg_factor, arena_steps=cfg.arena_steps, device=device, optimizer=kind,
-                             loss=loss_name, activation=act_name)
+                             loss=loss_name, activation=act_name, metrics=mask)
     elif getattr(engine, "optimizer", "adam") != kind:
         raise ValueError("the engine was built for optimizer %r, the config asks for %r"
                          % (getattr(engine, "optimizer", "adam"), kind))
@@ -142,6 +151,9 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
         have = getattr(engine, what, default)
         if have != want:
             raise ValueError("the engine was built for %s %r, the config asks for %r" % (what, have, want))
+    if getattr(engine, "metrics", 0) != mask:
+        raise ValueError("the engine accumulates metrics %#x, the config asks for %#x (%s)"
+                         % (getattr(engine, "metrics", 0), mask, ", ".join(k for k, _ in metrics)))
     dev = engine.device
     U0, A0, w0 = init_weights(table.n_users, table.n_anime, 128, cfg.seed, cfg.kernel_initializer)
     engine.set_head(w=w0)
@@ -161,7 +173,7 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     n_steps = len(starts)
     multi = hasattr(engine, "set_epoch_global")
     gen = torch.Generator(device=dev)
-    hist = {"loss": [], "mse": [], "val_loss": [], "val_mse": [], "lr": []}
+    hist = {k: [] for k in keys}
     best = np.inf if cfg.mode == "min" else -np.inf
     best_w = None
     best_epoch, stopped, wait = -1, -1, 0
@@ -188,14 +200,19 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
         engine.synchronize()
         loop_s.append(time.perf_counter() - t_loop)
         t_global += n_steps
-        loss, mse = engine.epoch_metrics()
-        val_loss, val_mse = engine.evaluate(vu, va, vt)
-        for k, v in (("loss", loss), ("mse", mse), ("val_loss", val_loss), ("val_mse", val_mse),
-                     ("lr", float(np.float32(lr)))):
+        if plain:
+            loss, mse = engine.epoch_metrics()
+            val_loss, val_mse = engine.evaluate(vu, va, vt)
+            logs, val_logs = {"loss": loss, "mse": mse}, {"loss": val_loss, "mse": val_mse}
+        else:
+            logs, val_logs = engine.epoch_logs(), engine.eval_logs(vu, va, vt)
+        row = [logs["loss"]] + [logs[kind] for _, kind in metrics]
+        row += [val_logs["loss"]] + [val_logs[kind] for _, kind in metrics] + [float(np.float32(lr))]
+        for k, v in zip(keys, row):
             hist[k].append(v)
         if cfg.verbose:
-            log("Epoch %d/%d - loss: %.4f - mse: %.4f - val_loss: %.4f - val_mse: %.4f - lr: %.4g"
-                % (epoch + 1, cfg.epochs, loss, mse, val_loss, val_mse, lr))
+            log("Epoch %d/%d - %s - lr: %.4g" % (epoch + 1, cfg.epochs,
+                                                 " - ".join("%s: %.4f" % (k, v) for k, v in zip(keys, row[:-1])), lr))
         cur = hist[cfg.monitor][-1]
         if _improved(cur, best, cfg.mode):                             # ModelCheckpoint / best_weights
             best, best_epoch, wait = cur, epoch, 0
@@ -228,6 +245,8 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
 
 
 def history_frame(history):
-    """pandas frame with the reference's History CSV layout (`,loss,mse,val_loss,val_mse,lr`)."""
+    """pandas frame with the reference's History CSV layout: `,loss,<metrics>,val_loss,val_<metrics>,lr`
+    (`,loss,mse,val_loss,val_mse,lr` with the default metrics), the columns in ``fit``'s order."""
     import pandas as pd
-    return pd.DataFrame({k: history[k] for k in ("loss", "mse", "val_loss", "val_mse", "lr")})
+    keys = [k for k in history if k != "lr"] + (["lr"] if "lr" in history else [])
+    return pd.DataFrame({k: history[k] for k in keys})

@@ -315,6 +315,45 @@ int anirec_trainer_run(anirec_trainer *t, int32_t first_step, int32_t n_steps, i
 int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32_t *anime_idx,
                 const float *rating, int32_t n, void *stream);
 
+/* Keras metrics of model.compile(metrics=...) (neural_network.py:102-104), accumulated on the GPU beside the train
+ * step and the validation pass.  Per rating, e = p - t, p = the head's output:
+ *   MAE      |e|                                     MAPE  100 |e| / max(|t|, 1e-7)
+ *   MSLE     (log(max(p, 1e-7) + 1) - log(max(t, 1e-7) + 1))^2
+ *   LOGCOSH  the LOSS_LOGCOSH term                   BCE   the LOSS_BCE term of the descriptor's activation
+ *   ACC      1 if t == (p > 0.5) else 0 (binary_accuracy)
+ *   AUC      Keras AUC() with its 200 evenly spaced thresholds: bucket max(ceil(p * 199) - 1, 0) (fp32 product)
+ *            receives the fixed-point label mass wt = rint(clamp(t, 0, 1) * 2^20) as positive and 2^20 - wt as
+ *            negative mass (integer sums: bitwise reproducible); the caller forms TP / FP as reverse cumulative sums
+ *            and the ROC area by the trapezoidal rule.  Sigmoid heads only (Keras asserts p in [0, 1]).
+ * MSE and RootMeanSquaredError come from state->se_sum / val_se_sum and need no bit.  Epoch values are the sums
+ * divided by state->n_seen (train) or val_n (validation). */
+enum {
+  ANIREC_METRIC_MAE = 1,
+  ANIREC_METRIC_MAPE = 2,
+  ANIREC_METRIC_MSLE = 4,
+  ANIREC_METRIC_LOGCOSH = 8,
+  ANIREC_METRIC_BCE = 16,
+  ANIREC_METRIC_ACC = 32,
+  ANIREC_METRIC_AUC = 64
+};
+#define ANIREC_METRIC_KINDS 6   /* the scalar kinds: bits 0..5, the order of anirec_metric_acc.sum */
+#define ANIREC_AUC_BINS 200     /* AUC thresholds */
+#define ANIREC_AUC_ONE (1u << 20) /* label mass of one rating in the AUC bins */
+typedef struct anirec_metric_acc { /* device-resident; zeroed by the caller at epoch / validation start */
+  double sum[ANIREC_METRIC_KINDS];  /* MAE, MAPE, MSLE, LOGCOSH, BCE, ACC: sums of the per-rating values */
+  uint64_t auc_pos[ANIREC_AUC_BINS], auc_neg[ANIREC_AUC_BINS]; /* label mass per bucket, units of 2^-20 */
+} anirec_metric_acc;
+/* The metric set of a handle's runs (anirec_trainer_run / anirec_dist_run and the stepper's step calls): every step
+ * adds the requested kinds of the whole (global) batch to *acc — on every rank, no collective needed.  Mask 0 or a
+ * NULL acc: no metrics, the step as without this call.  Bits outside ANIREC_METRIC_* or AUC with an activation other
+ * than ANIREC_ACT_SIGMOID: ANIREC_EINVAL, the handle unchanged.  Drops the handle's captured graph.  The stage calls
+ * (anirec_train_head, ...) never accumulate metrics. */
+int anirec_trainer_set_metrics(anirec_trainer *t, uint32_t mask, anirec_metric_acc *acc);
+int anirec_dist_stepper_set_metrics(anirec_dist_stepper *h, uint32_t mask, anirec_metric_acc *acc);
+/* anirec_eval that also adds the requested kinds of the n validation rows to *acc (same checks as above). */
+int anirec_eval_metrics(const anirec_train_desc *d, uint32_t mask, anirec_metric_acc *acc, const int32_t *user_idx,
+                        const int32_t *anime_idx, const float *rating, int32_t n, void *stream);
+
 /* Standalone fused Adam on a flat fp32 array with an explicit dense gradient
  * (Keras-2.12 Adam dense branch; bit-exact to the oracle given the same g). */
 int anirec_adam_flat(float *w, float *m, float *v, const float *g, size_t n, float alpha,
