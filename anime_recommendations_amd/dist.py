@@ -139,11 +139,22 @@ class DistTrainEngine:
         # ANIREC_DIST_LOOP=1: rehearse the N>1 loop on one rank; the replicated modes only exist as that loop
         loop = self.world > 1 or os.environ.get("ANIREC_DIST_LOOP") == "1" or self.mode != "sharded"
         self.loop = loop
+        self.optimizer = schedule.resolve_optimizer(optimizer)
         if self.mode == "sharded":
+            # a rank without users has no table shard to train: refused on every rank alike, before any collective
+            if self.n_users < self.world:
+                raise ValueError("the user-sharded mode needs at least one user per rank (%d users, %d ranks)"
+                                 % (self.n_users, self.world))
             self.n_local = local_user_rows(self.n_users, self.rank, self.world)
             max_batch = min(_lib.MAX_BATCH, batch_slack(self.batch_per_rank))
             # lazy: the lazy dense Adam — of the whole step on one rank without the loop, of this rank's user rows in
-            # the user-sharded loop (None: the engine decides from the shard size; ANIREC_LAZY_ADAM overrides)
+            # the user-sharded loop (None: automatic; ANIREC_LAZY_ADAM overrides).  In the loop every rank must take
+            # the same update path, so the choice is made here from rank 0's shard size, the largest and the same on
+            # every rank, not by each engine from its own shard, which can be one row short of the threshold.
+            if loop and lazy is None and self.optimizer == "adam":
+                env = os.environ.get("ANIREC_LAZY_ADAM")
+                big = local_user_rows(self.n_users, 0, self.world) >= 6 * max_batch
+                lazy = (env != "0") and (env == "1" or big)
             kw = dict(dense_mode=1 if loop else 0, lazy=lazy)
         else:
             self.n_local = self.n_users
@@ -154,7 +165,6 @@ class DistTrainEngine:
                 self.shard_rows = (rows + self.world - 1) // self.world
                 lo = min(rows, self.rank * self.shard_rows)
                 kw.update(row_pad=self.world, adam_rows=(lo, min(rows, lo + self.shard_rows)))
-        self.optimizer = schedule.resolve_optimizer(optimizer)
         if self.optimizer != "adam":   # (Adam is every engine's default: a factory need not know the keyword)
             kw["optimizer"] = self.optimizer
         self.loss, self.activation = schedule.resolve_loss(loss), schedule.resolve_activation(activation)

@@ -32,6 +32,14 @@ def _dev_bytes(n, device):
     return torch.zeros(int(n), dtype=torch.uint8, device=device)
 
 
+def _column(x, dtype, device):
+    """A contiguous device column for libanirec.  An empty tensor has no storage (data_ptr() is 0), which the entry
+    points refuse as a missing column; a rank whose share of the epoch is empty gets one unused element instead (every
+    step's count is 0, so nothing reads it)."""
+    t = torch.as_tensor(x, device=device).to(dtype).contiguous()
+    return t if t.numel() else torch.zeros(1, dtype=dtype, device=device)
+
+
 class TrainEngine:
     def __init__(self, n_user_rows, n_anime_rows, max_batch, l2=1e-4, arena_steps=64,
                  device="cuda:0", n_seg=1, my_seg=0, dense_mode=0, row_pad=1, adam_rows=None, lazy=None,
@@ -251,9 +259,9 @@ class TrainEngine:
         """Install one epoch: shuffled ratings (device int32/int32/fp32) + its step schedule."""
         self.stream.synchronize()
         dev = self.device
-        self.user_idx = torch.as_tensor(user_idx, device=dev).to(torch.int32).contiguous()
-        self.anime_idx = torch.as_tensor(anime_idx, device=dev).to(torch.int32).contiguous()
-        self.rating = torch.as_tensor(rating, device=dev).to(torch.float32).contiguous()
+        self.user_idx = _column(user_idx, torch.int32, dev)
+        self.anime_idx = _column(anime_idx, torch.int32, dev)
+        self.rating = _column(rating, torch.float32, dev)
         counts = np.asarray(counts, np.int32)
         if counts.size and int(counts.max()) > self.max_batch:
             raise ValueError("a step holds %d ratings > max_batch %d" % (counts.max(), self.max_batch))
@@ -393,10 +401,13 @@ class TrainEngine:
         if self.metrics:
             self.val_metric_acc.zero_()
             torch.cuda.synchronize(self.device)
+        # no rows (a rank's empty share of a split validation set): the sums stay 0 and nothing is launched — the
+        # entry points refuse the empty tensors' null pointers before they look at the count
+        if u.numel() and self.metrics:
             _lib.check(self.lib.anirec_eval_metrics(C.byref(self.desc), self.metrics, _lib.ptr(self.val_metric_acc),
                                                     _lib.ptr(u), _lib.ptr(a), _lib.ptr(t), int(u.numel()),
                                                     self._sp()), "anirec_eval_metrics")
-        else:
+        elif u.numel():
             _lib.check(self.lib.anirec_eval(C.byref(self.desc), _lib.ptr(u), _lib.ptr(a), _lib.ptr(t),
                                             int(u.numel()), self._sp()), "anirec_eval")
         rec = self.read_state()

@@ -1,6 +1,7 @@
 """GPU tests of the multi-GPU path with the REAL HIP step halves.
   * two ranks share cuda:0 and talk over gloo, in each of the three data-parallel modes: the result must match the
-    oracle stepping on the global batches and the replicated tables must stay bit-identical across ranks;
+    oracle stepping on the global batches and the replicated tables must stay bit-identical across ranks (3 and 8
+    ranks on cuda:0: test_dist_ranks_gpu.py);
   * backend "nccl" (= RCCL), world size 1, ANIREC_DIST_LOOP=1: the N>1 loop — all_gather_into_tensor, all_reduce /
     reduce_scatter_tensor on the engine's stream, the forked user-row Adam — runs on hardware and must equal the
     single-engine run bit for bit;
@@ -77,7 +78,7 @@ def _worker(rank, world, port, out_dir, mode="sharded", backend="gloo", lazy=Non
         eng.set_head(w=1.2)
         eng.set_weights(U, A)
         tu, ta, tt, tp = (torch.from_numpy(np.asarray(x)).to(dev) for x in (ui, ai, t, perm))
-        n_steps = (len(perm) + 2 * bpr - 1) // (2 * bpr)
+        n_steps = (len(perm) + world * bpr - 1) // (world * bpr)
         eng.set_epoch_global(tu, ta, tt, tp, schedule.adam_alphas(3e-5, 1, n_steps))
         eng.reset_metrics()
         eng.run(n_steps)
@@ -110,12 +111,12 @@ def _port():
     return port
 
 
-def _check_against_oracle(tmp_path, problem="uniform"):
+def _check_against_oracle(tmp_path, problem="uniform", world=2):
     d = np.load(tmp_path / "dist.npz")
     make, bpr = _PROBLEMS[problem]
     U, A, ui, ai, t, perm = make()
     st = orc.new_state(U, A, orc.new_head(w=1.2))
-    lr, Bg = 3e-5, 2 * bpr
+    lr, Bg = 3e-5, world * bpr                   # the global batches: world ranks of bpr ratings
     losses, ns = [], []
     for k in range(0, len(perm), Bg):
         g = perm[k:k + Bg]
