@@ -200,7 +200,8 @@ def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None,
     ``cand_timing``: a dict that receives ``ms`` / ``launches`` of all MFMA candidate-kernel launches of this call
     (HIP events on their stream, every batch and re-run included; the job then runs on one chain and blocks per
     batch — bench.py only).  ``stats``: a dict that receives ``batches``, ``learn_batches``, ``lanes``, ``starts``,
-    ``rerun_rows`` (unproven under the prior, run again without) and ``fallback_rows``.
+    ``rerun_rows`` (unproven under the prior, run again without; ``rerun_at``: their positions in ``queries``, a device
+    tensor) and ``fallback_rows``.
     Returns (idx, score, n_fallback)."""
     _need_gpu()
     lib = _lib.load()
@@ -280,6 +281,7 @@ def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None,
         out_i[bad] = fi
         out_s[bad] = fs
         stats["rerun_rows"] = int(bad.numel())
+        stats["rerun_at"] = bad
     elif bad.numel():
         n_fb = int(bad.numel())
         if fallback:
@@ -341,7 +343,9 @@ def predict_grid(U, A, head, users):
 
 
 def predict_grid_mfma(U, A, head, users, out=None):
-    """predict_grid on the matrix cores (split-fp16 MFMA, ratings within 1e-5 of the fp32 path)."""
+    """predict_grid on the matrix cores (split-fp16 MFMA).  Ratings measured within 1e-5 of the fp32 path on the
+    suite's heads; the proven worst case is max act' x |hs| x 3.2e-5 plus roundings of the head and the activation
+    (include/anirec.h), looser than 1e-5 once |hs| max act' exceeds ~0.3."""
     _need_gpu()
     lib = _lib.load()
     dev = U.device

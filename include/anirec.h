@@ -500,7 +500,11 @@ int anirec_predict_grid_act(const float *U, const float *A, int32_t n_anime, con
                             void *workspace, size_t workspace_bytes, void *stream);
 
 /* The same grid on the matrix cores: rows are split x = hi + lo in fp16 and accumulated as
- * hi*hi + hi*lo + lo*hi by v_mfma_f32_32x32x16_f16 (ratings within 1e-5 of the fp32 path). */
+ * hi*hi + hi*lo + lo*hi by v_mfma_f32_32x32x16_f16.  Proven bound against exact arithmetic, for cosine c of the
+ * normalised rows and S = sum |u_k a_k| <= 1: |dc| <= 3.2e-5 S (split 3 x 2^-22, 384 accumulation and 134
+ * normalisation roundings of 2^-24 each), so |drating| <= max act' x (|hs| |dc| + 2^-23 (|c hs| + |hb| + |y|)) plus
+ * the activation's own error — looser than 1e-5 once |hs| max act' > ~0.3.  Measured: within 1e-5 of the fp32 path
+ * on the suite's heads, and within 2e-6 of fp64 on adversarial rows (tests/test_mfma_bounds_gpu.py). */
 size_t anirec_predict_mfma_workspace_bytes(int32_t n_anime, int32_t n_users);
 int anirec_predict_grid_mfma(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                              int32_t n_users, const anirec_head *head_host, float *out,
