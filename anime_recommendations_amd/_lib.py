@@ -138,6 +138,8 @@ PROTOTYPES = {
     "anirec_cosine_scores": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "anirec_topk_workspace_bytes": (_sz, [_i32, _i32]),
     "anirec_cosine_topk": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "anirec_topk_large_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "anirec_cosine_topk_large": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "anirec_cosine_topk_job_plan": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                               C.POINTER(C.c_int32)]),
     "anirec_cosine_topk_job_workspace_bytes": (_sz, [_i32, _i32, _i32]),
@@ -159,6 +161,9 @@ PROTOTYPES = {
     "anirec_predict_grid_mfma_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _sz, _vp]),
     "anirec_predict_topk_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
                                           _vp, _vp, _sz, _vp]),
+    "anirec_predict_topk_large_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "anirec_predict_topk_large_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
+                                                _vp, _vp, _sz, _vp]),
     "anirec_predict_topk_mfma_act": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
                                                _vp, _vp, _vp, _sz, _vp]),
     "anirec_predict_topk_mfma_workspace_bytes": (_sz, [_i32, _i32]),

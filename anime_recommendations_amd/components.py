@@ -107,17 +107,15 @@ def genre_mask(genres_col, wanted):
     return m
 
 
-def _topk_count(asked, what):
-    """The reference returns as many rows as asked for (Frame[:count]); the fused top-k kernels hold at
-    most MAX_TOPK rows per query, so a larger request is an error here, never a silent truncation."""
-    from ._lib import MAX_TOPK
+def _topk_count(asked, what, rows):
+    """The k of a component's top-k call.  The reference returns as many rows as asked for (Frame[:count]),
+    which is at most the rows a query can return: `rows` (n_anime - 1 for similar_anime, n_users - 1 for
+    similar_users, n_anime for model_recs).  The count is clamped to it, so a huge request allocates no more
+    than a whole ranking; the top-k calls take any k (above MAX_TOPK the large-k kernels)."""
     k = int(asked)
     if k < 1:
         raise ValueError("%s must be >= 1 (got %d)" % (what, k))
-    if k > MAX_TOPK:
-        raise ValueError("%s = %d exceeds the %d rows the GPU top-k kernels return per query "
-                         "(ANIREC_MAX_TOPK)" % (what, k, MAX_TOPK))
-    return k
+    return max(1, min(k, int(rows)))
 
 
 def check_genres(wanted, anime_df):
@@ -206,7 +204,7 @@ def similar_anime_frame(A, anime_ids, anime_df, syn_df, name, count, types=None,
         check_genres(genres, anime_df)
         keep &= genre_mask(meta["Genres"], genres)
     Wh = ops.rownorm(torch.as_tensor(A))
-    k = _topk_count(count, "a_query_number")
+    k = _topk_count(count, "a_query_number", len(anime_ids) - 1)
     idx, sim = ops.cosine_topk(Wh, [q], k, exclude_self=True, keep=keep.astype(np.uint8))
     idx, sim = idx.cpu().numpy()[0], sim.cpu().numpy()[0]
     ok = idx >= 0
@@ -243,6 +241,30 @@ def fave_anime(df, anime_df, user_id, num_faves, tv_only):
     return str(f["name"].tolist()[: int(num_faves)])[1:-1]
 
 
+def fave_anime_many(df, anime_df, user_ids, num_faves, tv_only):
+    """fave_anime of every listed user from one pass over the rating frame (one isin filter and a groupby)
+    instead of a full-frame filter per user: the same strings, in the order of `user_ids`."""
+    ids = list(user_ids)
+    f = df[df.user_id.isin(ids)]
+    if len(f) == 0:
+        return ["" for _ in ids]
+    f = f[f.rating == f.groupby("user_id").rating.transform("max")].copy()
+    meta = anime_df.drop_duplicates("anime_id").set_index("anime_id")
+    f["name"] = meta["Name"].reindex(f.anime_id).to_numpy()
+    f["episodes"] = pd.to_numeric(meta["Episodes"].reindex(f.anime_id), errors="coerce").to_numpy(np.float32)
+    if "watched_episodes" in f.columns:
+        f["percent"] = f["watched_episodes"] / f["episodes"]
+        top = f.groupby("user_id").percent.transform("max")
+        has = f.percent.notna().groupby(f.user_id).transform("any")
+        f = f[~has | (f.percent == top)]
+    out = {}
+    for u, g in f.groupby("user_id", sort=False):
+        if tv_only:
+            g = g.sort_values(by="episodes", ascending=False)
+        out[u] = str(g["name"].tolist()[: int(num_faves)])[1:-1]
+    return [out.get(u, "") for u in ids]
+
+
 def similar_users_frame(U, user_ids, df, anime_df, user_id, n_users, num_faves, tv_only):
     """find_similar_users (similar_users.py:262-314): the n most similar users (query dropped),
     descending similarity, with each neighbour's favourite anime."""
@@ -252,13 +274,13 @@ def similar_users_frame(U, user_ids, df, anime_df, user_id, n_users, num_faves, 
     if len(pos) == 0:
         raise ValueError("user id %r has no embedding row" % (user_id,))
     Uh = ops.rownorm(torch.as_tensor(U))
-    k = _topk_count(n_users, "id_query_number")
+    k = _topk_count(n_users, "id_query_number", len(user_ids) - 1)
     idx, sim = ops.cosine_topk(Uh, [int(pos[0])], k, exclude_self=True)
     idx, sim = idx.cpu().numpy()[0], sim.cpu().numpy()[0]
     ok = idx >= 0
     ids = np.asarray(user_ids)[idx[ok]]
     frame = pd.DataFrame({"similar_users": ids, "similarity": sim[ok],
-                          "favorite_animes": [fave_anime(df, anime_df, u, num_faves, tv_only) for u in ids]})
+                          "favorite_animes": fave_anime_many(df, anime_df, ids, num_faves, tv_only)})
     fn = "User_" + str(user_id).translate({ord(c): None for c in string.whitespace}) + ".csv"
     return frame, fn
 
@@ -290,7 +312,7 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
     nz = np.nonzero(blocked)[0]
     np.bitwise_or.at(bits[0], nz >> 5, (np.uint32(1) << (nz & 31).astype(np.uint32)))
     tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
-    k = _topk_count(n_recs, "model_num_recs")
+    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
     idx, p = ops.predict_topk(tU, tA, head, [int(pos[0])], k, bits.view(np.int32))
     idx, p = idx.cpu().numpy()[0], p.cpu().numpy()[0]
     ok = idx >= 0

@@ -715,3 +715,578 @@ int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, con
 }
 
 }  // extern "C"
+
+// ====================================================================================
+// exact top-k for ANY k (anirec_cosine_topk_large, anirec_predict_topk_large_act)
+//
+// The same score rows (k_scores / k_scores_few through launch_scores) and the same keys (cand_key) as k_select,
+// so the result is k_select's for k <= ANIREC_MAX_TOPK.  Phases, all stream-ordered launches:
+//   select   the 4-pass MSB radix select of k_select -> threshold key T, `want` keys == T to take (first in index
+//            order), m = winners (k, or every candidate of a short row).  Few queries: the histograms of each pass
+//            are built per slice by one workgroup each (k_lk_hist) and summed by the next launch; many queries: one
+//            workgroup per query does all four passes (k_lk_select_row).
+//   collect  the m winners as (key << 32) | ~index, unique per query, into win[q][0..m).  Sliced: per-slice
+//            counts (k_lk_count), each slice's offset from the counts of the slices before it (k_lk_write).
+//   sort     descending on that 64-bit value = score descending, ties ascending index.  m <= kLkSortMax: one
+//            workgroup per query sorts in LDS and gathers; above: tiles of kLkTile sorted in LDS, then merge
+//            passes that place each entry by its rank in the partner run (k_lk_merge), the last one gathering.
+//   gather   out_idx[q][i] = index, out_score[q][i] = row[index] (bit for bit), -1 / NaN for i >= m.
+// ====================================================================================
+namespace anirec {
+
+constexpr int kLkSortMax = 20480;  // one-workgroup sort: 20480 x 8 B = the 160 KiB of LDS one workgroup may hold
+constexpr int kLkTile = 16384;     // tile of the multi-workgroup sort (128 KiB of LDS)
+constexpr size_t kLkHistBytes = (size_t)4 * kSelMaxBlocks * 256 * 4;  // [pass][query x slice][digit]
+constexpr size_t kLkCntBytes = (size_t)kSelMaxBlocks * 2 * 4;         // [query x slice][gt, eq]
+
+struct LkArgs {
+  SelectArgs s;             // scores [nq][ld], masks, k, nq (this batch), slices; s.src_idx == nullptr
+  unsigned long long *win;  // [nq][kcap] winners (key << 32) | ~index
+  unsigned long long *win2; // [nq][kcap] second buffer of the merge passes
+  size_t kcap;              // min(k, n): the most winners a query can have
+  uint4 *st;                // [4][nq] state after each select pass: prefix, want, m, short
+  uint32_t *hist;           // [4][nq * slices][256] digit histograms of the sliced select
+  uint32_t *cnt;            // [nq * slices][2] winners above / at the threshold per slice
+};
+
+// The digit of one radix pass from a 256-bin histogram in LDS: k_select's wave scan.  out[0], out[1] = the new
+// prefix and want, or 0xFFFFFFFF and 0 when fewer than `want` keys match (pass 0 only: fewer than k candidates);
+// out[2] = the keys matching the prefix.  Ends with a barrier.
+__device__ void lk_digit(const uint32_t *hist, uint32_t prefix, uint32_t want, int shift, uint32_t *out) {
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    uint32_t h4[4], run = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      h4[j] = hist[255 - (4 * tid + j)];
+      run += h4[j];
+    }
+    uint32_t inc = run;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(inc, o, 64);
+      if (tid >= o) inc += y;
+    }
+    const uint32_t before = inc - run;
+    const unsigned long long reach = __ballot(inc >= want);
+    if (tid == 63) out[2] = inc;
+    if (reach == 0ull) {
+      if (tid == 0) {
+        out[0] = 0xFFFFFFFFu;
+        out[1] = 0;
+      }
+    } else if (tid == __ffsll((long long)reach) - 1) {
+      uint32_t cum = before;
+      int j = 0;
+      for (; j < 3; ++j) {
+        if (cum + h4[j] >= want) break;
+        cum += h4[j];
+      }
+      out[0] = prefix | ((uint32_t)(255 - (4 * tid + j)) << shift);
+      out[1] = want - cum;
+    }
+  }
+  __syncthreads();
+}
+
+// hist[d] = candidates of [j_lo, j_hi) whose key matches `prefix` under `pmask` and has digit d at `shift`
+__device__ void lk_hist(const SelectArgs &a, const float *row, int q, int self, int j_lo, int j_hi, uint32_t prefix,
+                        uint32_t pmask, int shift, uint32_t *hist) {
+  const int tid = threadIdx.x;
+  hist[tid] = 0;
+  __syncthreads();
+  for (int j = j_lo + tid; j < j_hi; j += kSelThreads) {
+    const uint32_t key = cand_key(a, row, q, j, self);
+    if (key != 0u && (key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t lk_pmask(int pass) { return pass == 0 ? 0u : 0xFFFFFFFFu << (32 - 8 * pass); }
+
+// state (prefix, want, m, short) after pass p from the one after pass p - 1 and the digit scan of pass p
+__device__ uint4 lk_advance(uint4 prev, const uint32_t *sh) {
+  if (sh[0] == 0xFFFFFFFFu && sh[1] == 0) return make_uint4(0u, 0xFFFFFFFFu, sh[2], 1u);
+  return make_uint4(sh[0], sh[1], prev.z, 0u);
+}
+
+// Ordered collection of the winners of [j_lo, j_hi): k_select's loop, into a global row of `cap` entries.
+// n_out / eq_taken: winners / keys == T already taken by the slices before this one.
+__device__ void lk_collect(const SelectArgs &a, const float *row, int q, int self, int j_lo, int j_hi, uint32_t T,
+                           uint32_t need_eq, bool short_row, uint32_t n_out, uint32_t eq_taken,
+                           unsigned long long *w, uint32_t cap, uint32_t *wsum) {
+  const int tid = threadIdx.x;
+  constexpr int kPer = 16;
+  const int super = kSelThreads * kPer;
+  for (int base = j_lo; base < j_hi; base += super) {
+    uint32_t keys[kPer];
+    uint32_t c_gt = 0, c_eq = 0;
+    const int j0 = base + tid * kPer;
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) {
+      const int j = j0 + e;
+      keys[e] = j < j_hi ? cand_key(a, row, q, j, self) : 0u;
+      if (keys[e] != 0u) {
+        if (short_row || keys[e] > T) ++c_gt;
+        else if (keys[e] == T) ++c_eq;
+      }
+    }
+    if (__syncthreads_count((c_gt | c_eq) != 0) == 0) continue;
+    uint32_t tot_gt = 0, tot_eq = 0;
+    uint32_t o_gt, o_eq;
+    {
+      const int lane = tid & 63, wv = tid >> 6;
+      uint32_t inc = c_gt;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        uint32_t t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+      }
+      if (lane == 63) wsum[wv] = inc;
+      __syncthreads();
+      uint32_t b = 0;
+      for (int kk = 0; kk < kSelThreads / 64; ++kk) {
+        if (kk < wv) b += wsum[kk];
+        tot_gt += wsum[kk];
+      }
+      o_gt = b + inc - c_gt;
+      __syncthreads();
+      inc = c_eq;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        uint32_t t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+      }
+      if (lane == 63) wsum[wv] = inc;
+      __syncthreads();
+      b = 0;
+      for (int kk = 0; kk < kSelThreads / 64; ++kk) {
+        if (kk < wv) b += wsum[kk];
+        tot_eq += wsum[kk];
+      }
+      o_eq = b + inc - c_eq;
+      __syncthreads();
+    }
+    const uint32_t eq_room = need_eq == 0xFFFFFFFFu ? 0u : (need_eq - eq_taken);
+    const uint32_t eq_use = tot_eq < eq_room ? tot_eq : eq_room;
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) {
+      const uint32_t key = keys[e];
+      if (key == 0u) continue;
+      const int j = j0 + e;
+      if (short_row || key > T) {
+        const uint32_t slot = n_out + o_gt++;
+        if (slot < cap) w[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
+      } else if (key == T) {
+        const uint32_t r = o_eq++;
+        if (r < eq_use) {
+          const uint32_t slot = n_out + tot_gt + r;
+          if (slot < cap) w[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
+        }
+      }
+    }
+    n_out += tot_gt + eq_use;
+    eq_taken += eq_use;
+  }
+}
+
+// many queries: one workgroup per query runs the whole select and collects its winners
+__global__ __launch_bounds__(kSelThreads) void k_lk_select_row(LkArgs a) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t sh[3];
+  __shared__ uint32_t wsum[kSelThreads / 64];
+  const int q = blockIdx.x;
+  const SelectArgs &s = a.s;
+  const float *row = s.scores + (size_t)q * s.ld;
+  const int self = s.self ? s.self[q] : -1;
+  uint4 st = make_uint4(0u, (uint32_t)s.k, (uint32_t)s.k, 0u);
+  for (int pass = 0; pass < 4 && !st.w; ++pass) {
+    lk_hist(s, row, q, self, 0, s.n, st.x, lk_pmask(pass), 24 - 8 * pass, hist);
+    lk_digit(hist, st.x, st.y, 24 - 8 * pass, sh);
+    st = lk_advance(st, sh);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) a.st[3 * s.nq + q] = st;
+  lk_collect(s, row, q, self, 0, s.n, st.w ? 0u : st.x, st.w ? 0xFFFFFFFFu : st.y, st.w != 0, 0, 0,
+             a.win + (size_t)q * a.kcap, (uint32_t)a.kcap, wsum);
+}
+
+// Sliced select: the state after pass p - 1 of the workgroup's query, from the state after pass p - 2 and the slice
+// histograms of pass p - 1.  Every workgroup of the query computes the same; slice 0 stores it for later launches.
+__device__ uint4 lk_state(const LkArgs &a, int q, int slice, int pass, uint32_t *hist, uint32_t *sh) {
+  const SelectArgs &s = a.s;
+  const uint4 prev = pass >= 2 ? a.st[(size_t)(pass - 2) * s.nq + q] : make_uint4(0u, (uint32_t)s.k, (uint32_t)s.k, 0u);
+  uint4 st = prev;
+  if (!prev.w) {
+    const uint32_t *h = a.hist + ((size_t)(pass - 1) * s.nq + q) * s.slices * 256;
+    uint32_t sum = 0;
+    for (int b = 0; b < s.slices; ++b) sum += h[(size_t)b * 256 + threadIdx.x];
+    hist[threadIdx.x] = sum;
+    __syncthreads();
+    lk_digit(hist, prev.x, prev.y, 24 - 8 * (pass - 1), sh);
+    st = lk_advance(prev, sh);
+    __syncthreads();
+  }
+  if (slice == 0 && threadIdx.x == 0) a.st[(size_t)(pass - 1) * s.nq + q] = st;
+  return st;
+}
+
+template <int kPass>
+__global__ __launch_bounds__(kSelThreads) void k_lk_hist(LkArgs a) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t sh[3];
+  const SelectArgs &s = a.s;
+  const int q = blockIdx.x / s.slices, slice = blockIdx.x % s.slices;
+  const int j_lo = slice * s.slice_len, j_hi = min(s.n, j_lo + s.slice_len);
+  const float *row = s.scores + (size_t)q * s.ld;
+  const int self = s.self ? s.self[q] : -1;
+  uint4 st = make_uint4(0u, (uint32_t)s.k, (uint32_t)s.k, 0u);
+  if constexpr (kPass > 0) st = lk_state(a, q, slice, kPass, hist, sh);
+  if (st.w) return;  // short row: every candidate wins, nothing left to locate
+  lk_hist(s, row, q, self, j_lo, j_hi, st.x, lk_pmask(kPass), 24 - 8 * kPass, hist);
+  a.hist[((size_t)kPass * s.nq * s.slices + blockIdx.x) * 256 + threadIdx.x] = hist[threadIdx.x];
+}
+
+// final state (pass 3) and, per slice, the keys above the threshold and at it
+__global__ __launch_bounds__(kSelThreads) void k_lk_count(LkArgs a) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t sh[3];
+  __shared__ uint32_t tot[2];
+  const SelectArgs &s = a.s;
+  const int q = blockIdx.x / s.slices, slice = blockIdx.x % s.slices;
+  const int j_lo = slice * s.slice_len, j_hi = min(s.n, j_lo + s.slice_len);
+  const float *row = s.scores + (size_t)q * s.ld;
+  const int self = s.self ? s.self[q] : -1;
+  const uint4 st = lk_state(a, q, slice, 4, hist, sh);
+  const uint32_t T = st.w ? 0u : st.x;
+  if (threadIdx.x < 2) tot[threadIdx.x] = 0;
+  __syncthreads();
+  uint32_t c_gt = 0, c_eq = 0;
+  for (int j = j_lo + threadIdx.x; j < j_hi; j += kSelThreads) {
+    const uint32_t key = cand_key(s, row, q, j, self);
+    if (key == 0u) continue;
+    if (st.w || key > T) ++c_gt;
+    else if (key == T) ++c_eq;
+  }
+  if (c_gt) atomicAdd(&tot[0], c_gt);
+  if (c_eq) atomicAdd(&tot[1], c_eq);
+  __syncthreads();
+  if (threadIdx.x < 2) a.cnt[(size_t)blockIdx.x * 2 + threadIdx.x] = tot[threadIdx.x];
+}
+
+// each slice writes its winners after those of the slices before it
+__global__ __launch_bounds__(kSelThreads) void k_lk_write(LkArgs a) {
+  __shared__ uint32_t wsum[kSelThreads / 64];
+  const SelectArgs &s = a.s;
+  const int q = blockIdx.x / s.slices, slice = blockIdx.x % s.slices;
+  const int j_lo = slice * s.slice_len, j_hi = min(s.n, j_lo + s.slice_len);
+  const float *row = s.scores + (size_t)q * s.ld;
+  const int self = s.self ? s.self[q] : -1;
+  const uint4 st = a.st[(size_t)3 * s.nq + q];
+  const uint32_t need_eq = st.w ? 0xFFFFFFFFu : st.y;
+  uint32_t n_out = 0, eq_taken = 0;
+  for (int b = 0; b < slice; ++b) {
+    const uint32_t *c = a.cnt + ((size_t)q * s.slices + b) * 2;
+    const uint32_t room = need_eq == 0xFFFFFFFFu ? 0u : need_eq - eq_taken;
+    const uint32_t use = c[1] < room ? c[1] : room;
+    n_out += c[0] + use;
+    eq_taken += use;
+  }
+  lk_collect(s, row, q, self, j_lo, j_hi, st.w ? 0u : st.x, need_eq, st.w != 0, n_out, eq_taken,
+             a.win + (size_t)q * a.kcap, (uint32_t)a.kcap, wsum);
+}
+
+// out row q, position i: the winner v, or the -1 / NaN pad
+__device__ __forceinline__ void lk_out(const LkArgs &a, int q, size_t i, unsigned long long v, bool valid) {
+  const SelectArgs &s = a.s;
+  const size_t o = (size_t)q * s.k + i;
+  if (valid) {
+    const uint32_t j = ~(uint32_t)(v & 0xFFFFFFFFull);
+    s.out_idx[o] = (int32_t)j;
+    s.out_score[o] = s.scores[(size_t)q * s.ld + j];
+  } else {
+    s.out_idx[o] = -1;
+    s.out_score[o] = __uint_as_float(0x7FC00000u);
+  }
+}
+
+// Sort in LDS, descending, of the winners [t * tile, min(m, (t + 1) * tile)) of query blockIdx.x / tiles: a bitonic
+// network in its one-direction form (each merge starts by comparing mirrored pairs), so the entries past the count
+// are virtual zeros that no comparator moves and are skipped.  gather: tiles == 1 and tile == kcap, write the
+// output rows; else write the sorted tile back.
+__global__ __launch_bounds__(1024) void k_lk_sort(LkArgs a, int tiles, int tile, int gather) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long sw[];
+  const int q = blockIdx.x / tiles, t = blockIdx.x % tiles;
+  const uint32_t m = a.st[(size_t)3 * a.s.nq + q].z;
+  const uint32_t lo = (uint32_t)t * (uint32_t)tile;
+  const uint32_t cnt = m > lo ? min(m - lo, (uint32_t)tile) : 0u;
+  unsigned long long *w = a.win + (size_t)q * a.kcap + lo;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (uint32_t i = tid; i < cnt; i += nt) sw[i] = w[i];
+  __syncthreads();
+  uint32_t npad = 1;
+  while (npad < cnt) npad <<= 1;
+  for (uint32_t lg = 1; (1u << lg) <= npad; ++lg) {
+    const uint32_t size = 1u << lg, half = size >> 1;
+    for (uint32_t p = tid; p < npad / 2; p += nt) {
+      const uint32_t base = (p >> (lg - 1)) << lg, off = p & (half - 1);
+      const uint32_t x = base + off, y = base + size - 1 - off;
+      if (y < cnt) {
+        const unsigned long long u = sw[x], v = sw[y];
+        if (u < v) {
+          sw[x] = v;
+          sw[y] = u;
+        }
+      }
+    }
+    __syncthreads();
+    for (uint32_t stride = size >> 2; stride > 0; stride >>= 1) {
+      for (uint32_t p = tid; p < npad / 2; p += nt) {
+        const uint32_t x = 2 * p - (p & (stride - 1)), y = x + stride;
+        if (y < cnt) {
+          const unsigned long long u = sw[x], v = sw[y];
+          if (u < v) {
+            sw[x] = v;
+            sw[y] = u;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (gather) {
+    for (size_t i = tid; i < (size_t)a.s.k; i += nt) lk_out(a, q, i, i < cnt ? sw[i] : 0ull, i < cnt);
+  } else {
+    for (uint32_t i = tid; i < cnt; i += nt) w[i] = sw[i];
+  }
+}
+
+// One merge pass over sorted runs of length L: the entry at i of run r goes to the start of the pair of runs plus
+// its rank in its own run plus the entries of run r ^ 1 above it (binary search; the values are unique).  dst ==
+// nullptr: the last pass, which writes the output rows (and pads them to k).
+__global__ __launch_bounds__(256) void k_lk_merge(LkArgs a, const unsigned long long *src, unsigned long long *dst,
+                                                  uint32_t L) {
+  const int q = blockIdx.y;
+  const uint32_t m = a.st[(size_t)3 * a.s.nq + q].z;
+  const unsigned long long *r = src + (size_t)q * a.kcap;
+  const size_t lim = dst ? (size_t)m : (size_t)a.s.k;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < lim; i += (size_t)gridDim.x * 256) {
+    if (i >= m) {
+      lk_out(a, q, i, 0ull, false);
+      continue;
+    }
+    const uint32_t ii = (uint32_t)i;
+    const uint32_t rs = ii / L * L, ps = (ii / L ^ 1u) * L;
+    const uint32_t pe = ps < m ? min(ps + L, m) : ps;
+    const unsigned long long v = r[ii];
+    uint32_t lo = ps, hi = pe;  // first position of the partner run whose value is below v
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (r[mid] > v) lo = mid + 1;
+      else hi = mid;
+    }
+    const uint32_t o = (ii - rs) + (lo - ps) + min(rs, ps);
+    if (dst) dst[(size_t)q * a.kcap + o] = v;
+    else lk_out(a, q, o, v, true);
+  }
+}
+
+// select + collect + sort + gather for the a.s.nq score rows of one batch
+static int lk_run(LkArgs a, hipStream_t s) {
+  SelectArgs &sa = a.s;
+  sa.src_idx = nullptr;
+  int S = 1;
+  if (sa.nq < 1024 && sa.n >= 4096) {  // launch_select's slicing
+    S = sa.n / 2048;
+    if (S > 64) S = 64;
+    if (S > kSelMaxBlocks / sa.nq) S = kSelMaxBlocks / sa.nq;
+    if (S < 1) S = 1;
+  }
+  sa.slices = S;
+  sa.slice_len = (sa.n + S - 1) / S;
+  if (S == 1) {
+    hipLaunchKernelGGL(k_lk_select_row, dim3(sa.nq), dim3(kSelThreads), 0, s, a);
+  } else {
+    const dim3 g(sa.nq * S);
+    hipLaunchKernelGGL(k_lk_hist<0>, g, dim3(kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lk_hist<1>, g, dim3(kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lk_hist<2>, g, dim3(kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lk_hist<3>, g, dim3(kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lk_count, g, dim3(kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(k_lk_write, g, dim3(kSelThreads), 0, s, a);
+  }
+  ANIREC_HIP_CHECK(hipGetLastError());
+  ANIREC_HIP_CHECK(hipFuncSetAttribute((const void *)k_lk_sort, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       kLkSortMax * 8));
+  if (a.kcap <= (size_t)kLkSortMax) {
+    uint32_t npad = 1;
+    while (npad < a.kcap) npad <<= 1;
+    const int nt = npad / 2 < 64 ? 64 : (npad / 2 > 1024 ? 1024 : (int)(npad / 2));
+    hipLaunchKernelGGL(k_lk_sort, dim3(sa.nq), dim3(nt), a.kcap * 8, s, a, 1, (int)a.kcap, 1);
+    return (int)hipGetLastError();
+  }
+  const int tiles = (int)((a.kcap + kLkTile - 1) / kLkTile);
+  hipLaunchKernelGGL(k_lk_sort, dim3(sa.nq * tiles), dim3(1024), (size_t)kLkTile * 8, s, a, tiles, kLkTile, 0);
+  unsigned long long *src = a.win, *dst = a.win2;
+  for (size_t L = kLkTile; L < a.kcap; L *= 2) {
+    const bool last = 2 * L >= a.kcap;
+    const size_t lim = last ? (size_t)sa.k : a.kcap;
+    size_t bx = (lim + 255) / 256;
+    if (bx > 4096) bx = 4096;
+    hipLaunchKernelGGL(k_lk_merge, dim3((unsigned)bx, sa.nq), dim3(256), 0, s, a, src, last ? nullptr : dst,
+                       (uint32_t)L);
+    unsigned long long *t = src;
+    src = dst;
+    dst = t;
+  }
+  return (int)hipGetLastError();
+}
+
+// workspace of the large path after its fixed part: per query a state, the winners (two buffers when the
+// multi-workgroup sort merges) and a score row
+static size_t lk_kcap(int32_t n, int32_t k) { return (size_t)(k < n ? k : n); }
+static size_t lk_per_query(int32_t n, int32_t k) {
+  const size_t kc = lk_kcap(n, k);
+  return 4 * sizeof(uint4) + kc * 8 * (kc > (size_t)kLkSortMax ? 2 : 1) + (size_t)n * 4;
+}
+static size_t lk_batch_bytes(int32_t n, int32_t k, size_t qb) {
+  while (qb > 1 && qb * lk_per_query(n, k) > ((size_t)4 << 30)) qb >>= 1;
+  return kLkHistBytes + kLkCntBytes + qb * lk_per_query(n, k);
+}
+
+// carve a batch of qb queries out of `p` (256-aligned): hist | cnt | st | win (| win2) | score rows
+static float *lk_carve(LkArgs &la, char *p, int32_t n, int32_t k, size_t qb) {
+  la.hist = (uint32_t *)p;
+  la.cnt = (uint32_t *)(p + kLkHistBytes);
+  la.st = (uint4 *)(p + kLkHistBytes + kLkCntBytes);
+  la.kcap = lk_kcap(n, k);
+  la.win = (unsigned long long *)(la.st + 4 * qb);
+  la.win2 = la.kcap > (size_t)kLkSortMax ? la.win + qb * la.kcap : la.win;
+  return (float *)(la.win2 + qb * la.kcap);
+}
+
+}  // namespace anirec
+
+extern "C" {
+
+size_t anirec_topk_large_workspace_bytes(int32_t n, int32_t nq, int32_t k) {
+  if (n < 1 || nq < 1 || k < 1) return 0;
+  const size_t self_bytes = ((size_t)nq * 4 + 255) / 256 * 256;
+  return self_bytes + lk_batch_bytes(n, k, (size_t)nq < 1024 ? (size_t)nq : 1024);
+}
+
+int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *queries, int32_t nq, const uint8_t *keep,
+                             int32_t exclude_self, int32_t k, int32_t *out_idx, float *out_score, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+  if (!What || !queries || !out_idx || !out_score || !workspace) return ANIREC_EINVAL;
+  if (n < 1 || nq < 0 || k < 1) return ANIREC_EINVAL;
+  if (nq == 0) return ANIREC_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t self_bytes = ((size_t)nq * 4 + 255) / 256 * 256;
+  const size_t fixed = self_bytes + kLkHistBytes + kLkCntBytes;
+  const size_t pq = lk_per_query(n, k);
+  if (workspace_bytes < fixed + pq) return ANIREC_EWORKSPACE;
+  size_t qb = (workspace_bytes - fixed) / pq;
+  if (qb > (size_t)nq) qb = nq;
+  int32_t *self = (int32_t *)workspace;
+  LkArgs la;
+  float *buf = lk_carve(la, (char *)workspace + self_bytes, n, k, qb);
+  hipLaunchKernelGGL(k_fill_self, dim3((nq + 255) / 256), dim3(256), 0, s, queries, nq, self, exclude_self);
+  ANIREC_HIP_CHECK(hipGetLastError());
+  for (size_t q0 = 0; q0 < (size_t)nq; q0 += qb) {
+    const int cnt = (int)((size_t)nq - q0 < qb ? (size_t)nq - q0 : qb);
+    ScoreArgs a;
+    a.Q = What;
+    a.qrows = queries + q0;
+    a.nq = cnt;
+    a.W = What;
+    a.n = n;
+    a.out = buf;
+    a.ld = (size_t)n;
+    a.use_head = 0;
+    a.hs = a.hb = 0.f;
+    int e = launch_scores(a, s);
+    if (e) return e;
+    SelectArgs &sa = la.s;
+    sa.scores = buf;
+    sa.ld = (size_t)n;
+    sa.n = n;
+    sa.nq = cnt;
+    sa.k = k;
+    sa.self = self + q0;
+    sa.keep = keep;
+    sa.wbits = nullptr;
+    sa.wwords = 0;
+    sa.out_idx = out_idx + q0 * k;
+    sa.out_score = out_score + q0 * k;
+    e = lk_run(la, s);
+    if (e) return e;
+  }
+  return ANIREC_OK;
+}
+
+size_t anirec_predict_topk_large_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t k) {
+  if (n_anime < 1 || n_users < 1 || k < 1) return 0;
+  return norm_bytes(n_anime, n_users) + lk_batch_bytes(n_anime, k, (size_t)n_users < 4096 ? (size_t)n_users : 4096);
+}
+
+int anirec_predict_topk_large_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                                  int32_t n_users, const anirec_head *head, int32_t activation,
+                                  const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation)) return ANIREC_EINVAL;
+  if (n_anime < 1 || n_users < 0 || k < 1) return ANIREC_EINVAL;
+  if (n_users == 0) return ANIREC_OK;
+  const size_t fixed = norm_bytes(n_anime, n_users) + kLkHistBytes + kLkCntBytes;
+  const size_t pq = lk_per_query(n_anime, k);
+  if (workspace_bytes < fixed + pq) return ANIREC_EWORKSPACE;
+  size_t qb = (workspace_bytes - fixed) / pq;
+  if (qb > (size_t)n_users) qb = n_users;
+  hipStream_t s = (hipStream_t)stream;
+  float *Ah = (float *)workspace;
+  float *Uh = Ah + (size_t)n_anime * kDim;
+  LkArgs la;
+  float *buf = lk_carve(la, (char *)(Uh + (size_t)n_users * kDim), n_anime, k, qb);
+  int b1 = (n_anime + 7) / 8, b2 = (n_users + 7) / 8;
+  if (b1 > 4096) b1 = 4096;
+  if (b2 > 4096) b2 = 4096;
+  hipLaunchKernelGGL(k_rownorm<1>, dim3(b1), dim3(256), 0, s, A, nullptr, n_anime, Ah);
+  hipLaunchKernelGGL(k_rownorm<1>, dim3(b2), dim3(256), 0, s, U, users, n_users, Uh);
+  ANIREC_HIP_CHECK(hipGetLastError());
+  const int wwords = (n_anime + 31) / 32;
+  float hs, hb;
+  head_affine(head, &hs, &hb);
+  for (size_t q0 = 0; q0 < (size_t)n_users; q0 += qb) {
+    const int cnt = (int)((size_t)n_users - q0 < qb ? (size_t)n_users - q0 : qb);
+    ScoreArgs a;
+    a.Q = Uh + q0 * kDim;
+    a.qrows = nullptr;
+    a.nq = cnt;
+    a.W = Ah;
+    a.n = n_anime;
+    a.out = buf;
+    a.ld = (size_t)n_anime;
+    a.use_head = 1;
+    a.hs = hs;
+    a.hb = hb;
+    int e = launch_scores(a, s, activation);
+    if (e) return e;
+    SelectArgs &sa = la.s;
+    sa.scores = buf;
+    sa.ld = (size_t)n_anime;
+    sa.n = n_anime;
+    sa.nq = cnt;
+    sa.k = k;
+    sa.self = nullptr;
+    sa.keep = nullptr;
+    sa.wbits = watched ? watched + q0 * wwords : nullptr;
+    sa.wwords = wwords;
+    sa.out_idx = out_idx + q0 * k;
+    sa.out_score = out_p + q0 * k;
+    e = lk_run(la, s);
+    if (e) return e;
+  }
+  return ANIREC_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from ._lib import MAX_TOPK
+
 
 def shard_bounds(n, rank, world):
     """Contiguous, balanced [lo, hi) slice of n query rows for `rank`."""
@@ -29,9 +31,13 @@ def gather_rows(local, n_total, world, rank):
 
 def sharded_cosine_topk(What, k, exclude_self=True, keep=None, topk_fn=None):
     """All-pairs neighbours of every row of ``What`` (replicated on each rank): rank r scores the
-    queries of its slice against all keys; returns the gathered (idx [n,k], score [n,k])."""
+    queries of its slice against all keys; returns the gathered (idx [n,k], score [n,k]).  Without a
+    ``topk_fn``: the matrix cores for k <= MAX_TOPK - 1, the exact any-k kernels above."""
     if topk_fn is None:
-        from .ops import cosine_topk_mfma as topk_fn
+        if k > MAX_TOPK - 1:
+            from .ops import cosine_topk as topk_fn
+        else:
+            from .ops import cosine_topk_mfma as topk_fn
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     n = What.shape[0]
@@ -45,7 +51,10 @@ def sharded_cosine_topk(What, k, exclude_self=True, keep=None, topk_fn=None):
 def sharded_predict_topk(U, A, head, users, k, watched_bits=None, predict_fn=None):
     """Top-k unwatched anime for every listed user, users sharded across ranks."""
     if predict_fn is None:
-        from .ops import predict_topk_mfma as predict_fn     # matrix cores; exact kernels for flagged users
+        if k > MAX_TOPK - 1:
+            from .ops import predict_topk as predict_fn      # exact any-k kernels
+        else:
+            from .ops import predict_topk_mfma as predict_fn     # matrix cores; exact kernels for flagged users
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     users = torch.as_tensor(users, device=U.device)

@@ -59,16 +59,19 @@ def cosine_scores(What, q):
 
 
 def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
-    """Top-k rows by descending cosine for each query row index.
+    """Top-k rows by descending cosine for each query row index, any k >= 1.
 
     Returns (idx int32 [nq,k], score fp32 [nq,k]); padded with -1 / NaN.
-    Ties -> ascending row index; NaN scores rank last.
+    Ties -> ascending row index; NaN scores rank last.  k <= MAX_TOPK runs anirec_cosine_topk, a larger k
+    anirec_cosine_topk_large (same result for the first MAX_TOPK columns); `workspace` must suit the call taken.
     """
     _need_gpu()
     lib = _lib.load()
     assert What.is_cuda and What.dtype == torch.float32 and What.shape[1] == DIM
-    if not (1 <= k <= MAX_TOPK):
-        raise ValueError("k must be in 1..%d" % MAX_TOPK)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    large = k > MAX_TOPK
     dev = What.device
     n = What.shape[0]
     if not isinstance(queries, torch.Tensor) or not queries.is_cuda:
@@ -90,11 +93,12 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
         keep_t = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous()
         assert keep_t.numel() == n
     if workspace is None:
-        workspace = torch.empty(int(lib.anirec_topk_workspace_bytes(n, nq)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_cosine_topk(_lib.ptr(What), n, _lib.ptr(q), nq, _lib.ptr(keep_t),
-                                      int(bool(exclude_self)), int(k), _lib.ptr(out_i), _lib.ptr(out_s),
-                                      _lib.ptr(workspace), workspace.numel(), _stream()),
-               "anirec_cosine_topk")
+        nb = lib.anirec_topk_large_workspace_bytes(n, nq, k) if large else lib.anirec_topk_workspace_bytes(n, nq)
+        workspace = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+    fn, name = ((lib.anirec_cosine_topk_large, "anirec_cosine_topk_large") if large
+                else (lib.anirec_cosine_topk, "anirec_cosine_topk"))
+    _lib.check(fn(_lib.ptr(What), n, _lib.ptr(q), nq, _lib.ptr(keep_t), int(bool(exclude_self)), k, _lib.ptr(out_i),
+                  _lib.ptr(out_s), _lib.ptr(workspace), workspace.numel(), _stream()), name)
     return out_i, out_s
 
 
@@ -362,10 +366,15 @@ def predict_grid_mfma(U, A, head, users, out=None):
 
 
 def predict_topk(U, A, head, users, k, watched_bits=None):
-    """Top-k unwatched anime by predicted rating per user.  watched_bits: uint32/int32
-    [n_users, ceil(n_anime/32)] (bit set = watched) or None."""
+    """Top-k unwatched anime by predicted rating per user, any k >= 1 (k > MAX_TOPK runs
+    anirec_predict_topk_large_act).  watched_bits: uint32/int32 [n_users, ceil(n_anime/32)] (bit set = watched)
+    or None."""
     _need_gpu()
     lib = _lib.load()
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    large = k > MAX_TOPK
     dev = U.device
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())
@@ -377,11 +386,14 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
     if watched_bits is not None:
         wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
         assert wb.shape == (n_q, (n_a + 31) // 32)
-    ws = torch.empty(int(lib.anirec_predict_workspace_bytes(n_a, n_q, 1)), dtype=torch.uint8, device=dev)
+    nb = (lib.anirec_predict_topk_large_workspace_bytes(n_a, n_q, k) if large
+          else lib.anirec_predict_workspace_bytes(n_a, n_q, 1))
+    ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
     h = _head_struct(head)
-    _lib.check(lib.anirec_predict_topk_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
-                                           _head_act(head), _lib.ptr(wb), int(k), _lib.ptr(out_i), _lib.ptr(out_p),
-                                           _lib.ptr(ws), ws.numel(), _stream()), "anirec_predict_topk")
+    fn, name = ((lib.anirec_predict_topk_large_act, "anirec_predict_topk_large_act") if large
+                else (lib.anirec_predict_topk_act, "anirec_predict_topk"))
+    _lib.check(fn(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head), _lib.ptr(wb), k,
+                  _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(), _stream()), name)
     return out_i, out_p
 
 

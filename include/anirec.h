@@ -413,6 +413,16 @@ int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int
                        const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
                        float *out_score, void *workspace, size_t workspace_bytes, void *stream);
 
+/* anirec_cosine_topk for ANY k >= 1 (a whole ranking included): the same scores, candidates, order, ties and
+ * padding, and for k <= ANIREC_MAX_TOPK the same output.  The radix select finds the k-th key, the winners are
+ * collected per query and sorted in LDS (k <= 20480) or as LDS tiles plus merge passes (larger k).
+ * workspace: anirec_topk_large_workspace_bytes(n, nq, k) bytes (it grows with min(k, n)); less, down to one
+ * query's share, runs the queries in smaller batches. */
+size_t anirec_topk_large_workspace_bytes(int32_t n, int32_t nq, int32_t k);
+int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *queries, int32_t nq,
+                             const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                             float *out_score, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Same result as anirec_cosine_topk on the matrix cores: fp16 MFMA candidate scores for all
  * keys with a rigorous error window, exact fp32 fma-chain re-rank of the survivors.
  * The error window is proven for UNIT-NORM rows (the output of anirec_rownorm, as every reference call
@@ -525,6 +535,13 @@ int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, con
                             int32_t n_users, const anirec_head *head_host, int32_t activation,
                             const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
                             size_t workspace_bytes, void *stream);
+/* anirec_predict_topk_act for ANY k >= 1 (k >= n_anime: a user's whole ranking), as anirec_cosine_topk_large.
+ * workspace: anirec_predict_topk_large_workspace_bytes(n_anime, n_users, k) bytes. */
+size_t anirec_predict_topk_large_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t k);
+int anirec_predict_topk_large_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                                  int32_t n_users, const anirec_head *head_host, int32_t activation,
+                                  const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
