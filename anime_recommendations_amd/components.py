@@ -165,25 +165,45 @@ def metadata_by_index(anime_ids, anime_df, syn_df=None):
     out["has_meta"] = out["Name"].notna().to_numpy()
     out["anime_id"] = np.asarray(anime_ids)
     if syn_df is not None:
+        # "None" where the anime has no synopsis row (the reference's IndexError branch); an empty synopsis cell
+        # stays NaN, as get_sypnopsis returns it
         syn = syn_df.drop_duplicates("MAL_ID").set_index("MAL_ID")["sypnopsis"]
-        out["Sypnopsis"] = syn.reindex(anime_ids).fillna("None").to_numpy()
+        text = syn.reindex(anime_ids).to_numpy(dtype=object)
+        out["Sypnopsis"] = np.where(np.isin(np.asarray(anime_ids), syn.index.to_numpy()), text, "None")
     else:
         out["Sypnopsis"] = "None"
     return out.reset_index(drop=True)
+
+
+def filter_mask(meta, anime_df, types=None, genres=None):
+    """Rows of `meta` (metadata_by_index) a recommendation may list: the anime has an all_anime.csv row, and its Type
+    / Genres pass the optional filters (similar_anime.py:431-455, model_recs.py:429-448)."""
+    keep = meta["has_meta"].to_numpy().copy()
+    if types is not None:
+        keep &= meta["Type"].isin(check_types(types)).to_numpy()
+    if genres is not None:
+        check_genres(genres, anime_df)
+        keep &= genre_mask(meta["Genres"], genres)
+    return keep
+
+
+def unwatched_mask(df, anime_ids, user_id):
+    """get_unwatched (model_recs.py:132-156): indexed anime the user has not rated."""
+    watched_ids = set(df[df.user_id == int(user_id)].anime_id.values.tolist())
+    return ~np.isin(np.asarray(anime_ids), list(watched_ids))
 
 
 # ----------------------------------------------------------------------------------------
 # similar_anime
 # ----------------------------------------------------------------------------------------
 def find_anime_id(name, anime_df):
-    """Resolve a query title like anime_recs (similar_anime.py:389-399): exact Name, else the
-    cleaned name against the cleaned english names."""
-    hit = anime_df[anime_df.Name == name]
-    if len(hit) == 0:
-        hit = anime_df[anime_df.eng_version == clean(name)]
-    if len(hit) == 0:
-        raise ValueError("anime %r not found in the anime data frame" % (name,))
-    return int(hit.anime_id.values[0])
+    """Resolve a query title like anime_recs (similar_anime.py:389-399), in its order: a Name equal to the
+    cleaned query, else the exact Name, else the cleaned query against the cleaned english names."""
+    key = clean(name)
+    for hit in (anime_df[anime_df.Name == key], anime_df[anime_df.Name == name], anime_df[anime_df.eng_version == key]):
+        if len(hit):
+            return int(hit.anime_id.values[0])
+    raise ValueError("anime %r not found in the anime data frame" % (name,))
 
 
 def similar_anime_frame(A, anime_ids, anime_df, syn_df, name, count, types=None, genres=None):
@@ -197,12 +217,7 @@ def similar_anime_frame(A, anime_ids, anime_df, syn_df, name, count, types=None,
         raise ValueError("anime %r (id %d) has no embedding row" % (name, qid))
     q = int(pos[0])
     meta = metadata_by_index(anime_ids, anime_df, syn_df)
-    keep = meta["has_meta"].to_numpy().copy()
-    if types is not None:
-        keep &= meta["Type"].isin(check_types(types)).to_numpy()
-    if genres is not None:
-        check_genres(genres, anime_df)
-        keep &= genre_mask(meta["Genres"], genres)
+    keep = filter_mask(meta, anime_df, types, genres)
     Wh = ops.rownorm(torch.as_tensor(A))
     k = _topk_count(count, "a_query_number", len(anime_ids) - 1)
     idx, sim = ops.cosine_topk(Wh, [q], k, exclude_self=True, keep=keep.astype(np.uint8))
@@ -298,14 +313,7 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
     if len(pos) == 0:
         raise ValueError("user id %r has no embedding row" % (user_id,))
     meta = metadata_by_index(anime_ids, anime_df, syn_df)
-    watched_ids = set(df[df.user_id == int(user_id)].anime_id.values.tolist())
-    unwatched = ~np.isin(np.asarray(anime_ids), list(watched_ids))       # get_unwatched :132-156
-    keep = unwatched & meta["has_meta"].to_numpy()
-    if types is not None:
-        keep &= meta["Type"].isin(check_types(types)).to_numpy()
-    if genres is not None:
-        check_genres(genres, anime_df)
-        keep &= genre_mask(meta["Genres"], genres)
+    keep = unwatched_mask(df, anime_ids, user_id) & filter_mask(meta, anime_df, types, genres)
     n_a = len(anime_ids)
     blocked = ~keep
     bits = np.zeros((1, (n_a + 31) // 32), np.uint32)

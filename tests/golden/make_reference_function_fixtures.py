@@ -22,10 +22,10 @@ Functions executed (reference file:line):
   model_recs/model_recs.py:132-156 get_unwatched, :159-192 get_user_anime_arr -> model_recs.json
   neural_network/neural_network.py:109-125 lrfn         -> lrfn.json
 
-Not isolable (documented in DESIGN.md §2): anything that calls wandb (every ``go``, ``get_df``,
-``main_df_by_*``, ``get_anime_df``, ``get_model``), Keras (``neural_network()``, ``model.fit``,
-``model.predict`` inside ``recommendations``), and ``anime_recs`` / ``similar_user_recs`` whose
-bodies call those loaders directly.
+Bodies that reach W&B or Keras do so only through module-level names, which ``load_functions(..., extra=...)``
+binds to stubs: make_user_component_fixtures.py runs ``similar_user_recs`` that way, make_recs_fixtures.py runs
+``get_df``, ``main_df_by_anime``, ``get_anime_df``, ``anime_recs`` and ``recommendations``.  What
+executes inside Keras itself (``neural_network()``, ``model.fit``) stays unpinned.
 """
 import ast
 import json

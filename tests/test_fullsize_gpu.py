@@ -256,3 +256,64 @@ def test_predict_topk_mfma_c5_sample_equals_exact_path():
     bit = (watched.gather(1, idx >> 5) >> (idx & 31)) & 1
     assert int(bit.sum()) == 0
     assert bool((mp[:, 1:] <= mp[:, :-1]).all())
+
+
+def _part_edges(n_users, n_anime, parts_env):
+    """Anime columns on both sides of every part boundary of k_predict_mfma2's grid (anirec_predict_mfma.hip:
+    kPM = 128 users per workgroup, kPN = 64 anime per tile, parts = ceil(4096 / user blocks) unless pinned, at most
+    one per 16 tiles)."""
+    ub, ntile = (n_users + 127) // 128, (n_anime + 63) // 64
+    parts = int(parts_env) if parts_env else (4096 + ub - 1) // ub
+    parts = max(1, min(parts, ntile // 16))
+    per = (ntile + parts - 1) // parts
+    cols = []
+    for p in range(1, (ntile + per - 1) // per):
+        cols += [p * per * 64 - 1, p * per * 64]
+    return cols
+
+
+@pytest.mark.parametrize("n_users,n_anime", [(100_000, 18_000), (131_072, 17_560)])
+def test_predict_grid_mfma_full_size_sample_equals_pairwise_kernel_and_fp64(n_users, n_anime, monkeypatch):
+    """The benchmark's 100 000 x 18 000 grid and 131 072 x 17 560 (2.30e9 outputs, past 2^31): a sample of entries —
+    first and last user rows, the rows either side of output element 2^31, the last anime columns and both sides of
+    every anime-part boundary — within 3e-6 of the fp32 pairwise kernel and 1e-5 of the fp64 oracle, and identical
+    whatever ANIREC_PREDICT_PARTS is."""
+    from anime_recommendations_amd import ops
+    g = torch.Generator(device="cuda")
+    g.manual_seed(n_users + n_anime)
+    U = torch.randn(n_users, 128, generator=g, device="cuda") * 0.05
+    A = torch.randn(n_anime, 128, generator=g, device="cuda") * 0.05
+    head = dict(w=1.3, b=0.1, gamma=0.9, beta=-0.2, mov_mean=0.05, mov_var=0.4)
+    users = torch.arange(n_users, dtype=torch.int32, device="cuda")
+    rng = np.random.default_rng(n_users)
+    edge = (1 << 31) // n_anime
+    rows = np.unique(np.r_[0, 1, 127, 128, n_users - 129, n_users - 128, n_users - 1, edge - 1, edge, edge + 1,
+                           rng.integers(0, n_users, 40)])
+    rows = rows[rows < n_users]
+    out = torch.empty(n_users, n_anime, dtype=torch.float32, device="cuda")
+    first = None
+    for parts in (None, "3", "7"):
+        if parts is None:
+            monkeypatch.delenv("ANIREC_PREDICT_PARTS", raising=False)
+        else:
+            monkeypatch.setenv("ANIREC_PREDICT_PARTS", parts)
+        out.fill_(-7.0)
+        ops.predict_grid_mfma(U, A, head, users, out=out)
+        cols = np.unique(np.r_[0, 1, 63, 64, n_anime - 65, n_anime - 64, n_anime - 2, n_anime - 1,
+                               _part_edges(n_users, n_anime, parts), rng.integers(0, n_anime, 64)])
+        ju, ja = np.repeat(rows, len(cols)), np.tile(cols, len(rows))
+        ju = np.r_[ju, rng.integers(0, n_users, 20000)]
+        ja = np.r_[ja, rng.integers(0, n_anime, 20000)]
+        tu, ta = torch.from_numpy(ju).cuda(), torch.from_numpy(ja).cuda()
+        got = out[tu, ta].cpu().numpy()
+        p32 = ops.predict_pairs(U, A, head, tu.to(torch.int32), ta.to(torch.int32)).cpu().numpy()
+        np.testing.assert_allclose(got, p32, atol=3e-6)
+        p64 = orc.predict_pairs(U.cpu().numpy(), A.cpu().numpy(), orc.new_head(**head), ju, ja, dtype=np.float64)
+        np.testing.assert_allclose(got, p64, atol=1e-5)
+        # no entry left unwritten: the last row and the last column in full
+        assert bool((out[-1] != -7.0).all()) and bool((out[:, -1] != -7.0).all())
+        if first is None:
+            first = (tu, ta, got)
+        assert np.array_equal(out[first[0], first[1]].cpu().numpy(), first[2]), parts
+    del out
+    torch.cuda.empty_cache()
