@@ -19,6 +19,14 @@ that executes inside Keras/TensorFlow — the forward graph, the train step
 (closed-form backward + Adam), validation metrics and ``model.predict`` —
 because nothing in the reference holds a vector for it.
 
+This module is the ONE definition of the step: the output heads
+(``--model_loss`` / ``--activation_function``: ``head_terms``) and the update
+rules (``--optimizer``: ``opt_update``) are arguments of ``forward`` / ``grads``
+/ ``train_step`` / ``evaluate`` / ``predict_pairs`` and of ``new_state``, with
+the reference's model (sigmoid, binary_crossentropy, Adam) as the default.
+Every product and sum is in the order ``anirec_dev.hpp`` writes it, rounded
+once in the working dtype; the tests hold the kernels to it.
+
 Each function cites the reference file:line it follows.  ``dtype`` selects the
 arithmetic type: ``np.float32`` is the parity oracle (what Keras computes in),
 ``np.float64`` is used to sanity-check the closed-form backward.
@@ -36,6 +44,12 @@ BN_MOMENTUM = 0.99   # BatchNormalization() default momentum                    
 ADAM_B1 = 0.9        # optimizer='Adam' defaults                                 neural_network.py:104
 ADAM_B2 = 0.999
 ADAM_EPS = 1e-7
+EPS = np.float32(1e-7)               # keras.backend.epsilon(): the clip of a BCE on probabilities
+ONE_M_EPS = np.float32(1) - EPS
+LOSSES = ("binary_crossentropy", "mean_squared_error", "mean_absolute_error", "huber", "log_cosh")
+ACTIVATIONS = ("sigmoid", "linear", "tanh", "relu", "softplus")
+KINDS = ("sgd", "rmsprop", "adagrad")                 # the one-slot update rules beside Adam
+SLOT_INIT = {"adam": 0.0, "sgd": 0.0, "rmsprop": 0.0, "adagrad": 0.1}   # initial_accumulator_value of Adagrad
 
 
 # ---------------------------------------------------------------------------
@@ -104,8 +118,8 @@ def _inv_norm(ss, dt):
     return dt(1) / np.sqrt(np.maximum(ss, dt(L2N_EPS)), dtype=dt)
 
 
-def forward(U, A, ui, ai, head, training, dtype=np.float32):
-    """Embedding x2 -> Dot(normalize=True) -> Dense(1) -> BatchNorm -> sigmoid.
+def forward(U, A, ui, ai, head, training, dtype=np.float32, activation="sigmoid"):
+    """Embedding x2 -> Dot(normalize=True) -> Dense(1) -> BatchNorm -> Activation.
 
     head: dict with w, b, gamma, beta, mov_mean, mov_var (scalars).
     Returns dict of every intermediate (all ``dtype``).
@@ -131,7 +145,7 @@ def forward(U, A, ui, ai, head, training, dtype=np.float32):
     r = dt(1) / np.sqrt(var + dt(BN_EPS), dtype=dt)            # rsqrt(var + eps)
     inv = r * gamma                                            # tf.nn.batch_normalization
     y = z * inv + (beta - mu * inv)
-    p = _sigmoid(y, dt)                                        # Activation('sigmoid')
+    p = act_fwd(activation, y, dt)                             # Activation(activation_function)
     return dict(u=u, a=a, su=su, sa=sa, ru=ru, ra=ra, uh=uh, ah=ah, c=c, z=z,
                 mu=mu, var=var, r=r, y=y, p=p)
 
@@ -153,6 +167,80 @@ def bce_from_logits(y, t, dt=np.float32):
     return np.maximum(y, dt(0)) - y * t + np.log1p(np.exp(-np.abs(y), dtype=dt), dtype=dt)
 
 
+# The output heads (--activation_function / --model_loss; include/anirec.h, ANIREC_ACT_* / ANIREC_LOSS_*): Keras 2.12's
+# published activations and losses and TensorFlow's gradient ops, per rating.
+def softplus(x, dt=np.float32):
+    x = np.asarray(x, dt)
+    return (np.maximum(x, dt(0)) + np.log1p(np.exp(-np.abs(x), dtype=dt), dtype=dt)).astype(dt)
+
+
+def act_fwd(act, y, dt=np.float32):
+    y = np.asarray(y, dt)
+    if act == "sigmoid":
+        return _sigmoid(y, dt)
+    if act == "linear":
+        return y.copy()
+    if act == "tanh":
+        return np.tanh(y, dtype=dt)
+    if act == "relu":
+        return np.maximum(y, dt(0)).astype(dt)
+    if act == "softplus":
+        return softplus(y, dt)
+    raise ValueError(act)
+
+
+def act_grad(act, y, p, dt=np.float32):
+    if act == "sigmoid":
+        return (p * (dt(1) - p)).astype(dt)
+    if act == "linear":
+        return np.ones_like(y, dt)
+    if act == "tanh":
+        return (dt(1) - p * p).astype(dt)
+    if act == "relu":
+        return np.where(y > 0, dt(1), dt(0)).astype(dt)
+    if act == "softplus":
+        return _sigmoid(y, dt)
+    raise ValueError(act)
+
+
+def loss_terms(loss, p, t, dt=np.float32):
+    """(l(p, t), dl/dp) per rating"""
+    p, t = np.asarray(p, dt), np.asarray(t, dt)
+    e = (p - t).astype(dt)
+    if loss == "binary_crossentropy":
+        eps, ome = dt(EPS), dt(ONE_M_EPS)
+        q = np.minimum(np.maximum(p, eps), ome).astype(dt)
+        a = (q + eps).astype(dt)
+        b = ((dt(1) - q) + eps).astype(dt)
+        l = -(t * np.log(a, dtype=dt) + (dt(1) - t) * np.log(b, dtype=dt))
+        g = np.where((p >= eps) & (p <= ome), -(t / a) + (dt(1) - t) / b, dt(0))
+    elif loss == "mean_squared_error":
+        l, g = e * e, dt(2) * e
+    elif loss == "mean_absolute_error":
+        l, g = np.abs(e), np.sign(e)
+    elif loss == "huber":
+        ae = np.abs(e)
+        l = np.where(ae <= 1, dt(0.5) * (e * e), ae - dt(0.5))
+        g = np.where(ae <= 1, e, np.sign(e))
+    elif loss == "log_cosh":
+        l = (e + softplus(dt(-2) * e, dt)) - dt(np.log(2.0))
+        g = dt(1) - dt(2) * _sigmoid(dt(-2) * e, dt)
+    else:
+        raise ValueError(loss)
+    return np.asarray(l, dt), np.asarray(g, dt)
+
+
+def head_terms(loss, act, y, t, dt=np.float32):
+    """p = act(y), the data loss l and dl/dy of every rating (the 1/B of the batch mean not applied)"""
+    y, t = np.asarray(y, dt), np.asarray(t, dt)
+    if loss == "binary_crossentropy" and act == "sigmoid":      # from logits, as the reference's model always was
+        p = _sigmoid(y, dt)
+        return p, bce_from_logits(y, t, dt), (p - t).astype(dt)
+    p = act_fwd(act, y, dt)
+    l, gp = loss_terms(loss, p, t, dt)
+    return p, l, (gp * act_grad(act, y, p, dt)).astype(dt)
+
+
 def reg_sumsq(U, A, dtype=np.float32):
     """sum(U^2) + sum(A^2): the embeddings_regularizer L2 term without lambda
     (neural_network.py:73,78,85)."""
@@ -161,7 +249,7 @@ def reg_sumsq(U, A, dtype=np.float32):
 
 
 # ---------------------------------------------------------------------------
-# a3: one training step (forward, loss, closed-form backward, dense Adam)
+# a3: one training step (forward, loss, closed-form backward, dense update)
 #                                                              neural_network.py:210-217
 # ---------------------------------------------------------------------------
 def new_head(w=1.0, b=0.0, gamma=1.0, beta=0.0, mov_mean=0.0, mov_var=1.0):
@@ -172,33 +260,40 @@ def new_head(w=1.0, b=0.0, gamma=1.0, beta=0.0, mov_mean=0.0, mov_var=1.0):
                 m=np.zeros(4, np.float32), v=np.zeros(4, np.float32))
 
 
-def new_state(U, A, head=None):
-    """Full trainable + optimizer state (tables, Adam slots, head, iteration count)."""
+def new_state(U, A, head=None, optimizer="adam"):
+    """Full trainable + optimizer state (tables, slots, head, iteration count).  The update rule is fixed here;
+    a one-slot rule keeps its slot (RMSprop velocity / Adagrad accumulator) where the engine keeps it: in
+    vU / vA / head["v"], with mU / mA / head["m"] never touched."""
+    head = head if head is not None else new_head()
+    if optimizer != "adam":
+        head["v"] = np.full(4, SLOT_INIT[optimizer], np.float32)
     return dict(U=U.copy(), A=A.copy(),
-                mU=np.zeros_like(U), vU=np.zeros_like(U),
-                mA=np.zeros_like(A), vA=np.zeros_like(A),
-                head=head if head is not None else new_head(), t=0)
+                mU=np.zeros_like(U), vU=np.full_like(U, SLOT_INIT[optimizer]),
+                mA=np.zeros_like(A), vA=np.full_like(A, SLOT_INIT[optimizer]),
+                head=head, t=0, optimizer=optimizer)
 
 
-def grads(U, A, ui, ai, t, head, l2=1e-4, dtype=np.float32):
+def grads(U, A, ui, ai, t, head, l2=1e-4, dtype=np.float32, loss="binary_crossentropy", activation="sigmoid"):
     """Loss and every gradient of one batch (training-mode BN).
 
     Returns (fwd dict, grads dict, metrics dict).  gU/gA are the DENSE gradients
-    the Keras step hands to Adam: scatter-added gather gradients (IndexedSlices,
+    the Keras step hands to the optimizer: scatter-added gather gradients (IndexedSlices,
     duplicates summed in batch order) plus the dense regulariser term 2*l2*W.
+    ``met["bce"]`` is the data loss of ``loss`` (the name of the default's); ``g["dy"]``
+    the per-rating d loss / d y, everything downstream of it the same for every head.
     """
     dt = dtype
-    f = forward(U, A, ui, ai, head, training=True, dtype=dt)
+    f = forward(U, A, ui, ai, head, training=True, dtype=dt, activation=activation)
     tt = np.asarray(t, dtype=dt)
     B = dt(len(tt))
     w, gamma = dt(head["w"]), dt(head["gamma"])
-    li = bce_from_logits(f["y"], tt, dt)
+    _, li, gy = head_terms(loss, activation, f["y"], tt, dt)
     bce = np.sum(li, dtype=dt) / B
     reg = reg_sumsq(U, A, dt)
-    loss = bce + dt(l2) * reg
+    total = bce + dt(l2) * reg
     mse = np.sum((f["p"] - tt) ** 2, dtype=dt) / B            # metrics=['mse']  config.yaml:88
 
-    dy = (f["p"] - tt) / B
+    dy = gy / B
     zhat = (f["z"] - f["mu"]) * f["r"]
     d_beta = np.sum(dy, dtype=dt)
     d_gamma = np.sum(dy * zhat, dtype=dt)
@@ -223,8 +318,8 @@ def grads(U, A, ui, ai, t, head, l2=1e-4, dtype=np.float32):
     gU = gU + two_l2 * U.astype(dt)
     gA = gA + two_l2 * A.astype(dt)
     g = dict(U=gU, A=gA, w=d_w, b=d_b, gamma=d_gamma, beta=d_beta,
-             dc=dc, coef=coef, self_u=self_u, self_a=self_a)
-    met = dict(loss=loss, bce=bce, reg=reg, mse=mse)
+             dy=dy, dc=dc, coef=coef, self_u=self_u, self_a=self_a)
+    met = dict(loss=total, bce=bce, reg=reg, mse=mse)
     return f, g, met
 
 
@@ -241,20 +336,41 @@ def adam_update(W, m, v, g, alpha, dtype=np.float32):
     W -= (m * dt(alpha)) / (np.sqrt(v, dtype=dt) + dt(ADAM_EPS))
 
 
-def train_step(state, ui, ai, t, lr, l2=1e-4, dtype=np.float32):
-    """One ``model.fit`` step on one batch; mutates ``state``; returns metrics."""
+def opt_update(kind, W, m, v, g, rate, dtype=np.float32):
+    """One dense update of rule ``kind``, in place, in the order include/anirec.h writes it (ANIREC_OPT_*).
+    ``rate``: Adam's bias-corrected ``adam_alpha``, the plain learning rate of the Keras-2.12 SGD / RMSprop /
+    Adagrad rules.  ``v``: Adam's second moment, the RMSprop velocity or the Adagrad accumulator; ``m`` is Adam's."""
     dt = dtype
-    head = state["head"]
-    f, g, met = grads(state["U"], state["A"], ui, ai, t, head, l2, dt)
+    rate = dt(rate)
+    if kind == "adam":
+        adam_update(W, m, v, g, rate, dt)
+    elif kind == "sgd":
+        W[...] = W - g * rate
+    elif kind == "rmsprop":
+        v[...] = dt(0.9) * v + dt(0.1) * (g * g)
+        W[...] = W - (rate * g) * (dt(1) / np.sqrt(v + dt(1e-7)))
+    elif kind == "adagrad":
+        v[...] = v + g * g
+        W[...] = W - (rate * g) / np.sqrt(v + dt(1e-7))
+    else:
+        raise ValueError(kind)
+
+
+def train_step(state, ui, ai, t, lr, l2=1e-4, dtype=np.float32, loss="binary_crossentropy", activation="sigmoid"):
+    """One ``model.fit`` step on one batch with the rule the state was made for; mutates ``state``;
+    returns (metrics, fwd dict, grads dict).  ``met["alpha"]`` is the rate handed to the rule."""
+    dt = dtype
+    head, kind = state["head"], state["optimizer"]
+    f, g, met = grads(state["U"], state["A"], ui, ai, t, head, l2, dt, loss, activation)
     state["t"] += 1
-    alpha = adam_alpha(lr, state["t"], dt)
-    adam_update(state["U"], state["mU"], state["vU"], g["U"], alpha, dt)
-    adam_update(state["A"], state["mA"], state["vA"], g["A"], alpha, dt)
+    alpha = adam_alpha(lr, state["t"], dt) if kind == "adam" else dt(lr)
+    opt_update(kind, state["U"], state["mU"], state["vU"], g["U"], alpha, dt)
+    opt_update(kind, state["A"], state["mA"], state["vA"], g["A"], alpha, dt)
     hp = np.array([head["w"], head["b"], head["gamma"], head["beta"]], dt)
     hg = np.array([g["w"], g["b"], g["gamma"], g["beta"]], dt)
     hm = head["m"].astype(dt)
     hv = head["v"].astype(dt)
-    adam_update(hp, hm, hv, hg, alpha, dt)
+    opt_update(kind, hp, hm, hv, hg, alpha, dt)
     head["w"], head["b"], head["gamma"], head["beta"] = hp
     head["m"], head["v"] = hm, hv
     # moving stats: variable -= (variable - batch) * (1 - momentum); biased batch variance
@@ -266,17 +382,17 @@ def train_step(state, ui, ai, t, lr, l2=1e-4, dtype=np.float32):
     return met, f, g
 
 
-def evaluate(state, ui, ai, t, l2=1e-4, dtype=np.float32):
+def evaluate(state, ui, ai, t, l2=1e-4, dtype=np.float32, loss="binary_crossentropy", activation="sigmoid"):
     """Validation pass (BN inference mode); val_loss includes the L2 term
-    (neural_network.py:216)."""
+    (neural_network.py:216).  ``bce`` is the data loss of ``loss``."""
     dt = dtype
-    f = forward(state["U"], state["A"], ui, ai, state["head"], training=False, dtype=dt)
+    f = forward(state["U"], state["A"], ui, ai, state["head"], training=False, dtype=dt, activation=activation)
     tt = np.asarray(t, dt)
     B = dt(len(tt))
-    bce = np.sum(bce_from_logits(f["y"], tt, dt), dtype=dt) / B
-    loss = bce + dt(l2) * reg_sumsq(state["U"], state["A"], dt)
+    bce = np.sum(head_terms(loss, activation, f["y"], tt, dt)[1], dtype=dt) / B
+    val = bce + dt(l2) * reg_sumsq(state["U"], state["A"], dt)
     mse = np.sum((f["p"] - tt) ** 2, dtype=dt) / B
-    return dict(val_loss=loss, val_mse=mse, bce=bce, p=f["p"])
+    return dict(val_loss=val, val_mse=mse, bce=bce, y=f["y"], p=f["p"])
 
 
 # ---------------------------------------------------------------------------
@@ -341,16 +457,16 @@ def cosine_topk(Wh, queries, k, exclude_self=True, mask=None):
 # ---------------------------------------------------------------------------
 # a9: model.predict on (user, anime) pairs          model_recs.py:394 (+ :396 ranking)
 # ---------------------------------------------------------------------------
-def predict_pairs(U, A, head, ui, ai, dtype=np.float32):
+def predict_pairs(U, A, head, ui, ai, dtype=np.float32, activation="sigmoid"):
     """``model.predict([user_arr, anime_arr]).flatten()`` — BN in inference mode."""
-    return forward(U, A, ui, ai, head, training=False, dtype=dtype)["p"]
+    return forward(U, A, ui, ai, head, training=False, dtype=dtype, activation=activation)["p"]
 
 
-def predict_grid(U, A, head, users, dtype=np.float32):
+def predict_grid(U, A, head, users, dtype=np.float32, activation="sigmoid"):
     """Predicted rating of every anime for each user in ``users`` -> (len(users), n_anime)."""
     n_a = A.shape[0]
     out = np.empty((len(users), n_a), dtype)
     ai = np.arange(n_a)
     for j, u in enumerate(users):
-        out[j] = predict_pairs(U, A, head, np.full(n_a, u), ai, dtype)
+        out[j] = predict_pairs(U, A, head, np.full(n_a, u), ai, dtype, activation)
     return out

@@ -10,8 +10,7 @@ Keras only through module-level names, which are bound to stubs through ``extra=
   * ``get_model``: a two-array holder for ``get_weights`` (as gen_get_weights does);
   * the model handed to ``recommendations``: ``.predict([user_arr, anime_arr])`` is the forward pass in float64 on
     the committed tables and head (normalised dot, Dense(1), BatchNorm in inference mode, activation):
-    ``oracle.anirec_oracle.predict_pairs(..., dtype=np.float64)`` for sigmoid, ``act_fwd`` of
-    tests/test_heads_cpu.py in float64 for the other heads.
+    ``oracle.anirec_oracle.predict_pairs(..., dtype=np.float64, activation=...)``.
 Functions executed, on seeded inputs (reference file:line):
   neural_network/neural_network.py:25-63 get_df                                   -> recs.npz get_df_*
   similar_anime/similar_anime.py:25-60 main_df_by_anime, :63-93 get_anime_df (with get_anime_name, clean)
@@ -28,7 +27,6 @@ Next to every listed row the fp64 score is recorded: the fp64 dot of the referen
 tables, all_anime.csv and synopses.csv as UTF-8 bytes) and the outputs (the ranked lists and the reference's column
 values as a JSON blob); recs.json holds the flags, the case settings and the deviations.  Where a reference body
 raises, the exception type is recorded as a deviation instead of an output (recs.json "deviations")."""
-import importlib.util
 import io
 import json
 import os
@@ -95,30 +93,18 @@ class WandbStub:
         return _Run(self._files)
 
 
-def _act_fwd():
-    spec = importlib.util.spec_from_file_location("heads_restatement", os.path.join(ROOT, "tests", "test_heads_cpu.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m.act_fwd
-
-
 class ModelStub:
     """``model.predict([user_arr, anime_arr])``: the forward pass in float64 on the committed tables and head."""
 
     def __init__(self, U, A, head, act, user_rows, anime_rows):
         self.U, self.A, self.head, self.act = U, A, head, act
         self.user_rows, self.anime_rows = user_rows, anime_rows
-        self._act_fwd = _act_fwd() if act != "sigmoid" else None
 
     def predict(self, id_anime, verbose=0):
         # the caller's indices -> the table rows of the same ids (see run_recommendations)
         ui = self.user_rows[np.asarray(id_anime[0], np.int64)]
         ai = self.anime_rows[np.asarray(id_anime[1], np.int64)]
-        if self.act == "sigmoid":
-            p = orc.predict_pairs(self.U, self.A, self.head, ui, ai, dtype=np.float64)
-        else:
-            y = orc.forward(self.U, self.A, ui, ai, self.head, training=False, dtype=np.float64)["y"]
-            p = self._act_fwd(self.act, y, np.float64)
+        p = orc.predict_pairs(self.U, self.A, self.head, ui, ai, dtype=np.float64, activation=self.act)
         return np.asarray(p, np.float64).reshape(-1, 1)
 
 

@@ -1,9 +1,8 @@
 """NumPy restatement of the Keras 2.12 metrics the GPU accumulates (include/anirec.h, ANIREC_METRIC_*), per rating in
-fp32 from the head's y, p and the target t (the oracle's forward intermediates, as tests/test_heads_cpu.py feeds
-them), summed in fp64.  Each kind cites the Keras function it restates."""
+fp32 from the head's y, p and the target t (the forward intermediates the oracle's step and evaluate return), summed
+in fp64.  Each kind cites the Keras function it restates."""
 import numpy as np
 
-import test_heads_cpu as ref
 from oracle import anirec_oracle as orc
 
 f32 = np.float32
@@ -25,11 +24,11 @@ def per_rating(kind, y, p, t, act):
         d = (np.log(np.maximum(p, EPS) + f32(1), dtype=f32) - np.log(np.maximum(t, EPS) + f32(1), dtype=f32))
         return (d * d).astype(f32)
     if kind == "logcosh":        # keras.metrics.logcosh: x + softplus(-2x) - log(2), x = y_pred - y_true
-        return ref.loss_terms("log_cosh", p, t)[0]
+        return orc.loss_terms("log_cosh", p, t)[0]
     if kind == "bce":            # keras.metrics.binary_crossentropy (from the logits of a sigmoid: _keras_logits)
         if act == "sigmoid":
             return orc.bce_from_logits(y, t, f32)
-        return ref.loss_terms("binary_crossentropy", p, t)[0]
+        return orc.loss_terms("binary_crossentropy", p, t)[0]
     if kind == "accuracy":       # keras.metrics.binary_accuracy: equal(y_true, cast(y_pred > 0.5))
         return (t == (p > f32(0.5)).astype(f32)).astype(f32)
     raise ValueError(kind)
@@ -101,21 +100,18 @@ class Acc:
 
 
 def train_steps(state, ui, ai, t, starts, counts, lr, loss, act, acc=None):
-    """ref.train_step over the batches, the metrics of each batch's training-mode forward added to ``acc``"""
+    """orc.train_step over the batches, the metrics of each batch's training-mode forward added to ``acc``"""
     acc = acc or Acc()
     for s, c in zip(starts, counts):
-        u, a, tt = ui[s:s + c], ai[s:s + c], t[s:s + c]
-        f = orc.forward(state["U"], state["A"], u, a, state["head"], training=True)
-        p, _, _ = ref.head_terms(loss, act, f["y"], tt)
-        acc.add(f["y"], p, tt, act)
-        ref.train_step(state, u, a, tt, lr, loss, act)
+        tt = t[s:s + c]
+        _, f, _ = orc.train_step(state, ui[s:s + c], ai[s:s + c], tt, lr, loss=loss, activation=act)
+        acc.add(f["y"], f["p"], tt, act)
     return acc
 
 
 def evaluate(state, ui, ai, t, act, loss="binary_crossentropy"):
     """the metrics of a validation pass (BN inference mode)"""
-    f = orc.forward(state["U"], state["A"], ui, ai, state["head"], training=False)
-    p, _, _ = ref.head_terms(loss, act, f["y"], t)
+    r = orc.evaluate(state, ui, ai, t, loss=loss, activation=act)
     acc = Acc()
-    acc.add(f["y"], p, t, act)
+    acc.add(r["y"], r["p"], t, act)
     return acc

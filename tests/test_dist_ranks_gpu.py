@@ -23,7 +23,6 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 import metrics_restatement as mr
-from optim_restatement import new_state as opt_new_state, step as opt_step
 from oracle import anirec_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -427,11 +426,11 @@ def test_sgd_user_sharded_on_three_ranks_matches_the_restatement(tmp_path):
     _spawn(_sgd_worker, 3, str(tmp_path))
     d = np.load(tmp_path / "sgd.npz")
     U, A, ui, ai, t, perm = _sgd_problem()
-    st = opt_new_state("sgd", U, A)
+    st = orc.new_state(U, A, orc.new_head(w=1.2), optimizer="sgd")
     losses, ns = [], []
     for k in range(0, len(perm), 1998):
         g = perm[k:k + 1998]
-        met = opt_step("sgd", st, ui[g], ai[g], t[g], LR)
+        met, _, _ = orc.train_step(st, ui[g], ai[g], t[g], LR)
         losses.append(float(met["loss"]) * len(g))
         ns.append(len(g))
     tol = LR * 2e-3 * len(ns)

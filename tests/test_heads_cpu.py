@@ -1,9 +1,6 @@
 """CPU tests of the output heads (--model_loss / --activation_function / --kernel_initializer): name resolution, the
-NumPy restatement of the head kernels (include/anirec.h, ANIREC_LOSS_* / ANIREC_ACT_*) against the oracle and against
-central differences, the Dense(1) initialisers, the weights file and the descriptor layout.
-
-The restatement lives here and tests/test_heads_gpu.py holds the kernels to it: every product and sum in the order
-anirec_dev.hpp writes it, rounded once in fp32."""
+oracle's statement of the head kernels (include/anirec.h, ANIREC_LOSS_* / ANIREC_ACT_*; oracle.anirec_oracle.head_terms)
+against central differences, the Dense(1) initialisers, the weights file and the descriptor layout."""
 import os
 import subprocess
 
@@ -11,163 +8,12 @@ import numpy as np
 import pytest
 
 from anime_recommendations_amd import _lib, schedule, trainer, weights_io
-from oracle import anirec_oracle as orc
+from oracle.anirec_oracle import EPS, ONE_M_EPS, act_fwd, head_terms, loss_terms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 LOSSES = tuple(schedule.LOSSES)
 ACTS = tuple(schedule.ACTIVATIONS)
-EPS = f32(1e-7)
-ONE_M_EPS = f32(1) - EPS
-
-
-# ---- the restatement ------------------------------------------------------------------------------------------
-def softplus(x, dt=f32):
-    x = np.asarray(x, dt)
-    return (np.maximum(x, dt(0)) + np.log1p(np.exp(-np.abs(x), dtype=dt), dtype=dt)).astype(dt)
-
-
-def act_fwd(act, y, dt=f32):
-    y = np.asarray(y, dt)
-    if act == "sigmoid":
-        return orc._sigmoid(y, dt)
-    if act == "linear":
-        return y.copy()
-    if act == "tanh":
-        return np.tanh(y, dtype=dt)
-    if act == "relu":
-        return np.maximum(y, dt(0)).astype(dt)
-    if act == "softplus":
-        return softplus(y, dt)
-    raise ValueError(act)
-
-
-def act_grad(act, y, p, dt=f32):
-    if act == "sigmoid":
-        return (p * (dt(1) - p)).astype(dt)
-    if act == "linear":
-        return np.ones_like(y, dt)
-    if act == "tanh":
-        return (dt(1) - p * p).astype(dt)
-    if act == "relu":
-        return np.where(y > 0, dt(1), dt(0)).astype(dt)
-    if act == "softplus":
-        return orc._sigmoid(y, dt)
-    raise ValueError(act)
-
-
-def loss_terms(loss, p, t, dt=f32):
-    """(l(p, t), dl/dp) per rating"""
-    p, t = np.asarray(p, dt), np.asarray(t, dt)
-    e = (p - t).astype(dt)
-    if loss == "binary_crossentropy":
-        eps, ome = dt(EPS), dt(ONE_M_EPS)
-        q = np.minimum(np.maximum(p, eps), ome).astype(dt)
-        a = (q + eps).astype(dt)
-        b = ((dt(1) - q) + eps).astype(dt)
-        l = -(t * np.log(a, dtype=dt) + (dt(1) - t) * np.log(b, dtype=dt))
-        g = np.where((p >= eps) & (p <= ome), -(t / a) + (dt(1) - t) / b, dt(0))
-    elif loss == "mean_squared_error":
-        l, g = e * e, dt(2) * e
-    elif loss == "mean_absolute_error":
-        l, g = np.abs(e), np.sign(e)
-    elif loss == "huber":
-        ae = np.abs(e)
-        l = np.where(ae <= 1, dt(0.5) * (e * e), ae - dt(0.5))
-        g = np.where(ae <= 1, e, np.sign(e))
-    elif loss == "log_cosh":
-        l = (e + softplus(dt(-2) * e, dt)) - dt(np.log(2.0))
-        g = dt(1) - dt(2) * orc._sigmoid(dt(-2) * e, dt)
-    else:
-        raise ValueError(loss)
-    return np.asarray(l, dt), np.asarray(g, dt)
-
-
-def head_terms(loss, act, y, t, dt=f32):
-    """p = act(y), the data loss l and dl/dy of every rating (the 1/B of the batch mean not applied)"""
-    y, t = np.asarray(y, dt), np.asarray(t, dt)
-    if loss == "binary_crossentropy" and act == "sigmoid":      # from logits, as the reference's model always was
-        p = orc._sigmoid(y, dt)
-        return p, orc.bce_from_logits(y, t, dt), (p - t).astype(dt)
-    p = act_fwd(act, y, dt)
-    l, gp = loss_terms(loss, p, t, dt)
-    return p, l, (gp * act_grad(act, y, p, dt)).astype(dt)
-
-
-def grads(U, A, ui, ai, t, head, loss="binary_crossentropy", act="sigmoid", l2=1e-4, dt=f32):
-    """orc.grads with the head's p, data loss and dy; everything downstream of dy as there."""
-    f = orc.forward(U, A, ui, ai, head, training=True, dtype=dt)
-    p, li, gy = head_terms(loss, act, f["y"], t, dt)
-    f = dict(f, p=p)
-    tt = np.asarray(t, dtype=dt)
-    B = dt(len(tt))
-    w, gamma = dt(head["w"]), dt(head["gamma"])
-    data = np.sum(li, dtype=dt) / B
-    reg = orc.reg_sumsq(U, A, dt)
-    total = data + dt(l2) * reg
-    mse = np.sum((f["p"] - tt) ** 2, dtype=dt) / B
-
-    dy = gy / B
-    zhat = (f["z"] - f["mu"]) * f["r"]
-    d_beta = np.sum(dy, dtype=dt)
-    d_gamma = np.sum(dy * zhat, dtype=dt)
-    dzh = dy * gamma
-    m1 = np.sum(dzh, dtype=dt) / B
-    m2 = np.sum(dzh * zhat, dtype=dt) / B
-    dz = (dzh - m1 - zhat * m2) * f["r"]
-    d_w = np.sum(dz * f["c"], dtype=dt)
-    d_b = np.sum(dz, dtype=dt)
-    dc = dz * w
-    coef = dc * f["ru"] * f["ra"]
-    self_u = np.where(f["su"] >= dt(orc.L2N_EPS), dc * f["c"] * f["ru"] * f["ru"], dt(0)).astype(dt)
-    self_a = np.where(f["sa"] >= dt(orc.L2N_EPS), dc * f["c"] * f["ra"] * f["ra"], dt(0)).astype(dt)
-    du = coef[:, None] * f["a"] - self_u[:, None] * f["u"]
-    da = coef[:, None] * f["u"] - self_a[:, None] * f["a"]
-    gU = np.zeros(U.shape, dt)
-    gA = np.zeros(A.shape, dt)
-    np.add.at(gU, ui, du)
-    np.add.at(gA, ai, da)
-    two_l2 = dt(2.0 * l2)
-    gU = gU + two_l2 * U.astype(dt)
-    gA = gA + two_l2 * A.astype(dt)
-    g = dict(U=gU, A=gA, w=d_w, b=d_b, gamma=d_gamma, beta=d_beta,
-             dc=dc, coef=coef, self_u=self_u, self_a=self_a)
-    met = dict(loss=total, bce=data, reg=reg, mse=mse)
-    return f, g, met, dy
-
-
-def train_step(state, ui, ai, t, lr, loss, act, l2=1e-4, dt=f32):
-    """orc.train_step (Keras Adam) with the head of (loss, act)."""
-    head = state["head"]
-    f, g, met, _ = grads(state["U"], state["A"], ui, ai, t, head, loss, act, l2, dt)
-    state["t"] += 1
-    alpha = orc.adam_alpha(lr, state["t"], dt)
-    orc.adam_update(state["U"], state["mU"], state["vU"], g["U"], alpha, dt)
-    orc.adam_update(state["A"], state["mA"], state["vA"], g["A"], alpha, dt)
-    hp = np.array([head["w"], head["b"], head["gamma"], head["beta"]], dt)
-    hg = np.array([g["w"], g["b"], g["gamma"], g["beta"]], dt)
-    hm, hv = head["m"].astype(dt), head["v"].astype(dt)
-    orc.adam_update(hp, hm, hv, hg, alpha, dt)
-    head["w"], head["b"], head["gamma"], head["beta"] = hp
-    head["m"], head["v"] = hm, hv
-    dec = dt(1.0 - orc.BN_MOMENTUM)
-    head["mov_mean"] = dt(head["mov_mean"]) - (dt(head["mov_mean"]) - f["mu"]) * dec
-    head["mov_var"] = dt(head["mov_var"]) - (dt(head["mov_var"]) - f["var"]) * dec
-    return met
-
-
-def evaluate(state, ui, ai, t, loss, act, l2=1e-4, dt=f32):
-    f = orc.forward(state["U"], state["A"], ui, ai, state["head"], training=False, dtype=dt)
-    p, li, _ = head_terms(loss, act, f["y"], t, dt)
-    tt = np.asarray(t, dt)
-    B = dt(len(tt))
-    val = np.sum(li, dtype=dt) / B + dt(l2) * orc.reg_sumsq(state["U"], state["A"], dt)
-    return dict(val_loss=val, val_mse=np.sum((p - tt) ** 2, dtype=dt) / B, p=p)
-
-
-def predict_pairs(U, A, head, ui, ai, act):
-    f = orc.forward(U, A, ui, ai, head, training=False)
-    return act_fwd(act, f["y"])
 
 
 # ---- name resolution ------------------------------------------------------------------------------------------
@@ -213,29 +59,7 @@ def test_the_component_no_longer_rejects_the_three_flags():
         assert fn in src
 
 
-# ---- the restatement against the oracle and against central differences ---------------------------------------
-def _problem(seed, n_u=300, n_a=200, n=700):
-    rng = np.random.default_rng(seed)
-    U = rng.uniform(-0.05, 0.05, (n_u, 128)).astype(f32)
-    A = rng.uniform(-0.05, 0.05, (n_a, 128)).astype(f32)
-    ui = rng.integers(0, n_u, n)
-    ai = (rng.zipf(1.3, n) - 1) % n_a
-    t = (rng.integers(0, 11, n) / 10).astype(f32)
-    return U, A, ui, ai, t
-
-
-def test_default_head_restates_the_oracle_bitwise():
-    U, A, ui, ai, t = _problem(1)
-    head = orc.new_head(w=1.2, b=0.05, gamma=0.9, beta=0.1)
-    f0, g0, m0 = orc.grads(U, A, ui, ai, t, head)
-    f1, g1, m1, _ = grads(U, A, ui, ai, t, head)
-    for k in g0:
-        assert np.array_equal(np.asarray(g0[k]).view(np.uint32), np.asarray(g1[k]).view(np.uint32)), k
-    for k in m0:
-        assert np.asarray(m0[k]).view(np.uint32) == np.asarray(m1[k]).view(np.uint32), k
-    assert np.array_equal(f0["p"], f1["p"])
-
-
+# ---- the head terms against central differences ----------------------------------------------------------------
 def _away_from_kinks(loss, act, y, t):
     """ratings whose (y, p - t) lie at least 1e-3 from the kinks of the pair's loss and activation"""
     p = act_fwd(act, y, np.float64)

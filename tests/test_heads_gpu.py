@@ -1,5 +1,5 @@
 """GPU tests of the output heads (anirec_train_desc.loss / .activation, the predict calls' activation): the HIP head
-against the NumPy restatement of tests/test_heads_cpu.py, fed with the oracle's forward intermediates, through every
+against the oracle's statement of the heads (oracle.anirec_oracle.head_terms), through every
 layer — the head and eval kernels, the one-GPU engine (stage by stage, eager, graph, lazy), trainer.fit, two gloo
 ranks, the predict and model_recs paths and the neural_network component."""
 import ctypes as C
@@ -14,13 +14,12 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-import test_heads_cpu as ref
 from oracle import anirec_oracle as orc
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-LOSSES, ACTS = ref.LOSSES, ref.ACTS
+LOSSES, ACTS = orc.LOSSES, orc.ACTIVATIONS
 PAIRS = [(l, a) for l in LOSSES for a in ACTS]
 SET = [("mean_squared_error", "linear"), ("binary_crossentropy", "relu"), ("huber", "tanh"),
        ("log_cosh", "softplus"), ("mean_absolute_error", "sigmoid")]
@@ -63,7 +62,7 @@ def _dy_bracket(loss, act, y, t, B):
     (and its p by a few ulps of the transcendental), which moves a badly conditioned dy (a BCE of probabilities with p
     near 0 or 1) by far more than its own rounding"""
     d = f32(1e-6) * (f32(1) + np.abs(y))
-    ds = [ref.head_terms(loss, act, y + s * d, t)[2] / f32(B) for s in (-1, 0, 1)]
+    ds = [orc.head_terms(loss, act, y + s * d, t)[2] / f32(B) for s in (-1, 0, 1)]
     return np.minimum.reduce(ds), np.maximum.reduce(ds), ds[1]
 
 
@@ -77,7 +76,8 @@ def test_one_step_stage_by_stage(loss, act):
     eng.set_epoch(ui, ai, t, [0], [B], [orc.adam_alpha(1e-5, 1)])
     eng.fwd()
     eng.head()
-    f, g, met, dy_o = ref.grads(U, A, ui, ai, t, orc.new_head(**HEAD), loss, act)
+    f, g, met = orc.grads(U, A, ui, ai, t, orc.new_head(**HEAD), loss=loss, activation=act)
+    dy_o = g["dy"]
     dy = read_ws(eng, "dy")[:B]
     lo, hi, _ = _dy_bracket(loss, act, f["y"], t, B)
     tol = np.abs(dy_o).max() * 2e-5 + 2e-5 * np.abs(dy_o)
@@ -113,7 +113,8 @@ def test_steps_match_the_restatement(loss, act):
     head = dict(HEAD, gamma=0.25, beta=0.5) if (loss, act) == ("binary_crossentropy", "relu") else HEAD
     st = _state(U, A, head)
     starts, counts, alphas = _schedule(n, B, lr)
-    mets = [ref.train_step(st, ui[s:s + c], ai[s:s + c], t[s:s + c], lr, loss, act) for s, c in zip(starts, counts)]
+    mets = [orc.train_step(st, ui[s:s + c], ai[s:s + c], t[s:s + c], lr, loss=loss, activation=act)[0]
+            for s, c in zip(starts, counts)]
     eng = _engine(U, A, B, loss, act)
     eng.set_head(**head)
     eng.set_epoch(ui, ai, t, starts, counts, alphas)
@@ -180,7 +181,7 @@ def test_evaluate_matches_the_restatement(loss, act):
     eng.set_head(**hv)
     st = orc.new_state(U, A, orc.new_head(**hv))
     vl, vm = eng.evaluate(torch.from_numpy(ui).cuda(), torch.from_numpy(ai).cuda(), torch.from_numpy(t).cuda())
-    r = ref.evaluate(st, ui, ai, t, loss, act)
+    r = orc.evaluate(st, ui, ai, t, loss=loss, activation=act)
     assert abs(vl - float(r["val_loss"])) < 2e-6 + 2e-5 * abs(float(r["val_loss"]))
     assert abs(vm - float(r["val_mse"])) < 2e-6
     eng.close()
@@ -261,7 +262,7 @@ def test_predict_paths_match_the_restatement(act, n_a):
     users = np.arange(0, 300, 3)
     ui = np.repeat(users, n_a)
     ai = np.tile(np.arange(n_a), len(users))
-    want = ref.predict_pairs(U, A, orc.new_head(**HEADS[act]), ui, ai, act).reshape(len(users), n_a)
+    want = orc.predict_pairs(U, A, orc.new_head(**HEADS[act]), ui, ai, activation=act).reshape(len(users), n_a)
     p = ops.predict_pairs(Ut, At, head, ui, ai).cpu().numpy().reshape(len(users), n_a)
     np.testing.assert_allclose(p, want, rtol=0, atol=1e-5)
     g = ops.predict_grid(Ut, At, head, users).cpu().numpy()
@@ -364,7 +365,7 @@ def test_fit_history_mse_linear():
         L = M = 0.0
         for s in range(0, n_train, cfg.batch_size):
             g = perm[s:s + cfg.batch_size]
-            met = ref.train_step(st, ui[g], ai[g], rt[g], lr, "mean_squared_error", "linear")
+            met = orc.train_step(st, ui[g], ai[g], rt[g], lr, loss="mean_squared_error", activation="linear")[0]
             L += float(met["loss"]) * len(g)
             M += float(met["mse"]) * len(g)
         hist["loss"].append(L / n_train)
@@ -375,7 +376,7 @@ def test_fit_history_mse_linear():
     # elements whose gradient is rounding noise let the two runs' tables drift apart by far more than the History's
     # training columns show, so the restatement evaluates the engine's own final state
     fin = orc.new_state(res.U, res.A, orc.new_head(**res.head))
-    ev = ref.evaluate(fin, vu, va, vt, "mean_squared_error", "linear")
+    ev = orc.evaluate(fin, vu, va, vt, loss="mean_squared_error", activation="linear")
     assert abs(res.history["val_loss"][-1] - float(ev["val_loss"])) < 5e-6
     assert abs(res.history["val_mse"][-1] - float(ev["val_mse"])) < 5e-6
     assert res.stopped_epoch == -1
@@ -443,7 +444,7 @@ def test_two_gloo_ranks_sharded_match_the_restatement(tmp_path):
     losses, ns = [], []
     for k in range(0, len(perm), Bg):
         g = perm[k:k + Bg]
-        met = ref.train_step(st, ui[g], ai[g], t[g], lr, loss, act)
+        met = orc.train_step(st, ui[g], ai[g], t[g], lr, loss=loss, activation=act)[0]
         losses.append(float(met["loss"]) * len(g))
         ns.append(len(g))
     tol = lr * 2e-3 * len(ns)
@@ -506,6 +507,6 @@ def test_neural_network_component_mse_linear_then_model_recs(tmp_path):
     ids = list(np.asarray(anime_ids))
     ai = np.array([ids.index(a) for a in frame["anime_id"]])
     hd = orc.new_head(**{k: m["head"][k] for k in ("w", "b", "gamma", "beta", "mov_mean", "mov_var")})
-    want = ref.predict_pairs(m["U"], m["A"], hd, np.full(len(ai), pos), ai, "linear")
+    want = orc.predict_pairs(m["U"], m["A"], hd, np.full(len(ai), pos), ai, activation="linear")
     np.testing.assert_allclose(frame["Prediction"].to_numpy(), want, rtol=0, atol=1e-5)
     assert (np.diff(frame["Prediction"].to_numpy()) <= 0).all()

@@ -1,6 +1,6 @@
-"""GPU tests of the SGD / RMSprop / Adagrad train step (anirec_train_desc.optimizer): the HIP update against a NumPy
-restatement of the Keras-2.12 rules (include/anirec.h, ANIREC_OPT_*) on the oracle's gradients
-(oracle.anirec_oracle.grads), through every layer — the flat kernel, the one-GPU engine (graph, eager and stage by
+"""GPU tests of the SGD / RMSprop / Adagrad train step (anirec_train_desc.optimizer): the HIP update against the
+oracle's statement of the Keras-2.12 rules (include/anirec.h, ANIREC_OPT_*; oracle.anirec_oracle.opt_update) on the
+oracle's gradients, through every layer — the flat kernel, the one-GPU engine (graph, eager and stage by
 stage), trainer.fit, two gloo ranks, the neural_network component."""
 import json
 import os
@@ -15,7 +15,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import anirec_oracle as orc
-from optim_restatement import KINDS, SLOT_INIT, new_state, opt_update, step
+from oracle.anirec_oracle import KINDS, SLOT_INIT
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,7 +44,7 @@ def test_opt_flat_is_bitwise_the_restatement(kind):
     tw, ts, tg = (torch.from_numpy(x.copy()).cuda() for x in (w, s, g))
     ops.opt_flat(kind, tw, None if kind == "sgd" else ts, tg, lr)
     torch.cuda.synchronize()
-    opt_update(kind, w, s, g, lr)
+    orc.opt_update(kind, w, None, s, g, lr)
     assert np.array_equal(tw.cpu().numpy().view(np.uint32), w.view(np.uint32))
     if kind != "sgd":
         assert np.array_equal(ts.cpu().numpy().view(np.uint32), s.view(np.uint32))
@@ -100,10 +100,10 @@ def test_engine_run_matches_the_restated_update(kind, n_u, n_a, B, steps, zipf):
     n = B * steps - (B // 3 if steps > 1 else 0)      # ragged last batch
     U, A, ui, ai, t = _problem(3, n_u, n_a, n, zipf)
     lr = 3e-5
-    st = new_state(kind, U, A)
+    st = orc.new_state(U, A, orc.new_head(w=1.2), optimizer=kind)
     eng = _engine(kind, U, A, B)
     starts, counts = _epoch(kind, eng, ui, ai, t, B, lr)
-    mets = [step(kind, st, ui[s:s + c], ai[s:s + c], t[s:s + c], lr) for s, c in zip(starts, counts)]
+    mets = [orc.train_step(st, ui[s:s + c], ai[s:s + c], t[s:s + c], lr)[0] for s, c in zip(starts, counts)]
     eng.run(len(starts), use_graph=False)
     rec = eng.read_state()
     assert rec["step_fwd"] == len(starts)
@@ -113,7 +113,7 @@ def test_engine_run_matches_the_restated_update(kind, n_u, n_a, B, steps, zipf):
     np.testing.assert_allclose(eng.A.cpu().numpy(), st["A"], atol=tol)
     V = eng.V.cpu().numpy()
     if kind != "sgd":
-        for got, want in ((V[:n_u], st["sU"]), (V[n_u:], st["sA"])):
+        for got, want in ((V[:n_u], st["vU"]), (V[n_u:], st["vA"])):
             np.testing.assert_allclose(got, want, atol=np.abs(want).max() * 1e-4)
         np.testing.assert_allclose(np.array(rec["adam_v"]), st["head"]["v"], atol=np.abs(st["head"]["v"]).max() * 1e-4)
     else:
@@ -165,15 +165,15 @@ def test_adagrad_starts_from_its_initial_accumulator():
     assert (np.array(eng.read_state()["adam_v"]) == f32(0.1)).all()
     eng.set_head(w=1.2)
     assert (np.array(eng.read_state()["adam_v"]) == f32(0.1)).all()
-    st = new_state("adagrad", U, A)
+    st = orc.new_state(U, A, orc.new_head(w=1.2), optimizer="adagrad")
     _epoch("adagrad", eng, ui, ai, t, 400, lr)
-    step("adagrad", st, ui, ai, t, lr)
+    orc.train_step(st, ui, ai, t, lr)
     eng.run(1, use_graph=False)
     rec = eng.read_state()
     np.testing.assert_allclose(eng.U.cpu().numpy(), st["U"], atol=lr * 2e-3 + 1e-9)
     np.testing.assert_allclose(eng.A.cpu().numpy(), st["A"], atol=lr * 2e-3 + 1e-9)
     V = eng.V.cpu().numpy()
-    np.testing.assert_allclose(V, np.concatenate([st["sU"], st["sA"]]), rtol=1e-6)
+    np.testing.assert_allclose(V, np.concatenate([st["vU"], st["vA"]]), rtol=1e-6)
     for k in ("w", "gamma", "beta"):
         assert abs(float(rec[k]) - float(st["head"][k])) < lr * 2e-3 + 1e-9, k
     st2 = eng.optimizer_state(iterations=1)
@@ -255,7 +255,7 @@ def _oracle_fit(kind, table, cfg, dev):
     tr, te = table.split(cfg.test_size)
     n_train = tr.stop - tr.start
     U0, A0, w0 = trainer.init_weights(table.n_users, table.n_anime, 128, cfg.seed)
-    st = new_state(kind, U0, A0, w=w0)
+    st = orc.new_state(U0, A0, orc.new_head(w=w0), optimizer=kind)
     ui, ai, rt = table.user[tr], table.anime[tr], table.rating[tr].astype(f32)
     vu, va, vt = table.user[te], table.anime[te], table.rating[te].astype(f32)
     gen = torch.Generator(device=dev)
@@ -267,7 +267,7 @@ def _oracle_fit(kind, table, cfg, dev):
         lw = se = 0.0
         for s in range(0, n_train, cfg.batch_size):
             p = perm[s:s + cfg.batch_size]
-            met = step(kind, st, ui[p], ai[p], rt[p], lr, cfg.l2_reg_factor)
+            met, _, _ = orc.train_step(st, ui[p], ai[p], rt[p], lr, cfg.l2_reg_factor)
             lw += float(met["loss"]) * len(p)
             se += float(met["mse"]) * len(p)
         ev = orc.evaluate(st, vu, va, vt, cfg.l2_reg_factor)
@@ -359,20 +359,20 @@ def test_two_gloo_ranks_match_the_restatement(tmp_path, mode, kind):
     mp.spawn(_dist_worker, args=(2, _port(), str(tmp_path), mode, kind), nprocs=2, join=True)
     d = np.load(tmp_path / "dist.npz")
     U, A, ui, ai, t, perm = _dist_problem()
-    st = new_state(kind, U, A)
+    st = orc.new_state(U, A, orc.new_head(w=1.2), optimizer=kind)
     lr, Bg = 3e-5, 2000
     losses, ns = [], []
     for k in range(0, len(perm), Bg):
         g = perm[k:k + Bg]
-        met = step(kind, st, ui[g], ai[g], t[g], lr)
+        met, _, _ = orc.train_step(st, ui[g], ai[g], t[g], lr)
         losses.append(float(met["loss"]) * len(g))
         ns.append(len(g))
     tol = lr * 2e-3 * len(ns)
     np.testing.assert_allclose(d["U"], st["U"], atol=tol)
     np.testing.assert_allclose(d["A"], st["A"], atol=tol)
     if kind == "adagrad":
-        np.testing.assert_allclose(d["user_embedding__accumulator"], st["sU"], rtol=1e-6)
-        np.testing.assert_allclose(d["anime_embedding__accumulator"], st["sA"], rtol=1e-6)
+        np.testing.assert_allclose(d["user_embedding__accumulator"], st["vU"], rtol=1e-6)
+        np.testing.assert_allclose(d["anime_embedding__accumulator"], st["vA"], rtol=1e-6)
     else:
         assert "user_embedding__m" not in d.files and "iterations" in d.files
     h = st["head"]

@@ -15,8 +15,6 @@ import numpy as np
 import pytest
 import torch
 
-import optim_restatement as optr
-import test_heads_cpu as heads
 from oracle import anirec_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -289,15 +287,15 @@ def test_train_edges_match_oracle_dense_and_lazy(name):
 
 
 # ---- 2. the other optimizers and heads at the edges -----------------------------------------------------------
-@pytest.mark.parametrize("kind", optr.KINDS)
+@pytest.mark.parametrize("kind", orc.KINDS)
 @pytest.mark.parametrize("name", ["single", "capacity", "one_user"])
 def test_optimizer_edges_match_the_restatement(name, kind):
     from anime_recommendations_amd import schedule
     U, A, ui, ai, t, B, starts, counts, hd = _case(name)
     n_u, steps = U.shape[0], len(counts)
-    st = optr.new_state(kind, U, A, w=hd["w"])
+    st = orc.new_state(U, A, orc.new_head(w=hd["w"]), optimizer=kind)
     st["head"]["b"] = f32(hd.get("b", 0.0))
-    mets = [optr.step(kind, st, u, a, r, LR) for u, a, r in _batches(name)]
+    mets = [orc.train_step(st, u, a, r, LR)[0] for u, a, r in _batches(name)]
     eng = _engine(name, False, optimizer=kind)
     eng.set_epoch(ui, ai, t, starts, counts, schedule.step_rates(kind, LR, 1, steps))
     eng.reset_metrics()
@@ -310,7 +308,7 @@ def test_optimizer_edges_match_the_restatement(name, kind):
     np.testing.assert_allclose(eng.A.cpu().numpy(), st["A"], atol=tol)
     V = eng.V.cpu().numpy()
     if kind != "sgd":
-        for got, want in ((V[:n_u], st["sU"]), (V[n_u:], st["sA"])):
+        for got, want in ((V[:n_u], st["vU"]), (V[n_u:], st["vA"])):
             np.testing.assert_allclose(got, want, atol=np.abs(want).max() * 1e-4)
         np.testing.assert_allclose(np.array(rec["adam_v"]), st["head"]["v"], atol=np.abs(st["head"]["v"]).max() * 1e-4)
     else:
@@ -343,7 +341,7 @@ def test_head_edges_match_the_restatement(name, loss, act):
     if act == "relu":
         head.update(gamma=0.5, beta=-5.0)
     st = orc.new_state(U, A, orc.new_head(**head))
-    mets = [heads.train_step(st, u, a, r, LR, loss, act) for u, a, r in _batches(name)]
+    mets = [orc.train_step(st, u, a, r, LR, loss=loss, activation=act)[0] for u, a, r in _batches(name)]
     eng = _engine(name, False, loss=loss, activation=act)
     eng.set_head(**head)
     eng.set_epoch(ui, ai, t, starts, counts, [orc.adam_alpha(LR, i + 1) for i in range(steps)])
