@@ -17,6 +17,10 @@
  *  - the library never allocates device memory and never synchronises the stream
  *    (exception: the *_create/_destroy calls, which touch no stream work);
  *    all work is stream-ordered and graph-capturable.
+ *  - apart from the training `workspace`, `rowmap` and `lazy_state` (zero before first use), no buffer needs any
+ *    particular content on entry: a workspace may hold the leftovers of any earlier call.  Every output element in
+ *    the documented extent is written, padding included.  Count and flag words (*n_out, *n_unique, out_max2,
+ *    *err_flag, the flags arrays) are overwritten by the call: the caller need not clear them.
  *  - embedding rows are fp32, row-major, exactly ANIREC_DIM (=128) wide
  *    (reference: config/config.yaml:63 embedding_size: 128).
  */
