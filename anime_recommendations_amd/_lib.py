@@ -14,6 +14,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ANIREC_LIB_PATH") or os.path.join(_PKG, "libanirec.so")   # override: A/B of two builds on one box
 
 DIM = 128
+WIDTHS = (32, 64, 128, 256)   # row widths the *_w entry points implement (a row is width / 4 lanes of float4)
 MAX_BATCH = 16384
 CHUNK = 32
 ADAM_BLOCKS = 8192
@@ -181,7 +182,42 @@ PROTOTYPES = {
     "anirec_ingest_half_columns": (C.c_int, [_vp, _vp, _i64, C.POINTER(IngestOpts), _vp, _vp, _vp, _sz, _vp]),
     "anirec_ingest_encode_workspace_bytes": (_sz, [_i64, _i32]),
     "anirec_ingest_encode": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the twins that take the row width (`int32_t dim`; NAME(...) == NAME_w(..., 128))
+    "anirec_train_workspace_bytes_w": (_sz, [_i32, _i32, _i32]),
+    "anirec_train_init_reg_w": (C.c_int, [_DP, _i32, _vp]),
+    "anirec_train_prep_w": (C.c_int, [_DP, _i32, _i32, _i32, _vp]),
+    "anirec_train_fwd_w": (C.c_int, [_DP, _i32, _vp]),
+    "anirec_train_head_w": (C.c_int, [_DP, _i32, _vp]),
+    "anirec_train_bwd_w": (C.c_int, [_DP, _i32, _vp]),
+    "anirec_train_adam_w": (C.c_int, [_DP, _i32, _vp]),
+    "anirec_trainer_create_w": (C.c_int, [_DP, _i32, C.POINTER(_vp)]),
+    "anirec_eval_metrics_w": (C.c_int, [_DP, _i32, C.c_uint32, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "anirec_rownorm_w": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "anirec_cosine_scores_w": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    "anirec_cosine_topk_w": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "anirec_cosine_topk_large_w": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "anirec_predict_pairs_w": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp]),
+    "anirec_predict_workspace_bytes_w": (_sz, [_i32, _i32, _i32, _i32]),
+    "anirec_predict_grid_w": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _sz, _vp]),
+    "anirec_predict_topk_w": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
+                                        _vp, _vp, _sz, _vp]),
+    "anirec_predict_topk_large_workspace_bytes_w": (_sz, [_i32, _i32, _i32, _i32]),
+    "anirec_predict_topk_large_w": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
+                                              _vp, _vp, _sz, _vp]),
 }
+
+
+def check_width(width) -> int:
+    """The row width as an int, or a ValueError that lists the supported ones (Keras takes any positive int; the
+    kernels map a row to a power-of-two group of lanes)."""
+    try:
+        w = int(width)
+    except (TypeError, ValueError):
+        w = None
+    if w is None or w != width or w not in WIDTHS:
+        raise ValueError("embedding_size %r is not supported: the libanirec kernels take the widths %s"
+                         % (width, ", ".join(str(x) for x in WIDTHS)))
+    return w
 
 _lib = None
 

@@ -37,6 +37,16 @@ __device__ __forceinline__ float halfwave_sum(float v) {
   return v;
 }
 
+// Sum over the kG lanes of a row group (kG = width / 4 = 8, 16, 32 or 64 lanes: 8, 4, 2 or 1 rows per wave); every
+// lane of the group receives the total.  kG == 32 is halfwave_sum, butterfly step for step; kG == 64 crosses the two
+// 32-lane halves of the wave.
+template <int kG>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = kG / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, kG);
+  return v;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -161,6 +171,24 @@ __device__ __forceinline__ float act_fwd(float y) {
   }
 }
 
+// p = act(y) with the activation either a compile-time constant (kAct >= 0: the 128-wide kernels, one instantiation
+// per kind as ever) or, kAct < 0, the run-time value `act` (the kernels of the other widths: one instantiation per
+// width, not per width and kind).  The same act_fwd either way.
+template <int kAct>
+__device__ __forceinline__ float act_any(float y, int act) {
+  if constexpr (kAct >= 0) {
+    return act_fwd<kAct>(y);
+  } else {
+    switch (act) {
+      case ANIREC_ACT_LINEAR: return act_fwd<ANIREC_ACT_LINEAR>(y);
+      case ANIREC_ACT_TANH: return act_fwd<ANIREC_ACT_TANH>(y);
+      case ANIREC_ACT_RELU: return act_fwd<ANIREC_ACT_RELU>(y);
+      case ANIREC_ACT_SOFTPLUS: return act_fwd<ANIREC_ACT_SOFTPLUS>(y);
+      default: return act_fwd<ANIREC_ACT_SIGMOID>(y);
+    }
+  }
+}
+
 // d act / d y as TF's gradient op computes it, from y and p = act(y)
 template <int kAct>
 __device__ __forceinline__ float act_grad(float y, float p) {
@@ -234,9 +262,24 @@ __device__ __forceinline__ float head_loss(float y, float t, float p) {
 
 // rating of a pair from its cosine through the folded BN-inference head: ONE definition shared by the
 // exact path (k_scores epilogue) and the MFMA path's re-rank, so both produce the same fp32 value
+// (kAct < 0: the run-time activation `act`, act_any)
 template <int kAct = ANIREC_ACT_SIGMOID>
-__device__ __forceinline__ float rating_from_cosine(float c, float hs, float hb) {
-  return act_fwd<kAct>(__fmaf_rn(c, hs, hb));
+__device__ __forceinline__ float rating_from_cosine(float c, float hs, float hb, int act = 0) {
+  return act_any<kAct>(__fmaf_rn(c, hs, hb), act);
+}
+
+// host: a row width the *_w entry points implement (a row is dim / 4 lanes of float4: 8, 16, 32 or 64 lanes)
+static inline bool dim_ok(int32_t dim) { return dim == 32 || dim == 64 || dim == 128 || dim == 256; }
+// host: calls f(std::integral_constant<int, kD>) for a (checked) width OTHER than ANIREC_DIM — the 128-wide kernels
+// keep their own launches (and names), so nothing of them is instantiated twice
+template <typename F>
+static inline void with_width(int32_t dim, F &&f) {
+  switch (dim) {
+    case 32: f(std::integral_constant<int, 32>()); break;
+    case 64: f(std::integral_constant<int, 64>()); break;
+    case 256: f(std::integral_constant<int, 256>()); break;
+    default: break;
+  }
 }
 
 // host: an ANIREC_ACT_* / ANIREC_LOSS_* value the kernels implement

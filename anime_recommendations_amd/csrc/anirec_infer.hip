@@ -22,16 +22,53 @@ namespace anirec {
 // mode 0: NumPy get_weights  : x / sqrt(sum x^2)            (no epsilon, zero row -> NaN)
 // mode 1: tf.nn.l2_normalize : x * (1/sqrt(max(sum x^2, 1e-12)))   (Dot(normalize=True))
 // rows: optional gather list (out row j = W[rows[j]]), else identity.
-template <int kMode>
-__global__ __launch_bounds__(256) void k_rownorm(const float *W, const int32_t *rows, int n,
-                                                 float *out) {
-  const int l = threadIdx.x & 31;
-  const int nhw = gridDim.x * 8;
-  for (int r = blockIdx.x * 8 + (threadIdx.x >> 5); r < n; r += nhw) {
+// A row is one group of kD / 4 lanes (a half-wave at 128), 1024 / kD rows per workgroup.
+
+// sum(x^2) of a row in the order NumPy's add.reduce takes over a contiguous fp32 row of kD <= 256 elements (the
+// reference's np.linalg.norm(W, axis=1): squares rounded to fp32, then the pairwise sum's unrolled block): eight
+// accumulators r[j] = ((x[j] + x[j + 8]) + x[j + 16]) + ... folded in index order over blocks of 128 elements,
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) per block, the two blocks of a 256-wide row added last.  With
+// the same sum, the correctly rounded sqrt and divide give NumPy's row bit for bit, whatever the row holds; a
+// butterfly order (the 128-wide kernel's, pinned there by its bitwise tests) leaves the norm an ulp away on some
+// rows and some quotients three ulps away.  Lane l holds elements 4l .. 4l + 3: even lanes carry r0..r3, odd lanes
+// r4..r7, and the fold walks the lanes of equal parity in order — kB / 2 - 1 dependent steps of four shuffles.
+template <int kD>
+__device__ __forceinline__ float sumsq_numpy_order(const float4 &x, int l) {
+#pragma clang fp contract(off)
+  constexpr int kG = kD / 4, kB = kG < 32 ? kG : 32;  // lanes of one 128-element block
+  const int lb = l & (kB - 1);
+  const float4 sq = make_float4(x.x * x.x, x.y * x.y, x.z * x.z, x.w * x.w);
+  float4 p = sq;
+#pragma unroll
+  for (int s = 2; s < kB; s += 2) {
+    float4 up;
+    up.x = __shfl_up(p.x, 2, kG);
+    up.y = __shfl_up(p.y, 2, kG);
+    up.z = __shfl_up(p.z, 2, kG);
+    up.w = __shfl_up(p.w, 2, kG);
+    if ((lb & ~1) == s) p = make_float4(up.x + sq.x, up.y + sq.y, up.z + sq.z, up.w + sq.w);
+  }
+  const float h = (p.x + p.y) + (p.z + p.w);
+  float ss = __shfl(h, kB - 2, kG) + __shfl(h, kB - 1, kG);
+  if constexpr (kG > kB) ss = ss + (__shfl(h, kB + kB - 2, kG) + __shfl(h, kB + kB - 1, kG));
+  return ss;
+}
+
+template <int kMode, int kD>
+__device__ __forceinline__ void rownorm_body(const float *W, const int32_t *rows, int n, float *out) {
+  constexpr int kG = kD / 4, kRpb = 256 / kG;
+  const int l = threadIdx.x & (kG - 1);
+  const int nhw = gridDim.x * kRpb;
+  for (int r = blockIdx.x * kRpb + (threadIdx.x / kG); r < n; r += nhw) {
     const int src = rows ? rows[r] : r;
-    float4 x = reinterpret_cast<const float4 *>(W)[(size_t)src * kRowVec + l];
-    float ss = x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
-    ss = halfwave_sum(ss);
+    float4 x = reinterpret_cast<const float4 *>(W)[(size_t)src * kG + l];
+    float ss;
+    if constexpr (kMode == 0 && kD != kDim) {
+      ss = sumsq_numpy_order<kD>(x, l);
+    } else {
+      ss = x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
+      ss = group_sum<kG>(ss);
+    }
     float4 y;
     if (kMode == 0) {
       const float nrm = sqrtf(ss);
@@ -46,8 +83,28 @@ __global__ __launch_bounds__(256) void k_rownorm(const float *W, const int32_t *
       y.z = x.z * rinv;
       y.w = x.w * rinv;
     }
-    reinterpret_cast<float4 *>(out)[(size_t)r * kRowVec + l] = y;
+    reinterpret_cast<float4 *>(out)[(size_t)r * kG + l] = y;
   }
+}
+template <int kMode>
+__global__ __launch_bounds__(256) void k_rownorm(const float *W, const int32_t *rows, int n,
+                                                 float *out) {
+  rownorm_body<kMode, kDim>(W, rows, n, out);
+}
+template <int kMode, int kD>  // the widths other than 128 (the *_w entry points)
+__global__ __launch_bounds__(256) void k_rownorm_w(const float *W, const int32_t *rows, int n, float *out) {
+  rownorm_body<kMode, kD>(W, rows, n, out);
+}
+template <int kMode>
+static void launch_rownorm(const float *W, const int32_t *rows, int n, float *out, int dim, hipStream_t s) {
+  int blocks = (int)(((long long)n * dim + 1023) / 1024);  // 1024 / dim rows per workgroup
+  if (blocks > 4096) blocks = 4096;
+  if (dim == kDim)
+    hipLaunchKernelGGL(k_rownorm<kMode>, dim3(blocks), dim3(256), 0, s, W, rows, n, out);
+  else
+    with_width(dim, [&](auto kd) {
+      hipLaunchKernelGGL((k_rownorm_w<kMode, decltype(kd)::value>), dim3(blocks), dim3(256), 0, s, W, rows, n, out);
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -56,65 +113,78 @@ __global__ __launch_bounds__(256) void k_rownorm(const float *W, const int32_t *
 // in LDS with a 132-float row pitch (ds_read_b128 of rows tx+16r is conflict-free).
 // ------------------------------------------------------------------------------------
 constexpr int kTile = 64;
-constexpr int kPitch = kDim + 4;
+// floats of a row staged in LDS at a time: the whole row up to 128 (pitch 132: the two 64-row tiles take 66 KB); a
+// 256-wide row is walked in two 128-float slices, the fma chain running on through both
+template <int kD>
+struct ScoreGeom {
+  static constexpr int kS = kD < kDim ? kD : kDim;  // floats per slice
+  static constexpr int kSV = kS / 4, kPitch = kS + 4, kRowV = kD / 4;
+};
 
 struct ScoreArgs {
-  const float *Q;         // [*, 128] query matrix
+  const float *Q;         // [*, dim] query matrix
   const int32_t *qrows;   // optional: query j reads Q[qrows[j]]
   int nq;
-  const float *W;         // [n, 128]
+  const float *W;         // [n, dim]
   int n;
   float *out;             // [nq][ld]
   size_t ld;
   int use_head;           // 1: act(c*hs + hb), the kernel's activation kAct
   float hs, hb;
+  int act;                // the activation as a run-time value: read by the kernels of the other widths only
 };
 
-template <int kAct>
-__global__ __launch_bounds__(256) void k_scores(ScoreArgs a) {
+// kAct >= 0: the activation of the epilogue as a template parameter (k_scores: the 128-wide kernel); < 0: a.act
+template <int kAct, int kD>
+__device__ __forceinline__ void scores_body(const ScoreArgs &a) {
+  constexpr int kSV = ScoreGeom<kD>::kSV, kPitch = ScoreGeom<kD>::kPitch, kRowV = ScoreGeom<kD>::kRowV;
   __shared__ __attribute__((aligned(16))) float Qs[kTile * kPitch];
   __shared__ __attribute__((aligned(16))) float Ws[kTile * kPitch];
   const int tid = threadIdx.x;
   const int q0 = blockIdx.y * kTile, j0 = blockIdx.x * kTile;
-  // stage: 64 rows x 32 float4 per tile, 256 threads -> 8 float4 each per tile
-  for (int e = tid; e < kTile * kRowVec; e += 256) {
-    const int r = e >> 5, cidx = e & 31;
-    float4 qv = make_float4(0.f, 0.f, 0.f, 0.f), wv = qv;
-    if (q0 + r < a.nq) {
-      const int src = a.qrows ? a.qrows[q0 + r] : q0 + r;
-      qv = reinterpret_cast<const float4 *>(a.Q)[(size_t)src * kRowVec + cidx];
-    }
-    if (j0 + r < a.n) wv = reinterpret_cast<const float4 *>(a.W)[(size_t)(j0 + r) * kRowVec + cidx];
-    *reinterpret_cast<float4 *>(&Qs[r * kPitch + cidx * 4]) = qv;
-    *reinterpret_cast<float4 *>(&Ws[r * kPitch + cidx * 4]) = wv;
-  }
-  __syncthreads();
   const int tx = tid & 15, ty = tid >> 4;  // rows tx+16r, queries ty+16q
   float acc[4][4];
 #pragma unroll
   for (int qq = 0; qq < 4; ++qq)
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[qq][r] = 0.f;
-#pragma unroll 4
-  for (int k4 = 0; k4 < kRowVec; ++k4) {
-    float4 qv[4], wv[4];
 #pragma unroll
-    for (int qq = 0; qq < 4; ++qq)
-      qv[qq] = *reinterpret_cast<const float4 *>(&Qs[(ty + 16 * qq) * kPitch + k4 * 4]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      wv[r] = *reinterpret_cast<const float4 *>(&Ws[(tx + 16 * r) * kPitch + k4 * 4]);
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s = acc[qq][r];
-        s = __fmaf_rn(wv[r].x, qv[qq].x, s);
-        s = __fmaf_rn(wv[r].y, qv[qq].y, s);
-        s = __fmaf_rn(wv[r].z, qv[qq].z, s);
-        s = __fmaf_rn(wv[r].w, qv[qq].w, s);
-        acc[qq][r] = s;
+  for (int k0 = 0; k0 < kRowV; k0 += kSV) {  // (one pass up to 128)
+    if (k0) __syncthreads();                 // the previous slice has been read
+    // stage: 64 rows x kSV float4 per tile (128: 32 float4 a row, 8 per thread and tile)
+    for (int e = tid; e < kTile * kSV; e += 256) {
+      const int r = e / kSV, cidx = e % kSV;
+      float4 qv = make_float4(0.f, 0.f, 0.f, 0.f), wv = qv;
+      if (q0 + r < a.nq) {
+        const int src = a.qrows ? a.qrows[q0 + r] : q0 + r;
+        qv = reinterpret_cast<const float4 *>(a.Q)[(size_t)src * kRowV + k0 + cidx];
       }
+      if (j0 + r < a.n) wv = reinterpret_cast<const float4 *>(a.W)[(size_t)(j0 + r) * kRowV + k0 + cidx];
+      *reinterpret_cast<float4 *>(&Qs[r * kPitch + cidx * 4]) = qv;
+      *reinterpret_cast<float4 *>(&Ws[r * kPitch + cidx * 4]) = wv;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int k4 = 0; k4 < kSV; ++k4) {
+      float4 qv[4], wv[4];
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq)
+        qv[qq] = *reinterpret_cast<const float4 *>(&Qs[(ty + 16 * qq) * kPitch + k4 * 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        wv[r] = *reinterpret_cast<const float4 *>(&Ws[(tx + 16 * r) * kPitch + k4 * 4]);
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float s = acc[qq][r];
+          s = __fmaf_rn(wv[r].x, qv[qq].x, s);
+          s = __fmaf_rn(wv[r].y, qv[qq].y, s);
+          s = __fmaf_rn(wv[r].z, qv[qq].z, s);
+          s = __fmaf_rn(wv[r].w, qv[qq].w, s);
+          acc[qq][r] = s;
+        }
+    }
   }
 #pragma unroll
   for (int qq = 0; qq < 4; ++qq) {
@@ -125,10 +195,19 @@ __global__ __launch_bounds__(256) void k_scores(ScoreArgs a) {
       const int j = j0 + tx + 16 * r;
       if (j >= a.n) continue;
       float s = acc[qq][r];
-      if (a.use_head) s = rating_from_cosine<kAct>(s, a.hs, a.hb);
+      if (a.use_head) s = rating_from_cosine<kAct>(s, a.hs, a.hb, a.act);
       a.out[(size_t)q * a.ld + j] = s;
     }
   }
+}
+
+template <int kAct>
+__global__ __launch_bounds__(256) void k_scores(ScoreArgs a) {
+  scores_body<kAct, kDim>(a);
+}
+template <int kD>  // the widths other than 128, any activation (a.act)
+__global__ __launch_bounds__(256) void k_scores_w(ScoreArgs a) {
+  scores_body<-1, kD>(a);
 }
 
 // ------------------------------------------------------------------------------------
@@ -364,23 +443,36 @@ __global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a) {
 // ------------------------------------------------------------------------------------
 // predict on explicit pairs (model.predict([user_arr, anime_arr]))
 // ------------------------------------------------------------------------------------
+// a row group (kD / 4 lanes) per pair; kAct < 0: the run-time activation `act`
+template <int kAct, int kD>
+__device__ __forceinline__ void predict_pairs_body(const float *U, const float *A, const int32_t *ui,
+                                                   const int32_t *ai, int n, float hs, float hb, int act, float *p) {
+  constexpr int kG = kD / 4;
+  const int l = threadIdx.x & (kG - 1);
+  const int i = blockIdx.x * (256 / kG) + (threadIdx.x / kG);
+  if (i >= n) return;
+  const float4 u = reinterpret_cast<const float4 *>(U)[(size_t)ui[i] * kG + l];
+  const float4 x = reinterpret_cast<const float4 *>(A)[(size_t)ai[i] * kG + l];
+  const float su = group_sum<kG>(u.x * u.x + u.y * u.y + u.z * u.z + u.w * u.w);
+  const float sa = group_sum<kG>(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
+  const float dd = group_sum<kG>(u.x * x.x + u.y * x.y + u.z * x.z + u.w * x.w);
+  if (l == 0) {
+    const float ru = 1.0f / sqrtf(fmaxf(su, kL2nEps));
+    const float ra = 1.0f / sqrtf(fmaxf(sa, kL2nEps));
+    p[i] = act_any<kAct>(dd * ru * ra * hs + hb, act);
+  }
+}
 template <int kAct>
 __global__ __launch_bounds__(256) void k_predict_pairs(const float *U, const float *A,
                                                        const int32_t *ui, const int32_t *ai, int n,
                                                        float hs, float hb, float *p) {
-  const int l = threadIdx.x & 31;
-  const int i = blockIdx.x * 8 + (threadIdx.x >> 5);
-  if (i >= n) return;
-  const float4 u = reinterpret_cast<const float4 *>(U)[(size_t)ui[i] * kRowVec + l];
-  const float4 x = reinterpret_cast<const float4 *>(A)[(size_t)ai[i] * kRowVec + l];
-  const float su = halfwave_sum(u.x * u.x + u.y * u.y + u.z * u.z + u.w * u.w);
-  const float sa = halfwave_sum(x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w);
-  const float dd = halfwave_sum(u.x * x.x + u.y * x.y + u.z * x.z + u.w * x.w);
-  if (l == 0) {
-    const float ru = 1.0f / sqrtf(fmaxf(su, kL2nEps));
-    const float ra = 1.0f / sqrtf(fmaxf(sa, kL2nEps));
-    p[i] = act_fwd<kAct>(dd * ru * ra * hs + hb);
-  }
+  predict_pairs_body<kAct, kDim>(U, A, ui, ai, n, hs, hb, 0, p);
+}
+template <int kD>
+__global__ __launch_bounds__(256) void k_predict_pairs_w(const float *U, const float *A, const int32_t *ui,
+                                                         const int32_t *ai, int n, float hs, float hb, int act,
+                                                         float *p) {
+  predict_pairs_body<-1, kD>(U, A, ui, ai, n, hs, hb, act, p);
 }
 
 __global__ void k_fill_self(const int32_t *queries, int nq, int32_t *self, int enable) {
@@ -395,41 +487,57 @@ static inline void head_affine(const anirec_head *h, float *hs, float *hb) { hea
 // each thread runs the DEFINED k-ordered fma chain of one (key, query) pair — the same arithmetic as k_scores,
 // bit for bit — so the 64 x 64 tile kernel's 63/64 wasted lanes disappear and the pass is HBM-bound.
 constexpr int kFewQ = 16;
-constexpr int kFewPitch = kDim + 4;
-template <int kAct>
-__global__ __launch_bounds__(256) void k_scores_few(ScoreArgs a) {
+// Rows are staged a slice (ScoreGeom) at a time.  At 256 a (key, query) pair's chain value waits in its own output
+// element between the two slices: written and read back by the same thread, it goes on bit for bit.
+template <int kAct, int kD>
+__device__ __forceinline__ void scores_few_body(const ScoreArgs &a) {
+  constexpr int kS = ScoreGeom<kD>::kS, kSV = ScoreGeom<kD>::kSV, kFewPitch = ScoreGeom<kD>::kPitch,
+                kRowV = ScoreGeom<kD>::kRowV;
   __shared__ __attribute__((aligned(16))) float Ws[64 * kFewPitch];
-  __shared__ __attribute__((aligned(16))) float Qs[kFewQ * kDim];
+  __shared__ __attribute__((aligned(16))) float Qs[kFewQ * kS];
   const int tid = threadIdx.x;
   const int j0 = blockIdx.x * 64;
-  for (int e = tid; e < 64 * kRowVec; e += 256) {
-    const int r = e >> 5, c = e & 31;
-    float4 wv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (j0 + r < a.n) wv = reinterpret_cast<const float4 *>(a.W)[(size_t)(j0 + r) * kRowVec + c];
-    *reinterpret_cast<float4 *>(&Ws[r * kFewPitch + c * 4]) = wv;
-  }
-  for (int e = tid; e < a.nq * kRowVec; e += 256) {
-    const int q = e >> 5, c = e & 31;
-    const size_t src = a.qrows ? (size_t)a.qrows[q] : (size_t)q;
-    *reinterpret_cast<float4 *>(&Qs[q * kDim + c * 4]) = reinterpret_cast<const float4 *>(a.Q)[src * kRowVec + c];
-  }
-  __syncthreads();
   const int key = tid & 63, j = j0 + key;
-  for (int q = tid >> 6; q < a.nq; q += 4) {
-    const float4 *w4 = reinterpret_cast<const float4 *>(&Ws[key * kFewPitch]);
-    const float4 *q4 = reinterpret_cast<const float4 *>(&Qs[q * kDim]);
-    float s = 0.f;
-#pragma unroll 8
-    for (int k4 = 0; k4 < kRowVec; ++k4) {
-      const float4 x = w4[k4], y = q4[k4];
-      s = __fmaf_rn(x.x, y.x, s);
-      s = __fmaf_rn(x.y, y.y, s);
-      s = __fmaf_rn(x.z, y.z, s);
-      s = __fmaf_rn(x.w, y.w, s);
+#pragma unroll
+  for (int k0 = 0; k0 < kRowV; k0 += kSV) {  // (one pass up to 128)
+    if (k0) __syncthreads();
+    for (int e = tid; e < 64 * kSV; e += 256) {
+      const int r = e / kSV, c = e % kSV;
+      float4 wv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (j0 + r < a.n) wv = reinterpret_cast<const float4 *>(a.W)[(size_t)(j0 + r) * kRowV + k0 + c];
+      *reinterpret_cast<float4 *>(&Ws[r * kFewPitch + c * 4]) = wv;
     }
-    if (a.use_head) s = rating_from_cosine<kAct>(s, a.hs, a.hb);
-    if (j < a.n) a.out[(size_t)q * a.ld + j] = s;
+    for (int e = tid; e < a.nq * kSV; e += 256) {
+      const int q = e / kSV, c = e % kSV;
+      const size_t src = a.qrows ? (size_t)a.qrows[q] : (size_t)q;
+      *reinterpret_cast<float4 *>(&Qs[q * kS + c * 4]) = reinterpret_cast<const float4 *>(a.Q)[src * kRowV + k0 + c];
+    }
+    __syncthreads();
+    for (int q = tid >> 6; q < a.nq; q += 4) {
+      const float4 *w4 = reinterpret_cast<const float4 *>(&Ws[key * kFewPitch]);
+      const float4 *q4 = reinterpret_cast<const float4 *>(&Qs[q * kS]);
+      float s = 0.f;
+      if (k0 && j < a.n) s = a.out[(size_t)q * a.ld + j];
+#pragma unroll 8
+      for (int k4 = 0; k4 < kSV; ++k4) {
+        const float4 x = w4[k4], y = q4[k4];
+        s = __fmaf_rn(x.x, y.x, s);
+        s = __fmaf_rn(x.y, y.y, s);
+        s = __fmaf_rn(x.z, y.z, s);
+        s = __fmaf_rn(x.w, y.w, s);
+      }
+      if (k0 + kSV >= kRowV && a.use_head) s = rating_from_cosine<kAct>(s, a.hs, a.hb, a.act);
+      if (j < a.n) a.out[(size_t)q * a.ld + j] = s;
+    }
   }
+}
+template <int kAct>
+__global__ __launch_bounds__(256) void k_scores_few(ScoreArgs a) {
+  scores_few_body<kAct, kDim>(a);
+}
+template <int kD>
+__global__ __launch_bounds__(256) void k_scores_few_w(ScoreArgs a) {
+  scores_few_body<-1, kD>(a);
 }
 
 // scratch of the sliced select: at most kSelMaxBlocks slice winners lists of ANIREC_MAX_TOPK entries
@@ -472,8 +580,23 @@ static int launch_select(SelectArgs sa, void *tmp, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-// act: the activation of a head (use_head != 0); plain cosine scores take the default instantiation
-static int launch_scores(const ScoreArgs &a, hipStream_t s, int32_t act = ANIREC_ACT_SIGMOID) {
+// act: the activation of a head (use_head != 0); plain cosine scores take the default instantiation.  dim: the row
+// width of a.Q and a.W
+static int launch_scores(const ScoreArgs &a0, hipStream_t s, int32_t act = ANIREC_ACT_SIGMOID, int dim = kDim) {
+  ScoreArgs a = a0;
+  a.act = act;
+  if (dim != kDim) {
+    with_width(dim, [&](auto kd) {
+      constexpr int kD = decltype(kd)::value;
+      if (a.nq <= kFewQ) {
+        hipLaunchKernelGGL(k_scores_few_w<kD>, dim3((a.n + 63) / 64), dim3(256), 0, s, a);
+      } else {
+        dim3 grid((a.n + kTile - 1) / kTile, (a.nq + kTile - 1) / kTile);
+        hipLaunchKernelGGL(k_scores_w<kD>, grid, dim3(256), 0, s, a);
+      }
+    });
+    return (int)hipGetLastError();
+  }
   with_act(act, [&](auto k) {
     constexpr int kAct = decltype(k)::value;
     if (a.nq <= kFewQ) {
@@ -492,20 +615,26 @@ using namespace anirec;
 
 extern "C" {
 
+// Every entry point without a `dim` is its _w twin at ANIREC_DIM.
 int anirec_rownorm(const float *W, int32_t n, float *What, void *stream) {
-  if (!W || !What || n < 0) return ANIREC_EINVAL;
+  return anirec_rownorm_w(W, n, ANIREC_DIM, What, stream);
+}
+
+int anirec_rownorm_w(const float *W, int32_t n, int32_t dim, float *What, void *stream) {
+  if (!W || !What || n < 0 || !dim_ok(dim)) return ANIREC_EINVAL;
   if (n == 0) return ANIREC_OK;
-  int blocks = (n + 7) / 8;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_rownorm<0>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, W, nullptr, n,
-                     What);
+  launch_rownorm<0>(W, nullptr, n, What, dim, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
 
 int anirec_cosine_scores(const float *What, int32_t n, int32_t q, float *scores, void *stream) {
-  if (!What || !scores || n < 1 || q < 0 || q >= n) return ANIREC_EINVAL;
+  return anirec_cosine_scores_w(What, n, ANIREC_DIM, q, scores, stream);
+}
+
+int anirec_cosine_scores_w(const float *What, int32_t n, int32_t dim, int32_t q, float *scores, void *stream) {
+  if (!What || !scores || n < 1 || q < 0 || q >= n || !dim_ok(dim)) return ANIREC_EINVAL;
   ScoreArgs a;
-  a.Q = What + (size_t)q * kDim;
+  a.Q = What + (size_t)q * dim;
   a.qrows = nullptr;
   a.nq = 1;
   a.W = What;
@@ -514,7 +643,7 @@ int anirec_cosine_scores(const float *What, int32_t n, int32_t q, float *scores,
   a.ld = (size_t)n;
   a.use_head = 0;
   a.hs = a.hb = 0.f;
-  return launch_scores(a, (hipStream_t)stream);
+  return launch_scores(a, (hipStream_t)stream, ANIREC_ACT_SIGMOID, dim);
 }
 
 // workspace: self[nq] ints (256-aligned) + score rows for a batch of queries
@@ -530,7 +659,14 @@ size_t anirec_topk_workspace_bytes(int32_t n, int32_t nq) {
 int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int32_t nq,
                        const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
                        float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
-  if (!What || !queries || !out_idx || !out_score || !workspace) return ANIREC_EINVAL;
+  return anirec_cosine_topk_w(What, n, ANIREC_DIM, queries, nq, keep, exclude_self, k, out_idx, out_score, workspace,
+                              workspace_bytes, stream);
+}
+
+int anirec_cosine_topk_w(const float *What, int32_t n, int32_t dim, const int32_t *queries, int32_t nq,
+                         const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                         float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
+  if (!What || !queries || !out_idx || !out_score || !workspace || !dim_ok(dim)) return ANIREC_EINVAL;
   if (n < 1 || nq < 0 || k < 1 || k > ANIREC_MAX_TOPK) return ANIREC_EINVAL;
   if (nq == 0) return ANIREC_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -556,7 +692,7 @@ int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int
     a.ld = (size_t)n;
     a.use_head = 0;
     a.hs = a.hb = 0.f;
-    int e = launch_scores(a, s);
+    int e = launch_scores(a, s, ANIREC_ACT_SIGMOID, dim);
     if (e) return e;
     SelectArgs sa;
     sa.scores = buf;
@@ -579,10 +715,25 @@ int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int
 int anirec_predict_pairs_act(const float *U, const float *A, const int32_t *user_idx,
                              const int32_t *anime_idx, int32_t n, const anirec_head *head, int32_t activation,
                              float *p, void *stream) {
-  if (!U || !A || !user_idx || !anime_idx || !head || !p || n < 0 || !act_ok(activation)) return ANIREC_EINVAL;
+  return anirec_predict_pairs_w(U, A, ANIREC_DIM, user_idx, anime_idx, n, head, activation, p, stream);
+}
+
+int anirec_predict_pairs_w(const float *U, const float *A, int32_t dim, const int32_t *user_idx,
+                           const int32_t *anime_idx, int32_t n, const anirec_head *head, int32_t activation,
+                           float *p, void *stream) {
+  if (!U || !A || !user_idx || !anime_idx || !head || !p || n < 0 || !act_ok(activation) || !dim_ok(dim))
+    return ANIREC_EINVAL;
   if (n == 0) return ANIREC_OK;
   float hs, hb;
   head_affine(head, &hs, &hb);
+  if (dim != kDim) {
+    with_width(dim, [&](auto kd) {
+      constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
+      hipLaunchKernelGGL(k_predict_pairs_w<kD>, dim3((n + kRpb - 1) / kRpb), dim3(256), 0, (hipStream_t)stream, U, A,
+                         user_idx, anime_idx, n, hs, hb, (int)activation, p);
+    });
+    return (int)hipGetLastError();
+  }
   with_act(activation, [&](auto k) {
     hipLaunchKernelGGL(k_predict_pairs<decltype(k)::value>, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, U, A,
                        user_idx, anime_idx, n, hs, hb, p);
@@ -598,13 +749,17 @@ int anirec_predict_pairs(const float *U, const float *A, const int32_t *user_idx
 
 // workspace of predict_grid / predict_topk: normalised copies of the query users and of A,
 // plus (topk) a batch of rating rows.
-static size_t norm_bytes(int32_t n_anime, int32_t n_users) {
-  return ((size_t)n_anime + (size_t)n_users) * kDim * 4;
+static size_t norm_bytes(int32_t n_anime, int32_t n_users, int32_t dim) {
+  return ((size_t)n_anime + (size_t)n_users) * dim * 4;
 }
 
 size_t anirec_predict_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t topk) {
-  if (n_anime < 1 || n_users < 1) return 0;
-  size_t b = norm_bytes(n_anime, n_users);
+  return anirec_predict_workspace_bytes_w(n_anime, n_users, topk, ANIREC_DIM);
+}
+
+size_t anirec_predict_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t topk, int32_t dim) {
+  if (n_anime < 1 || n_users < 1 || !dim_ok(dim)) return 0;
+  size_t b = norm_bytes(n_anime, n_users, dim);
   if (topk) {
     size_t qb = (size_t)n_users < 4096 ? (size_t)n_users : 4096;
     b += kSelTmpBytes + qb * (size_t)n_anime * 4;
@@ -622,18 +777,23 @@ int anirec_predict_grid(const float *U, const float *A, int32_t n_anime, const i
 int anirec_predict_grid_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                             int32_t n_users, const anirec_head *head, int32_t activation, float *out,
                             void *workspace, size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out || !workspace || n_anime < 1 || n_users < 0 || !act_ok(activation))
+  return anirec_predict_grid_w(U, A, ANIREC_DIM, n_anime, users, n_users, head, activation, out, workspace,
+                               workspace_bytes, stream);
+}
+
+int anirec_predict_grid_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                          int32_t n_users, const anirec_head *head, int32_t activation, float *out,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out || !workspace || n_anime < 1 || n_users < 0 || !act_ok(activation) ||
+      !dim_ok(dim))
     return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
-  if (workspace_bytes < norm_bytes(n_anime, n_users)) return ANIREC_EWORKSPACE;
+  if (workspace_bytes < norm_bytes(n_anime, n_users, dim)) return ANIREC_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   float *Ah = (float *)workspace;
-  float *Uh = Ah + (size_t)n_anime * kDim;
-  int b1 = (n_anime + 7) / 8, b2 = (n_users + 7) / 8;
-  if (b1 > 4096) b1 = 4096;
-  if (b2 > 4096) b2 = 4096;
-  hipLaunchKernelGGL(k_rownorm<1>, dim3(b1), dim3(256), 0, s, A, nullptr, n_anime, Ah);
-  hipLaunchKernelGGL(k_rownorm<1>, dim3(b2), dim3(256), 0, s, U, users, n_users, Uh);
+  float *Uh = Ah + (size_t)n_anime * dim;
+  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
+  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
   ANIREC_HIP_CHECK(hipGetLastError());
   ScoreArgs a;
   a.Q = Uh;
@@ -645,7 +805,7 @@ int anirec_predict_grid_act(const float *U, const float *A, int32_t n_anime, con
   a.ld = (size_t)n_anime;
   a.use_head = 1;
   head_affine(head, &a.hs, &a.hb);
-  return launch_scores(a, s, activation);
+  return launch_scores(a, s, activation, dim);
 }
 
 int anirec_predict_topk(const float *U, const float *A, int32_t n_anime, const int32_t *users,
@@ -660,23 +820,29 @@ int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, con
                             int32_t n_users, const anirec_head *head, int32_t activation,
                             const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
                             size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation)) return ANIREC_EINVAL;
+  return anirec_predict_topk_w(U, A, ANIREC_DIM, n_anime, users, n_users, head, activation, watched, k, out_idx, out_p,
+                               workspace, workspace_bytes, stream);
+}
+
+int anirec_predict_topk_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                          int32_t n_users, const anirec_head *head, int32_t activation,
+                          const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation) || !dim_ok(dim))
+    return ANIREC_EINVAL;
   if (n_anime < 1 || n_users < 0 || k < 1 || k > ANIREC_MAX_TOPK) return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
-  const size_t nb = norm_bytes(n_anime, n_users) + kSelTmpBytes;
+  const size_t nb = norm_bytes(n_anime, n_users, dim) + kSelTmpBytes;
   if (workspace_bytes < nb + (size_t)n_anime * 4) return ANIREC_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   float *Ah = (float *)workspace;
-  float *Uh = Ah + (size_t)n_anime * kDim;
-  void *sel_tmp = Uh + (size_t)n_users * kDim;
+  float *Uh = Ah + (size_t)n_anime * dim;
+  void *sel_tmp = Uh + (size_t)n_users * dim;
   float *buf = (float *)((char *)sel_tmp + kSelTmpBytes);
   size_t qb = (workspace_bytes - nb) / ((size_t)n_anime * 4);
   if (qb > (size_t)n_users) qb = n_users;
-  int b1 = (n_anime + 7) / 8, b2 = (n_users + 7) / 8;
-  if (b1 > 4096) b1 = 4096;
-  if (b2 > 4096) b2 = 4096;
-  hipLaunchKernelGGL(k_rownorm<1>, dim3(b1), dim3(256), 0, s, A, nullptr, n_anime, Ah);
-  hipLaunchKernelGGL(k_rownorm<1>, dim3(b2), dim3(256), 0, s, U, users, n_users, Uh);
+  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
+  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
   ANIREC_HIP_CHECK(hipGetLastError());
   const int wwords = (n_anime + 31) / 32;
   float hs, hb;
@@ -684,7 +850,7 @@ int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, con
   for (size_t q0 = 0; q0 < (size_t)n_users; q0 += qb) {
     const int cnt = (int)((size_t)n_users - q0 < qb ? (size_t)n_users - q0 : qb);
     ScoreArgs a;
-    a.Q = Uh + q0 * kDim;
+    a.Q = Uh + q0 * dim;
     a.qrows = nullptr;
     a.nq = cnt;
     a.W = Ah;
@@ -694,7 +860,7 @@ int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, con
     a.use_head = 1;
     a.hs = hs;
     a.hb = hb;
-    int e = launch_scores(a, s, activation);
+    int e = launch_scores(a, s, activation, dim);
     if (e) return e;
     SelectArgs sa;
     sa.scores = buf;
@@ -1178,7 +1344,14 @@ size_t anirec_topk_large_workspace_bytes(int32_t n, int32_t nq, int32_t k) {
 int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *queries, int32_t nq, const uint8_t *keep,
                              int32_t exclude_self, int32_t k, int32_t *out_idx, float *out_score, void *workspace,
                              size_t workspace_bytes, void *stream) {
-  if (!What || !queries || !out_idx || !out_score || !workspace) return ANIREC_EINVAL;
+  return anirec_cosine_topk_large_w(What, n, ANIREC_DIM, queries, nq, keep, exclude_self, k, out_idx, out_score,
+                                    workspace, workspace_bytes, stream);
+}
+
+int anirec_cosine_topk_large_w(const float *What, int32_t n, int32_t dim, const int32_t *queries, int32_t nq,
+                               const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                               float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
+  if (!What || !queries || !out_idx || !out_score || !workspace || !dim_ok(dim)) return ANIREC_EINVAL;
   if (n < 1 || nq < 0 || k < 1) return ANIREC_EINVAL;
   if (nq == 0) return ANIREC_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -1205,7 +1378,7 @@ int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *querie
     a.ld = (size_t)n;
     a.use_head = 0;
     a.hs = a.hb = 0.f;
-    int e = launch_scores(a, s);
+    int e = launch_scores(a, s, ANIREC_ACT_SIGMOID, dim);
     if (e) return e;
     SelectArgs &sa = la.s;
     sa.scores = buf;
@@ -1226,32 +1399,42 @@ int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *querie
 }
 
 size_t anirec_predict_topk_large_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t k) {
-  if (n_anime < 1 || n_users < 1 || k < 1) return 0;
-  return norm_bytes(n_anime, n_users) + lk_batch_bytes(n_anime, k, (size_t)n_users < 4096 ? (size_t)n_users : 4096);
+  return anirec_predict_topk_large_workspace_bytes_w(n_anime, n_users, k, ANIREC_DIM);
+}
+
+size_t anirec_predict_topk_large_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t k, int32_t dim) {
+  if (n_anime < 1 || n_users < 1 || k < 1 || !dim_ok(dim)) return 0;
+  return norm_bytes(n_anime, n_users, dim) + lk_batch_bytes(n_anime, k, (size_t)n_users < 4096 ? (size_t)n_users : 4096);
 }
 
 int anirec_predict_topk_large_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                                   int32_t n_users, const anirec_head *head, int32_t activation,
                                   const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
                                   size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation)) return ANIREC_EINVAL;
+  return anirec_predict_topk_large_w(U, A, ANIREC_DIM, n_anime, users, n_users, head, activation, watched, k, out_idx,
+                                     out_p, workspace, workspace_bytes, stream);
+}
+
+int anirec_predict_topk_large_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                                int32_t n_users, const anirec_head *head, int32_t activation,
+                                const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation) || !dim_ok(dim))
+    return ANIREC_EINVAL;
   if (n_anime < 1 || n_users < 0 || k < 1) return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
-  const size_t fixed = norm_bytes(n_anime, n_users) + kLkHistBytes + kLkCntBytes;
+  const size_t fixed = norm_bytes(n_anime, n_users, dim) + kLkHistBytes + kLkCntBytes;
   const size_t pq = lk_per_query(n_anime, k);
   if (workspace_bytes < fixed + pq) return ANIREC_EWORKSPACE;
   size_t qb = (workspace_bytes - fixed) / pq;
   if (qb > (size_t)n_users) qb = n_users;
   hipStream_t s = (hipStream_t)stream;
   float *Ah = (float *)workspace;
-  float *Uh = Ah + (size_t)n_anime * kDim;
+  float *Uh = Ah + (size_t)n_anime * dim;
   LkArgs la;
-  float *buf = lk_carve(la, (char *)(Uh + (size_t)n_users * kDim), n_anime, k, qb);
-  int b1 = (n_anime + 7) / 8, b2 = (n_users + 7) / 8;
-  if (b1 > 4096) b1 = 4096;
-  if (b2 > 4096) b2 = 4096;
-  hipLaunchKernelGGL(k_rownorm<1>, dim3(b1), dim3(256), 0, s, A, nullptr, n_anime, Ah);
-  hipLaunchKernelGGL(k_rownorm<1>, dim3(b2), dim3(256), 0, s, U, users, n_users, Uh);
+  float *buf = lk_carve(la, (char *)(Uh + (size_t)n_users * dim), n_anime, k, qb);
+  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
+  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
   ANIREC_HIP_CHECK(hipGetLastError());
   const int wwords = (n_anime + 31) / 32;
   float hs, hb;
@@ -1259,7 +1442,7 @@ int anirec_predict_topk_large_act(const float *U, const float *A, int32_t n_anim
   for (size_t q0 = 0; q0 < (size_t)n_users; q0 += qb) {
     const int cnt = (int)((size_t)n_users - q0 < qb ? (size_t)n_users - q0 : qb);
     ScoreArgs a;
-    a.Q = Uh + q0 * kDim;
+    a.Q = Uh + q0 * dim;
     a.qrows = nullptr;
     a.nq = cnt;
     a.W = Ah;
@@ -1269,7 +1452,7 @@ int anirec_predict_topk_large_act(const float *U, const float *A, int32_t n_anim
     a.use_head = 1;
     a.hs = hs;
     a.hb = hb;
-    int e = launch_scores(a, s, activation);
+    int e = launch_scores(a, s, activation, dim);
     if (e) return e;
     SelectArgs &sa = la.s;
     sa.scores = buf;

@@ -60,6 +60,7 @@ struct StepPub {
 
 struct TrainWs {
   int cap, capC, arena_steps;
+  int dim;                      // row width of the tables (floats): ANIREC_DIM unless carved by a *_w entry point
   float *su, *sa;               // [cap] row square sums from fwd
   float *dy;                    // [cap] d loss / d y from head
   // everything below this line is double-buffered by step parity (index p = step & 1)
@@ -73,7 +74,7 @@ struct TrainWs {
   float *lzring;                // [ANIREC_LAZY_WINDOW][2] lazy: {n, bce mean} of the open window's steps (bce: the data
                                 //   term of the descriptor's loss, whichever it is)
   float *regpart;               // [2][2][ANIREC_ADAM_BLOCKS]: user-row / anime-row sum(W^2) partials
-  float *P;                     // [2][2*capC][128] chunk partial rows
+  float *P;                     // [2][2*capC][dim] chunk partial rows
   float *S;                     // [2][2*capC]      chunk self-coefficient sums
   // arena slot s: nchunks[2] (4 ints), sidx[2][cap], oth[2][cap], chunks[2][capC] (int4)
   char *arena;
@@ -90,8 +91,9 @@ __host__ inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) /
 
 __host__ __device__ inline int packet_cap(int max_batch) { return (max_batch + 3) & ~3; }
 
-__host__ inline TrainWs carve(void *base, int cap, int arena_steps) {
+__host__ inline TrainWs carve(void *base, int cap, int arena_steps, int dim = kDim) {
   TrainWs w;
+  w.dim = dim;
   w.cap = cap;
   w.capC = chunk_capacity(cap);
   w.arena_steps = arena_steps;
@@ -110,7 +112,7 @@ __host__ inline TrainWs carve(void *base, int cap, int arena_steps) {
   w.pub = (StepPub *)take(sizeof(StepPub) * 2);
   w.sel = (int32_t *)take(sizeof(int32_t) * 4);
   w.regpart = (float *)take(sizeof(float) * 2 * 2 * ANIREC_ADAM_BLOCKS);
-  w.P = (float *)take(sizeof(float) * 2 * 2 * (size_t)w.capC * kDim);
+  w.P = (float *)take(sizeof(float) * 2 * 2 * (size_t)w.capC * dim);
   w.S = (float *)take(sizeof(float) * 2 * 2 * (size_t)w.capC);
   w.slot_bytes = align_up(16) + 2 * align_up(sizeof(int32_t) * 2 * (size_t)cap) +
                  align_up(sizeof(int4) * 2 * (size_t)w.capC);
@@ -384,18 +386,20 @@ __device__ __forceinline__ void tick(unsigned long long *ticks, int which) {
   if (threadIdx.x == 0) ticks[2 * (size_t)blockIdx.x + which] = __builtin_amdgcn_s_memrealtime();
 }
 
-// One half-wave per rating.  Returns dot products through references; all 32 lanes of
-// the half hold the totals.
+// One row group (kD / 4 lanes: a half-wave at 128) per rating.  Returns dot products through references; all lanes
+// of the group hold the totals.
+template <int kD = kDim>
 __device__ __forceinline__ void pair_dots(const float4 *W4, int urow, int arow, int l32, float &su,
                                           float &sa, float &dd) {
-  const float4 u = W4[(size_t)urow * kRowVec + l32];
-  const float4 a = W4[(size_t)arow * kRowVec + l32];
+  constexpr int kG = kD / 4;
+  const float4 u = W4[(size_t)urow * kG + l32];
+  const float4 a = W4[(size_t)arow * kG + l32];
   float s0 = u.x * u.x + u.y * u.y + u.z * u.z + u.w * u.w;
   float s1 = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
   float s2 = u.x * a.x + u.y * a.y + u.z * a.z + u.w * a.w;
-  su = halfwave_sum(s0);
-  sa = halfwave_sum(s1);
-  dd = halfwave_sum(s2);
+  su = group_sum<kG>(s0);
+  sa = group_sum<kG>(s1);
+  dd = group_sum<kG>(s2);
 }
 
 __device__ __forceinline__ float cos_from_dots(float su, float sa, float dd) {
@@ -409,19 +413,21 @@ __device__ __forceinline__ int ld_i32(const int32_t *p) {
   return __hip_atomic_load(const_cast<int32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the forward pass of one workgroup: a half-wave per rating
+// the forward pass of one workgroup: a row group (a half-wave at 128) per rating
+template <int kD = kDim>
 __device__ __forceinline__ void fwd_block(const FwdArgs &a, const anirec_step sc, int vblk, int step) {
+  constexpr int kG = kD / 4;
   const int nb = min(sc.count, a.cap);
-  const int per_blk = blockDim.x >> 5;
-  const int i = vblk * per_blk + (threadIdx.x >> 5);
+  const int per_blk = blockDim.x / kG;
+  const int i = vblk * per_blk + (threadIdx.x / kG);
   if (vblk == 0 && threadIdx.x == 0) a.pk_count[0] = nb;
   if (i >= nb) return;
-  const int l32 = threadIdx.x & 31;
+  const int l32 = threadIdx.x & (kG - 1);
   const int g = sc.start + i;
   const int ur = a.user_idx[g];
   const int ar = a.anime_idx[g] + a.n_user_rows;
   float su, sa, dd;
-  pair_dots(reinterpret_cast<const float4 *>(a.W), ur, ar, l32, su, sa, dd);
+  pair_dots<kD>(reinterpret_cast<const float4 *>(a.W), ur, ar, l32, su, sa, dd);
   if (l32 == 0) {
     const float c = cos_from_dots(su, sa, dd);
     const float t = a.rating[g];
@@ -443,6 +449,12 @@ __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
   const int step = a.state->step_fwd;
   fwd_block(a, a.sched[step], blockIdx.x, step);
   tick(a.ticks, 1);
+}
+// the same at another width (anirec_train_fwd_w): 1024 / kD ratings per workgroup
+template <int kD>
+__global__ __launch_bounds__(256) void k_fwd_w(FwdArgs a) {
+  const int step = a.state->step_fwd;
+  fwd_block<kD>(a, a.sched[step], blockIdx.x, step);
 }
 
 // Multi-GPU only: (mean, M2) of this rank's z = w*c + b values, two-pass, written next to the
@@ -757,87 +769,120 @@ struct BwdArgs {
   unsigned long long *ticks;
 };
 
-// what one half-wave needs for its chunk, requested as early as possible
+// How a chunk (<= ANIREC_CHUNK contributions) sits on the kD / 4 lanes of its row group: lane l holds contributions
+// l, l + kG, ... — one per lane at 128 (a half-wave) and at 256 (a wave, the upper half idle), four / two at 32 / 64.
+template <int kD>
+struct BwdGeom {
+  static constexpr int kG = kD / 4;                                              // lanes of a row group
+  static constexpr int kC = kG >= ANIREC_CHUNK ? 1 : ANIREC_CHUNK / kG;          // contributions a lane holds
+  static constexpr int kRpb = 256 / kG;                                          // row groups per workgroup
+};
+
+// element `slot` (group-uniform) of a lane's per-contribution values; one element: the value itself
+template <int kC, typename T>
+__device__ __forceinline__ T pick(const T (&v)[kC], int slot) {
+  T r = v[0];
+#pragma unroll
+  for (int k = 1; k < kC; ++k) r = slot == k ? v[k] : r;
+  return r;
+}
+
+// what one row group needs for its chunk, requested as early as possible
+template <int kC>
 struct BwdPre {
   bool active;
-  int T, c, len, i, o;
+  int T, c, len, i[kC], o[kC];
   int4 rec;
-  float ci, dyi, su, sa;
+  float ci[kC], dyi[kC], su[kC], sa[kC];
   float4 r0[4];
 };
 
-__device__ __forceinline__ void bwd_prefetch(const BwdArgs &a, int slot, int vblk, BwdPre &x) {
-  const int l = threadIdx.x & 31;
-  const int hw = vblk * 8 + (threadIdx.x >> 5);
+template <int kD = kDim>
+__device__ __forceinline__ void bwd_prefetch(const BwdArgs &a, int slot, int vblk, BwdPre<BwdGeom<kD>::kC> &x) {
+  constexpr int kG = BwdGeom<kD>::kG, kC = BwdGeom<kD>::kC;
+  const int l = threadIdx.x & (kG - 1);
+  const int hw = vblk * BwdGeom<kD>::kRpb + (threadIdx.x / kG);
   x.T = hw >= a.capC ? 1 : 0;
   x.c = hw - x.T * a.capC;
   Slot sl = slot_of(a.arena, a.slot_bytes, a.cap, a.capC, slot);
   const float4 *W4 = reinterpret_cast<const float4 *>(a.W);
   x.active = hw < 2 * a.capC && x.c < sl.nchunks[x.T];
-  x.len = x.i = x.o = 0;
+  x.len = 0;
   x.rec = make_int4(0, 0, 0, 0);
-  x.ci = x.dyi = 0.f;
-  x.su = x.sa = 1.f;
+#pragma unroll
+  for (int k = 0; k < kC; ++k) {
+    x.i[k] = x.o[k] = 0;
+    x.ci[k] = x.dyi[k] = 0.f;
+    x.su[k] = x.sa[k] = 1.f;
+  }
 #pragma unroll
   for (int q = 0; q < 4; ++q) x.r0[q] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (x.active) {
     x.rec = sl.chunks[x.T * a.capC + x.c];
     x.len = x.rec.z;
-    // lane j < len holds contribution j of the chunk; the rest replicate the last one with
-    // weight 0 so every shuffle source is a valid row
-    const int pos = x.rec.y + min(l, x.len - 1);
-    x.i = sl.sidx[x.T * a.cap + pos];
-    x.o = sl.oth[x.T * a.cap + pos];
-    x.ci = a.pk_c[x.i];
-    x.dyi = a.dy[x.i];
-    x.su = a.su[x.i];
-    x.sa = a.sa[x.i];
+    // lane j < len holds contribution j of the chunk (+ j + kG, ... at the narrow widths); the rest replicate the
+    // last one with weight 0 so every shuffle source is a valid row
 #pragma unroll
-    for (int q = 0; q < 4; ++q) x.r0[q] = W4[(size_t)__shfl(x.o, q, 32) * kRowVec + l];
+    for (int k = 0; k < kC; ++k) {
+      const int pos = x.rec.y + min(l + k * kG, x.len - 1);
+      x.i[k] = sl.sidx[x.T * a.cap + pos];
+      x.o[k] = sl.oth[x.T * a.cap + pos];
+      x.ci[k] = a.pk_c[x.i[k]];
+      x.dyi[k] = a.dy[x.i[k]];
+      x.su[k] = a.su[x.i[k]];
+      x.sa[k] = a.sa[x.i[k]];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x.r0[q] = W4[(size_t)__shfl(x.o[0], q, kG) * kG + l];
   }
 }
 
-// mean(d zhat), mean(d zhat * zhat) numerators from the head partials: every half-wave sums them itself, lane l the
-// partials l, l + 32, ... in that order, then the fixed butterfly — no LDS, no barrier (round 2 reduced them per
+// mean(d zhat), mean(d zhat * zhat) numerators from the head partials: every row group sums them itself, lane l the
+// partials l, l + kG, ... in that order, then the fixed butterfly — no LDS, no barrier (round 2 reduced them per
 // workgroup through LDS: two barriers that every gather of the kernel had to wait behind)
 struct BwdMeans {
   float2 v[2];
 };
+template <int kG = kRowVec>
 __device__ __forceinline__ void bwd_means_issue(const float *hpart, int n_head_blocks, BwdMeans &x) {
-  const int l = threadIdx.x & 31;
+  const int l = threadIdx.x & (kG - 1);
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    const int k = l + 32 * q;
+    const int k = l + kG * q;
     x.v[q] = k < n_head_blocks ? *reinterpret_cast<const float2 *>(hpart + (size_t)k * kHeadCols) : make_float2(0.f, 0.f);
   }
 }
+template <int kG = kRowVec>
 __device__ __forceinline__ void bwd_means_finish(const float *hpart, int n_head_blocks, const BwdMeans &x, float (&m)[2]) {
-  const int l = threadIdx.x & 31;
+  const int l = threadIdx.x & (kG - 1);
   m[0] = x.v[0].x + x.v[1].x;
   m[1] = x.v[0].y + x.v[1].y;
-  for (int k = l + 64; k < n_head_blocks; k += 32) {  // more than 64 head workgroups: multi-GPU global batches only
+  // at 128: more than 64 head workgroups, multi-GPU global batches only
+  for (int k = l + 2 * kG; k < n_head_blocks; k += kG) {
     m[0] += hpart[(size_t)k * kHeadCols + 0];
     m[1] += hpart[(size_t)k * kHeadCols + 1];
   }
-  m[0] = halfwave_sum(m[0]);
-  m[1] = halfwave_sum(m[1]);
+  m[0] = group_sum<kG>(m[0]);
+  m[1] = group_sum<kG>(m[1]);
 }
 
-template <int kRows = 8>  // gathered rows in flight per half-wave
+template <int kD = kDim, int kRows = 8>  // kRows: gathered rows in flight per row group
 __device__ __forceinline__ void bwd_chunk(const BwdArgs &a, const StepPub &pub, int par, const float (&m)[2],
-                                          const BwdPre &x) {
+                                          const BwdPre<BwdGeom<kD>::kC> &x) {
   if (!x.active) return;
-  const int l = threadIdx.x & 31;
-  const int T = x.T, c = x.c, len = x.len, o = x.o;
+  constexpr int kG = BwdGeom<kD>::kG, kC = BwdGeom<kD>::kC;
+  const int l = threadIdx.x & (kG - 1);
+  const int T = x.T, c = x.c, len = x.len;
   const int4 rec = x.rec;
-  const float ci = x.ci, dyi = x.dyi, su = x.su, sa = x.sa;
   const float4 *W4 = reinterpret_cast<const float4 *>(a.W);
   const float Bf = (float)pub.n_total;
   const float m1 = pub.gamma * m[0] / Bf;
   const float m2 = pub.gamma * m[1] / Bf;
 
-  float cf, sf;
-  {
+  float cf[kC], sf[kC];
+#pragma unroll
+  for (int k = 0; k < kC; ++k) {
+    const float ci = x.ci[k], dyi = x.dyi[k], su = x.su[k], sa = x.sa[k];
     // closed-form backward of BatchNorm + Dense(1) + normalised dot for rating i
     const float z = ci * pub.w + pub.b;
     const float zh = (z - pub.mu) * pub.rs;
@@ -845,19 +890,19 @@ __device__ __forceinline__ void bwd_chunk(const BwdArgs &a, const StepPub &pub, 
     const float dc = dz * pub.w;
     const float ru = 1.0f / sqrtf(fmaxf(su, kL2nEps));
     const float ra = 1.0f / sqrtf(fmaxf(sa, kL2nEps));
-    cf = dc * ru * ra;
+    cf[k] = dc * ru * ra;
     const float sown = T == 0 ? su : sa;
     const float rown = T == 0 ? ru : ra;
-    sf = sown >= kL2nEps ? dc * ci * rown * rown : 0.f;
-  }
-  if (l >= len) {
-    cf = 0.f;
-    sf = 0.f;
+    sf[k] = sown >= kL2nEps ? dc * ci * rown * rown : 0.f;
+    if (l + k * kG >= len) {
+      cf[k] = 0.f;
+      sf[k] = 0.f;
+    }
   }
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int q = 0; q < 4; ++q) {  // contributions 0..3 (rows already here; weight 0 past len)
-    const float cq = __shfl(cf, q, 32);
+    const float cq = __shfl(cf[0], q, kG);
     acc.x += cq * x.r0[q].x;
     acc.y += cq * x.r0[q].y;
     acc.z += cq * x.r0[q].z;
@@ -869,12 +914,14 @@ __device__ __forceinline__ void bwd_chunk(const BwdArgs &a, const StepPub &pub, 
     float4 r[kRows];
 #pragma unroll
     for (int q = 0; q < kRows; ++q) {
-      const int src = min(j + q, 31);  // lanes >= len hold weight 0 and a valid row; past lane 31: weight 0
-      oj[q] = __shfl(o, src, 32);
-      cj[q] = j + q < 32 ? __shfl(cf, src, 32) : 0.f;
+      // contribution min(j + q, 31): lanes >= len hold weight 0 and a valid row; past the chunk: weight 0
+      const int jq = min(j + q, ANIREC_CHUNK - 1);
+      const int src = kC == 1 ? jq : (jq & (kG - 1)), slot = kC == 1 ? 0 : jq / kG;
+      oj[q] = __shfl(pick<kC>(x.o, slot), src, kG);
+      cj[q] = j + q < ANIREC_CHUNK ? __shfl(pick<kC>(cf, slot), src, kG) : 0.f;
     }
 #pragma unroll
-    for (int q = 0; q < kRows; ++q) r[q] = W4[(size_t)oj[q] * kRowVec + l];
+    for (int q = 0; q < kRows; ++q) r[q] = W4[(size_t)oj[q] * kG + l];
 #pragma unroll
     for (int q = 0; q < kRows; ++q) {
       acc.x += cj[q] * r[q].x;
@@ -883,10 +930,13 @@ __device__ __forceinline__ void bwd_chunk(const BwdArgs &a, const StepPub &pub, 
       acc.w += cj[q] * r[q].w;
     }
   }
-  const float ssum = halfwave_sum(sf);
+  float sfl = sf[0];
+#pragma unroll
+  for (int k = 1; k < kC; ++k) sfl += sf[k];
+  const float ssum = group_sum<kG>(sfl);
   const int gc = T * a.capC + c;  // chunk index inside this parity's P / S
   const size_t pc = (size_t)par * 2 * a.capC + gc;
-  reinterpret_cast<float4 *>(a.P)[pc * kRowVec + l] = acc;
+  reinterpret_cast<float4 *>(a.P)[pc * kG + l] = acc;
   if (l == 0) {
     a.S[pc] = ssum;
     if (rec.w > 0 && a.rowmap != nullptr && rec.x >= a.rowmap_lo)
@@ -894,8 +944,9 @@ __device__ __forceinline__ void bwd_chunk(const BwdArgs &a, const StepPub &pub, 
   }
 }
 
-__global__ __launch_bounds__(256, 7) void k_bwd(BwdArgs a) {
-  tick(a.ticks, 0);
+template <int kD = kDim>
+__device__ __forceinline__ void bwd_body(const BwdArgs &a) {
+  constexpr int kG = BwdGeom<kD>::kG;
   // The kernel is a chain of dependent memory round trips at this size, so nothing waits for more than it needs:
   // the step index alone gives the arena slot (chunk record -> sorted index + other-table row -> the rating's
   // scalars and the first four rows are requested at once); both parities' step constants and head partials are
@@ -905,28 +956,38 @@ __global__ __launch_bounds__(256, 7) void k_bwd(BwdArgs a) {
   // (the partial count of the OTHER parity bounds nothing: rows past a parity's count are never summed)
   BwdMeans h0, h1;
   const int hcap = (int)(a.hpart_stride / kHeadCols);  // partial rows a parity holds
-  bwd_means_issue(a.hpart, hcap, h0);
-  bwd_means_issue(a.hpart + a.hpart_stride, hcap, h1);
+  bwd_means_issue<kG>(a.hpart, hcap, h0);
+  bwd_means_issue<kG>(a.hpart + a.hpart_stride, hcap, h1);
   const int par = step & 1;
-  BwdPre x;
-  bwd_prefetch(a, step % a.arena_steps, blockIdx.x, x);
+  BwdPre<BwdGeom<kD>::kC> x;
+  bwd_prefetch<kD>(a, step % a.arena_steps, blockIdx.x, x);
   const StepPub pub = par ? pub1 : pub0;
   BwdMeans hm;
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    const int k = (threadIdx.x & 31) + 32 * q;
+    const int k = (threadIdx.x & (kG - 1)) + kG * q;
     const float2 v = par ? h1.v[q] : h0.v[q];
     hm.v[q] = k < pub.n_head_blocks ? v : make_float2(0.f, 0.f);
   }
   float m[2];
-  bwd_means_finish(a.hpart + par * a.hpart_stride, pub.n_head_blocks, hm, m);
-  bwd_chunk(a, pub, par, m, x);
+  bwd_means_finish<kG>(a.hpart + par * a.hpart_stride, pub.n_head_blocks, hm, m);
+  bwd_chunk<kD>(a, pub, par, m, x);
+}
+
+__global__ __launch_bounds__(256, 7) void k_bwd(BwdArgs a) {
+  tick(a.ticks, 0);
+  bwd_body(a);
   tick(a.ticks, 1);
+}
+// the same at another width (anirec_train_bwd_w): a row group per chunk, 1024 / kD chunks per workgroup
+template <int kD>
+__global__ __launch_bounds__(256) void k_bwd_w(BwdArgs a) {
+  bwd_body<kD>(a);
 }
 
 // g += P[c], s += S[c] for c = c0 .. c1-1 IN THAT ORDER (the sums are bit-reproducible), the loads issued kB
 // at a time: a popular anime row has ~30 chunks per batch (one dependent L2 round trip per chunk otherwise)
-template <int kB = 8>
+template <int kB = 8, int kD = kDim>
 __device__ __forceinline__ void add_chunks(const float4 *P4, const float *S, int c0, int c1, int l, float4 &g,
                                            float &s) {
   for (int c = c0; c < c1; c += kB) {
@@ -935,7 +996,7 @@ __device__ __forceinline__ void add_chunks(const float4 *P4, const float *S, int
 #pragma unroll
     for (int k = 0; k < kB; ++k) {
       const int cc = min(c + k, c1 - 1);
-      p[k] = P4[(size_t)cc * kRowVec + l];
+      p[k] = P4[(size_t)cc * (kD / 4) + l];
       sv[k] = S[cc];
     }
 #pragma unroll
@@ -1045,9 +1106,10 @@ struct RowLoad {
 // issue every load of one row up front: W and the slots the update rule keeps (Adam: M and V; RMSprop / Adagrad: V;
 // SGD: none) and — the row map word having been prefetched one iteration earlier — the first chunk partial of a
 // touched row
-template <bool kNT, int kOpt>
+template <bool kNT, int kOpt, int kD = kDim>
 __device__ __forceinline__ void row_issue(const AdamArgs &a, int par, int r, int l, int rm, RowLoad &x) {
-  const size_t e = (size_t)r * kRowVec + l;
+  constexpr int kG = kD / 4;
+  const size_t e = (size_t)r * kG + l;
   x.rm = rm;
   x.p0 = make_float4(0.f, 0.f, 0.f, 0.f);
   x.s0 = 0.f;
@@ -1061,29 +1123,30 @@ __device__ __forceinline__ void row_issue(const AdamArgs &a, int par, int r, int
   else x.v = x.p0;
   if (a.dense != nullptr && r >= a.dense_lo) {
     const int dr = r - a.dense_lo;
-    x.p0 = reinterpret_cast<const float4 *>(a.dense)[(size_t)dr * kRowVec + l];
-    x.s0 = a.dense[(size_t)a.dense_rows * kDim + dr];
+    x.p0 = reinterpret_cast<const float4 *>(a.dense)[(size_t)dr * kG + l];
+    x.s0 = a.dense[(size_t)a.dense_rows * kD + dr];
     x.rm = 0;
   } else if (rm) {
     const size_t first = (size_t)par * 2 * a.capC + ((rm - 1) >> 10);
-    x.p0 = reinterpret_cast<const float4 *>(a.P)[first * kRowVec + l];
+    x.p0 = reinterpret_cast<const float4 *>(a.P)[first * kG + l];
     x.s0 = a.S[first];
   }
 }
 
 // returns sum(W_new^2) of this lane's four elements; the row map word of a touched row is cleared.  `alpha` is the
 // step's rate: Adam's bias-corrected alpha, or lr
-template <bool kNT, int kOpt, int kB = 4>
+template <bool kNT, int kOpt, int kB = 4, int kD = kDim>
 __device__ __forceinline__ float row_finish(const AdamArgs &a, int par, int r, int l, float alpha, RowLoad &x) {
+  constexpr int kG = kD / 4;
   int32_t *rmw = a.rowmap + (size_t)par * a.rows + r;
-  const size_t e = (size_t)r * kRowVec + l;
+  const size_t e = (size_t)r * kG + l;
   float4 g = x.p0;
   float s = x.s0;
   if (x.rm) {
-    const float4 *P4 = reinterpret_cast<const float4 *>(a.P) + (size_t)par * 2 * a.capC * kRowVec;
+    const float4 *P4 = reinterpret_cast<const float4 *>(a.P) + (size_t)par * 2 * a.capC * kG;
     const float *S = a.S + (size_t)par * 2 * a.capC;
     const int first = (x.rm - 1) >> 10, nch = ((x.rm - 1) & 1023) + 1;
-    if (nch > 1) add_chunks<kB>(P4, S, first + 1, first + nch, l, g, s);  // rows with > ANIREC_CHUNK contributions
+    if (nch > 1) add_chunks<kB, kD>(P4, S, first + 1, first + nch, l, g, s);  // rows with > ANIREC_CHUNK contributions
   }
   if (x.rm && l == 0) *rmw = 0;
   float4 w = x.w, m = x.m, v = x.v;
@@ -1225,18 +1288,20 @@ __device__ __forceinline__ void finish_step(const AdamArgs &a, int par, float *s
   }
 }
 
-// every row of [row_lo, n_rows) under update rule kOpt (ANIREC_OPT_*); workgroup 0 finishes the step when parts & 4
-template <bool kNT, int kOpt>
+// every row of [row_lo, n_rows) under update rule kOpt (ANIREC_OPT_*); workgroup 0 finishes the step when parts & 4.
+// A row is one row group of kD / 4 lanes (a half-wave at 128), 1024 / kD rows per workgroup.
+template <bool kNT, int kOpt, int kD = kDim>
 __device__ __forceinline__ void adam_body(const AdamArgs &a, int bid, int nblocks, float *scratch) {
-  const int l = threadIdx.x & 31;
-  const int nhw = nblocks * 8;
+  constexpr int kG = kD / 4, kRpb = 256 / kG;
+  const int l = threadIdx.x & (kG - 1);
+  const int nhw = nblocks * kRpb;
   const int step = a.sel[0];
   const int par = step & 1;
   const float alpha = a.pub[par].alpha;
   const int32_t *rowmap = a.rowmap + (size_t)par * a.rows;
   float sq = 0.f, sqa = 0.f;  // sum(W_new^2) over user rows / anime rows of this thread
-  int r = a.row_lo + bid * 8 + (threadIdx.x >> 5);
-  // two rows in flight per half-wave; the row-map words of the NEXT pair are fetched one
+  int r = a.row_lo + bid * kRpb + (threadIdx.x / kG);
+  // two rows in flight per row group; the row-map words of the NEXT pair are fetched one
   // iteration ahead so a touched row's chunk partial is requested together with W/M/V
   int rm0 = 0, rm1 = 0;
   if (r < a.n_rows) rm0 = rowmap[r];
@@ -1244,20 +1309,20 @@ __device__ __forceinline__ void adam_body(const AdamArgs &a, int bid, int nblock
   for (; r + nhw < a.n_rows; r += 2 * nhw) {
     const int r1 = r + nhw;
     RowLoad x0, x1;
-    row_issue<kNT, kOpt>(a, par, r, l, rm0, x0);
-    row_issue<kNT, kOpt>(a, par, r1, l, rm1, x1);
+    row_issue<kNT, kOpt, kD>(a, par, r, l, rm0, x0);
+    row_issue<kNT, kOpt, kD>(a, par, r1, l, rm1, x1);
     const int rn0 = r + 2 * nhw, rn1 = r + 3 * nhw;
     rm0 = rn0 < a.n_rows ? rowmap[rn0] : 0;
     rm1 = rn1 < a.n_rows ? rowmap[rn1] : 0;
-    const float q0 = row_finish<kNT, kOpt>(a, par, r, l, alpha, x0);
-    const float q1 = row_finish<kNT, kOpt>(a, par, r1, l, alpha, x1);
+    const float q0 = row_finish<kNT, kOpt, 4, kD>(a, par, r, l, alpha, x0);
+    const float q1 = row_finish<kNT, kOpt, 4, kD>(a, par, r1, l, alpha, x1);
     if (r < a.n_user_rows) sq += q0; else sqa += q0;
     if (r1 < a.n_user_rows) sq += q1; else sqa += q1;
   }
   if (r < a.n_rows) {
     RowLoad x0;
-    row_issue<kNT, kOpt>(a, par, r, l, rm0, x0);
-    const float q0 = row_finish<kNT, kOpt>(a, par, r, l, alpha, x0);
+    row_issue<kNT, kOpt, kD>(a, par, r, l, rm0, x0);
+    const float q0 = row_finish<kNT, kOpt, 4, kD>(a, par, r, l, alpha, x0);
     if (r < a.n_user_rows) sq += q0; else sqa += q0;
   }
   float *rp = a.regpart + (size_t)(par * 2) * ANIREC_ADAM_BLOCKS;
@@ -1286,6 +1351,12 @@ __global__ __launch_bounds__(256) void k_dense_opt(AdamArgs a) {
   tick(a.ticks, 0);
   adam_body<kNT, kOpt>(a, blockIdx.x, gridDim.x, scratch);
   tick(a.ticks, 1);
+}
+// the dense update at another width (anirec_train_adam_w), any rule: one instantiation per (rule, width)
+template <bool kNT, int kOpt, int kD>
+__global__ __launch_bounds__(256) void k_dense_opt_w(AdamArgs a) {
+  __shared__ float scratch[kHeadCols * 16];
+  adam_body<kNT, kOpt, kD>(a, blockIdx.x, gridDim.x, scratch);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1987,22 +2058,22 @@ __global__ __launch_bounds__(1024) void k_lazy_reduce(LazyArgs a) {
 
 // sum(W^2) partials of the CURRENT weights into both parities (after (re)loading weights, before validation):
 // the next step's finish reads them whatever its parity
-__global__ __launch_bounds__(256) void k_reg_init(const float *W, int row_lo, int n_rows, int n_user_rows,
-                                                  float *regpart) {
+template <int kD = kDim>
+__device__ __forceinline__ void reg_init_body(const float *W, int row_lo, int n_rows, int n_user_rows,
+                                              float *regpart) {
   __shared__ float scratch[16];
-  const int l = threadIdx.x & 31;
-  const int nhw = gridDim.x * 8;
+  __shared__ float res[2];
+  constexpr int kG = kD / 4, kRpb = 256 / kG;
+  const int l = threadIdx.x & (kG - 1);
+  const int nhw = gridDim.x * kRpb;
   float sq = 0.f, sqa = 0.f;
-  for (int r = row_lo + blockIdx.x * 8 + (threadIdx.x >> 5); r < n_rows; r += nhw) {
-    const float4 w = reinterpret_cast<const float4 *>(W)[(size_t)r * kRowVec + l];
+  for (int r = row_lo + blockIdx.x * kRpb + (threadIdx.x / kG); r < n_rows; r += nhw) {
+    const float4 w = reinterpret_cast<const float4 *>(W)[(size_t)r * kG + l];
     const float q = w.x * w.x + w.y * w.y + w.z * w.z + w.w * w.w;
     if (r < n_user_rows) sq += q; else sqa += q;
   }
-  float u = 0.f, an = 0.f;
-  __shared__ float res[2];
   block_sq_partials(sq, sqa, scratch, &res[0], &res[1]);
-  u = res[0];
-  an = res[1];
+  const float u = res[0], an = res[1];
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
@@ -2010,6 +2081,15 @@ __global__ __launch_bounds__(256) void k_reg_init(const float *W, int row_lo, in
       regpart[(size_t)(p * 2 + 1) * ANIREC_ADAM_BLOCKS + blockIdx.x] = an;
     }
   }
+}
+__global__ __launch_bounds__(256) void k_reg_init(const float *W, int row_lo, int n_rows, int n_user_rows,
+                                                  float *regpart) {
+  reg_init_body(W, row_lo, n_rows, n_user_rows, regpart);
+}
+template <int kD>
+__global__ __launch_bounds__(256) void k_reg_init_w(const float *W, int row_lo, int n_rows, int n_user_rows,
+                                                    float *regpart) {
+  reg_init_body<kD>(W, row_lo, n_rows, n_user_rows, regpart);
 }
 
 // flat Adam with an explicit gradient (unit-testable bit-exact stage)
@@ -2224,38 +2304,90 @@ struct EvalArgs {
   const float *rating;
   int n;
   anirec_state *state;
+  int act, loss;  // ANIREC_ACT_* / ANIREC_LOSS_* of the descriptor: read by k_eval_w only
 };
 
-template <int kAct, int kLoss>
-__global__ __launch_bounds__(256) void k_eval(EvalArgs a) {
-  __shared__ float sh[2][8];
+// the head of one validation rating: prediction, data loss and (kMetrics) the Keras metric values
+template <int kAct, int kLoss, bool kMetrics>
+__device__ __forceinline__ void eval_terms(uint32_t mask, float y, float t, float &p, float &li,
+                                           float (&mv)[kMetricKinds]) {
+  float g;
+  head_grad<kAct, kLoss>(y, t, p, g);
+  li = head_loss<kAct, kLoss>(y, t, p);
+  if constexpr (kMetrics) metric_terms<kAct>(mask, y, t, p, mv);
+}
+// the same with the head as run-time values (the kernels of the other widths: one instantiation per width instead of
+// one per width, activation and loss); every case is the instantiation above
+template <int kAct, bool kMetrics>
+__device__ __forceinline__ void eval_terms_loss(int loss, uint32_t mask, float y, float t, float &p, float &li,
+                                                float (&mv)[kMetricKinds]) {
+  switch (loss) {
+    case ANIREC_LOSS_MSE: return eval_terms<kAct, ANIREC_LOSS_MSE, kMetrics>(mask, y, t, p, li, mv);
+    case ANIREC_LOSS_MAE: return eval_terms<kAct, ANIREC_LOSS_MAE, kMetrics>(mask, y, t, p, li, mv);
+    case ANIREC_LOSS_HUBER: return eval_terms<kAct, ANIREC_LOSS_HUBER, kMetrics>(mask, y, t, p, li, mv);
+    case ANIREC_LOSS_LOGCOSH: return eval_terms<kAct, ANIREC_LOSS_LOGCOSH, kMetrics>(mask, y, t, p, li, mv);
+    default: return eval_terms<kAct, ANIREC_LOSS_BCE, kMetrics>(mask, y, t, p, li, mv);
+  }
+}
+template <bool kMetrics>
+__device__ __forceinline__ void eval_terms_any(int act, int loss, uint32_t mask, float y, float t, float &p, float &li,
+                                               float (&mv)[kMetricKinds]) {
+  switch (act) {
+    case ANIREC_ACT_LINEAR: return eval_terms_loss<ANIREC_ACT_LINEAR, kMetrics>(loss, mask, y, t, p, li, mv);
+    case ANIREC_ACT_TANH: return eval_terms_loss<ANIREC_ACT_TANH, kMetrics>(loss, mask, y, t, p, li, mv);
+    case ANIREC_ACT_RELU: return eval_terms_loss<ANIREC_ACT_RELU, kMetrics>(loss, mask, y, t, p, li, mv);
+    case ANIREC_ACT_SOFTPLUS: return eval_terms_loss<ANIREC_ACT_SOFTPLUS, kMetrics>(loss, mask, y, t, p, li, mv);
+    default: return eval_terms_loss<ANIREC_ACT_SIGMOID, kMetrics>(loss, mask, y, t, p, li, mv);
+  }
+}
+
+// one row group per validation rating (1024 / kD ratings per workgroup).  kAct / kLoss >= 0: the head as template
+// parameters (k_eval, k_eval_metrics: the 128-wide kernels); < 0: a.act / a.loss (k_eval_w).  kMetrics: also the Keras
+// metrics of m
+template <int kAct, int kLoss, bool kMetrics, int kD>
+__device__ __forceinline__ void eval_body(const EvalArgs &a, const MetricArgs &m) {
+  constexpr int kG = kD / 4, kRpb = 256 / kG;
+  __shared__ float sh[kMetrics ? 2 + kMetricKinds : 2][kRpb];
   const anirec_state *st = a.state;
   const float w = st->w, b = st->b;
   const float inv = st->gamma * (1.0f / sqrtf(st->mov_var + kBnEps));
   const float shift = st->beta - st->mov_mean * inv;
-  const int l32 = threadIdx.x & 31, h = threadIdx.x >> 5;
-  const int i = blockIdx.x * 8 + h;
+  const int l32 = threadIdx.x & (kG - 1), h = threadIdx.x / kG;
+  const int i = blockIdx.x * kRpb + h;
   float li = 0.f, se = 0.f;
+  float mv[kMetricKinds] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (i < a.n) {
     float su, sa, dd;
-    pair_dots(reinterpret_cast<const float4 *>(a.W), a.user_idx[i], a.anime_idx[i] + a.n_user_rows,
-              l32, su, sa, dd);
+    pair_dots<kD>(reinterpret_cast<const float4 *>(a.W), a.user_idx[i], a.anime_idx[i] + a.n_user_rows,
+                  l32, su, sa, dd);
     const float c = cos_from_dots(su, sa, dd);
     const float y = (c * w + b) * inv + shift;
     const float t = a.rating[i];
-    float p, g;
-    head_grad<kAct, kLoss>(y, t, p, g);
-    li = head_loss<kAct, kLoss>(y, t, p);
+    float p;
+    if constexpr (kAct >= 0) eval_terms<kAct, kLoss, kMetrics>(m.mask, y, t, p, li, mv);
+    else eval_terms_any<kMetrics>(a.act, a.loss, m.mask, y, t, p, li, mv);
     se = (p - t) * (p - t);
+    if constexpr (kMetrics) {
+      if ((m.mask & ANIREC_METRIC_AUC) && l32 == 0) {  // a few ratings a workgroup: straight into the integer bins
+        const int bk = auc_bucket(p);
+        const uint32_t wt = auc_pos_mass(t);
+        if (wt) atomicAdd(&m.acc->auc_pos[bk], (unsigned long long)wt);
+        if (wt != ANIREC_AUC_ONE) atomicAdd(&m.acc->auc_neg[bk], (unsigned long long)(ANIREC_AUC_ONE - wt));
+      }
+    }
   }
   if (l32 == 0) {
     sh[0][h] = li;
     sh[1][h] = se;
+    if constexpr (kMetrics) {
+#pragma unroll
+      for (int k = 0; k < kMetricKinds; ++k) sh[2 + k][h] = mv[k];
+    }
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     double L = 0., E = 0.;
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < kRpb; ++k) {
       L += sh[0][k];
       E += sh[1][k];
     }
@@ -2263,64 +2395,33 @@ __global__ __launch_bounds__(256) void k_eval(EvalArgs a) {
     atomicAdd(&a.state->val_bce_sum, L);
     atomicAdd(&a.state->val_se_sum, E);
     if (blockIdx.x == 0) atomicAdd(&a.state->val_n, (double)a.n);
+    if constexpr (kMetrics) {
+#pragma unroll
+      for (int k = 0; k < kMetricKinds; ++k) {
+        if (!(m.mask & (1u << k))) continue;
+        double v = 0.;
+        for (int j = 0; j < kRpb; ++j) v += sh[2 + k][j];
+        atomicAdd(&m.acc->sum[k], v);
+      }
+    }
   }
 }
 
-// k_eval that also adds the Keras metrics of m (anirec_eval_metrics); k_eval itself stays the kernel it was
+template <int kAct, int kLoss>
+__global__ __launch_bounds__(256) void k_eval(EvalArgs a) {
+  eval_body<kAct, kLoss, false, kDim>(a, MetricArgs{});
+}
+
+// k_eval that also adds the Keras metrics of m (anirec_eval_metrics)
 template <int kAct, int kLoss>
 __global__ __launch_bounds__(256) void k_eval_metrics(EvalArgs a, MetricArgs m) {
-  __shared__ float sh[2 + kMetricKinds][8];
-  const anirec_state *st = a.state;
-  const float w = st->w, b = st->b;
-  const float inv = st->gamma * (1.0f / sqrtf(st->mov_var + kBnEps));
-  const float shift = st->beta - st->mov_mean * inv;
-  const int l32 = threadIdx.x & 31, h = threadIdx.x >> 5;
-  const int i = blockIdx.x * 8 + h;
-  float li = 0.f, se = 0.f;
-  float mv[kMetricKinds] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (i < a.n) {
-    float su, sa, dd;
-    pair_dots(reinterpret_cast<const float4 *>(a.W), a.user_idx[i], a.anime_idx[i] + a.n_user_rows,
-              l32, su, sa, dd);
-    const float c = cos_from_dots(su, sa, dd);
-    const float y = (c * w + b) * inv + shift;
-    const float t = a.rating[i];
-    float p, g;
-    head_grad<kAct, kLoss>(y, t, p, g);
-    li = head_loss<kAct, kLoss>(y, t, p);
-    se = (p - t) * (p - t);
-    metric_terms<kAct>(m.mask, y, t, p, mv);
-    if ((m.mask & ANIREC_METRIC_AUC) && l32 == 0) {  // 8 ratings a workgroup: straight into the integer bins
-      const int bk = auc_bucket(p);
-      const uint32_t wt = auc_pos_mass(t);
-      if (wt) atomicAdd(&m.acc->auc_pos[bk], (unsigned long long)wt);
-      if (wt != ANIREC_AUC_ONE) atomicAdd(&m.acc->auc_neg[bk], (unsigned long long)(ANIREC_AUC_ONE - wt));
-    }
-  }
-  if (l32 == 0) {
-    sh[0][h] = li;
-    sh[1][h] = se;
-#pragma unroll
-    for (int k = 0; k < kMetricKinds; ++k) sh[2 + k][h] = mv[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double L = 0., E = 0.;
-    for (int k = 0; k < 8; ++k) {
-      L += sh[0][k];
-      E += sh[1][k];
-    }
-    atomicAdd(&a.state->val_bce_sum, L);
-    atomicAdd(&a.state->val_se_sum, E);
-    if (blockIdx.x == 0) atomicAdd(&a.state->val_n, (double)a.n);
-#pragma unroll
-    for (int k = 0; k < kMetricKinds; ++k) {
-      if (!(m.mask & (1u << k))) continue;
-      double v = 0.;
-      for (int j = 0; j < 8; ++j) v += sh[2 + k][j];
-      atomicAdd(&m.acc->sum[k], v);
-    }
-  }
+  eval_body<kAct, kLoss, true, kDim>(a, m);
+}
+
+// validation at another width (anirec_eval_metrics_w), the head from a.act / a.loss
+template <bool kMetrics, int kD>
+__global__ __launch_bounds__(256) void k_eval_w(EvalArgs a, MetricArgs m) {
+  eval_body<-1, -1, kMetrics, kD>(a, m);
 }
 
 __global__ __launch_bounds__(1024) void k_sum_regpart(anirec_state *st, const float *regpart) {
@@ -2376,9 +2477,13 @@ static int check_opt(const anirec_train_desc *d) {
   return ANIREC_OK;
 }
 
-static int check_desc(const anirec_train_desc *d) {
+// dim: the row width of the tables (the *_w entry points; ANIREC_DIM otherwise).  Another width than ANIREC_DIM runs the
+// dense one-GPU step only
+static int check_desc(const anirec_train_desc *d, int dim = kDim) {
+  if (!dim_ok(dim)) return ANIREC_EINVAL;
   if (!d || !d->W || !d->M || !d->V || !d->rowmap || !d->state || !d->workspace || !d->packets)
     return ANIREC_EINVAL;
+  if (dim != kDim && (d->lazy != 0 || d->dense_mode != 0 || d->n_seg != 1)) return ANIREC_EINVAL;
   if (d->max_batch < 1 || d->max_batch > ANIREC_MAX_BATCH) return ANIREC_EINVAL;
   if (d->n_user_rows < 1 || d->n_anime_rows < 1 || d->arena_steps < 2) return ANIREC_EINVAL;
   if (d->n_seg < 1 || d->n_seg > ANIREC_MAX_SEG || d->my_seg < 0 || d->my_seg >= d->n_seg)
@@ -2389,7 +2494,7 @@ static int check_desc(const anirec_train_desc *d) {
     if (!d->dense_grad || d->dense_rows < table_rows(d) - dense_lo_of(d)) return ANIREC_EINVAL;
     if (d->adam_row_lo < 0 || d->adam_row_hi < d->adam_row_lo || d->adam_row_hi > table_rows(d)) return ANIREC_EINVAL;
   }
-  if (d->workspace_bytes < anirec_train_workspace_bytes(d->max_batch, d->arena_steps))
+  if (d->workspace_bytes < anirec_train_workspace_bytes_w(d->max_batch, d->arena_steps, dim))
     return ANIREC_EWORKSPACE;
   return ANIREC_OK;
 }
@@ -2452,7 +2557,14 @@ static FwdArgs fwd_args(const anirec_train_desc *d, const TrainWs &w) {
 static int launch_fwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   const FwdArgs a = fwd_args(d, w);
   float *pk = packet_ptr(d, d->my_seg);
-  hipLaunchKernelGGL(k_fwd, dim3((d->max_batch + 7) / 8), dim3(256), 0, s, a);
+  if (w.dim == kDim) {
+    hipLaunchKernelGGL(k_fwd, dim3((d->max_batch + 7) / 8), dim3(256), 0, s, a);
+  } else {
+    with_width(w.dim, [&](auto kd) {
+      constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
+      hipLaunchKernelGGL(k_fwd_w<kD>, dim3((d->max_batch + kRpb - 1) / kRpb), dim3(256), 0, s, a);
+    });
+  }
   if (int te = ticks_collect(w, 0, s)) return te;
   if (d->n_seg > 1)
     hipLaunchKernelGGL(k_seg_stats, dim3(1), dim3(1024), 0, s, pk, packet_cap(d->max_batch), d->max_batch,
@@ -2580,7 +2692,14 @@ static int launch_bwd_only(const anirec_train_desc *d, const TrainWs &w, hipStre
     else
       a.rowmap = nullptr;
   }
-  hipLaunchKernelGGL(k_bwd, dim3((2 * w.capC + 7) / 8), dim3(256), 0, s, a);
+  if (w.dim == kDim) {
+    hipLaunchKernelGGL(k_bwd, dim3((2 * w.capC + 7) / 8), dim3(256), 0, s, a);
+  } else {
+    with_width(w.dim, [&](auto kd) {
+      constexpr int kD = decltype(kd)::value, kRpb = BwdGeom<kD>::kRpb;
+      hipLaunchKernelGGL(k_bwd_w<kD>, dim3((2 * w.capC + kRpb - 1) / kRpb), dim3(256), 0, s, a);
+    });
+  }
   if (int te = ticks_collect(w, 2, s)) return te;
   return (int)hipGetLastError();
 }
@@ -2634,8 +2753,13 @@ static AdamArgs adam_args(const anirec_train_desc *d, const TrainWs &w) {
 
 // tables that overflow the 256-MiB Infinity Cache are streamed non-temporally; small ones
 // (the 7M-rating shape: 50 MB of W+M+V) stay cache-resident between steps
-static inline bool stream_nt(const anirec_train_desc *d) {
-  return (size_t)table_rows(d) * kDim * 4 * 3 > ((size_t)192 << 20);
+static inline bool stream_nt(const anirec_train_desc *d, int dim = kDim) {
+  return (size_t)table_rows(d) * dim * 4 * 3 > ((size_t)192 << 20);
+}
+// grid of the dense update and of the L2 init (the same: both write the regpart slots [0, grid)): sized by the tables'
+// bytes, so a row group has two rows at least at every width
+static inline int table_grid(const anirec_train_desc *d, const TrainWs &w) {
+  return stream_grid((long long)table_rows(d) * w.dim / kDim);
 }
 
 // which: 0 = every row this rank updates + finish (one GPU; replicated multi-GPU modes), 1 = the user rows only (may
@@ -2657,8 +2781,25 @@ static int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStr
       a.w0 = w.sel + 1;
     }
   }
-  const bool nt = stream_nt(d);
-  const dim3 grid(stream_grid(table_rows(d))), block(256);
+  const bool nt = stream_nt(d, w.dim);
+  const dim3 grid(table_grid(d, w)), block(256);
+  if (w.dim != kDim) {  // (dense one-GPU step only: check_desc)
+    with_width(w.dim, [&](auto kd) {
+      constexpr int kD = decltype(kd)::value;
+      const auto go = [&](auto opt) {
+        constexpr int kOpt = decltype(opt)::value;
+        if (nt) hipLaunchKernelGGL((k_dense_opt_w<true, kOpt, kD>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_dense_opt_w<false, kOpt, kD>), grid, block, 0, s, a);
+      };
+      switch (d->optimizer) {
+        case ANIREC_OPT_SGD: go(std::integral_constant<int, ANIREC_OPT_SGD>()); break;
+        case ANIREC_OPT_RMSPROP: go(std::integral_constant<int, ANIREC_OPT_RMSPROP>()); break;
+        case ANIREC_OPT_ADAGRAD: go(std::integral_constant<int, ANIREC_OPT_ADAGRAD>()); break;
+        default: go(std::integral_constant<int, ANIREC_OPT_ADAM>());
+      }
+    });
+    return (int)hipGetLastError();
+  }
   switch (d->optimizer) {
     case ANIREC_OPT_SGD:
       if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_SGD>), grid, block, 0, s, a);
@@ -2933,15 +3074,18 @@ size_t anirec_train_lazy_bytes(int32_t rows) {
   return 2 * ((sizeof(int32_t) * (size_t)rows + 255) / 256 * 256) + sizeof(float) * (size_t)rows * ANIREC_LAZY_WINDOW;
 }
 
+size_t anirec_train_workspace_bytes_w(int32_t max_batch, int32_t arena_steps, int32_t dim) {
+  if (max_batch < 1 || max_batch > ANIREC_MAX_BATCH || arena_steps < 2 || !dim_ok(dim)) return 0;
+  return carve(nullptr, max_batch, arena_steps, dim).total;
+}
 size_t anirec_train_workspace_bytes(int32_t max_batch, int32_t arena_steps) {
-  if (max_batch < 1 || max_batch > ANIREC_MAX_BATCH || arena_steps < 2) return 0;
-  return carve(nullptr, max_batch, arena_steps).total;
+  return anirec_train_workspace_bytes_w(max_batch, arena_steps, ANIREC_DIM);
 }
 
-int anirec_train_init_reg(const anirec_train_desc *d, void *stream) {
-  int rc = check_desc(d);
+int anirec_train_init_reg_w(const anirec_train_desc *d, int32_t dim, void *stream) {
+  int rc = check_desc(d, dim);
   if (rc) return rc;
-  TrainWs w = carve(d->workspace, d->max_batch, d->arena_steps);
+  TrainWs w = carve(d->workspace, d->max_batch, d->arena_steps, dim);
   hipStream_t s = (hipStream_t)stream;
   // entries beyond the grid are never written again: they must be (and stay) zero
   ANIREC_HIP_CHECK(hipMemsetAsync(w.regpart, 0, sizeof(float) * 4 * ANIREC_ADAM_BLOCKS, s));
@@ -2952,50 +3096,66 @@ int anirec_train_init_reg(const anirec_train_desc *d, void *stream) {
     lo = d->adam_row_lo;
     hi = d->adam_row_hi;
   }
-  hipLaunchKernelGGL(k_reg_init, dim3(stream_grid(table_rows(d))), dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
+  const dim3 grid(table_grid(d, w));
+  if (dim == kDim)
+    hipLaunchKernelGGL(k_reg_init, grid, dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
+  else
+    with_width(dim, [&](auto kd) {
+      hipLaunchKernelGGL(k_reg_init_w<decltype(kd)::value>, grid, dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
+    });
   ANIREC_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_sum_regpart, dim3(1), dim3(1024), 0, s, d->state, w.regpart);
   return (int)hipGetLastError();
 }
+int anirec_train_init_reg(const anirec_train_desc *d, void *stream) {
+  return anirec_train_init_reg_w(d, ANIREC_DIM, stream);
+}
 
-int anirec_train_prep(const anirec_train_desc *d, int32_t first_step, int32_t n_steps,
-                      void *stream) {
-  int rc = check_desc(d);
+int anirec_train_prep_w(const anirec_train_desc *d, int32_t dim, int32_t first_step, int32_t n_steps, void *stream) {
+  int rc = check_desc(d, dim);
   if (rc) return rc;
   if (!d->user_idx || !d->anime_idx || !d->sched) return ANIREC_EINVAL;
   if (first_step < 0 || n_steps < 0 || first_step + n_steps > d->n_steps ||
       n_steps > d->arena_steps)
     return ANIREC_EINVAL;
   if (n_steps == 0) return ANIREC_OK;
-  return launch_prep(d, carve(d->workspace, d->max_batch, d->arena_steps), first_step, n_steps, false,
+  return launch_prep(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), first_step, n_steps, false,
                      (hipStream_t)stream);
 }
+int anirec_train_prep(const anirec_train_desc *d, int32_t first_step, int32_t n_steps,
+                      void *stream) {
+  return anirec_train_prep_w(d, ANIREC_DIM, first_step, n_steps, stream);
+}
 
-int anirec_train_fwd(const anirec_train_desc *d, void *stream) {
-  int rc = check_desc(d);
+int anirec_train_fwd_w(const anirec_train_desc *d, int32_t dim, void *stream) {
+  int rc = check_desc(d, dim);
   if (rc) return rc;
   if (!d->user_idx || !d->anime_idx || !d->rating || !d->sched) return ANIREC_EINVAL;
-  return launch_fwd(d, carve(d->workspace, d->max_batch, d->arena_steps), (hipStream_t)stream);
+  return launch_fwd(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream);
 }
+int anirec_train_fwd(const anirec_train_desc *d, void *stream) { return anirec_train_fwd_w(d, ANIREC_DIM, stream); }
 
-int anirec_train_head(const anirec_train_desc *d, void *stream) {
-  int rc = check_desc(d);
+int anirec_train_head_w(const anirec_train_desc *d, int32_t dim, void *stream) {
+  int rc = check_desc(d, dim);
   if (rc) return rc;
   if (!d->sched) return ANIREC_EINVAL;
-  return launch_head(d, carve(d->workspace, d->max_batch, d->arena_steps), (hipStream_t)stream);
+  return launch_head(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream);
 }
+int anirec_train_head(const anirec_train_desc *d, void *stream) { return anirec_train_head_w(d, ANIREC_DIM, stream); }
 
-int anirec_train_bwd(const anirec_train_desc *d, void *stream) {
-  int rc = check_desc(d);
+int anirec_train_bwd_w(const anirec_train_desc *d, int32_t dim, void *stream) {
+  int rc = check_desc(d, dim);
   if (rc) return rc;
-  return launch_bwd(d, carve(d->workspace, d->max_batch, d->arena_steps), (hipStream_t)stream);
+  return launch_bwd(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream);
 }
+int anirec_train_bwd(const anirec_train_desc *d, void *stream) { return anirec_train_bwd_w(d, ANIREC_DIM, stream); }
 
-int anirec_train_adam(const anirec_train_desc *d, void *stream) {
-  int rc = check_desc(d);
+int anirec_train_adam_w(const anirec_train_desc *d, int32_t dim, void *stream) {
+  int rc = check_desc(d, dim);
   if (rc) return rc;
-  return launch_adam_full(d, carve(d->workspace, d->max_batch, d->arena_steps), (hipStream_t)stream, 0);
+  return launch_adam_full(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream, 0);
 }
+int anirec_train_adam(const anirec_train_desc *d, void *stream) { return anirec_train_adam_w(d, ANIREC_DIM, stream); }
 
 // Measurement hook (bench.py).  While armed, every training kernel launched through this library stamps the
 // constant-clock (100 MHz) time of each workgroup's first and last instruction into the workspace, and the launch
@@ -3300,14 +3460,19 @@ int anirec_dist_run(anirec_dist_stepper *h, anirec_dist_comm *c, int32_t first_s
 struct anirec_trainer : RunHandle {};
 
 int anirec_trainer_create(const anirec_train_desc *d, anirec_trainer **out) {
+  return anirec_trainer_create_w(d, ANIREC_DIM, out);
+}
+
+// the handle carries the width (its carved workspace): _run, _set_metrics and _destroy are the same calls at every width
+int anirec_trainer_create_w(const anirec_train_desc *d, int32_t dim, anirec_trainer **out) {
   if (!out) return ANIREC_EINVAL;
-  int rc = check_desc(d);
+  int rc = check_desc(d, dim);
   if (rc) return rc;
   if (d->n_seg != 1 || d->dense_mode) return ANIREC_EINVAL;  // multi-GPU drives the step halves itself
   anirec_trainer *t = new (std::nothrow) anirec_trainer;
   if (!t) return ANIREC_EINVAL;
   t->d = *d;
-  t->ws = carve(d->workspace, d->max_batch, d->arena_steps);
+  t->ws = carve(d->workspace, d->max_batch, d->arena_steps, dim);
   *out = t;
   return ANIREC_OK;
 }
@@ -3345,7 +3510,13 @@ int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32
 
 int anirec_eval_metrics(const anirec_train_desc *d, uint32_t mask, anirec_metric_acc *acc, const int32_t *user_idx,
                         const int32_t *anime_idx, const float *rating, int32_t n, void *stream) {
-  if (!d || !d->W || !d->state || !user_idx || !anime_idx || !rating || n < 0 || check_opt(d))
+  return anirec_eval_metrics_w(d, ANIREC_DIM, mask, acc, user_idx, anime_idx, rating, n, stream);
+}
+
+int anirec_eval_metrics_w(const anirec_train_desc *d, int32_t dim, uint32_t mask, anirec_metric_acc *acc,
+                          const int32_t *user_idx, const int32_t *anime_idx, const float *rating, int32_t n,
+                          void *stream) {
+  if (!dim_ok(dim) || !d || !d->W || !d->state || !user_idx || !anime_idx || !rating || n < 0 || check_opt(d))
     return ANIREC_EINVAL;
   if (check_metrics(d, mask)) return ANIREC_EINVAL;
   const MetricArgs m = (mask && acc) ? MetricArgs{mask, acc} : MetricArgs{};
@@ -3358,6 +3529,17 @@ int anirec_eval_metrics(const anirec_train_desc *d, uint32_t mask, anirec_metric
   a.rating = rating;
   a.n = n;
   a.state = d->state;
+  a.act = d->activation;
+  a.loss = d->loss;
+  if (dim != kDim) {  // the head as run-time values: one kernel per width
+    with_width(dim, [&](auto kd) {
+      constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
+      const dim3 grid((n + kRpb - 1) / kRpb);
+      if (m.mask) hipLaunchKernelGGL((k_eval_w<true, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
+      else hipLaunchKernelGGL((k_eval_w<false, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
+    });
+    return (int)hipGetLastError();
+  }
   with_act(d->activation, [&](auto act) {
     with_loss(d->loss, [&](auto loss) {
       if (m.mask)

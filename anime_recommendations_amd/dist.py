@@ -122,7 +122,13 @@ class DistTrainEngine:
 
     def __init__(self, n_users, n_anime, batch_per_rank, l2=1e-4, arena_steps=64, device="cuda:0",
                  engine_factory=None, mode=None, lazy=None, optimizer="adam", loss="binary_crossentropy",
-                 activation="sigmoid", metrics=0):
+                 activation="sigmoid", metrics=0, width=_lib.DIM):
+        # the same refusal on every rank, before any collective
+        self.width = _lib.check_width(width)
+        if self.width != _lib.DIM:
+            raise ValueError("multi-GPU training is %d-only: the dist_* calls and the dense gradient collectives are "
+                             "specialised for that embedding width (got %d); train another width on one GPU"
+                             % (_lib.DIM, self.width))
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
         self.rank, self.world = dist.get_rank(), dist.get_world_size()

@@ -6,7 +6,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from ._lib import MAX_TOPK
+from ._lib import DIM, MAX_TOPK
 
 
 def shard_bounds(n, rank, world):
@@ -32,9 +32,10 @@ def gather_rows(local, n_total, world, rank):
 def sharded_cosine_topk(What, k, exclude_self=True, keep=None, topk_fn=None):
     """All-pairs neighbours of every row of ``What`` (replicated on each rank): rank r scores the
     queries of its slice against all keys; returns the gathered (idx [n,k], score [n,k]).  Without a
-    ``topk_fn``: the matrix cores for k <= MAX_TOPK - 1, the exact any-k kernels above."""
+    ``topk_fn``: the matrix cores for k <= MAX_TOPK - 1 at width 128, the exact kernels (any k, any supported width)
+    otherwise."""
     if topk_fn is None:
-        if k > MAX_TOPK - 1:
+        if k > MAX_TOPK - 1 or What.shape[1] != DIM:
             from .ops import cosine_topk as topk_fn
         else:
             from .ops import cosine_topk_mfma as topk_fn
@@ -51,7 +52,7 @@ def sharded_cosine_topk(What, k, exclude_self=True, keep=None, topk_fn=None):
 def sharded_predict_topk(U, A, head, users, k, watched_bits=None, predict_fn=None):
     """Top-k unwatched anime for every listed user, users sharded across ranks."""
     if predict_fn is None:
-        if k > MAX_TOPK - 1:
+        if k > MAX_TOPK - 1 or U.shape[1] != DIM:      # (the MFMA path is 128-wide only)
             from .ops import predict_topk as predict_fn      # exact any-k kernels
         else:
             from .ops import predict_topk_mfma as predict_fn     # matrix cores; exact kernels for flagged users

@@ -4,7 +4,7 @@ PyTorch is used here for plumbing only: HBM allocations, streams, (later) RCCL.
 All arithmetic of the train step runs in libanirec's HIP kernels.
 
 HBM layout (one rank):
-  W, M, V     [(n_user_rows + n_anime_rows), 128] fp32 each — embeddings and Adam moments (RMSprop / Adagrad keep
+  W, M, V     [(n_user_rows + n_anime_rows), width] fp32 each (width 128 unless asked otherwise) — embeddings and Adam moments (RMSprop / Adagrad keep
               their one slot in V; SGD has none), users first then anime, so one dense launch covers both tables
   rowmap      [2][rows] int32 — per-step "row -> chunk list" map written by bwd, cleared by adam (one per step parity)
   state       anirec_state (136 B) — scalar head, BN moving stats, step cursors, metrics
@@ -43,7 +43,8 @@ def _column(x, dtype, device):
 class TrainEngine:
     def __init__(self, n_user_rows, n_anime_rows, max_batch, l2=1e-4, arena_steps=64,
                  device="cuda:0", n_seg=1, my_seg=0, dense_mode=0, row_pad=1, adam_rows=None, lazy=None,
-                 optimizer="adam", loss="binary_crossentropy", activation="sigmoid", metrics=0):
+                 optimizer="adam", loss="binary_crossentropy", activation="sigmoid", metrics=0, width=DIM,
+                 w_entry=None):
         """dense_mode: 0 one GPU; 1 user-sharded DP (anime gradient through ``dense_grad``); 2 replicated
         tables (every gradient through ``dense_grad``).  row_pad: the tables and the dense buffer are
         allocated with their row count rounded up to a multiple of it (equal reduce-scatter / all-gather
@@ -62,7 +63,23 @@ class TrainEngine:
         default is the reference's sigmoid + binary_crossentropy.
         metrics: ANIREC_METRIC_* bits (``schedule.metric_mask``) of the Keras metrics the train step and the validation
         pass accumulate on the GPU beside the squared error (``epoch_logs`` / ``eval_logs``); 0 = none, the step as
-        without them."""
+        without them.
+        width: the embedding width (``_lib.WIDTHS``: 32, 64, 128, 256; the reference's --embedding_size).  Another
+        width than 128 trains through the ``*_w`` entry points with the dense update on one GPU: ``lazy`` resolves to
+        False there (``lazy=True`` is a ValueError, as with a non-Adam optimizer), and ``dense_mode != 0`` / ``n_seg >
+        1`` are ValueErrors.  w_entry: call the ``*_w`` entry points (None: exactly when width != 128; True at 128 runs
+        the twins, which are the same kernels)."""
+        self.width = _lib.check_width(width)
+        if self.width != DIM:
+            if lazy:
+                raise ValueError("the lazy update exists at embedding width 128 only (width %d)" % self.width)
+            if int(dense_mode) != 0 or int(n_seg) != 1:
+                raise ValueError("multi-GPU training (dense_mode %r, n_seg %r) exists at embedding width 128 only "
+                                 "(width %d)" % (dense_mode, n_seg, self.width))
+            lazy = False
+        self.w_entry = (self.width != DIM) if w_entry is None else bool(w_entry)
+        if self.width != DIM and not self.w_entry:
+            raise ValueError("width %d needs the *_w entry points" % self.width)
         self.optimizer = schedule.resolve_optimizer(optimizer)
         self.loss = schedule.resolve_loss(loss)
         self.activation = schedule.resolve_activation(activation)
@@ -87,16 +104,19 @@ class TrainEngine:
         dev = self.device
         row_pad = max(1, int(row_pad))
         self.rows_alloc = (self.rows + row_pad - 1) // row_pad * row_pad
-        self._Wfull = torch.zeros(self.rows_alloc, DIM, dtype=torch.float32, device=dev)
+        self._Wfull = torch.zeros(self.rows_alloc, self.width, dtype=torch.float32, device=dev)
         self._W = self._Wfull[: self.rows]
-        self._M = torch.zeros(self.rows, DIM, dtype=torch.float32, device=dev)
+        self._M = torch.zeros(self.rows, self.width, dtype=torch.float32, device=dev)
         self._V = torch.full_like(self._M, _SLOT_INIT.get(self.optimizer, 0.0))   # (Adagrad: its initial accumulator)
         self.rowmap = torch.zeros(2 * self.rows, dtype=torch.int32, device=dev)
         self.adam_rows = (0, 0) if adam_rows is None else (int(adam_rows[0]), int(adam_rows[1]))
         self.state_buf = _dev_bytes(_lib.STATE_DTYPE.itemsize, dev)
         self.packet_floats = int(self.lib.anirec_packet_floats(self.max_batch))
         self.packets = torch.zeros(self.n_seg * self.packet_floats, dtype=torch.float32, device=dev)
-        ws = int(self.lib.anirec_train_workspace_bytes(self.max_batch, self.arena_steps))
+        if self.w_entry:
+            ws = int(self.lib.anirec_train_workspace_bytes_w(self.max_batch, self.arena_steps, self.width))
+        else:
+            ws = int(self.lib.anirec_train_workspace_bytes(self.max_batch, self.arena_steps))
         if ws == 0:
             raise _lib.AnirecError("anirec_train_workspace_bytes rejected the geometry")
         self.workspace = _dev_bytes(ws, dev)
@@ -180,7 +200,7 @@ class TrainEngine:
         """Load embedding tables (numpy or torch, fp32) and refresh the L2 partial sums."""
         U = torch.as_tensor(U, dtype=torch.float32)
         A = torch.as_tensor(A, dtype=torch.float32)
-        assert U.shape == (self.n_user_rows, DIM) and A.shape == (self.n_anime_rows, DIM)
+        assert U.shape == (self.n_user_rows, self.width) and A.shape == (self.n_anime_rows, self.width)
         self.stream.synchronize()
         self._W[: self.n_user_rows].copy_(U)
         self._W[self.n_user_rows:].copy_(A)
@@ -195,7 +215,7 @@ class TrainEngine:
         torch.cuda.synchronize(self.device)
 
     def slot_tensors(self):
-        """(Keras slot name, [rows, 128] table tensor) of this engine's optimiser, e.g. (("m", M), ("v", V))."""
+        """(Keras slot name, [rows, width] table tensor) of this engine's optimiser, e.g. (("m", M), ("v", V))."""
         return tuple((name, getattr(self, t)) for name, t in _SLOTS[self.optimizer])
 
     def optimizer_state(self, iterations=0):
@@ -251,8 +271,15 @@ class TrainEngine:
     def _sp(self):
         return C.c_void_p(self.stream.cuda_stream)
 
+    def _stage(self, name, *args):
+        """One descriptor call: NAME(desc, args..., stream), or its twin NAME_w(desc, width, args..., stream)."""
+        if self.w_entry:
+            name += "_w"
+            args = (self.width,) + args
+        _lib.check(getattr(self.lib, name)(C.byref(self.desc), *args, self._sp()), name)
+
     def init_reg(self):
-        _lib.check(self.lib.anirec_train_init_reg(C.byref(self.desc), self._sp()), "anirec_train_init_reg")
+        self._stage("anirec_train_init_reg")
 
     # ---- epoch data ----------------------------------------------------------------
     def set_epoch(self, user_idx, anime_idx, rating, starts, counts, alphas, global_counts=None):
@@ -299,20 +326,19 @@ class TrainEngine:
 
     # ---- stages (unit-testable) -----------------------------------------------------
     def prep(self, first_step, n_steps):
-        _lib.check(self.lib.anirec_train_prep(C.byref(self.desc), first_step, n_steps, self._sp()),
-                   "anirec_train_prep")
+        self._stage("anirec_train_prep", first_step, n_steps)
 
     def fwd(self):
-        _lib.check(self.lib.anirec_train_fwd(C.byref(self.desc), self._sp()), "anirec_train_fwd")
+        self._stage("anirec_train_fwd")
 
     def head(self):
-        _lib.check(self.lib.anirec_train_head(C.byref(self.desc), self._sp()), "anirec_train_head")
+        self._stage("anirec_train_head")
 
     def bwd(self):
-        _lib.check(self.lib.anirec_train_bwd(C.byref(self.desc), self._sp()), "anirec_train_bwd")
+        self._stage("anirec_train_bwd")
 
     def adam(self):
-        _lib.check(self.lib.anirec_train_adam(C.byref(self.desc), self._sp()), "anirec_train_adam")
+        self._stage("anirec_train_adam")
 
     def adam_users(self):
         _lib.check(self.lib.anirec_train_adam_part(C.byref(self.desc), 1, self._sp()), "anirec_train_adam_part")
@@ -325,6 +351,8 @@ class TrainEngine:
         "lazy_catchup", "lazy_adam", "lazy_flush", "lazy_reduce"} -> mean duration [us] of the launches made since the
         last call (None = not launched) and, under "launches", their counts; then arms / disarms.  Armed steps run
         eagerly and synchronise after every launch."""
+        if self.width != DIM:
+            raise _lib.AnirecError("anirec_train_stage_ticks exists at embedding width 128 only")
         us = (C.c_float * 8)()
         nl = (C.c_int32 * 8)()
         _lib.check(self.lib.anirec_train_stage_ticks(C.byref(self.desc), int(bool(enable)), us, nl, self._sp()),
@@ -378,7 +406,11 @@ class TrainEngine:
             n_steps = self.n_steps - first_step
         if self._trainer is None:
             h = C.c_void_p()
-            _lib.check(self.lib.anirec_trainer_create(C.byref(self.desc), C.byref(h)), "anirec_trainer_create")
+            if self.w_entry:    # (the handle carries the width: run / set_metrics / destroy are the same calls)
+                _lib.check(self.lib.anirec_trainer_create_w(C.byref(self.desc), self.width, C.byref(h)),
+                           "anirec_trainer_create_w")
+            else:
+                _lib.check(self.lib.anirec_trainer_create(C.byref(self.desc), C.byref(h)), "anirec_trainer_create")
             self._trainer = h
             if self.metrics:
                 _lib.check(self.lib.anirec_trainer_set_metrics(h, self.metrics, _lib.ptr(self.metric_acc)),
@@ -403,7 +435,11 @@ class TrainEngine:
             torch.cuda.synchronize(self.device)
         # no rows (a rank's empty share of a split validation set): the sums stay 0 and nothing is launched — the
         # entry points refuse the empty tensors' null pointers before they look at the count
-        if u.numel() and self.metrics:
+        if u.numel() and self.w_entry:      # (mask 0 with a NULL accumulator is anirec_eval)
+            _lib.check(self.lib.anirec_eval_metrics_w(C.byref(self.desc), self.width, self.metrics,
+                                                      _lib.ptr(self.val_metric_acc), _lib.ptr(u), _lib.ptr(a),
+                                                      _lib.ptr(t), int(u.numel()), self._sp()), "anirec_eval_metrics_w")
+        elif u.numel() and self.metrics:
             _lib.check(self.lib.anirec_eval_metrics(C.byref(self.desc), self.metrics, _lib.ptr(self.val_metric_acc),
                                                     _lib.ptr(u), _lib.ptr(a), _lib.ptr(t), int(u.numel()),
                                                     self._sp()), "anirec_eval_metrics")
@@ -472,7 +508,7 @@ def _align(x, a=256):
     return (x + a - 1) // a * a
 
 
-def workspace_layout(max_batch, arena_steps):
+def workspace_layout(max_batch, arena_steps, width=DIM):
     cap = max_batch
     capC = (cap + cap // _lib.CHUNK + 2 + 3) & ~3
     off = 0
@@ -481,7 +517,7 @@ def workspace_layout(max_batch, arena_steps):
     for name, nbytes in (("su", 4 * cap), ("sa", 4 * cap), ("dy", 4 * cap),
                          ("hpart", 2 * 4 * 8 * _lib.MAX_SEG * ((cap + 255) // 256)), ("pub", 2 * 64), ("sel", 16),
                          ("regpart", 4 * 4 * _lib.ADAM_BLOCKS),
-                         ("P", 2 * 4 * 2 * capC * DIM), ("S", 2 * 4 * 2 * capC)):
+                         ("P", 2 * 4 * 2 * capC * width), ("S", 2 * 4 * 2 * capC)):
         lay[name] = (off, nbytes)
         off += _align(nbytes)
     a1 = _align(4 * 2 * cap)
@@ -499,7 +535,7 @@ def workspace_layout(max_batch, arena_steps):
 
 def read_ws(engine, name, dtype=np.float32):
     """Copy one named workspace array back to the host (tests only)."""
-    lay = workspace_layout(engine.max_batch, engine.arena_steps)
+    lay = workspace_layout(engine.max_batch, engine.arena_steps, engine.width)
     off, nbytes = lay[name]
     engine.synchronize()
     raw = engine.workspace[off:off + nbytes].cpu().numpy()
@@ -508,7 +544,7 @@ def read_ws(engine, name, dtype=np.float32):
 
 def read_slot(engine, step):
     """Sorted-batch + chunk tables of one prepared step (tests only)."""
-    lay = workspace_layout(engine.max_batch, engine.arena_steps)
+    lay = workspace_layout(engine.max_batch, engine.arena_steps, engine.width)
     cap, capC = lay["cap"], lay["capC"]
     base = lay["arena"] + lay["slot_bytes"] * (step % engine.arena_steps)
     engine.synchronize()

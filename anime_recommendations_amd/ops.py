@@ -4,6 +4,8 @@ Names follow the reference: ``get_weights`` row-normalisation (similar_anime.py:
 cosine neighbours (similar_users.py:290-296), ``model.predict`` (model_recs.py:394).
 A head dict (w, b, gamma, beta, mov_mean, mov_var) may carry an "activation" (Keras name, ``schedule.ACTIVATIONS``);
 without one the head is the reference's sigmoid.
+The exact ops take the embedding width from the tables (``shape[1]``, one of ``_lib.WIDTHS``): 128 runs the entry
+points it always ran, another width their ``*_w`` twins.  The ``*_mfma`` ops exist at width 128 only.
 """
 from __future__ import annotations
 
@@ -36,14 +38,33 @@ def _need_gpu():
         raise _lib.AnirecError("no GPU: the anime_recommendations_amd hot path needs an MI355X")
 
 
+def _width(*tables):
+    """The common row width of 2-D fp32 device tables, checked against the supported widths."""
+    w = int(tables[0].shape[1])
+    for t in tables:
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == w, "fp32 [n, width] device tables"
+    return _lib.check_width(w)
+
+
+def _need_128(tables, exact):
+    """The matrix-core paths are specialised for 128-wide rows: say which exact op serves another width."""
+    for t in tables:
+        if t.dim() != 2 or t.shape[1] != DIM:
+            raise ValueError("the MFMA path takes %d-wide tables (got width %d): call ops.%s, which takes the width "
+                             "from the tables" % (DIM, t.shape[-1], exact))
+
+
 def rownorm(W, device="cuda:0"):
     """``W / np.linalg.norm(W, axis=1).reshape(-1, 1)`` on the GPU (fp32, no epsilon)."""
     _need_gpu()
     lib = _lib.load()
     W = _f32(W, device)
-    assert W.dim() == 2 and W.shape[1] == DIM
+    dim = _width(W)
     out = torch.empty_like(W)
-    _lib.check(lib.anirec_rownorm(_lib.ptr(W), W.shape[0], _lib.ptr(out), _stream()), "anirec_rownorm")
+    if dim == DIM:
+        _lib.check(lib.anirec_rownorm(_lib.ptr(W), W.shape[0], _lib.ptr(out), _stream()), "anirec_rownorm")
+    else:
+        _lib.check(lib.anirec_rownorm_w(_lib.ptr(W), W.shape[0], dim, _lib.ptr(out), _stream()), "anirec_rownorm_w")
     return out
 
 
@@ -51,10 +72,14 @@ def cosine_scores(What, q):
     """``np.dot(What, What[q])`` with the library's fixed fp32 summation order."""
     _need_gpu()
     lib = _lib.load()
-    assert What.is_cuda and What.dtype == torch.float32 and What.shape[1] == DIM
+    dim = _width(What)
     out = torch.empty(What.shape[0], dtype=torch.float32, device=What.device)
-    _lib.check(lib.anirec_cosine_scores(_lib.ptr(What), What.shape[0], int(q), _lib.ptr(out), _stream()),
-               "anirec_cosine_scores")
+    if dim == DIM:
+        _lib.check(lib.anirec_cosine_scores(_lib.ptr(What), What.shape[0], int(q), _lib.ptr(out), _stream()),
+                   "anirec_cosine_scores")
+    else:
+        _lib.check(lib.anirec_cosine_scores_w(_lib.ptr(What), What.shape[0], dim, int(q), _lib.ptr(out), _stream()),
+                   "anirec_cosine_scores_w")
     return out
 
 
@@ -67,7 +92,7 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
     """
     _need_gpu()
     lib = _lib.load()
-    assert What.is_cuda and What.dtype == torch.float32 and What.shape[1] == DIM
+    dim = _width(What)
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")
@@ -95,10 +120,13 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
     if workspace is None:
         nb = lib.anirec_topk_large_workspace_bytes(n, nq, k) if large else lib.anirec_topk_workspace_bytes(n, nq)
         workspace = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-    fn, name = ((lib.anirec_cosine_topk_large, "anirec_cosine_topk_large") if large
-                else (lib.anirec_cosine_topk, "anirec_cosine_topk"))
-    _lib.check(fn(_lib.ptr(What), n, _lib.ptr(q), nq, _lib.ptr(keep_t), int(bool(exclude_self)), k, _lib.ptr(out_i),
-                  _lib.ptr(out_s), _lib.ptr(workspace), workspace.numel(), _stream()), name)
+    name = "anirec_cosine_topk_large" if large else "anirec_cosine_topk"
+    tail = (_lib.ptr(q), nq, _lib.ptr(keep_t), int(bool(exclude_self)), k, _lib.ptr(out_i), _lib.ptr(out_s),
+            _lib.ptr(workspace), workspace.numel(), _stream())
+    if dim == DIM:
+        _lib.check(getattr(lib, name)(_lib.ptr(What), n, *tail), name)
+    else:       # (the workspaces hold score rows only: the same sizes at every width)
+        _lib.check(getattr(lib, name + "_w")(_lib.ptr(What), n, dim, *tail), name + "_w")
     return out_i, out_s
 
 
@@ -209,7 +237,8 @@ def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None,
     Returns (idx, score, n_fallback)."""
     _need_gpu()
     lib = _lib.load()
-    assert What.is_cuda and What.dtype == torch.float32 and What.shape[1] == DIM
+    _need_128((What,), "cosine_topk")
+    assert What.is_cuda and What.dtype == torch.float32
     if not (1 <= k <= MAX_TOPK - 1):
         raise ValueError("k must be in 1..%d" % (MAX_TOPK - 1))
     dev, n = What.device, What.shape[0]
@@ -324,9 +353,15 @@ def predict_pairs(U, A, head, user_idx, anime_idx):
     assert ui.numel() == ai.numel()
     p = torch.empty(ui.numel(), dtype=torch.float32, device=dev)
     h = _head_struct(head)
-    _lib.check(lib.anirec_predict_pairs_act(_lib.ptr(U), _lib.ptr(A), _lib.ptr(ui), _lib.ptr(ai),
-                                            int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
-               "anirec_predict_pairs")
+    dim = _width(U, A)
+    if dim == DIM:
+        _lib.check(lib.anirec_predict_pairs_act(_lib.ptr(U), _lib.ptr(A), _lib.ptr(ui), _lib.ptr(ai),
+                                                int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
+                   "anirec_predict_pairs")
+    else:
+        _lib.check(lib.anirec_predict_pairs_w(_lib.ptr(U), _lib.ptr(A), dim, _lib.ptr(ui), _lib.ptr(ai),
+                                              int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
+                   "anirec_predict_pairs_w")
     return p
 
 
@@ -338,11 +373,19 @@ def predict_grid(U, A, head, users):
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())
     out = torch.empty(n_q, n_a, dtype=torch.float32, device=dev)
-    ws = torch.empty(int(lib.anirec_predict_workspace_bytes(n_a, max(n_q, 1), 0)), dtype=torch.uint8, device=dev)
+    dim = _width(U, A)
     h = _head_struct(head)
-    _lib.check(lib.anirec_predict_grid_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
-                                           _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
-               "anirec_predict_grid")
+    if dim == DIM:
+        ws = torch.empty(int(lib.anirec_predict_workspace_bytes(n_a, max(n_q, 1), 0)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.anirec_predict_grid_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
+                                               _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
+                   "anirec_predict_grid")
+    else:
+        ws = torch.empty(int(lib.anirec_predict_workspace_bytes_w(n_a, max(n_q, 1), 0, dim)), dtype=torch.uint8,
+                         device=dev)
+        _lib.check(lib.anirec_predict_grid_w(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h),
+                                             _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
+                   "anirec_predict_grid_w")
     return out
 
 
@@ -352,6 +395,7 @@ def predict_grid_mfma(U, A, head, users, out=None):
     (include/anirec.h), looser than 1e-5 once |hs| max act' exceeds ~0.3."""
     _need_gpu()
     lib = _lib.load()
+    _need_128((U, A), "predict_grid")
     dev = U.device
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())
@@ -386,14 +430,24 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
     if watched_bits is not None:
         wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
         assert wb.shape == (n_q, (n_a + 31) // 32)
-    nb = (lib.anirec_predict_topk_large_workspace_bytes(n_a, n_q, k) if large
-          else lib.anirec_predict_workspace_bytes(n_a, n_q, 1))
-    ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+    dim = _width(U, A)
     h = _head_struct(head)
-    fn, name = ((lib.anirec_predict_topk_large_act, "anirec_predict_topk_large_act") if large
-                else (lib.anirec_predict_topk_act, "anirec_predict_topk"))
-    _lib.check(fn(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head), _lib.ptr(wb), k,
-                  _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(), _stream()), name)
+    if dim == DIM:
+        nb = (lib.anirec_predict_topk_large_workspace_bytes(n_a, n_q, k) if large
+              else lib.anirec_predict_workspace_bytes(n_a, n_q, 1))
+        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+        fn, name = ((lib.anirec_predict_topk_large_act, "anirec_predict_topk_large_act") if large
+                    else (lib.anirec_predict_topk_act, "anirec_predict_topk"))
+        _lib.check(fn(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head), _lib.ptr(wb), k,
+                      _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(), _stream()), name)
+    else:
+        nb = (lib.anirec_predict_topk_large_workspace_bytes_w(n_a, n_q, k, dim) if large
+              else lib.anirec_predict_workspace_bytes_w(n_a, n_q, 1, dim))
+        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+        fn, name = ((lib.anirec_predict_topk_large_w, "anirec_predict_topk_large_w") if large
+                    else (lib.anirec_predict_topk_w, "anirec_predict_topk_w"))
+        _lib.check(fn(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head), _lib.ptr(wb),
+                      k, _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(), _stream()), name)
     return out_i, out_p
 
 
@@ -403,6 +457,7 @@ def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fal
     Returns (idx, p, n_fallback)."""
     _need_gpu()
     lib = _lib.load()
+    _need_128((U, A), "predict_topk")
     dev = U.device
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())

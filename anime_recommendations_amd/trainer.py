@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import ops, schedule
+from . import _lib, ops, schedule
 from .data import RatingTable
 
 
@@ -125,8 +125,7 @@ def _column(col, rows, dtype, dev):
 def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda:0") -> FitResult:
     """Train the embedding model on ``table`` (a ``data.RatingTable`` of NumPy columns or an
     ``ingest.EncodedRatings`` whose columns already live in HBM); returns History + last and best weights."""
-    if cfg.embedding_size != 128:
-        raise ValueError("libanirec kernels are specialised for embedding_size 128 (config.yaml:63)")
+    width = _lib.check_width(cfg.embedding_size)     # (ValueError before anything is allocated or the engine touched)
     kind = schedule.resolve_optimizer(cfg.optimizer)
     loss_name, act_name = schedule.resolve_loss(cfg.loss), schedule.resolve_activation(cfg.activation)
     metrics = schedule.resolve_metrics(cfg.metrics, act_name)
@@ -143,7 +142,7 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
         from .engine import TrainEngine
         engine = TrainEngine(table.n_users, table.n_anime, max_batch=min(cfg.batch_size, n_train),
                              l2=cfg.l2_reg_factor, arena_steps=cfg.arena_steps, device=device, optimizer=kind,
-                             loss=loss_name, activation=act_name, metrics=mask)
+                             loss=loss_name, activation=act_name, metrics=mask, width=width)
     elif getattr(engine, "optimizer", "adam") != kind:
         raise ValueError("the engine was built for optimizer %r, the config asks for %r"
                          % (getattr(engine, "optimizer", "adam"), kind))
@@ -151,11 +150,14 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
         have = getattr(engine, what, default)
         if have != want:
             raise ValueError("the engine was built for %s %r, the config asks for %r" % (what, have, want))
+    if getattr(engine, "width", _lib.DIM) != width:
+        raise ValueError("the engine was built for embedding width %d, the config asks for %d"
+                         % (getattr(engine, "width", _lib.DIM), width))
     if getattr(engine, "metrics", 0) != mask:
         raise ValueError("the engine accumulates metrics %#x, the config asks for %#x (%s)"
                          % (getattr(engine, "metrics", 0), mask, ", ".join(k for k, _ in metrics)))
     dev = engine.device
-    U0, A0, w0 = init_weights(table.n_users, table.n_anime, 128, cfg.seed, cfg.kernel_initializer)
+    U0, A0, w0 = init_weights(table.n_users, table.n_anime, width, cfg.seed, cfg.kernel_initializer)
     engine.set_head(w=w0)
     engine.set_weights(U0, A0)
     engine.reset_optimizer()

@@ -22,7 +22,16 @@
  *    the documented extent is written, padding included.  Count and flag words (*n_out, *n_unique, out_max2,
  *    *err_flag, the flags arrays) are overwritten by the call: the caller need not clear them.
  *  - embedding rows are fp32, row-major, exactly ANIREC_DIM (=128) wide
- *    (reference: config/config.yaml:63 embedding_size: 128).
+ *    (reference: config/config.yaml:63 embedding_size: 128) — for every entry point without a `dim` argument.
+ *  - OTHER WIDTHS (the reference's --embedding_size, neural_network.py:75-85): an entry point whose work depends on the
+ *    row width has a twin NAME_w with an added `int32_t dim`; rows are then `dim` floats wide, dim in {32, 64, 128,
+ *    256} — a row is dim / 4 lanes of float4, the 8-, 16-, 32- and 64-lane groups of a 64-lane wave.  Any other dim:
+ *    ANIREC_EINVAL (0 from a *_bytes_w function) before anything is enqueued or written.  NAME(...) is
+ *    NAME_w(..., ANIREC_DIM): same kernels, same results.  Wherever a comment below says [rows][128], read
+ *    [rows][dim] for the twin.  128 only (no twin): the MFMA paths (*_mfma, anirec_cosine_topk_job), the lazy dense
+ *    Adam (a descriptor with lazy != 0 and dim != 128 is ANIREC_EINVAL), the multi-GPU calls (anirec_dist_*,
+ *    anirec_train_adam_part, dense_mode 1 and 2, n_seg > 1: ANIREC_EINVAL at another width) and
+ *    anirec_train_stage_ticks.
  */
 #ifndef ANIREC_H
 #define ANIREC_H
@@ -46,7 +55,7 @@ extern "C" {
 
 enum {
   ANIREC_OK = 0,
-  ANIREC_EINVAL = -1,     /* bad argument (null pointer, size out of range, dim != 128) */
+  ANIREC_EINVAL = -1,     /* bad argument (null pointer, size out of range, dim not one of 32, 64, 128, 256) */
   ANIREC_ENODEVICE = -2,  /* no HIP device / wrong architecture */
   ANIREC_EWORKSPACE = -3, /* workspace too small */
   ANIREC_ECAPTURE = -4,   /* graph capture / instantiate failed */
@@ -172,7 +181,7 @@ typedef struct anirec_train_desc {
   int32_t lazy;         /* != 0 (`lazy_state` set): the dense update of the rows a batch does not touch is deferred —
                            dense_mode 0: both tables, inside anirec_trainer_run; dense_mode 1: the rank's user rows,
                            inside anirec_dist_run / the stepper calls (LAZY USER ROWS); ignored in dense_mode 2 */
-  /* tables: rows [0,n_user_rows) users, then n_anime_rows anime; [rows][128] fp32.
+  /* tables: rows [0,n_user_rows) users, then n_anime_rows anime; [rows][128] fp32 ([rows][dim] for the _w calls).
    * W = embeddings, M/V = Adam first/second moments. */
   float *W, *M, *V;
   int32_t *rowmap;      /* [2][n_user_rows+n_anime_rows] (one map per step parity); zero before first use, left zero */
@@ -187,8 +196,9 @@ typedef struct anirec_train_desc {
   /* head packets: n_seg packets of anirec_packet_floats(max_batch) floats each; packet
    * my_seg is written by the fwd kernel, the others by the caller's all-gather. */
   float *packets;
-  float *dense_grad;    /* [dense_rows*128] gradients then [dense_rows] self-coefficient sums, or NULL */
-  void *workspace;      /* >= anirec_train_workspace_bytes(max_batch, arena_steps); zero before first use */
+  float *dense_grad;    /* [dense_rows*128] gradients then [dense_rows] self-coefficient sums, or NULL (128 only) */
+  void *workspace;      /* >= anirec_train_workspace_bytes(max_batch, arena_steps) (_w calls: ..._bytes_w(max_batch,
+                           arena_steps, dim)); zero before first use */
   size_t workspace_bytes;
   void *lazy_state;     /* lazy != 0: anirec_train_lazy_bytes(rows) bytes, zero before first use; else NULL */
   int32_t optimizer;    /* ANIREC_OPT_*: the update rule of the adam stage.  The lazy update exists for ADAM only: a
@@ -203,17 +213,22 @@ typedef struct anirec_train_desc {
  * up to a multiple of 4 */
 size_t anirec_packet_floats(int32_t max_batch);
 size_t anirec_train_workspace_bytes(int32_t max_batch, int32_t arena_steps);
+/* the workspace holds the chunk partial rows, so its size and its layout depend on the width: every call that takes
+ * the descriptor's workspace has a _w twin */
+size_t anirec_train_workspace_bytes_w(int32_t max_batch, int32_t arena_steps, int32_t dim);
 /* per-row state of the lazy dense Adam: the step each row has been updated to + its sum(W^2) of the window's steps */
 size_t anirec_train_lazy_bytes(int32_t table_rows);
 
 /* state.reg_sumsq <- sum(W^2) (both tables).  Call once after (re)loading weights. */
 int anirec_train_init_reg(const anirec_train_desc *d, void *stream);
+int anirec_train_init_reg_w(const anirec_train_desc *d, int32_t dim, void *stream);
 
 /* Sort each batch of steps [first_step, first_step+n_steps) by table row and cut the
  * per-row runs into chunks (<= ANIREC_CHUNK ratings) for the backward pass.  Results
  * land in arena slot (step % arena_steps).  Replaces TF's IndexedSlices ->
  * unsorted_segment_sum densification inside model.fit. */
 int anirec_train_prep(const anirec_train_desc *d, int32_t first_step, int32_t n_steps, void *stream);
+int anirec_train_prep_w(const anirec_train_desc *d, int32_t dim, int32_t first_step, int32_t n_steps, void *stream);
 
 /* The four stages of one step.  They read the step index from device memory (state->step_fwd /
  * state->step_bwd / a workspace word head publishes) so that a captured graph can be replayed for every step;
@@ -230,6 +245,13 @@ int anirec_train_fwd(const anirec_train_desc *d, void *stream);
 int anirec_train_head(const anirec_train_desc *d, void *stream);
 int anirec_train_bwd(const anirec_train_desc *d, void *stream);
 int anirec_train_adam(const anirec_train_desc *d, void *stream);
+/* The stages at width dim (tables, workspace and dense one-GPU descriptor of that width).  prep and head do
+ * width-independent work (a sort of indices; one dot product per rating) but find their arrays in the workspace, whose
+ * layout depends on the width. */
+int anirec_train_fwd_w(const anirec_train_desc *d, int32_t dim, void *stream);
+int anirec_train_head_w(const anirec_train_desc *d, int32_t dim, void *stream);
+int anirec_train_bwd_w(const anirec_train_desc *d, int32_t dim, void *stream);
+int anirec_train_adam_w(const anirec_train_desc *d, int32_t dim, void *stream);
 /* Measurement hook (bench.py): while armed, the training kernels stamp each workgroup's first / last instruction
  * with the 100 MHz constant clock and every launch is followed by a synchronisation that turns the stamps into one
  * duration.  Returns per kernel — 0 fwd, 1 head, 2 bwd, 3 adam, 4 lazy catch-up, 5 lazy adam, 6 lazy flush, 7 lazy
@@ -309,6 +331,8 @@ int anirec_dist_run(anirec_dist_stepper *h, anirec_dist_comm *c, int32_t first_s
  * work is needed between replays. */
 typedef struct anirec_trainer anirec_trainer; /* host-side handle: descriptor copy + graph cache */
 int anirec_trainer_create(const anirec_train_desc *d, anirec_trainer **out_host);
+/* a handle for tables of width dim; it carries the width: _run, _set_metrics and _destroy are the same calls */
+int anirec_trainer_create_w(const anirec_train_desc *d, int32_t dim, anirec_trainer **out_host);
 int anirec_trainer_destroy(anirec_trainer *t);
 int anirec_trainer_run(anirec_trainer *t, int32_t first_step, int32_t n_steps, int32_t use_graph,
                        void *stream);
@@ -357,6 +381,10 @@ int anirec_dist_stepper_set_metrics(anirec_dist_stepper *h, uint32_t mask, anire
 /* anirec_eval that also adds the requested kinds of the n validation rows to *acc (same checks as above). */
 int anirec_eval_metrics(const anirec_train_desc *d, uint32_t mask, anirec_metric_acc *acc, const int32_t *user_idx,
                         const int32_t *anime_idx, const float *rating, int32_t n, void *stream);
+/* at width dim; mask 0 with a NULL acc is anirec_eval at that width */
+int anirec_eval_metrics_w(const anirec_train_desc *d, int32_t dim, uint32_t mask, anirec_metric_acc *acc,
+                          const int32_t *user_idx, const int32_t *anime_idx, const float *rating, int32_t n,
+                          void *stream);
 
 /* Standalone fused Adam on a flat fp32 array with an explicit dense gradient
  * (Keras-2.12 Adam dense branch; bit-exact to the oracle given the same g). */
@@ -401,9 +429,12 @@ int anirec_gather_ratings(const int32_t *user_in, const int32_t *anime_in, const
 
 /* What = W / ||W||_2 row-wise, no epsilon (zero row -> NaN like NumPy). */
 int anirec_rownorm(const float *W, int32_t n, float *What, void *stream);
+int anirec_rownorm_w(const float *W, int32_t n, int32_t dim, float *What, void *stream);
 
-/* scores[j] = <What[j], What[q]> for every row j (k-ordered fp32 fma chain). */
+/* scores[j] = <What[j], What[q]> for every row j (k-ordered fp32 fma chain).  _w: the same chain over
+ * k = 0 .. dim-1 in index order. */
 int anirec_cosine_scores(const float *What, int32_t n, int32_t q, float *scores, void *stream);
+int anirec_cosine_scores_w(const float *What, int32_t n, int32_t dim, int32_t q, float *scores, void *stream);
 
 /* Top-k rows by descending score for a batch of query rows of the same table.
  *   queries[nq]   : query row indices
@@ -416,6 +447,10 @@ size_t anirec_topk_workspace_bytes(int32_t n, int32_t nq);
 int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int32_t nq,
                        const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
                        float *out_score, void *workspace, size_t workspace_bytes, void *stream);
+/* (the workspace holds score rows only: anirec_topk_workspace_bytes serves every width) */
+int anirec_cosine_topk_w(const float *What, int32_t n, int32_t dim, const int32_t *queries, int32_t nq,
+                         const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                         float *out_score, void *workspace, size_t workspace_bytes, void *stream);
 
 /* anirec_cosine_topk for ANY k >= 1 (a whole ranking included): the same scores, candidates, order, ties and
  * padding, and for k <= ANIREC_MAX_TOPK the same output.  The radix select finds the k-th key, the winners are
@@ -426,6 +461,10 @@ size_t anirec_topk_large_workspace_bytes(int32_t n, int32_t nq, int32_t k);
 int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *queries, int32_t nq,
                              const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
                              float *out_score, void *workspace, size_t workspace_bytes, void *stream);
+/* (anirec_topk_large_workspace_bytes serves every width) */
+int anirec_cosine_topk_large_w(const float *What, int32_t n, int32_t dim, const int32_t *queries, int32_t nq,
+                               const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                               float *out_score, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Same result as anirec_cosine_topk on the matrix cores: fp16 MFMA candidate scores for all
  * keys with a rigorous error window, exact fp32 fma-chain re-rank of the survivors.
@@ -500,10 +539,14 @@ int anirec_predict_pairs(const float *U, const float *A, const int32_t *user_idx
 int anirec_predict_pairs_act(const float *U, const float *A, const int32_t *user_idx,
                              const int32_t *anime_idx, int32_t n, const anirec_head *head_host,
                              int32_t activation, float *p, void *stream);
+int anirec_predict_pairs_w(const float *U, const float *A, int32_t dim, const int32_t *user_idx,
+                           const int32_t *anime_idx, int32_t n, const anirec_head *head_host,
+                           int32_t activation, float *p, void *stream);
 
 /* Workspace of predict_grid / predict_topk: l2-normalised copies of A and of the query
  * users (+ a batch of rating rows when topk != 0). */
 size_t anirec_predict_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t topk);
+size_t anirec_predict_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t topk, int32_t dim);
 
 /* out[j*n_anime + a] = model(users[j], a) for every anime a (the full rating grid). */
 int anirec_predict_grid(const float *U, const float *A, int32_t n_anime, const int32_t *users,
@@ -512,6 +555,10 @@ int anirec_predict_grid(const float *U, const float *A, int32_t n_anime, const i
 int anirec_predict_grid_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                             int32_t n_users, const anirec_head *head_host, int32_t activation, float *out,
                             void *workspace, size_t workspace_bytes, void *stream);
+/* the _w predict calls take the activation (as the *_act variants) and anirec_predict_workspace_bytes_w bytes */
+int anirec_predict_grid_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                          int32_t n_users, const anirec_head *head_host, int32_t activation, float *out,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* The same grid on the matrix cores: rows are split x = hi + lo in fp16 and accumulated as
  * hi*hi + hi*lo + lo*hi by v_mfma_f32_32x32x16_f16.  Proven bound against exact arithmetic, for cosine c of the
@@ -539,6 +586,10 @@ int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, con
                             int32_t n_users, const anirec_head *head_host, int32_t activation,
                             const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
                             size_t workspace_bytes, void *stream);
+int anirec_predict_topk_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                          int32_t n_users, const anirec_head *head_host, int32_t activation,
+                          const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                          size_t workspace_bytes, void *stream);
 /* anirec_predict_topk_act for ANY k >= 1 (k >= n_anime: a user's whole ranking), as anirec_cosine_topk_large.
  * workspace: anirec_predict_topk_large_workspace_bytes(n_anime, n_users, k) bytes. */
 size_t anirec_predict_topk_large_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t k);
@@ -546,6 +597,11 @@ int anirec_predict_topk_large_act(const float *U, const float *A, int32_t n_anim
                                   int32_t n_users, const anirec_head *head_host, int32_t activation,
                                   const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p,
                                   void *workspace, size_t workspace_bytes, void *stream);
+size_t anirec_predict_topk_large_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t k, int32_t dim);
+int anirec_predict_topk_large_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                                int32_t n_users, const anirec_head *head_host, int32_t activation,
+                                const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p,
+                                void *workspace, size_t workspace_bytes, void *stream);
 
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a

@@ -89,7 +89,8 @@ def go(args):
             per_rank = cfg.batch_size // world
         engine = DistTrainEngine(table.n_users, table.n_anime, min(per_rank, max(1, n_train // world)),
                                  l2=cfg.l2_reg_factor, device="cuda:%d" % local, optimizer=optimizer, loss=loss,
-                                 activation=activation, metrics=schedule.metric_mask(metrics))
+                                 activation=activation, metrics=schedule.metric_mask(metrics),
+                                 width=cfg.embedding_size)
         if rank != 0:
             cfg.verbose = 0
     res = trainer.fit(table, cfg, engine=engine, log=lambda s: (print(s), logger.info(s)))
