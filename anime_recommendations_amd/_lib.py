@@ -204,6 +204,11 @@ PROTOTYPES = {
     "anirec_predict_topk_large_workspace_bytes_w": (_sz, [_i32, _i32, _i32, _i32]),
     "anirec_predict_topk_large_w": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _i32, _vp,
                                               _vp, _vp, _sz, _vp]),
+    # ranks of held-out anime (one entry point, `int32_t dim` among its arguments) and the watched bits of a rating list
+    "anirec_predict_rank_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "anirec_predict_rank": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _vp, _i32, _vp,
+                                      _vp, _vp, _vp, _sz, _vp]),
+    "anirec_seen_bits": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
 }
 
 

@@ -336,6 +336,61 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
 
 
 # ----------------------------------------------------------------------------------------
+# evaluate
+# ----------------------------------------------------------------------------------------
+def held_out_targets(table, test_size, min_rating):
+    """The ranking targets of a rating table: (users, target_row, target_anime, train) — the held-out rows of
+    ``table.split(test_size)`` (the rows trainer.fit validates on) rated at or above ``min_rating``, as the sorted
+    distinct user indices among them, each target's position in that list and its anime index; ``train`` is the
+    training slice."""
+    train, test = table.split(test_size)
+    take = np.asarray(table.rating[test], np.float64) >= float(min_rating)
+    tu, ta = np.asarray(table.user[test])[take], np.asarray(table.anime[test])[take]
+    users, row = np.unique(tu, return_inverse=True)
+    return users.astype(np.int64), row.astype(np.int64).reshape(-1), ta.astype(np.int64), train
+
+
+def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0):
+    """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
+    among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
+    rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
+    mrr, mean_rank, median_rank, n, n_users, test_size, min_rating and the frame's figures as hit_rate@k / ndcg@k).
+    ``model``: weights_io.load_model's dict; its id tables must be the table's."""
+    import torch
+    from . import ops, recs, weights_io
+    U, A = np.asarray(model["U"]), np.asarray(model["A"])
+    mu, ma = model.get("user_ids"), model.get("anime_ids")
+    same = U.shape[0] == table.n_users and A.shape[0] == table.n_anime
+    if same and mu is not None and ma is not None:
+        same = np.array_equal(np.asarray(mu), np.asarray(table.user_ids)) and \
+            np.array_equal(np.asarray(ma), np.asarray(table.anime_ids))
+    if not same:
+        raise ValueError("the model's id tables are not the rating table's: the model holds %d users x %d anime, the "
+                         "table %d users x %d anime (evaluate a model on the data artifact it was trained on)"
+                         % (U.shape[0], A.shape[0], table.n_users, table.n_anime))
+    ks = sorted({int(k) for k in ks})
+    if not ks or ks[0] < 1:
+        raise ValueError("eval_k must list at least one k >= 1 (got %r)" % (ks,))
+    users, row, anime, train = held_out_targets(table, test_size, min_rating)
+    if len(row):
+        tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
+        seen = ops.seen_bits(torch.as_tensor(np.asarray(table.user[train])).cuda(),
+                             torch.as_tensor(np.asarray(table.anime[train])).cuda(), table.n_users, table.n_anime)
+        rank, _ = ops.predict_rank(tU, tA, weights_io.model_head(model), users, row, anime,
+                                   watched_bits=seen[torch.as_tensor(users).cuda()])
+    else:
+        rank = np.zeros(0, np.int32)
+    m = recs.ranking_metrics(rank, ks)
+    frame = pd.DataFrame({"k": ks, "hit_rate": [m["hit_rate"][k] for k in ks], "ndcg": [m["ndcg"][k] for k in ks]})
+    summary = {"n": m["n"], "n_users": int(len(users)), "test_size": int(test_size), "min_rating": float(min_rating),
+               "mrr": m["mrr"], "mean_rank": m["mean_rank"], "median_rank": m["median_rank"]}
+    for k in ks:
+        summary["hit_rate@%d" % k] = m["hit_rate"][k]
+        summary["ndcg@%d" % k] = m["ndcg"][k]
+    return frame, summary
+
+
+# ----------------------------------------------------------------------------------------
 # user_prefs / user_recs
 # ----------------------------------------------------------------------------------------
 MAX_CATEGORIES = 128     # anirec_fave_profile counts at most 128 categories per call

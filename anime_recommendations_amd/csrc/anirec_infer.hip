@@ -1473,3 +1473,263 @@ int anirec_predict_topk_large_w(const float *U, const float *A, int32_t dim, int
 }
 
 }  // extern "C"
+
+// ====================================================================================
+// rank of a target anime among a user's unwatched anime (anirec_predict_rank) and the watched-bit table of a
+// rating list (anirec_seen_bits)
+//
+// rank[t] = how many eligible anime come before target t in the user's whole ranking (anirec_predict_topk_large_*):
+// a count, so no rating row is written and nothing is sorted.  The ratings are the exact path's, bit for bit: rows
+// through rownorm_body<1>, the k-ordered fma chain of scores_body, rating_from_cosine; the order is score_key's.
+//   targets  one thread per target: its indices checked, p[t] by the chain, rank[t] = 0 (k_rank_targets)
+//   count    a workgroup holds 64 targets' user rows in LDS (whole rows: pitch width + 4) and walks the 64-row
+//            tiles of its slice of the anime table, scores_body's 4 x 4 register block per thread; the epilogue
+//            compares each rating's key with the target's and counts.  The per-slice counts of a target meet in an
+//            integer atomicAdd: any order gives the same sum (k_rank_count)
+// ====================================================================================
+namespace anirec {
+
+struct RankArgs {
+  const float *Uh;         // [n_users, dim] normalised rows of the call's users
+  const float *Ah;         // [n_anime, dim] normalised
+  int n_users, n_anime;
+  const int32_t *trow;     // [n_targets] row of target t in the users list
+  const int32_t *tanime;   // [n_targets] its anime
+  int n_targets;
+  const uint32_t *watched; // optional [n_users][wwords]: set bit = not eligible (the target's own bit is ignored)
+  int wwords;
+  float hs, hb;
+  int act;
+  int slices, slice_len;   // workgroup b counts targets [64 (b / slices), +64) over anime [(b % slices) slice_len, +slice_len)
+  int32_t *rank;           // [n_targets]
+  float *p;                // [n_targets]
+  int32_t *err;
+};
+
+__device__ __forceinline__ bool rank_target_ok(const RankArgs &a, int row, int at) {
+  return (uint32_t)row < (uint32_t)a.n_users && (uint32_t)at < (uint32_t)a.n_anime;
+}
+
+template <int kD>
+__global__ __launch_bounds__(256) void k_rank_targets(RankArgs a) {
+  constexpr int kRowV = kD / 4;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.n_targets) return;
+  const int row = a.trow[t], at = a.tanime[t];
+  if (!rank_target_ok(a, row, at)) {  // nothing is read through a bad index
+    *a.err = 1;
+    a.rank[t] = -1;
+    a.p[t] = __uint_as_float(0x7FC00000u);
+    return;
+  }
+  const float4 *q4 = reinterpret_cast<const float4 *>(a.Uh) + (size_t)row * kRowV;
+  const float4 *w4 = reinterpret_cast<const float4 *>(a.Ah) + (size_t)at * kRowV;
+  float s = 0.f;
+#pragma unroll 8
+  for (int k4 = 0; k4 < kRowV; ++k4) {
+    const float4 x = w4[k4], y = q4[k4];
+    s = __fmaf_rn(x.x, y.x, s);
+    s = __fmaf_rn(x.y, y.y, s);
+    s = __fmaf_rn(x.z, y.z, s);
+    s = __fmaf_rn(x.w, y.w, s);
+  }
+  a.p[t] = rating_from_cosine<-1>(s, a.hs, a.hb, a.act);
+  a.rank[t] = 0;
+}
+
+template <int kD>
+__global__ __launch_bounds__(256) void k_rank_count(RankArgs a) {
+  constexpr int kSV = ScoreGeom<kD>::kSV, kPitch = ScoreGeom<kD>::kPitch, kRowV = ScoreGeom<kD>::kRowV;
+  constexpr int kQPitch = kD + 4;  // the targets' rows stay whole: staged once for every tile of the slice
+  __shared__ __attribute__((aligned(16))) float Qs[kTile * kQPitch];
+  __shared__ __attribute__((aligned(16))) float Ws[kTile * kPitch];
+  const int tid = threadIdx.x;
+  const int q0 = (blockIdx.x / a.slices) * kTile;
+  const int j_lo = (blockIdx.x % a.slices) * a.slice_len;  // a multiple of 64: a tile's watched bits are two whole words
+  const int j_hi = min(a.n_anime, j_lo + a.slice_len);
+  const int tx = tid & 15, ty = tid >> 4;  // rows tx+16r, targets ty+16q
+  int at[4], wrow[4], cnt[4];              // at < 0: no target
+  uint32_t kt[4];
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) {
+    const int t = q0 + ty + 16 * qq;
+    at[qq] = -1;
+    wrow[qq] = 0;
+    kt[qq] = 0u;
+    cnt[qq] = 0;
+    if (t < a.n_targets) {
+      const int row = a.trow[t], x = a.tanime[t];
+      if (rank_target_ok(a, row, x)) {
+        at[qq] = x;
+        wrow[qq] = row;
+        kt[qq] = score_key(a.p[t]);
+      }
+    }
+  }
+  for (int e = tid; e < kTile * kRowV; e += 256) {
+    const int r = e / kRowV, cidx = e % kRowV;
+    float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q0 + r < a.n_targets) {
+      const int row = a.trow[q0 + r];
+      if ((uint32_t)row < (uint32_t)a.n_users) qv = reinterpret_cast<const float4 *>(a.Uh)[(size_t)row * kRowV + cidx];
+    }
+    *reinterpret_cast<float4 *>(&Qs[r * kQPitch + cidx * 4]) = qv;
+  }
+  for (int j0 = j_lo; j0 < j_hi; j0 += kTile) {
+    float acc[4][4];
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[qq][r] = 0.f;
+#pragma unroll
+    for (int k0 = 0; k0 < kRowV; k0 += kSV) {  // (one pass up to 128)
+      __syncthreads();                         // the previous tile / slice has been read
+      for (int e = tid; e < kTile * kSV; e += 256) {
+        const int r = e / kSV, cidx = e % kSV;
+        float4 wv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (j0 + r < a.n_anime) wv = reinterpret_cast<const float4 *>(a.Ah)[(size_t)(j0 + r) * kRowV + k0 + cidx];
+        *reinterpret_cast<float4 *>(&Ws[r * kPitch + cidx * 4]) = wv;
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int k4 = 0; k4 < kSV; ++k4) {
+        float4 qv[4], wv[4];
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq)
+          qv[qq] = *reinterpret_cast<const float4 *>(&Qs[(ty + 16 * qq) * kQPitch + (k0 + k4) * 4]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          wv[r] = *reinterpret_cast<const float4 *>(&Ws[(tx + 16 * r) * kPitch + k4 * 4]);
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float s = acc[qq][r];
+            s = __fmaf_rn(wv[r].x, qv[qq].x, s);
+            s = __fmaf_rn(wv[r].y, qv[qq].y, s);
+            s = __fmaf_rn(wv[r].z, qv[qq].z, s);
+            s = __fmaf_rn(wv[r].w, qv[qq].w, s);
+            acc[qq][r] = s;
+          }
+      }
+    }
+    const int w0 = j0 >> 5;
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      if (at[qq] < 0) continue;
+      uint32_t wb[2] = {0u, 0u};  // watched bits of anime j0 .. j0 + 63
+      if (a.watched) {
+        const uint32_t *wr = a.watched + (size_t)wrow[qq] * a.wwords;
+        wb[0] = wr[w0];
+        if (w0 + 1 < a.wwords) wb[1] = wr[w0 + 1];
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = j0 + tx + 16 * r;
+        if (j >= a.n_anime || j == at[qq]) continue;
+        if ((wb[r >> 1] >> (tx + 16 * (r & 1))) & 1u) continue;
+        const uint32_t key = score_key(rating_from_cosine<-1>(acc[qq][r], a.hs, a.hb, a.act));
+        cnt[qq] += (key > kt[qq] || (key == kt[qq] && j < at[qq])) ? 1 : 0;
+      }
+    }
+  }
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) {
+    int c = cnt[qq];  // the 16 lanes tx = 0..15 of a target are neighbours in the wave
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) c += __shfl_xor(c, o, 16);
+    if (tx == 0 && at[qq] >= 0 && c) atomicAdd(&a.rank[q0 + ty + 16 * qq], c);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_seen_bits(const int32_t *__restrict__ user_idx,
+                                                   const int32_t *__restrict__ anime_idx, long long n, int n_users,
+                                                   int n_anime, int wwords, uint32_t *__restrict__ bits,
+                                                   int32_t *__restrict__ err) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int u = user_idx[i], x = anime_idx[i];
+  if ((uint32_t)u >= (uint32_t)n_users || (uint32_t)x >= (uint32_t)n_anime) {
+    *err = 1;
+    return;
+  }
+  atomicOr(&bits[(size_t)u * wwords + (x >> 5)], 1u << (x & 31));
+}
+
+// slices of the anime table per block of 64 targets: enough workgroups to fill the chip when the targets are few
+constexpr int kRankBlocks = 1024;
+
+}  // namespace anirec
+
+extern "C" {
+
+size_t anirec_predict_rank_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t n_targets, int32_t dim) {
+  if (n_anime < 1 || n_users < 1 || n_targets < 0 || !dim_ok(dim)) return 0;
+  return norm_bytes(n_anime, n_users, dim);
+}
+
+int anirec_predict_rank(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                        int32_t n_users, const anirec_head *head, int32_t activation, const uint32_t *watched,
+                        const int32_t *target_row, const int32_t *target_anime, int32_t n_targets, int32_t *out_rank,
+                        float *out_p, int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream) {
+  if (!dim_ok(dim) || !act_ok(activation) || n_anime < 1 || n_users < 0 || n_targets < 0) return ANIREC_EINVAL;
+  if (n_targets == 0 || n_users == 0) return ANIREC_OK;
+  if (!U || !A || !users || !head || !target_row || !target_anime || !out_rank || !out_p || !err_flag || !workspace)
+    return ANIREC_EINVAL;
+  if (workspace_bytes < norm_bytes(n_anime, n_users, dim)) return ANIREC_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  float *Ah = (float *)workspace;
+  float *Uh = Ah + (size_t)n_anime * dim;
+  ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
+  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
+  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
+  ANIREC_HIP_CHECK(hipGetLastError());
+  RankArgs a;
+  a.Uh = Uh;
+  a.Ah = Ah;
+  a.n_users = n_users;
+  a.n_anime = n_anime;
+  a.trow = target_row;
+  a.tanime = target_anime;
+  a.n_targets = n_targets;
+  a.watched = watched;
+  a.wwords = (n_anime + 31) / 32;
+  head_affine(head, &a.hs, &a.hb);
+  a.act = activation;
+  a.rank = out_rank;
+  a.p = out_p;
+  a.err = err_flag;
+  const int tblocks = (n_targets + kTile - 1) / kTile, tiles = (n_anime + kTile - 1) / kTile;
+  int S = tblocks < kRankBlocks ? kRankBlocks / tblocks : 1;
+  if (S > tiles) S = tiles;
+  a.slice_len = (tiles + S - 1) / S * kTile;
+  a.slices = (n_anime + a.slice_len - 1) / a.slice_len;
+  const dim3 g0((n_targets + 255) / 256), g1((unsigned)tblocks * (unsigned)a.slices);
+  auto launch = [&](auto kd) {
+    constexpr int kD = decltype(kd)::value;
+    hipLaunchKernelGGL(k_rank_targets<kD>, g0, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_rank_count<kD>, g1, dim3(256), 0, s, a);
+  };
+  if (dim == kDim)
+    launch(std::integral_constant<int, kDim>());
+  else
+    with_width(dim, launch);
+  return (int)hipGetLastError();
+}
+
+int anirec_seen_bits(const int32_t *user_idx, const int32_t *anime_idx, int64_t n, int32_t n_users, int32_t n_anime,
+                     uint32_t *bits, int32_t *err_flag, void *stream) {
+  if (n < 0 || n_users < 0 || n_anime < 1 || !err_flag || (n > 0 && (!user_idx || !anime_idx))) return ANIREC_EINVAL;
+  if (n_users > 0 && !bits) return ANIREC_EINVAL;
+  if (n >= ((int64_t)1 << 39)) return ANIREC_EINVAL;  // one thread per rating, 256 per workgroup
+  hipStream_t s = (hipStream_t)stream;
+  const int wwords = (n_anime + 31) / 32;
+  ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
+  if (n_users > 0) ANIREC_HIP_CHECK(hipMemsetAsync(bits, 0, (size_t)n_users * wwords * 4, s));
+  if (n == 0) return ANIREC_OK;
+  hipLaunchKernelGGL(k_seen_bits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, user_idx, anime_idx, (long long)n,
+                     n_users, n_anime, wwords, bits, err_flag);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

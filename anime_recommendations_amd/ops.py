@@ -451,6 +451,75 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
     return out_i, out_p
 
 
+def seen_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
+    """Watched bits of a rating list: int32 [n_users, ceil(n_anime/32)], bit ``a & 31`` of word ``a >> 5`` of row u set
+    for every rating (u, a) — the ``watched_bits`` of predict_topk / predict_rank.  Raises ValueError on an index out
+    of range."""
+    _need_gpu()
+    lib = _lib.load()
+    dev = user_idx.device if isinstance(user_idx, torch.Tensor) and user_idx.is_cuda else device
+    u, a = _i32(user_idx, dev), _i32(anime_idx, dev)
+    assert u.dim() == 1 and u.shape == a.shape
+    n_users, n_anime = int(n_users), int(n_anime)
+    if n_users < 0 or n_anime < 1:
+        raise ValueError("seen_bits: n_users must be >= 0 and n_anime >= 1")
+    bits = torch.empty(n_users, (n_anime + 31) // 32, dtype=torch.int32, device=u.device)
+    err = torch.empty(1, dtype=torch.int32, device=u.device)
+    _lib.check(lib.anirec_seen_bits(_lib.ptr(u), _lib.ptr(a), int(u.numel()), n_users, n_anime, _lib.ptr(bits),
+                                    _lib.ptr(err), _stream()), "anirec_seen_bits")
+    if int(err.item()):
+        raise ValueError("seen_bits: user or anime index out of range")
+    return bits
+
+
+RANK_BATCH = 1 << 22    # targets per anirec_predict_rank call: far inside its 32-bit target offsets and grid
+
+
+def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None):
+    """Rank of each target anime among the anime its user has not watched, by predicted rating, without building
+    the ranking: target t is (``target_row[t]``: a position in ``users``, ``target_anime[t]``: an anime index).
+    Returns (rank int32 [n_t], p fp32 [n_t]): ``rank[t]`` = the position of the target in the whole ranking
+    ``predict_topk(U, A, head, users, k=n_anime, watched_bits with the target's own bit cleared)`` holds for that
+    user (0 = first), ``p[t]`` its rating there, bit for bit.  watched_bits as predict_topk.  Raises ValueError on a
+    target_row or target_anime out of range."""
+    _need_gpu()
+    lib = _lib.load()
+    dev = U.device
+    us = _i32(users, dev)
+    tr, ta = _i32(target_row, dev), _i32(target_anime, dev)
+    assert tr.dim() == 1 and tr.shape == ta.shape
+    n_a, n_q, n_t = A.shape[0], int(us.numel()), int(tr.numel())
+    dim = _width(U, A)
+    if n_q and bool(((us < 0) | (us >= U.shape[0])).any()):
+        raise ValueError("predict_rank: user row out of range")
+    rank = torch.empty(n_t, dtype=torch.int32, device=dev)
+    p = torch.empty(n_t, dtype=torch.float32, device=dev)
+    if n_t == 0:
+        return rank, p
+    if n_q == 0:
+        raise ValueError("predict_rank: target_row out of range (no users)")
+    wb = None
+    if watched_bits is not None:
+        wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
+        assert wb.shape == (n_q, (n_a + 31) // 32)
+    h = _head_struct(head)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.anirec_predict_rank_workspace_bytes(n_a, n_q, min(n_t, RANK_BATCH), dim)), dtype=torch.uint8,
+                     device=dev)
+    bad = False
+    for t0 in range(0, n_t, RANK_BATCH):
+        cnt = min(RANK_BATCH, n_t - t0)
+        _lib.check(lib.anirec_predict_rank(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h),
+                                           _head_act(head), _lib.ptr(wb), _lib.ptr(tr[t0:t0 + cnt]),
+                                           _lib.ptr(ta[t0:t0 + cnt]), cnt, _lib.ptr(rank[t0:t0 + cnt]),
+                                           _lib.ptr(p[t0:t0 + cnt]), _lib.ptr(err), _lib.ptr(ws), ws.numel(), _stream()),
+                   "anirec_predict_rank")
+        bad = bad or bool(int(err.item()))
+    if bad:
+        raise ValueError("predict_rank: target_row or target_anime out of range")
+    return rank, p
+
+
 def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fallback=True):
     """predict_topk on the matrix cores (the batched model_recs path).  Users whose candidate window
     could not be proven complete are transparently re-run through the exact kernels.

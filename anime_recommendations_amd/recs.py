@@ -117,3 +117,25 @@ def fave_profile(fav_bits, cat_bits, n_cat, users=None):
     if int(err.item()):
         raise ValueError("fave_profile: user index out of range")
     return counts
+
+
+def ranking_metrics(rank, ks):
+    """Ranking metrics of held-out anime from their ranks (``ops.predict_rank``; 0 = ranked first), in float64 on the
+    host: {"hit_rate": {k: mean(rank < k)}, "ndcg": {k: mean(1 / log2(rank + 2) if rank < k else 0)},
+    "mrr": mean(1 / (rank + 1)), "mean_rank", "median_rank", "n"}.  One relevant anime per row, so the ideal DCG is 1
+    and NDCG@k is the discounted gain itself.  An empty rank set gives NaN metrics and n = 0."""
+    r = rank.detach().cpu().numpy() if isinstance(rank, torch.Tensor) else np.asarray(rank)
+    r = r.reshape(-1).astype(np.float64)
+    ks = [int(k) for k in ks]
+    n = int(r.size)
+    if n == 0:
+        nan = float("nan")
+        return {"hit_rate": {k: nan for k in ks}, "ndcg": {k: nan for k in ks}, "mrr": nan, "mean_rank": nan,
+                "median_rank": nan, "n": 0}
+    if (r < 0).any():
+        raise ValueError("ranking_metrics: negative rank")
+    gain = 1.0 / np.log2(r + 2.0)
+    return {"hit_rate": {k: float(np.mean(r < k)) for k in ks},
+            "ndcg": {k: float(np.mean(np.where(r < k, gain, 0.0))) for k in ks},
+            "mrr": float(np.mean(1.0 / (r + 1.0))), "mean_rank": float(np.mean(r)), "median_rank": float(np.median(r)),
+            "n": n}

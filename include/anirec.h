@@ -603,6 +603,34 @@ int anirec_predict_topk_large_w(const float *U, const float *A, int32_t dim, int
                                 const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* Rank of held-out anime in a user's ranking, without the ranking: per target t = (target_row[t], target_anime[t]),
+ * target_row indexing `users`, with p_j the predicted rating of users[target_row[t]] for anime j,
+ *   out_rank[t] = #{ j != a_t : watched bit j of row target_row[t] clear and
+ *                    (key(p_j) > key(p_t) or (key(p_j) == key(p_t) and j < a_t)) },   out_p[t] = p_{a_t}
+ * key: larger rating first, NaN after every number, ties in ascending index — the order of anirec_predict_topk*.  The
+ * target's own watched bit is ignored, so out_rank[t] is the position of a_t in the whole ranking
+ * anirec_predict_topk_large_w(k >= n_anime) returns for that user under the same mask with bit a_t cleared, and
+ * out_p[t] that list's rating, bit for bit (the same normalised rows, fma chain, head and activation).
+ * dim: one of 32, 64, 128, 256.  watched: optional [n_users][ceil(n_anime/32)], as anirec_predict_topk.
+ * *err_flag (device) becomes 1 on a target_row outside [0, n_users) or a target_anime outside [0, n_anime): that
+ * target gets rank -1 and a NaN rating, nothing is read through it, the other targets are unaffected.
+ * n_targets == 0 or n_users == 0: ANIREC_OK, nothing enqueued.  The counts of a target over slices of the anime
+ * table meet in an integer atomic add: results are bit-reproducible.  Cost: 2 n_targets n_anime dim flops of the
+ * fp32 chain, 8 bytes stored per target; no [n_targets, n_anime] matrix exists.
+ * workspace: anirec_predict_rank_workspace_bytes(n_anime, n_users, n_targets, dim) bytes (the normalised rows). */
+size_t anirec_predict_rank_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t n_targets, int32_t dim);
+int anirec_predict_rank(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                        int32_t n_users, const anirec_head *head_host, int32_t activation, const uint32_t *watched,
+                        const int32_t *target_row, const int32_t *target_anime, int32_t n_targets, int32_t *out_rank,
+                        float *out_p, int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Watched bits of a rating list: bits[n_users][ceil(n_anime/32)] is zeroed, then bit (a & 31) of word a >> 5 of row u
+ * is set for each of the n ratings (user_idx[i], anime_idx[i]) = (u, a); repeats are harmless.  The table
+ * anirec_predict_topk* and anirec_predict_rank take as `watched`.  *err_flag (device) becomes 1 on an index out of
+ * range; that rating sets nothing. */
+int anirec_seen_bits(const int32_t *user_idx, const int32_t *anime_idx, int64_t n, int32_t n_users, int32_t n_anime,
+                     uint32_t *bits, int32_t *err_flag, void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
