@@ -303,6 +303,29 @@ def similar_users_frame(U, user_ids, df, anime_df, user_id, n_users, num_faves, 
 # ----------------------------------------------------------------------------------------
 # model_recs
 # ----------------------------------------------------------------------------------------
+def _blocked_bits(blocked):
+    """One row of watched-bit words ([1, ceil(n_anime/32)] uint32) with the bits of the anime ``blocked`` marks set:
+    the mask predict_topk takes for anime a list must not hold."""
+    bits = np.zeros((1, (len(blocked) + 31) // 32), np.uint32)
+    nz = np.nonzero(blocked)[0]
+    np.bitwise_or.at(bits[0], nz >> 5, (np.uint32(1) << (nz & 31).astype(np.uint32)))
+    return bits
+
+
+def _model_recs_rows(meta, idx, p):
+    """The model_recs frame (model_recs.py:451-456) of one user's top-k: ``idx`` anime indices (-1 padded) with
+    their predicted ratings ``p``, metadata from ``meta`` (metadata_by_index)."""
+    ok = idx >= 0
+    rows = meta.iloc[idx[ok]]
+    return pd.DataFrame({
+        "Name": rows["Name"].to_numpy(), "Prediction": p[ok], "Genres": rows["Genres"].to_numpy(),
+        "Source": rows["Source"].to_numpy(), "anime_id": rows["anime_id"].to_numpy(),
+        "Sypnopsis": rows["Sypnopsis"].to_numpy(), "Episodes": rows["Episodes"].to_numpy(),
+        "Japanese name": rows["japanese_name"].to_numpy(), "Studios": rows["Studios"].to_numpy(),
+        "Premiered": rows["Premiered"].to_numpy(), "Score": rows["Score"].to_numpy(),
+        "Type": rows["Type"].to_numpy()})
+
+
 def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
                      types=None, genres=None):
     """recommendations (model_recs.py:373-456): predicted rating of every unwatched, indexed
@@ -314,25 +337,69 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
         raise ValueError("user id %r has no embedding row" % (user_id,))
     meta = metadata_by_index(anime_ids, anime_df, syn_df)
     keep = unwatched_mask(df, anime_ids, user_id) & filter_mask(meta, anime_df, types, genres)
-    n_a = len(anime_ids)
-    blocked = ~keep
-    bits = np.zeros((1, (n_a + 31) // 32), np.uint32)
-    nz = np.nonzero(blocked)[0]
-    np.bitwise_or.at(bits[0], nz >> 5, (np.uint32(1) << (nz & 31).astype(np.uint32)))
+    bits = _blocked_bits(~keep)
     tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
     k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
     idx, p = ops.predict_topk(tU, tA, head, [int(pos[0])], k, bits.view(np.int32))
-    idx, p = idx.cpu().numpy()[0], p.cpu().numpy()[0]
+    return _model_recs_rows(meta, idx.cpu().numpy()[0], p.cpu().numpy()[0])
+
+
+# ----------------------------------------------------------------------------------------
+# new_user_recs: users the model was not trained on
+# ----------------------------------------------------------------------------------------
+def _folded_position(folded, user_id):
+    pos = np.nonzero(np.asarray(folded["ids"]) == int(user_id))[0]
+    if len(pos) == 0:
+        raise ValueError("user id %r is not in the new ratings file" % (user_id,))
+    return int(pos[0])
+
+
+def new_user_recs_frame(model, new_df, anime_df, syn_df, user_id, n_recs, types=None, genres=None, steps=None, lr=None,
+                        folded=None):
+    """model_recs for a user the model holds no row for: every user of ``new_df`` (``user_id, anime_id, rating`` in
+    [0, 1]) is folded in by one ``recs.fold_in_users`` call (or taken from ``folded``, an earlier call's result), then
+    the queried user's unwatched anime are ranked by predicted rating under the Type / Genre filters, exactly as
+    ``model_recs_frame`` does for a trained row.  Returns (frame with model_recs_frame's columns, folded)."""
+    import torch
+    from . import ops, recs, weights_io
+    if folded is None:
+        folded = recs.fold_in_users(model, new_df, steps=recs.FOLD_STEPS if steps is None else int(steps),
+                                    lr=recs.FOLD_LR if lr is None else float(lr))
+    q = _folded_position(folded, user_id)
+    anime_ids = np.asarray(model["anime_ids"])
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    bits = _blocked_bits(~filter_mask(meta, anime_df, types, genres))
+    n_a = len(anime_ids)
+    dev = folded["rows"].device
+    watched = folded["watched"][q:q + 1] | torch.as_tensor(bits.view(np.int32), device=dev)
+    tA = torch.as_tensor(np.ascontiguousarray(model["A"], np.float32), device=dev)
+    k = _topk_count(n_recs, "model_num_recs", n_a)
+    idx, p = ops.predict_topk(folded["rows"], tA, weights_io.model_head(model), [q], k, watched)
+    return _model_recs_rows(meta, idx.cpu().numpy()[0], p.cpu().numpy()[0]), folded
+
+
+def new_user_neighbours_frame(model, folded, df, anime_df, user_id, n_users, num_faves, tv_only):
+    """similar_users for a folded user: the trained users ranked by cosine against the folded row — the folded rows
+    are appended to the user table and barred as candidates (``keep`` zero), so only trained users are listed.
+    ``df``: the rating frame the favourites of the neighbours are read from.  Returns (similar_users frame, filename)."""
+    import torch
+    from . import ops
+    q = _folded_position(folded, user_id)
+    user_ids = np.asarray(model["user_ids"])
+    n_old = len(user_ids)
+    dev = folded["rows"].device
+    table = torch.cat([torch.as_tensor(np.ascontiguousarray(model["U"], np.float32), device=dev), folded["rows"]])
+    keep = np.zeros(table.shape[0], np.uint8)
+    keep[:n_old] = 1
+    k = _topk_count(n_users, "id_query_number", n_old)
+    idx, sim = ops.cosine_topk(ops.rownorm(table, device=dev), [n_old + q], k, exclude_self=True, keep=keep)
+    idx, sim = idx.cpu().numpy()[0], sim.cpu().numpy()[0]
     ok = idx >= 0
-    rows = meta.iloc[idx[ok]]
-    frame = pd.DataFrame({
-        "Name": rows["Name"].to_numpy(), "Prediction": p[ok], "Genres": rows["Genres"].to_numpy(),
-        "Source": rows["Source"].to_numpy(), "anime_id": rows["anime_id"].to_numpy(),
-        "Sypnopsis": rows["Sypnopsis"].to_numpy(), "Episodes": rows["Episodes"].to_numpy(),
-        "Japanese name": rows["japanese_name"].to_numpy(), "Studios": rows["Studios"].to_numpy(),
-        "Premiered": rows["Premiered"].to_numpy(), "Score": rows["Score"].to_numpy(),
-        "Type": rows["Type"].to_numpy()})
-    return frame
+    ids = user_ids[idx[ok]]
+    frame = pd.DataFrame({"similar_users": ids, "similarity": sim[ok],
+                          "favorite_animes": fave_anime_many(df, anime_df, ids, num_faves, tv_only)})
+    fn = "User_" + str(user_id).translate({ord(c): None for c in string.whitespace}) + ".csv"
+    return frame, fn
 
 
 # ----------------------------------------------------------------------------------------

@@ -282,6 +282,10 @@ static inline void with_width(int32_t dim, F &&f) {
   }
 }
 
+// host: out[r] = W[r] * (1 / sqrt(max(sum W[r]^2, 1e-12))) for n rows of a (checked) width, enqueued on s: the
+// tf.nn.l2_normalize rows of rownorm_body<1> (defined in anirec_infer.hip, beside the kernels it launches)
+void l2norm_rows(const float *W, int n, float *out, int dim, hipStream_t s);
+
 // host: an ANIREC_ACT_* / ANIREC_LOSS_* value the kernels implement
 static inline bool act_ok(int32_t a) { return a >= ANIREC_ACT_SIGMOID && a <= ANIREC_ACT_SOFTPLUS; }
 static inline bool loss_ok(int32_t l) { return l >= ANIREC_LOSS_BCE && l <= ANIREC_LOSS_LOGCOSH; }

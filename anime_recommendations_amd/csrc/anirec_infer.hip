@@ -106,6 +106,10 @@ static void launch_rownorm(const float *W, const int32_t *rows, int n, float *ou
       hipLaunchKernelGGL((k_rownorm_w<kMode, decltype(kd)::value>), dim3(blocks), dim3(256), 0, s, W, rows, n, out);
     });
 }
+// the mode-1 rows for the other translation units (anirec_foldin.hip): the same kernels, nothing instantiated twice
+void l2norm_rows(const float *W, int n, float *out, int dim, hipStream_t s) {
+  launch_rownorm<1>(W, nullptr, n, out, dim, s);
+}
 
 // ------------------------------------------------------------------------------------
 // tiled scores: out[q][j] = epilogue( chain_dot(Q[q], W[j]) )

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import DIM, MAX_TOPK
-from .schedule import ACTIVATIONS, OPTIMIZERS, resolve_activation, resolve_optimizer
+from .schedule import ACTIVATIONS, LOSSES, OPTIMIZERS, adam_alphas, resolve_activation, resolve_loss, resolve_optimizer
 
 
 def _stream():
@@ -518,6 +518,53 @@ def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None)
     if bad:
         raise ValueError("predict_rank: target_row or target_anime out of range")
     return rank, p
+
+
+def fold_in(A, head, offsets, anime_idx, rating, init, lr=0.01, steps=100, l2=1e-4, loss="binary_crossentropy"):
+    """Rows of new users fitted to their own ratings with the anime table and the head frozen (anirec_fold_in: the
+    reference's model with a fresh one-row user embedding, full-batch Keras-2.12 Adam at learning rate ``lr`` for
+    ``steps`` iterations, BatchNorm in inference mode).  New user j rated ``anime_idx[offsets[j]:offsets[j+1]]`` (rows
+    of A) with ``rating`` (the scaled targets in [0, 1]); ``init``: the start rows [n_new, width] or one row for all.
+    The width comes from ``A.shape[1]``, the activation from the head dict, ``loss`` is a Keras name.
+    Returns (rows fp32 [n_new, width], loss fp32 [n_new]): the final rows and the loss (data term + l2 * sum u^2) there;
+    a user without ratings keeps the start row and gets a NaN loss.  A user's result does not depend on the other
+    users of the call.  Raises ValueError on an anime index out of range or offsets that are not a CSR of the lists."""
+    _need_gpu()
+    lib = _lib.load()
+    loss_id = LOSSES[resolve_loss(loss)]
+    act_id = _head_act(head)
+    dim = _width(A)
+    dev = A.device
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("fold_in: steps must be >= 0")
+    off = torch.as_tensor(offsets).to(torch.int64).cpu()
+    ai, rt = _i32(anime_idx, dev), _f32(rating, dev)
+    assert off.dim() == 1 and off.numel() >= 1 and ai.dim() == 1 and ai.shape == rt.shape
+    n_new = int(off.numel()) - 1
+    if int(off[0]) != 0 or int(off[-1]) != ai.numel() or (n_new and bool((off[1:] < off[:-1]).any())):
+        raise ValueError("fold_in: offsets must rise from 0 to the number of ratings")
+    init_t = _f32(init, dev)
+    if init_t.dim() == 1:
+        init_t = init_t.expand(n_new, -1)
+    init_t = init_t.contiguous()
+    assert init_t.shape == (n_new, dim), "init: [n_new, width] or one row"
+    rows = torch.empty(n_new, dim, dtype=torch.float32, device=dev)
+    out_loss = torch.empty(n_new, dtype=torch.float32, device=dev)
+    if n_new == 0:
+        return rows, out_loss
+    alpha = torch.as_tensor(adam_alphas(lr, 1, steps), device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.anirec_fold_in_workspace_bytes(A.shape[0], n_new, dim)), dtype=torch.uint8, device=dev)
+    h = _head_struct(head)
+    off_d = off.to(dev)
+    _lib.check(lib.anirec_fold_in(_lib.ptr(A), dim, A.shape[0], C.byref(h), act_id, loss_id, float(l2),
+                                  _lib.ptr(off_d), _lib.ptr(ai), _lib.ptr(rt), n_new, _lib.ptr(init_t),
+                                  _lib.ptr(alpha), steps, _lib.ptr(rows), _lib.ptr(out_loss), _lib.ptr(err), _lib.ptr(ws),
+                                  ws.numel(), _stream()), "anirec_fold_in")
+    if int(err.item()):
+        raise ValueError("fold_in: anime index out of range")
+    return rows, out_loss
 
 
 def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fallback=True):

@@ -139,3 +139,62 @@ def ranking_metrics(rank, ks):
             "ndcg": {k: float(np.mean(np.where(r < k, gain, 0.0))) for k in ks},
             "mrr": float(np.mean(1.0 / (r + 1.0))), "mean_rank": float(np.mean(r)), "median_rank": float(np.median(r)),
             "n": n}
+
+
+FOLD_STEPS = 100        # Adam iterations of a fold-in
+FOLD_LR = 0.01          # and their learning rate
+
+
+def fold_in_csr(frame, user_ids, anime_ids):
+    """Host half of ``fold_in_users``: the CSR of a rating frame (``user_id, anime_id, rating``: the preprocess output
+    schema, rating in [0, 1]).  Users come in the order of their first appearance, each user's ratings in frame order
+    (repeats stay); ratings of anime outside ``anime_ids`` (the model has no row for them) are dropped and counted.
+    Returns (new_ids int64 [n_new], offsets int64 [n_new + 1], anime_idx int32 [nnz], rating fp32 [nnz], n_dropped).
+    ValueError, naming them, for user ids ``user_ids`` (the model's) already holds, and for a rating that is NaN or
+    outside [0, 1]."""
+    from .data import encode_ids
+    uid = np.asarray(frame["user_id"]).astype(np.int64)
+    aid = np.asarray(frame["anime_id"]).astype(np.int64)
+    rat = np.asarray(frame["rating"], np.float32)
+    if len(rat) and not bool(np.all((rat >= 0) & (rat <= 1))):      # (a NaN fails both comparisons)
+        raise ValueError("fold_in_users: ratings must be numbers in [0, 1] (the preprocess step's scaled ratings); "
+                         "%d of %d are not" % (int((~((rat >= 0) & (rat <= 1))).sum()), len(rat)))
+    row, new_ids = encode_ids(uid)
+    new_ids = np.asarray(new_ids, np.int64)
+    known = new_ids[np.isin(new_ids, np.asarray(user_ids, np.int64))]
+    if len(known):
+        raise ValueError("fold_in_users: user id(s) %s already have an embedding row in the model (use model_recs for them)"
+                         % ", ".join(str(int(x)) for x in known[:20]))
+    anime_ids = np.asarray(anime_ids, np.int64)
+    order = np.argsort(anime_ids, kind="stable")
+    pos = np.searchsorted(anime_ids[order], aid)
+    pos[pos == len(anime_ids)] = 0
+    has = (anime_ids[order][pos] == aid) if len(anime_ids) else np.zeros(len(aid), bool)
+    n_dropped = int((~has).sum())
+    row, a_idx, rat = np.asarray(row, np.int64)[has], order[pos][has].astype(np.int32), rat[has]
+    by_user = np.argsort(row, kind="stable")
+    offsets = np.zeros(len(new_ids) + 1, np.int64)
+    np.cumsum(np.bincount(row, minlength=len(new_ids)), out=offsets[1:])
+    return new_ids, offsets, np.ascontiguousarray(a_idx[by_user]), np.ascontiguousarray(rat[by_user]), n_dropped
+
+
+def fold_in_users(model, frame, steps=FOLD_STEPS, lr=FOLD_LR, l2=1e-4, init=None, device="cuda:0"):
+    """Embedding rows for the users of ``frame`` (``user_id, anime_id, rating`` in [0, 1]), none of whom the model
+    (``weights_io.load_model``'s dict) was trained on: ``ops.fold_in`` on their ratings, with the model's own head,
+    activation and loss (binary_crossentropy when the file records none).  ``init``: the start row(s); by default the
+    fp32 mean row of ``model["U"]``.  Returns dict(ids int64 [n_new], rows fp32 [n_new, width] and loss fp32 [n_new]
+    on the device, watched int32 [n_new, ceil(n_anime/32)]: the bits ``ops.seen_bits`` sets for the ratings kept,
+    n_dropped: ratings of anime the model has no row for, offsets / anime_idx / rating: the CSR that was fitted)."""
+    from . import ops, weights_io
+    if model.get("user_ids") is None or model.get("anime_ids") is None:
+        raise ValueError("fold_in_users: the model file has no id tables")
+    ids, offsets, a_idx, rat, n_dropped = fold_in_csr(frame, model["user_ids"], model["anime_ids"])
+    A = torch.as_tensor(np.ascontiguousarray(model["A"], np.float32), device=device)
+    if init is None:
+        init = np.asarray(model["U"], np.float32).mean(axis=0, dtype=np.float32)
+    rows, loss = ops.fold_in(A, weights_io.model_head(model), offsets, a_idx, rat, init, lr=lr, steps=steps, l2=l2,
+                             loss=model.get("loss") or "binary_crossentropy")
+    u_idx = np.repeat(np.arange(len(ids), dtype=np.int32), np.diff(offsets))
+    watched = ops.seen_bits(u_idx, a_idx, len(ids), A.shape[0], device=device)
+    return {"ids": ids, "rows": rows, "loss": loss, "watched": watched, "n_dropped": n_dropped, "offsets": offsets,
+            "anime_idx": a_idx, "rating": rat}

@@ -631,6 +631,41 @@ int anirec_predict_rank(const float *U, const float *A, int32_t dim, int32_t n_a
 int anirec_seen_bits(const int32_t *user_idx, const int32_t *anime_idx, int64_t n, int32_t n_users, int32_t n_anime,
                      uint32_t *bits, int32_t *err_flag, void *stream);
 
+/* FOLD-IN of new users: a user the model was not trained on (model_recs.py:373-394 reads the user's row out of the
+ * trained table and has none) gets a row fitted to that user's own ratings with everything else frozen — the Keras
+ * model of neural_network.py:66-106 with the anime table, Dense(1) and BatchNorm (inference mode) fixed and a fresh
+ * one-row user embedding, model.fit full-batch on the user's ratings with Keras-2.12 Adam.
+ * New user j holds ratings offsets[j] .. offsets[j+1]-1 of (anime_idx, rating) (CSR; n = their number; repeats count
+ * as separate ratings; rating = the scaled target t).  Ah = A with rows scaled by 1/sqrt(max(sum a^2, 1e-12)) (the
+ * train step's forward), hs, hb = the folded inference head (y = c*hs + hb), u starts at init[j], m = v = 0.  For
+ * s = 1 .. steps, in fp32:
+ *     ru = 1/sqrt(max(sum u^2, 1e-12));  uh = u*ru
+ *     c_i = <uh, ah_i>;  y_i = fma(c_i, hs, hb);  p_i = act(y_i), g_i = dl/dy_i of ANIREC_ACT_* / ANIREC_LOSS_* above
+ *     dc_i = (g_i / n) * hs
+ *     grad = ru * sum_i dc_i (ah_i - c_i uh) + 2*l2*u
+ *     m += (grad-m)*0.1; v += (grad*grad-v)*0.001; u -= (m*alpha[s-1])/(sqrt(v)+1e-7)      (the ADAM rule above:
+ *                                                               correctly rounded sqrt and divide, nothing contracted)
+ * alpha[s-1] = lr*sqrt(1-b2^s)/(1-b1^s), computed by the caller (device array).  out_rows[j] = u after the last step;
+ * out_loss[j] = (1/n) sum_i l(p_i, t_i) + l2 * sum u^2 at that final row.  steps == 0: out_rows = init, out_loss the
+ * loss there.  n == 0: out_rows[j] = init[j] bit for bit, out_loss[j] = NaN.
+ * One workgroup per user, every step inside one launch, no float atomics: the partial sums of a user's list meet in a
+ * fixed order that depends on that list alone, so a user's row and loss are the same bits run to run, whatever other
+ * users share the call and wherever the user stands in it.
+ * dim: one of 32, 64, 128, 256.  Bad dim / activation / loss, n_anime < 1, negative steps or n_new, a NULL pointer or
+ * workspace_bytes < anirec_fold_in_workspace_bytes(n_anime, n_new, dim): ANIREC_EINVAL before anything is enqueued
+ * (0 from the size query).  n_new == 0: ANIREC_OK, nothing enqueued.  anime_idx / rating may be NULL only when every
+ * list is empty.  *err_flag (device) becomes 1 on an anime_idx outside [0, n_anime), a negative or decreasing
+ * offsets pair, or a list of more than INT32_MAX ratings: that user's row and loss become NaN, nothing is read through
+ * the bad value, the other users are unaffected (anirec_predict_rank's convention).  The call does not know how many
+ * ratings anime_idx and rating hold (the ABI carries no count): the CALLER guarantees that every offset is at most
+ * that number — an offset past it is read through like any other.  The workspace (the normalised anime rows) may hold anything on
+ * entry; out_rows, out_loss and *err_flag are fully written. */
+size_t anirec_fold_in_workspace_bytes(int32_t n_anime, int32_t n_new, int32_t dim);
+int anirec_fold_in(const float *A, int32_t dim, int32_t n_anime, const anirec_head *head_host, int32_t activation,
+                   int32_t loss, float l2, const int64_t *offsets, const int32_t *anime_idx, const float *rating,
+                   int32_t n_new, const float *init, const float *alpha, int32_t steps, float *out_rows,
+                   float *out_loss, int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
