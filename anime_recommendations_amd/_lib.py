@@ -213,6 +213,10 @@ PROTOTYPES = {
     "anirec_fold_in_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "anirec_fold_in": (C.c_int, [_vp, _i32, _i32, C.POINTER(Head), _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp, _vp, _i32,
                                  _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the same fit for a few rows with long lists (new anime against the user table): lists split across workgroups
+    "anirec_fold_in_split_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "anirec_fold_in_split": (C.c_int, [_vp, _i32, _i32, C.POINTER(Head), _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp, _vp,
+                                       _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -206,6 +206,20 @@ def find_anime_id(name, anime_df):
     raise ValueError("anime %r not found in the anime data frame" % (name,))
 
 
+def _similar_anime_rows(meta, idx, sim):
+    """The frame anime_recs returns (similar_anime.py:364-471) for one query's top-k: ``idx`` anime indices (-1 padded) with
+    their similarities ``sim``, metadata from ``meta`` (metadata_by_index)."""
+    ok = idx >= 0
+    rows = meta.iloc[idx[ok]]
+    return pd.DataFrame({
+        "Name": rows["Name"].to_numpy(), "Similarity": sim[ok], "Genres": rows["Genres"].to_numpy(),
+        "Sypnopsis": rows["Sypnopsis"].to_numpy(), "Episodes": rows["Episodes"].to_numpy(),
+        "Japanese name": rows["japanese_name"].to_numpy(), "Studios": rows["Studios"].to_numpy(),
+        "Premiered": rows["Premiered"].to_numpy(), "Score": rows["Score"].to_numpy(),
+        "Type": rows["Type"].to_numpy(), "Source": rows["Source"].to_numpy(),
+        "Rating": rows["Rating"].to_numpy()})
+
+
 def similar_anime_frame(A, anime_ids, anime_df, syn_df, name, count, types=None, genres=None):
     """anime_recs (similar_anime.py:364-471): cosine of the query anime vs all, query excluded,
     optional Type / Genre filters, top ``count`` by similarity.  Returns (frame, filename)."""
@@ -222,15 +236,7 @@ def similar_anime_frame(A, anime_ids, anime_df, syn_df, name, count, types=None,
     k = _topk_count(count, "a_query_number", len(anime_ids) - 1)
     idx, sim = ops.cosine_topk(Wh, [q], k, exclude_self=True, keep=keep.astype(np.uint8))
     idx, sim = idx.cpu().numpy()[0], sim.cpu().numpy()[0]
-    ok = idx >= 0
-    rows = meta.iloc[idx[ok]]
-    frame = pd.DataFrame({
-        "Name": rows["Name"].to_numpy(), "Similarity": sim[ok], "Genres": rows["Genres"].to_numpy(),
-        "Sypnopsis": rows["Sypnopsis"].to_numpy(), "Episodes": rows["Episodes"].to_numpy(),
-        "Japanese name": rows["japanese_name"].to_numpy(), "Studios": rows["Studios"].to_numpy(),
-        "Premiered": rows["Premiered"].to_numpy(), "Score": rows["Score"].to_numpy(),
-        "Type": rows["Type"].to_numpy(), "Source": rows["Source"].to_numpy(),
-        "Rating": rows["Rating"].to_numpy()})
+    frame = _similar_anime_rows(meta, idx, sim)
     return frame, clean(name) + ".csv"
 
 
@@ -400,6 +406,56 @@ def new_user_neighbours_frame(model, folded, df, anime_df, user_id, n_users, num
                           "favorite_animes": fave_anime_many(df, anime_df, ids, num_faves, tv_only)})
     fn = "User_" + str(user_id).translate({ord(c): None for c in string.whitespace}) + ".csv"
     return frame, fn
+
+
+# ----------------------------------------------------------------------------------------
+# new_anime: anime the model was not trained on
+# ----------------------------------------------------------------------------------------
+def _folded_anime_position(folded, anime_id):
+    pos = np.nonzero(np.asarray(folded["ids"]) == int(anime_id))[0]
+    if len(pos) == 0:
+        raise ValueError("anime id %r is not in the new ratings file" % (anime_id,))
+    return int(pos[0])
+
+
+def new_anime_similar_frame(model, folded, anime_df, syn_df, anime_id, count, types=None, genres=None):
+    """similar_anime for a folded anime (``recs.fold_in_anime``'s result): the trained anime ranked by cosine against
+    the folded row under the Type / Genre filters — the folded rows are appended to the anime table and barred as
+    candidates (``keep`` zero), so only trained anime are listed.  Returns (frame with similar_anime_frame's columns,
+    filename)."""
+    import torch
+    from . import ops
+    q = _folded_anime_position(folded, anime_id)
+    anime_ids = np.asarray(model["anime_ids"])
+    n_old = len(anime_ids)
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    dev = folded["rows"].device
+    table = torch.cat([torch.as_tensor(np.ascontiguousarray(model["A"], np.float32), device=dev), folded["rows"]])
+    keep = np.zeros(table.shape[0], np.uint8)
+    keep[:n_old] = filter_mask(meta, anime_df, types, genres)
+    k = _topk_count(count, "a_query_number", n_old)
+    idx, sim = ops.cosine_topk(ops.rownorm(table, device=dev), [n_old + q], k, exclude_self=True, keep=keep)
+    idx, sim = idx.cpu().numpy()[0], sim.cpu().numpy()[0]
+    frame = _similar_anime_rows(meta, idx, sim)
+    return frame, "Anime_ID_" + str(int(anime_id)) + "_similar.csv"
+
+
+def new_anime_audience_frame(model, folded, anime_id, n_users):
+    """The trained users with the highest predicted rating of a folded anime among those who have not rated it:
+    ``ops.predict_topk`` with the two tables in each other's place (the head sees the rows through their cosine
+    alone) and the anime's ``rated`` bits as the mask.  Returns (frame ``user_id, Prediction``, filename)."""
+    import torch
+    from . import ops, weights_io
+    q = _folded_anime_position(folded, anime_id)
+    user_ids = np.asarray(model["user_ids"])
+    dev = folded["rows"].device
+    tU = torch.as_tensor(np.ascontiguousarray(model["U"], np.float32), device=dev)
+    k = _topk_count(n_users, "audience_number", len(user_ids))
+    idx, p = ops.predict_topk(folded["rows"], tU, weights_io.model_head(model), [q], k, folded["rated"][q:q + 1])
+    idx, p = idx.cpu().numpy()[0], p.cpu().numpy()[0]
+    ok = idx >= 0
+    frame = pd.DataFrame({"user_id": user_ids[idx[ok]], "Prediction": p[ok]})
+    return frame, "Anime_ID_" + str(int(anime_id)) + "_audience.csv"
 
 
 # ----------------------------------------------------------------------------------------

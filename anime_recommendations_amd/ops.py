@@ -567,6 +567,72 @@ def fold_in(A, head, offsets, anime_idx, rating, init, lr=0.01, steps=100, l2=1e
     return rows, out_loss
 
 
+FOLD_CHUNK = 1024       # ANIREC_FOLD_CHUNK: ratings of one chunk of anirec_fold_in_split
+
+
+def fold_chunk_map(offsets):
+    """The chunk map anirec_fold_in_split takes, from the CSR offsets (host): (chunk_offsets int32 [n_new + 1]: the
+    prefix sums of ceil(n_r / FOLD_CHUNK), chunk_row int32 [n_chunks]: the row of each chunk).  A decreasing pair
+    counts no chunks (the kernel poisons that row)."""
+    off = np.asarray(offsets, np.int64)
+    n = np.maximum(np.diff(off), 0)
+    chunk_offsets = np.zeros(len(off), np.int64)
+    np.cumsum((n + FOLD_CHUNK - 1) // FOLD_CHUNK, out=chunk_offsets[1:])
+    if chunk_offsets[-1] > np.iinfo(np.int32).max:
+        raise ValueError("fold_chunk_map: more than 2^31 - 1 chunks")
+    chunk_row = np.repeat(np.arange(len(off) - 1, dtype=np.int32), np.diff(chunk_offsets))
+    return chunk_offsets.astype(np.int32), chunk_row
+
+
+def fold_in_split(T, head, offsets, idx, rating, init, lr=0.01, steps=100, l2=1e-4, loss="binary_crossentropy"):
+    """``fold_in`` for a few rows with long lists — new anime fitted against the frozen user table ``T`` (the prediction
+    sees the two rows through their cosine alone, so the tables swap roles): anirec_fold_in_split, every list cut into
+    chunks of FOLD_CHUNK ratings that separate workgroups walk.  Same arguments, results, checks and errors as
+    ``fold_in``; the chunk map is built here from the offsets.  A row's result does not depend on the other rows of
+    the call, and a list of at most FOLD_CHUNK ratings gives the bits of ``fold_in``."""
+    _need_gpu()
+    lib = _lib.load()
+    loss_id = LOSSES[resolve_loss(loss)]
+    act_id = _head_act(head)
+    dim = _width(T)
+    dev = T.device
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("fold_in: steps must be >= 0")
+    off = torch.as_tensor(offsets).to(torch.int64).cpu()
+    ai, rt = _i32(idx, dev), _f32(rating, dev)
+    assert off.dim() == 1 and off.numel() >= 1 and ai.dim() == 1 and ai.shape == rt.shape
+    n_new = int(off.numel()) - 1
+    if int(off[0]) != 0 or int(off[-1]) != ai.numel() or (n_new and bool((off[1:] < off[:-1]).any())):
+        raise ValueError("fold_in: offsets must rise from 0 to the number of ratings")
+    init_t = _f32(init, dev)
+    if init_t.dim() == 1:
+        init_t = init_t.expand(n_new, -1)
+    init_t = init_t.contiguous()
+    assert init_t.shape == (n_new, dim), "init: [n_new, width] or one row"
+    rows = torch.empty(n_new, dim, dtype=torch.float32, device=dev)
+    out_loss = torch.empty(n_new, dtype=torch.float32, device=dev)
+    if n_new == 0:
+        return rows, out_loss
+    c_off, c_row = fold_chunk_map(off.numpy())
+    n_chunks = int(c_off[-1])
+    c_off_d, c_row_d = torch.as_tensor(c_off, device=dev), torch.as_tensor(c_row, device=dev)
+    alpha = torch.as_tensor(adam_alphas(lr, 1, steps), device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.anirec_fold_in_split_workspace_bytes(T.shape[0], n_new, n_chunks, dim)), dtype=torch.uint8,
+                     device=dev)
+    h = _head_struct(head)
+    off_d = off.to(dev)
+    _lib.check(lib.anirec_fold_in_split(_lib.ptr(T), dim, T.shape[0], C.byref(h), act_id, loss_id, float(l2),
+                                        _lib.ptr(off_d), _lib.ptr(ai), _lib.ptr(rt), n_new, _lib.ptr(c_off_d),
+                                        _lib.ptr(c_row_d), n_chunks, _lib.ptr(init_t), _lib.ptr(alpha), steps,
+                                        _lib.ptr(rows), _lib.ptr(out_loss), _lib.ptr(err), _lib.ptr(ws), ws.numel(),
+                                        _stream()), "anirec_fold_in_split")
+    if int(err.item()):
+        raise ValueError("fold_in: index out of range")
+    return rows, out_loss
+
+
 def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fallback=True):
     """predict_topk on the matrix cores (the batched model_recs path).  Users whose candidate window
     could not be proven complete are transparently re-run through the exact kernels.

@@ -145,6 +145,36 @@ FOLD_STEPS = 100        # Adam iterations of a fold-in
 FOLD_LR = 0.01          # and their learning rate
 
 
+def _fold_csr(fn, new, other, rat, held_ids, table_ids, known_msg):
+    """The CSR of rating triples grouped by ``new`` (ids in order of first appearance, each list in input order,
+    repeats kept), the ``other`` ids encoded as rows of ``table_ids`` and dropped (and counted) where it has none.
+    ValueError (prefixed ``fn``) for a rating that is NaN or outside [0, 1] and, with ``known_msg``, for ``new`` ids
+    that ``held_ids`` already holds."""
+    from .data import encode_ids
+    new = np.asarray(new).astype(np.int64)
+    other = np.asarray(other).astype(np.int64)
+    rat = np.asarray(rat, np.float32)
+    if len(rat) and not bool(np.all((rat >= 0) & (rat <= 1))):      # (a NaN fails both comparisons)
+        raise ValueError("%s: ratings must be numbers in [0, 1] (the preprocess step's scaled ratings); "
+                         "%d of %d are not" % (fn, int((~((rat >= 0) & (rat <= 1))).sum()), len(rat)))
+    row, new_ids = encode_ids(new)
+    new_ids = np.asarray(new_ids, np.int64)
+    known = new_ids[np.isin(new_ids, np.asarray(held_ids, np.int64))]
+    if len(known):
+        raise ValueError(fn + ": " + known_msg % ", ".join(str(int(x)) for x in known[:20]))
+    table_ids = np.asarray(table_ids, np.int64)
+    order = np.argsort(table_ids, kind="stable")
+    pos = np.searchsorted(table_ids[order], other)
+    pos[pos == len(table_ids)] = 0
+    has = (table_ids[order][pos] == other) if len(table_ids) else np.zeros(len(other), bool)
+    n_dropped = int((~has).sum())
+    row, t_idx, rat = np.asarray(row, np.int64)[has], order[pos][has].astype(np.int32), rat[has]
+    by_row = np.argsort(row, kind="stable")
+    offsets = np.zeros(len(new_ids) + 1, np.int64)
+    np.cumsum(np.bincount(row, minlength=len(new_ids)), out=offsets[1:])
+    return new_ids, offsets, np.ascontiguousarray(t_idx[by_row]), np.ascontiguousarray(rat[by_row]), n_dropped
+
+
 def fold_in_csr(frame, user_ids, anime_ids):
     """Host half of ``fold_in_users``: the CSR of a rating frame (``user_id, anime_id, rating``: the preprocess output
     schema, rating in [0, 1]).  Users come in the order of their first appearance, each user's ratings in frame order
@@ -152,30 +182,18 @@ def fold_in_csr(frame, user_ids, anime_ids):
     Returns (new_ids int64 [n_new], offsets int64 [n_new + 1], anime_idx int32 [nnz], rating fp32 [nnz], n_dropped).
     ValueError, naming them, for user ids ``user_ids`` (the model's) already holds, and for a rating that is NaN or
     outside [0, 1]."""
-    from .data import encode_ids
-    uid = np.asarray(frame["user_id"]).astype(np.int64)
-    aid = np.asarray(frame["anime_id"]).astype(np.int64)
-    rat = np.asarray(frame["rating"], np.float32)
-    if len(rat) and not bool(np.all((rat >= 0) & (rat <= 1))):      # (a NaN fails both comparisons)
-        raise ValueError("fold_in_users: ratings must be numbers in [0, 1] (the preprocess step's scaled ratings); "
-                         "%d of %d are not" % (int((~((rat >= 0) & (rat <= 1))).sum()), len(rat)))
-    row, new_ids = encode_ids(uid)
-    new_ids = np.asarray(new_ids, np.int64)
-    known = new_ids[np.isin(new_ids, np.asarray(user_ids, np.int64))]
-    if len(known):
-        raise ValueError("fold_in_users: user id(s) %s already have an embedding row in the model (use model_recs for them)"
-                         % ", ".join(str(int(x)) for x in known[:20]))
-    anime_ids = np.asarray(anime_ids, np.int64)
-    order = np.argsort(anime_ids, kind="stable")
-    pos = np.searchsorted(anime_ids[order], aid)
-    pos[pos == len(anime_ids)] = 0
-    has = (anime_ids[order][pos] == aid) if len(anime_ids) else np.zeros(len(aid), bool)
-    n_dropped = int((~has).sum())
-    row, a_idx, rat = np.asarray(row, np.int64)[has], order[pos][has].astype(np.int32), rat[has]
-    by_user = np.argsort(row, kind="stable")
-    offsets = np.zeros(len(new_ids) + 1, np.int64)
-    np.cumsum(np.bincount(row, minlength=len(new_ids)), out=offsets[1:])
-    return new_ids, offsets, np.ascontiguousarray(a_idx[by_user]), np.ascontiguousarray(rat[by_user]), n_dropped
+    return _fold_csr("fold_in_users", frame["user_id"], frame["anime_id"], frame["rating"], user_ids, anime_ids,
+                     "user id(s) %s already have an embedding row in the model (use model_recs for them)")
+
+
+def fold_in_anime_csr(frame, user_ids, anime_ids):
+    """Host half of ``fold_in_anime``, ``fold_in_csr`` with the roles swapped: the CSR by ``anime_id`` of the frame, the
+    anime in the order of their first appearance, each list in frame order; ratings by users outside ``user_ids`` are
+    dropped and counted.  Returns (new_ids int64 [n_new], offsets int64 [n_new + 1], user_idx int32 [nnz], rating fp32
+    [nnz], n_dropped).  ValueError, naming them, for anime ids ``anime_ids`` (the model's) already holds, and for a
+    rating that is NaN or outside [0, 1]."""
+    return _fold_csr("fold_in_anime", frame["anime_id"], frame["user_id"], frame["rating"], anime_ids, user_ids,
+                     "anime id(s) %s already have an embedding row in the model (similar_anime and model_recs serve them)")
 
 
 def fold_in_users(model, frame, steps=FOLD_STEPS, lr=FOLD_LR, l2=1e-4, init=None, device="cuda:0"):
@@ -198,3 +216,38 @@ def fold_in_users(model, frame, steps=FOLD_STEPS, lr=FOLD_LR, l2=1e-4, init=None
     watched = ops.seen_bits(u_idx, a_idx, len(ids), A.shape[0], device=device)
     return {"ids": ids, "rows": rows, "loss": loss, "watched": watched, "n_dropped": n_dropped, "offsets": offsets,
             "anime_idx": a_idx, "rating": rat}
+
+
+def fold_in_anime(model, frame, steps=FOLD_STEPS, lr=FOLD_LR, l2=1e-4, init=None, device="cuda:0"):
+    """Embedding rows for the anime of ``frame`` (``user_id, anime_id, rating`` in [0, 1]) that the model holds no row
+    for, from the ratings users it does hold gave them: ``ops.fold_in_split`` against the frozen ``model["U"]`` with the
+    model's own head, activation and loss.  ``init``: the start row(s); by default the fp32 mean row of ``model["A"]``.
+    Returns dict(ids int64 [n_new], rows fp32 [n_new, width] and loss fp32 [n_new] on the device, rated int32
+    [n_new, ceil(n_users/32)]: the bits ``ops.seen_bits`` sets for the users whose ratings were kept, n_dropped:
+    ratings by users the model has no row for, offsets / user_idx / rating: the CSR that was fitted)."""
+    from . import ops, weights_io
+    if model.get("user_ids") is None or model.get("anime_ids") is None:
+        raise ValueError("fold_in_anime: the model file has no id tables")
+    ids, offsets, u_idx, rat, n_dropped = fold_in_anime_csr(frame, model["user_ids"], model["anime_ids"])
+    U = torch.as_tensor(np.ascontiguousarray(model["U"], np.float32), device=device)
+    if init is None:
+        init = np.asarray(model["A"], np.float32).mean(axis=0, dtype=np.float32)
+    rows, loss = ops.fold_in_split(U, weights_io.model_head(model), offsets, u_idx, rat, init, lr=lr, steps=steps, l2=l2,
+                                   loss=model.get("loss") or "binary_crossentropy")
+    a_row = np.repeat(np.arange(len(ids), dtype=np.int32), np.diff(offsets))
+    rated = ops.seen_bits(a_row, u_idx, len(ids), U.shape[0], device=device)
+    return {"ids": ids, "rows": rows, "loss": loss, "rated": rated, "n_dropped": n_dropped, "offsets": offsets,
+            "user_idx": u_idx, "rating": rat}
+
+
+def append_anime(model, folded):
+    """The model dict with the folded anime (``fold_in_anime``'s result) at the end of ``A`` and ``anime_ids``; every
+    other entry is the model's own object.  Written with ``weights_io.save_model`` it is a model file that
+    similar_anime and model_recs serve the new anime from as they are."""
+    rows = folded["rows"]
+    rows = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    out = dict(model)
+    out["A"] = np.concatenate([np.asarray(model["A"], np.float32), rows.astype(np.float32)])
+    ids = np.asarray(model["anime_ids"])
+    out["anime_ids"] = np.concatenate([ids, np.asarray(folded["ids"]).astype(ids.dtype)])
+    return out

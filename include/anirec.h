@@ -52,6 +52,7 @@ extern "C" {
 #define ANIREC_MAX_SEG 16       /* max head packets (ranks of one node) */
 #define ANIREC_TOPK_MAX_BATCHES 64 /* query batches of one anirec_cosine_topk_job */
 #define ANIREC_LAZY_WINDOW 8    /* steps between two flushes of the lazy dense Adam (anirec_trainer_run) */
+#define ANIREC_FOLD_CHUNK 1024  /* ratings of one chunk of anirec_fold_in_split: part of its definition, not a knob */
 
 enum {
   ANIREC_OK = 0,
@@ -665,6 +666,37 @@ int anirec_fold_in(const float *A, int32_t dim, int32_t n_anime, const anirec_he
                    int32_t loss, float l2, const int64_t *offsets, const int32_t *anime_idx, const float *rating,
                    int32_t n_new, const float *init, const float *alpha, int32_t steps, float *out_rows,
                    float *out_loss, int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
+
+/* FOLD-IN WITH THE LIST SPLIT ACROSS WORKGROUPS: the fit above for a few rows with long lists — a new ANIME that
+ * known users have rated, fitted against the frozen user table (the prediction depends on the two rows through their
+ * cosine alone, so the tables swap roles).  T [n_table][dim] is the frozen table, idx its rows; every other argument,
+ * the definition of a step, the n == 0 and steps == 0 cases, the argument checks and the caller's guarantee on the
+ * offsets are anirec_fold_in's.  What differs is the order of the sums.  Row r's list is cut into
+ * ceil(n_r / ANIREC_FOLD_CHUNK) chunks, chunk j holding ratings [1024 j, min(n_r, 1024 (j+1))) of the list.  Per step
+ *     partial_j = the sum over chunk j's ratings of dc_i (ah_i - c_i uh), in anirec_fold_in's order over the chunk
+ *                 (lane group g takes ratings g, g + kNG, ... of the chunk, the groups added in order 0 .. kNG-1;
+ *                 dc_i = (g_i / n_r) * hs with the row's whole n_r), and the chunk's loss sum the same way
+ *     grad      = ru * (((partial_0 + partial_1) + partial_2) + ...) + 2*l2*u        (ascending chunk order)
+ * and out_loss = (((l_0 + l_1) + ...) / n_r) + l2 * sum u^2.  No atomics; a step is two plain launches (one workgroup
+ * per chunk, then one lane group per row), 2 steps + 4 launches a call, no grid-wide wait.  Two consequences:
+ *   - a row's bits depend on its own list, its start row and ANIREC_FOLD_CHUNK alone: not on the other rows, its
+ *     position in the call, or the run;
+ *   - a list of at most ANIREC_FOLD_CHUNK ratings gives the bits of anirec_fold_in, row and loss.
+ * The caller passes the chunk map (device arrays): chunk_offsets[n_new + 1] = the prefix sums of the rows' chunk
+ * counts (a row with a bad offsets pair counts 0 chunks), chunk_row[n_chunks] = the row of each chunk, n_chunks =
+ * chunk_offsets[n_new].  chunk_row may be NULL when n_chunks == 0.  Every offsets pair, every index and the map are
+ * validated before anything is gathered: a bad pair or index poisons its own row (NaN row and loss, *err_flag = 1),
+ * the others are unaffected; a map that is not the one the offsets define makes EVERY row and loss NaN with
+ * *err_flag = 1, and nothing is read through it.
+ * workspace: anirec_fold_in_split_workspace_bytes(n_table, n_new, n_chunks, dim) bytes (the normalised table, m, v,
+ * one partial row and loss per chunk, the row flags); it may hold anything on entry.  0 from the size query and
+ * ANIREC_EINVAL before anything is enqueued for a bad argument (n_chunks < 0 among them). */
+size_t anirec_fold_in_split_workspace_bytes(int32_t n_table, int32_t n_new, int32_t n_chunks, int32_t dim);
+int anirec_fold_in_split(const float *T, int32_t dim, int32_t n_table, const anirec_head *head_host, int32_t activation,
+                         int32_t loss, float l2, const int64_t *offsets, const int32_t *idx, const float *rating,
+                         int32_t n_new, const int32_t *chunk_offsets, const int32_t *chunk_row, int32_t n_chunks,
+                         const float *init, const float *alpha, int32_t steps, float *out_rows, float *out_loss,
+                         int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a

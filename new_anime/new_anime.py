@@ -1,0 +1,98 @@
+#!/usr/bin/env python
+"""new_anime component — similar_anime for anime the model was NOT trained on.  A new season's anime has no row in the
+trained table; here every anime of a ratings file (``user_id, anime_id, rating``: the preprocess output schema, rating
+in [0, 1]; the ratings known users gave the new anime) gets a row fitted to its own ratings with the rest of the model
+frozen (``recs.fold_in_anime``).  Writes ``folded_anime.npz`` (ids, rows, loss of every anime of the file),
+``Anime_ID_<id>_similar.csv``: the trained anime closest to the queried one (``--anime_query``: an anime id of the
+file, else the first anime of the file) under the similar_anime filters, ``Anime_ID_<id>_audience.csv``: the trained
+users predicted to rate it highest among those who have not rated it, and, with ``--output_model <file name>``, the
+model file extended by the folded rows, which similar_anime and model_recs serve the new anime from as they are.
+The similar_anime flags that pick a TRAINED anime or the rating frame (``random_anime``, ``main_df``,
+``main_df_type``) are accepted, so that a similar_anime flag set can be passed on, and not read."""
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+
+STR_FLAGS = ["main_df_type", "anime_df_type", "sypnopsis_df_type", "model_type", "model", "project_name",
+             "main_df", "sypnopses_df", "anime_df", "a_query_number", "anime_rec_genres",
+             "types", "a_rec_type", "ID_emb_name", "anime_emb_name",
+             "new_ratings", "fold_steps", "fold_lr", "audience_number"]
+BOOL_FLAGS = ["random_anime", "an_spec_genres", "spec_types", "save_sim_anime"]
+OPTIONAL_FLAGS = ["anime_query", "output_model"]     # "None" or absent: see select_anime / go
+FOLDED_FN = "folded_anime.npz"
+
+logger = C.setup_logging("new_anime")
+
+
+def make_parser():
+    p = C.make_parser("Fold in anime the model was not trained on", STR_FLAGS, BOOL_FLAGS)
+    for f in OPTIONAL_FLAGS:
+        p.add_argument("--" + f, type=str, default="None")
+    return p
+
+
+def read_ratings(path):
+    import pandas as pd
+    return pd.read_csv(path) if str(path).lower().endswith(".csv") else pd.read_parquet(path)
+
+
+def select_anime(args, new_df):
+    q = str(args.anime_query)
+    if q in ("None", ""):
+        return int(new_df["anime_id"].iloc[0])
+    try:
+        return int(q)
+    except ValueError:
+        raise ValueError("--anime_query %r: an anime id of the new ratings file is expected (a new anime has no title "
+                         "row to look up)" % (q,)) from None
+
+
+def go(args):
+    import numpy as np
+    from anime_recommendations_amd import recs, weights_io
+    anime_df = C.load_anime_df(artifacts.use_artifact(args.anime_df, args.anime_df_type))
+    syn_df = C.load_synopses(artifacts.use_artifact(args.sypnopses_df, args.sypnopsis_df_type))
+    model = weights_io.load_model(artifacts.use_artifact(args.model, args.model_type), args.ID_emb_name, args.anime_emb_name)
+    new_df = read_ratings(artifacts.use_artifact(args.new_ratings))
+    anime = select_anime(args, new_df)
+    logger.info("Using %s as input anime; %d new anime in %s", anime, new_df["anime_id"].nunique(), args.new_ratings)
+    folded = recs.fold_in_anime(model, new_df, steps=int(args.fold_steps), lr=float(args.fold_lr))
+    if folded["n_dropped"]:
+        logger.info("%d ratings by users the model has no row for were dropped", folded["n_dropped"])
+    np.savez(FOLDED_FN, ids=folded["ids"], rows=folded["rows"].cpu().numpy(), loss=folded["loss"].cpu().numpy())
+    artifacts.log_artifact(FOLDED_FN, FOLDED_FN, "npz", "Folded-in rows of the anime of " + str(args.new_ratings),
+                           metadata={"n_anime": int(len(folded["ids"])), "fold_steps": int(args.fold_steps),
+                                     "fold_lr": float(args.fold_lr), "n_dropped": folded["n_dropped"]})
+    frame, fn = C.new_anime_similar_frame(model, folded, anime_df, syn_df, anime, int(args.a_query_number),
+                                          types=C.literal(args.types) if args.spec_types else None,
+                                          genres=C.literal(args.anime_rec_genres) if args.an_spec_genres else None)
+    frame.to_csv(fn, index=False)
+    artifacts.log_artifact(fn, fn, args.a_rec_type, "Trained anime most similar to new anime : " + str(anime),
+                           metadata={"Queried anime": anime, "Model used": args.model, "Filename": fn})
+    audience, afn = C.new_anime_audience_frame(model, folded, anime, int(args.audience_number))
+    audience.to_csv(afn, index=False)
+    artifacts.log_artifact(afn, afn, args.a_rec_type, "Users predicted to rate new anime %s highest" % anime,
+                           metadata={"Queried anime": anime, "Model used": args.model, "Filename": afn})
+    if str(args.output_model) not in ("None", ""):
+        out = recs.append_anime(model, folded)
+        weights_io.save_model(args.output_model, out["U"], out["A"], out["head"], out["user_ids"], out["anime_ids"],
+                              user_name=args.ID_emb_name, anime_name=args.anime_emb_name,
+                              activation=out.get("activation"), loss=out.get("loss"))
+        artifacts.log_artifact(os.path.basename(args.output_model), args.output_model, args.model_type,
+                               "Model " + str(args.model) + " extended by the anime of " + str(args.new_ratings),
+                               metadata={"n_new_anime": int(len(folded["ids"])), "Model used": args.model})
+    if not args.save_sim_anime:
+        os.remove(fn)
+    return frame, audience
+
+
+if __name__ == "__main__":
+    _args = make_parser().parse_args()
+    try:
+        go(_args)
+    except Exception:                      # non-zero exit + the reason in ./new_anime.log
+        logger.exception("new_anime failed")
+        raise
