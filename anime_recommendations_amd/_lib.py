@@ -209,6 +209,8 @@ PROTOTYPES = {
     "anirec_predict_rank": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _vp, _i32, _vp,
                                       _vp, _vp, _vp, _sz, _vp]),
     "anirec_seen_bits": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    # the same ranks under one score vector shared by all users (the popularity baseline)
+    "anirec_score_rank": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     # rows of new users fitted to their own ratings, the rest of the model frozen
     "anirec_fold_in_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "anirec_fold_in": (C.c_int, [_vp, _i32, _i32, C.POINTER(Head), _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp, _vp, _i32,

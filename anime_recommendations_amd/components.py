@@ -462,25 +462,29 @@ def new_anime_audience_frame(model, folded, anime_id, n_users):
 # evaluate
 # ----------------------------------------------------------------------------------------
 def held_out_targets(table, test_size, min_rating):
-    """The ranking targets of a rating table: (users, target_row, target_anime, train) — the held-out rows of
-    ``table.split(test_size)`` (the rows trainer.fit validates on) rated at or above ``min_rating``, as the sorted
-    distinct user indices among them, each target's position in that list and its anime index; ``train`` is the
-    training slice."""
-    train, test = table.split(test_size)
-    take = np.asarray(table.rating[test], np.float64) >= float(min_rating)
-    tu, ta = np.asarray(table.user[test])[take], np.asarray(table.anime[test])[take]
-    users, row = np.unique(tu, return_inverse=True)
-    return users.astype(np.int64), row.astype(np.int64).reshape(-1), ta.astype(np.int64), train
+    """``recs.held_out_targets``: the one definition of the ranking targets, which trainer.fit's ranking columns read
+    too."""
+    from . import recs
+    return recs.held_out_targets(table, test_size, min_rating)
 
 
-def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0):
+BASELINES = ("popularity",)
+
+
+def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
     mrr, mean_rank, median_rank, n, n_users, test_size, min_rating and the frame's figures as hit_rate@k / ndcg@k).
-    ``model``: weights_io.load_model's dict; its id tables must be the table's."""
+    ``model``: weights_io.load_model's dict; its id tables must be the table's.
+    ``baseline="popularity"``: the same targets under the same bits ranked by the number of training ratings of each
+    anime instead (``recs.popularity_scores``, ``ops.score_rank``) — what recommending the most-rated unseen anime to
+    everyone scores; the frame gains hit_rate_popularity / ndcg_popularity, the summary popularity_mrr,
+    popularity_mean_rank, popularity_hit_rate@k and popularity_ndcg@k.  None: neither."""
     import torch
     from . import ops, recs, weights_io
+    if baseline is not None and baseline not in BASELINES:
+        raise ValueError("baseline %r is not supported (supported: %s, or None)" % (baseline, ", ".join(BASELINES)))
     U, A = np.asarray(model["U"]), np.asarray(model["A"])
     mu, ma = model.get("user_ids"), model.get("anime_ids")
     same = U.shape[0] == table.n_users and A.shape[0] == table.n_anime
@@ -495,12 +499,14 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0):
     if not ks or ks[0] < 1:
         raise ValueError("eval_k must list at least one k >= 1 (got %r)" % (ks,))
     users, row, anime, train = held_out_targets(table, test_size, min_rating)
+    base_rank = np.zeros(0, np.int32)
     if len(row):
         tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
-        seen = ops.seen_bits(torch.as_tensor(np.asarray(table.user[train])).cuda(),
-                             torch.as_tensor(np.asarray(table.anime[train])).cuda(), table.n_users, table.n_anime)
-        rank, _ = ops.predict_rank(tU, tA, weights_io.model_head(model), users, row, anime,
-                                   watched_bits=seen[torch.as_tensor(users).cuda()])
+        seen = recs.listed_seen_bits(table.user[train], table.anime[train], users, table.n_users, table.n_anime)
+        rank, _ = ops.predict_rank(tU, tA, weights_io.model_head(model), users, row, anime, watched_bits=seen)
+        if baseline == "popularity":
+            score = recs.popularity_scores(table.anime[train], table.n_anime, table.n_users).to(seen.device)
+            base_rank = ops.score_rank(score, len(users), row, anime, watched_bits=seen)
     else:
         rank = np.zeros(0, np.int32)
     m = recs.ranking_metrics(rank, ks)
@@ -510,6 +516,14 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0):
     for k in ks:
         summary["hit_rate@%d" % k] = m["hit_rate"][k]
         summary["ndcg@%d" % k] = m["ndcg"][k]
+    if baseline == "popularity":
+        b = recs.ranking_metrics(base_rank, ks)
+        frame["hit_rate_popularity"] = [b["hit_rate"][k] for k in ks]
+        frame["ndcg_popularity"] = [b["ndcg"][k] for k in ks]
+        summary["popularity_mrr"], summary["popularity_mean_rank"] = b["mrr"], b["mean_rank"]
+        for k in ks:
+            summary["popularity_hit_rate@%d" % k] = b["hit_rate"][k]
+            summary["popularity_ndcg@%d" % k] = b["ndcg"][k]
     return frame, summary
 
 

@@ -1663,6 +1663,43 @@ __global__ __launch_bounds__(256) void k_seen_bits(const int32_t *__restrict__ u
 // slices of the anime table per block of 64 targets: enough workgroups to fill the chip when the targets are few
 constexpr int kRankBlocks = 1024;
 
+// ------------------------------------------------------------------------------------
+// the same rank under ONE score vector shared by all users (anirec_score_rank): the popularity baseline.  Nothing is
+// multiplied, so a target costs n_anime compares: one wave per target, four targets per workgroup.  Lane l walks anime
+// l, l + 64, ...: score[j] is a coalesced load of a vector that stays in cache, the 64 anime of a step lie in two
+// watched words of the target's row (each lane reads its own: two distinct addresses per load), the count stays in a
+// register and the wave adds up once.  No workspace, no atomics, no LDS.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_score_rank(const float *__restrict__ score, int n_anime,
+                                                    const uint32_t *__restrict__ watched, int n_users,
+                                                    const int32_t *__restrict__ trow, const int32_t *__restrict__ tanime,
+                                                    int n_targets, int32_t *__restrict__ rank, int32_t *__restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);  // the same for the whole wave
+  if (t >= n_targets) return;
+  const int row = trow[t], at = tanime[t];
+  if ((uint32_t)row >= (uint32_t)n_users || (uint32_t)at >= (uint32_t)n_anime) {  // nothing is read through a bad index
+    if (lane == 0) {
+      *err = 1;
+      rank[t] = -1;
+    }
+    return;
+  }
+  const uint32_t kt = score_key(score[at]);
+  const uint32_t *wr = watched ? watched + (size_t)row * (size_t)((n_anime + 31) >> 5) : nullptr;
+  int cnt = 0;
+#pragma unroll 4
+  for (int j = lane; j < n_anime; j += 64) {  // j < n_anime: word j >> 5 is inside the row, bits past n_anime are never looked at
+    const uint32_t key = score_key(score[j]);
+    const uint32_t seen = wr ? (wr[j >> 5] >> (j & 31)) & 1u : 0u;
+    const bool before = key > kt || (key == kt && j < at);
+    cnt += (before && !seen && j != at) ? 1 : 0;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if (lane == 0) rank[t] = cnt;
+}
+
 }  // namespace anirec
 
 extern "C" {
@@ -1733,6 +1770,19 @@ int anirec_seen_bits(const int32_t *user_idx, const int32_t *anime_idx, int64_t 
   if (n == 0) return ANIREC_OK;
   hipLaunchKernelGGL(k_seen_bits, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, user_idx, anime_idx, (long long)n,
                      n_users, n_anime, wwords, bits, err_flag);
+  return (int)hipGetLastError();
+}
+
+int anirec_score_rank(const float *score, int32_t n_anime, const uint32_t *watched, int32_t n_users,
+                      const int32_t *target_row, const int32_t *target_anime, int32_t n_targets, int32_t *out_rank,
+                      int32_t *err_flag, void *stream) {
+  if (n_anime < 1 || n_users < 0 || n_targets < 0) return ANIREC_EINVAL;
+  if (n_targets == 0) return ANIREC_OK;
+  if (!score || !target_row || !target_anime || !out_rank || !err_flag) return ANIREC_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
+  hipLaunchKernelGGL(k_score_rank, dim3(((unsigned)n_targets + 3u) / 4u), dim3(256), 0, s, score, n_anime, watched,
+                     n_users, target_row, target_anime, n_targets, out_rank, err_flag);
   return (int)hipGetLastError();
 }
 

@@ -472,7 +472,7 @@ def seen_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
     return bits
 
 
-RANK_BATCH = 1 << 22    # targets per anirec_predict_rank call: far inside its 32-bit target offsets and grid
+RANK_BATCH = 1 << 22    # targets per anirec_predict_rank / anirec_score_rank call: far inside its 32-bit target offsets and grid
 
 
 def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None):
@@ -518,6 +518,45 @@ def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None)
     if bad:
         raise ValueError("predict_rank: target_row or target_anime out of range")
     return rank, p
+
+
+def score_rank(score, n_users, target_row, target_anime, watched_bits=None):
+    """predict_rank's ranks with ONE score vector in place of the predicted ratings (anirec_score_rank): ``score`` fp32
+    [n_anime] on the device, shared by all ``n_users`` rows; target t is (``target_row[t]``: a row of ``watched_bits``,
+    ``target_anime[t]``).  Returns rank int32 [n_t] (0 = first among the anime the row has no watched bit for, the
+    target's own bit ignored; larger score first, NaN last, ties by index).  watched_bits as predict_rank.  Raises
+    ValueError on a target_row or target_anime out of range."""
+    _need_gpu()
+    lib = _lib.load()
+    assert isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float32 and score.dim() == 1, \
+        "fp32 [n_anime] device vector"
+    dev = score.device
+    sc = score.contiguous()
+    tr, ta = _i32(target_row, dev), _i32(target_anime, dev)
+    assert tr.dim() == 1 and tr.shape == ta.shape
+    n_a, n_q, n_t = int(sc.numel()), int(n_users), int(tr.numel())
+    if n_a < 1 or n_q < 0:
+        raise ValueError("score_rank: n_anime must be >= 1 and n_users >= 0")
+    rank = torch.empty(n_t, dtype=torch.int32, device=dev)
+    if n_t == 0:
+        return rank
+    if n_q == 0:
+        raise ValueError("score_rank: target_row out of range (no users)")
+    wb = None
+    if watched_bits is not None:
+        wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
+        assert wb.shape == (n_q, (n_a + 31) // 32)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    bad = False
+    for t0 in range(0, n_t, RANK_BATCH):
+        cnt = min(RANK_BATCH, n_t - t0)
+        _lib.check(lib.anirec_score_rank(_lib.ptr(sc), n_a, _lib.ptr(wb), n_q, _lib.ptr(tr[t0:t0 + cnt]),
+                                         _lib.ptr(ta[t0:t0 + cnt]), cnt, _lib.ptr(rank[t0:t0 + cnt]), _lib.ptr(err),
+                                         _stream()), "anirec_score_rank")
+        bad = bad or bool(int(err.item()))
+    if bad:
+        raise ValueError("score_rank: target_row or target_anime out of range")
+    return rank
 
 
 def fold_in(A, head, offsets, anime_idx, rating, init, lr=0.01, steps=100, l2=1e-4, loss="binary_crossentropy"):

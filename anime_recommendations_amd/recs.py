@@ -141,6 +141,71 @@ def ranking_metrics(rank, ks):
             "n": n}
 
 
+def _host(col):
+    return col.detach().cpu().numpy() if isinstance(col, torch.Tensor) else np.asarray(col)
+
+
+def held_out_targets(table, test_size, min_rating):
+    """The ranking targets of a rating table: (users, target_row, target_anime, train) — the held-out rows of
+    ``table.split(test_size)`` (the rows trainer.fit validates on) rated at or above ``min_rating``, as the sorted
+    distinct user indices among them, each target's position in that list and its anime index; ``train`` is the
+    training slice."""
+    train, test = table.split(test_size)
+    take = _host(table.rating[test]).astype(np.float64) >= float(min_rating)
+    tu, ta = _host(table.user[test])[take], _host(table.anime[test])[take]
+    users, row = np.unique(tu, return_inverse=True)
+    return users.astype(np.int64), row.astype(np.int64).reshape(-1), ta.astype(np.int64), train
+
+
+def listed_seen_bits(user_idx, anime_idx, users, n_users, n_anime, device="cuda:0"):
+    """``ops.seen_bits`` of the listed users alone: int32 [len(users), ceil(n_anime/32)], row i the watched bits of
+    user ``users[i]`` (distinct indices) in the rating list — the rows ``ops.seen_bits(...)[users]`` would hold, without
+    the whole [n_users, words] table (769 MB at 350 000 users x 17 560 anime; 22 MB for 10 000 listed users).  The
+    ratings' users are mapped to positions in the list through a lookup tensor and those of no listed user dropped."""
+    from . import ops
+    dev = user_idx.device if isinstance(user_idx, torch.Tensor) and user_idx.is_cuda else torch.device(device)
+    u = torch.as_tensor(_host(user_idx) if not isinstance(user_idx, torch.Tensor) else user_idx, device=dev).long()
+    a = torch.as_tensor(_host(anime_idx) if not isinstance(anime_idx, torch.Tensor) else anime_idx, device=dev)
+    us = torch.as_tensor(np.asarray(users, np.int64), device=dev)
+    if us.numel() and (int(us.min()) < 0 or int(us.max()) >= int(n_users)):
+        raise ValueError("listed_seen_bits: listed user out of range")
+    if u.numel() and (int(u.min()) < 0 or int(u.max()) >= int(n_users)):
+        raise ValueError("listed_seen_bits: user index out of range")
+    lut = torch.full((int(n_users),), -1, dtype=torch.int32, device=dev)
+    lut[us] = torch.arange(int(us.numel()), dtype=torch.int32, device=dev)
+    pos = lut[u]
+    keep = pos >= 0
+    return ops.seen_bits(pos[keep], a[keep].to(torch.int32), int(us.numel()), n_anime, device=dev)
+
+
+def rank_figures(m, specs):
+    """``ranking_metrics``' dict read through ranking specs (``schedule.split_rank_metrics``): {key: figure} in the
+    specs' order, key ``hit_rate@K`` / ``ndcg@K`` / ``mrr``."""
+    return {key: (m["mrr"] if kind == "mrr" else m[kind][k]) for key, kind, k in specs}
+
+
+def popularity_scores(anime_idx, n_anime, n_users=None):
+    """The popularity baseline's score vector: fp32 [n_anime], the number of ratings each anime has in ``anime_idx``
+    (a slice of a rating table's anime column, NumPy or torch; the result lives where a torch input does, else on the
+    host) — the ``score`` of ``ops.score_rank``.  A count is exact in fp32 below 2**24, and an anime has at most one
+    rating per user (preprocess drops duplicate pairs): ValueError for ``n_users >= 2**24`` and, whatever ``n_users``
+    says, for a count that reaches 2**24."""
+    n_anime = int(n_anime)
+    if n_anime < 1:
+        raise ValueError("popularity_scores: n_anime must be >= 1")
+    if n_users is not None and int(n_users) >= 1 << 24:
+        raise ValueError("popularity_scores: n_users >= 2**24 (%d): rating counts that large are not exact in fp32"
+                         % int(n_users))
+    a = anime_idx if isinstance(anime_idx, torch.Tensor) else torch.as_tensor(np.asarray(anime_idx))
+    a = a.reshape(-1).to(torch.int64)
+    if a.numel() and bool(((a < 0) | (a >= n_anime)).any()):
+        raise ValueError("popularity_scores: anime index out of range")
+    counts = torch.bincount(a, minlength=n_anime)
+    if int(counts.max()) >= 1 << 24:
+        raise ValueError("popularity_scores: an anime has 2**24 ratings or more: not exact in fp32")
+    return counts.to(torch.float32)
+
+
 FOLD_STEPS = 100        # Adam iterations of a fold-in (DESIGN.md §4.7)
 FOLD_LR = 0.01          # and their learning rate
 

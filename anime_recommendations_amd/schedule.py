@@ -157,6 +157,43 @@ def resolve_metrics(metrics, activation="sigmoid"):
     return out
 
 
+RANK_METRIC_FORMS = "hit_rate@K and ndcg@K for an integer K >= 1, mrr (any case)"
+
+
+def split_rank_metrics(names):
+    """The ranking names of a metric list apart from the pointwise ones: returns (pointwise names in their order, to
+    hand to ``resolve_metrics``; ranking specs [(key, kind, k)] in their order) with key ``hit_rate@K`` / ``ndcg@K``
+    / ``mrr`` (lower case, K as a plain integer: the History column is ``val_`` + key), kind ``hit_rate`` / ``ndcg`` /
+    ``mrr`` and k an int or None.  ValueError, listing the accepted forms, for a ranking name without a K (``hit_rate``),
+    with a K that is no integer >= 1 (``hit_rate@0``, ``ndcg@x``), ``mrr`` with a K, or a ranking name given twice.
+    Anything that is not a list or tuple of names is returned as it is, for ``resolve_metrics`` to refuse."""
+    if isinstance(names, (str, bytes)) or not isinstance(names, (list, tuple)):
+        return names, []
+    point, specs, seen = [], [], set()
+    for m in names:
+        low = m.lower() if isinstance(m, str) else ""
+        kind, at, tail = low.partition("@")
+        if kind not in ("hit_rate", "ndcg", "mrr"):
+            point.append(m)
+            continue
+        bad = ValueError("ranking metric %r is not understood (accepted: %s)" % (m, RANK_METRIC_FORMS))
+        if kind == "mrr":
+            if at:
+                raise bad
+            key, k = "mrr", None
+        else:
+            if not (tail.isascii() and tail.isdigit()) or int(tail) < 1:
+                raise bad
+            k = int(tail)
+            key = "%s@%d" % (kind, k)
+        if key in seen:
+            raise ValueError("ranking metric %r names a column already in the list %r (accepted: %s)"
+                             % (m, list(names), RANK_METRIC_FORMS))
+        seen.add(key)
+        specs.append((key, kind, k))
+    return point, specs
+
+
 def metric_mask(resolved):
     """ANIREC_METRIC_* bits of a resolved metric set (0: nothing beyond the squared error every step keeps)."""
     mask = 0

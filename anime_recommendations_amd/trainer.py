@@ -2,6 +2,9 @@
 ``model.fit`` with LearningRateScheduler(lrfn), ModelCheckpoint(save_best_only on the monitored column) and
 EarlyStopping(patience=3, restore_best_weights=True), producing the Keras ``History`` columns
 ``loss, <metrics>, val_loss, val_<metrics>, lr`` (``loss, mse, val_loss, val_mse, lr`` with the default metrics).
+Ranking names among the metrics (``hit_rate@K``, ``ndcg@K``, ``mrr``: ``schedule.split_rank_metrics``) add one
+``val_<name>`` column each, between the ``val_`` columns and ``lr``: the held-out ratings ranked every epoch
+(``ops.predict_rank``, the ``evaluate`` component's definition), which ``monitor`` may name.
 
 All arithmetic of a step runs in libanirec (HIP); this file only sequences epochs.
 """
@@ -13,7 +16,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import _lib, ops, schedule
+from . import _lib, ops, recs, schedule
 from .data import RatingTable
 
 
@@ -42,7 +45,9 @@ class FitConfig:
     loss: str = "binary_crossentropy"        # config.yaml model.model_loss (schedule.LOSSES, any case / alias)
     activation: str = "sigmoid"              # config.yaml model.activation_function (schedule.ACTIVATIONS)
     kernel_initializer: str = "he_normal"    # config.yaml model.kernel_initializer (schedule.INITIALIZERS)
-    metrics: tuple = ("mse",)                # config.yaml model.model_metrics (schedule.resolve_metrics)
+    metrics: tuple = ("mse",)                # config.yaml model.model_metrics (schedule.resolve_metrics), and the
+                                             # ranking names hit_rate@K / ndcg@K / mrr (schedule.split_rank_metrics)
+    rank_min_rating: float = 0.0             # ranking columns: the validation rows rated at or above it are the targets
 
     def lr(self, epoch):
         return schedule.lrfn(epoch, self.start_lr, self.max_lr, self.min_lr, self.rampup_epochs,
@@ -66,6 +71,8 @@ class FitResult:
     activation: str = "sigmoid"
     step_loop_seconds: list = field(default_factory=list)   # per epoch: wall time of the step loop alone (synchronised)
     epoch_seconds: list = field(default_factory=list)       # per epoch: shuffle + steps + metrics + validation + snapshot
+    rank_seconds: list = field(default_factory=list)        # per epoch: wall time of the ranking columns (inside epoch_seconds)
+    rank_baseline: dict = field(default_factory=dict)       # the ranking columns' figures of the popularity baseline
 
 
 def _truncated_normal(rng, std):
@@ -128,14 +135,26 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     width = _lib.check_width(cfg.embedding_size)     # (ValueError before anything is allocated or the engine touched)
     kind = schedule.resolve_optimizer(cfg.optimizer)
     loss_name, act_name = schedule.resolve_loss(cfg.loss), schedule.resolve_activation(cfg.activation)
-    metrics = schedule.resolve_metrics(cfg.metrics, act_name)
+    point_names, rank_specs = schedule.split_rank_metrics(cfg.metrics)
+    metrics = schedule.resolve_metrics(point_names, act_name)
     mask = schedule.metric_mask(metrics)
     # the default set (mse alone) reads the two sums every step keeps: epoch_metrics / evaluate, as it always did
     plain = [kind for _, kind in metrics] == ["mse"]
     keys = ["loss"] + [k for k, _ in metrics]
-    keys = keys + ["val_" + k for k in keys] + ["lr"]
+    rank_keys = ["val_" + key for key, _, _ in rank_specs]
+    keys = keys + ["val_" + k for k in keys] + rank_keys + ["lr"]
     if cfg.monitor not in keys[:-1]:
         raise ValueError("monitor %r names no History column (%s)" % (cfg.monitor, ", ".join(keys[:-1])))
+    if rank_specs:
+        if engine is not None and hasattr(engine, "set_epoch_global"):
+            raise ValueError("ranking metrics (%s) need the whole user table on one GPU: a multi-GPU engine shards "
+                             "the user rows (rank a saved model with the evaluate component)"
+                             % ", ".join(key for key, _, _ in rank_specs))
+        r_users, r_row, r_anime, _ = recs.held_out_targets(table, cfg.test_size, cfg.rank_min_rating)
+        if len(r_row) == 0:
+            raise ValueError("no validation row is rated at or above rank_min_rating = %r: the ranking metrics (%s) "
+                             "have no target" % (cfg.rank_min_rating, ", ".join(key for key, _, _ in rank_specs)))
+        rank_ks = sorted({k for _, _, k in rank_specs if k is not None})
     tr, te = table.split(cfg.test_size)
     n_train = tr.stop - tr.start
     if engine is None:
@@ -180,7 +199,20 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     best_w = None
     best_epoch, stopped, wait = -1, -1, 0
     t_global = 0
-    loop_s, epoch_s = [], []
+    loop_s, epoch_s, rank_s = [], [], []
+    rank_baseline = {}
+    if rank_specs:
+        # once: the targets, the watched bits of the listed users alone and the popularity baseline on the same targets
+        with torch.cuda.device(dev):
+            r_row_t, r_anime_t = (torch.as_tensor(x, device=dev).to(torch.int32) for x in (r_row, r_anime))
+            r_users_t = torch.as_tensor(r_users, device=dev).to(torch.int32)
+            r_bits = recs.listed_seen_bits(ui, ai, r_users, table.n_users, table.n_anime, device=dev)
+            score = recs.popularity_scores(ai, table.n_anime, table.n_users)
+            base = recs.ranking_metrics(ops.score_rank(score, len(r_users), r_row_t, r_anime_t, watched_bits=r_bits),
+                                        rank_ks)
+        rank_baseline = {"val_" + k: v for k, v in recs.rank_figures(base, rank_specs).items()}
+        log("Popularity baseline on the %d ranking targets of %d users - %s"
+            % (len(r_row), len(r_users), " - ".join("%s: %.4f" % kv for kv in rank_baseline.items())))
     for epoch in range(cfg.epochs):
         t_epoch = time.perf_counter()
         lr = cfg.lr(epoch)
@@ -209,7 +241,19 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
         else:
             logs, val_logs = engine.epoch_logs(), engine.eval_logs(vu, va, vt)
         row = [logs["loss"]] + [logs[kind] for _, kind in metrics]
-        row += [val_logs["loss"]] + [val_logs[kind] for _, kind in metrics] + [float(np.float32(lr))]
+        row += [val_logs["loss"]] + [val_logs[kind] for _, kind in metrics]
+        if rank_specs:
+            # the tables are current here, as for the snapshot below: the engine's stream is drained, the rank kernels
+            # run on torch's and are finished (the ranks are read back) before the next epoch writes W
+            t_rank = time.perf_counter()
+            engine.synchronize()
+            with torch.cuda.device(dev):
+                rank, _ = ops.predict_rank(engine.U, engine.A, dict(head_of(engine.read_state()), activation=act_name),
+                                           r_users_t, r_row_t, r_anime_t, watched_bits=r_bits)
+                row += list(recs.rank_figures(recs.ranking_metrics(rank, rank_ks), rank_specs).values())
+                torch.cuda.synchronize(dev)
+            rank_s.append(time.perf_counter() - t_rank)
+        row.append(float(np.float32(lr)))
         for k, v in zip(keys, row):
             hist[k].append(v)
         if cfg.verbose:
@@ -235,7 +279,8 @@ def fit(table: RatingTable, cfg: FitConfig, engine=None, log=print, device="cuda
     rec = engine.read_state()
     res = FitResult(history=hist, U=engine.U.cpu().numpy().copy(), A=engine.A.cpu().numpy().copy(),
                     head=head_of(rec), best_epoch=best_epoch, stopped_epoch=stopped, step_loop_seconds=loop_s,
-                    epoch_seconds=epoch_s, optimizer_name=kind, loss=loss_name, activation=act_name)
+                    epoch_seconds=epoch_s, optimizer_name=kind, loss=loss_name, activation=act_name,
+                    rank_seconds=rank_s, rank_baseline=rank_baseline)
     if hasattr(engine, "optimizer_state"):       # optimiser slots and the step count of the LAST epoch (model.save)
         res.optimizer = engine.optimizer_state(iterations=t_global)
     if best_w is not None:

@@ -2,7 +2,8 @@
 """evaluate component — how well a trained model RANKS: the ratings the neural_network run held out for validation
 (the last ``test_size`` rows of the same encoding and RandomState(42) shuffle) are ranked among the anime their user
 has no training rating for, by predicted rating, and hit rate / NDCG at each ``eval_k``, MRR and the mean and median
-rank are written to ``eval_csv``.  The reference has no such step: its author lists comparing re-trained models as
+rank are written to ``eval_csv``; ``--baseline popularity`` adds the same figures for ranking by rating count alone, to
+read the model's against.  The reference has no such step: its author lists comparing re-trained models as
 an idea for improvement; ``val_loss`` cannot compare models across losses and activations, these figures can."""
 import json
 import os
@@ -27,7 +28,8 @@ def go(args):
     table = ingest.load_user_stats(artifacts.use_artifact(args.input_data, args.main_df_type))
     logger.info("Final df shape is (%d, 3); %d users, %d anime", len(table), table.n_users, table.n_anime)
     frame, summary = C.evaluate_frame(model, table, int(args.test_size), C.literal(args.eval_k),
-                                      float(args.min_rating))
+                                      float(args.min_rating),
+                                      baseline=None if args.baseline.lower() == "none" else args.baseline.lower())
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -38,7 +40,11 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = C.make_parser("Rank the held-out ratings with a trained model", STR_FLAGS, BOOL_FLAGS).parse_args()
+    _parser = C.make_parser("Rank the held-out ratings with a trained model", STR_FLAGS, BOOL_FLAGS)
+    # optional, unlike the flags above: "popularity" adds the figures of recommending the most-rated unseen anime
+    _parser.add_argument("--baseline", type=str, default="none", required=False,
+                         help="none, or popularity: rank the same targets by the anime's number of training ratings")
+    _args = _parser.parse_args()
     try:
         go(_args)
     except Exception:                      # non-zero exit + the reason in ./evaluate.log

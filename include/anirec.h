@@ -625,6 +625,21 @@ int anirec_predict_rank(const float *U, const float *A, int32_t dim, int32_t n_a
                         const int32_t *target_row, const int32_t *target_anime, int32_t n_targets, int32_t *out_rank,
                         float *out_p, int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The same rank under ONE score vector shared by all users (a popularity baseline: score[j] = how often anime j was
+ * rated): per target t = (target_row[t], target_anime[t]),
+ *   out_rank[t] = #{ j != a_t : watched bit j of row target_row[t] clear and
+ *                    (key(score[j]) > key(score[a_t]) or (key(score[j]) == key(score[a_t]) and j < a_t)) }
+ * key as anirec_predict_rank: larger score first, NaN after every number, ties in ascending index.  The target's own
+ * watched bit is ignored; bits at positions >= n_anime of a row's last word have no effect.
+ * watched: optional [n_users][ceil(n_anime/32)].  *err_flag (device) is cleared by the call and becomes 1 on a
+ * target_row outside [0, n_users) or a target_anime outside [0, n_anime): that target gets rank -1, nothing is read
+ * through it, the other targets are unaffected.  n_anime < 1, a negative count, or a NULL score, target array,
+ * out_rank or err_flag with n_targets > 0: ANIREC_EINVAL.  n_targets == 0: ANIREC_OK, nothing enqueued.  One wave
+ * per target, no workspace, no atomics: bit-reproducible.  Cost: n_targets n_anime compares, 4 bytes per target. */
+int anirec_score_rank(const float *score, int32_t n_anime, const uint32_t *watched, int32_t n_users,
+                      const int32_t *target_row, const int32_t *target_anime, int32_t n_targets, int32_t *out_rank,
+                      int32_t *err_flag, void *stream);
+
 /* Watched bits of a rating list: bits[n_users][ceil(n_anime/32)] is zeroed, then bit (a & 31) of word a >> 5 of row u
  * is set for each of the n ratings (user_idx[i], anime_idx[i]) = (u, a); repeats are harmless.  The table
  * anirec_predict_topk* and anirec_predict_rank take as `watched`.  *err_flag (device) becomes 1 on an index out of

@@ -36,8 +36,10 @@ def go(args):
     activation = schedule.resolve_activation(args.activation_function)   # sigmoid, linear, tanh, relu, softplus
     initializer = schedule.resolve_initializer(args.kernel_initializer)
     # model.compile(metrics=ast.literal_eval(args.model_metrics)) (neural_network.py:102-104): History columns and
-    # val_ columns, accumulated on the GPU
-    metrics = schedule.resolve_metrics(ast.literal_eval(args.model_metrics), activation)
+    # val_ columns, accumulated on the GPU.  The ranking names (hit_rate@K, ndcg@K, mrr: a val_ column each, which
+    # --checkpoint_metric may name with --mode max) are no Keras metrics and go to trainer.fit as they are
+    point_names, rank_specs = schedule.split_rank_metrics(ast.literal_eval(args.model_metrics))
+    metrics = schedule.resolve_metrics(point_names, activation)
     metric_names = tuple(ast.literal_eval(args.model_metrics))
     if args.TPU_INIT:
         logger.info("TPU_INIT requested: ignored, training runs on MI355X (use torchrun for >1 GPU)")
@@ -62,7 +64,8 @@ def go(args):
         rampup_epochs=int(args.rampup_epochs), sustain_epochs=int(args.sustain_epochs),
         exp_decay=float(args.exp_decay), monitor=args.checkpoint_metric, mode=args.mode,
         verbose=int(args.verbose), seed=int(os.environ.get("ANIREC_SEED", "0")), optimizer=optimizer, loss=loss,
-        activation=activation, kernel_initializer=initializer, metrics=metric_names)
+        activation=activation, kernel_initializer=initializer, metrics=metric_names,
+        rank_min_rating=float(os.environ.get("ANIREC_RANK_MIN_RATING", "0.0")))
     # >1 rank: ratings sharded by user over RCCL.  The reference's TPU branch (neural_network.py:173-178)
     # computes batch_size * replicas and max_lr * replicas but never uses them: model.fit gets
     # args.batch_size (:213) and lrfn reads args.max_lr (:113), so the GLOBAL batch and the schedule are
@@ -118,8 +121,13 @@ def go(args):
         hist.to_json(f)
     hist.to_csv(args.history_csv)
     artifacts.log_artifact(args.weights_artifact, wpath, args.weights_type, "file containing all weights")
+    # with ranking columns: what recommending the most-rated unseen anime to everyone scores on the same targets
+    hist_meta = None
+    if res.rank_baseline:
+        hist_meta = {"rank_min_rating": cfg.rank_min_rating}
+        hist_meta.update({"popularity_" + k: v for k, v in res.rank_baseline.items()})
     artifacts.log_artifact(args.history_csv, args.history_csv, args.history_type,
-                           "csv file of neural network training history")
+                           "csv file of neural network training history", metadata=hist_meta)
     if args.save_model:
         artifacts.log_artifact(args.model_artifact, mpath, args.model_type, "trained neural network",
                                metadata={"Loss function": args.model_loss, "Optimizer": args.optimizer,
