@@ -270,13 +270,15 @@ __device__ __forceinline__ float rating_from_cosine(float c, float hs, float hb,
 
 // host: a row width the *_w entry points implement (a row is dim / 4 lanes of float4: 8, 16, 32 or 64 lanes)
 static inline bool dim_ok(int32_t dim) { return dim == 32 || dim == 64 || dim == 128 || dim == 256; }
-// host: calls f(std::integral_constant<int, kD>) for a (checked) width OTHER than ANIREC_DIM — the 128-wide kernels
-// keep their own launches (and names), so nothing of them is instantiated twice
+// host: calls f(std::integral_constant<int, kD>) with a (checked) width as a compile-time constant.  A kernel that
+// exists off 128 only (the run-time-head kernels, whose 128 form takes the head as template constants) is launched
+// under `if constexpr (kD != kDim)` inside f, so nothing of it is instantiated at 128.
 template <typename F>
 static inline void with_width(int32_t dim, F &&f) {
   switch (dim) {
     case 32: f(std::integral_constant<int, 32>()); break;
     case 64: f(std::integral_constant<int, 64>()); break;
+    case 128: f(std::integral_constant<int, 128>()); break;
     case 256: f(std::integral_constant<int, 256>()); break;
     default: break;
   }
@@ -309,6 +311,16 @@ static inline auto with_loss(int32_t loss, F &&f) {
     case ANIREC_LOSS_HUBER: return f(std::integral_constant<int, ANIREC_LOSS_HUBER>());
     case ANIREC_LOSS_LOGCOSH: return f(std::integral_constant<int, ANIREC_LOSS_LOGCOSH>());
     default: return f(std::integral_constant<int, ANIREC_LOSS_BCE>());
+  }
+}
+// host: calls f(std::integral_constant<int, kOpt>) with the update rule (ANIREC_OPT_*) as a compile-time constant
+template <typename F>
+static inline auto with_opt(int32_t kind, F &&f) {
+  switch (kind) {
+    case ANIREC_OPT_SGD: return f(std::integral_constant<int, ANIREC_OPT_SGD>());
+    case ANIREC_OPT_RMSPROP: return f(std::integral_constant<int, ANIREC_OPT_RMSPROP>());
+    case ANIREC_OPT_ADAGRAD: return f(std::integral_constant<int, ANIREC_OPT_ADAGRAD>());
+    default: return f(std::integral_constant<int, ANIREC_OPT_ADAM>());
   }
 }
 

@@ -421,13 +421,9 @@ int anirec_fold_in(const float *A, int32_t dim, int32_t n_anime, const anirec_he
   a.out_rows = out_rows;
   a.out_loss = out_loss;
   a.err = err_flag;
-  auto launch = [&](auto kd) {
+  with_width(dim, [&](auto kd) {
     hipLaunchKernelGGL(k_fold_in<decltype(kd)::value>, dim3((unsigned)n_new), dim3(256), 0, s, a);
-  };
-  if (dim == kDim)
-    launch(std::integral_constant<int, kDim>());
-  else
-    with_width(dim, launch);
+  });
   return (int)hipGetLastError();
 }
 
@@ -482,7 +478,7 @@ int anirec_fold_in_split(const float *T, int32_t dim, int32_t n_table, const ani
   a.part = (float *)(ws + lay.part);
   a.part_loss = (float *)(ws + lay.part_loss);
   hipLaunchKernelGGL(k_fold_check, dim3((unsigned)n_new, kCheckY), dim3(256), 0, s, a);
-  auto chain = [&](auto kd) {
+  with_width(dim, [&](auto kd) {
     constexpr int kD = decltype(kd)::value;
     const dim3 rows((unsigned)((n_new + 1024 / kD - 1) / (1024 / kD)));  // 256 / (kD / 4) rows per workgroup
     for (int st = 0; st <= steps; ++st) {
@@ -492,11 +488,7 @@ int anirec_fold_in_split(const float *T, int32_t dim, int32_t n_table, const ani
       else
         hipLaunchKernelGGL((k_fold_step<kD, true>), rows, dim3(256), 0, s, a, st);
     }
-  };
-  if (dim == kDim)
-    chain(std::integral_constant<int, kDim>());
-  else
-    with_width(dim, chain);
+  });
   return (int)hipGetLastError();
 }
 

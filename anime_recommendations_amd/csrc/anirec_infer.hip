@@ -86,25 +86,17 @@ __device__ __forceinline__ void rownorm_body(const float *W, const int32_t *rows
     reinterpret_cast<float4 *>(out)[(size_t)r * kG + l] = y;
   }
 }
-template <int kMode>
-__global__ __launch_bounds__(256) void k_rownorm(const float *W, const int32_t *rows, int n,
-                                                 float *out) {
-  rownorm_body<kMode, kDim>(W, rows, n, out);
-}
-template <int kMode, int kD>  // the widths other than 128 (the *_w entry points)
-__global__ __launch_bounds__(256) void k_rownorm_w(const float *W, const int32_t *rows, int n, float *out) {
+template <int kMode, int kD = kDim>
+__global__ __launch_bounds__(256) void k_rownorm(const float *W, const int32_t *rows, int n, float *out) {
   rownorm_body<kMode, kD>(W, rows, n, out);
 }
 template <int kMode>
 static void launch_rownorm(const float *W, const int32_t *rows, int n, float *out, int dim, hipStream_t s) {
   int blocks = (int)(((long long)n * dim + 1023) / 1024);  // 1024 / dim rows per workgroup
   if (blocks > 4096) blocks = 4096;
-  if (dim == kDim)
-    hipLaunchKernelGGL(k_rownorm<kMode>, dim3(blocks), dim3(256), 0, s, W, rows, n, out);
-  else
-    with_width(dim, [&](auto kd) {
-      hipLaunchKernelGGL((k_rownorm_w<kMode, decltype(kd)::value>), dim3(blocks), dim3(256), 0, s, W, rows, n, out);
-    });
+  with_width(dim, [&](auto kd) {
+    hipLaunchKernelGGL((k_rownorm<kMode, decltype(kd)::value>), dim3(blocks), dim3(256), 0, s, W, rows, n, out);
+  });
 }
 // the mode-1 rows for the other translation units (anirec_foldin.hip): the same kernels, nothing instantiated twice
 void l2norm_rows(const float *W, int n, float *out, int dim, hipStream_t s) {
@@ -592,11 +584,13 @@ static int launch_scores(const ScoreArgs &a0, hipStream_t s, int32_t act = ANIRE
   if (dim != kDim) {
     with_width(dim, [&](auto kd) {
       constexpr int kD = decltype(kd)::value;
-      if (a.nq <= kFewQ) {
-        hipLaunchKernelGGL(k_scores_few_w<kD>, dim3((a.n + 63) / 64), dim3(256), 0, s, a);
-      } else {
-        dim3 grid((a.n + kTile - 1) / kTile, (a.nq + kTile - 1) / kTile);
-        hipLaunchKernelGGL(k_scores_w<kD>, grid, dim3(256), 0, s, a);
+      if constexpr (kD != kDim) {  // (nothing of the run-time-head kernels is instantiated at 128)
+        if (a.nq <= kFewQ) {
+          hipLaunchKernelGGL(k_scores_few_w<kD>, dim3((a.n + 63) / 64), dim3(256), 0, s, a);
+        } else {
+          dim3 grid((a.n + kTile - 1) / kTile, (a.nq + kTile - 1) / kTile);
+          hipLaunchKernelGGL(k_scores_w<kD>, grid, dim3(256), 0, s, a);
+        }
       }
     });
     return (int)hipGetLastError();
@@ -733,8 +727,9 @@ int anirec_predict_pairs_w(const float *U, const float *A, int32_t dim, const in
   if (dim != kDim) {
     with_width(dim, [&](auto kd) {
       constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
-      hipLaunchKernelGGL(k_predict_pairs_w<kD>, dim3((n + kRpb - 1) / kRpb), dim3(256), 0, (hipStream_t)stream, U, A,
-                         user_idx, anime_idx, n, hs, hb, (int)activation, p);
+      if constexpr (kD != kDim)  // (nothing of k_predict_pairs_w is instantiated at 128)
+        hipLaunchKernelGGL(k_predict_pairs_w<kD>, dim3((n + kRpb - 1) / kRpb), dim3(256), 0, (hipStream_t)stream, U, A,
+                           user_idx, anime_idx, n, hs, hb, (int)activation, p);
     });
     return (int)hipGetLastError();
   }
@@ -1746,15 +1741,11 @@ int anirec_predict_rank(const float *U, const float *A, int32_t dim, int32_t n_a
   a.slice_len = (tiles + S - 1) / S * kTile;
   a.slices = (n_anime + a.slice_len - 1) / a.slice_len;
   const dim3 g0((n_targets + 255) / 256), g1((unsigned)tblocks * (unsigned)a.slices);
-  auto launch = [&](auto kd) {
+  with_width(dim, [&](auto kd) {
     constexpr int kD = decltype(kd)::value;
     hipLaunchKernelGGL(k_rank_targets<kD>, g0, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_rank_count<kD>, g1, dim3(256), 0, s, a);
-  };
-  if (dim == kDim)
-    launch(std::integral_constant<int, kDim>());
-  else
-    with_width(dim, launch);
+  });
   return (int)hipGetLastError();
 }
 

@@ -444,17 +444,13 @@ __device__ __forceinline__ void fwd_block(const FwdArgs &a, const anirec_step sc
   }
 }
 
+// 1024 / kD ratings per workgroup.  The stamps are taken at 128 only (anirec_train_stage_ticks refuses the other widths).
+template <int kD = kDim>
 __global__ __launch_bounds__(256) void k_fwd(FwdArgs a) {
-  tick(a.ticks, 0);
-  const int step = a.state->step_fwd;
-  fwd_block(a, a.sched[step], blockIdx.x, step);
-  tick(a.ticks, 1);
-}
-// the same at another width (anirec_train_fwd_w): 1024 / kD ratings per workgroup
-template <int kD>
-__global__ __launch_bounds__(256) void k_fwd_w(FwdArgs a) {
+  if constexpr (kD == kDim) tick(a.ticks, 0);
   const int step = a.state->step_fwd;
   fwd_block<kD>(a, a.sched[step], blockIdx.x, step);
+  if constexpr (kD == kDim) tick(a.ticks, 1);
 }
 
 // Multi-GPU only: (mean, M2) of this rank's z = w*c + b values, two-pass, written next to the
@@ -974,15 +970,12 @@ __device__ __forceinline__ void bwd_body(const BwdArgs &a) {
   bwd_chunk<kD>(a, pub, par, m, x);
 }
 
-__global__ __launch_bounds__(256, 7) void k_bwd(BwdArgs a) {
-  tick(a.ticks, 0);
-  bwd_body(a);
-  tick(a.ticks, 1);
-}
-// the same at another width (anirec_train_bwd_w): a row group per chunk, 1024 / kD chunks per workgroup
-template <int kD>
-__global__ __launch_bounds__(256) void k_bwd_w(BwdArgs a) {
+// a row group per chunk, 1024 / kD chunks per workgroup; the occupancy hint and the stamps are 128's alone
+template <int kD = kDim>
+__global__ __launch_bounds__(256, kD == kDim ? 7 : 1) void k_bwd(BwdArgs a) {
+  if constexpr (kD == kDim) tick(a.ticks, 0);
   bwd_body<kD>(a);
+  if constexpr (kD == kDim) tick(a.ticks, 1);
 }
 
 // g += P[c], s += S[c] for c = c0 .. c1-1 IN THAT ORDER (the sums are bit-reproducible), the loads issued kB
@@ -1336,27 +1329,14 @@ __device__ __forceinline__ void adam_body(const AdamArgs &a, int bid, int nblock
   }
 }
 
-template <bool kNT>
+// the dense update under any rule (Adam: 24 B/element, SGD: 8, RMSprop / Adagrad: 16) at any width; the stamps are
+// taken at 128 only
+template <bool kNT, int kOpt = ANIREC_OPT_ADAM, int kD = kDim>
 __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
   __shared__ float scratch[kHeadCols * 16];
-  tick(a.ticks, 0);
-  adam_body<kNT, ANIREC_OPT_ADAM>(a, blockIdx.x, gridDim.x, scratch);
-  tick(a.ticks, 1);
-}
-
-// the same dense update under one of the one-slot rules (SGD: 8 B/element, RMSprop / Adagrad: 16 B/element)
-template <bool kNT, int kOpt>
-__global__ __launch_bounds__(256) void k_dense_opt(AdamArgs a) {
-  __shared__ float scratch[kHeadCols * 16];
-  tick(a.ticks, 0);
-  adam_body<kNT, kOpt>(a, blockIdx.x, gridDim.x, scratch);
-  tick(a.ticks, 1);
-}
-// the dense update at another width (anirec_train_adam_w), any rule: one instantiation per (rule, width)
-template <bool kNT, int kOpt, int kD>
-__global__ __launch_bounds__(256) void k_dense_opt_w(AdamArgs a) {
-  __shared__ float scratch[kHeadCols * 16];
+  if constexpr (kD == kDim) tick(a.ticks, 0);
   adam_body<kNT, kOpt, kD>(a, blockIdx.x, gridDim.x, scratch);
+  if constexpr (kD == kDim) tick(a.ticks, 1);
 }
 
 // ------------------------------------------------------------------------------------
@@ -2082,13 +2062,9 @@ __device__ __forceinline__ void reg_init_body(const float *W, int row_lo, int n_
     }
   }
 }
+template <int kD = kDim>
 __global__ __launch_bounds__(256) void k_reg_init(const float *W, int row_lo, int n_rows, int n_user_rows,
                                                   float *regpart) {
-  reg_init_body(W, row_lo, n_rows, n_user_rows, regpart);
-}
-template <int kD>
-__global__ __launch_bounds__(256) void k_reg_init_w(const float *W, int row_lo, int n_rows, int n_user_rows,
-                                                    float *regpart) {
   reg_init_body<kD>(W, row_lo, n_rows, n_user_rows, regpart);
 }
 
@@ -2557,14 +2533,10 @@ static FwdArgs fwd_args(const anirec_train_desc *d, const TrainWs &w) {
 static int launch_fwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   const FwdArgs a = fwd_args(d, w);
   float *pk = packet_ptr(d, d->my_seg);
-  if (w.dim == kDim) {
-    hipLaunchKernelGGL(k_fwd, dim3((d->max_batch + 7) / 8), dim3(256), 0, s, a);
-  } else {
-    with_width(w.dim, [&](auto kd) {
-      constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
-      hipLaunchKernelGGL(k_fwd_w<kD>, dim3((d->max_batch + kRpb - 1) / kRpb), dim3(256), 0, s, a);
-    });
-  }
+  with_width(w.dim, [&](auto kd) {
+    constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
+    hipLaunchKernelGGL(k_fwd<kD>, dim3((d->max_batch + kRpb - 1) / kRpb), dim3(256), 0, s, a);
+  });
   if (int te = ticks_collect(w, 0, s)) return te;
   if (d->n_seg > 1)
     hipLaunchKernelGGL(k_seg_stats, dim3(1), dim3(1024), 0, s, pk, packet_cap(d->max_batch), d->max_batch,
@@ -2692,14 +2664,10 @@ static int launch_bwd_only(const anirec_train_desc *d, const TrainWs &w, hipStre
     else
       a.rowmap = nullptr;
   }
-  if (w.dim == kDim) {
-    hipLaunchKernelGGL(k_bwd, dim3((2 * w.capC + 7) / 8), dim3(256), 0, s, a);
-  } else {
-    with_width(w.dim, [&](auto kd) {
-      constexpr int kD = decltype(kd)::value, kRpb = BwdGeom<kD>::kRpb;
-      hipLaunchKernelGGL(k_bwd_w<kD>, dim3((2 * w.capC + kRpb - 1) / kRpb), dim3(256), 0, s, a);
-    });
-  }
+  with_width(w.dim, [&](auto kd) {
+    constexpr int kD = decltype(kd)::value, kRpb = BwdGeom<kD>::kRpb;
+    hipLaunchKernelGGL(k_bwd<kD>, dim3((2 * w.capC + kRpb - 1) / kRpb), dim3(256), 0, s, a);
+  });
   if (int te = ticks_collect(w, 2, s)) return te;
   return (int)hipGetLastError();
 }
@@ -2783,40 +2751,13 @@ static int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStr
   }
   const bool nt = stream_nt(d, w.dim);
   const dim3 grid(table_grid(d, w)), block(256);
-  if (w.dim != kDim) {  // (dense one-GPU step only: check_desc)
-    with_width(w.dim, [&](auto kd) {
-      constexpr int kD = decltype(kd)::value;
-      const auto go = [&](auto opt) {
-        constexpr int kOpt = decltype(opt)::value;
-        if (nt) hipLaunchKernelGGL((k_dense_opt_w<true, kOpt, kD>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_dense_opt_w<false, kOpt, kD>), grid, block, 0, s, a);
-      };
-      switch (d->optimizer) {
-        case ANIREC_OPT_SGD: go(std::integral_constant<int, ANIREC_OPT_SGD>()); break;
-        case ANIREC_OPT_RMSPROP: go(std::integral_constant<int, ANIREC_OPT_RMSPROP>()); break;
-        case ANIREC_OPT_ADAGRAD: go(std::integral_constant<int, ANIREC_OPT_ADAGRAD>()); break;
-        default: go(std::integral_constant<int, ANIREC_OPT_ADAM>());
-      }
+  with_width(w.dim, [&](auto kd) {  // (off 128: the dense one-GPU step only, check_desc)
+    with_opt(d->optimizer, [&](auto opt) {
+      constexpr int kD = decltype(kd)::value, kOpt = decltype(opt)::value;
+      if (nt) hipLaunchKernelGGL((k_adam<true, kOpt, kD>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((k_adam<false, kOpt, kD>), grid, block, 0, s, a);
     });
-    return (int)hipGetLastError();
-  }
-  switch (d->optimizer) {
-    case ANIREC_OPT_SGD:
-      if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_SGD>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((k_dense_opt<false, ANIREC_OPT_SGD>), grid, block, 0, s, a);
-      break;
-    case ANIREC_OPT_RMSPROP:
-      if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_RMSPROP>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((k_dense_opt<false, ANIREC_OPT_RMSPROP>), grid, block, 0, s, a);
-      break;
-    case ANIREC_OPT_ADAGRAD:
-      if (nt) hipLaunchKernelGGL((k_dense_opt<true, ANIREC_OPT_ADAGRAD>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((k_dense_opt<false, ANIREC_OPT_ADAGRAD>), grid, block, 0, s, a);
-      break;
-    default:
-      if (nt) hipLaunchKernelGGL((k_adam<true>), grid, block, 0, s, a);
-      else hipLaunchKernelGGL((k_adam<false>), grid, block, 0, s, a);
-  }
+  });
   if (int te = ticks_collect(w, 3, s)) return te;
   return (int)hipGetLastError();
 }
@@ -3097,12 +3038,9 @@ int anirec_train_init_reg_w(const anirec_train_desc *d, int32_t dim, void *strea
     hi = d->adam_row_hi;
   }
   const dim3 grid(table_grid(d, w));
-  if (dim == kDim)
-    hipLaunchKernelGGL(k_reg_init, grid, dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
-  else
-    with_width(dim, [&](auto kd) {
-      hipLaunchKernelGGL(k_reg_init_w<decltype(kd)::value>, grid, dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
-    });
+  with_width(dim, [&](auto kd) {
+    hipLaunchKernelGGL(k_reg_init<decltype(kd)::value>, grid, dim3(256), 0, s, d->W, lo, hi, d->n_user_rows, w.regpart);
+  });
   ANIREC_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_sum_regpart, dim3(1), dim3(1024), 0, s, d->state, w.regpart);
   return (int)hipGetLastError();
@@ -3534,9 +3472,11 @@ int anirec_eval_metrics_w(const anirec_train_desc *d, int32_t dim, uint32_t mask
   if (dim != kDim) {  // the head as run-time values: one kernel per width
     with_width(dim, [&](auto kd) {
       constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
-      const dim3 grid((n + kRpb - 1) / kRpb);
-      if (m.mask) hipLaunchKernelGGL((k_eval_w<true, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
-      else hipLaunchKernelGGL((k_eval_w<false, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
+      if constexpr (kD != kDim) {  // (nothing of k_eval_w is instantiated at 128)
+        const dim3 grid((n + kRpb - 1) / kRpb);
+        if (m.mask) hipLaunchKernelGGL((k_eval_w<true, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
+        else hipLaunchKernelGGL((k_eval_w<false, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
+      }
     });
     return (int)hipGetLastError();
   }

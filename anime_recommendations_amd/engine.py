@@ -43,8 +43,7 @@ def _column(x, dtype, device):
 class TrainEngine:
     def __init__(self, n_user_rows, n_anime_rows, max_batch, l2=1e-4, arena_steps=64,
                  device="cuda:0", n_seg=1, my_seg=0, dense_mode=0, row_pad=1, adam_rows=None, lazy=None,
-                 optimizer="adam", loss="binary_crossentropy", activation="sigmoid", metrics=0, width=DIM,
-                 w_entry=None):
+                 optimizer="adam", loss="binary_crossentropy", activation="sigmoid", metrics=0, width=DIM):
         """dense_mode: 0 one GPU; 1 user-sharded DP (anime gradient through ``dense_grad``); 2 replicated
         tables (every gradient through ``dense_grad``).  row_pad: the tables and the dense buffer are
         allocated with their row count rounded up to a multiple of it (equal reduce-scatter / all-gather
@@ -64,11 +63,10 @@ class TrainEngine:
         metrics: ANIREC_METRIC_* bits (``schedule.metric_mask``) of the Keras metrics the train step and the validation
         pass accumulate on the GPU beside the squared error (``epoch_logs`` / ``eval_logs``); 0 = none, the step as
         without them.
-        width: the embedding width (``_lib.WIDTHS``: 32, 64, 128, 256; the reference's --embedding_size).  Another
-        width than 128 trains through the ``*_w`` entry points with the dense update on one GPU: ``lazy`` resolves to
-        False there (``lazy=True`` is a ValueError, as with a non-Adam optimizer), and ``dense_mode != 0`` / ``n_seg >
-        1`` are ValueErrors.  w_entry: call the ``*_w`` entry points (None: exactly when width != 128; True at 128 runs
-        the twins, which are the same kernels)."""
+        width: the embedding width (``_lib.WIDTHS``: 32, 64, 128, 256; the reference's --embedding_size), handed to the
+        ``*_w`` entry points the engine calls.  Another width than 128 trains with the dense update on one GPU:
+        ``lazy`` resolves to False there (``lazy=True`` is a ValueError, as with a non-Adam optimizer), and
+        ``dense_mode != 0`` / ``n_seg > 1`` are ValueErrors."""
         self.width = _lib.check_width(width)
         if self.width != DIM:
             if lazy:
@@ -77,9 +75,6 @@ class TrainEngine:
                 raise ValueError("multi-GPU training (dense_mode %r, n_seg %r) exists at embedding width 128 only "
                                  "(width %d)" % (dense_mode, n_seg, self.width))
             lazy = False
-        self.w_entry = (self.width != DIM) if w_entry is None else bool(w_entry)
-        if self.width != DIM and not self.w_entry:
-            raise ValueError("width %d needs the *_w entry points" % self.width)
         self.optimizer = schedule.resolve_optimizer(optimizer)
         self.loss = schedule.resolve_loss(loss)
         self.activation = schedule.resolve_activation(activation)
@@ -113,12 +108,9 @@ class TrainEngine:
         self.state_buf = _dev_bytes(_lib.STATE_DTYPE.itemsize, dev)
         self.packet_floats = int(self.lib.anirec_packet_floats(self.max_batch))
         self.packets = torch.zeros(self.n_seg * self.packet_floats, dtype=torch.float32, device=dev)
-        if self.w_entry:
-            ws = int(self.lib.anirec_train_workspace_bytes_w(self.max_batch, self.arena_steps, self.width))
-        else:
-            ws = int(self.lib.anirec_train_workspace_bytes(self.max_batch, self.arena_steps))
+        ws = int(self.lib.anirec_train_workspace_bytes_w(self.max_batch, self.arena_steps, self.width))
         if ws == 0:
-            raise _lib.AnirecError("anirec_train_workspace_bytes rejected the geometry")
+            raise _lib.AnirecError("anirec_train_workspace_bytes_w rejected the geometry")
         self.workspace = _dev_bytes(ws, dev)
         # anirec_metric_acc of the train steps and of the validation pass
         nacc = _lib.METRIC_ACC_DTYPE.itemsize
@@ -272,14 +264,11 @@ class TrainEngine:
         return C.c_void_p(self.stream.cuda_stream)
 
     def _stage(self, name, *args):
-        """One descriptor call: NAME(desc, args..., stream), or its twin NAME_w(desc, width, args..., stream)."""
-        if self.w_entry:
-            name += "_w"
-            args = (self.width,) + args
-        _lib.check(getattr(self.lib, name)(C.byref(self.desc), *args, self._sp()), name)
+        """One descriptor call: name(desc, width, args..., stream)."""
+        _lib.check(getattr(self.lib, name)(C.byref(self.desc), self.width, *args, self._sp()), name)
 
     def init_reg(self):
-        self._stage("anirec_train_init_reg")
+        self._stage("anirec_train_init_reg_w")
 
     # ---- epoch data ----------------------------------------------------------------
     def set_epoch(self, user_idx, anime_idx, rating, starts, counts, alphas, global_counts=None):
@@ -326,19 +315,19 @@ class TrainEngine:
 
     # ---- stages (unit-testable) -----------------------------------------------------
     def prep(self, first_step, n_steps):
-        self._stage("anirec_train_prep", first_step, n_steps)
+        self._stage("anirec_train_prep_w", first_step, n_steps)
 
     def fwd(self):
-        self._stage("anirec_train_fwd")
+        self._stage("anirec_train_fwd_w")
 
     def head(self):
-        self._stage("anirec_train_head")
+        self._stage("anirec_train_head_w")
 
     def bwd(self):
-        self._stage("anirec_train_bwd")
+        self._stage("anirec_train_bwd_w")
 
     def adam(self):
-        self._stage("anirec_train_adam")
+        self._stage("anirec_train_adam_w")
 
     def adam_users(self):
         _lib.check(self.lib.anirec_train_adam_part(C.byref(self.desc), 1, self._sp()), "anirec_train_adam_part")
@@ -406,11 +395,9 @@ class TrainEngine:
             n_steps = self.n_steps - first_step
         if self._trainer is None:
             h = C.c_void_p()
-            if self.w_entry:    # (the handle carries the width: run / set_metrics / destroy are the same calls)
-                _lib.check(self.lib.anirec_trainer_create_w(C.byref(self.desc), self.width, C.byref(h)),
-                           "anirec_trainer_create_w")
-            else:
-                _lib.check(self.lib.anirec_trainer_create(C.byref(self.desc), C.byref(h)), "anirec_trainer_create")
+            # (the handle carries the width: run / set_metrics / destroy take none)
+            _lib.check(self.lib.anirec_trainer_create_w(C.byref(self.desc), self.width, C.byref(h)),
+                       "anirec_trainer_create_w")
             self._trainer = h
             if self.metrics:
                 _lib.check(self.lib.anirec_trainer_set_metrics(h, self.metrics, _lib.ptr(self.metric_acc)),
@@ -435,17 +422,10 @@ class TrainEngine:
             torch.cuda.synchronize(self.device)
         # no rows (a rank's empty share of a split validation set): the sums stay 0 and nothing is launched — the
         # entry points refuse the empty tensors' null pointers before they look at the count
-        if u.numel() and self.w_entry:      # (mask 0 with a NULL accumulator is anirec_eval)
+        if u.numel():       # (mask 0 runs the plain k_eval path whatever the accumulator)
             _lib.check(self.lib.anirec_eval_metrics_w(C.byref(self.desc), self.width, self.metrics,
                                                       _lib.ptr(self.val_metric_acc), _lib.ptr(u), _lib.ptr(a),
                                                       _lib.ptr(t), int(u.numel()), self._sp()), "anirec_eval_metrics_w")
-        elif u.numel() and self.metrics:
-            _lib.check(self.lib.anirec_eval_metrics(C.byref(self.desc), self.metrics, _lib.ptr(self.val_metric_acc),
-                                                    _lib.ptr(u), _lib.ptr(a), _lib.ptr(t), int(u.numel()),
-                                                    self._sp()), "anirec_eval_metrics")
-        elif u.numel():
-            _lib.check(self.lib.anirec_eval(C.byref(self.desc), _lib.ptr(u), _lib.ptr(a), _lib.ptr(t),
-                                            int(u.numel()), self._sp()), "anirec_eval")
         rec = self.read_state()
         return {k: float(rec[k]) for k in ("val_bce_sum", "val_se_sum", "val_n", "reg_user_sumsq",
                                            "reg_anime_sumsq", "reg_sumsq")}

@@ -4,8 +4,8 @@ Names follow the reference: ``get_weights`` row-normalisation (similar_anime.py:
 cosine neighbours (similar_users.py:290-296), ``model.predict`` (model_recs.py:394).
 A head dict (w, b, gamma, beta, mov_mean, mov_var) may carry an "activation" (Keras name, ``schedule.ACTIVATIONS``);
 without one the head is the reference's sigmoid.
-The exact ops take the embedding width from the tables (``shape[1]``, one of ``_lib.WIDTHS``): 128 runs the entry
-points it always ran, another width their ``*_w`` twins.  The ``*_mfma`` ops exist at width 128 only.
+The exact ops take the embedding width from the tables (``shape[1]``, one of ``_lib.WIDTHS``) and call the ``*_w``
+entry points with it (the plain names of the C ABI are those calls at 128).  The ``*_mfma`` ops exist at width 128 only.
 """
 from __future__ import annotations
 
@@ -46,6 +46,15 @@ def _width(*tables):
     return _lib.check_width(w)
 
 
+def _watched(watched_bits, n_q, n_a, dev):
+    """The ``watched_bits`` argument as the library takes it: int32 [n_q, ceil(n_a / 32)] on ``dev``, or None."""
+    if watched_bits is None:
+        return None
+    wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
+    assert wb.shape == (n_q, (n_a + 31) // 32)
+    return wb
+
+
 def _need_128(tables, exact):
     """The matrix-core paths are specialised for 128-wide rows: say which exact op serves another width."""
     for t in tables:
@@ -61,10 +70,7 @@ def rownorm(W, device="cuda:0"):
     W = _f32(W, device)
     dim = _width(W)
     out = torch.empty_like(W)
-    if dim == DIM:
-        _lib.check(lib.anirec_rownorm(_lib.ptr(W), W.shape[0], _lib.ptr(out), _stream()), "anirec_rownorm")
-    else:
-        _lib.check(lib.anirec_rownorm_w(_lib.ptr(W), W.shape[0], dim, _lib.ptr(out), _stream()), "anirec_rownorm_w")
+    _lib.check(lib.anirec_rownorm_w(_lib.ptr(W), W.shape[0], dim, _lib.ptr(out), _stream()), "anirec_rownorm_w")
     return out
 
 
@@ -74,12 +80,8 @@ def cosine_scores(What, q):
     lib = _lib.load()
     dim = _width(What)
     out = torch.empty(What.shape[0], dtype=torch.float32, device=What.device)
-    if dim == DIM:
-        _lib.check(lib.anirec_cosine_scores(_lib.ptr(What), What.shape[0], int(q), _lib.ptr(out), _stream()),
-                   "anirec_cosine_scores")
-    else:
-        _lib.check(lib.anirec_cosine_scores_w(_lib.ptr(What), What.shape[0], dim, int(q), _lib.ptr(out), _stream()),
-                   "anirec_cosine_scores_w")
+    _lib.check(lib.anirec_cosine_scores_w(_lib.ptr(What), What.shape[0], dim, int(q), _lib.ptr(out), _stream()),
+               "anirec_cosine_scores_w")
     return out
 
 
@@ -87,8 +89,8 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
     """Top-k rows by descending cosine for each query row index, any k >= 1.
 
     Returns (idx int32 [nq,k], score fp32 [nq,k]); padded with -1 / NaN.
-    Ties -> ascending row index; NaN scores rank last.  k <= MAX_TOPK runs anirec_cosine_topk, a larger k
-    anirec_cosine_topk_large (same result for the first MAX_TOPK columns); `workspace` must suit the call taken.
+    Ties -> ascending row index; NaN scores rank last.  k <= MAX_TOPK runs anirec_cosine_topk_w, a larger k
+    anirec_cosine_topk_large_w (same result for the first MAX_TOPK columns); `workspace` must suit the call taken.
     """
     _need_gpu()
     lib = _lib.load()
@@ -117,16 +119,13 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
     if keep is not None:
         keep_t = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous()
         assert keep_t.numel() == n
-    if workspace is None:
+    if workspace is None:       # (the workspaces hold score rows only: the same sizes at every width)
         nb = lib.anirec_topk_large_workspace_bytes(n, nq, k) if large else lib.anirec_topk_workspace_bytes(n, nq)
         workspace = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-    name = "anirec_cosine_topk_large" if large else "anirec_cosine_topk"
-    tail = (_lib.ptr(q), nq, _lib.ptr(keep_t), int(bool(exclude_self)), k, _lib.ptr(out_i), _lib.ptr(out_s),
-            _lib.ptr(workspace), workspace.numel(), _stream())
-    if dim == DIM:
-        _lib.check(getattr(lib, name)(_lib.ptr(What), n, *tail), name)
-    else:       # (the workspaces hold score rows only: the same sizes at every width)
-        _lib.check(getattr(lib, name + "_w")(_lib.ptr(What), n, dim, *tail), name + "_w")
+    name = "anirec_cosine_topk_large_w" if large else "anirec_cosine_topk_w"
+    _lib.check(getattr(lib, name)(_lib.ptr(What), n, dim, _lib.ptr(q), nq, _lib.ptr(keep_t), int(bool(exclude_self)), k,
+                                  _lib.ptr(out_i), _lib.ptr(out_s), _lib.ptr(workspace), workspace.numel(), _stream()),
+               name)
     return out_i, out_s
 
 
@@ -354,14 +353,9 @@ def predict_pairs(U, A, head, user_idx, anime_idx):
     p = torch.empty(ui.numel(), dtype=torch.float32, device=dev)
     h = _head_struct(head)
     dim = _width(U, A)
-    if dim == DIM:
-        _lib.check(lib.anirec_predict_pairs_act(_lib.ptr(U), _lib.ptr(A), _lib.ptr(ui), _lib.ptr(ai),
-                                                int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
-                   "anirec_predict_pairs")
-    else:
-        _lib.check(lib.anirec_predict_pairs_w(_lib.ptr(U), _lib.ptr(A), dim, _lib.ptr(ui), _lib.ptr(ai),
-                                              int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
-                   "anirec_predict_pairs_w")
+    _lib.check(lib.anirec_predict_pairs_w(_lib.ptr(U), _lib.ptr(A), dim, _lib.ptr(ui), _lib.ptr(ai),
+                                          int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
+               "anirec_predict_pairs_w")
     return p
 
 
@@ -375,17 +369,10 @@ def predict_grid(U, A, head, users):
     out = torch.empty(n_q, n_a, dtype=torch.float32, device=dev)
     dim = _width(U, A)
     h = _head_struct(head)
-    if dim == DIM:
-        ws = torch.empty(int(lib.anirec_predict_workspace_bytes(n_a, max(n_q, 1), 0)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.anirec_predict_grid_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
-                                               _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
-                   "anirec_predict_grid")
-    else:
-        ws = torch.empty(int(lib.anirec_predict_workspace_bytes_w(n_a, max(n_q, 1), 0, dim)), dtype=torch.uint8,
-                         device=dev)
-        _lib.check(lib.anirec_predict_grid_w(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h),
-                                             _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
-                   "anirec_predict_grid_w")
+    ws = torch.empty(int(lib.anirec_predict_workspace_bytes_w(n_a, max(n_q, 1), 0, dim)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.anirec_predict_grid_w(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h),
+                                         _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
+               "anirec_predict_grid_w")
     return out
 
 
@@ -411,7 +398,7 @@ def predict_grid_mfma(U, A, head, users, out=None):
 
 def predict_topk(U, A, head, users, k, watched_bits=None):
     """Top-k unwatched anime by predicted rating per user, any k >= 1 (k > MAX_TOPK runs
-    anirec_predict_topk_large_act).  watched_bits: uint32/int32 [n_users, ceil(n_anime/32)] (bit set = watched)
+    anirec_predict_topk_large_w).  watched_bits: uint32/int32 [n_users, ceil(n_anime/32)] (bit set = watched)
     or None."""
     _need_gpu()
     lib = _lib.load()
@@ -426,28 +413,16 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
     out_p = torch.empty(n_q, k, dtype=torch.float32, device=dev)
     if n_q == 0:
         return out_i, out_p
-    wb = None
-    if watched_bits is not None:
-        wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
-        assert wb.shape == (n_q, (n_a + 31) // 32)
+    wb = _watched(watched_bits, n_q, n_a, dev)
     dim = _width(U, A)
     h = _head_struct(head)
-    if dim == DIM:
-        nb = (lib.anirec_predict_topk_large_workspace_bytes(n_a, n_q, k) if large
-              else lib.anirec_predict_workspace_bytes(n_a, n_q, 1))
-        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-        fn, name = ((lib.anirec_predict_topk_large_act, "anirec_predict_topk_large_act") if large
-                    else (lib.anirec_predict_topk_act, "anirec_predict_topk"))
-        _lib.check(fn(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head), _lib.ptr(wb), k,
-                      _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(), _stream()), name)
-    else:
-        nb = (lib.anirec_predict_topk_large_workspace_bytes_w(n_a, n_q, k, dim) if large
-              else lib.anirec_predict_workspace_bytes_w(n_a, n_q, 1, dim))
-        ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-        fn, name = ((lib.anirec_predict_topk_large_w, "anirec_predict_topk_large_w") if large
-                    else (lib.anirec_predict_topk_w, "anirec_predict_topk_w"))
-        _lib.check(fn(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head), _lib.ptr(wb),
-                      k, _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(), _stream()), name)
+    nb = (lib.anirec_predict_topk_large_workspace_bytes_w(n_a, n_q, k, dim) if large
+          else lib.anirec_predict_workspace_bytes_w(n_a, n_q, 1, dim))
+    ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
+    name = "anirec_predict_topk_large_w" if large else "anirec_predict_topk_w"
+    _lib.check(getattr(lib, name)(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head),
+                                  _lib.ptr(wb), k, _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(),
+                                  _stream()), name)
     return out_i, out_p
 
 
@@ -475,6 +450,18 @@ def seen_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
 RANK_BATCH = 1 << 22    # targets per anirec_predict_rank / anirec_score_rank call: far inside its 32-bit target offsets and grid
 
 
+def _rank_batches(n_t, dev, what, call):
+    """``call(t, cnt, err)`` (a status; ``t``: the slice of the batch's targets, ``err``: the device error flag) for the
+    targets RANK_BATCH at a time.  True if any batch raised its flag."""
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    bad = False
+    for t0 in range(0, n_t, RANK_BATCH):
+        cnt = min(RANK_BATCH, n_t - t0)
+        _lib.check(call(slice(t0, t0 + cnt), cnt, _lib.ptr(err)), what)
+        bad = bad or bool(int(err.item()))
+    return bad
+
+
 def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None):
     """Rank of each target anime among the anime its user has not watched, by predicted rating, without building
     the ranking: target t is (``target_row[t]``: a position in ``users``, ``target_anime[t]``: an anime index).
@@ -498,24 +485,16 @@ def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None)
         return rank, p
     if n_q == 0:
         raise ValueError("predict_rank: target_row out of range (no users)")
-    wb = None
-    if watched_bits is not None:
-        wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
-        assert wb.shape == (n_q, (n_a + 31) // 32)
+    wb = _watched(watched_bits, n_q, n_a, dev)
     h = _head_struct(head)
-    err = torch.empty(1, dtype=torch.int32, device=dev)
     ws = torch.empty(int(lib.anirec_predict_rank_workspace_bytes(n_a, n_q, min(n_t, RANK_BATCH), dim)), dtype=torch.uint8,
                      device=dev)
-    bad = False
-    for t0 in range(0, n_t, RANK_BATCH):
-        cnt = min(RANK_BATCH, n_t - t0)
-        _lib.check(lib.anirec_predict_rank(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h),
-                                           _head_act(head), _lib.ptr(wb), _lib.ptr(tr[t0:t0 + cnt]),
-                                           _lib.ptr(ta[t0:t0 + cnt]), cnt, _lib.ptr(rank[t0:t0 + cnt]),
-                                           _lib.ptr(p[t0:t0 + cnt]), _lib.ptr(err), _lib.ptr(ws), ws.numel(), _stream()),
-                   "anirec_predict_rank")
-        bad = bad or bool(int(err.item()))
-    if bad:
+
+    def batch(t, cnt, err):
+        return lib.anirec_predict_rank(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head),
+                                       _lib.ptr(wb), _lib.ptr(tr[t]), _lib.ptr(ta[t]), cnt, _lib.ptr(rank[t]),
+                                       _lib.ptr(p[t]), err, _lib.ptr(ws), ws.numel(), _stream())
+    if _rank_batches(n_t, dev, "anirec_predict_rank", batch):
         raise ValueError("predict_rank: target_row or target_anime out of range")
     return rank, p
 
@@ -542,21 +521,41 @@ def score_rank(score, n_users, target_row, target_anime, watched_bits=None):
         return rank
     if n_q == 0:
         raise ValueError("score_rank: target_row out of range (no users)")
-    wb = None
-    if watched_bits is not None:
-        wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
-        assert wb.shape == (n_q, (n_a + 31) // 32)
-    err = torch.empty(1, dtype=torch.int32, device=dev)
-    bad = False
-    for t0 in range(0, n_t, RANK_BATCH):
-        cnt = min(RANK_BATCH, n_t - t0)
-        _lib.check(lib.anirec_score_rank(_lib.ptr(sc), n_a, _lib.ptr(wb), n_q, _lib.ptr(tr[t0:t0 + cnt]),
-                                         _lib.ptr(ta[t0:t0 + cnt]), cnt, _lib.ptr(rank[t0:t0 + cnt]), _lib.ptr(err),
-                                         _stream()), "anirec_score_rank")
-        bad = bad or bool(int(err.item()))
-    if bad:
+    wb = _watched(watched_bits, n_q, n_a, dev)
+
+    def batch(t, cnt, err):
+        return lib.anirec_score_rank(_lib.ptr(sc), n_a, _lib.ptr(wb), n_q, _lib.ptr(tr[t]), _lib.ptr(ta[t]), cnt,
+                                     _lib.ptr(rank[t]), err, _stream())
+    if _rank_batches(n_t, dev, "anirec_score_rank", batch):
         raise ValueError("score_rank: target_row or target_anime out of range")
     return rank
+
+
+def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
+    """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
+    checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,
+    init, rows, out_loss): ``off`` the int64 offsets on the host, the other tensors on the table's device."""
+    loss_id = LOSSES[resolve_loss(loss)]
+    act_id = _head_act(head)
+    dim = _width(table)
+    dev = table.device
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("fold_in: steps must be >= 0")
+    off = torch.as_tensor(offsets).to(torch.int64).cpu()
+    ai, rt = _i32(idx, dev), _f32(rating, dev)
+    assert off.dim() == 1 and off.numel() >= 1 and ai.dim() == 1 and ai.shape == rt.shape
+    n_new = int(off.numel()) - 1
+    if int(off[0]) != 0 or int(off[-1]) != ai.numel() or (n_new and bool((off[1:] < off[:-1]).any())):
+        raise ValueError("fold_in: offsets must rise from 0 to the number of ratings")
+    init_t = _f32(init, dev)
+    if init_t.dim() == 1:
+        init_t = init_t.expand(n_new, -1)
+    init_t = init_t.contiguous()
+    assert init_t.shape == (n_new, dim), "init: [n_new, width] or one row"
+    rows = torch.empty(n_new, dim, dtype=torch.float32, device=dev)
+    out_loss = torch.empty(n_new, dtype=torch.float32, device=dev)
+    return loss_id, act_id, dim, steps, off, ai, rt, init_t, rows, out_loss
 
 
 def fold_in(A, head, offsets, anime_idx, rating, init, lr=0.01, steps=100, l2=1e-4, loss="binary_crossentropy"):
@@ -570,26 +569,8 @@ def fold_in(A, head, offsets, anime_idx, rating, init, lr=0.01, steps=100, l2=1e
     users of the call.  Raises ValueError on an anime index out of range or offsets that are not a CSR of the lists."""
     _need_gpu()
     lib = _lib.load()
-    loss_id = LOSSES[resolve_loss(loss)]
-    act_id = _head_act(head)
-    dim = _width(A)
-    dev = A.device
-    steps = int(steps)
-    if steps < 0:
-        raise ValueError("fold_in: steps must be >= 0")
-    off = torch.as_tensor(offsets).to(torch.int64).cpu()
-    ai, rt = _i32(anime_idx, dev), _f32(rating, dev)
-    assert off.dim() == 1 and off.numel() >= 1 and ai.dim() == 1 and ai.shape == rt.shape
-    n_new = int(off.numel()) - 1
-    if int(off[0]) != 0 or int(off[-1]) != ai.numel() or (n_new and bool((off[1:] < off[:-1]).any())):
-        raise ValueError("fold_in: offsets must rise from 0 to the number of ratings")
-    init_t = _f32(init, dev)
-    if init_t.dim() == 1:
-        init_t = init_t.expand(n_new, -1)
-    init_t = init_t.contiguous()
-    assert init_t.shape == (n_new, dim), "init: [n_new, width] or one row"
-    rows = torch.empty(n_new, dim, dtype=torch.float32, device=dev)
-    out_loss = torch.empty(n_new, dtype=torch.float32, device=dev)
+    loss_id, act_id, dim, steps, off, ai, rt, init_t, rows, out_loss = _fold_prepare(A, head, offsets, anime_idx, rating, init, steps, loss)
+    dev, n_new = A.device, rows.shape[0]
     if n_new == 0:
         return rows, out_loss
     alpha = torch.as_tensor(adam_alphas(lr, 1, steps), device=dev)
@@ -631,26 +612,8 @@ def fold_in_split(T, head, offsets, idx, rating, init, lr=0.01, steps=100, l2=1e
     the call, and a list of at most FOLD_CHUNK ratings gives the bits of ``fold_in``."""
     _need_gpu()
     lib = _lib.load()
-    loss_id = LOSSES[resolve_loss(loss)]
-    act_id = _head_act(head)
-    dim = _width(T)
-    dev = T.device
-    steps = int(steps)
-    if steps < 0:
-        raise ValueError("fold_in: steps must be >= 0")
-    off = torch.as_tensor(offsets).to(torch.int64).cpu()
-    ai, rt = _i32(idx, dev), _f32(rating, dev)
-    assert off.dim() == 1 and off.numel() >= 1 and ai.dim() == 1 and ai.shape == rt.shape
-    n_new = int(off.numel()) - 1
-    if int(off[0]) != 0 or int(off[-1]) != ai.numel() or (n_new and bool((off[1:] < off[:-1]).any())):
-        raise ValueError("fold_in: offsets must rise from 0 to the number of ratings")
-    init_t = _f32(init, dev)
-    if init_t.dim() == 1:
-        init_t = init_t.expand(n_new, -1)
-    init_t = init_t.contiguous()
-    assert init_t.shape == (n_new, dim), "init: [n_new, width] or one row"
-    rows = torch.empty(n_new, dim, dtype=torch.float32, device=dev)
-    out_loss = torch.empty(n_new, dtype=torch.float32, device=dev)
+    loss_id, act_id, dim, steps, off, ai, rt, init_t, rows, out_loss = _fold_prepare(T, head, offsets, idx, rating, init, steps, loss)
+    dev, n_new = T.device, rows.shape[0]
     if n_new == 0:
         return rows, out_loss
     c_off, c_row = fold_chunk_map(off.numpy())
@@ -688,10 +651,7 @@ def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fal
     out_p = torch.empty(n_q, k, dtype=torch.float32, device=dev)
     if n_q == 0:
         return out_i, out_p, 0
-    wb = None
-    if watched_bits is not None:
-        wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
-        assert wb.shape == (n_q, (n_a + 31) // 32)
+    wb = _watched(watched_bits, n_q, n_a, dev)
     h = _head_struct(head)
     act = _head_act(head)
     bq = min(n_q, int(batch))

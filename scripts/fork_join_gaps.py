@@ -9,7 +9,7 @@ ev = [(name(r), int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Strea
 gaps = {"bwd_end_to_forked_adam_start": [], "bwd_end_to_densify_start_same_stream": [],
         "forked_adam_end_to_joined_adam_start": []}
 for i, (n, s, e, q) in enumerate(ev):
-    if n == "k_bwd":
+    if n.split("<")[0] == "k_bwd":
         nxt = [x for x in ev[i + 1:i + 6]]
         ad = [x for x in nxt if x[0].startswith("k_adam")]
         dz = [x for x in nxt if x[0].startswith("k_densify")]

@@ -24,8 +24,8 @@ import numpy as np
 
 KINDS = ("adam", "sgd", "rmsprop", "adagrad")
 BYTES_PER_ELEM = {"adam": 24, "sgd": 8, "rmsprop": 16, "adagrad": 16}
-KERNEL = {"adam": "k_adam<true>", "sgd": "k_dense_opt<true, 1>", "rmsprop": "k_dense_opt<true, 2>",
-          "adagrad": "k_dense_opt<true, 3>"}
+KERNEL = {"adam": "k_adam<true, 0, 128>", "sgd": "k_adam<true, 1, 128>", "rmsprop": "k_adam<true, 2, 128>",
+          "adagrad": "k_adam<true, 3, 128>"}      # k_adam<kNT, kOpt (ANIREC_OPT_*), kD>
 HBM_BPS = 8e12
 N_USERS, N_ANIME, B = 350_000, 18_000, 10_000
 WARMUP, STEPS = 8, 32

@@ -2,9 +2,8 @@
 
     python scripts/time_width.py [--steps 200] [--rounds 4] [--out FILE]
 
-One process, five engines alive at once — D = 32, 64, 256 through the *_w entry points, 128 once through the old symbols
-("128") and once through the twins ("128_w") — every one on the dense Adam update (lazy=False: the lazy update exists at
-128 only, so like is compared with like).  The `--steps` timed steps of each engine are taken in `--rounds` slices,
+One process, four engines alive at once — D = 32, 64, 128 and 256 — every one on the dense Adam update (lazy=False: the
+lazy update exists at 128 only, so like is compared with like).  The `--steps` timed steps of each engine are taken in `--rounds` slices,
 the engines alternating slice by slice, so that a drift of the box (clocks, neighbours) falls on all of them alike.
 Reports ms/step (mean over the slices, and each slice) and the bytes a step moves by its shapes:
     gathers   fwd reads two rows per rating, bwd one row of the other table per contribution (2 per rating) and writes
@@ -22,7 +21,7 @@ import numpy as np
 
 N_USERS, N_ANIME, B = 350_000, 18_000, 10_000
 WARMUP = 8
-CASES = (("32", 32, None), ("64", 64, None), ("128", 128, False), ("128_w", 128, True), ("256", 256, None))
+CASES = (("32", 32), ("64", 64), ("128", 128), ("256", 256))
 
 
 def _arg(name, default):
@@ -45,10 +44,10 @@ def main():
     g = torch.Generator(device=dev)
     g.manual_seed(7)
     engines = {}
-    for name, dim, w_entry in CASES:
+    for name, dim in CASES:
         U = (torch.rand(N_USERS, dim, generator=g, device=dev) - 0.5) * 0.1
         A = (torch.rand(N_ANIME, dim, generator=g, device=dev) - 0.5) * 0.1
-        eng = TrainEngine(N_USERS, N_ANIME, max_batch=B, arena_steps=64, lazy=False, width=dim, w_entry=w_entry)
+        eng = TrainEngine(N_USERS, N_ANIME, max_batch=B, arena_steps=64, lazy=False, width=dim)
         eng.set_head(w=1.2)
         eng.set_weights(U, A)
         eng.set_epoch(ui, ai, t, np.arange(total) * B, np.full(total, B), bench.alphas_for(total))
@@ -66,7 +65,7 @@ def main():
             slices[name].append((time.perf_counter() - t0) / per * 1e3)
     out = {"shape": {"users": N_USERS, "anime": N_ANIME, "batch": B, "update": "dense adam", "steps": per * rounds,
                      "rounds": rounds}, "widths": {}}
-    for (name, dim, _), eng in zip(CASES, engines.values()):
+    for (name, dim), eng in zip(CASES, engines.values()):
         rec = eng.read_state()
         assert np.isfinite(rec["last_loss"]) and int(rec["step_fwd"]) == total
         ms = float(np.mean(slices[name]))

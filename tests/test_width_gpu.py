@@ -77,7 +77,7 @@ def test_forward_and_head_match_oracle(D):
     U, A, ui, ai, t = _problem(2, n_u, n_a, B, D)
     ui[-1], ai[-1] = n_u - 1, n_a - 1
     eng = _engine(U, A, B)
-    assert eng.width == D and eng.w_entry and not eng.lazy and tuple(eng.W.shape) == (n_u + n_a, D)
+    assert eng.width == D and not eng.lazy and tuple(eng.W.shape) == (n_u + n_a, D)
     eng.set_epoch(ui, ai, t, [0], [B], [orc.adam_alpha(1e-5, 1)])
     eng.fwd()
     head = orc.new_head(w=1.2)
@@ -221,14 +221,38 @@ def test_runs_are_bitwise_reproducible_and_graph_equals_eager(D):
 
 
 # ---- 5. _w(..., 128) is the old call -------------------------------------------------------------------------------
+class _PlainSymbols:
+    """An engine's library with every descriptor twin NAME_w(desc, 128, ...) answered by the plain NAME(desc, ...).
+    It relies on how TrainEngine calls its library: through ``eng.lib``, with (desc, width) as the first two arguments
+    of every ``*_w`` call it makes after the constructor."""
+
+    def __init__(self, lib):
+        self._lib, self.called = lib, set()
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.endswith("_w"):
+            return fn
+        plain = getattr(self._lib, name[:-2])
+
+        def call(desc, width, *args):
+            assert width == 128
+            self.called.add(name[:-2])
+            return plain(desc, *args)
+        return call
+
+
 def test_twins_at_128_are_the_old_symbols_bit_for_bit():
     from anime_recommendations_amd import _lib, ops
+    lib = _lib.load()
     U, A, ui, ai, t = _problem(6, 900, 250, 3 * 400 - 77, 128, 1.2)
     B, lr = 400, 4e-5
+    assert lib.anirec_train_workspace_bytes(B, 8) == lib.anirec_train_workspace_bytes_w(B, 8, 128)
     outs = []
-    for w_entry in (False, True):
-        eng = _engine(U, A, B, lazy=False, w_entry=w_entry, metrics=1)
-        assert eng.w_entry == w_entry
+    for plain in (True, False):
+        eng = _engine(U, A, B, lazy=False, metrics=1)       # (the engine calls the twins)
+        if plain:       # the same run on eng.desc through anirec_train_init_reg, anirec_trainer_create / _set_metrics /
+            eng.lib = _PlainSymbols(lib)                    # _run / _destroy and anirec_eval_metrics
         _epoch(eng, ui, ai, t, B, lr)
         eng.reset_metrics()
         eng.run(3, use_graph=False)
@@ -236,27 +260,76 @@ def test_twins_at_128_are_the_old_symbols_bit_for_bit():
         o["val"] = eng.eval_logs(ui[:300], ai[:300], t[:300])
         outs.append(o)
         eng.close()
+        if plain:
+            assert eng.lib.called == {"anirec_train_init_reg", "anirec_trainer_create", "anirec_eval_metrics"}
+    assert not np.array_equal(outs[0]["W"][:900], U) and outs[0]["rec"]["step_fwd"] == 3
     for k in ("W", "M", "V"):
         assert np.array_equal(_bits(outs[0][k]), _bits(outs[1][k])), k
     assert outs[0]["rec"].tobytes() == outs[1]["rec"].tobytes()
     assert outs[0]["val"] == outs[1]["val"]
-    # serving: a top-k list and a rating grid through both symbols
-    lib = _lib.load()
-    n, k = 1000, 10
-    Wh = ops.rownorm(torch.from_numpy(np.random.default_rng(7).normal(0, 0.05, (n, 128)).astype(f32)))
-    q = torch.tensor([3, 0, n - 1, 500], dtype=torch.int32, device="cuda")
-    i0, s0 = ops.cosine_topk(Wh, q, k)
-    i1 = torch.full_like(i0, -7)
-    s1 = torch.full_like(s0, -7.0)
-    ws = torch.empty(int(lib.anirec_topk_workspace_bytes(n, 4)), dtype=torch.uint8, device="cuda")
+
+    # serving: ops.* is the _w spelling; every op that had a branch against its plain symbol
+    n, dev = 1000, "cuda"
+    rng = np.random.default_rng(7)
+    W = torch.from_numpy(rng.normal(0, 0.05, (n, 128)).astype(f32)).to(dev)
+    Uq = torch.from_numpy(rng.normal(0, 0.05, (n, 128)).astype(f32)).to(dev)
+    q = torch.tensor([3, 0, n - 1, 500], dtype=torch.int32, device=dev)
+    wb = torch.from_numpy((rng.integers(0, 1 << 32, (4, (n + 31) // 32), dtype=np.uint64)
+                           & rng.integers(0, 1 << 32, (4, (n + 31) // 32), dtype=np.uint64)).astype(np.uint32)
+                          .view(np.int32)).to(dev)         # about a quarter of the anime watched
+    head = dict(w=1.3, b=0.1, gamma=0.9, beta=-0.2, mov_mean=0.05, mov_var=0.4)
+    h, act = ops._head_struct(head), ops._head_act(head)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    assert lib.anirec_cosine_topk_w(_lib.ptr(Wh), n, 128, _lib.ptr(q), 4, None, 1, k, _lib.ptr(i1), _lib.ptr(s1),
-                                    _lib.ptr(ws), ws.numel(), st) == 0
-    Wn = torch.empty_like(Wh)
-    assert lib.anirec_rownorm_w(_lib.ptr(Wh), n, 128, _lib.ptr(Wn), st) == 0
-    torch.cuda.synchronize()
-    assert torch.equal(i0, i1) and np.array_equal(_bits(s0.cpu().numpy()), _bits(s1.cpu().numpy()))
-    assert np.array_equal(_bits(Wn.cpu().numpy()), _bits(ops.rownorm(Wh).cpu().numpy()))
+    P = _lib.ptr
+
+    def same(got, want):
+        torch.cuda.synchronize()
+        assert got.dtype == want.dtype and got.shape == want.shape
+        assert np.array_equal(_bits(got.cpu().numpy()), _bits(want.cpu().numpy()))
+
+    def sentinel(like):
+        return torch.full_like(like, -7)
+
+    def bytes_(nb):
+        return torch.empty(int(nb), dtype=torch.uint8, device=dev)
+
+    Wh = ops.rownorm(W)
+    out = sentinel(Wh)
+    assert lib.anirec_rownorm(P(W), n, P(out), st) == 0
+    same(out, Wh)
+    sc = ops.cosine_scores(Wh, 500)
+    out = sentinel(sc)
+    assert lib.anirec_cosine_scores(P(Wh), n, 500, P(out), st) == 0
+    same(out, sc)
+    for k in (10, 130):                                     # both sides of ANIREC_MAX_TOPK
+        large = k > _lib.MAX_TOPK
+        i0, s0 = ops.cosine_topk(Wh, q, k)
+        i1, s1 = sentinel(i0), sentinel(s0)
+        ws = bytes_(lib.anirec_topk_large_workspace_bytes(n, 4, k) if large else lib.anirec_topk_workspace_bytes(n, 4))
+        fn = lib.anirec_cosine_topk_large if large else lib.anirec_cosine_topk
+        assert fn(P(Wh), n, P(q), 4, None, 1, k, P(i1), P(s1), P(ws), ws.numel(), st) == 0
+        same(i1, i0)
+        same(s1, s0)
+        i0, p0 = ops.predict_topk(Uq, W, head, q, k, wb)
+        i1, p1 = sentinel(i0), sentinel(p0)
+        ws = bytes_(lib.anirec_predict_topk_large_workspace_bytes(n, 4, k) if large
+                    else lib.anirec_predict_workspace_bytes(n, 4, 1))
+        fn = lib.anirec_predict_topk_large_act if large else lib.anirec_predict_topk_act
+        assert fn(P(Uq), P(W), n, P(q), 4, C.byref(h), act, P(wb), k, P(i1), P(p1), P(ws), ws.numel(), st) == 0
+        same(i1, i0)
+        same(p1, p0)
+        assert int(i0.min()) >= 0                           # (full lists: nothing compared is padding alone)
+    pu = torch.from_numpy(rng.integers(0, n, 37).astype(np.int32)).to(dev)
+    pa = torch.from_numpy(rng.integers(0, n, 37).astype(np.int32)).to(dev)
+    p0 = ops.predict_pairs(Uq, W, head, pu, pa)
+    p1 = sentinel(p0)
+    assert lib.anirec_predict_pairs_act(P(Uq), P(W), P(pu), P(pa), 37, C.byref(h), act, P(p1), st) == 0
+    same(p1, p0)
+    g0 = ops.predict_grid(Uq, W, head, q)
+    g1 = sentinel(g0)
+    ws = bytes_(lib.anirec_predict_workspace_bytes(n, 4, 0))
+    assert lib.anirec_predict_grid_act(P(Uq), P(W), n, P(q), 4, C.byref(h), act, P(g1), P(ws), ws.numel(), st) == 0
+    same(g1, g0)
 
 
 # ---- 6. evaluate and eval_logs -------------------------------------------------------------------------------------
