@@ -24,6 +24,7 @@ ABI_VERSION = 5
 TOPK_MAX_BATCHES = 64
 RCCL_ID_BYTES = 128
 LAZY_WINDOW = 8
+MMR_IMAGE_FLOATS = 32768    # anirec_mmr_max_cand(dim) = MMR_IMAGE_FLOATS // dim: the candidates' rows of a list in LDS
 # anirec_train_desc.optimizer (ANIREC_OPT_*)
 OPT_ADAM, OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
 # anirec_train_desc.loss (ANIREC_LOSS_*) and .activation / the predict calls' activation (ANIREC_ACT_*)
@@ -219,6 +220,9 @@ PROTOTYPES = {
     "anirec_fold_in_split_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "anirec_fold_in_split": (C.c_int, [_vp, _i32, _i32, C.POINTER(Head), _i32, _i32, _f32, _vp, _vp, _vp, _i32, _vp, _vp,
                                        _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # greedy MMR re-rank of candidate lists (diversified recommendations)
+    "anirec_mmr_max_cand": (_sz, [_i32]),
+    "anirec_mmr_rerank": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -233,6 +237,12 @@ def check_width(width) -> int:
         raise ValueError("embedding_size %r is not supported: the libanirec kernels take the widths %s"
                          % (width, ", ".join(str(x) for x in WIDTHS)))
     return w
+
+
+def mmr_max_cand(width) -> int:
+    """anirec_mmr_max_cand: the longest candidate list anirec_mmr_rerank takes at a (checked) row width."""
+    return MMR_IMAGE_FLOATS // check_width(width)
+
 
 _lib = None
 

@@ -351,6 +351,53 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
 
 
 # ----------------------------------------------------------------------------------------
+# diverse_recs: model_recs with a greedy MMR re-rank of the best `pool` candidates
+# ----------------------------------------------------------------------------------------
+def _list_cosines(Wh, idx):
+    """The cosine matrix (float64, host) of the listed rows ``idx`` (-1 padding dropped) of the normalised table ``Wh``."""
+    rows = Wh[np.asarray(idx[idx >= 0], np.int64)].cpu().numpy().astype(np.float64)
+    return rows @ rows.T
+
+
+def _mean_pairwise(S):
+    """Mean of the cosines of the distinct pairs of a list (NaN for a list of fewer than two)."""
+    n = len(S)
+    return float(S[np.triu_indices(n, 1)].mean()) if n >= 2 else float("nan")
+
+
+def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
+                       types=None, genres=None, pool=100, diversity=0.3):
+    """model_recs_frame with the list diversified (``recs.diverse_topk``): the same candidates (unwatched, indexed,
+    Type / Genre filters), the ``pool`` best by predicted rating re-ranked greedily with ``lam = 1 - diversity``.
+    Returns (frame, stats): model_recs_frame's columns plus ``Max_similarity`` — the largest cosine of the row's anime
+    to the rows above it, 0 for the first: the re-rank's own penalty (at diversity 0, where nothing is re-ranked and the
+    rows are model_recs_frame's, the same quantity from the host's cosines) — and stats = {"mean_similarity": the mean
+    pairwise cosine of the listed anime, "mean_similarity_topk": that of the plain top-k}."""
+    import torch
+    from . import ops, recs
+    pos = np.nonzero(np.asarray(user_ids) == int(user_id))[0]
+    if len(pos) == 0:
+        raise ValueError("user id %r has no embedding row" % (user_id,))
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    keep = unwatched_mask(df, anime_ids, user_id) & filter_mask(meta, anime_df, types, genres)
+    bits = _blocked_bits(~keep).view(np.int32)
+    tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
+    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
+    idx, p, pen = recs.diverse_topk(tU, tA, head, [int(pos[0])], k, pool, diversity, bits)
+    idx, p = idx.cpu().numpy()[0], p.cpu().numpy()[0]
+    Wh = ops.rownorm(tA, device=tA.device)
+    S = _list_cosines(Wh, idx)
+    if pen is None:
+        plain, pen = S, np.array([S[i, :i].max() if i else 0.0 for i in range(len(S))], np.float32)
+    else:
+        plain = _list_cosines(Wh, ops.predict_topk(tU, tA, head, [int(pos[0])], k, bits)[0].cpu().numpy()[0])
+        pen = pen.cpu().numpy()[0][idx >= 0]
+    frame = _model_recs_rows(meta, idx, p)
+    frame["Max_similarity"] = pen
+    return frame, {"mean_similarity": _mean_pairwise(S), "mean_similarity_topk": _mean_pairwise(plain)}
+
+
+# ----------------------------------------------------------------------------------------
 # new_user_recs: users the model was not trained on
 # ----------------------------------------------------------------------------------------
 def _folded_position(folded, user_id):

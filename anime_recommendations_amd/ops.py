@@ -531,6 +531,53 @@ def score_rank(score, n_users, target_row, target_anime, watched_bits=None):
     return rank
 
 
+def check_mmr(width, n_cand, k, lam):
+    """The argument checks of ``mmr_rerank`` (no device needed): ValueError naming the limit for a candidate list longer
+    than anirec_mmr_max_cand(width), k outside 1 .. n_cand, or ``lam`` outside [0, 1].  Returns (width, n_cand, k, lam)."""
+    dim, n_cand, k, lam = _lib.check_width(width), int(n_cand), int(k), float(lam)
+    if n_cand > _lib.mmr_max_cand(dim):
+        raise ValueError("mmr_rerank: %d candidates per list, at most %d at width %d (the candidates' rows are held in "
+                         "LDS: %d floats)" % (n_cand, _lib.mmr_max_cand(dim), dim, _lib.MMR_IMAGE_FLOATS))
+    if not 1 <= k <= n_cand:
+        raise ValueError("mmr_rerank: k = %d must be in 1 .. %d (the candidates per list)" % (k, n_cand))
+    if not 0.0 <= lam <= 1.0:       # (a NaN fails both comparisons)
+        raise ValueError("mmr_rerank: lam = %r must be in [0, 1]" % (lam,))
+    return dim, n_cand, k, lam
+
+
+def mmr_rerank(What, cand_idx, cand_score, k, lam):
+    """Greedy MMR re-rank of candidate lists (anirec_mmr_rerank): list l holds the rows ``cand_idx[l]`` of ``What``
+    (``rownorm`` output; -1 = an empty slot) with relevance ``cand_score[l]``; each of the ``k`` picks is the unpicked
+    candidate with the largest ``lam * score - (1 - lam) * pen``, pen = its largest cosine to a row already picked
+    (0 before the first pick); ties go to the lowest position.  ``lam`` = 1 keeps the score order.  The width comes
+    from ``What.shape[1]``.  Returns (idx int32, pos int32, score fp32, pen fp32), each [n_lists, k] on the device:
+    the row, its position in the list, its score and its pen when it was picked; -1 / -1 / NaN / NaN once a list has
+    no candidate left.  Raises ValueError for a list longer than anirec_mmr_max_cand(width), k outside 1 .. n_cand,
+    ``lam`` outside [0, 1], or a candidate index that is no row of ``What``."""
+    if cand_idx.dim() != 2 or tuple(cand_idx.shape) != tuple(cand_score.shape):
+        raise ValueError("mmr_rerank: cand_idx and cand_score must both be [n_lists, n_cand]")
+    dim, n_cand, k, lam = check_mmr(What.shape[1], cand_idx.shape[1], k, lam)
+    _need_gpu()
+    lib = _lib.load()
+    assert _width(What) == dim
+    dev = What.device
+    ci, cs = _i32(cand_idx, dev), _f32(cand_score, dev)
+    n_lists = int(ci.shape[0])
+    idx = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
+    pos = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
+    score = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    pen = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    if n_lists == 0:
+        return idx, pos, score, pen
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.anirec_mmr_rerank(_lib.ptr(What), dim, What.shape[0], _lib.ptr(ci), _lib.ptr(cs), n_lists, n_cand, k,
+                                     lam, _lib.ptr(idx), _lib.ptr(pos), _lib.ptr(score), _lib.ptr(pen), _lib.ptr(err),
+                                     _stream()), "anirec_mmr_rerank")
+    if int(err.item()):
+        raise ValueError("mmr_rerank: candidate index out of range")
+    return idx, pos, score, pen
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

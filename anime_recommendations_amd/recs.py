@@ -206,6 +206,34 @@ def popularity_scores(anime_idx, n_anime, n_users=None):
     return counts.to(torch.float32)
 
 
+def diverse_topk(U, A, head, users, k, pool, diversity, watched_bits=None):
+    """Diversified top-k per user: the ``pool`` best unwatched anime by predicted rating
+    (``ops.predict_topk``), re-ranked greedily by ``ops.mmr_rerank`` on the normalised anime rows with
+    ``lam = 1 - diversity`` — each pick trades a candidate's rating against its largest cosine to an anime already
+    picked.  Batched over ``users`` (rows of ``U``, which may be folded rows); ``watched_bits`` as predict_topk.
+    ``pool`` is clamped to the number of anime.  ``diversity`` == 0 is ``ops.predict_topk(..., k)`` itself: no pool,
+    no re-rank, the bits of model_recs.
+    Returns (idx int32 [n_users, k], p fp32 [n_users, k], pen fp32 [n_users, k] or None at diversity 0): the anime, their
+    predicted ratings and each pick's largest cosine to the picks before it (0 for the first); -1 / NaN / NaN padded.
+    Raises ValueError for ``diversity`` outside [0, 1], k < 1, pool < k, and, at diversity > 0, for k above the number of
+    anime or a pool above anirec_mmr_max_cand(width)."""
+    from . import ops
+    k, pool, diversity = int(k), int(pool), float(diversity)
+    if not 0.0 <= diversity <= 1.0:
+        raise ValueError("diverse_topk: diversity = %r must be in [0, 1]" % (diversity,))
+    if k < 1:
+        raise ValueError("diverse_topk: k must be >= 1")
+    if pool < k:
+        raise ValueError("diverse_topk: pool = %d is smaller than k = %d" % (pool, k))
+    if diversity == 0.0:
+        return ops.predict_topk(U, A, head, users, k, watched_bits) + (None,)
+    pool = min(pool, int(A.shape[0]))
+    ops.check_mmr(A.shape[1], pool, k, 1.0 - diversity)     # (k <= pool <= the kernel's list limit, before any GPU work)
+    cand, p = ops.predict_topk(U, A, head, users, pool, watched_bits)
+    idx, _, score, pen = ops.mmr_rerank(ops.rownorm(A, device=A.device), cand, p, k, 1.0 - diversity)
+    return idx, score, pen
+
+
 FOLD_STEPS = 100        # Adam iterations of a fold-in (DESIGN.md §4.7)
 FOLD_LR = 0.01          # and their learning rate
 

@@ -713,6 +713,44 @@ int anirec_fold_in_split(const float *T, int32_t dim, int32_t n_table, const ani
                          const float *init, const float *alpha, int32_t steps, float *out_rows, float *out_loss,
                          int32_t *err_flag, void *workspace, size_t workspace_bytes, void *stream);
 
+/* DIVERSIFIED LISTS — greedy maximal-marginal-relevance (MMR) re-rank.  model_recs.py:373-456 cuts a user's list by
+ * predicted rating alone, and the rating sees an anime only through the cosine of its row with the user's: rows that
+ * nearly coincide (the seasons, specials and movies of one franchise) enter a top-k together.  Here a list of n_cand
+ * candidates (anirec_predict_topk*'s output for k = the pool) becomes a list of k picks, each pick trading a
+ * candidate's score against its similarity to what is already picked.
+ * What [n_rows][dim] = the unit rows anirec_rownorm_w writes; list l holds the candidates cand_idx[l][0 .. n_cand)
+ * (rows of What; -1 = an empty slot) with relevance cand_score[l][.].  All arithmetic is fp32, nothing is contracted
+ * into an fma, oml = 1.0f - lambda.
+ *     absent   a candidate whose index is -1, whose score is NaN, or whose What row holds a non-finite value (a zero
+ *              row normalises to NaN); every other candidate is present.  An index that appears twice is two candidates.
+ *     sim(i,j) the k-ordered chain s = fmaf(What[a_i][t], What[a_j][t], s), t = 0 .. dim-1, from s = 0: the chain of
+ *              anirec_cosine_scores_w, the same bits
+ *     pen_i    0 while nothing is picked; after the first pick sim(i, first), then the larger of pen_i and sim(i, j)
+ *              for each later pick j (it may be negative; a NaN sim, which unit rows cannot give, replaces nothing)
+ *     val_i    (lambda * score_i) - (oml * pen_i): each product rounded, then the difference
+ *     pick s   = 0 .. k-1: among the present, unpicked candidates the one with the largest val; ties (-0 == +0) go to
+ *              the lowest position in the list; +-inf scores are ordinary numbers; a NaN val (inf - inf, 0 * inf)
+ *              sorts after every number.  The pick at position pos writes
+ *                  out_idx[l][s] = cand_idx[l][pos], out_pos[l][s] = pos, out_score[l][s] = cand_score[l][pos],
+ *                  out_pen[l][s] = pen_pos at that moment (0 for the first pick)
+ * With fewer than k present candidates the rest of the row is -1 / -1 / NaN / NaN.  lambda == 1 returns the first k
+ * present candidates in (score descending, position ascending) order.
+ * One workgroup per list, every pick inside one launch, the candidates' rows staged once in LDS (dim * n_cand <=
+ * 32768 floats: anirec_mmr_max_cand(dim) = 32768 / dim = 1024, 512, 256, 128 candidates; 0 for a bad dim); a pick
+ * costs n_cand chains against the picked row, the n_cand x n_cand matrix is never formed.  No workspace, no atomics,
+ * stream-ordered and graph-capturable.  A list's outputs depend on that list alone: not on the other lists, on its
+ * position in the call, or on the run.
+ * Bad dim, n_rows < 1, a negative count, k < 1 or k > n_cand, n_cand > anirec_mmr_max_cand(dim), lambda outside [0, 1]
+ * or NaN, a NULL pointer with n_lists > 0: ANIREC_EINVAL before anything is enqueued or written.  n_lists == 0:
+ * ANIREC_OK, nothing enqueued.  Otherwise every element of the four outputs and *err_flag (device) is written:
+ * *err_flag becomes 1 on a candidate index below -1 or at or above n_rows (0 without one): that list's whole output
+ * is -1 / -1 / NaN / NaN, nothing is read through the bad index, the other lists are unaffected (anirec_predict_rank's
+ * convention). */
+size_t anirec_mmr_max_cand(int32_t dim);
+int anirec_mmr_rerank(const float *What, int32_t dim, int32_t n_rows, const int32_t *cand_idx, const float *cand_score,
+                      int32_t n_lists, int32_t n_cand, int32_t k, float lambda, int32_t *out_idx, int32_t *out_pos,
+                      float *out_score, float *out_pen, int32_t *err_flag, void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
