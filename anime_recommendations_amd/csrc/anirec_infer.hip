@@ -243,87 +243,78 @@ __device__ __forceinline__ uint32_t cand_key(const SelectArgs &a, const float *r
 
 constexpr int kSelThreads = 256;
 
-__global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a) {
-  __shared__ uint32_t hist[256];
-  __shared__ uint32_t sh_prefix, sh_want;
-  __shared__ uint32_t wsum[kSelThreads / 64];
-  __shared__ unsigned long long win[ANIREC_MAX_TOPK];  // (key << 32) | ~idx  -> sort desc
+// ---- the select body, once: k_select collects into its LDS window, the any-k kernels (k_lk_*, further down) into
+// global rows.  The tie rule, the short-row rule and the eq_use accounting live here and nowhere else. ----
+
+// The digit of one radix pass from a 256-bin histogram in LDS: the digit d (from 255 down) where the running count
+// first reaches `want`, by a wave scan instead of a 256-step serial walk by one thread (that walk was ~8 us per pass:
+// most of a small select).  out[0], out[1] = the new prefix and want, or 0xFFFFFFFF and 0 when fewer than `want` keys
+// match (pass 0 only: fewer than k candidates); out[2] = the keys matching the prefix.  Ends with a barrier.
+__device__ void sel_digit(const uint32_t *hist, uint32_t prefix, uint32_t want, int shift, uint32_t *out) {
   const int tid = threadIdx.x;
-  // Few queries (the reference's literal call is ONE query against every row): a query's keys are cut
-  // into slices, one workgroup each, and a second launch of this kernel merges the slice winners.  The
-  // winners of a slice are sorted (score desc, index asc) and slices cover ascending index ranges, so
-  // list order among equal scores is ascending index — the tie rule survives the merge unchanged.
-  const int q = blockIdx.x / a.slices;
-  const int j_lo = (blockIdx.x % a.slices) * a.slice_len;
-  const int j_hi = min(a.n, j_lo + a.slice_len);
-  const size_t orow = blockIdx.x;
-  const float *row = a.scores + (size_t)q * a.ld;
-  const int self = a.self ? a.self[q] : -1;
-  const int k = a.k;
-
-  // MSB-first radix select for the k-th largest key among candidates (key != 0)
-  uint32_t prefix = 0, pmask = 0;
-  uint32_t want = (uint32_t)k;  // rank (1-based from the top) still to locate inside prefix
-  bool short_row = false;
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    hist[tid] = 0;
-    __syncthreads();
-    for (int j = j_lo + tid; j < j_hi; j += kSelThreads) {
-      const uint32_t key = cand_key(a, row, q, j, self);
-      if (key != 0u && (key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {
-      // digit d (from 255 down) where the running count first reaches `want`: wave scan instead of a
-      // 256-step serial walk by one thread (that walk was ~8 us per pass: most of a small select)
-      uint32_t h4[4], run = 0;
+  if (tid < 64) {
+    uint32_t h4[4], run = 0;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {  // lane l covers digits 255-4l .. 252-4l, in that order
-        h4[j] = hist[255 - (4 * tid + j)];
-        run += h4[j];
-      }
-      uint32_t inc = run;
+    for (int j = 0; j < 4; ++j) {  // lane l covers digits 255-4l .. 252-4l, in that order
+      h4[j] = hist[255 - (4 * tid + j)];
+      run += h4[j];
+    }
+    uint32_t inc = run;
 #pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(inc, o, 64);
-        if (tid >= o) inc += y;
-      }
-      const uint32_t before = inc - run;  // candidates in digits above this lane's four
-      const unsigned long long reach = __ballot(inc >= want);
-      if (reach == 0ull) {
-        if (tid == 0) {  // fewer than k candidates in total: take them all
-          sh_prefix = 0xFFFFFFFFu;
-          sh_want = 0;
-        }
-      } else if (tid == __ffsll((long long)reach) - 1) {
-        uint32_t cum = before;
-        int j = 0;
-        for (; j < 3; ++j) {
-          if (cum + h4[j] >= want) break;
-          cum += h4[j];
-        }
-        sh_prefix = prefix | ((uint32_t)(255 - (4 * tid + j)) << shift);
-        sh_want = want - cum;
-      }
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(inc, o, 64);
+      if (tid >= o) inc += y;
     }
-    __syncthreads();
-    if (sh_prefix == 0xFFFFFFFFu && sh_want == 0) {
-      short_row = true;
-      break;
+    const uint32_t before = inc - run;  // candidates in digits above this lane's four
+    const unsigned long long reach = __ballot(inc >= want);
+    if (tid == 63) out[2] = inc;
+    if (reach == 0ull) {
+      if (tid == 0) {  // fewer than k candidates in total: take them all
+        out[0] = 0xFFFFFFFFu;
+        out[1] = 0;
+      }
+    } else if (tid == __ffsll((long long)reach) - 1) {
+      uint32_t cum = before;
+      int j = 0;
+      for (; j < 3; ++j) {
+        if (cum + h4[j] >= want) break;
+        cum += h4[j];
+      }
+      out[0] = prefix | ((uint32_t)(255 - (4 * tid + j)) << shift);
+      out[1] = want - cum;
     }
-    prefix = sh_prefix;
-    want = sh_want;
-    pmask |= 255u << shift;
-    __syncthreads();
   }
-  // threshold T = prefix (exact key of the k-th largest); take all keys > T and the first
-  // `want` keys == T in ascending index order.  short_row: take every candidate.
-  const uint32_t T = short_row ? 0u : prefix;
-  const uint32_t need_eq = short_row ? 0xFFFFFFFFu : want;
+  __syncthreads();
+}
 
-  uint32_t n_out = 0;   // winners written so far (block-uniform)
-  uint32_t eq_taken = 0;
+// hist[d] = candidates of [j_lo, j_hi) whose key matches `prefix` under `pmask` and has digit d at `shift`
+__device__ void sel_hist(const SelectArgs &a, const float *row, int q, int self, int j_lo, int j_hi, uint32_t prefix,
+                         uint32_t pmask, int shift, uint32_t *hist) {
+  const int tid = threadIdx.x;
+  hist[tid] = 0;
+  __syncthreads();
+  for (int j = j_lo + tid; j < j_hi; j += kSelThreads) {
+    const uint32_t key = cand_key(a, row, q, j, self);
+    if (key != 0u && (key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t sel_pmask(int pass) { return pass == 0 ? 0u : 0xFFFFFFFFu << (32 - 8 * pass); }
+
+// state (prefix, want, m, short) after pass p from the one after pass p - 1 and the digit scan of pass p
+__device__ uint4 sel_advance(uint4 prev, const uint32_t *sh) {
+  if (sh[0] == 0xFFFFFFFFu && sh[1] == 0) return make_uint4(0u, 0xFFFFFFFFu, sh[2], 1u);
+  return make_uint4(sh[0], sh[1], prev.z, 0u);
+}
+
+// Ordered collection of the winners of [j_lo, j_hi) into w[0..cap): every key > T and the first `need_eq` keys == T in
+// ascending index order; short_row: every candidate.  n_out / eq_taken: winners / keys == T already taken by the
+// slices before this one.  w is k_select's LDS window or a global row.
+__device__ void sel_collect(const SelectArgs &a, const float *row, int q, int self, int j_lo, int j_hi, uint32_t T,
+                            uint32_t need_eq, bool short_row, uint32_t n_out, uint32_t eq_taken,
+                            unsigned long long *w, uint32_t cap, uint32_t *wsum) {
+  const int tid = threadIdx.x;
   constexpr int kPer = 16;
   const int super = kSelThreads * kPer;
   for (int base = j_lo; base < j_hi; base += super) {
@@ -340,23 +331,22 @@ __global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a) {
       }
     }
     if (__syncthreads_count((c_gt | c_eq) != 0) == 0) continue;
-    // ordered ranks of this thread's matches (two scans packed in one: gt in low 16 bits...
-    // counts can reach 4096 per super-chunk -> use two separate scans)
+    // ordered ranks of this thread's matches: counts can reach 4096 per super-chunk -> two separate scans
     uint32_t tot_gt = 0, tot_eq = 0;
     uint32_t o_gt, o_eq;
     {
-      const int lane = tid & 63, w = tid >> 6;
+      const int lane = tid & 63, wv = tid >> 6;
       uint32_t inc = c_gt;
 #pragma unroll
       for (int o = 1; o < 64; o <<= 1) {
         uint32_t t = __shfl_up(inc, o, 64);
         if (lane >= o) inc += t;
       }
-      if (lane == 63) wsum[w] = inc;
+      if (lane == 63) wsum[wv] = inc;
       __syncthreads();
       uint32_t b = 0;
       for (int kk = 0; kk < kSelThreads / 64; ++kk) {
-        if (kk < w) b += wsum[kk];
+        if (kk < wv) b += wsum[kk];
         tot_gt += wsum[kk];
       }
       o_gt = b + inc - c_gt;
@@ -367,11 +357,11 @@ __global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a) {
         uint32_t t = __shfl_up(inc, o, 64);
         if (lane >= o) inc += t;
       }
-      if (lane == 63) wsum[w] = inc;
+      if (lane == 63) wsum[wv] = inc;
       __syncthreads();
       b = 0;
       for (int kk = 0; kk < kSelThreads / 64; ++kk) {
-        if (kk < w) b += wsum[kk];
+        if (kk < wv) b += wsum[kk];
         tot_eq += wsum[kk];
       }
       o_eq = b + inc - c_eq;
@@ -387,22 +377,51 @@ __global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a) {
       const int j = j0 + e;
       if (short_row || key > T) {
         const uint32_t slot = n_out + o_gt++;
-        if (slot < (uint32_t)ANIREC_MAX_TOPK)
-          win[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
+        if (slot < cap) w[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
       } else if (key == T) {
         const uint32_t r = o_eq++;
         if (r < eq_use) {
           const uint32_t slot = n_out + tot_gt + r;
-          if (slot < (uint32_t)ANIREC_MAX_TOPK)
-            win[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
+          if (slot < cap) w[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
         }
       }
     }
     n_out += tot_gt + eq_use;
     eq_taken += eq_use;
-    if (n_out > (uint32_t)ANIREC_MAX_TOPK) n_out = ANIREC_MAX_TOPK;
+  }
+}
+
+__global__ __launch_bounds__(kSelThreads) void k_select(SelectArgs a) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t sh[3];
+  __shared__ uint32_t wsum[kSelThreads / 64];
+  __shared__ unsigned long long win[ANIREC_MAX_TOPK];  // (key << 32) | ~idx  -> sort desc
+  const int tid = threadIdx.x;
+  // Few queries (the reference's literal call is ONE query against every row): a query's keys are cut
+  // into slices, one workgroup each, and a second launch of this kernel merges the slice winners.  The
+  // winners of a slice are sorted (score desc, index asc) and slices cover ascending index ranges, so
+  // list order among equal scores is ascending index — the tie rule survives the merge unchanged.
+  const int q = blockIdx.x / a.slices;
+  const int j_lo = (blockIdx.x % a.slices) * a.slice_len;
+  const int j_hi = min(a.n, j_lo + a.slice_len);
+  const size_t orow = blockIdx.x;
+  const float *row = a.scores + (size_t)q * a.ld;
+  const int self = a.self ? a.self[q] : -1;
+  const int k = a.k;
+
+  // MSB-first radix select for the k-th largest key among candidates (key != 0)
+  uint4 st = make_uint4(0u, (uint32_t)k, (uint32_t)k, 0u);  // prefix, rank still to locate in it, winners, short row
+  for (int pass = 0; pass < 4 && !st.w; ++pass) {
+    sel_hist(a, row, q, self, j_lo, j_hi, st.x, sel_pmask(pass), 24 - 8 * pass, hist);
+    sel_digit(hist, st.x, st.y, 24 - 8 * pass, sh);
+    st = sel_advance(st, sh);
     __syncthreads();
   }
+  // threshold T = prefix (exact key of the k-th largest); take all keys > T and the first
+  // `want` keys == T in ascending index order.  short row: take every candidate.
+  sel_collect(a, row, q, self, j_lo, j_hi, st.w ? 0u : st.x, st.w ? 0xFFFFFFFFu : st.y, st.w != 0, 0, 0, win,
+              ANIREC_MAX_TOPK, wsum);
+  const uint32_t n_out = min(st.z, (uint32_t)ANIREC_MAX_TOPK);
   __syncthreads();
   // pad to 128 with zeros (sort last) and bitonic sort descending
   for (int i = tid; i < ANIREC_MAX_TOPK; i += kSelThreads)
@@ -540,16 +559,20 @@ __global__ __launch_bounds__(256) void k_scores_few_w(ScoreArgs a) {
 constexpr int kSelMaxBlocks = 2048;
 constexpr size_t kSelTmpBytes = (size_t)kSelMaxBlocks * ANIREC_MAX_TOPK * 8;
 
+// Few queries (the reference's literal call has ONE) against many keys: a query's keys are cut into S slices, one
+// workgroup each, so that the select fills the chip.  The one rule of k_select's launches and of the any-k ones.
+static int select_slices(int nq, int n) {
+  if (nq >= 1024 || n < 4096) return 1;
+  int S = n / 2048;
+  if (S > 64) S = 64;
+  if (S > kSelMaxBlocks / nq) S = kSelMaxBlocks / nq;
+  return S < 1 ? 1 : S;
+}
+
 // one launch when there are enough queries to fill the chip; otherwise slices + merge
 static int launch_select(SelectArgs sa, void *tmp, hipStream_t s) {
   sa.src_idx = nullptr;
-  int S = 1;
-  if (sa.nq < 1024 && sa.n >= 4096) {
-    S = sa.n / 2048;
-    if (S > 64) S = 64;
-    if (S > kSelMaxBlocks / sa.nq) S = kSelMaxBlocks / sa.nq;
-    if (S < 1) S = 1;
-  }
+  const int S = select_slices(sa.nq, sa.n);
   sa.slices = S;
   sa.slice_len = (sa.n + S - 1) / S;
   if (S == 1) {
@@ -607,6 +630,22 @@ static int launch_scores(const ScoreArgs &a0, hipStream_t s, int32_t act = ANIRE
   return (int)hipGetLastError();
 }
 
+// The head of every predict workspace: Ah | Uh, the tf.nn.l2_normalize rows of A and of the call's users.
+static size_t norm_bytes(int32_t n_anime, int32_t n_users, int32_t dim) {
+  return ((size_t)n_anime + (size_t)n_users) * dim * 4;
+}
+struct NormRows {
+  float *Ah, *Uh;
+};
+static hipError_t normalise_tables(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                                   int32_t n_users, void *workspace, hipStream_t s, NormRows *r) {
+  r->Ah = (float *)workspace;
+  r->Uh = r->Ah + (size_t)n_anime * dim;
+  launch_rownorm<1>(A, nullptr, n_anime, r->Ah, dim, s);
+  launch_rownorm<1>(U, users, n_users, r->Uh, dim, s);
+  return hipGetLastError();
+}
+
 }  // namespace anirec
 
 using namespace anirec;
@@ -642,72 +681,6 @@ int anirec_cosine_scores_w(const float *What, int32_t n, int32_t dim, int32_t q,
   a.use_head = 0;
   a.hs = a.hb = 0.f;
   return launch_scores(a, (hipStream_t)stream, ANIREC_ACT_SIGMOID, dim);
-}
-
-// workspace: self[nq] ints (256-aligned) + score rows for a batch of queries
-size_t anirec_topk_workspace_bytes(int32_t n, int32_t nq) {
-  if (n < 1 || nq < 1) return 0;
-  size_t self_bytes = ((size_t)nq * 4 + 255) / 256 * 256;
-  size_t qb = (size_t)nq < 1024 ? (size_t)nq : 1024;
-  // cap the score buffer at 4 GiB
-  while (qb > 1 && qb * (size_t)n * 4 > ((size_t)4 << 30)) qb >>= 1;
-  return self_bytes + kSelTmpBytes + qb * (size_t)n * 4;
-}
-
-int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int32_t nq,
-                       const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
-                       float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
-  return anirec_cosine_topk_w(What, n, ANIREC_DIM, queries, nq, keep, exclude_self, k, out_idx, out_score, workspace,
-                              workspace_bytes, stream);
-}
-
-int anirec_cosine_topk_w(const float *What, int32_t n, int32_t dim, const int32_t *queries, int32_t nq,
-                         const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
-                         float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
-  if (!What || !queries || !out_idx || !out_score || !workspace || !dim_ok(dim)) return ANIREC_EINVAL;
-  if (n < 1 || nq < 0 || k < 1 || k > ANIREC_MAX_TOPK) return ANIREC_EINVAL;
-  if (nq == 0) return ANIREC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  size_t self_bytes = ((size_t)nq * 4 + 255) / 256 * 256;
-  if (workspace_bytes < self_bytes + kSelTmpBytes + (size_t)n * 4) return ANIREC_EWORKSPACE;
-  int32_t *self = (int32_t *)workspace;
-  void *sel_tmp = (char *)workspace + self_bytes;
-  float *buf = (float *)((char *)workspace + self_bytes + kSelTmpBytes);
-  size_t qb = (workspace_bytes - self_bytes - kSelTmpBytes) / ((size_t)n * 4);
-  if (qb > (size_t)nq) qb = nq;
-  hipLaunchKernelGGL(k_fill_self, dim3((nq + 255) / 256), dim3(256), 0, s, queries, nq, self,
-                     exclude_self);
-  ANIREC_HIP_CHECK(hipGetLastError());
-  for (size_t q0 = 0; q0 < (size_t)nq; q0 += qb) {
-    const int cnt = (int)((size_t)nq - q0 < qb ? (size_t)nq - q0 : qb);
-    ScoreArgs a;
-    a.Q = What;
-    a.qrows = queries + q0;
-    a.nq = cnt;
-    a.W = What;
-    a.n = n;
-    a.out = buf;
-    a.ld = (size_t)n;
-    a.use_head = 0;
-    a.hs = a.hb = 0.f;
-    int e = launch_scores(a, s, ANIREC_ACT_SIGMOID, dim);
-    if (e) return e;
-    SelectArgs sa;
-    sa.scores = buf;
-    sa.ld = (size_t)n;
-    sa.n = n;
-    sa.nq = cnt;
-    sa.k = k;
-    sa.self = self + q0;
-    sa.keep = keep;
-    sa.wbits = nullptr;
-    sa.wwords = 0;
-    sa.out_idx = out_idx + q0 * k;
-    sa.out_score = out_score + q0 * k;
-    e = launch_select(sa, sel_tmp, s);
-    if (e) return e;
-  }
-  return ANIREC_OK;
 }
 
 int anirec_predict_pairs_act(const float *U, const float *A, const int32_t *user_idx,
@@ -746,26 +719,6 @@ int anirec_predict_pairs(const float *U, const float *A, const int32_t *user_idx
   return anirec_predict_pairs_act(U, A, user_idx, anime_idx, n, head, ANIREC_ACT_SIGMOID, p, stream);
 }
 
-// workspace of predict_grid / predict_topk: normalised copies of the query users and of A,
-// plus (topk) a batch of rating rows.
-static size_t norm_bytes(int32_t n_anime, int32_t n_users, int32_t dim) {
-  return ((size_t)n_anime + (size_t)n_users) * dim * 4;
-}
-
-size_t anirec_predict_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t topk) {
-  return anirec_predict_workspace_bytes_w(n_anime, n_users, topk, ANIREC_DIM);
-}
-
-size_t anirec_predict_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t topk, int32_t dim) {
-  if (n_anime < 1 || n_users < 1 || !dim_ok(dim)) return 0;
-  size_t b = norm_bytes(n_anime, n_users, dim);
-  if (topk) {
-    size_t qb = (size_t)n_users < 4096 ? (size_t)n_users : 4096;
-    b += kSelTmpBytes + qb * (size_t)n_anime * 4;
-  }
-  return b;
-}
-
 int anirec_predict_grid(const float *U, const float *A, int32_t n_anime, const int32_t *users,
                         int32_t n_users, const anirec_head *head, float *out, void *workspace,
                         size_t workspace_bytes, void *stream) {
@@ -789,16 +742,13 @@ int anirec_predict_grid_w(const float *U, const float *A, int32_t dim, int32_t n
   if (n_users == 0) return ANIREC_OK;
   if (workspace_bytes < norm_bytes(n_anime, n_users, dim)) return ANIREC_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  float *Ah = (float *)workspace;
-  float *Uh = Ah + (size_t)n_anime * dim;
-  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
-  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
-  ANIREC_HIP_CHECK(hipGetLastError());
+  NormRows t;
+  ANIREC_HIP_CHECK(normalise_tables(U, A, dim, n_anime, users, n_users, workspace, s, &t));
   ScoreArgs a;
-  a.Q = Uh;
+  a.Q = t.Uh;
   a.qrows = nullptr;
   a.nq = n_users;
-  a.W = Ah;
+  a.W = t.Ah;
   a.n = n_anime;
   a.out = out;
   a.ld = (size_t)n_anime;
@@ -807,95 +757,25 @@ int anirec_predict_grid_w(const float *U, const float *A, int32_t dim, int32_t n
   return launch_scores(a, s, activation, dim);
 }
 
-int anirec_predict_topk(const float *U, const float *A, int32_t n_anime, const int32_t *users,
-                        int32_t n_users, const anirec_head *head, const uint32_t *watched,
-                        int32_t k, int32_t *out_idx, float *out_p, void *workspace,
-                        size_t workspace_bytes, void *stream) {
-  return anirec_predict_topk_act(U, A, n_anime, users, n_users, head, ANIREC_ACT_SIGMOID, watched, k, out_idx, out_p,
-                                 workspace, workspace_bytes, stream);
-}
-
-int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
-                            int32_t n_users, const anirec_head *head, int32_t activation,
-                            const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
-                            size_t workspace_bytes, void *stream) {
-  return anirec_predict_topk_w(U, A, ANIREC_DIM, n_anime, users, n_users, head, activation, watched, k, out_idx, out_p,
-                               workspace, workspace_bytes, stream);
-}
-
-int anirec_predict_topk_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
-                          int32_t n_users, const anirec_head *head, int32_t activation,
-                          const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
-                          size_t workspace_bytes, void *stream) {
-  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation) || !dim_ok(dim))
-    return ANIREC_EINVAL;
-  if (n_anime < 1 || n_users < 0 || k < 1 || k > ANIREC_MAX_TOPK) return ANIREC_EINVAL;
-  if (n_users == 0) return ANIREC_OK;
-  const size_t nb = norm_bytes(n_anime, n_users, dim) + kSelTmpBytes;
-  if (workspace_bytes < nb + (size_t)n_anime * 4) return ANIREC_EWORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  float *Ah = (float *)workspace;
-  float *Uh = Ah + (size_t)n_anime * dim;
-  void *sel_tmp = Uh + (size_t)n_users * dim;
-  float *buf = (float *)((char *)sel_tmp + kSelTmpBytes);
-  size_t qb = (workspace_bytes - nb) / ((size_t)n_anime * 4);
-  if (qb > (size_t)n_users) qb = n_users;
-  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
-  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
-  ANIREC_HIP_CHECK(hipGetLastError());
-  const int wwords = (n_anime + 31) / 32;
-  float hs, hb;
-  head_affine(head, &hs, &hb);
-  for (size_t q0 = 0; q0 < (size_t)n_users; q0 += qb) {
-    const int cnt = (int)((size_t)n_users - q0 < qb ? (size_t)n_users - q0 : qb);
-    ScoreArgs a;
-    a.Q = Uh + q0 * dim;
-    a.qrows = nullptr;
-    a.nq = cnt;
-    a.W = Ah;
-    a.n = n_anime;
-    a.out = buf;
-    a.ld = (size_t)n_anime;
-    a.use_head = 1;
-    a.hs = hs;
-    a.hb = hb;
-    int e = launch_scores(a, s, activation, dim);
-    if (e) return e;
-    SelectArgs sa;
-    sa.scores = buf;
-    sa.ld = (size_t)n_anime;
-    sa.n = n_anime;
-    sa.nq = cnt;
-    sa.k = k;
-    sa.self = nullptr;
-    sa.keep = nullptr;
-    sa.wbits = watched ? watched + q0 * wwords : nullptr;
-    sa.wwords = wwords;
-    sa.out_idx = out_idx + q0 * k;
-    sa.out_score = out_p + q0 * k;
-    e = launch_select(sa, sel_tmp, s);
-    if (e) return e;
-  }
-  return ANIREC_OK;
-}
-
 }  // extern "C"
 
 // ====================================================================================
 // exact top-k for ANY k (anirec_cosine_topk_large, anirec_predict_topk_large_act)
 //
-// The same score rows (k_scores / k_scores_few through launch_scores) and the same keys (cand_key) as k_select,
-// so the result is k_select's for k <= ANIREC_MAX_TOPK.  Phases, all stream-ordered launches:
-//   select   the 4-pass MSB radix select of k_select -> threshold key T, `want` keys == T to take (first in index
-//            order), m = winners (k, or every candidate of a short row).  Few queries: the histograms of each pass
-//            are built per slice by one workgroup each (k_lk_hist) and summed by the next launch; many queries: one
-//            workgroup per query does all four passes (k_lk_select_row).
-//   collect  the m winners as (key << 32) | ~index, unique per query, into win[q][0..m).  Sliced: per-slice
-//            counts (k_lk_count), each slice's offset from the counts of the slices before it (k_lk_write).
+// The same score rows (k_scores / k_scores_few through launch_scores), the same keys (cand_key) and the same select
+// body (sel_hist / sel_digit / sel_advance / sel_collect, above k_select) as k_select, so the result is k_select's
+// for k <= ANIREC_MAX_TOPK.  Phases, all stream-ordered launches:
+//   select   the 4-pass MSB radix select (sel_hist + sel_digit) -> threshold key T, `want` keys == T to take (first
+//            in index order), m = winners (k, or every candidate of a short row).  Few queries (select_slices): the
+//            histograms of each pass are built per slice by one workgroup each (k_lk_hist) and summed by the next
+//            launch; many queries: one workgroup per query does all four passes (k_lk_select_row).
+//   collect  the m winners as (key << 32) | ~index, unique per query, into win[q][0..m) (sel_collect).  Sliced:
+//            per-slice counts (k_lk_count), each slice's offset from the counts of the slices before it (k_lk_write).
 //   sort     descending on that 64-bit value = score descending, ties ascending index.  m <= kLkSortMax: one
 //            workgroup per query sorts in LDS and gathers; above: tiles of kLkTile sorted in LDS, then merge
 //            passes that place each entry by its rank in the partner run (k_lk_merge), the last one gathering.
 //   gather   out_idx[q][i] = index, out_score[q][i] = row[index] (bit for bit), -1 / NaN for i >= m.
+// After the kernels: the batch driver (topk_batches) and the entry points of both exact paths, this one and k_select's.
 // ====================================================================================
 namespace anirec {
 
@@ -914,147 +794,6 @@ struct LkArgs {
   uint32_t *cnt;            // [nq * slices][2] winners above / at the threshold per slice
 };
 
-// The digit of one radix pass from a 256-bin histogram in LDS: k_select's wave scan.  out[0], out[1] = the new
-// prefix and want, or 0xFFFFFFFF and 0 when fewer than `want` keys match (pass 0 only: fewer than k candidates);
-// out[2] = the keys matching the prefix.  Ends with a barrier.
-__device__ void lk_digit(const uint32_t *hist, uint32_t prefix, uint32_t want, int shift, uint32_t *out) {
-  const int tid = threadIdx.x;
-  if (tid < 64) {
-    uint32_t h4[4], run = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      h4[j] = hist[255 - (4 * tid + j)];
-      run += h4[j];
-    }
-    uint32_t inc = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = __shfl_up(inc, o, 64);
-      if (tid >= o) inc += y;
-    }
-    const uint32_t before = inc - run;
-    const unsigned long long reach = __ballot(inc >= want);
-    if (tid == 63) out[2] = inc;
-    if (reach == 0ull) {
-      if (tid == 0) {
-        out[0] = 0xFFFFFFFFu;
-        out[1] = 0;
-      }
-    } else if (tid == __ffsll((long long)reach) - 1) {
-      uint32_t cum = before;
-      int j = 0;
-      for (; j < 3; ++j) {
-        if (cum + h4[j] >= want) break;
-        cum += h4[j];
-      }
-      out[0] = prefix | ((uint32_t)(255 - (4 * tid + j)) << shift);
-      out[1] = want - cum;
-    }
-  }
-  __syncthreads();
-}
-
-// hist[d] = candidates of [j_lo, j_hi) whose key matches `prefix` under `pmask` and has digit d at `shift`
-__device__ void lk_hist(const SelectArgs &a, const float *row, int q, int self, int j_lo, int j_hi, uint32_t prefix,
-                        uint32_t pmask, int shift, uint32_t *hist) {
-  const int tid = threadIdx.x;
-  hist[tid] = 0;
-  __syncthreads();
-  for (int j = j_lo + tid; j < j_hi; j += kSelThreads) {
-    const uint32_t key = cand_key(a, row, q, j, self);
-    if (key != 0u && (key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ uint32_t lk_pmask(int pass) { return pass == 0 ? 0u : 0xFFFFFFFFu << (32 - 8 * pass); }
-
-// state (prefix, want, m, short) after pass p from the one after pass p - 1 and the digit scan of pass p
-__device__ uint4 lk_advance(uint4 prev, const uint32_t *sh) {
-  if (sh[0] == 0xFFFFFFFFu && sh[1] == 0) return make_uint4(0u, 0xFFFFFFFFu, sh[2], 1u);
-  return make_uint4(sh[0], sh[1], prev.z, 0u);
-}
-
-// Ordered collection of the winners of [j_lo, j_hi): k_select's loop, into a global row of `cap` entries.
-// n_out / eq_taken: winners / keys == T already taken by the slices before this one.
-__device__ void lk_collect(const SelectArgs &a, const float *row, int q, int self, int j_lo, int j_hi, uint32_t T,
-                           uint32_t need_eq, bool short_row, uint32_t n_out, uint32_t eq_taken,
-                           unsigned long long *w, uint32_t cap, uint32_t *wsum) {
-  const int tid = threadIdx.x;
-  constexpr int kPer = 16;
-  const int super = kSelThreads * kPer;
-  for (int base = j_lo; base < j_hi; base += super) {
-    uint32_t keys[kPer];
-    uint32_t c_gt = 0, c_eq = 0;
-    const int j0 = base + tid * kPer;
-#pragma unroll
-    for (int e = 0; e < kPer; ++e) {
-      const int j = j0 + e;
-      keys[e] = j < j_hi ? cand_key(a, row, q, j, self) : 0u;
-      if (keys[e] != 0u) {
-        if (short_row || keys[e] > T) ++c_gt;
-        else if (keys[e] == T) ++c_eq;
-      }
-    }
-    if (__syncthreads_count((c_gt | c_eq) != 0) == 0) continue;
-    uint32_t tot_gt = 0, tot_eq = 0;
-    uint32_t o_gt, o_eq;
-    {
-      const int lane = tid & 63, wv = tid >> 6;
-      uint32_t inc = c_gt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
-      if (lane == 63) wsum[wv] = inc;
-      __syncthreads();
-      uint32_t b = 0;
-      for (int kk = 0; kk < kSelThreads / 64; ++kk) {
-        if (kk < wv) b += wsum[kk];
-        tot_gt += wsum[kk];
-      }
-      o_gt = b + inc - c_gt;
-      __syncthreads();
-      inc = c_eq;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        uint32_t t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-      }
-      if (lane == 63) wsum[wv] = inc;
-      __syncthreads();
-      b = 0;
-      for (int kk = 0; kk < kSelThreads / 64; ++kk) {
-        if (kk < wv) b += wsum[kk];
-        tot_eq += wsum[kk];
-      }
-      o_eq = b + inc - c_eq;
-      __syncthreads();
-    }
-    const uint32_t eq_room = need_eq == 0xFFFFFFFFu ? 0u : (need_eq - eq_taken);
-    const uint32_t eq_use = tot_eq < eq_room ? tot_eq : eq_room;
-#pragma unroll
-    for (int e = 0; e < kPer; ++e) {
-      const uint32_t key = keys[e];
-      if (key == 0u) continue;
-      const int j = j0 + e;
-      if (short_row || key > T) {
-        const uint32_t slot = n_out + o_gt++;
-        if (slot < cap) w[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
-      } else if (key == T) {
-        const uint32_t r = o_eq++;
-        if (r < eq_use) {
-          const uint32_t slot = n_out + tot_gt + r;
-          if (slot < cap) w[slot] = ((unsigned long long)key << 32) | (uint32_t)(~(uint32_t)j);
-        }
-      }
-    }
-    n_out += tot_gt + eq_use;
-    eq_taken += eq_use;
-  }
-}
-
 // many queries: one workgroup per query runs the whole select and collects its winners
 __global__ __launch_bounds__(kSelThreads) void k_lk_select_row(LkArgs a) {
   __shared__ uint32_t hist[256];
@@ -1066,13 +805,13 @@ __global__ __launch_bounds__(kSelThreads) void k_lk_select_row(LkArgs a) {
   const int self = s.self ? s.self[q] : -1;
   uint4 st = make_uint4(0u, (uint32_t)s.k, (uint32_t)s.k, 0u);
   for (int pass = 0; pass < 4 && !st.w; ++pass) {
-    lk_hist(s, row, q, self, 0, s.n, st.x, lk_pmask(pass), 24 - 8 * pass, hist);
-    lk_digit(hist, st.x, st.y, 24 - 8 * pass, sh);
-    st = lk_advance(st, sh);
+    sel_hist(s, row, q, self, 0, s.n, st.x, sel_pmask(pass), 24 - 8 * pass, hist);
+    sel_digit(hist, st.x, st.y, 24 - 8 * pass, sh);
+    st = sel_advance(st, sh);
     __syncthreads();
   }
   if (threadIdx.x == 0) a.st[3 * s.nq + q] = st;
-  lk_collect(s, row, q, self, 0, s.n, st.w ? 0u : st.x, st.w ? 0xFFFFFFFFu : st.y, st.w != 0, 0, 0,
+  sel_collect(s, row, q, self, 0, s.n, st.w ? 0u : st.x, st.w ? 0xFFFFFFFFu : st.y, st.w != 0, 0, 0,
              a.win + (size_t)q * a.kcap, (uint32_t)a.kcap, wsum);
 }
 
@@ -1088,8 +827,8 @@ __device__ uint4 lk_state(const LkArgs &a, int q, int slice, int pass, uint32_t 
     for (int b = 0; b < s.slices; ++b) sum += h[(size_t)b * 256 + threadIdx.x];
     hist[threadIdx.x] = sum;
     __syncthreads();
-    lk_digit(hist, prev.x, prev.y, 24 - 8 * (pass - 1), sh);
-    st = lk_advance(prev, sh);
+    sel_digit(hist, prev.x, prev.y, 24 - 8 * (pass - 1), sh);
+    st = sel_advance(prev, sh);
     __syncthreads();
   }
   if (slice == 0 && threadIdx.x == 0) a.st[(size_t)(pass - 1) * s.nq + q] = st;
@@ -1108,7 +847,7 @@ __global__ __launch_bounds__(kSelThreads) void k_lk_hist(LkArgs a) {
   uint4 st = make_uint4(0u, (uint32_t)s.k, (uint32_t)s.k, 0u);
   if constexpr (kPass > 0) st = lk_state(a, q, slice, kPass, hist, sh);
   if (st.w) return;  // short row: every candidate wins, nothing left to locate
-  lk_hist(s, row, q, self, j_lo, j_hi, st.x, lk_pmask(kPass), 24 - 8 * kPass, hist);
+  sel_hist(s, row, q, self, j_lo, j_hi, st.x, sel_pmask(kPass), 24 - 8 * kPass, hist);
   a.hist[((size_t)kPass * s.nq * s.slices + blockIdx.x) * 256 + threadIdx.x] = hist[threadIdx.x];
 }
 
@@ -1157,7 +896,7 @@ __global__ __launch_bounds__(kSelThreads) void k_lk_write(LkArgs a) {
     n_out += c[0] + use;
     eq_taken += use;
   }
-  lk_collect(s, row, q, self, j_lo, j_hi, st.w ? 0u : st.x, need_eq, st.w != 0, n_out, eq_taken,
+  sel_collect(s, row, q, self, j_lo, j_hi, st.w ? 0u : st.x, need_eq, st.w != 0, n_out, eq_taken,
              a.win + (size_t)q * a.kcap, (uint32_t)a.kcap, wsum);
 }
 
@@ -1260,13 +999,7 @@ __global__ __launch_bounds__(256) void k_lk_merge(LkArgs a, const unsigned long 
 static int lk_run(LkArgs a, hipStream_t s) {
   SelectArgs &sa = a.s;
   sa.src_idx = nullptr;
-  int S = 1;
-  if (sa.nq < 1024 && sa.n >= 4096) {  // launch_select's slicing
-    S = sa.n / 2048;
-    if (S > 64) S = 64;
-    if (S > kSelMaxBlocks / sa.nq) S = kSelMaxBlocks / sa.nq;
-    if (S < 1) S = 1;
-  }
+  const int S = select_slices(sa.nq, sa.n);
   sa.slices = S;
   sa.slice_len = (sa.n + S - 1) / S;
   if (S == 1) {
@@ -1307,37 +1040,186 @@ static int lk_run(LkArgs a, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-// workspace of the large path after its fixed part: per query a state, the winners (two buffers when the
-// multi-workgroup sort merges) and a score row
-static size_t lk_kcap(int32_t n, int32_t k) { return (size_t)(k < n ? k : n); }
-static size_t lk_per_query(int32_t n, int32_t k) {
-  const size_t kc = lk_kcap(n, k);
-  return 4 * sizeof(uint4) + kc * 8 * (kc > (size_t)kLkSortMax ? 2 : 1) + (size_t)n * 4;
+// ------------------------------------------------------------------------------------
+// the batch driver of the four exact top-k entry points: score rows for a batch of queries, then a select from them
+// ------------------------------------------------------------------------------------
+// The workspace of a call after its head (self[nq] of a cosine call, Ah | Uh of a predict call), for either select
+// kind: a fixed part, then per query of a batch what bytes() sizes and carve() hands out.
+//   launch_select  slice winners (kSelTmpBytes) | score rows
+//   lk_run         hist | cnt | per query: a state, the winners (two buffers when the multi-workgroup sort merges),
+//                  a score row
+struct TopkLayout {
+  bool large;        // the select kind: lk_run, else launch_select
+  size_t kcap;       // large: min(k, n), the most winners a query can have
+  size_t fixed, per_query;
+
+  // a call of nq queries in batches of at most `cap`, halved while a batch is above `limit` bytes
+  size_t bytes(size_t nq, size_t cap, size_t limit = (size_t)4 << 30) const {
+    size_t qb = nq < cap ? nq : cap;
+    while (qb > 1 && qb * per_query > limit) qb >>= 1;
+    return fixed + qb * per_query;
+  }
+  // a batch of qb queries out of `p` (256-aligned); returns its score rows
+  float *carve(char *p, size_t qb, LkArgs &la, void *&sel_tmp) const {
+    if (!large) {
+      sel_tmp = p;
+      return (float *)(p + fixed);
+    }
+    la.hist = (uint32_t *)p;
+    la.cnt = (uint32_t *)(p + kLkHistBytes);
+    la.st = (uint4 *)(p + fixed);
+    la.kcap = kcap;
+    la.win = (unsigned long long *)(la.st + 4 * qb);
+    la.win2 = kcap > (size_t)kLkSortMax ? la.win + qb * kcap : la.win;
+    return (float *)(la.win2 + qb * kcap);
+  }
+};
+static TopkLayout select_layout(int32_t n) { return {false, 0, kSelTmpBytes, (size_t)n * 4}; }
+static TopkLayout lk_layout(int32_t n, int32_t k) {
+  const size_t kc = (size_t)(k < n ? k : n);
+  return {true, kc, kLkHistBytes + kLkCntBytes,
+          4 * sizeof(uint4) + kc * 8 * (kc > (size_t)kLkSortMax ? 2 : 1) + (size_t)n * 4};
 }
-static size_t lk_batch_bytes(int32_t n, int32_t k, size_t qb) {
-  while (qb > 1 && qb * lk_per_query(n, k) > ((size_t)4 << 30)) qb >>= 1;
-  return kLkHistBytes + kLkCntBytes + qb * lk_per_query(n, k);
+static size_t self_bytes(int32_t nq) { return ((size_t)nq * 4 + 255) / 256 * 256; }
+
+// where the score rows come from: query q of the call is row (qrows ? qrows[q] : q) of Q
+struct ScoreSource {
+  const float *Q, *W;     // cosine: Q = W = What; predict: Uh, Ah
+  const int32_t *qrows;   // cosine: the call's queries
+  int dim;
+  int use_head;           // predict: act(c * hs + hb)
+  float hs, hb;
+  int32_t act;
+};
+// what a query may not return (SelectArgs): all optional
+struct RowMasks {
+  const int32_t *self;    // [nq]
+  const uint8_t *keep;    // [n]
+  const uint32_t *wbits;  // [nq][(n + 31) / 32]
+};
+
+// `ws`: the workspace after its head, at least L.fixed + L.per_query bytes (the entry point has checked)
+static int topk_batches(const ScoreSource &src, const RowMasks &m, const TopkLayout &L, int n, int nq, int k,
+                        int32_t *out_idx, float *out_score, char *ws, size_t ws_bytes, hipStream_t s) {
+  size_t qb = (ws_bytes - L.fixed) / L.per_query;
+  if (qb > (size_t)nq) qb = nq;
+  LkArgs la = {};
+  void *sel_tmp = nullptr;
+  float *buf = L.carve(ws, qb, la, sel_tmp);
+  const int wwords = (n + 31) / 32;
+  for (size_t q0 = 0; q0 < (size_t)nq; q0 += qb) {
+    const int cnt = (int)((size_t)nq - q0 < qb ? (size_t)nq - q0 : qb);
+    ScoreArgs a;
+    a.Q = src.qrows ? src.Q : src.Q + q0 * src.dim;
+    a.qrows = src.qrows ? src.qrows + q0 : nullptr;
+    a.nq = cnt;
+    a.W = src.W;
+    a.n = n;
+    a.out = buf;
+    a.ld = (size_t)n;
+    a.use_head = src.use_head;
+    a.hs = src.hs;
+    a.hb = src.hb;
+    int e = launch_scores(a, s, src.act, src.dim);
+    if (e) return e;
+    SelectArgs &sa = la.s;
+    sa.scores = buf;
+    sa.ld = (size_t)n;
+    sa.n = n;
+    sa.nq = cnt;
+    sa.k = k;
+    sa.self = m.self ? m.self + q0 : nullptr;
+    sa.keep = m.keep;
+    sa.wbits = m.wbits ? m.wbits + q0 * wwords : nullptr;
+    sa.wwords = wwords;
+    sa.out_idx = out_idx + q0 * k;
+    sa.out_score = out_score + q0 * k;
+    e = L.large ? lk_run(la, s) : launch_select(sa, sel_tmp, s);
+    if (e) return e;
+  }
+  return ANIREC_OK;
 }
 
-// carve a batch of qb queries out of `p` (256-aligned): hist | cnt | st | win (| win2) | score rows
-static float *lk_carve(LkArgs &la, char *p, int32_t n, int32_t k, size_t qb) {
-  la.hist = (uint32_t *)p;
-  la.cnt = (uint32_t *)(p + kLkHistBytes);
-  la.st = (uint4 *)(p + kLkHistBytes + kLkCntBytes);
-  la.kcap = lk_kcap(n, k);
-  la.win = (unsigned long long *)(la.st + 4 * qb);
-  la.win2 = la.kcap > (size_t)kLkSortMax ? la.win + qb * la.kcap : la.win;
-  return (float *)(la.win2 + qb * la.kcap);
+// the cosine calls: self[nq] (256-aligned) at the head of the workspace
+static int cosine_topk(const TopkLayout &L, const float *What, int32_t n, int32_t dim, const int32_t *queries,
+                       int32_t nq, const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                       float *out_score, void *workspace, size_t workspace_bytes, hipStream_t s) {
+  const size_t head = self_bytes(nq);
+  if (workspace_bytes < head + L.fixed + L.per_query) return ANIREC_EWORKSPACE;
+  int32_t *self = (int32_t *)workspace;
+  hipLaunchKernelGGL(k_fill_self, dim3((nq + 255) / 256), dim3(256), 0, s, queries, nq, self, exclude_self);
+  ANIREC_HIP_CHECK(hipGetLastError());
+  const ScoreSource src = {What, What, queries, dim, 0, 0.f, 0.f, ANIREC_ACT_SIGMOID};
+  const RowMasks m = {self, keep, nullptr};
+  return topk_batches(src, m, L, n, nq, k, out_idx, out_score, (char *)workspace + head, workspace_bytes - head, s);
+}
+
+// the predict calls: Ah | Uh at the head of the workspace
+static int predict_topk(const TopkLayout &L, const float *U, const float *A, int32_t dim, int32_t n_anime,
+                        const int32_t *users, int32_t n_users, const anirec_head *head, int32_t activation,
+                        const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                        size_t workspace_bytes, hipStream_t s) {
+  const size_t nb = norm_bytes(n_anime, n_users, dim);
+  if (workspace_bytes < nb + L.fixed + L.per_query) return ANIREC_EWORKSPACE;
+  NormRows t;
+  ANIREC_HIP_CHECK(normalise_tables(U, A, dim, n_anime, users, n_users, workspace, s, &t));
+  ScoreSource src = {t.Uh, t.Ah, nullptr, dim, 1, 0.f, 0.f, activation};
+  head_affine(head, &src.hs, &src.hb);
+  const RowMasks m = {nullptr, nullptr, watched};
+  return topk_batches(src, m, L, n_anime, n_users, k, out_idx, out_p, (char *)workspace + nb, workspace_bytes - nb, s);
 }
 
 }  // namespace anirec
 
 extern "C" {
 
+// Batches: 1024 queries for cosine, 4096 for predict; the score rows of a batch are capped at 4 GiB (not in
+// anirec_predict_workspace_bytes, which never was).  The least an entry point takes is the head, the fixed part and
+// one query: it then runs one query per batch.
+size_t anirec_topk_workspace_bytes(int32_t n, int32_t nq) {
+  if (n < 1 || nq < 1) return 0;
+  return self_bytes(nq) + select_layout(n).bytes(nq, 1024);
+}
+
 size_t anirec_topk_large_workspace_bytes(int32_t n, int32_t nq, int32_t k) {
   if (n < 1 || nq < 1 || k < 1) return 0;
-  const size_t self_bytes = ((size_t)nq * 4 + 255) / 256 * 256;
-  return self_bytes + lk_batch_bytes(n, k, (size_t)nq < 1024 ? (size_t)nq : 1024);
+  return self_bytes(nq) + lk_layout(n, k).bytes(nq, 1024);
+}
+
+size_t anirec_predict_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t topk) {
+  return anirec_predict_workspace_bytes_w(n_anime, n_users, topk, ANIREC_DIM);
+}
+
+// predict_grid (topk == 0): the normalised tables alone
+size_t anirec_predict_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t topk, int32_t dim) {
+  if (n_anime < 1 || n_users < 1 || !dim_ok(dim)) return 0;
+  return norm_bytes(n_anime, n_users, dim) + (topk ? select_layout(n_anime).bytes(n_users, 4096, SIZE_MAX) : 0);
+}
+
+size_t anirec_predict_topk_large_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t k) {
+  return anirec_predict_topk_large_workspace_bytes_w(n_anime, n_users, k, ANIREC_DIM);
+}
+
+size_t anirec_predict_topk_large_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t k, int32_t dim) {
+  if (n_anime < 1 || n_users < 1 || k < 1 || !dim_ok(dim)) return 0;
+  return norm_bytes(n_anime, n_users, dim) + lk_layout(n_anime, k).bytes(n_users, 4096);
+}
+
+int anirec_cosine_topk(const float *What, int32_t n, const int32_t *queries, int32_t nq,
+                       const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                       float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
+  return anirec_cosine_topk_w(What, n, ANIREC_DIM, queries, nq, keep, exclude_self, k, out_idx, out_score, workspace,
+                              workspace_bytes, stream);
+}
+
+int anirec_cosine_topk_w(const float *What, int32_t n, int32_t dim, const int32_t *queries, int32_t nq,
+                         const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
+                         float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
+  if (!What || !queries || !out_idx || !out_score || !workspace || !dim_ok(dim)) return ANIREC_EINVAL;
+  if (n < 1 || nq < 0 || k < 1 || k > ANIREC_MAX_TOPK) return ANIREC_EINVAL;
+  if (nq == 0) return ANIREC_OK;
+  return cosine_topk(select_layout(n), What, n, dim, queries, nq, keep, exclude_self, k, out_idx, out_score,
+                     workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *queries, int32_t nq, const uint8_t *keep,
@@ -1347,63 +1229,43 @@ int anirec_cosine_topk_large(const float *What, int32_t n, const int32_t *querie
                                     workspace, workspace_bytes, stream);
 }
 
+// (the any-k kernels whatever k is: the entry point chooses the select kind)
 int anirec_cosine_topk_large_w(const float *What, int32_t n, int32_t dim, const int32_t *queries, int32_t nq,
                                const uint8_t *keep, int32_t exclude_self, int32_t k, int32_t *out_idx,
                                float *out_score, void *workspace, size_t workspace_bytes, void *stream) {
   if (!What || !queries || !out_idx || !out_score || !workspace || !dim_ok(dim)) return ANIREC_EINVAL;
   if (n < 1 || nq < 0 || k < 1) return ANIREC_EINVAL;
   if (nq == 0) return ANIREC_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const size_t self_bytes = ((size_t)nq * 4 + 255) / 256 * 256;
-  const size_t fixed = self_bytes + kLkHistBytes + kLkCntBytes;
-  const size_t pq = lk_per_query(n, k);
-  if (workspace_bytes < fixed + pq) return ANIREC_EWORKSPACE;
-  size_t qb = (workspace_bytes - fixed) / pq;
-  if (qb > (size_t)nq) qb = nq;
-  int32_t *self = (int32_t *)workspace;
-  LkArgs la;
-  float *buf = lk_carve(la, (char *)workspace + self_bytes, n, k, qb);
-  hipLaunchKernelGGL(k_fill_self, dim3((nq + 255) / 256), dim3(256), 0, s, queries, nq, self, exclude_self);
-  ANIREC_HIP_CHECK(hipGetLastError());
-  for (size_t q0 = 0; q0 < (size_t)nq; q0 += qb) {
-    const int cnt = (int)((size_t)nq - q0 < qb ? (size_t)nq - q0 : qb);
-    ScoreArgs a;
-    a.Q = What;
-    a.qrows = queries + q0;
-    a.nq = cnt;
-    a.W = What;
-    a.n = n;
-    a.out = buf;
-    a.ld = (size_t)n;
-    a.use_head = 0;
-    a.hs = a.hb = 0.f;
-    int e = launch_scores(a, s, ANIREC_ACT_SIGMOID, dim);
-    if (e) return e;
-    SelectArgs &sa = la.s;
-    sa.scores = buf;
-    sa.ld = (size_t)n;
-    sa.n = n;
-    sa.nq = cnt;
-    sa.k = k;
-    sa.self = self + q0;
-    sa.keep = keep;
-    sa.wbits = nullptr;
-    sa.wwords = 0;
-    sa.out_idx = out_idx + q0 * k;
-    sa.out_score = out_score + q0 * k;
-    e = lk_run(la, s);
-    if (e) return e;
-  }
-  return ANIREC_OK;
+  return cosine_topk(lk_layout(n, k), What, n, dim, queries, nq, keep, exclude_self, k, out_idx, out_score, workspace,
+                     workspace_bytes, (hipStream_t)stream);
 }
 
-size_t anirec_predict_topk_large_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t k) {
-  return anirec_predict_topk_large_workspace_bytes_w(n_anime, n_users, k, ANIREC_DIM);
+int anirec_predict_topk(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                        int32_t n_users, const anirec_head *head, const uint32_t *watched,
+                        int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+  return anirec_predict_topk_act(U, A, n_anime, users, n_users, head, ANIREC_ACT_SIGMOID, watched, k, out_idx, out_p,
+                                 workspace, workspace_bytes, stream);
 }
 
-size_t anirec_predict_topk_large_workspace_bytes_w(int32_t n_anime, int32_t n_users, int32_t k, int32_t dim) {
-  if (n_anime < 1 || n_users < 1 || k < 1 || !dim_ok(dim)) return 0;
-  return norm_bytes(n_anime, n_users, dim) + lk_batch_bytes(n_anime, k, (size_t)n_users < 4096 ? (size_t)n_users : 4096);
+int anirec_predict_topk_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
+                            int32_t n_users, const anirec_head *head, int32_t activation,
+                            const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+  return anirec_predict_topk_w(U, A, ANIREC_DIM, n_anime, users, n_users, head, activation, watched, k, out_idx, out_p,
+                               workspace, workspace_bytes, stream);
+}
+
+int anirec_predict_topk_w(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                          int32_t n_users, const anirec_head *head, int32_t activation,
+                          const uint32_t *watched, int32_t k, int32_t *out_idx, float *out_p, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+  if (!U || !A || !users || !head || !out_idx || !out_p || !workspace || !act_ok(activation) || !dim_ok(dim))
+    return ANIREC_EINVAL;
+  if (n_anime < 1 || n_users < 0 || k < 1 || k > ANIREC_MAX_TOPK) return ANIREC_EINVAL;
+  if (n_users == 0) return ANIREC_OK;
+  return predict_topk(select_layout(n_anime), U, A, dim, n_anime, users, n_users, head, activation, watched, k,
+                      out_idx, out_p, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int anirec_predict_topk_large_act(const float *U, const float *A, int32_t n_anime, const int32_t *users,
@@ -1422,53 +1284,8 @@ int anirec_predict_topk_large_w(const float *U, const float *A, int32_t dim, int
     return ANIREC_EINVAL;
   if (n_anime < 1 || n_users < 0 || k < 1) return ANIREC_EINVAL;
   if (n_users == 0) return ANIREC_OK;
-  const size_t fixed = norm_bytes(n_anime, n_users, dim) + kLkHistBytes + kLkCntBytes;
-  const size_t pq = lk_per_query(n_anime, k);
-  if (workspace_bytes < fixed + pq) return ANIREC_EWORKSPACE;
-  size_t qb = (workspace_bytes - fixed) / pq;
-  if (qb > (size_t)n_users) qb = n_users;
-  hipStream_t s = (hipStream_t)stream;
-  float *Ah = (float *)workspace;
-  float *Uh = Ah + (size_t)n_anime * dim;
-  LkArgs la;
-  float *buf = lk_carve(la, (char *)(Uh + (size_t)n_users * dim), n_anime, k, qb);
-  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
-  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
-  ANIREC_HIP_CHECK(hipGetLastError());
-  const int wwords = (n_anime + 31) / 32;
-  float hs, hb;
-  head_affine(head, &hs, &hb);
-  for (size_t q0 = 0; q0 < (size_t)n_users; q0 += qb) {
-    const int cnt = (int)((size_t)n_users - q0 < qb ? (size_t)n_users - q0 : qb);
-    ScoreArgs a;
-    a.Q = Uh + q0 * dim;
-    a.qrows = nullptr;
-    a.nq = cnt;
-    a.W = Ah;
-    a.n = n_anime;
-    a.out = buf;
-    a.ld = (size_t)n_anime;
-    a.use_head = 1;
-    a.hs = hs;
-    a.hb = hb;
-    int e = launch_scores(a, s, activation, dim);
-    if (e) return e;
-    SelectArgs &sa = la.s;
-    sa.scores = buf;
-    sa.ld = (size_t)n_anime;
-    sa.n = n_anime;
-    sa.nq = cnt;
-    sa.k = k;
-    sa.self = nullptr;
-    sa.keep = nullptr;
-    sa.wbits = watched ? watched + q0 * wwords : nullptr;
-    sa.wwords = wwords;
-    sa.out_idx = out_idx + q0 * k;
-    sa.out_score = out_p + q0 * k;
-    e = lk_run(la, s);
-    if (e) return e;
-  }
-  return ANIREC_OK;
+  return predict_topk(lk_layout(n_anime, k), U, A, dim, n_anime, users, n_users, head, activation, watched, k,
+                      out_idx, out_p, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1714,15 +1531,12 @@ int anirec_predict_rank(const float *U, const float *A, int32_t dim, int32_t n_a
     return ANIREC_EINVAL;
   if (workspace_bytes < norm_bytes(n_anime, n_users, dim)) return ANIREC_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  float *Ah = (float *)workspace;
-  float *Uh = Ah + (size_t)n_anime * dim;
   ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
-  launch_rownorm<1>(A, nullptr, n_anime, Ah, dim, s);
-  launch_rownorm<1>(U, users, n_users, Uh, dim, s);
-  ANIREC_HIP_CHECK(hipGetLastError());
+  NormRows t;
+  ANIREC_HIP_CHECK(normalise_tables(U, A, dim, n_anime, users, n_users, workspace, s, &t));
   RankArgs a;
-  a.Uh = Uh;
-  a.Ah = Ah;
+  a.Uh = t.Uh;
+  a.Ah = t.Ah;
   a.n_users = n_users;
   a.n_anime = n_anime;
   a.trow = target_row;

@@ -218,6 +218,163 @@ def test_predict_topk_rejects_k_below_one():
         ops.predict_topk(torch.from_numpy(U).cuda(), torch.from_numpy(A).cuda(), PRED_HEADS["linear"], [0], 0)
 
 
+# ---- the batch loop, the merge pass and the slicing boundary of the four exact entry points -------------------------
+EWORKSPACE = -3
+
+
+def _cosine_w(lib, large, Wh, q, k, keep, ws_bytes):
+    """anirec_cosine_topk_w / anirec_cosine_topk_large_w on a workspace of exactly ws_bytes: status, idx, scores"""
+    from anime_recommendations_amd import _lib
+    dev, (n, dim), nq = Wh.device, Wh.shape, len(q)
+    qt = torch.as_tensor(q, dtype=torch.int32, device=dev)
+    kt = None if keep is None else torch.as_tensor(keep, dtype=torch.uint8, device=dev)
+    oi = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    os_ = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    fn = lib.anirec_cosine_topk_large_w if large else lib.anirec_cosine_topk_w
+    st = fn(_lib.ptr(Wh), n, dim, _lib.ptr(qt), nq, _lib.ptr(kt), 1, k, _lib.ptr(oi), _lib.ptr(os_), _lib.ptr(ws),
+            ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return st, oi, os_
+
+
+def _predict_w(lib, large, tU, tA, head, users, bits, k, ws_bytes):
+    """anirec_predict_topk_w / anirec_predict_topk_large_w on a workspace of exactly ws_bytes: status, idx, ratings"""
+    from anime_recommendations_amd import _lib, ops
+    dev, (n, dim), nq = tU.device, tA.shape, len(users)
+    us = torch.as_tensor(users, dtype=torch.int32, device=dev)
+    wb = torch.as_tensor(bits.view(np.int32), device=dev)
+    oi = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    op = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    h = ops._head_struct(head)
+    fn = lib.anirec_predict_topk_large_w if large else lib.anirec_predict_topk_w
+    st = fn(_lib.ptr(tU), _lib.ptr(tA), dim, n, _lib.ptr(us), nq, C.byref(h), ops._head_act(head), _lib.ptr(wb), k,
+            _lib.ptr(oi), _lib.ptr(op), _lib.ptr(ws), ws_bytes, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    return st, oi, op
+
+
+def _bit_rows(w):
+    bits = np.zeros((w.shape[0], (w.shape[1] + 31) // 32), np.uint32)
+    for r in range(w.shape[0]):
+        nz = np.nonzero(w[r])[0]
+        np.bitwise_or.at(bits[r], nz >> 5, np.uint32(1) << (nz & 31).astype(np.uint32))
+    return bits
+
+
+@pytest.mark.parametrize("width", [128, 32])
+@pytest.mark.parametrize("n", [300, 4100])                 # one workgroup per query; two slices and the merge pass
+def test_batch_loop_gives_the_same_lists_on_the_smallest_workspace(n, width):
+    """The four _w entry points with nq = 5, once on the workspace of their size function (one batch) and once on the
+    smallest they take (fixed part + one query: five trips through the batch loop, the masks and outputs advancing with
+    the batch): the same lists and score bits, the oracle's; one byte less is refused."""
+    from anime_recommendations_amd import _lib, ops
+    lib = _lib.load()
+    nq = 5
+    rng = np.random.default_rng(n + width)
+    W = rng.standard_normal((n, width)).astype(np.float32)
+    W[[11, n // 2, n - 1]] = W[3]                          # ties, across the slice boundary at 4100
+    Wh = ops.rownorm(torch.from_numpy(W))
+    q = np.array([3, n - 1, 17, n // 2 + 1, 200], np.int32)
+    keep = rng.random(n) < 0.8
+    rows = [ops.cosine_scores(Wh, int(x)).cpu().numpy() for x in q]
+    # nq = 1 and nq = 5 have the same 256-byte self[] head: the smallest workspace is the size of a one-query call
+    for large, k, full, least in ((False, 7, lib.anirec_topk_workspace_bytes(n, nq),
+                                   lib.anirec_topk_workspace_bytes(n, 1)),
+                                  (True, 7, lib.anirec_topk_large_workspace_bytes(n, nq, 7),
+                                   lib.anirec_topk_large_workspace_bytes(n, 1, 7)),
+                                  (True, 200, lib.anirec_topk_large_workspace_bytes(n, nq, 200),
+                                   lib.anirec_topk_large_workspace_bytes(n, 1, 200))):
+        orders = [orc.topk_desc(s, k, exclude=int(x), mask=keep) for s, x in zip(rows, q)]
+        assert least < full
+        for nb in (full, least):
+            st, gi, gs = _cosine_w(lib, large, Wh, q, k, keep, int(nb))
+            assert st == 0, (large, k, nb)
+            _check(gi, gs, orders, k, ("cosine", n, width, large, k, nb == least))
+        assert _cosine_w(lib, large, Wh, q, k, keep, int(least) - 1)[0] == EWORKSPACE
+
+    head = dict(PRED_HEADS["tanh"], activation="tanh")
+    tU = torch.from_numpy(rng.standard_normal((40, width)).astype(np.float32)).cuda()
+    A = rng.standard_normal((n, width)).astype(np.float32)
+    A[[11, n // 2, n - 1]] = A[3]
+    tA = torch.from_numpy(A).cuda()
+    users = np.array([7, 0, 39, 21, 8], np.int32)
+    w = rng.random((nq, n)) < 0.3
+    bits = _bit_rows(w)
+    grid = ops.predict_grid(tU, tA, head, users).cpu().numpy()
+    # the head of a predict workspace holds a normalised row per user of the call: four more than a one-user call
+    more = 4 * width * 4
+    for large, k, full, least in ((False, 7, lib.anirec_predict_workspace_bytes_w(n, nq, 1, width),
+                                   lib.anirec_predict_workspace_bytes_w(n, 1, 1, width) + more),
+                                  (True, 7, lib.anirec_predict_topk_large_workspace_bytes_w(n, nq, 7, width),
+                                   lib.anirec_predict_topk_large_workspace_bytes_w(n, 1, 7, width) + more),
+                                  (True, 200, lib.anirec_predict_topk_large_workspace_bytes_w(n, nq, 200, width),
+                                   lib.anirec_predict_topk_large_workspace_bytes_w(n, 1, 200, width) + more)):
+        orders = [orc.topk_desc(grid[r], k, mask=~w[r]) for r in range(nq)]
+        assert least < full
+        for nb in (full, least):
+            st, gi, gp = _predict_w(lib, large, tU, tA, head, users, bits, k, int(nb))
+            assert st == 0, (large, k, nb)
+            _check(gi, gp, orders, k, ("predict", n, width, large, k, nb == least))
+        assert _predict_w(lib, large, tU, tA, head, users, bits, k, int(least) - 1)[0] == EWORKSPACE
+
+
+def test_short_slice_goes_through_the_merge_pass():
+    """n = 4100, one query, k = 128: two slices of 2050 keys.  The second slice holds 50 candidates (fewer than k: its
+    winners list is short and padded), two of them copies of a row of the first slice, so equal scores meet in the merge
+    pass.  With 60 candidates in all the merged row is shorter than k: -1 / NaN from column 60 on."""
+    from anime_recommendations_amd import ops
+    n, k, half = 4100, 128, 2050
+    rng = np.random.default_rng(41)
+    W = rng.standard_normal((n, 128)).astype(np.float32)
+    second = half + rng.choice(half, 50, replace=False)
+    copies = np.sort(second[:2])
+    W[copies] = W[100]                                      # row 100 is in the first slice and is kept below
+    W[9] = W[100] + 0.05 * rng.standard_normal(128).astype(np.float32)   # a query whose list starts with the three
+    Wh = ops.rownorm(torch.from_numpy(W))
+    first10 = np.array([100, 5, 77, 640, 1200, 1999, 2000, 2047, 2048, 2049])
+    for first in (np.arange(half), first10):                # 2050 + 50 candidates; 10 + 50
+        keep = np.zeros(n, bool)
+        keep[first] = True
+        keep[second] = True
+        for q in (100, 9):                                  # the copies tie with each other; with row 100 itself too
+            row = ops.cosine_scores(Wh, q).cpu().numpy()
+            order = orc.topk_desc(row, k, exclude=q, mask=keep)
+            m = int(keep.sum()) - int(keep[q])
+            assert len(order[0]) == min(k, m)
+            tied = ([100] if q == 9 else []) + copies.tolist()          # equal scores from both slices lead the list
+            assert order[0][:len(tied)].tolist() == tied
+            gi, gs = ops.cosine_topk(Wh, [q], k, keep=keep)
+            _check(gi, gs, [order], k, ("short slice", len(first), q))
+            if m < k:
+                assert (gi.cpu().numpy()[0, m:] == -1).all() and (_bits(gs.cpu().numpy())[0, m:] == NAN_BITS).all()
+
+
+def test_slicing_boundary_both_sides_equal_the_oracle():
+    """The select is sliced for nq < 1024 and n >= 4096: n = 4095 | 4096 at nq = 1 and nq = 1023 | 1024 at n = 4096,
+    k = 10.  Each side equals the oracle, and the any-k entry point at the same shape equals the <= 128 one."""
+    from anime_recommendations_amd import _lib, ops
+    lib = _lib.load()
+    k = 10
+    W, dup, zero = _table(4096, seed=12)
+    keep = np.random.default_rng(6).random(4096) < 0.9
+    for n in (4095, 4096):
+        Wh = ops.rownorm(torch.from_numpy(W[:n]))
+        q = np.array([7], np.int32)
+        order = orc.topk_desc(ops.cosine_scores(Wh, 7).cpu().numpy(), k, exclude=7, mask=keep[:n])
+        gi, gs = ops.cosine_topk(Wh, q, k, keep=keep[:n])
+        _check(gi, gs, [order], k, ("boundary n", n))
+        li, ls = _large_cosine(lib, Wh, q, k, keep=keep[:n])
+        assert torch.equal(li, gi) and np.array_equal(_bits(ls.cpu()), _bits(gs.cpu())), n
+    Wh = ops.rownorm(torch.from_numpy(W))
+    q = _queries(4096, 1024, dup, zero, seed=3)
+    orders = [orc.topk_desc(ops.cosine_scores(Wh, int(x)).cpu().numpy(), k, exclude=int(x), mask=keep) for x in q]
+    for nq in (1023, 1024):
+        gi, gs = ops.cosine_topk(Wh, q[:nq], k, keep=keep)
+        _check(gi, gs, orders[:nq], k, ("boundary nq", nq))
+        li, ls = _large_cosine(lib, Wh, q[:nq], k, keep=keep)
+        assert torch.equal(li, gi) and np.array_equal(_bits(ls.cpu()), _bits(gs.cpu())), nq
+
+
 # ---- sharded: world 1 and gloo world 2 sharing one GPU --------------------------------------------------------------
 def _port():
     s = socket.socket()

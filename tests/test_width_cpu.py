@@ -1,6 +1,7 @@
 """CPU tests of --embedding_size: the width check of trainer.fit (before the engine is touched), the refusals of the
 multi-GPU engine and of an engine built for another width, weights files of another width, and the _w twins of the C
 ABI (declared, exported, bound, refusing a bad width without a GPU)."""
+import json
 import os
 import subprocess
 
@@ -218,6 +219,32 @@ def test_twins_are_exported_bound_and_refuse_a_bad_width_without_a_gpu():
         assert lib.anirec_train_fwd_w(None, bad, None) == -1
         assert lib.anirec_trainer_create_w(None, bad, None) == -1
         assert lib.anirec_eval_metrics_w(None, bad, 0, None, None, None, None, 0, None) == -1
+
+
+def test_topk_workspace_sizes_keep_their_recorded_values():
+    """The four workspace size functions of the exact top-k, value for value against tests/golden/
+    topk_workspace_bytes.json (make_topk_workspace_bytes.py, written from the build before the entry points came to
+    share one layout description): n, nq and k on both sides of every cap, the 4 GiB halving of a batch, the widths,
+    and the invalid arguments that give 0."""
+    from anime_recommendations_amd import build
+    build.build(verbose=False)
+    lib = _lib.load()
+    with open(os.path.join(ROOT, "tests", "golden", "topk_workspace_bytes.json")) as f:
+        rec = json.load(f)
+    assert sorted(rec) == ["anirec_predict_topk_large_workspace_bytes_w", "anirec_predict_workspace_bytes_w",
+                           "anirec_topk_large_workspace_bytes", "anirec_topk_workspace_bytes"]
+    assert sum(len(v) for v in rec.values()) == 1122
+    for name, rows in rec.items():
+        fn = getattr(lib, name)
+        for args, want in rows:
+            assert fn(*args) == want, (name, args)
+    # the grid does reach the halving (a 1024-query batch of 350 000-key rows is 1.3 GiB: 4096 users halve, 1024
+    # queries do not) and the zeros
+    small = dict((tuple(a), v) for a, v in rec["anirec_topk_workspace_bytes"])
+    large = dict((tuple(a), v) for a, v in rec["anirec_predict_topk_large_workspace_bytes_w"])
+    assert small[(350_000, 4096)] == 4096 * 4 + 2048 * 128 * 8 + 1024 * 350_000 * 4
+    assert large[(350_000, 4096, 1, 128)] < 4096 * 350_000 * 4 < 2 * large[(350_000, 4096, 1, 128)]
+    assert small[(0, 5)] == 0 and large[(300, 5, 10, 48)] == 0 and large[(300, 5, 0, 128)] == 0
 
 
 def test_python_mirror_of_the_workspace_follows_the_width():
