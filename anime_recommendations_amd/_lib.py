@@ -223,6 +223,8 @@ PROTOTYPES = {
     # greedy MMR re-rank of candidate lists (diversified recommendations)
     "anirec_mmr_max_cand": (_sz, [_i32]),
     "anirec_mmr_rerank": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # pairwise similarity structure of many lists (list evaluation)
+    "anirec_list_similarity": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -515,6 +515,21 @@ def held_out_targets(table, test_size, min_rating):
     return recs.held_out_targets(table, test_size, min_rating)
 
 
+def _tables_of(model, table):
+    """(U, A) of ``model`` as arrays, or a ValueError when its id tables are not the rating table's."""
+    U, A = np.asarray(model["U"]), np.asarray(model["A"])
+    mu, ma = model.get("user_ids"), model.get("anime_ids")
+    same = U.shape[0] == table.n_users and A.shape[0] == table.n_anime
+    if same and mu is not None and ma is not None:
+        same = np.array_equal(np.asarray(mu), np.asarray(table.user_ids)) and \
+            np.array_equal(np.asarray(ma), np.asarray(table.anime_ids))
+    if not same:
+        raise ValueError("the model's id tables are not the rating table's: the model holds %d users x %d anime, the "
+                         "table %d users x %d anime (evaluate a model on the data artifact it was trained on)"
+                         % (U.shape[0], A.shape[0], table.n_users, table.n_anime))
+    return U, A
+
+
 BASELINES = ("popularity",)
 
 
@@ -532,16 +547,7 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     from . import ops, recs, weights_io
     if baseline is not None and baseline not in BASELINES:
         raise ValueError("baseline %r is not supported (supported: %s, or None)" % (baseline, ", ".join(BASELINES)))
-    U, A = np.asarray(model["U"]), np.asarray(model["A"])
-    mu, ma = model.get("user_ids"), model.get("anime_ids")
-    same = U.shape[0] == table.n_users and A.shape[0] == table.n_anime
-    if same and mu is not None and ma is not None:
-        same = np.array_equal(np.asarray(mu), np.asarray(table.user_ids)) and \
-            np.array_equal(np.asarray(ma), np.asarray(table.anime_ids))
-    if not same:
-        raise ValueError("the model's id tables are not the rating table's: the model holds %d users x %d anime, the "
-                         "table %d users x %d anime (evaluate a model on the data artifact it was trained on)"
-                         % (U.shape[0], A.shape[0], table.n_users, table.n_anime))
+    U, A = _tables_of(model, table)
     ks = sorted({int(k) for k in ks})
     if not ks or ks[0] < 1:
         raise ValueError("eval_k must list at least one k >= 1 (got %r)" % (ks,))
@@ -571,6 +577,50 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         for k in ks:
             summary["popularity_hit_rate@%d" % k] = b["hit_rate"][k]
             summary["popularity_ndcg@%d" % k] = b["ndcg"][k]
+    return frame, summary
+
+
+LISTS_COLUMNS = ["diversity", "k", "pool", "hit_rate", "ndcg", "mrr", "mean_similarity", "mean_max_similarity",
+                 "coverage", "gini", "novelty"]
+
+
+def evaluate_lists_frame(model, table, test_size, min_rating, diversities, k=10, pool=100):
+    """What ``diverse_recs --diversity`` costs in hits and buys in spread: for each value d of
+    ``diversities`` every user with a held-out rating at or above ``min_rating`` gets the list
+    ``recs.diverse_topk(..., k, pool, d)`` under evaluate_frame's mask (the anime the user has a TRAINING rating for), and
+    ``recs.list_quality`` scores all lists at once: the held-out anime's place in its user's list (hit_rate, ndcg, mrr)
+    beside the lists' own figures (mean_similarity, mean_max_similarity, coverage, gini, and novelty against the training
+    slice's rating counts).  The users, the targets and the mask are evaluate_frame's, so the d = 0 row's hit_rate and ndcg
+    are its hit_rate@k and ndcg@k.  Returns (frame with one row per d and the columns LISTS_COLUMNS; summary dict with the
+    keys ``lists_<column>@<d>``).  ValueError for id tables that are not the table's, a d outside [0, 1], k < 1 or
+    pool < k, before any GPU use."""
+    import torch
+    from . import ops, recs, weights_io
+    U, A = _tables_of(model, table)
+    ds = [float(d) for d in diversities]
+    if not ds or not all(0.0 <= d <= 1.0 for d in ds):      # (a NaN fails both comparisons)
+        raise ValueError("lists_diversity must list at least one diversity in [0, 1] (got %r)" % (list(diversities),))
+    k, pool = int(k), int(pool)
+    if k < 1:
+        raise ValueError("lists_k must be >= 1 (got %d)" % k)
+    if pool < k:
+        raise ValueError("lists_pool = %d is smaller than lists_k = %d" % (pool, k))
+    users, row, anime, train = held_out_targets(table, test_size, min_rating)
+    rows = []
+    if len(row):
+        tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
+        head = weights_io.model_head(model)
+        seen = recs.listed_seen_bits(table.user[train], table.anime[train], users, table.n_users, table.n_anime)
+        count = recs.popularity_scores(table.anime[train], table.n_anime, table.n_users)
+        Wh = ops.rownorm(tA, device=tA.device)
+        for d in ds:
+            idx, _, _ = recs.diverse_topk(tU, tA, head, users, k, pool, d, seen)
+            rows.append(recs.list_quality(Wh, idx, k, row, anime, item_count=count, n_raters=table.n_users))
+    else:
+        rows = [dict.fromkeys(LISTS_COLUMNS[3:], float("nan")) for _ in ds]
+    frame = pd.DataFrame([dict({"diversity": d, "k": k, "pool": pool}, **{c: q[c] for c in LISTS_COLUMNS[3:]})
+                          for d, q in zip(ds, rows)], columns=LISTS_COLUMNS)
+    summary = {"lists_%s@%g" % (c, d): q[c] for d, q in zip(ds, rows) for c in LISTS_COLUMNS[3:]}
     return frame, summary
 
 

@@ -578,6 +578,47 @@ def mmr_rerank(What, cand_idx, cand_score, k, lam):
     return idx, pos, score, pen
 
 
+def check_list_similarity(width, k):
+    """The argument checks of ``list_similarity`` (no device needed): ValueError naming the limit for a list shorter than
+    one slot or longer than anirec_mmr_max_cand(width).  Returns (width, k)."""
+    dim, k = _lib.check_width(width), int(k)
+    if not 1 <= k <= _lib.mmr_max_cand(dim):
+        raise ValueError("list_similarity: %d slots per list, 1 .. %d at width %d (a list's rows are held in LDS: %d "
+                         "floats)" % (k, _lib.mmr_max_cand(dim), dim, _lib.MMR_IMAGE_FLOATS))
+    return dim, k
+
+
+def list_similarity(What, list_idx):
+    """The pairwise similarity structure of many lists (anirec_list_similarity): list l holds the rows ``list_idx[l]``
+    of ``What`` (``rownorm`` output; -1 = an empty slot), as ``predict_topk`` and ``mmr_rerank`` write them.  Returns
+    (sim_max fp32, sim_sum fp32), each [n_lists, k] on the device: for a present slot the largest cosine to (``mmr_rerank``'s
+    pen rule) and the sequential fp32 sum of the cosines to the present slots before it, 0 for the first; NaN for an
+    empty slot.  The width comes from ``What.shape[1]``.  Raises ValueError for a ``list_idx`` that is not
+    [n_lists, k], k outside 1 .. anirec_mmr_max_cand(width), or an index that is no row of ``What``."""
+    if What.dim() != 2 or list_idx.dim() != 2:
+        raise ValueError("list_similarity: What must be [n_rows, width] and list_idx [n_lists, k]")
+    dim, k = check_list_similarity(What.shape[1], list_idx.shape[1])
+    if What.shape[0] < 1:
+        raise ValueError("list_similarity: What has no rows")
+    _need_gpu()
+    lib = _lib.load()
+    assert _width(What) == dim
+    dev = What.device
+    li = _i32(list_idx, dev)
+    n_lists = int(li.shape[0])
+    sim_max = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    sim_sum = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    if n_lists == 0:
+        return sim_max, sim_sum
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.anirec_list_similarity(_lib.ptr(What), dim, What.shape[0], _lib.ptr(li), n_lists, k,
+                                          _lib.ptr(sim_max), _lib.ptr(sim_sum), _lib.ptr(err), _stream()),
+               "anirec_list_similarity")
+    if int(err.item()):
+        raise ValueError("list_similarity: list index out of range")
+    return sim_max, sim_sum
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

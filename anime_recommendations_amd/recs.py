@@ -234,6 +234,126 @@ def diverse_topk(U, A, head, users, k, pool, diversity, watched_bits=None):
     return idx, score, pen
 
 
+def gini(counts):
+    """Gini coefficient of non-negative counts, float64 on the host: with the n counts sorted ascending,
+    sum_i (2 i - n - 1) c_i / (n sum c), i 1-based — 0 for equal counts, (n - 1) / n when one holds everything.  NaN for
+    no counts or an all-zero vector."""
+    c = np.sort(np.asarray(counts, np.float64).reshape(-1))
+    n, total = c.size, float(c.sum()) if c.size else 0.0
+    if n == 0 or total == 0.0:
+        return float("nan")
+    return float(((2.0 * np.arange(1, n + 1) - n - 1.0) * c).sum() / (n * total))
+
+
+def hit_positions(lists, target_row, target_anime):
+    """Where each target is in its list: int64 [n_t] on the host, the lowest slot of ``lists[target_row[t]]`` that holds
+    ``target_anime[t]``, -1 where none does.  ``lists``: an int [n_lists, k] tensor; the compare runs where it lives."""
+    dev = lists.device
+    tr = torch.as_tensor(np.asarray(_host(target_row), np.int64), device=dev).reshape(-1)
+    ta = torch.as_tensor(np.asarray(_host(target_anime), np.int64), device=dev).reshape(-1)
+    if tr.shape != ta.shape:
+        raise ValueError("hit_positions: target_row and target_anime must have one length")
+    if tr.numel() == 0:
+        return np.zeros(0, np.int64)
+    if int(tr.min()) < 0 or int(tr.max()) >= int(lists.shape[0]):
+        raise ValueError("hit_positions: target_row out of range")
+    if int(ta.min()) < 0:
+        raise ValueError("hit_positions: target_anime out of range")
+    k = int(lists.shape[1])
+    pos = torch.full((tr.numel(),), -1, dtype=torch.int64, device=dev)
+    for t0 in range(0, int(tr.numel()), 1 << 22):             # (bounds the [n_t, k] compare)
+        t = slice(t0, t0 + (1 << 22))
+        hit = lists[tr[t]].to(torch.int64) == ta[t].unsqueeze(1)
+        slot = torch.where(hit, torch.arange(k, device=dev).expand_as(hit), torch.full_like(hit, k, dtype=torch.int64))
+        first = slot.min(dim=1).values
+        pos[t] = torch.where(first < k, first, torch.full_like(first, -1))
+    return pos.cpu().numpy()
+
+
+LIST_FIGURES = ("mean_similarity", "mean_max_similarity", "coverage", "gini", "novelty")
+HIT_FIGURES = ("hit_rate", "ndcg", "mrr")
+
+
+def list_figures(idx, n_rows, sim_max, sim_sum, target_row=None, target_anime=None, item_count=None, n_raters=None):
+    """``list_quality``'s figures from lists and their similarity structure, wherever the tensors live (no kernel):
+    ``idx`` int [n_lists, k] (-1 = an empty slot), ``sim_max`` / ``sim_sum`` fp32 [n_lists, k] as
+    ``ops.list_similarity`` writes them, ``n_rows`` the rows of the table the lists index."""
+    if (target_row is None) != (target_anime is None):
+        raise ValueError("list_quality: target_row and target_anime come together")
+    if item_count is not None and n_raters is None:
+        raise ValueError("list_quality: item_count needs n_raters")
+    n_rows, n_lists = int(n_rows), int(idx.shape[0])
+    nan = float("nan")
+    out = {"n_lists": n_lists, "mean_similarity": nan, "mean_max_similarity": nan, "coverage": nan, "gini": nan}
+    if item_count is not None:
+        out["novelty"] = nan
+    if target_row is not None:
+        out.update({"n_targets": int(np.asarray(_host(target_row)).size), "hit_rate": nan, "ndcg": nan, "mrr": nan})
+    if n_lists == 0:
+        if out.get("n_targets"):
+            raise ValueError("hit_positions: target_row out of range")
+        return out
+    present = idx >= 0
+    p = present.sum(dim=1).to(torch.float64)
+    pairs = p >= 2
+    if bool(pairs.any()):
+        zero = torch.zeros((), dtype=torch.float64, device=idx.device)
+        tot_sum = torch.where(present, sim_sum.to(torch.float64), zero).sum(dim=1)[pairs]
+        tot_max = torch.where(present, sim_max.to(torch.float64), zero).sum(dim=1)[pairs]    # (the first one's is 0)
+        pp = p[pairs]
+        out["mean_similarity"] = float((tot_sum / (pp * (pp - 1.0) / 2.0)).mean())
+        out["mean_max_similarity"] = float((tot_max / (pp - 1.0)).mean())
+    listed = idx[present].to(torch.int64)
+    exposure = torch.bincount(listed, minlength=n_rows)
+    out["coverage"] = float(int((exposure > 0).sum())) / n_rows
+    out["gini"] = gini(exposure.cpu().numpy())
+    if item_count is not None:
+        cnt = torch.as_tensor(_host(item_count) if not isinstance(item_count, torch.Tensor) else item_count,
+                              device=idx.device).to(torch.float64).reshape(-1)
+        if cnt.numel() != n_rows:
+            raise ValueError("list_quality: item_count must hold one count per row of What")
+        if listed.numel():
+            out["novelty"] = float((-torch.log2((cnt[listed] + 1.0) / (float(n_raters) + 1.0))).mean())
+    if target_row is not None:
+        pos = hit_positions(idx, target_row, target_anime)
+        if pos.size:
+            found = pos >= 0
+            r = np.where(found, pos, 0).astype(np.float64)
+            out["hit_rate"] = float(np.mean(found))
+            out["ndcg"] = float(np.mean(np.where(found, 1.0 / np.log2(r + 2.0), 0.0)))
+            out["mrr"] = float(np.mean(np.where(found, 1.0 / (r + 1.0), 0.0)))
+    return out
+
+
+def list_quality(What, lists, k=None, target_row=None, target_anime=None, item_count=None, n_raters=None):
+    """Figures of many top-k lists at once, over the first ``k`` columns of ``lists`` (all of them when
+    None): int [n_lists, K] rows of the normalised table ``What`` (``ops.rownorm`` output, on the device), -1 = an empty
+    slot, as ``ops.predict_topk`` / ``diverse_topk`` write them.  Every figure is float64; p = a list's present slots.
+        mean_similarity      mean over the lists with p >= 2 of (sum of ``ops.list_similarity``'s sim_sum) / (p (p - 1) / 2):
+                             the list's mean pairwise cosine
+        mean_max_similarity  mean over the same lists of the mean of sim_max over the present slots after the first
+        coverage             distinct listed rows / n_rows
+        gini                 ``gini`` of the rows' exposure counts over all n_rows (NaN when nothing is listed)
+        novelty              mean over the present slots of -log2((item_count[a] + 1) / (n_raters + 1)); with
+                             ``item_count`` ([n_rows] rating counts, ``popularity_scores``) and ``n_raters`` only
+        hit_rate, ndcg, mrr  with targets (``target_row[t]``: a list, ``target_anime[t]``: a row of What): pos = the
+                             target's lowest slot in its list; mean of [found], of 1 / log2(pos + 2) and of 1 / (pos + 1),
+                             0 where it is not found
+        n_lists, n_targets
+    An empty input gives NaN.  Only the similarities run a kernel (``ops.list_similarity``); exposure, novelty and hit
+    positions are plain torch (``list_figures``)."""
+    from . import ops
+    if lists.dim() != 2:
+        raise ValueError("list_quality: lists must be [n_lists, k]")
+    k = int(lists.shape[1]) if k is None else int(k)
+    if not 1 <= k <= int(lists.shape[1]):
+        raise ValueError("list_quality: k = %d must be in 1 .. %d (the columns of lists)" % (k, int(lists.shape[1])))
+    ops.check_list_similarity(What.shape[1], k)
+    idx = lists[:, :k].to(device=What.device, dtype=torch.int32).contiguous()
+    sims = ops.list_similarity(What, idx) if idx.shape[0] else (None, None)
+    return list_figures(idx, What.shape[0], sims[0], sims[1], target_row, target_anime, item_count, n_raters)
+
+
 FOLD_STEPS = 100        # Adam iterations of a fold-in (DESIGN.md §4.7)
 FOLD_LR = 0.01          # and their learning rate
 

@@ -3,8 +3,10 @@
 (the last ``test_size`` rows of the same encoding and RandomState(42) shuffle) are ranked among the anime their user
 has no training rating for, by predicted rating, and hit rate / NDCG at each ``eval_k``, MRR and the mean and median
 rank are written to ``eval_csv``; ``--baseline popularity`` adds the same figures for ranking by rating count alone, to
-read the model's against.  The reference has no such step: its author lists comparing re-trained models as
-an idea for improvement; ``val_loss`` cannot compare models across losses and activations, these figures can."""
+read the model's against; ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity
+costs in hits and buys in spread, over every held-out user's top ``lists_k`` list.  The reference has no such step:
+its author lists comparing re-trained models as an idea for improvement; ``val_loss`` cannot compare models across
+losses and activations, these figures can."""
 import json
 import os
 import sys
@@ -16,6 +18,14 @@ from anime_recommendations_amd import artifacts, components as C  # noqa: E402
 STR_FLAGS = ["input_data", "main_df_type", "model", "model_type", "project_name", "test_size", "eval_k", "min_rating",
              "eval_csv", "eval_type", "ID_emb_name", "anime_emb_name"]
 BOOL_FLAGS = []
+# optional: the accuracy / diversity trade-off of the model's top-k lists (components.evaluate_lists_frame)
+OPTIONAL_FLAGS = {
+    "lists_diversity": (str, "none", "none, or a list of diverse_recs --diversity values, e.g. \"[0, 0.1, 0.3, 0.5]\": "
+                                     "hit rate and spread of every held-out user's top list at each value"),
+    "lists_k": (int, 10, "the length of those lists"),
+    "lists_pool": (int, 100, "the candidates the re-rank picks from (diverse_recs --pool)"),
+    "lists_csv": (str, "eval_lists.csv", "the file the list figures are written to, logged as an eval_type artifact"),
+}
 
 logger = C.setup_logging("evaluate")
 
@@ -35,16 +45,32 @@ def go(args):
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
                            metadata={k: v for k, v in summary.items()})
     logger.info("Ranking metrics: %s", summary)
+    if args.lists_diversity.lower() != "none":
+        lists, lists_summary = C.evaluate_lists_frame(model, table, int(args.test_size), float(args.min_rating),
+                                                      C.literal(args.lists_diversity), int(args.lists_k),
+                                                      int(args.lists_pool))
+        lists.to_csv(args.lists_csv, index=False)
+        artifacts.log_artifact(args.lists_csv, args.lists_csv, args.eval_type,
+                               "Hits and spread of the top-%d lists per diversity for model : %s"
+                               % (int(args.lists_k), args.model), metadata=dict(lists_summary))
+        logger.info("List metrics: %s", lists_summary)
+        summary = dict(summary, **lists_summary)
     print(json.dumps(summary))
     return frame, summary
 
 
-if __name__ == "__main__":
-    _parser = C.make_parser("Rank the held-out ratings with a trained model", STR_FLAGS, BOOL_FLAGS)
+def make_parser():
+    parser = C.make_parser("Rank the held-out ratings with a trained model", STR_FLAGS, BOOL_FLAGS)
     # optional, unlike the flags above: "popularity" adds the figures of recommending the most-rated unseen anime
-    _parser.add_argument("--baseline", type=str, default="none", required=False,
-                         help="none, or popularity: rank the same targets by the anime's number of training ratings")
-    _args = _parser.parse_args()
+    parser.add_argument("--baseline", type=str, default="none", required=False,
+                        help="none, or popularity: rank the same targets by the anime's number of training ratings")
+    for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
+        parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
+    return parser
+
+
+if __name__ == "__main__":
+    _args = make_parser().parse_args()
     try:
         go(_args)
     except Exception:                      # non-zero exit + the reason in ./evaluate.log

@@ -751,6 +751,32 @@ int anirec_mmr_rerank(const float *What, int32_t dim, int32_t n_rows, const int3
                       int32_t n_lists, int32_t n_cand, int32_t k, float lambda, int32_t *out_idx, int32_t *out_pos,
                       float *out_score, float *out_pen, int32_t *err_flag, void *stream);
 
+/* LIST EVALUATION — the pairwise similarity structure of many lists at once: what a re-ranked list (anirec_mmr_rerank)
+ * buys is a property of the list itself, how alike its rows are.  What [n_rows][dim] = the unit rows anirec_rownorm_w
+ * writes; list_idx [n_lists][k] = rows of What, -1 = an empty slot: what anirec_predict_topk* and anirec_mmr_rerank
+ * write.  Both outputs are [n_lists][k] fp32.  All arithmetic is fp32 and nothing is contracted.
+ *     present  slot s is present when list_idx[l][s] != -1; an index that appears twice is two slots
+ *     sim(s,j) the k-ordered chain acc = fmaf(What[a_s][t], What[a_j][t], acc), t = 0 .. dim-1, from 0: the chain of
+ *              anirec_cosine_scores_w and anirec_mmr_rerank's sim, the same bits
+ *     a present slot s with the earlier present slots j1 < j2 < ... (ascending position):
+ *              out_sim_sum[l][s] = ((0 + sim(s,j1)) + sim(s,j2)) + ..., fp32 adds in that order
+ *              out_sim_max[l][s] = anirec_mmr_rerank's pen rule: sim(s,j1), then replaced by sim(s,j) for each later j
+ *                                  with sim(s,j) > the current value (a NaN replaces nothing)
+ *              both 0.0f with no earlier present slot
+ *     an absent slot: both are the NaN 0x7FC00000
+ * Rows with non-finite values are not special-cased: their NaN propagates by the rules above.  So for the out_idx of an
+ * anirec_mmr_rerank call out_sim_max holds that call's out_pen, bit for bit, padding included.
+ * A group of lanes per list (one wave for a short list, a workgroup beyond), the list's rows staged once in LDS (dim * k
+ * <= 32768 floats: k <= anirec_mmr_max_cand(dim)), the pairs of the triangle dealt evenly over the lanes.  No workspace,
+ * no atomics, stream-ordered and graph-capturable.  A list's outputs depend on that list alone.
+ * Bad dim, n_rows < 1, a negative count, k < 1, k > anirec_mmr_max_cand(dim), a NULL pointer with n_lists > 0:
+ * ANIREC_EINVAL before anything is enqueued or written.  n_lists == 0: ANIREC_OK, nothing enqueued.  Otherwise every
+ * element of both outputs and *err_flag (device) is written: *err_flag becomes 1 on an index below -1 or at or above
+ * n_rows (0 without one): that list's two output rows are all NaN, nothing is read through the bad index, the other
+ * lists are unaffected (anirec_predict_rank's convention). */
+int anirec_list_similarity(const float *What, int32_t dim, int32_t n_rows, const int32_t *list_idx, int32_t n_lists,
+                           int32_t k, float *out_sim_max, float *out_sim_sum, int32_t *err_flag, void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
