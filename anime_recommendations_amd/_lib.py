@@ -35,6 +35,11 @@ METRIC_MAE, METRIC_MAPE, METRIC_MSLE, METRIC_LOGCOSH, METRIC_BCE, METRIC_ACC, ME
 METRIC_KINDS = 6
 AUC_BINS = 200
 AUC_ONE = 1 << 20
+# anirec_group_topk: the aggregate over a group's members (ANIREC_GROUP_*) and the most members of one group
+GROUP_MEAN, GROUP_MIN, GROUP_MAX = 0, 1, 2
+GROUP_MODES = {"mean": GROUP_MEAN, "least_misery": GROUP_MIN, "min": GROUP_MIN, "most_pleasure": GROUP_MAX,
+               "max": GROUP_MAX}
+GROUP_MAX_MEMBERS = 64
 
 
 class AnirecError(RuntimeError):
@@ -225,6 +230,10 @@ PROTOTYPES = {
     "anirec_mmr_rerank": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     # pairwise similarity structure of many lists (list evaluation)
     "anirec_list_similarity": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
+    # one list per group of users: the aggregate of the members' ratings through the exact select
+    "anirec_group_topk_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "anirec_group_topk": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _vp, _i32, _i32,
+                                    _i32, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -398,6 +398,55 @@ def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
 
 
 # ----------------------------------------------------------------------------------------
+# group_recs: one list for several users who watch together
+# ----------------------------------------------------------------------------------------
+GROUP_STRATEGIES = ("mean", "least_misery", "most_pleasure")
+
+
+def group_label(members):
+    """The members of a group as a file name holds them: the ids joined by ``_``; above 8 members the first id and
+    how many more."""
+    members = [int(u) for u in members]
+    if len(members) > 8:
+        return "%d_and_%d_more" % (members[0], len(members) - 1)
+    return "_".join(str(u) for u in members)
+
+
+def group_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, members, n_recs, types=None, genres=None,
+                     strategy="mean", floor=None):
+    """model_recs_frame for a group (``ops.group_topk``): the candidates are the indexed anime no member
+    (``members``: user ids, a repeated id counts twice) has rated, under the same Type / Genre filters; they are ranked
+    by the ``strategy`` (``mean``, ``least_misery``, ``most_pleasure``) of the members' predicted ratings, and with
+    ``floor`` an anime any member rates below it is no candidate.  The frame has model_recs_frame's columns with
+    ``Prediction`` the aggregate, then ``Min_prediction``, ``Max_prediction`` and one ``User_<id>`` column per distinct
+    member: that member's own predicted rating.  A one-member group gives model_recs_frame's rows."""
+    import torch
+    from . import ops, recs
+    members = [int(u) for u in members]
+    if not members:
+        raise ValueError("group_recs: the group has no members")
+    users, offsets, member_row = recs.group_csr([members], user_ids)
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    uid = np.asarray(user_ids)
+    watched = np.concatenate([_blocked_bits(~unwatched_mask(df, anime_ids, uid[r])) for r in users])
+    exclude = _blocked_bits(~filter_mask(meta, anime_df, types, genres))
+    tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
+    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
+    idx, p, mp = ops.group_topk(tU, tA, head, users, offsets, member_row, k, mode=strategy, floor=floor,
+                                watched_bits=watched.view(np.int32), exclude_bits=exclude.view(np.int32),
+                                member_ratings=True)
+    idx, p, mp = idx.cpu().numpy()[0], p.cpu().numpy()[0], mp.cpu().numpy()
+    frame = _model_recs_rows(meta, idx, p)
+    ok = idx >= 0
+    frame["Min_prediction"] = mp[:, ok].min(axis=0)
+    frame["Max_prediction"] = mp[:, ok].max(axis=0)
+    for e, u in enumerate(members):
+        if "User_%d" % u not in frame.columns:
+            frame["User_%d" % u] = mp[e, ok]
+    return frame
+
+
+# ----------------------------------------------------------------------------------------
 # new_user_recs: users the model was not trained on
 # ----------------------------------------------------------------------------------------
 def _folded_position(folded, user_id):

@@ -1592,3 +1592,341 @@ int anirec_score_rank(const float *score, int32_t n_anime, const uint32_t *watch
 }
 
 }  // extern "C"
+
+// ====================================================================================
+// group recommendations (anirec_group_topk): a second feeder of the exact select
+//
+// One score row and one mask row per GROUP instead of per user, from one launch; the select (launch_select / lk_run)
+// then runs on them as on the rows of launch_scores.  The member ratings are predict_grid's, bit for bit: rows through
+// rownorm_body<1>, the k-ordered fma chain of scores_body in its 64 x 64 tile / 4 x 4 register block / pitch-132
+// geometry, rating_from_cosine.  No [members, n_anime] matrix exists.
+//   scores   a group holds m_pad = next_pow2(max_members) of a tile's 64 slots (64 / m_pad whole groups a tile: no
+//            group straddles one; slots past a group's count stage zero rows and are ignored).  After the chain the
+//            64 x 64 ratings go to LDS over the staging tiles, and one wave per (group of the tile, 64 anime) folds
+//            them in member order, ballots the floor test, ORs the members' watched words and the group's exclude
+//            words (a tile starts at a multiple of 64: two whole words) and stores the 64 aggregates and the two mask
+//            words.  A group with a bad offsets pair or member row raises *err and gets an all-ones mask, as does an
+//            empty one (no error): the select pads its rows with -1 / NaN (k_group_scores)
+//   select   launch_select (k <= ANIREC_MAX_TOPK) or lk_run on the batch's rows, wbits = the mask rows
+//   members  out_member_p[e][s] = the rating of member e for pick s of its group, one chain per thread
+//            (k_group_member_p)
+// No atomics, no host synchronisation.
+// ====================================================================================
+namespace anirec {
+
+struct GroupArgs {
+  const float *Uh;            // [n_users, dim] normalised rows of the call's users
+  const float *Ah;            // [n_anime, dim] normalised
+  int n_users, n_anime;
+  const int32_t *offsets;     // [n_groups + 1]
+  const int32_t *member_row;  // [n_members] positions in the users list
+  int n_members, max_members;
+  int m_shift;                // m_pad = 1 << m_shift slots per group
+  int g0, ng;                 // the batch: groups [g0, g0 + ng) of the call
+  const uint32_t *watched;    // optional [n_users][wwords]
+  const uint32_t *exclude;    // optional [n_groups][wwords]
+  int wwords;
+  int mode;
+  float floor, hs, hb;
+  int act;
+  float *score;               // [ng][n_anime] aggregate of each group of the batch
+  uint32_t *mask;             // [ng][wwords] set bit = not a candidate
+  int32_t *err;
+};
+
+__device__ __forceinline__ bool group_span_ok(const GroupArgs &a, int lo, int hi) {
+  return lo >= 0 && hi >= lo && hi <= a.n_members && hi - lo <= a.max_members;
+}
+
+constexpr int kGroupPitch = kTile + 16;  // ratings tile in LDS: the four rows ty = 0..3 of a wave's store fall on distinct banks
+
+template <int kD>
+__global__ __launch_bounds__(256) void k_group_scores(GroupArgs a) {
+  constexpr int kSV = ScoreGeom<kD>::kSV, kPitch = ScoreGeom<kD>::kPitch, kRowV = ScoreGeom<kD>::kRowV;
+  constexpr int kStage = 2 * kTile * kPitch, kFold = kTile * kGroupPitch;
+  __shared__ __attribute__((aligned(16))) float buf[kStage > kFold ? kStage : kFold];
+  __shared__ int32_t slot_row[kTile];  // row (in the users list) of the member in each slot, -1: none
+  __shared__ int32_t grp_cnt[kTile];   // per group of the tile: its count, -1: bad, -2: past the batch
+  float *Qs = buf, *Ws = buf + kTile * kPitch, *P = buf;
+  const int tid = threadIdx.x;
+  const int j0 = blockIdx.x * kTile;
+  const int m_pad = 1 << a.m_shift, gpt = kTile >> a.m_shift;
+  const int gt0 = blockIdx.y * gpt;  // first group of the tile, within the batch
+  if (tid < kTile) {                 // wave 0: slot tid = member tid % m_pad of group tid / m_pad
+    const int gl = tid >> a.m_shift, i = tid & (m_pad - 1);
+    const int g = gt0 + gl;
+    int row = -1, cnt = -2;
+    bool bad = false;
+    if (g < a.ng) {
+      const int lo = a.offsets[a.g0 + g], hi = a.offsets[a.g0 + g + 1];
+      if (!group_span_ok(a, lo, hi)) {  // nothing is read through a bad value
+        bad = true;
+      } else {
+        cnt = hi - lo;
+        if (i < cnt) {
+          row = a.member_row[lo + i];
+          if ((uint32_t)row >= (uint32_t)a.n_users) {
+            bad = true;
+            row = -1;
+          }
+        }
+      }
+    }
+    const unsigned long long span = (m_pad == 64 ? ~0ull : (1ull << m_pad) - 1ull) << (gl * m_pad);
+    const bool gbad = (__ballot(bad) & span) != 0ull;  // a group's slots are neighbours in the wave
+    slot_row[tid] = gbad ? -1 : row;
+    if (i == 0) {
+      grp_cnt[gl] = g < a.ng ? (gbad ? -1 : cnt) : -2;
+      if (gbad && blockIdx.x == 0) *a.err = 1;
+    }
+  }
+  __syncthreads();
+  const int tx = tid & 15, ty = tid >> 4;  // anime tx+16r, slots ty+16q
+  float acc[4][4];
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[qq][r] = 0.f;
+#pragma unroll
+  for (int k0 = 0; k0 < kRowV; k0 += kSV) {  // (one pass up to 128)
+    if (k0) __syncthreads();                 // the previous slice has been read
+    for (int e = tid; e < kTile * kSV; e += 256) {
+      const int r = e / kSV, cidx = e % kSV;
+      float4 qv = make_float4(0.f, 0.f, 0.f, 0.f), wv = qv;
+      const int src = slot_row[r];
+      if (src >= 0) qv = reinterpret_cast<const float4 *>(a.Uh)[(size_t)src * kRowV + k0 + cidx];
+      if (j0 + r < a.n_anime) wv = reinterpret_cast<const float4 *>(a.Ah)[(size_t)(j0 + r) * kRowV + k0 + cidx];
+      *reinterpret_cast<float4 *>(&Qs[r * kPitch + cidx * 4]) = qv;
+      *reinterpret_cast<float4 *>(&Ws[r * kPitch + cidx * 4]) = wv;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int k4 = 0; k4 < kSV; ++k4) {
+      float4 qv[4], wv[4];
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq)
+        qv[qq] = *reinterpret_cast<const float4 *>(&Qs[(ty + 16 * qq) * kPitch + k4 * 4]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        wv[r] = *reinterpret_cast<const float4 *>(&Ws[(tx + 16 * r) * kPitch + k4 * 4]);
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float s = acc[qq][r];
+          s = __fmaf_rn(wv[r].x, qv[qq].x, s);
+          s = __fmaf_rn(wv[r].y, qv[qq].y, s);
+          s = __fmaf_rn(wv[r].z, qv[qq].z, s);
+          s = __fmaf_rn(wv[r].w, qv[qq].w, s);
+          acc[qq][r] = s;
+        }
+    }
+  }
+  __syncthreads();  // the staging tiles have been read: the ratings take their place
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      P[(ty + 16 * qq) * kGroupPitch + tx + 16 * r] = rating_from_cosine<-1>(acc[qq][r], a.hs, a.hb, a.act);
+  __syncthreads();
+  // one wave per group of the tile; lane = anime j0 + lane
+  const int lane = tid & 63, w0 = j0 >> 5;
+  const int j = j0 + lane;
+  for (int gl = tid >> 6; gl < gpt; gl += 4) {
+    const int cnt = grp_cnt[gl];
+    if (cnt == -2) break;  // past the batch, and so is every later group of the tile
+    const int g = gt0 + gl;
+    uint32_t m_lo = 0xFFFFFFFFu, m_hi = 0xFFFFFFFFu;  // bad or empty: no candidates
+    if (cnt > 0) {
+#pragma clang fp contract(off)
+      const float *pg = P + (gl << a.m_shift) * kGroupPitch + lane;
+      float p = pg[0], s = p;
+      bool below = p < a.floor;  // false for a NaN rating
+      for (int i = 1; i < cnt; ++i) {
+        p = pg[i * kGroupPitch];
+        below |= p < a.floor;
+        if (a.mode == ANIREC_GROUP_MEAN) {
+          s = s + p;
+        } else if (p != p) {
+          s = p;  // a NaN sticks
+        } else if (s == s && (a.mode == ANIREC_GROUP_MIN ? p < s : p > s)) {
+          s = p;  // strict: of +-0 the earlier member stays
+        }
+      }
+      if (a.mode == ANIREC_GROUP_MEAN) s = s / (float)cnt;
+      const unsigned long long b = __ballot(below);
+      m_lo = (uint32_t)b;
+      m_hi = (uint32_t)(b >> 32);
+      uint32_t x_lo = 0u, x_hi = 0u;  // lane i: the words of member i; lane 0 also the group's exclude words
+      if (a.watched && lane < cnt) {
+        const uint32_t *wr = a.watched + (size_t)slot_row[(gl << a.m_shift) + lane] * a.wwords;
+        x_lo = wr[w0];
+        if (w0 + 1 < a.wwords) x_hi = wr[w0 + 1];
+      }
+      if (a.exclude && lane == 0) {
+        const uint32_t *xr = a.exclude + (size_t)(a.g0 + g) * a.wwords;
+        x_lo |= xr[w0];
+        if (w0 + 1 < a.wwords) x_hi |= xr[w0 + 1];
+      }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        x_lo |= __shfl_xor(x_lo, o, 64);
+        x_hi |= __shfl_xor(x_hi, o, 64);
+      }
+      m_lo |= x_lo;
+      m_hi |= x_hi;
+      if (j < a.n_anime) a.score[(size_t)g * a.n_anime + j] = s;
+    }
+    if (lane == 0) {
+      uint32_t *mr = a.mask + (size_t)g * a.wwords;
+      mr[w0] = m_lo;
+      if (w0 + 1 < a.wwords) mr[w0 + 1] = m_hi;  // (the last tile of a table with n_anime % 64 in 1..32 has one word)
+    }
+  }
+}
+
+// out_member_p[e][s] = rating of member e for pick s of its group g = blockIdx.x; rows no valid group covers keep the
+// NaN the entry point filled them with
+template <int kD>
+__global__ __launch_bounds__(256) void k_group_member_p(GroupArgs a, const int32_t *__restrict__ out_idx, int k,
+                                                        float *__restrict__ out_member_p) {
+  constexpr int kRowV = kD / 4;
+  const int g = blockIdx.x;
+  const int lo = a.offsets[g], hi = a.offsets[g + 1];
+  if (!group_span_ok(a, lo, hi)) return;
+  const size_t items = (size_t)(hi - lo) * k;
+  for (size_t t = (size_t)blockIdx.y * 256 + threadIdx.x; t < items; t += (size_t)gridDim.y * 256) {
+    const int e = lo + (int)(t / k), sl = (int)(t % k);
+    const int jj = out_idx[(size_t)g * k + sl], row = a.member_row[e];
+    float v = __uint_as_float(0x7FC00000u);
+    if ((uint32_t)jj < (uint32_t)a.n_anime && (uint32_t)row < (uint32_t)a.n_users) {
+      const float4 *q4 = reinterpret_cast<const float4 *>(a.Uh) + (size_t)row * kRowV;
+      const float4 *w4 = reinterpret_cast<const float4 *>(a.Ah) + (size_t)jj * kRowV;
+      float s = 0.f;
+#pragma unroll 8
+      for (int k4 = 0; k4 < kRowV; ++k4) {
+        const float4 x = w4[k4], y = q4[k4];
+        s = __fmaf_rn(x.x, y.x, s);
+        s = __fmaf_rn(x.y, y.y, s);
+        s = __fmaf_rn(x.z, y.z, s);
+        s = __fmaf_rn(x.w, y.w, s);
+      }
+      v = rating_from_cosine<-1>(s, a.hs, a.hb, a.act);
+    }
+    out_member_p[(size_t)e * k + sl] = v;
+  }
+}
+
+// the select's share of a group (either kind) and its mask row, which lies after the batch's score rows
+static TopkLayout group_layout(int32_t n, int32_t k) {
+  TopkLayout L = k <= ANIREC_MAX_TOPK ? select_layout(n) : lk_layout(n, k);
+  L.per_query += (size_t)((n + 31) / 32) * 4;
+  return L;
+}
+
+static bool group_shape_ok(int32_t n_anime, int32_t n_users, int32_t n_groups, int32_t k, int32_t dim) {
+  return dim_ok(dim) && n_anime >= 1 && n_users >= 0 && n_groups >= 0 && k >= 1;
+}
+
+}  // namespace anirec
+
+extern "C" {
+
+size_t anirec_group_topk_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t n_groups, int32_t k, int32_t dim) {
+  if (!group_shape_ok(n_anime, n_users, n_groups, k, dim)) return 0;
+  return norm_bytes(n_anime, n_users, dim) + group_layout(n_anime, k).bytes(n_groups < 1 ? 1 : n_groups, 4096);
+}
+
+int anirec_group_topk(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                      int32_t n_users, const anirec_head *head, int32_t activation, const uint32_t *watched,
+                      const int32_t *group_offsets, const int32_t *member_row, int32_t n_groups, int32_t n_members,
+                      int32_t max_members, const uint32_t *exclude, int32_t mode, float floor, int32_t k,
+                      int32_t *out_idx, float *out_score, float *out_member_p, int32_t *err_flag, void *workspace,
+                      size_t workspace_bytes, void *stream) {
+  if (!group_shape_ok(n_anime, n_users, n_groups, k, dim) || !act_ok(activation) || n_members < 0 ||
+      mode < ANIREC_GROUP_MEAN || mode > ANIREC_GROUP_MAX || floor != floor || max_members < 1 ||
+      max_members > ANIREC_GROUP_MAX_MEMBERS)
+    return ANIREC_EINVAL;
+  if (n_groups == 0) return ANIREC_OK;
+  if (!U || !A || !head || !group_offsets || !out_idx || !out_score || !err_flag || !workspace ||
+      (n_users > 0 && !users) || (n_members > 0 && !member_row))
+    return ANIREC_EINVAL;
+  const size_t nb = norm_bytes(n_anime, n_users, dim);
+  const TopkLayout L = group_layout(n_anime, k);
+  if (workspace_bytes < nb + L.fixed + L.per_query) return ANIREC_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
+  if (out_member_p && n_members > 0)
+    ANIREC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)out_member_p, 0x7FC00000, (size_t)n_members * k, s));
+  NormRows t;
+  if (n_users > 0) {
+    ANIREC_HIP_CHECK(normalise_tables(U, A, dim, n_anime, users, n_users, workspace, s, &t));
+  } else {  // no rows to read: every member is out of range
+    t.Ah = (float *)workspace;
+    t.Uh = t.Ah + (size_t)n_anime * dim;
+    launch_rownorm<1>(A, nullptr, n_anime, t.Ah, dim, s);
+    ANIREC_HIP_CHECK(hipGetLastError());
+  }
+  GroupArgs a;
+  a.Uh = t.Uh;
+  a.Ah = t.Ah;
+  a.n_users = n_users;
+  a.n_anime = n_anime;
+  a.offsets = group_offsets;
+  a.member_row = member_row;
+  a.n_members = n_members;
+  a.max_members = max_members;
+  a.m_shift = 0;
+  while ((1 << a.m_shift) < max_members) ++a.m_shift;
+  a.watched = watched;
+  a.exclude = exclude;
+  a.wwords = (n_anime + 31) / 32;
+  a.mode = mode;
+  a.floor = floor;
+  head_affine(head, &a.hs, &a.hb);
+  a.act = activation;
+  a.err = err_flag;
+  char *ws = (char *)workspace + nb;
+  size_t gb = (workspace_bytes - nb - L.fixed) / L.per_query;
+  if (gb > (size_t)n_groups) gb = n_groups;
+  LkArgs la = {};
+  void *sel_tmp = nullptr;
+  a.score = L.carve(ws, gb, la, sel_tmp);
+  a.mask = (uint32_t *)(a.score + gb * (size_t)n_anime);
+  const int gpt = kTile >> a.m_shift;
+  for (size_t g0 = 0; g0 < (size_t)n_groups; g0 += gb) {
+    a.g0 = (int)g0;
+    a.ng = (int)((size_t)n_groups - g0 < gb ? (size_t)n_groups - g0 : gb);
+    const dim3 grid((n_anime + kTile - 1) / kTile, (a.ng + gpt - 1) / gpt);
+    with_width(dim, [&](auto kd) {
+      hipLaunchKernelGGL(k_group_scores<decltype(kd)::value>, grid, dim3(256), 0, s, a);
+    });
+    ANIREC_HIP_CHECK(hipGetLastError());
+    SelectArgs &sa = la.s;
+    sa.scores = a.score;
+    sa.ld = (size_t)n_anime;
+    sa.n = n_anime;
+    sa.nq = a.ng;
+    sa.k = k;
+    sa.self = nullptr;
+    sa.keep = nullptr;
+    sa.wbits = a.mask;
+    sa.wwords = a.wwords;
+    sa.out_idx = out_idx + g0 * k;
+    sa.out_score = out_score + g0 * k;
+    const int e = L.large ? lk_run(la, s) : launch_select(sa, sel_tmp, s);
+    if (e) return e;
+  }
+  if (out_member_p && n_members > 0) {
+    size_t by = ((size_t)max_members * k + 255) / 256;
+    if (by > 64) by = 64;
+    with_width(dim, [&](auto kd) {
+      hipLaunchKernelGGL(k_group_member_p<decltype(kd)::value>, dim3(n_groups, (unsigned)by), dim3(256), 0, s, a, out_idx, k,
+                         out_member_p);
+    });
+    ANIREC_HIP_CHECK(hipGetLastError());
+  }
+  return ANIREC_OK;
+}
+
+}  // extern "C"

@@ -426,6 +426,69 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
     return out_i, out_p
 
 
+def group_mode(mode):
+    """ANIREC_GROUP_* of a strategy name, in any case: ``mean``, ``least_misery`` / ``min``, ``most_pleasure`` / ``max``.
+    ValueError, listing them, for another."""
+    m = _lib.GROUP_MODES.get(str(mode).strip().lower())
+    if m is None:
+        raise ValueError("group strategy %r is not one of %s" % (mode, ", ".join(_lib.GROUP_MODES)))
+    return m
+
+
+def group_topk(U, A, head, users, offsets, member_row, k, mode="mean", floor=None, watched_bits=None,
+               exclude_bits=None, member_ratings=False):
+    """One top-k list per GROUP of users (anirec_group_topk): group g has the members
+    ``member_row[offsets[g]:offsets[g + 1]]``, positions in ``users`` (rows of ``U``); a row listed twice counts twice.
+    The members' ratings are predict_grid's bits, aggregated in fp32 in member order (``mode``: ``mean``,
+    ``least_misery`` / ``min``, ``most_pleasure`` / ``max``, any case) and ranked as predict_topk ranks, any k >= 1, among
+    the anime no member has a watched bit for (``watched_bits`` [len(users), ceil(n_anime/32)], rows follow ``users``),
+    the group's row of ``exclude_bits`` ([n_groups, ceil(n_anime/32)]) has no bit for and, with ``floor``, no member
+    rates below it.  Returns (idx int32 [n_groups, k], score fp32 [n_groups, k]) padded with -1 / NaN, and with
+    ``member_ratings`` also member_p fp32 [n_members, k]: each member's own rating of its group's picks.  An empty
+    group's rows are all padding.  Raises ValueError for an unknown mode, k < 1, a NaN floor, a group of more than
+    GROUP_MAX_MEMBERS members, and for offsets or member rows out of range."""
+    m = group_mode(mode)
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    fl = float("-inf") if floor is None else float(floor)
+    if fl != fl:
+        raise ValueError("group_topk: floor is NaN")
+    dev = U.device
+    off_host = np.asarray(offsets.detach().cpu() if isinstance(offsets, torch.Tensor) else offsets, np.int64).reshape(-1)
+    if off_host.size < 1:
+        raise ValueError("group_topk: offsets holds n_groups + 1 entries")
+    n_g = int(off_host.size) - 1
+    biggest = int(np.diff(off_host).max()) if n_g else 0
+    if biggest > _lib.GROUP_MAX_MEMBERS:
+        raise ValueError("group_topk: a group of %d members is above the limit of %d (GROUP_MAX_MEMBERS)"
+                         % (biggest, _lib.GROUP_MAX_MEMBERS))
+    _need_gpu()
+    lib = _lib.load()
+    us, off, mr = _i32(users, dev), _i32(off_host, dev), _i32(member_row, dev)
+    assert us.dim() == 1 and mr.dim() == 1
+    n_a, n_q, n_m = A.shape[0], int(us.numel()), int(mr.numel())
+    dim = _width(U, A)
+    if n_q and bool(((us < 0) | (us >= U.shape[0])).any()):
+        raise ValueError("group_topk: user row out of range")
+    out_i = torch.empty(n_g, k, dtype=torch.int32, device=dev)
+    out_s = torch.empty(n_g, k, dtype=torch.float32, device=dev)
+    out_m = torch.empty(n_m, k, dtype=torch.float32, device=dev) if member_ratings else None
+    if n_g:
+        wb = _watched(watched_bits, n_q, n_a, dev)
+        xb = _watched(exclude_bits, n_g, n_a, dev)
+        h = _head_struct(head)
+        err = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(lib.anirec_group_topk_workspace_bytes(n_a, n_q, n_g, k, dim)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.anirec_group_topk(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head),
+                                         _lib.ptr(wb), _lib.ptr(off), _lib.ptr(mr), n_g, n_m, max(biggest, 1),
+                                         _lib.ptr(xb), m, fl, k, _lib.ptr(out_i), _lib.ptr(out_s), _lib.ptr(out_m),
+                                         _lib.ptr(err), _lib.ptr(ws), ws.numel(), _stream()), "anirec_group_topk")
+        if int(err.item()):
+            raise ValueError("group_topk: offsets or member_row out of range")
+    return (out_i, out_s, out_m) if member_ratings else (out_i, out_s)
+
+
 def seen_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
     """Watched bits of a rating list: int32 [n_users, ceil(n_anime/32)], bit ``a & 31`` of word ``a >> 5`` of row u set
     for every rating (u, a) — the ``watched_bits`` of predict_topk / predict_rank.  Raises ValueError on an index out

@@ -234,6 +234,56 @@ def diverse_topk(U, A, head, users, k, pool, diversity, watched_bits=None):
     return idx, score, pen
 
 
+def group_csr(groups, user_ids):
+    """The CSR ``ops.group_topk`` takes, from groups given as lists of user ids: (users int64 [n_distinct]: the rows of
+    ``user_ids`` (the model's index -> id table) of the distinct members, in order of first appearance, each once;
+    offsets int64 [n_groups + 1]; member_row int32 [n_members]: each member's position in ``users``, group after
+    group in the order given, a repeated id repeated).  A user may be in any number of groups.  ValueError, naming
+    them, for ids without a row."""
+    sizes = [len(g) for g in groups]
+    flat = np.asarray([int(u) for g in groups for u in g], np.int64)
+    offsets = np.zeros(len(sizes) + 1, np.int64)
+    np.cumsum(sizes, out=offsets[1:])
+    table = np.asarray(user_ids, np.int64)
+    distinct, first, inverse = np.unique(flat, return_index=True, return_inverse=True)
+    by_first = np.argsort(first, kind="stable")             # distinct ids in order of first appearance
+    place = np.empty(len(distinct), np.int64)
+    place[by_first] = np.arange(len(distinct))
+    ids = distinct[by_first]
+    order = np.argsort(table, kind="stable")
+    pos = np.searchsorted(table[order], ids)
+    pos[pos == len(table)] = 0
+    has = (table[order][pos] == ids) if len(table) else np.zeros(len(ids), bool)
+    if not bool(has.all()):
+        raise ValueError("group_csr: user id(s) %s have no embedding row" % ", ".join(str(int(x)) for x in ids[~has][:20]))
+    return order[pos].astype(np.int64), offsets, place[inverse.reshape(-1)].astype(np.int32)
+
+
+def group_topk(model_or_tables, groups, k, mode="mean", floor=None, watched_bits=None, exclude_bits=None,
+               member_ratings=False, device="cuda:0"):
+    """A top-k list per group of user ids: ``group_csr`` of ``groups``, then ``ops.group_topk``.
+    ``model_or_tables``: ``weights_io.load_model``'s dict (with its id tables), or (U, A, head, user_ids) with the
+    tables as arrays or device tensors.  ``watched_bits``: None, or a callable given ``users`` (the rows of the distinct
+    members) that returns their [len(users), ceil(n_anime/32)] bit rows (``listed_seen_bits`` with the rating list bound
+    is one).  ``exclude_bits`` [n_groups, ceil(n_anime/32)], ``mode``, ``floor``, ``member_ratings``: as ops.group_topk.
+    Returns (idx, score[, member_p], csr) with csr = (users, offsets, member_row)."""
+    from . import ops, weights_io
+    if isinstance(model_or_tables, dict):
+        model = model_or_tables
+        if model.get("user_ids") is None:
+            raise ValueError("group_topk: the model file has no id tables")
+        U, A, head, user_ids = model["U"], model["A"], weights_io.model_head(model), model["user_ids"]
+    else:
+        U, A, head, user_ids = model_or_tables
+    csr = group_csr(groups, user_ids)
+    tU = U if isinstance(U, torch.Tensor) and U.is_cuda else torch.as_tensor(np.ascontiguousarray(U, np.float32), device=device)
+    tA = A if isinstance(A, torch.Tensor) and A.is_cuda else torch.as_tensor(np.ascontiguousarray(A, np.float32), device=device)
+    wb = watched_bits(csr[0]) if callable(watched_bits) else watched_bits
+    out = ops.group_topk(tU, tA, head, csr[0], csr[1], csr[2], k, mode=mode, floor=floor, watched_bits=wb,
+                         exclude_bits=exclude_bits, member_ratings=member_ratings)
+    return out + (csr,)
+
+
 def gini(counts):
     """Gini coefficient of non-negative counts, float64 on the host: with the n counts sorted ascending,
     sum_i (2 i - n - 1) c_i / (n sum c), i 1-based — 0 for equal counts, (n - 1) / n when one holds everything.  NaN for

@@ -647,6 +647,52 @@ int anirec_score_rank(const float *score, int32_t n_anime, const uint32_t *watch
 int anirec_seen_bits(const int32_t *user_idx, const int32_t *anime_idx, int64_t n, int32_t n_users, int32_t n_anime,
                      uint32_t *bits, int32_t *err_flag, void *stream);
 
+/* GROUP recommendations: one list for several users who watch together.  Group g has the members
+ * e = group_offsets[g] .. group_offsets[g+1]-1 (CSR; c_g = their number); member e is user users[member_row[e]]
+ * (member_row indexes `users`, as anirec_predict_rank's target_row).  A row listed twice counts as two members; a user
+ * may belong to any number of groups.
+ *   p_e[j]   the rating anirec_predict_grid_w writes for that user and anime j, bit for bit (the same
+ *            tf.nn.l2_normalize rows, k-ordered fmaf chain from 0, head and activation)
+ *   s_g[j]   the aggregate over the group's members, fp32, in member order, nothing contracted:
+ *            ANIREC_GROUP_MEAN  s = p_0; s = s + p_i, i = 1 .. c-1; then s / (float)c, correctly rounded
+ *            ANIREC_GROUP_MIN   a = p_0; for i >= 1: p_i NaN -> a = p_i; else a not NaN and p_i < a -> a = p_i
+ *                               (least misery: a NaN sticks, of +-0 the earlier member stays)
+ *            ANIREC_GROUP_MAX   the same with > (most pleasure)
+ * Anime j is no candidate of group g if the watched bit j of any member is set (bits at positions >= n_anime have no
+ * effect), if bit j of exclude[g] is set, or if p_i[j] < floor for any member (false for a NaN rating; floor =
+ * -INFINITY switches the rule off).  The candidates are ranked by s_g in the order of anirec_predict_topk*: larger
+ * first, +0 above -0, NaN after every number, ties in ascending index; any k >= 1 (k <= ANIREC_MAX_TOPK and above it
+ * the two selects of anirec_predict_topk_w / _large_w, the same bits where they overlap); out_idx / out_score
+ * [n_groups][k] are padded with -1 / NaN.  out_member_p (optional, [n_members][k]): out_member_p[e][s] =
+ * p_e[out_idx[g][s]], NaN where the pick is -1; every element no valid group covers is NaN.  A one-member group
+ * returns, in every mode, that user's anirec_predict_topk_large_w list bit for bit.
+ * watched: optional [n_users][ceil(n_anime/32)], rows follow `users`; exclude: optional [n_groups][ceil(n_anime/32)].
+ * *err_flag (device) is overwritten by the call; it becomes 1 on a member_row outside [0, n_users) or an offsets pair
+ * that is negative, decreasing, past n_members or longer than max_members: that group's rows are -1 / NaN, nothing is
+ * read through the bad value, the other groups are unaffected (should the pairs of valid groups overlap after such a
+ * pair, the out_member_p rows they share hold either group's ratings).  An empty group gives -1 / NaN and no error.
+ * max_members: an upper bound of the c_g, 1 .. ANIREC_GROUP_MAX_MEMBERS; it sizes the kernel's tiles and changes no
+ * result.  A group's outputs depend on that group alone: not on the other groups, its position, max_members, the
+ * workspace size or the run.  No atomics, no host synchronisation: graph-capturable.
+ * A bad dim, activation or mode, a NaN floor, n_anime < 1, a negative count, k < 1, max_members out of range, or a
+ * NULL U, A, head_host, group_offsets, out_idx, out_score, err_flag or workspace (users with n_users > 0, member_row
+ * with n_members > 0) with n_groups > 0: ANIREC_EINVAL before anything is enqueued or written (0 from the size query
+ * for those it can see).  n_groups == 0: ANIREC_OK, nothing enqueued.
+ * workspace: may hold anything; Ah | Uh, then the select's fixed part and per group of a batch (at most 4096) a score
+ * row, a mask row and the select's share.  anirec_group_topk_workspace_bytes sizes it; anything down to one group's
+ * share runs the groups in smaller batches with the same results, less is ANIREC_EWORKSPACE.
+ * Cost: 2 (slots) n_anime dim flops of the fp32 chain with slots = n_groups next_pow2(max_members) rounded up to 64,
+ * 4 n_anime + n_anime / 8 bytes stored per group; no [n_members, n_anime] matrix exists. */
+enum { ANIREC_GROUP_MEAN = 0, ANIREC_GROUP_MIN = 1, ANIREC_GROUP_MAX = 2 };
+#define ANIREC_GROUP_MAX_MEMBERS 64
+size_t anirec_group_topk_workspace_bytes(int32_t n_anime, int32_t n_users, int32_t n_groups, int32_t k, int32_t dim);
+int anirec_group_topk(const float *U, const float *A, int32_t dim, int32_t n_anime, const int32_t *users,
+                      int32_t n_users, const anirec_head *head_host, int32_t activation, const uint32_t *watched,
+                      const int32_t *group_offsets, const int32_t *member_row, int32_t n_groups, int32_t n_members,
+                      int32_t max_members, const uint32_t *exclude, int32_t mode, float floor, int32_t k,
+                      int32_t *out_idx, float *out_score, float *out_member_p, int32_t *err_flag, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* FOLD-IN of new users: a user the model was not trained on (model_recs.py:373-394 reads the user's row out of the
  * trained table and has none) gets a row fitted to that user's own ratings with everything else frozen — the Keras
  * model of neural_network.py:66-106 with the anime table, Dense(1) and BatchNorm (inference mode) fixed and a fresh
