@@ -13,7 +13,11 @@
 //         instantiation per pair, the default sigmoid + BCE as it always was), d loss/d y, partial sums; with a
 //         handle's metric set (anirec_trainer_set_metrics) k_head_metrics also accumulates the Keras metrics
 //   bwd   half-wave per chunk: weighted sum of the OTHER table's rows, accumulated in
-//         registers in a fixed order, one coalesced 512-B store per chunk (no float atomics)
+//         registers in a fixed order, one coalesced 512-B store per chunk (no float atomics).  The anime table's
+//         chunk slots are the first of the grid (bwd and the lazy sparse step): the popular anime rows own the full
+//         chunks and the many-chunk rows, the longest chains of both launches, and start with the launch.  Every
+//         reader of a chunk table asks for the count word and the chunk record in one round trip (record index
+//         clamped into the table's slots; a record past the count is dropped unread).
 //   adam  half-wave per table row, dense: g = chunk sums - s*W + 2*l2*W, Keras-2.12 Adam,
 //         emits sum(W_new^2) partials for the L2 loss term.  HBM-bound: 24 B/element
 //         (+512 B per touched row) instead of 28 because the dense gradient never exists.
@@ -798,11 +802,20 @@ __device__ __forceinline__ void bwd_prefetch(const BwdArgs &a, int slot, int vbl
   constexpr int kG = BwdGeom<kD>::kG, kC = BwdGeom<kD>::kC;
   const int l = threadIdx.x & (kG - 1);
   const int hw = vblk * BwdGeom<kD>::kRpb + (threadIdx.x / kG);
-  x.T = hw >= a.capC ? 1 : 0;
-  x.c = hw - x.T * a.capC;
+  // The anime table's chunk slots come first in the grid: its popular rows own the full 32-contribution chunks, the
+  // longest chains of the launch, and those must not start in the dispatcher's second pass over the CUs.  Only the
+  // workgroup -> (table, chunk) map is this; the chunk index gc = T capC + c that P / S / the row map use is not.
+  x.T = hw < a.capC ? 1 : 0;
+  x.c = hw - (1 - x.T) * a.capC;
   Slot sl = slot_of(a.arena, a.slot_bytes, a.cap, a.capC, slot);
   const float4 *W4 = reinterpret_cast<const float4 *>(a.W);
-  x.active = hw < 2 * a.capC && x.c < sl.nchunks[x.T];
+  // the count word and the chunk record in ONE round trip (both addresses hang on the step index alone): the record
+  // index is clamped into the table's slots, and a record past the count is dropped unread
+  int4 rec = sl.chunks[x.T * a.capC + min(x.c, a.capC - 1)];
+  int nT = sl.nchunks[x.T];
+  // (both loads are issued here: hipcc would sink the record's behind the test of the count)
+  asm volatile("" : "+v"(nT), "+v"(rec.x), "+v"(rec.y), "+v"(rec.z), "+v"(rec.w));
+  x.active = hw < 2 * a.capC && x.c < nT;
   x.len = 0;
   x.rec = make_int4(0, 0, 0, 0);
 #pragma unroll
@@ -814,7 +827,7 @@ __device__ __forceinline__ void bwd_prefetch(const BwdArgs &a, int slot, int vbl
 #pragma unroll
   for (int q = 0; q < 4; ++q) x.r0[q] = make_float4(0.f, 0.f, 0.f, 0.f);
   if (x.active) {
-    x.rec = sl.chunks[x.T * a.capC + x.c];
+    x.rec = rec;
     x.len = x.rec.z;
     // lane j < len holds contribution j of the chunk (+ j + kG, ... at the narrow widths); the rest replicate the
     // last one with weight 0 so every shuffle source is a valid row
@@ -1710,14 +1723,23 @@ __device__ __forceinline__ void lazy_alphas(const LazyArgs &a, int w0, int nj, f
   for (int j = 0; j < kLzWin; ++j) alpha[j] = (j < nj && w0 + j < a.n_steps) ? a.sched[w0 + j].alpha : 0.f;
 }
 
-// the distinct row a half-wave of the chunk-table grid owns (first chunk of a row's run), or -1
+// the distinct row a half-wave of the chunk-table grid owns (first chunk of a row's run), or -1.
+// kAnimeFirst (the sparse step): the anime table's chunk slots come first in the grid, as in k_bwd — the rows with
+// many chunks are anime rows; the catch-up keeps the user chunks first (they are where ITS work is, and the slice of
+// them that rides in the head launch is cut from the front of the grid).
+// The count word and the chunk record come in ONE round trip: the record index is clamped into the table's slots, and
+// a record past the count is dropped unread.
+template <bool kAnimeFirst = false>
 __device__ __forceinline__ int lazy_chunk_row(const LazyArgs &a, int step, int bid, int &gc, int &nch) {
   const int hw = bid * 8 + (threadIdx.x >> 5);
-  const int T = hw >= a.capC ? 1 : 0;
-  const int c = hw - T * a.capC;
+  const bool flip = kAnimeFirst && a.tables == 2;
+  const int T = flip ? (hw < a.capC ? 1 : 0) : (hw >= a.capC ? 1 : 0);
+  const int c = hw >= a.capC ? hw - a.capC : hw;
   Slot sl = slot_of(a.arena, a.slot_bytes, a.cap, a.capC, step % a.arena_steps);
-  if (hw >= a.tables * a.capC || c >= sl.nchunks[T]) return -1;
-  const int4 rec = sl.chunks[T * a.capC + c];
+  int4 rec = sl.chunks[T * a.capC + min(c, a.capC - 1)];
+  int nT = sl.nchunks[T];
+  asm volatile("" : "+v"(nT), "+v"(rec.x), "+v"(rec.w));  // both loads are issued here (hipcc sinks rec.x behind the test)
+  if (hw >= a.tables * a.capC || c >= nT) return -1;
   if (rec.w <= 0) return -1;
   gc = T * a.capC + c;
   nch = rec.w;
@@ -1817,6 +1839,14 @@ __global__ __launch_bounds__(kHeadThreads) void k_head_metrics(HeadArgs a, LazyA
 // after bwd(t): step t on the rows the batch touched (chunk gradient - s W + 2 lambda W), the step finish in
 // workgroup 0.  Same operations, same order as the dense kernel's row_issue / row_finish for a touched row.
 // (the catch-up of batch t + 1's rows rides in k_head(t)'s launch)
+// The sparse half walks the anime table's chunk slots first: five workgroups per CU are resident and the user table's
+// ~1 250 live workgroups fill them, so behind the user chunks a popular anime row's workgroup — first partial + 8
+// rounds of add_chunks<4> for a 31-chunk row, the longest chain of the sparse step — started 3-4 us into the launch.
+// Measured, not built: that row's other partials fetched by its whole workgroup in one round trip through LDS.  By
+// the per-workgroup stamps (S109M, 8 eager steps) its workgroup ends a launch only when no catch-up rides in it
+// (11.3 us against 8.9 for the next one; one step per prepared block); in the launches that carry the next batch's
+// catch-up, those workgroups — the last of the grid, started 6.5-8.7 us in — end it at 13-17 us, 2-4 us after the
+// 31-chunk row's even where that one started 3.9 us late.
 __global__ __launch_bounds__(256) void k_lazy_adam(LazyArgs a, AdamArgs d) {
   __shared__ float scratch[kHeadCols * 16];
   tick(a.ticks, 0);
@@ -1834,7 +1864,7 @@ __global__ __launch_bounds__(256) void k_lazy_adam(LazyArgs a, AdamArgs d) {
     return;
   }
   int gc, nch;
-  const int row = lazy_chunk_row(a, step, (int)blockIdx.x, gc, nch);
+  const int row = lazy_chunk_row<true>(a, step, (int)blockIdx.x, gc, nch);
   if (row >= 0) {
     const size_t e = (size_t)row * kRowVec + l;
     const float4 *P4 = reinterpret_cast<const float4 *>(d.P) + (size_t)par * 2 * d.capC * kRowVec;
