@@ -887,6 +887,11 @@ __device__ __forceinline__ void bwd_chunk(const BwdArgs &a, const StepPub &pub, 
   const float Bf = (float)pub.n_total;
   const float m1 = pub.gamma * m[0] / Bf;
   const float m2 = pub.gamma * m[1] / Bf;
+  // A batch of one: z is its own mean and d loss / d z is exactly 0 (so the reference, so the oracle).  The expression
+  // below gives the difference of two roundings of dy * gamma there (the product contracted into the subtraction, and
+  // the product rounded in m1), 1e-7 after rs: a gradient Adam's epsilon lets move an element whose own L2 gradient is
+  // as small by 2e-6 (tests/test_train_edges_gpu.py, tiny_ragged at width 32).
+  const bool one = pub.n_total == 1;
 
   float cf[kC], sf[kC];
 #pragma unroll
@@ -895,7 +900,7 @@ __device__ __forceinline__ void bwd_chunk(const BwdArgs &a, const StepPub &pub, 
     // closed-form backward of BatchNorm + Dense(1) + normalised dot for rating i
     const float z = ci * pub.w + pub.b;
     const float zh = (z - pub.mu) * pub.rs;
-    const float dz = (dyi * pub.gamma - m1 - zh * m2) * pub.rs;
+    const float dz = one ? 0.f : (dyi * pub.gamma - m1 - zh * m2) * pub.rs;
     const float dc = dz * pub.w;
     const float ru = 1.0f / sqrtf(fmaxf(su, kL2nEps));
     const float ra = 1.0f / sqrtf(fmaxf(sa, kL2nEps));
@@ -1250,8 +1255,10 @@ __device__ __forceinline__ void finish_step(const AdamArgs &a, int par, float *s
     const double g = pub.gamma, rs = pub.rs;
     const double m1 = g * S1 / n, m2 = g * S2 / n;
     // sum dz*c and sum dz with dz = (gamma*dy - m1 - zh*m2)*rs, expanded over the batch sums
-    const float dW = (float)(rs * (g * Sdc - m1 * Sc - m2 * Szc));
-    const float dB = (float)(rs * (g * S1 - n * m1 - m2 * Sz));
+    // (a batch of one: dz is exactly 0, see bwd_chunk; Sdc is dy * c rounded to fp32 and would leave that rounding)
+    const bool one = pub.n_total == 1;
+    const float dW = one ? 0.f : (float)(rs * (g * Sdc - m1 * Sc - m2 * Szc));
+    const float dB = one ? 0.f : (float)(rs * (g * S1 - n * m1 - m2 * Sz));
     float p4[4] = {pub.w, pub.b, pub.gamma, pub.beta};
     const float g4[4] = {dW, dB, (float)S2, (float)S1};  // d w, d b, d gamma, d beta
 #pragma unroll
