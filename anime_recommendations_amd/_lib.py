@@ -25,6 +25,10 @@ TOPK_MAX_BATCHES = 64
 RCCL_ID_BYTES = 128
 LAZY_WINDOW = 8
 MMR_IMAGE_FLOATS = 32768    # anirec_mmr_max_cand(dim) = MMR_IMAGE_FLOATS // dim: the candidates' rows of a list in LDS
+EXPLAIN_MAX_M = 8           # ANIREC_EXPLAIN_MAX_M: the most history entries anirec_explain_lists picks per listed anime
+EXPLAIN_MAX_K = 128         # anirec_explain_max_k(dim) = min(EXPLAIN_MAX_K, EXPLAIN_IMAGE_FLOATS // dim)
+EXPLAIN_IMAGE_FLOATS = 16384
+EXPLAIN_TILE_FLOATS = 8192  # anirec_explain_tile(dim, k): dim * tile and k * (tile | 1) floats both within this
 # anirec_train_desc.optimizer (ANIREC_OPT_*)
 OPT_ADAM, OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
 # anirec_train_desc.loss (ANIREC_LOSS_*) and .activation / the predict calls' activation (ANIREC_ACT_*)
@@ -234,6 +238,10 @@ PROTOTYPES = {
     "anirec_group_topk_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "anirec_group_topk": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(Head), _i32, _vp, _vp, _vp, _i32, _i32,
                                     _i32, _vp, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the top contributing history entries of every listed anime (explained recommendations)
+    "anirec_explain_max_k": (_sz, [_i32]),
+    "anirec_explain_tile": (_sz, [_i32, _i32]),
+    "anirec_explain_lists": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 
@@ -253,6 +261,19 @@ def check_width(width) -> int:
 def mmr_max_cand(width) -> int:
     """anirec_mmr_max_cand: the longest candidate list anirec_mmr_rerank takes at a (checked) row width."""
     return MMR_IMAGE_FLOATS // check_width(width)
+
+
+def explain_max_k(width) -> int:
+    """anirec_explain_max_k: the longest list anirec_explain_lists takes at a (checked) row width."""
+    return min(EXPLAIN_MAX_K, EXPLAIN_IMAGE_FLOATS // check_width(width))
+
+
+def explain_tile(width, k) -> int:
+    """anirec_explain_tile: the history entries anirec_explain_lists stages per pass for lists of ``k`` slots."""
+    w, k = check_width(width), int(k)
+    if not 1 <= k <= explain_max_k(w):
+        raise ValueError("explain_tile: k = %d must be in 1 .. %d at width %d" % (k, explain_max_k(w), w))
+    return min(EXPLAIN_TILE_FLOATS // w, (EXPLAIN_TILE_FLOATS // k - 1) & ~7)
 
 
 _lib = None

@@ -336,6 +336,13 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
                      types=None, genres=None):
     """recommendations (model_recs.py:373-456): predicted rating of every unwatched, indexed
     anime for one user, Type / Genre filters, descending prediction, first ``n_recs``."""
+    meta, idx, p, _ = _model_recs_topk(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
+    return _model_recs_rows(meta, idx, p)
+
+
+def _model_recs_topk(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres):
+    """model_recs_frame's list before it becomes a frame: (meta, idx, p, tA) — the metadata by index, the anime indices
+    (-1 padded) with their predicted ratings on the host, and the anime table on the device."""
     import torch
     from . import ops
     pos = np.nonzero(np.asarray(user_ids) == int(user_id))[0]
@@ -347,7 +354,60 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
     tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
     k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
     idx, p = ops.predict_topk(tU, tA, head, [int(pos[0])], k, bits.view(np.int32))
-    return _model_recs_rows(meta, idx.cpu().numpy()[0], p.cpu().numpy()[0])
+    return meta, idx.cpu().numpy()[0], p.cpu().numpy()[0], tA
+
+
+# ----------------------------------------------------------------------------------------
+# explain_recs: model_recs with the user's own ratings that put each anime in the list
+# ----------------------------------------------------------------------------------------
+EXPLAIN_WEIGHTS = ("rating", "similarity")
+EXPLAIN_MAX_COUNT = 8    # ANIREC_EXPLAIN_MAX_M
+
+
+def explain_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
+                       types=None, genres=None, count=3, weight="rating", min_rating=0.0):
+    """model_recs_frame with a reason beside every row (``recs.explain_topk``): the rating sees an anime
+    only through the cosine of its row with the user's, so for a listed anime the ``count`` anime of the user's own
+    ratings (those at or above ``min_rating``, in the frame's order) with the largest rating * cosine to it
+    (``weight`` = ``rating``) or the largest cosine alone (``similarity``).  A list longer than
+    anirec_explain_max_k(width) is explained in column blocks of that many (a slot's picks do not depend on the others).
+    The frame has model_recs_frame's columns, the same values, then for r = 1 .. count ``Because_r`` (the anime's
+    Name), ``Because_r_rating`` (the user's rating of it as the frame holds it), ``Because_r_similarity`` and
+    ``Because_r_contribution``; the four cells are empty where the history has no r-th pick or its contribution is
+    not > 0."""
+    import torch
+    from . import _lib, ops, recs
+    count = int(count)
+    if not 1 <= count <= EXPLAIN_MAX_COUNT:
+        raise ValueError("explain_recs: count = %d must be in 1 .. %d" % (count, EXPLAIN_MAX_COUNT))
+    if str(weight).strip().lower() not in EXPLAIN_WEIGHTS:
+        raise ValueError("explain_recs: weight %r is not one of %s" % (weight, ", ".join(EXPLAIN_WEIGHTS)))
+    min_rating = float(min_rating)
+    if not 0.0 <= min_rating <= 1.0:
+        raise ValueError("explain_recs: min_rating = %r must be in [0, 1]" % (min_rating,))
+    meta, idx, p, tA = _model_recs_topk(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
+    frame = _model_recs_rows(meta, idx, p)
+    sub = df[df.user_id == int(user_id)]
+    arow = pd.Index(np.asarray(anime_ids)).get_indexer(sub.anime_id.to_numpy())
+    raw = sub.rating.to_numpy()[arow >= 0]
+    offsets, hist_idx, hist_rating = recs.history_csr(np.zeros(len(raw), np.int64), arow[arow >= 0], raw, [0], min_rating)
+    raw = raw[raw.astype(np.float32) >= np.float32(min_rating)]          # history_csr's own filter: aligned with the CSR
+    assert len(raw) == len(hist_idx)
+    What = ops.rownorm(tA, device=tA.device)
+    step = _lib.explain_max_k(What.shape[1])
+    lists = torch.as_tensor(idx[None, :], device=What.device)
+    outs = [recs.explain_topk(What, lists[:, c:c + step], offsets, hist_idx, hist_rating, m=count, weight=weight)
+            for c in range(0, lists.shape[1], step)]
+    pos, sim, contrib, hist_row = (torch.cat(t, dim=1)[0].cpu().numpy()[idx >= 0] for t in zip(*outs))
+    names = meta["Name"].to_numpy()
+    for r in range(count):
+        ok = (pos[:, r] >= 0) & (contrib[:, r] > 0)
+        at = np.where(ok, pos[:, r], 0)
+        frame["Because_%d" % (r + 1)] = np.where(ok, names[np.where(ok, hist_row[:, r], 0)], None)
+        frame["Because_%d_rating" % (r + 1)] = np.where(ok, raw[at], np.nan) if len(raw) else np.nan
+        frame["Because_%d_similarity" % (r + 1)] = np.where(ok, sim[:, r], np.float32(np.nan))
+        frame["Because_%d_contribution" % (r + 1)] = np.where(ok, contrib[:, r], np.float32(np.nan))
+    return frame
 
 
 # ----------------------------------------------------------------------------------------

@@ -682,6 +682,63 @@ def list_similarity(What, list_idx):
     return sim_max, sim_sum
 
 
+def check_explain(width, k, m):
+    """The argument checks of ``explain_lists`` (no device needed): ValueError naming the limit for a list shorter than
+    one slot or longer than anirec_explain_max_k(width), or ``m`` outside 1 .. ANIREC_EXPLAIN_MAX_M.  Returns
+    (width, k, m)."""
+    dim, k, m = _lib.check_width(width), int(k), int(m)
+    if not 1 <= k <= _lib.explain_max_k(dim):
+        raise ValueError("explain_lists: %d slots per list, 1 .. %d at width %d (a list's rows are held in LDS)"
+                         % (k, _lib.explain_max_k(dim), dim))
+    if not 1 <= m <= _lib.EXPLAIN_MAX_M:
+        raise ValueError("explain_lists: m = %d must be in 1 .. %d (the history entries picked per listed anime)"
+                         % (m, _lib.EXPLAIN_MAX_M))
+    return dim, k, m
+
+
+def explain_lists(What, list_idx, offsets, hist_idx, hist_weight, m):
+    """Why an anime is in a list (anirec_explain_lists): list l holds the rows ``list_idx[l]`` of ``What`` (``rownorm``
+    output; -1 = an empty slot) and comes with the history ``hist_idx[offsets[l]:offsets[l+1]]`` (rows of ``What``)
+    weighted by ``hist_weight``; every present slot gets its ``m`` history entries with the largest
+    ``weight * cosine(slot, entry)``, ties to the lowest position in the history, a NaN product never picked.
+    Returns (pos int32, sim fp32, contrib fp32), each [n_lists, k, m] on the device: the entry's position within the
+    list's own history, its cosine to the listed row and the product; -1 / NaN / NaN where a history has fewer than
+    ``m`` pickable entries and for an empty slot.  The width comes from ``What.shape[1]``.  Raises ValueError for a
+    ``list_idx`` that is not [n_lists, k], k outside 1 .. anirec_explain_max_k(width), m outside 1 .. 8, offsets that
+    are not a CSR of the histories, or an index that is no row of ``What``."""
+    if What.dim() != 2 or list_idx.dim() != 2:
+        raise ValueError("explain_lists: What must be [n_rows, width] and list_idx [n_lists, k]")
+    dim, k, m = check_explain(What.shape[1], list_idx.shape[1], m)
+    if What.shape[0] < 1:
+        raise ValueError("explain_lists: What has no rows")
+    _need_gpu()
+    lib = _lib.load()
+    assert _width(What) == dim
+    dev = What.device
+    li = _i32(list_idx, dev)
+    n_lists = int(li.shape[0])
+    off = torch.as_tensor(offsets).to(torch.int64).cpu()
+    hi, hw = _i32(hist_idx, dev), _f32(hist_weight, dev)
+    if off.dim() != 1 or off.numel() != n_lists + 1 or hi.dim() != 1 or hi.shape != hw.shape:
+        raise ValueError("explain_lists: offsets must be [n_lists + 1], hist_idx and hist_weight one entry per rating")
+    if int(off[0]) != 0 or int(off[-1]) != hi.numel() or (n_lists and bool((off[1:] < off[:-1]).any())):
+        raise ValueError("explain_lists: offsets must rise from 0 to the number of history entries")
+    pos = torch.empty(n_lists, k, m, dtype=torch.int32, device=dev)
+    sim = torch.empty(n_lists, k, m, dtype=torch.float32, device=dev)
+    contrib = torch.empty(n_lists, k, m, dtype=torch.float32, device=dev)
+    if n_lists == 0:
+        return pos, sim, contrib
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    off_d = off.to(dev)
+    _lib.check(lib.anirec_explain_lists(_lib.ptr(What), dim, What.shape[0], _lib.ptr(li), n_lists, k, _lib.ptr(off_d),
+                                        _lib.ptr(hi) if hi.numel() else None, _lib.ptr(hw) if hw.numel() else None, m,
+                                        _lib.ptr(pos), _lib.ptr(sim), _lib.ptr(contrib), _lib.ptr(err), _stream()),
+               "anirec_explain_lists")
+    if int(err.item()):
+        raise ValueError("explain_lists: list or history index out of range")
+    return pos, sim, contrib
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

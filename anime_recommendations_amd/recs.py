@@ -404,6 +404,70 @@ def list_quality(What, lists, k=None, target_row=None, target_anime=None, item_c
     return list_figures(idx, What.shape[0], sims[0], sims[1], target_row, target_anime, item_count, n_raters)
 
 
+EXPLAIN_WEIGHTS = ("rating", "similarity")
+
+
+def history_csr(user_idx, anime_idx, rating, users, min_rating=0.0):
+    """The CSR ``explain_topk`` takes, from a rating table's training columns (``user_idx``, ``anime_idx``: dense
+    indices; ``rating``: the scaled target the trainer uses; NumPy or torch): list i is the ratings of user
+    ``users[i]`` (a repeated user gets the history again) in their order in the table, those below ``min_rating``
+    (compared in fp32) or NaN dropped.  A user without ratings has an empty history.
+    Returns (offsets int64 [len(users) + 1], hist_idx int32 [n], hist_rating fp32 [n]) on the host."""
+    u = _host(user_idx).reshape(-1).astype(np.int64)
+    a = _host(anime_idx).reshape(-1)
+    r = _host(rating).reshape(-1).astype(np.float32)
+    if not len(u) == len(a) == len(r):
+        raise ValueError("history_csr: user_idx, anime_idx and rating must have one entry per rating")
+    users = np.asarray(users, np.int64).reshape(-1)
+    keep = r >= np.float32(min_rating)
+    u, a, r = u[keep], a[keep], r[keep]
+    order = np.argsort(u, kind="stable")                    # by user, the table's order within a user
+    su = u[order]
+    lo, hi = np.searchsorted(su, users, "left"), np.searchsorted(su, users, "right")
+    offsets = np.zeros(len(users) + 1, np.int64)
+    np.cumsum(hi - lo, out=offsets[1:])
+    take = order[np.repeat(lo - offsets[:-1], hi - lo) + np.arange(int(offsets[-1]))]
+    return offsets, a[take].astype(np.int32), r[take]
+
+
+def explain_topk(What_or_A, lists, offsets, hist_idx, hist_rating, m=3, weight="rating", normalised=None, device="cuda:0"):
+    """Why each anime of many lists is there (``ops.explain_lists``): for every listed anime the ``m``
+    entries of the list's own history with the largest ``weight * cosine``.  ``lists``: int [n_lists, k] rows of the
+    anime table, -1 = an empty slot — ``ops.predict_topk``'s, ``diverse_topk``'s, ``group_topk``'s (with the members'
+    histories concatenated) or a folded user's (with the fold-in CSR); list l's history is
+    ``hist_idx[offsets[l]:offsets[l+1]]`` with the scaled ratings ``hist_rating`` (``history_csr``).
+    ``weight``: ``rating`` weights an entry by its rating, ``similarity`` by 1 (the nearest history rows).
+    ``What_or_A``: a device tensor is taken as the normalised table (``ops.rownorm`` output) as it is, a host array as
+    the anime table A and normalised here; ``normalised`` = True / False says which instead.
+    Returns (pos int32, sim fp32, contrib fp32, hist_row int32), each [n_lists, k, m] on the device: ``ops.explain_lists``'
+    three tensors and the anime row at each pos (``hist_idx[offsets[l] + pos]``), -1 where there is no pick."""
+    from . import ops
+    w = str(weight).strip().lower()
+    if w not in EXPLAIN_WEIGHTS:
+        raise ValueError("explain_topk: weight %r is not one of %s" % (weight, ", ".join(EXPLAIN_WEIGHTS)))
+    on_dev = isinstance(What_or_A, torch.Tensor) and What_or_A.is_cuda
+    if normalised is None:
+        normalised = on_dev
+    T = What_or_A if on_dev else torch.as_tensor(np.ascontiguousarray(_host(What_or_A), np.float32), device=device)
+    What = T if normalised else ops.rownorm(T, device=T.device)
+    dev = What.device
+    li = torch.as_tensor(lists, device=dev).to(torch.int32)
+    if li.dim() != 2:
+        raise ValueError("explain_topk: lists must be [n_lists, k]")
+    ops.check_explain(What.shape[1], li.shape[1], m)
+    off = torch.as_tensor(offsets).to(torch.int64).cpu()
+    hi = torch.as_tensor(hist_idx, device=dev).to(torch.int32).reshape(-1)
+    hw = torch.as_tensor(hist_rating, device=dev).to(torch.float32).reshape(-1)
+    if w == "similarity":
+        hw = torch.ones_like(hw)
+    pos, sim, contrib = ops.explain_lists(What, li, off, hi, hw, m)
+    if hi.numel() == 0:
+        return pos, sim, contrib, torch.full_like(pos, -1)
+    at = (off[:-1].to(dev).view(-1, 1, 1) + pos.clamp(min=0).long()).clamp(max=hi.numel() - 1)
+    hist_row = torch.where(pos >= 0, hi[at], torch.full_like(pos, -1))
+    return pos, sim, contrib, hist_row
+
+
 FOLD_STEPS = 100        # Adam iterations of a fold-in (DESIGN.md §4.7)
 FOLD_LR = 0.01          # and their learning rate
 

@@ -823,6 +823,47 @@ int anirec_mmr_rerank(const float *What, int32_t dim, int32_t n_rows, const int3
 int anirec_list_similarity(const float *What, int32_t dim, int32_t n_rows, const int32_t *list_idx, int32_t n_lists,
                            int32_t k, float *out_sim_max, float *out_sim_sum, int32_t *err_flag, void *stream);
 
+/* EXPLAINED LISTS — why an anime is in a list: a predicted rating sees an anime only through the cosine of two rows,
+ * so "recommended because you rated X, Y, Z" has an answer inside the model: the anime of the user's own history whose
+ * rows lie closest to the listed one, each weighted by what the user gave it.
+ * What [n_rows][dim] = the unit rows anirec_rownorm_w writes; list_idx [n_lists][k] = rows of What, -1 = an empty slot
+ * (what anirec_predict_topk*, anirec_mmr_rerank and anirec_group_topk write).  List l's history is entries
+ * hist_offsets[l] .. hist_offsets[l+1]-1 of (hist_idx, hist_weight): anirec_fold_in's CSR, with the same CALLER's
+ * guarantee on the offsets (the ABI carries no count); a repeated anime is two entries.  The three outputs are
+ * [n_lists][k][m].  All arithmetic is fp32 and nothing is contracted.
+ *     sim(s,i)     the k-ordered chain acc = fmaf(What[a_s][t], What[h_i][t], acc), t = 0 .. dim-1, from 0: the chain of
+ *                  anirec_cosine_scores_w, anirec_mmr_rerank and anirec_list_similarity, the same bits
+ *     contrib(s,i) hist_weight[i] * sim(s,i): one rounded product
+ *     order        for a present slot s (list_idx != -1) the history entries by contrib descending, ties (==, so that
+ *                  -0 == +0; twin rows and repeated entries do tie) to the lowest history position; +-inf are ordinary
+ *                  numbers; an entry whose contrib is NaN (a zero row normalised to NaN, 0 * inf, a NaN weight) is
+ *                  never picked.  A history entry equal to the listed anime is not special-cased.
+ *     rank r < m   out_pos[l][s][r] = the entry's position within the list's own history (0-based),
+ *                  out_sim[l][s][r] = sim, out_contrib[l][s][r] = contrib
+ * With fewer than m pickable entries the rest of the slot's row is -1 / NaN / NaN (the NaN 0x7FC00000); an absent slot
+ * is -1 / NaN / NaN throughout.  The order is total, so the result does not depend on how the history is split over
+ * lanes, waves or passes, and a list's outputs depend on that list alone: not on the other lists, its position in the
+ * call, or the run.
+ * One workgroup per list, the list's rows staged once in LDS, the history streamed through a second LDS image in tiles
+ * of anirec_explain_tile(dim, k) entries (a history of any length runs through that loop), each slot's running top-m in
+ * registers.  anirec_explain_max_k(dim) = min(128, 16384 / dim) = 128, 128, 128, 64 slots; both queries return 0 for a
+ * bad argument.  No workspace, no atomics, stream-ordered and graph-capturable.
+ * Bad dim, n_rows < 1, a negative count, k < 1 or k > anirec_explain_max_k(dim), m < 1 or m > ANIREC_EXPLAIN_MAX_M, a
+ * NULL pointer with n_lists > 0 (hist_idx / hist_weight may be NULL only when every history is empty): ANIREC_EINVAL
+ * before anything is enqueued or written.  n_lists == 0: ANIREC_OK, nothing enqueued.  Otherwise every element of the
+ * three outputs and *err_flag (device) is written: *err_flag becomes 1 on a list index below -1 or at or above n_rows,
+ * a history index outside [0, n_rows), a negative or decreasing offsets pair, or a history of more than INT32_MAX
+ * entries (0 without one): that list's whole output is -1 / NaN / NaN, nothing is read through the bad value (every
+ * index of the list and its history is validated before any row is gathered), the other lists are unaffected
+ * (anirec_predict_rank's convention). */
+#define ANIREC_EXPLAIN_MAX_M 8
+size_t anirec_explain_max_k(int32_t dim);
+size_t anirec_explain_tile(int32_t dim, int32_t k);
+int anirec_explain_lists(const float *What, int32_t dim, int32_t n_rows, const int32_t *list_idx, int32_t n_lists,
+                         int32_t k, const int64_t *hist_offsets, const int32_t *hist_idx, const float *hist_weight,
+                         int32_t m, int32_t *out_pos, float *out_sim, float *out_contrib, int32_t *err_flag,
+                         void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
