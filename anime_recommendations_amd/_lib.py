@@ -29,6 +29,9 @@ EXPLAIN_MAX_M = 8           # ANIREC_EXPLAIN_MAX_M: the most history entries ani
 EXPLAIN_MAX_K = 128         # anirec_explain_max_k(dim) = min(EXPLAIN_MAX_K, EXPLAIN_IMAGE_FLOATS // dim)
 EXPLAIN_IMAGE_FLOATS = 16384
 EXPLAIN_TILE_FLOATS = 8192  # anirec_explain_tile(dim, k): dim * tile and k * (tile | 1) floats both within this
+KMEANS_MAX_K = 4096         # ANIREC_KMEANS_MAX_K: the most centroids anirec_kmeans_assign / anirec_kmeans_fit take
+KMEANS_MAX_ITER = 1000      # anirec_kmeans_fit: the most iterations one call enqueues
+KMEANS_IMAGE_FLOATS = 32768  # anirec_kmeans_tile(dim) = KMEANS_IMAGE_FLOATS // dim: the centroids of one LDS image
 # anirec_train_desc.optimizer (ANIREC_OPT_*)
 OPT_ADAM, OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
 # anirec_train_desc.loss (ANIREC_LOSS_*) and .activation / the predict calls' activation (ANIREC_ACT_*)
@@ -242,6 +245,11 @@ PROTOTYPES = {
     "anirec_explain_max_k": (_sz, [_i32]),
     "anirec_explain_tile": (_sz, [_i32, _i32]),
     "anirec_explain_lists": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # spherical k-means on an embedding table (clustered tables)
+    "anirec_kmeans_tile": (_sz, [_i32]),
+    "anirec_kmeans_assign": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "anirec_kmeans_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "anirec_kmeans_fit": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -274,6 +282,11 @@ def explain_tile(width, k) -> int:
     if not 1 <= k <= explain_max_k(w):
         raise ValueError("explain_tile: k = %d must be in 1 .. %d at width %d" % (k, explain_max_k(w), w))
     return min(EXPLAIN_TILE_FLOATS // w, (EXPLAIN_TILE_FLOATS // k - 1) & ~7)
+
+
+def kmeans_tile(width) -> int:
+    """anirec_kmeans_tile: the centroids anirec_kmeans_assign holds in LDS at once at a (checked) row width."""
+    return KMEANS_IMAGE_FLOATS // check_width(width)
 
 
 _lib = None

@@ -411,6 +411,102 @@ def explain_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
 
 
 # ----------------------------------------------------------------------------------------
+# clusters: the table as a whole — taste communities of the users, micro-genres of the anime
+# ----------------------------------------------------------------------------------------
+CLUSTER_TABLES = ("anime", "user")
+CLUSTER_PERCENTILE = 80.0    # a user's favourites, as user_prefs takes them
+CLUSTERS_COLUMNS = ["cluster", "size", "mean_similarity", "top_members", "top_genres"]
+_SEP = " | "
+
+
+def cluster_table_name(table):
+    t = str(table).strip().lower()
+    if t not in CLUSTER_TABLES:
+        raise ValueError("clusters: table %r is not one of %s" % (table, ", ".join(CLUSTER_TABLES)))
+    return t
+
+
+def cluster_genre_counts(table, meta, n_rows, fav_bits=None):
+    """(names, counts int64 [n_rows, len(names)]) of the rows of a clustered table: for ``anime`` the Genres tokens an
+    anime carries (``category_table``), for ``user`` the genre profile of the user's favourites (``recs.fave_profile``
+    over ``fav_bits``, ``favourite_bits`` output)."""
+    from . import recs
+    names, bits = category_table(meta, "Genres")
+    if not names:
+        return names, np.zeros((n_rows, 0), np.int64)
+    if cluster_table_name(table) == "anime":
+        flags = np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), axis=1, bitorder="little")[:, :len(names)]
+        return names, flags.astype(np.int64)
+    if fav_bits is None:
+        raise ValueError("clusters: the user table's genres need the users' favourite bits")
+    return names, recs.fave_profile(fav_bits, bits, len(names)).cpu().numpy().astype(np.int64)
+
+
+def clusters_frame(fit, table, ids, meta, top=10, n_genres=5, fav_bits=None):
+    """One row per cluster of a ``recs.cluster_rows`` result on the ``anime`` or ``user`` table (``ids``: the table's
+    index -> id array; ``meta``: ``metadata_by_index``): ``cluster``, ``size``, ``mean_similarity`` (the members' mean
+    cosine to the centroid, float64 on the host; empty for an empty cluster), ``top_members`` (the ``top`` members
+    nearest the centroid, nearest first, ties to the lower row: anime Names, user ids; joined by " | ") and
+    ``top_genres`` (the ``n_genres`` leading genres as "Genre (count)": for anime the members' genre counts, for users
+    the members' summed favourite profiles)."""
+    table = cluster_table_name(table)
+    top = int(top)
+    if top < 1:
+        raise ValueError("clusters: top = %d must be >= 1" % top)
+    a = fit["assign"].cpu().numpy()
+    sim = fit["sim"].cpu().numpy().astype(np.float64)
+    k = int(fit["C"].shape[0])
+    ids = np.asarray(ids)
+    if len(a) != len(ids):
+        raise ValueError("clusters: %d assignments for a table of %d ids" % (len(a), len(ids)))
+    names, counts = cluster_genre_counts(table, meta, len(ids), fav_bits)
+    label = meta["Name"].to_numpy() if table == "anime" else None
+    rows = []
+    for c in range(k):
+        members = np.flatnonzero(a == c)
+        order = members[np.lexsort((members, -sim[members]))][:top]
+        if table == "anime":
+            shown = [str(label[i]) if isinstance(label[i], str) else str(ids[i]) for i in order]
+        else:
+            shown = [str(ids[i]) for i in order]
+        tally = counts[members].sum(axis=0) if len(names) else np.zeros(0, np.int64)
+        lead = [g for g in np.lexsort((np.arange(len(names)), -tally))[:int(n_genres)] if tally[g] > 0]
+        rows.append({"cluster": c, "size": len(members),
+                     "mean_similarity": float(sim[members].mean()) if len(members) else np.nan,
+                     "top_members": _SEP.join(shown),
+                     "top_genres": _SEP.join("%s (%d)" % (names[g], tally[g]) for g in lead)})
+    return pd.DataFrame(rows, columns=CLUSTERS_COLUMNS)
+
+
+def cluster_assignments_frame(fit, table, ids):
+    """id, cluster, similarity of every row of the clustered table: ``anime_id`` / ``user_id``, ``cluster`` (-1 for a
+    row without one: a zero embedding row), ``similarity`` (its cosine to the cluster's centroid, fp32)."""
+    table = cluster_table_name(table)
+    return pd.DataFrame({table + "_id": np.asarray(ids), "cluster": fit["assign"].cpu().numpy(),
+                         "similarity": fit["sim"].cpu().numpy()})
+
+
+def cluster_query_row(table, query, user_ids, anime_ids, anime_df):
+    """The table row of a ``cluster_query``: for the anime table an anime id (an integer) or a title (resolved as
+    similar_anime resolves it), for the user table a user id."""
+    table = cluster_table_name(table)
+    q = str(query).strip()
+    try:
+        num = int(q)
+    except ValueError:
+        num = None
+    if table == "user":
+        if num is None:
+            raise ValueError("clusters: cluster_query %r is not a user id" % (query,))
+        return user_index(user_ids, num)
+    aid = num if num is not None and num in set(np.asarray(anime_ids).tolist()) else find_anime_id(q, anime_df)
+    pos = np.nonzero(np.asarray(anime_ids) == aid)[0]
+    if len(pos) == 0:
+        raise ValueError("clusters: anime %r is not in the model's anime table" % (query,))
+    return int(pos[0])
+
+
+# ----------------------------------------------------------------------------------------
 # diverse_recs: model_recs with a greedy MMR re-rank of the best `pool` candidates
 # ----------------------------------------------------------------------------------------
 def _list_cosines(Wh, idx):

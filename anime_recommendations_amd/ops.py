@@ -739,6 +739,78 @@ def explain_lists(What, list_idx, offsets, hist_idx, hist_weight, m):
     return pos, sim, contrib
 
 
+def check_kmeans(dim, k, max_iter=1):
+    """The argument checks of ``kmeans_assign`` / ``kmeans_fit`` (no device needed): ValueError naming the limit for a
+    width the kernels lack, ``k`` outside 1 .. ANIREC_KMEANS_MAX_K or ``max_iter`` outside 1 .. 1000.  Returns
+    (dim, k, max_iter)."""
+    dim, k, max_iter = _lib.check_width(dim), int(k), int(max_iter)
+    if not 1 <= k <= _lib.KMEANS_MAX_K:
+        raise ValueError("kmeans: k = %d centroids must be in 1 .. %d (KMEANS_MAX_K)" % (k, _lib.KMEANS_MAX_K))
+    if not 1 <= max_iter <= _lib.KMEANS_MAX_ITER:
+        raise ValueError("kmeans: max_iter = %d must be in 1 .. %d (the iterations one call enqueues)"
+                         % (max_iter, _lib.KMEANS_MAX_ITER))
+    return dim, k, max_iter
+
+
+def _kmeans_tables(What, C, what):
+    if What.dim() != 2 or C.dim() != 2 or What.shape[1] != C.shape[1]:
+        raise ValueError("%s: What must be [n_rows, width] and C [k, width] of one width" % what)
+    if What.shape[0] < 1:
+        raise ValueError("%s: What has no rows" % what)
+
+
+def kmeans_assign(What, C):
+    """The nearest centroid of every row (anirec_kmeans_assign): ``What`` [n_rows, width] unit rows
+    (``rownorm`` output), ``C`` [k, width] centroids.  Returns (assign int32 [n_rows], sim fp32 [n_rows]) on the device:
+    the centroid with the largest cosine (the library's k-ordered fp32 chain), ties to the lowest centroid, a NaN cosine
+    never picked; -1 / NaN for a row that is not usable (an element that is not finite or above 2 in magnitude) or has
+    no pickable centroid.  Raises ValueError for tables that are not 2-D of one supported width, no rows, or k outside
+    1 .. KMEANS_MAX_K."""
+    _kmeans_tables(What, C, "kmeans_assign")
+    dim, k, _ = check_kmeans(What.shape[1], C.shape[0])
+    _need_gpu()
+    lib = _lib.load()
+    dev = What.device
+    C = _f32(C, dev)
+    assert _width(What, C) == dim
+    What = What.contiguous()
+    n = int(What.shape[0])
+    assign = torch.empty(n, dtype=torch.int32, device=dev)
+    sim = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.check(lib.anirec_kmeans_assign(_lib.ptr(What), dim, n, _lib.ptr(C), k, _lib.ptr(assign), _lib.ptr(sim), _stream()),
+               "anirec_kmeans_assign")
+    return assign, sim
+
+
+def kmeans_fit(What, C0, max_iter=50):
+    """Spherical k-means from the centroids ``C0`` [k, width] on the unit rows ``What`` [n_rows, width]
+    (anirec_kmeans_fit): at most ``max_iter`` Lloyd iterations, all enqueued at once, stopping on the
+    device when no row changes its centroid.  Exact and order-free: the centroids are int64 sums of the rows' fixed-point
+    values normalised in fp64, so the result does not depend on the order of the rows' arrival.
+    Returns (C fp32 [k, width], assign int32 [n_rows], sim fp32 [n_rows], count int32 [k]) on the device — assign, sim
+    and count always belong to the returned C — and (iters int, converged bool).  ``C0`` is not modified.  Raises
+    ValueError as ``kmeans_assign`` does, and for ``max_iter`` outside 1 .. 1000."""
+    _kmeans_tables(What, C0, "kmeans_fit")
+    dim, k, max_iter = check_kmeans(What.shape[1], C0.shape[0], max_iter)
+    _need_gpu()
+    lib = _lib.load()
+    dev = What.device
+    C = _f32(C0, dev).clone()
+    assert _width(What, C) == dim
+    What = What.contiguous()
+    n = int(What.shape[0])
+    assign = torch.empty(n, dtype=torch.int32, device=dev)
+    sim = torch.empty(n, dtype=torch.float32, device=dev)
+    count = torch.empty(k, dtype=torch.int32, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.anirec_kmeans_workspace_bytes(n, k, dim)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.anirec_kmeans_fit(_lib.ptr(What), dim, n, _lib.ptr(C), k, max_iter, _lib.ptr(assign), _lib.ptr(sim),
+                                     _lib.ptr(count), _lib.ptr(info), _lib.ptr(ws), ws.numel(), _stream()),
+               "anirec_kmeans_fit")
+    iters, converged = info.tolist()
+    return C, assign, sim, count, int(iters), bool(converged)
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

@@ -468,6 +468,73 @@ def explain_topk(What_or_A, lists, offsets, hist_idx, hist_rating, m=3, weight="
     return pos, sim, contrib, hist_row
 
 
+def _unit_rows(What_or_table, normalised, device):
+    """A table as ``explain_topk`` takes it: a device tensor is the normalised table as it is, a host array the raw
+    table, normalised here; ``normalised`` = True / False says which instead."""
+    from . import ops
+    on_dev = isinstance(What_or_table, torch.Tensor) and What_or_table.is_cuda
+    if normalised is None:
+        normalised = on_dev
+    T = What_or_table if on_dev else torch.as_tensor(np.ascontiguousarray(_host(What_or_table), np.float32), device=device)
+    if T.dim() != 2:
+        raise ValueError("a table must be [n_rows, width]")
+    return T if normalised else ops.rownorm(T, device=T.device)
+
+
+def usable_rows(What):
+    """bool [n_rows] on the device: the rows anirec_kmeans_assign takes (every element finite and at most 2 in
+    magnitude; a zero row normalised to NaN is not one)."""
+    return (What.abs() <= 2).all(dim=1)
+
+
+def cluster_rows(What_or_table, k, seed=0, max_iter=50, init=None, normalised=None, device="cuda:0"):
+    """Spherical k-means on an embedding table (``ops.kmeans_fit``): ``k`` clusters of the unit rows by
+    cosine.  ``What_or_table``: a device tensor is taken as the normalised table (``ops.rownorm`` output) as it is, a
+    host array as the raw table and normalised here; ``normalised`` = True / False says which instead.
+    ``init``: None draws k distinct usable rows with ``np.random.default_rng(seed).choice`` (sorted row order kept as
+    drawn) as the first centroids; an int array [k] names the rows; a float array [k, width] is the centroids themselves.
+    Returns a dict: C fp32 [k, width], assign int32 [n_rows] (-1 for a row that is not usable), sim fp32 [n_rows],
+    count int32 [k] (device tensors), iters, converged, init_rows (the drawn or given rows as a NumPy array, else None).
+    Raises ValueError for k outside 1 .. KMEANS_MAX_K, fewer usable rows than k, or an ``init`` of another shape."""
+    from . import ops
+    shape = tuple(What_or_table.shape)
+    if len(shape) != 2:
+        raise ValueError("cluster_rows: a table must be [n_rows, width]")
+    # the refusals that need no device come first
+    dim, k, max_iter = ops.check_kmeans(shape[1], k, max_iter)
+    if k > shape[0]:
+        raise ValueError("cluster_rows: k = %d clusters but the table has only %d usable rows" % (k, shape[0]))
+    init_rows = arr = None
+    if init is not None:
+        arr = np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init)
+        if arr.ndim == 1 and arr.shape[0] == k and np.issubdtype(arr.dtype, np.integer):
+            if arr.min() < 0 or arr.max() >= shape[0]:
+                raise ValueError("cluster_rows: init row out of range")
+            init_rows = arr.astype(np.int64)
+        elif arr.shape != (k, dim) or not np.issubdtype(arr.dtype, np.floating):
+            raise ValueError("cluster_rows: init must be %d row indices or a float [%d, %d] array of centroids, got shape %s"
+                             % (k, k, dim, tuple(arr.shape)))
+    What = _unit_rows(What_or_table, normalised, device)
+    if init is None:
+        usable = np.flatnonzero(usable_rows(What).cpu().numpy())
+        if len(usable) < k:
+            raise ValueError("cluster_rows: k = %d clusters but the table has only %d usable rows" % (k, len(usable)))
+        init_rows = np.random.default_rng(seed).choice(usable, size=k, replace=False)
+    C0 = What[torch.as_tensor(init_rows, device=What.device)] if init_rows is not None else \
+        torch.as_tensor(np.ascontiguousarray(arr, np.float32), device=What.device)
+    C, assign, sim, count, iters, converged = ops.kmeans_fit(What, C0, max_iter)
+    return dict(C=C, assign=assign, sim=sim, count=count, iters=iters, converged=converged, init_rows=init_rows)
+
+
+def assign_clusters(C, rows, normalised=None, device="cuda:0"):
+    """The cluster of rows outside the fitted table — folded-in users, new anime — by an existing clustering, no refit:
+    ``ops.kmeans_assign`` on ``rows`` (a device tensor: unit rows as they are; a host array: raw rows, normalised here;
+    ``normalised`` says which instead) against the centroids ``C``.  Returns (assign int32, sim fp32) on the device."""
+    from . import ops
+    What = _unit_rows(rows, normalised, device)
+    return ops.kmeans_assign(What, torch.as_tensor(C, device=What.device))
+
+
 FOLD_STEPS = 100        # Adam iterations of a fold-in (DESIGN.md §4.7)
 FOLD_LR = 0.01          # and their learning rate
 

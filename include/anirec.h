@@ -864,6 +864,49 @@ int anirec_explain_lists(const float *What, int32_t dim, int32_t n_rows, const i
                          int32_t m, int32_t *out_pos, float *out_sim, float *out_contrib, int32_t *err_flag,
                          void *stream);
 
+/* CLUSTERED TABLES — spherical k-means (Lloyd's algorithm on unit rows, the cosine as similarity) on an embedding table:
+ * the view of the table as a whole that the per-row calls above cannot give.  Exact and order-free: the result does not
+ * depend on how the rows are dealt to lanes, waves or workgroups, and a NumPy restatement reproduces it bit for bit.
+ * What [n_rows][dim] = the unit rows anirec_rownorm_w writes; C [k][dim] = the centroids; dim one of 32, 64, 128, 256.
+ *   the assign rule
+ *     sim(i,c)    the k-ordered chain acc = fmaf(What[i][t], C[c][t], acc), t = 0 .. dim-1, from 0: the chain of
+ *                 anirec_cosine_scores_w, the same bits; nothing is contracted beyond it
+ *     usable row  every element finite and |x| <= 2; an unusable row (a zero row normalised to NaN) gets assignment -1
+ *                 and sim NaN (0x7FC00000) and contributes to no centroid
+ *     pick        for a usable row the centroid with the largest sim; ties (==, so that -0 == +0) to the lowest c; a
+ *                 NaN sim is never picked; +-inf are ordinary numbers; no pickable centroid: -1 / NaN.  A row's pick
+ *                 depends on that row and C alone.
+ *   the update rule
+ *     q(x)        llrint((double)x * 2^30): the product is exact, the rounding to nearest even
+ *     S_c[t]      the sum of q(What[i][t]) over the rows assigned to c, as int64: a sum of integers, its bits do not
+ *                 depend on order (2^31 rows of |x| <= 2 stay inside int64); cnt_c = the number of those rows
+ *     cnt_c > 0   d_t = (double)S_c[t] (rounded to nearest even); nn = the chain over ascending t from 0.0 of a rounded
+ *                 fp64 multiply d_t * d_t and a rounded fp64 add (no fma); with nn > 0: C[c][t] = (float)(d_t / sqrt(nn)),
+ *                 IEEE fp64 sqrt and divide, one rounding to fp32
+ *     cnt_c == 0 or nn == 0: the centroid keeps its bits (a NaN centroid, which nothing is ever assigned to, included)
+ *   the fit loop   a_0 = -2 everywhere.  Iteration j = 1 .. max_iter: assign with the current C -> a_j; changed_j =
+ *                 #{i : a_j[i] != a_(j-1)[i]}; changed_j == 0: stop, C untouched, converged; otherwise update C.  After
+ *                 max_iter iterations without a stop one last assign pass is made with the final C.  So out_assign,
+ *                 out_sim and out_count [k] (= cnt of out_assign) always belong to the returned C.
+ *                 out_info = {iterations run (the j of the stop, or max_iter), converged 0/1}.
+ * anirec_kmeans_assign is the assign rule alone (rows of any table against a given clustering).  The centroids are staged
+ * in LDS anirec_kmeans_tile(dim) = 32768 / dim at a time (0 for a bad dim); a larger k runs as passes over tiles with the
+ * running best kept per row, and the pick order is total, so the tiling cannot change a bit.
+ * anirec_kmeans_fit enqueues all max_iter iterations at once, plain launches only, no host read-back, no cooperative
+ * grid: stream-ordered and graph-capturable; once converged the remaining launches return on a device flag.  Integer
+ * atomics only.  ws: anirec_kmeans_workspace_bytes(n_rows, k, dim) bytes (0 for a bad argument), 8-byte aligned; the
+ * result does not depend on what it held before the call.
+ * Bad dim, n_rows < 1, k < 1 or k > ANIREC_KMEANS_MAX_K, max_iter < 1 or max_iter > 1000, a NULL pointer, ws_bytes too
+ * small: ANIREC_EINVAL before anything is enqueued or written.  Otherwise every element of every output is written. */
+#define ANIREC_KMEANS_MAX_K 4096
+size_t anirec_kmeans_tile(int32_t dim);
+int anirec_kmeans_assign(const float *What, int32_t dim, int32_t n_rows, const float *C, int32_t k,
+                         int32_t *out_assign, float *out_sim, void *stream);
+size_t anirec_kmeans_workspace_bytes(int32_t n_rows, int32_t k, int32_t dim);
+int anirec_kmeans_fit(const float *What, int32_t dim, int32_t n_rows, float *C_inout, int32_t k, int32_t max_iter,
+                      int32_t *out_assign, float *out_sim, int32_t *out_count, int32_t *out_info,
+                      void *ws, size_t ws_bytes, void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
