@@ -47,6 +47,9 @@ GROUP_MEAN, GROUP_MIN, GROUP_MAX = 0, 1, 2
 GROUP_MODES = {"mean": GROUP_MEAN, "least_misery": GROUP_MIN, "min": GROUP_MIN, "most_pleasure": GROUP_MAX,
                "max": GROUP_MAX}
 GROUP_MAX_MEMBERS = 64
+# anirec_cooc_scores: the similarity of two items' liked-by sets (ANIREC_COOC_*)
+COOC_COSINE, COOC_JACCARD, COOC_CONFIDENCE = 0, 1, 2
+COOC_MEASURES = {"cosine": COOC_COSINE, "jaccard": COOC_JACCARD, "confidence": COOC_CONFIDENCE}
 
 
 class AnirecError(RuntimeError):
@@ -250,6 +253,17 @@ PROTOTYPES = {
     "anirec_kmeans_assign": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "anirec_kmeans_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "anirec_kmeans_fit": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # item-kNN from co-occurrence: popcount similarity rows, the select / the rank over rows a caller holds, history scores
+    "anirec_cooc_chunk_words": (_sz, []),
+    "anirec_cooc_workspace_bytes": (_sz, [_i32, _i32]),
+    "anirec_cooc_scores": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                     _vp]),
+    "anirec_rows_topk_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "anirec_rows_topk": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "anirec_rows_rank": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "anirec_itemknn_lds_items": (_sz, []),
+    "anirec_itemknn_workspace_bytes": (_sz, [_i32, _i32]),
+    "anirec_itemknn_scores": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

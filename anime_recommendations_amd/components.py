@@ -241,6 +241,53 @@ def similar_anime_frame(A, anime_ids, anime_df, syn_df, name, count, types=None,
 
 
 # ----------------------------------------------------------------------------------------
+# also_liked: "people who liked this also liked ...", from the ratings alone
+# ----------------------------------------------------------------------------------------
+COOC_MEASURES = ("cosine", "jaccard", "confidence")
+
+
+def _np(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def also_liked_frame(df, anime_df, syn_df, name, count, types=None, genres=None, liked_min_rating=0.0,
+                     measure="cosine", shrink=0.0, min_support=1):
+    """The anime most often liked together with the query anime: no model takes part.  A user LIKED an anime when
+    ``df``'s rating of the pair is at or above ``liked_min_rating`` (0.0 = every rating counts); the similarity of two
+    anime is the ``measure`` (cosine, jaccard, confidence) of their liked-by sets (``ops.cooc_scores``), the list the
+    exact select's (``ops.rows_topk``: larger first, ties by index) over the anime that pass the optional Type / Genre
+    filters and share at least max(1, ``min_support``) users with the query.  Returns (frame, filename): similar_anime's
+    columns with the measure as ``Similarity``, then ``Liked_by_both`` (the users who liked both) and ``Liked_by`` (those
+    who liked the listed anime).  The anime index is the rating frame's own (order of first appearance)."""
+    from . import ops, recs
+    measure = str(measure).strip().lower()
+    if measure not in COOC_MEASURES:
+        raise ValueError("cooc_measure %r is not one of %s" % (measure, ", ".join(COOC_MEASURES)))
+    ops.check_cooc(measure, shrink, min_support)
+    user_ids, anime_ids = index_tables({}, df)
+    qid = find_anime_id(name, anime_df)
+    pos = np.nonzero(np.asarray(anime_ids) == qid)[0]
+    if len(pos) == 0:
+        raise ValueError("anime %r (id %d) has no rating in the main data frame" % (name, qid))
+    q = int(pos[0])
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    keep = filter_mask(meta, anime_df, types, genres)
+    ui, ai, r = rating_indices(df, user_ids, anime_ids)
+    liked = r.astype(np.float32) >= np.float32(liked_min_rating)
+    bits = recs.item_bits(ui[liked], ai[liked], len(user_ids), len(anime_ids))
+    k = _topk_count(count, "a_query_number", len(anime_ids) - 1)
+    sim, cnt, excl, pop = ops.cooc_scores(bits, len(user_ids), [q], measure, shrink, min_support, count=True, excl=True,
+                                          pop=True)
+    idx, s = ops.rows_topk(sim, k, keep=keep.astype(np.uint8), wbits=excl)
+    idx, s, cnt, pop = _np(idx)[0], _np(s)[0], _np(cnt)[0], _np(pop)
+    frame = _similar_anime_rows(meta, idx, s)
+    ok = idx >= 0
+    frame["Liked_by_both"] = cnt[idx[ok]].astype(np.int64)
+    frame["Liked_by"] = pop[idx[ok]].astype(np.int64)
+    return frame, clean(name) + "_also_liked.csv"
+
+
+# ----------------------------------------------------------------------------------------
 # similar_users
 # ----------------------------------------------------------------------------------------
 def fave_anime(df, anime_df, user_id, num_faves, tv_only):
@@ -735,10 +782,23 @@ def _tables_of(model, table):
     return U, A
 
 
-BASELINES = ("popularity",)
+BASELINES = ("popularity", "itemknn")
+ITEMKNN_DEFAULTS = {"neighbours": 50, "measure": "cosine", "shrink": 0.0, "min_support": 1, "min_rating": 0.0}
 
 
-def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None):
+def baseline_names(baseline):
+    """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in BASELINES' order: None -> (), a name or a
+    sequence of names; ValueError for anything else."""
+    if baseline is None:
+        return ()
+    names = [baseline] if isinstance(baseline, str) else list(baseline)
+    for b in names:
+        if b not in BASELINES:
+            raise ValueError("baseline %r is not supported (supported: %s, or None)" % (b, ", ".join(BASELINES)))
+    return tuple(b for b in BASELINES if b in names)
+
+
+def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -747,24 +807,40 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     ``baseline="popularity"``: the same targets under the same bits ranked by the number of training ratings of each
     anime instead (``recs.popularity_scores``, ``ops.score_rank``) — what recommending the most-rated unseen anime to
     everyone scores; the frame gains hit_rate_popularity / ndcg_popularity, the summary popularity_mrr,
-    popularity_mean_rank, popularity_hit_rate@k and popularity_ndcg@k.  None: neither."""
+    popularity_mean_rank, popularity_hit_rate@k and popularity_ndcg@k.
+    ``baseline="itemknn"``: the same targets under the same bits ranked by an item-kNN fitted on the TRAINING slice alone
+    (``recs.itemknn_fit`` / ``recs.itemknn_rank``), each listed user's history that user's training
+    ratings at or above the threshold with weight 1; the same columns and keys under the name itemknn.  ``itemknn``: a
+    dict overriding ITEMKNN_DEFAULTS (neighbours, measure, shrink, min_support, min_rating).
+    A sequence of names gives both, popularity first.  None: neither."""
     import torch
     from . import ops, recs, weights_io
-    if baseline is not None and baseline not in BASELINES:
-        raise ValueError("baseline %r is not supported (supported: %s, or None)" % (baseline, ", ".join(BASELINES)))
+    baselines = baseline_names(baseline)
+    knn_par = dict(ITEMKNN_DEFAULTS)
+    for key, v in (itemknn or {}).items():
+        if key not in knn_par:
+            raise ValueError("itemknn parameter %r is not one of %s" % (key, ", ".join(ITEMKNN_DEFAULTS)))
+        knn_par[key] = v
     U, A = _tables_of(model, table)
     ks = sorted({int(k) for k in ks})
     if not ks or ks[0] < 1:
         raise ValueError("eval_k must list at least one k >= 1 (got %r)" % (ks,))
     users, row, anime, train = held_out_targets(table, test_size, min_rating)
-    base_rank = np.zeros(0, np.int32)
+    base_rank = {b: np.zeros(0, np.int32) for b in baselines}
     if len(row):
         tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
         seen = recs.listed_seen_bits(table.user[train], table.anime[train], users, table.n_users, table.n_anime)
         rank, _ = ops.predict_rank(tU, tA, weights_io.model_head(model), users, row, anime, watched_bits=seen)
-        if baseline == "popularity":
+        if "popularity" in baselines:
             score = recs.popularity_scores(table.anime[train], table.n_anime, table.n_users).to(seen.device)
-            base_rank = ops.score_rank(score, len(users), row, anime, watched_bits=seen)
+            base_rank["popularity"] = ops.score_rank(score, len(users), row, anime, watched_bits=seen)
+        if "itemknn" in baselines:
+            knn = recs.itemknn_fit(table.user[train], table.anime[train], table.rating[train], table.n_users,
+                                   table.n_anime, knn_par["min_rating"], int(knn_par["neighbours"]), knn_par["measure"],
+                                   knn_par["shrink"], knn_par["min_support"], device=seen.device)
+            off, hist, _ = recs.history_csr(table.user[train], table.anime[train], table.rating[train], users,
+                                            min_rating=knn_par["min_rating"])
+            base_rank["itemknn"] = recs.itemknn_rank(knn, off, hist, None, seen, row, anime)
     else:
         rank = np.zeros(0, np.int32)
     m = recs.ranking_metrics(rank, ks)
@@ -774,14 +850,14 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     for k in ks:
         summary["hit_rate@%d" % k] = m["hit_rate"][k]
         summary["ndcg@%d" % k] = m["ndcg"][k]
-    if baseline == "popularity":
-        b = recs.ranking_metrics(base_rank, ks)
-        frame["hit_rate_popularity"] = [b["hit_rate"][k] for k in ks]
-        frame["ndcg_popularity"] = [b["ndcg"][k] for k in ks]
-        summary["popularity_mrr"], summary["popularity_mean_rank"] = b["mrr"], b["mean_rank"]
+    for name in baselines:
+        b = recs.ranking_metrics(base_rank[name], ks)
+        frame["hit_rate_" + name] = [b["hit_rate"][k] for k in ks]
+        frame["ndcg_" + name] = [b["ndcg"][k] for k in ks]
+        summary[name + "_mrr"], summary[name + "_mean_rank"] = b["mrr"], b["mean_rank"]
         for k in ks:
-            summary["popularity_hit_rate@%d" % k] = b["hit_rate"][k]
-            summary["popularity_ndcg@%d" % k] = b["ndcg"][k]
+            summary["%s_hit_rate@%d" % (name, k)] = b["hit_rate"][k]
+            summary["%s_ndcg@%d" % (name, k)] = b["ndcg"][k]
     return frame, summary
 
 

@@ -1482,7 +1482,8 @@ constexpr int kRankBlocks = 1024;
 // watched words of the target's row (each lane reads its own: two distinct addresses per load), the count stays in a
 // register and the wave adds up once.  No workspace, no atomics, no LDS.
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_score_rank(const float *__restrict__ score, int n_anime,
+// ld: floats between the score rows of two users (anirec_rows_rank); 0 = the one shared vector.
+__global__ __launch_bounds__(256) void k_score_rank(const float *__restrict__ score_rows, size_t ld, int n_anime,
                                                     const uint32_t *__restrict__ watched, int n_users,
                                                     const int32_t *__restrict__ trow, const int32_t *__restrict__ tanime,
                                                     int n_targets, int32_t *__restrict__ rank, int32_t *__restrict__ err) {
@@ -1497,6 +1498,7 @@ __global__ __launch_bounds__(256) void k_score_rank(const float *__restrict__ sc
     }
     return;
   }
+  const float *__restrict__ score = score_rows + (size_t)row * ld;
   const uint32_t kt = score_key(score[at]);
   const uint32_t *wr = watched ? watched + (size_t)row * (size_t)((n_anime + 31) >> 5) : nullptr;
   int cnt = 0;
@@ -1586,8 +1588,21 @@ int anirec_score_rank(const float *score, int32_t n_anime, const uint32_t *watch
   if (!score || !target_row || !target_anime || !out_rank || !err_flag) return ANIREC_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
-  hipLaunchKernelGGL(k_score_rank, dim3(((unsigned)n_targets + 3u) / 4u), dim3(256), 0, s, score, n_anime, watched,
-                     n_users, target_row, target_anime, n_targets, out_rank, err_flag);
+  hipLaunchKernelGGL(k_score_rank, dim3(((unsigned)n_targets + 3u) / 4u), dim3(256), 0, s, score, (size_t)0, n_anime,
+                     watched, n_users, target_row, target_anime, n_targets, out_rank, err_flag);
+  return (int)hipGetLastError();
+}
+
+int anirec_rows_rank(const float *scores, int64_t ld, int32_t n_anime, const uint32_t *watched, int32_t n_users,
+                     const int32_t *target_row, const int32_t *target_anime, int32_t n_targets, int32_t *out_rank,
+                     int32_t *err_flag, void *stream) {
+  if (n_anime < 1 || n_users < 0 || n_targets < 0 || (ld != 0 && ld < n_anime)) return ANIREC_EINVAL;
+  if (n_targets == 0) return ANIREC_OK;
+  if (!scores || !target_row || !target_anime || !out_rank || !err_flag) return ANIREC_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ANIREC_HIP_CHECK(hipMemsetAsync(err_flag, 0, 4, s));
+  hipLaunchKernelGGL(k_score_rank, dim3(((unsigned)n_targets + 3u) / 4u), dim3(256), 0, s, scores, (size_t)ld, n_anime,
+                     watched, n_users, target_row, target_anime, n_targets, out_rank, err_flag);
   return (int)hipGetLastError();
 }
 
@@ -1925,6 +1940,53 @@ int anirec_group_topk(const float *U, const float *A, int32_t dim, int32_t n_ani
                          out_member_p);
     });
     ANIREC_HIP_CHECK(hipGetLastError());
+  }
+  return ANIREC_OK;
+}
+
+// ------------------------------------------------------------------------------------
+// the select alone, over score rows the caller holds (anirec_rows_topk): a third feeder.  Nothing is scored here, so
+// a query's share of the workspace is the select's without a score row (none at all for k <= ANIREC_MAX_TOPK).
+// ------------------------------------------------------------------------------------
+size_t anirec_rows_topk_workspace_bytes(int32_t n, int32_t nq, int32_t k) {
+  if (n < 1 || nq < 0 || k < 1) return 0;
+  TopkLayout L = k <= ANIREC_MAX_TOPK ? select_layout(n) : lk_layout(n, k);
+  L.per_query -= (size_t)n * 4;
+  return L.bytes(nq < 1 ? 1 : nq, 4096);
+}
+
+int anirec_rows_topk(const float *scores, int64_t ld, int32_t n, int32_t nq, const int32_t *self, const uint8_t *keep,
+                     const uint32_t *wbits, int32_t k, int32_t *out_idx, float *out_score, void *workspace,
+                     size_t workspace_bytes, void *stream) {
+  if (n < 1 || nq < 0 || k < 1 || ld < n) return ANIREC_EINVAL;
+  if (nq == 0) return ANIREC_OK;
+  if (!scores || !out_idx || !out_score || !workspace) return ANIREC_EINVAL;
+  TopkLayout L = k <= ANIREC_MAX_TOPK ? select_layout(n) : lk_layout(n, k);
+  L.per_query -= (size_t)n * 4;
+  if (workspace_bytes < L.fixed + L.per_query) return ANIREC_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  size_t qb = L.per_query ? (workspace_bytes - L.fixed) / L.per_query : 4096;
+  if (qb > 4096) qb = 4096;
+  if (qb > (size_t)nq) qb = nq;
+  LkArgs la = {};
+  void *sel_tmp = nullptr;
+  L.carve((char *)workspace, qb, la, sel_tmp);
+  const int wwords = (n + 31) / 32;
+  for (size_t q0 = 0; q0 < (size_t)nq; q0 += qb) {
+    SelectArgs &sa = la.s;
+    sa.scores = scores + q0 * (size_t)ld;
+    sa.ld = (size_t)ld;
+    sa.n = n;
+    sa.nq = (int)((size_t)nq - q0 < qb ? (size_t)nq - q0 : qb);
+    sa.k = k;
+    sa.self = self ? self + q0 : nullptr;
+    sa.keep = keep;
+    sa.wbits = wbits ? wbits + q0 * wwords : nullptr;
+    sa.wwords = wwords;
+    sa.out_idx = out_idx + q0 * k;
+    sa.out_score = out_score + q0 * k;
+    const int e = L.large ? lk_run(la, s) : launch_select(sa, sel_tmp, s);
+    if (e) return e;
   }
   return ANIREC_OK;
 }

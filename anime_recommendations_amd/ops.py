@@ -811,6 +811,184 @@ def kmeans_fit(What, C0, max_iter=50):
     return C, assign, sim, count, int(iters), bool(converged)
 
 
+def cooc_measure(measure):
+    """ANIREC_COOC_* of a measure name, in any case: ``cosine``, ``jaccard``, ``confidence``.  ValueError, listing
+    them, for another."""
+    m = _lib.COOC_MEASURES.get(str(measure).strip().lower())
+    if m is None:
+        raise ValueError("co-occurrence measure %r is not one of %s" % (measure, ", ".join(_lib.COOC_MEASURES)))
+    return m
+
+
+def check_cooc(measure, shrink, min_support):
+    """The argument checks of ``cooc_scores`` (no device needed): (ANIREC_COOC_*, shrink float, min_support int), or a
+    ValueError for an unknown measure, a shrink that is negative or not finite, a negative min_support."""
+    m, shrink, min_support = cooc_measure(measure), float(shrink), int(min_support)
+    if not (0.0 <= shrink < float("inf")):
+        raise ValueError("cooc: shrink = %r must be finite and >= 0" % shrink)
+    if min_support < 0:
+        raise ValueError("cooc: min_support = %d must be >= 0" % min_support)
+    return m, shrink, min_support
+
+
+def _item_bits(bits, n_users):
+    assert isinstance(bits, torch.Tensor) and bits.is_cuda and bits.dtype == torch.int32 and bits.dim() == 2, \
+        "int32 [n_items, ceil(n_users/32)] device bit rows"
+    n_users = int(n_users)
+    if n_users < 1 or bits.shape[0] < 1 or bits.shape[1] != (n_users + 31) // 32:
+        raise ValueError("cooc: bits must be [n_items >= 1, ceil(n_users/32)] with n_users >= 1 (got %s for %d users)"
+                         % (tuple(bits.shape), n_users))
+    return bits.contiguous(), n_users
+
+
+def cooc_scores(bits, n_users, queries, measure="cosine", shrink=0.0, min_support=1, count=False, excl=False, pop=False,
+                workspace=None, check=True):
+    """Co-occurrence similarity rows (anirec_cooc_scores): ``bits`` int32 [n_items, ceil(n_users/32)]
+    on the device, bit u of row i set when user u liked item i (``recs.item_bits``); one row per query item against
+    every item.  With c = |liked(q) & liked(j)|: ``cosine`` c / (sqrt(pop_q pop_j) + shrink), ``jaccard``
+    c / (pop_q + pop_j - c + shrink), ``confidence`` c / (pop_q + shrink), in fp64 rounded once to fp32; +0 where
+    c < max(1, min_support).  Returns (sim fp32 [nq, n_items], count int32 [nq, n_items] | None, excl int32
+    [nq, ceil(n_items/32)] | None, pop int32 [n_items] | None): ``excl`` has bit j set where c is below the support or
+    j is the query itself (the ``wbits`` of ``rows_topk``).  Raises ValueError for a query out of range; with
+    ``check=False`` the device flag is returned as a fifth element instead and nothing synchronises."""
+    m, shrink, min_support = check_cooc(measure, shrink, min_support)
+    _need_gpu()
+    lib = _lib.load()
+    bits, n_users = _item_bits(bits, n_users)
+    dev = bits.device
+    n = int(bits.shape[0])
+    q = _i32(queries, dev).reshape(-1)
+    nq = int(q.numel())
+    sim = torch.empty(nq, n, dtype=torch.float32, device=dev)
+    cnt = torch.empty(nq, n, dtype=torch.int32, device=dev) if count else None
+    ex = torch.empty(nq, (n + 31) // 32, dtype=torch.int32, device=dev) if excl else None
+    pp = torch.empty(n, dtype=torch.int32, device=dev) if pop else None
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(int(lib.anirec_cooc_workspace_bytes(n, nq)), dtype=torch.uint8, device=dev)
+    if nq == 0 and pop:       # the call enqueues nothing for no query: the pop vector through one throw-away query
+        return (sim, cnt, ex, cooc_scores(bits, n_users, [0], measure, shrink, min_support, pop=True)[3]) + \
+            (() if check else (err,))
+    _lib.check(lib.anirec_cooc_scores(_lib.ptr(bits), n, n_users, _lib.ptr(q), nq, m, shrink, min_support, _lib.ptr(sim),
+                                      _lib.ptr(cnt), _lib.ptr(ex), _lib.ptr(pp), _lib.ptr(err), _lib.ptr(workspace),
+                                      workspace.numel(), _stream()), "anirec_cooc_scores")
+    if not check:
+        return sim, cnt, ex, pp, err
+    if int(err.item()):
+        raise ValueError("cooc_scores: query item out of range")
+    return sim, cnt, ex, pp
+
+
+def rows_topk(scores, k, n=None, self_idx=None, keep=None, wbits=None, workspace=None):
+    """The exact select over score rows the caller holds (anirec_rows_topk): ``scores`` fp32 [nq, ld] on the device,
+    the first ``n`` (default ld) columns of a row count.  Item j is no candidate of row t if ``self_idx[t] == j``,
+    ``keep[j] == 0`` or bit j of ``wbits[t]`` ([nq, ceil(n/32)]) is set.  Returns (idx int32 [nq, k], score fp32 [nq, k])
+    in predict_topk's order (larger first, +0 above -0, NaN last, ties by index), padded with -1 / NaN; any k >= 1."""
+    _need_gpu()
+    lib = _lib.load()
+    assert isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2, \
+        "fp32 [nq, ld] device score rows"
+    k = int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    sc = scores.contiguous()
+    dev = sc.device
+    nq, ld = int(sc.shape[0]), int(sc.shape[1])
+    n = ld if n is None else int(n)
+    if not 1 <= n <= ld:
+        raise ValueError("rows_topk: n = %d must be in 1 .. %d (the row length)" % (n, ld))
+    out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    if nq == 0:
+        return out_i, out_s
+    se = None
+    if self_idx is not None:
+        se = _i32(self_idx, dev)
+        assert se.shape == (nq,)
+    kp = None
+    if keep is not None:
+        kp = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous()
+        assert kp.numel() == n
+    wb = _watched(wbits, nq, n, dev)
+    if workspace is None:
+        workspace = torch.empty(int(lib.anirec_rows_topk_workspace_bytes(n, nq, k)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.anirec_rows_topk(_lib.ptr(sc), ld, n, nq, _lib.ptr(se), _lib.ptr(kp), _lib.ptr(wb), k, _lib.ptr(out_i),
+                                    _lib.ptr(out_s), _lib.ptr(workspace), workspace.numel(), _stream()),
+               "anirec_rows_topk")
+    return out_i, out_s
+
+
+def rows_rank(scores, target_row, target_anime, watched_bits=None):
+    """``score_rank`` with one score row per user (anirec_rows_rank): ``scores`` fp32 [n_users, n_anime] on the device,
+    target t is (``target_row[t]``: a row of ``scores`` and of ``watched_bits``, ``target_anime[t]``).  Returns rank int32
+    [n_t]: the position of the target in ``rows_topk(scores, k=n_anime, wbits=watched_bits with the target's bit
+    cleared)`` of its row.  Raises ValueError on a target_row or target_anime out of range."""
+    _need_gpu()
+    lib = _lib.load()
+    assert isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2, \
+        "fp32 [n_users, n_anime] device score rows"
+    sc = scores.contiguous()
+    dev = sc.device
+    tr, ta = _i32(target_row, dev), _i32(target_anime, dev)
+    assert tr.dim() == 1 and tr.shape == ta.shape
+    n_q, n_a, n_t = int(sc.shape[0]), int(sc.shape[1]), int(tr.numel())
+    if n_a < 1:
+        raise ValueError("rows_rank: n_anime must be >= 1")
+    rank = torch.empty(n_t, dtype=torch.int32, device=dev)
+    if n_t == 0:
+        return rank
+    if n_q == 0:
+        raise ValueError("rows_rank: target_row out of range (no rows)")
+    wb = _watched(watched_bits, n_q, n_a, dev)
+
+    def batch(t, cnt, err):
+        return lib.anirec_rows_rank(_lib.ptr(sc), n_a, n_a, _lib.ptr(wb), n_q, _lib.ptr(tr[t]), _lib.ptr(ta[t]), cnt,
+                                    _lib.ptr(rank[t]), err, _stream())
+    if _rank_batches(n_t, dev, "anirec_rows_rank", batch):
+        raise ValueError("rows_rank: target_row or target_anime out of range")
+    return rank
+
+
+def itemknn_scores(nbr_idx, nbr_sim, offsets, hist_idx, hist_w=None, workspace=None, check=True):
+    """Item-kNN score rows (anirec_itemknn_scores): ``nbr_idx`` int32 / ``nbr_sim`` fp32 [n_items, K]
+    neighbour tables on the device (index < 0 = padding), list l's history ``hist_idx[offsets[l]:offsets[l + 1]]`` with
+    the weights ``hist_w`` (None: 1).  out[l, j] = the sum over history entries (item i, weight w) and slots s with
+    nbr_idx[i, s] == j of w * nbr_sim[i, s], accumulated as int64 multiples of 2^-30: exact, whatever the order.
+    Returns fp32 [n_lists, n_items].  Raises ValueError for a history item or neighbour out of range, an offsets pair
+    that is not inside the history, a weight or similarity that is not finite or |w sim| > 1024; with ``check=False``
+    returns (out, device flag) and nothing synchronises."""
+    _need_gpu()
+    lib = _lib.load()
+    assert isinstance(nbr_idx, torch.Tensor) and nbr_idx.is_cuda and nbr_idx.dim() == 2 and nbr_idx.shape == nbr_sim.shape
+    dev = nbr_idx.device
+    ni, ns = _i32(nbr_idx, dev), _f32(nbr_sim, dev)
+    n, K = int(ni.shape[0]), int(ni.shape[1])
+    if n < 1 or K < 1:
+        raise ValueError("itemknn_scores: the neighbour tables must be [n_items >= 1, K >= 1]")
+    off = _i32(offsets, dev).reshape(-1)
+    if off.numel() < 1:
+        raise ValueError("itemknn_scores: offsets holds n_lists + 1 entries")
+    hi = _i32(hist_idx, dev).reshape(-1)
+    hw = None
+    if hist_w is not None:
+        hw = _f32(hist_w, dev).reshape(-1)
+        assert hw.shape == hi.shape
+    n_l, n_h = int(off.numel()) - 1, int(hi.numel())
+    out = torch.empty(n_l, n, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n_l:
+        if workspace is None:
+            workspace = torch.empty(int(lib.anirec_itemknn_workspace_bytes(n, n_l)), dtype=torch.uint8, device=dev)
+        _lib.check(lib.anirec_itemknn_scores(_lib.ptr(ni), _lib.ptr(ns), n, K, _lib.ptr(off), _lib.ptr(hi), _lib.ptr(hw),
+                                             n_l, n_h, _lib.ptr(out), _lib.ptr(err), _lib.ptr(workspace),
+                                             workspace.numel(), _stream()), "anirec_itemknn_scores")
+    if not check:
+        return out, err
+    if int(err.item()):
+        raise ValueError("itemknn_scores: history, neighbour table or offsets out of range, or an unusable term")
+    return out
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

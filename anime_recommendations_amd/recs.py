@@ -645,3 +645,128 @@ def append_anime(model, folded):
     ids = np.asarray(model["anime_ids"])
     out["anime_ids"] = np.concatenate([ids, np.asarray(folded["ids"]).astype(ids.dtype)])
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# item-kNN from co-occurrence: no model takes part
+# ----------------------------------------------------------------------------------------
+COOC_BATCH = 1024       # query items per anirec_cooc_scores call: a sim row and a count row each
+ITEMKNN_BATCH = 4096    # users per anirec_itemknn_scores call: a score row each
+
+
+def item_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
+    """The liked-by bits of a rating list: int32 [n_anime, ceil(n_users/32)], bit ``u & 31`` of word ``u >> 5`` of row a
+    set for every rating (u, a) — ``ops.seen_bits`` with the two columns swapped, the ``bits`` of ``ops.cooc_scores``.
+    Raises ValueError on an index out of range."""
+    from . import ops
+    return ops.seen_bits(anime_idx, user_idx, n_anime, n_users, device=device)
+
+
+def cooc_neighbours(bits, n_users, k, queries=None, measure="cosine", shrink=0.0, min_support=1, batch=COOC_BATCH):
+    """The ``k`` nearest items of each query item by co-occurrence (``ops.cooc_scores`` then ``ops.rows_topk`` with the
+    scores' own ``excl`` rows as the mask, ``batch`` queries at a time): ``bits`` as ``item_bits`` gives them,
+    ``queries`` item indices (None: every item).  Returns (idx int32 [nq, k], sim fp32 [nq, k], count int32 [nq, k]) on
+    the device: larger similarity first, ties by index, never the query itself nor an item below the support; padded
+    with -1 / NaN / -1.  ``count`` is the number of users who liked both."""
+    from . import ops
+    k, batch = int(k), int(batch)
+    if k < 1 or batch < 1:
+        raise ValueError("cooc_neighbours: k and batch must be >= 1")
+    ops.check_cooc(measure, shrink, min_support)
+    dev = bits.device
+    n = int(bits.shape[0])
+    q = torch.arange(n, dtype=torch.int32, device=dev) if queries is None else \
+        torch.as_tensor(_host(queries) if not isinstance(queries, torch.Tensor) else queries, device=dev) \
+        .to(torch.int32).reshape(-1)
+    nq = int(q.numel())
+    idx = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    sim = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    cnt = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    for q0 in range(0, nq, batch):
+        s, c, ex, _ = ops.cooc_scores(bits, n_users, q[q0:q0 + batch], measure, shrink, min_support, count=True, excl=True)
+        i, v = ops.rows_topk(s, k, wbits=ex)
+        idx[q0:q0 + batch], sim[q0:q0 + batch] = i, v
+        cnt[q0:q0 + batch] = torch.where(i >= 0, torch.gather(c, 1, i.clamp(min=0).long()), torch.full_like(i, -1))
+    return idx, sim, cnt
+
+
+def itemknn_fit(user_idx, anime_idx, rating, n_users, n_anime, liked_min_rating=0.0, K=50, measure="cosine", shrink=0.0,
+                min_support=1, device="cuda:0"):
+    """An item-kNN model from a rating list: a user LIKED an anime when the (scaled) rating is at or above
+    ``liked_min_rating`` (compared in fp32; 0.0 = every rating); every anime keeps its ``K`` nearest by co-occurrence of
+    the liked-by sets (``cooc_neighbours``).  Returns {"nbr_idx" int32 [n_anime, K], "nbr_sim" fp32, "nbr_count" int32,
+    "pop" int32 [n_anime] (how many users liked each anime)} on the device and the parameters ("n_users", "n_anime",
+    "K", "measure", "shrink", "min_support", "liked_min_rating")."""
+    from . import ops
+    u, a = _host(user_idx).reshape(-1), _host(anime_idx).reshape(-1)
+    r = _host(rating).reshape(-1).astype(np.float32)
+    if not len(u) == len(a) == len(r):
+        raise ValueError("itemknn_fit: user_idx, anime_idx and rating must have one entry per rating")
+    liked = r >= np.float32(liked_min_rating)
+    dev = torch.device(device)
+    bits = item_bits(torch.as_tensor(u[liked].astype(np.int32), device=dev),
+                     torch.as_tensor(a[liked].astype(np.int32), device=dev), n_users, n_anime, device=dev)
+    idx, sim, cnt = cooc_neighbours(bits, n_users, K, None, measure, shrink, min_support)
+    pop = ops.cooc_scores(bits, n_users, [0], measure, shrink, min_support, pop=True)[3]
+    return {"nbr_idx": idx, "nbr_sim": sim, "nbr_count": cnt, "pop": pop, "n_users": int(n_users),
+            "n_anime": int(n_anime), "K": int(K), "measure": str(measure).strip().lower(), "shrink": float(shrink),
+            "min_support": int(min_support), "liked_min_rating": float(liked_min_rating)}
+
+
+def _on(x, dev, dtype):
+    """``x`` (NumPy or torch, wherever it lives) as a tensor of ``dtype`` on ``dev``"""
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    return t.to(device=dev, dtype=dtype)
+
+
+def _knn_batches(knn, offsets, batch):
+    off = np.asarray(_host(offsets), np.int64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("itemknn: offsets holds n_lists + 1 entries")
+    n_l = int(off.size) - 1
+    return off, n_l, [(l0, min(n_l, l0 + int(batch))) for l0 in range(0, n_l, int(batch))]
+
+
+def itemknn_topk(knn, offsets, hist_idx, hist_w=None, k=10, watched_bits=None, batch=ITEMKNN_BATCH):
+    """Item-kNN recommendation lists: list l's history ``hist_idx[offsets[l]:offsets[l + 1]]`` (``history_csr`` builds
+    it; ``hist_w`` None = weight 1) scored through the neighbour tables of ``knn`` (``ops.itemknn_scores``) and the
+    ``k`` best anime without a bit in ``watched_bits`` [n_lists, ceil(n_anime/32)] taken by the exact select
+    (``ops.rows_topk``), ``batch`` lists at a time.  Returns (idx int32 [n_lists, k], score fp32 [n_lists, k])."""
+    from . import ops
+    off, n_l, spans = _knn_batches(knn, offsets, batch)
+    dev = knn["nbr_idx"].device
+    k = int(k)
+    idx = torch.empty(n_l, k, dtype=torch.int32, device=dev)
+    sc = torch.empty(n_l, k, dtype=torch.float32, device=dev)
+    hi = _on(hist_idx, dev, torch.int32)
+    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
+    for l0, l1 in spans:
+        rows = ops.itemknn_scores(knn["nbr_idx"], knn["nbr_sim"], off[l0:l1 + 1], hi, hw)
+        idx[l0:l1], sc[l0:l1] = ops.rows_topk(rows, k, wbits=None if watched_bits is None else watched_bits[l0:l1])
+    return idx, sc
+
+
+def itemknn_rank(knn, offsets, hist_idx, hist_w, watched_bits, target_row, target_anime, batch=ITEMKNN_BATCH):
+    """The ranks ``ops.predict_rank`` gives a model, for the item-kNN scores of ``itemknn_topk``: target t is
+    (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the anime
+    the list has no watched bit for, the target's own bit ignored).  ``batch`` lists at a time."""
+    from . import ops
+    off, n_l, spans = _knn_batches(knn, offsets, batch)
+    dev = knn["nbr_idx"].device
+    tr = np.asarray(_host(target_row), np.int64).reshape(-1)
+    ta = np.asarray(_host(target_anime), np.int64).reshape(-1)
+    if tr.shape != ta.shape:
+        raise ValueError("itemknn_rank: target_row and target_anime must have one entry per target")
+    if tr.size and (tr.min() < 0 or tr.max() >= n_l):
+        raise ValueError("itemknn_rank: target_row out of range")
+    rank = torch.empty(int(tr.size), dtype=torch.int32, device=dev)
+    hi = _on(hist_idx, dev, torch.int32)
+    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
+    for l0, l1 in spans:
+        sel = np.flatnonzero((tr >= l0) & (tr < l1))
+        if not sel.size:
+            continue
+        rows = ops.itemknn_scores(knn["nbr_idx"], knn["nbr_sim"], off[l0:l1 + 1], hi, hw)
+        r = ops.rows_rank(rows, tr[sel] - l0, ta[sel], None if watched_bits is None else watched_bits[l0:l1])
+        rank[torch.as_tensor(sel, device=dev)] = r
+    return rank

@@ -3,8 +3,10 @@
 (the last ``test_size`` rows of the same encoding and RandomState(42) shuffle) are ranked among the anime their user
 has no training rating for, by predicted rating, and hit rate / NDCG at each ``eval_k``, MRR and the mean and median
 rank are written to ``eval_csv``; ``--baseline popularity`` adds the same figures for ranking by rating count alone, to
-read the model's against; ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity
-costs in hits and buys in spread, over every held-out user's top ``lists_k`` list.  The reference has no such step:
+read the model's against, ``--baseline itemknn`` those of an item-kNN over co-occurrence counts fitted on the training
+slice alone (``popularity,itemknn``: both; the ``--itemknn_*`` flags of the command line tune it);
+``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
+spread, over every held-out user's top ``lists_k`` list.  The reference has no such step:
 its author lists comparing re-trained models as an idea for improvement; ``val_loss`` cannot compare models across
 losses and activations, these figures can."""
 import json
@@ -27,7 +29,24 @@ OPTIONAL_FLAGS = {
     "lists_csv": (str, "eval_lists.csv", "the file the list figures are written to, logged as an eval_type artifact"),
 }
 
+# optional and command-line only (not MLproject parameters; `mlflow run` takes the defaults): the item-kNN baseline
+ITEMKNN_FLAGS = {
+    "itemknn_neighbours": (int, 50, "neighbours every anime keeps"),
+    "itemknn_measure": (str, "cosine", "cosine, jaccard or confidence of the liked-by sets"),
+    "itemknn_shrink": (float, 0.0, "added to the measure's denominator"),
+    "itemknn_min_support": (int, 1, "users two anime must share to be neighbours"),
+    "itemknn_min_rating": (float, 0.0, "the scaled rating (0..1) from which a training rating counts as liked"),
+}
+
 logger = C.setup_logging("evaluate")
+
+
+def baseline_arg(text):
+    """``--baseline``: none, a name, or a comma list of names -> evaluate_frame's ``baseline`` (None, or a list)."""
+    names = [b.strip().lower() for b in str(text).split(",") if b.strip()]
+    if not names or names == ["none"]:
+        return None
+    return names
 
 
 def go(args):
@@ -38,8 +57,9 @@ def go(args):
     table = ingest.load_user_stats(artifacts.use_artifact(args.input_data, args.main_df_type))
     logger.info("Final df shape is (%d, 3); %d users, %d anime", len(table), table.n_users, table.n_anime)
     frame, summary = C.evaluate_frame(model, table, int(args.test_size), C.literal(args.eval_k),
-                                      float(args.min_rating),
-                                      baseline=None if args.baseline.lower() == "none" else args.baseline.lower())
+                                      float(args.min_rating), baseline=baseline_arg(args.baseline),
+                                      itemknn={f[len("itemknn_"):]: getattr(args, f) for f in ITEMKNN_FLAGS
+                                               if hasattr(args, f)})
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -63,14 +83,24 @@ def make_parser():
     parser = C.make_parser("Rank the held-out ratings with a trained model", STR_FLAGS, BOOL_FLAGS)
     # optional, unlike the flags above: "popularity" adds the figures of recommending the most-rated unseen anime
     parser.add_argument("--baseline", type=str, default="none", required=False,
-                        help="none, or popularity: rank the same targets by the anime's number of training ratings")
+                        help="none, popularity (rank the same targets by the anime's number of training ratings), "
+                             "itemknn (by an item-kNN over co-occurrence counts of the training ratings), or both "
+                             "separated by a comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 
 
+def make_cli_parser():
+    """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*`` flags."""
+    parser = make_parser()
+    for flag, (kind, default, text) in ITEMKNN_FLAGS.items():
+        parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
+    return parser
+
+
 if __name__ == "__main__":
-    _args = make_parser().parse_args()
+    _args = make_cli_parser().parse_args()
     try:
         go(_args)
     except Exception:                      # non-zero exit + the reason in ./evaluate.log

@@ -907,6 +907,91 @@ int anirec_kmeans_fit(const float *What, int32_t dim, int32_t n_rows, float *C_i
                       int32_t *out_assign, float *out_sim, int32_t *out_count, int32_t *out_info,
                       void *ws, size_t ws_bytes, void *stream);
 
+/* ITEM-kNN FROM CO-OCCURRENCE: "people who liked this also liked ...", and the baseline a neural model is judged by.
+ * No model takes part.  item_bits is [n_items][ceil(n_users/32)] uint32: bit (u & 31) of word u >> 5 of row i is set
+ * when user u liked item i — exactly what anirec_seen_bits writes when it is called with the two index columns swapped
+ * (user_idx := the item column, anime_idx := the user column, n_users := n_items, n_anime := n_users); there is no
+ * other builder.  Bits at positions >= n_users of a row's last word may hold anything and have no effect.
+ *
+ * anirec_cooc_scores: one similarity row per query item q = queries[t], against every item j:
+ *   pop[i]   the popcount of row i over the valid bits
+ *   c(q,j)   the popcount of row_q & row_j over the valid bits
+ *   den      fp64, every operation one IEEE rounding, nothing contracted:
+ *            ANIREC_COOC_COSINE      sqrt((double)pop_q * (double)pop_j) + shrink
+ *            ANIREC_COOC_JACCARD     (double)(int64)(pop_q + pop_j - c) + shrink
+ *            ANIREC_COOC_CONFIDENCE  (double)pop_q + shrink                            (P(j | q))
+ *   sim      c >= max(1, min_support) ? (float)((double)c / den) : +0.0f    (den > 0 whenever c > 0)
+ *   out_sim [nq][n_items] = sim; out_count (optional) [nq][n_items] = c; out_pop (optional) [n_items] = pop;
+ *   out_excl (optional) [nq][ceil(n_items/32)]: bit j of row t set iff c < max(1, min_support) or j == q — the mask
+ *   rows anirec_rows_topk takes as wbits; bits at positions >= n_items are clear.
+ * A query outside [0, n_items) raises *err_flag (device; overwritten by the call) to 1: its rows are NaN / -1 / every
+ * bit j < n_items set, nothing is read through it, the other queries are unaffected.  A query may repeat.  A query's
+ * rows depend on that query and the bits alone: not on nq, its position in `queries` or the launch shape.  Every count
+ * is a sum of integers, so the call is bit-reproducible.  A 256-thread workgroup owns 64 queries x 64 keys and stages
+ * anirec_cooc_chunk_words() user words of both row sets in LDS per pass.
+ * shrink must be finite and >= 0, min_support >= 0, n_users >= 1, n_items >= 1, measure one of the three; those, a
+ * negative nq or a NULL item_bits, queries, out_sim, err_flag or ws with nq > 0: ANIREC_EINVAL before anything is
+ * enqueued or written.  nq == 0: ANIREC_OK, nothing enqueued.  ws: anirec_cooc_workspace_bytes(n_items, nq) bytes (0
+ * for a bad argument; the pop vector), less is ANIREC_EWORKSPACE; the result does not depend on what it held.
+ * Stream-ordered plain launches, no host read-back: graph-capturable.
+ * Cost: nq n_items ceil(n_users/32) word pairs of one v_and and one accumulating popcount each. */
+enum { ANIREC_COOC_COSINE = 0, ANIREC_COOC_JACCARD = 1, ANIREC_COOC_CONFIDENCE = 2 };
+size_t anirec_cooc_chunk_words(void);
+size_t anirec_cooc_workspace_bytes(int32_t n_items, int32_t nq);
+int anirec_cooc_scores(const uint32_t *item_bits, int32_t n_items, int32_t n_users, const int32_t *queries, int32_t nq,
+                       int32_t measure, double shrink, int32_t min_support, float *out_sim, int32_t *out_count,
+                       uint32_t *out_excl, int32_t *out_pop, int32_t *err_flag, void *ws, size_t ws_bytes,
+                       void *stream);
+
+/* The exact select over score rows the caller already holds: scores [nq][ld] fp32 (ld >= n; the first n of a row
+ * count), any k >= 1.  Item j is no candidate of query t if j == self[t] (optional [nq]; -1 = none), keep[j] == 0
+ * (optional [n] bytes) or bit j of wbits[t] is set (optional [nq][ceil(n/32)]; bits at positions >= n have no effect).
+ * The order is that of anirec_predict_topk*: larger first, +0 above -0, NaN after every number, ties in ascending
+ * index; out_idx / out_score [nq][k] are padded with -1 / NaN, out_score holds the row's own bits.  k <=
+ * ANIREC_MAX_TOPK and above it run the two selects of anirec_predict_topk_w / _large_w exactly as anirec_group_topk
+ * does (the same bits where they overlap).  n < 1, nq < 0, k < 1, ld < n, or a NULL scores, out_idx, out_score or
+ * workspace with nq > 0: ANIREC_EINVAL before anything is enqueued.  nq == 0: ANIREC_OK.
+ * workspace: may hold anything; anirec_rows_topk_workspace_bytes(n, nq, k) sizes it (0 for a bad argument): the
+ * select's fixed part and per query of a batch (at most 4096) the select's share.  Anything down to one query's share
+ * runs smaller batches with the same results, less is ANIREC_EWORKSPACE.  Graph-capturable. */
+size_t anirec_rows_topk_workspace_bytes(int32_t n, int32_t nq, int32_t k);
+int anirec_rows_topk(const float *scores, int64_t ld, int32_t n, int32_t nq, const int32_t *self, const uint8_t *keep,
+                     const uint32_t *wbits, int32_t k, int32_t *out_idx, float *out_score, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/* anirec_score_rank with one score row per user: score(t) = scores + (size_t)target_row[t] * ld, otherwise the same
+ * key, tie rule, watched semantics and error rule (target_row outside [0, n_users) raises the flag before anything is
+ * read through it).  ld == 0 is anirec_score_rank bit for bit; any other ld must be >= n_anime (ANIREC_EINVAL).  One
+ * wave per target, no workspace, no atomics. */
+int anirec_rows_rank(const float *scores, int64_t ld, int32_t n_anime, const uint32_t *watched, int32_t n_users,
+                     const int32_t *target_row, const int32_t *target_anime, int32_t n_targets, int32_t *out_rank,
+                     int32_t *err_flag, void *stream);
+
+/* Item-kNN score rows from user histories and truncated neighbour lists.  nbr_idx / nbr_sim are [n_items][K] (what
+ * anirec_cooc_scores + anirec_rows_topk give per item; index < 0 is padding); list l's history is the entries
+ * e = hist_offsets[l] .. hist_offsets[l+1]-1 of hist_idx / hist_w (CSR over n_hist entries; hist_w NULL means 1.0f).
+ * For entry e (i = hist_idx[e], weight w) and slot s with j = nbr_idx[i][s] >= 0:
+ *   term = llrint((double)w * (double)nbr_sim[i][s] * 2^30)     (the product is exact, the rounding to nearest even)
+ *   S[l][j] += term as int64;     out_scores[l][j] = (float)((double)S[l][j] * 2^-30)
+ * Every element of every output row is written, 0 where nothing landed.  A repeated history item counts twice.  A
+ * term needs w and sim finite and |w sim| <= 1024; the documented bound is history length x K < 2^22 per list.
+ * *err_flag (device; overwritten by the call) becomes 1 on an unusable term, a history item outside [0, n_items) or a
+ * neighbour index >= n_items (that term, entry or slot adds nothing) and on an offsets pair that is negative,
+ * decreasing or past n_hist (that list's row is NaN); nothing is read through the bad value and the other lists are
+ * unaffected.  A list's row depends on that list's multiset of entries and the neighbour tables alone: not on entry
+ * order, the other lists or the launch shape.  Integer atomics only: in LDS when n_items <=
+ * anirec_itemknn_lds_items(), else on the list's int64 row of ws.
+ * n_items < 1, K < 1, a negative count, or a NULL nbr_idx, nbr_sim, hist_offsets, out_scores, err_flag or ws
+ * (hist_idx with n_hist > 0) with n_lists > 0: ANIREC_EINVAL before anything is enqueued or written.  n_lists == 0:
+ * ANIREC_OK.  ws: anirec_itemknn_workspace_bytes(n_items, n_lists) bytes (0 for a bad argument), 8-byte aligned, less
+ * is ANIREC_EWORKSPACE; the result does not depend on what it held.  Graph-capturable. */
+size_t anirec_itemknn_lds_items(void);
+size_t anirec_itemknn_workspace_bytes(int32_t n_items, int32_t n_lists);
+int anirec_itemknn_scores(const int32_t *nbr_idx, const float *nbr_sim, int32_t n_items, int32_t K,
+                          const int32_t *hist_offsets, const int32_t *hist_idx, const float *hist_w, int32_t n_lists,
+                          int32_t n_hist, float *out_scores, int32_t *err_flag, void *ws, size_t ws_bytes,
+                          void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
