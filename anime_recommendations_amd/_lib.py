@@ -32,6 +32,9 @@ EXPLAIN_TILE_FLOATS = 8192  # anirec_explain_tile(dim, k): dim * tile and k * (t
 KMEANS_MAX_K = 4096         # ANIREC_KMEANS_MAX_K: the most centroids anirec_kmeans_assign / anirec_kmeans_fit take
 KMEANS_MAX_ITER = 1000      # anirec_kmeans_fit: the most iterations one call enqueues
 KMEANS_IMAGE_FLOATS = 32768  # anirec_kmeans_tile(dim) = KMEANS_IMAGE_FLOATS // dim: the centroids of one LDS image
+CALIBRATE_MAX_CAND = 1024   # anirec_calibrate_max_cand(): the longest list anirec_calibrate_rerank / _list_calibration take
+CALIBRATE_MAX_CAT = 128     # the most categories of a profile (anirec_fave_profile's limit)
+CALIBRATE_PROFILE_MAX = 1 << 24   # the largest profile entry: the integer numerator then stays below 2**53
 # anirec_train_desc.optimizer (ANIREC_OPT_*)
 OPT_ADAM, OPT_SGD, OPT_RMSPROP, OPT_ADAGRAD = 0, 1, 2, 3
 # anirec_train_desc.loss (ANIREC_LOSS_*) and .activation / the predict calls' activation (ANIREC_ACT_*)
@@ -264,6 +267,11 @@ PROTOTYPES = {
     "anirec_itemknn_lds_items": (_sz, []),
     "anirec_itemknn_workspace_bytes": (_sz, [_i32, _i32]),
     "anirec_itemknn_scores": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    # greedy calibrated re-rank of candidate lists towards a favourite profile, and the miscalibration of lists held
+    "anirec_calibrate_max_cand": (_sz, []),
+    "anirec_calibrate_rerank": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
+                                          _vp]),
+    "anirec_list_calibration": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -601,6 +601,64 @@ def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
 
 
 # ----------------------------------------------------------------------------------------
+# calibrated_recs: model_recs with the list pulled towards the user's own genre (or source) proportions
+# ----------------------------------------------------------------------------------------
+CALIBRATION_COLUMNS = ("Genres", "Source")
+
+
+def calibrated_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
+                          types=None, genres=None, pool=100, calibration=0.5, column="Genres", favorite_percentile=80):
+    """model_recs_frame with the list calibrated (``recs.calibrated_topk``): the same candidates
+    (unwatched, indexed, Type / Genre filters), the ``pool`` best by predicted rating re-ranked greedily so that the
+    tokens of ``column`` (``Genres`` or ``Source``) in the list follow the proportions they have among the user's
+    favourites (user_prefs' profile: ratings at or above the ``favorite_percentile`` of the user's own).
+    Returns (frame, stats): model_recs_frame's columns plus ``Miscalibration`` — the total variation distance between
+    the two token distributions for the list down to and including the row: the re-rank's own penalty (at calibration
+    0, where nothing is re-ranked and the rows are model_recs_frame's, ``recs.list_calibration`` of the prefixes) — and
+    stats = {"calibration", "pool", "column", "n_favourites", "miscalibration": that of the whole list,
+    "miscalibration_topk": that of the plain top-k}."""
+    import torch
+    from . import ops, recs
+    if column not in CALIBRATION_COLUMNS:
+        raise ValueError("calibrated_recs: calibration_column %r is not one of %s" % (column, ", ".join(CALIBRATION_COLUMNS)))
+    u = user_index(user_ids, user_id)
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    names, cat_bits = category_table(meta, column)
+    n_cat = len(names)
+    if n_cat < 1:
+        raise ValueError("calibrated_recs: column %r holds no tokens to calibrate to" % (column,))
+    fav = favourite_bits(df, user_ids, anime_ids, favorite_percentile)
+    profile = recs.fave_profile(fav, cat_bits, n_cat, users=[u])
+    keep = unwatched_mask(df, anime_ids, user_id) & filter_mask(meta, anime_df, types, genres)
+    bits = _blocked_bits(~keep).view(np.int32)
+    tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
+    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
+    idx, p, pen = recs.calibrated_topk(tU, tA, head, [u], k, pool, calibration, cat_bits, n_cat, profile, bits)
+
+    def prefixes(row):
+        """the miscalibration of every prefix of one list (-1 padding dropped), by the list kernel"""
+        row = row[row >= 0]
+        if len(row) == 0:
+            return np.zeros(0, np.float32)
+        lists = np.where(np.arange(len(row))[None, :] <= np.arange(len(row))[:, None], row[None, :], -1).astype(np.int32)
+        return recs.list_calibration(torch.from_numpy(lists).cuda(), cat_bits, n_cat,
+                                     profile.expand(len(row), n_cat))[0].cpu().numpy()
+
+    idx, p = idx.cpu().numpy()[0], p.cpu().numpy()[0]
+    if pen is None:
+        pen = plain = prefixes(idx)
+    else:
+        plain = prefixes(ops.predict_topk(tU, tA, head, [u], k, bits)[0].cpu().numpy()[0])
+        pen = pen.cpu().numpy()[0][idx >= 0]
+    frame = _model_recs_rows(meta, idx, p)
+    frame["Miscalibration"] = pen
+    last = lambda x: float(x[-1]) if len(x) else float("nan")      # noqa: E731
+    return frame, {"calibration": float(calibration), "pool": int(pool), "column": column,
+                   "n_favourites": int(len(favourite_indices(fav, u, len(anime_ids)))),
+                   "miscalibration": last(pen), "miscalibration_topk": last(plain)}
+
+
+# ----------------------------------------------------------------------------------------
 # group_recs: one list for several users who watch together
 # ----------------------------------------------------------------------------------------
 GROUP_STRATEGIES = ("mean", "least_misery", "most_pleasure")

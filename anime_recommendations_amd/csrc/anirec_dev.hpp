@@ -268,6 +268,36 @@ __device__ __forceinline__ float rating_from_cosine(float c, float hs, float hb,
   return act_any<kAct>(__fmaf_rn(c, hs, hb), act);
 }
 
+// ---- the greedy re-ranks (anirec_mmr_rerank, anirec_calibrate_rerank): one order of the candidates' values, one
+// rounding of a value, one wave-wide max
+// larger val -> larger key; NaN -> 1 (after every number); -0 and +0 share a key; 0 is "not a candidate"
+__device__ __forceinline__ uint32_t mmr_key(float v) {
+  if (v != v) return 1u;
+  uint32_t u = __float_as_uint(v);
+  if ((u & 0x7FFFFFFFu) == 0u) u = 0u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return u < 2u ? 2u : u;
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// val_i = (lambda * score_i) - (oml * pen_i): each product rounded, then the difference
+__device__ __forceinline__ float mmr_val(float ls, float oml, float pen) {
+#pragma clang fp contract(off)
+  return ls - oml * pen;
+}
+__device__ __forceinline__ float mmr_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // host: a row width the *_w entry points implement (a row is dim / 4 lanes of float4: 8, 16, 32 or 64 lanes)
 static inline bool dim_ok(int32_t dim) { return dim == 32 || dim == 64 || dim == 128 || dim == 256; }
 // host: calls f(std::integral_constant<int, kD>) with a (checked) width as a compile-time constant.  A kernel that

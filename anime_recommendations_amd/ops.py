@@ -682,6 +682,115 @@ def list_similarity(What, list_idx):
     return sim_max, sim_sum
 
 
+def check_calibrate(n_cat, n_cand, k, calibration):
+    """The argument checks of ``calibrate_rerank`` (no device needed): ValueError naming the limit for ``n_cat`` outside
+    1 .. 128, a candidate list longer than anirec_calibrate_max_cand(), k outside 1 .. n_cand, or ``calibration``
+    outside [0, 1].  Returns (n_cat, n_cand, k, calibration)."""
+    n_cat, n_cand, k, calibration = int(n_cat), int(n_cand), int(k), float(calibration)
+    if not 1 <= n_cat <= _lib.CALIBRATE_MAX_CAT:
+        raise ValueError("calibrate_rerank: n_cat = %d, a profile holds 1 .. %d categories" % (n_cat, _lib.CALIBRATE_MAX_CAT))
+    if n_cand > _lib.CALIBRATE_MAX_CAND:
+        raise ValueError("calibrate_rerank: %d candidates per list, at most %d (a lane owns four candidates of a "
+                         "workgroup's list)" % (n_cand, _lib.CALIBRATE_MAX_CAND))
+    if not 1 <= k <= n_cand:
+        raise ValueError("calibrate_rerank: k = %d must be in 1 .. %d (the candidates per list)" % (k, n_cand))
+    if not 0.0 <= calibration <= 1.0:       # (a NaN fails both comparisons)
+        raise ValueError("calibrate_rerank: calibration = %r must be in [0, 1]" % (calibration,))
+    return n_cat, n_cand, k, calibration
+
+
+def _calibrate_tables(what, cat_bits, n_cat, lists, profile):
+    """The shape checks ``calibrate_rerank`` and ``list_calibration`` share (no device needed): ``cat_bits``
+    [n_rows >= 1, ceil(n_cat/32)], ``lists`` [n_lists, n], ``profile`` [n_lists, n_cat]."""
+    if len(cat_bits.shape) != 2 or int(cat_bits.shape[0]) < 1 or int(cat_bits.shape[1]) != (n_cat + 31) // 32:
+        raise ValueError("%s: cat_bits must be [n_rows >= 1, %d] bit words for %d categories, got %s"
+                         % (what, (n_cat + 31) // 32, n_cat, tuple(cat_bits.shape)))
+    if len(lists.shape) != 2:
+        raise ValueError("%s: the lists must be [n_lists, n], got %s" % (what, tuple(lists.shape)))
+    if tuple(profile.shape) != (int(lists.shape[0]), n_cat):
+        raise ValueError("%s: profile must be [n_lists, n_cat] = %s (one row of fave_profile counts per list), got %s"
+                         % (what, (int(lists.shape[0]), n_cat), tuple(profile.shape)))
+
+
+def _cat_words(cat_bits, dev):
+    if not torch.is_tensor(cat_bits):
+        cat_bits = torch.from_numpy(np.ascontiguousarray(cat_bits).view(np.int32))
+    return cat_bits.to(device=dev).contiguous()
+
+
+def calibrate_rerank(cat_bits, n_cat, cand_idx, cand_score, profile, k, calibration):
+    """Greedy calibrated re-rank of candidate lists (anirec_calibrate_rerank): list l holds the rows
+    ``cand_idx[l]`` of ``cat_bits`` ([n_rows, ceil(n_cat/32)] category bit words: ``components.category_table``; -1 = an
+    empty slot) with relevance ``cand_score[l]`` and the user's ``profile[l]`` (int32 [n_cat]: a row of
+    ``recs.fave_profile``); each of the ``k`` picks is the unpicked candidate with the largest
+    ``(1 - calibration) * score - calibration * pen``, pen = the total variation distance between the category-token
+    distribution of the list with that candidate added and the profile's; ties go to the lowest position.
+    ``calibration`` = 0 keeps the score order.  Returns (idx int32, pos int32, score fp32, pen fp32), each [n_lists, k]
+    on the device: the row, its position in the list, its score and the miscalibration of the list including it;
+    -1 / -1 / NaN / NaN once a list has no candidate left.  Raises ValueError for ``n_cat`` outside 1 .. 128, a list
+    longer than anirec_calibrate_max_cand(), k outside 1 .. n_cand, ``calibration`` outside [0, 1], a candidate index
+    that is no row of ``cat_bits``, or a profile entry that is negative or above 2**24."""
+    if cand_idx.dim() != 2 or tuple(cand_idx.shape) != tuple(cand_score.shape):
+        raise ValueError("calibrate_rerank: cand_idx and cand_score must both be [n_lists, n_cand]")
+    n_cat, n_cand, k, calibration = check_calibrate(n_cat, cand_idx.shape[1], k, calibration)
+    _calibrate_tables("calibrate_rerank", cat_bits, n_cat, cand_idx, profile)
+    _need_gpu()
+    lib = _lib.load()
+    dev = cand_idx.device if cand_idx.is_cuda else torch.device("cuda")
+    cat = _cat_words(cat_bits, dev)
+    ci, cs, pr = _i32(cand_idx, dev), _f32(cand_score, dev), _i32(profile, dev)
+    n_lists = int(ci.shape[0])
+    idx = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
+    pos = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
+    score = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    pen = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    if n_lists == 0:
+        return idx, pos, score, pen
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.anirec_calibrate_rerank(_lib.ptr(cat), int(cat.shape[0]), n_cat, _lib.ptr(ci), _lib.ptr(cs),
+                                           _lib.ptr(pr), n_lists, n_cand, k, calibration, _lib.ptr(idx), _lib.ptr(pos),
+                                           _lib.ptr(score), _lib.ptr(pen), _lib.ptr(err), _stream()),
+               "anirec_calibrate_rerank")
+    if int(err.item()):
+        raise ValueError("calibrate_rerank: candidate index out of range, or a profile entry outside 0 .. 2**24")
+    return idx, pos, score, pen
+
+
+def list_calibration(cat_bits, n_cat, lists, profile):
+    """The miscalibration of lists a caller holds (anirec_list_calibration): list l holds the rows ``lists[l]`` of
+    ``cat_bits`` (-1 = an empty slot, skipped), ``profile[l]`` its user's ``recs.fave_profile`` row.  Returns
+    (pen fp32, num int64, den int64), each [n_lists] on the device: the total variation distance between the list's
+    category-token distribution and the profile's, pen = float32(num / den) — ``calibrate_rerank``'s own ``pen`` on
+    every prefix of its lists, bit for bit; 0 / 1 / 0.0 for an all-zero profile, otherwise 1 / 1 / 1.0 for a list
+    without tokens.  Raises ValueError for ``n_cat`` outside 1 .. 128, lists of fewer than one or more than
+    anirec_calibrate_max_cand() slots, an index that is no row of ``cat_bits``, or a profile entry outside 0 .. 2**24."""
+    n_cat = int(n_cat)
+    if not 1 <= n_cat <= _lib.CALIBRATE_MAX_CAT:
+        raise ValueError("list_calibration: n_cat = %d, a profile holds 1 .. %d categories" % (n_cat, _lib.CALIBRATE_MAX_CAT))
+    _calibrate_tables("list_calibration", cat_bits, n_cat, lists, profile)
+    k = int(lists.shape[1])
+    if not 1 <= k <= _lib.CALIBRATE_MAX_CAND:
+        raise ValueError("list_calibration: %d slots per list, 1 .. %d" % (k, _lib.CALIBRATE_MAX_CAND))
+    _need_gpu()
+    lib = _lib.load()
+    dev = lists.device if torch.is_tensor(lists) and lists.is_cuda else torch.device("cuda")
+    cat = _cat_words(cat_bits, dev)
+    li, pr = _i32(lists, dev), _i32(profile, dev)
+    n_lists = int(li.shape[0])
+    num = torch.empty(n_lists, dtype=torch.int64, device=dev)
+    den = torch.empty(n_lists, dtype=torch.int64, device=dev)
+    pen = torch.empty(n_lists, dtype=torch.float32, device=dev)
+    if n_lists == 0:
+        return pen, num, den
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.anirec_list_calibration(_lib.ptr(cat), int(cat.shape[0]), n_cat, _lib.ptr(li), _lib.ptr(pr), n_lists,
+                                           k, _lib.ptr(num), _lib.ptr(den), _lib.ptr(pen), _lib.ptr(err), _stream()),
+               "anirec_list_calibration")
+    if int(err.item()):
+        raise ValueError("list_calibration: list index out of range, or a profile entry outside 0 .. 2**24")
+    return pen, num, den
+
+
 def check_explain(width, k, m):
     """The argument checks of ``explain_lists`` (no device needed): ValueError naming the limit for a list shorter than
     one slot or longer than anirec_explain_max_k(width), or ``m`` outside 1 .. ANIREC_EXPLAIN_MAX_M.  Returns

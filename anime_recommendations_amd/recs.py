@@ -234,6 +234,43 @@ def diverse_topk(U, A, head, users, k, pool, diversity, watched_bits=None):
     return idx, score, pen
 
 
+def calibrated_topk(U, A, head, users, k, pool, calibration, cat_bits, n_cat, profile, watched_bits=None):
+    """Calibrated top-k per user: the ``pool`` best unwatched anime by predicted rating
+    (``ops.predict_topk``), re-ranked greedily by ``ops.calibrate_rerank`` — each pick trades a candidate's rating
+    against the distance between the list's category proportions and the user's own (``profile``: one row of
+    ``fave_profile(..., users=users)`` counts per entry of ``users``; ``cat_bits`` [n_anime, ceil(n_cat/32)]: the
+    category bit rows of the anime).  Batched over ``users``; ``watched_bits`` as predict_topk.  ``pool`` is clamped to
+    the number of anime.  ``calibration`` == 0 is ``ops.predict_topk(..., k)`` itself: no pool, no re-rank, the bits of
+    model_recs.
+    Returns (idx int32 [n_users, k], p fp32 [n_users, k], miscal fp32 [n_users, k] or None at calibration 0): the anime,
+    their predicted ratings and the miscalibration of the list down to and including each pick; -1 / NaN / NaN padded.
+    Raises ValueError for ``calibration`` outside [0, 1], k < 1, pool < k, and, at calibration > 0, for k above the
+    number of anime, a pool above anirec_calibrate_max_cand() or ``n_cat`` outside 1 .. 128."""
+    from . import ops
+    k, pool, calibration = int(k), int(pool), float(calibration)
+    if not 0.0 <= calibration <= 1.0:
+        raise ValueError("calibrated_topk: calibration = %r must be in [0, 1]" % (calibration,))
+    if k < 1:
+        raise ValueError("calibrated_topk: k must be >= 1")
+    if pool < k:
+        raise ValueError("calibrated_topk: pool = %d is smaller than k = %d" % (pool, k))
+    if calibration == 0.0:
+        return ops.predict_topk(U, A, head, users, k, watched_bits) + (None,)
+    pool = min(pool, int(A.shape[0]))
+    ops.check_calibrate(n_cat, pool, k, calibration)      # (k <= pool <= the kernel's list limit, before any GPU work)
+    cand, p = ops.predict_topk(U, A, head, users, pool, watched_bits)
+    idx, _, score, pen = ops.calibrate_rerank(cat_bits, n_cat, cand, p, profile, k, calibration)
+    return idx, score, pen
+
+
+def list_calibration(lists, cat_bits, n_cat, profile):
+    """The miscalibration of lists (``ops.list_calibration``): (miscal fp32 [n_lists], num int64, den int64) on the
+    device — the total variation distance between the category-token distribution of ``lists[l]`` (rows of ``cat_bits``,
+    -1 padded) and that of ``profile[l]``, miscal = float32(num / den)."""
+    from . import ops
+    return ops.list_calibration(cat_bits, n_cat, lists, profile)
+
+
 def group_csr(groups, user_ids):
     """The CSR ``ops.group_topk`` takes, from groups given as lists of user ids: (users int64 [n_distinct]: the rows of
     ``user_ids`` (the model's index -> id table) of the distinct members, in order of first appearance, each once;

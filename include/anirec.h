@@ -823,6 +823,65 @@ int anirec_mmr_rerank(const float *What, int32_t dim, int32_t n_rows, const int3
 int anirec_list_similarity(const float *What, int32_t dim, int32_t n_rows, const int32_t *list_idx, int32_t n_lists,
                            int32_t k, float *out_sim_max, float *out_sim_sum, int32_t *err_flag, void *stream);
 
+/* CALIBRATED LISTS — greedy re-rank towards the user's own category proportions (Steck, "Calibrated recommendations",
+ * RecSys 2018, with total variation in place of KL).  A rating head amplifies the majority taste: favourites that are
+ * 70 % action and 30 % romance give a top-10 that is all action.  Here a list of n_cand candidates becomes a list of k
+ * picks, each pick trading a candidate's score against the miscalibration of the list with that candidate added.
+ * cat_bits [n_rows][cw] uint32, cw = ceil(n_cat / 32), 1 <= n_cat <= 128: bit c of row a set iff anime a carries
+ * category c (anirec_fave_profile's layout; bits at positions >= n_cat of the last word are ignored).  List l holds
+ * the candidates cand_idx[l][0 .. n_cand) (rows of cat_bits; -1 = an empty slot) with relevance cand_score[l][.] and the
+ * profile profile[l][0 .. n_cat): one row of anirec_fave_profile's counts.  Tokens are unweighted on both sides: an
+ * anime with three categories adds three tokens (the word-cloud semantics of get_genres, and what the profile counts).
+ *     present  a candidate whose index is >= 0 and whose score is not NaN; b_i its category bits, pop_i their number.
+ *              An index that appears twice is two candidates.
+ *     state    q_c = the number of picked candidates that carry category c, Q = sum q_c, P = sum p_c
+ *     pen_i    the total variation distance of the two token distributions for the list extended by candidate i,
+ *              Q' = Q + pop_i, q' = q + b_i:
+ *                  0.0f when P == 0 (nothing to calibrate to); otherwise 1.0f when Q' == 0 (the list says nothing);
+ *                  otherwise num = sum_c |p_c Q' - q'_c P|, den = 2 P Q', both int64, and
+ *                  pen = (float)((double)num / (double)den)
+ *              With p_c <= 2^24, n_cat <= 128 and n_cand <= 1024: P <= 2^31, Q' <= 2^17, every term < 2^42 and
+ *              num <= den <= 2^49 < 2^53: both conversions to double are exact, the division and the conversion to fp32
+ *              are each correctly rounded, and no sum depends on its order.
+ *     val_i    (omc * score_i) - (calibration * pen_i) in fp32, omc = 1.0f - calibration: each product rounded, then
+ *              the difference, nothing contracted into an fma
+ *     pick s   = 0 .. k-1: among the present, unpicked candidates the one with the largest val, in anirec_mmr_rerank's
+ *              order: ties (-0 == +0) go to the lowest position, a NaN val sorts after every number.  The pick at
+ *              position pos is added to q and writes
+ *                  out_idx[l][s] = cand_idx[l][pos], out_pos[l][s] = pos, out_score[l][s] = cand_score[l][pos],
+ *                  out_pen[l][s] = pen_pos at that moment: the miscalibration of the list INCLUDING pick s
+ * With fewer than k present candidates the rest of the row is -1 / -1 / NaN / NaN.  The result is greedy: its first k'
+ * columns are the result for k' < k.  calibration == 0 returns the first k present candidates in (score descending,
+ * position ascending) order.
+ * One group of lanes per list (a wave up to 256 candidates, a workgroup of four beyond), every pick inside one launch;
+ * anirec_calibrate_max_cand() = 1024 candidates at most.  No workspace, no atomics, stream-ordered and
+ * graph-capturable.  A list's outputs depend on that list alone.
+ * n_cat outside 1 .. 128, n_rows < 1, a negative count, k < 1 or k > n_cand, n_cand > anirec_calibrate_max_cand(),
+ * calibration outside [0, 1] or NaN, a NULL pointer with n_lists > 0: ANIREC_EINVAL before anything is enqueued or
+ * written.  n_lists == 0: ANIREC_OK, nothing enqueued.  Otherwise every element of the four outputs and *err_flag
+ * (device) is written: *err_flag becomes 1 on a bad list (0 without one) — a candidate index below -1 or at or above
+ * n_rows, or a profile entry that is negative or above 2^24: that list's whole output is -1 / -1 / NaN / NaN, nothing
+ * is read through its indices, the other lists are unaffected. */
+size_t anirec_calibrate_max_cand(void);
+int anirec_calibrate_rerank(const uint32_t *cat_bits, int32_t n_rows, int32_t n_cat, const int32_t *cand_idx,
+                            const float *cand_score, const int32_t *profile, int32_t n_lists, int32_t n_cand, int32_t k,
+                            float calibration, int32_t *out_idx, int32_t *out_pos, float *out_score, float *out_pen,
+                            int32_t *err_flag, void *stream);
+
+/* The miscalibration of lists a caller holds, by the definition above: lists [n_lists][k] = rows of cat_bits, -1 = an
+ * empty slot (skipped; an index that appears twice is two slots), 1 <= k <= anirec_calibrate_max_cand();
+ * profile [n_lists][n_cat].  With q_c and Q counted over the list's present slots:
+ *     P == 0:     out_num[l] = 0, out_den[l] = 1, out_pen[l] = 0.0f
+ *     else Q == 0: out_num[l] = 1, out_den[l] = 1, out_pen[l] = 1.0f
+ *     else        out_num[l] = sum_c |p_c Q - q_c P|, out_den[l] = 2 P Q, out_pen[l] = (float)((double)num / (double)den)
+ * So for the first s + 1 columns of an anirec_calibrate_rerank call's out_idx and the same profile, out_pen is that
+ * call's out_pen[l][s], bit for bit.  One wave per list, no workspace, no atomics, graph-capturable.  Refusals as above
+ * (n_cat, n_rows, counts, k, NULL pointers); a bad list (an index below -1 or at or above n_rows, a profile entry that
+ * is negative or above 2^24) gets -1 / -1 / NaN and *err_flag = 1, nothing read through its indices. */
+int anirec_list_calibration(const uint32_t *cat_bits, int32_t n_rows, int32_t n_cat, const int32_t *lists,
+                            const int32_t *profile, int32_t n_lists, int32_t k, int64_t *out_num, int64_t *out_den,
+                            float *out_pen, int32_t *err_flag, void *stream);
+
 /* EXPLAINED LISTS — why an anime is in a list: a predicted rating sees an anime only through the cosine of two rows,
  * so "recommended because you rated X, Y, Z" has an answer inside the model: the anime of the user's own history whose
  * rows lie closest to the listed one, each weighted by what the user gave it.
