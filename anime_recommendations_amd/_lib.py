@@ -272,6 +272,14 @@ PROTOTYPES = {
     "anirec_calibrate_rerank": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
                                           _vp]),
     "anirec_list_calibration": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    # ranks to per-unit metric sums, and the Poisson bootstrap of those sums over units (thr: a host table)
+    "anirec_boot_tile": (_sz, []),
+    "anirec_boot_col_tile": (_sz, [_i32]),
+    "anirec_boot_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "anirec_rank_gain_rows": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "anirec_boot_sums": (C.c_int, [_vp, _vp, _i32, _i32, C.c_uint32, _i32, C.POINTER(C.c_uint32), _i32, _vp, _vp, _vp,
+                                   _sz, _vp]),
+    "anirec_boot_weights": (C.c_int, [_vp, _i32, C.c_uint32, _i32, C.POINTER(C.c_uint32), _i32, _vp, _vp]),
 }
 
 

@@ -856,7 +856,30 @@ def baseline_names(baseline):
     return tuple(b for b in BASELINES if b in names)
 
 
-def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None):
+def _ci_columns(columns, boot, system, others, key):
+    """The bootstrap's columns of one system's figures: ``columns`` maps a column name to the bootstrap metric(s) behind it
+    (a name, or a list of names for a frame column with one row per k).  Returns {column + "_lo" / "_hi": ...} and, for
+    every system of ``others`` (name -> suffix), {column + "_diff_" + suffix (+ "_lo" / "_hi"), column + "_p_" + suffix},
+    where ``key(column, part)`` places the part ("lo", "diff_x", ...) in the column's name."""
+    out = {}
+
+    def pick(cell, metric):
+        return [cell[m] for m in metric] if isinstance(metric, list) else cell[metric]
+
+    for col, metric in columns.items():
+        fig = {m: boot["figures"][system][m] for m in (metric if isinstance(metric, list) else [metric])}
+        for part in ("lo", "hi"):
+            out[key(col, part)] = pick({m: f[part] for m, f in fig.items()}, metric)
+        for other, suffix in others.items():
+            d = boot["diffs"][other]
+            for part, name in (("diff", "diff_" + suffix), ("lo", "diff_%s_lo" % suffix), ("hi", "diff_%s_hi" % suffix),
+                               ("p", "p_" + suffix)):
+                out[key(col, name)] = pick({m: d[m][part] for m in d}, metric)
+    return out
+
+
+def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None,
+                   ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -870,25 +893,42 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     (``recs.itemknn_fit`` / ``recs.itemknn_rank``), each listed user's history that user's training
     ratings at or above the threshold with weight 1; the same columns and keys under the name itemknn.  ``itemknn``: a
     dict overriding ITEMKNN_DEFAULTS (neighbours, measure, shrink, min_support, min_rating).
-    A sequence of names gives both, popularity first.  None: neither."""
+    A sequence of names gives both, popularity first.  None: neither.
+    ``compare_model``: a second model dict over the same id tables, ranked by a second ``ops.predict_rank`` on the same
+    targets and bits and reported as the system ``compare`` (the baselines' columns and keys under that name).
+    ``ci_replicates`` > 0: a Poisson bootstrap over the held-out USERS (``recs.bootstrap_metrics``), seeded
+    by ``ci_seed``, the unit keys the user indices: the frame gains <col>_lo / <col>_hi (the ``ci_level`` percentile
+    interval) for hit_rate, ndcg and every other system's columns and, for every other system s, hit_rate_diff_<s> (the
+    model's figure minus s's, on the same weights), hit_rate_diff_<s>_lo / _hi and the two-sided hit_rate_p_<s>, the same
+    for ndcg; the summary gains the same for mrr and mean_rank and ci_replicates, ci_level, ci_seed, ci_n_rep_used.
+    median_rank is no sum and gets no interval.  With the defaults the frame and the summary are what they were, key for
+    key.  ValueError before any GPU use for ci_replicates < 0 or a ci_level outside (0, 1)."""
     import torch
     from . import ops, recs, weights_io
     baselines = baseline_names(baseline)
+    ci_replicates, ci_level = recs.check_bootstrap(ci_replicates, ci_level)
     knn_par = dict(ITEMKNN_DEFAULTS)
     for key, v in (itemknn or {}).items():
         if key not in knn_par:
             raise ValueError("itemknn parameter %r is not one of %s" % (key, ", ".join(ITEMKNN_DEFAULTS)))
         knn_par[key] = v
     U, A = _tables_of(model, table)
+    others = baselines + (("compare",) if compare_model is not None else ())
+    if compare_model is not None:
+        cU, cA = _tables_of(compare_model, table)
     ks = sorted({int(k) for k in ks})
     if not ks or ks[0] < 1:
         raise ValueError("eval_k must list at least one k >= 1 (got %r)" % (ks,))
     users, row, anime, train = held_out_targets(table, test_size, min_rating)
-    base_rank = {b: np.zeros(0, np.int32) for b in baselines}
+    base_rank = {b: np.zeros(0, np.int32) for b in others}
     if len(row):
         tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
         seen = recs.listed_seen_bits(table.user[train], table.anime[train], users, table.n_users, table.n_anime)
         rank, _ = ops.predict_rank(tU, tA, weights_io.model_head(model), users, row, anime, watched_bits=seen)
+        if compare_model is not None:
+            base_rank["compare"], _ = ops.predict_rank(torch.as_tensor(cU).cuda(), torch.as_tensor(cA).cuda(),
+                                                       weights_io.model_head(compare_model), users, row, anime,
+                                                       watched_bits=seen)
         if "popularity" in baselines:
             score = recs.popularity_scores(table.anime[train], table.n_anime, table.n_users).to(seen.device)
             base_rank["popularity"] = ops.score_rank(score, len(users), row, anime, watched_bits=seen)
@@ -908,7 +948,7 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     for k in ks:
         summary["hit_rate@%d" % k] = m["hit_rate"][k]
         summary["ndcg@%d" % k] = m["ndcg"][k]
-    for name in baselines:
+    for name in others:
         b = recs.ranking_metrics(base_rank[name], ks)
         frame["hit_rate_" + name] = [b["hit_rate"][k] for k in ks]
         frame["ndcg_" + name] = [b["ndcg"][k] for k in ks]
@@ -916,6 +956,21 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         for k in ks:
             summary["%s_hit_rate@%d" % (name, k)] = b["hit_rate"][k]
             summary["%s_ndcg@%d" % (name, k)] = b["ndcg"][k]
+    if ci_replicates:
+        systems = dict([("model", rank)] + [(name, base_rank[name]) for name in others])
+        boot = recs.bootstrap_metrics(systems, row, len(users), ks, ci_replicates, ci_seed, ci_level, unit_key=users,
+                                      n_rows=table.n_anime)
+        per_k = {"hit_rate": ["hit_rate@%d" % k for k in ks], "ndcg": ["ndcg@%d" % k for k in ks]}
+        once = {"mrr": "mrr", "mean_rank": "mean_rank"}
+        for col, v in _ci_columns(per_k, boot, "model", {o: o for o in others}, lambda c, part: c + "_" + part).items():
+            frame[col] = v
+        summary.update(_ci_columns(once, boot, "model", {o: o for o in others}, lambda c, part: c + "_" + part))
+        for name in others:
+            for col, v in _ci_columns(per_k, boot, name, {}, lambda c, part: "%s_%s_%s" % (c, name, part)).items():
+                frame[col] = v
+            summary.update(_ci_columns(once, boot, name, {}, lambda c, part: "%s_%s_%s" % (name, c, part)))
+        summary.update({"ci_replicates": ci_replicates, "ci_level": ci_level, "ci_seed": int(ci_seed),
+                        "ci_n_rep_used": boot["n_rep_used"]})
     return frame, summary
 
 
@@ -923,7 +978,8 @@ LISTS_COLUMNS = ["diversity", "k", "pool", "hit_rate", "ndcg", "mrr", "mean_simi
                  "coverage", "gini", "novelty"]
 
 
-def evaluate_lists_frame(model, table, test_size, min_rating, diversities, k=10, pool=100):
+def evaluate_lists_frame(model, table, test_size, min_rating, diversities, k=10, pool=100, ci_replicates=0,
+                         ci_level=0.95, ci_seed=0):
     """What ``diverse_recs --diversity`` costs in hits and buys in spread: for each value d of
     ``diversities`` every user with a held-out rating at or above ``min_rating`` gets the list
     ``recs.diverse_topk(..., k, pool, d)`` under evaluate_frame's mask (the anime the user has a TRAINING rating for), and
@@ -932,10 +988,16 @@ def evaluate_lists_frame(model, table, test_size, min_rating, diversities, k=10,
     slice's rating counts).  The users, the targets and the mask are evaluate_frame's, so the d = 0 row's hit_rate and ndcg
     are its hit_rate@k and ndcg@k.  Returns (frame with one row per d and the columns LISTS_COLUMNS; summary dict with the
     keys ``lists_<column>@<d>``).  ValueError for id tables that are not the table's, a d outside [0, 1], k < 1 or
-    pool < k, before any GPU use."""
+    pool < k, before any GPU use.
+    ``ci_replicates`` > 0: evaluate_frame's bootstrap over the same users and keys, on the targets' slots in the lists
+    (``recs.hit_positions``; gain tables of length k): hit_rate, ndcg and mrr of every row gain _lo / _hi and, against the
+    FIRST listed diversity on the same weights, <col>_diff (first - this row), <col>_diff_lo / _hi and <col>_p (0, 0, 0
+    and 1 on the first row itself); the summary gains them under the same keys and lists_ci_n_rep_used.  The five spread
+    figures are no sums over targets and get nothing."""
     import torch
     from . import ops, recs, weights_io
     U, A = _tables_of(model, table)
+    ci_replicates, ci_level = recs.check_bootstrap(ci_replicates, ci_level)
     ds = [float(d) for d in diversities]
     if not ds or not all(0.0 <= d <= 1.0 for d in ds):      # (a NaN fails both comparisons)
         raise ValueError("lists_diversity must list at least one diversity in [0, 1] (got %r)" % (list(diversities),))
@@ -945,21 +1007,38 @@ def evaluate_lists_frame(model, table, test_size, min_rating, diversities, k=10,
     if pool < k:
         raise ValueError("lists_pool = %d is smaller than lists_k = %d" % (pool, k))
     users, row, anime, train = held_out_targets(table, test_size, min_rating)
-    rows = []
+    rows, slots = [], {}
     if len(row):
         tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
         head = weights_io.model_head(model)
         seen = recs.listed_seen_bits(table.user[train], table.anime[train], users, table.n_users, table.n_anime)
         count = recs.popularity_scores(table.anime[train], table.n_anime, table.n_users)
         Wh = ops.rownorm(tA, device=tA.device)
-        for d in ds:
+        for i, d in enumerate(ds):
             idx, _, _ = recs.diverse_topk(tU, tA, head, users, k, pool, d, seen)
             rows.append(recs.list_quality(Wh, idx, k, row, anime, item_count=count, n_raters=table.n_users))
+            if ci_replicates:
+                slots[i] = torch.as_tensor(recs.hit_positions(idx[:, :k], row, anime), device=idx.device)
     else:
         rows = [dict.fromkeys(LISTS_COLUMNS[3:], float("nan")) for _ in ds]
-    frame = pd.DataFrame([dict({"diversity": d, "k": k, "pool": pool}, **{c: q[c] for c in LISTS_COLUMNS[3:]})
-                          for d, q in zip(ds, rows)], columns=LISTS_COLUMNS)
+        slots = {i: np.zeros(0, np.int64) for i in range(len(ds))}
+    columns = list(LISTS_COLUMNS)
     summary = {"lists_%s@%g" % (c, d): q[c] for d, q in zip(ds, rows) for c in LISTS_COLUMNS[3:]}
+    if ci_replicates:
+        boot = recs.bootstrap_metrics(slots, row, len(users), [k], ci_replicates, ci_seed, ci_level, unit_key=users,
+                                      n_rows=k)
+        metric = {"hit_rate": "hit_rate@%d" % k, "ndcg": "ndcg@%d" % k, "mrr": "mrr"}
+        for i, q in enumerate(rows):
+            q.update(_ci_columns(metric, boot, i, {}, lambda c, part: c + "_" + part))
+            for c, m in metric.items():
+                dv = boot["diffs"][i][m] if i else {"diff": 0.0, "lo": 0.0, "hi": 0.0, "p": 1.0}
+                q.update({c + "_diff": dv["diff"], c + "_diff_lo": dv["lo"], c + "_diff_hi": dv["hi"], c + "_p": dv["p"]})
+        extra = [c + s for c in metric for s in ("_lo", "_hi", "_diff", "_diff_lo", "_diff_hi", "_p")]
+        columns += extra
+        summary.update({"lists_%s@%g" % (c, d): q[c] for d, q in zip(ds, rows) for c in extra})
+        summary["lists_ci_n_rep_used"] = boot["n_rep_used"]
+    frame = pd.DataFrame([dict({"diversity": d, "k": k, "pool": pool}, **{c: q[c] for c in columns[3:]})
+                          for d, q in zip(ds, rows)], columns=columns)
     return frame, summary
 
 

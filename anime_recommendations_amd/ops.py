@@ -1098,6 +1098,112 @@ def itemknn_scores(nbr_idx, nbr_sim, offsets, hist_idx, hist_w=None, workspace=N
     return out
 
 
+BOOT_MAX_REP = 65536     # anirec_boot_sums / anirec_boot_weights: the most replicates of one call
+BOOT_MAX_THR = 16        # and the most thresholds of a weight table
+BOOT_MAX_COL = 4096      # the most columns anirec_boot_sums takes (anirec_rank_gain_rows: n_sys * n_metric + 1)
+
+
+def check_boot(n_rep, thr):
+    """The argument checks of ``boot_sums`` / ``boot_weights`` (no device needed): ValueError for ``n_rep`` outside
+    0 .. BOOT_MAX_REP or a threshold table that is longer than BOOT_MAX_THR, not uint32 or not ascending.  Returns
+    (n_rep, the table as a ctypes uint32 array, its length)."""
+    n_rep = int(n_rep)
+    if not 0 <= n_rep <= BOOT_MAX_REP:
+        raise ValueError("bootstrap: n_rep = %d must be in 0 .. %d" % (n_rep, BOOT_MAX_REP))
+    t = [int(x) for x in thr]
+    if len(t) > BOOT_MAX_THR or any(not 0 <= x <= 0xFFFFFFFF for x in t) or any(b < a for a, b in zip(t, t[1:])):
+        raise ValueError("bootstrap: the threshold table must hold at most %d ascending uint32 values" % BOOT_MAX_THR)
+    return n_rep, (C.c_uint32 * max(len(t), 1))(*t), len(t)
+
+
+def boot_limit(n_units, n_thr):
+    """The exactness guard of ``boot_sums``: every value must lie in [0, 2**62 // (max(n_thr, 1) * n_units))."""
+    return (1 << 62) // (max(int(n_thr), 1) * max(int(n_units), 1))
+
+
+def rank_gain_rows(ranks, target_unit, n_units, gain, check=True):
+    """Per-unit metric sums from ranks (anirec_rank_gain_rows): ``ranks`` int32 [n_sys, n_t] on the
+    device, ``target_unit`` int [n_t] (each target's position among the ``n_units`` units), ``gain`` uint32-valued
+    [n_metric, n_gain] fixed-point gains per rank (``recs.rank_gain_tables``; any integer dtype, values in
+    0 .. 2**32 - 1).  Returns int64 [n_units, n_sys * n_metric + 1]: column s * n_metric + m the unit's summed gain, a
+    rank < 0 or >= n_gain gaining 0; the last column the unit's number of targets.  Raises ValueError for a
+    target_unit out of range; with ``check=False`` returns (out, device flag) and nothing synchronises."""
+    _need_gpu()
+    lib = _lib.load()
+    assert isinstance(ranks, torch.Tensor) and ranks.is_cuda and ranks.dim() == 2, "int32 [n_sys, n_t] device ranks"
+    dev = ranks.device
+    rk = _i32(ranks, dev)
+    tu = _i32(target_unit, dev).reshape(-1)
+    g = torch.as_tensor(gain, device=dev)
+    assert g.dim() == 2 and not g.dtype.is_floating_point, "integer [n_metric, n_gain] gain tables"
+    g = (g.to(torch.int64) & 0xFFFFFFFF).to(torch.int32).contiguous()     # the uint32 bits, in an int32 tensor
+    n_sys, n_t, n_units = int(rk.shape[0]), int(rk.shape[1]), int(n_units)
+    n_metric, n_gain = int(g.shape[0]), int(g.shape[1])
+    if n_sys < 1 or n_metric < 1 or n_gain < 1 or n_units < 0 or n_sys * n_metric + 1 > BOOT_MAX_COL:
+        raise ValueError("rank_gain_rows: n_sys, n_metric and n_gain must be >= 1, n_units >= 0 and n_sys * n_metric + 1 "
+                         "<= %d" % BOOT_MAX_COL)
+    if int(tu.numel()) != n_t:
+        raise ValueError("rank_gain_rows: target_unit must hold one unit per target")
+    out = torch.empty(n_units, n_sys * n_metric + 1, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.anirec_rank_gain_rows(_lib.ptr(rk), n_sys, n_t, _lib.ptr(tu), n_units, _lib.ptr(g), n_metric, n_gain,
+                                         _lib.ptr(out), _lib.ptr(err), _stream()), "anirec_rank_gain_rows")
+    if not check:
+        return out, err
+    if int(err.item()):
+        raise ValueError("rank_gain_rows: target_unit out of range")
+    return out
+
+
+def boot_sums(values, unit_key, seed, n_rep, thr, workspace=None, check=True):
+    """Bootstrap replicates of column sums (anirec_boot_sums): ``values`` int64 [n_units, n_col] on the
+    device, ``unit_key`` int32 [n_units] (the unit's own number: the weight of replicate b is a hash of (seed, b, key),
+    so a subset of the units draws the same weights in a call of its own), ``thr`` the ascending uint32 weight table
+    (``recs.POISSON1_THRESHOLDS``).  Returns int64 [n_rep + 1, n_col]: row b the weighted column sums of replicate b,
+    row 0 the plain sums.  Raises ValueError for a value outside [0, ``boot_limit``) (the output is then all -1); with
+    ``check=False`` returns (out, device flag) and nothing synchronises."""
+    n_rep, table, n_thr = check_boot(n_rep, thr)
+    _need_gpu()
+    lib = _lib.load()
+    assert isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.int64 and values.dim() == 2, \
+        "int64 [n_units, n_col] device values"
+    dev = values.device
+    v = values.contiguous()
+    key = _i32(unit_key, dev).reshape(-1)
+    n_units, n_col = int(v.shape[0]), int(v.shape[1])
+    if not 1 <= n_col <= BOOT_MAX_COL:
+        raise ValueError("boot_sums: n_col = %d must be in 1 .. %d" % (n_col, BOOT_MAX_COL))
+    if int(key.numel()) != n_units:
+        raise ValueError("boot_sums: unit_key must hold one key per row of values")
+    out = torch.empty(n_rep + 1, n_col, dtype=torch.int64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty(int(lib.anirec_boot_workspace_bytes(n_units, n_col, n_rep)), dtype=torch.uint8, device=dev)
+    _lib.check(lib.anirec_boot_sums(_lib.ptr(v), _lib.ptr(key), n_units, n_col, int(seed) & 0xFFFFFFFF, n_rep, table,
+                                    n_thr, _lib.ptr(out), _lib.ptr(err), _lib.ptr(workspace), workspace.numel(),
+                                    _stream()), "anirec_boot_sums")
+    if not check:
+        return out, err
+    if int(err.item()):
+        raise ValueError("boot_sums: a value is negative or >= %d (2**62 / (max(n_thr, 1) * n_units)): the sums would "
+                         "not be exact" % boot_limit(n_units, n_thr))
+    return out
+
+
+def boot_weights(unit_key, seed, n_rep, thr, device="cuda:0"):
+    """The bootstrap weights themselves (anirec_boot_weights): uint8 [n_rep, n_units], row b - 1 the weights replicate
+    b = 1 .. n_rep gives the units of ``unit_key`` — what ``boot_sums`` multiplies by, for figures that are no sums."""
+    n_rep, table, n_thr = check_boot(n_rep, thr)
+    _need_gpu()
+    lib = _lib.load()
+    dev = unit_key.device if isinstance(unit_key, torch.Tensor) and unit_key.is_cuda else torch.device(device)
+    key = _i32(unit_key, dev).reshape(-1)
+    out = torch.empty(n_rep, int(key.numel()), dtype=torch.uint8, device=dev)
+    _lib.check(lib.anirec_boot_weights(_lib.ptr(key), int(key.numel()), int(seed) & 0xFFFFFFFF, n_rep, table, n_thr,
+                                       _lib.ptr(out), _stream()), "anirec_boot_weights")
+    return out
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

@@ -807,3 +807,139 @@ def itemknn_rank(knn, offsets, hist_idx, hist_w, watched_bits, target_row, targe
         r = ops.rows_rank(rows, tr[sel] - l0, ta[sel], None if watched_bits is None else watched_bits[l0:l1])
         rank[torch.as_tensor(sel, device=dev)] = r
     return rank
+
+
+# ----------------------------------------------------------------------------------------
+# confidence intervals: a Poisson bootstrap over users
+# ----------------------------------------------------------------------------------------
+# floor(2**32 * CDF(j)) of Poisson(1), j = 0 .. 12 (from 60-digit decimals): the weight of a unit is the number of
+# thresholds its hash reaches, 0 .. 13
+POISSON1_THRESHOLDS = (0x5e2d58d8, 0xbc5ab1b1, 0xeb715e1d, 0xfb239797, 0xff1025f5, 0xffd90f3b, 0xfffa8b71, 0xffff540c,
+                       0xffffed1f, 0xfffffe21, 0xffffffd4, 0xfffffffc, 0xffffffff)
+GAIN_SCALE = float(1 << 30)     # the fixed point of a gain table: q = rint(gain * 2**30)
+
+
+def rank_gain_tables(ks, n_rows):
+    """``ranking_metrics``' gains as integer tables over the ranks 0 .. n_rows - 1 (``ops.rank_gain_rows``): returns
+    (tables uint32 [M, n_rows], names, scales float64 [M]) with the metrics ``hit_rate@k`` (rank < k) and ``ndcg@k``
+    (1 / log2(rank + 2) where rank < k) for each k of ``ks`` in ascending order, then ``mrr`` (1 / (rank + 1)) and
+    ``mean_rank`` (the rank itself).  A table holds rint(gain * 2**30) computed in float64, the mean-rank table the rank
+    at scale 1: a metric is sum(table[rank]) / (scale * n), off from the float64 mean by at most 2**-31 per term.
+    ValueError for no k, a k < 1 or n_rows < 1."""
+    ks = sorted({int(k) for k in ks})
+    n_rows = int(n_rows)
+    if not ks or ks[0] < 1:
+        raise ValueError("rank_gain_tables: at least one k >= 1 (got %r)" % (ks,))
+    if not 1 <= n_rows < 1 << 31:
+        raise ValueError("rank_gain_tables: n_rows must be in 1 .. 2**31 - 1")
+    r = np.arange(n_rows, dtype=np.float64)
+    dcg = 1.0 / np.log2(r + 2.0)
+    tables = [np.where(r < k, 1.0, 0.0) for k in ks] + [np.where(r < k, dcg, 0.0) for k in ks] + [1.0 / (r + 1.0)]
+    q = [np.rint(t * GAIN_SCALE).astype(np.uint32) for t in tables] + [np.arange(n_rows, dtype=np.uint32)]
+    names = ["hit_rate@%d" % k for k in ks] + ["ndcg@%d" % k for k in ks] + ["mrr", "mean_rank"]
+    scales = np.asarray([GAIN_SCALE] * (len(names) - 1) + [1.0], np.float64)
+    return np.stack(q), names, scales
+
+
+def check_bootstrap(n_rep, level):
+    """``bootstrap_metrics``' checks of the replicate count and the level: (int n_rep >= 0, float level in (0, 1)), or a
+    ValueError."""
+    n_rep, level = int(n_rep), float(level)
+    if n_rep < 0:
+        raise ValueError("bootstrap: n_rep must be >= 0 (got %d)" % n_rep)
+    if not 0.0 < level < 1.0:
+        raise ValueError("bootstrap: level must lie inside (0, 1) (got %r)" % level)
+    return n_rep, level
+
+
+def bootstrap_figures(sums, scales, level=0.95):
+    """The host part of the bootstrap, float64: ``sums`` int64 [B + 1, n_sys * M + 1] as ``ops.boot_sums`` returns them
+    from ``ops.rank_gain_rows``' rows (row 0 the sample, row b replicate b; the last column the weighted number of
+    targets), ``scales`` [M] the metrics' fixed points.  The figure of row b is sum / (scale * count).  Returns a dict
+    of arrays: value [n_sys, M] (row 0), se (std with ddof = 1 of the replicates), lo / hi (np.quantile of the
+    replicates at (1 - level) / 2 and (1 + level) / 2); for the systems after the first, on the same weights, diff
+    [n_sys - 1, M] = first - other of the values, diff_lo / diff_hi the quantiles of the replicates' differences and
+    p = min(1, 2 (1 + min(#{d <= 0}, #{d >= 0})) / (n_rep_used + 1)), two-sided; n_rep = B and n_rep_used, the replicates
+    whose weighted count is above 0 (the others are dropped).  With fewer than 2 left, se, the quantiles and p are NaN."""
+    _, level = check_bootstrap(0, level)
+    s = np.asarray(sums, np.int64)
+    scales = np.asarray(scales, np.float64).reshape(-1)
+    M = int(scales.size)
+    if s.ndim != 2 or s.shape[0] < 1 or M < 1 or (s.shape[1] - 1) % M or s.shape[1] - 1 < M:
+        raise ValueError("bootstrap_figures: sums must be [B + 1, n_sys * %d + 1] (got %s)" % (M, tuple(s.shape)))
+    n_sys = (s.shape[1] - 1) // M
+    count = s[:, -1].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fig = s[:, :-1].astype(np.float64).reshape(-1, n_sys, M) / (scales[None, None, :] * count[:, None, None])
+    value = np.where(count[0] > 0, fig[0], np.nan)
+    reps = fig[1:][s[1:, -1] > 0]
+    used = int(reps.shape[0])
+    d = reps[:, :1, :] - reps[:, 1:, :]
+    nan = np.full((n_sys, M), np.nan)
+    out = {"value": value, "se": nan, "lo": nan, "hi": nan, "diff": value[:1] - value[1:],
+           "diff_lo": nan[1:], "diff_hi": nan[1:], "p": nan[1:], "n_rep": int(s.shape[0]) - 1, "n_rep_used": used}
+    if used >= 2:
+        qs = [(1.0 - level) / 2.0, (1.0 + level) / 2.0]
+        out["se"] = reps.std(axis=0, ddof=1)
+        out["lo"], out["hi"] = np.quantile(reps, qs, axis=0)
+        out["diff_lo"], out["diff_hi"] = np.quantile(d, qs, axis=0) if n_sys > 1 else (nan[1:], nan[1:])
+        tail = np.minimum((d <= 0).sum(axis=0), (d >= 0).sum(axis=0)).astype(np.float64)
+        out["p"] = np.minimum(1.0, 2.0 * (1.0 + tail) / (used + 1.0))
+    return out
+
+
+def bootstrap_metrics(ranks_by_system, target_row, n_units, ks, n_rep=1000, seed=0, level=0.95, unit_key=None,
+                      n_rows=None, device="cuda:0"):
+    """Ranking metrics with their spread: a Poisson bootstrap over USERS — replicate b >= 1 re-weights
+    every unit (a user: its held-out ratings are not independent) by an integer Poisson(1) draw that is a hash of
+    (seed, b, the unit's key) and is never stored; replicate 0 is the sample itself.  ``ranks_by_system``: an ordered
+    dict name -> ranks [n_t] (tensors on one device, or arrays; 0 = ranked first, a rank < 0 or >= ``n_rows`` gains
+    nothing) of the same targets; the first system is the one the others are compared with.  ``target_row`` [n_t]: each
+    target's position among the ``n_units`` units; ``unit_key`` [n_units]: the units' own numbers (the user indices;
+    default 0 .. n_units - 1) — the weights follow the key, so a subset of the users re-draws the same weights.
+    ``n_rows``: the length of the gain tables (default: the largest rank + 1).  The ranks are reduced to per-unit integer
+    sums (``ops.rank_gain_rows``), those to replicate sums (``ops.boot_sums``), and ``bootstrap_figures`` reads them.
+    Returns {"metrics": the names of ``rank_gain_tables(ks, n_rows)``, "systems", "n" (targets), "n_units", "n_rep",
+    "n_rep_used", "level", "seed", "figures": {system: {metric: {"value", "se", "lo", "hi"}}}, "diffs": {other system:
+    {metric: {"diff", "lo", "hi", "p"}}}} in float64.  ValueError before any GPU use for n_rep < 0, a level outside
+    (0, 1), rank vectors of different lengths, no system, or a k < 1."""
+    from . import ops
+    n_rep, level = check_bootstrap(n_rep, level)
+    ks = sorted({int(k) for k in ks})
+    if not ks or ks[0] < 1:
+        raise ValueError("bootstrap_metrics: at least one k >= 1 (got %r)" % (ks,))
+    systems = list(ranks_by_system)
+    if not systems:
+        raise ValueError("bootstrap_metrics: at least one system")
+    ranks = [ranks_by_system[s] for s in systems]
+    n_units = int(n_units)
+    n_t = int(np.asarray(_host(target_row)).size) if not isinstance(target_row, torch.Tensor) else int(target_row.numel())
+    if any(int(r.numel() if isinstance(r, torch.Tensor) else np.asarray(r).size) != n_t for r in ranks):
+        raise ValueError("bootstrap_metrics: every system must rank the same %d targets" % n_t)
+    if unit_key is not None and int(np.asarray(_host(unit_key)).size) != n_units:
+        raise ValueError("bootstrap_metrics: unit_key must hold one key per unit")
+    dev = next((r.device for r in ranks if isinstance(r, torch.Tensor)), torch.device(device))
+    if n_rows is None:
+        n_rows = max([1] + [int(torch.as_tensor(r).max()) + 1 for r in ranks if n_t])
+    tables, names, scales = rank_gain_tables(ks, n_rows)
+    if n_t:
+        rk = torch.stack([torch.as_tensor(_host(r) if not isinstance(r, torch.Tensor) else r, device=dev)
+                          .reshape(-1).to(torch.int32) for r in ranks])
+        rows = ops.rank_gain_rows(rk, torch.as_tensor(_host(target_row) if not isinstance(target_row, torch.Tensor)
+                                                      else target_row, device=dev).reshape(-1).to(torch.int32),
+                                  n_units, torch.as_tensor(tables.astype(np.int64), device=dev))
+        key = np.arange(n_units, dtype=np.int64) if unit_key is None else np.asarray(_host(unit_key)).reshape(-1)
+        key = torch.as_tensor((key.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32), device=dev)
+        sums = _host(ops.boot_sums(rows, key, seed, n_rep, POISSON1_THRESHOLDS))
+    else:
+        sums = np.zeros((n_rep + 1, len(systems) * len(names) + 1), np.int64)
+    f = bootstrap_figures(sums, scales, level)
+    out = {"metrics": names, "systems": systems, "n": int(sums[0, -1]), "n_units": n_units, "n_rep": n_rep,
+           "n_rep_used": f["n_rep_used"], "level": level, "seed": int(seed), "figures": {}, "diffs": {}}
+    for i, s in enumerate(systems):
+        out["figures"][s] = {m: {k: float(f[k][i, j]) for k in ("value", "se", "lo", "hi")} for j, m in enumerate(names)}
+        if i:
+            out["diffs"][s] = {m: {"diff": float(f["diff"][i - 1, j]), "lo": float(f["diff_lo"][i - 1, j]),
+                                   "hi": float(f["diff_hi"][i - 1, j]), "p": float(f["p"][i - 1, j])}
+                               for j, m in enumerate(names)}
+    return out

@@ -6,7 +6,9 @@ rank are written to ``eval_csv``; ``--baseline popularity`` adds the same figure
 read the model's against, ``--baseline itemknn`` those of an item-kNN over co-occurrence counts fitted on the training
 slice alone (``popularity,itemknn``: both; the ``--itemknn_*`` flags of the command line tune it);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
-spread, over every held-out user's top ``lists_k`` list.  The reference has no such step:
+spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
+held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
+second model as one of those systems (command line only, like the ``--itemknn_*`` flags).  The reference has no such step:
 its author lists comparing re-trained models as an idea for improvement; ``val_loss`` cannot compare models across
 losses and activations, these figures can."""
 import json
@@ -38,6 +40,16 @@ ITEMKNN_FLAGS = {
     "itemknn_min_rating": (float, 0.0, "the scaled rating (0..1) from which a training rating counts as liked"),
 }
 
+# optional and command-line only, like the item-kNN flags: confidence intervals and a second model to compare with
+CI_FLAGS = {
+    "ci_replicates": (int, 0, "bootstrap replicates over the held-out users (0: no intervals): every figure gains a "
+                              "percentile interval, every other system a paired difference and a p-value"),
+    "ci_level": (float, 0.95, "the level of those intervals"),
+    "ci_seed": (int, 0, "the seed of the bootstrap weights"),
+    "compare_model": (str, "none", "none, or a second model artifact (of model_type, over the same id tables): ranked on "
+                                   "the same targets and reported as the system compare"),
+}
+
 logger = C.setup_logging("evaluate")
 
 
@@ -56,10 +68,16 @@ def go(args):
     from anime_recommendations_amd import ingest            # (torch: after the cheap failures)
     table = ingest.load_user_stats(artifacts.use_artifact(args.input_data, args.main_df_type))
     logger.info("Final df shape is (%d, 3); %d users, %d anime", len(table), table.n_users, table.n_anime)
+    ci = {f: getattr(args, f, CI_FLAGS[f][1]) for f in ("ci_replicates", "ci_level", "ci_seed")}
+    compare = str(getattr(args, "compare_model", "none"))
+    compare_model = None
+    if compare.lower() != "none":
+        compare_model = weights_io.load_model(artifacts.use_artifact(compare, args.model_type), args.ID_emb_name,
+                                              args.anime_emb_name)
     frame, summary = C.evaluate_frame(model, table, int(args.test_size), C.literal(args.eval_k),
                                       float(args.min_rating), baseline=baseline_arg(args.baseline),
                                       itemknn={f[len("itemknn_"):]: getattr(args, f) for f in ITEMKNN_FLAGS
-                                               if hasattr(args, f)})
+                                               if hasattr(args, f)}, compare_model=compare_model, **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -68,7 +86,7 @@ def go(args):
     if args.lists_diversity.lower() != "none":
         lists, lists_summary = C.evaluate_lists_frame(model, table, int(args.test_size), float(args.min_rating),
                                                       C.literal(args.lists_diversity), int(args.lists_k),
-                                                      int(args.lists_pool))
+                                                      int(args.lists_pool), **ci)
         lists.to_csv(args.lists_csv, index=False)
         artifacts.log_artifact(args.lists_csv, args.lists_csv, args.eval_type,
                                "Hits and spread of the top-%d lists per diversity for model : %s"
@@ -92,9 +110,10 @@ def make_parser():
 
 
 def make_cli_parser():
-    """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*`` flags."""
+    """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--ci_*`` and
+    ``--compare_model`` flags."""
     parser = make_parser()
-    for flag, (kind, default, text) in ITEMKNN_FLAGS.items():
+    for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(CI_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

@@ -1051,6 +1051,59 @@ int anirec_itemknn_scores(const int32_t *nbr_idx, const float *nbr_sim, int32_t 
                           int32_t n_hist, float *out_scores, int32_t *err_flag, void *ws, size_t ws_bytes,
                           void *stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Ranks to metric sums, and a Poisson bootstrap over users on them.  Integer sums throughout: no
+ *  result depends on the order the rows are met in.
+ *  The statistic: the resampling UNIT is the user (a user's held-out ratings are not independent, so a replicate
+ *  re-weights whole users); replicate b >= 1 gives unit u an integer weight w(b, u), independent over (b, u) and
+ *  Poisson(1) under the Poisson threshold table, drawn from a counter-based hash and never stored; replicate 0 is the
+ *  sample itself (all weights 1).  A metric is a mean over targets of a gain that depends on the target's rank alone,
+ *  held as a uint32 fixed-point table over ranks (rint(gain * 2^30); the mean rank: the rank at scale 1); replicate b's
+ *  figure is sum_b[column] / (scale * sum_b[count]) in fp64 on the host.
+ *
+ * anirec_rank_gain_rows: ranks int32 [n_sys][n_t] (system s ranks target t at ranks[s][t]), target_unit int32 [n_t]
+ * (the target's position in the unit list), gain uint32 [n_metric][n_gain] (a metric's fixed-point gain per rank).
+ * out int64 [n_units][n_sys * n_metric + 1]: column s * n_metric + m is the sum over the unit's targets of
+ * gain[m][ranks[s][t]], a rank < 0 or >= n_gain gaining 0 (a missed list slot's -1 needs no special case); the last
+ * column is the unit's number of targets.  The call zeroes out itself.  *err_flag (device; overwritten) becomes 1 for
+ * a target_unit outside [0, n_units): that target is dropped, nothing is read or written through it, the others are
+ * unaffected.  A thread adds up a run of consecutive targets of one unit before it issues an atomic, so a unit with
+ * many targets does not serialise the call.  n_sys, n_metric or n_gain < 1, a negative count, n_sys * n_metric + 1 >
+ * 4096, a NULL err_flag, a NULL or misaligned (8 bytes) out with n_units > 0, or a NULL ranks, target_unit or gain
+ * with n_t > 0: ANIREC_EINVAL before anything is enqueued or written.  Graph-capturable.
+ *
+ * anirec_boot_sums: values int64 [n_units][n_col] (anirec_rank_gain_rows' out, or any non-negative sums), unit_key
+ * int32 [n_units].  out int64 [n_rep + 1][n_col]: out[b][c] = sum over u of w(b, unit_key[u]) * values[u][c], with
+ *     mix32(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16      (uint32, mod 2^32)
+ *     r = mix32( mix32(seed + 0x9e3779b9 * b) ^ mix32((uint32_t)key + 0x85ebca6b) )
+ *     w(b, key) = #{ j < n_thr : r >= thr[j] }  for b >= 1;   w(0, key) = 1      (row 0 is the plain column sums)
+ * thr: a HOST table of n_thr <= 16 ascending uint32, passed to the kernel by value (floor(2^32 CDF(j)) of a
+ * distribution on 0, 1, 2, ... draws from it; n_thr == 0 gives all-zero weights).  The weight depends on the key, not
+ * on the unit's position: a subset of the units gets the same weights in a call of its own, so the sums of two calls
+ * over a split of the units add up to the whole call's, bit for bit.  Exactness guard: limit = 2^62 / (max(n_thr, 1) *
+ * n_units); a value < 0 or >= limit sets *err_flag (device; overwritten) and every element of out is -1, so nothing
+ * overflows silently.  n_units == 0 writes zeros.  ws: anirec_boot_workspace_bytes(n_units, n_col, n_rep) bytes (0 for a
+ * bad argument; the unit splits' partial rows), 8-byte aligned, less is ANIREC_EWORKSPACE; the result does not depend
+ * on what it held.  One lane is one replicate; a workgroup stages anirec_boot_tile() units in LDS and keeps
+ * anirec_boot_col_tile(n_col) column sums per lane in registers, wider inputs go over a grid dimension.
+ * n_units < 0, n_col outside 1 .. 4096, n_rep outside 0 .. 65536, n_thr outside 0 .. 16, a thr that decreases, a NULL
+ * out or err_flag, a NULL values, unit_key or ws with n_units > 0, values, out or ws not 8-byte aligned: ANIREC_EINVAL
+ * before anything is enqueued or written.  No atomics; graph-capturable.
+ *
+ * anirec_boot_weights: the weights themselves, out uint8 [n_rep][n_units], row b - 1 = replicate b = 1 .. n_rep, for
+ * figures that are no sums (a median, a coverage) and for small cases.  The same argument rules. */
+size_t anirec_boot_tile(void);
+size_t anirec_boot_col_tile(int32_t n_col);
+size_t anirec_boot_workspace_bytes(int32_t n_units, int32_t n_col, int32_t n_rep);
+int anirec_rank_gain_rows(const int32_t *ranks, int32_t n_sys, int32_t n_t, const int32_t *target_unit, int32_t n_units,
+                          const uint32_t *gain, int32_t n_metric, int32_t n_gain, int64_t *out, int32_t *err_flag,
+                          void *stream);
+int anirec_boot_sums(const int64_t *values, const int32_t *unit_key, int32_t n_units, int32_t n_col, uint32_t seed,
+                     int32_t n_rep, const uint32_t *thr, int32_t n_thr, int64_t *out, int32_t *err_flag, void *ws,
+                     size_t ws_bytes, void *stream);
+int anirec_boot_weights(const int32_t *unit_key, int32_t n_units, uint32_t seed, int32_t n_rep, const uint32_t *thr,
+                        int32_t n_thr, uint8_t *out, void *stream);
+
 /* The same top-k on the matrix cores (the batched model_recs path: 100 k users x 18 k anime):
  * fp16 MFMA cosine candidates with a rigorous error window, the watched mask applied when a
  * candidate is appended, exact fp32 re-rank through the head.  Same results as
