@@ -16,7 +16,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["main_df_type", "anime_df_type", "sypnopsis_df_type", "project_name", "main_df", "sypnopses_df", "anime_df",
              "anime_query", "a_query_number", "anime_rec_genres", "types", "a_rec_type"]
@@ -90,9 +90,4 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = make_parser().parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./also_liked.log
-        logger.exception("also_liked failed")
-        raise
+    cli.run("also_liked", logger, go, make_parser())

@@ -365,6 +365,30 @@ def _blocked_bits(blocked):
     return bits
 
 
+def _filter_bits(anime_ids, anime_df, syn_df, types, genres):
+    """(meta, bits): the metadata by index and, as blocked-bit words (int32), the anime the Type / Genre filters (and a
+    missing all_anime.csv row) keep out of a list."""
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    return meta, _blocked_bits(~filter_mask(meta, anime_df, types, genres)).view(np.int32)
+
+
+def _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres, row=None):
+    """The candidate stage of the one-user lists (model_recs, explain_recs, diverse_recs, calibrated_recs):
+    (row, meta, bits, tU, tA, k) — the user's row of ``U`` (``row`` when the caller has looked it up), the metadata by
+    index, the blocked-bit words (int32) of the anime the user has rated or the filters refuse, the two tables on the
+    device and the clamped list length."""
+    import torch
+    if row is None:
+        pos = np.nonzero(np.asarray(user_ids) == int(user_id))[0]
+        if len(pos) == 0:
+            raise ValueError("user id %r has no embedding row" % (user_id,))
+        row = int(pos[0])
+    meta, bits = _filter_bits(anime_ids, anime_df, syn_df, types, genres)
+    bits = bits | _blocked_bits(~unwatched_mask(df, anime_ids, user_id)).view(np.int32)
+    tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
+    return row, meta, bits, tU, tA, _topk_count(n_recs, "model_num_recs", len(anime_ids))
+
+
 def _model_recs_rows(meta, idx, p):
     """The model_recs frame (model_recs.py:451-456) of one user's top-k: ``idx`` anime indices (-1 padded) with
     their predicted ratings ``p``, metadata from ``meta`` (metadata_by_index)."""
@@ -390,17 +414,9 @@ def model_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user
 def _model_recs_topk(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres):
     """model_recs_frame's list before it becomes a frame: (meta, idx, p, tA) — the metadata by index, the anime indices
     (-1 padded) with their predicted ratings on the host, and the anime table on the device."""
-    import torch
     from . import ops
-    pos = np.nonzero(np.asarray(user_ids) == int(user_id))[0]
-    if len(pos) == 0:
-        raise ValueError("user id %r has no embedding row" % (user_id,))
-    meta = metadata_by_index(anime_ids, anime_df, syn_df)
-    keep = unwatched_mask(df, anime_ids, user_id) & filter_mask(meta, anime_df, types, genres)
-    bits = _blocked_bits(~keep)
-    tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
-    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
-    idx, p = ops.predict_topk(tU, tA, head, [int(pos[0])], k, bits.view(np.int32))
+    row, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
+    idx, p = ops.predict_topk(tU, tA, head, [row], k, bits)
     return meta, idx.cpu().numpy()[0], p.cpu().numpy()[0], tA
 
 
@@ -576,24 +592,16 @@ def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
     to the rows above it, 0 for the first: the re-rank's own penalty (at diversity 0, where nothing is re-ranked and the
     rows are model_recs_frame's, the same quantity from the host's cosines) — and stats = {"mean_similarity": the mean
     pairwise cosine of the listed anime, "mean_similarity_topk": that of the plain top-k}."""
-    import torch
     from . import ops, recs
-    pos = np.nonzero(np.asarray(user_ids) == int(user_id))[0]
-    if len(pos) == 0:
-        raise ValueError("user id %r has no embedding row" % (user_id,))
-    meta = metadata_by_index(anime_ids, anime_df, syn_df)
-    keep = unwatched_mask(df, anime_ids, user_id) & filter_mask(meta, anime_df, types, genres)
-    bits = _blocked_bits(~keep).view(np.int32)
-    tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
-    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
-    idx, p, pen = recs.diverse_topk(tU, tA, head, [int(pos[0])], k, pool, diversity, bits)
+    row, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
+    idx, p, pen = recs.diverse_topk(tU, tA, head, [row], k, pool, diversity, bits)
     idx, p = idx.cpu().numpy()[0], p.cpu().numpy()[0]
     Wh = ops.rownorm(tA, device=tA.device)
     S = _list_cosines(Wh, idx)
     if pen is None:
         plain, pen = S, np.array([S[i, :i].max() if i else 0.0 for i in range(len(S))], np.float32)
     else:
-        plain = _list_cosines(Wh, ops.predict_topk(tU, tA, head, [int(pos[0])], k, bits)[0].cpu().numpy()[0])
+        plain = _list_cosines(Wh, ops.predict_topk(tU, tA, head, [row], k, bits)[0].cpu().numpy()[0])
         pen = pen.cpu().numpy()[0][idx >= 0]
     frame = _model_recs_rows(meta, idx, p)
     frame["Max_similarity"] = pen
@@ -621,18 +629,14 @@ def calibrated_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df,
     from . import ops, recs
     if column not in CALIBRATION_COLUMNS:
         raise ValueError("calibrated_recs: calibration_column %r is not one of %s" % (column, ", ".join(CALIBRATION_COLUMNS)))
-    u = user_index(user_ids, user_id)
-    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    u, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres,
+                                           row=user_index(user_ids, user_id))
     names, cat_bits = category_table(meta, column)
     n_cat = len(names)
     if n_cat < 1:
         raise ValueError("calibrated_recs: column %r holds no tokens to calibrate to" % (column,))
     fav = favourite_bits(df, user_ids, anime_ids, favorite_percentile)
     profile = recs.fave_profile(fav, cat_bits, n_cat, users=[u])
-    keep = unwatched_mask(df, anime_ids, user_id) & filter_mask(meta, anime_df, types, genres)
-    bits = _blocked_bits(~keep).view(np.int32)
-    tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
-    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
     idx, p, pen = recs.calibrated_topk(tU, tA, head, [u], k, pool, calibration, cat_bits, n_cat, profile, bits)
 
     def prefixes(row):
@@ -687,14 +691,13 @@ def group_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, memb
     if not members:
         raise ValueError("group_recs: the group has no members")
     users, offsets, member_row = recs.group_csr([members], user_ids)
-    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    meta, exclude = _filter_bits(anime_ids, anime_df, syn_df, types, genres)
     uid = np.asarray(user_ids)
     watched = np.concatenate([_blocked_bits(~unwatched_mask(df, anime_ids, uid[r])) for r in users])
-    exclude = _blocked_bits(~filter_mask(meta, anime_df, types, genres))
     tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
     k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
     idx, p, mp = ops.group_topk(tU, tA, head, users, offsets, member_row, k, mode=strategy, floor=floor,
-                                watched_bits=watched.view(np.int32), exclude_bits=exclude.view(np.int32),
+                                watched_bits=watched.view(np.int32), exclude_bits=exclude,
                                 member_ratings=True)
     idx, p, mp = idx.cpu().numpy()[0], p.cpu().numpy()[0], mp.cpu().numpy()
     frame = _model_recs_rows(meta, idx, p)
@@ -730,11 +733,10 @@ def new_user_recs_frame(model, new_df, anime_df, syn_df, user_id, n_recs, types=
                                     lr=recs.FOLD_LR if lr is None else float(lr))
     q = _folded_position(folded, user_id)
     anime_ids = np.asarray(model["anime_ids"])
-    meta = metadata_by_index(anime_ids, anime_df, syn_df)
-    bits = _blocked_bits(~filter_mask(meta, anime_df, types, genres))
+    meta, bits = _filter_bits(anime_ids, anime_df, syn_df, types, genres)
     n_a = len(anime_ids)
     dev = folded["rows"].device
-    watched = folded["watched"][q:q + 1] | torch.as_tensor(bits.view(np.int32), device=dev)
+    watched = folded["watched"][q:q + 1] | torch.as_tensor(bits, device=dev)
     tA = torch.as_tensor(np.ascontiguousarray(model["A"], np.float32), device=dev)
     k = _topk_count(n_recs, "model_num_recs", n_a)
     idx, p = ops.predict_topk(folded["rows"], tA, weights_io.model_head(model), [q], k, watched)

@@ -206,6 +206,28 @@ def popularity_scores(anime_idx, n_anime, n_users=None):
     return counts.to(torch.float32)
 
 
+def _pool_topk(fn, what, weight, U, A, head, users, k, pool, watched_bits, check, rerank):
+    """The skeleton of ``diverse_topk`` and ``calibrated_topk`` (``fn``; ``what`` names its ``weight``): the range
+    checks, weight 0 as ``ops.predict_topk(..., k)`` itself, ``pool`` clamped to the number of anime, ``check(pool, k,
+    weight)`` before any GPU work (k <= pool <= the kernel's list limit), the ``pool`` best by predicted rating, and
+    ``rerank(cand, p, k, weight)`` -> (idx, pool slot, rating, penalty).  Returns (idx, rating, penalty or None)."""
+    from . import ops
+    k, pool, weight = int(k), int(pool), float(weight)
+    if not 0.0 <= weight <= 1.0:
+        raise ValueError("%s: %s = %r must be in [0, 1]" % (fn, what, weight))
+    if k < 1:
+        raise ValueError("%s: k must be >= 1" % fn)
+    if pool < k:
+        raise ValueError("%s: pool = %d is smaller than k = %d" % (fn, pool, k))
+    if weight == 0.0:
+        return ops.predict_topk(U, A, head, users, k, watched_bits) + (None,)
+    pool = min(pool, int(A.shape[0]))
+    check(pool, k, weight)
+    cand, p = ops.predict_topk(U, A, head, users, pool, watched_bits)
+    idx, _, score, pen = rerank(cand, p, k, weight)
+    return idx, score, pen
+
+
 def diverse_topk(U, A, head, users, k, pool, diversity, watched_bits=None):
     """Diversified top-k per user: the ``pool`` best unwatched anime by predicted rating
     (``ops.predict_topk``), re-ranked greedily by ``ops.mmr_rerank`` on the normalised anime rows with
@@ -218,20 +240,9 @@ def diverse_topk(U, A, head, users, k, pool, diversity, watched_bits=None):
     Raises ValueError for ``diversity`` outside [0, 1], k < 1, pool < k, and, at diversity > 0, for k above the number of
     anime or a pool above anirec_mmr_max_cand(width)."""
     from . import ops
-    k, pool, diversity = int(k), int(pool), float(diversity)
-    if not 0.0 <= diversity <= 1.0:
-        raise ValueError("diverse_topk: diversity = %r must be in [0, 1]" % (diversity,))
-    if k < 1:
-        raise ValueError("diverse_topk: k must be >= 1")
-    if pool < k:
-        raise ValueError("diverse_topk: pool = %d is smaller than k = %d" % (pool, k))
-    if diversity == 0.0:
-        return ops.predict_topk(U, A, head, users, k, watched_bits) + (None,)
-    pool = min(pool, int(A.shape[0]))
-    ops.check_mmr(A.shape[1], pool, k, 1.0 - diversity)     # (k <= pool <= the kernel's list limit, before any GPU work)
-    cand, p = ops.predict_topk(U, A, head, users, pool, watched_bits)
-    idx, _, score, pen = ops.mmr_rerank(ops.rownorm(A, device=A.device), cand, p, k, 1.0 - diversity)
-    return idx, score, pen
+    return _pool_topk("diverse_topk", "diversity", diversity, U, A, head, users, k, pool, watched_bits,
+                      lambda pool, k, w: ops.check_mmr(A.shape[1], pool, k, 1.0 - w),
+                      lambda cand, p, k, w: ops.mmr_rerank(ops.rownorm(A, device=A.device), cand, p, k, 1.0 - w))
 
 
 def calibrated_topk(U, A, head, users, k, pool, calibration, cat_bits, n_cat, profile, watched_bits=None):
@@ -247,20 +258,9 @@ def calibrated_topk(U, A, head, users, k, pool, calibration, cat_bits, n_cat, pr
     Raises ValueError for ``calibration`` outside [0, 1], k < 1, pool < k, and, at calibration > 0, for k above the
     number of anime, a pool above anirec_calibrate_max_cand() or ``n_cat`` outside 1 .. 128."""
     from . import ops
-    k, pool, calibration = int(k), int(pool), float(calibration)
-    if not 0.0 <= calibration <= 1.0:
-        raise ValueError("calibrated_topk: calibration = %r must be in [0, 1]" % (calibration,))
-    if k < 1:
-        raise ValueError("calibrated_topk: k must be >= 1")
-    if pool < k:
-        raise ValueError("calibrated_topk: pool = %d is smaller than k = %d" % (pool, k))
-    if calibration == 0.0:
-        return ops.predict_topk(U, A, head, users, k, watched_bits) + (None,)
-    pool = min(pool, int(A.shape[0]))
-    ops.check_calibrate(n_cat, pool, k, calibration)      # (k <= pool <= the kernel's list limit, before any GPU work)
-    cand, p = ops.predict_topk(U, A, head, users, pool, watched_bits)
-    idx, _, score, pen = ops.calibrate_rerank(cat_bits, n_cat, cand, p, profile, k, calibration)
-    return idx, score, pen
+    return _pool_topk("calibrated_topk", "calibration", calibration, U, A, head, users, k, pool, watched_bits,
+                      lambda pool, k, w: ops.check_calibrate(n_cat, pool, k, w),
+                      lambda cand, p, k, w: ops.calibrate_rerank(cat_bits, n_cat, cand, p, profile, k, w))
 
 
 def list_calibration(lists, cat_bits, n_cat, profile):

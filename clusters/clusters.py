@@ -20,7 +20,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import _lib, artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import _lib, artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["main_df", "main_df_type", "project_name", "anime_df", "anime_df_type", "model", "model_type",
              "clusters_fn", "clusters_type"]
@@ -124,9 +124,4 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = make_parser().parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./clusters.log
-        logger.exception("clusters failed")
-        raise
+    cli.run("clusters", logger, go, make_parser())

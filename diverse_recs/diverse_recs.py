@@ -9,79 +9,38 @@ model_recs' own list.  Writes ``User_ID_<id>_diverse_<model_recs_fn>``: the mode
 ``Max_similarity``; the artifact's metadata carries diversity, pool and the mean pairwise cosine of the list and of
 the plain top-k."""
 import os
-import random
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import cli, components as C  # noqa: E402
+from anime_recommendations_amd.cli import (MODEL_RECS_BOOL_FLAGS as BOOL_FLAGS,  # noqa: E402
+                                           MODEL_RECS_STR_FLAGS as STR_FLAGS, select_user)
 
-# the model_recs flag set, as it is
-STR_FLAGS = ["main_df", "main_df_type", "project_name", "anime_df", "anime_df_type", "sypnopsis_df",
-             "sypnopsis_df_type", "model", "model_type", "model_user_query", "model_recs_fn", "model_num_recs",
-             "anime_types", "model_genres", "model_recs_type", "flow_ID", "flow_ID_type"]
-BOOL_FLAGS = ["random_user", "save_model_recs", "specify_types", "specify_genres", "model_ID_flow", "model_ID_conf"]
 OPTIONAL_FLAGS = {"diversity": 0.3, "pool": 100}
 
 logger = C.setup_logging("diverse_recs")
 
 
-def unit_float(v):
-    x = float(v)
-    if not 0.0 <= x <= 1.0:
-        raise ValueError("%r is not in [0, 1]" % (v,))
-    return x
-
-
 def make_parser():
     p = C.make_parser("Get diversified anime recommendations from the ranking model", STR_FLAGS, BOOL_FLAGS)
-    p.add_argument("--diversity", type=unit_float, default=OPTIONAL_FLAGS["diversity"])
+    p.add_argument("--diversity", type=cli.unit_float, default=OPTIONAL_FLAGS["diversity"])
     p.add_argument("--pool", type=int, default=OPTIONAL_FLAGS["pool"])
     return p
 
 
-def select_user(args, df):
-    """select_user (model_recs.py:334-370), as the model_recs component has it: the user of the MLflow run (flow_ID
-    artifact), the configured one, or a random one."""
-    import pandas as pd
-    if args.model_ID_flow:
-        flow = pd.read_csv(artifacts.use_artifact(args.flow_ID, args.flow_ID_type))
-        return int(flow["User_ID"].values[0])
-    if args.model_ID_conf:
-        return int(args.model_user_query)
-    return int(random.choice(df["user_id"].unique().tolist()))
-
-
 def go(args):
-    import pandas as pd
-    from anime_recommendations_amd import weights_io
-    df = pd.read_parquet(artifacts.use_artifact(args.main_df, args.main_df_type))
-    anime_df = C.load_anime_df(artifacts.use_artifact(args.anime_df, args.anime_df_type))
-    syn_df = C.load_synopses(artifacts.use_artifact(args.sypnopsis_df, args.sypnopsis_df_type))
-    model = weights_io.load_model(artifacts.use_artifact(args.model, args.model_type))
-    user_ids, anime_ids = C.index_tables(model, df)
-    user = select_user(args, df)
+    inp = cli.load_inputs(args)
+    user = select_user(args, inp.df)
     logger.info("Using %s as input user; diversity %s, pool %d", user, args.diversity, args.pool)
-    frame, stats = C.diverse_recs_frame(model["U"], model["A"], weights_io.model_head(model), user_ids, anime_ids, df,
-                                        anime_df, syn_df, user, int(args.model_num_recs),
-                                        types=C.literal(args.anime_types) if args.specify_types else None,
-                                        genres=C.literal(args.model_genres) if args.specify_genres else None,
+    frame, stats = C.diverse_recs_frame(*inp.tables, user, int(args.model_num_recs), **cli.filters(args),
                                         pool=args.pool, diversity=args.diversity)
     fn = "User_ID_" + str(user) + "_diverse_" + args.model_recs_fn
-    frame.to_csv(fn, index=False)
-    artifacts.log_artifact("diverse_" + args.model_recs_fn, fn, args.model_recs_type,
-                           "Diversified anime recs based on model rankings for user : " + str(user),
-                           metadata={"Queried user: ": user, "Filename": fn, "diversity": args.diversity,
-                                     "pool": args.pool, **stats})
-    if not args.save_model_recs:
-        os.remove(fn)
-    return frame
+    return cli.write_recs(args, frame, fn, "diverse_" + args.model_recs_fn,
+                          "Diversified anime recs based on model rankings for user : " + str(user),
+                          {"Queried user: ": user, "Filename": fn, "diversity": args.diversity, "pool": args.pool,
+                           **stats})
 
 
 if __name__ == "__main__":
-    _args = make_parser().parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./diverse_recs.log
-        logger.exception("diverse_recs failed")
-        raise
+    cli.run("diverse_recs", logger, go, make_parser())

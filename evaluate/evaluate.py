@@ -17,7 +17,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["input_data", "main_df_type", "model", "model_type", "project_name", "test_size", "eval_k", "min_rating",
              "eval_csv", "eval_type", "ID_emb_name", "anime_emb_name"]
@@ -119,9 +119,4 @@ def make_cli_parser():
 
 
 if __name__ == "__main__":
-    _args = make_cli_parser().parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./evaluate.log
-        logger.exception("evaluate failed")
-        raise
+    cli.run("evaluate", logger, go, make_cli_parser())

@@ -15,7 +15,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["test_size", "embedding_size", "kernel_initializer", "activation_function", "model_loss",
              "optimizer", "start_lr", "min_lr", "max_lr", "batch_size", "rampup_epochs", "sustain_epochs",
@@ -143,9 +143,5 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = C.make_parser("Train an anime recommendation neural network", STR_FLAGS, BOOL_FLAGS).parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./neural_network.log
-        logger.exception("neural_network failed")
-        raise
+    cli.run("neural_network", logger, go,
+            C.make_parser("Train an anime recommendation neural network", STR_FLAGS, BOOL_FLAGS))

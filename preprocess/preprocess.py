@@ -8,7 +8,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["raw_stats", "project_name", "preprocessed_stats", "preprocessed_artifact_type",
              "preprocessed_artifact_description", "num_reviews"]
@@ -46,9 +46,4 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = C.make_parser("Preprocess a dataset", STR_FLAGS, BOOL_FLAGS).parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./preprocess.log
-        logger.exception("preprocess failed")
-        raise
+    cli.run("preprocess", logger, go, C.make_parser("Preprocess a dataset", STR_FLAGS, BOOL_FLAGS))

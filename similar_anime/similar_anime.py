@@ -9,7 +9,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["main_df_type", "anime_df_type", "sypnopsis_df_type", "model_type", "model", "project_name",
              "main_df", "sypnopses_df", "anime_df", "anime_query", "a_query_number", "anime_rec_genres",
@@ -49,9 +49,5 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = C.make_parser("Get recommendations based on similar anime", STR_FLAGS, BOOL_FLAGS).parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./similar_anime.log
-        logger.exception("similar_anime failed")
-        raise
+    cli.run("similar_anime", logger, go,
+            C.make_parser("Get recommendations based on similar anime", STR_FLAGS, BOOL_FLAGS))

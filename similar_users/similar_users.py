@@ -8,7 +8,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["anime_df", "anime_df_type", "model", "model_type", "project_name", "main_df", "main_df_type",
              "sim_user_query", "id_query_number", "max_ratings", "num_faves", "sim_users_fn", "sim_users_type",
@@ -50,9 +50,4 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = C.make_parser("Find the users most similar to a user", STR_FLAGS, BOOL_FLAGS).parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./similar_users.log
-        logger.exception("similar_users failed")
-        raise
+    cli.run("similar_users", logger, go, C.make_parser("Find the users most similar to a user", STR_FLAGS, BOOL_FLAGS))

@@ -4,7 +4,6 @@ host logic of ``recs.bootstrap_metrics`` / ``components.evaluate_frame`` / ``eva
 the restatement, the flag surface and the binding.  The kernels themselves are held to the restatement in
 test_boot_gpu.py."""
 import ctypes
-import importlib.util
 import math
 import os
 import re
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 import boot_restatement as R
+from component_cli import load_component
 from test_cooc_cpu import _model, _table, host_ops  # noqa: F401  (the other ops as their restatements)
 
 from anime_recommendations_amd import _lib, build, components as C, ops, recs
@@ -362,16 +362,9 @@ def test_evaluate_lists_frame_host_logic(boot_ops, monkeypatch):
 
 
 # ---- the flag surface and the binding ---------------------------------------------------------------------------------
-def _load(path, name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, *path))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_the_ci_flags_are_command_line_only():
     import yaml
-    mod = _load(("evaluate", "evaluate.py"), "evaluate_cli_boot")
+    mod = load_component("evaluate")
     assert {f: v[1] for f, v in mod.CI_FLAGS.items()} == {"ci_replicates": 0, "ci_level": 0.95, "ci_seed": 0,
                                                          "compare_model": "none"}
     argv = []

@@ -3,7 +3,6 @@
 ops.calibrate_rerank / ops.list_calibration / recs.calibrated_topk / anirec_calibrate_rerank / anirec_list_calibration
 (none needs a device), the binding, and the calibrated_recs component's flag surface."""
 import ctypes
-import importlib.util
 import os
 from fractions import Fraction
 
@@ -12,6 +11,7 @@ import pytest
 import torch
 
 import calibrate_restatement as R
+from component_cli import load_component
 from anime_recommendations_amd import _lib, build, ops, recs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -271,12 +271,7 @@ def test_new_symbols_bound_and_entry_point_checks_need_no_gpu():
 
 
 def test_calibrated_recs_parser_and_mlproject_agree():
-    def load(comp):
-        spec = importlib.util.spec_from_file_location(comp + "_cli", os.path.join(ROOT, comp, comp + ".py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-    mod, ref = load("calibrated_recs"), load("model_recs")
+    mod, ref = load_component("calibrated_recs"), load_component("model_recs")
     assert mod.STR_FLAGS == ref.STR_FLAGS and mod.BOOL_FLAGS == ref.BOOL_FLAGS       # the model_recs flag set as it is
     defaults = {"calibration": 0.5, "pool": 100, "calibration_column": "Genres", "favorite_percentile": 80}
     assert mod.OPTIONAL_FLAGS == defaults

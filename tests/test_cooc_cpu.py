@@ -2,7 +2,6 @@
 and the entry points' refusals (no device needed), and the host logic of recs / components with ``ops`` replaced by the
 restatement."""
 import ctypes
-import importlib.util
 import math
 import os
 import re
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import cooc_restatement as R
+from component_cli import load_component
 
 from anime_recommendations_amd import _lib, build, components as C, data, ops, recs
 
@@ -500,16 +500,9 @@ def test_evaluate_frame_itemknn_host_logic(host_ops):
 
 
 # ---- the components' flag surfaces ---------------------------------------------------------------------------------
-def _load(path, name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, *path))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_also_liked_parser_and_mlproject_agree():
-    mod = _load(("also_liked", "also_liked.py"), "also_liked_cli")
-    sim = _load(("similar_anime", "similar_anime.py"), "similar_anime_cli")
+    mod = load_component("also_liked")
+    sim = load_component("similar_anime")
     model_flags = {"model_type", "model", "ID_emb_name", "anime_emb_name"}
     assert mod.STR_FLAGS == [f for f in sim.STR_FLAGS if f not in model_flags] and mod.BOOL_FLAGS == sim.BOOL_FLAGS
     assert mod.OPTIONAL_FLAGS == {"liked_min_rating": 0.0, "cooc_measure": "cosine", "cooc_shrink": 0.0,
@@ -548,7 +541,7 @@ def test_also_liked_parser_and_mlproject_agree():
 
 
 def test_evaluate_baseline_flag_takes_names_and_lists():
-    mod = _load(("evaluate", "evaluate.py"), "evaluate_cli_cooc")
+    mod = load_component("evaluate")
     assert mod.baseline_arg("none") is None and mod.baseline_arg(" None ") is None and mod.baseline_arg("") is None
     assert mod.baseline_arg("popularity") == ["popularity"] and mod.baseline_arg("ItemKNN") == ["itemknn"]
     assert mod.baseline_arg("popularity, itemknn") == ["popularity", "itemknn"]

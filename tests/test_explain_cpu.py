@@ -1,13 +1,13 @@
 """CPU tests of the explained lists: the restatement's own rules on hand-built cases, the binding and the entry point's
 refusals (no device needed), recs.history_csr, the ops checks and the explain_recs component's flag surface."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
 import explain_restatement as E
+from component_cli import load_component
 
 from anime_recommendations_amd import _lib, build, ops, recs
 
@@ -174,13 +174,8 @@ def test_ops_refusals_need_no_gpu():
 
 # ---- the component's flag surface -------------------------------------------------------------------------------
 def test_explain_recs_parser_and_mlproject_agree():
-    def load(comp):
-        spec = importlib.util.spec_from_file_location(comp + "_cli", os.path.join(ROOT, comp, comp + ".py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
     from anime_recommendations_amd import components as C
-    mod, ref = load("explain_recs"), load("model_recs")
+    mod, ref = load_component("explain_recs"), load_component("model_recs")
     assert mod.STR_FLAGS == ref.STR_FLAGS and mod.BOOL_FLAGS == ref.BOOL_FLAGS       # the model_recs flag set as it is
     assert mod.OPTIONAL_FLAGS == {"explain_count": 3, "explain_weight": "rating", "explain_min_rating": 0.0}
     assert C.EXPLAIN_WEIGHTS == recs.EXPLAIN_WEIGHTS == ("rating", "similarity") and C.EXPLAIN_MAX_COUNT == _lib.EXPLAIN_MAX_M

@@ -3,7 +3,6 @@ float32 restatement's distance from the float64 one on the GPU tests' inputs (th
 the host half of recs.fold_in_users, the new symbols in the header and the binding, the entry point's checks that
 need no device, and the new_user_recs component's flag surface."""
 import ctypes
-import importlib.util
 import os
 import re
 
@@ -14,6 +13,7 @@ import torch
 
 import foldin_cases as K
 import foldin_restatement as F
+from component_cli import load_component
 from anime_recommendations_amd import _lib, build, components as C, recs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -190,12 +190,7 @@ def test_fold_in_entry_point_checks_need_no_gpu():
 
 
 def test_new_user_recs_parser_and_mlproject_agree():
-    spec = importlib.util.spec_from_file_location("new_user_recs_cli", os.path.join(ROOT, "new_user_recs", "new_user_recs.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    spec = importlib.util.spec_from_file_location("model_recs_cli", os.path.join(ROOT, "model_recs", "model_recs.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    mod, ref = load_component("new_user_recs"), load_component("model_recs")
     extra = ["new_ratings", "fold_steps", "fold_lr", "fold_neighbours"]
     want = ref.STR_FLAGS + ref.BOOL_FLAGS + extra                 # the model_recs flags plus the fold-in ones
     assert sorted(mod.STR_FLAGS + mod.BOOL_FLAGS) == sorted(want) and mod.OPTIONAL_FLAGS == ["user_query"]

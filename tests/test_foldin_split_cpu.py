@@ -3,7 +3,6 @@ restatement's distance from the float64 one on the GPU tests' inputs (the figure
 chunk-map builder, the host half of recs.fold_in_anime, recs.append_anime, the new symbols in the header and the
 binding, the entry point's checks that need no device, and the component's flag surface."""
 import ctypes
-import importlib.util
 import os
 import re
 
@@ -13,6 +12,7 @@ import pytest
 
 import foldin_cases as K
 import foldin_split_cases as S
+from component_cli import load_component
 from anime_recommendations_amd import _lib, build, ops, recs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,12 +172,7 @@ def test_split_entry_point_checks_need_no_gpu():
 
 
 def test_new_anime_parser_and_mlproject_agree():
-    def load(comp):
-        spec = importlib.util.spec_from_file_location(comp + "_cli", os.path.join(ROOT, comp, comp + ".py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-    mod, ref = load("new_anime"), load("similar_anime")
+    mod, ref = load_component("new_anime"), load_component("similar_anime")
     extra = ["new_ratings", "fold_steps", "fold_lr", "audience_number"]
     # the similar_anime flags plus the fold-in ones; --anime_query stays a flag, now an optional id of the file
     assert sorted(mod.STR_FLAGS + mod.BOOL_FLAGS + ["anime_query"]) == sorted(ref.STR_FLAGS + ref.BOOL_FLAGS + extra)

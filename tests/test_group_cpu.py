@@ -1,13 +1,13 @@
 """CPU tests of group recommendations: the NumPy restatement checks itself, recs.group_csr, the size query and the
 argument checks of anirec_group_topk (none needs a device), the binding, and the group_recs component's flag surface."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
 import group_restatement as G
+from component_cli import load_component
 from rank_restatement import score_key
 
 from anime_recommendations_amd import _lib, build, ops, recs
@@ -176,13 +176,8 @@ def test_ops_refusals_need_no_gpu():
 
 # ---- the component's flag surface -------------------------------------------------------------------------------
 def test_group_recs_parser_and_mlproject_agree():
-    def load(comp):
-        spec = importlib.util.spec_from_file_location(comp + "_cli", os.path.join(ROOT, comp, comp + ".py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
     from anime_recommendations_amd import components as C
-    mod, ref = load("group_recs"), load("model_recs")
+    mod, ref = load_component("group_recs"), load_component("model_recs")
     assert mod.STR_FLAGS == ref.STR_FLAGS and mod.BOOL_FLAGS == ref.BOOL_FLAGS       # the model_recs flag set as it is
     assert mod.OPTIONAL_FLAGS == {"group_users": "[]", "group_strategy": "mean", "group_floor": None}
     assert C.GROUP_STRATEGIES == ("mean", "least_misery", "most_pleasure")

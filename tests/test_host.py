@@ -1,7 +1,6 @@
 """CPU tests of the host side: index contract, artifact store, model container, component
 flag surface (against the reference's flag lists), filters, and the epoch driver
 (LearningRateScheduler / ModelCheckpoint / EarlyStopping semantics) on a fake engine."""
-import importlib.util
 import json
 import os
 
@@ -11,6 +10,7 @@ import pytest
 
 from anime_recommendations_amd import artifacts, components as C, data, trainer, weights_io
 from oracle import anirec_oracle as orc
+from component_cli import load_component
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -166,9 +166,7 @@ def test_model_container_roundtrip(tmp_path):
 @pytest.mark.parametrize("comp", ["neural_network", "similar_anime", "similar_users", "model_recs", "preprocess"])
 def test_component_flag_surface_matches_reference(comp, golden_dir):
     ref = json.load(open(os.path.join(golden_dir, "component_flags.json")))[comp]
-    spec = importlib.util.spec_from_file_location(comp + "_cli", os.path.join(ROOT, comp, comp + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_component(comp)
     assert sorted(mod.STR_FLAGS + mod.BOOL_FLAGS) == sorted(ref["flags"])
     assert sorted(mod.BOOL_FLAGS) == sorted(ref["bool_flags"])
     # every flag is required, strings stay strings, booleans parse like strtobool

@@ -1,13 +1,13 @@
 """CPU tests of the clustered tables: the restatement's own rules on hand-built cases, the binding and the entry points'
 refusals (no device needed), the ops / recs checks and the clusters component's flag surface."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
 import kmeans_restatement as K
+from component_cli import load_component
 
 from anime_recommendations_amd import _lib, build, ops, recs
 
@@ -256,9 +256,7 @@ def test_cluster_rows_refusals_need_no_gpu():
 
 # ---- the component's flag surface -------------------------------------------------------------------------------
 def test_clusters_parser_and_mlproject_agree():
-    spec = importlib.util.spec_from_file_location("clusters_cli", os.path.join(ROOT, "clusters", "clusters.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_component("clusters")
     from anime_recommendations_amd import components as C
     assert mod.STR_FLAGS == ["main_df", "main_df_type", "project_name", "anime_df", "anime_df_type", "model", "model_type",
                              "clusters_fn", "clusters_type"] and mod.BOOL_FLAGS == ["save_clusters"]

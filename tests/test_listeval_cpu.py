@@ -3,7 +3,6 @@ against the properties its definition promises, recs.list_figures (list_quality 
 lists, the host-side argument checks of ops.list_similarity / recs.list_quality / components.evaluate_lists_frame /
 anirec_list_similarity (none needs a device), the binding, and the evaluate component's new flags."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
@@ -12,6 +11,7 @@ import torch
 
 import listeval_restatement as L
 import mmr_restatement as M
+from component_cli import load_component
 from anime_recommendations_amd import _lib, build, components as C, data, ops, recs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -260,9 +260,7 @@ def test_new_symbol_bound_and_entry_point_checks_need_no_gpu():
 
 
 def test_evaluate_parser_and_mlproject_agree_on_the_lists_flags():
-    spec = importlib.util.spec_from_file_location("evaluate_cli", os.path.join(ROOT, "evaluate", "evaluate.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_component("evaluate")
     want = {"lists_diversity": "none", "lists_k": 10, "lists_pool": 100, "lists_csv": "eval_lists.csv"}
     assert {f: v[1] for f, v in mod.OPTIONAL_FLAGS.items()} == want and len(mod.STR_FLAGS) == 12
     parser = mod.make_parser()

@@ -2,7 +2,6 @@
 against the properties its definition promises, the host-side argument checks of ops.mmr_rerank / recs.diverse_topk /
 anirec_mmr_rerank (none needs a device), the binding, and the diverse_recs component's flag surface."""
 import ctypes
-import importlib.util
 import os
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 import torch
 
 import mmr_restatement as M
+from component_cli import load_component
 from anime_recommendations_amd import _lib, build, ops, recs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -149,12 +149,7 @@ def test_new_symbols_bound_and_entry_point_checks_need_no_gpu():
 
 
 def test_diverse_recs_parser_and_mlproject_agree():
-    def load(comp):
-        spec = importlib.util.spec_from_file_location(comp + "_cli", os.path.join(ROOT, comp, comp + ".py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-    mod, ref = load("diverse_recs"), load("model_recs")
+    mod, ref = load_component("diverse_recs"), load_component("model_recs")
     assert mod.STR_FLAGS == ref.STR_FLAGS and mod.BOOL_FLAGS == ref.BOOL_FLAGS       # the model_recs flag set as it is
     assert mod.OPTIONAL_FLAGS == {"diversity": 0.3, "pool": 100}
     parser = mod.make_parser()

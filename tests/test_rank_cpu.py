@@ -2,7 +2,6 @@
 the rank definition (tests/rank_restatement.py) on hand-built ratings, the three new symbols in the header and the
 binding, the evaluate component's flag surface and evaluate_frame's id-table check."""
 import ctypes
-import importlib.util
 import math
 import os
 import re
@@ -11,6 +10,7 @@ import numpy as np
 import pytest
 
 import rank_restatement as R
+from component_cli import load_component
 from anime_recommendations_amd import _lib, build, components as C, data, recs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,9 +118,7 @@ def test_rank_entry_point_checks_need_no_gpu():
 
 
 def test_evaluate_parser_and_mlproject_agree():
-    spec = importlib.util.spec_from_file_location("evaluate_cli", os.path.join(ROOT, "evaluate", "evaluate.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_component("evaluate")
     want = ["input_data", "main_df_type", "model", "model_type", "project_name", "test_size", "eval_k", "min_rating",
             "eval_csv", "eval_type", "ID_emb_name", "anime_emb_name"]
     assert sorted(mod.STR_FLAGS + mod.BOOL_FLAGS) == sorted(want)

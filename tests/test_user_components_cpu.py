@@ -1,7 +1,6 @@
 """CPU tests of the user_prefs / user_recs components: flag surface, category tables and favourite profiles,
 and the counting of similar_user_recs, each held to the outputs of the reference's own function bodies
 (tests/golden/ref_fn/user_prefs.json, user_recs.json, written by make_user_component_fixtures.py)."""
-import importlib.util
 import json
 import os
 
@@ -10,6 +9,7 @@ import pandas as pd
 import pytest
 
 import prefs_restatement as R
+from component_cli import load_component
 from anime_recommendations_amd import components as C
 from oracle import recs_oracle
 
@@ -22,13 +22,6 @@ def _js(golden_dir, name):
 
 def _frame(d):
     return pd.DataFrame(d["rows"], columns=d["columns"], index=d["index"])
-
-
-def _module(comp):
-    spec = importlib.util.spec_from_file_location(comp + "_cli", os.path.join(ROOT, comp, comp + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def _indexed(d, pct):
@@ -45,7 +38,7 @@ def _indexed(d, pct):
 @pytest.mark.parametrize("comp", ["user_prefs", "user_recs"])
 def test_user_component_flag_surface_matches_reference(comp, golden_dir):
     ref = json.load(open(os.path.join(golden_dir, "user_component_flags.json")))[comp]
-    mod = _module(comp)
+    mod = load_component(comp)
     assert sorted(mod.STR_FLAGS + mod.BOOL_FLAGS) == sorted(ref["flags"])
     assert sorted(mod.BOOL_FLAGS) == sorted(ref["bool_flags"])
     assert len(ref["flags"]) == {"user_prefs": 22, "user_recs": 31}[comp]

@@ -7,7 +7,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["model", "main_df", "project_name", "anime_df", "prefs_user_query", "favorite_percentile", "genre_fn",
              "source_fn", "cloud_width", "cloud_height", "prefs_csv", "interval", "flow_user", "main_df_type",
@@ -70,9 +70,4 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = C.make_parser("Get user preferences", STR_FLAGS, BOOL_FLAGS).parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./user_prefs.log
-        logger.exception("user_prefs failed")
-        raise
+    cli.run("user_prefs", logger, go, C.make_parser("Get user preferences", STR_FLAGS, BOOL_FLAGS))

@@ -8,7 +8,7 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
-from anime_recommendations_amd import artifacts, components as C  # noqa: E402
+from anime_recommendations_amd import artifacts, cli, components as C  # noqa: E402
 
 STR_FLAGS = ["main_df", "project_name", "anime_df", "user_recs_query", "user_recs_fn", "sypnopses_df",
              "user_num_recs", "model", "ID_emb_name", "anime_emb_name", "main_df_type", "anime_df_type",
@@ -124,9 +124,4 @@ def go(args):
 
 
 if __name__ == "__main__":
-    _args = C.make_parser("Get user preferences", STR_FLAGS, BOOL_FLAGS).parse_args()
-    try:
-        go(_args)
-    except Exception:                      # non-zero exit + the reason in ./user_recs.log
-        logger.exception("user_recs failed")
-        raise
+    cli.run("user_recs", logger, go, C.make_parser("Get user preferences", STR_FLAGS, BOOL_FLAGS))
