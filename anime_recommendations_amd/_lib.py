@@ -32,6 +32,8 @@ EXPLAIN_TILE_FLOATS = 8192  # anirec_explain_tile(dim, k): dim * tile and k * (t
 KMEANS_MAX_K = 4096         # ANIREC_KMEANS_MAX_K: the most centroids anirec_kmeans_assign / anirec_kmeans_fit take
 KMEANS_MAX_ITER = 1000      # anirec_kmeans_fit: the most iterations one call enqueues
 KMEANS_IMAGE_FLOATS = 32768  # anirec_kmeans_tile(dim) = KMEANS_IMAGE_FLOATS // dim: the centroids of one LDS image
+ALS_MAX_CG = 16             # ANIREC_ALS_MAX_CG: the most conjugate-gradient steps of anirec_als_half_sweep
+ALS_GRAM_CHUNK = 1024       # ANIREC_ALS_GRAM_CHUNK: rows of one chunk of anirec_als_gram
 CALIBRATE_MAX_CAND = 1024   # anirec_calibrate_max_cand(): the longest list anirec_calibrate_rerank / _list_calibration take
 CALIBRATE_MAX_CAT = 128     # the most categories of a profile (anirec_fave_profile's limit)
 CALIBRATE_PROFILE_MAX = 1 << 24   # the largest profile entry: the integer numerator then stays below 2**53
@@ -280,6 +282,12 @@ PROTOTYPES = {
     "anirec_boot_sums": (C.c_int, [_vp, _vp, _i32, _i32, C.c_uint32, _i32, C.POINTER(C.c_uint32), _i32, _vp, _vp, _vp,
                                    _sz, _vp]),
     "anirec_boot_weights": (C.c_int, [_vp, _i32, C.c_uint32, _i32, C.POINTER(C.c_uint32), _i32, _vp, _vp]),
+    # implicit-feedback ALS: the Gram matrix of a table, one conjugate-gradient half-sweep, score rows from two tables
+    "anirec_als_gram_workspace_bytes": (_sz, [_i32, _i32]),
+    "anirec_als_gram": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "anirec_als_half_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _f32, _i32, _vp, _vp,
+                                        _vp]),
+    "anirec_dot_scores": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
 }
 
 

@@ -844,18 +844,23 @@ def _tables_of(model, table):
 
 BASELINES = ("popularity", "itemknn")
 ITEMKNN_DEFAULTS = {"neighbours": 50, "measure": "cosine", "shrink": 0.0, "min_support": 1, "min_rating": 0.0}
+# baselines that are fitted by optimisation on the training slice: reported after BASELINES.  ALS_DEFAULTS are the usual
+# library defaults with the width moved to the nearest supported one; they have not been tuned on this data.
+FITTED_BASELINES = ("als",)
+ALS_DEFAULTS = {"factors": 64, "sweeps": 15, "cg_steps": 3, "alpha": 1.0, "reg": 0.01, "min_rating": 0.0, "seed": 0}
 
 
 def baseline_names(baseline):
-    """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in BASELINES' order: None -> (), a name or a
-    sequence of names; ValueError for anything else."""
+    """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES then FITTED_BASELINES:
+    None -> (), a name or a sequence of names; ValueError for anything else."""
     if baseline is None:
         return ()
+    known = BASELINES + FITTED_BASELINES
     names = [baseline] if isinstance(baseline, str) else list(baseline)
     for b in names:
-        if b not in BASELINES:
-            raise ValueError("baseline %r is not supported (supported: %s, or None)" % (b, ", ".join(BASELINES)))
-    return tuple(b for b in BASELINES if b in names)
+        if b not in known:
+            raise ValueError("baseline %r is not supported (supported: %s, or None)" % (b, ", ".join(known)))
+    return tuple(b for b in known if b in names)
 
 
 def _ci_columns(columns, boot, system, others, key):
@@ -881,7 +886,7 @@ def _ci_columns(columns, boot, system, others, key):
 
 
 def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None,
-                   ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None):
+                   ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -895,7 +900,12 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     (``recs.itemknn_fit`` / ``recs.itemknn_rank``), each listed user's history that user's training
     ratings at or above the threshold with weight 1; the same columns and keys under the name itemknn.  ``itemknn``: a
     dict overriding ITEMKNN_DEFAULTS (neighbours, measure, shrink, min_support, min_rating).
-    A sequence of names gives both, popularity first.  None: neither.
+    ``baseline="als"``: the same targets under the same bits ranked by an implicit-feedback ALS factorisation fitted on
+    the TRAINING slice alone (``recs.als_fit`` / ``recs.als_rank``), on the training pairs rated at or
+    above its threshold, each with weight 1; the same columns and keys under the name als.  ``als``: a dict overriding
+    ALS_DEFAULTS (factors, sweeps, cg_steps, alpha, reg, min_rating, seed) — the usual library defaults, not tuned on this
+    data; a ``factors`` outside the supported widths is a ValueError before any GPU use.
+    A sequence of names gives each, in the order popularity, itemknn, als.  None: none.
     ``compare_model``: a second model dict over the same id tables, ranked by a second ``ops.predict_rank`` on the same
     targets and bits and reported as the system ``compare`` (the baselines' columns and keys under that name).
     ``ci_replicates`` > 0: a Poisson bootstrap over the held-out USERS (``recs.bootstrap_metrics``), seeded
@@ -914,6 +924,13 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         if key not in knn_par:
             raise ValueError("itemknn parameter %r is not one of %s" % (key, ", ".join(ITEMKNN_DEFAULTS)))
         knn_par[key] = v
+    als_par = dict(ALS_DEFAULTS)
+    for key, v in (als or {}).items():
+        if key not in als_par:
+            raise ValueError("als parameter %r is not one of %s" % (key, ", ".join(ALS_DEFAULTS)))
+        als_par[key] = v
+    if "als" in baselines:
+        ops.check_als(als_par["factors"], als_par["cg_steps"], als_par["reg"], als_par["alpha"])
     U, A = _tables_of(model, table)
     others = baselines + (("compare",) if compare_model is not None else ())
     if compare_model is not None:
@@ -941,6 +958,13 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
             off, hist, _ = recs.history_csr(table.user[train], table.anime[train], table.rating[train], users,
                                             min_rating=knn_par["min_rating"])
             base_rank["itemknn"] = recs.itemknn_rank(knn, off, hist, None, seen, row, anime)
+        if "als" in baselines:
+            tu, ta, tr = (recs._host(c[train]) for c in (table.user, table.anime, table.rating))
+            liked = tr.astype(np.float32) >= np.float32(als_par["min_rating"])
+            fit = recs.als_fit(tu[liked], ta[liked], table.n_users, table.n_anime,
+                               als_par["factors"], int(als_par["sweeps"]), als_par["cg_steps"], als_par["alpha"],
+                               als_par["reg"], seed=int(als_par["seed"]), device=seen.device)
+            base_rank["als"] = recs.als_rank(fit, users, seen, row, anime)
     else:
         rank = np.zeros(0, np.int32)
     m = recs.ranking_metrics(rank, ks)

@@ -683,6 +683,25 @@ int anirec_cosine_scores_w(const float *What, int32_t n, int32_t dim, int32_t q,
   return launch_scores(a, (hipStream_t)stream, ANIREC_ACT_SIGMOID, dim);
 }
 
+// the same kernels on two tables of rows that need not be normalised: one chain, one body
+int anirec_dot_scores(const float *Q, int32_t n_q, const float *Y, int32_t n, int32_t dim, float *out, int64_t ld,
+                      void *stream) {
+  if (n < 1 || n_q < 0 || n_q > 65535 * kTile || ld < n || !dim_ok(dim)) return ANIREC_EINVAL;
+  if (n_q == 0) return ANIREC_OK;
+  if (!Q || !Y || !out) return ANIREC_EINVAL;
+  ScoreArgs a;
+  a.Q = Q;
+  a.qrows = nullptr;
+  a.nq = n_q;
+  a.W = Y;
+  a.n = n;
+  a.out = out;
+  a.ld = (size_t)ld;
+  a.use_head = 0;
+  a.hs = a.hb = 0.f;
+  return launch_scores(a, (hipStream_t)stream, ANIREC_ACT_SIGMOID, dim);
+}
+
 int anirec_predict_pairs_act(const float *U, const float *A, const int32_t *user_idx,
                              const int32_t *anime_idx, int32_t n, const anirec_head *head, int32_t activation,
                              float *p, void *stream) {

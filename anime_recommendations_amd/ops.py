@@ -1204,6 +1204,108 @@ def boot_weights(unit_key, seed, n_rep, thr, device="cuda:0"):
     return out
 
 
+def check_als(factors, cg_steps, lam, alpha):
+    """The argument checks of the ALS ops (no device needed): ValueError listing the supported widths for another
+    ``factors``, for ``cg_steps`` outside 0 .. ALS_MAX_CG, a ``lam`` or ``alpha`` that is negative or not finite.  Returns
+    (factors, cg_steps, lam, alpha)."""
+    try:
+        factors = _lib.check_width(factors)
+    except ValueError:
+        raise ValueError("als: factors = %r is not supported: the kernels take the widths %s"
+                         % (factors, ", ".join(str(w) for w in _lib.WIDTHS))) from None
+    cg_steps, lam, alpha = int(cg_steps), float(lam), float(alpha)
+    if not 0 <= cg_steps <= _lib.ALS_MAX_CG:
+        raise ValueError("als: cg_steps = %d must be in 0 .. %d (ALS_MAX_CG)" % (cg_steps, _lib.ALS_MAX_CG))
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")):
+        raise ValueError("als: the regularisation and alpha must be finite and >= 0 (got %r, %r)" % (lam, alpha))
+    return factors, cg_steps, lam, alpha
+
+
+def als_gram(Y, workspace=None):
+    """``Y.T @ Y`` of a factor table (anirec_als_gram): ``Y`` fp32 [n, width] on the device.  Every
+    product is taken in fp64, where it is exact, and added in fp64 in a fixed order (chunks of ALS_GRAM_CHUNK rows in row
+    order, the chunks in chunk order); the sum is rounded once to fp32.  Returns fp32 [width, width]."""
+    _need_gpu()
+    lib = _lib.load()
+    dim = _width(Y)
+    Y = Y.contiguous()
+    n = int(Y.shape[0])
+    if n < 1:
+        raise ValueError("als_gram: Y has no rows")
+    G = torch.empty(dim, dim, dtype=torch.float32, device=Y.device)
+    if workspace is None:
+        workspace = torch.empty(int(lib.anirec_als_gram_workspace_bytes(n, dim)), dtype=torch.uint8, device=Y.device)
+    _lib.check(lib.anirec_als_gram(_lib.ptr(Y), n, dim, _lib.ptr(G), _lib.ptr(workspace), workspace.numel(), _stream()),
+               "anirec_als_gram")
+    return G
+
+
+def als_half_sweep(Y, G, offsets, idx, X, lam, cg_steps, excess=None, alpha=1.0, check=True):
+    """One ALS half-sweep (anirec_als_half_sweep): every row of ``X`` [n_rows, width] refitted by
+    ``cg_steps`` warm-started conjugate-gradient steps against the frozen table ``Y`` [n_other, width] and its Gram
+    matrix ``G`` (``als_gram``).  Row u likes the items ``idx[offsets[u]:offsets[u + 1]]`` with the confidence excess
+    ``excess`` (per entry, finite and >= 0) or ``alpha`` for every entry when ``excess`` is None; ``lam`` is the L2
+    weight.  Returns (rows fp32 [n_rows, width], row_loss fp32 [n_rows]); ``X`` is not modified.  A row without entries
+    becomes 0 with loss 0; ``cg_steps`` = 0 returns the rows bit for bit with their loss.  The rows are handed to the
+    workgroups by descending list length; a row's bits do not depend on that, nor on the other rows.  Raises ValueError
+    for an index out of range or offsets that are not a CSR of the lists (that row is NaN); with ``check=False`` returns
+    (rows, row_loss, device flag) and nothing synchronises beyond the offsets' own checks."""
+    dim, cg_steps, lam, alpha = check_als(Y.shape[1], cg_steps, lam, alpha)
+    _need_gpu()
+    lib = _lib.load()
+    assert _width(Y, G, X) == dim and G.shape[0] == dim
+    dev = Y.device
+    Y, G = Y.contiguous(), G.contiguous()
+    rows = X.contiguous().clone()
+    n_rows, n_other = int(rows.shape[0]), int(Y.shape[0])
+    off = torch.as_tensor(offsets).to(device=dev, dtype=torch.int64).contiguous()
+    ix = _i32(idx, dev).reshape(-1)
+    assert off.dim() == 1 and off.numel() == n_rows + 1, "offsets holds n_rows + 1 entries"
+    ex = None
+    if excess is not None:
+        ex = _f32(excess, dev).reshape(-1)
+        assert ex.shape == ix.shape
+        if ex.numel() and not bool((torch.isfinite(ex) & (ex >= 0)).all()):
+            raise ValueError("als_half_sweep: excess must be finite and >= 0")
+    loss = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n_rows:
+        # the offsets are checked against the entries here, so that the kernel reads no entry past the list's end
+        bad = (off[0] != 0) | (off[-1] != ix.numel()) | (off[1:] < off[:-1]).any()
+        if bool(bad):
+            raise ValueError("als_half_sweep: offsets must rise from 0 to the number of entries")
+        order = torch.argsort(off[1:] - off[:-1], descending=True, stable=True).to(torch.int32)
+        _lib.check(lib.anirec_als_half_sweep(_lib.ptr(Y), n_other, dim, _lib.ptr(G), _lib.ptr(off), _lib.ptr(ix),
+                                             _lib.ptr(ex), alpha, _lib.ptr(order), _lib.ptr(rows), n_rows, lam, cg_steps,
+                                             _lib.ptr(loss), _lib.ptr(err), _stream()), "anirec_als_half_sweep")
+    if not check:
+        return rows, loss, err
+    if int(err.item()):
+        raise ValueError("als_half_sweep: index out of range")
+    return rows, loss
+
+
+def dot_scores(Q, Y, out=None):
+    """Score rows from two factor tables (anirec_dot_scores): out[q, j] = the library's k-ordered fp32 fma chain over
+    ``Q[q]`` and ``Y[j]`` (``cosine_scores``' chain on rows that need not be normalised): what ``rows_topk`` and
+    ``rows_rank`` take.  ``Q`` [n_q, width], ``Y`` [n, width] on the device; ``out``: an fp32 [n_q, ld >= n] device
+    tensor to write the first n columns of, or None for a fresh [n_q, n].  Returns it."""
+    _need_gpu()
+    lib = _lib.load()
+    dim = _width(Q, Y)
+    Q, Y = Q.contiguous(), Y.contiguous()
+    n_q, n = int(Q.shape[0]), int(Y.shape[0])
+    if n < 1:
+        raise ValueError("dot_scores: Y has no rows")
+    if out is None:
+        out = torch.empty(n_q, n, dtype=torch.float32, device=Q.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous() and \
+        out.shape[0] == n_q and out.shape[1] >= n, "out: contiguous fp32 [n_q, ld >= n]"
+    _lib.check(lib.anirec_dot_scores(_lib.ptr(Q), n_q, _lib.ptr(Y), n, dim, _lib.ptr(out), int(out.shape[1]), _stream()),
+               "anirec_dot_scores")
+    return out
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

@@ -810,6 +810,127 @@ def itemknn_rank(knn, offsets, hist_idx, hist_w, watched_bits, target_row, targe
 
 
 # ----------------------------------------------------------------------------------------
+# implicit-feedback ALS: no model takes part
+# ----------------------------------------------------------------------------------------
+ALS_BATCH = 4096        # users per anirec_dot_scores call: a score row each
+
+
+def _als_csr(row, col, n_rows, excess):
+    """(offsets int64 [n_rows + 1], col int32, excess | None) on the device: a stable sort by ``row``, so a row's entries
+    keep the pairs' own order"""
+    order = torch.sort(row, stable=True)[1]
+    off = torch.zeros(n_rows + 1, dtype=torch.int64, device=row.device)
+    off[1:] = torch.cumsum(torch.bincount(row, minlength=n_rows), 0)
+    return off, col[order].to(torch.int32).contiguous(), None if excess is None else excess[order].contiguous()
+
+
+def als_fit(user_idx, item_idx, n_users, n_items, factors=64, sweeps=15, cg_steps=3, alpha=1.0, reg=0.01, weight=None,
+            seed=0, device="cuda:0"):
+    """Implicit-feedback matrix factorisation (Hu, Koren and Volinsky 2008) of the liked pairs (user_idx[t], item_idx[t]) by
+    alternating least squares, every half-sweep ``cg_steps`` warm-started conjugate-gradient steps per row
+    (``ops.als_half_sweep``).  A liked pair has preference 1 and confidence 1 + alpha * weight[t]
+    (``weight`` None: 1), every other pair preference 0 and confidence 1; ``reg`` is the L2 weight on both tables.  A pair
+    that repeats counts twice.  Both CSRs are built on the device; the start is
+    ``default_rng(seed).standard_normal * 0.01`` in fp32, X then Y; a sweep is the user half then the item half, the Gram
+    matrix recomputed before each (``ops.als_gram``).
+    Returns {"X" fp32 [n_users, factors], "Y" fp32 [n_items, factors]} on the device, "loss" (the objective after every
+    half-sweep: the row losses summed in fp64 + reg |frozen table|^2) and the parameters ("n_users", "n_items",
+    "factors", "sweeps", "cg_steps", "alpha", "reg", "seed").  Raises ValueError, before any GPU use, for ``factors``
+    outside the supported widths, ``cg_steps`` outside 0 .. 16, a negative ``sweeps``, ``alpha`` or ``reg``; and for an
+    index out of range or a weight that is negative or not finite."""
+    from . import ops
+    factors, cg_steps, reg, alpha = ops.check_als(factors, cg_steps, reg, alpha)
+    n_users, n_items, sweeps = int(n_users), int(n_items), int(sweeps)
+    if n_users < 1 or n_items < 1 or sweeps < 0:
+        raise ValueError("als_fit: n_users and n_items must be >= 1 and sweeps >= 0")
+    u, i = _host(user_idx).reshape(-1), _host(item_idx).reshape(-1)
+    if len(u) != len(i) or (weight is not None and len(_host(weight).reshape(-1)) != len(u)):
+        raise ValueError("als_fit: user_idx, item_idx and weight must have one entry per pair")
+    if len(u) and (u.min() < 0 or u.max() >= n_users or i.min() < 0 or i.max() >= n_items):
+        raise ValueError("als_fit: index out of range")
+    dev = torch.device(device)
+    ud, idd = _on(u, dev, torch.int64), _on(i, dev, torch.int64)
+    ex = None
+    if weight is not None:
+        w = _on(_host(weight).reshape(-1), dev, torch.float32)
+        if w.numel() and not bool((torch.isfinite(w) & (w >= 0)).all()):
+            raise ValueError("als_fit: weight must be finite and >= 0")
+        ex = torch.tensor(alpha, dtype=torch.float32, device=dev) * w
+    u_off, u_idx, u_ex = _als_csr(ud, idd, n_users, ex)
+    i_off, i_idx, i_ex = _als_csr(idd, ud, n_items, ex)
+    rng = np.random.default_rng(seed)
+    X = torch.as_tensor((rng.standard_normal((n_users, factors)) * 0.01).astype(np.float32), device=dev)
+    Y = torch.as_tensor((rng.standard_normal((n_items, factors)) * 0.01).astype(np.float32), device=dev)
+    loss, flags = [], []
+    for _ in range(sweeps):
+        X, rl, e = ops.als_half_sweep(Y, ops.als_gram(Y), u_off, u_idx, X, reg, cg_steps, u_ex, alpha, check=False)
+        loss.append(rl.double().sum() + reg * Y.double().square().sum())
+        flags.append(e)
+        Y, rl, e = ops.als_half_sweep(X, ops.als_gram(X), i_off, i_idx, Y, reg, cg_steps, i_ex, alpha, check=False)
+        loss.append(rl.double().sum() + reg * X.double().square().sum())
+        flags.append(e)
+    if flags and int(torch.cat(flags).max().item()):
+        raise ValueError("als_fit: index out of range")
+    return {"X": X, "Y": Y, "loss": [float(v) for v in (torch.stack(loss).tolist() if loss else [])],
+            "n_users": n_users, "n_items": n_items, "factors": factors, "sweeps": sweeps, "cg_steps": cg_steps,
+            "alpha": alpha, "reg": reg, "seed": int(seed)}
+
+
+def _als_users(fit, users):
+    dev = fit["X"].device
+    us = _on(_host(users).reshape(-1) if not isinstance(users, torch.Tensor) else users.reshape(-1), dev, torch.int64)
+    if us.numel() and (int(us.min()) < 0 or int(us.max()) >= fit["X"].shape[0]):
+        raise ValueError("als: user out of range")
+    return us
+
+
+def als_topk(fit, users, k, watched_bits=None, batch=ALS_BATCH):
+    """ALS recommendation lists: for each user of ``users`` (rows of ``fit["X"]``) the ``k`` best items by
+    ``ops.dot_scores(X[users], Y)`` without a bit in ``watched_bits`` [n_listed, ceil(n_items/32)], taken by the exact
+    select (``ops.rows_topk``), ``batch`` users at a time.  Returns (idx int32 [n_listed, k], score fp32 [n_listed, k])."""
+    from . import ops
+    us = _als_users(fit, users)
+    dev, k, batch = us.device, int(k), int(batch)
+    if batch < 1:
+        raise ValueError("als_topk: batch must be >= 1")
+    n_l = int(us.numel())
+    idx = torch.empty(n_l, k, dtype=torch.int32, device=dev)
+    sc = torch.empty(n_l, k, dtype=torch.float32, device=dev)
+    for l0 in range(0, n_l, batch):
+        l1 = min(n_l, l0 + batch)
+        rows = ops.dot_scores(fit["X"][us[l0:l1]], fit["Y"])
+        idx[l0:l1], sc[l0:l1] = ops.rows_topk(rows, k, wbits=None if watched_bits is None else watched_bits[l0:l1])
+    return idx, sc
+
+
+def als_rank(fit, users, watched_bits, target_row, target_anime, batch=ALS_BATCH):
+    """The ranks ``ops.predict_rank`` gives a model, for the ALS scores of ``als_topk``: target t is (``target_row[t]``:
+    a position in ``users``, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the items the
+    listed user has no watched bit for, the target's own bit ignored).  ``batch`` users at a time."""
+    from . import ops
+    us = _als_users(fit, users)
+    dev, n_l, batch = us.device, int(us.numel()), int(batch)
+    if batch < 1:
+        raise ValueError("als_rank: batch must be >= 1")
+    tr = np.asarray(_host(target_row), np.int64).reshape(-1)
+    ta = np.asarray(_host(target_anime), np.int64).reshape(-1)
+    if tr.shape != ta.shape:
+        raise ValueError("als_rank: target_row and target_anime must have one entry per target")
+    if tr.size and (tr.min() < 0 or tr.max() >= n_l):
+        raise ValueError("als_rank: target_row out of range")
+    rank = torch.empty(int(tr.size), dtype=torch.int32, device=dev)
+    for l0 in range(0, n_l, batch):
+        l1 = min(n_l, l0 + batch)
+        sel = np.flatnonzero((tr >= l0) & (tr < l1))
+        if not sel.size:
+            continue
+        rows = ops.dot_scores(fit["X"][us[l0:l1]], fit["Y"])
+        r = ops.rows_rank(rows, tr[sel] - l0, ta[sel], None if watched_bits is None else watched_bits[l0:l1])
+        rank[torch.as_tensor(sel, device=dev)] = r
+    return rank
+
+
+# ----------------------------------------------------------------------------------------
 # confidence intervals: a Poisson bootstrap over users (DESIGN.md §4.16)
 # ----------------------------------------------------------------------------------------
 # floor(2**32 * CDF(j)) of Poisson(1), j = 0 .. 12 (from 60-digit decimals): the weight of a unit is the number of

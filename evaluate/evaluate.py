@@ -4,7 +4,9 @@
 has no training rating for, by predicted rating, and hit rate / NDCG at each ``eval_k``, MRR and the mean and median
 rank are written to ``eval_csv``; ``--baseline popularity`` adds the same figures for ranking by rating count alone, to
 read the model's against, ``--baseline itemknn`` those of an item-kNN over co-occurrence counts fitted on the training
-slice alone (``popularity,itemknn``: both; the ``--itemknn_*`` flags of the command line tune it);
+slice alone, ``--baseline als`` those of an implicit-feedback ALS factorisation fitted on the same slice (a comma list
+gives several; the ``--itemknn_*`` and ``--als_*`` flags of the command line set their parameters, which are the usual
+library defaults and have not been tuned on this data);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
 spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
 held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
@@ -38,6 +40,18 @@ ITEMKNN_FLAGS = {
     "itemknn_shrink": (float, 0.0, "added to the measure's denominator"),
     "itemknn_min_support": (int, 1, "users two anime must share to be neighbours"),
     "itemknn_min_rating": (float, 0.0, "the scaled rating (0..1) from which a training rating counts as liked"),
+}
+
+# optional and command-line only, like the item-kNN flags: the implicit-feedback ALS baseline (components.ALS_DEFAULTS:
+# the usual library defaults with the width moved to the nearest supported one, not tuned on this data)
+ALS_FLAGS = {
+    "als_factors": (int, 64, "the width of the factor tables: 32, 64, 128 or 256"),
+    "als_sweeps": (int, 15, "sweeps, each a user half and an item half"),
+    "als_cg_steps": (int, 3, "conjugate-gradient steps per row and half-sweep (0 .. 16)"),
+    "als_alpha": (float, 1.0, "a liked pair's confidence is 1 + alpha"),
+    "als_reg": (float, 0.01, "the L2 weight on both factor tables"),
+    "als_min_rating": (float, 0.0, "the scaled rating (0..1) from which a training rating counts as liked"),
+    "als_seed": (int, 0, "the seed of the start tables"),
 }
 
 # optional and command-line only, like the item-kNN flags: confidence intervals and a second model to compare with
@@ -77,7 +91,9 @@ def go(args):
     frame, summary = C.evaluate_frame(model, table, int(args.test_size), C.literal(args.eval_k),
                                       float(args.min_rating), baseline=baseline_arg(args.baseline),
                                       itemknn={f[len("itemknn_"):]: getattr(args, f) for f in ITEMKNN_FLAGS
-                                               if hasattr(args, f)}, compare_model=compare_model, **ci)
+                                               if hasattr(args, f)},
+                                      als={f[len("als_"):]: getattr(args, f) for f in ALS_FLAGS if hasattr(args, f)},
+                                      compare_model=compare_model, **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -102,18 +118,19 @@ def make_parser():
     # optional, unlike the flags above: "popularity" adds the figures of recommending the most-rated unseen anime
     parser.add_argument("--baseline", type=str, default="none", required=False,
                         help="none, popularity (rank the same targets by the anime's number of training ratings), "
-                             "itemknn (by an item-kNN over co-occurrence counts of the training ratings), or both "
-                             "separated by a comma")
+                             "itemknn (by an item-kNN over co-occurrence counts of the training ratings), als (by an "
+                             "implicit-feedback ALS factorisation of the training ratings), or several separated by a "
+                             "comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 
 
 def make_cli_parser():
-    """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--ci_*`` and
+    """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*`` and
     ``--compare_model`` flags."""
     parser = make_parser()
-    for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(CI_FLAGS.items()):
+    for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

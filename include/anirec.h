@@ -1052,6 +1052,75 @@ int anirec_itemknn_scores(const int32_t *nbr_idx, const float *nbr_sim, int32_t 
                           void *stream);
 
 /* ------------------------------------------------------------------------- *
+ *  IMPLICIT-FEEDBACK ALS (Hu, Koren, Volinsky 2008) with the warm-started conjugate-gradient solve of Takacs, Pilaszy
+ *  and Tikk (2011): the learned baseline a ranking table is read against.  No model takes part.
+ *  Tables X [n_users][dim], Y [n_items][dim], dim one of 32, 64, 128, 256.  A liked pair (u, i) carries a confidence
+ *  excess e_ui >= 0 (confidence c = 1 + e) and preference 1; every other pair preference 0 and confidence 1.  The
+ *  objective is sum_all c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2).  All arithmetic below is fp32 unless it
+ *  says fp64; there are no float atomics and no kernel waits on another workgroup.
+ *
+ * anirec_als_gram: G_out [dim][dim] = Y^T Y for Y [n][dim].  Every product Y[r][a] * Y[r][b] is taken in fp64, where it
+ * is exact; the rows are cut into chunks of ANIREC_ALS_GRAM_CHUNK, a cell's products are added in fp64 in row order
+ * inside a chunk, the chunk partials in chunk order from chunk 0's, and the sum is rounded once to fp32.  So
+ * |G - G64| <= 2^-24 |G64| + n 2^-52 sum_r |Y[r][a] Y[r][b]| for finite input, and the bits depend on Y and n alone.
+ * n < 1, a bad dim, a NULL Y, G_out or workspace, a workspace not 8-byte aligned: ANIREC_EINVAL before anything is
+ * enqueued.  workspace: anirec_als_gram_workspace_bytes(n, dim) bytes (0 for a bad argument; needs no GPU), less is
+ * ANIREC_EWORKSPACE; the result does not depend on what it held.  Graph-capturable.
+ *
+ * anirec_als_half_sweep: refits every row of X_inout [n_rows][dim] in place with Y [n_other][dim] frozen and
+ * G = Y^T Y (anirec_als_gram's, or any [dim][dim] the caller holds; only its rows are read, as a symmetric matrix's).
+ * Row u's list I is the entries k = offsets[u] .. offsets[u+1]-1: item i_k = idx[k], excess e_k = excess[k], or alpha
+ * for every entry when excess is NULL.  A repeated index is two entries.  With
+ *     A v  :=  G v + lambda v + sum_{k in I} e_k (y_k . v) y_k                          (never formed as a matrix)
+ * the row is
+ *     empty list:  x = 0 exactly, row_loss = 0, no iteration
+ *     cg_steps == 0:  x stays bit for bit
+ *     r = sum_k ((1 + e_k) - e_k (y_k . x)) y_k - G x - lambda x;   p = r;   rs0 = rs = r . r
+ *     for t = 1 .. cg_steps:   stop unless rs > ANIREC_ALS_CG_RTOL2 * rs0        (which also stops rs0 == 0 and NaN)
+ *         a = rs / (p . Ap);  x += a p;  r -= a Ap;  rs' = r . r;  p = r + (rs' / rs) p;  rs = rs'
+ *     row_loss = x . G x + sum_k [ (1 + e_k)(1 - s_k)^2 - s_k^2 ] + lambda x . x,   s_k = y_k . x, at the final x
+ * (row_loss is the row's share of the objective over ALL items, the constant sum over the unlisted items of 0 dropped
+ * into x . G x - sum_k s_k^2.)  The item half-sweep is the same call on the transposed CSR with X as the frozen table.
+ * The order of every sum, nothing contracted into an fma (kNG = 1024 / dim lane groups, group g, lane l = 0 .. dim/4-1
+ * holding elements 4l .. 4l+3):
+ *     u . v     per lane ((u0 v0 + u1 v1) + u2 v2) + u3 v3, then the xor butterfly over the group's lanes at distances
+ *               dim/8, dim/16, .., 1
+ *     a walk    group g starts from 0, adds w_k G[k] for the rows k = g, g + kNG, .. of G (w_k = v[k]; -v[k] in r, where
+ *               the list term follows in the same accumulator), then c_k y_k for the entries k = g, g + kNG, .. of the
+ *               list in list order (c_k = e_k s_k in A v; (1 + e_k) - e_k s_k in r); the kNG partial rows are added in
+ *               group order from group 0's; the lambda term is added (A v) or subtracted (r) last
+ *     row_loss  (x . Gx + L) + lambda (x . x), L the groups' sums of ((1 + e_k) (d d) - s_k s_k), d = 1 - s_k, over
+ *               their entries in list order, added in group order
+ * So a row's bits are a function of its own list, its start row, Y, G and the scalars: the same alone or among any
+ * other rows, at any position, under any `order`, from run to run.
+ * order: NULL, or a permutation of 0 .. n_rows-1: workgroup b takes row order[b] (longest lists first keeps the tail
+ * short).  A value outside [0, n_rows) raises *err_flag and fits nothing; a value that repeats is undefined.
+ * *err_flag (device; overwritten by the call) becomes 1 on an index outside [0, n_other) or an offsets pair that is
+ * negative, decreasing or longer than INT32_MAX: that row and its loss are NaN, nothing is read through the bad value,
+ * the other rows are unaffected.  excess must be finite and >= 0 (the caller's check; the kernel takes what it is given).
+ * A bad dim, n_other < 1, n_rows < 0, cg_steps outside 0 .. ANIREC_ALS_MAX_CG, lambda or alpha negative or not finite, a
+ * NULL Y, G, offsets, X_inout, row_loss or err_flag with n_rows > 0: ANIREC_EINVAL before anything is enqueued.
+ * n_rows == 0: ANIREC_OK.  No workspace.  Every loop is bounded by cg_steps and the list length.  Graph-capturable.
+ *
+ * anirec_dot_scores: out[q][j] = the chain acc = fmaf(Q[q][t], Y[j][t], acc), t = 0 .. dim-1, from 0, for Q [n_q][dim]
+ * and Y [n][dim]; out is [n_q][ld], ld >= n, elements j >= n of a row are not written.  It is anirec_cosine_scores_w's
+ * chain (the same kernels) on rows that need not be normalised: the score rows anirec_rows_topk / anirec_rows_rank
+ * take.  n < 1, n_q outside 0 .. 4 194 240, ld < n, a bad dim or a NULL pointer with n_q > 0: ANIREC_EINVAL.
+ * ------------------------------------------------------------------------- */
+#define ANIREC_ALS_MAX_CG 16         /* the most conjugate-gradient steps of a half-sweep */
+#define ANIREC_ALS_CG_RTOL2 1e-10f   /* a row stops iterating once r . r <= this x its first r . r */
+#define ANIREC_ALS_GRAM_CHUNK 1024   /* rows of one chunk of anirec_als_gram: part of its definition, not a knob */
+size_t anirec_als_gram_workspace_bytes(int32_t n, int32_t dim);
+int anirec_als_gram(const float *Y, int32_t n, int32_t dim, float *G_out, void *workspace, size_t workspace_bytes,
+                    void *stream);
+int anirec_als_half_sweep(const float *Y, int32_t n_other, int32_t dim, const float *G, const int64_t *offsets,
+                          const int32_t *idx, const float *excess, float alpha, const int32_t *order, float *X_inout,
+                          int32_t n_rows, float lambda, int32_t cg_steps, float *row_loss, int32_t *err_flag,
+                          void *stream);
+int anirec_dot_scores(const float *Q, int32_t n_q, const float *Y, int32_t n, int32_t dim, float *out, int64_t ld,
+                      void *stream);
+
+/* ------------------------------------------------------------------------- *
  *  Ranks to metric sums, and a Poisson bootstrap over users on them.  Integer sums throughout: no
  *  result depends on the order the rows are met in.
  *  The statistic: the resampling UNIT is the user (a user's held-out ratings are not independent, so a replicate
