@@ -55,6 +55,7 @@ GROUP_MAX_MEMBERS = 64
 # anirec_cooc_scores: the similarity of two items' liked-by sets (ANIREC_COOC_*)
 COOC_COSINE, COOC_JACCARD, COOC_CONFIDENCE = 0, 1, 2
 COOC_MEASURES = {"cosine": COOC_COSINE, "jaccard": COOC_JACCARD, "confidence": COOC_CONFIDENCE}
+COVER_MAX_PICKS = 1024      # ANIREC_COVER_MAX_PICKS: the longest list anirec_cover_greedy picks
 
 
 class AnirecError(RuntimeError):
@@ -269,6 +270,12 @@ PROTOTYPES = {
     "anirec_itemknn_lds_items": (_sz, []),
     "anirec_itemknn_workspace_bytes": (_sz, [_i32, _i32]),
     "anirec_itemknn_scores": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    # onboarding lists: greedy maximum coverage over the rated-by bit rows, and the levels of any list
+    "anirec_cover_step_words": (_sz, []),
+    "anirec_cover_lds_words": (_sz, []),
+    "anirec_cover_workspace_bytes": (_sz, [_i32, _i32]),
+    "anirec_cover_greedy": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "anirec_cover_levels": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     # greedy calibrated re-rank of candidate lists towards a favourite profile, and the miscalibration of lists held
     "anirec_calibrate_max_cand": (_sz, []),
     "anirec_calibrate_rerank": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp,

@@ -288,6 +288,62 @@ def also_liked_frame(df, anime_df, syn_df, name, count, types=None, genres=None,
 
 
 # ----------------------------------------------------------------------------------------
+# onboarding: which anime to show a newcomer, from the ratings alone
+# ----------------------------------------------------------------------------------------
+ONBOARD_STRATEGIES = ("coverage", "popularity")
+
+
+def onboarding_frame(df, anime_df, syn_df, count, depth=3, strategy="coverage", types=None, genres=None, max_ratings=0,
+                     holdout=0.2, seed=0):
+    """The ``count`` anime to ask a newcomer about: no model takes part.  ``strategy="coverage"``: the greedy
+    maximum-coverage list (``recs.onboarding_list``) — each anime is the one the most users who know fewer than ``depth``
+    of the list so far have rated; ``"popularity"``: the most rated anime.  Only anime that pass the optional Type /
+    Genre filters are listed.  ``max_ratings > 0`` restricts the population to users with at most that many ratings in
+    ``df`` (a newcomer resembles a light user); 0 means everyone.  A share ``holdout`` of the population (a fixed
+    ``default_rng(seed)`` permutation) takes no part in the picking and is what the list is judged on.  Returns (frame,
+    summary): similar_anime's metadata columns without ``Similarity``, then ``Rated_by`` (raters among all users),
+    ``New_reach`` (the pick's gain: pick users it reached who were still below their depth) and ``Reach_share`` (the
+    running sum of the gains over greedy depth x pick users: the share of the best possible the list has reached; the
+    greedy depth is ``depth`` for coverage and ``count`` for popularity).  ``summary`` holds the settings and, under
+    "coverage" and "popularity", the figures of the chosen strategy AND of the other one on the same split.  The anime
+    index is the rating frame's own (order of first appearance)."""
+    from . import ops, recs
+    strategy = str(strategy).strip().lower()
+    if strategy not in ONBOARD_STRATEGIES:
+        raise ValueError("onboard_strategy %r is not one of %s" % (strategy, ", ".join(ONBOARD_STRATEGIES)))
+    max_ratings = int(max_ratings)
+    if max_ratings < 0:
+        raise ValueError("onboard_max_ratings must be >= 0 (got %d)" % max_ratings)
+    user_ids, anime_ids = index_tables({}, df)
+    m = _topk_count(count, "onboard_number", len(anime_ids))
+    m, depth = ops.check_cover(m, depth)[0], int(depth)
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    keep = filter_mask(meta, anime_df, types, genres)
+    ui, ai, _ = rating_indices(df, user_ids, anime_ids)
+    n_users, n_anime = len(user_ids), len(anime_ids)
+    population = None
+    if max_ratings > 0:
+        population = np.bincount(ui, minlength=n_users) <= max_ratings
+    bits = recs.item_bits(ui, ai, n_users, n_anime)
+    lists = {s: recs.onboarding_list(ui, ai, n_users, n_anime, m, depth, s, population, keep.astype(np.uint8), holdout,
+                                     seed, bits=bits)
+             for s in (strategy,) + tuple(s for s in ONBOARD_STRATEGIES if s != strategy)}
+    res = lists[strategy]
+    idx = res["pick"]
+    ok = idx >= 0
+    frame = _similar_anime_rows(meta, idx, np.zeros(len(idx), np.float32)).drop(columns=["Similarity"])
+    frame["Rated_by"] = res["rated_by"][ok].astype(np.int64)
+    frame["New_reach"] = res["gain"][ok].astype(np.int64)
+    best = res["greedy_depth"] * res["pick_users"]["users"]
+    frame["Reach_share"] = np.cumsum(res["gain"][ok].astype(np.int64)) / float(best) if best else np.nan
+    summary = {"strategy": strategy, "count": m, "depth": depth, "max_ratings": max_ratings, "holdout": float(holdout),
+               "seed": int(seed), "population": res["pick_users"]["users"] + res["holdout_users"]["users"]}
+    for s, r in lists.items():
+        summary[s] = {"picks": r["picks"], "pick_users": r["pick_users"], "holdout_users": r["holdout_users"]}
+    return frame, summary
+
+
+# ----------------------------------------------------------------------------------------
 # similar_users
 # ----------------------------------------------------------------------------------------
 def fave_anime(df, anime_df, user_id, num_faves, tv_only):

@@ -164,8 +164,9 @@ def _job_workspace(nbytes, dev):
 
 
 def release_workspaces():
-    """Give the cached job workspaces back to the allocator."""
+    """Give the cached job workspaces (and ``cover_greedy``'s) back to the allocator."""
     _JOB_WS.clear()
+    _COVER_WS.clear()
 
 
 def _allpairs_pilot(What, n, k_eff, stats):
@@ -1096,6 +1097,94 @@ def itemknn_scores(nbr_idx, nbr_sim, offsets, hist_idx, hist_w=None, workspace=N
     if int(err.item()):
         raise ValueError("itemknn_scores: history, neighbour table or offsets out of range, or an unusable term")
     return out
+
+
+COVER_MAX_PICKS = _lib.COVER_MAX_PICKS
+_COVER_WS = {}
+
+
+def check_cover(m, depth=1):
+    """The argument checks of ``cover_greedy`` (no device needed): (m, depth) as ints, or a ValueError for ``m`` outside
+    1 .. 1024 (ANIREC_COVER_MAX_PICKS) or ``depth`` < 1.  A depth above m closes nobody, whatever its size: it is passed
+    on as m + 1."""
+    try:
+        mi, di = int(m), int(depth)
+    except (TypeError, ValueError):
+        raise ValueError("cover: m = %r and depth = %r must be integers" % (m, depth))
+    if mi != m or di != depth:
+        raise ValueError("cover: m = %r and depth = %r must be integers" % (m, depth))
+    if not 1 <= mi <= COVER_MAX_PICKS:
+        raise ValueError("cover: m = %d must be in 1 .. %d" % (mi, COVER_MAX_PICKS))
+    if di < 1:
+        raise ValueError("cover: depth = %d must be >= 1" % di)
+    return mi, min(di, mi + 1)
+
+
+def _cover_workspace(nbytes, dev):
+    """The greedy's workspace, kept between calls (grow-only, one per device and stream; ``release_workspaces`` drops
+    it): the call needs nothing of what it held."""
+    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _COVER_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        _COVER_WS.pop(key, None)
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        _COVER_WS[key] = ws
+    return ws
+
+
+def cover_greedy(bits, n_users, m, depth=1, open_bits=None, keep=None):
+    """A greedy maximum-coverage list (anirec_cover_greedy): ``bits`` int32 [n_items, ceil(n_users/32)]
+    on the device (``recs.item_bits``).  ``m`` picks; each is the candidate (``keep[i] != 0``, not picked yet) that the
+    most OPEN users have rated, ties to the lowest index; a user is open while it is in the population (``open_bits``
+    int32 [ceil(n_users/32)], None: everyone) and fewer than ``depth`` picks hold it.  The list stops when no candidate
+    reaches an open user.  ``depth >= m`` is the popularity list within the population.  Returns (pick int32 [m] padded
+    with -1, gain int32 [m] padded with 0, info int32 [4] = picks made, users at depth, users in the population, 0) on
+    the device; nothing synchronises.  Exact integer counts: bit-reproducible.  ValueError as ``check_cover``."""
+    m, depth = check_cover(m, depth)
+    _need_gpu()
+    lib = _lib.load()
+    bits, n_users = _item_bits(bits, n_users)
+    dev = bits.device
+    n, W = int(bits.shape[0]), int(bits.shape[1])
+    ob = None
+    if open_bits is not None:
+        ob = torch.as_tensor(open_bits, device=dev).to(torch.int32).contiguous().reshape(-1)
+        if ob.numel() != W:
+            raise ValueError("cover_greedy: open_bits holds ceil(n_users/32) = %d words (got %d)" % (W, ob.numel()))
+    kp = None
+    if keep is not None:
+        kp = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous().reshape(-1)
+        if kp.numel() != n:
+            raise ValueError("cover_greedy: keep holds one byte per item (%d, got %d)" % (n, kp.numel()))
+    pick = torch.empty(m, dtype=torch.int32, device=dev)
+    gain = torch.empty(m, dtype=torch.int32, device=dev)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    ws = _cover_workspace(int(lib.anirec_cover_workspace_bytes(n, n_users)), dev)
+    _lib.check(lib.anirec_cover_greedy(_lib.ptr(bits), n, n_users, _lib.ptr(ob), _lib.ptr(kp), depth, m, _lib.ptr(pick),
+                                       _lib.ptr(gain), _lib.ptr(info), _lib.ptr(ws), ws.numel(), _stream()),
+               "anirec_cover_greedy")
+    return pick, gain, info
+
+
+def cover_levels(bits, n_users, picks, check=True):
+    """How many rows of a list hold each user (anirec_cover_levels): ``picks`` item indices, -1 entries skipped (the
+    padding of ``cover_greedy``), a repeated entry counted twice.  Returns level int32 [n_users] on the device.  Raises
+    ValueError for any other entry out of range; with ``check=False`` returns (level, device flag) and nothing
+    synchronises."""
+    _need_gpu()
+    lib = _lib.load()
+    bits, n_users = _item_bits(bits, n_users)
+    dev = bits.device
+    pk = _i32(picks, dev).reshape(-1)
+    level = torch.empty(n_users, dtype=torch.int32, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.anirec_cover_levels(_lib.ptr(bits), int(bits.shape[0]), n_users, _lib.ptr(pk), int(pk.numel()),
+                                       _lib.ptr(level), _lib.ptr(err), _stream()), "anirec_cover_levels")
+    if not check:
+        return level, err
+    if int(err.item()):
+        raise ValueError("cover_levels: pick out of range")
+    return level
 
 
 BOOT_MAX_REP = 65536     # anirec_boot_sums / anirec_boot_weights: the most replicates of one call

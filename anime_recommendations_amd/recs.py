@@ -1064,3 +1064,86 @@ def bootstrap_metrics(ranks_by_system, target_row, n_units, ks, n_rep=1000, seed
                                    "hi": float(f["diff_hi"][i - 1, j]), "p": float(f["p"][i - 1, j])}
                                for j, m in enumerate(names)}
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# onboarding lists: a greedy maximum-coverage questionnaire: no model takes part
+# ----------------------------------------------------------------------------------------
+ONBOARD_STRATEGIES = ("coverage", "popularity")
+
+
+def _user_words(users, n_users):
+    """int32 [ceil(n_users/32)] with the bits of ``users`` set: the ``open_bits`` of ``ops.cover_greedy``."""
+    flags = np.zeros(((n_users + 31) // 32) * 32, np.uint8)
+    flags[np.asarray(users, np.int64)] = 1
+    return np.packbits(flags.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).view(np.int32)
+
+
+def _known_summary(level, users, depth):
+    """Of ``users``: the share that knows >= 1 listed item, the share that knows >= ``depth``, the mean number known."""
+    if len(users) == 0:
+        return {"users": 0, "share_any": None, "share_depth": None, "mean_known": None}
+    lv = level[users]
+    return {"users": int(len(users)), "share_any": float((lv >= 1).mean()), "share_depth": float((lv >= depth).mean()),
+            "mean_known": float(lv.mean())}
+
+
+def onboarding_split(n_users, population=None, holdout=0.0, seed=0):
+    """The (pick users, held-out users) of an onboarding list, both sorted: the population (None: every user; a bool mask
+    [n_users]; or user indices) in ascending order, permuted by ``numpy.random.default_rng(seed).permutation`` on the
+    host; the first ``floor(holdout * |population|)`` of the permutation are held out, the rest pick.  A function of
+    ``n_users``, the population, ``holdout`` and ``seed`` alone."""
+    n_users = int(n_users)
+    holdout = float(holdout)
+    if not 0.0 <= holdout < 1.0:
+        raise ValueError("onboarding: holdout = %r must be in [0, 1)" % holdout)
+    if population is None:
+        pop = np.arange(n_users, dtype=np.int64)
+    else:
+        p = _host(population).reshape(-1)
+        if p.dtype == np.bool_:
+            if len(p) != n_users:
+                raise ValueError("onboarding: a population mask holds one entry per user")
+            pop = np.flatnonzero(p).astype(np.int64)
+        else:
+            pop = np.unique(p.astype(np.int64))
+            if len(pop) and (pop[0] < 0 or pop[-1] >= n_users):
+                raise ValueError("onboarding: population user out of range")
+    perm = np.random.default_rng(int(seed)).permutation(len(pop))
+    n_hold = int(np.floor(holdout * len(pop)))
+    return np.sort(pop[perm[n_hold:]]), np.sort(pop[perm[:n_hold]])
+
+
+def onboarding_list(user_idx, anime_idx, n_users, n_anime, m, depth=3, strategy="coverage", population=None, keep=None,
+                    holdout=0.0, seed=0, device="cuda:0", bits=None):
+    """Which ``m`` anime to show a newcomer: the greedy maximum-coverage list of the rated-by bits of
+    the rating list (``item_bits``; or ``bits`` when the caller holds them).  The population's users (``population``:
+    None = everyone, a bool mask or user indices) are split into pick and held-out users by ``onboarding_split``: a
+    fixed ``numpy.random.default_rng(seed)`` permutation of the sorted population on the host, its first
+    ``floor(holdout * |population|)`` entries held out.  ``strategy="coverage"``: each pick is the anime (``keep[i] != 0``)
+    the most pick users with fewer than ``depth`` listed anime so far have rated (``ops.cover_greedy``);
+    ``"popularity"``: the same call at depth = m, the most rated anime among the pick users.  The list is then scored on
+    every user (``ops.cover_levels``).  Returns a dict of host values: ``pick`` int32 [m] (-1 padded), ``gain`` int32
+    [m], ``rated_by`` int32 [m] (raters of the pick among ALL users), ``picks`` (made), ``greedy_depth``, and for
+    ``pick_users`` and ``holdout_users`` each {"users", "share_any" (know >= 1), "share_depth" (know >= ``depth``),
+    "mean_known"} (None where the group is empty)."""
+    from . import ops
+    strategy = str(strategy).strip().lower()
+    if strategy not in ONBOARD_STRATEGIES:
+        raise ValueError("onboarding strategy %r is not one of %s" % (strategy, ", ".join(ONBOARD_STRATEGIES)))
+    m, depth = int(m), int(depth)
+    ops.check_cover(m, depth)
+    n_users, n_anime = int(n_users), int(n_anime)
+    pick_users, held_users = onboarding_split(n_users, population, holdout, seed)
+    if bits is None:
+        bits = item_bits(user_idx, anime_idx, n_users, n_anime, device=device)
+    greedy_depth = depth if strategy == "coverage" else m
+    pick, gain, info = ops.cover_greedy(bits, n_users, m, greedy_depth, open_bits=_user_words(pick_users, n_users),
+                                        keep=keep)
+    level = _host(ops.cover_levels(bits, n_users, pick)).astype(np.int64)
+    pop = _host(ops.cooc_scores(bits, n_users, [0], pop=True)[3]).astype(np.int32)     # the raters of every anime
+    pick, gain, info = _host(pick).astype(np.int32), _host(gain).astype(np.int32), _host(info)
+    rated = np.where(pick >= 0, pop[np.maximum(pick, 0)], 0).astype(np.int32)
+    return {"strategy": strategy, "m": m, "depth": depth, "greedy_depth": int(greedy_depth), "pick": pick, "gain": gain,
+            "rated_by": rated, "picks": int(info[0]), "pick_users": _known_summary(level, pick_users, depth),
+            "holdout_users": _known_summary(level, held_users, depth)}

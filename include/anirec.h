@@ -1051,6 +1051,54 @@ int anirec_itemknn_scores(const int32_t *nbr_idx, const float *nbr_sim, int32_t 
                           int32_t n_hist, float *out_scores, int32_t *err_flag, void *ws, size_t ws_bytes,
                           void *stream);
 
+/* ONBOARDING LISTS: which m items to show a newcomer so that there is something to fit.  A greedy
+ * maximum-coverage questionnaire over the rated-by bit rows: pick the m items such that as many users of a population
+ * as possible have rated at least `depth` of them.  item_bits is [n_items][W] uint32, W = ceil(n_users/32), exactly as
+ * anirec_cooc_scores takes it; bits at positions >= n_users may hold anything and have no effect, in the rows and in
+ * open_bits alike.
+ *
+ * anirec_cover_greedy, the rule:
+ *   population P   user u < n_users is in P iff open_bits is NULL or bit u of open_bits[W] is set
+ *   level          level_u = 0 for every u; user u is OPEN iff u is in P and level_u < depth
+ *   pick p = 0 .. m-1:
+ *     gain_p(i)    the number of open users whose bit is set in row i
+ *     candidates   the items with keep[i] != 0 (every item when keep is NULL) that are not picked yet
+ *     the pick     the candidate of the largest gain, ties to the lowest index
+ *     stop         no candidate, or a largest gain of 0: out_pick[p .. m-1] = -1, out_gain[p .. m-1] = 0
+ *     otherwise    out_pick[p] = i, out_gain[p] = gain_p(i), and level_u += 1 for every open u of row i
+ *   out_info[4]    {picks made, #{u in P : level_u == depth} at the end, |P|, 0}
+ * So sum(out_gain) = the sum over P of min(depth, picked rows holding u), out_gain never increases, and depth >= m
+ * never closes a user: the list is then "most rated within P", ties by index — the popularity questionnaire from the
+ * same call.  The objective is monotone and submodular, so greedy is within 1 - 1/e of the best list.  Every quantity
+ * is an integer count: a list depends on the bits, open_bits, keep, depth and m alone, not on the launch shape, on what
+ * ws held, or on the rows the gain pass does not read (those that are no candidate).
+ * Per pick two plain launches, all m enqueued at once: a gain pass (a wave per row, anirec_cover_step_words() words per
+ * step of its row loop, 16-byte loads from the row's first 16-byte boundary, one 64-bit atomicMax of the key
+ * gain << 32 | 0xFFFFFFFF - index per workgroup; the open mask in LDS up to anirec_cover_lds_words() words, past that
+ * read from global memory) and a tail (writes the pick, raises the levels — bit planes over the
+ * mask's words — and closes users).  Once the stop rule fires the remaining gain launches return on a device word.  No
+ * workgroup waits on another, no host read-back, no cooperative grid: graph-capturable.
+ * n_items < 1, n_users < 1, depth < 1, m outside 1 .. ANIREC_COVER_MAX_PICKS, a NULL item_bits, out_pick, out_gain,
+ * out_info or ws, or a ws not 16-byte aligned: ANIREC_EINVAL before anything is enqueued or written.  ws:
+ * anirec_cover_workspace_bytes(n_items, n_users) bytes (0 for a bad argument), less is ANIREC_EWORKSPACE; it may hold
+ * anything on entry.  Cost: a pick reads n_items * W * 4 bytes less the picked and unkept rows.
+ *
+ * anirec_cover_levels: out_level[u], u < n_users, = the number of entries t < n_picks with picks[t] in [0, n_items) and
+ * bit u of that row set: any list scored against any users (held-out users, a hand-made questionnaire).  An entry -1 is
+ * skipped silently, so out_pick can be fed straight back; any other entry out of range raises *err_flag (device;
+ * overwritten by the call) and is skipped, nothing is read through it; a repeated entry counts twice.  n_picks == 0
+ * writes zeros.  n_items < 1, n_users < 1, n_picks < 0, a NULL item_bits, out_level or err_flag, a NULL picks with
+ * n_picks > 0: ANIREC_EINVAL before anything is enqueued or written.  No workspace.  Graph-capturable. */
+#define ANIREC_COVER_MAX_PICKS 1024
+size_t anirec_cover_step_words(void);
+size_t anirec_cover_lds_words(void);
+size_t anirec_cover_workspace_bytes(int32_t n_items, int32_t n_users);
+int anirec_cover_greedy(const uint32_t *item_bits, int32_t n_items, int32_t n_users, const uint32_t *open_bits,
+                        const uint8_t *keep, int32_t depth, int32_t m, int32_t *out_pick, int32_t *out_gain,
+                        int32_t *out_info, void *ws, size_t ws_bytes, void *stream);
+int anirec_cover_levels(const uint32_t *item_bits, int32_t n_items, int32_t n_users, const int32_t *picks,
+                        int32_t n_picks, int32_t *out_level, int32_t *err_flag, void *stream);
+
 /* ------------------------------------------------------------------------- *
  *  IMPLICIT-FEEDBACK ALS (Hu, Koren, Volinsky 2008) with the warm-started conjugate-gradient solve of Takacs, Pilaszy
  *  and Tikk (2011): the learned baseline a ranking table is read against.  No model takes part.
