@@ -56,6 +56,12 @@ GROUP_MAX_MEMBERS = 64
 COOC_COSINE, COOC_JACCARD, COOC_CONFIDENCE = 0, 1, 2
 COOC_MEASURES = {"cosine": COOC_COSINE, "jaccard": COOC_JACCARD, "confidence": COOC_CONFIDENCE}
 COVER_MAX_PICKS = 1024      # ANIREC_COVER_MAX_PICKS: the longest list anirec_cover_greedy picks
+# anirec_fuse_rows: the fusion of several systems' score rows (ANIREC_FUSE_*)
+FUSE_RRF, FUSE_MINMAX = 0, 1
+FUSE_METHODS = {"rrf": FUSE_RRF, "minmax": FUSE_MINMAX}
+FUSE_MAX_SYS = 8            # ANIREC_FUSE_MAX_SYS: the most systems of one call
+FUSE_MAX_ITEMS = 20480      # anirec_fuse_max_items(): one row's sort image (8 B an item) in the LDS of a workgroup
+FUSE_MAX_RRF_C = 1 << 20    # the largest rrf_c: c + 1 + rank stays below 2^24, exact in fp32
 
 
 class AnirecError(RuntimeError):
@@ -295,6 +301,10 @@ PROTOTYPES = {
     "anirec_als_half_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _f32, _i32, _vp, _vp,
                                         _vp]),
     "anirec_dot_scores": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
+    # hybrid lists: several systems' score rows fused into one (the pointers, pitches and weights: host arrays)
+    "anirec_fuse_max_items": (_sz, []),
+    "anirec_fuse_rows": (C.c_int, [C.POINTER(_vp), C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, C.POINTER(_f32), _i32,
+                                   _i32, _vp, _i64, _vp]),
 }
 
 
@@ -327,6 +337,11 @@ def explain_tile(width, k) -> int:
     if not 1 <= k <= explain_max_k(w):
         raise ValueError("explain_tile: k = %d must be in 1 .. %d at width %d" % (k, explain_max_k(w), w))
     return min(EXPLAIN_TILE_FLOATS // w, (EXPLAIN_TILE_FLOATS // k - 1) & ~7)
+
+
+def fuse_max_items() -> int:
+    """anirec_fuse_max_items: the longest row anirec_fuse_rows takes."""
+    return FUSE_MAX_ITEMS
 
 
 def kmeans_tile(width) -> int:

@@ -16,7 +16,7 @@ LIB = os.path.join(PKG, "libanirec.so")
 SOURCES = ["anirec_misc.hip", "anirec_train.hip", "anirec_infer.hip", "anirec_topk_mfma.hip", "anirec_predict_mfma.hip",
            "anirec_ingest.hip", "anirec_recs.hip", "anirec_foldin.hip", "anirec_mmr.hip", "anirec_listeval.hip",
            "anirec_explain.hip", "anirec_kmeans.hip", "anirec_cooc.hip", "anirec_calibrate.hip", "anirec_boot.hip",
-           "anirec_als.hip", "anirec_cover.hip"]
+           "anirec_als.hip", "anirec_cover.hip", "anirec_fuse.hip"]
 
 
 def hipcc_path() -> str:

@@ -1,5 +1,6 @@
 """Command-line plumbing the component scripts share.  ``run`` is every script's ``__main__`` tail; the rest serves the
-model_recs family (model_recs, diverse_recs, calibrated_recs, explain_recs, group_recs, new_user_recs), whose scripts
+model_recs family (model_recs, diverse_recs, calibrated_recs, explain_recs, group_recs, new_user_recs, hybrid_recs), whose
+scripts
 answer one question with one flag set: its flags, the user pick, the input artifacts, the Type / Genre filters and the
 CSV-and-artifact a run leaves behind.  A script of the family keeps what is its own: its extra flags, its log line, its
 ``components.*_frame`` call, its file and artifact names and its metadata."""
@@ -31,6 +32,34 @@ def percentile(v):
     if not 0.0 <= x <= 100.0:
         raise ValueError("%r is not in [0, 100]" % (v,))
     return x
+
+
+# the flags of a hybrid list (hybrid_recs; evaluate --baseline hybrid): all optional.  Equal weights and rrf_c = 60 are the
+# literature's defaults, not tuned on this data.
+HYBRID_FLAGS = {
+    "hybrid_systems": (str, "model,itemknn,als", "the systems whose score rows are fused, separated by a comma: model, "
+                                                 "popularity, itemknn, als"),
+    "hybrid_weights": (str, "none", "none (all 1), or a list with one weight >= 0 per system, e.g. \"[1, 1, 0.5]\""),
+    "hybrid_method": (str, "rrf", "rrf (reciprocal rank fusion) or minmax (the sum of min-max normalised scores)"),
+    "hybrid_rrf_c": (int, 60, "the constant of reciprocal rank fusion: a term is weight / (rrf_c + rank), rank from 1"),
+}
+
+
+def hybrid_args(args):
+    """The ``systems`` / ``weights`` / ``method`` / ``rrf_c`` of the HYBRID_FLAGS on ``args`` (the defaults where a parser
+    has none of them)."""
+    def get(f):
+        return getattr(args, f, HYBRID_FLAGS[f][1])
+    weights = str(get("hybrid_weights")).strip()
+    return {"systems": tuple(x.strip().lower() for x in str(get("hybrid_systems")).split(",") if x.strip()),
+            "weights": None if weights.lower() == "none" else list(C.literal(weights)),
+            "method": str(get("hybrid_method")).strip().lower(), "rrf_c": int(get("hybrid_rrf_c"))}
+
+
+def add_flags(parser, flags):
+    for flag, (kind, default, text) in flags.items():
+        parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
+    return parser
 
 
 def select_user(args, df):

@@ -665,6 +665,74 @@ def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
 
 
 # ----------------------------------------------------------------------------------------
+# hybrid_recs: model_recs' list from the fused score rows of several systems
+# ----------------------------------------------------------------------------------------
+def _member_params(defaults, given, what):
+    par = dict(defaults)
+    for key, v in (given or {}).items():
+        if key not in par:
+            raise ValueError("%s parameter %r is not one of %s" % (what, key, ", ".join(defaults)))
+        par[key] = v
+    return par
+
+
+def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
+                      types=None, genres=None, systems=("model", "itemknn", "als"), weights=None, method="rrf", rrf_c=60,
+                      itemknn=None, als=None):
+    """model_recs_frame with the list taken from several systems at once (``recs.hybrid_topk``): the same candidates
+    (unwatched, indexed, Type / Genre filters), each member of ``systems`` (names of ``recs.HYBRID_SYSTEMS``) scoring
+    every anime for the user, the score rows fused per row under the candidates' mask (``ops.fuse_rows``: ``method`` rrf
+    with ``rrf_c``, or minmax; ``weights`` None = all 1) and the best ``n_recs`` taken by the exact select.  The item-kNN
+    and ALS members are fitted from ``df`` (ITEMKNN_DEFAULTS / ALS_DEFAULTS overridden by ``itemknn`` / ``als``), the
+    user's history and the liked pairs built as ``evaluate_frame`` builds them; popularity is the rating count.
+    Returns (frame, stats): model_recs_frame's columns — ``Prediction`` remains the model's predicted rating of the
+    listed anime — plus ``Hybrid_score`` (the fused value) and one ``Rank_<system>`` per member: the 1-based place of the
+    anime in that member's own ranking under the same mask (``ops.rows_rank``); stats = {"hybrid_systems",
+    "hybrid_weights", "hybrid_method", "hybrid_rrf_c"}.  ValueError before any GPU use for an unknown or repeated system,
+    no system, or a weights list of another length."""
+    from . import ops, recs
+    members, ws, method, rrf_c = recs.check_hybrid(systems, weights, method, rrf_c)
+    knn_par = _member_params(ITEMKNN_DEFAULTS, itemknn, "itemknn")
+    als_par = _member_params(ALS_DEFAULTS, als, "als")
+    if "als" in members:
+        ops.check_als(als_par["factors"], als_par["cg_steps"], als_par["reg"], als_par["alpha"])
+    row, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
+    n_users, n_anime = len(user_ids), len(anime_ids)
+    dev = tA.device
+    if set(members) - {"model"}:
+        ui, ai, r = rating_indices(df, user_ids, anime_ids)
+    sources = []
+    for m in members:
+        if m == "model":
+            sources.append(recs.model_rows_source(tU, tA, head, [row]))
+        elif m == "popularity":
+            sources.append(recs.popularity_scores(ai, n_anime, n_users).to(dev))
+        elif m == "itemknn":
+            knn = recs.itemknn_fit(ui, ai, r, n_users, n_anime, knn_par["min_rating"], int(knn_par["neighbours"]),
+                                   knn_par["measure"], knn_par["shrink"], knn_par["min_support"], device=dev)
+            off, hist, _ = recs.history_csr(ui, ai, r, [row], min_rating=knn_par["min_rating"])
+            sources.append(recs.itemknn_rows_source(knn, off, hist))
+        else:
+            liked = r.astype(np.float32) >= np.float32(als_par["min_rating"])
+            fit = recs.als_fit(ui[liked], ai[liked], n_users, n_anime, als_par["factors"], int(als_par["sweeps"]),
+                               als_par["cg_steps"], als_par["alpha"], als_par["reg"], seed=int(als_par["seed"]), device=dev)
+            sources.append(recs.als_rows_source(fit, [row]))
+    rows = [src(0, 1) if callable(src) else src.reshape(1, -1) for src in sources]   # scored once: fused and ranked below
+    idx, fused = recs.hybrid_topk(rows, k, ws, method, rrf_c, bits)
+    idx, fused = _np(idx)[0], _np(fused)[0]
+    ok = idx >= 0
+    grid = rows[members.index("model")] if "model" in members else ops.predict_grid(tU, tA, head, [row])
+    p = np.full(len(idx), np.nan, np.float32)
+    p[ok] = _np(grid)[0][idx[ok]]
+    frame = _model_recs_rows(meta, idx, p)
+    frame["Hybrid_score"] = fused[ok]
+    for m, x in zip(members, rows):
+        frame["Rank_" + m] = _np(ops.rows_rank(x, np.zeros(int(ok.sum()), np.int64), idx[ok], bits)).astype(np.int64) + 1
+    return frame, {"hybrid_systems": list(members), "hybrid_weights": [float(w) for w in ws], "hybrid_method": method,
+                   "hybrid_rrf_c": int(rrf_c)}
+
+
+# ----------------------------------------------------------------------------------------
 # calibrated_recs: model_recs with the list pulled towards the user's own genre (or source) proportions
 # ----------------------------------------------------------------------------------------
 CALIBRATION_COLUMNS = ("Genres", "Source")
@@ -906,12 +974,18 @@ FITTED_BASELINES = ("als",)
 ALS_DEFAULTS = {"factors": 64, "sweeps": 15, "cg_steps": 3, "alpha": 1.0, "reg": 0.01, "min_rating": 0.0, "seed": 0}
 
 
+# systems that fuse the score rows of others: reported after FITTED_BASELINES.  Equal weights and
+# rrf_c = 60 are the literature's defaults (Cormack, Clarke and Buettcher 2009); neither is tuned on this data.
+FUSED_BASELINES = ("hybrid",)
+HYBRID_DEFAULTS = {"systems": ("model", "itemknn", "als"), "weights": None, "method": "rrf", "rrf_c": 60}
+
+
 def baseline_names(baseline):
-    """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES then FITTED_BASELINES:
-    None -> (), a name or a sequence of names; ValueError for anything else."""
+    """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES, FITTED_BASELINES, then
+    FUSED_BASELINES: None -> (), a name or a sequence of names; ValueError for anything else."""
     if baseline is None:
         return ()
-    known = BASELINES + FITTED_BASELINES
+    known = BASELINES + FITTED_BASELINES + FUSED_BASELINES
     names = [baseline] if isinstance(baseline, str) else list(baseline)
     for b in names:
         if b not in known:
@@ -942,7 +1016,7 @@ def _ci_columns(columns, boot, system, others, key):
 
 
 def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None,
-                   ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None):
+                   ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None, hybrid=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -961,7 +1035,13 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     above its threshold, each with weight 1; the same columns and keys under the name als.  ``als``: a dict overriding
     ALS_DEFAULTS (factors, sweeps, cg_steps, alpha, reg, min_rating, seed) — the usual library defaults, not tuned on this
     data; a ``factors`` outside the supported widths is a ValueError before any GPU use.
-    A sequence of names gives each, in the order popularity, itemknn, als.  None: none.
+    ``baseline="hybrid"``: the same targets under the same bits ranked by the fused score rows of several of the systems
+    above (``recs.hybrid_rank``, ``ops.fuse_rows``), the item-kNN and ALS members fitted on the TRAINING
+    slice with the ``itemknn`` / ``als`` parameters (one fit serves the baseline of the same name too); the same columns
+    and keys under the name hybrid.  ``hybrid``: a dict overriding HYBRID_DEFAULTS (systems: names of
+    ``recs.HYBRID_SYSTEMS``; weights: None = all 1; method: rrf or minmax; rrf_c) — the literature's defaults, not tuned
+    on this data.
+    A sequence of names gives each, in the order popularity, itemknn, als, hybrid.  None: none.
     ``compare_model``: a second model dict over the same id tables, ranked by a second ``ops.predict_rank`` on the same
     targets and bits and reported as the system ``compare`` (the baselines' columns and keys under that name).
     ``ci_replicates`` > 0: a Poisson bootstrap over the held-out USERS (``recs.bootstrap_metrics``), seeded
@@ -985,7 +1065,16 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         if key not in als_par:
             raise ValueError("als parameter %r is not one of %s" % (key, ", ".join(ALS_DEFAULTS)))
         als_par[key] = v
-    if "als" in baselines:
+    hyb_par = dict(HYBRID_DEFAULTS)
+    for key, v in (hybrid or {}).items():
+        if key not in hyb_par:
+            raise ValueError("hybrid parameter %r is not one of %s" % (key, ", ".join(HYBRID_DEFAULTS)))
+        hyb_par[key] = v
+    members = ()
+    if "hybrid" in baselines:
+        members, hyb_w, hyb_method, hyb_c = recs.check_hybrid(hyb_par["systems"], hyb_par["weights"], hyb_par["method"],
+                                                              hyb_par["rrf_c"])
+    if "als" in baselines or "als" in members:
         ops.check_als(als_par["factors"], als_par["cg_steps"], als_par["reg"], als_par["alpha"])
     U, A = _tables_of(model, table)
     others = baselines + (("compare",) if compare_model is not None else ())
@@ -1004,23 +1093,32 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
             base_rank["compare"], _ = ops.predict_rank(torch.as_tensor(cU).cuda(), torch.as_tensor(cA).cuda(),
                                                        weights_io.model_head(compare_model), users, row, anime,
                                                        watched_bits=seen)
-        if "popularity" in baselines:
+        if "popularity" in baselines or "popularity" in members:
             score = recs.popularity_scores(table.anime[train], table.n_anime, table.n_users).to(seen.device)
+        if "popularity" in baselines:
             base_rank["popularity"] = ops.score_rank(score, len(users), row, anime, watched_bits=seen)
-        if "itemknn" in baselines:
+        if "itemknn" in baselines or "itemknn" in members:
             knn = recs.itemknn_fit(table.user[train], table.anime[train], table.rating[train], table.n_users,
                                    table.n_anime, knn_par["min_rating"], int(knn_par["neighbours"]), knn_par["measure"],
                                    knn_par["shrink"], knn_par["min_support"], device=seen.device)
             off, hist, _ = recs.history_csr(table.user[train], table.anime[train], table.rating[train], users,
                                             min_rating=knn_par["min_rating"])
+        if "itemknn" in baselines:
             base_rank["itemknn"] = recs.itemknn_rank(knn, off, hist, None, seen, row, anime)
-        if "als" in baselines:
+        if "als" in baselines or "als" in members:
             tu, ta, tr = (recs._host(c[train]) for c in (table.user, table.anime, table.rating))
             liked = tr.astype(np.float32) >= np.float32(als_par["min_rating"])
             fit = recs.als_fit(tu[liked], ta[liked], table.n_users, table.n_anime,
                                als_par["factors"], int(als_par["sweeps"]), als_par["cg_steps"], als_par["alpha"],
                                als_par["reg"], seed=int(als_par["seed"]), device=seen.device)
+        if "als" in baselines:
             base_rank["als"] = recs.als_rank(fit, users, seen, row, anime)
+        if "hybrid" in baselines:
+            source = {"model": lambda: recs.model_rows_source(tU, tA, weights_io.model_head(model), users),
+                      "popularity": lambda: score, "itemknn": lambda: recs.itemknn_rows_source(knn, off, hist),
+                      "als": lambda: recs.als_rows_source(fit, users)}
+            base_rank["hybrid"] = recs.hybrid_rank([source[m]() for m in members], seen, row, anime, hyb_w, hyb_method,
+                                                   hyb_c)
     else:
         rank = np.zeros(0, np.int32)
     m = recs.ranking_metrics(rank, ks)

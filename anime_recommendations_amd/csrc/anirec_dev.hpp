@@ -298,6 +298,54 @@ __device__ __forceinline__ float mmr_mul(float a, float b) {
   return a * b;
 }
 
+// ---- the order of a score row (the exact select of anirec_infer.hip, the fusion of anirec_fuse.hip): one key, one sort
+// larger score -> larger key; NaN -> 1 (ranks after every number); 0 is "not a candidate"
+__device__ __forceinline__ uint32_t score_key(float s) {
+  if (s != s) return 1u;
+  uint32_t u = __float_as_uint(s);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return u < 2u ? 2u : u;
+}
+
+constexpr int kLdsSortMax = 20480;  // one-workgroup sort: 20480 x 8 B = the 160 KiB of LDS one workgroup may hold
+
+// Sort in LDS, descending, of sw[0 .. cnt) by the whole workgroup (thread tid of nt): a bitonic network in its
+// one-direction form (each merge starts by comparing mirrored pairs), so the entries past the count are virtual zeros
+// that no comparator moves and are skipped.  The entries must be in place behind a barrier; every pass ends with one
+// (cnt < 2 has no pass).
+__device__ __forceinline__ void lds_sort_desc(unsigned long long *sw, uint32_t cnt, int tid, int nt) {
+  uint32_t npad = 1;
+  while (npad < cnt) npad <<= 1;
+  for (uint32_t lg = 1; (1u << lg) <= npad; ++lg) {
+    const uint32_t size = 1u << lg, half = size >> 1;
+    for (uint32_t p = tid; p < npad / 2; p += nt) {
+      const uint32_t base = (p >> (lg - 1)) << lg, off = p & (half - 1);
+      const uint32_t x = base + off, y = base + size - 1 - off;
+      if (y < cnt) {
+        const unsigned long long u = sw[x], v = sw[y];
+        if (u < v) {
+          sw[x] = v;
+          sw[y] = u;
+        }
+      }
+    }
+    __syncthreads();
+    for (uint32_t stride = size >> 2; stride > 0; stride >>= 1) {
+      for (uint32_t p = tid; p < npad / 2; p += nt) {
+        const uint32_t x = 2 * p - (p & (stride - 1)), y = x + stride;
+        if (y < cnt) {
+          const unsigned long long u = sw[x], v = sw[y];
+          if (u < v) {
+            sw[x] = v;
+            sw[y] = u;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // host: a row width the *_w entry points implement (a row is dim / 4 lanes of float4: 8, 16, 32 or 64 lanes)
 static inline bool dim_ok(int32_t dim) { return dim == 32 || dim == 64 || dim == 128 || dim == 256; }
 // host: calls f(std::integral_constant<int, kD>) with a (checked) width as a compile-time constant.  A kernel that

@@ -210,14 +210,7 @@ __global__ __launch_bounds__(256) void k_scores_w(ScoreArgs a) {
 // exact top-k of each score row: 4-pass MSB radix select on order-preserving keys, then
 // ordered collection (ties -> ascending index) and a bitonic sort of the k winners.
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t score_key(float s) {
-  // larger score -> larger key; NaN -> 1 (ranks after every number); 0 is "not a candidate"
-  if (s != s) return 1u;
-  uint32_t u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return u < 2u ? 2u : u;
-}
-
+// (the key of a score, score_key, is in anirec_dev.hpp: the fusion of anirec_fuse.hip orders by it too)
 struct SelectArgs {
   const float *scores;   // [nq][ld]
   size_t ld;
@@ -798,7 +791,7 @@ int anirec_predict_grid_w(const float *U, const float *A, int32_t dim, int32_t n
 // ====================================================================================
 namespace anirec {
 
-constexpr int kLkSortMax = 20480;  // one-workgroup sort: 20480 x 8 B = the 160 KiB of LDS one workgroup may hold
+constexpr int kLkSortMax = kLdsSortMax;  // one-workgroup sort (lds_sort_desc): 20480 x 8 B of LDS
 constexpr int kLkTile = 16384;     // tile of the multi-workgroup sort (128 KiB of LDS)
 constexpr size_t kLkHistBytes = (size_t)4 * kSelMaxBlocks * 256 * 4;  // [pass][query x slice][digit]
 constexpr size_t kLkCntBytes = (size_t)kSelMaxBlocks * 2 * 4;         // [query x slice][gt, eq]
@@ -947,36 +940,7 @@ __global__ __launch_bounds__(1024) void k_lk_sort(LkArgs a, int tiles, int tile,
   const int tid = threadIdx.x, nt = blockDim.x;
   for (uint32_t i = tid; i < cnt; i += nt) sw[i] = w[i];
   __syncthreads();
-  uint32_t npad = 1;
-  while (npad < cnt) npad <<= 1;
-  for (uint32_t lg = 1; (1u << lg) <= npad; ++lg) {
-    const uint32_t size = 1u << lg, half = size >> 1;
-    for (uint32_t p = tid; p < npad / 2; p += nt) {
-      const uint32_t base = (p >> (lg - 1)) << lg, off = p & (half - 1);
-      const uint32_t x = base + off, y = base + size - 1 - off;
-      if (y < cnt) {
-        const unsigned long long u = sw[x], v = sw[y];
-        if (u < v) {
-          sw[x] = v;
-          sw[y] = u;
-        }
-      }
-    }
-    __syncthreads();
-    for (uint32_t stride = size >> 2; stride > 0; stride >>= 1) {
-      for (uint32_t p = tid; p < npad / 2; p += nt) {
-        const uint32_t x = 2 * p - (p & (stride - 1)), y = x + stride;
-        if (y < cnt) {
-          const unsigned long long u = sw[x], v = sw[y];
-          if (u < v) {
-            sw[x] = v;
-            sw[y] = u;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  lds_sort_desc(sw, cnt, tid, nt);
   if (gather) {
     for (size_t i = tid; i < (size_t)a.s.k; i += nt) lk_out(a, q, i, i < cnt ? sw[i] : 0ull, i < cnt);
   } else {

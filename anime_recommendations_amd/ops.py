@@ -1187,6 +1187,97 @@ def cover_levels(bits, n_users, picks, check=True):
     return level
 
 
+FUSE_MAX_SYS = _lib.FUSE_MAX_SYS
+FUSE_METHODS = tuple(_lib.FUSE_METHODS)
+FUSE_MAX_RRF_C = _lib.FUSE_MAX_RRF_C
+
+
+def check_fuse(n_sys, n, weights=None, method="rrf", rrf_c=60):
+    """The argument checks of ``fuse_rows`` (no device needed): (n_sys, n, weights as a list of floats, the method as an
+    ANIREC_FUSE_* value, rrf_c), or a ValueError naming the limit: ``n_sys`` outside 1 .. 8 (ANIREC_FUSE_MAX_SYS), ``n``
+    outside 1 .. 20480 (anirec_fuse_max_items), a ``method`` that is not rrf or minmax (any case), ``rrf_c`` outside
+    0 .. 2^20, ``weights`` (None: all 1) of another length than n_sys, negative or not finite as fp32, or all zero."""
+    def whole(x):
+        try:
+            return int(x) if int(x) == x else None
+        except (TypeError, ValueError):
+            return None
+    si, ni, ci = whole(n_sys), whole(n), whole(rrf_c)
+    if si is None or not 1 <= si <= FUSE_MAX_SYS:
+        raise ValueError("fuse: n_sys = %r must be an integer in 1 .. %d" % (n_sys, FUSE_MAX_SYS))
+    if ni is None or not 1 <= ni <= _lib.fuse_max_items():
+        raise ValueError("fuse: n = %r must be an integer in 1 .. %d (a row is sorted in the LDS of one workgroup)"
+                         % (n, _lib.fuse_max_items()))
+    m = _lib.FUSE_METHODS.get(str(method).strip().lower())
+    if m is None:
+        raise ValueError("fuse: method %r is not one of %s" % (method, ", ".join(FUSE_METHODS)))
+    if ci is None or not 0 <= ci <= FUSE_MAX_RRF_C:
+        raise ValueError("fuse: rrf_c = %r must be an integer in 0 .. %d" % (rrf_c, FUSE_MAX_RRF_C))
+    if weights is None:
+        ws = [1.0] * si
+    else:
+        try:
+            with np.errstate(over="ignore"):
+                ws = [float(np.float32(w)) for w in weights]
+        except (TypeError, ValueError):
+            raise ValueError("fuse: weights = %r must be %d numbers" % (weights, si))
+        if len(ws) != si:
+            raise ValueError("fuse: weights holds %d entries for %d systems" % (len(ws), si))
+        if not all(np.isfinite(w) and w >= 0.0 for w in ws):
+            raise ValueError("fuse: weights = %r must be finite in fp32 and >= 0" % (list(weights),))
+        if not any(w > 0.0 for w in ws):
+            raise ValueError("fuse: weights = %r must not all be 0" % (list(weights),))
+    return si, ni, ws, m, ci
+
+
+def fuse_rows(rows, weights=None, method="rrf", rrf_c=60, n=None, wbits=None, keep=None):
+    """Several systems' score rows fused into one (anirec_fuse_rows): ``rows`` a list of fp32 device
+    tensors, each [nq, ld] or a 1-D vector [>= n] shared by every row; the first ``n`` columns count (default: the
+    shortest ld).  Item j is eligible in row t when ``keep[j] != 0`` and bit j of ``wbits[t]`` ([nq, ceil(n/32)]) is
+    clear.  ``rrf``: the sum over systems of w_s / (rrf_c + 1 + the item's 0-based place among the row's eligible items
+    in that system, in rows_topk's order); ``minmax``: the sum of w_s * (x - lo) / (hi - lo) over the row's finite
+    eligible scores (1 for +inf, 0 for -inf and NaN).  Returns fp32 [nq, n]: NaN where an item is not eligible, so
+    ``rows_topk`` / ``rows_rank`` take it with the same masks.  Bit-reproducible; nothing synchronises.  ValueError as
+    ``check_fuse``; when every system is a shared vector, nq comes from ``wbits`` (else 1)."""
+    rows = list(rows)
+    mats = [r for r in rows if isinstance(r, torch.Tensor) and r.dim() == 2]
+    lens = [int(r.shape[-1]) for r in rows if isinstance(r, torch.Tensor) and r.dim() in (1, 2)]
+    if len(lens) != len(rows):
+        raise ValueError("fuse_rows: every system is a fp32 device tensor [nq, ld] or [n]")
+    n = (min(lens) if lens else 0) if n is None else n
+    n_sys, n, ws, m, rrf_c = check_fuse(len(rows), n, weights, method, rrf_c)
+    if min(lens) < n:
+        raise ValueError("fuse_rows: n = %d must be in 1 .. %d (the shortest row)" % (n, min(lens)))
+    _need_gpu()
+    lib = _lib.load()
+    dev = rows[0].device
+    if mats:
+        nq = int(mats[0].shape[0])
+    else:
+        nq = 1 if wbits is None else int(torch.as_tensor(wbits).shape[0])
+    held = []
+    for r in rows:
+        assert r.is_cuda and r.dtype == torch.float32 and r.device == dev, "fp32 device score rows on one device"
+        if r.dim() == 2 and int(r.shape[0]) != nq:
+            raise ValueError("fuse_rows: every system holds the same number of rows (%d, got %d)" % (nq, r.shape[0]))
+        held.append(r.contiguous())
+    kp = None
+    if keep is not None:
+        kp = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous().reshape(-1)
+        if kp.numel() != n:
+            raise ValueError("fuse_rows: keep holds one byte per item (%d, got %d)" % (n, kp.numel()))
+    wb = _watched(wbits, nq, n, dev)
+    out = torch.empty(nq, n, dtype=torch.float32, device=dev)
+    if nq == 0:
+        return out
+    ptrs = (C.c_void_p * n_sys)(*[r.data_ptr() for r in held])
+    lds = (C.c_int64 * n_sys)(*[int(r.shape[1]) if r.dim() == 2 else 0 for r in held])
+    wts = (C.c_float * n_sys)(*ws)
+    _lib.check(lib.anirec_fuse_rows(ptrs, lds, n_sys, n, nq, _lib.ptr(wb), _lib.ptr(kp), wts, m, rrf_c, _lib.ptr(out), n,
+                                    _stream()), "anirec_fuse_rows")
+    return out
+
+
 BOOT_MAX_REP = 65536     # anirec_boot_sums / anirec_boot_weights: the most replicates of one call
 BOOT_MAX_THR = 16        # and the most thresholds of a weight table
 BOOT_MAX_COL = 4096      # the most columns anirec_boot_sums takes (anirec_rank_gain_rows: n_sys * n_metric + 1)

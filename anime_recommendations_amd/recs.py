@@ -931,6 +931,140 @@ def als_rank(fit, users, watched_bits, target_row, target_anime, batch=ALS_BATCH
 
 
 # ----------------------------------------------------------------------------------------
+# hybrid lists: several systems' score rows fused into one
+# ----------------------------------------------------------------------------------------
+HYBRID_SYSTEMS = ("model", "popularity", "itemknn", "als")
+HYBRID_BATCH = 4096     # users per anirec_fuse_rows call: a score row per system and a fused row each
+
+
+def check_hybrid(systems, weights=None, method="rrf", rrf_c=60):
+    """(systems as a tuple of names, weights as floats, the method's name, rrf_c), or a ValueError before any GPU use:
+    a name that is not one of HYBRID_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
+    weights list of another length among it)."""
+    from . import ops
+    names = [systems] if isinstance(systems, str) else list(systems)
+    names = [str(s).strip().lower() for s in names]
+    for s in names:
+        if s not in HYBRID_SYSTEMS:
+            raise ValueError("hybrid system %r is not one of %s" % (s, ", ".join(HYBRID_SYSTEMS)))
+    if not names or len(set(names)) != len(names):
+        raise ValueError("hybrid systems %r must be one or more distinct names of %s" % (names, ", ".join(HYBRID_SYSTEMS)))
+    _, _, ws, _, rrf_c = ops.check_fuse(len(names), 1, weights, method, rrf_c)
+    return tuple(names), ws, str(method).strip().lower(), rrf_c
+
+
+def model_rows_source(U, A, head, users):
+    """A row source (``(l0, l1) -> fp32 [l1 - l0, n_anime]``) of the model's predicted ratings of ``users`` (rows of
+    ``U``), through ``ops.predict_grid``."""
+    from . import ops
+    us = np.asarray(_host(users), np.int64).reshape(-1)
+    return lambda l0, l1: ops.predict_grid(U, A, head, us[l0:l1])
+
+
+def itemknn_rows_source(knn, offsets, hist_idx, hist_w=None):
+    """A row source of the item-kNN scores of the lists ``itemknn_topk`` takes, through ``ops.itemknn_scores``."""
+    from . import ops
+    off = _knn_batches(knn, offsets, 1)[0]
+    dev = knn["nbr_idx"].device
+    hi = _on(hist_idx, dev, torch.int32)
+    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
+    return lambda l0, l1: ops.itemknn_scores(knn["nbr_idx"], knn["nbr_sim"], off[l0:l1 + 1], hi, hw)
+
+
+def als_rows_source(fit, users):
+    """A row source of the ALS scores of ``users`` (rows of ``fit["X"]``), through ``ops.dot_scores``."""
+    from . import ops
+    us = _als_users(fit, users)
+    return lambda l0, l1: ops.dot_scores(fit["X"][us[l0:l1]], fit["Y"])
+
+
+def _hybrid_spans(n_l, batch):
+    n_l, batch = int(n_l), int(batch)
+    if batch < 1:
+        raise ValueError("hybrid: batch must be >= 1")
+    return [(l0, min(n_l, l0 + batch)) for l0 in range(0, n_l, batch)]
+
+
+def _hybrid_rows(sources, l0, l1):
+    """the score rows of a span: a callable source is asked for them, a 1-D vector is shared by every row"""
+    return [src(l0, l1) if callable(src) else src for src in sources]
+
+
+def hybrid_fused(sources, l0, l1, weights=None, method="rrf", rrf_c=60, watched_bits=None, keep=None):
+    """The fused rows fp32 [l1 - l0, n_anime] of the lists l0 .. l1 (``ops.fuse_rows`` over the sources' rows)."""
+    from . import ops
+    return ops.fuse_rows(_hybrid_rows(sources, l0, l1), weights, method, rrf_c,
+                         wbits=None if watched_bits is None else watched_bits[l0:l1], keep=keep)
+
+
+def hybrid_topk(sources, k, weights=None, method="rrf", rrf_c=60, watched_bits=None, keep=None, batch=HYBRID_BATCH,
+                n_lists=None):
+    """Hybrid recommendation lists: ``sources`` one row source per system (a callable ``(l0, l1) -> fp32 [l1 - l0,
+    n_anime]`` on the device: ``model_rows_source``, ``itemknn_rows_source``, ``als_rows_source``; or a 1-D vector shared
+    by every list: ``popularity_scores``), fused per list by ``ops.fuse_rows`` under ``watched_bits`` [n_lists,
+    ceil(n_anime/32)] and ``keep`` [n_anime], and the ``k`` best taken by the exact select (``ops.rows_topk``), ``batch``
+    lists at a time.  ``n_lists`` defaults to the rows of ``watched_bits``.  Returns (idx int32 [n_lists, k], score fp32
+    [n_lists, k]: the fused values) like ``als_topk``."""
+    from . import ops
+    sources = list(sources)
+    if n_lists is None:
+        if watched_bits is None:
+            raise ValueError("hybrid_topk: n_lists is needed without watched_bits")
+        n_lists = int(watched_bits.shape[0])
+    k = int(k)
+    idx = sc = None
+    for l0, l1 in _hybrid_spans(n_lists, batch):
+        wb = None if watched_bits is None else watched_bits[l0:l1]
+        fused = hybrid_fused(sources, l0, l1, weights, method, rrf_c, watched_bits, keep)
+        if idx is None:
+            idx = torch.empty(int(n_lists), k, dtype=torch.int32, device=fused.device)
+            sc = torch.empty(int(n_lists), k, dtype=torch.float32, device=fused.device)
+        idx[l0:l1], sc[l0:l1] = ops.rows_topk(fused, k, keep=keep, wbits=wb)
+    if idx is None:
+        idx, sc = torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32)
+    return idx, sc
+
+
+def hybrid_rank(sources, watched_bits, target_row, target_anime, weights=None, method="rrf", rrf_c=60,
+                batch=HYBRID_BATCH):
+    """The ranks ``ops.predict_rank`` gives a model, for the fused rows of ``hybrid_topk``: target t is
+    (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the anime
+    the list has no watched bit for).  Raises ValueError if a target has its own watched bit set: a fused row holds no
+    value there.  ``batch`` lists at a time."""
+    from . import ops
+    sources = list(sources)
+    if watched_bits is None:
+        raise ValueError("hybrid_rank: watched_bits [n_lists, ceil(n_anime/32)] is needed")
+    if not isinstance(watched_bits, torch.Tensor):
+        watched_bits = torch.as_tensor(np.ascontiguousarray(watched_bits))
+    n_l = int(watched_bits.shape[0])
+    tr = np.asarray(_host(target_row), np.int64).reshape(-1)
+    ta = np.asarray(_host(target_anime), np.int64).reshape(-1)
+    if tr.shape != ta.shape:
+        raise ValueError("hybrid_rank: target_row and target_anime must have one entry per target")
+    if tr.size and (tr.min() < 0 or tr.max() >= n_l):
+        raise ValueError("hybrid_rank: target_row out of range")
+    if ta.size and (ta.min() < 0 or ta.max() >= 32 * int(watched_bits.shape[1])):
+        raise ValueError("hybrid_rank: target_anime out of range")
+    if tr.size:
+        words = _host(watched_bits[torch.as_tensor(tr, device=watched_bits.device),
+                                   torch.as_tensor(ta >> 5, device=watched_bits.device)]).astype(np.int64)
+        if ((words >> (ta & 31)) & 1).any():
+            raise ValueError("hybrid_rank: a target has its own watched bit set (a fused row holds no value there)")
+    rank = None
+    for l0, l1 in _hybrid_spans(n_l, batch):
+        sel = np.flatnonzero((tr >= l0) & (tr < l1))
+        if not sel.size:
+            continue
+        fused = hybrid_fused(sources, l0, l1, weights, method, rrf_c, watched_bits)
+        r = ops.rows_rank(fused, tr[sel] - l0, ta[sel], watched_bits[l0:l1])
+        if rank is None:
+            rank = torch.empty(int(tr.size), dtype=torch.int32, device=r.device)
+        rank[torch.as_tensor(sel, device=rank.device)] = r
+    return torch.empty(0, dtype=torch.int32) if rank is None else rank
+
+
+# ----------------------------------------------------------------------------------------
 # confidence intervals: a Poisson bootstrap over users (DESIGN.md §4.16)
 # ----------------------------------------------------------------------------------------
 # floor(2**32 * CDF(j)) of Poisson(1), j = 0 .. 12 (from 60-digit decimals): the weight of a unit is the number of

@@ -6,7 +6,9 @@ rank are written to ``eval_csv``; ``--baseline popularity`` adds the same figure
 read the model's against, ``--baseline itemknn`` those of an item-kNN over co-occurrence counts fitted on the training
 slice alone, ``--baseline als`` those of an implicit-feedback ALS factorisation fitted on the same slice (a comma list
 gives several; the ``--itemknn_*`` and ``--als_*`` flags of the command line set their parameters, which are the usual
-library defaults and have not been tuned on this data);
+library defaults and have not been tuned on this data), ``--baseline hybrid`` those of the fused score rows of several
+systems (``--hybrid_systems model,itemknn,als``, ``--hybrid_method rrf|minmax``, ``--hybrid_weights``, ``--hybrid_rrf_c``:
+command line only; equal weights and rrf_c = 60 are the literature's defaults, not tuned on this data either);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
 spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
 held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
@@ -64,6 +66,10 @@ CI_FLAGS = {
                                    "the same targets and reported as the system compare"),
 }
 
+# optional and command-line only, like the item-kNN flags: the members and the fusion of --baseline hybrid
+# (components.HYBRID_DEFAULTS: equal weights and rrf_c = 60, the literature's defaults, not tuned on this data)
+HYBRID_FLAGS = cli.HYBRID_FLAGS
+
 logger = C.setup_logging("evaluate")
 
 
@@ -93,7 +99,7 @@ def go(args):
                                       itemknn={f[len("itemknn_"):]: getattr(args, f) for f in ITEMKNN_FLAGS
                                                if hasattr(args, f)},
                                       als={f[len("als_"):]: getattr(args, f) for f in ALS_FLAGS if hasattr(args, f)},
-                                      compare_model=compare_model, **ci)
+                                      compare_model=compare_model, hybrid=cli.hybrid_args(args), **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -119,18 +125,19 @@ def make_parser():
     parser.add_argument("--baseline", type=str, default="none", required=False,
                         help="none, popularity (rank the same targets by the anime's number of training ratings), "
                              "itemknn (by an item-kNN over co-occurrence counts of the training ratings), als (by an "
-                             "implicit-feedback ALS factorisation of the training ratings), or several separated by a "
-                             "comma")
+                             "implicit-feedback ALS factorisation of the training ratings), hybrid (by the fused "
+                             "score rows of several of them and the model), or several separated by a comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 
 
 def make_cli_parser():
-    """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*`` and
-    ``--compare_model`` flags."""
+    """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*``,
+    ``--compare_model`` and ``--hybrid_*`` flags."""
     parser = make_parser()
-    for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()):
+    for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()) + \
+            list(HYBRID_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

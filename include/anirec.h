@@ -1100,6 +1100,44 @@ int anirec_cover_levels(const uint32_t *item_bits, int32_t n_items, int32_t n_us
                         int32_t n_picks, int32_t *out_level, int32_t *err_flag, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ *  HYBRID LISTS: several systems' score rows fused into one.  Every system ends in fp32 score rows
+ *  [nq][n] on a scale of its own, so the fusion is per row and scale-free: reciprocal rank fusion (Cormack, Clarke and
+ *  Buettcher 2009) or CombSUM of min-max normalised scores (Fox and Shaw 1994), both under the row's own mask.
+ *
+ *  rows_host[s], s < n_sys, is a DEVICE pointer to system s's rows, ld_host[s] the floats between two of them (0: one
+ *  vector shared by every row, as anirec_rows_rank has it); the two arrays and weight_host are HOST arrays, read
+ *  before the call returns (they travel in the kernel's argument struct).  watched: optional [nq][ceil(n/32)] words, a
+ *  set bit excludes (bits at positions >= n are ignored); keep: optional [n] bytes.  Item j of row t is ELIGIBLE when
+ *  keep[j] != 0 and its watched bit is clear.  out[t * ld_out + j] is the fused value of an eligible j and the
+ *  canonical NaN (0x7FC00000) of any other j < n; columns n .. ld_out are not written.  Nothing is read back: the call
+ *  is stream-ordered and can be captured into a graph.
+ *
+ *  The order of a row is the select's: score_key descending (larger first, +0 above -0, NaN after every number), ties
+ *  to the ascending index.  r_s(t, j) = the 0-based place of an eligible j among the eligible items of row t in
+ *  system s.
+ *    ANIREC_FUSE_RRF     term_s = fl32(w_s / fl32(rrf_c + 1 + r_s)): the integer is exact in fp32, the division is
+ *                        correctly rounded.  NaN scores are eligible and rank last, by index.
+ *    ANIREC_FUSE_MINMAX  hi / lo = the first / the last FINITE eligible score of the row in the order above (chosen by
+ *                        key: a row holding both zeros has one answer); v_s = fl32(fl32(x - lo) / fl32(hi - lo)) for a
+ *                        finite x, 0 where hi - lo == 0 or the row has no finite eligible score, 1 for +inf, 0 for
+ *                        -inf and NaN; term_s = fl32(w_s * v_s).
+ *  out = ((+0 + term_0) + term_1) + ... in system order, every add rounded, nothing contracted: a pure function of
+ *  the row's values, equal to a NumPy restatement bit for bit.
+ *
+ *  ANIREC_EINVAL before any launch: n_sys outside 1 .. ANIREC_FUSE_MAX_SYS, n outside 1 .. anirec_fuse_max_items()
+ *  (one row's sort image in LDS), nq < 0, an ld_host[s] that is neither 0 nor >= n, ld_out < n, an unknown method,
+ *  rrf_c outside 0 .. 2^20, a weight that is negative or not finite, weights that are all zero, a null rows_host,
+ *  ld_host, weight_host, rows_host[s] or out.  nq == 0: ANIREC_OK, nothing launched.
+ * ------------------------------------------------------------------------- */
+#define ANIREC_FUSE_RRF     0
+#define ANIREC_FUSE_MINMAX  1
+#define ANIREC_FUSE_MAX_SYS 8
+size_t anirec_fuse_max_items(void);
+int anirec_fuse_rows(const float *const *rows_host, const int64_t *ld_host, int32_t n_sys, int32_t n, int32_t nq,
+                     const uint32_t *watched, const uint8_t *keep, const float *weight_host, int32_t method,
+                     int32_t rrf_c, float *out, int64_t ld_out, void *stream);
+
+/* ------------------------------------------------------------------------- *
  *  IMPLICIT-FEEDBACK ALS (Hu, Koren, Volinsky 2008) with the warm-started conjugate-gradient solve of Takacs, Pilaszy
  *  and Tikk (2011): the learned baseline a ranking table is read against.  No model takes part.
  *  Tables X [n_users][dim], Y [n_items][dim], dim one of 32, 64, 128, 256.  A liked pair (u, i) carries a confidence
