@@ -667,15 +667,6 @@ def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
 # ----------------------------------------------------------------------------------------
 # hybrid_recs: model_recs' list from the fused score rows of several systems
 # ----------------------------------------------------------------------------------------
-def _member_params(defaults, given, what):
-    par = dict(defaults)
-    for key, v in (given or {}).items():
-        if key not in par:
-            raise ValueError("%s parameter %r is not one of %s" % (what, key, ", ".join(defaults)))
-        par[key] = v
-    return par
-
-
 def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
                       types=None, genres=None, systems=("model", "itemknn", "als"), weights=None, method="rrf", rrf_c=60,
                       itemknn=None, als=None):
@@ -692,33 +683,14 @@ def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, use
     no system, or a weights list of another length."""
     from . import ops, recs
     members, ws, method, rrf_c = recs.check_hybrid(systems, weights, method, rrf_c)
-    knn_par = _member_params(ITEMKNN_DEFAULTS, itemknn, "itemknn")
-    als_par = _member_params(ALS_DEFAULTS, als, "als")
-    if "als" in members:
-        ops.check_als(als_par["factors"], als_par["cg_steps"], als_par["reg"], als_par["alpha"])
+    params = _system_params({"itemknn": itemknn, "als": als}, members)
     row, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
-    n_users, n_anime = len(user_ids), len(anime_ids)
-    dev = tA.device
+    cols = None
     if set(members) - {"model"}:
-        ui, ai, r = rating_indices(df, user_ids, anime_ids)
-    sources = []
-    for m in members:
-        if m == "model":
-            sources.append(recs.model_rows_source(tU, tA, head, [row]))
-        elif m == "popularity":
-            sources.append(recs.popularity_scores(ai, n_anime, n_users).to(dev))
-        elif m == "itemknn":
-            knn = recs.itemknn_fit(ui, ai, r, n_users, n_anime, knn_par["min_rating"], int(knn_par["neighbours"]),
-                                   knn_par["measure"], knn_par["shrink"], knn_par["min_support"], device=dev)
-            off, hist, _ = recs.history_csr(ui, ai, r, [row], min_rating=knn_par["min_rating"])
-            sources.append(recs.itemknn_rows_source(knn, off, hist))
-        else:
-            liked = r.astype(np.float32) >= np.float32(als_par["min_rating"])
-            fit = recs.als_fit(ui[liked], ai[liked], n_users, n_anime, als_par["factors"], int(als_par["sweeps"]),
-                               als_par["cg_steps"], als_par["alpha"], als_par["reg"], seed=int(als_par["seed"]), device=dev)
-            sources.append(recs.als_rows_source(fit, [row]))
+        cols = rating_indices(df, user_ids, anime_ids) + (len(user_ids), len(anime_ids))
+    sources = [_system_source(m, (tU, tA, head), cols, params, [row], tA.device) for m in members]
     rows = [src(0, 1) if callable(src) else src.reshape(1, -1) for src in sources]   # scored once: fused and ranked below
-    idx, fused = recs.hybrid_topk(rows, k, ws, method, rrf_c, bits)
+    idx, fused = recs.hybrid_topk([lambda l0, l1, x=x: x[l0:l1] for x in rows], k, ws, method, rrf_c, bits)
     idx, fused = _np(idx)[0], _np(fused)[0]
     ok = idx >= 0
     grid = rows[members.index("model")] if "model" in members else ops.predict_grid(tU, tA, head, [row])
@@ -980,6 +952,61 @@ FUSED_BASELINES = ("hybrid",)
 HYBRID_DEFAULTS = {"systems": ("model", "itemknn", "als"), "weights": None, "method": "rrf", "rrf_c": 60}
 
 
+def _member_params(defaults, given, what):
+    par = dict(defaults)
+    for key, v in (given or {}).items():
+        if key not in par:
+            raise ValueError("%s parameter %r is not one of %s" % (what, key, ", ".join(defaults)))
+        par[key] = v
+    return par
+
+
+def _systems():
+    """One description per system that scores every anime for a list of users (the names of ``recs.HYBRID_SYSTEMS``),
+    which evaluate_frame and hybrid_recs_frame both go through: ``defaults`` the parameters a caller may override;
+    ``check(par)`` the ValueErrors that need no GPU; ``fit(user, anime, rating, n_users, n_anime, par, device)`` the fit
+    from training columns (the model has none: its fit is the caller's (U, A, head)); ``source(fit, users, cols, par)``
+    the fit's row source for ``users``, cols = fit's first five arguments."""
+    from . import ops, recs
+
+    def itemknn_source(knn, users, cols, par):
+        off, hist, _ = recs.history_csr(*cols[:3], users, min_rating=par["min_rating"])
+        return recs.itemknn_rows_source(knn, off, hist)
+
+    def als_fit(user, anime, rating, n_users, n_anime, par, device):
+        u, a, r = (recs._host(c) for c in (user, anime, rating))
+        liked = r.astype(np.float32) >= np.float32(par["min_rating"])
+        return recs.als_fit(u[liked], a[liked], n_users, n_anime, par["factors"], int(par["sweeps"]), par["cg_steps"],
+                            par["alpha"], par["reg"], seed=int(par["seed"]), device=device)
+    return {
+        "model": dict(source=lambda tables, users, cols, par: recs.model_rows_source(*tables, users)),
+        "popularity": dict(fit=lambda user, anime, rating, n_users, n_anime, par, device:
+                           recs.popularity_scores(anime, n_anime, n_users).to(device),
+                           source=lambda score, users, cols, par: score),
+        "itemknn": dict(defaults=ITEMKNN_DEFAULTS, source=itemknn_source,
+                        fit=lambda user, anime, rating, n_users, n_anime, par, device: recs.itemknn_fit(
+                            user, anime, rating, n_users, n_anime, par["min_rating"], int(par["neighbours"]),
+                            par["measure"], par["shrink"], par["min_support"], device=device)),
+        "als": dict(defaults=ALS_DEFAULTS, fit=als_fit, source=lambda fit, users, cols, par: recs.als_rows_source(fit, users),
+                    check=lambda par: ops.check_als(par["factors"], par["cg_steps"], par["reg"], par["alpha"]))}
+
+
+def _system_params(given, used):
+    """{system: its defaults overridden by ``given[system]``}, the pre-GPU check made for each system of ``used``"""
+    table = _systems()
+    params = {name: _member_params(s["defaults"], given.get(name), name) for name, s in table.items() if "defaults" in s}
+    for name in used:
+        table[name].get("check", lambda par: None)(params.get(name))
+    return params
+
+
+def _system_source(name, tables, cols, params, users, device):
+    """The row source of system ``name`` for ``users``, the system fitted from the training columns ``cols`` = (user,
+    anime, rating, n_users, n_anime) on ``device``; ``tables`` = the model's (U, A, head) on the device."""
+    s, par = _systems()[name], params.get(name)
+    return s["source"](s["fit"](*cols, par, device) if "fit" in s else tables, users, cols, par)
+
+
 def baseline_names(baseline):
     """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES, FITTED_BASELINES, then
     FUSED_BASELINES: None -> (), a name or a sequence of names; ValueError for anything else."""
@@ -1027,11 +1054,11 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     everyone scores; the frame gains hit_rate_popularity / ndcg_popularity, the summary popularity_mrr,
     popularity_mean_rank, popularity_hit_rate@k and popularity_ndcg@k.
     ``baseline="itemknn"``: the same targets under the same bits ranked by an item-kNN fitted on the TRAINING slice alone
-    (``recs.itemknn_fit`` / ``recs.itemknn_rank``), each listed user's history that user's training
+    (``recs.itemknn_fit``, ``recs.itemknn_rank``'s ranks), each listed user's history that user's training
     ratings at or above the threshold with weight 1; the same columns and keys under the name itemknn.  ``itemknn``: a
     dict overriding ITEMKNN_DEFAULTS (neighbours, measure, shrink, min_support, min_rating).
     ``baseline="als"``: the same targets under the same bits ranked by an implicit-feedback ALS factorisation fitted on
-    the TRAINING slice alone (``recs.als_fit`` / ``recs.als_rank``), on the training pairs rated at or
+    the TRAINING slice alone (``recs.als_fit``, ``recs.als_rank``'s ranks), on the training pairs rated at or
     above its threshold, each with weight 1; the same columns and keys under the name als.  ``als``: a dict overriding
     ALS_DEFAULTS (factors, sweeps, cg_steps, alpha, reg, min_rating, seed) — the usual library defaults, not tuned on this
     data; a ``factors`` outside the supported widths is a ValueError before any GPU use.
@@ -1055,27 +1082,13 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     from . import ops, recs, weights_io
     baselines = baseline_names(baseline)
     ci_replicates, ci_level = recs.check_bootstrap(ci_replicates, ci_level)
-    knn_par = dict(ITEMKNN_DEFAULTS)
-    for key, v in (itemknn or {}).items():
-        if key not in knn_par:
-            raise ValueError("itemknn parameter %r is not one of %s" % (key, ", ".join(ITEMKNN_DEFAULTS)))
-        knn_par[key] = v
-    als_par = dict(ALS_DEFAULTS)
-    for key, v in (als or {}).items():
-        if key not in als_par:
-            raise ValueError("als parameter %r is not one of %s" % (key, ", ".join(ALS_DEFAULTS)))
-        als_par[key] = v
-    hyb_par = dict(HYBRID_DEFAULTS)
-    for key, v in (hybrid or {}).items():
-        if key not in hyb_par:
-            raise ValueError("hybrid parameter %r is not one of %s" % (key, ", ".join(HYBRID_DEFAULTS)))
-        hyb_par[key] = v
+    hyb_par = _member_params(HYBRID_DEFAULTS, hybrid, "hybrid")
     members = ()
     if "hybrid" in baselines:
         members, hyb_w, hyb_method, hyb_c = recs.check_hybrid(hyb_par["systems"], hyb_par["weights"], hyb_par["method"],
                                                               hyb_par["rrf_c"])
-    if "als" in baselines or "als" in members:
-        ops.check_als(als_par["factors"], als_par["cg_steps"], als_par["reg"], als_par["alpha"])
+    fitted = [s for s in recs.HYBRID_SYSTEMS if s in baselines or s in members]     # each fitted once, in this order
+    params = _system_params({"itemknn": itemknn, "als": als}, fitted)
     U, A = _tables_of(model, table)
     others = baselines + (("compare",) if compare_model is not None else ())
     if compare_model is not None:
@@ -1083,7 +1096,7 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     ks = sorted({int(k) for k in ks})
     if not ks or ks[0] < 1:
         raise ValueError("eval_k must list at least one k >= 1 (got %r)" % (ks,))
-    users, row, anime, train = held_out_targets(table, test_size, min_rating)
+    users, row, anime, train = recs.held_out_targets(table, test_size, min_rating)
     base_rank = {b: np.zeros(0, np.int32) for b in others}
     if len(row):
         tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()
@@ -1093,31 +1106,16 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
             base_rank["compare"], _ = ops.predict_rank(torch.as_tensor(cU).cuda(), torch.as_tensor(cA).cuda(),
                                                        weights_io.model_head(compare_model), users, row, anime,
                                                        watched_bits=seen)
-        if "popularity" in baselines or "popularity" in members:
-            score = recs.popularity_scores(table.anime[train], table.n_anime, table.n_users).to(seen.device)
-        if "popularity" in baselines:
-            base_rank["popularity"] = ops.score_rank(score, len(users), row, anime, watched_bits=seen)
-        if "itemknn" in baselines or "itemknn" in members:
-            knn = recs.itemknn_fit(table.user[train], table.anime[train], table.rating[train], table.n_users,
-                                   table.n_anime, knn_par["min_rating"], int(knn_par["neighbours"]), knn_par["measure"],
-                                   knn_par["shrink"], knn_par["min_support"], device=seen.device)
-            off, hist, _ = recs.history_csr(table.user[train], table.anime[train], table.rating[train], users,
-                                            min_rating=knn_par["min_rating"])
-        if "itemknn" in baselines:
-            base_rank["itemknn"] = recs.itemknn_rank(knn, off, hist, None, seen, row, anime)
-        if "als" in baselines or "als" in members:
-            tu, ta, tr = (recs._host(c[train]) for c in (table.user, table.anime, table.rating))
-            liked = tr.astype(np.float32) >= np.float32(als_par["min_rating"])
-            fit = recs.als_fit(tu[liked], ta[liked], table.n_users, table.n_anime,
-                               als_par["factors"], int(als_par["sweeps"]), als_par["cg_steps"], als_par["alpha"],
-                               als_par["reg"], seed=int(als_par["seed"]), device=seen.device)
-        if "als" in baselines:
-            base_rank["als"] = recs.als_rank(fit, users, seen, row, anime)
+        cols = (table.user[train], table.anime[train], table.rating[train], table.n_users, table.n_anime)
+        sources = {}
+        for s in fitted:        # one fit serves the baseline of that name and the hybrid's member of that name
+            sources[s] = _system_source(s, (tU, tA, weights_io.model_head(model)), cols, params, users, seen.device)
+            if s == "popularity" and s in baselines:        # the shared vector has an entry point of its own
+                base_rank[s] = ops.score_rank(sources[s], len(users), row, anime, watched_bits=seen)
+            elif s in baselines:
+                base_rank[s] = recs.rows_rank_batched(sources[s], len(users), seen, row, anime, what=s + "_rank")
         if "hybrid" in baselines:
-            source = {"model": lambda: recs.model_rows_source(tU, tA, weights_io.model_head(model), users),
-                      "popularity": lambda: score, "itemknn": lambda: recs.itemknn_rows_source(knn, off, hist),
-                      "als": lambda: recs.als_rows_source(fit, users)}
-            base_rank["hybrid"] = recs.hybrid_rank([source[m]() for m in members], seen, row, anime, hyb_w, hyb_method,
+            base_rank["hybrid"] = recs.hybrid_rank([sources[m] for m in members], seen, row, anime, hyb_w, hyb_method,
                                                    hyb_c)
     else:
         rank = np.zeros(0, np.int32)
@@ -1186,7 +1184,7 @@ def evaluate_lists_frame(model, table, test_size, min_rating, diversities, k=10,
         raise ValueError("lists_k must be >= 1 (got %d)" % k)
     if pool < k:
         raise ValueError("lists_pool = %d is smaller than lists_k = %d" % (pool, k))
-    users, row, anime, train = held_out_targets(table, test_size, min_rating)
+    users, row, anime, train = recs.held_out_targets(table, test_size, min_rating)
     rows, slots = [], {}
     if len(row):
         tU, tA = torch.as_tensor(U).cuda(), torch.as_tensor(A).cuda()

@@ -685,6 +685,89 @@ def append_anime(model, folded):
 
 
 # ----------------------------------------------------------------------------------------
+# the score-row driver: any system's lists and ranks, a span of lists at a time
+# ----------------------------------------------------------------------------------------
+def _spans(n_lists, batch, what):
+    n_lists, batch = int(n_lists), int(batch)
+    if batch < 1:
+        raise ValueError("%s: batch must be >= 1" % what)
+    return [(l0, min(n_lists, l0 + batch)) for l0 in range(0, n_lists, batch)]
+
+
+def _span_rows(source, l0, l1):
+    """the score rows fp32 [l1 - l0, n_anime] of a span: a callable source is asked for them, a 1-D vector is every
+    list's row"""
+    return source(l0, l1) if callable(source) else source.reshape(1, -1).expand(l1 - l0, -1)
+
+
+def _span_bits(watched_bits, l0, l1):
+    return None if watched_bits is None else watched_bits[l0:l1]
+
+
+def _targets(what, target_row, target_anime, n_lists, unwatched=None):
+    """(target_row, target_anime) as int64 host arrays, or a ValueError that starts with ``what``: another length, a
+    target_row outside 0 .. n_lists - 1 and, with ``unwatched`` (watched bits [n_lists, words] on any device), a
+    target_anime past its words or a target whose own bit is set there."""
+    tr = np.asarray(_host(target_row), np.int64).reshape(-1)
+    ta = np.asarray(_host(target_anime), np.int64).reshape(-1)
+    if tr.shape != ta.shape:
+        raise ValueError("%s: target_row and target_anime must have one entry per target" % what)
+    if tr.size and (tr.min() < 0 or tr.max() >= int(n_lists)):
+        raise ValueError("%s: target_row out of range" % what)
+    if unwatched is not None and tr.size:
+        if ta.min() < 0 or ta.max() >= 32 * int(unwatched.shape[1]):
+            raise ValueError("%s: target_anime out of range" % what)
+        words = _host(unwatched[torch.as_tensor(tr, device=unwatched.device),
+                                torch.as_tensor(ta >> 5, device=unwatched.device)]).astype(np.int64)
+        if ((words >> (ta & 31)) & 1).any():
+            raise ValueError("%s: a target has its own watched bit set (a fused row holds no value there)" % what)
+    return tr, ta
+
+
+def rows_topk_batched(source, n_lists, k, watched_bits=None, keep=None, batch=4096, what="rows_topk_batched",
+                      device=None):
+    """The ``k`` best anime of each of ``n_lists`` lists by the score rows of ``source`` — a callable ``(l0, l1) -> fp32
+    [l1 - l0, n_anime]`` on the device, or a 1-D vector shared by every list — without a bit in ``watched_bits``
+    [n_lists, ceil(n_anime/32)] and with ``keep`` [n_anime] set, by the exact select (``ops.rows_topk``), ``batch`` lists
+    at a time.  Returns (idx int32 [n_lists, k], score fp32 [n_lists, k]) on ``device`` (None: where the select leaves
+    them; the host when there is no list).  ValueError, starting with ``what``, for ``batch`` < 1."""
+    from . import ops
+    n_lists, k = int(n_lists), int(k)
+    out = None if device is None else (torch.empty(n_lists, k, dtype=torch.int32, device=device),
+                                       torch.empty(n_lists, k, dtype=torch.float32, device=device))
+    for l0, l1 in _spans(n_lists, batch, what):
+        i, s = ops.rows_topk(_span_rows(source, l0, l1), k, keep=keep, wbits=_span_bits(watched_bits, l0, l1))
+        if out is None:
+            out = (torch.empty(n_lists, k, dtype=torch.int32, device=i.device),
+                   torch.empty(n_lists, k, dtype=torch.float32, device=i.device))
+        out[0][l0:l1], out[1][l0:l1] = i, s
+    return out if out is not None else (torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32))
+
+
+def rows_rank_batched(source, n_lists, watched_bits, target_row, target_anime, batch=4096, what="rows_rank_batched",
+                      device=None, own_bit_clear=False):
+    """The ranks ``ops.predict_rank`` gives a model, for the score rows of ``source`` (as ``rows_topk_batched`` takes
+    it): target t is (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on ``device`` (None:
+    where ``ops.rows_rank`` leaves them; the host without targets): 0 = first among the anime the list has no watched bit
+    for, the target's own bit ignored.  ``batch`` lists at a time; a span that holds no target is not scored.
+    ValueError, starting with ``what``, for ``batch`` < 1, targets of two lengths, a target_row out of range and, with
+    ``own_bit_clear``, a target whose own watched bit is set."""
+    from . import ops
+    spans = _spans(n_lists, batch, what)
+    tr, ta = _targets(what, target_row, target_anime, n_lists, watched_bits if own_bit_clear else None)
+    rank = None if device is None else torch.empty(int(tr.size), dtype=torch.int32, device=device)
+    for l0, l1 in spans:
+        sel = np.flatnonzero((tr >= l0) & (tr < l1))
+        if not sel.size:
+            continue
+        r = ops.rows_rank(_span_rows(source, l0, l1), tr[sel] - l0, ta[sel], _span_bits(watched_bits, l0, l1))
+        if rank is None:
+            rank = torch.empty(int(tr.size), dtype=torch.int32, device=r.device)
+        rank[torch.as_tensor(sel, device=rank.device)] = r
+    return torch.empty(0, dtype=torch.int32) if rank is None else rank
+
+
+# ----------------------------------------------------------------------------------------
 # item-kNN from co-occurrence (DESIGN.md §4.14): no model takes part
 # ----------------------------------------------------------------------------------------
 COOC_BATCH = 1024       # query items per anirec_cooc_scores call: a sim row and a count row each
@@ -756,12 +839,16 @@ def _on(x, dev, dtype):
     return t.to(device=dev, dtype=dtype)
 
 
-def _knn_batches(knn, offsets, batch):
+def _knn_source(knn, offsets, hist_idx, hist_w):
+    """(the row source of ``itemknn_rows_source``, n_lists)"""
+    from . import ops
     off = np.asarray(_host(offsets), np.int64).reshape(-1)
     if off.size < 1:
         raise ValueError("itemknn: offsets holds n_lists + 1 entries")
-    n_l = int(off.size) - 1
-    return off, n_l, [(l0, min(n_l, l0 + int(batch))) for l0 in range(0, n_l, int(batch))]
+    dev = knn["nbr_idx"].device
+    hi = _on(hist_idx, dev, torch.int32)
+    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
+    return lambda l0, l1: ops.itemknn_scores(knn["nbr_idx"], knn["nbr_sim"], off[l0:l1 + 1], hi, hw), int(off.size) - 1
 
 
 def itemknn_topk(knn, offsets, hist_idx, hist_w=None, k=10, watched_bits=None, batch=ITEMKNN_BATCH):
@@ -769,44 +856,17 @@ def itemknn_topk(knn, offsets, hist_idx, hist_w=None, k=10, watched_bits=None, b
     it; ``hist_w`` None = weight 1) scored through the neighbour tables of ``knn`` (``ops.itemknn_scores``) and the
     ``k`` best anime without a bit in ``watched_bits`` [n_lists, ceil(n_anime/32)] taken by the exact select
     (``ops.rows_topk``), ``batch`` lists at a time.  Returns (idx int32 [n_lists, k], score fp32 [n_lists, k])."""
-    from . import ops
-    off, n_l, spans = _knn_batches(knn, offsets, batch)
-    dev = knn["nbr_idx"].device
-    k = int(k)
-    idx = torch.empty(n_l, k, dtype=torch.int32, device=dev)
-    sc = torch.empty(n_l, k, dtype=torch.float32, device=dev)
-    hi = _on(hist_idx, dev, torch.int32)
-    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
-    for l0, l1 in spans:
-        rows = ops.itemknn_scores(knn["nbr_idx"], knn["nbr_sim"], off[l0:l1 + 1], hi, hw)
-        idx[l0:l1], sc[l0:l1] = ops.rows_topk(rows, k, wbits=None if watched_bits is None else watched_bits[l0:l1])
-    return idx, sc
+    source, n_l = _knn_source(knn, offsets, hist_idx, hist_w)
+    return rows_topk_batched(source, n_l, k, watched_bits, None, batch, "itemknn_topk", knn["nbr_idx"].device)
 
 
 def itemknn_rank(knn, offsets, hist_idx, hist_w, watched_bits, target_row, target_anime, batch=ITEMKNN_BATCH):
     """The ranks ``ops.predict_rank`` gives a model, for the item-kNN scores of ``itemknn_topk``: target t is
     (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the anime
     the list has no watched bit for, the target's own bit ignored).  ``batch`` lists at a time."""
-    from . import ops
-    off, n_l, spans = _knn_batches(knn, offsets, batch)
-    dev = knn["nbr_idx"].device
-    tr = np.asarray(_host(target_row), np.int64).reshape(-1)
-    ta = np.asarray(_host(target_anime), np.int64).reshape(-1)
-    if tr.shape != ta.shape:
-        raise ValueError("itemknn_rank: target_row and target_anime must have one entry per target")
-    if tr.size and (tr.min() < 0 or tr.max() >= n_l):
-        raise ValueError("itemknn_rank: target_row out of range")
-    rank = torch.empty(int(tr.size), dtype=torch.int32, device=dev)
-    hi = _on(hist_idx, dev, torch.int32)
-    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
-    for l0, l1 in spans:
-        sel = np.flatnonzero((tr >= l0) & (tr < l1))
-        if not sel.size:
-            continue
-        rows = ops.itemknn_scores(knn["nbr_idx"], knn["nbr_sim"], off[l0:l1 + 1], hi, hw)
-        r = ops.rows_rank(rows, tr[sel] - l0, ta[sel], None if watched_bits is None else watched_bits[l0:l1])
-        rank[torch.as_tensor(sel, device=dev)] = r
-    return rank
+    source, n_l = _knn_source(knn, offsets, hist_idx, hist_w)
+    return rows_rank_batched(source, n_l, watched_bits, target_row, target_anime, batch, "itemknn_rank",
+                             knn["nbr_idx"].device)
 
 
 # ----------------------------------------------------------------------------------------
@@ -884,50 +944,27 @@ def _als_users(fit, users):
     return us
 
 
+def _als_source(fit, users):
+    """(the row source of ``als_rows_source``, n_lists)"""
+    from . import ops
+    us = _als_users(fit, users)
+    return lambda l0, l1: ops.dot_scores(fit["X"][us[l0:l1]], fit["Y"]), int(us.numel())
+
+
 def als_topk(fit, users, k, watched_bits=None, batch=ALS_BATCH):
     """ALS recommendation lists: for each user of ``users`` (rows of ``fit["X"]``) the ``k`` best items by
     ``ops.dot_scores(X[users], Y)`` without a bit in ``watched_bits`` [n_listed, ceil(n_items/32)], taken by the exact
     select (``ops.rows_topk``), ``batch`` users at a time.  Returns (idx int32 [n_listed, k], score fp32 [n_listed, k])."""
-    from . import ops
-    us = _als_users(fit, users)
-    dev, k, batch = us.device, int(k), int(batch)
-    if batch < 1:
-        raise ValueError("als_topk: batch must be >= 1")
-    n_l = int(us.numel())
-    idx = torch.empty(n_l, k, dtype=torch.int32, device=dev)
-    sc = torch.empty(n_l, k, dtype=torch.float32, device=dev)
-    for l0 in range(0, n_l, batch):
-        l1 = min(n_l, l0 + batch)
-        rows = ops.dot_scores(fit["X"][us[l0:l1]], fit["Y"])
-        idx[l0:l1], sc[l0:l1] = ops.rows_topk(rows, k, wbits=None if watched_bits is None else watched_bits[l0:l1])
-    return idx, sc
+    source, n_l = _als_source(fit, users)
+    return rows_topk_batched(source, n_l, k, watched_bits, None, batch, "als_topk", fit["X"].device)
 
 
 def als_rank(fit, users, watched_bits, target_row, target_anime, batch=ALS_BATCH):
     """The ranks ``ops.predict_rank`` gives a model, for the ALS scores of ``als_topk``: target t is (``target_row[t]``:
     a position in ``users``, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the items the
     listed user has no watched bit for, the target's own bit ignored).  ``batch`` users at a time."""
-    from . import ops
-    us = _als_users(fit, users)
-    dev, n_l, batch = us.device, int(us.numel()), int(batch)
-    if batch < 1:
-        raise ValueError("als_rank: batch must be >= 1")
-    tr = np.asarray(_host(target_row), np.int64).reshape(-1)
-    ta = np.asarray(_host(target_anime), np.int64).reshape(-1)
-    if tr.shape != ta.shape:
-        raise ValueError("als_rank: target_row and target_anime must have one entry per target")
-    if tr.size and (tr.min() < 0 or tr.max() >= n_l):
-        raise ValueError("als_rank: target_row out of range")
-    rank = torch.empty(int(tr.size), dtype=torch.int32, device=dev)
-    for l0 in range(0, n_l, batch):
-        l1 = min(n_l, l0 + batch)
-        sel = np.flatnonzero((tr >= l0) & (tr < l1))
-        if not sel.size:
-            continue
-        rows = ops.dot_scores(fit["X"][us[l0:l1]], fit["Y"])
-        r = ops.rows_rank(rows, tr[sel] - l0, ta[sel], None if watched_bits is None else watched_bits[l0:l1])
-        rank[torch.as_tensor(sel, device=dev)] = r
-    return rank
+    source, n_l = _als_source(fit, users)
+    return rows_rank_batched(source, n_l, watched_bits, target_row, target_anime, batch, "als_rank", fit["X"].device)
 
 
 # ----------------------------------------------------------------------------------------
@@ -963,38 +1000,21 @@ def model_rows_source(U, A, head, users):
 
 def itemknn_rows_source(knn, offsets, hist_idx, hist_w=None):
     """A row source of the item-kNN scores of the lists ``itemknn_topk`` takes, through ``ops.itemknn_scores``."""
-    from . import ops
-    off = _knn_batches(knn, offsets, 1)[0]
-    dev = knn["nbr_idx"].device
-    hi = _on(hist_idx, dev, torch.int32)
-    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
-    return lambda l0, l1: ops.itemknn_scores(knn["nbr_idx"], knn["nbr_sim"], off[l0:l1 + 1], hi, hw)
+    return _knn_source(knn, offsets, hist_idx, hist_w)[0]
 
 
 def als_rows_source(fit, users):
     """A row source of the ALS scores of ``users`` (rows of ``fit["X"]``), through ``ops.dot_scores``."""
+    return _als_source(fit, users)[0]
+
+
+def hybrid_rows_source(sources, weights=None, method="rrf", rrf_c=60, watched_bits=None, keep=None):
+    """A row source of the fused rows (``ops.fuse_rows`` over the member sources' rows of a span, under the span's
+    ``watched_bits`` and ``keep``): a callable member is asked for its rows, a 1-D vector is shared by every list."""
     from . import ops
-    us = _als_users(fit, users)
-    return lambda l0, l1: ops.dot_scores(fit["X"][us[l0:l1]], fit["Y"])
-
-
-def _hybrid_spans(n_l, batch):
-    n_l, batch = int(n_l), int(batch)
-    if batch < 1:
-        raise ValueError("hybrid: batch must be >= 1")
-    return [(l0, min(n_l, l0 + batch)) for l0 in range(0, n_l, batch)]
-
-
-def _hybrid_rows(sources, l0, l1):
-    """the score rows of a span: a callable source is asked for them, a 1-D vector is shared by every row"""
-    return [src(l0, l1) if callable(src) else src for src in sources]
-
-
-def hybrid_fused(sources, l0, l1, weights=None, method="rrf", rrf_c=60, watched_bits=None, keep=None):
-    """The fused rows fp32 [l1 - l0, n_anime] of the lists l0 .. l1 (``ops.fuse_rows`` over the sources' rows)."""
-    from . import ops
-    return ops.fuse_rows(_hybrid_rows(sources, l0, l1), weights, method, rrf_c,
-                         wbits=None if watched_bits is None else watched_bits[l0:l1], keep=keep)
+    sources = list(sources)
+    return lambda l0, l1: ops.fuse_rows([src(l0, l1) if callable(src) else src for src in sources], weights, method,
+                                        rrf_c, wbits=_span_bits(watched_bits, l0, l1), keep=keep)
 
 
 def hybrid_topk(sources, k, weights=None, method="rrf", rrf_c=60, watched_bits=None, keep=None, batch=HYBRID_BATCH,
@@ -1005,24 +1025,12 @@ def hybrid_topk(sources, k, weights=None, method="rrf", rrf_c=60, watched_bits=N
     ceil(n_anime/32)] and ``keep`` [n_anime], and the ``k`` best taken by the exact select (``ops.rows_topk``), ``batch``
     lists at a time.  ``n_lists`` defaults to the rows of ``watched_bits``.  Returns (idx int32 [n_lists, k], score fp32
     [n_lists, k]: the fused values) like ``als_topk``."""
-    from . import ops
-    sources = list(sources)
     if n_lists is None:
         if watched_bits is None:
             raise ValueError("hybrid_topk: n_lists is needed without watched_bits")
         n_lists = int(watched_bits.shape[0])
-    k = int(k)
-    idx = sc = None
-    for l0, l1 in _hybrid_spans(n_lists, batch):
-        wb = None if watched_bits is None else watched_bits[l0:l1]
-        fused = hybrid_fused(sources, l0, l1, weights, method, rrf_c, watched_bits, keep)
-        if idx is None:
-            idx = torch.empty(int(n_lists), k, dtype=torch.int32, device=fused.device)
-            sc = torch.empty(int(n_lists), k, dtype=torch.float32, device=fused.device)
-        idx[l0:l1], sc[l0:l1] = ops.rows_topk(fused, k, keep=keep, wbits=wb)
-    if idx is None:
-        idx, sc = torch.empty(0, k, dtype=torch.int32), torch.empty(0, k, dtype=torch.float32)
-    return idx, sc
+    fused = hybrid_rows_source(sources, weights, method, rrf_c, watched_bits, keep)
+    return rows_topk_batched(fused, n_lists, k, watched_bits, keep, batch, "hybrid_topk")
 
 
 def hybrid_rank(sources, watched_bits, target_row, target_anime, weights=None, method="rrf", rrf_c=60,
@@ -1031,37 +1039,13 @@ def hybrid_rank(sources, watched_bits, target_row, target_anime, weights=None, m
     (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the anime
     the list has no watched bit for).  Raises ValueError if a target has its own watched bit set: a fused row holds no
     value there.  ``batch`` lists at a time."""
-    from . import ops
-    sources = list(sources)
     if watched_bits is None:
         raise ValueError("hybrid_rank: watched_bits [n_lists, ceil(n_anime/32)] is needed")
     if not isinstance(watched_bits, torch.Tensor):
         watched_bits = torch.as_tensor(np.ascontiguousarray(watched_bits))
-    n_l = int(watched_bits.shape[0])
-    tr = np.asarray(_host(target_row), np.int64).reshape(-1)
-    ta = np.asarray(_host(target_anime), np.int64).reshape(-1)
-    if tr.shape != ta.shape:
-        raise ValueError("hybrid_rank: target_row and target_anime must have one entry per target")
-    if tr.size and (tr.min() < 0 or tr.max() >= n_l):
-        raise ValueError("hybrid_rank: target_row out of range")
-    if ta.size and (ta.min() < 0 or ta.max() >= 32 * int(watched_bits.shape[1])):
-        raise ValueError("hybrid_rank: target_anime out of range")
-    if tr.size:
-        words = _host(watched_bits[torch.as_tensor(tr, device=watched_bits.device),
-                                   torch.as_tensor(ta >> 5, device=watched_bits.device)]).astype(np.int64)
-        if ((words >> (ta & 31)) & 1).any():
-            raise ValueError("hybrid_rank: a target has its own watched bit set (a fused row holds no value there)")
-    rank = None
-    for l0, l1 in _hybrid_spans(n_l, batch):
-        sel = np.flatnonzero((tr >= l0) & (tr < l1))
-        if not sel.size:
-            continue
-        fused = hybrid_fused(sources, l0, l1, weights, method, rrf_c, watched_bits)
-        r = ops.rows_rank(fused, tr[sel] - l0, ta[sel], watched_bits[l0:l1])
-        if rank is None:
-            rank = torch.empty(int(tr.size), dtype=torch.int32, device=r.device)
-        rank[torch.as_tensor(sel, device=rank.device)] = r
-    return torch.empty(0, dtype=torch.int32) if rank is None else rank
+    fused = hybrid_rows_source(sources, weights, method, rrf_c, watched_bits)
+    return rows_rank_batched(fused, int(watched_bits.shape[0]), watched_bits, target_row, target_anime, batch,
+                             "hybrid_rank", own_bit_clear=True)
 
 
 # ----------------------------------------------------------------------------------------
