@@ -386,3 +386,11 @@ def ptr(t) -> int:
     if not t.is_contiguous():
         raise AnirecError("non-contiguous tensor passed to libanirec")
     return t.data_ptr()
+
+
+def call(name, *args) -> None:
+    """``name(*args)`` of the loaded library, its status checked under that name.  An argument with a ``data_ptr`` (a
+    tensor) goes through ``ptr``; None is NULL; ints, floats, ctypes arrays, ``byref``s and ``c_void_p`` handles pass as
+    they are.  Size queries return sizes, not statuses: they are called on ``load()`` directly."""
+    fn = getattr(load(), name)
+    check(fn(*[ptr(a) if hasattr(a, "data_ptr") else a for a in args]), name)

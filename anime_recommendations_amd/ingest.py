@@ -14,13 +14,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ops import _call, _workspace
 
 NULL_I32 = -2 ** 31
 COLUMNS = ("user_id", "anime_id", "rating", "watching_status", "watched_episodes")
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _need_gpu():
@@ -78,7 +75,6 @@ def preprocess_columns(cols, num_reviews, drop_unwatched=False, drop_plan=False,
     Returns a dict of device tensors with the surviving rows in their original order; its ``bounds`` are the
     input's id bounds (the surviving ids are a subset), so a following ``encode_columns`` need not scan for them."""
     _need_gpu()
-    lib = _lib.load()
     u, a = _aligned(cols["user_id"]), _aligned(cols["anime_id"])
     r = _aligned(cols["rating"])
     s, e = _aligned(cols["watching_status"]), _aligned(cols["watched_episodes"])
@@ -94,7 +90,7 @@ def preprocess_columns(cols, num_reviews, drop_unwatched=False, drop_plan=False,
     ub, ab = known.get("user_id"), known.get("anime_id")
     if not (ub and ab):          # both maxima in one pass and one readback
         mx = torch.empty(2, dtype=torch.int32, device=dev)
-        _lib.check(lib.anirec_ingest_id_max(_lib.ptr(u), _lib.ptr(a), n, _lib.ptr(mx), _stream()), "anirec_ingest_id_max")
+        _call("anirec_ingest_id_max", u, a, n, mx)
         mu, ma = mx.tolist()
         ub, ab = ub or max(mu + 1, 1), ab or max(ma + 1, 1)
     opts = _lib.IngestOpts(int(num_reviews), int(bool(drop_unwatched)), int(bool(drop_plan)),
@@ -103,18 +99,12 @@ def preprocess_columns(cols, num_reviews, drop_unwatched=False, drop_plan=False,
     orr, os_, oe = torch.empty_like(r), torch.empty_like(s), torch.empty_like(e)
     res = torch.zeros(2, dtype=torch.int64, device=dev)   # row count | error flag: one readback
     n_out, err = res[0:1], res[1:2].view(torch.int32)[0:1]
-    ws = torch.empty(int(lib.anirec_ingest_workspace_bytes(n, opts.user_id_bound, opts.anime_id_bound)),
-                     dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_ingest_preprocess(_lib.ptr(u), _lib.ptr(a), _lib.ptr(r), _lib.ptr(s), _lib.ptr(e), n,
-                                            C.byref(opts), _lib.ptr(ou), _lib.ptr(oa), _lib.ptr(orr),
-                                            _lib.ptr(os_), _lib.ptr(oe), _lib.ptr(n_out), _lib.ptr(err),
-                                            _lib.ptr(ws), ws.numel(), _stream()), "anirec_ingest_preprocess")
+    ws = _workspace(None, dev, "anirec_ingest_workspace_bytes", n, opts.user_id_bound, opts.anime_id_bound)
+    _call("anirec_ingest_preprocess", u, a, r, s, e, n, C.byref(opts), ou, oa, orr, os_, oe, n_out, err, ws, ws.numel())
     half = None
     if drop_half_watched:        # the reference's frame keeps max_eps / half_eps for this flag (preprocess.py:99-104)
         half = (torch.empty_like(a), torch.empty_like(r))
-        _lib.check(lib.anirec_ingest_half_columns(_lib.ptr(oa), _lib.ptr(n_out), n, C.byref(opts), _lib.ptr(half[0]),
-                                                  _lib.ptr(half[1]), _lib.ptr(ws), ws.numel(), _stream()),
-                   "anirec_ingest_half_columns")
+        _call("anirec_ingest_half_columns", oa, n_out, n, C.byref(opts), *half, ws, ws.numel())
     m, bad, first_nan = torch.cat([n_out, err.to(torch.int64), torch.isnan(orr[:1]).to(torch.int64)]).tolist()
     if bad:
         raise ValueError("negative user_id / anime_id in the rating table")
@@ -133,7 +123,6 @@ def encode_ids(ids, bound=None):
     """``Series.unique()`` encoding on the GPU: (index int32 [n], uniques int32 [n_unique]).
     ``bound``: an exclusive upper bound of the ids if the caller knows one (default: max + 1, one pass more)."""
     _need_gpu()
-    lib = _lib.load()
     ids = _aligned(ids)
     assert ids.dtype == torch.int32
     n = int(ids.numel())
@@ -145,10 +134,8 @@ def encode_ids(ids, bound=None):
     uniq = torch.empty(min(n, bound), dtype=torch.int32, device=dev)
     res = torch.zeros(2, dtype=torch.int64, device=dev)   # number of ids | error flag: one readback
     n_u, err = res[0:1], res[1:2].view(torch.int32)[0:1]
-    ws = torch.empty(int(lib.anirec_ingest_encode_workspace_bytes(n, bound)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_ingest_encode(_lib.ptr(ids), n, bound, _lib.ptr(idx), _lib.ptr(uniq), _lib.ptr(n_u),
-                                        _lib.ptr(err), _lib.ptr(ws), ws.numel(), _stream()),
-               "anirec_ingest_encode")
+    ws = _workspace(None, dev, "anirec_ingest_encode_workspace_bytes", n, bound)
+    _call("anirec_ingest_encode", ids, n, bound, idx, uniq, n_u, err, ws, ws.numel())
     count, bad = res.tolist()
     if bad & 0xFFFFFFFF:
         raise ValueError("negative id in the column to encode")

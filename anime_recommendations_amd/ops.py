@@ -6,6 +6,10 @@ A head dict (w, b, gamma, beta, mov_mean, mov_var) may carry an "activation" (Ke
 without one the head is the reference's sigmoid.
 The exact ops take the embedding width from the tables (``shape[1]``, one of ``_lib.WIDTHS``) and call the ``*_w``
 entry points with it (the plain names of the C ABI are those calls at 128).  The ``*_mfma`` ops exist at width 128 only.
+
+Every wrapper has one shape: its checks that need no device (the ``check_*`` functions) before
+``_need_gpu()``, its arguments through the conversions below, its outputs from ``_outputs``, one ``_call`` line with the
+tensors as they are (``_lib.call`` takes their addresses), and, where the entry point has an error flag, ``_finish``.
 """
 from __future__ import annotations
 
@@ -22,6 +26,11 @@ from .schedule import ACTIVATIONS, LOSSES, OPTIMIZERS, adam_alphas, resolve_acti
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _call(name, *args):
+    """One library call on torch's current stream (the last argument of every entry point that enqueues)."""
+    _lib.call(name, *args, _stream())
 
 
 def _f32(x, device):
@@ -50,9 +59,96 @@ def _watched(watched_bits, n_q, n_a, dev):
     """The ``watched_bits`` argument as the library takes it: int32 [n_q, ceil(n_a / 32)] on ``dev``, or None."""
     if watched_bits is None:
         return None
-    wb = torch.as_tensor(watched_bits, device=dev).to(torch.int32).contiguous()
+    wb = _i32(watched_bits, dev)
     assert wb.shape == (n_q, (n_a + 31) // 32)
     return wb
+
+
+def _keep_bytes(keep, n, dev, what=None):
+    """The ``keep`` argument as the library takes it: uint8 [n] on ``dev``, or None.  Another length is the caller's
+    failure: the ValueError of the op ``what`` names, an assert without one."""
+    if keep is None:
+        return None
+    kp = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous().reshape(-1)
+    if what is None:
+        assert kp.numel() == n
+    elif kp.numel() != n:
+        raise ValueError("%s: keep holds one byte per item (%d, got %d)" % (what, n, kp.numel()))
+    return kp
+
+
+def _bit_words(x, dev, shape=None, what=None):
+    """32-bit words on ``dev``, contiguous (a NumPy uint32 / int32 array or an int32 tensor); with ``shape``, a ValueError
+    naming ``what`` for another one."""
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x).view(np.int32))
+    x = x.to(device=dev).contiguous()
+    if shape is not None and tuple(x.shape) != tuple(shape):
+        raise ValueError("%s: expected shape %s, got %s" % (what, tuple(shape), tuple(x.shape)))
+    return x
+
+
+def _score_rows(scores, shape):
+    """Score rows a caller holds, contiguous: an fp32 2-D device tensor (``shape``: how the op's assert names it)."""
+    assert isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2, \
+        "fp32 %s device score rows" % shape
+    return scores.contiguous()
+
+
+def _check_csr(off, n_rows, n_entries, what, noun):
+    """ValueError unless the int64 offsets ``off`` are a CSR of ``n_rows`` lists over ``n_entries`` entries.  On the
+    host tensor of explain_lists and fold_in this reads nothing from the device; on a device tensor (als_half_sweep) it
+    is one reduction and one readback."""
+    if off.numel() != n_rows + 1 or bool((off[0] != 0) | (off[-1] != n_entries) | (off[1:] < off[:-1]).any()):
+        raise ValueError("%s: offsets must rise from 0 to the number of %s" % (what, noun))
+
+
+def _outputs(dev, *specs):
+    """Uninitialised outputs on ``dev``, one per ``(dtype, *shape)``."""
+    return tuple(torch.empty(*shape, dtype=dtype, device=dev) for dtype, *shape in specs)
+
+
+def _rerank_outputs(dev, n_lists, k):
+    """(idx int32, pos int32, score fp32, pen fp32), each [n_lists, k]: what the greedy re-ranks return."""
+    return _outputs(dev, (torch.int32, n_lists, k), (torch.int32, n_lists, k), (torch.float32, n_lists, k),
+                    (torch.float32, n_lists, k))
+
+
+def _err_flag(dev, handed_on=False):
+    """The device error flag of an entry point that has one.  An op that reads the flag itself, right after a call that
+    enqueued work, takes it as it comes: the entry point clears it before its first kernel, and the dirty-memory tests
+    fill it with their patterns to hold the library to that.  ``handed_on``: the op has a ``check=False`` form that
+    gives the flag to its caller unread, or may skip its call or make one that enqueues nothing for an empty input
+    (the entry point then returns before its own clearing); that flag is zero whatever the library did."""
+    return (torch.zeros if handed_on else torch.empty)(1, dtype=torch.int32, device=dev)
+
+
+def _finish(result, err, check, message):
+    """The end of an op with an error flag: ``result`` (a tensor or a tuple of them) once the flag is read and clear,
+    ValueError(message) if it is raised; with ``check=False`` the flag is appended unread and nothing synchronises."""
+    if not check:
+        return (*result, err) if isinstance(result, tuple) else (result, err)
+    if int(err.item()):
+        raise ValueError(message)
+    return result
+
+
+def _workspace(given, dev, size_fn, *sizes):
+    """The workspace of one call: ``given`` if the caller passed one, else the bytes the library's ``size_fn(*sizes)``
+    asks for."""
+    if given is not None:
+        return given
+    return torch.empty(int(getattr(_lib.load(), size_fn)(*sizes)), dtype=torch.uint8, device=dev)
+
+
+def _cached_workspace(cache, nbytes, dev):
+    """A workspace kept in ``cache`` between calls (grow-only, one per device and stream).  Stream-ordered reuse is safe:
+    the calls that use it run on torch's current stream and need nothing of what it held."""
+    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
+    if key not in cache or cache[key].numel() < nbytes:
+        cache.pop(key, None)        # the smaller block goes back to the allocator before the larger one is asked for
+        cache[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    return cache[key]
 
 
 def _need_128(tables, exact):
@@ -66,22 +162,19 @@ def _need_128(tables, exact):
 def rownorm(W, device="cuda:0"):
     """``W / np.linalg.norm(W, axis=1).reshape(-1, 1)`` on the GPU (fp32, no epsilon)."""
     _need_gpu()
-    lib = _lib.load()
     W = _f32(W, device)
     dim = _width(W)
     out = torch.empty_like(W)
-    _lib.check(lib.anirec_rownorm_w(_lib.ptr(W), W.shape[0], dim, _lib.ptr(out), _stream()), "anirec_rownorm_w")
+    _call("anirec_rownorm_w", W, W.shape[0], dim, out)
     return out
 
 
 def cosine_scores(What, q):
     """``np.dot(What, What[q])`` with the library's fixed fp32 summation order."""
     _need_gpu()
-    lib = _lib.load()
     dim = _width(What)
     out = torch.empty(What.shape[0], dtype=torch.float32, device=What.device)
-    _lib.check(lib.anirec_cosine_scores_w(_lib.ptr(What), What.shape[0], dim, int(q), _lib.ptr(out), _stream()),
-               "anirec_cosine_scores_w")
+    _call("anirec_cosine_scores_w", What, What.shape[0], dim, int(q), out)
     return out
 
 
@@ -93,7 +186,6 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
     anirec_cosine_topk_large_w (same result for the first MAX_TOPK columns); `workspace` must suit the call taken.
     """
     _need_gpu()
-    lib = _lib.load()
     dim = _width(What)
     k = int(k)
     if k < 1:
@@ -111,32 +203,25 @@ def cosine_topk(What, queries, k, exclude_self=True, keep=None, workspace=None):
         if q.numel() and bool(((q < 0) | (q >= n)).any()):     # one sync instead of two
             raise ValueError("query row out of range")
     nq = int(q.numel())
-    out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
-    out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    out_i, out_s = _outputs(dev, (torch.int32, nq, k), (torch.float32, nq, k))
     if nq == 0:
         return out_i, out_s
-    keep_t = None
-    if keep is not None:
-        keep_t = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous()
-        assert keep_t.numel() == n
-    if workspace is None:       # (the workspaces hold score rows only: the same sizes at every width)
-        nb = lib.anirec_topk_large_workspace_bytes(n, nq, k) if large else lib.anirec_topk_workspace_bytes(n, nq)
-        workspace = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-    name = "anirec_cosine_topk_large_w" if large else "anirec_cosine_topk_w"
-    _lib.check(getattr(lib, name)(_lib.ptr(What), n, dim, _lib.ptr(q), nq, _lib.ptr(keep_t), int(bool(exclude_self)), k,
-                                  _lib.ptr(out_i), _lib.ptr(out_s), _lib.ptr(workspace), workspace.numel(), _stream()),
-               name)
+    keep_t = _keep_bytes(keep, n, dev)
+    # (the workspaces hold score rows only: the same sizes at every width)
+    size = ("anirec_topk_large_workspace_bytes", n, nq, k) if large else ("anirec_topk_workspace_bytes", n, nq)
+    ws = _workspace(workspace, dev, *size)
+    _call("anirec_cosine_topk_large_w" if large else "anirec_cosine_topk_w", What, n, dim, q, nq, keep_t,
+          int(bool(exclude_self)), k, out_i, out_s, ws, ws.numel())
     return out_i, out_s
 
 
 def topk_job_plan(nq, k, prior="auto", batch=None, lanes=2):
     """The library's default batch plan of a cosine_topk_mfma job: (starts [n_batches + 1], learn_batches, lanes)."""
-    lib = _lib.load()
     st = (C.c_int32 * (_lib.TOPK_MAX_BATCHES + 1))()
     nb, nl = C.c_int32(0), C.c_int32(0)
     lanes = max(1, min(4, int(lanes)))
-    _lib.check(lib.anirec_cosine_topk_job_plan(int(nq), int(k), int(prior == "auto"), int(batch or 0), lanes, st,
-                                               C.byref(nb), C.byref(nl)), "anirec_cosine_topk_job_plan")
+    _lib.call("anirec_cosine_topk_job_plan", int(nq), int(k), int(prior == "auto"), int(batch or 0), lanes, st,
+              C.byref(nb), C.byref(nl))
     return [int(st[i]) for i in range(nb.value + 1)], int(nl.value), lanes
 
 
@@ -144,23 +229,16 @@ _JOB_WS = {}
 
 
 def _job_workspace(nbytes, dev):
-    """The job's workspace, kept between calls (grow-only, one per device and stream): at 350 k rows it is several GB
+    """The job's workspace, kept between calls (``_cached_workspace``): at 350 k rows it is several GB
     (the all-pairs job: two inboxes of n x 256 x 8 B = 1.4 GB, two chains' logs of ~2 GB each, the candidate buffers —
     7-8 GB in all), and torch's caching allocator may carve a freed block of that size up for the next small
-    allocations, so that the following job pays a hipMalloc inside its call.  Stream-ordered reuse is safe: every job
-    runs on torch's current stream and ends joined to it.  ``release_workspaces`` drops the cache; a workspace larger
+    allocations, so that the following job pays a hipMalloc inside its call.  Every job runs on torch's current stream
+    and ends joined to it.  ``release_workspaces`` drops the cache; a workspace larger
     than ANIREC_TOPK_WS_CACHE_GB (default 16) is never cached: a memory policy for callers that cannot spare it."""
     cap = float(os.environ.get("ANIREC_TOPK_WS_CACHE_GB", "16")) * (1 << 30)
     if nbytes > cap:
         return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _JOB_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _JOB_WS.pop(key, None)
-        ws = None
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        _JOB_WS[key] = ws
-    return ws
+    return _cached_workspace(_JOB_WS, nbytes, dev)
 
 
 def release_workspaces():
@@ -201,12 +279,10 @@ def _allpairs_pilot(What, n, k_eff, stats):
 
 def topk_allpairs_plan(n, k, lanes=2, main_batches=0):
     """The library's plan of the all-pairs job (learning batch + batches of equal work): (starts, learn_batches, lanes)."""
-    lib = _lib.load()
     st = (C.c_int32 * (_lib.TOPK_MAX_BATCHES + 1))()
     nb, nl = C.c_int32(0), C.c_int32(0)
     lanes = max(1, min(2, int(lanes)))
-    _lib.check(lib.anirec_cosine_topk_allpairs_plan(int(n), int(k), lanes, int(main_batches), st, C.byref(nb), C.byref(nl)),
-               "anirec_cosine_topk_allpairs_plan")
+    _lib.call("anirec_cosine_topk_allpairs_plan", int(n), int(k), lanes, int(main_batches), st, C.byref(nb), C.byref(nl))
     return [int(st[i]) for i in range(nb.value + 1)], int(nl.value), lanes
 
 
@@ -244,8 +320,7 @@ def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None,
     dev, n = What.device, What.shape[0]
     q = _i32(queries, dev)
     nq = int(q.numel())
-    out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
-    out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    out_i, out_s = _outputs(dev, (torch.int32, nq, k), (torch.float32, nq, k))
     if stats is None:
         stats = {}
     stats.update(batches=0, learn_batches=0, rerun_rows=0, fallback_rows=0)
@@ -293,9 +368,8 @@ def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None,
     st = (C.c_int32 * (nb + 1))(*starts)
     if cand_timing is not None:
         topk_mfma_timing(True)
-    _lib.check(lib.anirec_cosine_topk_job(_lib.ptr(What), n, _lib.ptr(q), nq, _lib.ptr(keep_t), int(bool(exclude_self)),
-                                          int(k), mode, theta0, st, nb, learn, eff_lanes, _lib.ptr(out_i), _lib.ptr(out_s),
-                                          _lib.ptr(flags), _lib.ptr(ws), ws.numel(), _stream()), "anirec_cosine_topk_job")
+    _call("anirec_cosine_topk_job", What, n, q, nq, keep_t, int(bool(exclude_self)), int(k), mode, theta0, st, nb, learn,
+          eff_lanes, out_i, out_s, flags, ws, ws.numel())
     if cand_timing is not None:
         ms, nl = topk_mfma_timing(False)
         cand_timing["ms"] = cand_timing.get("ms", 0.0) + ms
@@ -328,9 +402,8 @@ def cosine_topk_mfma(What, queries, k, exclude_self=True, keep=None, batch=None,
 def topk_mfma_timing(enable):
     """Arm / disarm HIP-event timing of the MFMA candidate kernel; returns (ms, launches) summed over the calls
     made since it was last armed (bench.py's roofline leg)."""
-    lib = _lib.load()
     ms, nl = C.c_float(0.0), C.c_int32(0)
-    _lib.check(lib.anirec_topk_mfma_timing(int(bool(enable)), C.byref(ms), C.byref(nl)), "anirec_topk_mfma_timing")
+    _lib.call("anirec_topk_mfma_timing", int(bool(enable)), C.byref(ms), C.byref(nl))
     return float(ms.value), int(nl.value)
 
 
@@ -344,36 +417,35 @@ def _head_struct(head):
                      float(head["mov_mean"]), float(head["mov_var"]))
 
 
+def _head_args(head):
+    """The two arguments every predicting entry point takes for a head dict: (its struct by reference, ANIREC_ACT_*)."""
+    return C.byref(_head_struct(head)), _head_act(head)
+
+
 def predict_pairs(U, A, head, user_idx, anime_idx):
     """``model.predict([user_arr, anime_arr]).flatten()`` (BN inference mode)."""
     _need_gpu()
-    lib = _lib.load()
     dev = U.device
     ui, ai = _i32(user_idx, dev), _i32(anime_idx, dev)
     assert ui.numel() == ai.numel()
     p = torch.empty(ui.numel(), dtype=torch.float32, device=dev)
-    h = _head_struct(head)
+    h = _head_args(head)
     dim = _width(U, A)
-    _lib.check(lib.anirec_predict_pairs_w(_lib.ptr(U), _lib.ptr(A), dim, _lib.ptr(ui), _lib.ptr(ai),
-                                          int(ui.numel()), C.byref(h), _head_act(head), _lib.ptr(p), _stream()),
-               "anirec_predict_pairs_w")
+    _call("anirec_predict_pairs_w", U, A, dim, ui, ai, int(ui.numel()), *h, p)
     return p
 
 
 def predict_grid(U, A, head, users):
     """Predicted rating of every anime for each listed user -> [len(users), n_anime] fp32."""
     _need_gpu()
-    lib = _lib.load()
     dev = U.device
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())
     out = torch.empty(n_q, n_a, dtype=torch.float32, device=dev)
     dim = _width(U, A)
-    h = _head_struct(head)
-    ws = torch.empty(int(lib.anirec_predict_workspace_bytes_w(n_a, max(n_q, 1), 0, dim)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_predict_grid_w(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h),
-                                         _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
-               "anirec_predict_grid_w")
+    h = _head_args(head)
+    ws = _workspace(None, dev, "anirec_predict_workspace_bytes_w", n_a, max(n_q, 1), 0, dim)
+    _call("anirec_predict_grid_w", U, A, dim, n_a, us, n_q, *h, out, ws, ws.numel())
     return out
 
 
@@ -382,18 +454,14 @@ def predict_grid_mfma(U, A, head, users, out=None):
     suite's heads; the proven worst case is max act' x |hs| x 3.2e-5 plus roundings of the head and the activation
     (include/anirec.h), looser than 1e-5 once |hs| max act' exceeds ~0.3."""
     _need_gpu()
-    lib = _lib.load()
     _need_128((U, A), "predict_grid")
     dev = U.device
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())
     if out is None:
         out = torch.empty(n_q, n_a, dtype=torch.float32, device=dev)
-    ws = torch.empty(int(lib.anirec_predict_mfma_workspace_bytes(n_a, max(n_q, 1))), dtype=torch.uint8, device=dev)
-    h = _head_struct(head)
-    _lib.check(lib.anirec_predict_grid_mfma_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us), n_q, C.byref(h),
-                                                _head_act(head), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _stream()),
-               "anirec_predict_grid_mfma")
+    ws = _workspace(None, dev, "anirec_predict_mfma_workspace_bytes", n_a, max(n_q, 1))
+    _call("anirec_predict_grid_mfma_act", U, A, n_a, us, n_q, *_head_args(head), out, ws, ws.numel())
     return out
 
 
@@ -402,7 +470,6 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
     anirec_predict_topk_large_w).  watched_bits: uint32/int32 [n_users, ceil(n_anime/32)] (bit set = watched)
     or None."""
     _need_gpu()
-    lib = _lib.load()
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")
@@ -410,20 +477,17 @@ def predict_topk(U, A, head, users, k, watched_bits=None):
     dev = U.device
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())
-    out_i = torch.empty(n_q, k, dtype=torch.int32, device=dev)
-    out_p = torch.empty(n_q, k, dtype=torch.float32, device=dev)
+    out_i, out_p = _outputs(dev, (torch.int32, n_q, k), (torch.float32, n_q, k))
     if n_q == 0:
         return out_i, out_p
     wb = _watched(watched_bits, n_q, n_a, dev)
     dim = _width(U, A)
-    h = _head_struct(head)
-    nb = (lib.anirec_predict_topk_large_workspace_bytes_w(n_a, n_q, k, dim) if large
-          else lib.anirec_predict_workspace_bytes_w(n_a, n_q, 1, dim))
-    ws = torch.empty(int(nb), dtype=torch.uint8, device=dev)
-    name = "anirec_predict_topk_large_w" if large else "anirec_predict_topk_w"
-    _lib.check(getattr(lib, name)(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head),
-                                  _lib.ptr(wb), k, _lib.ptr(out_i), _lib.ptr(out_p), _lib.ptr(ws), ws.numel(),
-                                  _stream()), name)
+    h = _head_args(head)
+    size = (("anirec_predict_topk_large_workspace_bytes_w", n_a, n_q, k, dim) if large
+            else ("anirec_predict_workspace_bytes_w", n_a, n_q, 1, dim))
+    ws = _workspace(None, dev, *size)
+    _call("anirec_predict_topk_large_w" if large else "anirec_predict_topk_w", U, A, dim, n_a, us, n_q, *h, wb, k,
+          out_i, out_p, ws, ws.numel())
     return out_i, out_p
 
 
@@ -465,29 +529,24 @@ def group_topk(U, A, head, users, offsets, member_row, k, mode="mean", floor=Non
         raise ValueError("group_topk: a group of %d members is above the limit of %d (GROUP_MAX_MEMBERS)"
                          % (biggest, _lib.GROUP_MAX_MEMBERS))
     _need_gpu()
-    lib = _lib.load()
     us, off, mr = _i32(users, dev), _i32(off_host, dev), _i32(member_row, dev)
     assert us.dim() == 1 and mr.dim() == 1
     n_a, n_q, n_m = A.shape[0], int(us.numel()), int(mr.numel())
     dim = _width(U, A)
     if n_q and bool(((us < 0) | (us >= U.shape[0])).any()):
         raise ValueError("group_topk: user row out of range")
-    out_i = torch.empty(n_g, k, dtype=torch.int32, device=dev)
-    out_s = torch.empty(n_g, k, dtype=torch.float32, device=dev)
+    out_i, out_s = _outputs(dev, (torch.int32, n_g, k), (torch.float32, n_g, k))
     out_m = torch.empty(n_m, k, dtype=torch.float32, device=dev) if member_ratings else None
-    if n_g:
-        wb = _watched(watched_bits, n_q, n_a, dev)
-        xb = _watched(exclude_bits, n_g, n_a, dev)
-        h = _head_struct(head)
-        err = torch.empty(1, dtype=torch.int32, device=dev)
-        ws = torch.empty(int(lib.anirec_group_topk_workspace_bytes(n_a, n_q, n_g, k, dim)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.anirec_group_topk(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head),
-                                         _lib.ptr(wb), _lib.ptr(off), _lib.ptr(mr), n_g, n_m, max(biggest, 1),
-                                         _lib.ptr(xb), m, fl, k, _lib.ptr(out_i), _lib.ptr(out_s), _lib.ptr(out_m),
-                                         _lib.ptr(err), _lib.ptr(ws), ws.numel(), _stream()), "anirec_group_topk")
-        if int(err.item()):
-            raise ValueError("group_topk: offsets or member_row out of range")
-    return (out_i, out_s, out_m) if member_ratings else (out_i, out_s)
+    res = (out_i, out_s, out_m) if member_ratings else (out_i, out_s)
+    if n_g == 0:
+        return res
+    wb = _watched(watched_bits, n_q, n_a, dev)
+    xb = _watched(exclude_bits, n_g, n_a, dev)
+    err = _err_flag(dev)
+    ws = _workspace(None, dev, "anirec_group_topk_workspace_bytes", n_a, n_q, n_g, k, dim)
+    _call("anirec_group_topk", U, A, dim, n_a, us, n_q, *_head_args(head), wb, off, mr, n_g, n_m, max(biggest, 1), xb,
+          m, fl, k, out_i, out_s, out_m, err, ws, ws.numel())
+    return _finish(res, err, True, "group_topk: offsets or member_row out of range")
 
 
 def seen_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
@@ -495,7 +554,6 @@ def seen_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
     for every rating (u, a) — the ``watched_bits`` of predict_topk / predict_rank.  Raises ValueError on an index out
     of range."""
     _need_gpu()
-    lib = _lib.load()
     dev = user_idx.device if isinstance(user_idx, torch.Tensor) and user_idx.is_cuda else device
     u, a = _i32(user_idx, dev), _i32(anime_idx, dev)
     assert u.dim() == 1 and u.shape == a.shape
@@ -503,27 +561,27 @@ def seen_bits(user_idx, anime_idx, n_users, n_anime, device="cuda:0"):
     if n_users < 0 or n_anime < 1:
         raise ValueError("seen_bits: n_users must be >= 0 and n_anime >= 1")
     bits = torch.empty(n_users, (n_anime + 31) // 32, dtype=torch.int32, device=u.device)
-    err = torch.empty(1, dtype=torch.int32, device=u.device)
-    _lib.check(lib.anirec_seen_bits(_lib.ptr(u), _lib.ptr(a), int(u.numel()), n_users, n_anime, _lib.ptr(bits),
-                                    _lib.ptr(err), _stream()), "anirec_seen_bits")
-    if int(err.item()):
-        raise ValueError("seen_bits: user or anime index out of range")
-    return bits
+    err = _err_flag(u.device)
+    _call("anirec_seen_bits", u, a, int(u.numel()), n_users, n_anime, bits, err)
+    return _finish(bits, err, True, "seen_bits: user or anime index out of range")
 
 
 RANK_BATCH = 1 << 22    # targets per anirec_predict_rank / anirec_score_rank call: far inside its 32-bit target offsets and grid
 
 
-def _rank_batches(n_t, dev, what, call):
-    """``call(t, cnt, err)`` (a status; ``t``: the slice of the batch's targets, ``err``: the device error flag) for the
-    targets RANK_BATCH at a time.  True if any batch raised its flag."""
-    err = torch.empty(1, dtype=torch.int32, device=dev)
+def _rank_batches(name, n_t, result, dev, message, args):
+    """The entry point ``name`` with the arguments ``args(t, cnt, err)`` (``t``: the slice of the batch's targets,
+    ``err``: the device error flag) for the targets RANK_BATCH at a time.  Every call clears the one flag, so it is read
+    after each batch; ``result``, or ValueError(message) once all batches have run if any of them raised it."""
+    err = _err_flag(dev)
     bad = False
     for t0 in range(0, n_t, RANK_BATCH):
         cnt = min(RANK_BATCH, n_t - t0)
-        _lib.check(call(slice(t0, t0 + cnt), cnt, _lib.ptr(err)), what)
+        _call(name, *args(slice(t0, t0 + cnt), cnt, err))
         bad = bad or bool(int(err.item()))
-    return bad
+    if bad:
+        raise ValueError(message)
+    return result
 
 
 def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None):
@@ -534,7 +592,6 @@ def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None)
     user (0 = first), ``p[t]`` its rating there, bit for bit.  watched_bits as predict_topk.  Raises ValueError on a
     target_row or target_anime out of range."""
     _need_gpu()
-    lib = _lib.load()
     dev = U.device
     us = _i32(users, dev)
     tr, ta = _i32(target_row, dev), _i32(target_anime, dev)
@@ -543,24 +600,17 @@ def predict_rank(U, A, head, users, target_row, target_anime, watched_bits=None)
     dim = _width(U, A)
     if n_q and bool(((us < 0) | (us >= U.shape[0])).any()):
         raise ValueError("predict_rank: user row out of range")
-    rank = torch.empty(n_t, dtype=torch.int32, device=dev)
-    p = torch.empty(n_t, dtype=torch.float32, device=dev)
+    rank, p = _outputs(dev, (torch.int32, n_t), (torch.float32, n_t))
     if n_t == 0:
         return rank, p
     if n_q == 0:
         raise ValueError("predict_rank: target_row out of range (no users)")
     wb = _watched(watched_bits, n_q, n_a, dev)
-    h = _head_struct(head)
-    ws = torch.empty(int(lib.anirec_predict_rank_workspace_bytes(n_a, n_q, min(n_t, RANK_BATCH), dim)), dtype=torch.uint8,
-                     device=dev)
-
-    def batch(t, cnt, err):
-        return lib.anirec_predict_rank(_lib.ptr(U), _lib.ptr(A), dim, n_a, _lib.ptr(us), n_q, C.byref(h), _head_act(head),
-                                       _lib.ptr(wb), _lib.ptr(tr[t]), _lib.ptr(ta[t]), cnt, _lib.ptr(rank[t]),
-                                       _lib.ptr(p[t]), err, _lib.ptr(ws), ws.numel(), _stream())
-    if _rank_batches(n_t, dev, "anirec_predict_rank", batch):
-        raise ValueError("predict_rank: target_row or target_anime out of range")
-    return rank, p
+    h = _head_args(head)
+    ws = _workspace(None, dev, "anirec_predict_rank_workspace_bytes", n_a, n_q, min(n_t, RANK_BATCH), dim)
+    return _rank_batches("anirec_predict_rank", n_t, (rank, p), dev, "predict_rank: target_row or target_anime out of range",
+                         lambda t, cnt, err: (U, A, dim, n_a, us, n_q, *h, wb, tr[t], ta[t], cnt, rank[t], p[t], err, ws,
+                                              ws.numel()))
 
 
 def score_rank(score, n_users, target_row, target_anime, watched_bits=None):
@@ -570,7 +620,6 @@ def score_rank(score, n_users, target_row, target_anime, watched_bits=None):
     target's own bit ignored; larger score first, NaN last, ties by index).  watched_bits as predict_rank.  Raises
     ValueError on a target_row or target_anime out of range."""
     _need_gpu()
-    lib = _lib.load()
     assert isinstance(score, torch.Tensor) and score.is_cuda and score.dtype == torch.float32 and score.dim() == 1, \
         "fp32 [n_anime] device vector"
     dev = score.device
@@ -586,13 +635,8 @@ def score_rank(score, n_users, target_row, target_anime, watched_bits=None):
     if n_q == 0:
         raise ValueError("score_rank: target_row out of range (no users)")
     wb = _watched(watched_bits, n_q, n_a, dev)
-
-    def batch(t, cnt, err):
-        return lib.anirec_score_rank(_lib.ptr(sc), n_a, _lib.ptr(wb), n_q, _lib.ptr(tr[t]), _lib.ptr(ta[t]), cnt,
-                                     _lib.ptr(rank[t]), err, _stream())
-    if _rank_batches(n_t, dev, "anirec_score_rank", batch):
-        raise ValueError("score_rank: target_row or target_anime out of range")
-    return rank
+    return _rank_batches("anirec_score_rank", n_t, rank, dev, "score_rank: target_row or target_anime out of range",
+                         lambda t, cnt, err: (sc, n_a, wb, n_q, tr[t], ta[t], cnt, rank[t], err))
 
 
 def check_mmr(width, n_cand, k, lam):
@@ -622,24 +666,16 @@ def mmr_rerank(What, cand_idx, cand_score, k, lam):
         raise ValueError("mmr_rerank: cand_idx and cand_score must both be [n_lists, n_cand]")
     dim, n_cand, k, lam = check_mmr(What.shape[1], cand_idx.shape[1], k, lam)
     _need_gpu()
-    lib = _lib.load()
     assert _width(What) == dim
     dev = What.device
     ci, cs = _i32(cand_idx, dev), _f32(cand_score, dev)
     n_lists = int(ci.shape[0])
-    idx = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
-    pos = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
-    score = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
-    pen = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    res = _rerank_outputs(dev, n_lists, k)
     if n_lists == 0:
-        return idx, pos, score, pen
-    err = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_mmr_rerank(_lib.ptr(What), dim, What.shape[0], _lib.ptr(ci), _lib.ptr(cs), n_lists, n_cand, k,
-                                     lam, _lib.ptr(idx), _lib.ptr(pos), _lib.ptr(score), _lib.ptr(pen), _lib.ptr(err),
-                                     _stream()), "anirec_mmr_rerank")
-    if int(err.item()):
-        raise ValueError("mmr_rerank: candidate index out of range")
-    return idx, pos, score, pen
+        return res
+    err = _err_flag(dev)
+    _call("anirec_mmr_rerank", What, dim, What.shape[0], ci, cs, n_lists, n_cand, k, lam, *res, err)
+    return _finish(res, err, True, "mmr_rerank: candidate index out of range")
 
 
 def check_list_similarity(width, k):
@@ -665,22 +701,16 @@ def list_similarity(What, list_idx):
     if What.shape[0] < 1:
         raise ValueError("list_similarity: What has no rows")
     _need_gpu()
-    lib = _lib.load()
     assert _width(What) == dim
     dev = What.device
     li = _i32(list_idx, dev)
     n_lists = int(li.shape[0])
-    sim_max = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
-    sim_sum = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    res = sim_max, sim_sum = _outputs(dev, (torch.float32, n_lists, k), (torch.float32, n_lists, k))
     if n_lists == 0:
-        return sim_max, sim_sum
-    err = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_list_similarity(_lib.ptr(What), dim, What.shape[0], _lib.ptr(li), n_lists, k,
-                                          _lib.ptr(sim_max), _lib.ptr(sim_sum), _lib.ptr(err), _stream()),
-               "anirec_list_similarity")
-    if int(err.item()):
-        raise ValueError("list_similarity: list index out of range")
-    return sim_max, sim_sum
+        return res
+    err = _err_flag(dev)
+    _call("anirec_list_similarity", What, dim, What.shape[0], li, n_lists, k, sim_max, sim_sum, err)
+    return _finish(res, err, True, "list_similarity: list index out of range")
 
 
 def check_calibrate(n_cat, n_cand, k, calibration):
@@ -713,12 +743,6 @@ def _calibrate_tables(what, cat_bits, n_cat, lists, profile):
                          % (what, (int(lists.shape[0]), n_cat), tuple(profile.shape)))
 
 
-def _cat_words(cat_bits, dev):
-    if not torch.is_tensor(cat_bits):
-        cat_bits = torch.from_numpy(np.ascontiguousarray(cat_bits).view(np.int32))
-    return cat_bits.to(device=dev).contiguous()
-
-
 def calibrate_rerank(cat_bits, n_cat, cand_idx, cand_score, profile, k, calibration):
     """Greedy calibrated re-rank of candidate lists (anirec_calibrate_rerank): list l holds the rows
     ``cand_idx[l]`` of ``cat_bits`` ([n_rows, ceil(n_cat/32)] category bit words: ``components.category_table``; -1 = an
@@ -736,25 +760,17 @@ def calibrate_rerank(cat_bits, n_cat, cand_idx, cand_score, profile, k, calibrat
     n_cat, n_cand, k, calibration = check_calibrate(n_cat, cand_idx.shape[1], k, calibration)
     _calibrate_tables("calibrate_rerank", cat_bits, n_cat, cand_idx, profile)
     _need_gpu()
-    lib = _lib.load()
     dev = cand_idx.device if cand_idx.is_cuda else torch.device("cuda")
-    cat = _cat_words(cat_bits, dev)
+    cat = _bit_words(cat_bits, dev)
     ci, cs, pr = _i32(cand_idx, dev), _f32(cand_score, dev), _i32(profile, dev)
     n_lists = int(ci.shape[0])
-    idx = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
-    pos = torch.empty(n_lists, k, dtype=torch.int32, device=dev)
-    score = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
-    pen = torch.empty(n_lists, k, dtype=torch.float32, device=dev)
+    res = _rerank_outputs(dev, n_lists, k)
     if n_lists == 0:
-        return idx, pos, score, pen
-    err = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_calibrate_rerank(_lib.ptr(cat), int(cat.shape[0]), n_cat, _lib.ptr(ci), _lib.ptr(cs),
-                                           _lib.ptr(pr), n_lists, n_cand, k, calibration, _lib.ptr(idx), _lib.ptr(pos),
-                                           _lib.ptr(score), _lib.ptr(pen), _lib.ptr(err), _stream()),
-               "anirec_calibrate_rerank")
-    if int(err.item()):
-        raise ValueError("calibrate_rerank: candidate index out of range, or a profile entry outside 0 .. 2**24")
-    return idx, pos, score, pen
+        return res
+    err = _err_flag(dev)
+    _call("anirec_calibrate_rerank", cat, int(cat.shape[0]), n_cat, ci, cs, pr, n_lists, n_cand, k, calibration, *res, err)
+    return _finish(res, err, True,
+                   "calibrate_rerank: candidate index out of range, or a profile entry outside 0 .. 2**24")
 
 
 def list_calibration(cat_bits, n_cat, lists, profile):
@@ -773,23 +789,17 @@ def list_calibration(cat_bits, n_cat, lists, profile):
     if not 1 <= k <= _lib.CALIBRATE_MAX_CAND:
         raise ValueError("list_calibration: %d slots per list, 1 .. %d" % (k, _lib.CALIBRATE_MAX_CAND))
     _need_gpu()
-    lib = _lib.load()
     dev = lists.device if torch.is_tensor(lists) and lists.is_cuda else torch.device("cuda")
-    cat = _cat_words(cat_bits, dev)
+    cat = _bit_words(cat_bits, dev)
     li, pr = _i32(lists, dev), _i32(profile, dev)
     n_lists = int(li.shape[0])
-    num = torch.empty(n_lists, dtype=torch.int64, device=dev)
-    den = torch.empty(n_lists, dtype=torch.int64, device=dev)
-    pen = torch.empty(n_lists, dtype=torch.float32, device=dev)
+    num, den, pen = _outputs(dev, (torch.int64, n_lists), (torch.int64, n_lists), (torch.float32, n_lists))
     if n_lists == 0:
         return pen, num, den
-    err = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_list_calibration(_lib.ptr(cat), int(cat.shape[0]), n_cat, _lib.ptr(li), _lib.ptr(pr), n_lists,
-                                           k, _lib.ptr(num), _lib.ptr(den), _lib.ptr(pen), _lib.ptr(err), _stream()),
-               "anirec_list_calibration")
-    if int(err.item()):
-        raise ValueError("list_calibration: list index out of range, or a profile entry outside 0 .. 2**24")
-    return pen, num, den
+    err = _err_flag(dev)
+    _call("anirec_list_calibration", cat, int(cat.shape[0]), n_cat, li, pr, n_lists, k, num, den, pen, err)
+    return _finish((pen, num, den), err, True,
+                   "list_calibration: list index out of range, or a profile entry outside 0 .. 2**24")
 
 
 def check_explain(width, k, m):
@@ -822,7 +832,6 @@ def explain_lists(What, list_idx, offsets, hist_idx, hist_weight, m):
     if What.shape[0] < 1:
         raise ValueError("explain_lists: What has no rows")
     _need_gpu()
-    lib = _lib.load()
     assert _width(What) == dim
     dev = What.device
     li = _i32(list_idx, dev)
@@ -831,22 +840,16 @@ def explain_lists(What, list_idx, offsets, hist_idx, hist_weight, m):
     hi, hw = _i32(hist_idx, dev), _f32(hist_weight, dev)
     if off.dim() != 1 or off.numel() != n_lists + 1 or hi.dim() != 1 or hi.shape != hw.shape:
         raise ValueError("explain_lists: offsets must be [n_lists + 1], hist_idx and hist_weight one entry per rating")
-    if int(off[0]) != 0 or int(off[-1]) != hi.numel() or (n_lists and bool((off[1:] < off[:-1]).any())):
-        raise ValueError("explain_lists: offsets must rise from 0 to the number of history entries")
-    pos = torch.empty(n_lists, k, m, dtype=torch.int32, device=dev)
-    sim = torch.empty(n_lists, k, m, dtype=torch.float32, device=dev)
-    contrib = torch.empty(n_lists, k, m, dtype=torch.float32, device=dev)
+    _check_csr(off, n_lists, hi.numel(), "explain_lists", "history entries")
+    res = _outputs(dev, (torch.int32, n_lists, k, m), (torch.float32, n_lists, k, m), (torch.float32, n_lists, k, m))
     if n_lists == 0:
-        return pos, sim, contrib
-    err = torch.empty(1, dtype=torch.int32, device=dev)
+        return res
+    err = _err_flag(dev)
     off_d = off.to(dev)
-    _lib.check(lib.anirec_explain_lists(_lib.ptr(What), dim, What.shape[0], _lib.ptr(li), n_lists, k, _lib.ptr(off_d),
-                                        _lib.ptr(hi) if hi.numel() else None, _lib.ptr(hw) if hw.numel() else None, m,
-                                        _lib.ptr(pos), _lib.ptr(sim), _lib.ptr(contrib), _lib.ptr(err), _stream()),
-               "anirec_explain_lists")
-    if int(err.item()):
-        raise ValueError("explain_lists: list or history index out of range")
-    return pos, sim, contrib
+    # (an empty history is NULL to the library, not the address of a zero-element tensor)
+    _call("anirec_explain_lists", What, dim, What.shape[0], li, n_lists, k, off_d, hi if hi.numel() else None,
+          hw if hw.numel() else None, m, *res, err)
+    return _finish(res, err, True, "explain_lists: list or history index out of range")
 
 
 def check_kmeans(dim, k, max_iter=1):
@@ -879,16 +882,13 @@ def kmeans_assign(What, C):
     _kmeans_tables(What, C, "kmeans_assign")
     dim, k, _ = check_kmeans(What.shape[1], C.shape[0])
     _need_gpu()
-    lib = _lib.load()
     dev = What.device
     C = _f32(C, dev)
     assert _width(What, C) == dim
     What = What.contiguous()
     n = int(What.shape[0])
-    assign = torch.empty(n, dtype=torch.int32, device=dev)
-    sim = torch.empty(n, dtype=torch.float32, device=dev)
-    _lib.check(lib.anirec_kmeans_assign(_lib.ptr(What), dim, n, _lib.ptr(C), k, _lib.ptr(assign), _lib.ptr(sim), _stream()),
-               "anirec_kmeans_assign")
+    assign, sim = _outputs(dev, (torch.int32, n), (torch.float32, n))
+    _call("anirec_kmeans_assign", What, dim, n, C, k, assign, sim)
     return assign, sim
 
 
@@ -903,20 +903,14 @@ def kmeans_fit(What, C0, max_iter=50):
     _kmeans_tables(What, C0, "kmeans_fit")
     dim, k, max_iter = check_kmeans(What.shape[1], C0.shape[0], max_iter)
     _need_gpu()
-    lib = _lib.load()
     dev = What.device
     C = _f32(C0, dev).clone()
     assert _width(What, C) == dim
     What = What.contiguous()
     n = int(What.shape[0])
-    assign = torch.empty(n, dtype=torch.int32, device=dev)
-    sim = torch.empty(n, dtype=torch.float32, device=dev)
-    count = torch.empty(k, dtype=torch.int32, device=dev)
-    info = torch.empty(2, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(lib.anirec_kmeans_workspace_bytes(n, k, dim)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_kmeans_fit(_lib.ptr(What), dim, n, _lib.ptr(C), k, max_iter, _lib.ptr(assign), _lib.ptr(sim),
-                                     _lib.ptr(count), _lib.ptr(info), _lib.ptr(ws), ws.numel(), _stream()),
-               "anirec_kmeans_fit")
+    assign, sim, count, info = _outputs(dev, (torch.int32, n), (torch.float32, n), (torch.int32, k), (torch.int32, 2))
+    ws = _workspace(None, dev, "anirec_kmeans_workspace_bytes", n, k, dim)
+    _call("anirec_kmeans_fit", What, dim, n, C, k, max_iter, assign, sim, count, info, ws, ws.numel())
     iters, converged = info.tolist()
     return C, assign, sim, count, int(iters), bool(converged)
 
@@ -963,7 +957,6 @@ def cooc_scores(bits, n_users, queries, measure="cosine", shrink=0.0, min_suppor
     ``check=False`` the device flag is returned as a fifth element instead and nothing synchronises."""
     m, shrink, min_support = check_cooc(measure, shrink, min_support)
     _need_gpu()
-    lib = _lib.load()
     bits, n_users = _item_bits(bits, n_users)
     dev = bits.device
     n = int(bits.shape[0])
@@ -973,20 +966,13 @@ def cooc_scores(bits, n_users, queries, measure="cosine", shrink=0.0, min_suppor
     cnt = torch.empty(nq, n, dtype=torch.int32, device=dev) if count else None
     ex = torch.empty(nq, (n + 31) // 32, dtype=torch.int32, device=dev) if excl else None
     pp = torch.empty(n, dtype=torch.int32, device=dev) if pop else None
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    if workspace is None:
-        workspace = torch.empty(int(lib.anirec_cooc_workspace_bytes(n, nq)), dtype=torch.uint8, device=dev)
+    err = _err_flag(dev, handed_on=True)
+    ws = _workspace(workspace, dev, "anirec_cooc_workspace_bytes", n, nq)
     if nq == 0 and pop:       # the call enqueues nothing for no query: the pop vector through one throw-away query
-        return (sim, cnt, ex, cooc_scores(bits, n_users, [0], measure, shrink, min_support, pop=True)[3]) + \
-            (() if check else (err,))
-    _lib.check(lib.anirec_cooc_scores(_lib.ptr(bits), n, n_users, _lib.ptr(q), nq, m, shrink, min_support, _lib.ptr(sim),
-                                      _lib.ptr(cnt), _lib.ptr(ex), _lib.ptr(pp), _lib.ptr(err), _lib.ptr(workspace),
-                                      workspace.numel(), _stream()), "anirec_cooc_scores")
-    if not check:
-        return sim, cnt, ex, pp, err
-    if int(err.item()):
-        raise ValueError("cooc_scores: query item out of range")
-    return sim, cnt, ex, pp
+        pp = cooc_scores(bits, n_users, [0], measure, shrink, min_support, pop=True)[3]
+        return (sim, cnt, ex, pp) if check else (sim, cnt, ex, pp, err)     # (the flag is clear: nothing to read)
+    _call("anirec_cooc_scores", bits, n, n_users, q, nq, m, shrink, min_support, sim, cnt, ex, pp, err, ws, ws.numel())
+    return _finish((sim, cnt, ex, pp), err, check, "cooc_scores: query item out of range")
 
 
 def rows_topk(scores, k, n=None, self_idx=None, keep=None, wbits=None, workspace=None):
@@ -995,36 +981,26 @@ def rows_topk(scores, k, n=None, self_idx=None, keep=None, wbits=None, workspace
     ``keep[j] == 0`` or bit j of ``wbits[t]`` ([nq, ceil(n/32)]) is set.  Returns (idx int32 [nq, k], score fp32 [nq, k])
     in predict_topk's order (larger first, +0 above -0, NaN last, ties by index), padded with -1 / NaN; any k >= 1."""
     _need_gpu()
-    lib = _lib.load()
-    assert isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2, \
-        "fp32 [nq, ld] device score rows"
+    sc = _score_rows(scores, "[nq, ld]")
     k = int(k)
     if k < 1:
         raise ValueError("k must be >= 1")
-    sc = scores.contiguous()
     dev = sc.device
     nq, ld = int(sc.shape[0]), int(sc.shape[1])
     n = ld if n is None else int(n)
     if not 1 <= n <= ld:
         raise ValueError("rows_topk: n = %d must be in 1 .. %d (the row length)" % (n, ld))
-    out_i = torch.empty(nq, k, dtype=torch.int32, device=dev)
-    out_s = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    out_i, out_s = _outputs(dev, (torch.int32, nq, k), (torch.float32, nq, k))
     if nq == 0:
         return out_i, out_s
     se = None
     if self_idx is not None:
         se = _i32(self_idx, dev)
         assert se.shape == (nq,)
-    kp = None
-    if keep is not None:
-        kp = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous()
-        assert kp.numel() == n
+    kp = _keep_bytes(keep, n, dev)
     wb = _watched(wbits, nq, n, dev)
-    if workspace is None:
-        workspace = torch.empty(int(lib.anirec_rows_topk_workspace_bytes(n, nq, k)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_rows_topk(_lib.ptr(sc), ld, n, nq, _lib.ptr(se), _lib.ptr(kp), _lib.ptr(wb), k, _lib.ptr(out_i),
-                                    _lib.ptr(out_s), _lib.ptr(workspace), workspace.numel(), _stream()),
-               "anirec_rows_topk")
+    ws = _workspace(workspace, dev, "anirec_rows_topk_workspace_bytes", n, nq, k)
+    _call("anirec_rows_topk", sc, ld, n, nq, se, kp, wb, k, out_i, out_s, ws, ws.numel())
     return out_i, out_s
 
 
@@ -1034,10 +1010,7 @@ def rows_rank(scores, target_row, target_anime, watched_bits=None):
     [n_t]: the position of the target in ``rows_topk(scores, k=n_anime, wbits=watched_bits with the target's bit
     cleared)`` of its row.  Raises ValueError on a target_row or target_anime out of range."""
     _need_gpu()
-    lib = _lib.load()
-    assert isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2, \
-        "fp32 [n_users, n_anime] device score rows"
-    sc = scores.contiguous()
+    sc = _score_rows(scores, "[n_users, n_anime]")
     dev = sc.device
     tr, ta = _i32(target_row, dev), _i32(target_anime, dev)
     assert tr.dim() == 1 and tr.shape == ta.shape
@@ -1050,13 +1023,8 @@ def rows_rank(scores, target_row, target_anime, watched_bits=None):
     if n_q == 0:
         raise ValueError("rows_rank: target_row out of range (no rows)")
     wb = _watched(watched_bits, n_q, n_a, dev)
-
-    def batch(t, cnt, err):
-        return lib.anirec_rows_rank(_lib.ptr(sc), n_a, n_a, _lib.ptr(wb), n_q, _lib.ptr(tr[t]), _lib.ptr(ta[t]), cnt,
-                                    _lib.ptr(rank[t]), err, _stream())
-    if _rank_batches(n_t, dev, "anirec_rows_rank", batch):
-        raise ValueError("rows_rank: target_row or target_anime out of range")
-    return rank
+    return _rank_batches("anirec_rows_rank", n_t, rank, dev, "rows_rank: target_row or target_anime out of range",
+                         lambda t, cnt, err: (sc, n_a, n_a, wb, n_q, tr[t], ta[t], cnt, rank[t], err))
 
 
 def itemknn_scores(nbr_idx, nbr_sim, offsets, hist_idx, hist_w=None, workspace=None, check=True):
@@ -1068,7 +1036,6 @@ def itemknn_scores(nbr_idx, nbr_sim, offsets, hist_idx, hist_w=None, workspace=N
     that is not inside the history, a weight or similarity that is not finite or |w sim| > 1024; with ``check=False``
     returns (out, device flag) and nothing synchronises."""
     _need_gpu()
-    lib = _lib.load()
     assert isinstance(nbr_idx, torch.Tensor) and nbr_idx.is_cuda and nbr_idx.dim() == 2 and nbr_idx.shape == nbr_sim.shape
     dev = nbr_idx.device
     ni, ns = _i32(nbr_idx, dev), _f32(nbr_sim, dev)
@@ -1085,18 +1052,12 @@ def itemknn_scores(nbr_idx, nbr_sim, offsets, hist_idx, hist_w=None, workspace=N
         assert hw.shape == hi.shape
     n_l, n_h = int(off.numel()) - 1, int(hi.numel())
     out = torch.empty(n_l, n, dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    err = _err_flag(dev, handed_on=True)
     if n_l:
-        if workspace is None:
-            workspace = torch.empty(int(lib.anirec_itemknn_workspace_bytes(n, n_l)), dtype=torch.uint8, device=dev)
-        _lib.check(lib.anirec_itemknn_scores(_lib.ptr(ni), _lib.ptr(ns), n, K, _lib.ptr(off), _lib.ptr(hi), _lib.ptr(hw),
-                                             n_l, n_h, _lib.ptr(out), _lib.ptr(err), _lib.ptr(workspace),
-                                             workspace.numel(), _stream()), "anirec_itemknn_scores")
-    if not check:
-        return out, err
-    if int(err.item()):
-        raise ValueError("itemknn_scores: history, neighbour table or offsets out of range, or an unusable term")
-    return out
+        ws = _workspace(workspace, dev, "anirec_itemknn_workspace_bytes", n, n_l)
+        _call("anirec_itemknn_scores", ni, ns, n, K, off, hi, hw, n_l, n_h, out, err, ws, ws.numel())
+    return _finish(out, err, check,
+                   "itemknn_scores: history, neighbour table or offsets out of range, or an unusable term")
 
 
 COVER_MAX_PICKS = _lib.COVER_MAX_PICKS
@@ -1120,18 +1081,6 @@ def check_cover(m, depth=1):
     return mi, min(di, mi + 1)
 
 
-def _cover_workspace(nbytes, dev):
-    """The greedy's workspace, kept between calls (grow-only, one per device and stream; ``release_workspaces`` drops
-    it): the call needs nothing of what it held."""
-    key = (torch.device(dev).index, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _COVER_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        _COVER_WS.pop(key, None)
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        _COVER_WS[key] = ws
-    return ws
-
-
 def cover_greedy(bits, n_users, m, depth=1, open_bits=None, keep=None):
     """A greedy maximum-coverage list (anirec_cover_greedy): ``bits`` int32 [n_items, ceil(n_users/32)]
     on the device (``recs.item_bits``).  ``m`` picks; each is the candidate (``keep[i] != 0``, not picked yet) that the
@@ -1142,27 +1091,19 @@ def cover_greedy(bits, n_users, m, depth=1, open_bits=None, keep=None):
     the device; nothing synchronises.  Exact integer counts: bit-reproducible.  ValueError as ``check_cover``."""
     m, depth = check_cover(m, depth)
     _need_gpu()
-    lib = _lib.load()
     bits, n_users = _item_bits(bits, n_users)
     dev = bits.device
     n, W = int(bits.shape[0]), int(bits.shape[1])
     ob = None
     if open_bits is not None:
-        ob = torch.as_tensor(open_bits, device=dev).to(torch.int32).contiguous().reshape(-1)
+        ob = _i32(open_bits, dev).reshape(-1)
         if ob.numel() != W:
             raise ValueError("cover_greedy: open_bits holds ceil(n_users/32) = %d words (got %d)" % (W, ob.numel()))
-    kp = None
-    if keep is not None:
-        kp = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous().reshape(-1)
-        if kp.numel() != n:
-            raise ValueError("cover_greedy: keep holds one byte per item (%d, got %d)" % (n, kp.numel()))
-    pick = torch.empty(m, dtype=torch.int32, device=dev)
-    gain = torch.empty(m, dtype=torch.int32, device=dev)
-    info = torch.empty(4, dtype=torch.int32, device=dev)
-    ws = _cover_workspace(int(lib.anirec_cover_workspace_bytes(n, n_users)), dev)
-    _lib.check(lib.anirec_cover_greedy(_lib.ptr(bits), n, n_users, _lib.ptr(ob), _lib.ptr(kp), depth, m, _lib.ptr(pick),
-                                       _lib.ptr(gain), _lib.ptr(info), _lib.ptr(ws), ws.numel(), _stream()),
-               "anirec_cover_greedy")
+    kp = _keep_bytes(keep, n, dev, "cover_greedy")
+    pick, gain, info = _outputs(dev, (torch.int32, m), (torch.int32, m), (torch.int32, 4))
+    # kept between calls (``release_workspaces`` drops it): the call needs nothing of what it held
+    ws = _cached_workspace(_COVER_WS, int(_lib.load().anirec_cover_workspace_bytes(n, n_users)), dev)
+    _call("anirec_cover_greedy", bits, n, n_users, ob, kp, depth, m, pick, gain, info, ws, ws.numel())
     return pick, gain, info
 
 
@@ -1172,19 +1113,13 @@ def cover_levels(bits, n_users, picks, check=True):
     ValueError for any other entry out of range; with ``check=False`` returns (level, device flag) and nothing
     synchronises."""
     _need_gpu()
-    lib = _lib.load()
     bits, n_users = _item_bits(bits, n_users)
     dev = bits.device
     pk = _i32(picks, dev).reshape(-1)
     level = torch.empty(n_users, dtype=torch.int32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_cover_levels(_lib.ptr(bits), int(bits.shape[0]), n_users, _lib.ptr(pk), int(pk.numel()),
-                                       _lib.ptr(level), _lib.ptr(err), _stream()), "anirec_cover_levels")
-    if not check:
-        return level, err
-    if int(err.item()):
-        raise ValueError("cover_levels: pick out of range")
-    return level
+    err = _err_flag(dev, handed_on=True)
+    _call("anirec_cover_levels", bits, int(bits.shape[0]), n_users, pk, int(pk.numel()), level, err)
+    return _finish(level, err, check, "cover_levels: pick out of range")
 
 
 FUSE_MAX_SYS = _lib.FUSE_MAX_SYS
@@ -1249,7 +1184,6 @@ def fuse_rows(rows, weights=None, method="rrf", rrf_c=60, n=None, wbits=None, ke
     if min(lens) < n:
         raise ValueError("fuse_rows: n = %d must be in 1 .. %d (the shortest row)" % (n, min(lens)))
     _need_gpu()
-    lib = _lib.load()
     dev = rows[0].device
     if mats:
         nq = int(mats[0].shape[0])
@@ -1261,11 +1195,7 @@ def fuse_rows(rows, weights=None, method="rrf", rrf_c=60, n=None, wbits=None, ke
         if r.dim() == 2 and int(r.shape[0]) != nq:
             raise ValueError("fuse_rows: every system holds the same number of rows (%d, got %d)" % (nq, r.shape[0]))
         held.append(r.contiguous())
-    kp = None
-    if keep is not None:
-        kp = torch.as_tensor(keep, device=dev).to(torch.uint8).contiguous().reshape(-1)
-        if kp.numel() != n:
-            raise ValueError("fuse_rows: keep holds one byte per item (%d, got %d)" % (n, kp.numel()))
+    kp = _keep_bytes(keep, n, dev, "fuse_rows")
     wb = _watched(wbits, nq, n, dev)
     out = torch.empty(nq, n, dtype=torch.float32, device=dev)
     if nq == 0:
@@ -1273,8 +1203,7 @@ def fuse_rows(rows, weights=None, method="rrf", rrf_c=60, n=None, wbits=None, ke
     ptrs = (C.c_void_p * n_sys)(*[r.data_ptr() for r in held])
     lds = (C.c_int64 * n_sys)(*[int(r.shape[1]) if r.dim() == 2 else 0 for r in held])
     wts = (C.c_float * n_sys)(*ws)
-    _lib.check(lib.anirec_fuse_rows(ptrs, lds, n_sys, n, nq, _lib.ptr(wb), _lib.ptr(kp), wts, m, rrf_c, _lib.ptr(out), n,
-                                    _stream()), "anirec_fuse_rows")
+    _call("anirec_fuse_rows", ptrs, lds, n_sys, n, nq, wb, kp, wts, m, rrf_c, out, n)
     return out
 
 
@@ -1309,7 +1238,6 @@ def rank_gain_rows(ranks, target_unit, n_units, gain, check=True):
     rank < 0 or >= n_gain gaining 0; the last column the unit's number of targets.  Raises ValueError for a
     target_unit out of range; with ``check=False`` returns (out, device flag) and nothing synchronises."""
     _need_gpu()
-    lib = _lib.load()
     assert isinstance(ranks, torch.Tensor) and ranks.is_cuda and ranks.dim() == 2, "int32 [n_sys, n_t] device ranks"
     dev = ranks.device
     rk = _i32(ranks, dev)
@@ -1325,14 +1253,9 @@ def rank_gain_rows(ranks, target_unit, n_units, gain, check=True):
     if int(tu.numel()) != n_t:
         raise ValueError("rank_gain_rows: target_unit must hold one unit per target")
     out = torch.empty(n_units, n_sys * n_metric + 1, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_rank_gain_rows(_lib.ptr(rk), n_sys, n_t, _lib.ptr(tu), n_units, _lib.ptr(g), n_metric, n_gain,
-                                         _lib.ptr(out), _lib.ptr(err), _stream()), "anirec_rank_gain_rows")
-    if not check:
-        return out, err
-    if int(err.item()):
-        raise ValueError("rank_gain_rows: target_unit out of range")
-    return out
+    err = _err_flag(dev, handed_on=True)
+    _call("anirec_rank_gain_rows", rk, n_sys, n_t, tu, n_units, g, n_metric, n_gain, out, err)
+    return _finish(out, err, check, "rank_gain_rows: target_unit out of range")
 
 
 def boot_sums(values, unit_key, seed, n_rep, thr, workspace=None, check=True):
@@ -1344,7 +1267,6 @@ def boot_sums(values, unit_key, seed, n_rep, thr, workspace=None, check=True):
     ``check=False`` returns (out, device flag) and nothing synchronises."""
     n_rep, table, n_thr = check_boot(n_rep, thr)
     _need_gpu()
-    lib = _lib.load()
     assert isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.int64 and values.dim() == 2, \
         "int64 [n_units, n_col] device values"
     dev = values.device
@@ -1356,18 +1278,11 @@ def boot_sums(values, unit_key, seed, n_rep, thr, workspace=None, check=True):
     if int(key.numel()) != n_units:
         raise ValueError("boot_sums: unit_key must hold one key per row of values")
     out = torch.empty(n_rep + 1, n_col, dtype=torch.int64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    if workspace is None:
-        workspace = torch.empty(int(lib.anirec_boot_workspace_bytes(n_units, n_col, n_rep)), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_boot_sums(_lib.ptr(v), _lib.ptr(key), n_units, n_col, int(seed) & 0xFFFFFFFF, n_rep, table,
-                                    n_thr, _lib.ptr(out), _lib.ptr(err), _lib.ptr(workspace), workspace.numel(),
-                                    _stream()), "anirec_boot_sums")
-    if not check:
-        return out, err
-    if int(err.item()):
-        raise ValueError("boot_sums: a value is negative or >= %d (2**62 / (max(n_thr, 1) * n_units)): the sums would "
-                         "not be exact" % boot_limit(n_units, n_thr))
-    return out
+    err = _err_flag(dev, handed_on=True)
+    ws = _workspace(workspace, dev, "anirec_boot_workspace_bytes", n_units, n_col, n_rep)
+    _call("anirec_boot_sums", v, key, n_units, n_col, int(seed) & 0xFFFFFFFF, n_rep, table, n_thr, out, err, ws, ws.numel())
+    return _finish(out, err, check, "boot_sums: a value is negative or >= %d (2**62 / (max(n_thr, 1) * n_units)): the sums "
+                   "would not be exact" % boot_limit(n_units, n_thr))
 
 
 def boot_weights(unit_key, seed, n_rep, thr, device="cuda:0"):
@@ -1375,12 +1290,10 @@ def boot_weights(unit_key, seed, n_rep, thr, device="cuda:0"):
     b = 1 .. n_rep gives the units of ``unit_key`` — what ``boot_sums`` multiplies by, for figures that are no sums."""
     n_rep, table, n_thr = check_boot(n_rep, thr)
     _need_gpu()
-    lib = _lib.load()
     dev = unit_key.device if isinstance(unit_key, torch.Tensor) and unit_key.is_cuda else torch.device(device)
     key = _i32(unit_key, dev).reshape(-1)
     out = torch.empty(n_rep, int(key.numel()), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_boot_weights(_lib.ptr(key), int(key.numel()), int(seed) & 0xFFFFFFFF, n_rep, table, n_thr,
-                                       _lib.ptr(out), _stream()), "anirec_boot_weights")
+    _call("anirec_boot_weights", key, int(key.numel()), int(seed) & 0xFFFFFFFF, n_rep, table, n_thr, out)
     return out
 
 
@@ -1406,17 +1319,14 @@ def als_gram(Y, workspace=None):
     product is taken in fp64, where it is exact, and added in fp64 in a fixed order (chunks of ALS_GRAM_CHUNK rows in row
     order, the chunks in chunk order); the sum is rounded once to fp32.  Returns fp32 [width, width]."""
     _need_gpu()
-    lib = _lib.load()
     dim = _width(Y)
     Y = Y.contiguous()
     n = int(Y.shape[0])
     if n < 1:
         raise ValueError("als_gram: Y has no rows")
     G = torch.empty(dim, dim, dtype=torch.float32, device=Y.device)
-    if workspace is None:
-        workspace = torch.empty(int(lib.anirec_als_gram_workspace_bytes(n, dim)), dtype=torch.uint8, device=Y.device)
-    _lib.check(lib.anirec_als_gram(_lib.ptr(Y), n, dim, _lib.ptr(G), _lib.ptr(workspace), workspace.numel(), _stream()),
-               "anirec_als_gram")
+    ws = _workspace(workspace, Y.device, "anirec_als_gram_workspace_bytes", n, dim)
+    _call("anirec_als_gram", Y, n, dim, G, ws, ws.numel())
     return G
 
 
@@ -1432,7 +1342,6 @@ def als_half_sweep(Y, G, offsets, idx, X, lam, cg_steps, excess=None, alpha=1.0,
     (rows, row_loss, device flag) and nothing synchronises beyond the offsets' own checks."""
     dim, cg_steps, lam, alpha = check_als(Y.shape[1], cg_steps, lam, alpha)
     _need_gpu()
-    lib = _lib.load()
     assert _width(Y, G, X) == dim and G.shape[0] == dim
     dev = Y.device
     Y, G = Y.contiguous(), G.contiguous()
@@ -1448,21 +1357,14 @@ def als_half_sweep(Y, G, offsets, idx, X, lam, cg_steps, excess=None, alpha=1.0,
         if ex.numel() and not bool((torch.isfinite(ex) & (ex >= 0)).all()):
             raise ValueError("als_half_sweep: excess must be finite and >= 0")
     loss = torch.empty(n_rows, dtype=torch.float32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    err = _err_flag(dev, handed_on=True)
     if n_rows:
-        # the offsets are checked against the entries here, so that the kernel reads no entry past the list's end
-        bad = (off[0] != 0) | (off[-1] != ix.numel()) | (off[1:] < off[:-1]).any()
-        if bool(bad):
-            raise ValueError("als_half_sweep: offsets must rise from 0 to the number of entries")
+        # the offsets are checked against the entries here (on the device, where they are), so that the kernel reads no
+        # entry past the list's end
+        _check_csr(off, n_rows, ix.numel(), "als_half_sweep", "entries")
         order = torch.argsort(off[1:] - off[:-1], descending=True, stable=True).to(torch.int32)
-        _lib.check(lib.anirec_als_half_sweep(_lib.ptr(Y), n_other, dim, _lib.ptr(G), _lib.ptr(off), _lib.ptr(ix),
-                                             _lib.ptr(ex), alpha, _lib.ptr(order), _lib.ptr(rows), n_rows, lam, cg_steps,
-                                             _lib.ptr(loss), _lib.ptr(err), _stream()), "anirec_als_half_sweep")
-    if not check:
-        return rows, loss, err
-    if int(err.item()):
-        raise ValueError("als_half_sweep: index out of range")
-    return rows, loss
+        _call("anirec_als_half_sweep", Y, n_other, dim, G, off, ix, ex, alpha, order, rows, n_rows, lam, cg_steps, loss, err)
+    return _finish((rows, loss), err, check, "als_half_sweep: index out of range")
 
 
 def dot_scores(Q, Y, out=None):
@@ -1471,7 +1373,6 @@ def dot_scores(Q, Y, out=None):
     ``rows_rank`` take.  ``Q`` [n_q, width], ``Y`` [n, width] on the device; ``out``: an fp32 [n_q, ld >= n] device
     tensor to write the first n columns of, or None for a fresh [n_q, n].  Returns it."""
     _need_gpu()
-    lib = _lib.load()
     dim = _width(Q, Y)
     Q, Y = Q.contiguous(), Y.contiguous()
     n_q, n = int(Q.shape[0]), int(Y.shape[0])
@@ -1481,8 +1382,7 @@ def dot_scores(Q, Y, out=None):
         out = torch.empty(n_q, n, dtype=torch.float32, device=Q.device)
     assert out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous() and \
         out.shape[0] == n_q and out.shape[1] >= n, "out: contiguous fp32 [n_q, ld >= n]"
-    _lib.check(lib.anirec_dot_scores(_lib.ptr(Q), n_q, _lib.ptr(Y), n, dim, _lib.ptr(out), int(out.shape[1]), _stream()),
-               "anirec_dot_scores")
+    _call("anirec_dot_scores", Q, n_q, Y, n, dim, out, int(out.shape[1]))
     return out
 
 
@@ -1501,15 +1401,13 @@ def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     ai, rt = _i32(idx, dev), _f32(rating, dev)
     assert off.dim() == 1 and off.numel() >= 1 and ai.dim() == 1 and ai.shape == rt.shape
     n_new = int(off.numel()) - 1
-    if int(off[0]) != 0 or int(off[-1]) != ai.numel() or (n_new and bool((off[1:] < off[:-1]).any())):
-        raise ValueError("fold_in: offsets must rise from 0 to the number of ratings")
+    _check_csr(off, n_new, ai.numel(), "fold_in", "ratings")
     init_t = _f32(init, dev)
     if init_t.dim() == 1:
         init_t = init_t.expand(n_new, -1)
     init_t = init_t.contiguous()
     assert init_t.shape == (n_new, dim), "init: [n_new, width] or one row"
-    rows = torch.empty(n_new, dim, dtype=torch.float32, device=dev)
-    out_loss = torch.empty(n_new, dtype=torch.float32, device=dev)
+    rows, out_loss = _outputs(dev, (torch.float32, n_new, dim), (torch.float32, n_new))
     return loss_id, act_id, dim, steps, off, ai, rt, init_t, rows, out_loss
 
 
@@ -1523,23 +1421,17 @@ def fold_in(A, head, offsets, anime_idx, rating, init, lr=0.01, steps=100, l2=1e
     a user without ratings keeps the start row and gets a NaN loss.  A user's result does not depend on the other
     users of the call.  Raises ValueError on an anime index out of range or offsets that are not a CSR of the lists."""
     _need_gpu()
-    lib = _lib.load()
     loss_id, act_id, dim, steps, off, ai, rt, init_t, rows, out_loss = _fold_prepare(A, head, offsets, anime_idx, rating, init, steps, loss)
     dev, n_new = A.device, rows.shape[0]
     if n_new == 0:
         return rows, out_loss
     alpha = torch.as_tensor(adam_alphas(lr, 1, steps), device=dev)
-    err = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(lib.anirec_fold_in_workspace_bytes(A.shape[0], n_new, dim)), dtype=torch.uint8, device=dev)
-    h = _head_struct(head)
+    err = _err_flag(dev)
+    ws = _workspace(None, dev, "anirec_fold_in_workspace_bytes", A.shape[0], n_new, dim)
     off_d = off.to(dev)
-    _lib.check(lib.anirec_fold_in(_lib.ptr(A), dim, A.shape[0], C.byref(h), act_id, loss_id, float(l2),
-                                  _lib.ptr(off_d), _lib.ptr(ai), _lib.ptr(rt), n_new, _lib.ptr(init_t),
-                                  _lib.ptr(alpha), steps, _lib.ptr(rows), _lib.ptr(out_loss), _lib.ptr(err), _lib.ptr(ws),
-                                  ws.numel(), _stream()), "anirec_fold_in")
-    if int(err.item()):
-        raise ValueError("fold_in: anime index out of range")
-    return rows, out_loss
+    _call("anirec_fold_in", A, dim, A.shape[0], C.byref(_head_struct(head)), act_id, loss_id, float(l2), off_d, ai, rt,
+          n_new, init_t, alpha, steps, rows, out_loss, err, ws, ws.numel())
+    return _finish((rows, out_loss), err, True, "fold_in: anime index out of range")
 
 
 FOLD_CHUNK = 1024       # ANIREC_FOLD_CHUNK: ratings of one chunk of anirec_fold_in_split
@@ -1566,7 +1458,6 @@ def fold_in_split(T, head, offsets, idx, rating, init, lr=0.01, steps=100, l2=1e
     ``fold_in``; the chunk map is built here from the offsets.  A row's result does not depend on the other rows of
     the call, and a list of at most FOLD_CHUNK ratings gives the bits of ``fold_in``."""
     _need_gpu()
-    lib = _lib.load()
     loss_id, act_id, dim, steps, off, ai, rt, init_t, rows, out_loss = _fold_prepare(T, head, offsets, idx, rating, init, steps, loss)
     dev, n_new = T.device, rows.shape[0]
     if n_new == 0:
@@ -1575,19 +1466,12 @@ def fold_in_split(T, head, offsets, idx, rating, init, lr=0.01, steps=100, l2=1e
     n_chunks = int(c_off[-1])
     c_off_d, c_row_d = torch.as_tensor(c_off, device=dev), torch.as_tensor(c_row, device=dev)
     alpha = torch.as_tensor(adam_alphas(lr, 1, steps), device=dev)
-    err = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(lib.anirec_fold_in_split_workspace_bytes(T.shape[0], n_new, n_chunks, dim)), dtype=torch.uint8,
-                     device=dev)
-    h = _head_struct(head)
+    err = _err_flag(dev)
+    ws = _workspace(None, dev, "anirec_fold_in_split_workspace_bytes", T.shape[0], n_new, n_chunks, dim)
     off_d = off.to(dev)
-    _lib.check(lib.anirec_fold_in_split(_lib.ptr(T), dim, T.shape[0], C.byref(h), act_id, loss_id, float(l2),
-                                        _lib.ptr(off_d), _lib.ptr(ai), _lib.ptr(rt), n_new, _lib.ptr(c_off_d),
-                                        _lib.ptr(c_row_d), n_chunks, _lib.ptr(init_t), _lib.ptr(alpha), steps,
-                                        _lib.ptr(rows), _lib.ptr(out_loss), _lib.ptr(err), _lib.ptr(ws), ws.numel(),
-                                        _stream()), "anirec_fold_in_split")
-    if int(err.item()):
-        raise ValueError("fold_in: index out of range")
-    return rows, out_loss
+    _call("anirec_fold_in_split", T, dim, T.shape[0], C.byref(_head_struct(head)), act_id, loss_id, float(l2), off_d, ai, rt,
+          n_new, c_off_d, c_row_d, n_chunks, init_t, alpha, steps, rows, out_loss, err, ws, ws.numel())
+    return _finish((rows, out_loss), err, True, "fold_in: index out of range")
 
 
 def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fallback=True):
@@ -1595,32 +1479,26 @@ def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fal
     could not be proven complete are transparently re-run through the exact kernels.
     Returns (idx, p, n_fallback)."""
     _need_gpu()
-    lib = _lib.load()
     _need_128((U, A), "predict_topk")
     dev = U.device
     us = _i32(users, dev)
     n_a, n_q = A.shape[0], int(us.numel())
     if not (1 <= k <= MAX_TOPK - 1):
         raise ValueError("k must be in 1..%d" % (MAX_TOPK - 1))
-    out_i = torch.empty(n_q, k, dtype=torch.int32, device=dev)
-    out_p = torch.empty(n_q, k, dtype=torch.float32, device=dev)
+    out_i, out_p = _outputs(dev, (torch.int32, n_q, k), (torch.float32, n_q, k))
     if n_q == 0:
         return out_i, out_p, 0
     wb = _watched(watched_bits, n_q, n_a, dev)
-    h = _head_struct(head)
-    act = _head_act(head)
+    h = _head_args(head)
     bq = min(n_q, int(batch))
-    ws = torch.empty(int(lib.anirec_predict_topk_mfma_workspace_bytes(n_a, bq)), dtype=torch.uint8, device=dev)
+    ws = _workspace(None, dev, "anirec_predict_topk_mfma_workspace_bytes", n_a, bq)
     flags = torch.empty(bq, dtype=torch.int32, device=dev)
     n_fb = 0
     for q0 in range(0, n_q, bq):
         cnt = min(bq, n_q - q0)
         wq = wb[q0:q0 + cnt] if wb is not None else None
-        _lib.check(lib.anirec_predict_topk_mfma_act(_lib.ptr(U), _lib.ptr(A), n_a, _lib.ptr(us[q0:q0 + cnt]), cnt,
-                                                    C.byref(h), act, _lib.ptr(wq), int(k),
-                                                    _lib.ptr(out_i[q0:q0 + cnt]), _lib.ptr(out_p[q0:q0 + cnt]),
-                                                    _lib.ptr(flags), _lib.ptr(ws), ws.numel(), _stream()),
-                   "anirec_predict_topk_mfma")
+        _call("anirec_predict_topk_mfma_act", U, A, n_a, us[q0:q0 + cnt], cnt, *h, wq, int(k), out_i[q0:q0 + cnt],
+              out_p[q0:q0 + cnt], flags, ws, ws.numel())
         bad = torch.nonzero(flags[:cnt], as_tuple=False).flatten()
         n_fb += int(bad.numel())
         if bad.numel() and fallback:
@@ -1633,31 +1511,22 @@ def predict_topk_mfma(U, A, head, users, k, watched_bits=None, batch=131072, fal
 def adam_flat(w, m, v, g, alpha):
     """In-place Keras-2.12 Adam dense update of flat fp32 tensors (bit-exact vs the oracle)."""
     _need_gpu()
-    lib = _lib.load()
-    _lib.check(lib.anirec_adam_flat(_lib.ptr(w), _lib.ptr(m), _lib.ptr(v), _lib.ptr(g), w.numel(),
-                                    float(np.float32(alpha)), _stream()), "anirec_adam_flat")
+    _call("anirec_adam_flat", w, m, v, g, w.numel(), float(np.float32(alpha)))
 
 
 def opt_flat(kind, w, slot, g, rate):
     """In-place SGD / RMSprop / Adagrad update of flat fp32 tensors (``slot``: the RMSprop velocity / Adagrad
     accumulator, None for SGD; ``rate``: lr), the dense train step's element rule."""
     _need_gpu()
-    lib = _lib.load()
-    _lib.check(lib.anirec_opt_flat(OPTIMIZERS[resolve_optimizer(kind)], _lib.ptr(w), _lib.ptr(slot), _lib.ptr(g),
-                                   w.numel(), float(np.float32(rate)), _stream()), "anirec_opt_flat")
+    _call("anirec_opt_flat", OPTIMIZERS[resolve_optimizer(kind)], w, slot, g, w.numel(), float(np.float32(rate)))
 
 
 def gather_ratings(user_idx, anime_idx, rating, perm):
     """Epoch shuffle: returns the three rating columns permuted by ``perm`` (int64)."""
     _need_gpu()
-    lib = _lib.load()
     dev = user_idx.device
     perm = torch.as_tensor(perm, device=dev).to(torch.int64).contiguous()
     n = perm.numel()
-    uo = torch.empty(n, dtype=torch.int32, device=dev)
-    ao = torch.empty(n, dtype=torch.int32, device=dev)
-    to = torch.empty(n, dtype=torch.float32, device=dev)
-    _lib.check(lib.anirec_gather_ratings(_lib.ptr(user_idx), _lib.ptr(anime_idx), _lib.ptr(rating),
-                                         _lib.ptr(perm), n, _lib.ptr(uo), _lib.ptr(ao), _lib.ptr(to),
-                                         _stream()), "anirec_gather_ratings")
+    uo, ao, to = _outputs(dev, (torch.int32, n), (torch.int32, n), (torch.float32, n))
+    _call("anirec_gather_ratings", user_idx, anime_idx, rating, perm, n, uo, ao, to)
     return uo, ao, to

@@ -7,16 +7,11 @@ favourites the query user has not favourited, rank by count), similar_users.py:2
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from .ops import _bit_words, _call, _err_flag, _finish, _i32, _outputs, _workspace
 
 
 def _aligned(t):
@@ -30,33 +25,17 @@ def user_favourites(user_idx, anime_idx, rating, n_users, n_anime, percentile=80
     Bit a of row u is set iff rating(u, a) >= np.percentile(ratings of u, percentile)."""
     if not torch.cuda.is_available():
         raise _lib.AnirecError("no GPU: the anime_recommendations_amd recs path needs an MI355X")
-    lib = _lib.load()
     dev = user_idx.device
     u = _aligned(user_idx.to(torch.int32))
     a = _aligned(anime_idx.to(torch.int32))
     r = _aligned(rating.to(torch.float64))
     n = int(u.numel())
     ww = (int(n_anime) + 31) // 32
-    fav = torch.empty(int(n_users), ww, dtype=torch.int32, device=dev)
-    thr = torch.empty(int(n_users), dtype=torch.float64, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(lib.anirec_fav_workspace_bytes(n, int(n_users))), dtype=torch.uint8, device=dev)
-    _lib.check(lib.anirec_user_favourites(_lib.ptr(u), _lib.ptr(a), _lib.ptr(r), n, int(n_users), int(n_anime),
-                                          float(percentile), _lib.ptr(fav), _lib.ptr(thr), _lib.ptr(err),
-                                          _lib.ptr(ws), ws.numel(), _stream()), "anirec_user_favourites")
-    if int(err.item()):
-        raise ValueError("user / anime index out of range")
-    return fav, thr
-
-
-def _bit_words(x, shape, dev, what):
-    """32-bit words on ``dev``, contiguous, of the given shape (a NumPy uint32 / int32 array or an int32 tensor)."""
-    if not torch.is_tensor(x):
-        x = torch.from_numpy(np.ascontiguousarray(x).view(np.int32))
-    x = x.to(device=dev).contiguous()
-    if tuple(x.shape) != tuple(shape):
-        raise ValueError("%s: expected shape %s, got %s" % (what, tuple(shape), tuple(x.shape)))
-    return x
+    fav, thr = _outputs(dev, (torch.int32, int(n_users), ww), (torch.float64, int(n_users)))
+    err = _err_flag(dev)
+    ws = _workspace(None, dev, "anirec_fav_workspace_bytes", n, int(n_users))
+    _call("anirec_user_favourites", u, a, r, n, int(n_users), int(n_anime), float(percentile), fav, thr, err, ws, ws.numel())
+    return _finish((fav, thr), err, True, "user / anime index out of range")
 
 
 def user_recs(fav_bits, n_anime, query_users, sim_users, n_recs, exclude=None, keep=None):
@@ -67,28 +46,23 @@ def user_recs(fav_bits, n_anime, query_users, sim_users, n_recs, exclude=None, k
     ``exclude`` ([nq, ceil(n_anime/32)] bit words) replaces the query user's own favourite row as the skipped set
     (``query_users`` is then not read); ``keep`` ([ceil(n_anime/32)] bit words) limits the candidates to its set bits
     (anirec_user_recs_ex).  With both None this is anirec_user_recs."""
-    lib = _lib.load()
     dev = fav_bits.device
-    sim = torch.as_tensor(sim_users, device=dev).to(torch.int32).contiguous()
+    sim = _i32(sim_users, dev)
     nq, k_sim = int(sim.shape[0]), int(sim.shape[1])
-    out_a = torch.empty(nq, int(n_recs), dtype=torch.int32, device=dev)
-    out_c = torch.empty(nq, int(n_recs), dtype=torch.int32, device=dev)
+    out_a, out_c = _outputs(dev, (torch.int32, nq, int(n_recs)), (torch.int32, nq, int(n_recs)))
     if exclude is None and keep is None:
-        q = torch.as_tensor(query_users, device=dev).to(torch.int32).contiguous()
+        q = _i32(query_users, dev)
         assert q.numel() == nq
-        _lib.check(lib.anirec_user_recs(_lib.ptr(fav_bits), int(fav_bits.shape[0]), int(n_anime), _lib.ptr(q),
-                                        _lib.ptr(sim), nq, k_sim, int(n_recs), _lib.ptr(out_a), _lib.ptr(out_c),
-                                        _stream()), "anirec_user_recs")
+        _call("anirec_user_recs", fav_bits, int(fav_bits.shape[0]), int(n_anime), q, sim, nq, k_sim, int(n_recs), out_a, out_c)
         return out_a, out_c
     ww = (int(n_anime) + 31) // 32
     if exclude is None:         # a keep mask alone: the query users' own favourites are still skipped
         q = torch.as_tensor(query_users, device=dev).to(torch.long)
         exclude = fav_bits[q]
-    ex = _bit_words(exclude, (nq, ww), dev, "exclude")
-    kp = None if keep is None else _bit_words(keep, (ww,), dev, "keep")
-    _lib.check(lib.anirec_user_recs_ex(_lib.ptr(fav_bits), int(fav_bits.shape[0]), int(n_anime), _lib.ptr(sim), nq,
-                                       k_sim, _lib.ptr(ex), _lib.ptr(kp), int(n_recs), _lib.ptr(out_a),
-                                       _lib.ptr(out_c), _stream()), "anirec_user_recs_ex")
+    ex = _bit_words(exclude, dev, (nq, ww), "exclude")
+    kp = None if keep is None else _bit_words(keep, dev, (ww,), "keep")
+    _call("anirec_user_recs_ex", fav_bits, int(fav_bits.shape[0]), int(n_anime), sim, nq, k_sim, ex, kp, int(n_recs), out_a,
+          out_c)
     return out_a, out_c
 
 
@@ -96,7 +70,6 @@ def fave_profile(fav_bits, cat_bits, n_cat, users=None):
     """Favourite profiles: int32 [n_rows, n_cat], entry [r, c] = number of favourites of user ``users[r]`` (every
     user when None) whose category row (``cat_bits`` [n_anime, ceil(n_cat/32)] bit words) has bit c set.
     Raises ValueError on a user index out of range."""
-    lib = _lib.load()
     dev = fav_bits.device
     n_cat = int(n_cat)
     if not 1 <= n_cat <= 128:
@@ -104,19 +77,15 @@ def fave_profile(fav_bits, cat_bits, n_cat, users=None):
     n_users = int(fav_bits.shape[0])
     cw = (n_cat + 31) // 32
     n_anime = int(cat_bits.shape[0])
-    cat = _bit_words(cat_bits, (n_anime, cw), dev, "cat_bits")
+    cat = _bit_words(cat_bits, dev, (n_anime, cw), "cat_bits")
     if int(fav_bits.shape[1]) != (n_anime + 31) // 32:
         raise ValueError("fav_bits has %d words per row, cat_bits describes %d anime" % (int(fav_bits.shape[1]), n_anime))
-    u = None if users is None else torch.as_tensor(users, device=dev).to(torch.int32).contiguous().view(-1)
+    u = None if users is None else _i32(users, dev).view(-1)
     n_rows = n_users if u is None else int(u.numel())
     counts = torch.empty(n_rows, n_cat, dtype=torch.int32, device=dev)
-    err = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.anirec_fave_profile(_lib.ptr(fav_bits.contiguous()), n_users, n_anime, _lib.ptr(u), n_rows,
-                                       _lib.ptr(cat), n_cat, _lib.ptr(counts), _lib.ptr(err), _stream()),
-               "anirec_fave_profile")
-    if int(err.item()):
-        raise ValueError("fave_profile: user index out of range")
-    return counts
+    err = _err_flag(dev)
+    _call("anirec_fave_profile", fav_bits.contiguous(), n_users, n_anime, u, n_rows, cat, n_cat, counts, err)
+    return _finish(counts, err, True, "fave_profile: user index out of range")
 
 
 def ranking_metrics(rank, ks):
