@@ -13,7 +13,10 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libanirec.so")
-SOURCES = ["anirec_misc.hip", "anirec_train.hip", "anirec_infer.hip", "anirec_topk_mfma.hip", "anirec_predict_mfma.hip",
+# (all are compiled at once; the four with the most device code come first, so that they start first)
+SOURCES = ["anirec_train_head_metrics.hip", "anirec_train_head.hip", "anirec_train.hip", "anirec_train_eval.hip",
+           "anirec_train_util.hip", "anirec_train_run.hip",
+           "anirec_misc.hip", "anirec_infer.hip", "anirec_topk_mfma.hip", "anirec_predict_mfma.hip",
            "anirec_ingest.hip", "anirec_recs.hip", "anirec_foldin.hip", "anirec_mmr.hip", "anirec_listeval.hip",
            "anirec_explain.hip", "anirec_kmeans.hip", "anirec_cooc.hip", "anirec_calibrate.hip", "anirec_boot.hip",
            "anirec_als.hip", "anirec_cover.hip", "anirec_fuse.hip"]

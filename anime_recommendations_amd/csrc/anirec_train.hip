@@ -37,116 +37,16 @@
 // kernels it hides once the extra hot launch (13 us) is paid; fused INTO the rest launch (256-1024 workgroups
 // running fwd -> barrier -> head -> barrier -> bwd beside the stream) the latency-bound chain crawls behind the
 // bandwidth-saturating stream (270-400 us per step against 232).
+//
+// This unit holds the step's kernels outside the head — prep, fwd, bwd, the dense update, the lazy window — with their
+// argument builders and launchers.  The head, validation, the self-tests and the host loop are units of their own
+// (anirec_train_head.hip, _head_metrics, _eval, _util, _run; the map is in DESIGN.md, 4.1).
 #include <hip/hip_runtime.h>
 
-#include <dlfcn.h>
-#include <rccl/rccl.h>  // types and prototypes only: the library is bound at run time (dlopen), never linked
-#include <stdlib.h>
-#include <string.h>
-
-#include <new>
-
-#include "anirec_dev.hpp"
+#include "anirec_train.hpp"
+#include "anirec_train_lazy.hpp"
 
 namespace anirec {
-
-// ------------------------------------------------------------------------------------
-// workspace layout
-// ------------------------------------------------------------------------------------
-// Step constants written by workgroup 0 of the head kernel, read by bwd and adam.
-struct StepPub {
-  int slot, n_total, n_head_blocks, step;
-  float alpha, mu, var, rs;
-  float w, b, gamma, beta;
-  float l2, pad0, pad1, pad2;
-};
-
-
-struct TrainWs {
-  int cap, capC, arena_steps;
-  int dim;                      // row width of the tables (floats): ANIREC_DIM unless carved by a *_w entry point
-  float *su, *sa;               // [cap] row square sums from fwd
-  float *dy;                    // [cap] d loss / d y from head
-  // everything below this line is double-buffered by step parity (index p = step & 1)
-  float *hpart;                 // [2][ANIREC_MAX_SEG * ceil(cap/256)][8] head partial sums
-  size_t hpart_stride;          // floats per parity
-  StepPub *pub;                 // [2] step constants published by head workgroup 0
-  int32_t *sel;                 // step index of the last head launch (read by bwd / densify / adam)
-  unsigned long long *ticks;    // [8][ANIREC_ADAM_BLOCKS][2] measurement stamps (fwd, head, bwd, adam, lazy catch-up,
-                                // lazy adam, lazy flush, lazy reduce), behind the arena
-  float *lzpart;                // [ANIREC_LAZY_WINDOW][2][ANIREC_ADAM_BLOCKS] lazy flush: per-step sum(W^2) block partials
-  float *lzring;                // [ANIREC_LAZY_WINDOW][2] lazy: {n, bce mean} of the open window's steps (bce: the data
-                                //   term of the descriptor's loss, whichever it is)
-  float *regpart;               // [2][2][ANIREC_ADAM_BLOCKS]: user-row / anime-row sum(W^2) partials
-  float *P;                     // [2][2*capC][dim] chunk partial rows
-  float *S;                     // [2][2*capC]      chunk self-coefficient sums
-  // arena slot s: nchunks[2] (4 ints), sidx[2][cap], oth[2][cap], chunks[2][capC] (int4)
-  char *arena;
-  size_t slot_bytes;
-  size_t total;
-};
-
-__host__ __device__ inline int chunk_capacity(int cap) {
-  int c = cap + cap / ANIREC_CHUNK + 2;
-  return (c + 3) & ~3;
-}
-
-__host__ inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-__host__ __device__ inline int packet_cap(int max_batch) { return (max_batch + 3) & ~3; }
-
-__host__ inline TrainWs carve(void *base, int cap, int arena_steps, int dim = kDim) {
-  TrainWs w;
-  w.dim = dim;
-  w.cap = cap;
-  w.capC = chunk_capacity(cap);
-  w.arena_steps = arena_steps;
-  size_t off = 0;
-  char *b = (char *)base;
-  auto take = [&](size_t bytes) {
-    char *p = b + off;
-    off += align_up(bytes);
-    return p;
-  };
-  w.su = (float *)take(sizeof(float) * cap);
-  w.sa = (float *)take(sizeof(float) * cap);
-  w.dy = (float *)take(sizeof(float) * cap);
-  w.hpart_stride = 8 * ANIREC_MAX_SEG * (size_t)((cap + 255) / 256);
-  w.hpart = (float *)take(sizeof(float) * 2 * w.hpart_stride);
-  w.pub = (StepPub *)take(sizeof(StepPub) * 2);
-  w.sel = (int32_t *)take(sizeof(int32_t) * 4);
-  w.regpart = (float *)take(sizeof(float) * 2 * 2 * ANIREC_ADAM_BLOCKS);
-  w.P = (float *)take(sizeof(float) * 2 * 2 * (size_t)w.capC * dim);
-  w.S = (float *)take(sizeof(float) * 2 * 2 * (size_t)w.capC);
-  w.slot_bytes = align_up(16) + 2 * align_up(sizeof(int32_t) * 2 * (size_t)cap) +
-                 align_up(sizeof(int4) * 2 * (size_t)w.capC);
-  w.arena = take(w.slot_bytes * (size_t)arena_steps);
-  w.ticks = (unsigned long long *)take(sizeof(unsigned long long) * 8 * 2 * ANIREC_ADAM_BLOCKS);
-  w.lzpart = (float *)take(sizeof(float) * ANIREC_LAZY_WINDOW * 2 * ANIREC_ADAM_BLOCKS);
-  w.lzring = (float *)take(sizeof(float) * ANIREC_LAZY_WINDOW * 2);
-  w.total = off;
-  return w;
-}
-
-struct Slot {
-  int32_t *nchunks;  // [2] (+2 pad)
-  int32_t *sidx;     // [2][cap]  batch-local rating index in row-sorted order
-  int32_t *oth;      // [2][cap]  global W row of the other table, same order
-  int4 *chunks;      // [2][capC] {global row, start, len, nch if first chunk of row else 0}
-};
-
-__host__ __device__ inline Slot slot_of(char *arena, size_t slot_bytes, int cap, int capC, int s) {
-  char *p = arena + slot_bytes * (size_t)s;
-  Slot r;
-  size_t a0 = 256;
-  size_t a1 = ((sizeof(int32_t) * 2 * (size_t)cap) + 255) / 256 * 256;
-  r.nchunks = (int32_t *)p;
-  r.sidx = (int32_t *)(p + a0);
-  r.oth = (int32_t *)(p + a0 + a1);
-  r.chunks = (int4 *)(p + a0 + 2 * a1);
-  (void)capC;
-  return r;
-}
 
 // ------------------------------------------------------------------------------------
 // prep: stable LSD radix sort (8-bit digits) of one batch in LDS + chunk table
@@ -377,46 +277,6 @@ struct FwdArgs {
   unsigned long long *ticks;  // measurement hook: [gridDim.x][2] start / end stamps per workgroup, or nullptr
 };
 
-// Measurement hook (bench.py): every workgroup leaves the 100 MHz constant-clock time of its first and last
-// instruction; a kernel's duration is max(end) - min(start) over its workgroups — taken IN the step, on the batch the
-// step really reads, with whatever the previous kernel left in the caches.
-__device__ __forceinline__ void tick(unsigned long long *ticks, int which) {
-  if (ticks == nullptr) return;  // kernel-uniform
-  if (blockIdx.x >= ANIREC_ADAM_BLOCKS) return;  // a slot holds ANIREC_ADAM_BLOCKS stamp pairs (workgroup-uniform)
-  if (which) {                   // the end stamp covers every wave of the workgroup and its stores
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) ticks[2 * (size_t)blockIdx.x + which] = __builtin_amdgcn_s_memrealtime();
-}
-
-// One row group (kD / 4 lanes: a half-wave at 128) per rating.  Returns dot products through references; all lanes
-// of the group hold the totals.
-template <int kD = kDim>
-__device__ __forceinline__ void pair_dots(const float4 *W4, int urow, int arow, int l32, float &su,
-                                          float &sa, float &dd) {
-  constexpr int kG = kD / 4;
-  const float4 u = W4[(size_t)urow * kG + l32];
-  const float4 a = W4[(size_t)arow * kG + l32];
-  float s0 = u.x * u.x + u.y * u.y + u.z * u.z + u.w * u.w;
-  float s1 = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
-  float s2 = u.x * a.x + u.y * a.y + u.z * a.z + u.w * a.w;
-  su = group_sum<kG>(s0);
-  sa = group_sum<kG>(s1);
-  dd = group_sum<kG>(s2);
-}
-
-__device__ __forceinline__ float cos_from_dots(float su, float sa, float dd) {
-  const float ru = 1.0f / sqrtf(fmaxf(su, kL2nEps));
-  const float ra = 1.0f / sqrtf(fmaxf(sa, kL2nEps));
-  return dd * ru * ra;
-}
-
-// the packet count word travels through an all-gather on the multi-GPU path: read it with an agent-scope load
-__device__ __forceinline__ int ld_i32(const int32_t *p) {
-  return __hip_atomic_load(const_cast<int32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // the forward pass of one workgroup: a row group (a half-wave at 128) per rating
 template <int kD = kDim>
 __device__ __forceinline__ void fwd_block(const FwdArgs &a, const anirec_step sc, int vblk, int step) {
@@ -479,273 +339,6 @@ __global__ __launch_bounds__(1024) void k_seg_stats(float *pk, int pcap, int cap
     pk[2 * (size_t)pcap + 2] = r[0];
   }
 }
-
-// ------------------------------------------------------------------------------------
-// head: Dense(1) -> BatchNorm(batch stats) -> activation -> loss (head_terms), spread over many workgroups.
-// Every workgroup recomputes the batch mean/variance of z from all c (two-pass, no
-// transcendentals, 40 KB from L2), then does the sigmoid/log work of ITS 256 ratings and
-// leaves eight partial sums.  Workgroup 0 publishes the step constants for bwd / adam.
-// ------------------------------------------------------------------------------------
-constexpr int kHeadThreads = 256;
-constexpr int kHeadCols = 8;  // S1, S2, L, SE, sum dy*c, sum c, sum zh*c, sum zh
-
-struct HeadArgs {
-  const anirec_state *state;
-  const anirec_step *sched;
-  const float *packets;  // n_seg packets
-  size_t packet_floats;
-  int n_seg, my_seg, cap, arena_steps;
-  float *dy;             // [cap] d loss / d y of this rank's ratings
-  float *hpart;          // [2][n_seg*blocks_per_seg][8]
-  size_t hpart_stride;
-  StepPub *pub;          // [2]
-  int32_t *sel;
-  float l2;
-  unsigned long long *ticks;
-};
-
-__device__ __forceinline__ int packet_count(const float *pk, int cap) {
-  return min(ld_i32(reinterpret_cast<const int32_t *>(pk + 2 * (size_t)packet_cap(cap))), cap);
-}
-
-// A packet's c values for the batch statistics: every 16-B load of the thread is issued before
-// the first use (a scalar strided loop serialises ~40 L2 round trips) and does not depend on
-// the packet's count word, so state, counts and values arrive in ONE memory round trip.
-constexpr int kHeadVec = ANIREC_MAX_BATCH / (4 * kHeadThreads);  // 16 float4 per thread at most
-
-// A packet's c values for the batch statistics: every 16-B load of the thread is issued before the first use (a
-// scalar strided loop serialises ~40 L2 round trips) and does not depend on the packet's count word, so state,
-// counts and values arrive in ONE memory round trip; they stay in registers for both passes (re-reading them
-// from L2 for the second pass measured 12.1 us per launch against 8.8 us).
-struct SegVals {
-  float4 v[kHeadVec];
-};
-
-__device__ __forceinline__ void seg_load(const float *pk, int pcap, SegVals &x) {
-  const float4 *p4 = reinterpret_cast<const float4 *>(pk);
-#pragma unroll
-  for (int k = 0; k < kHeadVec; ++k) {
-    const int i4 = threadIdx.x + k * kHeadThreads;
-    x.v[k] = (i4 * 4 < pcap) ? p4[i4] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-template <bool kSecond>
-__device__ __forceinline__ float seg_stat(const SegVals &x, int cnt, float w, float b, float mu) {
-  float acc = 0.f;
-#pragma unroll
-  for (int k = 0; k < kHeadVec; ++k) {
-    const int i = (threadIdx.x + k * kHeadThreads) * 4;
-    const float c4[4] = {x.v[k].x, x.v[k].y, x.v[k].z, x.v[k].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (i + j < cnt) {
-        const float z = c4[j] * w + b;
-        acc += kSecond ? (z - mu) * (z - mu) : z;
-      }
-    }
-  }
-  return acc;
-}
-
-// the step index and the four head scalars a head workgroup works with
-struct HeadIn {
-  int step;
-  float w, b, gamma, beta;
-};
-
-// ---- Keras metrics (include/anirec.h, ANIREC_METRIC_*): the metrics instantiations of the head and of validation
-// add the requested kinds to a caller-owned anirec_metric_acc; the default instantiations never see these
-struct MetricArgs {
-  uint32_t mask;  // ANIREC_METRIC_* bits, non-zero (wave-uniform: a kernel argument)
-  anirec_metric_acc *acc;
-};
-constexpr int kMetricKinds = ANIREC_METRIC_KINDS;
-constexpr int kAucBins = ANIREC_AUC_BINS;
-constexpr uint32_t kMetricBits = (1u << (kMetricKinds + 1)) - 1;  // every ANIREC_METRIC_* bit
-
-// the per-rating values of the scalar kinds (0 for a kind the mask does not ask for), Keras 2.12 definitions with one
-// rounding per operation
-template <int kAct>
-__device__ __forceinline__ void metric_terms(uint32_t mask, float y, float t, float p, float (&v)[kMetricKinds]) {
-#pragma clang fp contract(off)
-  const float ae = fabsf(p - t);
-  v[0] = ae;                                                                          // mean_absolute_error
-  v[1] = (mask & ANIREC_METRIC_MAPE) ? 100.f * (ae / fmaxf(fabsf(t), kBceEps)) : 0.f;  // ..._percentage_error
-  if (mask & ANIREC_METRIC_MSLE) {                                                    // ..._squared_logarithmic_error
-    const float d = logf(fmaxf(p, kBceEps) + 1.f) - logf(fmaxf(t, kBceEps) + 1.f);
-    v[2] = d * d;
-  } else {
-    v[2] = 0.f;
-  }
-  float l = 0.f, g;
-  if (mask & ANIREC_METRIC_LOGCOSH) loss_terms<ANIREC_LOSS_LOGCOSH>(p, t, l, g);
-  v[3] = l;
-  v[4] = (mask & ANIREC_METRIC_BCE) ? head_loss<kAct, ANIREC_LOSS_BCE>(y, t, p) : 0.f;  // (from logits: sigmoid)
-  v[5] = t == (p > 0.5f ? 1.f : 0.f) ? 1.f : 0.f;                                       // binary_accuracy
-}
-
-// AUC bucket of a prediction (Keras' evenly-spaced-thresholds path: ceil(p * (200 - 1)) - 1 in fp32, relu) and the
-// fixed-point label mass of a rating; the clamps only keep a NaN or out-of-range value inside the bins
-__device__ __forceinline__ int auc_bucket(float p) {
-  return (int)fminf(fmaxf(ceilf(p * (float)(kAucBins - 1)) - 1.f, 0.f), (float)(kAucBins - 1));
-}
-__device__ __forceinline__ uint32_t auc_pos_mass(float t) {
-  return (uint32_t)rintf(fminf(fmaxf(t, 0.f), 1.f) * (float)ANIREC_AUC_ONE);
-}
-
-// a workgroup's block-summed kinds into the fp64 accumulators: one atomic per requested kind (the order dependence
-// stays far below the History's fp32, as in k_eval)
-__device__ __forceinline__ void metric_flush(const MetricArgs &m, const float (&v)[kMetricKinds]) {
-#pragma unroll
-  for (int k = 0; k < kMetricKinds; ++k)
-    if (m.mask & (1u << k)) atomicAdd(&m.acc->sum[k], (double)v[k]);
-}
-
-// workgroup vblk of nvb: the batch statistics (recomputed per workgroup) + 256 ratings; kAct / kLoss: the output head
-// (ANIREC_ACT_* / ANIREC_LOSS_*, head_terms), one instantiation per pair.  kMetrics: also the Keras metrics of m over
-// the workgroup's ratings — scratch then holds kHeadCols * 16 floats and, behind them, the zeroed 2 * kAucBins-word AUC
-// histogram (k_head_metrics)
-template <int kAct, int kLoss, bool kMetrics = false>
-__device__ __forceinline__ void head_block(const HeadArgs &a, const HeadIn in, int vblk, int nvb, float *scratch,
-                                           MetricArgs m = {}) {
-  const int tid = threadIdx.x;
-  const int pcap = packet_cap(a.cap);
-  const int bps = (a.cap + kHeadThreads - 1) / kHeadThreads;  // blocks per segment
-  const int seg = vblk / bps;
-  const int i = (vblk % bps) * kHeadThreads + tid;
-
-  // ---- issue every independent load first --------------------------------------------
-  SegVals x0;
-  seg_load(a.packets, pcap, x0);  // segment 0 stays in registers for both passes
-  const float *mypk = a.packets + a.packet_floats * seg;
-  const float my_c = i < a.cap ? mypk[i] : 0.f;
-  const float my_t = i < a.cap ? mypk[pcap + i] : 0.f;
-  const int step = in.step;
-  const float w = in.w, b = in.b, gamma = in.gamma, beta = in.beta;
-  int cnts[ANIREC_MAX_SEG];
-  int n_total = 0;
-#pragma unroll
-  for (int s = 0; s < ANIREC_MAX_SEG; ++s) {
-    cnts[s] = s < a.n_seg ? packet_count(a.packets + a.packet_floats * s, a.cap) : 0;
-    n_total += cnts[s];
-  }
-  const float Bf = (float)n_total;
-
-  // ---- batch statistics of z over the whole (global) batch ------------------------------------
-  float mu, var;
-  if (a.n_seg == 1) {
-    // one rank: two passes over the 40 KB of c (registers), redundantly per workgroup
-    float r[1];
-    r[0] = seg_stat<false>(x0, cnts[0], w, b, 0.f);
-    block_sum<1>(r, scratch);
-    mu = r[0] / Bf;
-    r[0] = seg_stat<true>(x0, cnts[0], w, b, mu);
-    block_sum<1>(r, scratch);
-    var = r[0] / Bf;  // biased (tf.nn.moments)
-  } else {
-    // several ranks: every packet carries (count, mean, M2) of its own z values (k_seg_stats on
-    // the owning rank, same w and b everywhere); merge them in rank order (Chan et al.)
-    double nsum = 0.0, msum = 0.0;
-#pragma unroll
-    for (int s = 0; s < ANIREC_MAX_SEG; ++s) {
-      if (s < a.n_seg && cnts[s] > 0) {
-        const float *tail = a.packets + a.packet_floats * s + 2 * (size_t)pcap;
-        nsum += (double)cnts[s];
-        msum += (double)cnts[s] * (double)tail[1];
-      }
-    }
-    const double mean = msum / nsum;
-    double m2 = 0.0;
-#pragma unroll
-    for (int s = 0; s < ANIREC_MAX_SEG; ++s) {
-      if (s < a.n_seg && cnts[s] > 0) {
-        const float *tail = a.packets + a.packet_floats * s + 2 * (size_t)pcap;
-        const double dm = (double)tail[1] - mean;
-        m2 += (double)tail[2] + (double)cnts[s] * dm * dm;
-      }
-    }
-    mu = (float)mean;
-    var = (float)(m2 / nsum);
-  }
-  const float rs = 1.0f / sqrtf(var + kBnEps);
-  const float inv = rs * gamma;
-  const float shift = beta - mu * inv;
-
-  // ---- this workgroup's 256 ratings ---------------------------------------------------------
-  int cnt = 0;
-#pragma unroll
-  for (int s = 0; s < ANIREC_MAX_SEG; ++s)
-    if (s == seg) cnt = cnts[s];
-  float r[kHeadCols] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float mv[kMetricKinds] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  uint32_t *hist = reinterpret_cast<uint32_t *>(scratch + kHeadCols * 16);
-  if constexpr (kMetrics) __syncthreads();  // the zeroed histogram (the several-rank branch has no barrier)
-  if (i < cnt) {
-    const float c = my_c, t = my_t;
-    const float z = c * w + b;
-    const float y = z * inv + shift;
-    float p, g;
-    head_grad<kAct, kLoss>(y, t, p, g);
-    const float dy = g / Bf;
-    const float zh = (z - mu) * rs;
-    r[0] = dy;
-    r[1] = dy * zh;
-    r[2] = head_loss<kAct, kLoss>(y, t, p);
-    r[3] = (p - t) * (p - t);
-    r[4] = dy * c;
-    r[5] = c;
-    r[6] = zh * c;
-    r[7] = zh;
-    if (seg == a.my_seg) a.dy[i] = dy;
-    if constexpr (kMetrics) {
-      metric_terms<kAct>(m.mask, y, t, p, mv);
-      if (m.mask & ANIREC_METRIC_AUC) {  // LDS integer adds: order-independent
-        const int bk = auc_bucket(p);
-        const uint32_t wt = auc_pos_mass(t);
-        atomicAdd(&hist[bk], wt);
-        atomicAdd(&hist[kAucBins + bk], ANIREC_AUC_ONE - wt);
-      }
-    }
-  }
-  block_sum<kHeadCols>(r, scratch);
-  const int par = step & 1;
-  if (tid < kHeadCols) a.hpart[par * a.hpart_stride + (size_t)vblk * kHeadCols + tid] = r[tid];
-  if constexpr (kMetrics) {
-    block_sum<kMetricKinds>(mv, scratch);  // (its barriers also complete the histogram)
-    if (tid == 0) metric_flush(m, mv);
-    if (m.mask & ANIREC_METRIC_AUC) {
-      for (int k = tid; k < 2 * kAucBins; k += kHeadThreads) {
-        const uint32_t h = hist[k];
-        if (h) atomicAdd(k < kAucBins ? &m.acc->auc_pos[k] : &m.acc->auc_neg[k - kAucBins], (unsigned long long)h);
-      }
-    }
-  }
-
-  if (vblk == 0) {
-    if (tid == 0) {
-      StepPub p;
-      p.slot = step % a.arena_steps;
-      p.n_total = n_total;
-      p.n_head_blocks = nvb;
-      p.step = step;
-      p.alpha = a.sched[step].alpha;
-      p.mu = mu;
-      p.var = var;
-      p.rs = rs;
-      p.w = w;
-      p.b = b;
-      p.gamma = gamma;
-      p.beta = beta;
-      p.l2 = a.l2;
-      p.pad0 = p.pad1 = p.pad2 = 0.f;
-      a.pub[par] = p;
-      a.sel[0] = step;
-    }
-  }
-}
-
-// (k_head itself is defined below the lazy update's row kernels: its launch also carries their catch-up workgroups)
 
 // ------------------------------------------------------------------------------------
 // bwd: per-chunk weighted row sums
@@ -1362,484 +955,10 @@ __global__ __launch_bounds__(256) void k_adam(AdamArgs a) {
 // ------------------------------------------------------------------------------------
 // lazy dense Adam (one GPU; include/anirec.h, "LAZY DENSE ADAM")
 // ------------------------------------------------------------------------------------
-constexpr int kLzWin = ANIREC_LAZY_WINDOW;
-
-struct LazyState {
-  int32_t *row_step;  // [rows] the step every row has been updated to (rows are current at the window's start)
-  int32_t *mark;      // [rows] t + 1 for the rows batch t touched (written by fwd(t))
-  float *rowsq;       // [rows][kLzWin] sum(W_s^2) of the row for the window's steps it has already taken
-};
-__host__ __device__ inline LazyState lazy_carve(void *base, int rows) {
-  const size_t col = (sizeof(int32_t) * (size_t)rows + 255) / 256 * 256;
-  LazyState z;
-  z.row_step = (int32_t *)base;
-  z.mark = (int32_t *)((char *)base + col);
-  z.rowsq = (float *)((char *)base + 2 * col);
-  return z;
-}
-
-struct LazyArgs {
-  float *W, *M, *V;
-  int rows, n_user_rows;
-  LazyState z;
-  const anirec_step *sched;
-  int n_steps;
-  anirec_state *state;
-  int32_t *w0;  // device word: first step of the open window
-  float two_l2, l2;
-  char *arena;
-  size_t slot_bytes;
-  int cap, capC, arena_steps;
-  float *lzpart, *lzring, *regpart;
-  int tables;   // 2: both tables are updated lazily (one GPU); 1: the user rows only (user-sharded multi-GPU step: the
-                // replicated anime rows take their dense update behind the all-reduce every step)
-  int lazy_rows;  // rows [0, lazy_rows) are the lazily updated ones (all rows, or the user rows)
-  int split;      // k_lazy_flush: workgroups [0, split) take the user rows, [split, grid) the anime rows
-  int cu_lo;      // catch-up workgroups riding in another kernel's launch: they cover chunk-grid blocks [cu_lo, ...)
-  int n_sparse;   // k_lazy_adam: workgroups [0, n_sparse) take the sparse step, the others a catch-up slice
-  unsigned long long *ticks;
-};
-
-struct Row3 {
-  float4 w, m, v;
-};
-
-// pending pure-L2 steps [j0, j1) (window-relative) of one row, a float4 per lane: g = 2 lambda W exactly as the
-// dense kernel forms it for a row no rating touched; sq[j] receives this lane's part of sum(W_s^2), the weights
-// step s READ
-// the dense kernel's gradient of a row no rating touched, grad_total(0, 0, w, 2 lambda) = (0 - 0 w) + 2 lambda w:
-// (0 - 0 w) is +0 for every finite w, so it is (2 lambda w) + 0 — the "+ 0" kept because it turns a -0 product into
-// the +0 the dense expression yields (bit-identical tables, zeros included)
-__device__ __forceinline__ float l2_only_grad(float w, float two_l2) {
-#pragma clang fp contract(off)
-  return two_l2 * w + 0.0f;
-}
-
-// ---- the replayed Adam step on packed pairs -----------------------------------------------------------------
-// The flush is bound by its arithmetic: the compiler's correctly rounded sqrtf (15 instructions: scaling for tiny
-// inputs, v_sqrt_f32, two +-1 ulp residual tests, class fix-up) and IEEE divide (11: v_div_scale x2, v_rcp_f32, the
-// Markstein fma chain, v_div_fmas, v_div_fixup) per element-step, all scalar.  For operands in the exponent range
-// Adam's moments live in, the scaling and fix-up steps are identities, and what is left — the residual tests and the
-// fma chain, instruction for instruction what the expansions execute — runs on PAIRS (v_pk_fma_f32 / v_pk_mul_f32 /
-// v_pk_add_f32).  A wave whose operands leave the range (a moment decayed to a denormal, an exact zero) takes the
-// compiler's path for that row: the results are the dense kernel's bit for bit either way (tested on every element
-// of the S109M tables; the square root is compared with sqrtf on EVERY float of its range, anirec_selftest_lazy_math).
-//
-// Round 4 (PMC: the kernel issues, it does not wait — profiles/r04_pmc_valu_train_s109m.json):
-//  * the range tests left the step: every pair-step folds its second moment and |m alpha| into a running
-//    min / max (v_min3_f32 / v_max3_f32: 4 instructions instead of 8 compares + 7 s_and) and the row is tested ONCE,
-//    after its last step.  A NaN slips through min / max, but it is sticky (w NaN -> g, m, v NaN; m or v NaN -> w NaN),
-//    so one test of the final w catches it.
-//  * the square root is ONE exact-residual Newton correction from v_rsq_f32 (sqrt4_normal) instead of v_sqrt_f32
-//    + both neighbours' residuals + a three-way selection (v_cmp + v_cndmask through VCC cost two wait states each
-//    on gfx950 that the compiler could only half fill: 494 s_nop in the round-3 kernel).
-//  * g = 2 lambda w without the "+ 0" of l2_only_grad: it only matters when the product is -0, and then the first
-//    moment of that step is +-0, |m alpha| = 0 fails the range test and the row is redone by the compiler's path.
-// Round 5: the running minima / maxima left the step too — the bounds are derived once per row from the values the
-// replay starts from (lz_entry_ok), only the smallest |m| is still folded per step; and the divide takes one
-// correction instead of two (div4_normal, checked by exhaustion).
-// The four elements of a lane are two PAIRS stepped side by side, statement by statement: every operation is two
-// independent v_pk_*_f32 back to back.  (Written as one pair after the other, hipcc ran one pair's divide chain behind
-// the other's — gfx950 wants a wait state between DEPENDENT packed-f32 instructions, and that schedule paid an s_nop
-// for each; written as one 4-wide vector, its subtractions and negations come out scalar.)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-struct Quad {
-  f32x2 a, b;
-};
-// (the contraction flag of an operation is the one in force where it is WRITTEN: these bodies, not their callers)
-#pragma clang fp contract(off)
-__device__ __forceinline__ Quad operator+(Quad x, Quad y) { return {x.a + y.a, x.b + y.b}; }
-__device__ __forceinline__ Quad operator-(Quad x, Quad y) { return {x.a - y.a, x.b - y.b}; }
-__device__ __forceinline__ Quad operator*(Quad x, Quad y) { return {x.a * y.a, x.b * y.b}; }
-__device__ __forceinline__ Quad operator*(Quad x, float y) { return {x.a * y, x.b * y}; }
-__device__ __forceinline__ Quad operator+(Quad x, float y) { return {x.a + y, x.b + y}; }
-__device__ __forceinline__ Quad operator-(Quad x) { return {-x.a, -x.b}; }
-#pragma clang fp contract(fast)
-__device__ __forceinline__ Quad qfma(Quad x, Quad y, Quad z) {
-  return {__builtin_elementwise_fma(x.a, y.a, z.a), __builtin_elementwise_fma(x.b, y.b, z.b)};
-}
-
-// Correctly rounded sqrt of x in [2^-96, 2^96] (no scaling of tiny inputs needed there): y = v_rsq_f32(x),
-// s0 = x y, h = y / 2, then ONE Newton correction with the EXACT residual (fma): s = s0 + (x - s0^2) h.
-// 4 packed operations + 1 transcendental per element, against 1 + 9 for the form the compiler expands sqrtf into
-// (v_sqrt_f32, both neighbours' residuals, a three-way selection).  In general such a step is only faithful: that on
-// gfx950 — with this part's v_rsq_f32 — its fma rounds to the correctly rounded root for EVERY float of the range is
-// not argued but CHECKED: anirec_selftest_lazy_math compares it with sqrtf on all 1.6e9 of them
-// (tests/test_train_gpu.py: 0 mismatches; the same code without the correction, kSteps = 0, misses on 4.8e8 — the
-// comparison can fail; with a second correction, kSteps = 2, measured 0 as well and 7 % slower).  A part whose
-// transcendental unit rounded differently would fail that test, not silently change a table.
-template <int kSteps = 1>
-__device__ __forceinline__ Quad sqrt4_normal(Quad x) {
-#pragma clang fp contract(off)
-  Quad y;
-  y.a.x = __builtin_amdgcn_rsqf(x.a.x);
-  y.a.y = __builtin_amdgcn_rsqf(x.a.y);
-  y.b.x = __builtin_amdgcn_rsqf(x.b.x);
-  y.b.y = __builtin_amdgcn_rsqf(x.b.y);
-  const Quad s0 = x * y;
-  if (kSteps == 0) return s0;
-  const Quad h = y * 0.5f;
-  const Quad d0 = qfma(-s0, s0, x);
-  const Quad s1 = qfma(d0, h, s0);
-  if (kSteps == 1) return s1;
-  const Quad d1 = qfma(-s1, s1, x);
-  return qfma(d1, h, s1);
-}
-
-// refined reciprocal y = y0 + (1 - d y0) y0, y0 = v_rcp_f32(d): anirec_selftest_lazy_div checks y == 1.0f / d on
-// EVERY float d of [1e-7, 2^48] (the denominators sqrt(v) + 1e-7 the replay admits)
-__device__ __forceinline__ Quad rcp4_refined(Quad d) {
-#pragma clang fp contract(off)
-  Quad y0;
-  y0.a.x = __builtin_amdgcn_rcpf(d.a.x);
-  y0.a.y = __builtin_amdgcn_rcpf(d.a.y);
-  y0.b.x = __builtin_amdgcn_rcpf(d.b.x);
-  y0.b.y = __builtin_amdgcn_rcpf(d.b.y);
-  const Quad one = {{1.0f, 1.0f}, {1.0f, 1.0f}};
-  const Quad e = qfma(-d, y0, one);
-  return qfma(e, y0, y0);
-}
-
-// Correctly rounded n / d for |n| in [2^-60, 2^60], d in [1e-7, 2^48]: q0 = n y, ONE correction q1 = q0 + (n - d q0) y.
-// The compiler's chain (v_div_scale / v_div_fixup aside) takes a second one, r1 = n - d q1, q2 = q1 + r1 y, because
-// Markstein's theorem — y = RN(1/d), q within 1 ulp of n/d, the residual n - d q exact, no underflow — then makes q2
-// = RN(n/d) for any q1 within 1 ulp.  It does NOT cover q1 itself: with y = RN(1/d), q0 = RN(n y) is off by up to
-// 1.48 ulp and the fma's residual n - d q0 is inexact for ~0.15 % of operand pairs.  q1 = RN(n/d) is established by
-// exhaustion instead (anirec_selftest_lazy_div, tests/test_lazy_div_exhaustive_gpu.py):
-//  * y == RN(1/d) for every float d of the range (6e8 values), so y(d 2^k) = y(d) 2^k there;
-//  * then every operation of the sequence commutes with scaling n and d by powers of two as long as no result is
-//    subnormal: q0 and q1 are within 2 ulp of n/d in [2^-108, 2^84], and a nonzero residual n - d q0 is a multiple
-//    of ulp(d) ulp(q0) >= 2^-48 |n| >= 2^-108 (normal: the fma rounds it once, as it does for n, d in [1, 2));
-//  * so q1 == RN(n/d) for the whole range iff it holds for all 2^46 significand pairs n, d in [1, 2) (signs are
-//    symmetric) — the self-test compares q1 with IEEE `/` on every one of them: 0 mismatches.
-// (The second correction is 4 packed operations per lane-step, ~7 % of the flush's VALU issue.)
-__device__ __forceinline__ Quad div4_normal(Quad n, Quad d) {
-#pragma clang fp contract(off)
-  const Quad y = rcp4_refined(d);
-  const Quad q0 = n * y;
-  const Quad r0 = qfma(-d, q0, n);
-  return qfma(r0, y, q0);
-}
-
-// What the short sequences are exact for: every step's second moment in [2^-96, 2^96] (no sqrt scaling), |m alpha| in
-// [2^-60, 2^60] with the denominator sqrt(v) + 1e-7 in [1e-7, 2^48 + eps] (no v_div_scale, no v_div_fixup).
-// The bounds are tested ONCE per row, from the values the replay starts from, instead of folding every step's
-// operands into running minima / maxima (round 4: 8 v_min3 / v_max3 per lane-step).  Window constants (lz_bound):
-// amin / A = the smallest / largest alpha of the window's steps, L = |2 lambda|.  Per element, u = 2^-24, every
-// operation rounding to nearest (monotone, |RN(x)| <= |x| (1 + u), and RN(x) >= x (1 - u) for normal x > 0; a flush
-// to zero only lowers a magnitude), by induction over the <= 8 steps:
-//  (v lo) g^2 >= 0, so RN(g^2 - v) >= RN(-v) = -v and v' = RN(v + RN(RN(g^2 - v) c2)) >= v (1 - c2 (1 + u)) (1 - u)
-//         >= 0.99899 v for normal v.  The FIRST step also lifts v: with G = RN(g_0^2) normal, either v_0 <= G / 2,
-//         then RN(G - v_0) >= (G - v_0) (1 - u) and v_1 >= (v_0 + (G - v_0) c2 (1 - u)^2) (1 - u) >= c2 G (1 - u)^3,
-//         or v_0 > G / 2 and v_1 >= 0.99899 v_0 > c2 G.  So v_1 >= max(0.99899 v_0, c2 G (1 - u)^3), and the
-//         per-element vb = max(v_0, e), e = RN(RN(c2 L^2) RN(w_0^2)) <= c2 G (1 - u)^-10, gives every v_j (j >= 1,
-//         the moments the steps produce) >= 0.99899^7 (1 - 13 u) 0.99899 vb >= 0.989 vb > 2^-96 for vb >= 2^-95 (the
-//         factor-2 margin).  (Rows fresh from initialisation, v_0 = 0, are admitted through e: |w_0| >~ 1e-9 at
-//         lambda = 1e-4, as the per-step test of the moments admitted them.)
-//  (v hi) v' is RN of a combination of v and RN(g^2) with weights (1 - c), c in (0, 1): v' <= max(v, g^2) (1 + u)^2.
-//  (m)    likewise |m'| <= max(|m|, |g|) (1 + u)^3, and |g| = |RN(2 lambda w)| <= L |w| (1 + u).
-//  (w)    |w'| <= (|w| + |q|) (1 + u), q = RN(RN(m' alpha) / RN(RN(sqrt v') + eps)), the denominator >= RN(sqrt v')
-//         >= sqrt(0.989 vb) (1 - u) and >= eps: |q| <= |m'| S, S = min(1.006 A / sqrt(vb), 1.0001 A / eps) (the
-//         second term is what bounds the first window's rows whose tiny |w_0| makes vb tiny).
-//  With X = max(|m|, L |w|): X' <= X (1 + L S) (1 + u)^5.  Over the window, with F = (1 + L S)^8: every |m_j| and
-//  |g_j| <= X_0 F (1 + 2^-17), so every v_j <= max(v_0, (X_0 F)^2) (1 + 2^-15) and |m_j alpha_j| <= A X_0 F (1 + 2^-16).
-//  The row is admitted if every vb >= 2^-95, v_0 <= 2^95, X_0 F <= 2^46 and X_0 F A <= 2^58: a factor 2 below the
-//  2^47 / 2^59 the bounds need, which covers F's own roundings in fp32 and v_rsq_f32's error (with 1.01 for 1.006
-//  and for 1.0001; F is taken at the lane's smallest vb).
-//  (|m alpha| lo) the one bound no entry value gives — m crossing zero — stays per step: the smallest |m_j| of the
-//  steps taken (one v_min3 per pair), times amin once: RN(|m_j| alpha_j) >= RN(min |m| amin) >= 2^-60.
-// A NaN slips through min / max (and fails every comparison); it is sticky (w NaN -> g, m, v NaN; m or v NaN -> w
-// NaN), so the test of the final w catches it.
-struct LzBound {
-  float amin;  // smallest alpha of the window's steps [0, nj)
-  float amax;  // A
-  float k;     // 1.01 L A
-  float kmax;  // 1.01 L A / eps
-  float kv;    // c2 L^2
-};
-__device__ __forceinline__ LzBound lz_bound(const float (&alpha)[kLzWin], int nj, float two_l2) {
-  float amin = 3.0e38f, amax = 0.f;
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j) {
-    if (j < nj) amin = fminf(amin, alpha[j]);
-    amax = fmaxf(amax, alpha[j]);
-  }
-  const float k = 1.01f * fabsf(two_l2) * amax;
-  return {amin, amax, k, k * 1e7f, kOneMinusB2 * two_l2 * two_l2};
-}
-__device__ __forceinline__ float min3f(float a, float b, float c) { return fminf(fminf(a, b), c); }
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-// the entry half of the test above, for a lane's four elements
-__device__ __forceinline__ bool lz_entry_ok(const Row3 &x, const LzBound &bd, float two_l2) {
-  const float vb0 = fmaxf(x.v.x, bd.kv * (x.w.x * x.w.x)), vb1 = fmaxf(x.v.y, bd.kv * (x.w.y * x.w.y)),
-              vb2 = fmaxf(x.v.z, bd.kv * (x.w.z * x.w.z)), vb3 = fmaxf(x.v.w, bd.kv * (x.w.w * x.w.w));
-  const float vlo = fminf(min3f(vb0, vb1, vb2), vb3);
-  const float vhi = fmaxf(max3f(x.v.x, x.v.y, x.v.z), x.v.w);
-  const float mx = fmaxf(max3f(fabsf(x.m.x), fabsf(x.m.y), fabsf(x.m.z)), fabsf(x.m.w));
-  const float wx = fmaxf(max3f(fabsf(x.w.x), fabsf(x.w.y), fabsf(x.w.z)), fabsf(x.w.w));
-  const float x0 = fmaxf(mx, fabsf(two_l2) * wx);
-  float f = 1.0f + fminf(bd.k * __builtin_amdgcn_rsqf(vlo), bd.kmax);
-  f = f * f;
-  f = f * f;
-  f = f * f;
-  const float xf = x0 * f;
-  return vlo >= 0x1p-95f && vhi <= 0x1p95f && xf <= 0x1p46f && xf * bd.amax <= 0x1p58f;
-}
-
-// The catch-up (k_head / k_lazy_adam / k_lazy_catchup) replays a row's few pending steps on a latency-bound path:
-// there the ~50 instructions of lz_bound + lz_entry_ok cost more than they save (measured: +0.3 / +0.75 / +0.35 us
-// per launch), so it keeps the round-4 test instead — every pair-step folds its second moment and |m alpha| into
-// running minima / maxima, tested after the row's last step (kRowTest = false).  The flush (a whole window per row,
-// VALU-bound) takes the once-per-row test (kRowTest = true).
-struct LzRange {
-  float vlo, vhi, nlo, nhi;  // kRowTest: nlo = the smallest |m| alone
-};
-__device__ __forceinline__ bool lz_range_ok(const LzRange &r) {
-  return r.vlo >= 0x1p-96f && r.vhi <= 0x1p96f && r.nlo >= 0x1p-60f && r.nhi <= 0x1p60f;
-}
-
-// one L2-only Adam step of a lane's four elements by the short sequences; kRowTest: the smallest |m| of the step is
-// folded into rg.nlo (tested by the caller once per row, with the window's smallest alpha); otherwise every operand
-// the sequences are conditional on is folded into rg
-template <bool kRowTest>
-__device__ __forceinline__ void adam4_l2(Quad &w, Quad &m, Quad &v, float alpha, float two_l2, LzRange &rg) {
-#pragma clang fp contract(off)
-  const Quad g = w * two_l2;
-  const Quad mn = m + (g - m) * kOneMinusB1;
-  const Quad vn = v + (g * g - v) * kOneMinusB2;
-  const Quad num = mn * alpha;
-  if (kRowTest) {
-    rg.nlo = min3f(min3f(rg.nlo, fabsf(mn.a.x), fabsf(mn.a.y)), fabsf(mn.b.x), fabsf(mn.b.y));
-  } else {
-    rg.vlo = min3f(min3f(rg.vlo, vn.a.x, vn.a.y), vn.b.x, vn.b.y);
-    rg.vhi = max3f(max3f(rg.vhi, vn.a.x, vn.a.y), vn.b.x, vn.b.y);
-    rg.nlo = min3f(min3f(rg.nlo, fabsf(num.a.x), fabsf(num.a.y)), fabsf(num.b.x), fabsf(num.b.y));
-    rg.nhi = max3f(max3f(rg.nhi, fabsf(num.a.x), fabsf(num.a.y)), fabsf(num.b.x), fabsf(num.b.y));
-  }
-  const Quad den = sqrt4_normal(vn) + kAdamEps;
-  w = w - div4_normal(num, den);
-  m = mn;
-  v = vn;
-}
-
-template <bool kFast, bool kRowTest>
-__device__ __forceinline__ void lazy_one_step(Row3 &x, float alpha, float two_l2, float &sq, LzRange &rg) {
-  sq = x.w.x * x.w.x + x.w.y * x.w.y + x.w.z * x.w.z + x.w.w * x.w.w;
-  if (kFast) {
-    Quad w = {{x.w.x, x.w.y}, {x.w.z, x.w.w}}, m = {{x.m.x, x.m.y}, {x.m.z, x.m.w}}, v = {{x.v.x, x.v.y}, {x.v.z, x.v.w}};
-    adam4_l2<kRowTest>(w, m, v, alpha, two_l2, rg);
-    x.w = make_float4(w.a.x, w.a.y, w.b.x, w.b.y);
-    x.m = make_float4(m.a.x, m.a.y, m.b.x, m.b.y);
-    x.v = make_float4(v.a.x, v.a.y, v.b.x, v.b.y);
-    return;
-  }
-  // the compiler's full expansions (scaling, fix-up)
-  const float gx = l2_only_grad(x.w.x, two_l2), gy = l2_only_grad(x.w.y, two_l2), gz = l2_only_grad(x.w.z, two_l2),
-              gw = l2_only_grad(x.w.w, two_l2);
-  adam_elem(x.w.x, x.m.x, x.v.x, gx, alpha);
-  adam_elem(x.w.y, x.m.y, x.v.y, gy, alpha);
-  adam_elem(x.w.z, x.m.z, x.v.z, gz, alpha);
-  adam_elem(x.w.w, x.m.w, x.v.w, gw, alpha);
-}
-
-// returns whether the short sequences were exact for every operand of every step this lane took (kFast)
-template <bool kFast, bool kRowTest>
-__device__ __forceinline__ bool lazy_replay_path(Row3 &x, int j0, int j1, const float (&alpha)[kLzWin], float two_l2,
-                                                 const LzBound &bd, float (&sq)[kLzWin]) {
-  const bool entry_ok = kFast && kRowTest ? lz_entry_ok(x, bd, two_l2) : true;
-  LzRange rg = {3.0e38f, 0.f, 3.0e38f, 0.f};
-  if (__all(j0 <= 0 && j1 >= kLzWin)) {  // the common case (a row untouched for a whole window): no predication
-#pragma unroll
-    for (int j = 0; j < kLzWin; ++j) lazy_one_step<kFast, kRowTest>(x, alpha[j], two_l2, sq[j], rg);
-  } else {
-#pragma unroll
-    for (int j = 0; j < kLzWin; ++j) {
-      if (__any(j >= j0 && j < j1)) {  // wave-uniform skip, then per-lane selection of the stepped values
-        Row3 y = x;
-        LzRange ry = rg;
-        float q;
-        lazy_one_step<kFast, kRowTest>(y, alpha[j], two_l2, q, ry);
-        if (j >= j0 && j < j1) {
-          x = y;
-          rg = ry;
-          sq[j] = q;
-        }
-      }
-    }
-  }
-  if (!kFast) return true;
-  if (j1 <= j0) return true;           // nothing taken
-  const float t = (x.w.x + x.w.y) + (x.w.z + x.w.w);  // a NaN anywhere in the replay has reached w
-  if (!kRowTest) return lz_range_ok(rg) && t == t;
-  return entry_ok && rg.nlo * bd.amin >= 0x1p-60f && t == t;
-}
-
-// The replay by the compiler's full expansions, OUT OF LINE: it runs for a handful of rows per table (a moment decayed
-// to a denormal, an exact zero) but, inlined, its 4 x 8 unrolled IEEE divides and square roots set the register
-// allocation of every kernel that can reach it (the flush: 150-166 VGPRs, three waves per SIMD).  Everything goes in
-// and out by value: an array whose address escaped into the call would live in scratch memory on the hot path too.
-struct SlowReplay {
-  Row3 x;
-  float sq[kLzWin];
-};
-struct AlphaPack {
-  float a[kLzWin];
-};
-__device__ __attribute__((noinline)) SlowReplay lazy_replay_slow(Row3 x, int j0, int j1, AlphaPack al, float two_l2) {
-  SlowReplay o;
-  float alpha[kLzWin], sq[kLzWin];
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j) {
-    alpha[j] = al.a[j];
-    sq[j] = 0.f;
-  }
-  (void)lazy_replay_path<false, false>(x, j0, j1, alpha, two_l2, LzBound{}, sq);
-  o.x = x;
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j) o.sq[j] = sq[j];
-  return o;
-}
-
-// pending pure-L2 steps [j0, j1) (window-relative) of one row, a float4 per lane; sq[j] receives this lane's part of
-// sum(W_s^2), the weights step s READ, for the steps taken (the others keep what the caller put there).  The packed
-// short sequences first; if any lane of the wave met an operand
-// outside their range, the whole replay is redone from the saved row with the compiler's expansions (rare: a moment
-// decayed to a denormal, an exact zero).
-// (the row is re-read from memory for the redo — nothing has been stored yet — rather than kept in 12 more registers)
-template <bool kRowTest>
-__device__ __forceinline__ void lazy_replay(Row3 &x, int j0, int j1, const float (&alpha)[kLzWin], float two_l2,
-                                            const LzBound &bd, float (&sq)[kLzWin], const float *W, const float *M,
-                                            const float *V, size_t e) {
-  if (__all(lazy_replay_path<true, kRowTest>(x, j0, j1, alpha, two_l2, bd, sq))) return;
-  Row3 y;
-  y.w = reinterpret_cast<const float4 *>(W)[e];
-  y.m = reinterpret_cast<const float4 *>(M)[e];
-  y.v = reinterpret_cast<const float4 *>(V)[e];
-  AlphaPack al;
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j) al.a[j] = alpha[j];
-  const SlowReplay o = lazy_replay_slow(y, j0, j1, al, two_l2);
-  x = o.x;
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j)
-    if (j >= j0 && j < j1) sq[j] = o.sq[j];
-}
-
-__device__ __forceinline__ void lazy_alphas(const LazyArgs &a, int w0, int nj, float (&alpha)[kLzWin]) {
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j) alpha[j] = (j < nj && w0 + j < a.n_steps) ? a.sched[w0 + j].alpha : 0.f;
-}
-
-// the distinct row a half-wave of the chunk-table grid owns (first chunk of a row's run), or -1.
-// kAnimeFirst (the sparse step): the anime table's chunk slots come first in the grid, as in k_bwd — the rows with
-// many chunks are anime rows; the catch-up keeps the user chunks first (they are where ITS work is, and the slice of
-// them that rides in the head launch is cut from the front of the grid).
-// The count word and the chunk record come in ONE round trip: the record index is clamped into the table's slots, and
-// a record past the count is dropped unread.
-template <bool kAnimeFirst = false>
-__device__ __forceinline__ int lazy_chunk_row(const LazyArgs &a, int step, int bid, int &gc, int &nch) {
-  const int hw = bid * 8 + (threadIdx.x >> 5);
-  const bool flip = kAnimeFirst && a.tables == 2;
-  const int T = flip ? (hw < a.capC ? 1 : 0) : (hw >= a.capC ? 1 : 0);
-  const int c = hw >= a.capC ? hw - a.capC : hw;
-  Slot sl = slot_of(a.arena, a.slot_bytes, a.cap, a.capC, step % a.arena_steps);
-  int4 rec = sl.chunks[T * a.capC + min(c, a.capC - 1)];
-  int nT = sl.nchunks[T];
-  asm volatile("" : "+v"(nT), "+v"(rec.x), "+v"(rec.w));  // both loads are issued here (hipcc sinks rec.x behind the test)
-  if (hw >= a.tables * a.capC || c >= nT) return -1;
-  if (rec.w <= 0) return -1;
-  gc = T * a.capC + c;
-  nch = rec.w;
-  return rec.x;
-}
-
-// the rows batch `step` touches take their pending L2-only steps, so that fwd / bwd of that step read current rows.
-// skip_mark > 0: rows whose mark equals it belong to the batch the sparse step of the SAME launch is updating —
-// not ours (that half of the launch brings them to `step` itself)
-__device__ __forceinline__ void lazy_catchup_row(const LazyArgs &a, int step, int w0, int bid, int skip_mark) {
-  const int l = threadIdx.x & 31;
-  int gc, nch;
-  const int row = lazy_chunk_row(a, step, bid, gc, nch);
-  if (row < 0) return;
-  // the row's mark, step word and W / M / V are requested TOGETHER: the two words only say whether the row needs
-  // anything, and waiting for them before asking for the row costs every stale row one more memory round trip on a
-  // path that is nothing but round trips (rows that turn out current — the popular anime rows — cost 1.5 KB each)
-  const size_t e = (size_t)row * kRowVec + l;
-  const int mk = skip_mark > 0 ? a.z.mark[row] : 0;
-  const int ta = a.z.row_step[row];
-  Row3 x;
-  x.w = reinterpret_cast<const float4 *>(a.W)[e];
-  x.m = reinterpret_cast<const float4 *>(a.M)[e];
-  x.v = reinterpret_cast<const float4 *>(a.V)[e];
-  if (skip_mark > 0 && mk == skip_mark) return;
-  if (ta >= step) return;
-  float alpha[kLzWin], sq[kLzWin];
-  lazy_alphas(a, w0, step - w0, alpha);
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j) sq[j] = 0.f;
-  lazy_replay<false>(x, ta - w0, step - w0, alpha, a.two_l2, LzBound{}, sq, a.W, a.M, a.V, e);
-  reinterpret_cast<float4 *>(a.W)[e] = x.w;
-  reinterpret_cast<float4 *>(a.M)[e] = x.m;
-  reinterpret_cast<float4 *>(a.V)[e] = x.v;
-  float mine = 0.f;
-#pragma unroll
-  for (int j = 0; j < kLzWin; ++j) {
-    const float t = halfwave_sum(sq[j]);
-    if (l == j) mine = t;
-  }
-  if (l >= ta - w0 && l < step - w0) a.z.rowsq[(size_t)row * kLzWin + l] = mine;
-  if (l == 0) a.z.row_step[row] = step;
-}
 
 __global__ __launch_bounds__(256) void k_lazy_catchup(LazyArgs a) {
   tick(a.ticks, 0);
   lazy_catchup_row(a, a.state->step_fwd, a.w0[0], blockIdx.x, 0);
-  tick(a.ticks, 1);
-}
-
-// head(t) — and, lazy dense Adam with the next batch already prepared (n_head < gridDim.x), beside it the catch-up of
-// the rows of batch t + 1 that batch t does NOT touch (fwd(t) marked its rows): workgroups [n_head, gridDim.x) bring
-// them up to step t + 1 while the forty head workgroups, bwd and the sparse step of batch t run — the rows are
-// disjoint from everything those read or write, so no order between them matters, and the next step starts at fwd.
-// (Step t itself is an L2-only step for them.)  Round 3 ran this catch-up as the second half of k_lazy_adam(t), on
-// the critical path behind bwd: 19 us for that launch; here it hides behind a head launch that used 40 of 256 CUs.
-template <int kAct, int kLoss>
-__global__ __launch_bounds__(kHeadThreads) void k_head(HeadArgs a, LazyArgs z, int n_head) {
-  __shared__ float scratch[kHeadCols * 16];
-  tick(a.ticks, 0);
-  const anirec_state *st = a.state;
-  if ((int)blockIdx.x >= n_head) {
-    const int step = st->step_fwd, w0 = z.w0[0];
-    if (step + 1 < z.n_steps && step + 1 - w0 <= kLzWin)
-      lazy_catchup_row(z, step + 1, w0, z.cu_lo + (int)blockIdx.x - n_head, step + 1);
-    tick(a.ticks, 1);
-    return;
-  }
-  const HeadIn in = {st->step_fwd, st->w, st->b, st->gamma, st->beta};
-  head_block<kAct, kLoss>(a, in, blockIdx.x, n_head, scratch);
-  tick(a.ticks, 1);
-}
-
-// the same launch with the Keras metrics of m (anirec_trainer_set_metrics / anirec_dist_stepper_set_metrics).  ALL of
-// its LDS is one array — the block-sum scratch, then the AUC histogram — since a second __shared__ object can make
-// hipcc wait vmcnt(0) in front of LDS accesses (the histogram is zeroed before the first barrier of head_block)
-template <int kAct, int kLoss>
-__global__ __launch_bounds__(kHeadThreads) void k_head_metrics(HeadArgs a, LazyArgs z, int n_head, MetricArgs m) {
-  __shared__ float lds[kHeadCols * 16 + 2 * kAucBins];
-  tick(a.ticks, 0);
-  const anirec_state *st = a.state;
-  if ((int)blockIdx.x >= n_head) {  // (the catch-up workgroups as in k_head)
-    const int step = st->step_fwd, w0 = z.w0[0];
-    if (step + 1 < z.n_steps && step + 1 - w0 <= kLzWin)
-      lazy_catchup_row(z, step + 1, w0, z.cu_lo + (int)blockIdx.x - n_head, step + 1);
-    tick(a.ticks, 1);
-    return;
-  }
-  if (m.mask & ANIREC_METRIC_AUC) {
-    for (int k = threadIdx.x; k < 2 * kAucBins; k += kHeadThreads) lds[kHeadCols * 16 + k] = 0.f;  // (0.f: 0u)
-  }
-  const HeadIn in = {st->step_fwd, st->w, st->b, st->gamma, st->beta};
-  head_block<kAct, kLoss, true>(a, in, blockIdx.x, n_head, lds, m);
   tick(a.ticks, 1);
 }
 
@@ -2105,150 +1224,18 @@ __global__ __launch_bounds__(256) void k_reg_init(const float *W, int row_lo, in
   reg_init_body<kD>(W, row_lo, n_rows, n_user_rows, regpart);
 }
 
-// flat Adam with an explicit gradient (unit-testable bit-exact stage)
-__global__ __launch_bounds__(256) void k_adam_flat(float *w, float *m, float *v, const float *g,
-                                                   size_t n, float alpha) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float ww = w[i], mm = m[i], vv = v[i];
-    adam_elem(ww, mm, vv, g[i], alpha);
-    w[i] = ww;
-    m[i] = mm;
-    v[i] = vv;
+__global__ __launch_bounds__(1024) void k_sum_regpart(anirec_state *st, const float *regpart) {
+  __shared__ float scratch[2 * 16];
+  float r[2] = {0.f, 0.f};
+  for (int i = threadIdx.x; i < 2 * ANIREC_ADAM_BLOCKS / 4; i += blockDim.x) {
+    const float4 v = reinterpret_cast<const float4 *>(regpart)[i];
+    r[i >= ANIREC_ADAM_BLOCKS / 4 ? 1 : 0] += (v.x + v.y) + (v.z + v.w);
   }
-}
-
-// flat one-slot update with an explicit gradient (anirec_opt_flat; the dense kernel's element rule)
-template <int kOpt>
-__global__ __launch_bounds__(256) void k_opt_flat(float *w, float *slot, const float *g, size_t n, float rate) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float ww = w[i], mm = 0.f, vv = kOpt == ANIREC_OPT_SGD ? 0.f : slot[i];
-    opt_elem<kOpt>(ww, mm, vv, g[i], rate);
-    w[i] = ww;
-    if (kOpt != ANIREC_OPT_SGD) slot[i] = vv;
-  }
-}
-
-// Self-test of the lazy replay's short sequences (anirec_selftest_lazy_math; tests only).  Square root: EVERY float
-// of the range the sequence is used on, [2^-96, 2^96], against the compiler's correctly rounded sqrtf — 1.6 x 10^9
-// inputs, exhaustive.  Divide: `n_div` pseudo-random (numerator, denominator) pairs drawn over the ranges the
-// replay admits, against the IEEE `/` (the sequence is the compiler's own Markstein chain without its scaling and
-// fix-up steps, so this is a regression guard, not the argument).  counts[0] += sqrt mismatches, counts[1] += divide
-// mismatches.
-template <int kVar>
-__global__ __launch_bounds__(256) void k_selftest_lazy_math(unsigned long long n_div, unsigned long long *counts) {
-  const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long nth = (unsigned long long)gridDim.x * blockDim.x;
-  const uint32_t lo = __float_as_uint(0x1p-96f), hi = __float_as_uint(0x1p96f);
-  unsigned long long bad_s = 0, bad_d = 0;
-  for (unsigned long long b = (unsigned long long)lo + 4 * tid; b <= hi; b += 4 * nth) {
-    Quad x;
-    x.a.x = __uint_as_float((uint32_t)min(b + 0, (unsigned long long)hi));
-    x.a.y = __uint_as_float((uint32_t)min(b + 1, (unsigned long long)hi));
-    x.b.x = __uint_as_float((uint32_t)min(b + 2, (unsigned long long)hi));
-    x.b.y = __uint_as_float((uint32_t)min(b + 3, (unsigned long long)hi));
-    const Quad s = sqrt4_normal<kVar>(x);
-    bad_s += __float_as_uint(s.a.x) != __float_as_uint(sqrtf(x.a.x));
-    bad_s += __float_as_uint(s.a.y) != __float_as_uint(sqrtf(x.a.y));
-    bad_s += __float_as_uint(s.b.x) != __float_as_uint(sqrtf(x.b.x));
-    bad_s += __float_as_uint(s.b.y) != __float_as_uint(sqrtf(x.b.y));
-  }
-  // numerators +-[2^-60, 2^60], denominators [1e-7, 2^48]: mantissa bits and exponent from a 64-bit mix of the index
-  auto mix = [](unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  };
-  auto draw = [&](unsigned long long h, int e_lo, int e_span, bool sign) {
-    const uint32_t man = (uint32_t)h & 0x7FFFFFu;
-    const uint32_t ex = (uint32_t)(127 + e_lo + (int)((h >> 23) % (unsigned)e_span));
-    const uint32_t sg = sign ? (uint32_t)((h >> 40) & 1u) << 31 : 0u;
-    return __uint_as_float(sg | (ex << 23) | man);
-  };
-  for (unsigned long long i = 4 * tid; i < n_div; i += 4 * nth) {
-    float nv[4], dv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const unsigned long long h1 = mix(2 * (i + k)), h2 = mix(2 * (i + k) + 1);
-      nv[k] = draw(h1, -60, 120, true);
-      dv[k] = fmaxf(draw(h2, -24, 72, false), kAdamEps);
-    }
-    const Quad n = {{nv[0], nv[1]}, {nv[2], nv[3]}}, d = {{dv[0], dv[1]}, {dv[2], dv[3]}};
-    const Quad q = div4_normal(n, d);
-    const float qs[4] = {q.a.x, q.a.y, q.b.x, q.b.y};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) bad_d += __float_as_uint(qs[k]) != __float_as_uint(nv[k] / dv[k]);
-  }
-  bad_s = (unsigned long long)wave_sum_d((double)bad_s);
-  bad_d = (unsigned long long)wave_sum_d((double)bad_d);
-  if ((threadIdx.x & 63) == 0) {
-    if (bad_s) atomicAdd(counts + 0, bad_s);
-    if (bad_d) atomicAdd(counts + 1, bad_d);
-  }
-}
-
-// Self-test of the replay's one-correction divide (anirec_selftest_lazy_div; tests only), see div4_normal.
-// kMode 0: the refined reciprocal against 1.0f / d on EVERY float d with bits in [lo, hi].  kMode 1: q1 against the
-// IEEE `/` on every significand pair n, d in [1, 2), d's significands [lo, hi) (one workgroup each) x all 2^23 n's.
-// kMode 2: the same with the uncorrected q0 = n y (the comparison's own sanity leg: it must report misses).
-// counts[0] += mismatches, counts[1] += operands checked, counts[2] / counts[3] = min / max bits of a failing d.
-template <int kMode>
-__global__ __launch_bounds__(256) void k_selftest_lazy_div(uint32_t lo, uint32_t hi, unsigned long long *counts) {
-  unsigned long long bad = 0, seen = 0;
-  uint32_t fmin = 0xFFFFFFFFu, fmax = 0u;
-  if (kMode == 0) {
-    const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long nth = (unsigned long long)gridDim.x * blockDim.x;
-    for (unsigned long long b = (unsigned long long)lo + 4 * tid; b <= hi; b += 4 * nth) {
-      uint32_t u[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) u[k] = (uint32_t)min(b + k, (unsigned long long)hi);
-      const Quad d = {{__uint_as_float(u[0]), __uint_as_float(u[1])}, {__uint_as_float(u[2]), __uint_as_float(u[3])}};
-      const Quad y = rcp4_refined(d);
-      const float ys[4] = {y.a.x, y.a.y, y.b.x, y.b.y};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (b + k > hi) continue;
-        ++seen;
-        if (__float_as_uint(ys[k]) != __float_as_uint(1.0f / __uint_as_float(u[k]))) {
-          ++bad;
-          fmin = min(fmin, u[k]);
-          fmax = max(fmax, u[k]);
-        }
-      }
-    }
-  } else {
-    const uint32_t db = 0x3F800000u | (lo + blockIdx.x);
-    const float dv = __uint_as_float(db);
-    const Quad d = {{dv, dv}, {dv, dv}};
-    for (uint32_t i = 4 * threadIdx.x; i < (1u << 23); i += 4 * blockDim.x) {
-      const Quad n = {{__uint_as_float(0x3F800000u | i), __uint_as_float(0x3F800000u | (i + 1))},
-                      {__uint_as_float(0x3F800000u | (i + 2)), __uint_as_float(0x3F800000u | (i + 3))}};
-      Quad q;
-      if (kMode == 1) {
-        q = div4_normal(n, d);
-      } else {
-        const Quad y = rcp4_refined(d);
-        q = n * y;
-      }
-      const float qs[4] = {q.a.x, q.a.y, q.b.x, q.b.y}, ns[4] = {n.a.x, n.a.y, n.b.x, n.b.y};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) bad += __float_as_uint(qs[k]) != __float_as_uint(ns[k] / dv);
-      seen += 4;
-    }
-    if (bad) fmin = fmax = db;
-  }
-  bad = (unsigned long long)wave_sum_d((double)bad);
-  seen = (unsigned long long)wave_sum_d((double)seen);
-  if ((threadIdx.x & 63) == 0) {
-    if (bad) atomicAdd(counts + 0, bad);
-    atomicAdd(counts + 1, seen);
-  }
-  if (fmin != 0xFFFFFFFFu) {
-    atomicMin(counts + 2, (unsigned long long)fmin);
-    atomicMax(counts + 3, (unsigned long long)fmax);
+  block_sum<2>(r, scratch);
+  if (threadIdx.x == 0) {
+    st->reg_user_sumsq = r[0];
+    st->reg_anime_sumsq = r[1];
+    st->reg_sumsq = r[0] + r[1];
   }
 }
 
@@ -2257,6 +1244,9 @@ __global__ __launch_bounds__(256) void k_selftest_lazy_div(uint32_t lo, uint32_t
 // catch-up's per-step one — the packed sequences, the row test, the redo by the
 // compiler's expansions — and, separately, by the dense kernel's adam_elem; fast[row] = 1 if every lane of the row
 // passed the short sequences' range test (the row alone would not trigger the redo).  wmv / out_*: [3][rows][kDim].
+// (It is here, beside the lazy kernels, and not with the other two self-tests in anirec_train_util.hip: it never reads
+// the sq[] that lazy_replay_slow returns, and in a unit where it is the only caller the compiler cuts that part out of
+// the unit's copy of the function.  Here it runs the very copy the lazy kernels run.)
 __global__ __launch_bounds__(256) void k_selftest_lazy_replay(const float *wmv, int rows, const float *alpha8, int nj,
                                                               const int32_t *j0s, float two_l2, float *out_lazy,
                                                               float *out_dense, int32_t *fast, int row_test) {
@@ -2308,224 +1298,19 @@ __global__ __launch_bounds__(256) void k_selftest_lazy_replay(const float *wmv, 
 }
 
 // ------------------------------------------------------------------------------------
-// validation (BN inference mode) and misc
-// ------------------------------------------------------------------------------------
-struct EvalArgs {
-  const float *W;
-  int n_user_rows;
-  const int32_t *user_idx, *anime_idx;
-  const float *rating;
-  int n;
-  anirec_state *state;
-  int act, loss;  // ANIREC_ACT_* / ANIREC_LOSS_* of the descriptor: read by k_eval_w only
-};
-
-// the head of one validation rating: prediction, data loss and (kMetrics) the Keras metric values
-template <int kAct, int kLoss, bool kMetrics>
-__device__ __forceinline__ void eval_terms(uint32_t mask, float y, float t, float &p, float &li,
-                                           float (&mv)[kMetricKinds]) {
-  float g;
-  head_grad<kAct, kLoss>(y, t, p, g);
-  li = head_loss<kAct, kLoss>(y, t, p);
-  if constexpr (kMetrics) metric_terms<kAct>(mask, y, t, p, mv);
-}
-// the same with the head as run-time values (the kernels of the other widths: one instantiation per width instead of
-// one per width, activation and loss); every case is the instantiation above
-template <int kAct, bool kMetrics>
-__device__ __forceinline__ void eval_terms_loss(int loss, uint32_t mask, float y, float t, float &p, float &li,
-                                                float (&mv)[kMetricKinds]) {
-  switch (loss) {
-    case ANIREC_LOSS_MSE: return eval_terms<kAct, ANIREC_LOSS_MSE, kMetrics>(mask, y, t, p, li, mv);
-    case ANIREC_LOSS_MAE: return eval_terms<kAct, ANIREC_LOSS_MAE, kMetrics>(mask, y, t, p, li, mv);
-    case ANIREC_LOSS_HUBER: return eval_terms<kAct, ANIREC_LOSS_HUBER, kMetrics>(mask, y, t, p, li, mv);
-    case ANIREC_LOSS_LOGCOSH: return eval_terms<kAct, ANIREC_LOSS_LOGCOSH, kMetrics>(mask, y, t, p, li, mv);
-    default: return eval_terms<kAct, ANIREC_LOSS_BCE, kMetrics>(mask, y, t, p, li, mv);
-  }
-}
-template <bool kMetrics>
-__device__ __forceinline__ void eval_terms_any(int act, int loss, uint32_t mask, float y, float t, float &p, float &li,
-                                               float (&mv)[kMetricKinds]) {
-  switch (act) {
-    case ANIREC_ACT_LINEAR: return eval_terms_loss<ANIREC_ACT_LINEAR, kMetrics>(loss, mask, y, t, p, li, mv);
-    case ANIREC_ACT_TANH: return eval_terms_loss<ANIREC_ACT_TANH, kMetrics>(loss, mask, y, t, p, li, mv);
-    case ANIREC_ACT_RELU: return eval_terms_loss<ANIREC_ACT_RELU, kMetrics>(loss, mask, y, t, p, li, mv);
-    case ANIREC_ACT_SOFTPLUS: return eval_terms_loss<ANIREC_ACT_SOFTPLUS, kMetrics>(loss, mask, y, t, p, li, mv);
-    default: return eval_terms_loss<ANIREC_ACT_SIGMOID, kMetrics>(loss, mask, y, t, p, li, mv);
-  }
-}
-
-// one row group per validation rating (1024 / kD ratings per workgroup).  kAct / kLoss >= 0: the head as template
-// parameters (k_eval, k_eval_metrics: the 128-wide kernels); < 0: a.act / a.loss (k_eval_w).  kMetrics: also the Keras
-// metrics of m
-template <int kAct, int kLoss, bool kMetrics, int kD>
-__device__ __forceinline__ void eval_body(const EvalArgs &a, const MetricArgs &m) {
-  constexpr int kG = kD / 4, kRpb = 256 / kG;
-  __shared__ float sh[kMetrics ? 2 + kMetricKinds : 2][kRpb];
-  const anirec_state *st = a.state;
-  const float w = st->w, b = st->b;
-  const float inv = st->gamma * (1.0f / sqrtf(st->mov_var + kBnEps));
-  const float shift = st->beta - st->mov_mean * inv;
-  const int l32 = threadIdx.x & (kG - 1), h = threadIdx.x / kG;
-  const int i = blockIdx.x * kRpb + h;
-  float li = 0.f, se = 0.f;
-  float mv[kMetricKinds] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (i < a.n) {
-    float su, sa, dd;
-    pair_dots<kD>(reinterpret_cast<const float4 *>(a.W), a.user_idx[i], a.anime_idx[i] + a.n_user_rows,
-                  l32, su, sa, dd);
-    const float c = cos_from_dots(su, sa, dd);
-    const float y = (c * w + b) * inv + shift;
-    const float t = a.rating[i];
-    float p;
-    if constexpr (kAct >= 0) eval_terms<kAct, kLoss, kMetrics>(m.mask, y, t, p, li, mv);
-    else eval_terms_any<kMetrics>(a.act, a.loss, m.mask, y, t, p, li, mv);
-    se = (p - t) * (p - t);
-    if constexpr (kMetrics) {
-      if ((m.mask & ANIREC_METRIC_AUC) && l32 == 0) {  // a few ratings a workgroup: straight into the integer bins
-        const int bk = auc_bucket(p);
-        const uint32_t wt = auc_pos_mass(t);
-        if (wt) atomicAdd(&m.acc->auc_pos[bk], (unsigned long long)wt);
-        if (wt != ANIREC_AUC_ONE) atomicAdd(&m.acc->auc_neg[bk], (unsigned long long)(ANIREC_AUC_ONE - wt));
-      }
-    }
-  }
-  if (l32 == 0) {
-    sh[0][h] = li;
-    sh[1][h] = se;
-    if constexpr (kMetrics) {
-#pragma unroll
-      for (int k = 0; k < kMetricKinds; ++k) sh[2 + k][h] = mv[k];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double L = 0., E = 0.;
-    for (int k = 0; k < kRpb; ++k) {
-      L += sh[0][k];
-      E += sh[1][k];
-    }
-    // fp64 atomics: order-dependent only below 1e-16 relative, far under the fp32 History values
-    atomicAdd(&a.state->val_bce_sum, L);
-    atomicAdd(&a.state->val_se_sum, E);
-    if (blockIdx.x == 0) atomicAdd(&a.state->val_n, (double)a.n);
-    if constexpr (kMetrics) {
-#pragma unroll
-      for (int k = 0; k < kMetricKinds; ++k) {
-        if (!(m.mask & (1u << k))) continue;
-        double v = 0.;
-        for (int j = 0; j < kRpb; ++j) v += sh[2 + k][j];
-        atomicAdd(&m.acc->sum[k], v);
-      }
-    }
-  }
-}
-
-template <int kAct, int kLoss>
-__global__ __launch_bounds__(256) void k_eval(EvalArgs a) {
-  eval_body<kAct, kLoss, false, kDim>(a, MetricArgs{});
-}
-
-// k_eval that also adds the Keras metrics of m (anirec_eval_metrics)
-template <int kAct, int kLoss>
-__global__ __launch_bounds__(256) void k_eval_metrics(EvalArgs a, MetricArgs m) {
-  eval_body<kAct, kLoss, true, kDim>(a, m);
-}
-
-// validation at another width (anirec_eval_metrics_w), the head from a.act / a.loss
-template <bool kMetrics, int kD>
-__global__ __launch_bounds__(256) void k_eval_w(EvalArgs a, MetricArgs m) {
-  eval_body<-1, -1, kMetrics, kD>(a, m);
-}
-
-__global__ __launch_bounds__(1024) void k_sum_regpart(anirec_state *st, const float *regpart) {
-  __shared__ float scratch[2 * 16];
-  float r[2] = {0.f, 0.f};
-  for (int i = threadIdx.x; i < 2 * ANIREC_ADAM_BLOCKS / 4; i += blockDim.x) {
-    const float4 v = reinterpret_cast<const float4 *>(regpart)[i];
-    r[i >= ANIREC_ADAM_BLOCKS / 4 ? 1 : 0] += (v.x + v.y) + (v.z + v.w);
-  }
-  block_sum<2>(r, scratch);
-  if (threadIdx.x == 0) {
-    st->reg_user_sumsq = r[0];
-    st->reg_anime_sumsq = r[1];
-    st->reg_sumsq = r[0] + r[1];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gather_ratings(const int32_t *ui, const int32_t *ai,
-                                                        const float *t, const int64_t *perm,
-                                                        size_t n, int32_t *uo, int32_t *ao,
-                                                        float *to) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int64_t p = perm[i];
-    uo[i] = ui[p];
-    ao[i] = ai[p];
-    to[i] = t[p];
-  }
-}
-
-// ------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------
-static inline int table_rows(const anirec_train_desc *d) { return d->n_user_rows + d->n_anime_rows; }
-// first table row whose gradient travels through the dense buffer
-static inline int dense_lo_of(const anirec_train_desc *d) { return d->dense_mode == 2 ? 0 : d->n_user_rows; }
-
-// ---- which update the descriptor asks for ----
-static inline bool lazy_on(const anirec_train_desc *d) {
-  return d->lazy != 0 && d->lazy_state != nullptr && d->dense_mode == 0 && d->n_seg == 1;
-}
-// the user-sharded multi-GPU step with lazily updated user rows (the replicated anime rows stay dense: their
-// gradient is summed over the ranks every step and most of them are touched by the global batch anyway)
-static inline bool lazy_users(const anirec_train_desc *d) {
-  return d->lazy != 0 && d->lazy_state != nullptr && d->dense_mode == 1;
-}
-
-// the update rule: a known kind, and the lazy update (Adam's only) not asked for with another; a known head
-static int check_opt(const anirec_train_desc *d) {
-  if (!loss_ok(d->loss) || !act_ok(d->activation)) return ANIREC_EINVAL;
-  if (d->optimizer < ANIREC_OPT_ADAM || d->optimizer > ANIREC_OPT_ADAGRAD) return ANIREC_EINVAL;
-  if (d->lazy != 0 && d->optimizer != ANIREC_OPT_ADAM) return ANIREC_EINVAL;
-  return ANIREC_OK;
-}
-
-// dim: the row width of the tables (the *_w entry points; ANIREC_DIM otherwise).  Another width than ANIREC_DIM runs the
-// dense one-GPU step only
-static int check_desc(const anirec_train_desc *d, int dim = kDim) {
-  if (!dim_ok(dim)) return ANIREC_EINVAL;
-  if (!d || !d->W || !d->M || !d->V || !d->rowmap || !d->state || !d->workspace || !d->packets)
-    return ANIREC_EINVAL;
-  if (dim != kDim && (d->lazy != 0 || d->dense_mode != 0 || d->n_seg != 1)) return ANIREC_EINVAL;
-  if (d->max_batch < 1 || d->max_batch > ANIREC_MAX_BATCH) return ANIREC_EINVAL;
-  if (d->n_user_rows < 1 || d->n_anime_rows < 1 || d->arena_steps < 2) return ANIREC_EINVAL;
-  if (d->n_seg < 1 || d->n_seg > ANIREC_MAX_SEG || d->my_seg < 0 || d->my_seg >= d->n_seg)
-    return ANIREC_EINVAL;
-  if (d->dense_mode < 0 || d->dense_mode > 2) return ANIREC_EINVAL;
-  if (check_opt(d)) return ANIREC_EINVAL;
-  if (d->dense_mode) {
-    if (!d->dense_grad || d->dense_rows < table_rows(d) - dense_lo_of(d)) return ANIREC_EINVAL;
-    if (d->adam_row_lo < 0 || d->adam_row_hi < d->adam_row_lo || d->adam_row_hi > table_rows(d)) return ANIREC_EINVAL;
-  }
-  if (d->workspace_bytes < anirec_train_workspace_bytes_w(d->max_batch, d->arena_steps, dim))
-    return ANIREC_EWORKSPACE;
-  return ANIREC_OK;
-}
-
 static inline float *packet_ptr(const anirec_train_desc *d, int seg) {
   return d->packets + anirec_packet_floats(d->max_batch) * (size_t)seg;
 }
 
 // measurement hook armed (anirec_train_stage_ticks): kernels stamp their workgroups' start / end times
-static bool g_ticks_on = false;
+bool g_ticks_on = false;
 static double g_tick_sum_us[8];  // per kernel: sum of the launch durations since the hook was last read
 static int g_tick_launches[8];
-static inline unsigned long long *ticks_of(const TrainWs &w, int kernel) {
-  return g_ticks_on ? w.ticks + (size_t)kernel * 2 * ANIREC_ADAM_BLOCKS : nullptr;
-}
 // armed only: wait for the launch just made, turn its workgroups' stamps into ONE duration (max end - min start),
 // add it to the kernel's sum and clear the slot for the next launch
-static int ticks_collect(const TrainWs &w, int kernel, hipStream_t s) {
+int ticks_collect(const TrainWs &w, int kernel, hipStream_t s) {
   if (!g_ticks_on) return ANIREC_OK;
   static unsigned long long h[2 * ANIREC_ADAM_BLOCKS];
   unsigned long long *dev = w.ticks + (size_t)kernel * 2 * ANIREC_ADAM_BLOCKS;
@@ -2567,7 +1352,7 @@ static FwdArgs fwd_args(const anirec_train_desc *d, const TrainWs &w) {
   return a;
 }
 
-static int launch_fwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
+int launch_fwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   const FwdArgs a = fwd_args(d, w);
   float *pk = packet_ptr(d, d->my_seg);
   with_width(w.dim, [&](auto kd) {
@@ -2581,74 +1366,7 @@ static int launch_fwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t 
   return (int)hipGetLastError();
 }
 
-static HeadArgs head_args(const anirec_train_desc *d, const TrainWs &w) {
-  HeadArgs a;
-  a.state = d->state;
-  a.sched = d->sched;
-  a.packets = d->packets;
-  a.packet_floats = anirec_packet_floats(d->max_batch);
-  a.n_seg = d->n_seg;
-  a.my_seg = d->my_seg;
-  a.cap = d->max_batch;
-  a.arena_steps = d->arena_steps;
-  a.dy = w.dy;
-  a.hpart = w.hpart;
-  a.hpart_stride = w.hpart_stride;
-  a.pub = w.pub;
-  a.sel = w.sel;
-  a.l2 = d->l2;
-  a.ticks = ticks_of(w, 1);
-  return a;
-}
-
-static inline int head_blocks(const anirec_train_desc *d) {
-  return (d->max_batch + kHeadThreads - 1) / kHeadThreads * d->n_seg;
-}
-
-static LazyArgs lazy_args(const anirec_train_desc *d, const TrainWs &w, int ticks_slot);
-static inline int lazy_chunk_grid(const anirec_train_desc *d, const TrainWs &w);
-// The catch-up of the next batch's rows is cut in two slices of the chunk grid: blocks [0, head_share) ride in the
-// head launch, the rest beside the sparse step in k_lazy_adam's.  The user chunks come first in that grid and are
-// where the work is (the anime rows a batch touches are mostly current already).  Measured (S109M, one box,
-// fwd + head + bwd + lazy_adam by the in-kernel stamps): share 0 % (round 3's place: everything behind bwd) 37.9 us,
-// 35 % 34.8, 50 % 35.9, 65 % 36.2, 100 % 36.7 — the head launch, at the head's 109 VGPRs, holds four waves per
-// SIMD and its own forty workgroups leave it after 7 us; more than ~3 500 rows in it only move the tail from one
-// launch to the other.
-constexpr int kCatchupHeadPct = 35;
-static inline int catchup_head_share(const anirec_train_desc *d, const TrainWs &w) {
-  return (int)((long long)lazy_chunk_grid(d, w) * kCatchupHeadPct / 100);
-}
-
-// fuse_next (lazy update, the next batch's chunk table is in the arena): the launch also carries the catch-up
-// workgroups of that batch's rows.  m.mask != 0: the metrics instantiation (k_head_metrics)
-static int launch_head(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool fuse_next = false,
-                       MetricArgs m = {}) {
-  const HeadArgs a = head_args(d, w);
-  const int nh = head_blocks(d);
-  LazyArgs z;
-  memset(&z, 0, sizeof(z));
-  int extra = 0;
-  if (fuse_next && d->lazy != 0 && d->lazy_state != nullptr) {
-    z = lazy_args(d, w, 1);
-    z.ticks = nullptr;  // (the head's own stamps cover every workgroup of the launch)
-    extra = catchup_head_share(d, w);
-  }
-  // the output head is a template parameter: the default pair's instantiation is the kernel as it always was
-  with_act(d->activation, [&](auto act) {
-    with_loss(d->loss, [&](auto loss) {
-      if (m.mask)
-        hipLaunchKernelGGL((k_head_metrics<decltype(act)::value, decltype(loss)::value>), dim3(nh + extra),
-                           dim3(kHeadThreads), 0, s, a, z, nh, m);
-      else
-        hipLaunchKernelGGL((k_head<decltype(act)::value, decltype(loss)::value>), dim3(nh + extra),
-                           dim3(kHeadThreads), 0, s, a, z, nh);
-    });
-  });
-  if (int te = ticks_collect(w, 1, s)) return te;
-  return (int)hipGetLastError();
-}
-
-static int launch_densify(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
+int launch_densify(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   DensifyArgs g;
   g.dense_lo = dense_lo_of(d);
   g.n_rows = table_rows(d);
@@ -2693,7 +1411,7 @@ static BwdArgs bwd_args(const anirec_train_desc *d, const TrainWs &w) {
   return a;
 }
 
-static int launch_bwd_only(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool lazy = false) {
+int launch_bwd_only(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool lazy) {
   BwdArgs a = bwd_args(d, w);
   if (lazy) {  // the lazy update walks the chunk table itself: no row map to fill (or to clear)
     if (d->dense_mode == 1)
@@ -2709,7 +1427,7 @@ static int launch_bwd_only(const anirec_train_desc *d, const TrainWs &w, hipStre
   return (int)hipGetLastError();
 }
 
-static int launch_bwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
+int launch_bwd(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   int e = launch_bwd_only(d, w, s);
   if (!e && d->dense_mode) e = launch_densify(d, w, s);
   return e;
@@ -2769,7 +1487,7 @@ static inline int table_grid(const anirec_train_desc *d, const TrainWs &w) {
 
 // which: 0 = every row this rank updates + finish (one GPU; replicated multi-GPU modes), 1 = the user rows only (may
 // run while the anime gradient is still in the all-reduce: user-sharded mode), 2 = the anime rows + finish
-static int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, int which) {
+int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, int which) {
   AdamArgs a = adam_args(d, w);
   if (d->dense_mode == 2 && (d->adam_row_lo | d->adam_row_hi)) {  // reduce-scatter shard (possibly empty)
     a.row_lo = d->adam_row_lo;
@@ -2800,7 +1518,7 @@ static int launch_adam_full(const anirec_train_desc *d, const TrainWs &w, hipStr
 }
 
 // ---- lazy dense Adam: host side ----
-static LazyArgs lazy_args(const anirec_train_desc *d, const TrainWs &w, int ticks_slot) {
+LazyArgs lazy_args(const anirec_train_desc *d, const TrainWs &w, int ticks_slot) {
   LazyArgs a;
   a.W = d->W;
   a.M = d->M;
@@ -2831,13 +1549,8 @@ static LazyArgs lazy_args(const anirec_train_desc *d, const TrainWs &w, int tick
   return a;
 }
 
-// grid of the lazy kernels that walk the chunk table (a half-wave per chunk slot of the lazily updated tables)
-static inline int lazy_chunk_grid(const anirec_train_desc *d, const TrainWs &w) {
-  return ((lazy_users(d) ? 1 : 2) * w.capC + 7) / 8;
-}
-
 // every row is current as of `first_step` (every run ends flushed): open a window there
-static int lazy_begin(const anirec_train_desc *d, const TrainWs &w, int first_step, hipStream_t s) {
+int lazy_begin(const anirec_train_desc *d, const TrainWs &w, int first_step, hipStream_t s) {
   const LazyState z = lazy_carve(d->lazy_state, table_rows(d));
   ANIREC_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)z.row_step, first_step, (size_t)table_rows(d), s));
   ANIREC_HIP_CHECK(hipMemsetAsync(z.mark, 0, sizeof(int32_t) * (size_t)table_rows(d), s));  // (marks of an earlier schedule)
@@ -2845,47 +1558,14 @@ static int lazy_begin(const anirec_train_desc *d, const TrainWs &w, int first_st
   return ANIREC_OK;
 }
 
-// What a step of the lazy update launches besides fwd, head, bwd and the sparse step; ignored by the dense update.
-struct StepFlags {
-  bool catchup_first;  // the rows of this step's batch are not known to be current: a stand-alone catch-up launch
-  bool fuse_next;      // the NEXT step's batch is in the prep arena: this step's launches also catch its rows up
-  bool flush_after;    // a flush follows the step: its window is full, or the run ends with it
-};
-
-// The cadence of a run of steps walked in prepared blocks (a block: steps whose batches are all in the prep arena).
-// Only a block's first step needs a catch-up launch of its own, every step but a block's last fuses the next batch's
-// catch-up, and a flush follows every kLzWin steps and the last step of the run, so a run ends flushed.
-struct Walk {
-  int run_left = 0;              // steps of the run still to come
-  int blk_len = 0, blk_pos = 0;  // the prepared block the next step belongs to
-  int open = 0;                  // steps taken since the last flush
-  void begin(int n_steps) {
-    run_left = n_steps;
-    blk_len = blk_pos = open = 0;
-  }
-  void block(int n_steps) {
-    blk_len = n_steps;
-    blk_pos = 0;
-  }
-  bool in_block() const { return run_left > 0 && blk_pos < blk_len; }
-  StepFlags peek() const { return {blk_pos == 0, blk_pos + 1 < blk_len, open + 1 == kLzWin || run_left == 1}; }
-  StepFlags next() {  // the flags of the next step, which is taken
-    const StepFlags f = peek();
-    open = f.flush_after ? 0 : open + 1;
-    if (run_left > 0) --run_left;
-    if (blk_pos < blk_len) ++blk_pos;
-    return f;
-  }
-};
-
-static int launch_lazy_catchup(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
+int launch_lazy_catchup(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   hipLaunchKernelGGL(k_lazy_catchup, dim3(lazy_chunk_grid(d, w)), dim3(256), 0, s, lazy_args(d, w, 4));
   if (int e = ticks_collect(w, 4, s)) return e;
   return (int)hipGetLastError();
 }
 
 // the sparse step of the batch bwd has just processed
-static int launch_lazy_adam(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool fuse_next) {
+int launch_lazy_adam(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, bool fuse_next) {
   const int grid = lazy_chunk_grid(d, w);
   AdamArgs aa = adam_args(d, w);
   aa.ticks = nullptr;
@@ -2898,7 +1578,7 @@ static int launch_lazy_adam(const anirec_train_desc *d, const TrainWs &w, hipStr
   return (int)hipGetLastError();
 }
 
-static int lazy_flush(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
+int lazy_flush(const anirec_train_desc *d, const TrainWs &w, hipStream_t s) {
   LazyArgs a = lazy_args(d, w, 6);
   const int grid = stream_grid(a.lazy_rows);
   // the grid's share of each table (a function of the table sizes only: the same partial slots every window)
@@ -2919,7 +1599,7 @@ static int lazy_flush(const anirec_train_desc *d, const TrainWs &w, hipStream_t 
   return (int)hipGetLastError();
 }
 
-static int launch_prep(const anirec_train_desc *d, const TrainWs &w, int first_step, int n_steps,
+int launch_prep(const anirec_train_desc *d, const TrainWs &w, int first_step, int n_steps,
                        bool relative_to_cursor, hipStream_t s) {
   PrepArgs a;
   a.user_idx = d->user_idx;
@@ -2939,126 +1619,11 @@ static int launch_prep(const anirec_train_desc *d, const TrainWs &w, int first_s
   return (int)hipGetLastError();
 }
 
-// The part of a handle (anirec_trainer, anirec_dist_stepper) the block scheduler works on.
-struct RunHandle {
-  anirec_train_desc d;
-  TrainWs ws;
-  hipGraphExec_t exec = nullptr;  // the captured block of graph_steps steps
-  int graph_steps = 0;            // < 0: a capture failed, the handle runs eagerly from then on
-  MetricArgs metrics = {};        // the Keras metrics of every step (mask 0: none)
-};
-
-// host: a metric set the kernels implement for this descriptor (AUC needs p in [0, 1]: the sigmoid head)
-static int check_metrics(const anirec_train_desc *d, uint32_t mask) {
-  if (mask & ~kMetricBits) return ANIREC_EINVAL;
-  if ((mask & ANIREC_METRIC_AUC) && d->activation != ANIREC_ACT_SIGMOID) return ANIREC_EINVAL;
-  return ANIREC_OK;
-}
-
-// a handle's metric set; the captured graph holds the old kernel arguments: dropped
-static int set_metrics(RunHandle *h, uint32_t mask, anirec_metric_acc *acc) {
-  if (int e = check_metrics(&h->d, mask)) return e;
-  h->metrics = (mask && acc) ? MetricArgs{mask, acc} : MetricArgs{};
-  if (h->exec) (void)hipGraphExecDestroy(h->exec);
-  h->exec = nullptr;
-  if (h->graph_steps > 0) h->graph_steps = 0;
-  return ANIREC_OK;
-}
-
-// Runs steps [first_step, first_step + n_steps) of h's descriptor, `step(stream, flags)` enqueuing the launches of one
-// step.  With use_graph a block of G = min(32, arena_steps / 2) steps is captured once per handle and replayed: a
-// replay starts with the prep of the G steps AFTER it (relative to the device cursor), so no host work falls between
-// replays; the arena holds 2G steps.  The steps left over run eagerly, in arena-sized blocks prepared from the host —
-// except after a replay, which has prepared them already.  A failed capture returns ANIREC_ECAPTURE with nothing of
-// the run enqueued.
-template <class Step>
-static int run_blocks(RunHandle *h, hipStream_t s, int first_step, int n_steps, bool use_graph, Step step) {
-  const anirec_train_desc *d = &h->d;
-  int G = d->arena_steps / 2;
-  if (G > 32) G = 32;
-  // (stamped steps run eagerly)
-  const bool graph = use_graph && s != nullptr && G >= 4 && n_steps >= G && !g_ticks_on && h->graph_steps >= 0;
-  if (graph && !h->exec) {
-    hipGraph_t g = nullptr;
-    int e = ANIREC_ECAPTURE;
-    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
-      e = launch_prep(d, h->ws, G, G, true, s);  // steps cursor+G .. cursor+2G
-      Walk walk;  // a run of G steps in one block of G: a replay leaves the tables up to date
-      walk.begin(G);
-      walk.block(G);
-      for (int i = 0; i < G && !e; ++i) e = step(s, walk.next());
-      if (hipStreamEndCapture(s, &g) != hipSuccess || !g) e = ANIREC_ECAPTURE;
-    }
-    if (!e && hipGraphInstantiate(&h->exec, g, nullptr, nullptr, 0) != hipSuccess) e = ANIREC_ECAPTURE;
-    if (g) (void)hipGraphDestroy(g);
-    if (e) {
-      h->exec = nullptr;
-      (void)hipGetLastError();
-      return ANIREC_ECAPTURE;
-    }
-    h->graph_steps = G;
-  }
-  if (n_steps > 0 && (lazy_on(d) || lazy_users(d))) {
-    const int e = lazy_begin(d, h->ws, first_step, s);
-    if (e) return e;
-  }
-  int done = 0;
-  if (graph) {
-    const int e = launch_prep(d, h->ws, first_step, G, false, s);  // the first block; later ones by the graph
-    if (e) return e;
-    for (; n_steps - done >= G; done += G) ANIREC_HIP_CHECK(hipGraphLaunch(h->exec, s));
-  }
-  Walk walk;
-  walk.begin(n_steps - done);
-  while (done < n_steps) {
-    int blk = n_steps - done;
-    if (!graph) {  // (after replays the last one has prepared the tail)
-      if (blk > d->arena_steps) blk = d->arena_steps;
-      const int e = launch_prep(d, h->ws, first_step + done, blk, false, s);
-      if (e) return e;
-    }
-    walk.block(blk);
-    for (int i = 0; i < blk; ++i)
-      if (const int e = step(s, walk.next())) return e;
-    done += blk;
-  }
-  return ANIREC_OK;
-}
-
-// one step on one GPU: the dense update, or the lazy one with the launches its flags ask for
-static int train_step(const anirec_train_desc *d, const TrainWs &w, hipStream_t s, StepFlags f, MetricArgs m) {
-  const bool lazy = lazy_on(d);
-  int e;
-  if (lazy && f.catchup_first && (e = launch_lazy_catchup(d, w, s))) return e;
-  if ((e = launch_fwd(d, w, s))) return e;
-  if ((e = launch_head(d, w, s, lazy && f.fuse_next, m))) return e;
-  if ((e = launch_bwd_only(d, w, s, lazy))) return e;
-  if (!lazy) return launch_adam_full(d, w, s, 0);
-  if ((e = launch_lazy_adam(d, w, s, f.fuse_next))) return e;
-  return f.flush_after ? lazy_flush(d, w, s) : ANIREC_OK;
-}
-
 }  // namespace anirec
 
 using namespace anirec;
 
 extern "C" {
-
-// c[pcap] | t[pcap] | {count,0,0,0}, pcap = max_batch rounded up to 4 floats (16-B aligned rows)
-size_t anirec_packet_floats(int32_t max_batch) { return 2 * (size_t)packet_cap(max_batch) + 4; }
-
-size_t anirec_train_lazy_bytes(int32_t rows) {
-  if (rows < 1) return 0;
-  return 2 * ((sizeof(int32_t) * (size_t)rows + 255) / 256 * 256) + sizeof(float) * (size_t)rows * ANIREC_LAZY_WINDOW;
-}
-
-size_t anirec_train_workspace_bytes_w(int32_t max_batch, int32_t arena_steps, int32_t dim) {
-  if (max_batch < 1 || max_batch > ANIREC_MAX_BATCH || arena_steps < 2 || !dim_ok(dim)) return 0;
-  return carve(nullptr, max_batch, arena_steps, dim).total;
-}
-size_t anirec_train_workspace_bytes(int32_t max_batch, int32_t arena_steps) {
-  return anirec_train_workspace_bytes_w(max_batch, arena_steps, ANIREC_DIM);
-}
 
 int anirec_train_init_reg_w(const anirec_train_desc *d, int32_t dim, void *stream) {
   int rc = check_desc(d, dim);
@@ -3086,52 +1651,6 @@ int anirec_train_init_reg(const anirec_train_desc *d, void *stream) {
   return anirec_train_init_reg_w(d, ANIREC_DIM, stream);
 }
 
-int anirec_train_prep_w(const anirec_train_desc *d, int32_t dim, int32_t first_step, int32_t n_steps, void *stream) {
-  int rc = check_desc(d, dim);
-  if (rc) return rc;
-  if (!d->user_idx || !d->anime_idx || !d->sched) return ANIREC_EINVAL;
-  if (first_step < 0 || n_steps < 0 || first_step + n_steps > d->n_steps ||
-      n_steps > d->arena_steps)
-    return ANIREC_EINVAL;
-  if (n_steps == 0) return ANIREC_OK;
-  return launch_prep(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), first_step, n_steps, false,
-                     (hipStream_t)stream);
-}
-int anirec_train_prep(const anirec_train_desc *d, int32_t first_step, int32_t n_steps,
-                      void *stream) {
-  return anirec_train_prep_w(d, ANIREC_DIM, first_step, n_steps, stream);
-}
-
-int anirec_train_fwd_w(const anirec_train_desc *d, int32_t dim, void *stream) {
-  int rc = check_desc(d, dim);
-  if (rc) return rc;
-  if (!d->user_idx || !d->anime_idx || !d->rating || !d->sched) return ANIREC_EINVAL;
-  return launch_fwd(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream);
-}
-int anirec_train_fwd(const anirec_train_desc *d, void *stream) { return anirec_train_fwd_w(d, ANIREC_DIM, stream); }
-
-int anirec_train_head_w(const anirec_train_desc *d, int32_t dim, void *stream) {
-  int rc = check_desc(d, dim);
-  if (rc) return rc;
-  if (!d->sched) return ANIREC_EINVAL;
-  return launch_head(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream);
-}
-int anirec_train_head(const anirec_train_desc *d, void *stream) { return anirec_train_head_w(d, ANIREC_DIM, stream); }
-
-int anirec_train_bwd_w(const anirec_train_desc *d, int32_t dim, void *stream) {
-  int rc = check_desc(d, dim);
-  if (rc) return rc;
-  return launch_bwd(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream);
-}
-int anirec_train_bwd(const anirec_train_desc *d, void *stream) { return anirec_train_bwd_w(d, ANIREC_DIM, stream); }
-
-int anirec_train_adam_w(const anirec_train_desc *d, int32_t dim, void *stream) {
-  int rc = check_desc(d, dim);
-  if (rc) return rc;
-  return launch_adam_full(d, carve(d->workspace, d->max_batch, d->arena_steps, dim), (hipStream_t)stream, 0);
-}
-int anirec_train_adam(const anirec_train_desc *d, void *stream) { return anirec_train_adam_w(d, ANIREC_DIM, stream); }
-
 // Measurement hook (bench.py).  While armed, every training kernel launched through this library stamps the
 // constant-clock (100 MHz) time of each workgroup's first and last instruction into the workspace, and the launch
 // function waits for it and adds max(end) - min(start) over its workgroups to the kernel's sum.  This call returns,
@@ -3156,446 +1675,6 @@ int anirec_train_stage_ticks(const anirec_train_desc *d, int32_t enable, float *
   return ANIREC_OK;
 }
 
-int anirec_train_adam_part(const anirec_train_desc *d, int32_t which, void *stream) {
-  int rc = check_desc(d);
-  if (rc) return rc;
-  TrainWs w = carve(d->workspace, d->max_batch, d->arena_steps);
-  hipStream_t s = (hipStream_t)stream;
-  if ((which != 1 && which != 2) || d->dense_mode != 1) return ANIREC_EINVAL;
-  // lazy user rows are only kept current by the run's cadence (anirec_dist_stepper_begin / _block): a part on its own
-  // would update rows that are steps behind, or account into a window that was never opened
-  if (lazy_users(d)) return ANIREC_EINVAL;
-  return launch_adam_full(d, w, s, which);
-}
-
-// ---- multi-GPU step halves (one C call each; the caller issues the two collectives between them) ----------
-// (the graph of anirec_dist_run holds a block of steps, collectives included)
-struct anirec_dist_stepper : RunHandle {
-  hipStream_t side = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  Walk walk;  // lazy user rows: where the step-by-step callers are in their run and prepared block
-};
-
-int anirec_dist_stepper_create(const anirec_train_desc *d, anirec_dist_stepper **out) {
-  if (!out) return ANIREC_EINVAL;
-  int rc = check_desc(d);
-  if (rc) return rc;
-  if (!d->dense_mode) return ANIREC_EINVAL;
-  anirec_dist_stepper *h = new (std::nothrow) anirec_dist_stepper;
-  if (!h) return ANIREC_EINVAL;
-  h->d = *d;
-  h->ws = carve(d->workspace, d->max_batch, d->arena_steps);
-  if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&h->join, hipEventDisableTiming) != hipSuccess) {
-    anirec_dist_stepper_destroy(h);
-    return ANIREC_ENODEVICE;
-  }
-  *out = h;
-  return ANIREC_OK;
-}
-
-int anirec_dist_stepper_destroy(anirec_dist_stepper *h) {
-  if (!h) return ANIREC_EINVAL;
-  if (h->exec) (void)hipGraphExecDestroy(h->exec);
-  if (h->fork) (void)hipEventDestroy(h->fork);
-  if (h->join) (void)hipEventDestroy(h->join);
-  if (h->side) (void)hipStreamDestroy(h->side);
-  delete h;
-  return ANIREC_OK;
-}
-
-// ---- the three parts of a multi-GPU step (the collectives go between them) ----------------------------------
-// front: [lazy user rows: the catch-up of this batch's rows when no earlier step of the block has done it] + fwd
-static int dist_front(anirec_dist_stepper *h, hipStream_t s, bool catchup_first) {
-  int e;
-  if (lazy_users(&h->d) && catchup_first && (e = launch_lazy_catchup(&h->d, h->ws, s))) return e;
-  return launch_fwd(&h->d, h->ws, s);
-}
-
-// mid — after the all-gather of the head packets: head, bwd, and the densify pass that feeds the gradient
-// collective.  User-sharded mode: the update of this rank's user rows needs nothing from the collective, so it is
-// forked onto the stepper's side stream right behind bwd and runs beside densify + all-reduce: the dense Adam stream
-// over the user rows, or — lazy user rows — the sparse step of the rows the batch touched (the catch-up of the next
-// batch's rows rides in the head launch when `fuse_next`: its chunk table is in the arena).
-static int dist_mid(anirec_dist_stepper *h, hipStream_t s, bool fuse_next) {
-  const bool lz = lazy_users(&h->d);
-  int e;
-  if ((e = launch_head(&h->d, h->ws, s, lz && fuse_next, h->metrics))) return e;
-  if ((e = launch_bwd_only(&h->d, h->ws, s, lz))) return e;
-  if (h->d.dense_mode == 1) {
-    ANIREC_HIP_CHECK(hipEventRecord(h->fork, s));
-    ANIREC_HIP_CHECK(hipStreamWaitEvent(h->side, h->fork, 0));
-    if ((e = lz ? launch_lazy_adam(&h->d, h->ws, h->side, fuse_next) : launch_adam_full(&h->d, h->ws, h->side, 1)))
-      return e;
-    ANIREC_HIP_CHECK(hipEventRecord(h->join, h->side));
-  }
-  return launch_densify(&h->d, h->ws, s);
-}
-
-// back — after the gradient collective: the rows that needed it + the step finish [+ lazy user rows: the flush of
-// the window when `flush_after`]
-static int dist_back(anirec_dist_stepper *h, hipStream_t s, bool flush_after) {
-  int e;
-  if (h->d.dense_mode == 1) {
-    ANIREC_HIP_CHECK(hipStreamWaitEvent(s, h->join, 0));
-    e = launch_adam_full(&h->d, h->ws, s, 2);
-  } else {
-    e = launch_adam_full(&h->d, h->ws, s, 0);
-  }
-  if (!e && flush_after && lazy_users(&h->d)) e = lazy_flush(&h->d, h->ws, s);
-  return e;
-}
-
-// Callers that drive the step themselves (three C calls + their own collectives per step) say where they are:
-// begin(first_step, n_steps) once per run — the tables are current there, a lazy window opens — and block(n) after
-// every anirec_train_prep of n steps.  With lazy user rows both are REQUIRED (ANIREC_EINVAL from the step calls
-// otherwise: a run that is never told where it ends would leave the tables behind); without, they are no-ops.
-int anirec_dist_stepper_begin(anirec_dist_stepper *h, int32_t first_step, int32_t n_steps, void *stream) {
-  if (!h || first_step < 0 || n_steps < 0 || first_step + n_steps > h->d.n_steps) return ANIREC_EINVAL;
-  h->walk.begin(n_steps);
-  if (lazy_users(&h->d) && n_steps > 0) return lazy_begin(&h->d, h->ws, first_step, (hipStream_t)stream);
-  return ANIREC_OK;
-}
-
-int anirec_dist_stepper_block(anirec_dist_stepper *h, int32_t n_steps) {
-  if (!h || n_steps < 0 || n_steps > h->d.arena_steps) return ANIREC_EINVAL;
-  h->walk.block(n_steps);
-  return ANIREC_OK;
-}
-
-// (the walk advances at the back of a step: front and mid look at the step it is at)
-static bool outside_walk(const anirec_dist_stepper *h) { return lazy_users(&h->d) && !h->walk.in_block(); }
-
-int anirec_dist_step_front(anirec_dist_stepper *h, void *stream) {
-  if (!h || outside_walk(h)) return ANIREC_EINVAL;
-  return dist_front(h, (hipStream_t)stream, h->walk.peek().catchup_first);
-}
-
-int anirec_dist_step_mid(anirec_dist_stepper *h, void *stream) {
-  if (!h || outside_walk(h)) return ANIREC_EINVAL;
-  return dist_mid(h, (hipStream_t)stream, h->walk.peek().fuse_next);
-}
-
-int anirec_dist_step_back(anirec_dist_stepper *h, void *stream) {
-  if (!h || outside_walk(h)) return ANIREC_EINVAL;
-  return dist_back(h, (hipStream_t)stream, h->walk.next().flush_after);
-}
-
-// ---- multi-GPU: the whole loop in the library, RCCL called from here -----------------------------------------
-// The step sequence above driven from C: one call enqueues prep + n_steps x {fwd -> all-gather(packets) -> mid ->
-// all-reduce | reduce-scatter(dense grad) -> back [-> all-gather(W rows)]} on the engine's stream, the collectives
-// issued to RCCL on that same stream (no Python, no torch.distributed in the step).  RCCL is bound with dlopen — the
-// copy the process has already loaded (torch's) when there is one — so the library has no link-time dependency on
-// it and a box without RCCL still loads libanirec.
-struct RcclApi {
-  void *lib = nullptr;
-  decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-  decltype(&ncclCommInitRank) CommInitRank = nullptr;
-  decltype(&ncclCommDestroy) CommDestroy = nullptr;
-  decltype(&ncclAllGather) AllGather = nullptr;
-  decltype(&ncclAllReduce) AllReduce = nullptr;
-  decltype(&ncclReduceScatter) ReduceScatter = nullptr;
-  decltype(&ncclGroupStart) GroupStart = nullptr;
-  decltype(&ncclGroupEnd) GroupEnd = nullptr;
-};
-static RcclApi g_rccl;
-
-static int rccl_bind(void *lib) {
-  RcclApi a;
-  a.lib = lib;
-#define ANIREC_SYM(F)                                               \
-  a.F = reinterpret_cast<decltype(a.F)>(dlsym(lib, "nccl" #F));     \
-  if (!a.F) return ANIREC_ENODEVICE;
-  ANIREC_SYM(GetUniqueId)
-  ANIREC_SYM(CommInitRank)
-  ANIREC_SYM(CommDestroy)
-  ANIREC_SYM(AllGather)
-  ANIREC_SYM(AllReduce)
-  ANIREC_SYM(ReduceScatter)
-  ANIREC_SYM(GroupStart)
-  ANIREC_SYM(GroupEnd)
-#undef ANIREC_SYM
-  g_rccl = a;
-  return ANIREC_OK;
-}
-
-int anirec_rccl_load(const char *path_host) {
-  if (g_rccl.lib) return ANIREC_OK;
-  if (path_host && path_host[0]) {
-    void *l = dlopen(path_host, RTLD_NOW | RTLD_LOCAL);
-    return l ? rccl_bind(l) : ANIREC_ENODEVICE;
-  }
-  static const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-  for (int pass = 0; pass < 2; ++pass)  // first a copy that is already mapped (torch's), then a fresh load
-    for (const char *nm : names) {
-      void *l = dlopen(nm, RTLD_NOW | RTLD_LOCAL | (pass == 0 ? RTLD_NOLOAD : 0));
-      if (l && rccl_bind(l) == ANIREC_OK) return ANIREC_OK;
-    }
-  return ANIREC_ENODEVICE;
-}
-
-int anirec_rccl_unique_id(char *id_host) {
-  if (!id_host) return ANIREC_EINVAL;
-  if (!g_rccl.lib) return ANIREC_ENODEVICE;
-  ncclUniqueId id;
-  if (g_rccl.GetUniqueId(&id) != ncclSuccess) return ANIREC_ECOMM;
-  static_assert(sizeof(id) == ANIREC_RCCL_ID_BYTES, "ncclUniqueId size");
-  memcpy(id_host, &id, sizeof(id));
-  return ANIREC_OK;
-}
-
-struct anirec_dist_comm {
-  ncclComm_t comm;
-  int rank, world;
-};
-
-int anirec_dist_comm_create(const char *id_host, int32_t rank, int32_t world, anirec_dist_comm **out) {
-  if (!id_host || !out || world < 1 || world > ANIREC_MAX_SEG || rank < 0 || rank >= world) return ANIREC_EINVAL;
-  if (!g_rccl.lib) return ANIREC_ENODEVICE;
-  anirec_dist_comm *c = new (std::nothrow) anirec_dist_comm;
-  if (!c) return ANIREC_EINVAL;
-  ncclUniqueId id;
-  memcpy(&id, id_host, sizeof(id));
-  c->rank = rank;
-  c->world = world;
-  if (g_rccl.CommInitRank(&c->comm, world, id, rank) != ncclSuccess) {  // collective: every rank calls it
-    delete c;
-    return ANIREC_ECOMM;
-  }
-  *out = c;
-  return ANIREC_OK;
-}
-
-int anirec_dist_comm_destroy(anirec_dist_comm *c) {
-  if (!c) return ANIREC_EINVAL;
-  if (g_rccl.lib) (void)g_rccl.CommDestroy(c->comm);
-  delete c;
-  return ANIREC_OK;
-}
-
-#define ANIREC_RCCL_CHECK(expr)                      \
-  do {                                               \
-    if ((expr) != ncclSuccess) return ANIREC_ECOMM;  \
-  } while (0)
-
-// reduce-scatter form of the replicated tables: this rank's Adam only updates its row shard
-static inline bool row_sharded(const anirec_train_desc *d) {
-  return d->dense_mode == 2 && (d->adam_row_lo | d->adam_row_hi) != 0;
-}
-
-static int dist_one_step(anirec_dist_stepper *h, anirec_dist_comm *c, hipStream_t s, StepFlags f) {
-  const anirec_train_desc *d = &h->d;
-  int e;
-  if ((e = dist_front(h, s, f.catchup_first))) return e;
-  // BatchNorm sees the global batch: every rank's (c, t, count, mean, M2) packet, gathered in place
-  const size_t pf = anirec_packet_floats(d->max_batch);
-  ANIREC_RCCL_CHECK(g_rccl.AllGather(d->packets + pf * (size_t)c->rank, d->packets, pf, ncclFloat, c->comm, s));
-  if ((e = dist_mid(h, s, f.fuse_next))) return e;
-  float *g = d->dense_grad;
-  const size_t nd = (size_t)d->dense_rows;
-  if (row_sharded(d)) {
-    // rows and self-coefficient sums of this rank's shard only, in place (dense_rows is a multiple of the world size)
-    const size_t sr = nd / (size_t)c->world;
-    ANIREC_RCCL_CHECK(g_rccl.GroupStart());
-    ANIREC_RCCL_CHECK(g_rccl.ReduceScatter(g, g + (size_t)c->rank * sr * kDim, sr * kDim, ncclFloat, ncclSum, c->comm, s));
-    ANIREC_RCCL_CHECK(g_rccl.ReduceScatter(g + nd * kDim, g + nd * kDim + (size_t)c->rank * sr, sr, ncclFloat, ncclSum,
-                                           c->comm, s));
-    ANIREC_RCCL_CHECK(g_rccl.GroupEnd());
-  } else {
-    ANIREC_RCCL_CHECK(g_rccl.AllReduce(g, g, nd * (kDim + 1), ncclFloat, ncclSum, c->comm, s));
-  }
-  if ((e = dist_back(h, s, f.flush_after))) return e;
-  if (row_sharded(d)) {  // every rank updated its row shard: collect the updated rows of W (padded to whole shards)
-    const size_t sr = nd / (size_t)c->world;
-    ANIREC_RCCL_CHECK(g_rccl.AllGather(d->W + (size_t)c->rank * sr * kDim, d->W, sr * kDim, ncclFloat, c->comm, s));
-  }
-  return ANIREC_OK;
-}
-
-// use_graph: the blocks run_blocks captures hold their RCCL collectives and the side-stream fork / join too; every rank
-// replays in lockstep.  If the capture or the instantiation fails the loop falls back to eager launches for good.
-int anirec_dist_run(anirec_dist_stepper *h, anirec_dist_comm *c, int32_t first_step, int32_t n_steps, int32_t use_graph,
-                    void *stream) {
-  if (!h || !c || n_steps < 0 || first_step < 0 || first_step + n_steps > h->d.n_steps) return ANIREC_EINVAL;
-  if (!g_rccl.lib) return ANIREC_ENODEVICE;
-  if (c->world != h->d.n_seg || c->rank != h->d.my_seg) return ANIREC_EINVAL;
-  if (!h->d.user_idx || !h->d.anime_idx || !h->d.rating || !h->d.sched || !h->d.dense_grad) return ANIREC_EINVAL;
-  if (row_sharded(&h->d) && h->d.dense_rows % c->world) return ANIREC_EINVAL;
-  const auto step = [h, c](hipStream_t s, StepFlags f) { return dist_one_step(h, c, s, f); };
-  int e = run_blocks(h, (hipStream_t)stream, first_step, n_steps, use_graph != 0, step);
-  if (e == ANIREC_ECAPTURE) {
-    h->graph_steps = -1;
-    e = run_blocks(h, (hipStream_t)stream, first_step, n_steps, false, step);
-  }
-  return e;
-}
-
-// ---- one GPU: the whole loop ------------------------------------------------------------------------------
-struct anirec_trainer : RunHandle {};
-
-int anirec_trainer_create(const anirec_train_desc *d, anirec_trainer **out) {
-  return anirec_trainer_create_w(d, ANIREC_DIM, out);
-}
-
-// the handle carries the width (its carved workspace): _run, _set_metrics and _destroy are the same calls at every width
-int anirec_trainer_create_w(const anirec_train_desc *d, int32_t dim, anirec_trainer **out) {
-  if (!out) return ANIREC_EINVAL;
-  int rc = check_desc(d, dim);
-  if (rc) return rc;
-  if (d->n_seg != 1 || d->dense_mode) return ANIREC_EINVAL;  // multi-GPU drives the step halves itself
-  anirec_trainer *t = new (std::nothrow) anirec_trainer;
-  if (!t) return ANIREC_EINVAL;
-  t->d = *d;
-  t->ws = carve(d->workspace, d->max_batch, d->arena_steps, dim);
-  *out = t;
-  return ANIREC_OK;
-}
-
-int anirec_trainer_destroy(anirec_trainer *t) {
-  if (!t) return ANIREC_EINVAL;
-  if (t->exec) (void)hipGraphExecDestroy(t->exec);
-  delete t;
-  return ANIREC_OK;
-}
-
-// Runs steps [first_step, first_step + n_steps); first_step must equal the device cursor (state->step_fwd).
-int anirec_trainer_run(anirec_trainer *t, int32_t first_step, int32_t n_steps, int32_t use_graph,
-                       void *stream) {
-  if (!t || n_steps < 0 || first_step < 0 || first_step + n_steps > t->d.n_steps) return ANIREC_EINVAL;
-  if (!t->d.user_idx || !t->d.anime_idx || !t->d.rating || !t->d.sched) return ANIREC_EINVAL;
-  return run_blocks(t, (hipStream_t)stream, first_step, n_steps, use_graph != 0,
-                    [t](hipStream_t s, StepFlags f) { return train_step(&t->d, t->ws, s, f, t->metrics); });
-}
-
-int anirec_trainer_set_metrics(anirec_trainer *t, uint32_t mask, anirec_metric_acc *acc) {
-  if (!t) return ANIREC_EINVAL;
-  return set_metrics(t, mask, acc);
-}
-
-int anirec_dist_stepper_set_metrics(anirec_dist_stepper *h, uint32_t mask, anirec_metric_acc *acc) {
-  if (!h) return ANIREC_EINVAL;
-  return set_metrics(h, mask, acc);
-}
-
-int anirec_eval(const anirec_train_desc *d, const int32_t *user_idx, const int32_t *anime_idx,
-                const float *rating, int32_t n, void *stream) {
-  return anirec_eval_metrics(d, 0, nullptr, user_idx, anime_idx, rating, n, stream);
-}
-
-int anirec_eval_metrics(const anirec_train_desc *d, uint32_t mask, anirec_metric_acc *acc, const int32_t *user_idx,
-                        const int32_t *anime_idx, const float *rating, int32_t n, void *stream) {
-  return anirec_eval_metrics_w(d, ANIREC_DIM, mask, acc, user_idx, anime_idx, rating, n, stream);
-}
-
-int anirec_eval_metrics_w(const anirec_train_desc *d, int32_t dim, uint32_t mask, anirec_metric_acc *acc,
-                          const int32_t *user_idx, const int32_t *anime_idx, const float *rating, int32_t n,
-                          void *stream) {
-  if (!dim_ok(dim) || !d || !d->W || !d->state || !user_idx || !anime_idx || !rating || n < 0 || check_opt(d))
-    return ANIREC_EINVAL;
-  if (check_metrics(d, mask)) return ANIREC_EINVAL;
-  const MetricArgs m = (mask && acc) ? MetricArgs{mask, acc} : MetricArgs{};
-  if (n == 0) return ANIREC_OK;
-  EvalArgs a;
-  a.W = d->W;
-  a.n_user_rows = d->n_user_rows;
-  a.user_idx = user_idx;
-  a.anime_idx = anime_idx;
-  a.rating = rating;
-  a.n = n;
-  a.state = d->state;
-  a.act = d->activation;
-  a.loss = d->loss;
-  if (dim != kDim) {  // the head as run-time values: one kernel per width
-    with_width(dim, [&](auto kd) {
-      constexpr int kD = decltype(kd)::value, kRpb = 1024 / kD;
-      if constexpr (kD != kDim) {  // (nothing of k_eval_w is instantiated at 128)
-        const dim3 grid((n + kRpb - 1) / kRpb);
-        if (m.mask) hipLaunchKernelGGL((k_eval_w<true, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
-        else hipLaunchKernelGGL((k_eval_w<false, kD>), grid, dim3(256), 0, (hipStream_t)stream, a, m);
-      }
-    });
-    return (int)hipGetLastError();
-  }
-  with_act(d->activation, [&](auto act) {
-    with_loss(d->loss, [&](auto loss) {
-      if (m.mask)
-        hipLaunchKernelGGL((k_eval_metrics<decltype(act)::value, decltype(loss)::value>), dim3((n + 7) / 8),
-                           dim3(256), 0, (hipStream_t)stream, a, m);
-      else
-        hipLaunchKernelGGL((k_eval<decltype(act)::value, decltype(loss)::value>), dim3((n + 7) / 8), dim3(256), 0,
-                           (hipStream_t)stream, a);
-    });
-  });
-  return (int)hipGetLastError();
-}
-
-int anirec_adam_flat(float *w, float *m, float *v, const float *g, size_t n, float alpha,
-                     void *stream) {
-  if (!w || !m || !v || !g) return ANIREC_EINVAL;
-  if (n == 0) return ANIREC_OK;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_adam_flat, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, m,
-                     v, g, n, alpha);
-  return (int)hipGetLastError();
-}
-
-int anirec_opt_flat(int32_t kind, float *w, float *slot, const float *g, size_t n, float rate, void *stream) {
-  if (kind < ANIREC_OPT_SGD || kind > ANIREC_OPT_ADAGRAD || !w || !g || (kind != ANIREC_OPT_SGD && !slot))
-    return ANIREC_EINVAL;
-  if (n == 0) return ANIREC_OK;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipStream_t s = (hipStream_t)stream;
-  if (kind == ANIREC_OPT_SGD)
-    hipLaunchKernelGGL(k_opt_flat<ANIREC_OPT_SGD>, dim3((unsigned)blocks), dim3(256), 0, s, w, slot, g, n, rate);
-  else if (kind == ANIREC_OPT_RMSPROP)
-    hipLaunchKernelGGL(k_opt_flat<ANIREC_OPT_RMSPROP>, dim3((unsigned)blocks), dim3(256), 0, s, w, slot, g, n, rate);
-  else
-    hipLaunchKernelGGL(k_opt_flat<ANIREC_OPT_ADAGRAD>, dim3((unsigned)blocks), dim3(256), 0, s, w, slot, g, n, rate);
-  return (int)hipGetLastError();
-}
-
-int anirec_selftest_lazy_math(uint64_t n_div, uint64_t *counts2, void *stream) {
-  if (!counts2) return ANIREC_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  ANIREC_HIP_CHECK(hipMemsetAsync(counts2, 0, 2 * sizeof(uint64_t), s));
-  // ANIREC_SELFTEST_NEWTON=0|2 (the test's own sanity legs): the square root without its Newton correction (only
-  // faithful: the comparison must report misses) / with a second one, instead of the ONE the replay uses
-  const char *var = getenv("ANIREC_SELFTEST_NEWTON");
-  const int steps = var && (var[0] == '0' || var[0] == '2') ? var[0] - '0' : 1;
-  if (steps == 0)
-    hipLaunchKernelGGL(k_selftest_lazy_math<0>, dim3(8192), dim3(256), 0, s, (unsigned long long)n_div,
-                       reinterpret_cast<unsigned long long *>(counts2));
-  else if (steps == 2)
-    hipLaunchKernelGGL(k_selftest_lazy_math<2>, dim3(8192), dim3(256), 0, s, (unsigned long long)n_div,
-                       reinterpret_cast<unsigned long long *>(counts2));
-  else
-    hipLaunchKernelGGL(k_selftest_lazy_math<1>, dim3(8192), dim3(256), 0, s, (unsigned long long)n_div,
-                       reinterpret_cast<unsigned long long *>(counts2));
-  return (int)hipGetLastError();
-}
-
-int anirec_selftest_lazy_div(int32_t mode, uint32_t lo, uint32_t hi, uint64_t *counts4, void *stream) {
-  if (!counts4 || mode < 0 || mode > 2 || hi < lo) return ANIREC_EINVAL;
-  if (mode != 0 && hi > (1u << 23)) return ANIREC_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const uint64_t init[4] = {0, 0, ~0ull, 0};
-  ANIREC_HIP_CHECK(hipMemcpyAsync(counts4, init, sizeof(init), hipMemcpyHostToDevice, s));
-  ANIREC_HIP_CHECK(hipStreamSynchronize(s));  // (init lives on this stack frame)
-  unsigned long long *c = reinterpret_cast<unsigned long long *>(counts4);
-  if (mode == 0) {
-    hipLaunchKernelGGL(k_selftest_lazy_div<0>, dim3(8192), dim3(256), 0, s, lo, hi, c);
-  } else if (hi > lo) {
-    if (mode == 1)
-      hipLaunchKernelGGL(k_selftest_lazy_div<1>, dim3(hi - lo), dim3(256), 0, s, lo, hi, c);
-    else
-      hipLaunchKernelGGL(k_selftest_lazy_div<2>, dim3(hi - lo), dim3(256), 0, s, lo, hi, c);
-  }
-  return (int)hipGetLastError();
-}
-
 int anirec_selftest_lazy_replay(const float *wmv, int32_t rows, const float *alpha8, int32_t nj, const int32_t *j0,
                                 float two_l2, int32_t row_test, float *out_lazy, float *out_dense, int32_t *fast,
                                 void *stream) {
@@ -3603,19 +1682,6 @@ int anirec_selftest_lazy_replay(const float *wmv, int32_t rows, const float *alp
     return ANIREC_EINVAL;
   hipLaunchKernelGGL(k_selftest_lazy_replay, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream,
                      wmv, (int)rows, alpha8, (int)nj, j0, two_l2, out_lazy, out_dense, fast, (int)(row_test != 0));
-  return (int)hipGetLastError();
-}
-
-int anirec_gather_ratings(const int32_t *user_in, const int32_t *anime_in, const float *rating_in,
-                          const int64_t *perm, size_t n, int32_t *user_out, int32_t *anime_out,
-                          float *rating_out, void *stream) {
-  if (!user_in || !anime_in || !rating_in || !perm || !user_out || !anime_out || !rating_out)
-    return ANIREC_EINVAL;
-  if (n == 0) return ANIREC_OK;
-  size_t blocks = (n + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(k_gather_ratings, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                     user_in, anime_in, rating_in, perm, n, user_out, anime_out, rating_out);
   return (int)hipGetLastError();
 }
 

@@ -483,7 +483,7 @@ class TrainEngine:
             pass
 
 
-# ---- debug/test helper: python mirror of csrc/anirec_train.hip::carve() ----------------
+# ---- debug/test helper: python mirror of csrc/anirec_train.hpp::carve() ----------------
 def _align(x, a=256):
     return (x + a - 1) // a * a
 

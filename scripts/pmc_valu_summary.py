@@ -90,8 +90,17 @@ def blob(path):
     return hashlib.sha1(b"blob %d\0" % len(data) + data).hexdigest()
 
 
+def train_sources():
+    """Blob hashes of the training path's units and headers (csrc/anirec_train*), by file name.  bench.py reads the
+    anirec_train.hip key: the unit of the two kernels it takes counters for, k_adam and k_lazy_flush."""
+    csrc = "anime_recommendations_amd/csrc"
+    names = sorted(f for f in os.listdir(csrc) if f.startswith("anirec_train") and f.endswith((".hip", ".hpp")))
+    assert "anirec_train.hip" in names
+    return {f: blob(os.path.join(csrc, f)) for f in names}
+
+
 print(json.dumps({"workload": "bench.py --no-also --no-cpu-baseline --steps 96 --warmup 32 (S109M, lazy dense Adam)",
                   "tag": tag, "kernels": out,
-                  "sources": {"anirec_train.hip": blob("anime_recommendations_amd/csrc/anirec_train.hip")},
+                  "sources": train_sources(),
                   "note": "three separate rocprofv3 --pmc passes (scripts/pmc_valu.sh); SQ cycle counters in quad-cycles, "
                           "summed over the chip; per-launch means"}, indent=1))

@@ -75,6 +75,25 @@ def test_size_queries_need_no_gpu(lib):
     assert lib.anirec_topk_workspace_bytes(1000, 4) >= 4 * 1000 * 4
 
 
+def test_build_sources_are_exactly_the_csrc_units():
+    """No source is forgotten by the build and none is listed that is not there; every header is included by a unit
+    (directly or through another header)."""
+    files = os.listdir(build.CSRC)
+    hips = sorted(f for f in files if f.endswith(".hip"))
+    assert len(build.SOURCES) == len(set(build.SOURCES)) and sorted(build.SOURCES) == hips
+    includes = {f: set(re.findall(r'^\s*#include\s+"([^"/]+)"', open(os.path.join(build.CSRC, f)).read(), re.M))
+                for f in files}
+    reached = set()
+    todo = [h for f in hips for h in includes[f]]
+    while todo:
+        h = todo.pop()
+        if h not in reached:
+            assert h in includes, "%s is included and is not in csrc" % h
+            reached.add(h)
+            todo += includes[h]
+    assert reached == {f for f in files if f.endswith(".hpp")}
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, "anime_recommendations_amd")
     for dp, _, fs in os.walk(pkg):

@@ -1,4 +1,4 @@
-"""CPU restatement of the lazy replay's once-per-row range test (anirec_train.hip, lz_bound / lz_entry_ok): the
+"""CPU restatement of the lazy replay's once-per-row range test (anirec_train_lazy.hpp, lz_bound / lz_entry_ok): the
 L2-only Adam step in NumPy fp32 (every operation correctly rounded, as on the GPU), the entry test as the kernel
 computes it, and, for every admitted element, the bounds the kernel's comment proves — checked step by step over
 whole windows on operands drawn log-uniformly over many binades, most of them near the admission limits."""

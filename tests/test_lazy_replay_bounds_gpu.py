@@ -1,4 +1,4 @@
-"""GPU tests of the lazy replay's one-correction divide and its once-per-row range test (anirec_train.hip,
+"""GPU tests of the lazy replay's one-correction divide and its once-per-row range test (anirec_train_lazy.hpp,
 div4_normal / lz_bound / lz_entry_ok): the divide is checked by exhaustion — its reciprocal on every float of the
 denominator range, its quotient on every significand pair — and the replay is held bitwise to the dense update on
 rows built to sit at each edge of the range test, on both sides of it."""

@@ -28,7 +28,7 @@ N_U, N_A, B = 5000, 64, 2048
 STEPS = 11
 LAST = 777                                   # the last batch is short
 HEAVY = 6                                    # chunks from which a row takes more than one add_chunks<4> batch
-CAP_C = (B + B // 32 + 2 + 3) & ~3           # chunk slots per table (chunk_capacity in csrc/anirec_train.hip)
+CAP_C = (B + B // 32 + 2 + 3) & ~3           # chunk slots per table (chunk_capacity in csrc/anirec_train.hpp)
 SMALL = [32, 31, 64, 63, 160, 159, 192, 191]  # 1, 2, 5 and 6 chunks, full and one short
 
 # per step: {row: run length}; the rest of the batch goes to filler rows (anime: rows 20..59 in turn, at most two chunks
