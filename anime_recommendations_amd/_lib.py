@@ -62,6 +62,7 @@ FUSE_METHODS = {"rrf": FUSE_RRF, "minmax": FUSE_MINMAX}
 FUSE_MAX_SYS = 8            # ANIREC_FUSE_MAX_SYS: the most systems of one call
 FUSE_MAX_ITEMS = 20480      # anirec_fuse_max_items(): one row's sort image (8 B an item) in the LDS of a workgroup
 FUSE_MAX_RRF_C = 1 << 20    # the largest rrf_c: c + 1 + rank stays below 2^24, exact in fp32
+FUSE_MAX_GRID = 4095        # ANIREC_FUSE_MAX_GRID: the most weight vectors of anirec_fuse_rank_grid (BOOT_MAX_COL - 1)
 
 
 class AnirecError(RuntimeError):
@@ -305,6 +306,10 @@ PROTOTYPES = {
     "anirec_fuse_max_items": (_sz, []),
     "anirec_fuse_rows": (C.c_int, [C.POINTER(_vp), C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, C.POINTER(_f32), _i32,
                                    _i32, _vp, _i64, _vp]),
+    # the rank of every target under every weight vector of a grid (the weights: a device array)
+    "anirec_fuse_rank_grid_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "anirec_fuse_rank_grid": (C.c_int, [C.POINTER(_vp), C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32,
+                                        _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

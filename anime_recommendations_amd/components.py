@@ -950,6 +950,11 @@ ALS_DEFAULTS = {"factors": 64, "sweeps": 15, "cg_steps": 3, "alpha": 1.0, "reg":
 # rrf_c = 60 are the literature's defaults (Cormack, Clarke and Buettcher 2009); neither is tuned on this data.
 FUSED_BASELINES = ("hybrid",)
 HYBRID_DEFAULTS = {"systems": ("model", "itemknn", "als"), "weights": None, "method": "rrf", "rrf_c": 60}
+# fused systems whose weights are learned, beside FUSED_BASELINES (which stays as it is) and reported
+# after it.  hybrid_tuned: the hybrid's members, method and rrf_c with weights chosen from a grid: equal weights and
+# every vector of multiples of 1 / steps with sum 1, the best by ``metric`` on the other folds of users
+TUNED_BASELINES = ("hybrid_tuned",)
+HYBRID_TUNE_DEFAULTS = {"metric": "ndcg@10", "steps": 10, "folds": 2, "seed": 0}
 
 
 def _member_params(defaults, given, what):
@@ -1008,11 +1013,11 @@ def _system_source(name, tables, cols, params, users, device):
 
 
 def baseline_names(baseline):
-    """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES, FITTED_BASELINES, then
-    FUSED_BASELINES: None -> (), a name or a sequence of names; ValueError for anything else."""
+    """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES, FITTED_BASELINES,
+    FUSED_BASELINES, then TUNED_BASELINES: None -> (), a name or a sequence of names; ValueError for anything else."""
     if baseline is None:
         return ()
-    known = BASELINES + FITTED_BASELINES + FUSED_BASELINES
+    known = BASELINES + FITTED_BASELINES + FUSED_BASELINES + TUNED_BASELINES
     names = [baseline] if isinstance(baseline, str) else list(baseline)
     for b in names:
         if b not in known:
@@ -1043,7 +1048,8 @@ def _ci_columns(columns, boot, system, others, key):
 
 
 def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None,
-                   ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None, hybrid=None):
+                   ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None, hybrid=None,
+                   hybrid_tune=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -1068,7 +1074,17 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     and keys under the name hybrid.  ``hybrid``: a dict overriding HYBRID_DEFAULTS (systems: names of
     ``recs.HYBRID_SYSTEMS``; weights: None = all 1; method: rrf or minmax; rrf_c) — the literature's defaults, not tuned
     on this data.
-    A sequence of names gives each, in the order popularity, itemknn, als, hybrid.  None: none.
+    ``baseline="hybrid_tuned"``: the hybrid's members, method and rrf_c with LEARNED weights: every
+    target is ranked under every vector of ``recs.hybrid_weight_grid`` at once (``recs.hybrid_rank_grid``,
+    ``ops.fuse_rank_grid``), the listed users are dealt into folds (``recs.hybrid_fold_deal``) and a user's targets take
+    the ranks of the vector with the largest exact metric sum over the OTHER folds' users (``recs.hybrid_cross_fit``;
+    ties to the lowest grid index, equal weights first), so no target helps choose the weights it is ranked with and the
+    figures are free of selection leakage; the same columns and keys under the name hybrid_tuned, and the summary gains
+    hybrid_tuned_metric, hybrid_tuned_grid (the number of vectors), hybrid_tuned_fold_weights (one vector per fold) and
+    hybrid_tuned_weights (the best vector on ALL targets: what to pass to hybrid_recs, used for no reported figure).
+    ``hybrid_tune``: a dict overriding HYBRID_TUNE_DEFAULTS (metric: ndcg@K, hit_rate@K or mrr; steps; folds >= 2; seed);
+    an unknown metric, folds < 2 or a grid of more than 4095 vectors is a ValueError before any GPU use.
+    A sequence of names gives each, in the order popularity, itemknn, als, hybrid, hybrid_tuned.  None: none.
     ``compare_model``: a second model dict over the same id tables, ranked by a second ``ops.predict_rank`` on the same
     targets and bits and reported as the system ``compare`` (the baselines' columns and keys under that name).
     ``ci_replicates`` > 0: a Poisson bootstrap over the held-out USERS (``recs.bootstrap_metrics``), seeded
@@ -1083,10 +1099,16 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     baselines = baseline_names(baseline)
     ci_replicates, ci_level = recs.check_bootstrap(ci_replicates, ci_level)
     hyb_par = _member_params(HYBRID_DEFAULTS, hybrid, "hybrid")
+    tune_par = _member_params(HYBRID_TUNE_DEFAULTS, hybrid_tune, "hybrid_tune")
     members = ()
-    if "hybrid" in baselines:
+    if "hybrid" in baselines or "hybrid_tuned" in baselines:
         members, hyb_w, hyb_method, hyb_c = recs.check_hybrid(hyb_par["systems"], hyb_par["weights"], hyb_par["method"],
                                                               hyb_par["rrf_c"])
+    if "hybrid_tuned" in baselines:
+        tune_metric, _ = recs.hybrid_tune_metric(tune_par["metric"])
+        tune_grid = recs.hybrid_weight_grid(len(members), tune_par["steps"])
+        recs.hybrid_fold_deal(0, tune_par["folds"], tune_par["seed"])        # (the check of folds; dealt below)
+        tune_pick, tune_best = [0] * int(tune_par["folds"]), 0
     fitted = [s for s in recs.HYBRID_SYSTEMS if s in baselines or s in members]     # each fitted once, in this order
     params = _system_params({"itemknn": itemknn, "als": als}, fitted)
     U, A = _tables_of(model, table)
@@ -1117,6 +1139,15 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         if "hybrid" in baselines:
             base_rank["hybrid"] = recs.hybrid_rank([sources[m] for m in members], seen, row, anime, hyb_w, hyb_method,
                                                    hyb_c)
+        if "hybrid_tuned" in baselines:
+            grid_rank = recs.hybrid_rank_grid([sources[m] for m in members], seen, row, anime, tune_grid, hyb_method,
+                                              hyb_c)
+            sums, tune_best = recs.hybrid_fit_weights(grid_rank, row, len(users), tune_metric, table.n_anime)
+            tune_fold = recs.hybrid_fold_deal(len(users), tune_par["folds"], tune_par["seed"])
+            tune_pick = recs.hybrid_cross_fit(sums, tune_fold, tune_par["folds"])
+            pick = torch.as_tensor(np.asarray(tune_pick, np.int64)[tune_fold[np.asarray(row, np.int64)]],
+                                   device=grid_rank.device)
+            base_rank["hybrid_tuned"] = grid_rank[pick, torch.arange(len(row), device=grid_rank.device)]
     else:
         rank = np.zeros(0, np.int32)
     m = recs.ranking_metrics(rank, ks)
@@ -1134,6 +1165,10 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         for k in ks:
             summary["%s_hit_rate@%d" % (name, k)] = b["hit_rate"][k]
             summary["%s_ndcg@%d" % (name, k)] = b["ndcg"][k]
+    if "hybrid_tuned" in baselines:
+        summary.update({"hybrid_tuned_metric": tune_metric, "hybrid_tuned_grid": int(len(tune_grid)),
+                        "hybrid_tuned_fold_weights": [[float(w) for w in tune_grid[i]] for i in tune_pick],
+                        "hybrid_tuned_weights": [float(w) for w in tune_grid[tune_best]]})
     if ci_replicates:
         systems = dict([("model", rank)] + [(name, base_rank[name]) for name in others])
         boot = recs.bootstrap_metrics(systems, row, len(users), ks, ci_replicates, ci_seed, ci_level, unit_key=users,

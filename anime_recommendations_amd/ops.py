@@ -1165,24 +1165,21 @@ def check_fuse(n_sys, n, weights=None, method="rrf", rrf_c=60):
     return si, ni, ws, m, ci
 
 
-def fuse_rows(rows, weights=None, method="rrf", rrf_c=60, n=None, wbits=None, keep=None):
-    """Several systems' score rows fused into one (anirec_fuse_rows; DESIGN.md 4.19): ``rows`` a list of fp32 device
-    tensors, each [nq, ld] or a 1-D vector [>= n] shared by every row; the first ``n`` columns count (default: the
-    shortest ld).  Item j is eligible in row t when ``keep[j] != 0`` and bit j of ``wbits[t]`` ([nq, ceil(n/32)]) is
-    clear.  ``rrf``: the sum over systems of w_s / (rrf_c + 1 + the item's 0-based place among the row's eligible items
-    in that system, in rows_topk's order); ``minmax``: the sum of w_s * (x - lo) / (hi - lo) over the row's finite
-    eligible scores (1 for +inf, 0 for -inf and NaN).  Returns fp32 [nq, n]: NaN where an item is not eligible, so
-    ``rows_topk`` / ``rows_rank`` take it with the same masks.  Bit-reproducible; nothing synchronises.  ValueError as
-    ``check_fuse``; when every system is a shared vector, nq comes from ``wbits`` (else 1)."""
+def _fuse_systems(what, rows, n, wbits, check):
+    """The systems of ``fuse_rows`` / ``fuse_rank_grid`` as the library takes them.  ``check(n_sys, n)`` is the op's
+    ``check_*`` (run before any device use) with ``n`` the given one or the shortest row.  Returns (what ``check``
+    returned, the device, nq, the rows held contiguous — the caller keeps them until its call is enqueued —, their device
+    pointers and their pitches as host arrays).  ValueError naming ``what`` for a system that is no 1-D or 2-D tensor, an ``n`` past the
+    shortest row, or systems of different row counts."""
     rows = list(rows)
     mats = [r for r in rows if isinstance(r, torch.Tensor) and r.dim() == 2]
     lens = [int(r.shape[-1]) for r in rows if isinstance(r, torch.Tensor) and r.dim() in (1, 2)]
     if len(lens) != len(rows):
-        raise ValueError("fuse_rows: every system is a fp32 device tensor [nq, ld] or [n]")
-    n = (min(lens) if lens else 0) if n is None else n
-    n_sys, n, ws, m, rrf_c = check_fuse(len(rows), n, weights, method, rrf_c)
+        raise ValueError("%s: every system is a fp32 device tensor [nq, ld] or [n]" % what)
+    checked = check(len(rows), (min(lens) if lens else 0) if n is None else n)
+    n = checked[1]
     if min(lens) < n:
-        raise ValueError("fuse_rows: n = %d must be in 1 .. %d (the shortest row)" % (n, min(lens)))
+        raise ValueError("%s: n = %d must be in 1 .. %d (the shortest row)" % (what, n, min(lens)))
     _need_gpu()
     dev = rows[0].device
     if mats:
@@ -1193,17 +1190,89 @@ def fuse_rows(rows, weights=None, method="rrf", rrf_c=60, n=None, wbits=None, ke
     for r in rows:
         assert r.is_cuda and r.dtype == torch.float32 and r.device == dev, "fp32 device score rows on one device"
         if r.dim() == 2 and int(r.shape[0]) != nq:
-            raise ValueError("fuse_rows: every system holds the same number of rows (%d, got %d)" % (nq, r.shape[0]))
+            raise ValueError("%s: every system holds the same number of rows (%d, got %d)" % (what, nq, r.shape[0]))
         held.append(r.contiguous())
+    ptrs = (C.c_void_p * len(held))(*[r.data_ptr() for r in held])
+    lds = (C.c_int64 * len(held))(*[int(r.shape[1]) if r.dim() == 2 else 0 for r in held])
+    return checked, dev, nq, held, ptrs, lds
+
+
+def fuse_rows(rows, weights=None, method="rrf", rrf_c=60, n=None, wbits=None, keep=None):
+    """Several systems' score rows fused into one (anirec_fuse_rows; DESIGN.md 4.19): ``rows`` a list of fp32 device
+    tensors, each [nq, ld] or a 1-D vector [>= n] shared by every row; the first ``n`` columns count (default: the
+    shortest ld).  Item j is eligible in row t when ``keep[j] != 0`` and bit j of ``wbits[t]`` ([nq, ceil(n/32)]) is
+    clear.  ``rrf``: the sum over systems of w_s / (rrf_c + 1 + the item's 0-based place among the row's eligible items
+    in that system, in rows_topk's order); ``minmax``: the sum of w_s * (x - lo) / (hi - lo) over the row's finite
+    eligible scores (1 for +inf, 0 for -inf and NaN).  Returns fp32 [nq, n]: NaN where an item is not eligible, so
+    ``rows_topk`` / ``rows_rank`` take it with the same masks.  Bit-reproducible; nothing synchronises.  ValueError as
+    ``check_fuse``; when every system is a shared vector, nq comes from ``wbits`` (else 1)."""
+    (n_sys, n, ws, m, rrf_c), dev, nq, held, ptrs, lds = _fuse_systems(
+        "fuse_rows", rows, n, wbits, lambda n_sys, n: check_fuse(n_sys, n, weights, method, rrf_c))
     kp = _keep_bytes(keep, n, dev, "fuse_rows")
     wb = _watched(wbits, nq, n, dev)
     out = torch.empty(nq, n, dtype=torch.float32, device=dev)
     if nq == 0:
         return out
-    ptrs = (C.c_void_p * n_sys)(*[r.data_ptr() for r in held])
-    lds = (C.c_int64 * n_sys)(*[int(r.shape[1]) if r.dim() == 2 else 0 for r in held])
     wts = (C.c_float * n_sys)(*ws)
     _call("anirec_fuse_rows", ptrs, lds, n_sys, n, nq, wb, kp, wts, m, rrf_c, out, n)
+    return out
+
+
+FUSE_MAX_GRID = _lib.FUSE_MAX_GRID
+
+
+def check_fuse_grid(n_sys, n, weight_grid, method="rrf", rrf_c=60):
+    """The argument checks of ``fuse_rank_grid`` (no device needed): (n_sys, n, the grid as a contiguous fp32 NumPy
+    array [n_w, n_sys], the method as an ANIREC_FUSE_* value, rrf_c), or a ValueError naming the limit: everything
+    ``check_fuse`` refuses, a grid that is not [n_w, n_sys] with n_w in 1 .. 4095 (ANIREC_FUSE_MAX_GRID: one column of
+    ``rank_gain_rows`` per weight vector), and any weight vector ``check_fuse`` refuses (negative or not finite as fp32,
+    or all zero)."""
+    si, ni, _, m, ci = check_fuse(n_sys, n, None, method, rrf_c)
+    try:
+        host = weight_grid.detach().cpu().numpy() if isinstance(weight_grid, torch.Tensor) else weight_grid
+        with np.errstate(over="ignore"):
+            g = np.ascontiguousarray(np.asarray(host, dtype=np.float64).astype(np.float32))
+    except (TypeError, ValueError):
+        raise ValueError("fuse grid: the weight grid must be numbers [n_w, %d]" % si)
+    if g.ndim != 2 or g.shape[1] != si or not 1 <= g.shape[0] <= FUSE_MAX_GRID:
+        raise ValueError("fuse grid: the weight grid must be [n_w, n_sys = %d] with n_w in 1 .. %d (got shape %s)"
+                         % (si, FUSE_MAX_GRID, tuple(g.shape)))
+    bad = ~(np.isfinite(g) & (g >= 0)).all(axis=1) | ~(g > 0).any(axis=1)
+    if bad.any():
+        w = int(np.flatnonzero(bad)[0])
+        raise ValueError("fuse grid: weight vector %d = %r must be finite in fp32 and >= 0 and not all 0"
+                         % (w, g[w].tolist()))
+    return si, ni, g, m, ci
+
+
+def fuse_rank_grid(rows, weight_grid, method, rrf_c, target_row, target_anime, n=None, wbits=None, keep=None):
+    """The rank of every target under every weight vector of a grid (anirec_fuse_rank_grid): ``rows``,
+    ``n``, ``wbits`` and ``keep`` as ``fuse_rows`` takes them, ``weight_grid`` [n_w, n_sys] (host or device), target t
+    is (``target_row[t]``: a row, ``target_anime[t]``: an item that is eligible there).  Returns int32 [n_w, n_t] on the
+    device: ``rows_rank(fuse_rows(rows, weight_grid[w], ...), target_row, target_anime, wbits)[t]`` at [w, t], from one
+    sort of every system's row instead of one per weight vector; the layout is ``rank_gain_rows``' ranks.  ValueError as
+    ``check_fuse_grid``; AnirecError if the library raises its flag: a target out of range or not eligible in its row."""
+    (n_sys, n, grid, m, rrf_c), dev, nq, held, ptrs, lds = _fuse_systems(
+        "fuse_rank_grid", rows, n, wbits, lambda n_sys, n: check_fuse_grid(n_sys, n, weight_grid, method, rrf_c))
+    tr, ta = _i32(target_row, dev).reshape(-1), _i32(target_anime, dev).reshape(-1)
+    if tr.shape != ta.shape:
+        raise ValueError("fuse_rank_grid: target_row and target_anime must have one entry per target")
+    n_w, n_t = int(grid.shape[0]), int(tr.numel())
+    kp = _keep_bytes(keep, n, dev, "fuse_rank_grid")
+    wb = _watched(wbits, nq, n, dev)
+    (out,) = _outputs(dev, (torch.int32, n_w, n_t))
+    if n_t == 0:
+        return out
+    if nq == 0:
+        raise ValueError("fuse_rank_grid: target_row out of range (no rows)")
+    wg = torch.as_tensor(grid, device=dev)
+    ws = _workspace(None, dev, "anirec_fuse_rank_grid_workspace_bytes", n_sys, n, nq, m)
+    err = _err_flag(dev)
+    _call("anirec_fuse_rank_grid", ptrs, lds, n_sys, n, nq, wb, kp, m, rrf_c, wg, n_w, tr, ta, n_t, out, err, ws,
+          ws.numel())
+    if int(err.item()):
+        raise _lib.AnirecError("fuse_rank_grid: a target is out of range or not eligible in its own row (its watched "
+                               "bit is set or keep is 0)")
     return out
 
 

@@ -1017,6 +1017,124 @@ def hybrid_rank(sources, watched_bits, target_row, target_anime, weights=None, m
                              "hybrid_rank", own_bit_clear=True)
 
 
+# learned hybrid weights: every target's rank under a grid of weight vectors, and the best vector
+HYBRID_GRID_BATCH = 1024            # users per anirec_fuse_rank_grid call: a score row and a unit row per system each
+HYBRID_GRID_WS_BYTES = 1 << 30      # the batch shrinks until the call's workspace fits in this
+HYBRID_TUNE_METRICS = ("ndcg@K", "hit_rate@K", "mrr")
+
+
+def hybrid_weight_grid(n_sys, steps):
+    """The candidate weight vectors of a simplex grid, fp32 [n_w, n_sys]: row 0 all ones (the untuned default), then
+    every integer composition (i_0 .. i_{S-1}) of ``steps`` in ascending lexicographic order as fl32(i_s / steps):
+    n_w = 1 + C(steps + S - 1, S - 1).  ValueError for n_sys outside 1 .. 8, steps < 1, or more than 4095 rows
+    (``ops.FUSE_MAX_GRID``)."""
+    import math
+    from . import ops
+    n_sys, steps = int(n_sys), int(steps)
+    if not 1 <= n_sys <= ops.FUSE_MAX_SYS:
+        raise ValueError("hybrid_weight_grid: n_sys = %d must be in 1 .. %d" % (n_sys, ops.FUSE_MAX_SYS))
+    if steps < 1:
+        raise ValueError("hybrid_weight_grid: steps = %d must be >= 1" % steps)
+    n_w = 1 + math.comb(steps + n_sys - 1, n_sys - 1)
+    if n_w > ops.FUSE_MAX_GRID:
+        raise ValueError("hybrid_weight_grid: steps = %d over %d systems gives %d weight vectors, more than the %d one "
+                         "grid call ranks" % (steps, n_sys, n_w, ops.FUSE_MAX_GRID))
+    grid = np.asarray(_compositions(steps, n_sys), np.float64) / float(steps)
+    return np.concatenate([np.ones((1, n_sys), np.float32), grid.astype(np.float32)])
+
+
+def _compositions(total, parts):
+    """the tuples of ``parts`` non-negative integers with sum ``total``, in ascending lexicographic order"""
+    if parts == 1:
+        return [(total,)]
+    return [(i,) + rest for i in range(total + 1) for rest in _compositions(total - i, parts - 1)]
+
+
+def hybrid_rank_grid(sources, watched_bits, target_row, target_anime, weight_grid, method="rrf", rrf_c=60,
+                     batch=HYBRID_GRID_BATCH):
+    """``hybrid_rank`` under every weight vector of ``weight_grid`` [n_w, n_sys] at once (``ops.fuse_rank_grid``):
+    returns rank int32 [n_w, n_t] on the device, row w what ``hybrid_rank(..., weights=weight_grid[w])`` returns.  The
+    span loop of ``rows_rank_batched``: ``batch`` lists at a time (fewer where the call's workspace would pass
+    HYBRID_GRID_WS_BYTES), a span that holds no target is not scored, and no rank depends on the batch.  ValueError
+    before any GPU use as ``ops.check_fuse_grid`` and ``hybrid_rank``."""
+    from . import ops
+    if watched_bits is None:
+        raise ValueError("hybrid_rank_grid: watched_bits [n_lists, ceil(n_anime/32)] is needed")
+    if not isinstance(watched_bits, torch.Tensor):
+        watched_bits = torch.as_tensor(np.ascontiguousarray(watched_bits))
+    sources = list(sources)
+    n_lists = int(watched_bits.shape[0])
+    _, _, grid, _, rrf_c = ops.check_fuse_grid(len(sources), 1, weight_grid, method, rrf_c)
+    m_name = str(method).strip().lower()
+    # a row's units take n_sys * 4 bytes an item; 32 items a watched word is an upper bound that needs no scoring
+    per_row = len(sources) * 32 * max(1, int(watched_bits.shape[1])) * 4
+    spans = _spans(n_lists, min(int(batch), max(1, HYBRID_GRID_WS_BYTES // per_row)), "hybrid_rank_grid")
+    tr, ta = _targets("hybrid_rank_grid", target_row, target_anime, n_lists, watched_bits)
+    rank = None
+    for l0, l1 in spans:
+        sel = np.flatnonzero((tr >= l0) & (tr < l1))
+        if not sel.size:
+            continue
+        rows = [src(l0, l1) if callable(src) else src for src in sources]
+        r = ops.fuse_rank_grid(rows, grid, m_name, rrf_c, tr[sel] - l0, ta[sel], wbits=_span_bits(watched_bits, l0, l1))
+        if rank is None:
+            rank = torch.empty(int(grid.shape[0]), int(tr.size), dtype=torch.int32, device=r.device)
+        rank[:, torch.as_tensor(sel, device=rank.device)] = r
+    return torch.empty(int(grid.shape[0]), 0, dtype=torch.int32) if rank is None else rank
+
+
+def hybrid_tune_metric(metric):
+    """(name, k or None) of a tuning metric: ``ndcg@K`` / ``hit_rate@K`` with an integer K >= 1, or ``mrr``; ValueError
+    for anything else."""
+    name = str(metric).strip().lower()
+    if name == "mrr":
+        return name, None
+    head, _, k = name.partition("@")
+    if head in ("ndcg", "hit_rate") and k.isdigit() and int(k) >= 1:
+        return "%s@%d" % (head, int(k)), int(k)
+    raise ValueError("hybrid tuning metric %r is not one of %s" % (metric, ", ".join(HYBRID_TUNE_METRICS)))
+
+
+def hybrid_fit_weights(rank_grid, target_unit, n_units, metric, n_rows, units=None):
+    """Which weight vector of a grid ranks a set of units' targets best: ``rank_grid`` int32 [n_w, n_t] on the device
+    (``hybrid_rank_grid``), ``target_unit`` [n_t] each target's unit among ``n_units``, ``metric`` one of ndcg@K,
+    hit_rate@K, mrr, ``n_rows`` the length of the gain table (the number of anime).  The per-unit gain sums are the exact
+    int64 sums of ``ops.rank_gain_rows`` over ``rank_gain_tables``' fixed-point gains.  Returns (sums int64 NumPy
+    [n_units, n_w], best): ``best`` the index of the largest total over ``units`` (an index array or a bool mask; None:
+    every unit), ties to the lowest index, so that row 0 — equal weights — wins unless a vector is strictly better.
+    Integer sums: the choice does not depend on the order of anything."""
+    from . import ops
+    name, k = hybrid_tune_metric(metric)
+    tables, names, _ = rank_gain_tables([k if k is not None else 1], n_rows)
+    gain = tables[names.index(name)][None, :]
+    rows = ops.rank_gain_rows(rank_grid, target_unit, n_units, torch.as_tensor(gain.astype(np.int64)))
+    sums = np.asarray(_host(rows), np.int64)[:, :-1]
+    return sums, hybrid_best_weights(sums, units)
+
+
+def hybrid_fold_deal(n_units, folds, seed):
+    """int64 [n_units]: the fold of every unit, ``np.random.default_rng(seed).permutation(n_units) % folds``; ValueError
+    for folds < 2"""
+    folds = int(folds)
+    if folds < 2:
+        raise ValueError("hybrid tuning needs folds >= 2 (got %d): a fold's weights come from the other folds" % folds)
+    return np.random.default_rng(int(seed)).permutation(int(n_units)).astype(np.int64) % folds
+
+
+def hybrid_cross_fit(sums, fold, folds):
+    """[folds] grid indices: entry f is ``hybrid_best_weights`` over the units that are NOT in fold f, so no unit helps
+    choose the weights its own targets are ranked with"""
+    fold = np.asarray(fold, np.int64)
+    return [hybrid_best_weights(sums, fold != f) for f in range(int(folds))]
+
+
+def hybrid_best_weights(sums, units=None):
+    """the grid index with the largest total of ``sums`` [n_units, n_w] over ``units``; ties to the lowest index"""
+    s = np.asarray(sums, np.int64)
+    total = (s if units is None else s[np.asarray(units)]).sum(axis=0)
+    return int(np.argmax(total))
+
+
 # ----------------------------------------------------------------------------------------
 # confidence intervals: a Poisson bootstrap over users (DESIGN.md §4.16)
 # ----------------------------------------------------------------------------------------

@@ -8,7 +8,10 @@ slice alone, ``--baseline als`` those of an implicit-feedback ALS factorisation 
 gives several; the ``--itemknn_*`` and ``--als_*`` flags of the command line set their parameters, which are the usual
 library defaults and have not been tuned on this data), ``--baseline hybrid`` those of the fused score rows of several
 systems (``--hybrid_systems model,itemknn,als``, ``--hybrid_method rrf|minmax``, ``--hybrid_weights``, ``--hybrid_rrf_c``:
-command line only; equal weights and rrf_c = 60 are the literature's defaults, not tuned on this data either);
+command line only; equal weights and rrf_c = 60 are the literature's defaults, not tuned on this data either),
+``--baseline hybrid_tuned`` those of the same fusion with weights chosen from a grid, every user's targets ranked with
+the weights that scored best on the OTHER folds of users (``--hybrid_tune_metric``, ``--hybrid_tune_steps``,
+``--hybrid_tune_folds``, ``--hybrid_tune_seed``: command line only);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
 spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
 held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
@@ -70,6 +73,15 @@ CI_FLAGS = {
 # (components.HYBRID_DEFAULTS: equal weights and rrf_c = 60, the literature's defaults, not tuned on this data)
 HYBRID_FLAGS = cli.HYBRID_FLAGS
 
+# optional and command-line only: how --baseline hybrid_tuned chooses its weights (components.HYBRID_TUNE_DEFAULTS)
+HYBRID_TUNE_FLAGS = {
+    "hybrid_tune_metric": (str, "ndcg@10", "the figure the weights are chosen by: ndcg@K, hit_rate@K or mrr"),
+    "hybrid_tune_steps": (int, 10, "the grid: equal weights and every weight vector of multiples of 1 / steps with sum 1"),
+    "hybrid_tune_folds": (int, 2, "folds of held-out users (>= 2): a user's targets are ranked with the weights that "
+                                  "scored best on the other folds"),
+    "hybrid_tune_seed": (int, 0, "the seed of the deal of users into folds"),
+}
+
 logger = C.setup_logging("evaluate")
 
 
@@ -99,7 +111,9 @@ def go(args):
                                       itemknn={f[len("itemknn_"):]: getattr(args, f) for f in ITEMKNN_FLAGS
                                                if hasattr(args, f)},
                                       als={f[len("als_"):]: getattr(args, f) for f in ALS_FLAGS if hasattr(args, f)},
-                                      compare_model=compare_model, hybrid=cli.hybrid_args(args), **ci)
+                                      compare_model=compare_model, hybrid=cli.hybrid_args(args),
+                                      hybrid_tune={f[len("hybrid_tune_"):]: getattr(args, f) for f in HYBRID_TUNE_FLAGS
+                                                   if hasattr(args, f)}, **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -126,7 +140,8 @@ def make_parser():
                         help="none, popularity (rank the same targets by the anime's number of training ratings), "
                              "itemknn (by an item-kNN over co-occurrence counts of the training ratings), als (by an "
                              "implicit-feedback ALS factorisation of the training ratings), hybrid (by the fused "
-                             "score rows of several of them and the model), or several separated by a comma")
+                             "score rows of several of them and the model), hybrid_tuned (the same with cross-fitted "
+                             "weights from a grid), or several separated by a comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
@@ -134,10 +149,10 @@ def make_parser():
 
 def make_cli_parser():
     """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*``,
-    ``--compare_model`` and ``--hybrid_*`` flags."""
+    ``--compare_model``, ``--hybrid_*`` and ``--hybrid_tune_*`` flags."""
     parser = make_parser()
     for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()) + \
-            list(HYBRID_FLAGS.items()):
+            list(HYBRID_FLAGS.items()) + list(HYBRID_TUNE_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

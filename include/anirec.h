@@ -1137,6 +1137,40 @@ int anirec_fuse_rows(const float *const *rows_host, const int64_t *ld_host, int3
                      const uint32_t *watched, const uint8_t *keep, const float *weight_host, int32_t method,
                      int32_t rrf_c, float *out, int64_t ld_out, void *stream);
 
+/* anirec_fuse_rank_grid: the rank of every held-out target under every candidate weight vector, without a fused row
+ * (DESIGN.md 4.22).  rows_host, ld_host, n_sys, n, watched, keep, method and rrf_c are anirec_fuse_rows' over n_rows
+ * rows; weights is a DEVICE array [n_w][n_sys]; target t is (target_row[t]: a row, target_anime[t]: an item).  For every
+ * w < n_w and t < n_targets
+ *   out_rank[w * n_targets + t] = #{ eligible j of row target_row[t] :
+ *                                    (score_key(fused_w(t, j)) << 32 | ~j)  >  (score_key(fused_w(t, a)) << 32 | ~a) },
+ * a = target_anime[t], fused_w(t, j) the value anirec_fuse_rows writes at out[t][j] with weight_host = weights[w]: the
+ * same fp32 steps (one correctly rounded division, or one product, per term; the adds in system order from +0; nothing
+ * contracted).  That is exactly what anirec_rows_rank returns for the target on that fused row under the same watched
+ * bits.  (With a keep, an item that is not kept holds NaN in the fused row, which anirec_rows_rank, knowing no keep,
+ * would count above a target whose own fused value is NaN; the grid counts eligible items alone.)  The layout is the
+ * ranks [n_sys][n_t] anirec_rank_gain_rows takes, one "system" per weight vector: hence ANIREC_FUSE_MAX_GRID, its
+ * column bound with one metric.
+ * A system's place in a row, and its min-max normalised score, do not depend on the weights: a first kernel (a
+ * workgroup per row, anirec_fuse_rows' own sort or extrema) writes per row, system and item the int32 c + 1 + r_s or
+ * the fp32 v_s to ws; a second (a workgroup per target and 64 weight vectors, a lane per vector) walks them and counts.
+ * *err_flag (device; overwritten by the call) becomes 1, and the ranks named are -1, for a target_row outside
+ * [0, n_rows), a target_anime outside [0, n), a target that is not eligible in its own row (out_rank[.][t]) and for a
+ * weight vector that holds a negative, NaN or infinite entry or is all zero (out_rank[w][.]); nothing is read through a
+ * bad index and the other targets and vectors are unaffected.
+ * ANIREC_EINVAL before any launch: what anirec_fuse_rows refuses for the arguments both have, n_w outside
+ * 1 .. ANIREC_FUSE_MAX_GRID, n_targets < 0, a NULL weights, out_rank or err_flag, a NULL target array with
+ * n_targets > 0, a ws that is NULL or not 16-byte aligned.  ws: anirec_fuse_rank_grid_workspace_bytes(n_sys, n, n_rows,
+ * method) bytes (0 for a bad argument; needs no GPU), less is ANIREC_EWORKSPACE; the result does not depend on what it
+ * held.  n_targets == 0 or n_rows == 0: ANIREC_OK, nothing launched.  No float atomics, nothing read back:
+ * stream-ordered and graph-capturable. */
+#define ANIREC_FUSE_MAX_GRID 4095
+size_t anirec_fuse_rank_grid_workspace_bytes(int32_t n_sys, int32_t n, int32_t n_rows, int32_t method);
+int anirec_fuse_rank_grid(const float *const *rows_host, const int64_t *ld_host, int32_t n_sys, int32_t n,
+                          int32_t n_rows, const uint32_t *watched, const uint8_t *keep, int32_t method, int32_t rrf_c,
+                          const float *weights, int32_t n_w, const int32_t *target_row, const int32_t *target_anime,
+                          int32_t n_targets, int32_t *out_rank, int32_t *err_flag, void *ws, size_t ws_bytes,
+                          void *stream);
+
 /* ------------------------------------------------------------------------- *
  *  IMPLICIT-FEEDBACK ALS (Hu, Koren, Volinsky 2008) with the warm-started conjugate-gradient solve of Takacs, Pilaszy
  *  and Tikk (2011): the learned baseline a ranking table is read against.  No model takes part.
