@@ -277,6 +277,9 @@ PROTOTYPES = {
     "anirec_itemknn_lds_items": (_sz, []),
     "anirec_itemknn_workspace_bytes": (_sz, [_i32, _i32]),
     "anirec_itemknn_scores": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "anirec_content_lds_tokens": (_sz, []),
+    "anirec_content_workspace_bytes": (_sz, [_i32, _i32]),
+    "anirec_content_scores": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     # onboarding lists: greedy maximum coverage over the rated-by bit rows, and the levels of any list
     "anirec_cover_step_words": (_sz, []),
     "anirec_cover_lds_words": (_sz, []),

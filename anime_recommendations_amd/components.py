@@ -288,6 +288,80 @@ def also_liked_frame(df, anime_df, syn_df, name, count, types=None, genres=None,
 
 
 # ----------------------------------------------------------------------------------------
+# content_recs: lists from all_anime.csv's own columns, for titles nobody has rated too
+# ----------------------------------------------------------------------------------------
+CONTENT_SHARED_TOKENS = 5    # tokens named per listed anime in Shared_tokens
+
+
+def content_universe(anime_df):
+    """The item index of the content components: every anime of all_anime.csv, in the frame's order."""
+    return anime_df.drop_duplicates("anime_id")["anime_id"].to_numpy()
+
+
+def _content_checks(columns, weight="rating"):
+    from . import recs
+    recs.content_history_weights([], weight)
+    return recs.check_content_fit(columns)[0]
+
+
+def content_similar_frame(anime_df, syn_df, name, count, types=None, genres=None, columns=None):
+    """The anime closest to the query anime by content: no model and no rating takes part, so the query and the listed
+    anime may have no rating at all.  The items are every row of ``anime_df``; their TF-IDF rows come from ``columns``
+    (default CONTENT_COLUMNS; ``recs.content_fit``), the list from ``recs.content_similar`` over the anime that pass the
+    optional Type / Genre filters.  Returns (frame, filename): similar_anime's columns with the content cosine as
+    ``Similarity``, then ``Shared_tokens``: the (at most CONTENT_SHARED_TOKENS) tokens both rows carry with the largest
+    product of weights, joined by " | "."""
+    from . import recs
+    columns = _content_checks(CONTENT_COLUMNS if columns is None else columns)
+    anime_ids = content_universe(anime_df)
+    qid = find_anime_id(name, anime_df)
+    q = int(np.nonzero(anime_ids == qid)[0][0])
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    keep = filter_mask(meta, anime_df, types, genres)
+    fit = recs.content_fit(meta, columns)
+    k = _topk_count(count, "a_query_number", len(anime_ids) - 1)
+    idx, s = recs.content_similar(fit, [q], k, keep.astype(np.uint8))
+    idx, s = _np(idx)[0], _np(s)[0]
+    frame = _similar_anime_rows(meta, idx, s)
+    off, ti, tw = _np(fit["tok_offsets"]), _np(fit["tok_idx"]), _np(fit["tok_w"])
+    own = {int(v): float(w) for v, w in zip(ti[off[q]:off[q + 1]], tw[off[q]:off[q + 1]])}
+    shared = []
+    for j in idx[idx >= 0]:
+        both = [(-own[int(v)] * float(w), int(v)) for v, w in zip(ti[off[j]:off[j + 1]], tw[off[j]:off[j + 1]])
+                if int(v) in own]
+        shared.append(_SEP.join(fit["vocab"][v] for _, v in sorted(both)[:CONTENT_SHARED_TOKENS]))
+    frame["Shared_tokens"] = shared
+    return frame, clean(name) + "_content.csv"
+
+
+def content_recs_frame(df, anime_df, syn_df, user_id, n_recs, types=None, genres=None, columns=None, weight="rating",
+                       min_rating=0.0):
+    """One user's content-based list among the anime they have not rated: the items are every row of ``anime_df``, the
+    profile the weighted mean of the TF-IDF rows (``recs.content_fit`` over ``columns``, default CONTENT_COLUMNS) of the
+    user's ratings in ``df`` at or above ``min_rating`` (compared in fp32), weighted per ``weight``
+    (``recs.content_history_weights``); the list is ``recs.content_topk``'s over the unrated anime that pass the optional
+    Type / Genre filters.  Returns model_recs_frame's columns with ``Content_score`` in the place of ``Prediction``.
+    ValueError before any GPU use for an unknown column or weight and for a user without ratings."""
+    from . import recs
+    columns = _content_checks(CONTENT_COLUMNS if columns is None else columns, weight)
+    anime_ids = content_universe(anime_df)
+    mine = df[df.user_id == int(user_id)]
+    if not len(mine):
+        raise ValueError("user id %r has no rating in the main data frame" % (user_id,))
+    pos = pd.Series(np.arange(len(anime_ids)), index=anime_ids).reindex(mine.anime_id.to_numpy()).to_numpy()
+    r = mine.rating.to_numpy().astype(np.float32)
+    take = ~np.isnan(pos) & (r >= np.float32(min_rating))
+    hist, r = pos[take].astype(np.int32), r[take]
+    meta, bits = _filter_bits(anime_ids, anime_df, syn_df, types, genres)
+    bits = bits | _blocked_bits(~unwatched_mask(df, anime_ids, user_id)).view(np.int32)
+    fit = recs.content_fit(meta, columns)
+    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
+    idx, s = recs.content_topk(fit, [0, len(hist)], hist, recs.content_history_weights(r, weight), k, bits)
+    idx, s = _np(idx)[0], _np(s)[0]
+    return _model_recs_rows(meta, idx, s).rename(columns={"Prediction": "Content_score"})
+
+
+# ----------------------------------------------------------------------------------------
 # onboarding: which anime to show a newcomer, from the ratings alone (DESIGN.md §4.18)
 # ----------------------------------------------------------------------------------------
 ONBOARD_STRATEGIES = ("coverage", "popularity")
@@ -672,7 +746,8 @@ def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, use
                       itemknn=None, als=None):
     """model_recs_frame with the list taken from several systems at once (``recs.hybrid_topk``): the same candidates
     (unwatched, indexed, Type / Genre filters), each member of ``systems`` (names of ``recs.HYBRID_SYSTEMS``) scoring
-    every anime for the user, the score rows fused per row under the candidates' mask (``ops.fuse_rows``: ``method`` rrf
+    every anime for the user (``content``, of ``recs.CONTENT_SYSTEMS``, with CONTENT_DEFAULTS and this call's metadata), the
+    score rows fused per row under the candidates' mask (``ops.fuse_rows``: ``method`` rrf
     with ``rrf_c``, or minmax; ``weights`` None = all 1) and the best ``n_recs`` taken by the exact select.  The item-kNN
     and ALS members are fitted from ``df`` (ITEMKNN_DEFAULTS / ALS_DEFAULTS overridden by ``itemknn`` / ``als``), the
     user's history and the liked pairs built as ``evaluate_frame`` builds them; popularity is the rating count.
@@ -683,7 +758,8 @@ def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, use
     no system, or a weights list of another length."""
     from . import ops, recs
     members, ws, method, rrf_c = recs.check_hybrid(systems, weights, method, rrf_c)
-    params = _system_params({"itemknn": itemknn, "als": als}, members)
+    content = {"meta": metadata_by_index(anime_ids, anime_df, syn_df)} if "content" in members else None
+    params = _system_params({"itemknn": itemknn, "als": als, "content": content}, members)
     row, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
     cols = None
     if set(members) - {"model"}:
@@ -955,6 +1031,12 @@ HYBRID_DEFAULTS = {"systems": ("model", "itemknn", "als"), "weights": None, "met
 # every vector of multiples of 1 / steps with sum 1, the best by ``metric`` on the other folds of users
 TUNED_BASELINES = ("hybrid_tuned",)
 HYBRID_TUNE_DEFAULTS = {"metric": "ndcg@10", "steps": 10, "folds": 2, "seed": 0}
+# the content-based system, beside the constants above (which stay as they are) and reported last: it
+# scores from all_anime.csv's columns, so it needs the metadata frame by index (the parameter ``meta``).  The defaults
+# are the plain choices (every categorical column, the rating as the weight); none is tuned on this data.
+CONTENT_BASELINES = ("content",)
+CONTENT_COLUMNS = ("Genres", "Type", "Source", "Studios", "Rating")
+CONTENT_DEFAULTS = {"columns": CONTENT_COLUMNS, "weight": "rating", "min_rating": 0.0, "min_df": 1, "max_df": 1.0}
 
 
 def _member_params(defaults, given, what):
@@ -967,7 +1049,8 @@ def _member_params(defaults, given, what):
 
 
 def _systems():
-    """One description per system that scores every anime for a list of users (the names of ``recs.HYBRID_SYSTEMS``),
+    """One description per system that scores every anime for a list of users (the names of ``recs.HYBRID_SYSTEMS`` and
+    ``recs.CONTENT_SYSTEMS``),
     which evaluate_frame and hybrid_recs_frame both go through: ``defaults`` the parameters a caller may override;
     ``check(par)`` the ValueErrors that need no GPU; ``fit(user, anime, rating, n_users, n_anime, par, device)`` the fit
     from training columns (the model has none: its fit is the caller's (U, A, head)); ``source(fit, users, cols, par)``
@@ -977,6 +1060,23 @@ def _systems():
     def itemknn_source(knn, users, cols, par):
         off, hist, _ = recs.history_csr(*cols[:3], users, min_rating=par["min_rating"])
         return recs.itemknn_rows_source(knn, off, hist)
+
+    def content_check(par):
+        recs.check_content_fit(par["columns"], par["min_df"], par["max_df"])
+        recs.content_history_weights([], par["weight"])
+        if par["meta"] is None:
+            raise ValueError("the content system scores from the anime metadata: give it the frame by index "
+                             "(content={'meta': ...}; evaluate: --anime_df)")
+
+    def content_fit(user, anime, rating, n_users, n_anime, par, device):
+        if len(par["meta"]) != int(n_anime):
+            raise ValueError("content: the metadata frame holds %d rows, the anime index %d" % (len(par["meta"]), n_anime))
+        return recs.content_fit(par["meta"], par["columns"], par["min_df"], par["max_df"], device=device)
+
+    def content_source(fit, users, cols, par):
+        off, hist, r = recs.history_csr(*cols[:3], users, min_rating=par["min_rating"])
+        w = None if str(par["weight"]).strip().lower() == "one" else recs.content_history_weights(r, par["weight"], off)
+        return recs.content_rows_source(fit, off, hist, w)
 
     def als_fit(user, anime, rating, n_users, n_anime, par, device):
         u, a, r = (recs._host(c) for c in (user, anime, rating))
@@ -993,7 +1093,9 @@ def _systems():
                             user, anime, rating, n_users, n_anime, par["min_rating"], int(par["neighbours"]),
                             par["measure"], par["shrink"], par["min_support"], device=device)),
         "als": dict(defaults=ALS_DEFAULTS, fit=als_fit, source=lambda fit, users, cols, par: recs.als_rows_source(fit, users),
-                    check=lambda par: ops.check_als(par["factors"], par["cg_steps"], par["reg"], par["alpha"]))}
+                    check=lambda par: ops.check_als(par["factors"], par["cg_steps"], par["reg"], par["alpha"])),
+        "content": dict(defaults=dict(CONTENT_DEFAULTS, meta=None), check=content_check, fit=content_fit,
+                        source=content_source)}
 
 
 def _system_params(given, used):
@@ -1014,10 +1116,11 @@ def _system_source(name, tables, cols, params, users, device):
 
 def baseline_names(baseline):
     """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES, FITTED_BASELINES,
-    FUSED_BASELINES, then TUNED_BASELINES: None -> (), a name or a sequence of names; ValueError for anything else."""
+    FUSED_BASELINES, TUNED_BASELINES, then CONTENT_BASELINES: None -> (), a name or a sequence of names; ValueError for
+    anything else."""
     if baseline is None:
         return ()
-    known = BASELINES + FITTED_BASELINES + FUSED_BASELINES + TUNED_BASELINES
+    known = BASELINES + FITTED_BASELINES + FUSED_BASELINES + TUNED_BASELINES + CONTENT_BASELINES
     names = [baseline] if isinstance(baseline, str) else list(baseline)
     for b in names:
         if b not in known:
@@ -1049,7 +1152,7 @@ def _ci_columns(columns, boot, system, others, key):
 
 def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None,
                    ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None, hybrid=None,
-                   hybrid_tune=None):
+                   hybrid_tune=None, content=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -1084,7 +1187,14 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     hybrid_tuned_weights (the best vector on ALL targets: what to pass to hybrid_recs, used for no reported figure).
     ``hybrid_tune``: a dict overriding HYBRID_TUNE_DEFAULTS (metric: ndcg@K, hit_rate@K or mrr; steps; folds >= 2; seed);
     an unknown metric, folds < 2 or a grid of more than 4095 vectors is a ValueError before any GPU use.
-    A sequence of names gives each, in the order popularity, itemknn, als, hybrid, hybrid_tuned.  None: none.
+    ``baseline="content"``: the same targets under the same bits ranked by the content-based system:
+    TF-IDF item vectors from the metadata (``recs.content_fit``: no rating takes part in them), each listed user's profile
+    the weighted mean of the vectors of that user's TRAINING ratings at or above its threshold (``recs.content_rank``'s
+    ranks); the same columns and keys under the name content, and ``content`` is a member the hybrids take too.
+    ``content``: a dict overriding CONTENT_DEFAULTS (columns, weight: one of ``recs.CONTENT_WEIGHTS``, min_rating, min_df,
+    max_df) plus ``meta``: the metadata frame by the table's anime index (``metadata_by_index(table.anime_ids, ...)``),
+    without which asking for the system is a ValueError before any GPU use.
+    A sequence of names gives each, in the order popularity, itemknn, als, hybrid, hybrid_tuned, content.  None: none.
     ``compare_model``: a second model dict over the same id tables, ranked by a second ``ops.predict_rank`` on the same
     targets and bits and reported as the system ``compare`` (the baselines' columns and keys under that name).
     ``ci_replicates`` > 0: a Poisson bootstrap over the held-out USERS (``recs.bootstrap_metrics``), seeded
@@ -1109,8 +1219,8 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         tune_grid = recs.hybrid_weight_grid(len(members), tune_par["steps"])
         recs.hybrid_fold_deal(0, tune_par["folds"], tune_par["seed"])        # (the check of folds; dealt below)
         tune_pick, tune_best = [0] * int(tune_par["folds"]), 0
-    fitted = [s for s in recs.HYBRID_SYSTEMS if s in baselines or s in members]     # each fitted once, in this order
-    params = _system_params({"itemknn": itemknn, "als": als}, fitted)
+    fitted = [s for s in recs.HYBRID_SYSTEMS + recs.CONTENT_SYSTEMS if s in baselines or s in members]  # each once
+    params = _system_params({"itemknn": itemknn, "als": als, "content": content}, fitted)
     U, A = _tables_of(model, table)
     others = baselines + (("compare",) if compare_model is not None else ())
     if compare_model is not None:

@@ -1060,6 +1060,57 @@ def itemknn_scores(nbr_idx, nbr_sim, offsets, hist_idx, hist_w=None, workspace=N
                    "itemknn_scores: history, neighbour table or offsets out of range, or an unusable term")
 
 
+def check_content(tok_offsets, tok_idx, tok_w, n_tokens):
+    """The argument checks of ``content_scores`` that need no device: (n_items, n_tokens, nnz) as ints, or a ValueError
+    for an item CSR whose offsets hold fewer than two entries, whose ``tok_idx`` and ``tok_w`` differ in length, or for
+    ``n_tokens`` < 1.  Only shapes are looked at, so device tensors are not read."""
+    n_tokens = int(n_tokens)
+    n_off, nnz, n_w = (int(np.prod(tuple(x.shape))) for x in (tok_offsets, tok_idx, tok_w))
+    if n_off < 2:
+        raise ValueError("content_scores: tok_offsets holds n_items + 1 >= 2 entries")
+    if nnz != n_w:
+        raise ValueError("content_scores: tok_idx and tok_w must have one entry per token slot (%d and %d)" % (nnz, n_w))
+    if n_tokens < 1:
+        raise ValueError("content_scores: n_tokens = %d must be >= 1" % n_tokens)
+    return n_off - 1, n_tokens, nnz
+
+
+def content_scores(tok_offsets, tok_idx, tok_w, n_tokens, hist_offsets, hist_idx, hist_w=None, workspace=None,
+                   check=True):
+    """Content-based score rows (anirec_content_scores): the item CSR ``tok_offsets`` int64 [n_items +
+    1] / ``tok_idx`` int32 / ``tok_w`` fp32 on the device over ``n_tokens`` token ids, list l's history
+    ``hist_idx[hist_offsets[l]:hist_offsets[l + 1]]`` with the weights ``hist_w`` (None: 1; a negative weight pushes
+    away).  The profile of a list is the weighted mean of its items' rows, summed as int64 multiples of 2^-30 and
+    divided once; out[l, j] is the fp32 fma chain of item j's row against it: exact, whatever the order.
+    Returns fp32 [n_lists, n_items].  Raises ValueError for an item CSR that does not rise from 0 to its length, a
+    history item or token id out of range, an offsets pair that is not inside the history, a weight that is not finite
+    or a term above 1024; with ``check=False`` returns (out, device flag), the item CSR's offsets are trusted and
+    nothing synchronises."""
+    n, n_tokens, nnz = check_content(tok_offsets, tok_idx, tok_w, n_tokens)
+    _need_gpu()
+    assert isinstance(tok_offsets, torch.Tensor) and tok_offsets.is_cuda and tok_offsets.dtype == torch.int64
+    dev = tok_offsets.device
+    to, ti, tw = tok_offsets.contiguous().reshape(-1), _i32(tok_idx, dev).reshape(-1), _f32(tok_w, dev).reshape(-1)
+    if check:
+        _check_csr(to, n, nnz, "content_scores", "token slots")
+    off = _i32(hist_offsets, dev).reshape(-1)
+    if off.numel() < 1:
+        raise ValueError("content_scores: hist_offsets holds n_lists + 1 entries")
+    hi = _i32(hist_idx, dev).reshape(-1)
+    hw = None
+    if hist_w is not None:
+        hw = _f32(hist_w, dev).reshape(-1)
+        assert hw.shape == hi.shape
+    n_l, n_h = int(off.numel()) - 1, int(hi.numel())
+    out = torch.empty(n_l, n, dtype=torch.float32, device=dev)
+    err = _err_flag(dev, handed_on=True)
+    if n_l:
+        ws = _workspace(workspace, dev, "anirec_content_workspace_bytes", n_tokens, n_l)
+        _call("anirec_content_scores", to, ti, tw, n, n_tokens, off, hi, hw, n_l, n_h, out, err, ws, ws.numel())
+    return _finish(out, err, check,
+                   "content_scores: history, token id or offsets out of range, or an unusable weight or term")
+
+
 COVER_MAX_PICKS = _lib.COVER_MAX_PICKS
 _COVER_WS = {}
 

@@ -839,6 +839,184 @@ def itemknn_rank(knn, offsets, hist_idx, hist_w, watched_bits, target_row, targe
 
 
 # ----------------------------------------------------------------------------------------
+# content-based lists from the metadata: no model and no rating of the listed anime takes part
+# ----------------------------------------------------------------------------------------
+CONTENT_SYSTEMS = ("content",)  # row-score systems beside HYBRID_SYSTEMS (which stays as it is): hybrid members too
+CONTENT_COLUMNS = ("Genres", "Type", "Source", "Studios", "Rating")
+CONTENT_SYNOPSIS = "Sypnopsis"  # the opt-in text column (metadata_by_index's spelling)
+CONTENT_WEIGHTS = ("rating", "centered", "one")
+CONTENT_BATCH = 4096            # users per anirec_content_scores call: a score row each
+CONTENT_WS_BYTES = 1 << 30      # the batch shrinks until the call's workspace (its global form) fits in this
+
+
+def check_content_fit(columns=CONTENT_COLUMNS, min_df=1, max_df=1.0):
+    """(columns as a tuple, min_df, max_df), or a ValueError before any GPU use: no column, a column twice, a column
+    that is neither one of CONTENT_COLUMNS nor the synopsis, ``min_df`` < 1 or ``max_df`` outside (0, 1]."""
+    cols = [columns] if isinstance(columns, str) else list(columns)
+    cols = [str(c).strip() for c in cols]
+    known = CONTENT_COLUMNS + (CONTENT_SYNOPSIS,)
+    for c in cols:
+        if c not in known:
+            raise ValueError("content column %r is not one of %s" % (c, ", ".join(known)))
+    if not cols or len(set(cols)) != len(cols):
+        raise ValueError("content columns %r must be one or more distinct names of %s" % (cols, ", ".join(known)))
+    min_df, max_df = int(min_df), float(max_df)
+    if min_df < 1 or not 0.0 < max_df <= 1.0:
+        raise ValueError("content_fit: min_df = %r must be >= 1 and max_df = %r in (0, 1]" % (min_df, max_df))
+    return tuple(cols), min_df, max_df
+
+
+def content_rows(meta, columns=CONTENT_COLUMNS, min_df=1, max_df=1.0):
+    """The TF-IDF rows of ``content_fit`` on the host: (vocab, rows) — the sorted token strings and, per row of ``meta``,
+    (token ids ascending int32, weights fp32)."""
+    import math
+    import re
+    from collections import Counter
+    from .components import category_tokens
+    cols, min_df, max_df = check_content_fit(columns, min_df, max_df)
+    for c in cols:
+        if c not in meta.columns:
+            raise ValueError("content_fit: the metadata frame has no column %r" % c)
+    n = len(meta)
+    tf = [{} for _ in range(n)]
+    for c in cols:
+        cells = meta[c].tolist()
+        if c == CONTENT_SYNOPSIS:
+            counts = [Counter(re.findall(r"[a-z]{3,}", cell.lower())) if isinstance(cell, str) and cell != "None"
+                      else Counter() for cell in cells]
+            df = Counter(t for cnt in counts for t in cnt)
+            kept = {t for t, d in df.items() if min_df <= d <= max_df * n}
+            for row, cnt in zip(tf, counts):
+                for t, k in cnt.items():
+                    if t in kept:
+                        row[c + "=" + t] = 1.0 + math.log(k)
+        else:
+            for row, cell in zip(tf, cells):
+                for t in category_tokens(cell):
+                    if t:
+                        row[c + "=" + t] = 1.0
+    vocab = sorted({t for row in tf for t in row})
+    index = {t: i for i, t in enumerate(vocab)}
+    df = Counter(t for row in tf for t in row)
+    idf = {t: math.log((1.0 + n) / (1.0 + df[t])) + 1.0 for t in vocab}
+    rows = []
+    for row in tf:
+        toks = sorted(row, key=index.__getitem__)
+        w = [row[t] * idf[t] for t in toks]
+        norm = math.sqrt(math.fsum(x * x for x in w))        # the correctly rounded sum: no order to restate
+        rows.append((np.asarray([index[t] for t in toks], np.int32), np.asarray([x / norm for x in w], np.float32)))
+    return vocab, rows
+
+
+def content_fit(meta, columns=CONTENT_COLUMNS, min_df=1, max_df=1.0, device="cuda:0"):
+    """TF-IDF item vectors from the metadata, on the host (NumPy and pandas alone): ``meta`` a frame aligned with the
+    caller's item index (``components.metadata_by_index``), ``columns`` of CONTENT_COLUMNS and, opt-in, "Sypnopsis".
+    A categorical cell is split by ``components.category_tokens``, each token prefixed with its column
+    ("Genres=Action"; the same word in two columns is two tokens), tf 1.  A synopsis cell is lower-cased and tokenised
+    by ``re.findall(r"[a-z]{3,}")``, tf = 1 + ln(count); only these tokens pass the document-frequency filter ``min_df``
+    <= df <= ``max_df`` * n.  idf = ln((1 + n) / (1 + df)) + 1; a row is tf * idf, L2-normalised in fp64 and rounded to
+    fp32; token ids ascend within a row, the vocabulary is sorted, a row without metadata (NaN cells) is empty.
+    Returns {"tok_offsets" int64 [n_items + 1], "tok_idx" int32, "tok_w" fp32} on ``device``, "vocab" (the token
+    strings), "n_items", "n_tokens" (at least 1) and the parameters ("columns", "min_df", "max_df").  ValueError, before
+    any GPU use, as ``check_content_fit`` and for a column the frame lacks."""
+    cols, min_df, max_df = check_content_fit(columns, min_df, max_df)
+    vocab, rows = content_rows(meta, cols, min_df, max_df)
+    off = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(i) for i, _ in rows], out=off[1:])
+    idx = np.concatenate([i for i, _ in rows]) if rows else np.zeros(0, np.int32)
+    w = np.concatenate([x for _, x in rows]) if rows else np.zeros(0, np.float32)
+    dev = torch.device(device)
+    return {"tok_offsets": torch.as_tensor(off, device=dev), "tok_idx": torch.as_tensor(idx.astype(np.int32), device=dev),
+            "tok_w": torch.as_tensor(w.astype(np.float32), device=dev), "vocab": vocab, "n_items": len(rows),
+            "n_tokens": max(1, len(vocab)), "columns": cols, "min_df": min_df, "max_df": max_df}
+
+
+def content_history_weights(rating, mode="rating", offsets=None):
+    """The history weights of a content profile, fp32 on the host, one per rating: ``rating`` the rating itself,
+    ``one`` 1, ``centered`` the rating minus the mean of its own list's ratings (``offsets``: the history CSR; None: one
+    list), mean and difference in fp32 — a title rated below the user's mean pushes the profile away from its tokens.
+    ValueError for a mode that is not one of CONTENT_WEIGHTS."""
+    mode = str(mode).strip().lower()
+    if mode not in CONTENT_WEIGHTS:
+        raise ValueError("content_weight %r is not one of %s" % (mode, ", ".join(CONTENT_WEIGHTS)))
+    r = _host(rating).reshape(-1).astype(np.float32)
+    if mode == "one":
+        return np.ones_like(r)
+    if mode == "rating":
+        return r
+    off = np.asarray([0, len(r)] if offsets is None else _host(offsets), np.int64).reshape(-1)
+    out = np.empty_like(r)
+    for lo, hi in zip(off[:-1], off[1:]):
+        if hi > lo:
+            out[lo:hi] = r[lo:hi] - r[lo:hi].mean(dtype=np.float32)
+    return out
+
+
+def content_batch(fit, batch=CONTENT_BATCH):
+    """The lists per ``ops.content_scores`` call: ``batch``, fewer where the call's workspace (n_tokens * 8 bytes a list
+    above ``anirec_content_lds_tokens()``) would pass CONTENT_WS_BYTES."""
+    return max(1, min(int(batch), CONTENT_WS_BYTES // (8 * int(fit["n_tokens"]))))
+
+
+def _content_source(fit, offsets, hist_idx, hist_w):
+    """(the row source of ``content_rows_source``, n_lists)"""
+    from . import ops
+    off = np.asarray(_host(offsets), np.int64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("content: offsets holds n_lists + 1 entries")
+    dev = fit["tok_offsets"].device
+    hi = _on(hist_idx, dev, torch.int32)
+    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
+    step = content_batch(fit)
+
+    def rows(l0, l1):       # a span of any driver, in calls whose workspace fits
+        parts = [ops.content_scores(fit["tok_offsets"], fit["tok_idx"], fit["tok_w"], fit["n_tokens"],
+                                    off[a:min(l1, a + step) + 1], hi, hw) for a in range(l0, max(l1, l0 + 1), step)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+    return rows, int(off.size) - 1
+
+
+def content_rows_source(fit, offsets, hist_idx, hist_w=None):
+    """A row source of the content scores of the lists ``content_topk`` takes, through ``ops.content_scores``."""
+    return _content_source(fit, offsets, hist_idx, hist_w)[0]
+
+
+def content_topk(fit, offsets, hist_idx, hist_w=None, k=10, watched_bits=None, keep=None, batch=CONTENT_BATCH):
+    """Content-based recommendation lists: list l's history ``hist_idx[offsets[l]:offsets[l + 1]]`` (``history_csr``
+    builds it; ``hist_w`` None = weight 1, ``content_history_weights`` gives the others) scored against the item
+    vectors of ``fit`` (``ops.content_scores``) and the ``k`` best items without a bit in ``watched_bits`` [n_lists,
+    ceil(n_items/32)] and with ``keep`` [n_items] set taken by the exact select (``ops.rows_topk``), ``content_batch``
+    lists at a time.  Returns (idx int32 [n_lists, k], score fp32 [n_lists, k])."""
+    source, n_l = _content_source(fit, offsets, hist_idx, hist_w)
+    return rows_topk_batched(source, n_l, k, watched_bits, keep, content_batch(fit, batch), "content_topk",
+                             fit["tok_offsets"].device)
+
+
+def content_rank(fit, offsets, hist_idx, hist_w, watched_bits, target_row, target_anime, batch=CONTENT_BATCH):
+    """The ranks ``ops.predict_rank`` gives a model, for the content scores of ``content_topk``: target t is
+    (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the items
+    the list has no watched bit for, the target's own bit ignored)."""
+    source, n_l = _content_source(fit, offsets, hist_idx, hist_w)
+    return rows_rank_batched(source, n_l, watched_bits, target_row, target_anime, content_batch(fit, batch),
+                             "content_rank", fit["tok_offsets"].device)
+
+
+def content_similar(fit, queries, k, keep=None, batch=CONTENT_BATCH):
+    """The ``k`` nearest items of each query item by content: a query is a one-entry history of weight 1, so the score is
+    the cosine of the two unit-length TF-IDF rows up to the 2^-30 quantisation of the profile; the query itself is never
+    listed.  Returns (idx int32 [nq, k], score fp32 [nq, k]) in ``ops.rows_topk``'s order.  ValueError for a query
+    outside the items."""
+    q = np.asarray(_host(queries), np.int64).reshape(-1)
+    n = int(fit["n_items"])
+    if q.size and (q.min() < 0 or q.max() >= n):
+        raise ValueError("content_similar: query item out of range")
+    own = np.zeros((q.size, (n + 31) // 32), np.uint32)
+    own[np.arange(q.size), q >> 5] = np.uint32(1) << (q & 31).astype(np.uint32)
+    bits = torch.as_tensor(own.view(np.int32), device=fit["tok_offsets"].device)
+    return content_topk(fit, np.arange(q.size + 1), q.astype(np.int32), None, k, bits, keep, batch)
+
+
+# ----------------------------------------------------------------------------------------
 # implicit-feedback ALS (DESIGN.md §4.17): no model takes part
 # ----------------------------------------------------------------------------------------
 ALS_BATCH = 4096        # users per anirec_dot_scores call: a score row each
@@ -945,16 +1123,17 @@ HYBRID_BATCH = 4096     # users per anirec_fuse_rows call: a score row per syste
 
 def check_hybrid(systems, weights=None, method="rrf", rrf_c=60):
     """(systems as a tuple of names, weights as floats, the method's name, rrf_c), or a ValueError before any GPU use:
-    a name that is not one of HYBRID_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
+    a name that is not one of HYBRID_SYSTEMS + CONTENT_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
     weights list of another length among it)."""
     from . import ops
     names = [systems] if isinstance(systems, str) else list(systems)
     names = [str(s).strip().lower() for s in names]
+    known = HYBRID_SYSTEMS + CONTENT_SYSTEMS
     for s in names:
-        if s not in HYBRID_SYSTEMS:
-            raise ValueError("hybrid system %r is not one of %s" % (s, ", ".join(HYBRID_SYSTEMS)))
+        if s not in known:
+            raise ValueError("hybrid system %r is not one of %s" % (s, ", ".join(known)))
     if not names or len(set(names)) != len(names):
-        raise ValueError("hybrid systems %r must be one or more distinct names of %s" % (names, ", ".join(HYBRID_SYSTEMS)))
+        raise ValueError("hybrid systems %r must be one or more distinct names of %s" % (names, ", ".join(known)))
     _, _, ws, _, rrf_c = ops.check_fuse(len(names), 1, weights, method, rrf_c)
     return tuple(names), ws, str(method).strip().lower(), rrf_c
 

@@ -11,7 +11,9 @@ systems (``--hybrid_systems model,itemknn,als``, ``--hybrid_method rrf|minmax``,
 command line only; equal weights and rrf_c = 60 are the literature's defaults, not tuned on this data either),
 ``--baseline hybrid_tuned`` those of the same fusion with weights chosen from a grid, every user's targets ranked with
 the weights that scored best on the OTHER folds of users (``--hybrid_tune_metric``, ``--hybrid_tune_steps``,
-``--hybrid_tune_folds``, ``--hybrid_tune_seed``: command line only);
+``--hybrid_tune_folds``, ``--hybrid_tune_seed``: command line only), ``--baseline content`` those of the content-based
+system over all_anime.csv's columns (``--anime_df``, ``--sypnopses_df``, ``--content_columns``, ``--content_weight``,
+``--content_min_rating``: command line only; also a member ``--hybrid_systems`` takes);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
 spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
 held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
@@ -82,6 +84,21 @@ HYBRID_TUNE_FLAGS = {
     "hybrid_tune_seed": (int, 0, "the seed of the deal of users into folds"),
 }
 
+# optional and command-line only, like the item-kNN flags: the content-based system (--baseline content, or a member of
+# --hybrid_systems; components.CONTENT_DEFAULTS).  It scores from all_anime.csv, so it needs --anime_df
+CONTENT_FLAGS = {
+    "anime_df": (str, "none", "none, or the all_anime.csv artifact: the metadata the content system scores from"),
+    "anime_df_type": (str, "raw_data", "the type of that artifact"),
+    "sypnopses_df": (str, "none", "none, or the synopsis artifact (for --content_columns with Sypnopsis)"),
+    "sypnopsis_df_type": (str, "raw_data", "the type of that artifact"),
+    "content_columns": (str, ",".join(C.CONTENT_DEFAULTS["columns"]), "the columns the item vectors are built from, "
+                                                                      "separated by a comma (Sypnopsis is opt-in)"),
+    "content_weight": (str, C.CONTENT_DEFAULTS["weight"], "rating, centered or one: how a training rating weighs its "
+                                                          "title in the user's profile"),
+    "content_min_rating": (float, C.CONTENT_DEFAULTS["min_rating"], "the scaled rating (0..1) from which a training "
+                                                                    "rating enters the profile"),
+}
+
 logger = C.setup_logging("evaluate")
 
 
@@ -93,7 +110,39 @@ def baseline_arg(text):
     return names
 
 
+def _content_flag(args, f):
+    return getattr(args, f, CONTENT_FLAGS[f][1])
+
+
+def wants_content(args):
+    """whether the content system takes part: as a baseline, or as a member of a hybrid that is asked for"""
+    names = baseline_arg(args.baseline) or []
+    fused = {"hybrid", "hybrid_tuned"} & set(names)
+    return "content" in names or bool(fused and "content" in cli.hybrid_args(args)["systems"])
+
+
+def content_args(args, anime_ids=None):
+    """evaluate_frame's ``content``: the content flags and, with ``anime_ids``, the metadata by that index.  ValueError
+    without --anime_df."""
+    if str(_content_flag(args, "anime_df")).lower() == "none":
+        raise ValueError("--baseline content (and content as a hybrid member) scores from the anime metadata: give "
+                         "--anime_df (command line only)")
+    par = {"columns": [c.strip() for c in str(_content_flag(args, "content_columns")).split(",") if c.strip()],
+           "weight": _content_flag(args, "content_weight"), "min_rating": float(_content_flag(args, "content_min_rating")),
+           "meta": ()}
+    if anime_ids is not None:
+        anime_df = C.load_anime_df(artifacts.use_artifact(args.anime_df, _content_flag(args, "anime_df_type")))
+        syn = str(_content_flag(args, "sypnopses_df"))
+        syn_df = None if syn.lower() == "none" else \
+            C.load_synopses(artifacts.use_artifact(syn, _content_flag(args, "sypnopsis_df_type")))
+        par["meta"] = C.metadata_by_index(anime_ids, anime_df, syn_df)
+    return par
+
+
 def go(args):
+    content = None
+    if wants_content(args):                                 # the cheap failures: before any file or GPU use
+        C._system_params({"content": content_args(args)}, ["content"])
     from anime_recommendations_amd import weights_io
     model = weights_io.load_model(artifacts.use_artifact(args.model, args.model_type), args.ID_emb_name,
                                   args.anime_emb_name)
@@ -102,6 +151,8 @@ def go(args):
     logger.info("Final df shape is (%d, 3); %d users, %d anime", len(table), table.n_users, table.n_anime)
     ci = {f: getattr(args, f, CI_FLAGS[f][1]) for f in ("ci_replicates", "ci_level", "ci_seed")}
     compare = str(getattr(args, "compare_model", "none"))
+    if wants_content(args):
+        content = content_args(args, table.anime_ids)
     compare_model = None
     if compare.lower() != "none":
         compare_model = weights_io.load_model(artifacts.use_artifact(compare, args.model_type), args.ID_emb_name,
@@ -113,7 +164,7 @@ def go(args):
                                       als={f[len("als_"):]: getattr(args, f) for f in ALS_FLAGS if hasattr(args, f)},
                                       compare_model=compare_model, hybrid=cli.hybrid_args(args),
                                       hybrid_tune={f[len("hybrid_tune_"):]: getattr(args, f) for f in HYBRID_TUNE_FLAGS
-                                                   if hasattr(args, f)}, **ci)
+                                                   if hasattr(args, f)}, content=content, **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -141,7 +192,8 @@ def make_parser():
                              "itemknn (by an item-kNN over co-occurrence counts of the training ratings), als (by an "
                              "implicit-feedback ALS factorisation of the training ratings), hybrid (by the fused "
                              "score rows of several of them and the model), hybrid_tuned (the same with cross-fitted "
-                             "weights from a grid), or several separated by a comma")
+                             "weights from a grid), content (by TF-IDF vectors of the anime metadata; needs "
+                             "--anime_df), or several separated by a comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
@@ -149,10 +201,10 @@ def make_parser():
 
 def make_cli_parser():
     """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*``,
-    ``--compare_model``, ``--hybrid_*`` and ``--hybrid_tune_*`` flags."""
+    ``--compare_model``, ``--hybrid_*``, ``--hybrid_tune_*`` and content (``CONTENT_FLAGS``) flags."""
     parser = make_parser()
     for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()) + \
-            list(HYBRID_FLAGS.items()) + list(HYBRID_TUNE_FLAGS.items()):
+            list(HYBRID_FLAGS.items()) + list(HYBRID_TUNE_FLAGS.items()) + list(CONTENT_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

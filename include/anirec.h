@@ -1051,6 +1051,44 @@ int anirec_itemknn_scores(const int32_t *nbr_idx, const float *nbr_sim, int32_t 
                           int32_t n_hist, float *out_scores, int32_t *err_flag, void *ws, size_t ws_bytes,
                           void *stream);
 
+/* CONTENT-BASED SCORE ROWS from item metadata: the one system that scores an item nobody has rated.
+ * The item features are a CSR over n_tokens token ids: row j is the entries t = tok_offsets[j] .. tok_offsets[j+1]-1 of
+ * tok_idx / tok_w (TF-IDF weights; tok_offsets int64 [n_items + 1], ascending from 0 — it is trusted: the call is not
+ * told the arrays' length).  The histories are the CSR anirec_itemknn_scores takes (hist_w NULL means 1.0f; a negative
+ * weight pushes away from a title).  out_scores is [n_lists][n_items].  The rule, for list l with entries e (item
+ * i_e = hist_idx[e], weight w_e):
+ *   Wq   = sum_e llrint(|w_e| * 2^30)                                                            as int64
+ *   P[v] = sum_e sum_{t in row(i_e), tok_idx[t] == v} llrint((double)w_e * (double)tok_w[t] * 2^30)   as int64
+ *          (the product of two fp32 values is exact in fp64: each term has one rounding, to the nearest even integer;
+ *          a repeated item or a repeated token adds again)
+ *   p[v] = Wq > 0 ? (float)((double)P[v] / (double)Wq) : 0.0f
+ *          (two correctly rounded int64 -> fp64 conversions, one correctly rounded divide, one rounding to fp32: the
+ *          weighted mean item vector, so scores are on one scale across users)
+ *   out[l][j] = acc after acc = fmaf(p[tok_idx[t]], tok_w[t], acc) over t = tok_offsets[j] .. tok_offsets[j+1]-1 in
+ *          storage order, from +0.0f: an item without tokens scores +0.0f
+ * Integer sums followed by a fixed chain: a list's row depends on that list's multiset of entries and the item CSR
+ * alone, not on entry order, the other lists of the call or the launch shape.  The documented bound is (history length
+ * x longest item row) < 2^22 per list.
+ * *err_flag (device; overwritten by the call) becomes 1, and the offending part adds nothing, on: a history entry whose
+ * item is outside [0, n_items) or whose weight is not finite or above 1024 in magnitude (the entry adds nothing, to Wq
+ * either); a token slot whose id is outside [0, n_tokens) or whose weight is not finite (the slot is skipped in the
+ * profile and in the chain); a profile term with |w x| > 1024.  An offsets pair that is negative, decreasing or past
+ * n_hist raises it too and makes that list's row NaN; nothing is read through a bad value and the other lists are
+ * unaffected.
+ * One workgroup per list; the int64 profile, and its fp32 image in place, live in LDS when n_tokens <=
+ * anirec_content_lds_tokens(); above it the profile is on the list's int64 row of ws, the image still in LDS up to
+ * twice that many tokens and on the ws row beyond.
+ * n_items < 1, n_tokens < 1, a negative count, or a NULL tok_offsets, tok_idx, tok_w, hist_offsets, out_scores,
+ * err_flag or ws (hist_idx with n_hist > 0) with n_lists > 0: ANIREC_EINVAL before anything is enqueued or written.
+ * n_lists == 0: ANIREC_OK.  ws: anirec_content_workspace_bytes(n_tokens, n_lists) bytes (0 for a bad argument), 8-byte
+ * aligned, less is ANIREC_EWORKSPACE; the result does not depend on what it or out_scores held.  Graph-capturable. */
+size_t anirec_content_lds_tokens(void);
+size_t anirec_content_workspace_bytes(int32_t n_tokens, int32_t n_lists);
+int anirec_content_scores(const int64_t *tok_offsets, const int32_t *tok_idx, const float *tok_w, int32_t n_items,
+                          int32_t n_tokens, const int32_t *hist_offsets, const int32_t *hist_idx, const float *hist_w,
+                          int32_t n_lists, int32_t n_hist, float *out_scores, int32_t *err_flag, void *ws,
+                          size_t ws_bytes, void *stream);
+
 /* ONBOARDING LISTS: which m items to show a newcomer so that there is something to fit.  A greedy
  * maximum-coverage questionnaire over the rated-by bit rows: pick the m items such that as many users of a population
  * as possible have rated at least `depth` of them.  item_bits is [n_items][W] uint32, W = ceil(n_users/32), exactly as
