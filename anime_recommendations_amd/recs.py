@@ -22,7 +22,8 @@ def _aligned(t):
 
 def user_favourites(user_idx, anime_idx, rating, n_users, n_anime, percentile=80.0):
     """Returns (fav_bits int32 [n_users, ceil(n_anime/32)], threshold float64 [n_users]).
-    Bit a of row u is set iff rating(u, a) >= np.percentile(ratings of u, percentile)."""
+    Bit a of row u is set iff rating(u, a) >= np.percentile(ratings of u, percentile).  A user without ratings has
+    threshold NaN and no bit; an empty table is that for every user, answered here without a library call."""
     if not torch.cuda.is_available():
         raise _lib.AnirecError("no GPU: the anime_recommendations_amd recs path needs an MI355X")
     dev = user_idx.device
@@ -31,6 +32,9 @@ def user_favourites(user_idx, anime_idx, rating, n_users, n_anime, percentile=80
     r = _aligned(rating.to(torch.float64))
     n = int(u.numel())
     ww = (int(n_anime) + 31) // 32
+    if n == 0:          # np.percentile of no rating: no threshold, no favourite (the entry point takes n >= 1)
+        return (torch.zeros(int(n_users), ww, dtype=torch.int32, device=dev),
+                torch.full((int(n_users),), float("nan"), dtype=torch.float64, device=dev))
     fav, thr = _outputs(dev, (torch.int32, int(n_users), ww), (torch.float64, int(n_users)))
     err = _err_flag(dev)
     ws = _workspace(None, dev, "anirec_fav_workspace_bytes", n, int(n_users))
