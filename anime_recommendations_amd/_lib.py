@@ -305,6 +305,14 @@ PROTOTYPES = {
     "anirec_als_half_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _f32, _i32, _vp, _vp,
                                         _vp]),
     "anirec_dot_scores": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
+    # EASE: the fp64 inverse of a symmetric positive definite matrix, the weights from it, score rows from histories
+    "anirec_spd_inverse_block": (_i32, []),
+    "anirec_spd_inverse_workspace_bytes": (_sz, [_i32]),
+    "anirec_spd_inverse": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "anirec_ease_weights": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp]),
+    "anirec_ease_scores_col_tile": (_i32, []),
+    "anirec_ease_scores_entry_tile": (_i32, []),
+    "anirec_ease_scores": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
     # hybrid lists: several systems' score rows fused into one (the pointers, pitches and weights: host arrays)
     "anirec_fuse_max_items": (_sz, []),
     "anirec_fuse_rows": (C.c_int, [C.POINTER(_vp), C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, C.POINTER(_f32), _i32,

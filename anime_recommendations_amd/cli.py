@@ -45,6 +45,14 @@ HYBRID_FLAGS = {
 }
 
 
+# the flags of an EASE fit (ease_recs; evaluate --baseline ease): all optional.  reg = 500 is the paper's value (Steck
+# 2019) for a data set of about this many users, not tuned on this data.
+EASE_FLAGS = {
+    "ease_reg": (float, 500.0, "the L2 weight of the EASE fit, > 0: the larger, the more the weights shrink"),
+    "ease_neighbours": (int, 0, "K > 0 keeps the K largest weights of every anime only; 0 = the dense model"),
+}
+
+
 def hybrid_args(args):
     """The ``systems`` / ``weights`` / ``method`` / ``rrf_c`` of the HYBRID_FLAGS on ``args`` (the defaults where a parser
     has none of them)."""

@@ -1506,6 +1506,80 @@ def dot_scores(Q, Y, out=None):
     return out
 
 
+def check_ease(reg, neighbours=0):
+    """The argument checks of the EASE fit (no device needed): ValueError for a ``reg`` that is not finite or not > 0,
+    a negative ``neighbours``.  Returns (reg, neighbours)."""
+    reg, neighbours = float(reg), int(neighbours)
+    if not (0.0 < reg < float("inf")):
+        raise ValueError("ease: reg = %r must be finite and > 0" % reg)
+    if neighbours < 0:
+        raise ValueError("ease: neighbours = %d must be >= 0" % neighbours)
+    return reg, neighbours
+
+
+def spd_inverse(A, workspace=None):
+    """The inverse of a symmetric positive definite matrix in fp64 (anirec_spd_inverse): ``A`` fp64
+    [n, n] on the device, not modified.  A blocked Gauss-Jordan elimination without pivoting on the f64 matrix cores;
+    the bits are a function of ``A`` alone.  Returns (P fp64 [n, n], info int32 [1] on the device): info is 0 on success,
+    else 1 + the first block step (of ``_lib.load().anirec_spd_inverse_block()`` rows) that met a pivot <= 0 or not
+    finite, and P is unspecified.  Nothing synchronises: the caller reads ``info``."""
+    _need_gpu()
+    assert isinstance(A, torch.Tensor) and A.is_cuda and A.dtype == torch.float64 and A.dim() == 2 and \
+        A.shape[0] == A.shape[1], "fp64 [n, n] device matrix"
+    n = int(A.shape[0])
+    if n < 1:
+        raise ValueError("spd_inverse: A has no rows")
+    P = A.contiguous().clone()
+    info = _err_flag(P.device)
+    ws = _workspace(workspace, P.device, "anirec_spd_inverse_workspace_bytes", n)
+    _call("anirec_spd_inverse", P, n, n, info, ws, ws.numel())
+    return P, info
+
+
+def ease_weights(P):
+    """The EASE item-item weights of an inverse (anirec_ease_weights): ``P`` fp64 [n, n] on the device.  Returns fp32
+    [n, n]: W[i, j] = -P[i, j] / P[j, j] (one fp64 divide, one rounding), W[i, i] = +0."""
+    _need_gpu()
+    assert isinstance(P, torch.Tensor) and P.is_cuda and P.dtype == torch.float64 and P.dim() == 2 and \
+        P.shape[0] == P.shape[1], "fp64 [n, n] device matrix"
+    n = int(P.shape[0])
+    if n < 1:
+        raise ValueError("ease_weights: P has no rows")
+    P = P.contiguous()
+    W = torch.empty(n, n, dtype=torch.float32, device=P.device)
+    _call("anirec_ease_weights", P, n, n, W, n)
+    return W
+
+
+def ease_scores(W, offsets, hist_idx, hist_w=None, check=True):
+    """EASE score rows (anirec_ease_scores): ``W`` fp32 [n_items, n_items] on the device
+    (``ease_weights``), list l's history ``hist_idx[offsets[l]:offsets[l + 1]]`` with the weights ``hist_w`` (None: 1).
+    out[l, j] = the sum over history entries (item i, weight w) of w * W[i, j], accumulated as int64 multiples of
+    2^-30 (``itemknn_scores``' term rule): exact, whatever the order.  Returns fp32 [n_lists, n_items].  Raises
+    ValueError for a history item out of range, an offsets pair that is not inside the history, a weight that is not
+    finite or |w W| > 1024; with ``check=False`` returns (out, device flag) and nothing synchronises."""
+    _need_gpu()
+    W = _score_rows(W, "[n_items, n_items]")
+    dev = W.device
+    n, ldw = int(W.shape[0]), int(W.shape[1])
+    if n < 1 or ldw < n:
+        raise ValueError("ease_scores: W must be [n_items >= 1, ld >= n_items]")
+    off = _i32(offsets, dev).reshape(-1)
+    if off.numel() < 1:
+        raise ValueError("ease_scores: offsets holds n_lists + 1 entries")
+    hi = _i32(hist_idx, dev).reshape(-1)
+    hw = None
+    if hist_w is not None:
+        hw = _f32(hist_w, dev).reshape(-1)
+        assert hw.shape == hi.shape
+    n_l, n_h = int(off.numel()) - 1, int(hi.numel())
+    out = torch.empty(n_l, n, dtype=torch.float32, device=dev)
+    err = _err_flag(dev, handed_on=True)
+    if n_l:
+        _call("anirec_ease_scores", W, ldw, n, off, hi, hw, n_l, n_h, out, n, err)
+    return _finish(out, err, check, "ease_scores: history or offsets out of range, or an unusable term")
+
+
 def _fold_prepare(table, head, offsets, idx, rating, init, steps, loss):
     """What fold_in and fold_in_split share before their call, the checks in their order: the arguments converted and
     checked, the start rows broadcast, the outputs allocated.  Returns (loss_id, act_id, dim, steps, off, idx, rating,

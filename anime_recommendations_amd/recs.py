@@ -1119,6 +1119,121 @@ def als_rank(fit, users, watched_bits, target_row, target_anime, batch=ALS_BATCH
 
 
 # ----------------------------------------------------------------------------------------
+# EASE, the closed-form linear item-item autoencoder (Steck 2019): no model takes part
+# ----------------------------------------------------------------------------------------
+EASE_SYSTEMS = ("ease",)    # row-score systems beside HYBRID_SYSTEMS and CONTENT_SYSTEMS (which stay as they are)
+EASE_BATCH = 4096           # users per anirec_ease_scores call: a score row each
+EASE_REG = 500.0            # the paper's value for a data set of about this many users; not tuned on this data
+
+
+def ease_fit(user_idx, anime_idx, rating, n_users, n_items, liked_min_rating=0.0, reg=EASE_REG, neighbours=0,
+             device="cuda:0"):
+    """An EASE model from a rating list: a user LIKED an anime when the (scaled) rating is at or above
+    ``liked_min_rating`` (compared in fp32; 0.0 = every rating).  With B the 0/1 item x user matrix of liked pairs:
+    G = B B^T (the exact count rows of ``ops.cooc_scores``, COOC_BATCH query items at a time), A = G + reg I in fp64,
+    P = A^-1 (``ops.spd_inverse``), W = -P / diag(P) with a zero diagonal (``ops.ease_weights``).  ``reg`` = 500 is the
+    paper's value for a data set of about this many users; it is not tuned on this data.  The inverse is held to its
+    residual for reg >= 1; a reg far below 1 on a rank-deficient G is outside the tested domain.
+    Returns {"W" fp32 [n_items, n_items], "pop" int32 [n_items] (how many users liked each anime)} on the device and the
+    parameters ("reg", "n_items", "n_users", "n_liked", "liked_min_rating", "neighbours").  With ``neighbours`` = K > 0
+    the fit additionally holds "knn": the K largest entries of every row of W other than the diagonal, as the
+    {"nbr_idx", "nbr_sim"} tables of an item-kNN model (``ops.rows_topk`` with ``self_idx``); the rows of this
+    truncated model are ``itemknn_rows_source(fit["knn"], ...)``.
+    Raises ValueError, before any GPU use, for a ``reg`` that is not finite or not > 0 or a negative ``neighbours``;
+    and, naming ``reg``, when the inverse meets a pivot that is not positive."""
+    from . import ops
+    reg, neighbours = ops.check_ease(reg, neighbours)
+    n_users, n_items = int(n_users), int(n_items)
+    if n_users < 1 or n_items < 1:
+        raise ValueError("ease_fit: n_users and n_items must be >= 1")
+    if neighbours > max(1, n_items - 1):
+        raise ValueError("ease_fit: neighbours = %d is more than the %d other items" % (neighbours, n_items - 1))
+    u, a = _host(user_idx).reshape(-1), _host(anime_idx).reshape(-1)
+    r = _host(rating).reshape(-1).astype(np.float32)
+    if not len(u) == len(a) == len(r):
+        raise ValueError("ease_fit: user_idx, anime_idx and rating must have one entry per rating")
+    liked = r >= np.float32(liked_min_rating)
+    dev = torch.device(device)
+    bits = item_bits(torch.as_tensor(u[liked].astype(np.int32), device=dev),
+                     torch.as_tensor(a[liked].astype(np.int32), device=dev), n_users, n_items, device=dev)
+    A = torch.empty(n_items, n_items, dtype=torch.float64, device=dev)
+    q = torch.arange(n_items, dtype=torch.int32, device=dev)
+    pop = None
+    for q0 in range(0, n_items, COOC_BATCH):
+        _, cnt, _, pp = ops.cooc_scores(bits, n_users, q[q0:q0 + COOC_BATCH], count=True, pop=pop is None)
+        pop = pp if pop is None else pop
+        A[q0:q0 + COOC_BATCH] = cnt
+    A.diagonal().add_(reg)
+    P, info = ops.spd_inverse(A)
+    del A
+    if int(info.item()):
+        raise ValueError("ease_fit: the inverse met a pivot that is not positive in block step %d: reg = %r is too "
+                         "small for this data" % (int(info.item()) - 1, reg))
+    W = ops.ease_weights(P)
+    del P
+    fit = {"W": W, "pop": pop, "reg": reg, "n_items": n_items, "n_users": n_users, "n_liked": int(liked.sum()),
+           "liked_min_rating": float(liked_min_rating), "neighbours": neighbours}
+    if neighbours:
+        idx = torch.empty(n_items, neighbours, dtype=torch.int32, device=dev)
+        sim = torch.empty(n_items, neighbours, dtype=torch.float32, device=dev)
+        for q0 in range(0, n_items, COOC_BATCH):
+            idx[q0:q0 + COOC_BATCH], sim[q0:q0 + COOC_BATCH] = ops.rows_topk(W[q0:q0 + COOC_BATCH], neighbours,
+                                                                             self_idx=q[q0:q0 + COOC_BATCH])
+        fit["knn"] = {"nbr_idx": idx, "nbr_sim": sim}
+    return fit
+
+
+def _ease_source(fit, offsets, hist_idx, hist_w):
+    """(the row source of ``ease_rows_source``, n_lists)"""
+    from . import ops
+    off = np.asarray(_host(offsets), np.int64).reshape(-1)
+    if off.size < 1:
+        raise ValueError("ease: offsets holds n_lists + 1 entries")
+    dev = fit["W"].device
+    hi = _on(hist_idx, dev, torch.int32)
+    hw = None if hist_w is None else _on(hist_w, dev, torch.float32)
+    return lambda l0, l1: ops.ease_scores(fit["W"], off[l0:l1 + 1], hi, hw), int(off.size) - 1
+
+
+def ease_rows_source(fit, offsets, hist_idx, hist_w=None):
+    """A row source of the EASE scores of the lists ``ease_topk`` takes, through ``ops.ease_scores``."""
+    return _ease_source(fit, offsets, hist_idx, hist_w)[0]
+
+
+def ease_topk(fit, offsets, hist_idx, hist_w=None, k=10, watched_bits=None, keep=None, batch=EASE_BATCH):
+    """EASE recommendation lists: list l's history ``hist_idx[offsets[l]:offsets[l + 1]]`` (``history_csr`` builds it;
+    ``hist_w`` None = weight 1) scored through the weights of ``fit`` (``ops.ease_scores``) and the ``k`` best anime
+    without a bit in ``watched_bits`` [n_lists, ceil(n_items/32)] and with ``keep`` [n_items] set taken by the exact
+    select (``ops.rows_topk``), ``batch`` lists at a time.  Returns (idx int32 [n_lists, k], score fp32 [n_lists, k])."""
+    source, n_l = _ease_source(fit, offsets, hist_idx, hist_w)
+    return rows_topk_batched(source, n_l, k, watched_bits, keep, batch, "ease_topk", fit["W"].device)
+
+
+def ease_rank(fit, offsets, hist_idx, hist_w, watched_bits, target_row, target_anime, batch=EASE_BATCH):
+    """The ranks ``ops.predict_rank`` gives a model, for the EASE scores of ``ease_topk``: target t is
+    (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the anime
+    the list has no watched bit for, the target's own bit ignored).  ``batch`` lists at a time."""
+    source, n_l = _ease_source(fit, offsets, hist_idx, hist_w)
+    return rows_rank_batched(source, n_l, watched_bits, target_row, target_anime, batch, "ease_rank", fit["W"].device)
+
+
+def ease_similar(fit, queries, k, keep=None, batch=EASE_BATCH):
+    """The ``k`` anime with the largest weights in each query item's row of W (what liking the query adds most to); the
+    query itself is never listed.  Returns (idx int32 [nq, k], score fp32 [nq, k]) in ``ops.rows_topk``'s order.
+    ValueError for a query outside the items."""
+    q = np.asarray(_host(queries), np.int64).reshape(-1)
+    n = int(fit["n_items"])
+    if q.size and (q.min() < 0 or q.max() >= n):
+        raise ValueError("ease_similar: query item out of range")
+    own = np.zeros((q.size, (n + 31) // 32), np.uint32)
+    own[np.arange(q.size), q >> 5] = np.uint32(1) << (q & 31).astype(np.uint32)
+    dev = fit["W"].device
+    qd = torch.as_tensor(q, device=dev)
+    return rows_topk_batched(lambda l0, l1: fit["W"][qd[l0:l1]], int(q.size), k,
+                             torch.as_tensor(own.view(np.int32), device=dev), keep, batch, "ease_similar", dev)
+
+
+# ----------------------------------------------------------------------------------------
 # hybrid lists: several systems' score rows fused into one (DESIGN.md §4.19)
 # ----------------------------------------------------------------------------------------
 HYBRID_SYSTEMS = ("model", "popularity", "itemknn", "als")
@@ -1127,12 +1242,12 @@ HYBRID_BATCH = 4096     # users per anirec_fuse_rows call: a score row per syste
 
 def check_hybrid(systems, weights=None, method="rrf", rrf_c=60):
     """(systems as a tuple of names, weights as floats, the method's name, rrf_c), or a ValueError before any GPU use:
-    a name that is not one of HYBRID_SYSTEMS + CONTENT_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
+    a name that is not one of HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
     weights list of another length among it)."""
     from . import ops
     names = [systems] if isinstance(systems, str) else list(systems)
     names = [str(s).strip().lower() for s in names]
-    known = HYBRID_SYSTEMS + CONTENT_SYSTEMS
+    known = HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS
     for s in names:
         if s not in known:
             raise ValueError("hybrid system %r is not one of %s" % (s, ", ".join(known)))

@@ -13,7 +13,10 @@ command line only; equal weights and rrf_c = 60 are the literature's defaults, n
 the weights that scored best on the OTHER folds of users (``--hybrid_tune_metric``, ``--hybrid_tune_steps``,
 ``--hybrid_tune_folds``, ``--hybrid_tune_seed``: command line only), ``--baseline content`` those of the content-based
 system over all_anime.csv's columns (``--anime_df``, ``--sypnopses_df``, ``--content_columns``, ``--content_weight``,
-``--content_min_rating``: command line only; also a member ``--hybrid_systems`` takes);
+``--content_min_rating``: command line only; also a member ``--hybrid_systems`` takes), ``--baseline ease`` those of
+EASE, the closed-form linear item-item model fitted on the training slice (``--ease_reg``, ``--ease_min_rating``,
+``--ease_neighbours``: command line only; reg = 500 is the paper's value for a data set of about this many users, not
+tuned on this data; also a member ``--hybrid_systems`` takes);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
 spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
 held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
@@ -99,6 +102,11 @@ CONTENT_FLAGS = {
                                                                     "rating enters the profile"),
 }
 
+# optional and command-line only, like the item-kNN flags: EASE (--baseline ease, or a member of --hybrid_systems;
+# components.EASE_DEFAULTS: reg = 500 is the paper's value for a data set of about this many users, not tuned on this data)
+EASE_FLAGS = dict(cli.EASE_FLAGS, ease_min_rating=(float, C.EASE_DEFAULTS["min_rating"],
+                                                   "the scaled rating (0..1) from which a training rating counts as liked"))
+
 logger = C.setup_logging("evaluate")
 
 
@@ -114,11 +122,16 @@ def _content_flag(args, f):
     return getattr(args, f, CONTENT_FLAGS[f][1])
 
 
-def wants_content(args):
-    """whether the content system takes part: as a baseline, or as a member of a hybrid that is asked for"""
+def wants(args, system):
+    """whether ``system`` takes part: as a baseline, or as a member of a hybrid that is asked for"""
     names = baseline_arg(args.baseline) or []
     fused = {"hybrid", "hybrid_tuned"} & set(names)
-    return "content" in names or bool(fused and "content" in cli.hybrid_args(args)["systems"])
+    return system in names or bool(fused and system in cli.hybrid_args(args)["systems"])
+
+
+def wants_content(args):
+    """whether the content system takes part"""
+    return wants(args, "content")
 
 
 def content_args(args, anime_ids=None):
@@ -139,8 +152,15 @@ def content_args(args, anime_ids=None):
     return par
 
 
+def ease_args(args):
+    """evaluate_frame's ``ease``: the EASE flags the parser has"""
+    return {f[len("ease_"):]: getattr(args, f) for f in EASE_FLAGS if hasattr(args, f)}
+
+
 def go(args):
     content = None
+    if wants(args, "ease"):                                 # the cheap failures: before any file or GPU use
+        C._system_params({"ease": ease_args(args)}, ["ease"])
     if wants_content(args):                                 # the cheap failures: before any file or GPU use
         C._system_params({"content": content_args(args)}, ["content"])
     from anime_recommendations_amd import weights_io
@@ -164,7 +184,8 @@ def go(args):
                                       als={f[len("als_"):]: getattr(args, f) for f in ALS_FLAGS if hasattr(args, f)},
                                       compare_model=compare_model, hybrid=cli.hybrid_args(args),
                                       hybrid_tune={f[len("hybrid_tune_"):]: getattr(args, f) for f in HYBRID_TUNE_FLAGS
-                                                   if hasattr(args, f)}, content=content, **ci)
+                                                   if hasattr(args, f)}, content=content, ease=ease_args(args),
+                                      **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -193,7 +214,8 @@ def make_parser():
                              "implicit-feedback ALS factorisation of the training ratings), hybrid (by the fused "
                              "score rows of several of them and the model), hybrid_tuned (the same with cross-fitted "
                              "weights from a grid), content (by TF-IDF vectors of the anime metadata; needs "
-                             "--anime_df), or several separated by a comma")
+                             "--anime_df), ease (by the closed-form linear item-item model EASE fitted on the "
+                             "training ratings), or several separated by a comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
@@ -201,10 +223,11 @@ def make_parser():
 
 def make_cli_parser():
     """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*``,
-    ``--compare_model``, ``--hybrid_*``, ``--hybrid_tune_*`` and content (``CONTENT_FLAGS``) flags."""
+    ``--compare_model``, ``--hybrid_*``, ``--hybrid_tune_*``, content (``CONTENT_FLAGS``) and ``--ease_*`` flags."""
     parser = make_parser()
     for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()) + \
-            list(HYBRID_FLAGS.items()) + list(HYBRID_TUNE_FLAGS.items()) + list(CONTENT_FLAGS.items()):
+            list(HYBRID_FLAGS.items()) + list(HYBRID_TUNE_FLAGS.items()) + list(CONTENT_FLAGS.items()) + \
+            list(EASE_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

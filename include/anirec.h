@@ -1279,6 +1279,68 @@ int anirec_dot_scores(const float *Q, int32_t n_q, const float *Y, int32_t n, in
                       void *stream);
 
 /* ------------------------------------------------------------------------- *
+ *  EASE (Steck 2019, "Embarrassingly Shallow Autoencoders for Sparse Data"): the linear item-item autoencoder a
+ *  ranking table reads item-kNN and ALS against.  With B the n_items x n_users 0/1 matrix of liked
+ *  pairs: G = B B^T (anirec_cooc_scores' out_count rows), A = G + reg I, P = A^-1, W[i][j] = -P[i][j] / P[j][j] off the
+ *  diagonal and 0 on it; a history H scores item j as sum_{i in H} w_i W[i][j].  Every call below is stream-ordered
+ *  plain launches: no host read-back, no cooperative launch, no float atomics, no kernel that waits on another
+ *  workgroup, every loop bounded by the arguments.  Graph-capturable.  All indexing is 64-bit.
+ *
+ * anirec_spd_inverse: A_inout [n][ld] fp64, symmetric positive definite, is replaced by its inverse (elements j >= n of
+ * a row are neither read nor written).  The route is part of the definition: blocked Gauss-Jordan elimination in
+ * place, without pivoting, NB = anirec_spd_inverse_block() (a constant, not a knob), T = ceil(n / NB) block steps.
+ * Block step b, K = the rows b NB .. min(n, (b + 1) NB) - 1, every block padded to NB x NB (the diagonal block with the
+ * identity, any other with zeros):
+ *     R  = A[K][K]^-1, by the unblocked form of the same elimination: for p = 0 .. NB-1 in order, t = 1 / D[p][p],
+ *          row[j] = D[p][j] t, col[i] = D[i][p];  D[i][j] = fma(-col[i], row[j], D[i][j]) for i, j != p;
+ *          D[p][j] = row[j];  D[i][p] = -(col[i] t);  D[p][p] = t
+ *     Rp = R A[K][:]   (NB x n; each element an fma chain over k = 0 .. NB-1 from 0), with Rp[:][K] = R
+ *     A[I][J] = A[I][J] - A[I][K] Rp[:][J]   for I, J outside K
+ *     A[K][J] = Rp[:][J];   A[I][K] = -A[I][K] R;   A[K][K] = R
+ *   the two products with A[I][K] summed over k ascending on v_mfma_f64_16x16x4_f64 (four k to an instruction), each
+ *   output element by one lane.  The hardware's order inside one instruction is not documented, so the result is held
+ *   to a residual, not to NumPy's bits: max |A P - I| <= 8 max(the same of a LAPACK inverse, n 2^-52) on the tested
+ *   domain (co-occurrence counts with reg >= 1; a reg far below 1 on a rank-deficient G is outside it).
+ *   The bits of the result are a function of A, n and ld alone: the same from run to run and whatever ws held.
+ *   *info (device; overwritten by the call): 0 on success, else 1 + the first block step that met a pivot D[p][p] that
+ *   was not > 0 or not finite; the call still runs every step in bounded time, reads nothing out of bounds, and leaves
+ *   A_inout unspecified.
+ *   n < 1, ld < n, n > 65535 NB, a NULL A_inout, info or ws, an A_inout or ws not 8-byte aligned, an info not 4-byte
+ *   aligned: ANIREC_EINVAL before anything is enqueued.  ws: anirec_spd_inverse_workspace_bytes(n) bytes (0 for
+ *   n < 1; needs no GPU), less is ANIREC_EWORKSPACE.
+ *
+ * anirec_ease_weights: W_out[i][j] = (float)(-P[i][j] / P[j][j]) for i != j (one correctly rounded fp64 divide, one
+ * rounding to fp32), W_out[i][i] = +0.0f; P [n][ldp] fp64, W_out [n][ldw] fp32, elements j >= n of a row are not
+ * written.  n < 1, ldp < n, ldw < n, a NULL or misaligned pointer: ANIREC_EINVAL.
+ *
+ * anirec_ease_scores: score rows from histories.  W [n_items][ldw]; the histories are the CSR anirec_itemknn_scores
+ * takes (hist_w NULL means 1.0f) and the term rule is that call's, so the two agree bit for bit where they overlap:
+ *     term = llrint((double)w * (double)W[i][j] * 2^30);  S[l][j] += term as int64;
+ *     out_scores[l][j] = (float)((double)S[l][j] * 2^-30)          out_scores is [n_lists][ld]
+ * Every element j < n_items of every row is written (0 for an empty list); elements past n_items are not.  A repeated
+ * item counts twice.  A term needs w and W[i][j] finite and |w W[i][j]| <= 1024; the documented bound is 2^22 entries a
+ * list.  A row depends on its list's multiset of entries and on W alone: not on entry order, the other lists or the
+ * launch shape.  One thread owns an output element: no atomics, no workspace; the column tile
+ * (anirec_ease_scores_col_tile() columns) is the slow grid index, a list's entries are staged
+ * anirec_ease_scores_entry_tile() at a time.
+ * *err_flag (device; overwritten by the call) becomes 1 on an unusable term or a history item outside [0, n_items)
+ * (that term or entry adds nothing) and on an offsets pair that is negative, decreasing or past n_hist (that list's
+ * row is NaN); nothing is read through the bad value and the other lists are unaffected.
+ * n_items < 1, a negative count, ldw < n_items, ld < n_items, or a NULL W, hist_offsets, out_scores or err_flag
+ * (hist_idx with n_hist > 0) with n_lists > 0: ANIREC_EINVAL before anything is enqueued.  n_lists == 0: ANIREC_OK.
+ * ------------------------------------------------------------------------- */
+int32_t anirec_spd_inverse_block(void);
+size_t anirec_spd_inverse_workspace_bytes(int32_t n);
+int anirec_spd_inverse(double *A_inout, int64_t ld, int32_t n, int32_t *info, void *ws, size_t ws_bytes,
+                       void *stream);
+int anirec_ease_weights(const double *P, int64_t ldp, int32_t n, float *W_out, int64_t ldw, void *stream);
+int32_t anirec_ease_scores_col_tile(void);
+int32_t anirec_ease_scores_entry_tile(void);
+int anirec_ease_scores(const float *W, int64_t ldw, int32_t n_items, const int32_t *hist_offsets,
+                       const int32_t *hist_idx, const float *hist_w, int32_t n_lists, int32_t n_hist,
+                       float *out_scores, int64_t ld, int32_t *err_flag, void *stream);
+
+/* ------------------------------------------------------------------------- *
  *  Ranks to metric sums, and a Poisson bootstrap over users on them.  Integer sums throughout: no
  *  result depends on the order the rows are met in.
  *  The statistic: the resampling UNIT is the user (a user's held-out ratings are not independent, so a replicate
