@@ -55,6 +55,8 @@ GROUP_MAX_MEMBERS = 64
 # anirec_cooc_scores: the similarity of two items' liked-by sets (ANIREC_COOC_*)
 COOC_COSINE, COOC_JACCARD, COOC_CONFIDENCE = 0, 1, 2
 COOC_MEASURES = {"cosine": COOC_COSINE, "jaccard": COOC_JACCARD, "confidence": COOC_CONFIDENCE}
+WCOOC_MAX_Q = 16383         # ANIREC_WCOOC_MAX_Q: the largest user weight of anirec_wcooc_scores (two 7-bit limbs)
+WCOOC_MAX_USERS = 1 << 24   # and the most users: 127 * 2^24 < 2^31 keeps a limb's int32 accumulator exact
 COVER_MAX_PICKS = 1024      # ANIREC_COVER_MAX_PICKS: the longest list anirec_cover_greedy picks
 # anirec_fuse_rows: the fusion of several systems' score rows (ANIREC_FUSE_*)
 FUSE_RRF, FUSE_MINMAX = 0, 1
@@ -313,6 +315,10 @@ PROTOTYPES = {
     "anirec_ease_scores_col_tile": (_i32, []),
     "anirec_ease_scores_entry_tile": (_i32, []),
     "anirec_ease_scores": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]),
+    # user-weighted co-occurrence on the i8 matrix cores (the graph baselines)
+    "anirec_wcooc_chunk_words": (_sz, []),
+    "anirec_wcooc_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "anirec_wcooc_scores": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # hybrid lists: several systems' score rows fused into one (the pointers, pitches and weights: host arrays)
     "anirec_fuse_max_items": (_sz, []),
     "anirec_fuse_rows": (C.c_int, [C.POINTER(_vp), C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, C.POINTER(_f32), _i32,

@@ -53,6 +53,15 @@ EASE_FLAGS = {
 }
 
 
+# the flags of an RP3beta fit (rp3_recs; evaluate --baseline rp3): all optional.  alpha = 1, beta = 0.3 and 100
+# neighbours are common values from the literature (Paudel et al. 2017), not tuned on this data.
+RP3_FLAGS = {
+    "rp3_alpha": (float, 1.0, "the exponent of the user and start-item degrees, >= 0: 1 is the plain random walk"),
+    "rp3_beta": (float, 0.3, "the popularity penalty on the end item, >= 0: 0 is P3alpha"),
+    "rp3_neighbours": (int, 100, "the largest weights every anime keeps; 0 = the dense matrix"),
+}
+
+
 def hybrid_args(args):
     """The ``systems`` / ``weights`` / ``method`` / ``rrf_c`` of the HYBRID_FLAGS on ``args`` (the defaults where a parser
     has none of them)."""

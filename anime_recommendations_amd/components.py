@@ -425,6 +425,70 @@ def ease_recs_frame(df, anime_df, syn_df, user_id, n_recs, types=None, genres=No
 
 
 # ----------------------------------------------------------------------------------------
+# rp3_recs: lists from the three-step random walk with a popularity penalty, from the ratings alone
+# ----------------------------------------------------------------------------------------
+def _rp3_fit_frame(df, liked_min_rating, alpha, beta, neighbours):
+    """(fit, user_ids, anime_ids, (ui, ai, r)): ``recs.rp3_fit`` on the rating frame's own index (order of first
+    appearance), the checks that need no GPU first"""
+    from . import recs
+    alpha, beta, neighbours = recs.check_rp3(alpha, beta, neighbours)
+    user_ids, anime_ids = index_tables({}, df)
+    ui, ai, r = rating_indices(df, user_ids, anime_ids)
+    fit = recs.rp3_fit(ui, ai, r, len(user_ids), len(anime_ids), liked_min_rating, alpha, beta, neighbours)
+    return fit, user_ids, anime_ids, (ui, ai, r)
+
+
+def rp3_stats(fit):
+    """What the rp3_recs artifacts record about the fit"""
+    return {"alpha": float(fit["alpha"]), "beta": float(fit["beta"]), "neighbours": int(fit["neighbours"]),
+            "n_items": int(fit["n_items"]), "liked_pairs": int(fit["n_liked"]), "scale": float(fit["scale"]),
+            "liked_min_rating": float(fit["liked_min_rating"])}
+
+
+def rp3_similar_frame(df, anime_df, syn_df, name, count, types=None, genres=None, liked_min_rating=0.0, alpha=1.0,
+                      beta=0.3, neighbours=100):
+    """The anime with the largest weights in the query anime's row of the RP3beta item-item matrix (where a three-step
+    walk from the query ends most often, popular endpoints penalised): no model takes part.  A user LIKED an anime when
+    ``df``'s rating of the pair is at or above ``liked_min_rating``; the fit is ``recs.rp3_fit`` (alpha = 1, beta = 0.3
+    and 100 neighbours are common values from the literature, not tuned on this data), the list ``recs.rp3_similar``'s
+    over the anime that pass the optional Type / Genre filters.  Returns (frame, filename, stats): similar_anime's
+    columns with the weight as ``Similarity``."""
+    from . import recs
+    recs.check_rp3(alpha, beta, neighbours)
+    qid = find_anime_id(name, anime_df)
+    pos = np.nonzero(np.asarray(index_tables({}, df)[1]) == qid)[0]
+    if len(pos) == 0:
+        raise ValueError("anime %r (id %d) has no rating in the main data frame" % (name, qid))
+    fit, user_ids, anime_ids, _ = _rp3_fit_frame(df, liked_min_rating, alpha, beta, neighbours)
+    meta = metadata_by_index(anime_ids, anime_df, syn_df)
+    keep = filter_mask(meta, anime_df, types, genres)
+    k = _topk_count(count, "a_query_number", len(anime_ids) - 1)
+    idx, s = recs.rp3_similar(fit, [int(pos[0])], k, keep.astype(np.uint8))
+    return _similar_anime_rows(meta, _np(idx)[0], _np(s)[0]), clean(name) + "_rp3.csv", rp3_stats(fit)
+
+
+def rp3_recs_frame(df, anime_df, syn_df, user_id, n_recs, types=None, genres=None, liked_min_rating=0.0, alpha=1.0,
+                   beta=0.3, neighbours=100):
+    """One user's RP3beta list among the anime they have not rated: the history is the user's ratings in ``df`` at or
+    above ``liked_min_rating`` (compared in fp32) with weight 1, scored through ``recs.rp3_fit``'s weights; the list is
+    the exact select's over the unrated anime that pass the optional Type / Genre filters.  Returns (frame, stats):
+    model_recs_frame's columns with ``Rp3_score`` in the place of ``Prediction``.  ValueError before any GPU use for a
+    bad ``alpha``, ``beta`` or ``neighbours`` and a user without ratings."""
+    from . import recs
+    recs.check_rp3(alpha, beta, neighbours)
+    if not (df.user_id == int(user_id)).any():
+        raise ValueError("user id %r has no rating in the main data frame" % (user_id,))
+    fit, user_ids, anime_ids, (ui, ai, r) = _rp3_fit_frame(df, liked_min_rating, alpha, beta, neighbours)
+    row = int(np.nonzero(np.asarray(user_ids) == int(user_id))[0][0])
+    off, hist, _ = recs.history_csr(ui, ai, r, [row], min_rating=liked_min_rating)
+    meta, bits = _filter_bits(anime_ids, anime_df, syn_df, types, genres)
+    bits = bits | _blocked_bits(~unwatched_mask(df, anime_ids, user_id)).view(np.int32)
+    k = _topk_count(n_recs, "model_num_recs", len(anime_ids))
+    idx, s = recs.rows_topk_batched(recs.rp3_rows_source(fit, off, hist), 1, k, bits, what="rp3_recs")
+    return _model_recs_rows(meta, _np(idx)[0], _np(s)[0]).rename(columns={"Prediction": "Rp3_score"}), rp3_stats(fit)
+
+
+# ----------------------------------------------------------------------------------------
 # onboarding: which anime to show a newcomer, from the ratings alone (DESIGN.md §4.18)
 # ----------------------------------------------------------------------------------------
 ONBOARD_STRATEGIES = ("coverage", "popularity")
@@ -806,14 +870,15 @@ def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
 # ----------------------------------------------------------------------------------------
 def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
                       types=None, genres=None, systems=("model", "itemknn", "als"), weights=None, method="rrf", rrf_c=60,
-                      itemknn=None, als=None, ease=None):
+                      itemknn=None, als=None, ease=None, rp3=None):
     """model_recs_frame with the list taken from several systems at once (``recs.hybrid_topk``): the same candidates
     (unwatched, indexed, Type / Genre filters), each member of ``systems`` (names of ``recs.HYBRID_SYSTEMS``) scoring
     every anime for the user (``content``, of ``recs.CONTENT_SYSTEMS``, with CONTENT_DEFAULTS and this call's metadata), the
     score rows fused per row under the candidates' mask (``ops.fuse_rows``: ``method`` rrf
     with ``rrf_c``, or minmax; ``weights`` None = all 1) and the best ``n_recs`` taken by the exact select.  The item-kNN
     and ALS members are fitted from ``df`` (ITEMKNN_DEFAULTS / ALS_DEFAULTS overridden by ``itemknn`` / ``als``), the
-    ``ease`` member (of ``recs.EASE_SYSTEMS``) likewise (EASE_DEFAULTS overridden by ``ease``), the
+    ``ease`` member (of ``recs.EASE_SYSTEMS``) likewise (EASE_DEFAULTS overridden by ``ease``), the ``rp3`` member (of
+    ``recs.GRAPH_SYSTEMS``) likewise (RP3_DEFAULTS overridden by ``rp3``), the
     user's history and the liked pairs built as ``evaluate_frame`` builds them; popularity is the rating count.
     Returns (frame, stats): model_recs_frame's columns — ``Prediction`` remains the model's predicted rating of the
     listed anime — plus ``Hybrid_score`` (the fused value) and one ``Rank_<system>`` per member: the 1-based place of the
@@ -823,7 +888,7 @@ def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, use
     from . import ops, recs
     members, ws, method, rrf_c = recs.check_hybrid(systems, weights, method, rrf_c)
     content = {"meta": metadata_by_index(anime_ids, anime_df, syn_df)} if "content" in members else None
-    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease}, members)
+    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease, "rp3": rp3}, members)
     row, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
     cols = None
     if set(members) - {"model"}:
@@ -1106,6 +1171,11 @@ CONTENT_DEFAULTS = {"columns": CONTENT_COLUMNS, "weight": "rating", "min_rating"
 # many users; it is not tuned on this data.  neighbours = K > 0 keeps the K largest weights of every row only.
 LINEAR_BASELINES = ("ease",)
 EASE_DEFAULTS = {"reg": 500.0, "min_rating": 0.0, "neighbours": 0}
+# graph / random-walk models (P3alpha, Cooper et al. 2014; RP3beta, Paudel et al. 2017), beside the
+# constants above (which stay as they are) and reported after LINEAR_BASELINES.  alpha = 1, beta = 0.3 and 100
+# neighbours are common values from the literature; none is tuned on this data.  neighbours = 0 keeps the dense matrix.
+GRAPH_BASELINES = ("rp3",)
+RP3_DEFAULTS = {"alpha": 1.0, "beta": 0.3, "neighbours": 100, "min_rating": 0.0}
 
 
 def _member_params(defaults, given, what):
@@ -1183,9 +1253,25 @@ def _system_table():
             user, anime, rating, n_users, n_anime, par["min_rating"], par["reg"], int(par["neighbours"]), device=device)))
 
 
+def _system_lookup():
+    """``_system_table()`` plus the systems of ``recs.GRAPH_SYSTEMS``: what every lookup by name goes through."""
+    from . import recs
+
+    def rp3_source(fit, users, cols, par):
+        off, hist, _ = recs.history_csr(*cols[:3], users, min_rating=par["min_rating"])
+        return recs.rp3_rows_source(fit, off, hist)
+
+    return dict(_system_table(), rp3=dict(
+        defaults=RP3_DEFAULTS, check=lambda par: recs.check_rp3(par["alpha"], par["beta"], par["neighbours"]),
+        source=rp3_source,
+        fit=lambda user, anime, rating, n_users, n_anime, par, device: recs.rp3_fit(
+            user, anime, rating, n_users, n_anime, par["min_rating"], par["alpha"], par["beta"], int(par["neighbours"]),
+            device=device)))
+
+
 def _system_params(given, used):
     """{system: its defaults overridden by ``given[system]``}, the pre-GPU check made for each system of ``used``"""
-    table = _system_table()
+    table = _system_lookup()
     params = {name: _member_params(s["defaults"], given.get(name), name) for name, s in table.items() if "defaults" in s}
     for name in used:
         table[name].get("check", lambda par: None)(params.get(name))
@@ -1195,17 +1281,18 @@ def _system_params(given, used):
 def _system_source(name, tables, cols, params, users, device):
     """The row source of system ``name`` for ``users``, the system fitted from the training columns ``cols`` = (user,
     anime, rating, n_users, n_anime) on ``device``; ``tables`` = the model's (U, A, head) on the device."""
-    s, par = _system_table()[name], params.get(name)
+    s, par = _system_lookup()[name], params.get(name)
     return s["source"](s["fit"](*cols, par, device) if "fit" in s else tables, users, cols, par)
 
 
 def baseline_names(baseline):
     """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES, FITTED_BASELINES,
-    FUSED_BASELINES, TUNED_BASELINES, CONTENT_BASELINES, then LINEAR_BASELINES: None -> (), a name or a sequence of
-    names; ValueError for anything else."""
+    FUSED_BASELINES, TUNED_BASELINES, CONTENT_BASELINES, LINEAR_BASELINES, then GRAPH_BASELINES: None -> (), a name or a
+    sequence of names; ValueError for anything else."""
     if baseline is None:
         return ()
-    known = BASELINES + FITTED_BASELINES + FUSED_BASELINES + TUNED_BASELINES + CONTENT_BASELINES + LINEAR_BASELINES
+    known = (BASELINES + FITTED_BASELINES + FUSED_BASELINES + TUNED_BASELINES + CONTENT_BASELINES + LINEAR_BASELINES +
+             GRAPH_BASELINES)
     names = [baseline] if isinstance(baseline, str) else list(baseline)
     for b in names:
         if b not in known:
@@ -1237,7 +1324,7 @@ def _ci_columns(columns, boot, system, others, key):
 
 def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None,
                    ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None, hybrid=None,
-                   hybrid_tune=None, content=None, ease=None):
+                   hybrid_tune=None, content=None, ease=None, rp3=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -1285,7 +1372,15 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     under the name ease, and ``ease`` is a member the hybrids take too.  ``ease``: a dict overriding EASE_DEFAULTS (reg:
     500, the paper's value for a data set of about this many users, not tuned on this data; min_rating; neighbours: K > 0
     keeps the K largest weights of every row only); a reg that is not finite or not > 0 is a ValueError before any GPU use.
-    A sequence of names gives each, in the order popularity, itemknn, als, hybrid, hybrid_tuned, content, ease.  None: none.
+    ``baseline="rp3"``: the same targets under the same bits ranked by RP3beta (Paudel et al. 2017), the
+    three-step random walk with a popularity penalty fitted on the TRAINING pairs rated at or above its threshold
+    (``recs.rp3_fit``, ``recs.rp3_rank``'s ranks), each listed user's history that user's such pairs with weight 1; the same
+    columns and keys under the name rp3, and ``rp3`` is a member the hybrids take too.  ``rp3``: a dict overriding
+    RP3_DEFAULTS (alpha: 1, beta: 0.3, neighbours: 100 — common values from the literature, not tuned on this data;
+    neighbours = 0 keeps the dense matrix; min_rating); an alpha or beta that is negative or not finite is a ValueError
+    before any GPU use.
+    A sequence of names gives each, in the order popularity, itemknn, als, hybrid, hybrid_tuned, content, ease, rp3.  None:
+    none.
     ``compare_model``: a second model dict over the same id tables, ranked by a second ``ops.predict_rank`` on the same
     targets and bits and reported as the system ``compare`` (the baselines' columns and keys under that name).
     ``ci_replicates`` > 0: a Poisson bootstrap over the held-out USERS (``recs.bootstrap_metrics``), seeded
@@ -1310,9 +1405,9 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         tune_grid = recs.hybrid_weight_grid(len(members), tune_par["steps"])
         recs.hybrid_fold_deal(0, tune_par["folds"], tune_par["seed"])        # (the check of folds; dealt below)
         tune_pick, tune_best = [0] * int(tune_par["folds"]), 0
-    fitted = [s for s in recs.HYBRID_SYSTEMS + recs.CONTENT_SYSTEMS + recs.EASE_SYSTEMS
+    fitted = [s for s in recs.HYBRID_SYSTEMS + recs.CONTENT_SYSTEMS + recs.EASE_SYSTEMS + recs.GRAPH_SYSTEMS
               if s in baselines or s in members]     # each once
-    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease}, fitted)
+    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease, "rp3": rp3}, fitted)
     U, A = _tables_of(model, table)
     others = baselines + (("compare",) if compare_model is not None else ())
     if compare_model is not None:

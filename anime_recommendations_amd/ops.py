@@ -975,6 +975,61 @@ def cooc_scores(bits, n_users, queries, measure="cosine", shrink=0.0, min_suppor
     return _finish((sim, cnt, ex, pp), err, check, "cooc_scores: query item out of range")
 
 
+def check_wcooc(n_items, n_users, user_q=None, row_scale=None, col_scale=None):
+    """The argument checks of ``wcooc_scores`` (no device needed): (n_items, n_users) as ints, or a ValueError for
+    n_items < 1, n_users outside 1 .. 2^24 (the bound that keeps a limb's int32 accumulator exact), a ``user_q`` that
+    does not hold one entry per user, a ``row_scale`` / ``col_scale`` that does not hold one entry per item.  The VALUES
+    of ``user_q`` are checked on the device (the call's flag)."""
+    n_items, n_users = int(n_items), int(n_users)
+    if n_items < 1:
+        raise ValueError("wcooc: n_items = %d must be >= 1" % n_items)
+    if not 1 <= n_users <= _lib.WCOOC_MAX_USERS:
+        raise ValueError("wcooc: n_users = %d must be in 1 .. %d (2^24: past it a limb's int32 sum could wrap)"
+                         % (n_users, _lib.WCOOC_MAX_USERS))
+    if user_q is not None and tuple(user_q.shape) != (n_users,):
+        raise ValueError("wcooc: user_q must hold one weight per user (got %s for %d users)"
+                         % (tuple(user_q.shape), n_users))
+    for name, sc in (("row_scale", row_scale), ("col_scale", col_scale)):
+        if sc is not None and tuple(sc.shape) != (n_items,):
+            raise ValueError("wcooc: %s must hold one fp64 factor per item (got %s for %d items)"
+                             % (name, tuple(sc.shape), n_items))
+    return n_items, n_users
+
+
+def wcooc_scores(bits, n_users, user_q, queries, row_scale=None, col_scale=None, sums=False, excl=False, workspace=None,
+                 check=True):
+    """User-weighted co-occurrence rows on the i8 matrix cores (anirec_wcooc_scores): ``bits`` as
+    ``cooc_scores`` takes them, ``user_q`` an integer weight per user in 0 .. 16383, one row per query item against every
+    item.  With S = the sum of user_q over the users who liked both (exact, int64):
+    w = float32((float64(S) * row_scale[q]) * col_scale[j]) (a scale of None is 1; fp64 factors from the host), +0 where
+    S is 0.  Returns (w fp32 [nq, n_items], sum int64 [nq, n_items] | None, excl int32 [nq, ceil(n_items/32)] | None):
+    ``excl`` has bit j set where S is 0 or j is the query itself (the ``wbits`` of ``rows_topk``).  Raises ValueError
+    for a query out of range or a weight outside 0 .. 16383 (which counts as 0); with ``check=False`` the device flag is
+    returned as a fourth element instead and nothing synchronises."""
+    if not isinstance(bits, torch.Tensor) or bits.dim() != 2:
+        raise ValueError("wcooc: bits must be int32 [n_items, ceil(n_users/32)] device bit rows")
+    uq = torch.as_tensor(user_q)
+    rs = None if row_scale is None else torch.as_tensor(row_scale)
+    cs = None if col_scale is None else torch.as_tensor(col_scale)
+    n, n_users = check_wcooc(bits.shape[0], n_users, uq, rs, cs)
+    _need_gpu()
+    bits, n_users = _item_bits(bits, n_users)
+    dev = bits.device
+    uq = _i32(uq, dev)
+    rs = None if rs is None else rs.to(device=dev, dtype=torch.float64).contiguous()
+    cs = None if cs is None else cs.to(device=dev, dtype=torch.float64).contiguous()
+    q = _i32(queries, dev).reshape(-1)
+    nq = int(q.numel())
+    w = torch.empty(nq, n, dtype=torch.float32, device=dev)
+    sm = torch.empty(nq, n, dtype=torch.int64, device=dev) if sums else None
+    ex = torch.empty(nq, (n + 31) // 32, dtype=torch.int32, device=dev) if excl else None
+    err = _err_flag(dev, handed_on=True)
+    ws = _workspace(workspace, dev, "anirec_wcooc_workspace_bytes", n, n_users, nq)
+    _call("anirec_wcooc_scores", bits, n, n_users, uq, q, nq, rs, cs, w, sm, ex, err, ws, ws.numel())
+    return _finish((w, sm, ex), err, check, "wcooc_scores: query item out of range, or a user weight outside 0 .. %d"
+                   % _lib.WCOOC_MAX_Q)
+
+
 def rows_topk(scores, k, n=None, self_idx=None, keep=None, wbits=None, workspace=None):
     """The exact select over score rows the caller holds (anirec_rows_topk): ``scores`` fp32 [nq, ld] on the device,
     the first ``n`` (default ld) columns of a row count.  Item j is no candidate of row t if ``self_idx[t] == j``,

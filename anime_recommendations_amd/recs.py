@@ -1234,20 +1234,195 @@ def ease_similar(fit, queries, k, keep=None, batch=EASE_BATCH):
 
 
 # ----------------------------------------------------------------------------------------
+# RP3beta, the three-step random walk with a popularity penalty (Cooper et al. 2014, Paudel et al. 2017; DESIGN.md
+# §4.25): no model takes part
+# ----------------------------------------------------------------------------------------
+GRAPH_SYSTEMS = ("rp3",)    # row-score systems beside HYBRID_SYSTEMS, CONTENT_SYSTEMS and EASE_SYSTEMS (which stay)
+RP3_ALPHA = 1.0             # common values from the literature (alpha = 1, beta = 0 is the plain walk P3); not tuned
+RP3_BETA = 0.3              # on this data
+RP3_NEIGHBOURS = 100
+RP3_MAX_Q = 16383           # ANIREC_WCOOC_MAX_Q: the user weight is an integer of 14 bits
+
+
+def rp3_user_weights(deg, alpha):
+    """The integer user weights of an RP3 fit, int32 [n_users], on the host in NumPy fp64: 0 where ``deg`` (how many
+    items the user liked) is 0, else max(1, rint(16383 (d_min / deg) ** alpha)) with d_min the smallest positive degree.
+    14 bits: the walk's deg ** -alpha relative to the lightest user's, so that every sum over users is one of integers.
+    A user with 10 000 likes gets 2 instead of 1.6 when d_min is 1: the heaviest users are the coarsest."""
+    deg = np.asarray(_host(deg), np.int64).reshape(-1)
+    q = np.zeros(len(deg), np.int32)
+    pos = deg > 0
+    if pos.any():
+        d_min = np.float64(deg[pos].min())
+        q[pos] = np.maximum(1.0, np.rint(16383.0 * (d_min / deg[pos].astype(np.float64)) ** np.float64(alpha))) \
+            .astype(np.int32)
+    return q
+
+
+def check_rp3(alpha, beta, neighbours):
+    """(alpha, beta as floats, neighbours as an int), or a ValueError before any GPU use: an ``alpha`` or ``beta`` that
+    is negative or not finite, a negative ``neighbours``."""
+    alpha, beta, neighbours = float(alpha), float(beta), int(neighbours)
+    for name, v in (("alpha", alpha), ("beta", beta)):
+        if not (0.0 <= v < float("inf")):
+            raise ValueError("rp3: %s = %r must be finite and >= 0" % (name, v))
+    if neighbours < 0:
+        raise ValueError("rp3: neighbours = %d must be >= 0" % neighbours)
+    return alpha, beta, neighbours
+
+
+def _rp3_pow2(m):
+    """the power of two that puts ``m`` in [256, 512); 1 for an m that is not a positive number"""
+    if not (m > 0.0 and m < float("inf")):
+        return 1.0
+    return float(np.ldexp(1.0, 9 - int(np.frexp(m)[1])))
+
+
+def rp3_fit(user_idx, anime_idx, rating, n_users, n_items, liked_min_rating=0.0, alpha=RP3_ALPHA, beta=RP3_BETA,
+            neighbours=RP3_NEIGHBOURS, device="cuda:0"):
+    """An RP3beta model from a rating list: a user LIKED an anime when the (scaled) rating is at or above
+    ``liked_min_rating`` (compared in fp32; 0.0 = every rating).  With pop(i) the users who liked item i and deg(u) the
+    items user u liked:  W[i][j] = pop(i)^-alpha pop(j)^-beta sum_{u liked i and j} deg(u)^-alpha  off the diagonal, 0
+    on it; a history H scores item j as sum_{i in H} h_i W[i][j].  alpha = 1, beta = 0 is the plain three-step walk P3,
+    beta > 0 the popularity penalty.  The defaults (1.0, 0.3, 100 neighbours) are common values from the literature,
+    not tuned on this data.  The user term is the integer ``rp3_user_weights`` (14 bits), the sum S over users is exact
+    (``ops.wcooc_scores`` on the i8 matrix cores, COOC_BATCH query items a call), w = float32((float64(S) pop(i)^-alpha)
+    pop(j)^-beta) with fp64 scale arrays from the host (0 where pop is 0).  Every row keeps its ``neighbours`` largest
+    weights (``ops.rows_topk`` under the call's own excl rows: never the item itself nor an item without a common
+    user) — truncation is part of the method; ``neighbours`` = 0 keeps the dense matrix.  All kept weights are then
+    multiplied by the one power of two that puts the largest of them in [256, 512): exact, no ranking changes, and
+    history weights up to 2 stay inside ``ops.itemknn_scores``' term bound of 1024.
+    Returns {"nbr_idx" int32 [n_items, K], "nbr_sim" fp32 [n_items, K]} (the tables of an item-kNN model; padded with
+    -1 / NaN) or, for neighbours = 0, {"W" fp32 [n_items, n_items]} with a zero diagonal; plus "pop" int32 [n_items],
+    "deg" int32 [n_users], "user_q" int32 [n_users] on the device and the parameters ("alpha", "beta", "neighbours",
+    "scale", "n_items", "n_users", "n_liked", "liked_min_rating").
+    Raises ValueError, before any GPU use, for an ``alpha`` / ``beta`` that is negative or not finite, a negative
+    ``neighbours`` or more than the other items, columns of unequal length."""
+    from . import ops
+    alpha, beta, neighbours = check_rp3(alpha, beta, neighbours)
+    n_users, n_items = int(n_users), int(n_items)
+    ops.check_wcooc(n_items, n_users)
+    if neighbours > max(1, n_items - 1):
+        raise ValueError("rp3_fit: neighbours = %d is more than the %d other items" % (neighbours, n_items - 1))
+    u, a = _host(user_idx).reshape(-1), _host(anime_idx).reshape(-1)
+    r = _host(rating).reshape(-1).astype(np.float32)
+    if not len(u) == len(a) == len(r):
+        raise ValueError("rp3_fit: user_idx, anime_idx and rating must have one entry per rating")
+    liked = r >= np.float32(liked_min_rating)
+    dev = torch.device(device)
+    ud = torch.as_tensor(u[liked].astype(np.int32), device=dev)
+    ad = torch.as_tensor(a[liked].astype(np.int32), device=dev)
+    bits = item_bits(ud, ad, n_users, n_items, device=dev)
+    # (the popcounts of the rows of both bit matrices: a repeated pair counts once, as in the bits)
+    pop = ops.cooc_scores(bits, n_users, [0], pop=True)[3]
+    deg = ops.cooc_scores(ops.seen_bits(ud, ad, n_users, n_items, device=dev), n_items, [0], pop=True)[3]
+    del ud, ad
+    user_q = rp3_user_weights(deg, alpha)
+    p = _host(pop).astype(np.float64)
+    row, col = np.zeros(n_items), np.zeros(n_items)
+    row[p > 0] = p[p > 0] ** np.float64(-alpha)
+    col[p > 0] = p[p > 0] ** np.float64(-beta)
+    uq = torch.as_tensor(user_q, device=dev)
+    row, col = torch.as_tensor(row, device=dev), torch.as_tensor(col, device=dev)
+    q = torch.arange(n_items, dtype=torch.int32, device=dev)
+    fit = {"pop": pop, "deg": deg, "user_q": uq, "alpha": alpha, "beta": beta, "neighbours": neighbours,
+           "n_items": n_items, "n_users": n_users, "n_liked": int(liked.sum()),
+           "liked_min_rating": float(liked_min_rating)}
+    if neighbours:
+        idx = torch.empty(n_items, neighbours, dtype=torch.int32, device=dev)
+        sim = torch.empty(n_items, neighbours, dtype=torch.float32, device=dev)
+        for q0 in range(0, n_items, COOC_BATCH):
+            w, _, ex = ops.wcooc_scores(bits, n_users, uq, q[q0:q0 + COOC_BATCH], row, col, excl=True)
+            idx[q0:q0 + COOC_BATCH], sim[q0:q0 + COOC_BATCH] = ops.rows_topk(w, neighbours, wbits=ex)
+        kept = torch.where(idx >= 0, sim, torch.zeros_like(sim))
+        fit["scale"] = _rp3_pow2(float(kept.max().item()))
+        fit["nbr_idx"], fit["nbr_sim"] = idx, sim * fit["scale"]
+    else:
+        W = torch.empty(n_items, n_items, dtype=torch.float32, device=dev)
+        for q0 in range(0, n_items, COOC_BATCH):
+            W[q0:q0 + COOC_BATCH] = ops.wcooc_scores(bits, n_users, uq, q[q0:q0 + COOC_BATCH], row, col)[0]
+        W.diagonal().zero_()
+        fit["scale"] = _rp3_pow2(float(W.max().item()))
+        fit["W"] = W.mul_(fit["scale"])
+    return fit
+
+
+def _rp3_source(fit, offsets, hist_idx, hist_w):
+    """(the row source of ``rp3_rows_source``, n_lists)"""
+    return _ease_source(fit, offsets, hist_idx, hist_w) if "W" in fit else _knn_source(fit, offsets, hist_idx, hist_w)
+
+
+def _rp3_device(fit):
+    return (fit["W"] if "W" in fit else fit["nbr_idx"]).device
+
+
+def rp3_rows_source(fit, offsets, hist_idx, hist_w=None):
+    """A row source of the RP3 scores of the lists ``rp3_topk`` takes: ``itemknn_rows_source`` over a truncated fit,
+    ``ease_rows_source`` over a dense one (``ops.itemknn_scores`` / ``ops.ease_scores``: the same fixed-point sums)."""
+    return _rp3_source(fit, offsets, hist_idx, hist_w)[0]
+
+
+def rp3_topk(fit, offsets, hist_idx, hist_w=None, k=10, watched_bits=None, keep=None, batch=ITEMKNN_BATCH):
+    """RP3 recommendation lists: list l's history ``hist_idx[offsets[l]:offsets[l + 1]]`` (``history_csr`` builds it;
+    ``hist_w`` None = weight 1, at most 2) scored through the weights of ``fit`` and the ``k`` best anime without a bit
+    in ``watched_bits`` [n_lists, ceil(n_items/32)] and with ``keep`` [n_items] set taken by the exact select
+    (``ops.rows_topk``), ``batch`` lists at a time.  Returns (idx int32 [n_lists, k], score fp32 [n_lists, k])."""
+    source, n_l = _rp3_source(fit, offsets, hist_idx, hist_w)
+    return rows_topk_batched(source, n_l, k, watched_bits, keep, batch, "rp3_topk", _rp3_device(fit))
+
+
+def rp3_rank(fit, offsets, hist_idx, hist_w, watched_bits, target_row, target_anime, batch=ITEMKNN_BATCH):
+    """The ranks ``ops.predict_rank`` gives a model, for the RP3 scores of ``rp3_topk``: target t is
+    (``target_row[t]``: a list, ``target_anime[t]``); returns rank int32 [n_t] on the device (0 = first among the anime
+    the list has no watched bit for, the target's own bit ignored).  ``batch`` lists at a time."""
+    source, n_l = _rp3_source(fit, offsets, hist_idx, hist_w)
+    return rows_rank_batched(source, n_l, watched_bits, target_row, target_anime, batch, "rp3_rank", _rp3_device(fit))
+
+
+def rp3_similar(fit, queries, k, keep=None, batch=ITEMKNN_BATCH):
+    """The ``k`` anime with the largest weights in each query item's row of the fit (where a walk from the query ends
+    most often): of the dense W, or of the row's kept neighbours; the query itself is never listed.  Returns (idx int32
+    [nq, k], score fp32 [nq, k]) in ``ops.rows_topk``'s order.  ValueError for a query outside the items."""
+    q = np.asarray(_host(queries), np.int64).reshape(-1)
+    n = int(fit["n_items"])
+    if q.size and (q.min() < 0 or q.max() >= n):
+        raise ValueError("rp3_similar: query item out of range")
+    dev = _rp3_device(fit)
+    qd = torch.as_tensor(q, device=dev)
+    out = np.zeros((q.size, ((n + 31) // 32) * 32), bool)      # the anime that are no candidates of a row
+    if "W" in fit:
+        out[np.arange(q.size), q] = True
+        source = lambda l0, l1: fit["W"][qd[l0:l1]]
+    else:
+        ni, ns = fit["nbr_idx"][qd].long(), fit["nbr_sim"][qd]
+        nh = _host(ni)
+        out[:, :n] = True
+        rr, cc = np.nonzero(nh >= 0)
+        out[rr, nh[rr, cc]] = False
+        rows = torch.zeros(q.size, n + 1, dtype=torch.float32, device=dev)      # (column n takes the padding slots)
+        rows.scatter_(1, torch.where(ni >= 0, ni, torch.full_like(ni, n)), ns)
+        rows = rows[:, :n].contiguous()
+        source = lambda l0, l1: rows[l0:l1]
+    wb = (out.reshape(q.size, -1, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    return rows_topk_batched(source, int(q.size), k, torch.as_tensor(wb.view(np.int32), device=dev), keep, batch,
+                             "rp3_similar", dev)
+
+
+# ----------------------------------------------------------------------------------------
 # hybrid lists: several systems' score rows fused into one (DESIGN.md §4.19)
 # ----------------------------------------------------------------------------------------
-HYBRID_SYSTEMS = ("model", "popularity", "itemknn", "als")
+HYBRID_SYSTEMS =("model", "popularity", "itemknn", "als")
 HYBRID_BATCH = 4096     # users per anirec_fuse_rows call: a score row per system and a fused row each
 
 
 def check_hybrid(systems, weights=None, method="rrf", rrf_c=60):
     """(systems as a tuple of names, weights as floats, the method's name, rrf_c), or a ValueError before any GPU use:
-    a name that is not one of HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
+    a name that is not one of HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS + GRAPH_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
     weights list of another length among it)."""
     from . import ops
     names = [systems] if isinstance(systems, str) else list(systems)
     names = [str(s).strip().lower() for s in names]
-    known = HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS
+    known = HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS + GRAPH_SYSTEMS
     for s in names:
         if s not in known:
             raise ValueError("hybrid system %r is not one of %s" % (s, ", ".join(known)))

@@ -16,7 +16,10 @@ system over all_anime.csv's columns (``--anime_df``, ``--sypnopses_df``, ``--con
 ``--content_min_rating``: command line only; also a member ``--hybrid_systems`` takes), ``--baseline ease`` those of
 EASE, the closed-form linear item-item model fitted on the training slice (``--ease_reg``, ``--ease_min_rating``,
 ``--ease_neighbours``: command line only; reg = 500 is the paper's value for a data set of about this many users, not
-tuned on this data; also a member ``--hybrid_systems`` takes);
+tuned on this data; also a member ``--hybrid_systems`` takes), ``--baseline rp3`` those of RP3beta, the three-step random
+walk with a popularity penalty fitted on the training slice (``--rp3_alpha``, ``--rp3_beta``, ``--rp3_neighbours``,
+``--rp3_min_rating``: command line only; 1, 0.3 and 100 are common values from the literature, not tuned on this data; also
+a member ``--hybrid_systems`` takes);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
 spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
 held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
@@ -107,6 +110,11 @@ CONTENT_FLAGS = {
 EASE_FLAGS = dict(cli.EASE_FLAGS, ease_min_rating=(float, C.EASE_DEFAULTS["min_rating"],
                                                    "the scaled rating (0..1) from which a training rating counts as liked"))
 
+# optional and command-line only, like the item-kNN flags: RP3beta (--baseline rp3, or a member of --hybrid_systems;
+# components.RP3_DEFAULTS: common values from the literature, not tuned on this data)
+RP3_FLAGS = dict(cli.RP3_FLAGS, rp3_min_rating=(float, C.RP3_DEFAULTS["min_rating"],
+                                                "the scaled rating (0..1) from which a training rating counts as liked"))
+
 logger = C.setup_logging("evaluate")
 
 
@@ -157,8 +165,15 @@ def ease_args(args):
     return {f[len("ease_"):]: getattr(args, f) for f in EASE_FLAGS if hasattr(args, f)}
 
 
+def rp3_args(args):
+    """evaluate_frame's ``rp3``: the RP3 flags the parser has"""
+    return {f[len("rp3_"):]: getattr(args, f) for f in RP3_FLAGS if hasattr(args, f)}
+
+
 def go(args):
     content = None
+    if wants(args, "rp3"):                                  # the cheap failures: before any file or GPU use
+        C._system_params({"rp3": rp3_args(args)}, ["rp3"])
     if wants(args, "ease"):                                 # the cheap failures: before any file or GPU use
         C._system_params({"ease": ease_args(args)}, ["ease"])
     if wants_content(args):                                 # the cheap failures: before any file or GPU use
@@ -185,7 +200,7 @@ def go(args):
                                       compare_model=compare_model, hybrid=cli.hybrid_args(args),
                                       hybrid_tune={f[len("hybrid_tune_"):]: getattr(args, f) for f in HYBRID_TUNE_FLAGS
                                                    if hasattr(args, f)}, content=content, ease=ease_args(args),
-                                      **ci)
+                                      rp3=rp3_args(args), **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -215,7 +230,8 @@ def make_parser():
                              "score rows of several of them and the model), hybrid_tuned (the same with cross-fitted "
                              "weights from a grid), content (by TF-IDF vectors of the anime metadata; needs "
                              "--anime_df), ease (by the closed-form linear item-item model EASE fitted on the "
-                             "training ratings), or several separated by a comma")
+                             "training ratings), rp3 (by the RP3beta random walk over the training ratings), or "
+                             "several separated by a comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
@@ -223,11 +239,11 @@ def make_parser():
 
 def make_cli_parser():
     """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*``,
-    ``--compare_model``, ``--hybrid_*``, ``--hybrid_tune_*``, content (``CONTENT_FLAGS``) and ``--ease_*`` flags."""
+    ``--compare_model``, ``--hybrid_*``, ``--hybrid_tune_*``, content (``CONTENT_FLAGS``), ``--ease_*`` and ``--rp3_*`` flags."""
     parser = make_parser()
     for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()) + \
             list(HYBRID_FLAGS.items()) + list(HYBRID_TUNE_FLAGS.items()) + list(CONTENT_FLAGS.items()) + \
-            list(EASE_FLAGS.items()):
+            list(EASE_FLAGS.items()) + list(RP3_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

@@ -1341,6 +1341,40 @@ int anirec_ease_scores(const float *W, int64_t ldw, int32_t n_items, const int32
                        float *out_scores, int64_t ld, int32_t *err_flag, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ *  USER-WEIGHTED CO-OCCURRENCE on the i8 matrix cores: what the graph baselines P3alpha (Cooper et al. 2014) and
+ *  RP3beta (Paudel et al. 2017) are built from.  item_bits as anirec_cooc_scores takes it; user_q
+ *  [n_users] is an integer weight per user, 0 .. ANIREC_WCOOC_MAX_Q (14 bits: two 7-bit limbs of the signed i8
+ *  operand).
+ *
+ * anirec_wcooc_scores: one row per query item q = queries[t], against every item j:
+ *   S(q,j)   the sum of user_q[u] over the users u < n_users set in both row q and row j, exact in int64
+ *   w        S != 0 ? (float)(((double)S * rs) * cs) : +0.0f, with rs = row_scale ? row_scale[q] : 1.0 and
+ *            cs = col_scale ? col_scale[j] : 1.0; the two fp64 multiplies are rounded one by one, nothing contracted
+ *   out_w [nq][n_items] = w; out_sum (optional) [nq][n_items] = S;
+ *   out_excl (optional) [nq][ceil(n_items/32)]: bit j of row t set iff S == 0 or j == q — the mask rows
+ *   anirec_rows_topk takes as wbits; bits at positions >= n_items are clear.
+ * A query outside [0, n_items) raises *err_flag (device; overwritten by the call) to 1: its rows are NaN / -1 / every
+ * bit j < n_items set, nothing is read through it, the other queries are unaffected.  A user_q outside its range counts
+ * as 0 and raises the flag too.  A query may repeat.  A query's rows depend on that query, the bits, user_q and the two
+ * scales alone: not on nq, its position in `queries`, the launch shape or what the workspace held.  Each limb is
+ * accumulated in int32 by v_mfma_i32_16x16x64_i8: 127 * 2^24 < 2^31, so n_users <= 2^24 keeps every accumulator
+ * exact and the call bit-reproducible.  A 256-thread workgroup owns 64 queries x 64 keys and stages
+ * anirec_wcooc_chunk_words() user words of both row sets, and the limb bytes of those users, in LDS per pass.
+ * n_items < 1, n_users outside 1 .. 2^24, a negative nq, or with nq > 0 a NULL item_bits, user_q, queries, out_w,
+ * err_flag or ws, a pointer not aligned to its element (ws: 16 bytes): ANIREC_EINVAL before anything is enqueued or
+ * written.  nq == 0: ANIREC_OK, nothing enqueued.  ws: anirec_wcooc_workspace_bytes(n_items, n_users, nq) bytes (0 for
+ * a bad argument; the two limb byte arrays), less is ANIREC_EWORKSPACE.  Stream-ordered plain launches, no host
+ * read-back: graph-capturable.
+ * ------------------------------------------------------------------------- */
+#define ANIREC_WCOOC_MAX_Q 16383
+size_t anirec_wcooc_chunk_words(void);
+size_t anirec_wcooc_workspace_bytes(int32_t n_items, int32_t n_users, int32_t nq);
+int anirec_wcooc_scores(const uint32_t *item_bits, int32_t n_items, int32_t n_users, const int32_t *user_q,
+                        const int32_t *queries, int32_t nq, const double *row_scale, const double *col_scale,
+                        float *out_w, int64_t *out_sum, uint32_t *out_excl, int32_t *err_flag, void *ws,
+                        size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------- *
  *  Ranks to metric sums, and a Poisson bootstrap over users on them.  Integer sums throughout: no
  *  result depends on the order the rows are met in.
  *  The statistic: the resampling UNIT is the user (a user's held-out ratings are not independent, so a replicate
