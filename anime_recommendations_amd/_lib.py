@@ -32,6 +32,10 @@ EXPLAIN_TILE_FLOATS = 8192  # anirec_explain_tile(dim, k): dim * tile and k * (t
 KMEANS_MAX_K = 4096         # ANIREC_KMEANS_MAX_K: the most centroids anirec_kmeans_assign / anirec_kmeans_fit take
 KMEANS_MAX_ITER = 1000      # anirec_kmeans_fit: the most iterations one call enqueues
 KMEANS_IMAGE_FLOATS = 32768  # anirec_kmeans_tile(dim) = KMEANS_IMAGE_FLOATS // dim: the centroids of one LDS image
+TSNE_MAX_ROWS = 1 << 20     # ANIREC_TSNE_MAX_ROWS: the most rows anirec_tsne_forces / anirec_tsne_fit take
+TSNE_MAX_ITER = 4096        # ANIREC_TSNE_MAX_ITER: the most iterations one anirec_tsne_fit enqueues
+TSNE_TILE = 1024            # anirec_tsne_tile(): the j points of one LDS tile of the all-pairs kernel
+TSNE_MAX_SPLITS = 1024      # the largest j_splits
 ALS_MAX_CG = 16             # ANIREC_ALS_MAX_CG: the most conjugate-gradient steps of anirec_als_half_sweep
 ALS_GRAM_CHUNK = 1024       # ANIREC_ALS_GRAM_CHUNK: rows of one chunk of anirec_als_gram
 CALIBRATE_MAX_CAND = 1024   # anirec_calibrate_max_cand(): the longest list anirec_calibrate_rerank / _list_calibration take
@@ -268,6 +272,12 @@ PROTOTYPES = {
     "anirec_kmeans_assign": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
     "anirec_kmeans_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "anirec_kmeans_fit": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # exact t-SNE on a neighbour graph (mapped tables)
+    "anirec_tsne_tile": (_sz, []),
+    "anirec_tsne_workspace_bytes": (_sz, [_i32, _i32]),
+    "anirec_tsne_forces": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "anirec_tsne_fit": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _i32, C.c_double, C.c_double, _i32, _vp, _vp,
+                                  _vp, _vp, _sz, _vp]),
     # item-kNN from co-occurrence: popcount similarity rows, the select / the rank over rows a caller holds, history scores
     "anirec_cooc_chunk_words": (_sz, []),
     "anirec_cooc_workspace_bytes": (_sz, [_i32, _i32]),

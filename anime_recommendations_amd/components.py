@@ -827,6 +827,79 @@ def cluster_query_row(table, query, user_ids, anime_ids, anime_df):
 
 
 # ----------------------------------------------------------------------------------------
+# embedding_map: a two-dimensional picture of a table (exact t-SNE)
+# ----------------------------------------------------------------------------------------
+MAP_MAX_ROWS = 50000     # --map_max_rows: a larger table is sampled by the seed
+
+
+def map_sample(n_rows, max_rows, seed, always=None):
+    """The table rows a map is drawn from, ascending: all of them when ``max_rows`` is 0 or the table has no more,
+    else ``max_rows`` rows drawn without replacement by ``np.random.default_rng(seed)`` (``always``: a row that is in
+    the sample whatever the draw, the query's)."""
+    n_rows, max_rows = int(n_rows), int(max_rows)
+    if max_rows < 0:
+        raise ValueError("embedding_map: map_max_rows = %d must not be negative" % max_rows)
+    if max_rows == 0 or n_rows <= max_rows:
+        return np.arange(n_rows)
+    take = np.random.default_rng(seed).choice(n_rows, size=max_rows, replace=False)
+    if always is not None and always not in take:
+        take[0] = always
+    return np.sort(take)
+
+
+def map_frame(fit, table, ids, meta=None, clusters=None):
+    """One row per mapped table row of a ``recs.map_rows`` result on the ``anime`` or ``user`` table (``ids``: the id of
+    every mapped row; ``meta``: the rows' ``metadata_by_index`` for the anime table): ``anime_id`` / ``user_id``,
+    ``name`` (anime only), ``x``, ``y`` (fp32; empty for a row without a position: a zero embedding row) and
+    ``cluster`` (the rows' ``recs.cluster_rows`` assignment where ``clusters`` is one, else -1)."""
+    table = cluster_table_name(table)
+    Y = fit["Y"].cpu().numpy()
+    ids = np.asarray(ids)
+    if len(Y) != len(ids):
+        raise ValueError("embedding_map: %d positions for %d ids" % (len(Y), len(ids)))
+    cols = {table + "_id": ids}
+    if table == "anime":
+        label = meta["Name"].to_numpy() if meta is not None else [None] * len(ids)
+        cols["name"] = [str(label[i]) if isinstance(label[i], str) else str(ids[i]) for i in range(len(ids))]
+    cols["x"], cols["y"] = Y[:, 0], Y[:, 1]
+    cols["cluster"] = clusters["assign"].cpu().numpy() if clusters is not None else np.full(len(ids), -1, np.int32)
+    return pd.DataFrame(cols)
+
+
+def map_neighbours_on_map(frame, row, k=10):
+    """The ``k`` rows of a ``map_frame`` nearest ``row`` ON THE MAP (Euclidean, float64, ties to the lower row; rows
+    without a position never): a list of (id, name or None, distance)."""
+    xy = frame[["x", "y"]].to_numpy(np.float64)
+    d = np.sqrt(((xy - xy[row]) ** 2).sum(axis=1))
+    d[row] = np.nan
+    order = [i for i in np.lexsort((np.arange(len(d)), d)) if np.isfinite(d[i])][:int(k)]
+    idc = frame.columns[0]
+    return [(frame[idc].iloc[i].item(), str(frame["name"].iloc[i]) if "name" in frame else None, float(d[i]))
+            for i in order]
+
+
+def map_plot(frame, path, title=None):
+    """A PNG scatter of a ``map_frame`` coloured by cluster (matplotlib's Agg backend).  Returns False, having written
+    nothing, where matplotlib cannot be imported."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return False
+    ok = np.isfinite(frame["x"].to_numpy()) & np.isfinite(frame["y"].to_numpy())
+    fig, ax = plt.subplots(figsize=(10, 10))
+    ax.scatter(frame["x"][ok], frame["y"][ok], c=frame["cluster"][ok], s=4, cmap="tab20", linewidths=0)
+    ax.set_xticks([])
+    ax.set_yticks([])
+    if title:
+        ax.set_title(title)
+    fig.savefig(path, dpi=120, bbox_inches="tight")
+    plt.close(fig)
+    return True
+
+
+# ----------------------------------------------------------------------------------------
 # diverse_recs: model_recs with a greedy MMR re-rank of the best `pool` candidates
 # ----------------------------------------------------------------------------------------
 def _list_cosines(Wh, idx):

@@ -915,6 +915,88 @@ def kmeans_fit(What, C0, max_iter=50):
     return C, assign, sim, count, int(iters), bool(converged)
 
 
+def check_tsne(n_rows, iters=1, exag_iters=0, exaggeration=12.0, lr=200.0, j_splits=0):
+    """The argument checks of ``tsne_forces`` / ``tsne_fit`` (no device needed): ValueError naming the limit for
+    ``n_rows`` outside 1 .. TSNE_MAX_ROWS, ``iters`` outside 1 .. TSNE_MAX_ITER, a negative ``exag_iters``, an
+    ``exaggeration`` outside (0, 1e6] or ``lr`` outside (0, 1e9] (a NaN included), ``j_splits`` outside
+    0 .. TSNE_MAX_SPLITS.  Returns (n_rows, iters, exag_iters, exaggeration, lr, j_splits)."""
+    n_rows, iters, exag_iters, j_splits = int(n_rows), int(iters), int(exag_iters), int(j_splits)
+    exaggeration, lr = float(exaggeration), float(lr)
+    if not 1 <= n_rows <= _lib.TSNE_MAX_ROWS:
+        raise ValueError("tsne: n_rows = %d must be in 1 .. %d (TSNE_MAX_ROWS)" % (n_rows, _lib.TSNE_MAX_ROWS))
+    if not 1 <= iters <= _lib.TSNE_MAX_ITER:
+        raise ValueError("tsne: iters = %d must be in 1 .. %d (the iterations one call enqueues)"
+                         % (iters, _lib.TSNE_MAX_ITER))
+    if exag_iters < 0:
+        raise ValueError("tsne: exag_iters = %d must not be negative" % exag_iters)
+    if not 0.0 < exaggeration <= 1e6:
+        raise ValueError("tsne: exaggeration = %r must be in (0, 1e6]" % exaggeration)
+    if not 0.0 < lr <= 1e9:
+        raise ValueError("tsne: lr = %r must be in (0, 1e9]" % lr)
+    if not 0 <= j_splits <= _lib.TSNE_MAX_SPLITS:
+        raise ValueError("tsne: j_splits = %d must be in 0 .. %d (0 = the library's choice)"
+                         % (j_splits, _lib.TSNE_MAX_SPLITS))
+    return n_rows, iters, exag_iters, exaggeration, lr, j_splits
+
+
+def _tsne_rows(Y, what):
+    if not isinstance(Y, torch.Tensor) or Y.dim() != 2 or Y.shape[1] != 2:
+        raise ValueError("%s: Y must be an [n_rows, 2] tensor" % what)
+    return int(Y.shape[0])
+
+
+def _tsne_inputs(Y, offsets, idx, val, what):
+    """The checks of the CSR that need no device (shapes; the offsets when they are on the host), and the tensors as the
+    library takes them: (Y fp32 [n, 2], offsets int64, idx int32, val fp32) on Y's device.  Offsets that live on the
+    device are checked there (one reduction, one readback)."""
+    n = int(Y.shape[0])
+    off = torch.as_tensor(offsets).to(torch.int64)
+    idx, val = torch.as_tensor(idx), torch.as_tensor(val)
+    if off.dim() != 1 or idx.dim() != 1 or val.dim() != 1 or idx.shape != val.shape:
+        raise ValueError("%s: offsets must be [n_rows + 1], idx and val one entry per stored pair" % what)
+    _check_csr(off, n, idx.numel(), what, "stored pairs")
+    _need_gpu()
+    dev = Y.device
+    assert Y.is_cuda and Y.dtype == torch.float32, "fp32 [n, 2] device coordinates"
+    return Y.contiguous(), off.to(dev).contiguous(), _i32(idx, dev), _f32(val, dev)
+
+
+def tsne_forces(Y, offsets, idx, val, j_splits=0):
+    """The integer sums of one t-SNE iteration at the coordinates ``Y`` fp32 [n, 2] (anirec_tsne_forces; DESIGN.md
+    4.26): all pairs for the repulsion, the stored pairs of the symmetric CSR (``offsets`` int64 [n + 1], ``idx``,
+    ``val`` = P' in [0, 2]) for the attraction.  Returns (rx, ry, ax, ay int64 [n], z int64 [2] = the low and high word
+    of the exact sum, as bit patterns) on the device and the info bits as an int (1: a row that is out, 2: a stored
+    value outside [0, 2], 4: a stored index or a row's offsets out of range).  No bit depends on ``j_splits``.  Raises
+    ValueError as ``check_tsne`` does and for a CSR that does not rise from 0 to the number of stored pairs."""
+    check_tsne(_tsne_rows(Y, "tsne_forces"), j_splits=j_splits)
+    Y, off, idx, val = _tsne_inputs(Y, offsets, idx, val, "tsne_forces")
+    dev, n = Y.device, int(Y.shape[0])
+    rx, ry, ax, ay, z, info = _outputs(dev, (torch.int64, n), (torch.int64, n), (torch.int64, n), (torch.int64, n),
+                                       (torch.int64, 2), (torch.int32, 1))
+    _call("anirec_tsne_forces", Y, n, off, idx if idx.numel() else None, val if val.numel() else None, idx.numel(),
+          int(j_splits), rx, ry, ax, ay, z, info)
+    return rx, ry, ax, ay, z, int(info.item())
+
+
+def tsne_fit(Y0, offsets, idx, val, iters=1000, exag_iters=250, exaggeration=12.0, lr=200.0, j_splits=0):
+    """``iters`` iterations of exact t-SNE from the coordinates ``Y0`` fp32 [n, 2] on the symmetric CSR affinities
+    (anirec_tsne_fit), all enqueued at once: gradient descent with momentum (0.5, then 0.8) and gains,
+    the first ``exag_iters`` iterations with the attraction times ``exaggeration``.  Exact and order-free: the sums are
+    int64 sums of fixed-point pair terms and the update is fp64, so the same inputs give the same bits whatever
+    ``j_splits``.  Returns (Y fp32 [n, 2], V fp64 [n, 2], G fp64 [n, 2]) on the device and the info bits as
+    ``tsne_forces`` does.  ``Y0`` is not modified.  Raises ValueError as ``tsne_forces`` does."""
+    _, iters, exag_iters, exaggeration, lr, j_splits = check_tsne(_tsne_rows(Y0, "tsne_fit"), iters, exag_iters,
+                                                                  exaggeration, lr, j_splits)
+    Y0, off, idx, val = _tsne_inputs(Y0, offsets, idx, val, "tsne_fit")
+    dev, n = Y0.device, int(Y0.shape[0])
+    Y = Y0.clone()
+    V, G, info = _outputs(dev, (torch.float64, n, 2), (torch.float64, n, 2), (torch.int32, 1))
+    ws = _workspace(None, dev, "anirec_tsne_workspace_bytes", n, iters)
+    _call("anirec_tsne_fit", Y, n, off, idx if idx.numel() else None, val if val.numel() else None, idx.numel(), iters,
+          exag_iters, exaggeration, lr, j_splits, V, G, info, ws, ws.numel())
+    return Y, V, G, int(info.item())
+
+
 def cooc_measure(measure):
     """ANIREC_COOC_* of a measure name, in any case: ``cosine``, ``jaccard``, ``confidence``.  ValueError, listing
     them, for another."""

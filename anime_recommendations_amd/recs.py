@@ -545,6 +545,188 @@ def assign_clusters(C, rows, normalised=None, device="cuda:0"):
     return ops.kmeans_assign(What, torch.as_tensor(C, device=What.device))
 
 
+MAP_BISECT_STEPS = 64   # bisection steps of a row's bandwidth
+MAP_QUERY_BATCH = 4096  # query rows of one cosine_topk call of the neighbour lists
+
+
+def _map_bandwidths(d2, perplexity, steps=MAP_BISECT_STEPS):
+    """p(j|i) over each row's neighbour distances ``d2`` fp64 [n, k] (any device): the precision beta of every row by
+    ``steps`` bisection steps on the entropy of exp(-beta (d2 - min d2)) towards log(perplexity), the bracket [0, inf)
+    doubled while it is open.  Plumbing in torch fp64 (it contains ``exp``: held to NumPy by tolerance, not by bits).
+    Returns (p fp64 [n, k], rows summing to 1; beta fp64 [n])."""
+    d2 = d2.to(torch.float64)
+    n = d2.shape[0]
+    target = float(np.log(np.float64(perplexity)))
+    d0 = d2 - d2.min(dim=1, keepdim=True).values
+    beta = torch.ones(n, dtype=torch.float64, device=d2.device)
+    lo = torch.zeros_like(beta)
+    hi = torch.full_like(beta, float("inf"))
+    for _ in range(int(steps)):
+        p = torch.exp(-d0 * beta[:, None])
+        s = p.sum(dim=1)
+        h = torch.log(s) + beta * (d0 * p).sum(dim=1) / s
+        high = h > target                       # too flat: beta must grow
+        lo = torch.where(high, beta, lo)
+        hi = torch.where(high, hi, beta)
+        beta = torch.where(torch.isinf(hi), beta * 2.0, (lo + hi) / 2.0)
+    p = torch.exp(-d0 * beta[:, None])
+    return p / p.sum(dim=1, keepdim=True), beta
+
+
+def _map_symmetrise(nbr, p, n):
+    """P' = p(j|i) + p(i|j) as a CSR over ``n`` rows (offsets int64 [n + 1], idx int32 ascending in a row, val fp32) from
+    the neighbour lists ``nbr`` int [n, k] (-1 = none) and ``p`` fp64 [n, k], on their device.  Each value is the sum of
+    at most two terms, so the order the adds land in cannot change it."""
+    dev = nbr.device
+    rows = torch.arange(n, device=dev).repeat_interleave(nbr.shape[1])
+    cols = nbr.reshape(-1).long()
+    vals = p.reshape(-1).to(torch.float64)
+    keep = cols >= 0
+    rows, cols, vals = rows[keep], cols[keep], vals[keep]
+    key = torch.cat([rows * n + cols, cols * n + rows])
+    uniq, inv = torch.unique(key, return_inverse=True)
+    summed = torch.zeros(uniq.numel(), dtype=torch.float64, device=dev).index_add_(0, inv, torch.cat([vals, vals]))
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(torch.bincount(uniq // n, minlength=n), 0)
+    return offsets, (uniq % n).to(torch.int32), summed.to(torch.float32)
+
+
+def _map_neighbours(What, queries, k, keep=None):
+    """(idx int32 [nq, k], cos fp32 [nq, k]) of the query rows' nearest rows by ``ops.cosine_topk`` (exclude_self set),
+    a batch of query rows at a time"""
+    from . import ops
+    out = [ops.cosine_topk(What, queries[b:b + MAP_QUERY_BATCH], k, exclude_self=True, keep=keep)
+           for b in range(0, int(queries.numel()), MAP_QUERY_BATCH)]
+    return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+
+
+def check_map(n_rows, perplexity, neighbours=None):
+    """The argument checks of ``map_affinities`` on a table of ``n_rows`` usable rows (no device needed): (perplexity
+    float, neighbours int), ``neighbours`` = None being min(n_rows - 1, 3 * perplexity).  ValueError for fewer than 2
+    rows or more than TSNE_MAX_ROWS, ``neighbours`` outside 1 .. n_rows - 1, a perplexity outside [1, neighbours]."""
+    n_rows, perplexity = int(n_rows), float(perplexity)
+    if not 2 <= n_rows <= _lib.TSNE_MAX_ROWS:
+        raise ValueError("map: a table of %d usable rows; a map takes 2 .. %d (TSNE_MAX_ROWS)"
+                         % (n_rows, _lib.TSNE_MAX_ROWS))
+    if not perplexity >= 1.0:
+        raise ValueError("map: perplexity = %r must be at least 1" % perplexity)
+    k = min(n_rows - 1, int(3 * perplexity)) if neighbours is None else int(neighbours)
+    if not 1 <= k <= n_rows - 1:
+        raise ValueError("map: neighbours = %d must be in 1 .. %d (the other usable rows)" % (k, n_rows - 1))
+    if perplexity > k:
+        raise ValueError("map: perplexity = %r cannot exceed the %d neighbours of a row" % (perplexity, k))
+    return perplexity, k
+
+
+def map_affinities(What_or_table, perplexity=30.0, neighbours=None, normalised=None, device="cuda:0"):
+    """The t-SNE affinities of an embedding table: for every usable row (``usable_rows``) its
+    ``neighbours`` nearest usable rows by the exact ``ops.cosine_topk`` (default min(n - 1, 3 * perplexity)), d^2 = 2 -
+    2 cos on the unit rows, the row's bandwidth by 64 bisection steps towards ``perplexity``, symmetrised to P'_ij =
+    p(j|i) + p(i|j).  ``What_or_table`` as ``cluster_rows`` takes it.
+    Returns a dict: rows int64 [m] (the usable rows of the table, ascending: the CSR's row r is table row rows[r]),
+    offsets int64 [m + 1], idx int32, val fp32 (device tensors), beta fp64 [m], n_rows, perplexity, neighbours, What (the
+    unit rows).  Raises ValueError as ``check_map`` does."""
+    if len(tuple(What_or_table.shape)) != 2:
+        raise ValueError("map_affinities: a table must be [n_rows, width]")
+    _lib.check_width(What_or_table.shape[1])
+    check_map(What_or_table.shape[0], perplexity, neighbours)      # the refusals that need no device come first
+    What = _unit_rows(What_or_table, normalised, device)
+    rows = torch.nonzero(usable_rows(What)).reshape(-1)
+    m = int(rows.numel())
+    perplexity, k = check_map(m, perplexity, neighbours)
+    Wu = What if m == What.shape[0] else What[rows].contiguous()
+    nbr, cos = _map_neighbours(Wu, torch.arange(m, device=What.device, dtype=torch.int32), k)
+    p, beta = _map_bandwidths(2.0 - 2.0 * cos.to(torch.float64), perplexity)
+    offsets, idx, val = _map_symmetrise(nbr, p, m)
+    return dict(rows=rows, offsets=offsets, idx=idx, val=val, beta=beta, n_rows=int(What.shape[0]),
+                perplexity=perplexity, neighbours=k, What=What)
+
+
+def map_lr(n_rows, exaggeration=12.0):
+    """scikit-learn's automatic learning rate: max(n / exaggeration / 4, 50)"""
+    return max(float(n_rows) / float(exaggeration) / 4.0, 50.0)
+
+
+def map_kl(Y, offsets, idx, val):
+    """KL(P || Q) of the map ``Y`` [m, 2] under the CSR affinities (P = P' / (2 m)), torch fp64 in row chunks; for
+    reporting only."""
+    Y = Y.to(torch.float64)
+    m = int(Y.shape[0])
+    Z = torch.zeros((), dtype=torch.float64, device=Y.device)
+    chunk = max(1, (1 << 24) // m)
+    for b in range(0, m, chunk):
+        d2 = (Y[b:b + chunk, None, :] - Y[None, :, :]).square().sum(dim=2)
+        Z += (1.0 / (1.0 + d2)).sum() - min(chunk, m - b)     # the self pairs: q = 1 each
+    r = torch.arange(m, device=Y.device).repeat_interleave(offsets[1:] - offsets[:-1])
+    q = 1.0 / (1.0 + (Y[r] - Y[idx.long()]).square().sum(dim=1))
+    P = val.to(torch.float64) / (2.0 * m)
+    ok = P > 0
+    return float((P[ok] * torch.log(P[ok] * Z / q[ok])).sum())
+
+
+def map_rows(What_or_table, perplexity=30.0, iters=1000, exag_iters=250, exaggeration=12.0, lr=None, seed=0, init=None,
+             affinities=None, normalised=None, device="cuda:0"):
+    """A two-dimensional map of an embedding table by exact t-SNE (``ops.tsne_fit``): the same seed
+    gives the same bits.  ``affinities``: a ``map_affinities`` result (None computes it with ``perplexity``).
+    Y0 = 1e-4 * ``np.random.default_rng(seed).standard_normal((n_rows, 2))`` as fp32 unless ``init`` [n_rows, 2] is
+    given; ``lr`` = None is scikit-learn's rule max(m / exaggeration / 4, 50) over the m usable rows.
+    Returns a dict: Y fp32 [n_rows, 2] on the device, centred over the usable rows, NaN for a row that is not usable;
+    kl (the final KL divergence, float); info (``ops.tsne_fit``'s bits); lr, iters, seed, affinities."""
+    from . import ops
+    shape = tuple(What_or_table.shape)
+    ops.check_tsne(max(1, min(shape[0], _lib.TSNE_MAX_ROWS)), iters, exag_iters, exaggeration, 1.0 if lr is None else lr)
+    if init is not None and tuple(np.shape(init)) != (shape[0], 2):
+        raise ValueError("map_rows: init must be [%d, 2], got %s" % (shape[0], tuple(np.shape(init))))
+    aff = affinities if affinities is not None else map_affinities(What_or_table, perplexity, None, normalised, device)
+    if aff["n_rows"] != shape[0]:
+        raise ValueError("map_rows: affinities of a table of %d rows, not %d" % (aff["n_rows"], shape[0]))
+    rows, dev = aff["rows"], aff["offsets"].device
+    m = int(rows.numel())
+    lr = map_lr(m, exaggeration) if lr is None else float(lr)
+    if init is None:
+        Y0 = (1e-4 * np.random.default_rng(seed).standard_normal((shape[0], 2))).astype(np.float32)
+    else:
+        Y0 = np.ascontiguousarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init, np.float32)
+    Y0 = torch.as_tensor(Y0, device=dev)[rows].contiguous()
+    Ym, _, _, info = ops.tsne_fit(Y0, aff["offsets"], aff["idx"], aff["val"], iters, exag_iters, exaggeration, lr)
+    kl = map_kl(Ym, aff["offsets"], aff["idx"], aff["val"])
+    Ym = (Ym.to(torch.float64) - Ym.to(torch.float64).mean(dim=0, keepdim=True)).to(torch.float32)
+    Y = torch.full((shape[0], 2), float("nan"), dtype=torch.float32, device=dev)
+    Y[rows] = Ym
+    return dict(Y=Y, kl=kl, info=info, lr=lr, iters=int(iters), seed=seed, affinities=aff)
+
+
+def _map_place_positions(Y, nbr, cos, perplexity):
+    """The positions of placed rows: the p(j|row)-weighted mean (fp64) of the map positions ``Y`` [m, 2] of each row's
+    neighbours ``nbr`` int [r, k] with the cosines ``cos`` [r, k]; the bandwidth code of the fit.  fp32 [r, 2]."""
+    p, _ = _map_bandwidths(2.0 - 2.0 * cos.to(torch.float64), perplexity)
+    return (p[:, :, None] * Y.to(torch.float64)[nbr.long()]).sum(dim=1).to(torch.float32)
+
+
+def map_place(fit, rows, normalised=None, device="cuda:0"):
+    """The map positions of rows outside the fitted table — folded-in users, new anime — by a ``map_rows`` result, no
+    refit: a placed row sits at the affinity-weighted mean of the map positions of its nearest fitted rows (the
+    neighbour count, perplexity and bandwidth code of the fit).  ``rows`` as ``assign_clusters`` takes them.  Returns
+    fp32 [n, 2] on the device, NaN for a row that is not usable."""
+    aff = fit["affinities"]
+    What, used = aff["What"], aff["rows"]
+    R = _unit_rows(rows, normalised, device)
+    if R.shape[1] != What.shape[1]:
+        raise ValueError("map_place: rows of width %d on a map of width %d" % (R.shape[1], What.shape[1]))
+    ok = torch.nonzero(usable_rows(R)).reshape(-1)
+    out = torch.full((int(R.shape[0]), 2), float("nan"), dtype=torch.float32, device=What.device)
+    if ok.numel() == 0:
+        return out
+    m = int(used.numel())
+    stacked = torch.cat([What[used], R[ok]]).contiguous()
+    keep = torch.zeros(stacked.shape[0], dtype=torch.uint8, device=What.device)
+    keep[:m] = 1                                                  # neighbours among the fitted rows only
+    q = torch.arange(m, m + int(ok.numel()), device=What.device, dtype=torch.int32)
+    nbr, cos = _map_neighbours(stacked, q, aff["neighbours"], keep)
+    out[ok] = _map_place_positions(fit["Y"][used], nbr, cos, aff["perplexity"])
+    return out
+
+
 FOLD_STEPS = 100        # Adam iterations of a fold-in (DESIGN.md §4.7)
 FOLD_LR = 0.01          # and their learning rate
 

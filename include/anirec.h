@@ -966,6 +966,66 @@ int anirec_kmeans_fit(const float *What, int32_t dim, int32_t n_rows, float *C_i
                       int32_t *out_assign, float *out_sim, int32_t *out_count, int32_t *out_info,
                       void *ws, size_t ws_bytes, void *stream);
 
+/* MAPPED TABLES — exact t-SNE: a two-dimensional map of an embedding table from its neighbour graph.  All pairs per
+ * iteration, exact and order-free: the result is a function of (Y0, the CSR, the parameters) alone, it does not depend on
+ * lanes, waves, j_splits or the order atomics land in, and a NumPy restatement reproduces every bit of Y, V and G after
+ * any number of iterations.
+ * Y [n][2] fp32 = the coordinates.  The affinities: a symmetric sparse matrix in CSR, offsets int64 [n + 1], idx int32,
+ * val fp32 = P'_ij = p(j|i) + p(i|j) in [0, 2]; the attraction uses P' / (2 n) (the values stay in P' units: p itself,
+ * about 1 / (n k), would drown in any fixed-point scale).  V, G [n][2] fp64 = velocity and gains.
+ *   out row      a row with a coordinate that is not finite or above 2^60 in magnitude.  It takes part in no pair, as i
+ *                or as j, stored or not: all its sums are 0 and it adds nothing to another row's sums or to Z.  Bit 0
+ *                of out_info is raised.
+ *   pair chain   for i != j, both in (excluded by index, not by distance: duplicate points give q = 1, count in Z and
+ *                exert no force).  fp32, every operation rounded on its own, nothing contracted into an fma:
+ *                dx = xi - xj, dy = yi - yj, d2 = dx*dx + dy*dy, q = 1 / (1 + d2) (IEEE divide), w = q*q.
+ *   integer terms  S = 2^30; I(p) = rint(p * S): the product is exact, the rounding to the nearest even integer.
+ *                Z     += I(q)           over every ordered pair (i, j)
+ *                Rx_i  += I(w*dx),  Ry_i += I(w*dy)
+ *                for a stored pair with a = val*q:  Ax_i += I(a*dx),  Ay_i += I(a*dy)
+ *   bounds       q <= 1; |w*dx| <= 3 sqrt(3) / 16 < 0.33; |a*dx| <= 2 * 1/2 = 1 (a few fp32 roundings above it at
+ *                most): every term fits an int32, a row sum stays inside int64 for any n < 2^31.  With coordinates up
+ *                to 2^60, d2 <= 2^121 is finite and no term is a NaN: no input reaches a conversion that is not defined.
+ *   Z            does NOT fit int64 (n^2 terms of up to 2^30): it is the exact integer sum in two words, out_z =
+ *                {low, high} uint64, Z = high * 2^64 + low.  Z = 0 is possible (every point farther than 2^15.5 from
+ *                every other); the repulsive term is then 0.
+ *   stored pairs  an entry with idx outside 0 .. n-1 or idx == i, and every entry of a row whose offsets are not
+ *                0 <= offsets[i] <= offsets[i+1] <= nnz, contributes 0 and raises bit 2; an entry whose val is not in
+ *                [0, 2] (a NaN included) contributes 0 and raises bit 1.  Nothing is read through a bad value.
+ *   update       iteration t = 0 .. iters-1, every row and coordinate on its own, fp64, each operation correctly rounded
+ *                and none contracted.  e = exaggeration and momentum m = 0.5 while t < exag_iters, then e = 1, m = 0.8.
+ *                Ad, Rd = (double) of the int64 sums; Zd = (double)high * 2^64 + (double)low (two roundings to nearest
+ *                even, one rounded add)
+ *                att  = (e * Ad) / (2^31 * n)              rep = Zd > 0 ? Rd / Zd : 0
+ *                grad = 4 * (att - rep)
+ *                g    = sgn(grad) != sgn(v) ? g + 0.2 : g * 0.8, then max(g, 0.01)   (sgn in {-1, 0, 1})
+ *                v    = m * v - (lr * g) * grad
+ *                y    = (float)((double)y + v)
+ *                from v = 0, g = 1.  All rows move at once: every sum of iteration t is taken at the coordinates
+ *                iteration t - 1 left.  No recentring.
+ * anirec_tsne_forces: the integer sums at the given Y: out_rx, out_ry, out_ax, out_ay int64 [n], out_z uint64 [2],
+ * out_info int32 [1]; no workspace.  anirec_tsne_fit: Y_inout moves by `iters` iterations; out_V, out_G [n][2] fp64 and
+ * out_info are written.  One init kernel, then iters x (forces, attract + update), plain launches enqueued at once on
+ * `stream`: no host read-back, no cooperative grid, no second stream; integer vector atomics only.  The all-pairs kernel
+ * stages anirec_tsne_tile() j points in LDS at a time and splits the j range over j_splits workgroups a block of rows
+ * (0 = the library's choice, at most 1024); no bit depends on it.  ws: anirec_tsne_workspace_bytes(n_rows, iters) bytes
+ * (0 for a bad argument), 8-byte aligned; the call zeroes it, and the result does not depend on what it held.
+ * n_rows < 1 or above ANIREC_TSNE_MAX_ROWS, iters < 1 or above ANIREC_TSNE_MAX_ITER, exag_iters < 0, nnz < 0, j_splits
+ * outside 0 .. 1024, exaggeration not in (0, 1e6] or lr not in (0, 1e9] (a NaN included), a NULL pointer (idx and val
+ * may be NULL with nnz == 0), ws_bytes too small or ws misaligned: ANIREC_EINVAL before anything is enqueued or written.
+ * offsets is device memory: that it rises from 0 to nnz is the caller's to check; a row that breaks it is handled as
+ * above. */
+#define ANIREC_TSNE_MAX_ROWS 1048576
+#define ANIREC_TSNE_MAX_ITER 4096
+size_t anirec_tsne_tile(void);
+size_t anirec_tsne_workspace_bytes(int32_t n_rows, int32_t iters);
+int anirec_tsne_forces(const float *Y, int32_t n_rows, const int64_t *offsets, const int32_t *idx, const float *val,
+                       int64_t nnz, int32_t j_splits, int64_t *out_rx, int64_t *out_ry, int64_t *out_ax, int64_t *out_ay,
+                       uint64_t *out_z, int32_t *out_info, void *stream);
+int anirec_tsne_fit(float *Y_inout, int32_t n_rows, const int64_t *offsets, const int32_t *idx, const float *val,
+                    int64_t nnz, int32_t iters, int32_t exag_iters, double exaggeration, double lr, int32_t j_splits,
+                    double *out_V, double *out_G, int32_t *out_info, void *ws, size_t ws_bytes, void *stream);
+
 /* ITEM-kNN FROM CO-OCCURRENCE: "people who liked this also liked ...", and the baseline a neural model is judged by.
  * No model takes part.  item_bits is [n_items][ceil(n_users/32)] uint32: bit (u & 31) of word u >> 5 of row i is set
  * when user u liked item i — exactly what anirec_seen_bits writes when it is called with the two index columns swapped
