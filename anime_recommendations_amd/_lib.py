@@ -38,6 +38,8 @@ TSNE_TILE = 1024            # anirec_tsne_tile(): the j points of one LDS tile o
 TSNE_MAX_SPLITS = 1024      # the largest j_splits
 ALS_MAX_CG = 16             # ANIREC_ALS_MAX_CG: the most conjugate-gradient steps of anirec_als_half_sweep
 ALS_GRAM_CHUNK = 1024       # ANIREC_ALS_GRAM_CHUNK: rows of one chunk of anirec_als_gram
+BPR_MAX_TRIES = 16          # ANIREC_BPR_MAX_TRIES: the most negative candidates of a slot of anirec_bpr_steps
+BPR_ERR_INDEX, BPR_ERR_DIVERGED = 1, 2   # ANIREC_BPR_ERR_*: the bits of anirec_bpr_steps' error flag
 CALIBRATE_MAX_CAND = 1024   # anirec_calibrate_max_cand(): the longest list anirec_calibrate_rerank / _list_calibration take
 CALIBRATE_MAX_CAT = 128     # the most categories of a profile (anirec_fave_profile's limit)
 CALIBRATE_PROFILE_MAX = 1 << 24   # the largest profile entry: the integer numerator then stays below 2**53
@@ -317,6 +319,11 @@ PROTOTYPES = {
     "anirec_als_half_sweep": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _f32, _i32, _vp, _vp,
                                         _vp]),
     "anirec_dot_scores": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _vp, _i64, _vp]),
+    # BPR matrix factorisation: SGD steps over hashed triples with integer gradient sums, and the sampler on its own
+    "anirec_bpr_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "anirec_bpr_sample": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i64, _i32, _i32, C.c_uint32, _i32, _i32, _vp, _vp, _vp]),
+    "anirec_bpr_steps": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, C.c_uint32, _i32, _i32,
+                                   _f32, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     # EASE: the fp64 inverse of a symmetric positive definite matrix, the weights from it, score rows from histories
     "anirec_spd_inverse_block": (_i32, []),
     "anirec_spd_inverse_workspace_bytes": (_sz, [_i32]),

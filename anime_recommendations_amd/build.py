@@ -20,7 +20,7 @@ SOURCES = ["anirec_train_head_metrics.hip", "anirec_train_head.hip", "anirec_tra
            "anirec_ingest.hip", "anirec_recs.hip", "anirec_foldin.hip", "anirec_mmr.hip", "anirec_listeval.hip",
            "anirec_explain.hip", "anirec_kmeans.hip", "anirec_cooc.hip", "anirec_calibrate.hip", "anirec_boot.hip",
            "anirec_als.hip", "anirec_cover.hip", "anirec_fuse.hip", "anirec_content.hip",
-           "anirec_ease.hip", "anirec_wcooc.hip", "anirec_tsne.hip"]
+           "anirec_ease.hip", "anirec_wcooc.hip", "anirec_tsne.hip", "anirec_bpr.hip"]
 
 
 def hipcc_path() -> str:

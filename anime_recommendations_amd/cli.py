@@ -38,7 +38,7 @@ def percentile(v):
 # literature's defaults, not tuned on this data.
 HYBRID_FLAGS = {
     "hybrid_systems": (str, "model,itemknn,als", "the systems whose score rows are fused, separated by a comma: model, "
-                                                 "popularity, itemknn, als"),
+                                                 "popularity, itemknn, als, content, ease, rp3, bpr"),
     "hybrid_weights": (str, "none", "none (all 1), or a list with one weight >= 0 per system, e.g. \"[1, 1, 0.5]\""),
     "hybrid_method": (str, "rrf", "rrf (reciprocal rank fusion) or minmax (the sum of min-max normalised scores)"),
     "hybrid_rrf_c": (int, 60, "the constant of reciprocal rank fusion: a term is weight / (rrf_c + rank), rank from 1"),

@@ -943,7 +943,7 @@ def diverse_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, us
 # ----------------------------------------------------------------------------------------
 def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs,
                       types=None, genres=None, systems=("model", "itemknn", "als"), weights=None, method="rrf", rrf_c=60,
-                      itemknn=None, als=None, ease=None, rp3=None):
+                      itemknn=None, als=None, ease=None, rp3=None, bpr=None):
     """model_recs_frame with the list taken from several systems at once (``recs.hybrid_topk``): the same candidates
     (unwatched, indexed, Type / Genre filters), each member of ``systems`` (names of ``recs.HYBRID_SYSTEMS``) scoring
     every anime for the user (``content``, of ``recs.CONTENT_SYSTEMS``, with CONTENT_DEFAULTS and this call's metadata), the
@@ -951,7 +951,8 @@ def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, use
     with ``rrf_c``, or minmax; ``weights`` None = all 1) and the best ``n_recs`` taken by the exact select.  The item-kNN
     and ALS members are fitted from ``df`` (ITEMKNN_DEFAULTS / ALS_DEFAULTS overridden by ``itemknn`` / ``als``), the
     ``ease`` member (of ``recs.EASE_SYSTEMS``) likewise (EASE_DEFAULTS overridden by ``ease``), the ``rp3`` member (of
-    ``recs.GRAPH_SYSTEMS``) likewise (RP3_DEFAULTS overridden by ``rp3``), the
+    ``recs.GRAPH_SYSTEMS``) likewise (RP3_DEFAULTS overridden by ``rp3``), the ``bpr`` member (of
+    ``recs.PAIRWISE_SYSTEMS``) likewise (BPR_DEFAULTS overridden by ``bpr``), the
     user's history and the liked pairs built as ``evaluate_frame`` builds them; popularity is the rating count.
     Returns (frame, stats): model_recs_frame's columns — ``Prediction`` remains the model's predicted rating of the
     listed anime — plus ``Hybrid_score`` (the fused value) and one ``Rank_<system>`` per member: the 1-based place of the
@@ -961,7 +962,8 @@ def hybrid_recs_frame(U, A, head, user_ids, anime_ids, df, anime_df, syn_df, use
     from . import ops, recs
     members, ws, method, rrf_c = recs.check_hybrid(systems, weights, method, rrf_c)
     content = {"meta": metadata_by_index(anime_ids, anime_df, syn_df)} if "content" in members else None
-    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease, "rp3": rp3}, members)
+    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease, "rp3": rp3, "bpr": bpr},
+                            members)
     row, meta, bits, tU, tA, k = _candidates(U, A, user_ids, anime_ids, df, anime_df, syn_df, user_id, n_recs, types, genres)
     cols = None
     if set(members) - {"model"}:
@@ -1249,6 +1251,12 @@ EASE_DEFAULTS = {"reg": 500.0, "min_rating": 0.0, "neighbours": 0}
 # neighbours are common values from the literature; none is tuned on this data.  neighbours = 0 keeps the dense matrix.
 GRAPH_BASELINES = ("rp3",)
 RP3_DEFAULTS = {"alpha": 1.0, "beta": 0.3, "neighbours": 100, "min_rating": 0.0}
+# learned models with a PAIRWISE objective (BPR matrix factorisation, Rendle et al. 2009), beside the
+# constants above (which stay as they are) and reported last.  BPR_DEFAULTS are the literature's and the ``implicit``
+# library's common values with the width moved to the nearest supported one; none is tuned on this data.
+PAIRWISE_BASELINES = ("bpr",)
+BPR_DEFAULTS = {"factors": 64, "epochs": 30, "batch": 131072, "lr": 0.05, "reg": 0.01, "tries": 8, "bias": True,
+                "min_rating": 0.0, "seed": 0}
 
 
 def _member_params(defaults, given, what):
@@ -1342,9 +1350,29 @@ def _system_lookup():
             device=device)))
 
 
+def _system_layers():
+    """``_system_lookup()`` plus the systems of ``recs.PAIRWISE_SYSTEMS``: what every lookup by name goes through."""
+    from . import ops, recs
+
+    def bpr_fit(user, anime, rating, n_users, n_anime, par, device):
+        u, a, r = (recs._host(c) for c in (user, anime, rating))
+        liked = r.astype(np.float32) >= np.float32(par["min_rating"])
+        return recs.bpr_fit(u[liked], a[liked], n_users, n_anime, par["factors"], int(par["epochs"]), par["batch"],
+                            par["lr"], par["reg"], par["tries"], par["bias"], seed=int(par["seed"]), device=device)
+
+    def bpr_check(par):
+        ops.check_bpr(par["factors"], par["batch"], par["tries"], par["lr"], par["reg"], par["bias"])
+        if int(par["epochs"]) < 0:
+            raise ValueError("bpr: epochs = %d must be >= 0" % int(par["epochs"]))
+
+    return dict(_system_lookup(), bpr=dict(
+        defaults=BPR_DEFAULTS, check=bpr_check, fit=bpr_fit,
+        source=lambda fit, users, cols, par: recs.bpr_rows_source(fit, users)))
+
+
 def _system_params(given, used):
     """{system: its defaults overridden by ``given[system]``}, the pre-GPU check made for each system of ``used``"""
-    table = _system_lookup()
+    table = _system_layers()
     params = {name: _member_params(s["defaults"], given.get(name), name) for name, s in table.items() if "defaults" in s}
     for name in used:
         table[name].get("check", lambda par: None)(params.get(name))
@@ -1354,18 +1382,18 @@ def _system_params(given, used):
 def _system_source(name, tables, cols, params, users, device):
     """The row source of system ``name`` for ``users``, the system fitted from the training columns ``cols`` = (user,
     anime, rating, n_users, n_anime) on ``device``; ``tables`` = the model's (U, A, head) on the device."""
-    s, par = _system_lookup()[name], params.get(name)
+    s, par = _system_layers()[name], params.get(name)
     return s["source"](s["fit"](*cols, par, device) if "fit" in s else tables, users, cols, par)
 
 
 def baseline_names(baseline):
     """``evaluate_frame``'s ``baseline`` as a tuple of distinct names in the order of BASELINES, FITTED_BASELINES,
-    FUSED_BASELINES, TUNED_BASELINES, CONTENT_BASELINES, LINEAR_BASELINES, then GRAPH_BASELINES: None -> (), a name or a
-    sequence of names; ValueError for anything else."""
+    FUSED_BASELINES, TUNED_BASELINES, CONTENT_BASELINES, LINEAR_BASELINES, GRAPH_BASELINES, then PAIRWISE_BASELINES: None
+    -> (), a name or a sequence of names; ValueError for anything else."""
     if baseline is None:
         return ()
     known = (BASELINES + FITTED_BASELINES + FUSED_BASELINES + TUNED_BASELINES + CONTENT_BASELINES + LINEAR_BASELINES +
-             GRAPH_BASELINES)
+             GRAPH_BASELINES + PAIRWISE_BASELINES)
     names = [baseline] if isinstance(baseline, str) else list(baseline)
     for b in names:
         if b not in known:
@@ -1397,7 +1425,7 @@ def _ci_columns(columns, boot, system, others, key):
 
 def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, baseline=None, itemknn=None,
                    ci_replicates=0, ci_level=0.95, ci_seed=0, compare_model=None, als=None, hybrid=None,
-                   hybrid_tune=None, content=None, ease=None, rp3=None):
+                   hybrid_tune=None, content=None, ease=None, rp3=None, bpr=None):
     """How well a model ranks held-out ratings: each held-out (user, anime) rated at or above ``min_rating`` is ranked
     among the anime that user has no TRAINING rating for (the candidates model_recs would offer before the held-out
     rows were known), by predicted rating.  Returns (frame with one row per k: k, hit_rate, ndcg; summary dict:
@@ -1452,8 +1480,14 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
     RP3_DEFAULTS (alpha: 1, beta: 0.3, neighbours: 100 — common values from the literature, not tuned on this data;
     neighbours = 0 keeps the dense matrix; min_rating); an alpha or beta that is negative or not finite is a ValueError
     before any GPU use.
-    A sequence of names gives each, in the order popularity, itemknn, als, hybrid, hybrid_tuned, content, ease, rp3.  None:
-    none.
+    ``baseline="bpr"``: the same targets under the same bits ranked by a BPR matrix factorisation (Rendle et al. 2009;
+    DESIGN.md 4.27), the learned model with a PAIRWISE objective, fitted on the TRAINING slice alone (``recs.bpr_fit``,
+    ``recs.bpr_rank``'s ranks) on the training pairs rated at or above its threshold; the same columns and keys under the
+    name bpr, and ``bpr`` is a member the hybrids take too.  ``bpr``: a dict overriding BPR_DEFAULTS (factors, epochs,
+    batch, lr, reg, tries, bias, min_rating, seed) — the literature's and the ``implicit`` library's common values, not
+    tuned on this data; a ``factors`` outside the supported widths is a ValueError before any GPU use.
+    A sequence of names gives each, in the order popularity, itemknn, als, hybrid, hybrid_tuned, content, ease, rp3, bpr.
+    None: none.
     ``compare_model``: a second model dict over the same id tables, ranked by a second ``ops.predict_rank`` on the same
     targets and bits and reported as the system ``compare`` (the baselines' columns and keys under that name).
     ``ci_replicates`` > 0: a Poisson bootstrap over the held-out USERS (``recs.bootstrap_metrics``), seeded
@@ -1478,9 +1512,10 @@ def evaluate_frame(model, table, test_size, ks=(1, 5, 10, 50), min_rating=0.0, b
         tune_grid = recs.hybrid_weight_grid(len(members), tune_par["steps"])
         recs.hybrid_fold_deal(0, tune_par["folds"], tune_par["seed"])        # (the check of folds; dealt below)
         tune_pick, tune_best = [0] * int(tune_par["folds"]), 0
-    fitted = [s for s in recs.HYBRID_SYSTEMS + recs.CONTENT_SYSTEMS + recs.EASE_SYSTEMS + recs.GRAPH_SYSTEMS
-              if s in baselines or s in members]     # each once
-    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease, "rp3": rp3}, fitted)
+    fitted = [s for s in (recs.HYBRID_SYSTEMS + recs.CONTENT_SYSTEMS + recs.EASE_SYSTEMS + recs.GRAPH_SYSTEMS +
+                          recs.PAIRWISE_SYSTEMS) if s in baselines or s in members]     # each once
+    params = _system_params({"itemknn": itemknn, "als": als, "content": content, "ease": ease, "rp3": rp3, "bpr": bpr},
+                            fitted)
     U, A = _tables_of(model, table)
     others = baselines + (("compare",) if compare_model is not None else ())
     if compare_model is not None:

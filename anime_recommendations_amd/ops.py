@@ -1643,6 +1643,113 @@ def dot_scores(Q, Y, out=None):
     return out
 
 
+def check_bpr(factors, batch, tries, lr, reg, bias=True):
+    """The argument checks of the BPR ops (no device needed): ValueError listing the supported widths for another
+    ``factors``, for ``batch`` < 1, ``tries`` outside 1 .. BPR_MAX_TRIES, an ``lr`` or ``reg`` that is negative or not
+    finite, a ``bias`` that is not a truth value.  Returns (factors, batch, tries, lr, reg, bias as 0 / 1)."""
+    try:
+        factors = _lib.check_width(factors)
+    except ValueError:
+        raise ValueError("bpr: factors = %r is not supported: the kernels take the widths %s"
+                         % (factors, ", ".join(str(w) for w in _lib.WIDTHS))) from None
+    batch, tries, lr, reg = int(batch), int(tries), float(lr), float(reg)
+    if not 1 <= batch < 2 ** 31:
+        raise ValueError("bpr: batch = %d must be in 1 .. 2^31 - 1" % batch)
+    if not 1 <= tries <= _lib.BPR_MAX_TRIES:
+        raise ValueError("bpr: tries = %d must be in 1 .. %d (BPR_MAX_TRIES)" % (tries, _lib.BPR_MAX_TRIES))
+    if not (0.0 <= lr < float("inf")) or not (0.0 <= reg < float("inf")):
+        raise ValueError("bpr: the learning rate and the regularisation must be finite and >= 0 (got %r, %r)" % (lr, reg))
+    if bias not in (0, 1, False, True):
+        raise ValueError("bpr: bias = %r must be True or False" % (bias,))
+    return factors, batch, tries, lr, reg, int(bool(bias))
+
+
+def _bpr_steps_range(step0, n_steps, what):
+    step0, n_steps = int(step0), int(n_steps)
+    if step0 < 0 or n_steps < 0 or step0 + n_steps > 2 ** 31 - 1:
+        raise ValueError("%s: step0 and n_steps must be >= 0 and step0 + n_steps below 2^31" % what)
+    return step0, n_steps
+
+
+def _bpr_csr(offsets, idx, pair_user, n_items, dev, what):
+    """(offsets int64, idx int32, pair_user int32, n_users, nnz) on ``dev``, the offsets checked against the entries"""
+    off = torch.as_tensor(offsets).to(device=dev, dtype=torch.int64).contiguous()
+    ix, pu = _i32(idx, dev).reshape(-1), _i32(pair_user, dev).reshape(-1)
+    n_users, nnz = int(off.numel()) - 1, int(ix.numel())
+    if n_users < 1 or int(n_items) < 1 or not 1 <= nnz < 2 ** 31 or pu.numel() != nnz:
+        raise ValueError("%s: needs users, items, 1 .. 2^31 - 1 liked pairs and one pair_user entry per pair" % what)
+    _check_csr(off, n_users, nnz, what, "pairs")
+    return off, ix, pu, n_users, nnz
+
+
+def bpr_workspace_bytes(n_users, n_items, width, batch):
+    """anirec_bpr_workspace_bytes: the bytes ``bpr_steps`` needs (the int64 accumulators and the counts of both tables,
+    and a step's triples).  Needs no GPU; ValueError for a bad argument."""
+    n = int(_lib.load().anirec_bpr_workspace_bytes(int(n_users), int(n_items), int(width), int(batch)))
+    if n == 0:
+        raise ValueError("bpr_workspace_bytes: n_users, n_items and batch must be >= 1 and the width one of %s"
+                         % ", ".join(str(w) for w in _lib.WIDTHS))
+    return n
+
+
+def bpr_sample(offsets, idx, pair_user, n_items, batch, tries=8, seed=0, step0=0, n_steps=1, check=True, device="cuda:0"):
+    """The triples ``bpr_steps`` draws (anirec_bpr_sample): int32 [n_steps, batch, 3] on the device, (u, i,
+    j) of every slot of the steps ``step0 .. step0 + n_steps - 1``: a liked pair picked by a counter-based hash of (seed,
+    step, slot) and the first of ``tries`` hashed items that the user has not liked; j = -1 when every candidate is liked
+    (the slot is dropped).  The liked pairs: a CSR by user (``offsets`` int64 [n_users + 1], ``idx`` int32 [nnz], items
+    ascending inside a row without repeats) and ``pair_user`` int32 [nnz].  Raises ValueError for an index out of range;
+    with ``check=False`` returns (triples, device flag)."""
+    _, batch, tries, _, _, _ = check_bpr(_lib.WIDTHS[0], batch, tries, 0.0, 0.0)
+    step0, n_steps = _bpr_steps_range(step0, n_steps, "bpr_sample")
+    _need_gpu()
+    dev = torch.device(device)
+    off, ix, pu, n_users, nnz = _bpr_csr(offsets, idx, pair_user, n_items, dev, "bpr_sample")
+    out, = _outputs(dev, (torch.int32, n_steps, batch, 3))
+    err = _err_flag(dev)
+    _call("anirec_bpr_sample", off, ix, pu, n_users, int(n_items), nnz, batch, tries, int(seed) & 0xFFFFFFFF, step0, n_steps,
+          out, err)
+    return _finish(out, err, check, "bpr_sample: index out of range")
+
+
+def bpr_steps(X, Y, offsets, idx, pair_user, batch, tries=8, seed=0, step0=0, n_steps=1, lr=0.05, reg=0.01, bias=True,
+              workspace=None, check=True):
+    """Mini-batch SGD steps of BPR matrix factorisation IN PLACE on the factor tables (anirec_bpr_steps):
+    ``X`` fp32 [n_users, width] and ``Y`` fp32 [n_items, width] on the device, both CONTIGUOUS (they are written through
+    their own storage: a non-contiguous table is an AssertionError, as in the other ops that take tables).  Step t takes ``batch`` triples
+    (``bpr_sample``'s), sums the gradient of ln sigmoid(x_u . (y_i - y_j)) against the tables as they stand before the
+    step as int64 of 2^30-scaled fp32 terms, and moves every touched row by ``lr`` times (its sum minus ``reg`` times its
+    slot count times the row).  The bits are a function of the arguments alone.  With ``bias`` the last column of the user
+    rows is never written.  All steps are enqueued at once.  Returns counts int64 [n_steps, 3] on the device (slots kept,
+    slots dropped, kept slots already in the right order).  Raises ValueError for an index out of range or a diverged
+    step (a gradient term not finite or above 2^20); with ``check=False`` returns (counts, device flag: the
+    ``_lib.BPR_ERR_*`` bits) and nothing synchronises beyond the offsets' own check."""
+    dim, batch, tries, lr, reg, bias = check_bpr(X.shape[1], batch, tries, lr, reg, bias)
+    step0, n_steps = _bpr_steps_range(step0, n_steps, "bpr_steps")
+    _need_gpu()
+    assert _width(X, Y) == dim and X.is_contiguous() and Y.is_contiguous(), "contiguous tables: they are updated in place"
+    dev = X.device
+    off, ix, pu, n_users, nnz = _bpr_csr(offsets, idx, pair_user, Y.shape[0], dev, "bpr_steps")
+    if n_users != int(X.shape[0]):
+        raise ValueError("bpr_steps: offsets holds %d rows, X %d" % (n_users, X.shape[0]))
+    counts, = _outputs(dev, (torch.int64, n_steps, 3))
+    err = _err_flag(dev)
+    ws = _workspace(workspace, dev, "anirec_bpr_workspace_bytes", n_users, int(Y.shape[0]), dim, batch)
+    _call("anirec_bpr_steps", X, Y, n_users, int(Y.shape[0]), dim, off, ix, pu, nnz, batch, tries, int(seed) & 0xFFFFFFFF,
+          step0, n_steps, lr, reg, bias, counts, err, ws, ws.numel())
+    if not check:
+        return counts, err
+    bpr_raise(int(err.item()), "bpr_steps")
+    return counts
+
+
+def bpr_raise(flag, what):
+    """ValueError for the bits of a BPR error flag read from the device; nothing for 0"""
+    if flag & _lib.BPR_ERR_INDEX:
+        raise ValueError("%s: index out of range" % what)
+    if flag & _lib.BPR_ERR_DIVERGED:
+        raise ValueError("%s: the fit diverged (a gradient term was not finite or above 2^20): lower lr" % what)
+
+
 def check_ease(reg, neighbours=0):
     """The argument checks of the EASE fit (no device needed): ValueError for a ``reg`` that is not finite or not > 0,
     a negative ``neighbours``.  Returns (reg, neighbours)."""

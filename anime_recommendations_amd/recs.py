@@ -1301,6 +1301,89 @@ def als_rank(fit, users, watched_bits, target_row, target_anime, batch=ALS_BATCH
 
 
 # ----------------------------------------------------------------------------------------
+# BPR matrix factorisation, the pairwise learned baseline (Rendle et al. 2009): no model takes part
+# ----------------------------------------------------------------------------------------
+PAIRWISE_SYSTEMS = ("bpr",)     # row-score systems beside HYBRID_SYSTEMS, CONTENT_SYSTEMS, ... (which stay as they are)
+BPR_BATCH = ALS_BATCH           # users per anirec_dot_scores call: a score row each
+
+
+def bpr_fit(user_idx, item_idx, n_users, n_items, factors=64, epochs=30, batch=131072, lr=0.05, reg=0.01, tries=8,
+            bias=True, seed=0, device="cuda:0"):
+    """BPR matrix factorisation (Rendle et al. 2009) of the liked pairs (user_idx[t], item_idx[t]) by mini-batch SGD on
+    sampled (user, liked item, unliked item) triples (``ops.bpr_steps``).  A pair that repeats counts once.
+    The start is ``default_rng(seed).standard_normal * 0.01`` in fp32, X then Y, as ``als_fit`` draws it; with ``bias`` the
+    last column of X is then 1 and never written and that of Y starts at 0: an item bias, the scores still plain dot
+    products.  An epoch is ``ceil(pairs / batch)`` steps of ``batch`` triples, drawn by a hash of (``seed``, step, slot);
+    the negative is the first of ``tries`` hashed items the user has not liked.  The defaults are the literature's and the
+    ``implicit`` library's common values, not tuned on this data.  The result is a function of the arguments alone, bit
+    for bit.
+    Returns {"X" fp32 [n_users, factors], "Y" fp32 [n_items, factors]} on the device, "counts" (per epoch: triples kept,
+    slots dropped, kept triples already in the right order before their step), "n_pairs" and the parameters ("n_users",
+    "n_items", "factors", "epochs", "batch", "lr", "reg", "tries", "bias", "seed").  Raises ValueError, before any GPU use,
+    for ``factors`` outside the supported widths, a ``batch`` < 1, ``tries`` outside 1 .. 16, a negative ``epochs``, ``lr``
+    or ``reg``, an index out of range, no pair at all or ``ceil(len(user_idx) / batch) * epochs`` of 2^31 or more; and,
+    after the fit, for one that diverged (lower ``lr``)."""
+    from . import ops
+    factors, batch, tries, lr, reg, bias = ops.check_bpr(factors, batch, tries, lr, reg, bias)
+    n_users, n_items, epochs = int(n_users), int(n_items), int(epochs)
+    if n_users < 1 or n_items < 1 or epochs < 0:
+        raise ValueError("bpr_fit: n_users and n_items must be >= 1 and epochs >= 0")
+    u, i = _host(user_idx).reshape(-1), _host(item_idx).reshape(-1)
+    if len(u) != len(i) or len(u) == 0:
+        raise ValueError("bpr_fit: user_idx and item_idx must have one entry per pair, and one pair at least")
+    if u.min() < 0 or u.max() >= n_users or i.min() < 0 or i.max() >= n_items:
+        raise ValueError("bpr_fit: index out of range")
+    if -(-len(u) // batch) * epochs >= 2 ** 31:       # on the pairs as given (no fewer than the distinct ones): no GPU yet
+        raise ValueError("bpr_fit: ceil(pairs / batch) * epochs must stay below 2^31 steps")
+    dev = torch.device(device)
+    key = torch.unique(_on(u, dev, torch.int64) * n_items + _on(i, dev, torch.int64))       # sorted: rows, items ascending
+    pair_user, idx = (key // n_items).to(torch.int32), (key % n_items).to(torch.int32)
+    off = torch.zeros(n_users + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(torch.bincount(pair_user.long(), minlength=n_users), 0)
+    n_pairs = int(key.numel())
+    rng = np.random.default_rng(seed)
+    X0 = (rng.standard_normal((n_users, factors)) * 0.01).astype(np.float32)
+    Y0 = (rng.standard_normal((n_items, factors)) * 0.01).astype(np.float32)
+    if bias:
+        X0[:, -1], Y0[:, -1] = 1.0, 0.0
+    X, Y = torch.as_tensor(X0, device=dev), torch.as_tensor(Y0, device=dev)
+    per = -(-n_pairs // batch)
+    ws = torch.empty(ops.bpr_workspace_bytes(n_users, n_items, factors, batch), dtype=torch.uint8, device=dev)
+    counts, flags = [], []
+    for e in range(epochs):
+        c, f = ops.bpr_steps(X, Y, off, idx, pair_user, batch, tries, seed, e * per, per, lr, reg, bias, workspace=ws,
+                             check=False)
+        counts.append(c.sum(0))
+        flags.append(f)
+    if flags:
+        flag = 0
+        for f in torch.cat(flags).tolist():
+            flag |= int(f)
+        ops.bpr_raise(flag, "bpr_fit")
+    return {"X": X, "Y": Y, "counts": [[int(v) for v in row] for row in (torch.stack(counts).tolist() if counts else [])],
+            "n_pairs": n_pairs, "n_users": n_users, "n_items": n_items, "factors": factors, "epochs": epochs,
+            "batch": batch, "lr": lr, "reg": reg, "tries": tries, "bias": bool(bias), "seed": int(seed)}
+
+
+def bpr_topk(fit, users, k, watched_bits=None, batch=BPR_BATCH):
+    """BPR recommendation lists: ``als_topk`` on a ``bpr_fit``'s tables (``ops.dot_scores(X[users], Y)``, the exact select,
+    ``batch`` users at a time).  Returns (idx int32 [n_listed, k], score fp32 [n_listed, k])."""
+    source, n_l = _als_source(fit, users)
+    return rows_topk_batched(source, n_l, k, watched_bits, None, batch, "bpr_topk", fit["X"].device)
+
+
+def bpr_rank(fit, users, watched_bits, target_row, target_anime, batch=BPR_BATCH):
+    """The ranks ``als_rank`` gives, for the scores of a ``bpr_fit``: rank int32 [n_t] on the device."""
+    source, n_l = _als_source(fit, users)
+    return rows_rank_batched(source, n_l, watched_bits, target_row, target_anime, batch, "bpr_rank", fit["X"].device)
+
+
+def bpr_rows_source(fit, users):
+    """A row source of the BPR scores of ``users`` (rows of ``fit["X"]``), through ``ops.dot_scores``."""
+    return _als_source(fit, users)[0]
+
+
+# ----------------------------------------------------------------------------------------
 # EASE, the closed-form linear item-item autoencoder (Steck 2019; DESIGN.md §4.24): no model takes part
 # ----------------------------------------------------------------------------------------
 EASE_SYSTEMS = ("ease",)    # row-score systems beside HYBRID_SYSTEMS and CONTENT_SYSTEMS (which stay as they are)
@@ -1599,12 +1682,13 @@ HYBRID_BATCH = 4096     # users per anirec_fuse_rows call: a score row per syste
 
 def check_hybrid(systems, weights=None, method="rrf", rrf_c=60):
     """(systems as a tuple of names, weights as floats, the method's name, rrf_c), or a ValueError before any GPU use:
-    a name that is not one of HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS + GRAPH_SYSTEMS, a name twice, no name at all, and what ``ops.check_fuse`` refuses (a
+    a name that is not one of HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS + GRAPH_SYSTEMS + PAIRWISE_SYSTEMS, a name
+    twice, no name at all, and what ``ops.check_fuse`` refuses (a
     weights list of another length among it)."""
     from . import ops
     names = [systems] if isinstance(systems, str) else list(systems)
     names = [str(s).strip().lower() for s in names]
-    known = HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS + GRAPH_SYSTEMS
+    known = HYBRID_SYSTEMS + CONTENT_SYSTEMS + EASE_SYSTEMS + GRAPH_SYSTEMS + PAIRWISE_SYSTEMS
     for s in names:
         if s not in known:
             raise ValueError("hybrid system %r is not one of %s" % (s, ", ".join(known)))

@@ -19,7 +19,10 @@ EASE, the closed-form linear item-item model fitted on the training slice (``--e
 tuned on this data; also a member ``--hybrid_systems`` takes), ``--baseline rp3`` those of RP3beta, the three-step random
 walk with a popularity penalty fitted on the training slice (``--rp3_alpha``, ``--rp3_beta``, ``--rp3_neighbours``,
 ``--rp3_min_rating``: command line only; 1, 0.3 and 100 are common values from the literature, not tuned on this data; also
-a member ``--hybrid_systems`` takes);
+a member ``--hybrid_systems`` takes), ``--baseline bpr`` those of a BPR matrix factorisation, the learned model with a
+pairwise objective, fitted on the training slice (``--bpr_factors``, ``--bpr_epochs``, ``--bpr_batch``, ``--bpr_lr``,
+``--bpr_reg``, ``--bpr_tries``, ``--bpr_bias``, ``--bpr_min_rating``, ``--bpr_seed``: command line only; the literature's and
+the ``implicit`` library's common values, not tuned on this data; also a member ``--hybrid_systems`` takes);
 ``--lists_diversity "[0, 0.3]"`` adds ``lists_csv``: what each diverse_recs diversity costs in hits and buys in
 spread, over every held-out user's top ``lists_k`` list; ``--ci_replicates 1000`` adds a bootstrap interval over the
 held-out users to every figure and a paired difference and p-value against every other system, ``--compare_model`` a
@@ -115,6 +118,22 @@ EASE_FLAGS = dict(cli.EASE_FLAGS, ease_min_rating=(float, C.EASE_DEFAULTS["min_r
 RP3_FLAGS = dict(cli.RP3_FLAGS, rp3_min_rating=(float, C.RP3_DEFAULTS["min_rating"],
                                                 "the scaled rating (0..1) from which a training rating counts as liked"))
 
+# optional and command-line only, like the item-kNN flags: BPR matrix factorisation (--baseline bpr, or a member of
+# --hybrid_systems; components.BPR_DEFAULTS: the literature's and the ``implicit`` library's common values with the width
+# moved to the nearest supported one, not tuned on this data)
+BPR_FLAGS = {
+    "bpr_factors": (int, C.BPR_DEFAULTS["factors"], "the width of the factor tables: 32, 64, 128 or 256"),
+    "bpr_epochs": (int, C.BPR_DEFAULTS["epochs"], "epochs, each ceil(liked pairs / batch) steps"),
+    "bpr_batch": (int, C.BPR_DEFAULTS["batch"], "sampled triples per step"),
+    "bpr_lr": (float, C.BPR_DEFAULTS["lr"], "the learning rate"),
+    "bpr_reg": (float, C.BPR_DEFAULTS["reg"], "the L2 weight on both factor tables"),
+    "bpr_tries": (int, C.BPR_DEFAULTS["tries"], "negative candidates drawn per triple before it is dropped (1 .. 16)"),
+    "bpr_bias": (C.str2bool, C.BPR_DEFAULTS["bias"], "whether the last factor column is an item bias"),
+    "bpr_min_rating": (float, C.BPR_DEFAULTS["min_rating"],
+                       "the scaled rating (0..1) from which a training rating counts as liked"),
+    "bpr_seed": (int, C.BPR_DEFAULTS["seed"], "the seed of the start tables and the sampler"),
+}
+
 logger = C.setup_logging("evaluate")
 
 
@@ -170,8 +189,15 @@ def rp3_args(args):
     return {f[len("rp3_"):]: getattr(args, f) for f in RP3_FLAGS if hasattr(args, f)}
 
 
+def bpr_args(args):
+    """evaluate_frame's ``bpr``: the BPR flags the parser has"""
+    return {f[len("bpr_"):]: getattr(args, f) for f in BPR_FLAGS if hasattr(args, f)}
+
+
 def go(args):
     content = None
+    if wants(args, "bpr"):                                  # the cheap failures: before any file or GPU use
+        C._system_params({"bpr": bpr_args(args)}, ["bpr"])
     if wants(args, "rp3"):                                  # the cheap failures: before any file or GPU use
         C._system_params({"rp3": rp3_args(args)}, ["rp3"])
     if wants(args, "ease"):                                 # the cheap failures: before any file or GPU use
@@ -200,7 +226,7 @@ def go(args):
                                       compare_model=compare_model, hybrid=cli.hybrid_args(args),
                                       hybrid_tune={f[len("hybrid_tune_"):]: getattr(args, f) for f in HYBRID_TUNE_FLAGS
                                                    if hasattr(args, f)}, content=content, ease=ease_args(args),
-                                      rp3=rp3_args(args), **ci)
+                                      rp3=rp3_args(args), bpr=bpr_args(args), **ci)
     frame.to_csv(args.eval_csv, index=False)
     artifacts.log_artifact(args.eval_csv, args.eval_csv, args.eval_type,
                            "Ranking metrics of the held-out ratings for model : " + str(args.model),
@@ -230,8 +256,9 @@ def make_parser():
                              "score rows of several of them and the model), hybrid_tuned (the same with cross-fitted "
                              "weights from a grid), content (by TF-IDF vectors of the anime metadata; needs "
                              "--anime_df), ease (by the closed-form linear item-item model EASE fitted on the "
-                             "training ratings), rp3 (by the RP3beta random walk over the training ratings), or "
-                             "several separated by a comma")
+                             "training ratings), rp3 (by the RP3beta random walk over the training ratings), bpr "
+                             "(by a BPR matrix factorisation fitted on the training ratings), or several separated "
+                             "by a comma")
     for flag, (kind, default, text) in OPTIONAL_FLAGS.items():
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
@@ -239,11 +266,12 @@ def make_parser():
 
 def make_cli_parser():
     """``make_parser`` (the MLproject's parameters) and the command-line-only ``--itemknn_*``, ``--als_*``, ``--ci_*``,
-    ``--compare_model``, ``--hybrid_*``, ``--hybrid_tune_*``, content (``CONTENT_FLAGS``), ``--ease_*`` and ``--rp3_*`` flags."""
+    ``--compare_model``, ``--hybrid_*``, ``--hybrid_tune_*``, content (``CONTENT_FLAGS``), ``--ease_*``, ``--rp3_*`` and
+    ``--bpr_*`` flags."""
     parser = make_parser()
     for flag, (kind, default, text) in list(ITEMKNN_FLAGS.items()) + list(ALS_FLAGS.items()) + list(CI_FLAGS.items()) + \
             list(HYBRID_FLAGS.items()) + list(HYBRID_TUNE_FLAGS.items()) + list(CONTENT_FLAGS.items()) + \
-            list(EASE_FLAGS.items()) + list(RP3_FLAGS.items()):
+            list(EASE_FLAGS.items()) + list(RP3_FLAGS.items()) + list(BPR_FLAGS.items()):
         parser.add_argument("--" + flag, type=kind, default=default, required=False, help=text)
     return parser
 

@@ -1339,6 +1339,76 @@ int anirec_dot_scores(const float *Q, int32_t n_q, const float *Y, int32_t n, in
                       void *stream);
 
 /* ------------------------------------------------------------------------- *
+ *  BPR MATRIX FACTORISATION (Rendle, Freudenthaler, Gantner and Schmidt-Thieme 2009, "BPR: Bayesian Personalized Ranking
+ *  from Implicit Feedback"): the learned baseline with a PAIRWISE objective.  No model takes part.
+ *  Mini-batch SGD ascent on sum ln sigmoid(x_u . (y_i - y_j)) - reg (|x_u|^2 + |y_i|^2 + |y_j|^2) / 2 over sampled
+ *  triples (u, liked i, unliked j).  Every quantity that crosses a slot is an integer, so the result is a function of
+ *  the inputs alone: not of the launch shape, the order of the atomics or the run.
+ *
+ * Inputs.  The distinct liked pairs as a CSR by user: offsets int64 [n_users + 1], idx int32 [nnz], the items ascending
+ * inside a row without repeats (the caller's promise; the binary search below needs it), and pair_user int32 [nnz], the
+ * row of every entry.  1 <= nnz < 2^31.  Tables X [n_users][width], Y [n_items][width], fp32, 16-byte aligned, width one
+ * of 32, 64, 128, 256, updated in place.
+ *
+ * Draws, all in uint32 arithmetic mod 2^32, mix32 as in the bootstrap section above:
+ *     h(t, s)    = mix32( mix32(seed + 0x9e3779b9 * t) ^ mix32(s + 0x85ebca6b) )
+ *     r(t, s, c) = mix32( h(t, s) + 0x9e3779b9 * (c + 1) )
+ *     pick(r, n) = (uint64(r) * n) >> 32
+ * Step t, slot s < batch: the positive pair is p = pick(r(t, s, 0), nnz), u = pair_user[p], i = idx[p]; the negative is
+ * the first j = pick(r(t, s, c), n_items), c = 1 .. tries, that is not in u's row (binary search).  If all `tries`
+ * candidates are liked the slot is DROPPED: it contributes nothing.  1 <= tries <= ANIREC_BPR_MAX_TRIES.
+ *
+ * Gradient of step t, every slot against the tables as they stand BEFORE the step; fp32, nothing contracted:
+ *     d[k] = y_i[k] - y_j[k]
+ *     x^   = sum_k x_u[k] d[k]: lane l = 0 .. width/4-1 holds elements 4l .. 4l+3 and takes
+ *            ((x0 d0 + x1 d1) + x2 d2) + x3 d3; then the xor butterfly v[l] += v[l ^ o] over the lanes at distances
+ *            o = width/8, width/16, .., 1 (anirec_als_half_sweep's u . v)
+ *     g    = 1 / (1 + e(x^)), with e(x) operation by operation:
+ *            xc = fmin(fmax(x, -30), 30)   (a NaN becomes -30);   kf = rint(xc * L2E)   (to nearest, ties to even)
+ *            r = (xc - kf * C1) - kf * C2;   p = ((((((P6 r + P5) r + P4) r + P3) r + P2) r + 1) r + 1   (Horner)
+ *            e = ldexp(p, kf);   g = 1 / (1 + e)   (one IEEE divide)
+ *            L2E = 0x3FB8AA3B, C1 = 0x3F317200, C2 = 0x35BFBE8E (ln 2 = C1 + C2), P6 .. P2 = fp32(1/720), fp32(1/120),
+ *            fp32(1/24), fp32(1/6), 0.5.  No expf: a NumPy restatement gives g bit for bit.  |g - logistic(-x^)| < 1e-6.
+ *     terms: row u gets llrint((double)(float)(g * d[k]) * 2^30) in column k; row i gets
+ *            llrint((double)(float)(g * x_u[k]) * 2^30), row j its negative.  A product that is not finite or above 2^20
+ *            in magnitude contributes 0 and sets ANIREC_BPR_ERR_DIVERGED in *err_flag.
+ * The terms are summed as int64 (mod 2^64) per (row, column), and every row counts the slots that touch it (c).
+ * Update, every row with c > 0, plain fp32 operations in this order:
+ *     grad = (float)((double)sum * 2^-30);    x <- x + lr * (grad - (reg * (float)c) * x)
+ * With bias = 1 column width-1 of the USER rows is never written: the caller sets it to 1 (and the items' column to 0 at
+ * the start), which makes the items' column width-1 an item bias while the scores stay anirec_dot_scores'.
+ * out_counts [n_steps][3] int64: per step the slots kept, the slots dropped and the kept slots with x^ > 0.
+ *
+ * anirec_bpr_steps runs the steps step0 .. step0 + n_steps - 1 in place; all launches are enqueued at once, nothing is
+ * read back: graph-capturable.  A step is two launches: the gradient phase reads the tables and writes accumulators
+ * only; the apply phase writes the tables, each touched row once, and scans no table.
+ * workspace: anirec_bpr_workspace_bytes(n_users, n_items, width, batch) bytes (0 for a bad argument; needs no GPU), less
+ * is ANIREC_EWORKSPACE; the call zeroes what it uses, so the result does not depend on what the workspace held.
+ * *err_flag (device; overwritten by the call): ANIREC_BPR_ERR_INDEX on a pair_user or idx entry out of range at a drawn
+ * pair, or an offsets pair of the drawn user that is negative, decreasing or past nnz: nothing is read through the bad
+ * value and the slot counts as dropped; ANIREC_BPR_ERR_DIVERGED as above.
+ * A bad width, n_users or n_items < 1, nnz outside 1 .. 2^31-1, batch < 1, tries outside 1 .. ANIREC_BPR_MAX_TRIES,
+ * step0 < 0, n_steps < 0, step0 + n_steps > INT32_MAX, lr or reg negative or not finite, bias not 0 or 1, a NULL pointer
+ * (out_counts may be NULL with n_steps == 0), tables not 16-byte or workspace / out_counts not 8-byte aligned:
+ * ANIREC_EINVAL before anything is enqueued.  n_steps == 0: ANIREC_OK, the tables untouched.
+ *
+ * anirec_bpr_sample: out_triples int32 [n_steps][batch][3] = (u, i, j) of the steps step0 .. step0 + n_steps - 1 as
+ * anirec_bpr_steps draws them; j = -1 for a dropped slot, (-1, -1, -1) and ANIREC_BPR_ERR_INDEX for an index out of
+ * range.  The same argument rules.
+ * ------------------------------------------------------------------------- */
+#define ANIREC_BPR_MAX_TRIES 16     /* the most negative candidates of a slot */
+#define ANIREC_BPR_ERR_INDEX 1      /* *err_flag bit: an index out of range */
+#define ANIREC_BPR_ERR_DIVERGED 2   /* *err_flag bit: a gradient term not finite or above 2^20 */
+size_t anirec_bpr_workspace_bytes(int32_t n_users, int32_t n_items, int32_t width, int32_t batch);
+int anirec_bpr_sample(const int64_t *offsets, const int32_t *idx, const int32_t *pair_user, int32_t n_users,
+                      int32_t n_items, int64_t nnz, int32_t batch, int32_t tries, uint32_t seed, int32_t step0,
+                      int32_t n_steps, int32_t *out_triples, int32_t *err_flag, void *stream);
+int anirec_bpr_steps(float *X, float *Y, int32_t n_users, int32_t n_items, int32_t width, const int64_t *offsets,
+                     const int32_t *idx, const int32_t *pair_user, int64_t nnz, int32_t batch, int32_t tries,
+                     uint32_t seed, int32_t step0, int32_t n_steps, float lr, float reg, int32_t bias,
+                     int64_t *out_counts, int32_t *err_flag, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------- *
  *  EASE (Steck 2019, "Embarrassingly Shallow Autoencoders for Sparse Data"): the linear item-item autoencoder a
  *  ranking table reads item-kNN and ALS against.  With B the n_items x n_users 0/1 matrix of liked
  *  pairs: G = B B^T (anirec_cooc_scores' out_count rows), A = G + reg I, P = A^-1, W[i][j] = -P[i][j] / P[j][j] off the
